@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- scheduled TTIs/s of the RadioSaber downlink RBG allocation path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no launcher around it starts its own N ranks: the parent process touches
@@ -22,6 +22,11 @@ both sides, max over ranks.  Cells are independent, so ranks share nothing durin
 rand() seeds and CQI grids are functions of the GLOBAL cell id); the only collective is the final
 all-reduce (RCCL) of the per-slice cumulative byte counters uint64[S].
 
+A plain run sets up, warms up, times the K steps, writes its outputs when --dump-outputs DIR is given and prints the line.
+--dump-outputs DIR writes what the caller of the timed path holds after its last step: every cell's PF averages, cumulative bytes,
+cumulative RBs and slice state, and the per-slice byte vector after the final reduction, as DIR/<name>.npy (float64; on N > 1 GPUs
+rank 0's cells).  The inputs are functions of the arguments alone, so two builds can be compared output for output.
+
 The JSON line also carries
   roofline        SURVEY.md 8d as the contract defines it: algorithmic bytes (B_TTI = U*R + 16U + 4U + 4R + 16S per
                   cell-TTI, "streamed-CQI" accounting) of one launch / that launch's HIP-event duration, against the
@@ -31,6 +36,8 @@ The JSON line also carries
                   `traffic_source`) say what actually moves;
   roofline_issue  what really bounds the kernel: wave-instructions per cell-TTI (SQ_INSTS_* from profiles/inst_counts.json,
                   tools/pmc_insts.sh) x this run's TTIs/s against the chip's VALU issue rate;
+and, with --full only (each of these takes runs of its own):
+  roofline.measured_copy_gbs  the attainable HBM rate of this GPU (a streaming copy probe) beside the spec peak;
   roofline.streamed   the same batch with `cqi_refresh = 1` -- a new CQI grid from HBM every TTI, SURVEY 8d's "streamed-CQI" mode:
                   the one figure of the line where moved bytes ~ algorithmic bytes, i.e. real bytes / real time (N = 1 only;
                   a bounded set of epochs cycles, larger than the 256 MiB Infinity Cache; `--cqi-refresh R` runs the MAIN batch
@@ -311,6 +318,11 @@ def main():
                          "fixture, on the as-shipped 64-RBG grid unless --rbgs says otherwise; every flow backlogged")
     ap.add_argument("--allow-variant", action="store_true",
                     help="run although RS_JIT_EXTRA / RS_JIT is set in the environment (tuning experiments; the line says so)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the HBM copy probe, roofline.streamed, value_r64, "
+                         "value_cells1024, cpu_baseline and parity_sample (the --no-* switches above leave single ones out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the timed path computed, after its last step, as DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     # A headline must come from the product kernel: build switches in the environment are refused unless asked for, and the
@@ -456,7 +468,14 @@ def main():
     batch_epochs, batch_wrap = batch.n_epochs_resident, batch.epochs_wrap
     jit_code, jit_msg = batch.jit_status()  # (before close: a closed batch has no status to read)
     clk_mhz, cell_ms = batch.debug_clocks()  # the last timed launch, from the kernel's own s_memtime / s_memrealtime readings
+    outputs = batch.state() if args.dump_outputs else None  # what a caller of the timed path holds after its last step
     batch.close()
+    if outputs is not None and rank == 0:
+        out_dir = Path(args.dump_outputs)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        outputs["slice_bytes"] = slice_bytes.cpu().numpy()
+        for name, a in outputs.items():  # float64 holds the int64 counters exactly (all far below 2**53)
+            np.save(out_dir / f"{name}.npy", np.ascontiguousarray(a, np.float64))
 
     parity_failed = False
     if rank == 0:
@@ -487,11 +506,12 @@ def main():
             traffic = ent["hbm_bytes_per_cell_tti"] * args.cells * args.ttis
             traffic_src = (f"profiles/traffic.json[{key}]@{ent.get('commit', '?')} source_hash {ent.get('source_hash', 'none')} "
                            "(PMC passes of an earlier run, not this one)")
-        try:  # attainable HBM rate of this GPU (16 B/lane streaming copy, 1 GiB each way), beside the spec peak
-            copy_gbs = rs.hbm_copy_probe(local_rank, 1 << 30, 10)
-        except Exception as e:  # measurement nicety only
-            print(f"hbm_copy_probe failed: {e}", file=sys.stderr)
-            copy_gbs = None
+        copy_gbs = None
+        if args.full:
+            try:  # attainable HBM rate of this GPU (16 B/lane streaming copy, 1 GiB each way), beside the spec peak
+                copy_gbs = rs.hbm_copy_probe(local_rank, 1 << 30, 10)
+            except Exception as e:  # measurement nicety only
+                print(f"hbm_copy_probe failed: {e}", file=sys.stderr)
         line = {
             "metric": "scheduled TTIs/sec (and us/TTI) at 20 slices x 500 UEs x 25 RBGs; HBM GB/s",
             "value": value, "unit": "TTIs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -552,7 +572,7 @@ def main():
                 "source": f"profiles/inst_counts.json[{key}]@{ent.get('commit', '?')} source_hash {ent.get('source_hash', 'none')} "
                           "(SQ_INSTS_* per cell-TTI from tools/pmc_insts.sh, phase shares from tools/phase_stamps.py; counts "
                           "are per build, the rate is this run's)"}
-        if world == 1 and not args.no_streamed and args.cqi_refresh != 1:
+        if args.full and world == 1 and not args.no_streamed and args.cqi_refresh != 1:
             # SURVEY 8(d) asks for both modes: the same cells with a new CQI grid from HBM EVERY TTI (cqi_refresh = 1), where the
             # bytes the kernel moves are ~ the algorithmic bytes: the one roofline figure of this line that is real bytes / real time
             st_ttis = min(args.ttis, 2000)
@@ -577,7 +597,7 @@ def main():
                 "ttis_per_launch": st_ttis, "launches": 3,
                 "note": "cqi_refresh = 1: every TTI loads its grid from HBM (epochs cycle through a set larger than the Infinity "
                         "Cache); achieved_gbs = algorithmic bytes x this rate, traffic_* = PMC bytes of the same mode"}
-        if world == 1 and not args.no_r64 and (R, args.rbg_size) != (64, 8):
+        if args.full and world == 1 and not args.no_r64 and (R, args.rbg_size) != (64, 8):
             # the as-shipped grid: 100 MHz = 512 PRBs = 64 RBGs of 8 (SURVEY 8d asks for it beside the headline)
             b64 = make_batch(64, 8, 4, args.ttis)
             b64.run(args.ttis)
@@ -595,7 +615,7 @@ def main():
                                     "traffic_bytes_per_cell_tti": ent["hbm_bytes_per_cell_tti"] if ent else None,
                                     "traffic_stale": stale,
                                     "traffic_source": f"profiles/traffic.json[{key}]@{ent.get('commit', '?')}" if ent else None}
-        if world == 1 and not args.no_cells1024 and args.cells != 1024:
+        if args.full and world == 1 and not args.no_cells1024 and args.cells != 1024:
             # The headline's 512 cells are two workgroups of 8 waves on every CU -- 16 of its 32 wave slots (BASELINE configs[3] fixes the
             # 512); LDS would hold four.  The same workload with 1 024 cells shows what the idle slots are worth, so that
             # roofline_issue.valu_issue_frac is not read as "the kernel leaves two thirds of the chip idle".
@@ -614,7 +634,7 @@ def main():
                              "lds_bytes_per_cell": lds, "cells_per_cu_lds_allows": (160 * 1024) // lds,
                              "note": "BASELINE configs[3] fixes 512 cells: half of the CU's wave slots hold a wave; value_cells1024 is the same "
                                      "workload with the slots the LDS carve allows filled (the library picks 256 threads per cell there)"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args, slices, seeds)
             try:
                 line["parity_sample"] = parity_sample(rs, args, slices, sharding, local_rank)

@@ -468,7 +468,7 @@ def _bench(args, env_extra=None, timeout=900):
 
 def test_bench_line_carries_a_parity_sample_and_fails_when_it_is_wrong():
     common = ["--steps", "1", "--warmup", "0", "--cells", "64", "--ttis", "400", "--no-r64", "--no-streamed", "--no-cells1024",
-              "--cpu-baseline-seconds", "0.5"]
+              "--cpu-baseline-seconds", "0.5", "--full"]
     r = _bench(common)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])

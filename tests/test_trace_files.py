@@ -4,9 +4,11 @@ The parser lives in the C ABI (rs_trace_*; host code, no GPU needed).  Checked a
   * small files written here in the reference's format (ue<id>.log: one line per report, space-separated
     CQI per PRB; mapping<i>.config: "<user> <trace>" lines), incl. the extraction loop's corner cases
     (short lines repeat the last value, ref: enb-mac-entity.cc:175-186);
-  * when the reference tree is present (build container only): the shipped corpus against the committed
-    fixture tests/golden/cqi_traces_rbg64.npz (which tools/make_trace_fixture.py made with numpy).
+  * the shipped corpus (the first 40 lines of every ue<k>.log and the four mapping files of cqi-traces-noise0, kept as
+    data in tests/golden/cqi_traces_noise0_head40.tar.xz) against the committed fixture tests/golden/cqi_traces_rbg64.npz
+    (which tools/make_trace_fixture.py made with numpy).
 """
+import tarfile
 from pathlib import Path
 
 import numpy as np
@@ -14,8 +16,8 @@ import pytest
 
 import radiosaber_amd as rs
 
-REF = Path("/root/reference/cqi-traces-noise0")
 GOLD = Path(__file__).parent / "golden" / "cqi_traces_rbg64.npz"
+CORPUS = Path(__file__).parent / "golden" / "cqi_traces_noise0_head40.tar.xz"
 
 
 def write_log(path, rows):
@@ -88,8 +90,10 @@ def test_mapping_and_directory(tmp_path):
     assert (m[users % len(m)] == [2, 0, 1, 2, 2, 0, 1, 2, 2, 0]).all()
 
 
-@pytest.mark.skipif(not REF.exists() or not GOLD.exists(), reason="reference corpus only exists in the build container")
-def test_shipped_corpus_matches_the_committed_fixture():
+def test_shipped_corpus_matches_the_committed_fixture(tmp_path):
+    with tarfile.open(CORPUS) as tf:
+        tf.extractall(tmp_path, **({"filter": "data"} if hasattr(tarfile, "data_filter") else {}))
+    REF = tmp_path
     g = np.load(GOLD)  # cqi [158 traces][first 40 rows][64 RBGs], mapping [4 files][474 entries]
     for t in (0, 76, 157):
         got, mixed = rs.read_ue_trace(REF / f"ue{t}.log")
