@@ -25,7 +25,9 @@
 extern "C" {
 #endif
 
-#define RS_ABI_VERSION 11 /* 11: rs_config.link_tables (RS_LINK_*) + rs_link_tables_pinned / rs_link_tables_compare, rs_tti_in.cqi_epoch (the context keeps the
+#define RS_ABI_VERSION 11 /* 11: (additions, no layout changed) rs_batch_flow_record (flow completion times of the queue model),
+                               rs_batch_bearer_log + rs_batch_run_logged_bearers (per-bearer DoStopSchedule rows);
+                               rs_config.link_tables (RS_LINK_*) + rs_link_tables_pinned / rs_link_tables_compare, rs_tti_in.cqi_epoch (the context keeps the
                                CQI image of an unchanged report set on the device), rs_ctx_jit_status (a specialised context checks its run-time build against the
                                built-in kernel during its first calls), rs_batch_config.selfcheck -1 / 0 / 1 with run-time builds verified by default and the
                                self-check mark in the cache file, rs_jit_compiler_identity (the compiler's full identity in the cache key);
@@ -413,6 +415,14 @@ int rs_batch_read_bearer_state(rs_batch* b, double* avg_rate, int64_t* cum_bytes
  * bursts written (<= max_bursts) or a negative RS_ERR_*. */
 int rs_internet_flow_arrivals(double rate_mbps, double start_time, double stop_time, uint32_t size_seed, int32_t max_bursts,
                               double* time, int32_t* n_full, int32_t* last_bytes);
+/* The flow completion record (ABI 11 addition): one entry per arrival burst, in the order of rs_batch_set_arrivals' arrays (a burst is
+ * one InternetFlow flow, InternetFlow::Send).  done_tti = the scheduled TTI, counted from the batch's first, whose DoStopSchedule sent
+ * the burst's last packet (whole or as its last fragment: um-rlc-entity.cpp:143-160, "ipflow end"); done_time = that TTI's clock value
+ * (the flow's completion time is done_time - time[i]); -1 in both while the flow is not complete.  rs_batch_set_arrivals resets it;
+ * every launch of the queue model writes it (one store per completed flow).  It is output, not state: a checkpoint does not carry it
+ * (rs_batch_checkpoint_bytes is unchanged), so a resumed batch records the flows that complete after the resume.  The self-check's
+ * trial launches leave it as it was.  Either pointer may be NULL; RS_ERR_STATE without the queue model's arrivals. */
+int rs_batch_flow_record(rs_batch* b, int32_t* done_tti, double* done_time);
 
 /* run n_ttis scheduled TTIs of every cell in ONE kernel launch on the batch's stream and wait */
 int rs_batch_run(rs_batch* b, int32_t n_ttis);
@@ -438,6 +448,17 @@ typedef struct rs_batch_log {
                             flow_spectraleff / user_index of ref :545-567 */
 } rs_batch_log;
 int rs_batch_run_logged_ex(rs_batch* b, int32_t n_ttis, const rs_batch_log* log);
+/* The same with the queue model's per-bearer rows (ABI 11 addition; RS_ERR_STATE without rs_batch_set_bearers).  Both arrays are
+ * [n_cells][n_ttis][U][2] (index = bearer priority), row = the TTI whose DoStopSchedule credited the bytes
+ * (downlink-transport-scheduler.cpp:179-199, dl-pf-packet-scheduler.cpp:77-96): bytes = what UpdateTransmittedBytes added (0: the
+ * bearer sent nothing, no log line), hol_delay = RadioBearer::GetHeadOfLinePacketDelay at that moment, before the RLC dequeue: 0 for
+ * an empty MAC queue or an InfiniteBuffer bearer, else the TTI's clock - the head packet's time stamp, at least 1e-5 (the value the
+ * customised slice's metric used in that TTI).  Either pointer may be NULL; `bearers` may be NULL (= rs_batch_run_logged_ex). */
+typedef struct rs_batch_bearer_log {
+  int32_t* bytes;        /* [n_cells][n_ttis][U][2] */
+  double* hol_delay;     /* [n_cells][n_ttis][U][2] */
+} rs_batch_bearer_log;
+int rs_batch_run_logged_bearers(rs_batch* b, int32_t n_ttis, const rs_batch_log* log, const rs_batch_bearer_log* bearers);
 /* `launches` back-to-back launches of n_ttis each, timed with HIP events on the batch's stream;
  * ms_per_launch[launches] receives each launch's duration */
 int rs_batch_run_timed(rs_batch* b, int32_t n_ttis, int32_t launches, float* ms_per_launch);

@@ -80,6 +80,10 @@ class _BatchLog(C.Structure):
                 ("slice_keys", C.POINTER(C.c_uint32))]
 
 
+class _BatchBearerLog(C.Structure):
+    _fields_ = [("bytes", C.POINTER(C.c_int32)), ("hol_delay", C.POINTER(C.c_double))]
+
+
 # every symbol include/radiosaber_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "rs_last_error", "rs_abi_version", "rs_device_count", "rs_link_tables",
@@ -101,6 +105,7 @@ ABI_SYMBOLS = [
     "rs_jit_cache_stats", "rs_jit_cache_file", "rs_jit_cache_warm", "rs_batch_autotune_report", "rs_batch_debug_clocks",
     "rs_batch_checkpoint_bytes", "rs_batch_checkpoint_save", "rs_batch_checkpoint_load",
     "rs_link_tables_pinned", "rs_link_tables_compare", "rs_ctx_jit_status", "rs_jit_compiler_identity",
+    "rs_batch_flow_record", "rs_batch_run_logged_bearers",
 ]
 
 _lib = None
@@ -143,6 +148,8 @@ def lib():
     L.rs_batch_synthesize_cqi.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_double), C.c_int32]
     L.rs_batch_synthesize_cqi_at.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_double), C.c_int32, C.c_int64]
     L.rs_batch_run_logged_ex.argtypes = [C.c_void_p, C.c_int32, C.POINTER(_BatchLog)]
+    L.rs_batch_run_logged_bearers.argtypes = [C.c_void_p, C.c_int32, C.POINTER(_BatchLog), C.POINTER(_BatchBearerLog)]
+    L.rs_batch_flow_record.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]
     L.rs_batch_read_clock.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.rs_batch_jit_status.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.rs_batch_prepare_launch.argtypes = [C.c_void_p, C.c_int32]
@@ -645,9 +652,11 @@ class BatchScheduler:
     def sync(self):
         _check(lib().rs_batch_sync(self._h))
 
-    def run_logged(self, n_ttis, slice_keys=False):
+    def run_logged(self, n_ttis, slice_keys=False, bearers=False):
         """slice_keys=True (transport schedulers) adds what the inter-slice step read: 'slice_cqi' [cells][ttis][R][S]
-        (CQI of the slice's best user, 0 = no user) and 'slice_user' (its id, -1 = none)."""
+        (CQI of the slice's best user, 0 = no user) and 'slice_user' (its id, -1 = none).  bearers=True (queue model) adds the
+        DoStopSchedule rows of every bearer: 'bearer_bytes' int32 [cells][ttis][U][2] (bytes credited, 0 = no log line) and
+        'bearer_hol' float64 [cells][ttis][U][2] (GetHeadOfLinePacketDelay before the RLC dequeue)."""
         m = np.zeros((self.n_cells, n_ttis, self.R), np.int16)
         tb = np.zeros((self.n_cells, n_ttis, self.U), np.int32)
         q = np.zeros((self.n_cells, n_ttis, self.S), np.int16)
@@ -656,12 +665,20 @@ class BatchScheduler:
         keys = np.zeros((self.n_cells, n_ttis, self.R, self.S), np.uint32) if slice_keys else None
         lg = _BatchLog(_p(m, C.c_int16), _p(tb, C.c_int32), _p(q, C.c_int16), _p(tg, C.c_int16), _p(ui, C.c_int32),
                        _p(keys, C.c_uint32) if slice_keys else None)
-        _check(lib().rs_batch_run_logged_ex(self._h, n_ttis, C.byref(lg)))
+        if bearers:
+            bb = np.zeros((self.n_cells, n_ttis, self.U, 2), np.int32)
+            bh = np.zeros((self.n_cells, n_ttis, self.U, 2), np.float64)
+            blg = _BatchBearerLog(_p(bb, C.c_int32), _p(bh, C.c_double))
+            _check(lib().rs_batch_run_logged_bearers(self._h, n_ttis, C.byref(lg), C.byref(blg)))
+        else:
+            _check(lib().rs_batch_run_logged_ex(self._h, n_ttis, C.byref(lg)))
         out = {"rbg_to_user": m, "tbs_bits": tb, "quota": q, "target": tg, "nprb": ui & 0xFFFF,
                "final_cqi": (ui >> 16) & 0xFF, "mcs": (ui >> 24) & 0xFF}
         if slice_keys:
             out["slice_cqi"] = (keys & 0xFF).astype(np.int32)
             out["slice_user"] = (keys >> 8).astype(np.int32) - 1
+        if bearers:
+            out["bearer_bytes"], out["bearer_hol"] = bb, bh
         return out
 
     def run_timed(self, n_ttis, launches):
@@ -712,6 +729,20 @@ class BatchScheduler:
             t_all[i:i + len(t)], nf_all[i:i + len(t)], la_all[i:i + len(t)] = t, nf, la
         _check(lib().rs_batch_set_arrivals(self._h, _p(off, C.c_int64), _p(t_all, C.c_double), _p(nf_all, C.c_int32),
                                            _p(la_all, C.c_int32)))
+        self._burst_slots = {key: (int(off[(key[0] * self.U + key[1]) * 2 + key[2]]), len(v[0])) for key, v in bursts.items()}
+        self._n_bursts = total
+
+    def flow_record(self):
+        """The flow completion record (rs_batch_flow_record), keyed like the `bursts` of set_arrivals:
+        {(cell, user, prio): (done_tti int32[n], done_time f64[n])}, per burst the TTI (counted from the batch's first scheduled
+        TTI) whose DoStopSchedule sent the burst's last packet and that TTI's clock value; -1 while the flow is not complete.
+        The flow completion time is done_time - time."""
+        if not hasattr(self, "_burst_slots"):
+            raise RadioSaberError(-4, "flow_record() before set_arrivals()")
+        tti = np.zeros(max(self._n_bursts, 1), np.int32)
+        tm = np.zeros(max(self._n_bursts, 1), np.float64)
+        _check(lib().rs_batch_flow_record(self._h, _p(tti, C.c_int32), _p(tm, C.c_double)))
+        return {key: (tti[i:i + n].copy(), tm[i:i + n].copy()) for key, (i, n) in self._burst_slots.items()}
 
     def bearer_state(self):
         shp = (self.n_cells, self.U, 2)

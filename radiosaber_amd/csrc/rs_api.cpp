@@ -309,6 +309,10 @@ struct rs_batch {
   int64_t* d_bcum = nullptr; /* 2 arrays [cells][2][U]: bytes, rbs */
   uint8_t* d_qflags = nullptr;
   double* d_qhol = nullptr;
+  /* the flow completion record, one entry per arrival burst (rs_batch_flow_record): output, not state -- not in a checkpoint */
+  int32_t* d_flow_tti = nullptr;
+  double* d_flow_time = nullptr;
+  size_t n_bursts = 0;
   RsJitKernel* jit = nullptr; /* shape-specialised kernel (owned by the process-wide cache) */
   RsJitKernel* jit_lean = nullptr; /* its lean build, compiled at the first launch that can use it (launch()) */
   bool jit_lean_tried = false;
@@ -676,7 +680,7 @@ RsJitKernel* lean_kernel(rs_batch* b, int n_ttis, bool logged) {
 }
 
 int launch(rs_batch* b, int n_ttis, int16_t* d_map, int16_t* d_quota, int16_t* d_target, int32_t* d_tbs, int32_t* d_uinfo,
-           uint32_t* d_keys = nullptr);
+           uint32_t* d_keys = nullptr, int32_t* d_bbytes = nullptr, double* d_bhol = nullptr);
 
 /* Everything a batch carries from one launch to the next, as (device pointer, bytes): PF averages, pending grants, cumulative counters,
  * slice state, clock / rand() ring / CQI-report state, and with the queue model the bearers' queues, averages, counters and per-user
@@ -700,7 +704,12 @@ std::vector<StatePart> state_parts(rs_batch* b) {
 struct StateParts {
   std::vector<StatePart> parts;
   size_t total = 0;
-  explicit StateParts(rs_batch* b) : parts(state_parts(b)) {
+  /* with_record: the flow completion record too (the self-check's trials write it; it is output, so the checkpoint leaves it out) */
+  explicit StateParts(rs_batch* b, bool with_record = false) : parts(state_parts(b)) {
+    if (with_record && b->queues && b->d_flow_tti) {
+      parts.push_back({b->d_flow_tti, 4 * b->n_bursts});
+      parts.push_back({b->d_flow_time, 8 * b->n_bursts});
+    }
     for (const StatePart& q : parts) total += (q.n + 255) & ~(size_t)255;
   }
   hipError_t copy(rs_batch* b, void* snapshot, bool save) const {
@@ -719,15 +728,15 @@ struct StateParts {
  * state, the bytes of the pending grants (the shape-specialised kernels pack more into that word), clock, rand() ring and CQI-report
  * state.  FNV-1a over the host copy (a few MB, once per trial). */
 struct StateDigest {
-  unsigned long long part[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; /* PF averages, cumulative bytes, cumulative RBs, slice state, pending grants' bytes, scalars; queue model: the bearers' queues, averages, counters */
+  unsigned long long part[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; /* PF averages, cumulative bytes, cumulative RBs, slice state, pending grants' bytes, scalars; queue model: the bearers' queues, averages, counters, the flow completion record */
   bool operator==(const StateDigest& o) const { return memcmp(part, o.part, sizeof part) == 0; }
   bool operator!=(const StateDigest& o) const { return !(*this == o); }
   std::string diff(const StateDigest& o) const {
-    static const char* const names[13] = {"PF averages", "cumulative bytes", "cumulative RBs", "slice state", "pending grants", "simulated time",
+    static const char* const names[14] = {"PF averages", "cumulative bytes", "cumulative RBs", "slice state", "pending grants", "simulated time",
                                           "last EWMA update", "TTIs done", "users served in the last TTI", "rand() ring / CQI-report state",
-                                          "bearers' queues", "bearers' PF averages", "bearers' cumulative counters"};
+                                          "bearers' queues", "bearers' PF averages", "bearers' cumulative counters", "flow completion record"};
     std::string d;
-    for (int i = 0; i < 13; i++)
+    for (int i = 0; i < 14; i++)
       if (part[i] != o.part[i]) d += std::string(d.empty() ? "" : ", ") + names[i];
     return d;
   }
@@ -776,6 +785,12 @@ int state_digest(rs_batch* b, StateDigest* out) {
       std::vector<unsigned char> hq(q[i].n);
       HIP_TRY(hipMemcpy(hq.data(), q[i].p, q[i].n, hipMemcpyDeviceToHost));
       out->part[10 + i] = fnv(hq.data(), q[i].n);
+    }
+    if (b->d_flow_tti) { /* the record: TTI indices and clock values of the completed flows */
+      std::vector<unsigned char> hr(12 * b->n_bursts);
+      HIP_TRY(hipMemcpy(hr.data(), b->d_flow_tti, 4 * b->n_bursts, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(hr.data() + 4 * b->n_bursts, b->d_flow_time, 8 * b->n_bursts, hipMemcpyDeviceToHost));
+      out->part[13] = fnv(hr.data(), hr.size());
     }
   }
   return RS_OK;
@@ -925,7 +940,7 @@ int selfcheck(rs_batch* b, int n_ttis, bool logged) {
   }
   b->in_selfcheck = true;
   struct Leave { rs_batch* b; ~Leave() { b->in_selfcheck = false; } } leave{b};
-  const StateParts sp(b);
+  const StateParts sp(b, true); /* (the trials write the flow completion record: it is put back with the state and compared) */
   ScratchBuffers scratch;
   void* snap = nullptr;
   HIP_TRY(scratch.alloc(&snap, sp.total));
@@ -1007,7 +1022,7 @@ int selfcheck(rs_batch* b, int n_ttis, bool logged) {
 }
 
 int launch(rs_batch* b, int n_ttis, int16_t* d_map, int16_t* d_quota, int16_t* d_target, int32_t* d_tbs, int32_t* d_uinfo,
-           uint32_t* d_keys) {
+           uint32_t* d_keys, int32_t* d_bbytes, double* d_bhol) {
   if (n_ttis < 1) return fail(RS_ERR_INVALID, "n_ttis %d < 1", n_ttis);
   if (b->cqi_mode == RS_CQI_NONE) return fail(RS_ERR_STATE, "no CQI source set");
   if (b->any_alpha && !b->direct && !b->queues)
@@ -1015,7 +1030,7 @@ int launch(rs_batch* b, int n_ttis, int16_t* d_map, int16_t* d_quota, int16_t* d
   if (b->queues && !b->d_arr_off) return fail(RS_ERR_STATE, "rs_batch_set_arrivals has not been called");
   if (n_ttis > RS_MAX_TTIS_PER_LAUNCH) {
     /* longer runs go out as several launches (state carries over; the per-launch counters of the kernel are 32-bit) */
-    if (d_map || d_tbs || d_uinfo || d_keys) return fail(RS_ERR_INVALID, "logged runs are limited to %d TTIs per call", RS_MAX_TTIS_PER_LAUNCH);
+    if (d_map || d_tbs || d_uinfo || d_keys || d_bbytes) return fail(RS_ERR_INVALID, "logged runs are limited to %d TTIs per call", RS_MAX_TTIS_PER_LAUNCH);
     for (int done = 0; done < n_ttis;) {
       const int chunk = n_ttis - done < RS_MAX_TTIS_PER_LAUNCH ? n_ttis - done : RS_MAX_TTIS_PER_LAUNCH;
       const int rc = launch(b, chunk, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
@@ -1043,8 +1058,10 @@ int launch(rs_batch* b, int n_ttis, int16_t* d_map, int16_t* d_quota, int16_t* d
     L.q_bytes = b->d_qi + 4 * n; L.q_pkts = b->d_qi + 5 * n; L.b_tx = b->d_qi + 6 * n;
     L.b_avg = b->d_bavg; L.b_cumb = b->d_bcum; L.b_cumr = b->d_bcum + n;
     L.q_flags = b->d_qflags; L.q_hol = b->d_qhol;
+    L.flow_tti = b->d_flow_tti; L.flow_time = b->d_flow_time;
+    L.log_bbytes = d_bbytes; L.log_bhol = d_bhol;
   }
-  const bool logged = d_map || d_quota || d_target || d_tbs || d_uinfo || d_keys;
+  const bool logged = d_map || d_quota || d_target || d_tbs || d_uinfo || d_keys || d_bbytes;
   if (!b->selfchecked && !b->in_selfcheck && b->jit && !b->direct) {
     const int rc = selfcheck(b, n_ttis, logged); /* (its trials come back through here with `in_selfcheck` set) */
     if (rc) return rc;
@@ -1085,7 +1102,7 @@ void rs_batch_destroy(rs_batch* b) {
   void* ptrs[] = {b->d_tab, b->d_weight, b->d_eps, b->d_psi, b->d_alpha, b->d_beta, b->d_user_slice, b->d_tbs_eff, b->d_avg, b->d_tx, b->d_cumb, b->d_cumr,
                   b->d_sstate, b->d_scal, b->d_epochs, b->d_trace, b->d_user_trace, b->d_err, b->d_slice_bytes, b->d_stamps,
                   b->d_bearer_kind, b->d_arr_off, b->d_arr_time, b->d_arr_nfull, b->d_arr_last, b->d_qi, b->d_bavg, b->d_bcum,
-                  b->d_qflags, b->d_qhol, b->d_epochs_prb, b->d_trace_prb, b->d_gen_num, b->d_prio_sum};
+                  b->d_qflags, b->d_qhol, b->d_flow_tti, b->d_flow_time, b->d_epochs_prb, b->d_trace_prb, b->d_gen_num, b->d_prio_sum};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (b->own_stream && b->stream) (void)hipStreamDestroy(b->stream);
@@ -1262,8 +1279,12 @@ int rs_batch_run_logged(rs_batch* b, int32_t n_ttis, int16_t* h_map, int32_t* h_
   return rs_batch_run_logged_ex(b, n_ttis, &lg);
 }
 
-int rs_batch_run_logged_ex(rs_batch* b, int32_t n_ttis, const rs_batch_log* lg) {
+int rs_batch_run_logged_ex(rs_batch* b, int32_t n_ttis, const rs_batch_log* lg) { return rs_batch_run_logged_bearers(b, n_ttis, lg, nullptr); }
+
+int rs_batch_run_logged_bearers(rs_batch* b, int32_t n_ttis, const rs_batch_log* lg, const rs_batch_bearer_log* blg) {
   if (!b || !lg) return fail(RS_ERR_INVALID, "null argument");
+  const bool bearers = blg && (blg->bytes || blg->hol_delay);
+  if (bearers && !b->queues) return fail(RS_ERR_STATE, "per-bearer log rows: the batch has no bearers (rs_batch_set_bearers)");
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   if (n_ttis < 1) return fail(RS_ERR_INVALID, "n_ttis %d < 1", n_ttis);
   const bool transport = b->sched == RS_SCHED_SEQUENTIAL || b->sched == RS_SCHED_MAXCELL || b->sched == RS_SCHED_UPPERBOUND ||
@@ -1282,7 +1303,15 @@ int rs_batch_run_logged_ex(rs_batch* b, int32_t n_ttis, const rs_batch_log* lg) 
   if (lg->slice_keys) HIP_TRY(scratch.alloc(&d_keys, 4 * rows * b->R * b->S));
   HIP_TRY(hipMemsetAsync(d_tbs, 0, 4 * rows * b->U, b->stream));
   HIP_TRY(hipMemsetAsync(d_uinfo, 0, 4 * rows * b->U, b->stream));
-  int rc = launch(b, n_ttis, d_map, d_quota, d_target, d_tbs, d_uinfo, d_keys);
+  int32_t* d_bbytes = nullptr;
+  double* d_bhol = nullptr;
+  if (bearers) {
+    HIP_TRY(scratch.alloc(&d_bbytes, 4 * rows * b->U * 2));
+    HIP_TRY(scratch.alloc(&d_bhol, 8 * rows * b->U * 2));
+    HIP_TRY(hipMemsetAsync(d_bbytes, 0, 4 * rows * b->U * 2, b->stream));
+    HIP_TRY(hipMemsetAsync(d_bhol, 0, 8 * rows * b->U * 2, b->stream));
+  }
+  int rc = launch(b, n_ttis, d_map, d_quota, d_target, d_tbs, d_uinfo, d_keys, d_bbytes, d_bhol);
   if (!rc) rc = rs_batch_sync(b);
   if (!rc) {
     if (lg->rbg_to_user) HIP_TRY(hipMemcpy(lg->rbg_to_user, d_map, 2 * rows * b->R, hipMemcpyDeviceToHost));
@@ -1291,6 +1320,8 @@ int rs_batch_run_logged_ex(rs_batch* b, int32_t n_ttis, const rs_batch_log* lg) 
     if (lg->tbs_bits) HIP_TRY(hipMemcpy(lg->tbs_bits, d_tbs, 4 * rows * b->U, hipMemcpyDeviceToHost));
     if (lg->uinfo) HIP_TRY(hipMemcpy(lg->uinfo, d_uinfo, 4 * rows * b->U, hipMemcpyDeviceToHost));
     if (lg->slice_keys) HIP_TRY(hipMemcpy(lg->slice_keys, d_keys, 4 * rows * b->R * b->S, hipMemcpyDeviceToHost));
+    if (bearers && blg->bytes) HIP_TRY(hipMemcpy(blg->bytes, d_bbytes, 4 * rows * b->U * 2, hipMemcpyDeviceToHost));
+    if (bearers && blg->hol_delay) HIP_TRY(hipMemcpy(blg->hol_delay, d_bhol, 8 * rows * b->U * 2, hipMemcpyDeviceToHost));
   }
   return rc;
 }
@@ -1426,10 +1457,11 @@ int rs_batch_set_arrivals(rs_batch* b, const int64_t* offsets, const double* tim
   }
   const size_t total = (size_t)offsets[nb];
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  void* old[] = {b->d_arr_off, b->d_arr_time, b->d_arr_nfull, b->d_arr_last};
+  void* old[] = {b->d_arr_off, b->d_arr_time, b->d_arr_nfull, b->d_arr_last, b->d_flow_tti, b->d_flow_time};
   for (void* q : old)
     if (q) HIP_TRY(hipFree(q));
   b->d_arr_off = nullptr; b->d_arr_time = nullptr; b->d_arr_nfull = nullptr; b->d_arr_last = nullptr;
+  b->d_flow_tti = nullptr; b->d_flow_time = nullptr; b->n_bursts = 0;
   HIP_TRY(hipMalloc(&b->d_arr_off, 8 * (nb + 1)));
   HIP_TRY(hipMalloc(&b->d_arr_time, 8 * (total ? total : 1)));
   HIP_TRY(hipMalloc(&b->d_arr_nfull, 4 * (total ? total : 1)));
@@ -1440,6 +1472,26 @@ int rs_batch_set_arrivals(rs_batch* b, const int64_t* offsets, const double* tim
     HIP_TRY(hipMemcpy(b->d_arr_nfull, n_full, 4 * total, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(b->d_arr_last, last_bytes, 4 * total, hipMemcpyHostToDevice));
   }
+  /* the flow completion record: -1 = not completed */
+  HIP_TRY(hipMalloc(&b->d_flow_tti, 4 * (total ? total : 1)));
+  HIP_TRY(hipMalloc(&b->d_flow_time, 8 * (total ? total : 1)));
+  b->n_bursts = total;
+  if (total) {
+    const std::vector<int32_t> none_tti(total, -1);
+    const std::vector<double> none_time(total, -1.0);
+    HIP_TRY(hipMemcpy(b->d_flow_tti, none_tti.data(), 4 * total, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->d_flow_time, none_time.data(), 8 * total, hipMemcpyHostToDevice));
+  }
+  return RS_OK;
+}
+
+int rs_batch_flow_record(rs_batch* b, int32_t* done_tti, double* done_time) {
+  if (!b) return fail(RS_ERR_INVALID, "null batch");
+  if (!b->queues || !b->d_flow_tti) return fail(RS_ERR_STATE, "no flow completion record: the batch has no arrivals (rs_batch_set_bearers / rs_batch_set_arrivals)");
+  HIP_TRY(hipSetDevice(b->cfg.cell.device));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  if (done_tti && b->n_bursts) HIP_TRY(hipMemcpy(done_tti, b->d_flow_tti, 4 * b->n_bursts, hipMemcpyDeviceToHost));
+  if (done_time && b->n_bursts) HIP_TRY(hipMemcpy(done_time, b->d_flow_time, 8 * b->n_bursts, hipMemcpyDeviceToHost));
   return RS_OK;
 }
 

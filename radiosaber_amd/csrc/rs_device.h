@@ -280,6 +280,10 @@ struct RsLaunch {
   int64_t *b_cumb, *b_cumr;   /* [cells][2][U] m_cumulativeBytes / m_cumulativeRBs */
   uint8_t* q_flags;           /* [cells][U] bit 0: prioritized bearer has data, bit 1: user has queued data */
   double* q_hol;              /* [cells][U] head-of-line delay of the slice-priority bearer */
+  /* flow completion record (NULL: off), one entry per arrival burst in the arr_* layout: the scheduled TTI (counted from the batch's first)
+   * whose DoStopSchedule sent the burst's last packet, and that TTI's clock value; -1 until then (rs_batch_set_arrivals) */
+  int32_t* flow_tti;
+  double* flow_time;
   int32_t exact_scan;        /* drop-in mode: an input lies outside the FP32 filter's safe range -> every user is compared exactly */
   int32_t synthetic;         /* rs_config.synthetic_exp: transport blocks PRB by PRB (schedulers 7, 8, 9, 10, 101, 103) */
   int32_t gen_exp;           /* drop-in mode: some slice has algo_epsilon / algo_psi outside {0, 1}: `avg` holds pow(avg_kbps, psi) as the
@@ -315,6 +319,8 @@ struct RsLaunch {
   int32_t* log_tbs;          /* [cells][n_ttis][U], pre-zeroed */
   int32_t* log_uinfo;        /* [cells][n_ttis][U], pre-zeroed: nprb | final_cqi<<16 | mcs<<24 */
   uint32_t* log_keys;        /* [cells][n_ttis][R][S] transport schedulers: CQI key of the slice's best user | (user+1)<<8 */
+  int32_t* log_bbytes;       /* queue model: [cells][n_ttis][U][2] bytes DoStopSchedule credited to the bearer, pre-zeroed (0: no line) */
+  double* log_bhol;          /* queue model: [cells][n_ttis][U][2] the bearer's head-of-line delay at that moment, pre-zeroed */
   int32_t* err;              /* device error word */
   unsigned long long* stamps; /* diagnostic build (-DRS_STAMPS): [cells][20] phase cycles, else unused */
   /* LDS carve (byte offsets from the dynamic LDS base) */

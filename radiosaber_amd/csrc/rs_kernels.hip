@@ -663,12 +663,13 @@ __device__ __forceinline__ void rs_cell_body(const RsLaunch& p, unsigned char* l
       epoch_pos = 0;
       if (++epoch == p.n_epochs && p.epoch_wrap) epoch = 0;
     }
+    if constexpr (QUEUE) q_stop_t = t; /* the clock of the TTI whose DoStopSchedule runs next */
     if (!kDirect) t += 0.001; /* ref: src/core/eventScheduler/simulator.cc:117-126 */
   }
 
   if constexpr (QUEUE) {
     /* DoStopSchedule of the launch's last TTI, so that the bearers' counters and queues the host reads are complete */
-    for (int u = tid; u < U; u += nt) stop_schedule_user(u);
+    for (int u = tid; u < U; u += nt) stop_schedule_user(u, p.n_ttis - 1);
     if constexpr (kQCumRegs) { /* the launch's cumulative counts of this thread's one user: plain adds, the owner is the only writer */
       if (tid < U) {
 #pragma unroll
@@ -786,6 +787,7 @@ extern "C" __global__ void __launch_bounds__(RS_JIT_NT, RS_JIT_WPE) rs_cell_kern
   p.cqi_mode = RS_CQI_EPOCHS;
   p.trace = nullptr; p.trace_prb = nullptr; p.epochs_prb = nullptr; p.user_trace = nullptr;
   p.log_map = nullptr; p.log_quota = nullptr; p.log_target = nullptr; p.log_tbs = nullptr; p.log_uinfo = nullptr; p.log_keys = nullptr;
+  p.log_bbytes = nullptr; p.log_bhol = nullptr;
   p.phy_draws = 0; p.synthetic = 0;
 #elif defined(RS_JIT_LEAN) && RS_JIT_LEAN
   /* ... and of a drop-in context's one-TTI kernel: the plain call -- per-RBG reports, no customised slices, no m_requiredRBs /

@@ -147,7 +147,7 @@
       const bool do_ewma = !(t == last_update);
       const double dt = t - last_update;
       for (int u = tid; u < U; u += nt) {
-        stop_schedule_user(u);
+        stop_schedule_user(u, tti - 1);
         bool has[2] = {false, false};
         double bavg[2] = {0, 0};
         for (int b = 0; b < 2; ++b) {

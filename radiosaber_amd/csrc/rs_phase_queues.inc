@@ -65,8 +65,12 @@
       cum_add(&p.cum_rbs[(size_t)cell * U + u], rbs);
     }
   };
+  /* DoStopSchedule of TTI k runs at the top of TTI k + 1 (or at the end of the launch): the TTI it belongs to is n_done - 1 then, and
+   * its clock value is kept here (t_k exactly, not t_{k+1} - 0.001) */
+  double q_stop_t = t;
   /* one bearer's RLC dequeue of `sent` bytes (TransmissionProcedure): whole packets cost their data + 8 bytes, the last one may
-   * leave as a fragment */
+   * leave as a fragment.  A burst is one InternetFlow flow (InternetFlow::Send): where its last packet leaves, whole or as its last
+   * fragment, the flow completion record gets the TTI and its clock (um-rlc-entity.cpp:143-160, "ipflow end") -- one store each */
   auto rlc_dequeue = [&](int u, int b, int sent) {
     int left = sent, head = QI(QF_HEAD, b, u), pk = QI(QF_PK, b, u), frag = QI(QF_FRAG, b, u), qb = QI(QF_BYTES, b, u), qp = QI(QF_PKTS, b, u);
     const int head0 = head;
@@ -100,6 +104,10 @@
         pk += k;
       }
       if (pk >= nfull + (last > 0 ? 1 : 0)) {
+        if (p.flow_tti) {
+          p.flow_tti[a0 + head] = (int32_t)(n_done - 1);
+          p.flow_time[a0 + head] = q_stop_t;
+        }
         head += 1;
         pk = 0;
         if (qp > 0) { nfull = p.arr_nfull[a0 + head]; last = p.arr_last[a0 + head]; } /* (packets left: the next burst exists) */
@@ -112,7 +120,24 @@
       qs_hla[b * U + u] = last;
     }
   };
-  auto stop_schedule_user = [&](int u) {
+  /* logged launches: one row per (TTI, user, bearer) -- the bytes DoStopSchedule credited and RadioBearer::GetHeadOfLinePacketDelay
+   * at that moment, before the RLC dequeue (radio-bearer.cpp:282-307: 0 with an empty MAC queue or an InfiniteBuffer bearer, else
+   * now - the head packet's time stamp, at least 1e-5; the slice-priority bearer's value is the q_ho its metric used in that TTI) */
+  auto log_bearer = [&](int u, int b, int kind, int bytes, int row) {
+    if (!p.log_bbytes || row < 0) return;
+    double hol = 0.0;
+    if (kind == 2 && QI(QF_BYTES, b, u) != 0) {
+      const double head_time = q_lds ? qs_headt[b * U + u]
+                                     : p.arr_time[(size_t)p.arr_off[(size_t)(cell * U + u) * 2 + b] + QI(QF_HEAD, b, u)];
+      hol = q_stop_t - head_time;
+      if (hol < 0.00001) hol = 0.00001;
+    }
+    const size_t i = (((size_t)cell * p.n_ttis + row) * U + u) * 2 + b;
+    p.log_bbytes[i] = bytes;
+    p.log_bhol[i] = hol;
+  };
+  /* row: the launch's TTI whose grant this is (its log row) */
+  auto stop_schedule_user = [&](int u, int row) {
     if constexpr (SCHED == 1) {
       /* DL_PF_PacketScheduler::DoStopSchedule (dl-pf-packet-scheduler.cpp:60-125): every flow is credited its own transport
        * block in full and hands it to its RLC */
@@ -128,7 +153,9 @@
         count_bearer(u, b, bytes, nprb);
         user_bytes += bytes;
         user_rbs += nprb;
-        if (kind_of[u * 2 + b] == 2) rlc_dequeue(u, b, bytes);
+        const int kind = kind_of[u * 2 + b];
+        log_bearer(u, b, kind, bytes, row);
+        if (kind == 2) rlc_dequeue(u, b, bytes);
       }
       if (user_bytes) count_user(u, user_bytes, user_rbs);
       return;
@@ -150,6 +177,7 @@
       QI(QF_TX, b, u) += sent;
       count_bearer(u, b, sent, nprb);
       user_bytes += sent;
+      log_bearer(u, b, kind, sent, row);
       if (kind == 2) rlc_dequeue(u, b, sent);
     }
     if (user_bytes) count_user(u, user_bytes, nprb);

@@ -99,3 +99,228 @@ def slice_throughput_from_log(lines: Iterable[str], n_users: int, n_slices: int,
         np.add.at(mbps, last[:, 4], last[:, 2] / seconds)
         np.add.at(rbs, last[:, 4], last[:, 3] / seconds)
     return list(mbps * 8 / 1e6), list(rbs)
+
+
+# ---- the queue model's per-bearer lines and the customised-slice experiment's outputs (exp-customization) ----
+#
+#   stderr, DoStopSchedule, one line per bearer credited with bytes (downlink-transport-scheduler.cpp:179-199,
+#   dl-pf-packet-scheduler.cpp:77-96) -- the line above, with the bearer's own application id and GetHeadOfLinePacketDelay;
+#   "ipflow start app: <A> flow: <F> flowsize: <Z>"                            (radio-bearer.cpp:335, MacQueue enqueue of a flow)
+#   "ipflow end app: <A> flow: <F> fct: <T> flowsize: <Z> priority: <P>"      (um-rlc-entity.cpp:154-160, its last packet sent)
+
+
+def fmt_double(x: float) -> str:
+    """A double as std::ostream prints it by default (%g: 6 significant digits, e.g. 0.003, 1e-05, 0)."""
+    return f"{float(x):g}"
+
+
+def app_ids(slices) -> np.ndarray:
+    """[U][2] application id of the bearer (user, priority), -1 = no bearer: the scenario's creation order
+    (single-cell-with-interference.h:206, 308-440) -- one global counter from 0; per UE its video applications, then its backlogged
+    flows, then InternetFlow j (priority j).  The bearer that SliceConfig.bearer_kinds() gives an application: InternetFlow j at
+    priority j; else the first video application, else the first backlogged flow at priority 0.  No traffic section: one backlogged
+    flow per UE, app id == user id."""
+    U = slices.n_users
+    out = np.full((U, 2), -1, np.int64)
+    nxt = 0
+    for u, s in enumerate(slices.user_to_slice):
+        t = slices.traffic[s] if slices.traffic else {}
+        n_vid, n_if = int(t.get("video_app", 0)), int(t.get("internet_flow", 0))
+        n_bl = int(t.get("backlog_flow", 0)) if t else 1
+        vid = list(range(nxt, nxt + n_vid))
+        bl = list(range(nxt + n_vid, nxt + n_vid + n_bl))
+        ipf = list(range(nxt + n_vid + n_bl, nxt + n_vid + n_bl + n_if))
+        nxt += n_vid + n_bl + n_if
+        if ipf:
+            out[u, :len(ipf)] = ipf
+        elif vid:
+            out[u, 0] = vid[0]
+        elif bl:
+            out[u, 0] = bl[0]
+    return out
+
+
+def internet_flow_bearers(slices) -> np.ndarray:
+    """[U][2] bool: the bearer carries an InternetFlow application (the ones that print ipflow lines; video bearers do not)."""
+    out = np.zeros((slices.n_users, 2), bool)
+    for u, s in enumerate(slices.user_to_slice):
+        t = slices.traffic[s] if slices.traffic else {}
+        out[u, :int(t.get("internet_flow", 0))] = True
+    return out
+
+
+def bearer_rows_from_users(tbs_bits):
+    """The bearer rows of a batch without the queue model (one backlogged bearer per UE, priority 0): what DoStopSchedule credits,
+    min(tbs / 8, 1e8) bytes, and hol_delay 0 (an InfiniteBuffer bearer has an empty MAC queue).  -> (bytes, hol) [n_ttis][U][2]."""
+    tbs_bits = np.asarray(tbs_bits)
+    by = np.zeros(tbs_bits.shape + (2,), np.int64)
+    by[..., 0] = np.minimum(tbs_bits // 8, 100000000)
+    return by, np.zeros(by.shape, np.float64)
+
+
+def bearer_prbs(rbg_to_user, nprb, rbg_size: int, pf_flows: bool = False):
+    """[n_ttis][U][2] PRBs that UpdateCumulateRBs adds to a bearer that transmitted: the user's PRB count (transport and NVS schedulers,
+    downlink-transport-scheduler.cpp:189-191), or with DL_PF on flows (pf_flows: the queue model's scheduler 1, whose rbg_to_user
+    holds flow ids 2 * user + priority) the flow's own PRBs (dl-pf-packet-scheduler.cpp:81)."""
+    rbg_to_user = np.asarray(rbg_to_user)
+    n = rbg_to_user.shape[0]
+    if pf_flows:
+        U = np.asarray(nprb).shape[1]
+        out = np.zeros((n, U * 2), np.int64)
+        for k in range(n):
+            m = rbg_to_user[k]
+            out[k] = np.bincount(m[m >= 0], minlength=U * 2)[:U * 2] * rbg_size
+        return out.reshape(n, U, 2)
+    p = np.asarray(nprb, np.int64)
+    return np.repeat(p[:, :, None], 2, axis=2)
+
+
+class BearerLogWriter:
+    """The reference's stderr lines of one cell of a queue-model batch, launch after launch: the per-bearer counter lines of every
+    scheduler (scheduler 1 included: DL_PF_PacketScheduler::DoStopSchedule prints the same "app: .. user: .. slice:" line) and the
+    ipflow lines of the InternetFlow bearers.
+
+    Within a TTI: first the "ipflow start" lines of the flows enqueued since the previous TTI (time in (t_{k-1}, t_k], by time, app,
+    flow), then the users ascending, each user's bearers in the reference's loop order -- priority 1 before 0 (transport and NVS
+    schedulers, downlink-transport-scheduler.cpp:179), 0 before 1 for DL_PF's FlowsToSchedule -- and right after a bearer's counter
+    line the "ipflow end" lines of its flows whose last packet left in that TTI, in flow order.  A flow is numbered by its burst index
+    on its bearer; flowsize = n_full * 1490 + last; fct = t_k - time in double.
+
+    app_of [U][2] (app_ids), flows {(user, prio): (time, n_full, last)} of the InternetFlow bearers of this cell (set_arrivals'
+    bursts), pf_flows: scheduler 1 (bearer order 0, 1).  Stamps are first_ts + the TTI's index in the batch.  flow_format: the
+    base class's "<ts> flow: <A> cumu_bytes: .. cumu_rbs: .. hol_delay: .." line (downlink-packet-scheduler.cpp:140-145, what
+    stderr_lines(pf_format=True) writes) instead of the "app: .. user: .. slice:" line."""
+
+    def __init__(self, app_of, user_to_slice, pf_flows: bool = False, flows=None, first_ts: int = 100,
+                 cum_bytes0=None, cum_rbs0=None, flow_format: bool = False):
+        self.app_of = np.asarray(app_of)
+        U = self.app_of.shape[0]
+        self.u2s = np.asarray(user_to_slice)
+        self.order = (0, 1) if pf_flows else (1, 0)
+        self.first_ts = first_ts
+        self.flow_format = flow_format
+        self.cb = np.zeros((U, 2), np.int64) if cum_bytes0 is None else np.array(cum_bytes0, np.int64)
+        self.cr = np.zeros((U, 2), np.int64) if cum_rbs0 is None else np.array(cum_rbs0, np.int64)
+        self.tti = 0  # index in the batch of the next TTI
+        self.flows = {}
+        starts = []
+        for (u, k), (t, nf, la) in (flows or {}).items():
+            t, nf, la = np.asarray(t, np.float64), np.asarray(nf, np.int64), np.asarray(la, np.int64)
+            self.flows[(u, k)] = (t, nf * 1490 + la)
+            starts += [(float(t[i]), int(self.app_of[u, k]), i, u, k) for i in range(len(t))]
+        starts.sort()
+        self.starts = starts
+        self.next_start = 0
+
+    def lines(self, bearer_bytes, bearer_hol, bearer_rbs, t_first: float, done=None) -> List[str]:
+        """One launch: bearer_bytes / bearer_hol / bearer_rbs [n_ttis][U][2] (run_logged(bearers=True), bearer_prbs), t_first = the
+        batch clock before the launch (BatchScheduler.clock()[0][cell]; t_{k+1} = t_k + 0.001), done = {(user, prio): (done_tti,
+        done_time)} of this cell (BatchScheduler.flow_record())."""
+        bearer_bytes = np.asarray(bearer_bytes)
+        n = bearer_bytes.shape[0]
+        g0 = self.tti
+        ends = {}
+        for key, (dt, dtime) in (done or {}).items():
+            if key not in self.flows:
+                continue
+            dt = np.asarray(dt)
+            for i in np.flatnonzero((dt >= g0) & (dt < g0 + n)):
+                ends.setdefault((int(dt[i]) - g0, key[0], key[1]), []).append((int(i), float(dtime[i])))
+        out = []
+        tk = t_first
+        for j in range(n):
+            if j:
+                tk = tk + 0.001
+            ts = self.first_ts + g0 + j
+            while self.next_start < len(self.starts) and self.starts[self.next_start][0] <= tk:
+                t, app, i, u, k = self.starts[self.next_start]
+                out.append(f"ipflow start app: {app} flow: {i} flowsize: {int(self.flows[(u, k)][1][i])}")
+                self.next_start += 1
+            for u in np.flatnonzero(bearer_bytes[j].any(1)):
+                for k in self.order:
+                    by = int(bearer_bytes[j, u, k])
+                    if by > 0:
+                        self.cb[u, k] += by
+                        self.cr[u, k] += int(bearer_rbs[j, u, k])
+                        line = (f"{ts} {'flow' if self.flow_format else 'app'}: {self.app_of[u, k]} cumu_bytes: {self.cb[u, k]} "
+                                f"cumu_rbs: {self.cr[u, k]} hol_delay: {fmt_double(bearer_hol[j, u, k])}")
+                        out.append(line if self.flow_format else f"{line} user: {u} slice: {self.u2s[u]}")
+                    for i, dtime in sorted(ends.get((j, int(u), k), [])):
+                        t, size = self.flows[(int(u), k)]
+                        out.append(f"ipflow end app: {self.app_of[u, k]} flow: {i} fct: {fmt_double(dtime - t[i])} "
+                                   f"flowsize: {int(size[i])} priority: {k}")
+        self.tti = g0 + n
+        return out
+
+
+# reducers of the customised-slice experiment (what exp-customization/plot_fctdelay.py computes from a run's stderr)
+def _words(line: str):
+    return line.split()
+
+
+def fct_from_log(lines: Iterable[str], slice_begin: int, slice_end: int, priority_only: bool = False, ts_shoot: int = 10000):
+    """Flow completion times (get_fct): an app's slice is the slice: field of its counter lines; flows of apps whose slice lies outside
+    [slice_begin, slice_end] are skipped (apps without a counter line are kept).  A flow counts when its "ipflow start" line comes
+    before the first counter line stamped after ts_shoot, and its fct is that of its "ipflow end" line; priority_only keeps end lines
+    of non-zero priority only.  Returns the fcts in the order the flows started."""
+    lines = list(lines)
+    slice_of = {}
+    for line in lines:
+        w = _words(line)
+        if w and w[0].isdigit():
+            slice_of[int(w[2])] = int(w[12])
+    captured = {}
+    after = False
+    for line in lines:
+        w = _words(line)
+        if not w:
+            continue
+        if w[0].isdigit() and int(w[0]) > ts_shoot:
+            after = True
+        if w[0] != "ipflow":
+            continue
+        app = int(w[3])
+        if app in slice_of and not (slice_begin <= slice_of[app] <= slice_end):
+            continue
+        if w[1] == "start" and not after:
+            captured[(app, int(w[5]))] = -1
+        if w[1] == "end":
+            if priority_only and int(w[11]) == 0:
+                continue
+            if (app, int(w[5])) in captured:
+                captured[(app, int(w[5]))] = float(w[7])
+    return [v for v in captured.values() if v != -1]
+
+
+def hol_from_log(lines: Iterable[str], slice_begin: int, slice_end: int):
+    """Head-of-line delays (get_hol): the hol_delay: of every counter line of a slice in [slice_begin, slice_end], in log order."""
+    out = []
+    for line in lines:
+        w = _words(line)
+        if w and w[0].isdigit() and slice_begin <= int(w[12]) <= slice_end:
+            out.append(float(w[8]))
+    return out
+
+
+def slice_throughput_window(lines: Iterable[str], slice_begin: int, slice_end: int, begin_ts: int = 20000, end_ts: int = 22000):
+    """Per-slice throughput (get_throughput) of the slices in [slice_begin, slice_end) -- end exclusive here: for every app the
+    cumu_bytes of its last counter line stamped in (begin_ts, end_ts], over end_ts milliseconds, in Mbit/s, summed per slice in the
+    order the apps first appear; lines after the first stamp beyond end_ts are not read."""
+    per_app = {s: {} for s in range(slice_begin, slice_end)}
+    for line in lines:
+        w = _words(line)
+        if not w or not w[0].isdigit():
+            continue
+        if int(w[0]) > end_ts:
+            break
+        if int(w[0]) > begin_ts:
+            sid = int(w[12])
+            if slice_begin <= sid < slice_end:
+                per_app[sid][int(w[2])] = int(w[4]) / (end_ts / 1000) * 8 / (1000 * 1000)
+    out = []
+    for s in range(slice_begin, slice_end):
+        acc = 0
+        for v in per_app[s].values():
+            acc += v
+        out.append(acc)
+    return out

@@ -3,23 +3,35 @@
 
     LTE-Sim SingleCellWithI 1 <sched> 1 30 <seed> <duration_s> <config.json>   2> <log>
 
-on the GPU: one cell, backlogged flows, the CQI traces and mapping file of the reference's cqi-traces-noise0 directory,
-and the reference's stderr lines (what plot_*.py parse) written to --log.
+on the GPU: one cell, the CQI traces and mapping file of the reference's cqi-traces-noise0 directory (or, without --traces,
+synthetic grids drawn from the traces' CQI histogram), and the reference's stderr lines (what plot_*.py parse) written to --log.
 
     python tools/run_experiment.py --sched 9 --seed 0 --duration 12 --config <config.json> \\
-        --traces <dir with ue*.log and mapping.config> --log maxcell_pf0.log [--cells 9: one per seed 0..8]
+        --traces <dir with ue*.log and mapping.config> --log maxcell_pf0.log
+
+Every scheduler writes the per-bearer DoStopSchedule line "<ts> app: A cumu_bytes: B cumu_rbs: K hol_delay: H user: U slice: S"
+(logfmt.BearerLogWriter).  Scheduler 1 too: DL_PF_PacketScheduler::DoStopSchedule prints that line, not the base class's
+"<ts> flow: A cumu_bytes: B cumu_rbs: K hol_delay: H" line -- except that a backlogged configuration keeps, by default, the "flow:"
+line earlier versions of this tool wrote for it (--sched1-line auto; `app` gives the reference's line there too).  A config with
+internet_flow / video_app applications (exp-customization) runs on the queue model: InternetFlow bursts from
+rs_internet_flow_arrivals at the config's rates, the video applications from the 1 280 kbit/s foreman trace
+(tests/golden/video_foreman_1280k.json, --video-trace), and the log also carries the "ipflow start" / "ipflow end" lines of the
+InternetFlow flows, with flow completion times from the batch's flow completion record.
 
 The scheduler's arithmetic is bit-exact; the position of the libc rand() stream at the first scheduled TTI depends on
 simulator set-up code outside this path (103 300 draws for the 100-UE configuration) and is taken
-from --rand-skip, so runs are statistically, not bitwise, those of the reference unless that number is known.
+from --rand-skip, and the flow sizes come from our generator's own rand() stream per bearer (rs_internet_flow_arrivals), not
+from the simulator's shared one: runs are statistically, not bitwise, those of the reference.
 """
 import argparse
+import json
 import sys
 from pathlib import Path
 
 import numpy as np
 
-sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
 import radiosaber_amd as rs  # noqa: E402
 from radiosaber_amd import logfmt  # noqa: E402
 
@@ -30,40 +42,82 @@ ap.add_argument("--sched", type=int, default=9, help="the reference's CLI schedu
 ap.add_argument("--seed", type=int, default=0, help="index into the reference's nine common seeds")
 ap.add_argument("--duration", type=float, default=12.0, help="simulated seconds after the 0.1 s start-up")
 ap.add_argument("--config", required=True, help="slice configuration JSON of the experiment directory")
-ap.add_argument("--traces", required=True, help="directory with ue<id>.log and the mapping file")
+ap.add_argument("--traces", default=None, help="directory with ue<id>.log and the mapping file (default: synthetic CQI grids)")
 ap.add_argument("--mapping", default="mapping.config")
 ap.add_argument("--nb-rbs", type=int, default=512)
 ap.add_argument("--rbg-size", type=int, default=8)
 ap.add_argument("--rand-skip", type=int, default=0)
+ap.add_argument("--video-trace", default=str(ROOT / "tests" / "golden" / "video_foreman_1280k.json"),
+                help="frame sizes and times of the video applications (JSON: time_ms, bytes)")
+ap.add_argument("--sched1-line", choices=("auto", "app", "flow"), default="auto",
+                help="scheduler 1's counter line: app (DL_PF_PacketScheduler's own), flow (the base class's); auto = app with the queue "
+                     "model, flow for backlogged configurations (this tool's earlier format)")
 ap.add_argument("--log", default="-", help="where the stderr-format lines go ('-' = stdout)")
 a = ap.parse_args()
 
 sc = rs.SliceConfig.from_json(a.config)
 R = a.nb_rbs // a.rbg_size
 n_ttis = int(round(a.duration * 1000))
-mapping = rs.read_trace_mapping(Path(a.traces) / a.mapping)
-n_traces = int(mapping.max()) + 1
-trace, mixed = rs.load_trace_dir(a.traces, n_traces=n_traces, nb_rbs=a.nb_rbs, rbg_size=a.rbg_size)
-if mixed:
-    raise SystemExit(f"{mixed} RBGs carry different CQI on their PRBs: the batched replay needs uniform RBGs")
 U = sc.n_users
-b = rs.BatchScheduler(sc, R, a.rbg_size, 1, sched=a.sched, phy_error_draws=True, jit=True)
-b.seed(np.array([COMMON_SEEDS[a.seed] if 0 <= a.seed < 9 else COMMON_SEEDS[0]], np.uint32),
-       np.array([a.rand_skip], np.int64))
-b.set_trace(trace, mapping[np.arange(U) % len(mapping)][None, :].astype(np.int32))
+seed = COMMON_SEEDS[a.seed] if 0 <= a.seed < 9 else COMMON_SEEDS[0]
+queues = any(int(t.get("internet_flow", 0)) or int(t.get("video_app", 0)) for t in sc.traffic)
+# (the queue model's batches run without the PHY error model's draws: its parity with the oracle is pinned that way)
+b = rs.BatchScheduler(sc, R, a.rbg_size, 1, sched=a.sched, phy_error_draws=not queues, jit=True)
+b.seed(np.array([seed], np.uint32), np.array([a.rand_skip], np.int64))
+if a.traces:
+    mapping = rs.read_trace_mapping(Path(a.traces) / a.mapping)
+    trace, mixed = rs.load_trace_dir(a.traces, n_traces=int(mapping.max()) + 1, nb_rbs=a.nb_rbs, rbg_size=a.rbg_size)
+    if mixed:
+        raise SystemExit(f"{mixed} RBGs carry different CQI on their PRBs: the batched replay needs uniform RBGs")
+    b.set_trace(trace, mapping[np.arange(U) % len(mapping)][None, :].astype(np.int32))
+else:
+    b.synthesize_cqi(seed, (n_ttis + 39) // 40)
+
+flows = {}
+if queues:
+    # the applications of single-cell-with-interference.h:308-440, started at 0.1 s and stopped at the end of the run
+    stop = 0.1 + n_ttis / 1000.0
+    u2s = sc.user_to_slice
+    bursts = {}
+    video = None
+    for u in range(U):
+        tr = sc.traffic[u2s[u]]
+        for j in range(int(tr.get("internet_flow", 0))):
+            rate = tr["if_bitrate"][j] / sc.ues_per_slice[u2s[u]]  # single-cell-with-interference.h:415-416
+            bursts[(0, u, j)] = rs.internet_flow_arrivals(rate, 0.1, stop, 1000 * a.seed + 2 * u + j)
+            flows[(u, j)] = bursts[(0, u, j)]
+        if int(tr.get("video_app", 0)) and not int(tr.get("internet_flow", 0)):
+            if video is None:
+                video = json.loads(Path(a.video_trace).read_text())
+            t, ts = 0.1, []
+            for k in range(len(video["bytes"])):  # TraceBased::Send: the next frame TimeToSend * 0.001 after this one
+                if k:
+                    t = (video["time_ms"][k] - video["time_ms"][k - 1]) * 0.001 + t
+                if t >= stop:
+                    break
+                ts.append(t)
+            bursts[(0, u, 0)] = rs.frames_to_bursts(ts, video["bytes"][:len(ts)])
+    b.set_bearers(sc.bearer_kinds())
+    b.set_arrivals(bursts)
+
+flow_line = a.sched == 1 and (a.sched1_line == "flow" or (a.sched1_line == "auto" and not queues))
+writer = logfmt.BearerLogWriter(logfmt.app_ids(sc), sc.user_to_slice, pf_flows=queues and a.sched == 1, flows=flows,
+                                flow_format=flow_line)
 out = sys.stdout if a.log == "-" else open(a.log, "w")
-cb = np.zeros(U, np.int64)
-cr = np.zeros(U, np.int64)
 done = 0
 while done < n_ttis:  # logged launches of at most 2 000 TTIs keep the host log small
     n = min(2000, n_ttis - done)
-    got = b.run_logged(n)
-    lines = logfmt.stderr_lines(got["tbs_bits"][0], got["rbg_to_user"][0], sc.user_to_slice, a.rbg_size,
-                                first_ts=100 + done, cum_bytes0=cb, cum_rbs0=cr, nprb=got["nprb"][0],
-                                pf_format=a.sched == 1)
+    t_first = float(b.clock()[0][0])
+    got = b.run_logged(n, bearers=queues)
+    if queues:
+        by, hol = got["bearer_bytes"][0], got["bearer_hol"][0]
+        rec = {(u, k): v for (c, u, k), v in b.flow_record().items() if (u, k) in flows}
+    else:
+        by, hol = logfmt.bearer_rows_from_users(got["tbs_bits"][0])
+        rec = None
+    rbs = logfmt.bearer_prbs(got["rbg_to_user"][0], got["nprb"][0], a.rbg_size, pf_flows=queues and a.sched == 1)
+    lines = writer.lines(by, hol, rbs, t_first, rec)
     out.write("\n".join(lines) + ("\n" if lines else ""))
-    st = b.state()
-    cb, cr = st["cum_bytes"][0].copy(), st["cum_rbs"][0].copy()
     done += n
 if out is not sys.stdout:
     out.close()
