@@ -26,7 +26,8 @@ extern "C" {
 #endif
 
 #define RS_ABI_VERSION 11 /* 11: (additions, no layout changed) rs_batch_flow_record (flow completion times of the queue model),
-                               rs_batch_bearer_log + rs_batch_run_logged_bearers (per-bearer DoStopSchedule rows);
+                               rs_batch_bearer_log + rs_batch_run_logged_bearers (per-bearer DoStopSchedule rows),
+                               rs_group_* (one TTI of several drop-in cells in one launch);
                                rs_config.link_tables (RS_LINK_*) + rs_link_tables_pinned / rs_link_tables_compare, rs_tti_in.cqi_epoch (the context keeps the
                                CQI image of an unchanged report set on the device), rs_ctx_jit_status (a specialised context checks its run-time build against the
                                built-in kernel during its first calls), rs_batch_config.selfcheck -1 / 0 / 1 with run-time builds verified by default and the
@@ -253,6 +254,46 @@ int rs_jit_selfcheck_dropin(int n_slices, int n_users, int n_rbgs, int rbg_size,
 /* slice_rbs_offset_ accessors (ref: downlink-transport-scheduler.h:38) */
 int rs_get_slice_offset(rs_ctx* ctx, double* offset /* [S] */);
 int rs_set_slice_offset(rs_ctx* ctx, const double* offset /* [S] */);
+
+/* ------------------------------------------------------------------------------------------
+ * Drop-in mode for a host that owns several cells: one TTI of up to n_cells cells in ONE kernel launch
+ * (one workgroup per cell) instead of one launch, one wait and one unpack per cell.  (ABI 11 addition, no layout changed.)
+ *
+ * Cell k of a group behaves exactly like an rs_ctx of its own, created from the same rs_config and fed the same sequence of
+ * rs_tti_in: every rs_tti_out field, the upper_* lists of RS_SCHED_UPPERBOUND and the slice state it carries to its next call are
+ * identical.  Cells are independent of each other; in one call they may differ in n_users / user_id, rand0 / rand1 and every input
+ * value.  A call that names a subset of the cells leaves the others' state untouched.
+ *
+ * Rules (each one is RS_ERR_INVALID with a message in rs_last_error(); a rejected call launches nothing and moves no cell's state):
+ *   - 1 <= n_cells <= RS_GROUP_MAX_CELLS (a sanity bound, not a tuned number); 1 <= n <= n_cells per call.
+ *   - cell_ids are distinct and in 0..n_cells-1 (NULL: cells 0..n-1).
+ *   - The PRESENCE of optional inputs is the same for every cell of one call: all cells give cqi_prb or none does (then all give cqi);
+ *     all or none give hol_delay; all or none give prio_has_data; all or none give the scheduler's gate (required_rbs for
+ *     RS_SCHED_NVS, data_to_transmit for RS_SCHED_PF); all or none ask for the upper_* outputs.  These are per-launch switches of
+ *     the kernel.
+ *   - The exact FP64 scan that rs_schedule_tti uses when an average or a HoL delay lies outside the FP32 filter's safe range is
+ *     decided per call: if any cell of the call needs it, every cell of the call uses it (same results: DESIGN.md 2.6).
+ *   - cqi_epoch is accepted and ignored: a group takes every grid from the caller's block on every call.
+ *   - Every scheduler rs_create accepts except RS_SCHED_NVS_NONGREEDY; general integer exponents and synthetic_exp are supported
+ *     (they belong to the config, so they are the same for the whole group).
+ *   - Only the kernels built into the library serve a group (no run-time specialisation): a shape they cannot run is rejected by
+ *     rs_group_create.
+ * One host thread per group at a time; different groups may run on different threads.
+ * ------------------------------------------------------------------------------------------ */
+#define RS_GROUP_MAX_CELLS 1024
+typedef struct rs_group rs_group;
+rs_group* rs_group_create(const rs_config* cfg, int32_t n_cells);
+rs_group* rs_group_create_checked(const rs_config* cfg, int32_t n_cells, int abi_version, size_t cfg_size);
+#define RS_GROUP_CREATE(cfg, n_cells) rs_group_create_checked((cfg), (n_cells), RS_ABI_VERSION, sizeof(rs_config))
+void rs_group_destroy(rs_group* g);
+/* in[k] / out[k] belong to cell cell_ids[k] (NULL: cell k), k = 0..n-1; every cell is validated before anything is launched */
+int rs_group_schedule_tti(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in /* [n] */, rs_tti_out* out /* [n] */);
+/* slice_rbs_offset_ of one cell (RS_SCHED_NVS: its slice EWMAs), as rs_get_slice_offset / rs_set_slice_offset */
+int rs_group_get_slice_offset(rs_group* g, int32_t cell, double* offset /* [S] */);
+int rs_group_set_slice_offset(rs_group* g, int32_t cell, const double* offset /* [S] */);
+/* scheduling kernels launched so far: one per successful rs_group_schedule_tti, none for a rejected one (tests, tools) */
+int64_t rs_group_launch_count(const rs_group* g);
+const char* rs_group_kernel_name(rs_group* g);
 
 /* ------------------------------------------------------------------------------------------
  * Batched mode: many independent cells resident on the device, whole DoSchedule() loops

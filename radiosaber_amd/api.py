@@ -6,6 +6,7 @@ The classes keep the reference's vocabulary (slices, UEs, RBGs, TTIs):
                    (downlink-transport-scheduler.cpp:55-97): ues_per_slice + per-slice
                    weight / algo_alpha / algo_beta / algo_epsilon / algo_psi
   TtiScheduler     drop-in mode, one RBsAllocation() per call            (rs_create / rs_schedule_tti)
+  GroupScheduler   drop-in mode, one TTI of several cells per call       (rs_group_create / rs_group_schedule_tti)
   BatchScheduler   many device-resident cells, whole DoSchedule() loops  (rs_batch_*)
 """
 import ctypes as C
@@ -106,6 +107,8 @@ ABI_SYMBOLS = [
     "rs_batch_checkpoint_bytes", "rs_batch_checkpoint_save", "rs_batch_checkpoint_load",
     "rs_link_tables_pinned", "rs_link_tables_compare", "rs_ctx_jit_status", "rs_jit_compiler_identity",
     "rs_batch_flow_record", "rs_batch_run_logged_bearers",
+    "rs_group_create", "rs_group_create_checked", "rs_group_destroy", "rs_group_schedule_tti",
+    "rs_group_get_slice_offset", "rs_group_set_slice_offset", "rs_group_launch_count", "rs_group_kernel_name",
 ]
 
 _lib = None
@@ -133,6 +136,18 @@ def lib():
     L.rs_schedule_tti.argtypes = [C.c_void_p, C.POINTER(_TtiIn), C.POINTER(_TtiOut)]
     L.rs_get_slice_offset.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.rs_set_slice_offset.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    L.rs_group_create.restype = C.c_void_p
+    L.rs_group_create.argtypes = [C.POINTER(_Config), C.c_int32]
+    L.rs_group_create_checked.restype = C.c_void_p
+    L.rs_group_create_checked.argtypes = [C.POINTER(_Config), C.c_int32, C.c_int, C.c_size_t]
+    L.rs_group_destroy.argtypes = [C.c_void_p]
+    L.rs_group_schedule_tti.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_TtiIn), C.POINTER(_TtiOut)]
+    L.rs_group_get_slice_offset.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double)]
+    L.rs_group_set_slice_offset.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double)]
+    L.rs_group_launch_count.restype = C.c_int64
+    L.rs_group_launch_count.argtypes = [C.c_void_p]
+    L.rs_group_kernel_name.restype = C.c_char_p
+    L.rs_group_kernel_name.argtypes = [C.c_void_p]
     L.rs_batch_create.restype = C.c_void_p
     L.rs_batch_create.argtypes = [C.POINTER(_BatchConfig)]
     L.rs_create_checked.restype = C.c_void_p
@@ -470,6 +485,51 @@ class TtiResult:
     upper_user: Optional[np.ndarray] = None  # ... and the user each one went to
 
 
+def _marshal_tti(S, R, rbg_size, sched, cqi, avg_rate, rand0=0, rand1=0, user_id=None, cqi_prb=None, hol_delay=None, prio_has_data=None,
+                 rand_draws=None, required_rbs=None, data_to_transmit=None, cqi_epoch=0):
+    """One call's arguments as (rs_tti_in, rs_tti_out, TtiResult, the arrays the two structs point at)."""
+    prb = None
+    if cqi_prb is not None:
+        prb = np.ascontiguousarray(cqi_prb, np.uint8)
+        n = prb.shape[0]
+        assert prb.shape == (n, R * rbg_size)
+        cqi = None
+    else:
+        cqi = np.ascontiguousarray(cqi, np.uint8)
+        n = cqi.shape[0]
+        assert cqi.shape == (n, R)
+    avg = np.ascontiguousarray(avg_rate, np.float64)
+    assert avg.shape == (n,)
+    uid = None if user_id is None else np.ascontiguousarray(user_id, np.int32)
+    hol = None if hol_delay is None else np.ascontiguousarray(hol_delay, np.float64)
+    prio = None if prio_has_data is None else np.ascontiguousarray(prio_has_data, np.uint8)
+    draws = None if rand_draws is None else np.ascontiguousarray(rand_draws, np.int32)
+    assert draws is None or draws.size == 300 * n
+    req = None if required_rbs is None else np.ascontiguousarray(required_rbs, np.int32)
+    dat = None if data_to_transmit is None else np.ascontiguousarray(data_to_transmit, np.int32)
+    assert (req is None or req.shape == (n,)) and (dat is None or dat.shape == (n,))
+    res = TtiResult(np.zeros(S, np.int32), np.zeros(S, np.int32), np.zeros(R, np.int32),
+                    np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32))
+    tin = _TtiIn(n, _p(uid, C.c_int32) if uid is not None else None,
+                 _p(cqi, C.c_uint8) if cqi is not None else None, _p(avg, C.c_double), rand0, rand1,
+                 _p(prb, C.c_uint8) if prb is not None else None,
+                 _p(hol, C.c_double) if hol is not None else None,
+                 _p(prio, C.c_uint8) if prio is not None else None,
+                 _p(draws, C.c_int32) if draws is not None else None,
+                 _p(req, C.c_int32) if req is not None else None,
+                 _p(dat, C.c_int32) if dat is not None else None, int(cqi_epoch))
+    if sched == RS_SCHED_UPPERBOUND:
+        res.upper_rbg = np.full((S, R), -1, np.int32)
+        res.upper_user = np.full((S, R), -1, np.int32)
+    tout = _TtiOut(_p(res.target_rbs, C.c_int32), _p(res.quota_rbgs, C.c_int32),
+                   _p(res.rbg_to_user, C.c_int32), _p(res.user_nprb, C.c_int32),
+                   _p(res.user_final_cqi, C.c_int32), _p(res.user_mcs, C.c_int32),
+                   _p(res.user_tbs_bits, C.c_int32),
+                   _p(res.upper_rbg, C.c_int32) if res.upper_rbg is not None else None,
+                   _p(res.upper_user, C.c_int32) if res.upper_user is not None else None)
+    return tin, tout, res, (cqi, prb, avg, uid, hol, prio, draws, req, dat)
+
+
 class TtiScheduler:
     """Drop-in mode: RBsAllocation() of one TTI on the GPU (rs_create / rs_schedule_tti)."""
 
@@ -508,46 +568,8 @@ class TtiScheduler:
         rand_draws (RS_SCHED_NVS_NONGREEDY): the 300 * n rand() values of RBsAllocationNonGreedyPF, in draw order.
         cqi_epoch: non-zero = the caller's version number of the CQI block; a call with the number (and users) of the call before reads
         the context's device-resident image instead of the block (rs_tti_in.cqi_epoch)."""
-        prb = None
-        if cqi_prb is not None:
-            prb = np.ascontiguousarray(cqi_prb, np.uint8)
-            n = prb.shape[0]
-            assert prb.shape == (n, self.R * self.rbg_size)
-            cqi = None
-        else:
-            cqi = np.ascontiguousarray(cqi, np.uint8)
-            n = cqi.shape[0]
-            assert cqi.shape == (n, self.R)
-        avg = np.ascontiguousarray(avg_rate, np.float64)
-        assert avg.shape == (n,)
-        uid = None if user_id is None else np.ascontiguousarray(user_id, np.int32)
-        hol = None if hol_delay is None else np.ascontiguousarray(hol_delay, np.float64)
-        prio = None if prio_has_data is None else np.ascontiguousarray(prio_has_data, np.uint8)
-        draws = None if rand_draws is None else np.ascontiguousarray(rand_draws, np.int32)
-        assert draws is None or draws.size == 300 * n
-        req = None if required_rbs is None else np.ascontiguousarray(required_rbs, np.int32)
-        dat = None if data_to_transmit is None else np.ascontiguousarray(data_to_transmit, np.int32)
-        assert (req is None or req.shape == (n,)) and (dat is None or dat.shape == (n,))
-        S = self.slices.n_slices
-        res = TtiResult(np.zeros(S, np.int32), np.zeros(S, np.int32), np.zeros(self.R, np.int32),
-                        np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32))
-        tin = _TtiIn(n, _p(uid, C.c_int32) if uid is not None else None,
-                     _p(cqi, C.c_uint8) if cqi is not None else None, _p(avg, C.c_double), rand0, rand1,
-                     _p(prb, C.c_uint8) if prb is not None else None,
-                     _p(hol, C.c_double) if hol is not None else None,
-                     _p(prio, C.c_uint8) if prio is not None else None,
-                     _p(draws, C.c_int32) if draws is not None else None,
-                     _p(req, C.c_int32) if req is not None else None,
-                     _p(dat, C.c_int32) if dat is not None else None, int(cqi_epoch))
-        if self.sched == RS_SCHED_UPPERBOUND:
-            res.upper_rbg = np.full((S, self.R), -1, np.int32)
-            res.upper_user = np.full((S, self.R), -1, np.int32)
-        tout = _TtiOut(_p(res.target_rbs, C.c_int32), _p(res.quota_rbgs, C.c_int32),
-                       _p(res.rbg_to_user, C.c_int32), _p(res.user_nprb, C.c_int32),
-                       _p(res.user_final_cqi, C.c_int32), _p(res.user_mcs, C.c_int32),
-                       _p(res.user_tbs_bits, C.c_int32),
-                       _p(res.upper_rbg, C.c_int32) if res.upper_rbg is not None else None,
-                       _p(res.upper_user, C.c_int32) if res.upper_user is not None else None)
+        tin, tout, res, _keep = _marshal_tti(self.slices.n_slices, self.R, self.rbg_size, self.sched, cqi, avg_rate, rand0, rand1, user_id,
+                                             cqi_prb, hol_delay, prio_has_data, rand_draws, required_rbs, data_to_transmit, cqi_epoch)
         _check(lib().rs_schedule_tti(self._h, C.byref(tin), C.byref(tout)))
         return res
 
@@ -567,6 +589,62 @@ class TtiScheduler:
     def slice_offset(self, v):
         a = np.ascontiguousarray(v, np.float64)
         _check(lib().rs_set_slice_offset(self._h, _p(a, C.c_double)))
+
+
+class GroupScheduler:
+    """Drop-in mode for a host that owns several cells: one TTI of up to n_cells cells in one kernel launch, one workgroup per cell
+    (rs_group_create / rs_group_schedule_tti).  Cell k behaves exactly like a TtiScheduler of its own."""
+
+    def __init__(self, slices: SliceConfig, n_rbgs: int, rbg_size: int, n_cells: int, sched: int = RS_SCHED_MAXCELL,
+                 device: int = 0, stream: Optional[int] = None, synthetic_exp: bool = False, link_tables: int = RS_LINK_DEFAULT):
+        self.slices, self.R, self.rbg_size, self.sched, self.n_cells = slices, n_rbgs, rbg_size, sched, n_cells
+        self._cfg = _CfgHolder(slices, n_rbgs, rbg_size, sched, device, stream, synthetic_exp, link_tables)
+        self._h = lib().rs_group_create_checked(C.byref(self._cfg.c), n_cells, RS_ABI_VERSION, C.sizeof(_Config))
+        if not self._h:
+            raise RadioSaberError(-1, lib().rs_last_error().decode())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().rs_group_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def schedule_tti(self, calls: Sequence[dict], cell_ids: Optional[Sequence[int]] = None) -> List[TtiResult]:
+        """calls[k]: the keyword arguments of TtiScheduler.schedule_tti for cell cell_ids[k] (None: cell k).  Optional inputs are
+        given by every cell of a call or by none (a mixed call raises, nothing is launched)."""
+        n = len(calls)
+        ins, outs, results, keep = (_TtiIn * n)(), (_TtiOut * n)(), [], []
+        for k, kw in enumerate(calls):
+            kw = dict(kw)
+            tin, tout, res, arrays = _marshal_tti(self.slices.n_slices, self.R, self.rbg_size, self.sched, kw.pop("cqi", None),
+                                                  kw.pop("avg_rate"), **kw)
+            ins[k], outs[k] = tin, tout
+            results.append(res)
+            keep.append(arrays)
+        ids = None if cell_ids is None else np.ascontiguousarray(cell_ids, np.int32)
+        assert ids is None or ids.shape == (n,)
+        _check(lib().rs_group_schedule_tti(self._h, n, _p(ids, C.c_int32) if ids is not None else None, ins, outs))
+        return results
+
+    def slice_offset(self, cell):
+        out = np.zeros(self.slices.n_slices, np.float64)
+        _check(lib().rs_group_get_slice_offset(self._h, cell, _p(out, C.c_double)))
+        return out
+
+    def set_slice_offset(self, cell, v):
+        a = np.ascontiguousarray(v, np.float64)
+        assert a.shape == (self.slices.n_slices,)
+        _check(lib().rs_group_set_slice_offset(self._h, cell, _p(a, C.c_double)))
+
+    @property
+    def launch_count(self):
+        """scheduling kernels launched so far: one per successful schedule_tti"""
+        return int(lib().rs_group_launch_count(self._h))
+
+    @property
+    def kernel_name(self):
+        return lib().rs_group_kernel_name(self._h).decode()
 
 
 class BatchScheduler:

@@ -1869,6 +1869,149 @@ CtxLayout ctx_layout(int n, int R, int S, int G, bool with_draws) {
   l.out_total = l.upper + 4 * (size_t)S * R; /* sched 10 only uses it */
   return l;
 }
+
+/* What packing one rs_tti_in leaves for the launch (pack_tti). */
+struct TtiPack {
+  CtxLayout l;              /* the block layout for the call's n users */
+  size_t in_bytes = 0;      /* bytes of the input block that travel (the per-PRB block only when given) */
+  bool exact_scan = false;  /* an input lies outside the FP32 filter's safe range (or general exponents): FP64 scan of every user */
+  const int32_t* gate = nullptr; /* the scheduler's gate array of this call, or null */
+  bool grid_touched = false;     /* the block's grid area was written (a context's device-resident CQI image no longer mirrors it) */
+};
+
+/* One cell's rs_tti_in validated and packed into a staging input block `h_in` (the layout of ctx_layout for its n users): slice
+ * bytes, the CQI grid with its zero padding (reuse_grid: left alone -- rs_tti_in.cqi_epoch), averages or the general exponents'
+ * denominators, the exact-scan test, draws, gate, HoL delays and priority flags.  Shared by rs_schedule_tti (its one block) and
+ * rs_group_schedule_tti (one slot per cell): the two paths cannot drift apart.  Touches nothing but `h_in` and `pk`. */
+int pack_tti(const rs_batch* b, const rs_tti_in* in, const rs_tti_out* out, uint8_t* h_in, bool reuse_grid, TtiPack* pk) {
+  const int n = in->n_users, R = b->R, S = b->S;
+  if (n < 1 || n > b->U) return fail(RS_ERR_INVALID, "n_users %d outside 1..%d", n, b->U);
+  if ((!in->cqi && !in->cqi_prb) || !in->avg_rate) return fail(RS_ERR_INVALID, "null cqi/avg_rate");
+  if (!out->rbg_to_user || !out->user_tbs_bits) return fail(RS_ERR_INVALID, "null output array");
+  const CtxLayout l = ctx_layout(n, R, S, b->G, b->sched == RS_SCHED_NVS_NONGREEDY);
+  pk->l = l;
+  uint8_t* h_slice = h_in + l.slice;
+  for (int i = 0; i < n; i++) {
+    int id = in->user_id ? in->user_id[i] : i;
+    if (id < 0 || id >= b->U) return fail(RS_ERR_INVALID, "user id %d out of range", id);
+    if (i && in->user_id && in->user_id[i] <= in->user_id[i - 1]) return fail(RS_ERR_INVALID, "user_id must ascend");
+    h_slice[i] = (uint8_t)b->u2s[id];
+    if ((b->sched == RS_SCHED_NVS || b->sched == RS_SCHED_NVS_NONGREEDY) && h_slice[i] != h_slice[0])
+      return fail(RS_ERR_INVALID, "RS_SCHED_NVS*: pass only the users of the served slice");
+  }
+  const int G = b->G;
+  pk->in_bytes = l.prb; /* the per-PRB block travels only when given */
+  if (in->cqi_prb) {
+    const size_t np = (size_t)n * R * G;
+    if (!reuse_grid) {
+      if (const uint8_t* bad = first_bad_cqi(in->cqi_prb, np)) return fail(RS_ERR_INVALID, "CQI %d outside 1..15", *bad);
+      memcpy(h_in + l.prb, in->cqi_prb, np);
+      for (int i = 0; i < n; i++)
+        for (int r = 0; r < R; r++) h_in[l.grid + (size_t)i * R + r] = in->cqi_prb[((size_t)i * R + r) * G];
+    }
+    pk->in_bytes = l.prb + np;
+  } else if (!reuse_grid) {
+    if (const uint8_t* bad = first_bad_cqi(in->cqi, (size_t)n * R)) return fail(RS_ERR_INVALID, "CQI %d outside 1..15", *bad);
+    memcpy(h_in + l.grid, in->cqi, (size_t)n * R);
+  }
+  if (!reuse_grid) memset(h_in + l.grid + (size_t)n * R, 0, l.slice - (size_t)n * R);
+  pk->grid_touched = true;
+  memcpy(h_in + l.avg, in->avg_rate, 8 * (size_t)n);
+  if (b->gen_exp) {
+    /* general exponents: pow(averageRate / 1000.0, psi) with averageRate = 1 + the caller's sum (ref: :681-693), host libm */
+    double* den = (double*)(h_in + l.avg);
+    for (int i = 0; i < n; i++) {
+      double k = 1;
+      k += in->avg_rate[i];
+      k /= 1000.0;
+      den[i] = pow(k, b->psi[h_slice[i]]);
+    }
+  }
+  /* The metric scan ranks users with an FP32 product first (DESIGN.md 2.6); its error bound needs every factor to be an
+   * ordinary FP32 number.  The reference takes any double (downlink-transport-scheduler.cpp:677-713: a non-finite, huge, tiny
+   * or negative average simply flows through the division and the strict '>' scan), so inputs outside the safe range switch
+   * this call to the exact FP64 scan of every user instead of being rejected.  (The EWMA keeps real averages in [1, ~1e12].) */
+  bool exact_scan = b->gen_exp; /* (powers of any size: no FP32 ranking, every user is compared with the reference's expression) */
+  if (!exact_scan) {
+    auto ordinary = [](double x, double lo, double hi) { return x >= lo && x <= hi; }; /* false for NaN */
+    for (int i = 0; i < n; i++) {
+      const double a = in->avg_rate[i];
+      const double k = b->sched == RS_SCHED_PF ? a : (1 + a) / 1000.0;
+      exact_scan |= !ordinary(k, 0x1p-60, 0x1p60);
+    }
+    if (b->any_alpha && in->hol_delay)
+      for (int i = 0; i < n; i++) {
+        const double h = in->hol_delay[i];
+        exact_scan |= !(h == 0 || ordinary(h, 0x1p-40, 0x1p40));
+      }
+  }
+  pk->exact_scan = exact_scan;
+  if (b->sched == RS_SCHED_NVS_NONGREEDY) {
+    if (!in->rand_draws) return fail(RS_ERR_INVALID, "RS_SCHED_NVS_NONGREEDY needs rand_draws (%d x n_users values)", RS_NVS_SAMPLES);
+    const size_t nd = (size_t)RS_NVS_SAMPLES * n;
+    for (size_t i = 0; i < nd; i++) {
+      if (in->rand_draws[i] < 0) return fail(RS_ERR_INVALID, "rand_draws[%zu] = %d is not a rand() value", i, in->rand_draws[i]);
+      h_in[l.draws + i] = (uint8_t)(in->rand_draws[i] % 4); /* downlink-nvs-scheduler.cpp:438 */
+    }
+  }
+  const int32_t* gate = b->sched == RS_SCHED_NVS ? in->required_rbs : (b->sched == RS_SCHED_PF ? in->data_to_transmit : nullptr);
+  pk->gate = gate;
+  if (gate) {
+    for (int i = 0; i < n; i++)
+      if (gate[i] < 0) return fail(RS_ERR_INVALID, "%s[%d] = %d is negative", b->sched == RS_SCHED_NVS ? "required_rbs" : "data_to_transmit", i, gate[i]);
+    memcpy(h_in + l.gate, gate, 4 * (size_t)n);
+  }
+  if (b->any_alpha) {
+    bool need_hol = false;
+    for (int i = 0; i < n; i++) {
+      const int sl = h_slice[i];
+      need_hol |= b->alpha[sl] && (b->sched == RS_SCHED_NVS || b->sched == RS_SCHED_NVS_NONGREEDY || b->beta[sl]);
+    }
+    if (need_hol && !in->hol_delay) return fail(RS_ERR_INVALID, "hol_delay is required by a customised (alpha=1, beta=1) slice");
+    if (in->hol_delay) memcpy(h_in + l.hol, in->hol_delay, 8 * (size_t)n);
+    else memset(h_in + l.hol, 0, 8 * (size_t)n);
+    if (in->prio_has_data) memcpy(h_in + l.prio, in->prio_has_data, (size_t)n);
+    else memset(h_in + l.prio, 1, (size_t)n);
+  }
+  return RS_OK;
+}
+
+/* One cell's output block `h_out` (layout `l`) unpacked into the caller's rs_tti_out: call positions back to user ids, the packed
+ * per-user word split.  Shared by rs_schedule_tti and rs_group_schedule_tti. */
+void unpack_tti(const rs_batch* b, const rs_tti_in* in, rs_tti_out* out, const uint8_t* h_out, const CtxLayout& l, bool want_upper) {
+  const int n = in->n_users, R = b->R, S = b->S;
+  const int16_t* h_map = (const int16_t*)(h_out + l.map);
+  const int16_t* h_quota = (const int16_t*)(h_out + l.quota);
+  const int16_t* h_target = (const int16_t*)(h_out + l.target);
+  const int32_t* h_tbs = (const int32_t*)(h_out + l.tbs);
+  const int32_t* h_uinfo = (const int32_t*)(h_out + l.uinfo);
+  for (int r = 0; r < R; r++) {
+    int o = h_map[r];
+    out->rbg_to_user[r] = o < 0 ? -1 : (in->user_id ? in->user_id[o] : o);
+  }
+  if (want_upper) {
+    const int32_t* h_upper = (const int32_t*)(h_out + l.upper);
+    for (int i = 0; i < S * R; i++) {
+      const int32_t v = h_upper[i];
+      if (out->upper_rbg) out->upper_rbg[i] = v < 0 ? -1 : (v & 63);
+      if (out->upper_user) out->upper_user[i] = v < 0 ? -1 : (in->user_id ? in->user_id[v >> 8] : (v >> 8));
+    }
+  } else {
+    if (out->upper_rbg) for (int i = 0; i < S * R; i++) out->upper_rbg[i] = -1;
+    if (out->upper_user) for (int i = 0; i < S * R; i++) out->upper_user[i] = -1;
+  }
+  for (int s = 0; s < S; s++) {
+    if (out->target_rbs) out->target_rbs[s] = h_target[s];
+    if (out->quota_rbgs) out->quota_rbgs[s] = h_quota[s];
+  }
+  for (int i = 0; i < n; i++) {
+    int32_t ui = h_uinfo[i];
+    if (out->user_nprb) out->user_nprb[i] = ui & 0xFFFF;
+    if (out->user_final_cqi) out->user_final_cqi[i] = (ui >> 16) & 0xFF;
+    if (out->user_mcs) out->user_mcs[i] = (ui >> 24) & 0xFF;
+    out->user_tbs_bits[i] = h_tbs[i];
+  }
+}
 }  // namespace
 
 extern "C" {
@@ -1974,97 +2117,20 @@ int rs_schedule_tti(rs_ctx* c, const rs_tti_in* in, rs_tti_out* out) {
   const clk::time_point t0 = c->timing ? clk::now() : clk::time_point();
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   const int n = in->n_users, R = b->R, S = b->S;
-  if (n < 1 || n > b->U) return fail(RS_ERR_INVALID, "n_users %d outside 1..%d", n, b->U);
-  if ((!in->cqi && !in->cqi_prb) || !in->avg_rate) return fail(RS_ERR_INVALID, "null cqi/avg_rate");
-  if (!out->rbg_to_user || !out->user_tbs_bits) return fail(RS_ERR_INVALID, "null output array");
-  const CtxLayout l = ctx_layout(n, R, S, b->G, b->sched == RS_SCHED_NVS_NONGREEDY);
-  uint8_t* h_slice = c->h_in + l.slice;
-  for (int i = 0; i < n; i++) {
-    int id = in->user_id ? in->user_id[i] : i;
-    if (id < 0 || id >= b->U) return fail(RS_ERR_INVALID, "user id %d out of range", id);
-    if (i && in->user_id && in->user_id[i] <= in->user_id[i - 1]) return fail(RS_ERR_INVALID, "user_id must ascend");
-    h_slice[i] = (uint8_t)b->u2s[id];
-    if ((b->sched == RS_SCHED_NVS || b->sched == RS_SCHED_NVS_NONGREEDY) && h_slice[i] != h_slice[0])
-      return fail(RS_ERR_INVALID, "RS_SCHED_NVS*: pass only the users of the served slice");
-  }
-  const int G = b->G;
-  size_t in_bytes = l.prb; /* the per-PRB block travels only when given */
   /* rs_tti_in.cqi_epoch: the same reports for the same users as the call before?  Then the caller's block is not touched -- the kernel
    * reads the image the context kept on the device (and, per-PRB reports, the device copy of the block) */
   const bool same_users = c->img_valid && c->img_n == n && c->img_has_ids == (in->user_id != nullptr) &&
                           (!in->user_id || memcmp(c->img_ids.data(), in->user_id, 4 * (size_t)n) == 0);
   const bool reuse_grid = in->cqi_epoch != 0 && same_users && in->cqi_epoch == c->img_epoch && c->img_prb == (in->cqi_prb != nullptr);
   const int image_mode = in->cqi_epoch == 0 ? 0 : (reuse_grid ? 2 : 1);
-  if (in->cqi_prb) {
-    const size_t np = (size_t)n * R * G;
-    if (!reuse_grid) {
-      if (const uint8_t* bad = first_bad_cqi(in->cqi_prb, np)) return fail(RS_ERR_INVALID, "CQI %d outside 1..15", *bad);
-      memcpy(c->h_in + l.prb, in->cqi_prb, np);
-      for (int i = 0; i < n; i++)
-        for (int r = 0; r < R; r++) c->h_in[l.grid + (size_t)i * R + r] = in->cqi_prb[((size_t)i * R + r) * G];
-    }
-    in_bytes = l.prb + np;
-  } else if (!reuse_grid) {
-    if (const uint8_t* bad = first_bad_cqi(in->cqi, (size_t)n * R)) return fail(RS_ERR_INVALID, "CQI %d outside 1..15", *bad);
-    memcpy(c->h_in + l.grid, in->cqi, (size_t)n * R);
-  }
-  if (!reuse_grid) memset(c->h_in + l.grid + (size_t)n * R, 0, l.slice - (size_t)n * R);
-  c->img_valid = false; /* (until this call has gone through) */
-  memcpy(c->h_in + l.avg, in->avg_rate, 8 * (size_t)n);
-  if (b->gen_exp) {
-    /* general exponents: pow(averageRate / 1000.0, psi) with averageRate = 1 + the caller's sum (ref: :681-693), host libm */
-    double* den = (double*)(c->h_in + l.avg);
-    for (int i = 0; i < n; i++) {
-      double k = 1;
-      k += in->avg_rate[i];
-      k /= 1000.0;
-      den[i] = pow(k, b->psi[h_slice[i]]);
-    }
-  }
-  /* The metric scan ranks users with an FP32 product first (DESIGN.md 2.6); its error bound needs every factor to be an
-   * ordinary FP32 number.  The reference takes any double (downlink-transport-scheduler.cpp:677-713: a non-finite, huge, tiny
-   * or negative average simply flows through the division and the strict '>' scan), so inputs outside the safe range switch
-   * this call to the exact FP64 scan of every user instead of being rejected.  (The EWMA keeps real averages in [1, ~1e12].) */
-  bool exact_scan = b->gen_exp; /* (powers of any size: no FP32 ranking, every user is compared with the reference's expression) */
-  if (!exact_scan) {
-    auto ordinary = [](double x, double lo, double hi) { return x >= lo && x <= hi; }; /* false for NaN */
-    for (int i = 0; i < n; i++) {
-      const double a = in->avg_rate[i];
-      const double k = b->sched == RS_SCHED_PF ? a : (1 + a) / 1000.0;
-      exact_scan |= !ordinary(k, 0x1p-60, 0x1p60);
-    }
-    if (b->any_alpha && in->hol_delay)
-      for (int i = 0; i < n; i++) {
-        const double h = in->hol_delay[i];
-        exact_scan |= !(h == 0 || ordinary(h, 0x1p-40, 0x1p40));
-      }
-  }
-  if (b->sched == RS_SCHED_NVS_NONGREEDY) {
-    if (!in->rand_draws) return fail(RS_ERR_INVALID, "RS_SCHED_NVS_NONGREEDY needs rand_draws (%d x n_users values)", RS_NVS_SAMPLES);
-    const size_t nd = (size_t)RS_NVS_SAMPLES * n;
-    for (size_t i = 0; i < nd; i++) {
-      if (in->rand_draws[i] < 0) return fail(RS_ERR_INVALID, "rand_draws[%zu] = %d is not a rand() value", i, in->rand_draws[i]);
-      c->h_in[l.draws + i] = (uint8_t)(in->rand_draws[i] % 4); /* downlink-nvs-scheduler.cpp:438 */
-    }
-  }
-  const int32_t* gate = b->sched == RS_SCHED_NVS ? in->required_rbs : (b->sched == RS_SCHED_PF ? in->data_to_transmit : nullptr);
-  if (gate) {
-    for (int i = 0; i < n; i++)
-      if (gate[i] < 0) return fail(RS_ERR_INVALID, "%s[%d] = %d is negative", b->sched == RS_SCHED_NVS ? "required_rbs" : "data_to_transmit", i, gate[i]);
-    memcpy(c->h_in + l.gate, gate, 4 * (size_t)n);
-  }
-  if (b->any_alpha) {
-    bool need_hol = false;
-    for (int i = 0; i < n; i++) {
-      const int sl = h_slice[i];
-      need_hol |= b->alpha[sl] && (b->sched == RS_SCHED_NVS || b->sched == RS_SCHED_NVS_NONGREEDY || b->beta[sl]);
-    }
-    if (need_hol && !in->hol_delay) return fail(RS_ERR_INVALID, "hol_delay is required by a customised (alpha=1, beta=1) slice");
-    if (in->hol_delay) memcpy(c->h_in + l.hol, in->hol_delay, 8 * (size_t)n);
-    else memset(c->h_in + l.hol, 0, 8 * (size_t)n);
-    if (in->prio_has_data) memcpy(c->h_in + l.prio, in->prio_has_data, (size_t)n);
-    else memset(c->h_in + l.prio, 1, (size_t)n);
-  }
+  TtiPack pk;
+  const int pack_rc = pack_tti(b, in, out, c->h_in, reuse_grid, &pk);
+  if (pk.grid_touched) c->img_valid = false; /* (until this call has gone through) */
+  if (pack_rc) return pack_rc;
+  const CtxLayout& l = pk.l;
+  const size_t in_bytes = pk.in_bytes;
+  const bool exact_scan = pk.exact_scan;
+  const int32_t* const gate = pk.gate;
   hipStream_t st = b->stream;
   const clk::time_point t1 = c->timing ? clk::now() : clk::time_point();
   /* per-PRB reports and queue state are read again and again inside the TTI: those calls keep the device copies */
@@ -2225,37 +2291,7 @@ int rs_schedule_tti(rs_ctx* c, const rs_tti_in* in, rs_tti_out* out) {
     if (reuse_grid) c->n_img_reused++;
   }
   const clk::time_point t3 = c->timing ? clk::now() : clk::time_point();
-  const int16_t* h_map = (const int16_t*)(c->h_out + l.map);
-  const int16_t* h_quota = (const int16_t*)(c->h_out + l.quota);
-  const int16_t* h_target = (const int16_t*)(c->h_out + l.target);
-  const int32_t* h_tbs = (const int32_t*)(c->h_out + l.tbs);
-  const int32_t* h_uinfo = (const int32_t*)(c->h_out + l.uinfo);
-  for (int r = 0; r < R; r++) {
-    int o = h_map[r];
-    out->rbg_to_user[r] = o < 0 ? -1 : (in->user_id ? in->user_id[o] : o);
-  }
-  if (want_upper) {
-    const int32_t* h_upper = (const int32_t*)(c->h_out + l.upper);
-    for (int i = 0; i < S * R; i++) {
-      const int32_t v = h_upper[i];
-      if (out->upper_rbg) out->upper_rbg[i] = v < 0 ? -1 : (v & 63);
-      if (out->upper_user) out->upper_user[i] = v < 0 ? -1 : (in->user_id ? in->user_id[v >> 8] : (v >> 8));
-    }
-  } else {
-    if (out->upper_rbg) for (int i = 0; i < S * R; i++) out->upper_rbg[i] = -1;
-    if (out->upper_user) for (int i = 0; i < S * R; i++) out->upper_user[i] = -1;
-  }
-  for (int s = 0; s < S; s++) {
-    if (out->target_rbs) out->target_rbs[s] = h_target[s];
-    if (out->quota_rbgs) out->quota_rbgs[s] = h_quota[s];
-  }
-  for (int i = 0; i < n; i++) {
-    int32_t ui = h_uinfo[i];
-    if (out->user_nprb) out->user_nprb[i] = ui & 0xFFFF;
-    if (out->user_final_cqi) out->user_final_cqi[i] = (ui >> 16) & 0xFF;
-    if (out->user_mcs) out->user_mcs[i] = (ui >> 24) & 0xFF;
-    out->user_tbs_bits[i] = h_tbs[i];
-  }
+  unpack_tti(b, in, out, c->h_out, l, want_upper);
   if (c->timing) {
     const clk::time_point t4 = clk::now();
     auto us = [](clk::time_point a, clk::time_point b2) { return std::chrono::duration<double, std::micro>(b2 - a).count(); };
@@ -2342,6 +2378,272 @@ int rs_set_slice_offset(rs_ctx* c, const double* offset) {
   HIP_TRY(hipMemcpy(c->b->d_sstate, offset, 8 * c->b->S, hipMemcpyHostToDevice));
   return RS_OK;
 }
+
+/* ---- a group of drop-in cells: one TTI of K cells in one launch (include/radiosaber_hip.h) ---- */
+
+struct rs_group {
+  rs_batch* b = nullptr;     /* a direct-mode batch of n_cells cells: the config's device tables, [cells][S] slice state, [cells] scalars, the stream */
+  int n_cells = 0;
+  /* one mapped pinned block each way, n_cells call slots each, and their device twins for the calls that copy (per-PRB reports,
+   * customised slices: read again and again inside the TTI).  Input slot: RsGroupCell header | the single call's input block;
+   * output slot: the single call's output block.  The completion word lies behind the last output slot, on its own cache line. */
+  uint8_t *h_in = nullptr, *d_in = nullptr, *h_out = nullptr, *d_out = nullptr, *z_in = nullptr, *z_out = nullptr;
+  size_t in_stride = 0, out_stride = 0, flag_off = 0;
+  uint32_t* d_count = nullptr; /* the launch's completion counter (rs_group_kernel) */
+  bool poll = false;
+  uint32_t seq = 0;
+  long poll_us = 2000;
+  int64_t launches = 0;
+  std::vector<uint8_t> named; /* cell_ids check: which cells this call has named so far */
+  std::vector<TtiPack> packs;
+  /* RS_DROPIN_TIMING=1: the host-side split of the calls, printed by rs_group_destroy */
+  bool timing = false;
+  double t_prep = 0, t_enq = 0, t_wait = 0, t_unpack = 0;
+  long n_calls = 0, n_cell_ttis = 0, n_polled = 0, n_fallback = 0;
+  char kname[48] = "";
+};
+
+extern "C" hipError_t rs_launch_group(const RsLaunch* p, int threads, hipStream_t stream);
+
+rs_group* rs_group_create_checked(const rs_config* cfg, int32_t n_cells, int abi_version, size_t cfg_size) {
+  if (abi_version != RS_ABI_VERSION || cfg_size != sizeof(rs_config)) {
+    fail(RS_ERR_INVALID, "ABI mismatch: caller was built against ABI %d with an rs_config of %zu bytes, this library is ABI %d with %zu bytes",
+         abi_version, cfg_size, RS_ABI_VERSION, sizeof(rs_config));
+    return nullptr;
+  }
+  return rs_group_create(cfg, n_cells);
+}
+
+rs_group* rs_group_create(const rs_config* cfg, int32_t n_cells) {
+  if (!cfg) { fail(RS_ERR_INVALID, "null config"); return nullptr; }
+  if (n_cells < 1 || n_cells > RS_GROUP_MAX_CELLS) { fail(RS_ERR_INVALID, "n_cells %d outside 1..%d", n_cells, RS_GROUP_MAX_CELLS); return nullptr; }
+  if (cfg->sched == RS_SCHED_NVS_NONGREEDY) {
+    fail(RS_ERR_INVALID, "RS_SCHED_NVS_NONGREEDY is not served by a group (its draw block and kernels differ): use one rs_ctx per cell");
+    return nullptr;
+  }
+  rs_batch_config bc;
+  memset(&bc, 0, sizeof bc);
+  bc.cell = *cfg;
+  bc.n_cells = n_cells;
+  bc.cqi_refresh = 1;
+  rs_batch* b = batch_new(&bc, true);
+  if (!b) return nullptr;
+  if (b->threads > 512) { /* (only the kernels built into the library serve a group) */
+    fail(RS_ERR_INVALID, "a group runs the built-in kernels only: %d threads per cell exceed their 512", b->threads);
+    rs_batch_destroy(b);
+    return nullptr;
+  }
+  rs_group* g = new (std::nothrow) rs_group();
+  if (!g) { rs_batch_destroy(b); fail(RS_ERR_INVALID, "out of memory"); return nullptr; }
+  g->b = b;
+  g->n_cells = n_cells;
+  const CtxLayout l = ctx_layout(b->U, b->R, b->S, b->G, false);
+  g->in_stride = round_up((int)(RS_GROUP_HDR_BYTES + l.in_total), 256);
+  g->out_stride = round_up((int)l.out_total, 256);
+  g->flag_off = g->out_stride * (size_t)n_cells;
+  const size_t in_bytes = g->in_stride * (size_t)n_cells, out_bytes = g->flag_off + 64;
+  const bool ok = hipMalloc(&g->d_in, in_bytes) == hipSuccess && hipMalloc(&g->d_out, out_bytes) == hipSuccess &&
+                  hipMalloc(&g->d_count, 64) == hipSuccess && hipMemset(g->d_count, 0, 64) == hipSuccess &&
+                  hipHostMalloc((void**)&g->h_in, in_bytes, hipHostMallocMapped) == hipSuccess &&
+                  hipHostMalloc((void**)&g->h_out, out_bytes, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
+  if (!ok) { fail(RS_ERR_HIP, "allocation of the group's staging blocks failed (%zu + %zu bytes)", in_bytes, out_bytes); rs_group_destroy(g); return nullptr; }
+  const char* force_copy = getenv("RS_DROPIN_COPY");
+  if (!(force_copy && force_copy[0] == '1')) {
+    void *zi = nullptr, *zo = nullptr;
+    if (hipHostGetDevicePointer(&zi, g->h_in, 0) == hipSuccess && hipHostGetDevicePointer(&zo, g->h_out, 0) == hipSuccess) {
+      g->z_in = (uint8_t*)zi;
+      g->z_out = (uint8_t*)zo;
+    }
+  }
+  memset(g->h_in, 0, in_bytes);
+  memset(g->h_out, 0, out_bytes);
+  const char* tm = getenv("RS_DROPIN_TIMING");
+  g->timing = tm && tm[0] == '1';
+  const char* pl = getenv("RS_DROPIN_POLL");
+  g->poll = g->z_out != nullptr && !(pl && pl[0] == '0');
+  if (const char* pu = getenv("RS_DROPIN_POLL_US")) g->poll_us = atol(pu) > 0 ? atol(pu) : 2000;
+  g->named.assign(n_cells, 0);
+  g->packs.resize(n_cells);
+  const int ept = (b->R * b->S + b->threads - 1) / b->threads;
+  const bool sorts = b->sched == RS_SCHED_MAXCELL || b->sched == RS_SCHED_UPPERBOUND;
+  snprintf(g->kname, sizeof g->kname, "rs_group_kernel<%d, %d>", b->sched, sorts && ept <= 4 ? ept : 0);
+  g_err[0] = 0;
+  return g;
+}
+
+void rs_group_destroy(rs_group* g) {
+  if (!g) return;
+  if (g->timing && g->n_calls)
+    fprintf(stderr, "rs_group_schedule_tti x %ld (%.1f cells per call): prepare %.2f us, enqueue %.2f us, wait %.2f us, unpack %.2f us per call (%ld completed by the polled word, %ld by the stream)\n",
+            g->n_calls, (double)g->n_cell_ttis / g->n_calls, g->t_prep / g->n_calls, g->t_enq / g->n_calls, g->t_wait / g->n_calls,
+            g->t_unpack / g->n_calls, g->n_polled, g->n_fallback);
+  if (g->b && g->b->stream) (void)hipStreamSynchronize(g->b->stream);
+  if (g->d_in) (void)hipFree(g->d_in);
+  if (g->d_out) (void)hipFree(g->d_out);
+  if (g->d_count) (void)hipFree(g->d_count);
+  if (g->h_in) (void)hipHostFree(g->h_in);
+  if (g->h_out) (void)hipHostFree(g->h_out);
+  rs_batch_destroy(g->b);
+  delete g;
+}
+
+int rs_group_schedule_tti(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out) {
+  if (!g || !in || !out) return fail(RS_ERR_INVALID, "null argument");
+  rs_batch* b = g->b;
+  using clk = std::chrono::steady_clock;
+  const clk::time_point t0 = g->timing ? clk::now() : clk::time_point();
+  if (n < 1 || n > g->n_cells) return fail(RS_ERR_INVALID, "n %d outside 1..%d (the group's cells)", n, g->n_cells);
+  /* ---- every cell is validated before the device is touched: a rejected call is a no-op ---- */
+  if (cell_ids) {
+    int bad = -1, dup = -1;
+    for (int k = 0; k < n && bad < 0 && dup < 0; k++) {
+      const int c = cell_ids[k];
+      if (c < 0 || c >= g->n_cells) bad = k;
+      else if (g->named[c]) dup = k;
+      else g->named[c] = 1;
+    }
+    for (int k = 0; k < n; k++)
+      if (cell_ids[k] >= 0 && cell_ids[k] < g->n_cells) g->named[cell_ids[k]] = 0;
+    if (bad >= 0) return fail(RS_ERR_INVALID, "cell_ids[%d] = %d outside 0..%d", bad, cell_ids[bad], g->n_cells - 1);
+    if (dup >= 0) return fail(RS_ERR_INVALID, "cell_ids[%d] = %d names a cell twice", dup, cell_ids[dup]);
+  }
+  /* the presence of optional inputs is a per-launch switch of the kernel: the same for every cell of the call */
+  auto gate_of = [&](const rs_tti_in& t) { return b->sched == RS_SCHED_NVS ? t.required_rbs : (b->sched == RS_SCHED_PF ? t.data_to_transmit : nullptr); };
+  auto upper_of = [&](const rs_tti_out& o) { return b->sched == RS_SCHED_UPPERBOUND && (o.upper_rbg || o.upper_user); };
+  const bool has_prb = in[0].cqi_prb != nullptr, has_hol = in[0].hol_delay != nullptr, has_prio = in[0].prio_has_data != nullptr,
+             has_gate = gate_of(in[0]) != nullptr, want_upper = upper_of(out[0]);
+  for (int k = 1; k < n; k++) {
+    const char* what = (in[k].cqi_prb != nullptr) != has_prb ? "cqi_prb" : (in[k].hol_delay != nullptr) != has_hol ? "hol_delay"
+                     : (in[k].prio_has_data != nullptr) != has_prio ? "prio_has_data"
+                     : (gate_of(in[k]) != nullptr) != has_gate ? (b->sched == RS_SCHED_NVS ? "required_rbs" : "data_to_transmit")
+                     : upper_of(out[k]) != want_upper ? "upper_rbg / upper_user" : nullptr;
+    if (what) return fail(RS_ERR_INVALID, "mixed call: cell slot %d and cell slot 0 differ in whether they give %s (optional inputs are given by every cell of a call or by none)", k, what);
+  }
+  HIP_TRY(hipSetDevice(b->cfg.cell.device));
+  bool exact_scan = false;
+  for (int k = 0; k < n; k++) {
+    uint8_t* const slot = g->h_in + (size_t)k * g->in_stride;
+    TtiPack& pk = g->packs[k];
+    pk = TtiPack();
+    const int rc = pack_tti(b, &in[k], &out[k], slot + RS_GROUP_HDR_BYTES, false, &pk);
+    if (rc) {
+      char msg[sizeof g_err];
+      snprintf(msg, sizeof msg, "%s", g_err);
+      return fail(rc, "cell slot %d (cell %d): %.400s", k, cell_ids ? cell_ids[k] : k, msg);
+    }
+    exact_scan |= pk.exact_scan; /* decided per call: one cell outside the FP32 filter's range, the exact scan for all (same results) */
+    const CtxLayout& l = pk.l;
+    const int nu = in[k].n_users;
+    RsGroupCell h;
+    memset(&h, 0, sizeof h);
+    h.cell = cell_ids ? cell_ids[k] : k;
+    h.U = nu;
+    h.Upad = upad_of(nu);
+    h.n_seg = b->base.n_seg;
+    h.n_items = b->base.n_items;
+    if (b->sched == RS_SCHED_PF) { h.n_seg = (nu + RS_PF_SEG - 1) / RS_PF_SEG; h.n_items = b->R * h.n_seg; }
+    h.rand0 = in[k].rand0;
+    h.rand1 = in[k].rand1;
+    h.in_slice = (int32_t)l.slice; h.in_avg = (int32_t)l.avg; h.in_hol = (int32_t)l.hol; h.in_prio = (int32_t)l.prio;
+    h.in_gate = (int32_t)l.gate; h.in_prb = (int32_t)l.prb;
+    h.out_uinfo = (int32_t)l.uinfo; h.out_map = (int32_t)l.map; h.out_quota = (int32_t)l.quota; h.out_target = (int32_t)l.target;
+    h.out_upper = (int32_t)l.upper;
+    memcpy(slot, &h, sizeof h);
+  }
+  hipStream_t st = b->stream;
+  const clk::time_point t1 = g->timing ? clk::now() : clk::time_point();
+  /* per-PRB reports and queue state are read again and again inside the TTI: those calls keep the device copies */
+  const bool zc = g->z_in != nullptr && !has_prb && !b->any_alpha;
+  uint8_t* const dev_in = zc ? g->z_in : g->d_in;
+  uint8_t* const dev_out = zc ? g->z_out : g->d_out;
+  if (!zc) HIP_TRY(hipMemcpyAsync(g->d_in, g->h_in, (size_t)n * g->in_stride, hipMemcpyHostToDevice, st));
+  RsLaunch L = b->base;
+  L.n_cells = n; /* call slots of this launch */
+  L.n_ttis = 1;
+  L.direct = 1;
+  L.cqi_mode = RS_CQI_EPOCHS;
+  L.refresh = 1;
+  L.n_epochs = 1;
+  L.image_mode = 0; /* (cqi_epoch: accepted and ignored) */
+  L.grid_image = nullptr;
+  L.queue_mode = b->any_alpha ? 1 : 0;
+  L.exact_scan = exact_scan ? 1 : 0;
+  L.gen_exp = b->gen_exp ? 1 : 0;
+  L.gen_num = b->d_gen_num;
+  /* given / not given; the workgroups take the addresses from their slots */
+  L.prb_cqi = has_prb ? dev_in : nullptr;
+  L.gate = has_gate ? (const int32_t*)dev_in : nullptr;
+  L.log_upper = want_upper ? (int32_t*)dev_out : nullptr;
+  L.grp_in = dev_in;
+  L.grp_out = dev_out;
+  L.grp_in_stride = (int64_t)g->in_stride;
+  L.grp_out_stride = (int64_t)g->out_stride;
+  L.grp_count = g->d_count;
+  const bool poll = zc && g->poll;
+  if (poll) {
+    if (++g->seq == 0) g->seq = 1; /* (0 is the word's initial value) */
+    L.done_flag = (uint32_t*)(g->z_out + g->flag_off);
+    L.done_seq = g->seq;
+  }
+  HIP_TRY(rs_launch_group(&L, b->threads, st));
+  g->launches++;
+  if (!zc) HIP_TRY(hipMemcpyAsync(g->h_out, g->d_out, (size_t)n * g->out_stride, hipMemcpyDeviceToHost, st));
+  const clk::time_point t2 = g->timing ? clk::now() : clk::time_point();
+  bool seen = false;
+  if (poll) {
+    /* the last workgroup to finish publishes the sequence number behind every workgroup's outputs (release, system scope) */
+    const volatile uint32_t* const h_flag = (const volatile uint32_t*)(g->h_out + g->flag_off);
+    const clk::time_point give_up = clk::now() + std::chrono::microseconds(g->poll_us);
+    for (unsigned spins = 0;; ++spins) {
+      if (__atomic_load_n((const uint32_t*)h_flag, __ATOMIC_ACQUIRE) == g->seq) { seen = true; break; }
+      __builtin_ia32_pause();
+      if ((spins & 255u) == 255u && clk::now() > give_up) break;
+    }
+    if (seen) {
+      g->n_polled++;
+      if ((g->n_polled & 63) == 0) (void)hipStreamQuery(st); /* (the stream's own bookkeeping, as in rs_schedule_tti) */
+    }
+  }
+  if (!seen) {
+    g->n_fallback++;
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  const clk::time_point t3 = g->timing ? clk::now() : clk::time_point();
+  for (int k = 0; k < n; k++) unpack_tti(b, &in[k], &out[k], g->h_out + (size_t)k * g->out_stride, g->packs[k].l, want_upper);
+  if (g->timing) {
+    const clk::time_point t4 = clk::now();
+    auto us = [](clk::time_point a, clk::time_point b2) { return std::chrono::duration<double, std::micro>(b2 - a).count(); };
+    g->t_prep += us(t0, t1);
+    g->t_enq += us(t1, t2);
+    g->t_wait += us(t2, t3);
+    g->t_unpack += us(t3, t4);
+    g->n_calls++;
+    g->n_cell_ttis += n;
+  }
+  return RS_OK;
+}
+
+int rs_group_get_slice_offset(rs_group* g, int32_t cell, double* offset) {
+  if (!g || !offset) return fail(RS_ERR_INVALID, "null argument");
+  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
+  HIP_TRY(hipSetDevice(g->b->cfg.cell.device));
+  HIP_TRY(hipStreamSynchronize(g->b->stream));
+  HIP_TRY(hipMemcpy(offset, g->b->d_sstate + (size_t)cell * g->b->S, 8 * g->b->S, hipMemcpyDeviceToHost));
+  return RS_OK;
+}
+
+int rs_group_set_slice_offset(rs_group* g, int32_t cell, const double* offset) {
+  if (!g || !offset) return fail(RS_ERR_INVALID, "null argument");
+  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
+  HIP_TRY(hipSetDevice(g->b->cfg.cell.device));
+  HIP_TRY(hipStreamSynchronize(g->b->stream));
+  HIP_TRY(hipMemcpy(g->b->d_sstate + (size_t)cell * g->b->S, offset, 8 * g->b->S, hipMemcpyHostToDevice));
+  return RS_OK;
+}
+
+int64_t rs_group_launch_count(const rs_group* g) { return g ? g->launches : 0; }
+
+const char* rs_group_kernel_name(rs_group* g) { return g ? g->kname : ""; }
 
 /* ---- the reference's CQI trace files (include/radiosaber_hip.h) ---- */
 

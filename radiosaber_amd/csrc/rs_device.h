@@ -344,6 +344,26 @@ struct RsLaunch {
    * RS_PRIO_PERIOD TTIs); a cell whose own count times n_cells is below it is behind the average and runs boosted until the next
    * look.  nullptr: off.  Zeroed by the host before every launch. */
   unsigned long long* prio_sum;
+  /* group calls (rs_group_schedule_tti, rs_group_kernel in rs_kernels.hip): one workgroup per call slot.  Slot k of the input block
+   * starts with an RsGroupCell header, the cell's inputs follow at RS_GROUP_HDR_BYTES in the layout of a single call; slot k of the
+   * output block holds its outputs.  n_cells is the number of slots of the launch.  The fields above that a single call passes as
+   * one pointer (grid, slice ids, averages, hol, prio, gate, per-PRB block, the output rows) only say "given / not given" here --
+   * null or not -- and the workgroup takes the addresses from its slot.  Read by the group kernels alone. */
+  const uint8_t* grp_in;
+  uint8_t* grp_out;
+  int64_t grp_in_stride, grp_out_stride; /* bytes per slot, multiples of 256 */
+  uint32_t* grp_count;       /* device word, 0 between launches: workgroups of this launch that have published their outputs */
+};
+
+/* per-slot header of a group call, written by the host (rs_api.cpp: group_fill_header) */
+#define RS_GROUP_HDR_BYTES 128
+struct RsGroupCell {
+  int32_t cell;              /* whose slice state and scalars this slot schedules */
+  int32_t U, Upad, n_seg, n_items, rand0, rand1; /* what RsLaunch carries for a single call */
+  /* byte offsets of the slot's arrays behind the header (input block) and inside the output slot: the single call's layout for U users */
+  int32_t in_slice, in_avg, in_hol, in_prio, in_gate, in_prb;
+  int32_t out_uinfo, out_map, out_quota, out_target, out_upper;
+  int32_t pad_[RS_GROUP_HDR_BYTES / 4 - 18];
 };
 
 #endif /* RS_DEVICE_H_ */

@@ -30,7 +30,8 @@
  *
  * Template parameters of the cell body: SCHED = the reference's CLI scheduler number (1, 7, 8, 9, 10, 11; 101 = SubOpt, 103 = Vogel),
  * EPT = sort positions per thread (0: state in LDS, any size), FIXED = shape-specialised build, DIRECT = the drop-in
- * entry point's one-TTI form on caller-provided state.  Wave-level building blocks live in rs_wave.h.
+ * entry point's one-TTI form on caller-provided state, GROUP = that form as one workgroup of a group call (rs_group_kernel: K cells
+ * of one host, K workgroups of one launch).  Wave-level building blocks live in rs_wave.h.
  *
  * The same source is compiled three ways: into the library with the cell shape as launch arguments; at run time (hiprtc,
  * rs_jit.cpp) with the shape as compile-time constants (RS_JIT_*); and as the LEAN build of that kernel (RS_JIT_LEAN), in which the
@@ -149,13 +150,15 @@ __device__ __forceinline__ double rs_div_1000(double x) {
                          * context; 2: queue model, bearers' hot words in LDS when they fit; 3: queue model, words in HBM) */
 #endif
 
-template <int SCHED, int EPT, bool FIXED, bool DIRECT, bool QUEUE = false>
+template <int SCHED, int EPT, bool FIXED, bool DIRECT, bool QUEUE = false, bool GROUP = false>
 __device__ __forceinline__ void rs_cell_body(const RsLaunch& p, unsigned char* lds) {
+  static_assert(!GROUP || (DIRECT && !FIXED && !QUEUE && SCHED != 11), "group calls: the built-in one-TTI kernels, scheduler 11 excepted");
   static_assert(!QUEUE || (!DIRECT && (SCHED == 8 || SCHED == 9 || SCHED == 101 || SCHED == 103 || SCHED == 1 || SCHED == 7)),
                 "finite queues: batches of schedulers 1, 7, 8, 9, 101, 103");
   /* schedulers 1 and 7 with queues allocate RBG by RBG on wave 0 (the satisfied-flow break / the m_requiredRBs gate bind) */
   constexpr bool kQSerial = QUEUE && (SCHED == 1 || SCHED == 7);
-  const int cell = blockIdx.x;
+  /* (a group call's workgroup gets a launch block of its own, every per-cell pointer already moved to its cell: rs_group_kernel) */
+  const int cell = GROUP ? 0 : blockIdx.x;
 #ifdef RS_STAMPS
   const unsigned long long stamp_entry = __builtin_readcyclecounter(); /* diagnostic build, one-TTI kernels: the load phase is slot 9, the store phase slot 10 */
 #endif
@@ -750,7 +753,7 @@ __device__ __forceinline__ void rs_cell_body(const RsLaunch& p, unsigned char* l
     scal->rng_f = rng.f;
     scal->rng_b = rng.b;
   }
-  if constexpr (DIRECT) {
+  if constexpr (DIRECT && !GROUP) { /* (a group call completes once, behind its last workgroup: rs_group_kernel) */
     /* rs_schedule_tti's completion word: every thread's outputs are out (system scope) before thread 0 publishes the sequence number */
     if (p.done_flag) {
       __threadfence_system();
@@ -767,6 +770,59 @@ template <int SCHED, int EPT, bool DIRECT, bool QUEUE = false>
 __global__ void __launch_bounds__(512, 4) rs_cell_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
   rs_cell_body<SCHED, EPT, false, DIRECT, QUEUE>(p, lds);
+}
+
+/* One TTI for a group of drop-in cells in one launch (rs_group_schedule_tti): workgroup k serves call slot k.  It reads the slot's
+ * header (which cell, how many users, the rand() pair, where the slot's arrays lie), moves every per-cell pointer of the launch
+ * block to its slot / its cell and runs the one-TTI body on that block -- the phases never learn that other cells exist.
+ * Completion: every thread's outputs are out at system scope (fence), then the workgroup counts itself in on a device word; the
+ * workgroup that brings the count to the number of slots -- the last to finish, whichever it is and whenever the others ran: nothing
+ * here assumes that the workgroups are resident together -- puts the word back to 0 for the next launch and publishes the call's
+ * sequence number to the host.  Its acquire of the counter orders it behind every other workgroup's fence and release. */
+template <int SCHED, int EPT>
+__global__ void __launch_bounds__(512, 4) rs_group_kernel(RsLaunch p) {
+  extern __shared__ __align__(16) unsigned char lds[];
+  const uint8_t* const in = p.grp_in + (size_t)blockIdx.x * (size_t)p.grp_in_stride;
+  uint8_t* const out = p.grp_out + (size_t)blockIdx.x * (size_t)p.grp_out_stride;
+  const RsGroupCell* const h = (const RsGroupCell*)in;
+  /* (one address for the whole workgroup: the values are wave-uniform, and the compiler is told so) */
+  auto word = [](const int32_t* q) { return __builtin_amdgcn_readfirstlane(*q); };
+  const uint8_t* const data = in + RS_GROUP_HDR_BYTES;
+  RsLaunch q = p;
+  const int cell = word(&h->cell);
+  q.U = word(&h->U);
+  q.Upad = word(&h->Upad);
+  q.n_seg = word(&h->n_seg);
+  q.n_items = word(&h->n_items);
+  q.rand0 = word(&h->rand0);
+  q.rand1 = word(&h->rand1);
+  const int in_slice = word(&h->in_slice);
+  q.epochs = data;
+  q.grid_stride = (int64_t)in_slice;
+  q.user_slice = data + in_slice;
+  q.avg = (double*)(data + word(&h->in_avg));
+  q.hol = (const double*)(data + word(&h->in_hol));
+  q.prio = data + word(&h->in_prio);
+  q.gate = p.gate ? (const int32_t*)(data + word(&h->in_gate)) : nullptr;
+  q.prb_cqi = p.prb_cqi ? data + word(&h->in_prb) : nullptr;
+  q.log_tbs = (int32_t*)out;
+  q.log_uinfo = (int32_t*)(out + word(&h->out_uinfo));
+  q.log_map = (int16_t*)(out + word(&h->out_map));
+  q.log_quota = (int16_t*)(out + word(&h->out_quota));
+  q.log_target = (int16_t*)(out + word(&h->out_target));
+  q.log_upper = p.log_upper ? (int32_t*)(out + word(&h->out_upper)) : nullptr;
+  q.slice_state = p.slice_state + (size_t)cell * p.S;
+  q.scal = p.scal + cell;
+  rs_cell_body<SCHED, EPT, false, true, false, true>(q, lds);
+  __threadfence_system();
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t before = __hip_atomic_fetch_add(p.grp_count, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (before + 1u == (uint32_t)p.n_cells) {
+      __hip_atomic_store(p.grp_count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (p.done_flag) __hip_atomic_store(p.done_flag, p.done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
 }
 #else
 #ifndef RS_JIT_DIRECT
@@ -933,6 +989,37 @@ extern "C" hipError_t rs_launch_cells(const RsLaunch* p, int threads, hipStream_
   return hipGetLastError();
 }
 
+/* a group call: p->n_cells call slots, one workgroup each (schedulers 1, 7, 8, 9, 10, 101, 103) */
+extern "C" hipError_t rs_launch_group(const RsLaunch* p, int threads, hipStream_t stream) {
+  dim3 grid(p->n_cells), block(threads);
+  const int ept = (p->R * p->S + threads - 1) / threads;
+#define RS_LAUNCH_GROUP(SCHED_, EPT_) hipLaunchKernelGGL((rs_group_kernel<SCHED_, EPT_>), grid, block, p->lds_bytes, stream, *p)
+  switch (p->sched) {
+    case 1: RS_LAUNCH_GROUP(1, 0); break;
+    case 7: RS_LAUNCH_GROUP(7, 0); break;
+    case 8: RS_LAUNCH_GROUP(8, 0); break;
+    case 101: RS_LAUNCH_GROUP(101, 0); break;
+    case 103: RS_LAUNCH_GROUP(103, 0); break;
+    case 10:
+      if (ept <= 1) RS_LAUNCH_GROUP(10, 1);
+      else if (ept <= 2) RS_LAUNCH_GROUP(10, 2);
+      else if (ept <= 3) RS_LAUNCH_GROUP(10, 3);
+      else if (ept <= 4) RS_LAUNCH_GROUP(10, 4);
+      else return hipErrorInvalidValue;
+      break;
+    case 9:
+      if (ept <= 1) RS_LAUNCH_GROUP(9, 1);
+      else if (ept <= 2) RS_LAUNCH_GROUP(9, 2);
+      else if (ept <= 3) RS_LAUNCH_GROUP(9, 3);
+      else if (ept <= 4) RS_LAUNCH_GROUP(9, 4);
+      else RS_LAUNCH_GROUP(9, 0);
+      break;
+    default: return hipErrorInvalidValue;
+  }
+#undef RS_LAUNCH_GROUP
+  return hipGetLastError();
+}
+
 extern "C" hipError_t rs_prepare_kernels(int max_lds_bytes) {
 #define RS_BOTH(SCHED_, EPT_) (const void*)rs_cell_kernel<SCHED_, EPT_, false>, (const void*)rs_cell_kernel<SCHED_, EPT_, true>
   const void* fns[] = {RS_BOTH(1, 0),  RS_BOTH(7, 0),  RS_BOTH(8, 0),  RS_BOTH(101, 0), RS_BOTH(103, 0), RS_BOTH(11, 0),
@@ -942,7 +1029,12 @@ extern "C" hipError_t rs_prepare_kernels(int max_lds_bytes) {
                        (const void*)rs_cell_kernel<8, 0, false, true>, (const void*)rs_cell_kernel<101, 0, false, true>,
                        (const void*)rs_cell_kernel<103, 0, false, true>, (const void*)rs_cell_kernel<9, 0, false, true>,
                        (const void*)rs_cell_kernel<9, 1, false, true>, (const void*)rs_cell_kernel<9, 2, false, true>,
-                       (const void*)rs_cell_kernel<9, 3, false, true>, (const void*)rs_cell_kernel<9, 4, false, true>};
+                       (const void*)rs_cell_kernel<9, 3, false, true>, (const void*)rs_cell_kernel<9, 4, false, true>,
+                       (const void*)rs_group_kernel<1, 0>,  (const void*)rs_group_kernel<7, 0>,  (const void*)rs_group_kernel<8, 0>,
+                       (const void*)rs_group_kernel<101, 0>, (const void*)rs_group_kernel<103, 0>,
+                       (const void*)rs_group_kernel<10, 1>, (const void*)rs_group_kernel<10, 2>, (const void*)rs_group_kernel<10, 3>,
+                       (const void*)rs_group_kernel<10, 4>, (const void*)rs_group_kernel<9, 0>,  (const void*)rs_group_kernel<9, 1>,
+                       (const void*)rs_group_kernel<9, 2>,  (const void*)rs_group_kernel<9, 3>,  (const void*)rs_group_kernel<9, 4>};
 #undef RS_BOTH
 
   for (const void* f : fns) {

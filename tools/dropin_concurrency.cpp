@@ -8,6 +8,9 @@
  *   dropin_concurrency threads K SHAPE [calls] [epoch|noepoch] [builtin]     K contexts on K host threads of ONE process
  *   dropin_concurrency procs   K SHAPE [calls] [epoch|noepoch] [builtin]     K processes, one context each (fork + exec of this binary
  *                                                                            from a parent that never touches the GPU)
+ *   dropin_concurrency seq     K SHAPE [calls] [epoch|noepoch] [builtin]     K contexts on ONE host thread, called one after the other
+ *   dropin_concurrency group=K   SHAPE [calls]                               K cells of one rs_group on ONE host thread: one
+ *                                                                            rs_group_schedule_tti (one kernel launch) per TTI of all K cells
  *   SHAPE: 500x25 (20 slices x 25 UEs, 25 RBGs of 4 PRBs) | 100x64 (20 x 5 UEs, 64 RBGs of 8: the shipped exp-fix20slices/5ues shape)
  *   further options: think=US (host time between two calls of a worker: the simulator's own work per TTI; default 0 = back to back),
  *                    hwq=N (GPU_MAX_HW_QUEUES=N before the first HIP call: ROCclr maps a process's streams onto 4 hardware queues by default),
@@ -17,7 +20,9 @@
  * see rs_ctx_jit_status), then -- all workers released together -- `calls` timed calls (default 2 000).  The CQI block changes every 40
  * calls (CQI_INTERVAL, enb-mac-entity.cc:38) and `epoch` (default) says so through rs_tti_in.cqi_epoch; the PF averages change on every
  * call.  Output: one line per run with the pooled per-call p50 / p90 / p99 / max in microseconds and the aggregate TTIs/s
- * (K x calls / (last end - first start)).
+ * (K x calls / (last end - first start)) with its reciprocal, the wall time per cell-TTI.  `seq` and `group` time one ROUND (one TTI
+ * of all K cells) per sample.  `group` first checks parity: during the warm-up every cell's answer (RBG map, transport blocks, slice
+ * offsets) is compared with a context of its own that is fed the same inputs (built-in kernels on both sides).
  *
  * Build: g++ -O2 -std=c++17 -pthread -Iinclude tools/dropin_concurrency.cpp -Lradiosaber_amd -lradiosaber_hip \
  *            -Wl,-rpath,'$ORIGIN/../radiosaber_amd' -o tools/dropin_concurrency
@@ -53,7 +58,7 @@ struct Worker {
   Shape sh;
   int calls = 2000, sched = RS_SCHED_MAXCELL, id = 0;
   int think_us = 0; /* host time between two calls (the simulator's own work per TTI): 0 = back to back */
-  bool epoch = true, specialise = true;
+  bool epoch = true, specialise = true, make_ctx = true; /* (make_ctx = false: the inputs and output arrays of a group's cell) */
   std::vector<float> us;      /* per-call latency */
   double t_first = 0, t_last = 0; /* seconds on CLOCK_MONOTONIC (the same clock in every process of the machine) */
   long long checksum = 0;
@@ -77,9 +82,9 @@ struct Worker {
     cfg.n_slices = S; cfg.n_users = U; cfg.n_rbgs = sh.R; cfg.rbg_size = sh.G; cfg.sched = sched; cfg.device = 0;
     cfg.slice_weight = w.data(); cfg.algo_alpha = zero.data(); cfg.algo_beta = zero.data();
     cfg.algo_epsilon = one.data(); cfg.algo_psi = one.data(); cfg.user_to_slice = u2s.data();
-    c = RS_CREATE(&cfg);
-    if (!c) { error = std::string("rs_create: ") + rs_last_error(); return false; }
-    if (specialise && rs_ctx_specialize(c) != RS_OK) { error = std::string("rs_ctx_specialize: ") + rs_last_error(); return false; }
+    if (make_ctx) c = RS_CREATE(&cfg);
+    if (make_ctx && !c) { error = std::string("rs_create: ") + rs_last_error(); return false; }
+    if (make_ctx && specialise && rs_ctx_specialize(c) != RS_OK) { error = std::string("rs_ctx_specialize: ") + rs_last_error(); return false; }
     g.seed(1000 + id);
     cqi.resize((size_t)U * sh.R); avg.resize(U);
     grids.resize(4 * cqi.size());
@@ -91,7 +96,7 @@ struct Worker {
     out.user_mcs = mcs.data(); out.target_rbs = tgt.data(); out.quota_rbgs = quo.data();
     return true;
   }
-  bool one_call() {
+  void next_inputs() {
     if (n_done % 40 == 0) { /* new reports: the caller's block changes, as a UE's GetCqiFeedbacks() vector does every CQI_INTERVAL */
       memcpy(cqi.data(), grids.data() + (size_t)((n_done / 40) % 4) * cqi.size(), cqi.size());
       ++ep;
@@ -99,6 +104,9 @@ struct Worker {
     in.cqi_epoch = epoch ? ep : 0;
     in.rand0 = (int)(g() >> 1); in.rand1 = (int)(g() >> 1);
     avg[n_done % avg.size()] += 1000;
+  }
+  bool one_call() {
+    next_inputs();
     if (rs_schedule_tti(c, &in, &out) != RS_OK) { error = std::string("rs_schedule_tti: ") + rs_last_error(); return false; }
     checksum += map[0] + tbs[map[0] < 0 ? 0 : map[0]];
     ++n_done;
@@ -135,7 +143,7 @@ struct Worker {
 };
 
 void report(const char* mode, int K, const char* shape, const Worker& proto, std::vector<float>& all, double first, double last, long long checksum,
-            const std::string& status) {
+            const std::string& status, int cells_per_sample = 1) {
   std::sort(all.begin(), all.end());
   auto pct = [&](double p) { return all.empty() ? 0.f : all[std::min(all.size() - 1, (size_t)(p * all.size()))]; };
   double mean = 0;
@@ -144,9 +152,10 @@ void report(const char* mode, int K, const char* shape, const Worker& proto, std
   char extra[96] = "";
   if (proto.think_us) snprintf(extra, sizeof extra, " think=%dus", proto.think_us);
   if (const char* q = getenv("GPU_MAX_HW_QUEUES")) snprintf(extra + strlen(extra), sizeof extra - strlen(extra), " GPU_MAX_HW_QUEUES=%s", q);
-  printf("%s K=%d %s %s %s%s calls=%d: per call p50 %.1f us, p90 %.1f, p99 %.1f, max %.1f, mean %.1f; aggregate %.0f TTIs/s over %.1f ms (checksum %lld; worker 0: %s)\n",
+  const double cell_ttis = (double)all.size() * cells_per_sample;
+  printf("%s K=%d %s %s %s%s calls=%d: per call p50 %.1f us, p90 %.1f, p99 %.1f, max %.1f, mean %.1f; aggregate %.0f TTIs/s over %.1f ms, %.2f us per cell-TTI (checksum %lld; worker 0: %s)\n",
          mode, K, shape, proto.specialise ? "specialised" : "built-in", proto.epoch ? "cqi_epoch" : "no-epoch", extra, proto.calls, pct(0.5), pct(0.9), pct(0.99),
-         all.empty() ? 0.f : all.back(), mean, all.size() / (last - first), (last - first) * 1e3, checksum, status.c_str());
+         all.empty() ? 0.f : all.back(), mean, cell_ttis / (last - first), (last - first) * 1e3, (last - first) * 1e6 / (cell_ttis > 0 ? cell_ttis : 1), checksum, status.c_str());
   fflush(stdout);
 }
 
@@ -179,6 +188,96 @@ int run_threads(int K, const char* shape, const Worker& proto) {
   long long sum = 0;
   for (auto& w : ws) { all.insert(all.end(), w.us.begin(), w.us.end()); first = std::min(first, w.t_first); last = std::max(last, w.t_last); sum += w.checksum; }
   report("threads", K, shape, proto, all, first, last, sum, ws[0].status);
+  return 0;
+}
+
+double now_sec() { return std::chrono::duration<double>(clk::now().time_since_epoch()).count(); }
+
+/* K contexts on one host thread, one call each per round: what a multi-cell host does today */
+int run_seq(int K, const char* shape, const Worker& proto) {
+  std::vector<Worker> ws(K, proto);
+  for (int i = 0; i < K; i++) {
+    ws[i].id = i;
+    if (!ws[i].setup() || !ws[i].warm()) { fprintf(stderr, "worker %d: %s\n", i, ws[i].error.c_str()); return 1; }
+  }
+  std::vector<float> all(proto.calls);
+  long long sum = 0;
+  const double first = now_sec();
+  clk::time_point t0 = clk::now();
+  for (int it = 0; it < proto.calls; it++) {
+    for (auto& w : ws)
+      if (!w.one_call()) { fprintf(stderr, "worker %d: %s\n", w.id, w.error.c_str()); return 1; }
+    const clk::time_point t1 = clk::now();
+    all[it] = std::chrono::duration<float, std::micro>(t1 - t0).count();
+    t0 = t1;
+  }
+  const double last = now_sec();
+  for (auto& w : ws) { sum += w.checksum; w.close(); }
+  report("seq", K, shape, proto, all, first, last, sum, ws[0].status, K);
+  return 0;
+}
+
+/* K cells of one rs_group on one host thread: one rs_group_schedule_tti per round */
+int run_group(int K, const char* shape, Worker proto) {
+  proto.make_ctx = false;
+  proto.specialise = false; /* (a group runs the kernels built into the library) */
+  proto.epoch = false;      /* (cqi_epoch is accepted and ignored by a group) */
+  std::vector<Worker> ws(K, proto), twins(K, proto);
+  std::vector<rs_tti_in> ins(K);
+  std::vector<rs_tti_out> outs(K);
+  for (int i = 0; i < K; i++) {
+    ws[i].id = twins[i].id = i;
+    twins[i].make_ctx = true;
+    if (!ws[i].setup() || !twins[i].setup()) { fprintf(stderr, "cell %d: %s%s\n", i, ws[i].error.c_str(), twins[i].error.c_str()); return 1; }
+  }
+  const int S = 20;
+  std::vector<int32_t> u2s = ws[0].u2s;
+  rs_config cfg{};
+  cfg.n_slices = S; cfg.n_users = (int)u2s.size(); cfg.n_rbgs = proto.sh.R; cfg.rbg_size = proto.sh.G; cfg.sched = proto.sched; cfg.device = 0;
+  cfg.slice_weight = ws[0].w.data(); cfg.algo_alpha = ws[0].zero.data(); cfg.algo_beta = ws[0].zero.data();
+  cfg.algo_epsilon = ws[0].one.data(); cfg.algo_psi = ws[0].one.data(); cfg.user_to_slice = u2s.data();
+  rs_group* g = RS_GROUP_CREATE(&cfg, K);
+  if (!g) { fprintf(stderr, "rs_group_create: %s\n", rs_last_error()); return 1; }
+  auto round = [&]() {
+    for (int i = 0; i < K; i++) { ws[i].next_inputs(); ins[i] = ws[i].in; outs[i] = ws[i].out; }
+    if (rs_group_schedule_tti(g, K, nullptr, ins.data(), outs.data()) != RS_OK) { fprintf(stderr, "rs_group_schedule_tti: %s\n", rs_last_error()); return false; }
+    for (auto& w : ws) { w.checksum += w.map[0] + w.tbs[w.map[0] < 0 ? 0 : w.map[0]]; ++w.n_done; }
+    return true;
+  };
+  /* warm-up = parity: every cell against a context of its own on the same inputs */
+  std::vector<double> so_g(S), so_c(S);
+  for (int it = 0; it < 60; it++) {
+    if (!round()) return 1;
+    for (int i = 0; i < K; i++) {
+      if (!twins[i].one_call()) { fprintf(stderr, "twin %d: %s\n", i, twins[i].error.c_str()); return 1; }
+      const bool same = ws[i].map == twins[i].map && ws[i].tbs == twins[i].tbs && ws[i].nprb == twins[i].nprb && ws[i].fcqi == twins[i].fcqi &&
+                        ws[i].mcs == twins[i].mcs && ws[i].tgt == twins[i].tgt && ws[i].quo == twins[i].quo;
+      if (!same) { fprintf(stderr, "PARITY: round %d cell %d differs from its own context\n", it, i); return 1; }
+    }
+  }
+  for (int i = 0; i < K; i++) {
+    if (rs_group_get_slice_offset(g, i, so_g.data()) != RS_OK || rs_get_slice_offset(twins[i].c, so_c.data()) != RS_OK ||
+        memcmp(so_g.data(), so_c.data(), 8 * S) != 0) { fprintf(stderr, "PARITY: cell %d: slice offsets differ from its own context\n", i); return 1; }
+    twins[i].close();
+  }
+  std::vector<float> all(proto.calls);
+  const long long launches0 = rs_group_launch_count(g);
+  const double first = now_sec();
+  clk::time_point t0 = clk::now();
+  for (int it = 0; it < proto.calls; it++) {
+    if (!round()) return 1;
+    const clk::time_point t1 = clk::now();
+    all[it] = std::chrono::duration<float, std::micro>(t1 - t0).count();
+    t0 = t1;
+  }
+  const double last = now_sec();
+  long long sum = 0;
+  for (auto& w : ws) sum += w.checksum;
+  char status[160];
+  snprintf(status, sizeof status, "%s, %lld launches for %d calls, parity with %d contexts over 60 rounds ok", rs_group_kernel_name(g),
+           (long long)rs_group_launch_count(g) - launches0, proto.calls, K);
+  rs_group_destroy(g);
+  report("group", K, shape, proto, all, first, last, sum, status, K);
   return 0;
 }
 
@@ -253,7 +352,20 @@ int run_procs(int K, const char* shape, const Worker& proto, char** argv_tail, i
 }  // namespace
 
 int main(int argc, char** argv) {
-  if (argc < 4) { fprintf(stderr, "usage: %s threads|procs K 500x25|100x64|500x64 [calls] [epoch|noepoch] [builtin] [sched=N]\n", argv[0]); return 2; }
+  const bool group_mode = argc >= 2 && !strncmp(argv[1], "group=", 6);
+  if (argc < (group_mode ? 3 : 4)) {
+    fprintf(stderr, "usage: %s threads|procs|seq K 500x25|100x64|500x64 [calls] [epoch|noepoch] [builtin] [sched=N]\n       %s group=K 500x25|100x64|500x64 [calls] [sched=N]\n", argv[0], argv[0]);
+    return 2;
+  }
+  if (group_mode) { /* group=K SHAPE ...: the same argument positions as the other modes from here on */
+    static char* shifted[64];
+    static char kbuf[16];
+    snprintf(kbuf, sizeof kbuf, "%d", atoi(argv[1] + 6));
+    int n = 0;
+    shifted[n++] = argv[0]; shifted[n++] = (char*)"group"; shifted[n++] = kbuf;
+    for (int i = 2; i < argc && n < 63; i++) shifted[n++] = argv[i];
+    argv = shifted; argc = n;
+  }
   const std::string mode = argv[1];
   const int K = atoi(argv[2]);
   Worker proto;
@@ -270,6 +382,8 @@ int main(int argc, char** argv) {
   }
   if (mode == "worker") return run_worker(K /* = id */, argv[3], proto);
   if (K < 1 || K > 256) { fprintf(stderr, "K = %d?\n", K); return 2; }
+  if (mode == "seq") return run_seq(K, argv[3], proto);
+  if (mode == "group") return run_group(K, argv[3], proto);
   if (mode == "threads") return run_threads(K, argv[3], proto);
   if (mode == "procs") return run_procs(K, argv[3], proto, argv + 3, argc - 3);
   fprintf(stderr, "unknown mode %s\n", mode.c_str());
