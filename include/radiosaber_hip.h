@@ -27,7 +27,7 @@ extern "C" {
 
 #define RS_ABI_VERSION 11 /* 11: (additions, no layout changed) rs_batch_flow_record (flow completion times of the queue model),
                                rs_batch_bearer_log + rs_batch_run_logged_bearers (per-bearer DoStopSchedule rows),
-                               rs_group_* (one TTI of several drop-in cells in one launch);
+                               rs_group_* (one TTI of several drop-in cells in one launch), rs_group_image_stats (cqi_epoch per cell of a group);
                                rs_config.link_tables (RS_LINK_*) + rs_link_tables_pinned / rs_link_tables_compare, rs_tti_in.cqi_epoch (the context keeps the
                                CQI image of an unchanged report set on the device), rs_ctx_jit_status (a specialised context checks its run-time build against the
                                built-in kernel during its first calls), rs_batch_config.selfcheck -1 / 0 / 1 with run-time builds verified by default and the
@@ -202,8 +202,9 @@ typedef struct rs_tti_in {
                                refreshes a UE's CQI every 40 TTIs (src/protocolStack/mac/enb-mac-entity.cc:38 CQI_INTERVAL,
                                src/device/CqiManager/cqi-manager.cpp:115), so 39 calls of 40 see the grid of the call before.  A call
                                whose cqi_epoch, n_users and user_id list equal the previous call's does not touch the caller's block:
-                               the kernel reads the image the context kept on the device (the grid in the layout of its LDS, HBM-resident)
-                               instead of n * R bytes over the host link, and the host skips the range check and the copy.  (ABI 11) */
+                               the kernel reads the image the context -- or, in a group call, the CELL -- kept on the device (the grid in the
+                               layout of its LDS, HBM-resident) instead of n * R bytes over the host link, and the host skips the range
+                               check and the copy.  (ABI 11) */
 } rs_tti_in;
 
 /* What RBsAllocation() leaves behind (ref: :589-620 allocation lists + slice_rbs_offset_,
@@ -273,7 +274,16 @@ int rs_set_slice_offset(rs_ctx* ctx, const double* offset /* [S] */);
  *     the kernel.
  *   - The exact FP64 scan that rs_schedule_tti uses when an average or a HoL delay lies outside the FP32 filter's safe range is
  *     decided per call: if any cell of the call needs it, every cell of the call uses it (same results: DESIGN.md 2.6).
- *   - cqi_epoch is accepted and ignored: a group takes every grid from the caller's block on every call.
+ *   - cqi_epoch is honoured per CELL and per call, as by an rs_ctx of the cell's own: every cell keeps the CQI image of its last call
+ *     under a non-zero number on the device (and a device copy of the per-PRB block when that call gave cqi_prb).  A cell whose call
+ *     carries the number, n_users, user_id list (or both NULL) and kind of report (cqi / cqi_prb) of its image is served from it: the
+ *     caller's block is neither range-checked, copied nor read.  Any other non-zero number: the block is read and the image replaced.
+ *     0: the block is read and the cell's image ends.  The image belongs to the cell, not to the call slot: cell_ids may
+ *     map cells to other slots on every call, cells that a call does not name keep theirs, and the cells of one call may differ in
+ *     what they do.  A rejected call leaves every image as it was; a call that fails with RS_ERR_HIP ends the images of the cells it
+ *     named.  RS_GROUP_IMAGE=0 in the environment of rs_group_create: every cqi_epoch counts as 0 (every block read on every call).
+ *     If the per-PRB store cannot be allocated (first cqi_prb call under a number), that call still returns RS_OK, says so once
+ *     through rs_last_error(), and the group serves cqi_prb calls as if cqi_epoch were 0 from then on.
  *   - Every scheduler rs_create accepts except RS_SCHED_NVS_NONGREEDY; general integer exponents and synthetic_exp are supported
  *     (they belong to the config, so they are the same for the whole group).
  *   - Only the kernels built into the library serve a group (no run-time specialisation): a shape they cannot run is rejected by
@@ -293,6 +303,9 @@ int rs_group_get_slice_offset(rs_group* g, int32_t cell, double* offset /* [S] *
 int rs_group_set_slice_offset(rs_group* g, int32_t cell, const double* offset /* [S] */);
 /* scheduling kernels launched so far: one per successful rs_group_schedule_tti, none for a rejected one (tests, tools) */
 int64_t rs_group_launch_count(const rs_group* g);
+/* cell-TTIs of the successful calls so far: out[0] served from the cell's image (the caller's block not read), out[1] that read the
+ * block and stored an image (non-zero cqi_epoch, no match), out[2] without a promise (cqi_epoch 0, or RS_GROUP_IMAGE=0) */
+int rs_group_image_stats(const rs_group* g, int64_t out[3]);
 const char* rs_group_kernel_name(rs_group* g);
 
 /* ------------------------------------------------------------------------------------------

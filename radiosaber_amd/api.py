@@ -109,6 +109,7 @@ ABI_SYMBOLS = [
     "rs_batch_flow_record", "rs_batch_run_logged_bearers",
     "rs_group_create", "rs_group_create_checked", "rs_group_destroy", "rs_group_schedule_tti",
     "rs_group_get_slice_offset", "rs_group_set_slice_offset", "rs_group_launch_count", "rs_group_kernel_name",
+    "rs_group_image_stats",
 ]
 
 _lib = None
@@ -146,6 +147,7 @@ def lib():
     L.rs_group_set_slice_offset.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double)]
     L.rs_group_launch_count.restype = C.c_int64
     L.rs_group_launch_count.argtypes = [C.c_void_p]
+    L.rs_group_image_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.rs_group_kernel_name.restype = C.c_char_p
     L.rs_group_kernel_name.argtypes = [C.c_void_p]
     L.rs_batch_create.restype = C.c_void_p
@@ -612,7 +614,8 @@ class GroupScheduler:
 
     def schedule_tti(self, calls: Sequence[dict], cell_ids: Optional[Sequence[int]] = None) -> List[TtiResult]:
         """calls[k]: the keyword arguments of TtiScheduler.schedule_tti for cell cell_ids[k] (None: cell k).  Optional inputs are
-        given by every cell of a call or by none (a mixed call raises, nothing is launched)."""
+        given by every cell of a call or by none (a mixed call raises, nothing is launched).  cqi_epoch counts per cell: a cell whose
+        call repeats the number, users and kind of report of its last stored call is served from its device-resident image."""
         n = len(calls)
         ins, outs, results, keep = (_TtiIn * n)(), (_TtiOut * n)(), [], []
         for k, kw in enumerate(calls):
@@ -641,6 +644,14 @@ class GroupScheduler:
     def launch_count(self):
         """scheduling kernels launched so far: one per successful schedule_tti"""
         return int(lib().rs_group_launch_count(self._h))
+
+    @property
+    def image_stats(self):
+        """(cell-TTIs served from the cell's device-resident CQI image, cell-TTIs that stored one, cell-TTIs without a cqi_epoch) of
+        the successful calls so far (rs_group_image_stats)"""
+        out = np.zeros(3, np.int64)
+        _check(lib().rs_group_image_stats(self._h, _p(out, C.c_int64)))
+        return tuple(int(x) for x in out)
 
     @property
     def kernel_name(self):

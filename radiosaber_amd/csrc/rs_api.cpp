@@ -2396,6 +2396,23 @@ struct rs_group {
   int64_t launches = 0;
   std::vector<uint8_t> named; /* cell_ids check: which cells this call has named so far */
   std::vector<TtiPack> packs;
+  /* rs_tti_in.cqi_epoch, per CELL (not per call slot): the grid of the cell's last call under a non-zero number, kept on the device as
+   * the LDS image ([R][Upad of that call's n], d_img: [n_cells][img_stride]), its per-PRB block beside it when that call gave one
+   * (d_prb: [n_cells][prb_stride], allocated by the first call that needs it), and the record that decides whether a later call may
+   * be served from them -- rs_ctx's rules (rs_schedule_tti).  A record changes only after its launch has completed.
+   * RS_GROUP_IMAGE=0 (read at create): every cqi_epoch counts as 0. */
+  struct CellImage {
+    bool valid = false, prb = false, has_ids = false;
+    uint64_t epoch = 0;
+    int n = 0;
+    std::vector<int32_t> ids;
+  };
+  bool image_on = true, prb_store_failed = false;
+  uint8_t *d_img = nullptr, *d_prb = nullptr;
+  size_t img_stride = 0, prb_stride = 0;
+  std::vector<CellImage> img;
+  std::vector<uint8_t> modes;  /* per call slot: RsGroupCell::image_mode of the call being served */
+  int64_t n_reused = 0, n_stored = 0, n_plain = 0; /* cell-TTIs of successful calls in mode 2 / 1 / 0 (rs_group_image_stats) */
   /* RS_DROPIN_TIMING=1: the host-side split of the calls, printed by rs_group_destroy */
   bool timing = false;
   double t_prep = 0, t_enq = 0, t_wait = 0, t_unpack = 0;
@@ -2442,8 +2459,11 @@ rs_group* rs_group_create(const rs_config* cfg, int32_t n_cells) {
   g->out_stride = round_up((int)l.out_total, 256);
   g->flag_off = g->out_stride * (size_t)n_cells;
   const size_t in_bytes = g->in_stride * (size_t)n_cells, out_bytes = g->flag_off + 64;
+  g->img_stride = round_up(rs_upad_of(b->U) * b->R, 16);
+  g->prb_stride = round_up(b->U * b->R * b->G, 16);
   const bool ok = hipMalloc(&g->d_in, in_bytes) == hipSuccess && hipMalloc(&g->d_out, out_bytes) == hipSuccess &&
                   hipMalloc(&g->d_count, 64) == hipSuccess && hipMemset(g->d_count, 0, 64) == hipSuccess &&
+                  hipMalloc(&g->d_img, g->img_stride * (size_t)n_cells) == hipSuccess &&
                   hipHostMalloc((void**)&g->h_in, in_bytes, hipHostMallocMapped) == hipSuccess &&
                   hipHostMalloc((void**)&g->h_out, out_bytes, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
   if (!ok) { fail(RS_ERR_HIP, "allocation of the group's staging blocks failed (%zu + %zu bytes)", in_bytes, out_bytes); rs_group_destroy(g); return nullptr; }
@@ -2464,6 +2484,10 @@ rs_group* rs_group_create(const rs_config* cfg, int32_t n_cells) {
   if (const char* pu = getenv("RS_DROPIN_POLL_US")) g->poll_us = atol(pu) > 0 ? atol(pu) : 2000;
   g->named.assign(n_cells, 0);
   g->packs.resize(n_cells);
+  const char* im = getenv("RS_GROUP_IMAGE");
+  g->image_on = !(im && im[0] == '0');
+  g->img.resize(n_cells);
+  g->modes.assign(n_cells, 0);
   const int ept = (b->R * b->S + b->threads - 1) / b->threads;
   const bool sorts = b->sched == RS_SCHED_MAXCELL || b->sched == RS_SCHED_UPPERBOUND;
   snprintf(g->kname, sizeof g->kname, "rs_group_kernel<%d, %d>", b->sched, sorts && ept <= 4 ? ept : 0);
@@ -2474,13 +2498,15 @@ rs_group* rs_group_create(const rs_config* cfg, int32_t n_cells) {
 void rs_group_destroy(rs_group* g) {
   if (!g) return;
   if (g->timing && g->n_calls)
-    fprintf(stderr, "rs_group_schedule_tti x %ld (%.1f cells per call): prepare %.2f us, enqueue %.2f us, wait %.2f us, unpack %.2f us per call (%ld completed by the polled word, %ld by the stream)\n",
+    fprintf(stderr, "rs_group_schedule_tti x %ld (%.1f cells per call): prepare %.2f us, enqueue %.2f us, wait %.2f us, unpack %.2f us per call (%ld completed by the polled word, %ld by the stream; cell-TTIs served from the cell's CQI image %lld, that stored one %lld, without a cqi_epoch %lld)\n",
             g->n_calls, (double)g->n_cell_ttis / g->n_calls, g->t_prep / g->n_calls, g->t_enq / g->n_calls, g->t_wait / g->n_calls,
-            g->t_unpack / g->n_calls, g->n_polled, g->n_fallback);
+            g->t_unpack / g->n_calls, g->n_polled, g->n_fallback, (long long)g->n_reused, (long long)g->n_stored, (long long)g->n_plain);
   if (g->b && g->b->stream) (void)hipStreamSynchronize(g->b->stream);
   if (g->d_in) (void)hipFree(g->d_in);
   if (g->d_out) (void)hipFree(g->d_out);
   if (g->d_count) (void)hipFree(g->d_count);
+  if (g->d_img) (void)hipFree(g->d_img);
+  if (g->d_prb) (void)hipFree(g->d_prb);
   if (g->h_in) (void)hipHostFree(g->h_in);
   if (g->h_out) (void)hipHostFree(g->h_out);
   rs_batch_destroy(g->b);
@@ -2525,18 +2551,28 @@ int rs_group_schedule_tti(rs_group* g, int32_t n, const int32_t* cell_ids, const
     uint8_t* const slot = g->h_in + (size_t)k * g->in_stride;
     TtiPack& pk = g->packs[k];
     pk = TtiPack();
-    const int rc = pack_tti(b, &in[k], &out[k], slot + RS_GROUP_HDR_BYTES, false, &pk);
+    /* rs_tti_in.cqi_epoch, decided per cell as a context of its own would (rs_schedule_tti): the number, the user count, the user list
+     * and the kind of report of the cell's valid image -- then the caller's block is neither checked, copied nor read */
+    const int cell = cell_ids ? cell_ids[k] : k;
+    const rs_group::CellImage& im = g->img[cell];
+    const uint64_t epoch = (g->image_on && !(has_prb && g->prb_store_failed)) ? in[k].cqi_epoch : 0;
+    const bool reuse_grid = epoch != 0 && im.valid && im.epoch == epoch && im.n == in[k].n_users && im.prb == has_prb &&
+                            im.has_ids == (in[k].user_id != nullptr) &&
+                            (!in[k].user_id || memcmp(im.ids.data(), in[k].user_id, 4 * (size_t)im.n) == 0);
+    g->modes[k] = (uint8_t)(epoch == 0 ? 0 : (reuse_grid ? 2 : 1));
+    const int rc = pack_tti(b, &in[k], &out[k], slot + RS_GROUP_HDR_BYTES, reuse_grid, &pk);
     if (rc) {
       char msg[sizeof g_err];
       snprintf(msg, sizeof msg, "%s", g_err);
-      return fail(rc, "cell slot %d (cell %d): %.400s", k, cell_ids ? cell_ids[k] : k, msg);
+      return fail(rc, "cell slot %d (cell %d): %.400s", k, cell, msg);
     }
     exact_scan |= pk.exact_scan; /* decided per call: one cell outside the FP32 filter's range, the exact scan for all (same results) */
     const CtxLayout& l = pk.l;
     const int nu = in[k].n_users;
     RsGroupCell h;
     memset(&h, 0, sizeof h);
-    h.cell = cell_ids ? cell_ids[k] : k;
+    h.cell = cell;
+    h.image_mode = g->modes[k];
     h.U = nu;
     h.Upad = upad_of(nu);
     h.n_seg = b->base.n_seg;
@@ -2550,9 +2586,34 @@ int rs_group_schedule_tti(rs_group* g, int32_t n, const int32_t* cell_ids, const
     h.out_upper = (int32_t)l.upper;
     memcpy(slot, &h, sizeof h);
   }
+  /* the per-PRB store comes with the first call that gives per-PRB reports under a number.  (Until it exists no record says "per-PRB",
+   * so such a call holds no reuse slot yet.)  Without it those calls are served as if they made no promise: same results. */
+  bool store_failed_now = false;
+  if (has_prb && !g->d_prb && !g->prb_store_failed) {
+    bool wanted = false;
+    for (int k = 0; k < n; k++) wanted |= g->modes[k] != 0;
+    if (wanted && hipMalloc(&g->d_prb, g->prb_stride * (size_t)g->n_cells) != hipSuccess) {
+      (void)hipGetLastError();
+      g->d_prb = nullptr;
+      g->prb_store_failed = store_failed_now = true;
+    }
+  }
+  if (has_prb && !g->d_prb)
+    for (int k = 0; k < n; k++) {
+      g->modes[k] = 0;
+      ((RsGroupCell*)(g->h_in + (size_t)k * g->in_stride))->image_mode = 0;
+    }
+  /* from here on the device is touched: a failure leaves the named cells' images in an unknown state */
+  struct ImageGuard {
+    rs_group* g; int n; const int32_t* ids; bool ok;
+    ~ImageGuard() {
+      if (!ok) for (int k = 0; k < n; k++) g->img[ids ? ids[k] : k].valid = false;
+    }
+  } guard{g, n, cell_ids, false};
   hipStream_t st = b->stream;
   const clk::time_point t1 = g->timing ? clk::now() : clk::time_point();
-  /* per-PRB reports and queue state are read again and again inside the TTI: those calls keep the device copies */
+  /* per-PRB reports and queue state are read again and again inside the TTI: those calls keep the device copies.  (The copy sends
+   * whole slots: a reuse slot's grid area and per-PRB block travel stale and are not read.) */
   const bool zc = g->z_in != nullptr && !has_prb && !b->any_alpha;
   uint8_t* const dev_in = zc ? g->z_in : g->d_in;
   uint8_t* const dev_out = zc ? g->z_out : g->d_out;
@@ -2564,8 +2625,12 @@ int rs_group_schedule_tti(rs_group* g, int32_t n, const int32_t* cell_ids, const
   L.cqi_mode = RS_CQI_EPOCHS;
   L.refresh = 1;
   L.n_epochs = 1;
-  L.image_mode = 0; /* (cqi_epoch: accepted and ignored) */
+  L.image_mode = 0; /* (per slot: RsGroupCell::image_mode) */
   L.grid_image = nullptr;
+  L.grp_image = g->d_img;
+  L.grp_image_stride = (int64_t)g->img_stride;
+  L.grp_prb = g->d_prb;
+  L.grp_prb_stride = (int64_t)g->prb_stride;
   L.queue_mode = b->any_alpha ? 1 : 0;
   L.exact_scan = exact_scan ? 1 : 0;
   L.gen_exp = b->gen_exp ? 1 : 0;
@@ -2608,7 +2673,22 @@ int rs_group_schedule_tti(rs_group* g, int32_t n, const int32_t* cell_ids, const
     g->n_fallback++;
     HIP_TRY(hipStreamSynchronize(st));
   }
+  guard.ok = true;
   const clk::time_point t3 = g->timing ? clk::now() : clk::time_point();
+  /* the launch has completed: the device holds these calls' reports now */
+  for (int k = 0; k < n; k++) {
+    const int mode = g->modes[k];
+    rs_group::CellImage& im = g->img[cell_ids ? cell_ids[k] : k];
+    if (mode == 0) { g->n_plain++; im.valid = false; continue; } /* (as a context: a call without a number ends the image's term) */
+    if (mode == 2) { g->n_reused++; continue; }
+    g->n_stored++;
+    im.valid = true;
+    im.epoch = in[k].cqi_epoch;
+    im.n = in[k].n_users;
+    im.prb = has_prb;
+    im.has_ids = in[k].user_id != nullptr;
+    if (in[k].user_id) im.ids.assign(in[k].user_id, in[k].user_id + in[k].n_users);
+  }
   for (int k = 0; k < n; k++) unpack_tti(b, &in[k], &out[k], g->h_out + (size_t)k * g->out_stride, g->packs[k].l, want_upper);
   if (g->timing) {
     const clk::time_point t4 = clk::now();
@@ -2620,6 +2700,9 @@ int rs_group_schedule_tti(rs_group* g, int32_t n, const int32_t* cell_ids, const
     g->n_calls++;
     g->n_cell_ttis += n;
   }
+  if (store_failed_now)
+    snprintf(g_err, sizeof g_err, "note: the group's per-PRB report store (%zu bytes) could not be allocated: calls with cqi_prb are served as if "
+             "cqi_epoch were 0 from now on (same results, the block is sent on every call)", g->prb_stride * (size_t)g->n_cells);
   return RS_OK;
 }
 
@@ -2642,6 +2725,14 @@ int rs_group_set_slice_offset(rs_group* g, int32_t cell, const double* offset) {
 }
 
 int64_t rs_group_launch_count(const rs_group* g) { return g ? g->launches : 0; }
+
+int rs_group_image_stats(const rs_group* g, int64_t out[3]) {
+  if (!g || !out) return fail(RS_ERR_INVALID, "null argument");
+  out[0] = g->n_reused;
+  out[1] = g->n_stored;
+  out[2] = g->n_plain;
+  return RS_OK;
+}
 
 const char* rs_group_kernel_name(rs_group* g) { return g ? g->kname : ""; }
 

@@ -353,6 +353,13 @@ struct RsLaunch {
   uint8_t* grp_out;
   int64_t grp_in_stride, grp_out_stride; /* bytes per slot, multiples of 256 */
   uint32_t* grp_count;       /* device word, 0 between launches: workgroups of this launch that have published their outputs */
+  /* group calls, rs_tti_in.cqi_epoch: every CELL of the group has a CQI image of its own ([R][Upad] like grid_image above, one stride apart
+   * whatever slot serves the cell) and, once a call has given per-PRB reports under a number, a device copy of its per-PRB block.  The
+   * slot header's image_mode says per slot what the workgroup does with them (RsGroupCell); image_mode / grid_image above are not read. */
+  uint8_t* grp_image;        /* [group cells][grp_image_stride] */
+  int64_t grp_image_stride;  /* round_up(rs_upad_of(U) * R, 16) of the config's U */
+  uint8_t* grp_prb;          /* [group cells][grp_prb_stride]: [n][R*G] of the cell's last stored reports; null until first needed */
+  int64_t grp_prb_stride;    /* round_up(U * R * G, 16) */
 };
 
 /* per-slot header of a group call, written by the host (rs_api.cpp: group_fill_header) */
@@ -363,7 +370,12 @@ struct RsGroupCell {
   /* byte offsets of the slot's arrays behind the header (input block) and inside the output slot: the single call's layout for U users */
   int32_t in_slice, in_avg, in_hol, in_prio, in_gate, in_prb;
   int32_t out_uinfo, out_map, out_quota, out_target, out_upper;
-  int32_t pad_[RS_GROUP_HDR_BYTES / 4 - 18];
+  /* rs_tti_in.cqi_epoch of this slot, the single call's RsLaunch::image_mode: 0 read the slot's grid; 1 read it and leave the LDS grid
+   * behind as the cell's image (per-PRB reports: copy the slot's block to the cell's store too); 2 the slot's grid area (and per-PRB
+   * block) is stale -- load the cell's image, link adaptation reads the cell's per-PRB store */
+  int32_t image_mode;
+  int32_t pad_[RS_GROUP_HDR_BYTES / 4 - 19];
 };
+static_assert(sizeof(RsGroupCell) == RS_GROUP_HDR_BYTES, "the slot header keeps its size: new words come out of its padding");
 
 #endif /* RS_DEVICE_H_ */

@@ -773,8 +773,8 @@ __global__ void __launch_bounds__(512, 4) rs_cell_kernel(RsLaunch p) {
 }
 
 /* One TTI for a group of drop-in cells in one launch (rs_group_schedule_tti): workgroup k serves call slot k.  It reads the slot's
- * header (which cell, how many users, the rand() pair, where the slot's arrays lie), moves every per-cell pointer of the launch
- * block to its slot / its cell and runs the one-TTI body on that block -- the phases never learn that other cells exist.
+ * header (which cell, how many users, the rand() pair, where the slot's arrays lie, what to do with the cell's CQI image), moves every
+ * per-cell pointer of the launch block to its slot / its cell and runs the one-TTI body on that block -- the phases never learn that other cells exist.
  * Completion: every thread's outputs are out at system scope (fence), then the workgroup counts itself in on a device word; the
  * workgroup that brings the count to the number of slots -- the last to finish, whichever it is and whenever the others ran: nothing
  * here assumes that the workgroups are resident together -- puts the word back to 0 for the next launch and publishes the call's
@@ -813,6 +813,22 @@ __global__ void __launch_bounds__(512, 4) rs_group_kernel(RsLaunch p) {
   q.log_upper = p.log_upper ? (int32_t*)(out + word(&h->out_upper)) : nullptr;
   q.slice_state = p.slice_state + (size_t)cell * p.S;
   q.scal = p.scal + cell;
+  /* rs_tti_in.cqi_epoch, per slot: the image belongs to the CELL (the slot that serves it changes from call to call) */
+  const int mode = word(&h->image_mode);
+  q.image_mode = mode;
+  q.grid_image = p.grp_image + (size_t)cell * (size_t)p.grp_image_stride;
+  if (p.prb_cqi && mode != 0) {
+    uint8_t* const store = p.grp_prb + (size_t)cell * (size_t)p.grp_prb_stride;
+    if (mode == 2) {
+      q.prb_cqi = store; /* same reports as the cell's last stored call: the slot's per-PRB block was not sent */
+    } else {
+      /* new reports: the cell's copy for the calls that follow, 16 bytes per lane.  Nothing in this launch reads it (the body reads
+       * the slot's block), so the stores drain behind the body's first phase; the next launch is what orders them. */
+      const uint4* const src = (const uint4*)q.prb_cqi;
+      const int n16 = (q.U * p.R * p.G + 15) >> 4;
+      for (int i = threadIdx.x; i < n16; i += blockDim.x) ((uint4*)store)[i] = src[i];
+    }
+  }
   rs_cell_body<SCHED, EPT, false, true, false, true>(q, lds);
   __threadfence_system();
   __syncthreads();

@@ -9,7 +9,7 @@
  *   dropin_concurrency procs   K SHAPE [calls] [epoch|noepoch] [builtin]     K processes, one context each (fork + exec of this binary
  *                                                                            from a parent that never touches the GPU)
  *   dropin_concurrency seq     K SHAPE [calls] [epoch|noepoch] [builtin]     K contexts on ONE host thread, called one after the other
- *   dropin_concurrency group=K   SHAPE [calls]                               K cells of one rs_group on ONE host thread: one
+ *   dropin_concurrency group=K   SHAPE [calls] [epoch|noepoch]               K cells of one rs_group on ONE host thread: one
  *                                                                            rs_group_schedule_tti (one kernel launch) per TTI of all K cells
  *   SHAPE: 500x25 (20 slices x 25 UEs, 25 RBGs of 4 PRBs) | 100x64 (20 x 5 UEs, 64 RBGs of 8: the shipped exp-fix20slices/5ues shape)
  *   further options: think=US (host time between two calls of a worker: the simulator's own work per TTI; default 0 = back to back),
@@ -22,7 +22,8 @@
  * call.  Output: one line per run with the pooled per-call p50 / p90 / p99 / max in microseconds and the aggregate TTIs/s
  * (K x calls / (last end - first start)) with its reciprocal, the wall time per cell-TTI.  `seq` and `group` time one ROUND (one TTI
  * of all K cells) per sample.  `group` first checks parity: during the warm-up every cell's answer (RBG map, transport blocks, slice
- * offsets) is compared with a context of its own that is fed the same inputs (built-in kernels on both sides).
+ * offsets) is compared with a context of its own that is fed the same inputs and the same cqi_epoch (built-in kernels on both sides);
+ * at the end it prints rs_group_image_stats (cell-TTIs served from a cell's device image / that stored one / without a number).
  *
  * Build: g++ -O2 -std=c++17 -pthread -Iinclude tools/dropin_concurrency.cpp -Lradiosaber_amd -lradiosaber_hip \
  *            -Wl,-rpath,'$ORIGIN/../radiosaber_amd' -o tools/dropin_concurrency
@@ -221,7 +222,6 @@ int run_seq(int K, const char* shape, const Worker& proto) {
 int run_group(int K, const char* shape, Worker proto) {
   proto.make_ctx = false;
   proto.specialise = false; /* (a group runs the kernels built into the library) */
-  proto.epoch = false;      /* (cqi_epoch is accepted and ignored by a group) */
   std::vector<Worker> ws(K, proto), twins(K, proto);
   std::vector<rs_tti_in> ins(K);
   std::vector<rs_tti_out> outs(K);
@@ -273,9 +273,11 @@ int run_group(int K, const char* shape, Worker proto) {
   const double last = now_sec();
   long long sum = 0;
   for (auto& w : ws) sum += w.checksum;
-  char status[160];
-  snprintf(status, sizeof status, "%s, %lld launches for %d calls, parity with %d contexts over 60 rounds ok", rs_group_kernel_name(g),
-           (long long)rs_group_launch_count(g) - launches0, proto.calls, K);
+  int64_t st[3] = {0, 0, 0};
+  if (rs_group_image_stats(g, st) != RS_OK) { fprintf(stderr, "rs_group_image_stats: %s\n", rs_last_error()); return 1; }
+  char status[240];
+  snprintf(status, sizeof status, "%s, %lld launches for %d calls, parity with %d contexts over 60 rounds ok, cell-TTIs from the image %lld / stored %lld / no epoch %lld",
+           rs_group_kernel_name(g), (long long)rs_group_launch_count(g) - launches0, proto.calls, K, (long long)st[0], (long long)st[1], (long long)st[2]);
   rs_group_destroy(g);
   report("group", K, shape, proto, all, first, last, sum, status, K);
   return 0;
@@ -354,7 +356,7 @@ int run_procs(int K, const char* shape, const Worker& proto, char** argv_tail, i
 int main(int argc, char** argv) {
   const bool group_mode = argc >= 2 && !strncmp(argv[1], "group=", 6);
   if (argc < (group_mode ? 3 : 4)) {
-    fprintf(stderr, "usage: %s threads|procs|seq K 500x25|100x64|500x64 [calls] [epoch|noepoch] [builtin] [sched=N]\n       %s group=K 500x25|100x64|500x64 [calls] [sched=N]\n", argv[0], argv[0]);
+    fprintf(stderr, "usage: %s threads|procs|seq K 500x25|100x64|500x64 [calls] [epoch|noepoch] [builtin] [sched=N]\n       %s group=K 500x25|100x64|500x64 [calls] [epoch|noepoch] [sched=N]\n", argv[0], argv[0]);
     return 2;
   }
   if (group_mode) { /* group=K SHAPE ...: the same argument positions as the other modes from here on */
