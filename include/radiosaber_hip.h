@@ -27,7 +27,8 @@ extern "C" {
 
 #define RS_ABI_VERSION 11 /* 11: (additions, no layout changed) rs_batch_flow_record (flow completion times of the queue model),
                                rs_batch_bearer_log + rs_batch_run_logged_bearers (per-bearer DoStopSchedule rows),
-                               rs_group_* (one TTI of several drop-in cells in one launch), rs_group_image_stats (cqi_epoch per cell of a group);
+                               rs_group_* (one TTI of several drop-in cells in one launch), rs_group_image_stats (cqi_epoch per cell of a group),
+                               rs_group_specialize / rs_group_jit_status / rs_jit_selfcheck_group (a group's own self-checked builds of the one-TTI kernel);
                                rs_config.link_tables (RS_LINK_*) + rs_link_tables_pinned / rs_link_tables_compare, rs_tti_in.cqi_epoch (the context keeps the
                                CQI image of an unchanged report set on the device), rs_ctx_jit_status (a specialised context checks its run-time build against the
                                built-in kernel during its first calls), rs_batch_config.selfcheck -1 / 0 / 1 with run-time builds verified by default and the
@@ -286,8 +287,9 @@ int rs_set_slice_offset(rs_ctx* ctx, const double* offset /* [S] */);
  *     through rs_last_error(), and the group serves cqi_prb calls as if cqi_epoch were 0 from then on.
  *   - Every scheduler rs_create accepts except RS_SCHED_NVS_NONGREEDY; general integer exponents and synthetic_exp are supported
  *     (they belong to the config, so they are the same for the whole group).
- *   - Only the kernels built into the library serve a group (no run-time specialisation): a shape they cannot run is rejected by
- *     rs_group_create.
+ *   - A group starts on the kernels built into the library and may get builds of its own (rs_group_specialize below).  The built-in
+ *     kernels also run beside those builds' checked calls, so a shape they cannot run (more than 512 threads per cell) is rejected
+ *     by rs_group_create either way.
  * One host thread per group at a time; different groups may run on different threads.
  * ------------------------------------------------------------------------------------------ */
 #define RS_GROUP_MAX_CELLS 1024
@@ -306,7 +308,30 @@ int64_t rs_group_launch_count(const rs_group* g);
 /* cell-TTIs of the successful calls so far: out[0] served from the cell's image (the caller's block not read), out[1] that read the
  * block and stored an image (non-zero cqi_epoch, no match), out[2] without a promise (cqi_epoch 0, or RS_GROUP_IMAGE=0) */
 int rs_group_image_stats(const rs_group* g, int64_t out[3]);
+/* "rs_group_kernel_jit" while the group's own builds serve its calls; the built-in instantiation's name before rs_group_specialize and
+ * after a build was dropped */
 const char* rs_group_kernel_name(rs_group* g);
+/* Optional, at any time between two calls: rs_ctx_specialize for a group -- the one-TTI kernel compiled for the config's slices, RBGs,
+ * PRBs per RBG, scheduler, workgroup size and user capacity (hiprtc, ~2 s per build and process, cached on disk apart from the
+ * contexts' builds), one workgroup per call slot.  Two builds: the general one, and a lean one that rs_group_schedule_tti picks when
+ * the call is plain for EVERY cell (per-RBG CQI, no customised slices, no gate, exponents in {0, 1}, every input an ordinary FP32
+ * number, no upper_* lists; RS_JIT_LEAN=0: the general one only).  Results are identical.  Slice state, CQI images and per-PRB stores
+ * are not touched: a call right after it is served from the images the built-in kernels stored.  RS_OK; RS_ERR_HIP with the group left
+ * on the built-in kernels; a second call is a no-op; RS_ERR_STATE (with the reason) once a build was dropped.
+ * The builds are checked as a context's are (rs_ctx_jit_status above, same switches): a build without the self-check mark serves its
+ * first RS_DROPIN_SELFCHECK_CALLS (default 8) calls beside the built-in group kernel -- same slots, same slice state, completion by
+ * the stream -- and every named cell's rs_tti_out fields, upper_* lists and slice state are compared bit for bit.  Agreement on all of
+ * them leaves the mark in the cache file.  One difference drops BOTH builds and unlinks their cache files: that call returns the
+ * built-in kernel's results and state with RS_OK, later calls run the built-in kernels, and rs_last_error() / rs_group_jit_status name
+ * the cell, the field and the index ("cell 3: user_tbs_bits[3] = 2224, the built-in kernel's 2216").  rs_group_launch_count counts a
+ * checked call once.  RS_JIT_SELFCHECK=0 never checks, =2 checks marked builds too. */
+int rs_group_specialize(rs_group* g);
+/* 1 = the group's own builds serve the calls (msg: per build, how it earned its trust), 0 = rs_group_specialize was not called,
+ * -1 = it failed to build, -2 = the builds were dropped by the check (msg says what differed) */
+int rs_group_jit_status(rs_group* g, char* msg, size_t msglen);
+/* build check without a GPU: do the general and the lean build of a group of this shape compile?  (the larger code size, or a
+ * negative value with the compiler's log in err) */
+int rs_jit_selfcheck_group(int n_slices, int n_users, int n_rbgs, int rbg_size, int threads, int sched, char* err, size_t errlen);
 
 /* ------------------------------------------------------------------------------------------
  * Batched mode: many independent cells resident on the device, whole DoSchedule() loops

@@ -32,7 +32,8 @@ extern "C" hipError_t rs_launch_cells(const RsLaunch* p, int threads, hipStream_
 extern "C" hipError_t rs_prepare_kernels(int max_lds_bytes);
 struct RsJitKernel;
 extern "C" RsJitKernel* rs_jit_get(int device, int S, int U, int R, int G, int NT, int sched, int qmode, int win, char* err, size_t errlen,
-                                   int flags, /* bit 0: drop-in (one-TTI) kernel, bit 1: streamed batch (cqi_refresh <= 4), bit 2: lean build */
+                                   int flags, /* bit 0: drop-in (one-TTI) kernel, bit 1: streamed batch (cqi_refresh <= 4), bit 2: lean build,
+                                                * bit 3: a group's build of the one-TTI kernel (rs_group_kernel_jit) */
                                    const char* variant = nullptr); /* an autotune candidate: extra -D options and / or "ss=<LLVM scheduler strategy>" */
 extern "C" int rs_jit_is_untuned(const RsJitKernel* k);
 extern "C" int rs_jit_is_verified(const RsJitKernel* k);  /* carries the self-check mark (this process, or its cache file) */
@@ -2418,7 +2419,21 @@ struct rs_group {
   double t_prep = 0, t_enq = 0, t_wait = 0, t_unpack = 0;
   long n_calls = 0, n_cell_ttis = 0, n_polled = 0, n_fallback = 0;
   char kname[48] = "";
+  /* rs_group_specialize: the group's own builds of the one-TTI form (index 0: general build, 1: lean build for the plain call), and
+   * their check against the built-in group kernel -- calls still to be checked, calls that agreed so far (rs_ctx's scheme) */
+  RsJitKernel* jit[2] = {nullptr, nullptr};
+  bool jit_wanted = false, jit_dropped = false;
+  int chk_left[2] = {0, 0}, chk_agreed[2] = {0, 0};
+  uint8_t *d_out2 = nullptr, *d_chk = nullptr; /* the built-in kernel's output slots; the group's slice state + scalars before / after it */
+  std::vector<uint8_t> h_out2;
+  char jit_msg[512] = "";
 };
+
+namespace {
+/* bytes of one half of rs_group::d_chk: [n_cells][S] slice state, then [n_cells] RsCellScalars */
+size_t group_chk_sstate(const rs_group* g) { return round_up((int)(8 * (size_t)g->b->S * g->n_cells), 256); }
+size_t group_chk_half(const rs_group* g) { return group_chk_sstate(g) + round_up((int)(sizeof(RsCellScalars) * (size_t)g->n_cells), 256); }
+}  // namespace
 
 extern "C" hipError_t rs_launch_group(const RsLaunch* p, int threads, hipStream_t stream);
 
@@ -2445,8 +2460,8 @@ rs_group* rs_group_create(const rs_config* cfg, int32_t n_cells) {
   bc.cqi_refresh = 1;
   rs_batch* b = batch_new(&bc, true);
   if (!b) return nullptr;
-  if (b->threads > 512) { /* (only the kernels built into the library serve a group) */
-    fail(RS_ERR_INVALID, "a group runs the built-in kernels only: %d threads per cell exceed their 512", b->threads);
+  if (b->threads > 512) { /* (the built-in kernels serve a group until rs_group_specialize, and beside its builds' checked calls) */
+    fail(RS_ERR_INVALID, "a group needs the built-in kernels: %d threads per cell exceed their 512", b->threads);
     rs_batch_destroy(b);
     return nullptr;
   }
@@ -2507,6 +2522,8 @@ void rs_group_destroy(rs_group* g) {
   if (g->d_count) (void)hipFree(g->d_count);
   if (g->d_img) (void)hipFree(g->d_img);
   if (g->d_prb) (void)hipFree(g->d_prb);
+  if (g->d_out2) (void)hipFree(g->d_out2);
+  if (g->d_chk) (void)hipFree(g->d_chk);
   if (g->h_in) (void)hipHostFree(g->h_in);
   if (g->h_out) (void)hipHostFree(g->h_out);
   rs_batch_destroy(g->b);
@@ -2644,17 +2661,47 @@ int rs_group_schedule_tti(rs_group* g, int32_t n, const int32_t* cell_ids, const
   L.grp_in_stride = (int64_t)g->in_stride;
   L.grp_out_stride = (int64_t)g->out_stride;
   L.grp_count = g->d_count;
-  const bool poll = zc && g->poll;
+  bool poll = zc && g->poll;
   if (poll) {
     if (++g->seq == 0) g->seq = 1; /* (0 is the word's initial value) */
     L.done_flag = (uint32_t*)(g->z_out + g->flag_off);
     L.done_seq = g->seq;
   }
-  HIP_TRY(rs_launch_group(&L, b->threads, st));
+  /* rs_group_specialize: the group's own build -- its lean form when the call is plain for every cell (the uniform-presence rules above
+   * make that a fact of the launch), the general one otherwise */
+  RsJitKernel* kd = g->jit[0];
+  int which = 0;
+  if (g->jit[1] && !has_prb && !L.queue_mode && !has_gate && !L.exact_scan && !L.gen_exp && !want_upper && !L.synthetic) { kd = g->jit[1]; which = 1; }
+  /* A build without the self-check mark serves its first calls beside the built-in group kernel (rs_group_jit_status): same slots,
+   * same slice state; every named cell's output fields and the slice state left behind must agree. */
+  const bool checked_call = kd != nullptr && g->chk_left[which] > 0;
+  const size_t ss_all = 8 * (size_t)b->S * g->n_cells, sc_all = sizeof(RsCellScalars) * (size_t)g->n_cells;
+  if (checked_call) {
+    uint8_t* const before = g->d_chk;
+    uint8_t* const after = g->d_chk + group_chk_half(g);
+    HIP_TRY(hipMemcpyAsync(before, b->d_sstate, ss_all, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(before + group_chk_sstate(g), b->d_scal, sc_all, hipMemcpyDeviceToDevice, st));
+    RsLaunch Lb = L; /* the built-in kernel, its outputs into slots of its own */
+    Lb.grp_out = g->d_out2;
+    Lb.log_upper = want_upper ? (int32_t*)g->d_out2 : nullptr;
+    Lb.done_flag = nullptr;
+    HIP_TRY(rs_launch_group(&Lb, b->threads, st));
+    HIP_TRY(hipMemcpyAsync(g->h_out2.data(), g->d_out2, (size_t)n * g->out_stride, hipMemcpyDeviceToHost, st));
+    /* keep what it left, put back what it found: the run-time build starts from the same state */
+    HIP_TRY(hipMemcpyAsync(after, b->d_sstate, ss_all, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b->d_sstate, before, ss_all, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b->d_scal, before + group_chk_sstate(g), sc_all, hipMemcpyDeviceToDevice, st));
+    /* (a mode-1 slot: BOTH kernels transpose the slot's block and store the cell's image and per-PRB copy -- the same bytes when the
+     * build is right; a wrong image shows in the checked calls that read it) */
+    L.done_flag = nullptr; /* completion by the stream */
+  }
+  if (kd) HIP_TRY(rs_jit_launch(kd, &L, st));
+  else HIP_TRY(rs_launch_group(&L, b->threads, st));
   g->launches++;
   if (!zc) HIP_TRY(hipMemcpyAsync(g->h_out, g->d_out, (size_t)n * g->out_stride, hipMemcpyDeviceToHost, st));
   const clk::time_point t2 = g->timing ? clk::now() : clk::time_point();
   bool seen = false;
+  if (checked_call) poll = false;
   if (poll) {
     /* the last workgroup to finish publishes the sequence number behind every workgroup's outputs (release, system scope) */
     const volatile uint32_t* const h_flag = (const volatile uint32_t*)(g->h_out + g->flag_off);
@@ -2672,6 +2719,56 @@ int rs_group_schedule_tti(rs_group* g, int32_t n, const int32_t* cell_ids, const
   if (!seen) {
     g->n_fallback++;
     HIP_TRY(hipStreamSynchronize(st));
+  }
+  if (checked_call) {
+    /* slot by slot, field by field: the first difference is the message */
+    std::vector<double> ss_jit((size_t)b->S * g->n_cells), ss_ref(ss_jit.size());
+    HIP_TRY(hipMemcpy(ss_jit.data(), b->d_sstate, ss_all, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ss_ref.data(), g->d_chk + group_chk_half(g), ss_all, hipMemcpyDeviceToHost));
+    char what[240] = "";
+    for (int k = 0; k < n && !what[0]; k++) {
+      const int cell = cell_ids ? cell_ids[k] : k;
+      const CtxLayout& l = g->packs[k].l;
+      const uint8_t *ho = g->h_out + (size_t)k * g->out_stride, *hr = g->h_out2.data() + (size_t)k * g->out_stride;
+      auto differ32 = [&](const char* name, size_t off, int count) {
+        const int32_t *a = (const int32_t*)(ho + off), *r = (const int32_t*)(hr + off);
+        for (int i = 0; i < count && !what[0]; i++)
+          if (a[i] != r[i]) snprintf(what, sizeof what, "cell %d: %s[%d] = %d, the built-in kernel's %d", cell, name, i, a[i], r[i]);
+      };
+      auto differ16 = [&](const char* name, size_t off, int count) {
+        const int16_t *a = (const int16_t*)(ho + off), *r = (const int16_t*)(hr + off);
+        for (int i = 0; i < count && !what[0]; i++)
+          if (a[i] != r[i]) snprintf(what, sizeof what, "cell %d: %s[%d] = %d, the built-in kernel's %d", cell, name, i, a[i], r[i]);
+      };
+      differ16("rbg_to_user (call position)", l.map, b->R);
+      differ16("quota_rbgs", l.quota, b->S);
+      differ16("target_rbs", l.target, b->S);
+      differ32("user_tbs_bits", l.tbs, in[k].n_users);
+      differ32("user_nprb | final_cqi << 16 | mcs << 24", l.uinfo, in[k].n_users);
+      if (want_upper) differ32("upper lists", l.upper, b->S * b->R);
+      for (int i = 0; i < b->S && !what[0]; i++) {
+        const double a = ss_jit[(size_t)cell * b->S + i], r = ss_ref[(size_t)cell * b->S + i];
+        if (to_bits(a) != to_bits(r)) snprintf(what, sizeof what, "cell %d: slice state[%d] = %a, the built-in kernel's %a", cell, i, a, r);
+      }
+    }
+    if (what[0]) {
+      /* the build is wrong: neither build of the shape is trusted.  Both are dropped (and their cache files); this call returns the
+       * built-in kernel's outputs and state, later calls run the built-in kernels */
+      for (int w = 0; w < 2; w++) {
+        if (g->jit[w]) rs_jit_reject(g->jit[w]);
+        g->jit[w] = nullptr;
+        g->chk_left[w] = 0;
+      }
+      g->jit_dropped = true;
+      memcpy(g->h_out, g->h_out2.data(), (size_t)n * g->out_stride);
+      HIP_TRY(hipMemcpy(b->d_sstate, g->d_chk + group_chk_half(g), ss_all, hipMemcpyDeviceToDevice));
+      snprintf(g->jit_msg, sizeof g->jit_msg, "self-check of the group's specialised %s build, checked call %d: %s; both builds are dropped, the built-in kernels "
+               "serve this group (lint the code object: tools/lint_exec_restore.py)", which ? "lean" : "general", g->chk_agreed[which] + 1, what);
+      snprintf(g_err, sizeof g_err, "%s", g->jit_msg);
+    } else {
+      g->chk_agreed[which]++;
+      if (--g->chk_left[which] == 0) rs_jit_mark_verified(kd);
+    }
   }
   guard.ok = true;
   const clk::time_point t3 = g->timing ? clk::now() : clk::time_point();
@@ -2734,7 +2831,75 @@ int rs_group_image_stats(const rs_group* g, int64_t out[3]) {
   return RS_OK;
 }
 
-const char* rs_group_kernel_name(rs_group* g) { return g ? g->kname : ""; }
+const char* rs_group_kernel_name(rs_group* g) { return !g ? "" : (g->jit[0] ? "rs_group_kernel_jit" : g->kname); }
+
+/* Shape specialisation of a group: rs_ctx_specialize for the group surface -- the one-TTI form compiled for the config's slices, RBGs,
+ * PRBs per RBG, scheduler, workgroup size and user CAPACITY, entry point rs_group_kernel_jit (one workgroup per call slot), in a
+ * general and a lean build.  Between calls at any time: slice state, CQI images and per-PRB stores are not touched. */
+int rs_group_specialize(rs_group* g) {
+  if (!g) return fail(RS_ERR_INVALID, "null group");
+  rs_batch* b = g->b;
+  if (g->jit[0]) return RS_OK;
+  if (g->jit_dropped) return fail(RS_ERR_STATE, "%s", g->jit_msg);
+  HIP_TRY(hipSetDevice(b->cfg.cell.device));
+  g->jit_wanted = true;
+  if (!g->d_out2) {
+    const size_t out_bytes = g->out_stride * (size_t)g->n_cells;
+    if (hipMalloc(&g->d_out2, out_bytes) != hipSuccess || hipMalloc(&g->d_chk, 2 * group_chk_half(g)) != hipSuccess) {
+      (void)hipGetLastError();
+      if (g->d_out2) (void)hipFree(g->d_out2);
+      g->d_out2 = g->d_chk = nullptr;
+      snprintf(g->jit_msg, sizeof g->jit_msg, "allocation of the self-check's twin blocks failed (%zu + %zu bytes)", out_bytes, 2 * group_chk_half(g));
+      return fail(RS_ERR_HIP, "%s", g->jit_msg);
+    }
+    g->h_out2.assign(out_bytes, 0);
+  }
+  const int qmode = (b->sched == RS_SCHED_PF || b->sched == RS_SCHED_NVS) ? 1 : 0; /* (the gate scratch of the group's carve: carve_lds) */
+  char msg[512] = "";
+  g->jit[0] = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, qmode, 0, msg, sizeof msg, 1 | 8);
+  if (!g->jit[0]) {
+    snprintf(g->jit_msg, sizeof g->jit_msg, "%s", msg[0] ? msg : "hiprtc build failed");
+    return fail(RS_ERR_HIP, "%s", g->jit_msg);
+  }
+  g->jit_msg[0] = 0;
+  /* ... and its lean form (the plain call); without it the general build serves every call */
+  const char* const e_on = getenv("RS_JIT_LEAN");
+  if (!e_on || atoi(e_on) != 0) g->jit[1] = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, qmode, 0, msg, sizeof msg, 1 | 4 | 8);
+  /* the policy and the switches of rs_ctx_specialize: no checked calls for a build that came with the mark of an earlier check */
+  int calls = 8;
+  if (const char* e = getenv("RS_DROPIN_SELFCHECK_CALLS")) calls = atoi(e) > 0 ? atoi(e) : 0;
+  const char* pol = getenv("RS_JIT_SELFCHECK");
+  const bool never = pol && pol[0] == '0', always = pol && pol[0] == '2';
+  for (int w = 0; w < 2; w++) {
+    g->chk_agreed[w] = 0;
+    g->chk_left[w] = (g->jit[w] && !never && (always || !rs_jit_is_verified(g->jit[w]))) ? calls : 0;
+  }
+  return RS_OK;
+}
+
+int rs_group_jit_status(rs_group* g, char* msg, size_t msglen) {
+  if (!g) return fail(RS_ERR_INVALID, "null group");
+  if (msg && msglen) {
+    if (g->jit_dropped || !g->jit[0]) {
+      snprintf(msg, msglen, "%s", g->jit_msg);
+    } else {
+      auto state = [&](int which, char* out, size_t n) {
+        RsJitKernel* const k = g->jit[which];
+        if (!k) snprintf(out, n, "not built");
+        else if (g->chk_left[which] > 0) snprintf(out, n, "%d checked call(s) agreed with the built-in kernel field by field, %d to go", g->chk_agreed[which], g->chk_left[which]);
+        else if (g->chk_agreed[which] > 0) snprintf(out, n, "verified (%d checked calls agreed with the built-in kernel field by field)", g->chk_agreed[which]);
+        else if (rs_jit_is_verified(k)) snprintf(out, n, "carries the self-check mark of an earlier check (cache file)");
+        else snprintf(out, n, "unchecked (RS_JIT_SELFCHECK=0)");
+      };
+      char ge[160], le[160];
+      state(0, ge, sizeof ge);
+      state(1, le, sizeof le);
+      snprintf(msg, msglen, "general build: %s; lean build: %s", ge, le);
+    }
+  }
+  if (g->jit_dropped) return -2;
+  return g->jit[0] ? 1 : (g->jit_wanted ? -1 : 0);
+}
 
 /* ---- the reference's CQI trace files (include/radiosaber_hip.h) ---- */
 

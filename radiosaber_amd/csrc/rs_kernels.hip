@@ -26,6 +26,7 @@
  *   rs_phase_p4.inc           P4 on all waves (sort emulation, UpperBound)
  *   rs_phase_p4_serial.inc    wave 0: the inter-slice policy / per-RBG reduction      rs_phase_p5.inc   wave 0: P5
  *   rs_phase_next.inc         the other waves meanwhile: TTI t+1 prepared (kEarly17, held winners, speculation)
+ *   rs_phase_group.inc        (outside the cell body) a group call's workgroup: slot header, pointer moves, completion chain
  * One function on purpose: the per-thread state (sort records, byte counters, quota lanes) lives in registers across phases.
  *
  * Template parameters of the cell body: SCHED = the reference's CLI scheduler number (1, 7, 8, 9, 10, 11; 101 = SubOpt, 103 = Vogel),
@@ -152,7 +153,7 @@ __device__ __forceinline__ double rs_div_1000(double x) {
 
 template <int SCHED, int EPT, bool FIXED, bool DIRECT, bool QUEUE = false, bool GROUP = false>
 __device__ __forceinline__ void rs_cell_body(const RsLaunch& p, unsigned char* lds) {
-  static_assert(!GROUP || (DIRECT && !FIXED && !QUEUE && SCHED != 11), "group calls: the built-in one-TTI kernels, scheduler 11 excepted");
+  static_assert(!GROUP || (DIRECT && !QUEUE && SCHED != 11), "group calls: the one-TTI form (built in, or a group's run-time build), scheduler 11 excepted");
   static_assert(!QUEUE || (!DIRECT && (SCHED == 8 || SCHED == 9 || SCHED == 101 || SCHED == 103 || SCHED == 1 || SCHED == 7)),
                 "finite queues: batches of schedulers 1, 7, 8, 9, 101, 103");
   /* schedulers 1 and 7 with queues allocate RBG by RBG on wave 0 (the satisfied-flow break / the m_requiredRBs gate bind) */
@@ -772,73 +773,13 @@ __global__ void __launch_bounds__(512, 4) rs_cell_kernel(RsLaunch p) {
   rs_cell_body<SCHED, EPT, false, DIRECT, QUEUE>(p, lds);
 }
 
-/* One TTI for a group of drop-in cells in one launch (rs_group_schedule_tti): workgroup k serves call slot k.  It reads the slot's
- * header (which cell, how many users, the rand() pair, where the slot's arrays lie, what to do with the cell's CQI image), moves every
- * per-cell pointer of the launch block to its slot / its cell and runs the one-TTI body on that block -- the phases never learn that other cells exist.
- * Completion: every thread's outputs are out at system scope (fence), then the workgroup counts itself in on a device word; the
- * workgroup that brings the count to the number of slots -- the last to finish, whichever it is and whenever the others ran: nothing
- * here assumes that the workgroups are resident together -- puts the word back to 0 for the next launch and publishes the call's
- * sequence number to the host.  Its acquire of the counter orders it behind every other workgroup's fence and release. */
+/* a group call on the kernels built into the library: 14 instantiations (rs_launch_group); the body is rs_phase_group.inc */
 template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
-  const uint8_t* const in = p.grp_in + (size_t)blockIdx.x * (size_t)p.grp_in_stride;
-  uint8_t* const out = p.grp_out + (size_t)blockIdx.x * (size_t)p.grp_out_stride;
-  const RsGroupCell* const h = (const RsGroupCell*)in;
-  /* (one address for the whole workgroup: the values are wave-uniform, and the compiler is told so) */
-  auto word = [](const int32_t* q) { return __builtin_amdgcn_readfirstlane(*q); };
-  const uint8_t* const data = in + RS_GROUP_HDR_BYTES;
-  RsLaunch q = p;
-  const int cell = word(&h->cell);
-  q.U = word(&h->U);
-  q.Upad = word(&h->Upad);
-  q.n_seg = word(&h->n_seg);
-  q.n_items = word(&h->n_items);
-  q.rand0 = word(&h->rand0);
-  q.rand1 = word(&h->rand1);
-  const int in_slice = word(&h->in_slice);
-  q.epochs = data;
-  q.grid_stride = (int64_t)in_slice;
-  q.user_slice = data + in_slice;
-  q.avg = (double*)(data + word(&h->in_avg));
-  q.hol = (const double*)(data + word(&h->in_hol));
-  q.prio = data + word(&h->in_prio);
-  q.gate = p.gate ? (const int32_t*)(data + word(&h->in_gate)) : nullptr;
-  q.prb_cqi = p.prb_cqi ? data + word(&h->in_prb) : nullptr;
-  q.log_tbs = (int32_t*)out;
-  q.log_uinfo = (int32_t*)(out + word(&h->out_uinfo));
-  q.log_map = (int16_t*)(out + word(&h->out_map));
-  q.log_quota = (int16_t*)(out + word(&h->out_quota));
-  q.log_target = (int16_t*)(out + word(&h->out_target));
-  q.log_upper = p.log_upper ? (int32_t*)(out + word(&h->out_upper)) : nullptr;
-  q.slice_state = p.slice_state + (size_t)cell * p.S;
-  q.scal = p.scal + cell;
-  /* rs_tti_in.cqi_epoch, per slot: the image belongs to the CELL (the slot that serves it changes from call to call) */
-  const int mode = word(&h->image_mode);
-  q.image_mode = mode;
-  q.grid_image = p.grp_image + (size_t)cell * (size_t)p.grp_image_stride;
-  if (p.prb_cqi && mode != 0) {
-    uint8_t* const store = p.grp_prb + (size_t)cell * (size_t)p.grp_prb_stride;
-    if (mode == 2) {
-      q.prb_cqi = store; /* same reports as the cell's last stored call: the slot's per-PRB block was not sent */
-    } else {
-      /* new reports: the cell's copy for the calls that follow, 16 bytes per lane.  Nothing in this launch reads it (the body reads
-       * the slot's block), so the stores drain behind the body's first phase; the next launch is what orders them. */
-      const uint4* const src = (const uint4*)q.prb_cqi;
-      const int n16 = (q.U * p.R * p.G + 15) >> 4;
-      for (int i = threadIdx.x; i < n16; i += blockDim.x) ((uint4*)store)[i] = src[i];
-    }
-  }
-  rs_cell_body<SCHED, EPT, false, true, false, true>(q, lds);
-  __threadfence_system();
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const uint32_t before = __hip_atomic_fetch_add(p.grp_count, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    if (before + 1u == (uint32_t)p.n_cells) {
-      __hip_atomic_store(p.grp_count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (p.done_flag) __hip_atomic_store(p.done_flag, p.done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
+  constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
+  constexpr bool kGrpFixed = false, kGrpLean = false;
+#include "rs_phase_group.inc"
 }
 #else
 #ifndef RS_JIT_DIRECT
@@ -850,6 +791,31 @@ __global__ void __launch_bounds__(512, 4) rs_group_kernel(RsLaunch p) {
 #ifndef RS_JIT_WPE
 #define RS_JIT_WPE 4
 #endif
+#ifndef RS_JIT_GROUP
+#define RS_JIT_GROUP 0 /* 1: a group's build of the one-TTI form (rs_group_specialize): one workgroup per call slot */
+#endif
+#if RS_JIT_GROUP
+extern "C" __global__ void __launch_bounds__(RS_JIT_NT, RS_JIT_WPE) rs_group_kernel_jit(RsLaunch p) {
+#if defined(RS_JIT_LEAN) && RS_JIT_LEAN
+  /* The lean build of a group's kernel: the plain call, exactly as in the one-TTI lean kernel below -- per-RBG reports, no customised
+   * slices, no gates, exponents in {0, 1}, every input an ordinary FP32 number, no UpperBound lists, no synthetic-experiment blocks
+   * (the call's uniform-presence rules make that a per-launch fact; rs_group_schedule_tti picks the build per call).  image_mode stays
+   * the slot header's word: the cells of one launch mix modes 0 / 1 / 2. */
+  p.cqi_mode = RS_CQI_EPOCHS;
+  p.prb_cqi = nullptr; p.queue_mode = 0; p.alpha = nullptr; p.beta = nullptr; p.hol = nullptr; p.prio = nullptr;
+  p.gate = nullptr; p.exact_scan = 0; p.gen_exp = 0; p.gen_num = nullptr; p.log_upper = nullptr; p.synthetic = 0;
+  p.trace = nullptr; p.trace_prb = nullptr; p.epochs_prb = nullptr; p.log_keys = nullptr;
+  constexpr bool kGrpLean = true;
+#else
+  constexpr bool kGrpLean = false;
+#endif
+  constexpr RsCarve kCv = rs_carve(RS_JIT_S, RS_JIT_U, RS_JIT_R, RS_JIT_SCHED, RS_JIT_NT, RS_JIT_CARVEQ, RS_JIT_WIN);
+  __shared__ __align__(16) unsigned char lds[kCv.lds_bytes];
+  constexpr int kGrpSched = RS_JIT_SCHED, kGrpEpt = (RS_JIT_SCHED != 9 && RS_JIT_SCHED != 10) ? 0 : (kCv.ept <= 4 ? kCv.ept : 0);
+  constexpr bool kGrpFixed = true;
+#include "rs_phase_group.inc"
+}
+#else
 extern "C" __global__ void __launch_bounds__(RS_JIT_NT, RS_JIT_WPE) rs_cell_kernel_jit(RsLaunch p) {
 #if defined(RS_JIT_LEAN) && RS_JIT_LEAN && !RS_JIT_DIRECT
   /* The lean build of a batch kernel: the launch's run-time options that the long runs never use are constants here -- epoch grids
@@ -875,6 +841,7 @@ extern "C" __global__ void __launch_bounds__(RS_JIT_NT, RS_JIT_WPE) rs_cell_kern
   constexpr int kEpt = (RS_JIT_SCHED != 9 && RS_JIT_SCHED != 10) ? 0 : (kCv.ept <= 4 ? kCv.ept : 0);
   rs_cell_body<RS_JIT_SCHED, kEpt, true, RS_JIT_DIRECT != 0, (RS_JIT_CARVEQ >= 2)>(p, lds);
 }
+#endif
 #endif
 
 /* ------------------------------------------------------------------------------------------

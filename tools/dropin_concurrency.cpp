@@ -9,8 +9,10 @@
  *   dropin_concurrency procs   K SHAPE [calls] [epoch|noepoch] [builtin]     K processes, one context each (fork + exec of this binary
  *                                                                            from a parent that never touches the GPU)
  *   dropin_concurrency seq     K SHAPE [calls] [epoch|noepoch] [builtin]     K contexts on ONE host thread, called one after the other
- *   dropin_concurrency group=K   SHAPE [calls] [epoch|noepoch]               K cells of one rs_group on ONE host thread: one
- *                                                                            rs_group_schedule_tti (one kernel launch) per TTI of all K cells
+ *   dropin_concurrency group=K   SHAPE [calls] [epoch|noepoch] [spec]        K cells of one rs_group on ONE host thread: one
+ *                                                                            rs_group_schedule_tti (one kernel launch) per TTI of all K cells;
+ *                                                                            spec: rs_group_specialize before the warm-up (the group's own
+ *                                                                            run-time builds instead of the built-in kernels)
  *   SHAPE: 500x25 (20 slices x 25 UEs, 25 RBGs of 4 PRBs) | 100x64 (20 x 5 UEs, 64 RBGs of 8: the shipped exp-fix20slices/5ues shape)
  *   further options: think=US (host time between two calls of a worker: the simulator's own work per TTI; default 0 = back to back),
  *                    hwq=N (GPU_MAX_HW_QUEUES=N before the first HIP call: ROCclr maps a process's streams onto 4 hardware queues by default),
@@ -22,8 +24,10 @@
  * call.  Output: one line per run with the pooled per-call p50 / p90 / p99 / max in microseconds and the aggregate TTIs/s
  * (K x calls / (last end - first start)) with its reciprocal, the wall time per cell-TTI.  `seq` and `group` time one ROUND (one TTI
  * of all K cells) per sample.  `group` first checks parity: during the warm-up every cell's answer (RBG map, transport blocks, slice
- * offsets) is compared with a context of its own that is fed the same inputs and the same cqi_epoch (built-in kernels on both sides);
- * at the end it prints rs_group_image_stats (cell-TTIs served from a cell's device image / that stored one / without a number).
+ * offsets) is compared with a context of its own that is fed the same inputs and the same cqi_epoch (the contexts always on the built-in
+ * kernels; with `spec` the warm-up rounds include the group builds' checked calls, see rs_group_jit_status);
+ * at the end it prints rs_group_image_stats (cell-TTIs served from a cell's device image / that stored one / without a number) and the
+ * group's jit status.
  *
  * Build: g++ -O2 -std=c++17 -pthread -Iinclude tools/dropin_concurrency.cpp -Lradiosaber_amd -lradiosaber_hip \
  *            -Wl,-rpath,'$ORIGIN/../radiosaber_amd' -o tools/dropin_concurrency
@@ -60,6 +64,7 @@ struct Worker {
   int calls = 2000, sched = RS_SCHED_MAXCELL, id = 0;
   int think_us = 0; /* host time between two calls (the simulator's own work per TTI): 0 = back to back */
   bool epoch = true, specialise = true, make_ctx = true; /* (make_ctx = false: the inputs and output arrays of a group's cell) */
+  bool group_spec = false; /* group=K ... spec: rs_group_specialize before the warm-up */
   std::vector<float> us;      /* per-call latency */
   double t_first = 0, t_last = 0; /* seconds on CLOCK_MONOTONIC (the same clock in every process of the machine) */
   long long checksum = 0;
@@ -221,7 +226,7 @@ int run_seq(int K, const char* shape, const Worker& proto) {
 /* K cells of one rs_group on one host thread: one rs_group_schedule_tti per round */
 int run_group(int K, const char* shape, Worker proto) {
   proto.make_ctx = false;
-  proto.specialise = false; /* (a group runs the kernels built into the library) */
+  proto.specialise = false; /* (the twin contexts stay on the kernels built into the library; the group: see `spec`) */
   std::vector<Worker> ws(K, proto), twins(K, proto);
   std::vector<rs_tti_in> ins(K);
   std::vector<rs_tti_out> outs(K);
@@ -238,6 +243,7 @@ int run_group(int K, const char* shape, Worker proto) {
   cfg.algo_epsilon = ws[0].one.data(); cfg.algo_psi = ws[0].one.data(); cfg.user_to_slice = u2s.data();
   rs_group* g = RS_GROUP_CREATE(&cfg, K);
   if (!g) { fprintf(stderr, "rs_group_create: %s\n", rs_last_error()); return 1; }
+  if (proto.group_spec && rs_group_specialize(g) != RS_OK) { fprintf(stderr, "rs_group_specialize: %s\n", rs_last_error()); return 1; }
   auto round = [&]() {
     for (int i = 0; i < K; i++) { ws[i].next_inputs(); ins[i] = ws[i].in; outs[i] = ws[i].out; }
     if (rs_group_schedule_tti(g, K, nullptr, ins.data(), outs.data()) != RS_OK) { fprintf(stderr, "rs_group_schedule_tti: %s\n", rs_last_error()); return false; }
@@ -275,11 +281,15 @@ int run_group(int K, const char* shape, Worker proto) {
   for (auto& w : ws) sum += w.checksum;
   int64_t st[3] = {0, 0, 0};
   if (rs_group_image_stats(g, st) != RS_OK) { fprintf(stderr, "rs_group_image_stats: %s\n", rs_last_error()); return 1; }
-  char status[240];
+  char status[240], jit[600] = "";
   snprintf(status, sizeof status, "%s, %lld launches for %d calls, parity with %d contexts over 60 rounds ok, cell-TTIs from the image %lld / stored %lld / no epoch %lld",
            rs_group_kernel_name(g), (long long)rs_group_launch_count(g) - launches0, proto.calls, K, (long long)st[0], (long long)st[1], (long long)st[2]);
+  const int jit_code = rs_group_jit_status(g, jit, sizeof jit);
   rs_group_destroy(g);
+  proto.specialise = proto.group_spec; /* (what the report line calls the run) */
   report("group", K, shape, proto, all, first, last, sum, status, K);
+  printf("group jit status %d%s%s\n", jit_code, jit[0] ? ": " : "", jit);
+  if (proto.group_spec && jit_code != 1) { fprintf(stderr, "the group's run-time builds are not in use\n"); return 1; }
   return 0;
 }
 
@@ -356,7 +366,7 @@ int run_procs(int K, const char* shape, const Worker& proto, char** argv_tail, i
 int main(int argc, char** argv) {
   const bool group_mode = argc >= 2 && !strncmp(argv[1], "group=", 6);
   if (argc < (group_mode ? 3 : 4)) {
-    fprintf(stderr, "usage: %s threads|procs|seq K 500x25|100x64|500x64 [calls] [epoch|noepoch] [builtin] [sched=N]\n       %s group=K 500x25|100x64|500x64 [calls] [epoch|noepoch] [sched=N]\n", argv[0], argv[0]);
+    fprintf(stderr, "usage: %s threads|procs|seq K 500x25|100x64|500x64 [calls] [epoch|noepoch] [builtin] [sched=N]\n       %s group=K 500x25|100x64|500x64 [calls] [epoch|noepoch] [spec] [sched=N]\n", argv[0], argv[0]);
     return 2;
   }
   if (group_mode) { /* group=K SHAPE ...: the same argument positions as the other modes from here on */
@@ -376,6 +386,7 @@ int main(int argc, char** argv) {
     if (!strcmp(argv[i], "epoch")) proto.epoch = true;
     else if (!strcmp(argv[i], "noepoch")) proto.epoch = false;
     else if (!strcmp(argv[i], "builtin")) proto.specialise = false;
+    else if (!strcmp(argv[i], "spec")) proto.group_spec = true;
     else if (!strncmp(argv[i], "sched=", 6)) proto.sched = atoi(argv[i] + 6);
     else if (!strncmp(argv[i], "think=", 6)) proto.think_us = atoi(argv[i] + 6);
     /* ROCclr multiplexes a process's streams onto GPU_MAX_HW_QUEUES (default 4) hardware queues: set before the first HIP call */
