@@ -28,7 +28,8 @@ extern "C" {
 #define RS_ABI_VERSION 11 /* 11: (additions, no layout changed) rs_batch_flow_record (flow completion times of the queue model),
                                rs_batch_bearer_log + rs_batch_run_logged_bearers (per-bearer DoStopSchedule rows),
                                rs_group_* (one TTI of several drop-in cells in one launch), rs_group_image_stats (cqi_epoch per cell of a group),
-                               rs_group_specialize / rs_group_jit_status / rs_jit_selfcheck_group (a group's own self-checked builds of the one-TTI kernel);
+                               rs_group_specialize / rs_group_jit_status / rs_jit_selfcheck_group (a group's own self-checked builds of the one-TTI kernel),
+                               rs_group_set_avg / rs_group_get_avg / rs_group_set_pending / rs_group_schedule_tti_at (a group cell's PF averages resident on the device);
                                rs_config.link_tables (RS_LINK_*) + rs_link_tables_pinned / rs_link_tables_compare, rs_tti_in.cqi_epoch (the context keeps the
                                CQI image of an unchanged report set on the device), rs_ctx_jit_status (a specialised context checks its run-time build against the
                                built-in kernel during its first calls), rs_batch_config.selfcheck -1 / 0 / 1 with run-time builds verified by default and the
@@ -332,6 +333,48 @@ int rs_group_jit_status(rs_group* g, char* msg, size_t msglen);
 /* build check without a GPU: do the general and the lean build of a group of this shape compile?  (the larger code size, or a
  * negative value with the compiler's log in err) */
 int rs_jit_selfcheck_group(int n_slices, int n_users, int n_rbgs, int rbg_size, int threads, int sched, char* err, size_t errlen);
+
+/* Resident averages (ABI 11 addition, no layout changed): a cell of a group may keep what RadioBearer keeps for the PF metric on the
+ * device -- every user's average rate (m_averageTransmissionRate), the bytes granted since the last update (m_transmittedData) and
+ * the time of that update (m_lastUpdate) -- next to its slice state.  A call through rs_group_schedule_tti_at then does
+ * DoSchedule()'s first line, UpdateAverageTransmissionRate() (ref: src/flows/radio-bearer.cpp:139-164), on the device, schedules the
+ * TTI on the result and records the TTI's grants for the next update; once cqi_epoch matches, such a call sends only the slot header
+ * and the slice ids of the cell.  Per resident slot, in this order:
+ *   1. now == last_update: nothing is updated (the reference's early return).  Otherwise, for EVERY user id u of the config, named by
+ *      the call or not:  rate = (double)(pending[u] * 8) / (now - last_update);  a = ((1 - 0.02) * a) + (0.02 * rate);
+ *      if (a < 1) a = 1;  pending[u] = 0;  -- then last_update = now.  (The batch kernels' operations, in their order, unfused.)
+ *   2. The call's users (user_id[i], or 0..n-1) are scheduled as by rs_group_schedule_tti with avg_rate[i] = avg[user_id[i]].
+ *   3. Each served user's grant, min(tbs_bits / 8, 100000000) bytes (the InfiniteBuffer's dataToTransmit), is added to pending[user_id[i]].
+ * A cell is one bearer per user.  A user that holds two bearers needs the ((1 + a0) + a1) - 1 form of avg_rate and
+ * stays on the plain call.  A caller whose bearers have finite queues, where DoStopSchedule credits min(grant, dataToTransmit)
+ * (downlink-transport-scheduler.cpp:177-188) and not the transport block, overwrites the pending bytes after the call
+ * (rs_group_set_pending: a synchronising copy, outside the fast path).
+ * rs_group_schedule_tti is unchanged: it still needs avg_rate, and on a resident cell it uses the caller's averages and neither reads
+ * nor writes the resident state.
+ * A specialised group (rs_group_specialize) serves resident calls with the resident kernel built into the library; run-time builds of
+ * the resident form, and their self-check, are a follow-up.  rs_group_kernel_name reports that kernel
+ * ("rs_group_resident_kernel<sched, ept>") while a resident call is the last one served. */
+/* Makes `cell` resident (again, at any time between two calls): avg[cfg.n_users] by user id, zero pending bytes, last_update =
+ * m_lastUpdate.  RS_ERR_INVALID for an average that is not in 1..2^52 (an updated average is never below 1; the upper bound keeps
+ * the metric scan's FP32 filter in its range without the host seeing the values -- DESIGN.md 7d) or a last_update that is not finite. */
+int rs_group_set_avg(rs_group* g, int32_t cell, const double* avg /* [cfg.n_users], by user id */, double last_update);
+/* The resident state as it is after the last call (a synchronising copy for tests, checkpoints and logs; not part of a TTI).  Each
+ * output may be NULL.  RS_ERR_STATE: the cell is not resident. */
+int rs_group_get_avg(rs_group* g, int32_t cell, double* avg /* [U] or NULL */, int32_t* pending_bytes /* [U] or NULL */, double* last_update /* or NULL */);
+/* Overwrites the bytes that wait for the next update (0 <= bytes < 2^28: times 8 an int32); a synchronising copy, outside the fast path */
+int rs_group_set_pending(rs_group* g, int32_t cell, const int32_t* pending_bytes /* [U] */);
+/* rs_group_schedule_tti for resident cells; now[k] is the simulator clock of cell cell_ids[k]'s TTI.  Every rule of a group call
+ * holds (uniform presence of optional inputs, cqi_epoch per cell, subsets and permutations through cell_ids; a rejected call
+ * launches nothing and moves nothing; rs_group_launch_count and rs_group_image_stats count these calls like any others), and
+ *   - in[k].avg_rate is NULL for every k (RS_ERR_INVALID);
+ *   - every named cell is resident (RS_ERR_STATE, the message names the cell);
+ *   - now[k] is finite, not before the cell's last_update, and now[k] - last_update is 0 or at least 2^-20 s (RS_ERR_INVALID); a
+ *     shorter interval is accepted only while no byte can be pending (no resident call since rs_group_set_avg or an all-zero
+ *     rs_group_set_pending), as for a first TTI at 0.1 + 7e-17 s behind an m_lastUpdate of 0.1;
+ *   - the config's exponents are in {0, 1} (RS_ERR_INVALID: the general exponents' pow() of the averages is taken on the host).
+ * hol_delay outside the FP32 filter's range still switches the call to the exact scan.  A call that fails with RS_ERR_HIP leaves the
+ * cells it named not resident. */
+int rs_group_schedule_tti_at(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in /* [n] */, rs_tti_out* out /* [n] */, const double* now /* [n] */);
 
 /* ------------------------------------------------------------------------------------------
  * Batched mode: many independent cells resident on the device, whole DoSchedule() loops

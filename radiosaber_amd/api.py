@@ -110,6 +110,7 @@ ABI_SYMBOLS = [
     "rs_group_create", "rs_group_create_checked", "rs_group_destroy", "rs_group_schedule_tti",
     "rs_group_get_slice_offset", "rs_group_set_slice_offset", "rs_group_launch_count", "rs_group_kernel_name",
     "rs_group_image_stats", "rs_group_specialize", "rs_group_jit_status", "rs_jit_selfcheck_group",
+    "rs_group_set_avg", "rs_group_get_avg", "rs_group_set_pending", "rs_group_schedule_tti_at",
 ]
 
 _lib = None
@@ -151,6 +152,10 @@ def lib():
     L.rs_group_kernel_name.restype = C.c_char_p
     L.rs_group_kernel_name.argtypes = [C.c_void_p]
     L.rs_group_specialize.argtypes = [C.c_void_p]
+    L.rs_group_set_avg.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.c_double]
+    L.rs_group_get_avg.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double)]
+    L.rs_group_set_pending.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+    L.rs_group_schedule_tti_at.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_TtiIn), C.POINTER(_TtiOut), C.POINTER(C.c_double)]
     L.rs_group_jit_status.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.rs_jit_selfcheck_group.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
     L.rs_batch_create.restype = C.c_void_p
@@ -511,8 +516,8 @@ def _marshal_tti(S, R, rbg_size, sched, cqi, avg_rate, rand0=0, rand1=0, user_id
         cqi = np.ascontiguousarray(cqi, np.uint8)
         n = cqi.shape[0]
         assert cqi.shape == (n, R)
-    avg = np.ascontiguousarray(avg_rate, np.float64)
-    assert avg.shape == (n,)
+    avg = None if avg_rate is None else np.ascontiguousarray(avg_rate, np.float64)  # (None: a resident call, GroupScheduler.schedule_tti_at)
+    assert avg is None or avg.shape == (n,)
     uid = None if user_id is None else np.ascontiguousarray(user_id, np.int32)
     hol = None if hol_delay is None else np.ascontiguousarray(hol_delay, np.float64)
     prio = None if prio_has_data is None else np.ascontiguousarray(prio_has_data, np.uint8)
@@ -524,7 +529,7 @@ def _marshal_tti(S, R, rbg_size, sched, cqi, avg_rate, rand0=0, rand1=0, user_id
     res = TtiResult(np.zeros(S, np.int32), np.zeros(S, np.int32), np.zeros(R, np.int32),
                     np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32))
     tin = _TtiIn(n, _p(uid, C.c_int32) if uid is not None else None,
-                 _p(cqi, C.c_uint8) if cqi is not None else None, _p(avg, C.c_double), rand0, rand1,
+                 _p(cqi, C.c_uint8) if cqi is not None else None, _p(avg, C.c_double) if avg is not None else None, rand0, rand1,
                  _p(prb, C.c_uint8) if prb is not None else None,
                  _p(hol, C.c_double) if hol is not None else None,
                  _p(prio, C.c_uint8) if prio is not None else None,
@@ -654,6 +659,48 @@ class GroupScheduler:
         ids = None if cell_ids is None else np.ascontiguousarray(cell_ids, np.int32)
         assert ids is None or ids.shape == (n,)
         _check(lib().rs_group_schedule_tti(self._h, n, _p(ids, C.c_int32) if ids is not None else None, ins, outs))
+        return results
+
+    # ---- resident averages: the cell's PF averages, pending bytes and last-update time stay on the device ----
+    def set_avg(self, cell, avg, last_update):
+        """rs_group_set_avg: makes `cell` resident with avg [n_users] by user id (1 <= avg <= 2**52), zero pending bytes and
+        last_update (RadioBearer's m_lastUpdate).  Any time between two calls."""
+        a = np.ascontiguousarray(avg, np.float64)
+        assert a.shape == (self.slices.n_users,)
+        _check(lib().rs_group_set_avg(self._h, cell, _p(a, C.c_double), float(last_update)))
+
+    def get_avg(self, cell):
+        """(avg float64 [n_users], pending bytes int32 [n_users], last_update) of a resident cell: a synchronising copy, not part of a TTI."""
+        a = np.zeros(self.slices.n_users, np.float64)
+        pend = np.zeros(self.slices.n_users, np.int32)
+        last = C.c_double(0)
+        _check(lib().rs_group_get_avg(self._h, cell, _p(a, C.c_double), _p(pend, C.c_int32), C.byref(last)))
+        return a, pend, float(last.value)
+
+    def set_pending(self, cell, pending_bytes):
+        """rs_group_set_pending: overwrites the bytes that wait for the cell's next update (finite queues: what DoStopSchedule
+        credited instead of the transport blocks).  Outside the fast path."""
+        b = np.ascontiguousarray(pending_bytes, np.int32)
+        assert b.shape == (self.slices.n_users,)
+        _check(lib().rs_group_set_pending(self._h, cell, _p(b, C.c_int32)))
+
+    def schedule_tti_at(self, calls: Sequence[dict], now, cell_ids: Optional[Sequence[int]] = None) -> List[TtiResult]:
+        """rs_group_schedule_tti_at: schedule_tti for resident cells.  calls[k] as for schedule_tti but without avg_rate; now[k] is
+        the simulator clock of that cell's TTI (a scalar: the same for every cell).  Per cell the device applies the reference's
+        EWMA to every user's average, schedules the TTI on the result and records the grants for the next update."""
+        n = len(calls)
+        ins, outs, results, keep = (_TtiIn * n)(), (_TtiOut * n)(), [], []
+        for k, kw in enumerate(calls):
+            kw = dict(kw)
+            tin, tout, res, arrays = _marshal_tti(self.slices.n_slices, self.R, self.rbg_size, self.sched, kw.pop("cqi", None),
+                                                  kw.pop("avg_rate", None), **kw)
+            ins[k], outs[k] = tin, tout
+            results.append(res)
+            keep.append(arrays)
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(now, np.float64), (n,)))
+        ids = None if cell_ids is None else np.ascontiguousarray(cell_ids, np.int32)
+        assert ids is None or ids.shape == (n,)
+        _check(lib().rs_group_schedule_tti_at(self._h, n, _p(ids, C.c_int32) if ids is not None else None, ins, outs, _p(t, C.c_double)))
         return results
 
     def slice_offset(self, cell):

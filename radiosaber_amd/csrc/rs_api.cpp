@@ -1884,10 +1884,13 @@ struct TtiPack {
  * bytes, the CQI grid with its zero padding (reuse_grid: left alone -- rs_tti_in.cqi_epoch), averages or the general exponents'
  * denominators, the exact-scan test, draws, gate, HoL delays and priority flags.  Shared by rs_schedule_tti (its one block) and
  * rs_group_schedule_tti (one slot per cell): the two paths cannot drift apart.  Touches nothing but `h_in` and `pk`. */
-int pack_tti(const rs_batch* b, const rs_tti_in* in, const rs_tti_out* out, uint8_t* h_in, bool reuse_grid, TtiPack* pk) {
+int pack_tti(const rs_batch* b, const rs_tti_in* in, const rs_tti_out* out, uint8_t* h_in, bool reuse_grid, TtiPack* pk, bool resident_avg = false) {
   const int n = in->n_users, R = b->R, S = b->S;
   if (n < 1 || n > b->U) return fail(RS_ERR_INVALID, "n_users %d outside 1..%d", n, b->U);
-  if ((!in->cqi && !in->cqi_prb) || !in->avg_rate) return fail(RS_ERR_INVALID, "null cqi/avg_rate");
+  /* resident_avg (rs_group_schedule_tti_at): the cell's averages are on the device -- none are given, and the place of the averages in
+   * the block carries the call's user ids instead when it names them (4 of the 8 bytes per user) */
+  if (resident_avg && in->avg_rate) return fail(RS_ERR_INVALID, "avg_rate must be NULL: the cell's averages are resident on the device");
+  if ((!in->cqi && !in->cqi_prb) || (!in->avg_rate && !resident_avg)) return fail(RS_ERR_INVALID, "null cqi/avg_rate");
   if (!out->rbg_to_user || !out->user_tbs_bits) return fail(RS_ERR_INVALID, "null output array");
   const CtxLayout l = ctx_layout(n, R, S, b->G, b->sched == RS_SCHED_NVS_NONGREEDY);
   pk->l = l;
@@ -1917,8 +1920,12 @@ int pack_tti(const rs_batch* b, const rs_tti_in* in, const rs_tti_out* out, uint
   }
   if (!reuse_grid) memset(h_in + l.grid + (size_t)n * R, 0, l.slice - (size_t)n * R);
   pk->grid_touched = true;
-  memcpy(h_in + l.avg, in->avg_rate, 8 * (size_t)n);
-  if (b->gen_exp) {
+  if (resident_avg) {
+    if (in->user_id) memcpy(h_in + l.avg, in->user_id, 4 * (size_t)n);
+  } else {
+    memcpy(h_in + l.avg, in->avg_rate, 8 * (size_t)n);
+  }
+  if (b->gen_exp && !resident_avg) { /* (a resident call of such a config is refused before it gets here) */
     /* general exponents: pow(averageRate / 1000.0, psi) with averageRate = 1 + the caller's sum (ref: :681-693), host libm */
     double* den = (double*)(h_in + l.avg);
     for (int i = 0; i < n; i++) {
@@ -1935,7 +1942,8 @@ int pack_tti(const rs_batch* b, const rs_tti_in* in, const rs_tti_out* out, uint
   bool exact_scan = b->gen_exp; /* (powers of any size: no FP32 ranking, every user is compared with the reference's expression) */
   if (!exact_scan) {
     auto ordinary = [](double x, double lo, double hi) { return x >= lo && x <= hi; }; /* false for NaN */
-    for (int i = 0; i < n; i++) {
+    /* (resident averages are inside the range by construction: kResidentAvgMax / kResidentMinDt below) */
+    for (int i = 0; i < n && !resident_avg; i++) {
       const double a = in->avg_rate[i];
       const double k = b->sched == RS_SCHED_PF ? a : (1 + a) / 1000.0;
       exact_scan |= !ordinary(k, 0x1p-60, 0x1p60);
@@ -2427,6 +2435,15 @@ struct rs_group {
   uint8_t *d_out2 = nullptr, *d_chk = nullptr; /* the built-in kernel's output slots; the group's slice state + scalars before / after it */
   std::vector<uint8_t> h_out2;
   char jit_msg[512] = "";
+  /* resident averages (rs_group_set_avg, rs_group_schedule_tti_at): per cell [U] averages, [U] pending bytes and the time of their
+   * last update on the device (allocated by the first rs_group_set_avg), the gather rows of calls that name their users, and on the
+   * host which cells are resident and a mirror of their last-update times (the clock check needs no read-back) */
+  double *d_ravg = nullptr, *d_rlast = nullptr, *d_rgather = nullptr;
+  int32_t *d_rpend = nullptr, *d_ruid = nullptr;
+  std::vector<uint8_t> resident, pending_zero; /* pending_zero: no byte can be waiting (nothing served since rs_group_set_avg / an all-zero rs_group_set_pending) */
+  std::vector<double> last_update;
+  bool last_call_resident = false;
+  char kname_res[56] = "";
 };
 
 namespace {
@@ -2506,6 +2523,10 @@ rs_group* rs_group_create(const rs_config* cfg, int32_t n_cells) {
   const int ept = (b->R * b->S + b->threads - 1) / b->threads;
   const bool sorts = b->sched == RS_SCHED_MAXCELL || b->sched == RS_SCHED_UPPERBOUND;
   snprintf(g->kname, sizeof g->kname, "rs_group_kernel<%d, %d>", b->sched, sorts && ept <= 4 ? ept : 0);
+  snprintf(g->kname_res, sizeof g->kname_res, "rs_group_resident_kernel<%d, %d>", b->sched, sorts && ept <= 4 ? ept : 0);
+  g->resident.assign(n_cells, 0);
+  g->pending_zero.assign(n_cells, 0);
+  g->last_update.assign(n_cells, 0.0);
   g_err[0] = 0;
   return g;
 }
@@ -2524,15 +2545,56 @@ void rs_group_destroy(rs_group* g) {
   if (g->d_prb) (void)hipFree(g->d_prb);
   if (g->d_out2) (void)hipFree(g->d_out2);
   if (g->d_chk) (void)hipFree(g->d_chk);
+  if (g->d_ravg) (void)hipFree(g->d_ravg);
+  if (g->d_rpend) (void)hipFree(g->d_rpend);
+  if (g->d_rlast) (void)hipFree(g->d_rlast);
+  if (g->d_rgather) (void)hipFree(g->d_rgather);
+  if (g->d_ruid) (void)hipFree(g->d_ruid);
   if (g->h_in) (void)hipHostFree(g->h_in);
   if (g->h_out) (void)hipHostFree(g->h_out);
   rs_batch_destroy(g->b);
   delete g;
 }
 
+extern "C" hipError_t rs_launch_group_resident(const RsLaunch* p, int threads, hipStream_t stream);
+
+namespace {
+/* Resident averages and the FP32 filter.  The metric scan's filter needs (1 + a) / 1000 (scheduler 1: a) inside [2^-60, 2^60] for every
+ * average a (pack_tti); a resident average is not on the host to be inspected, so the library keeps it inside by construction:
+ *   below   every update ends with `if (a < 1) a = 1` and rs_group_set_avg refuses a < 1: a >= 1, so a >= 2^-60 and (1 + a) / 1000 >= 2^-9;
+ *   above   an update makes a' = 0.98 a + 0.02 rate, a weighted mean: a' <= max(a, rate) up to three roundings (2^-51 relative).
+ *           rate = (double)(pending * 8) / dt with pending * 8 an int32 product, as the reference's (the device forms it so that it
+ *           wraps where grants of calls that repeat one clock value pile up past 2^28 bytes; rs_group_set_pending refuses such
+ *           values), so |rate| < 2^31 / dt whatever pending holds, and a call is
+ *           refused unless dt = now - last_update is 0 (no update) or at least kResidentMinDt = 2^-20 s (a TTI is 2^-10 s): rate < 2^51.
+ *           (A shorter interval is accepted while no byte can be pending -- no resident call since rs_group_set_avg or an all-zero
+ *           rs_group_set_pending: rate = 0 / dt = 0 whatever dt > 0 is.  A run that starts as the reference's does, m_lastUpdate = 0.1
+ *           and a first TTI at the clock's hundredth tick, 0.1 + 7e-17, needs that.)
+ *           rs_group_set_avg refuses a > kResidentAvgMax = 2^52.  So a <= 2^52 (1 + 2^-51)^k after k updates, and 2^52 to 2^60 is a
+ *           factor the roundings would need more than 2^53 updates for; (1 + a) / 1000 is smaller still.
+ *   NaN     a finite, dt finite and > 0: no operation of the update makes one.
+ * hol_delay is still the caller's and still switches a call to the exact scan. */
+constexpr double kResidentAvgMax = 0x1p52;
+constexpr double kResidentMinDt = 0x1p-20;
+
+int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out, const double* now);
+}  // namespace
+
 int rs_group_schedule_tti(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out) {
   if (!g || !in || !out) return fail(RS_ERR_INVALID, "null argument");
+  return group_schedule(g, n, cell_ids, in, out, nullptr);
+}
+
+int rs_group_schedule_tti_at(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out, const double* now) {
+  if (!g || !in || !out || !now) return fail(RS_ERR_INVALID, "null argument");
+  return group_schedule(g, n, cell_ids, in, out, now);
+}
+
+namespace {
+/* one group call; now != null: the resident form (rs_group_schedule_tti_at) */
+int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out, const double* now) {
   rs_batch* b = g->b;
+  const bool res = now != nullptr;
   using clk = std::chrono::steady_clock;
   const clk::time_point t0 = g->timing ? clk::now() : clk::time_point();
   if (n < 1 || n > g->n_cells) return fail(RS_ERR_INVALID, "n %d outside 1..%d (the group's cells)", n, g->n_cells);
@@ -2562,6 +2624,20 @@ int rs_group_schedule_tti(rs_group* g, int32_t n, const int32_t* cell_ids, const
                      : upper_of(out[k]) != want_upper ? "upper_rbg / upper_user" : nullptr;
     if (what) return fail(RS_ERR_INVALID, "mixed call: cell slot %d and cell slot 0 differ in whether they give %s (optional inputs are given by every cell of a call or by none)", k, what);
   }
+  if (res) {
+    if (b->gen_exp)
+      return fail(RS_ERR_INVALID, "resident averages need exponents in {0, 1}: the general exponents' pow() of the averages is taken on the host per call");
+    for (int k = 0; k < n; k++) {
+      const int cell = cell_ids ? cell_ids[k] : k;
+      if (in[k].avg_rate) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): avg_rate must be NULL: the cell's averages are resident on the device", k, cell);
+      if (!g->resident[cell]) return fail(RS_ERR_STATE, "cell slot %d: cell %d is not resident (rs_group_set_avg first)", k, cell);
+      const double last = g->last_update[cell];
+      if (!std::isfinite(now[k])) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): now is not finite", k, cell);
+      if (now[k] < last) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): now = %.17g lies before the cell's last update at %.17g", k, cell, now[k], last);
+      if (now[k] != last && !(now[k] - last >= kResidentMinDt) && !g->pending_zero[cell])
+        return fail(RS_ERR_INVALID, "cell slot %d (cell %d): now - last_update = %.3g s is neither 0 nor at least %.3g s, and the cell may have bytes pending", k, cell, now[k] - last, kResidentMinDt);
+    }
+  }
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   bool exact_scan = false;
   for (int k = 0; k < n; k++) {
@@ -2577,7 +2653,7 @@ int rs_group_schedule_tti(rs_group* g, int32_t n, const int32_t* cell_ids, const
                             im.has_ids == (in[k].user_id != nullptr) &&
                             (!in[k].user_id || memcmp(im.ids.data(), in[k].user_id, 4 * (size_t)im.n) == 0);
     g->modes[k] = (uint8_t)(epoch == 0 ? 0 : (reuse_grid ? 2 : 1));
-    const int rc = pack_tti(b, &in[k], &out[k], slot + RS_GROUP_HDR_BYTES, reuse_grid, &pk);
+    const int rc = pack_tti(b, &in[k], &out[k], slot + RS_GROUP_HDR_BYTES, reuse_grid, &pk, res);
     if (rc) {
       char msg[sizeof g_err];
       snprintf(msg, sizeof msg, "%s", g_err);
@@ -2601,6 +2677,10 @@ int rs_group_schedule_tti(rs_group* g, int32_t n, const int32_t* cell_ids, const
     h.in_gate = (int32_t)l.gate; h.in_prb = (int32_t)l.prb;
     h.out_uinfo = (int32_t)l.uinfo; h.out_map = (int32_t)l.map; h.out_quota = (int32_t)l.quota; h.out_target = (int32_t)l.target;
     h.out_upper = (int32_t)l.upper;
+    if (res) {
+      h.in_uid = in[k].user_id ? (int32_t)l.avg : 0; /* (l.avg lies behind the grid and the slice ids: never 0) */
+      h.now = now[k];
+    }
     memcpy(slot, &h, sizeof h);
   }
   /* the per-PRB store comes with the first call that gives per-PRB reports under a number.  (Until it exists no record says "per-PRB",
@@ -2622,11 +2702,14 @@ int rs_group_schedule_tti(rs_group* g, int32_t n, const int32_t* cell_ids, const
     }
   /* from here on the device is touched: a failure leaves the named cells' images in an unknown state */
   struct ImageGuard {
-    rs_group* g; int n; const int32_t* ids; bool ok;
+    rs_group* g; int n; const int32_t* ids; bool ok, res;
     ~ImageGuard() {
-      if (!ok) for (int k = 0; k < n; k++) g->img[ids ? ids[k] : k].valid = false;
+      if (!ok) for (int k = 0; k < n; k++) {
+        g->img[ids ? ids[k] : k].valid = false;
+        if (res) g->resident[ids ? ids[k] : k] = 0; /* (averages half updated, perhaps: resident again with rs_group_set_avg) */
+      }
     }
-  } guard{g, n, cell_ids, false};
+  } guard{g, n, cell_ids, false, res};
   hipStream_t st = b->stream;
   const clk::time_point t1 = g->timing ? clk::now() : clk::time_point();
   /* per-PRB reports and queue state are read again and again inside the TTI: those calls keep the device copies.  (The copy sends
@@ -2661,6 +2744,13 @@ int rs_group_schedule_tti(rs_group* g, int32_t n, const int32_t* cell_ids, const
   L.grp_in_stride = (int64_t)g->in_stride;
   L.grp_out_stride = (int64_t)g->out_stride;
   L.grp_count = g->d_count;
+  if (res) {
+    L.grp_avg = g->d_ravg;
+    L.grp_pending = g->d_rpend;
+    L.grp_last = g->d_rlast;
+    L.grp_gather = g->d_rgather;
+    L.grp_uid = g->d_ruid;
+  }
   bool poll = zc && g->poll;
   if (poll) {
     if (++g->seq == 0) g->seq = 1; /* (0 is the word's initial value) */
@@ -2669,9 +2759,9 @@ int rs_group_schedule_tti(rs_group* g, int32_t n, const int32_t* cell_ids, const
   }
   /* rs_group_specialize: the group's own build -- its lean form when the call is plain for every cell (the uniform-presence rules above
    * make that a fact of the launch), the general one otherwise */
-  RsJitKernel* kd = g->jit[0];
+  RsJitKernel* kd = res ? nullptr : g->jit[0]; /* (a resident call: the built-in resident kernel, whatever serves the plain calls) */
   int which = 0;
-  if (g->jit[1] && !has_prb && !L.queue_mode && !has_gate && !L.exact_scan && !L.gen_exp && !want_upper && !L.synthetic) { kd = g->jit[1]; which = 1; }
+  if (!res && g->jit[1] && !has_prb && !L.queue_mode && !has_gate && !L.exact_scan && !L.gen_exp && !want_upper && !L.synthetic) { kd = g->jit[1]; which = 1; }
   /* A build without the self-check mark serves its first calls beside the built-in group kernel (rs_group_jit_status): same slots,
    * same slice state; every named cell's output fields and the slice state left behind must agree. */
   const bool checked_call = kd != nullptr && g->chk_left[which] > 0;
@@ -2696,8 +2786,10 @@ int rs_group_schedule_tti(rs_group* g, int32_t n, const int32_t* cell_ids, const
     L.done_flag = nullptr; /* completion by the stream */
   }
   if (kd) HIP_TRY(rs_jit_launch(kd, &L, st));
+  else if (res) HIP_TRY(rs_launch_group_resident(&L, b->threads, st));
   else HIP_TRY(rs_launch_group(&L, b->threads, st));
   g->launches++;
+  g->last_call_resident = res;
   if (!zc) HIP_TRY(hipMemcpyAsync(g->h_out, g->d_out, (size_t)n * g->out_stride, hipMemcpyDeviceToHost, st));
   const clk::time_point t2 = g->timing ? clk::now() : clk::time_point();
   bool seen = false;
@@ -2771,6 +2863,11 @@ int rs_group_schedule_tti(rs_group* g, int32_t n, const int32_t* cell_ids, const
     }
   }
   guard.ok = true;
+  if (res) /* the launch has completed: the cells' updates are dated now[k], and grants may be waiting */
+    for (int k = 0; k < n; k++) {
+      g->last_update[cell_ids ? cell_ids[k] : k] = now[k];
+      g->pending_zero[cell_ids ? cell_ids[k] : k] = 0;
+    }
   const clk::time_point t3 = g->timing ? clk::now() : clk::time_point();
   /* the launch has completed: the device holds these calls' reports now */
   for (int k = 0; k < n; k++) {
@@ -2802,6 +2899,76 @@ int rs_group_schedule_tti(rs_group* g, int32_t n, const int32_t* cell_ids, const
              "cqi_epoch were 0 from now on (same results, the block is sent on every call)", g->prb_stride * (size_t)g->n_cells);
   return RS_OK;
 }
+}  // namespace
+
+int rs_group_set_avg(rs_group* g, int32_t cell, const double* avg, double last_update) {
+  if (!g || !avg) return fail(RS_ERR_INVALID, "null argument");
+  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
+  rs_batch* b = g->b;
+  const size_t U = (size_t)b->U;
+  if (!std::isfinite(last_update)) return fail(RS_ERR_INVALID, "last_update is not finite");
+  for (size_t u = 0; u < U; u++)
+    if (!(avg[u] >= 1 && avg[u] <= kResidentAvgMax)) /* (false for NaN) */
+      return fail(RS_ERR_INVALID, "avg[%zu] = %g outside 1..2^52 (an updated average is never below 1; the bound above keeps the FP32 filter's range)", u, avg[u]);
+  HIP_TRY(hipSetDevice(b->cfg.cell.device));
+  if (!g->d_ravg) {
+    const size_t nu = U * (size_t)g->n_cells;
+    const bool ok = hipMalloc(&g->d_ravg, 8 * nu) == hipSuccess && hipMalloc(&g->d_rgather, 8 * nu) == hipSuccess &&
+                    hipMalloc(&g->d_rpend, 4 * nu) == hipSuccess && hipMalloc(&g->d_ruid, 4 * nu) == hipSuccess &&
+                    hipMalloc(&g->d_rlast, 8 * (size_t)g->n_cells) == hipSuccess;
+    if (!ok) {
+      (void)hipGetLastError();
+      for (void* q : {(void*)g->d_ravg, (void*)g->d_rgather, (void*)g->d_rpend, (void*)g->d_ruid, (void*)g->d_rlast})
+        if (q) (void)hipFree(q);
+      g->d_ravg = g->d_rgather = g->d_rlast = nullptr;
+      g->d_rpend = g->d_ruid = nullptr;
+      return fail(RS_ERR_HIP, "allocation of the group's resident averages failed (%zu bytes)", 24 * nu + 8 * (size_t)g->n_cells);
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  g->resident[cell] = 0; /* (until all three copies are through) */
+  HIP_TRY(hipMemcpy(g->d_ravg + (size_t)cell * U, avg, 8 * U, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(g->d_rpend + (size_t)cell * U, 0, 4 * U));
+  HIP_TRY(hipMemcpy(g->d_rlast + cell, &last_update, 8, hipMemcpyHostToDevice));
+  g->resident[cell] = 1;
+  g->pending_zero[cell] = 1;
+  g->last_update[cell] = last_update;
+  return RS_OK;
+}
+
+int rs_group_get_avg(rs_group* g, int32_t cell, double* avg, int32_t* pending_bytes, double* last_update) {
+  if (!g) return fail(RS_ERR_INVALID, "null group");
+  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
+  if (!g->resident[cell]) return fail(RS_ERR_STATE, "cell %d is not resident (rs_group_set_avg first)", cell);
+  rs_batch* b = g->b;
+  const size_t U = (size_t)b->U;
+  HIP_TRY(hipSetDevice(b->cfg.cell.device));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  if (avg) HIP_TRY(hipMemcpy(avg, g->d_ravg + (size_t)cell * U, 8 * U, hipMemcpyDeviceToHost));
+  if (pending_bytes) HIP_TRY(hipMemcpy(pending_bytes, g->d_rpend + (size_t)cell * U, 4 * U, hipMemcpyDeviceToHost));
+  if (last_update) HIP_TRY(hipMemcpy(last_update, g->d_rlast + cell, 8, hipMemcpyDeviceToHost));
+  return RS_OK;
+}
+
+int rs_group_set_pending(rs_group* g, int32_t cell, const int32_t* pending_bytes) {
+  if (!g || !pending_bytes) return fail(RS_ERR_INVALID, "null argument");
+  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
+  if (!g->resident[cell]) return fail(RS_ERR_STATE, "cell %d is not resident (rs_group_set_avg first)", cell);
+  rs_batch* b = g->b;
+  const size_t U = (size_t)b->U;
+  bool all_zero = true;
+  for (size_t u = 0; u < U; u++) {
+    if (pending_bytes[u] < 0 || pending_bytes[u] >= (1 << 28)) /* (times 8 it stays an int32) */
+      return fail(RS_ERR_INVALID, "pending_bytes[%zu] = %d outside 0..2^28-1", u, pending_bytes[u]);
+    all_zero &= pending_bytes[u] == 0;
+  }
+  HIP_TRY(hipSetDevice(b->cfg.cell.device));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  g->pending_zero[cell] = 0; /* (until the copy is through) */
+  HIP_TRY(hipMemcpy(g->d_rpend + (size_t)cell * U, pending_bytes, 4 * U, hipMemcpyHostToDevice));
+  g->pending_zero[cell] = all_zero ? 1 : 0;
+  return RS_OK;
+}
 
 int rs_group_get_slice_offset(rs_group* g, int32_t cell, double* offset) {
   if (!g || !offset) return fail(RS_ERR_INVALID, "null argument");
@@ -2831,7 +2998,11 @@ int rs_group_image_stats(const rs_group* g, int64_t out[3]) {
   return RS_OK;
 }
 
-const char* rs_group_kernel_name(rs_group* g) { return !g ? "" : (g->jit[0] ? "rs_group_kernel_jit" : g->kname); }
+const char* rs_group_kernel_name(rs_group* g) {
+  if (!g) return "";
+  if (g->last_call_resident) return g->kname_res; /* (resident calls run the built-in resident kernel, specialised group or not) */
+  return g->jit[0] ? "rs_group_kernel_jit" : g->kname;
+}
 
 /* Shape specialisation of a group: rs_ctx_specialize for the group surface -- the one-TTI form compiled for the config's slices, RBGs,
  * PRBs per RBG, scheduler, workgroup size and user CAPACITY, entry point rs_group_kernel_jit (one workgroup per call slot), in a

@@ -360,6 +360,16 @@ struct RsLaunch {
   int64_t grp_image_stride;  /* round_up(rs_upad_of(U) * R, 16) of the config's U */
   uint8_t* grp_prb;          /* [group cells][grp_prb_stride]: [n][R*G] of the cell's last stored reports; null until first needed */
   int64_t grp_prb_stride;    /* round_up(U * R * G, 16) */
+  /* group calls, resident averages (rs_group_schedule_tti_at, rs_group_resident_kernel): a CELL of the group may keep RadioBearer's three
+   * words per user on the device -- m_averageTransmissionRate, the bytes granted since the last update (m_transmittedData) and the
+   * time of that update (m_lastUpdate, one per cell) -- all in HBM, indexed by user id of the config, one stride of the config's U
+   * apart.  grp_gather / grp_uid: per cell, the call's averages in call order and the ids they belong to when the call names its
+   * users (user_id); the workgroup that writes a row is the only one that reads it.  Read by the resident kernels alone; null in every other launch. */
+  double* grp_avg;           /* [group cells][U] */
+  int32_t* grp_pending;      /* [group cells][U] */
+  double* grp_last;          /* [group cells] */
+  double* grp_gather;        /* [group cells][U] */
+  int32_t* grp_uid;          /* [group cells][U]: the ids that grp_gather's row was gathered by */
 };
 
 /* per-slot header of a group call, written by the host (rs_api.cpp: group_fill_header) */
@@ -374,8 +384,14 @@ struct RsGroupCell {
    * behind as the cell's image (per-PRB reports: copy the slot's block to the cell's store too); 2 the slot's grid area (and per-PRB
    * block) is stale -- load the cell's image, link adaptation reads the cell's per-PRB store */
   int32_t image_mode;
-  int32_t pad_[RS_GROUP_HDR_BYTES / 4 - 19];
+  /* resident averages (rs_group_schedule_tti_at; the other kernels read neither): where the call's user_id list lies behind the header
+   * (0: the call's users are 0..U-1; else it takes the place of the averages, which such a call does not send), and the simulator
+   * clock of this cell's TTI */
+  int32_t in_uid;
+  double now;
+  int32_t pad_[RS_GROUP_HDR_BYTES / 4 - 22];
 };
 static_assert(sizeof(RsGroupCell) == RS_GROUP_HDR_BYTES, "the slot header keeps its size: new words come out of its padding");
+static_assert(__builtin_offsetof(RsGroupCell, image_mode) == 72 && __builtin_offsetof(RsGroupCell, now) == 80, "no existing word of the slot header moves");
 
 #endif /* RS_DEVICE_H_ */

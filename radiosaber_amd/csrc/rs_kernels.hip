@@ -778,7 +778,17 @@ template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
   constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
-  constexpr bool kGrpFixed = false, kGrpLean = false;
+  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false;
+#include "rs_phase_group.inc"
+}
+
+/* ... and its resident form (rs_group_schedule_tti_at): the cells' PF averages, pending bytes and last-update times stay on the device.
+ * Kernels of their own, the same 14 shapes (rs_launch_group_resident): the plain group kernels above carry none of it. */
+template <int SCHED, int EPT>
+__global__ void __launch_bounds__(512, 4) rs_group_resident_kernel(RsLaunch p) {
+  extern __shared__ __align__(16) unsigned char lds[];
+  constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
+  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = true;
 #include "rs_phase_group.inc"
 }
 #else
@@ -812,7 +822,7 @@ extern "C" __global__ void __launch_bounds__(RS_JIT_NT, RS_JIT_WPE) rs_group_ker
   constexpr RsCarve kCv = rs_carve(RS_JIT_S, RS_JIT_U, RS_JIT_R, RS_JIT_SCHED, RS_JIT_NT, RS_JIT_CARVEQ, RS_JIT_WIN);
   __shared__ __align__(16) unsigned char lds[kCv.lds_bytes];
   constexpr int kGrpSched = RS_JIT_SCHED, kGrpEpt = (RS_JIT_SCHED != 9 && RS_JIT_SCHED != 10) ? 0 : (kCv.ept <= 4 ? kCv.ept : 0);
-  constexpr bool kGrpFixed = true;
+  constexpr bool kGrpFixed = true, kGrpRes = false; /* (resident calls of a specialised group run the built-in resident kernel) */
 #include "rs_phase_group.inc"
 }
 #else
@@ -1003,6 +1013,38 @@ extern "C" hipError_t rs_launch_group(const RsLaunch* p, int threads, hipStream_
   return hipGetLastError();
 }
 
+/* a resident group call (rs_group_schedule_tti_at): the same grid, the kernels that keep the cells' averages on the device */
+extern "C" hipError_t rs_launch_group_resident(const RsLaunch* p, int threads, hipStream_t stream) {
+  dim3 grid(p->n_cells), block(threads);
+  const int ept = (p->R * p->S + threads - 1) / threads;
+  if (!p->grp_avg || !p->grp_pending || !p->grp_last || !p->grp_gather || !p->grp_uid) return hipErrorInvalidValue;
+#define RS_LAUNCH_GROUP(SCHED_, EPT_) hipLaunchKernelGGL((rs_group_resident_kernel<SCHED_, EPT_>), grid, block, p->lds_bytes, stream, *p)
+  switch (p->sched) {
+    case 1: RS_LAUNCH_GROUP(1, 0); break;
+    case 7: RS_LAUNCH_GROUP(7, 0); break;
+    case 8: RS_LAUNCH_GROUP(8, 0); break;
+    case 101: RS_LAUNCH_GROUP(101, 0); break;
+    case 103: RS_LAUNCH_GROUP(103, 0); break;
+    case 10:
+      if (ept <= 1) RS_LAUNCH_GROUP(10, 1);
+      else if (ept <= 2) RS_LAUNCH_GROUP(10, 2);
+      else if (ept <= 3) RS_LAUNCH_GROUP(10, 3);
+      else if (ept <= 4) RS_LAUNCH_GROUP(10, 4);
+      else return hipErrorInvalidValue;
+      break;
+    case 9:
+      if (ept <= 1) RS_LAUNCH_GROUP(9, 1);
+      else if (ept <= 2) RS_LAUNCH_GROUP(9, 2);
+      else if (ept <= 3) RS_LAUNCH_GROUP(9, 3);
+      else if (ept <= 4) RS_LAUNCH_GROUP(9, 4);
+      else RS_LAUNCH_GROUP(9, 0);
+      break;
+    default: return hipErrorInvalidValue;
+  }
+#undef RS_LAUNCH_GROUP
+  return hipGetLastError();
+}
+
 extern "C" hipError_t rs_prepare_kernels(int max_lds_bytes) {
 #define RS_BOTH(SCHED_, EPT_) (const void*)rs_cell_kernel<SCHED_, EPT_, false>, (const void*)rs_cell_kernel<SCHED_, EPT_, true>
   const void* fns[] = {RS_BOTH(1, 0),  RS_BOTH(7, 0),  RS_BOTH(8, 0),  RS_BOTH(101, 0), RS_BOTH(103, 0), RS_BOTH(11, 0),
@@ -1017,7 +1059,14 @@ extern "C" hipError_t rs_prepare_kernels(int max_lds_bytes) {
                        (const void*)rs_group_kernel<101, 0>, (const void*)rs_group_kernel<103, 0>,
                        (const void*)rs_group_kernel<10, 1>, (const void*)rs_group_kernel<10, 2>, (const void*)rs_group_kernel<10, 3>,
                        (const void*)rs_group_kernel<10, 4>, (const void*)rs_group_kernel<9, 0>,  (const void*)rs_group_kernel<9, 1>,
-                       (const void*)rs_group_kernel<9, 2>,  (const void*)rs_group_kernel<9, 3>,  (const void*)rs_group_kernel<9, 4>};
+                       (const void*)rs_group_kernel<9, 2>,  (const void*)rs_group_kernel<9, 3>,  (const void*)rs_group_kernel<9, 4>,
+                       (const void*)rs_group_resident_kernel<1, 0>,  (const void*)rs_group_resident_kernel<7, 0>,
+                       (const void*)rs_group_resident_kernel<8, 0>,  (const void*)rs_group_resident_kernel<101, 0>,
+                       (const void*)rs_group_resident_kernel<103, 0>, (const void*)rs_group_resident_kernel<10, 1>,
+                       (const void*)rs_group_resident_kernel<10, 2>, (const void*)rs_group_resident_kernel<10, 3>,
+                       (const void*)rs_group_resident_kernel<10, 4>, (const void*)rs_group_resident_kernel<9, 0>,
+                       (const void*)rs_group_resident_kernel<9, 1>,  (const void*)rs_group_resident_kernel<9, 2>,
+                       (const void*)rs_group_resident_kernel<9, 3>,  (const void*)rs_group_resident_kernel<9, 4>};
 #undef RS_BOTH
 
   for (const void* f : fns) {

@@ -11,7 +11,14 @@
  * The includer provides `p` (the launch block), `lds` and four constants: kGrpSched, kGrpEpt, kGrpFixed -- shape, workgroup size and LDS
  * carve are the constants RS_JIT_*, RS_JIT_U being the user CAPACITY while the users of a slot stay the slot header's word -- and
  * kGrpLean -- the plain call's per-launch options are constants too.  (Text, not a function of its own: the built-in instantiations
- * must stay the machine code they were, and a wrapper function around the inlined cell body changed their instruction counts.) */
+ * must stay the machine code they were, and a wrapper function around the inlined cell body changed their instruction counts.)
+ *
+ * A fifth constant, kGrpRes, makes the resident form (rs_group_schedule_tti_at, rs_group_resident_kernel): the cell keeps its users' PF
+ * averages, the bytes granted since their last update and the time of that update in HBM.  Before the body the workgroup applies
+ * RadioBearer::UpdateAverageTransmissionRate to EVERY user of the cell (ref: src/flows/radio-bearer.cpp:139-164, the operations of
+ * rs_phase_p0_p1.inc's batch EWMA in their order), hands the body the averages of the call's users, and behind the body adds each
+ * served user's grant -- which the one-TTI body leaves per call position in LDS (s_tx, rs_phase_p5.inc) -- to the user's pending
+ * bytes.  A compile-time constant for the reason above: with kGrpRes false none of this text reaches the other instantiations. */
   const uint8_t* const in = p.grp_in + (size_t)blockIdx.x * (size_t)p.grp_in_stride;
   uint8_t* const out = p.grp_out + (size_t)blockIdx.x * (size_t)p.grp_out_stride;
   const RsGroupCell* const h = (const RsGroupCell*)in;
@@ -59,11 +66,87 @@
       for (int i = threadIdx.x; i < n16; i += (kGrpFixed ? (unsigned)RS_JIT_NT : blockDim.x)) ((uint4*)store)[i] = src[i];
     }
   }
+#ifdef RS_STAMPS
+  /* diagnostic build: every call slot stamps a row of its own (the body stamps row `cell` of its block, and cell is 0 there) */
+  if (p.stamps) q.stamps = p.stamps + (size_t)blockIdx.x * 20;
+  unsigned long long grp_res_cycles = 0;
+#endif
+  if constexpr (kGrpRes) {
+    /* (the built-in kernels only: run-time builds of the resident form are a follow-up, so shape and carve are the launch block's) */
+#ifdef RS_STAMPS
+    const unsigned long long grp_res_entry = __builtin_readcyclecounter();
+#endif
+    const int nthreads = (int)blockDim.x;
+    const int n_all = p.U; /* the config's users: the stores' stride and the update's range */
+    double* const r_avg = p.grp_avg + (size_t)cell * (size_t)n_all;
+    int32_t* const r_pend = p.grp_pending + (size_t)cell * (size_t)n_all;
+    /* (two words, one address for the workgroup, as the header's other words) */
+    auto dword = [&](const double* d) { return __hiloint2double(word((const int32_t*)d + 1), word((const int32_t*)d)); };
+    const double now = dword(&h->now);
+    const double last = dword(p.grp_last + cell);
+    /* 1. the update, for every user id of the cell whether or not this call names it (the reference updates every bearer, with or
+     *    without data); Now == m_lastUpdate is the reference's early return.  The host has checked now >= last and bounded now - last. */
+    if (!(now == last)) {
+      const double dt = now - last;
+      for (int u = threadIdx.x; u < n_all; u += nthreads) {
+        double a = r_avg[u];
+        const int txb = r_pend[u];
+        /* (the reference's int product m_transmittedData * 8; written so that it wraps, as that one does on its machine, where calls
+         * that repeat one clock value have piled up 2^28 bytes or more) */
+        double rate = (double)(int32_t)((uint32_t)txb * 8u) / dt;
+        const double beta = 0.02;
+        a = ((1 - beta) * a) + (beta * rate);
+        if (a < 1) a = 1;
+        r_avg[u] = a;
+        r_pend[u] = 0;
+      }
+    }
+    /* every thread has read the cell's last-update word and written its share of the averages: the one barrier of this form (part of
+     * the load phase; behind it a thread reads averages that other threads wrote) */
+    __syncthreads();
+    if (threadIdx.x == 0 && !(now == last)) p.grp_last[cell] = now;
+    /* 2. the call's averages: the store itself when the call's users are 0..U-1, else gathered in call order.  Thread i writes row
+     *    entry i and is the thread that reads it in the body's load phase (same stride), whose own first barrier serves the rest. */
+    const int in_uid = word(&h->in_uid);
+    q.avg = r_avg;
+    if (in_uid != 0) {
+      const int32_t* const uid = (const int32_t*)(data + in_uid);
+      double* const row = p.grp_gather + (size_t)cell * (size_t)n_all;
+      int32_t* const ids = p.grp_uid + (size_t)cell * (size_t)n_all; /* (kept for step 3: the slot may lie in host memory) */
+      for (int i = threadIdx.x; i < q.U; i += nthreads) {
+        const int id = uid[i];
+        row[i] = r_avg[id];
+        ids[i] = id;
+      }
+      q.avg = row;
+    }
+#ifdef RS_STAMPS
+    grp_res_cycles = __builtin_readcyclecounter() - grp_res_entry;
+#endif
+  }
   if constexpr (kGrpLean) { /* the plain call (rs_group_kernel_jit): no customised slices -- the slots' HoL delays and priority flags are not read */
     q.hol = nullptr;
     q.prio = nullptr;
   }
   rs_cell_body<kGrpSched, kGrpEpt, kGrpFixed, true, false, true>(q, lds);
+  if constexpr (kGrpRes) {
+    /* 3. the grants (DoStopSchedule: min(tbs_bits / 8, 100000000) bytes, rs_phase_p5.inc) from LDS, where the body's closing barrier
+     *    left them for every thread -- not from the slot's output rows, which lie in host memory in the zero-copy mode.  A user is
+     *    named once per call, a cell once per launch: plain adds. */
+    const int nthreads = (int)blockDim.x;
+    const int n_all = p.U;
+    const int32_t* const granted = (const int32_t*)(lds + p.off_tx);
+    int32_t* const r_pend = p.grp_pending + (size_t)cell * (size_t)n_all;
+    const int in_uid = word(&h->in_uid);
+    const int32_t* const ids = p.grp_uid + (size_t)cell * (size_t)n_all; /* entry i: written by this thread before the body */
+    for (int i = threadIdx.x; i < q.U; i += nthreads) {
+      const int bytes = granted[i];
+      if (bytes != 0) r_pend[in_uid != 0 ? ids[i] : i] += bytes;
+    }
+#ifdef RS_STAMPS
+    if (threadIdx.x == 0 && q.stamps) q.stamps[9] += grp_res_cycles; /* (the update and the gather belong to the load phase; this slot's own row) */
+#endif
+  }
   __threadfence_system();
   __syncthreads();
   if (threadIdx.x == 0) {
