@@ -29,7 +29,8 @@ extern "C" {
                                rs_batch_bearer_log + rs_batch_run_logged_bearers (per-bearer DoStopSchedule rows),
                                rs_group_* (one TTI of several drop-in cells in one launch), rs_group_image_stats (cqi_epoch per cell of a group),
                                rs_group_specialize / rs_group_jit_status / rs_jit_selfcheck_group (a group's own self-checked builds of the one-TTI kernel),
-                               rs_group_set_avg / rs_group_get_avg / rs_group_set_pending / rs_group_schedule_tti_at (a group cell's PF averages resident on the device);
+                               rs_group_set_avg / rs_group_get_avg / rs_group_set_pending / rs_group_schedule_tti_at (a group cell's PF averages resident on the device),
+                               rs_group_specialize_resident / rs_group_resident_jit_status / rs_jit_selfcheck_group_resident (a group's own builds of the resident kernel, self-checked on state);
                                rs_config.link_tables (RS_LINK_*) + rs_link_tables_pinned / rs_link_tables_compare, rs_tti_in.cqi_epoch (the context keeps the
                                CQI image of an unchanged report set on the device), rs_ctx_jit_status (a specialised context checks its run-time build against the
                                built-in kernel during its first calls), rs_batch_config.selfcheck -1 / 0 / 1 with run-time builds verified by default and the
@@ -310,7 +311,8 @@ int64_t rs_group_launch_count(const rs_group* g);
  * block and stored an image (non-zero cqi_epoch, no match), out[2] without a promise (cqi_epoch 0, or RS_GROUP_IMAGE=0) */
 int rs_group_image_stats(const rs_group* g, int64_t out[3]);
 /* "rs_group_kernel_jit" while the group's own builds serve its calls; the built-in instantiation's name before rs_group_specialize and
- * after a build was dropped */
+ * after a build was dropped.  While the last call was a resident one: "rs_group_resident_kernel_jit" if the group's resident builds
+ * served it (rs_group_specialize_resident), else the built-in "rs_group_resident_kernel<sched, ept>". */
 const char* rs_group_kernel_name(rs_group* g);
 /* Optional, at any time between two calls: rs_ctx_specialize for a group -- the one-TTI kernel compiled for the config's slices, RBGs,
  * PRBs per RBG, scheduler, workgroup size and user capacity (hiprtc, ~2 s per build and process, cached on disk apart from the
@@ -351,9 +353,9 @@ int rs_jit_selfcheck_group(int n_slices, int n_users, int n_rbgs, int rbg_size, 
  * (rs_group_set_pending: a synchronising copy, outside the fast path).
  * rs_group_schedule_tti is unchanged: it still needs avg_rate, and on a resident cell it uses the caller's averages and neither reads
  * nor writes the resident state.
- * A specialised group (rs_group_specialize) serves resident calls with the resident kernel built into the library; run-time builds of
- * the resident form, and their self-check, are a follow-up.  rs_group_kernel_name reports that kernel
- * ("rs_group_resident_kernel<sched, ept>") while a resident call is the last one served. */
+ * Resident calls run the resident kernel built into the library ("rs_group_resident_kernel<sched, ept>" in rs_group_kernel_name while
+ * a resident call is the last one served), after rs_group_specialize too: that call specialises the plain call only.  Run-time builds of
+ * the resident form are an option of their own, rs_group_specialize_resident below. */
 /* Makes `cell` resident (again, at any time between two calls): avg[cfg.n_users] by user id, zero pending bytes, last_update =
  * m_lastUpdate.  RS_ERR_INVALID for an average that is not in 1..2^52 (an updated average is never below 1; the upper bound keeps
  * the metric scan's FP32 filter in its range without the host seeing the values -- DESIGN.md 7d) or a last_update that is not finite. */
@@ -375,6 +377,28 @@ int rs_group_set_pending(rs_group* g, int32_t cell, const int32_t* pending_bytes
  * hol_delay outside the FP32 filter's range still switches the call to the exact scan.  A call that fails with RS_ERR_HIP leaves the
  * cells it named not resident. */
 int rs_group_schedule_tti_at(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in /* [n] */, rs_tti_out* out /* [n] */, const double* now /* [n] */);
+/* Optional, at any time between two calls, with or without rs_group_specialize: rs_group_specialize for the RESIDENT call -- the resident
+ * kernel compiled for the group's shape (entry point rs_group_resident_kernel_jit, cache files of its own), a general and a lean build;
+ * rs_group_schedule_tti_at picks the lean one under the plain call's per-launch condition (no per-PRB reports, no customised slices, no
+ * gate, no exact scan, no upper_* lists, no synthetic-experiment blocks; RS_JIT_LEAN=0: the general build only).  rs_group_schedule_tti
+ * is not affected.  Cell state, CQI images and the resident stores are not touched.  RS_OK; a second call is a no-op; RS_ERR_HIP if a
+ * build fails, the group left on the built-in resident kernel; RS_ERR_STATE (with the reason) once the resident builds were dropped.
+ * The check follows rs_group_specialize's policy and switches (RS_DROPIN_SELFCHECK_CALLS, RS_JIT_SELFCHECK, the mark in the cache file)
+ * and compares STATE as well: before a checked call the slice state, the cell scalars and the resident stores are kept; the built-in
+ * resident kernel runs into twin output slots; what it left is kept and the earlier state put back; then the group's build runs, with
+ * completion by the stream.  For every named cell the rs_tti_out fields (upper_* lists if asked), the slice state, the averages of
+ * EVERY user id of the config, the pending bytes and last_update must agree bit for bit.  One difference drops the resident pair and
+ * unlinks its cache files -- the plain pair of rs_group_specialize is independent and stays, and the reverse holds too --; that call
+ * returns the built-in kernel's outputs and leaves its state, resident stores included; later resident calls run the built-in resident
+ * kernel; the message names cell, field and index ("cell 2: pending_bytes[5] = 1391, the built-in kernel's 1390").
+ * rs_group_launch_count counts a checked call once. */
+int rs_group_specialize_resident(rs_group* g);
+/* rs_group_jit_status for the resident pair: 1 = the group's resident builds serve the resident calls, 0 = rs_group_specialize_resident
+ * was not called, -1 = it failed to build, -2 = the builds were dropped by the check.  rs_group_jit_status reports the plain pair only. */
+int rs_group_resident_jit_status(rs_group* g, char* msg, size_t msglen);
+/* build check without a GPU: do the general and the lean resident build of a group of this shape compile?  (the larger code size, or a
+ * negative value with the compiler's log in err; RS_SCHED_NVS_NONGREEDY has no group builds) */
+int rs_jit_selfcheck_group_resident(int n_slices, int n_users, int n_rbgs, int rbg_size, int threads, int sched, char* err, size_t errlen);
 
 /* ------------------------------------------------------------------------------------------
  * Batched mode: many independent cells resident on the device, whole DoSchedule() loops

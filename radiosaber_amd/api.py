@@ -111,6 +111,7 @@ ABI_SYMBOLS = [
     "rs_group_get_slice_offset", "rs_group_set_slice_offset", "rs_group_launch_count", "rs_group_kernel_name",
     "rs_group_image_stats", "rs_group_specialize", "rs_group_jit_status", "rs_jit_selfcheck_group",
     "rs_group_set_avg", "rs_group_get_avg", "rs_group_set_pending", "rs_group_schedule_tti_at",
+    "rs_group_specialize_resident", "rs_group_resident_jit_status", "rs_jit_selfcheck_group_resident",
 ]
 
 _lib = None
@@ -158,6 +159,9 @@ def lib():
     L.rs_group_schedule_tti_at.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_TtiIn), C.POINTER(_TtiOut), C.POINTER(C.c_double)]
     L.rs_group_jit_status.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.rs_jit_selfcheck_group.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
+    L.rs_group_specialize_resident.argtypes = [C.c_void_p]
+    L.rs_group_resident_jit_status.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    L.rs_jit_selfcheck_group_resident.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
     L.rs_batch_create.restype = C.c_void_p
     L.rs_batch_create.argtypes = [C.POINTER(_BatchConfig)]
     L.rs_create_checked.restype = C.c_void_p
@@ -253,16 +257,19 @@ def _p(a, t):
 
 
 def jit_selfcheck(n_slices, n_users, n_rbgs, rbg_size, threads=512, sched=RS_SCHED_MAXCELL, queues=False, untuned=False, dropin=False,
-                  group=False):
+                  group=False, resident=False):
     """Compile the shape-specialised kernel for one shape (hiprtc, no GPU needed); returns the code size.  queues=True: the
     queue-model kernel of the shape.  untuned=True: without the -mllvm tuning options (the library's fallback build).
-    group=True: the general and the lean build of a group of this shape (rs_group_specialize); the larger code size."""
+    group=True: the general and the lean build of a group of this shape (rs_group_specialize); the larger code size.
+    group=True, resident=True: the two builds of the group's resident kernel (rs_group_specialize_resident)."""
+    if resident and not group:
+        raise ValueError("resident=True needs group=True: only a group has a resident kernel")
     buf = C.create_string_buffer(4096)
     fn = lib().rs_jit_selfcheck_queue if queues else (lib().rs_jit_selfcheck_untuned if untuned else lib().rs_jit_selfcheck)
     if dropin:  # the drop-in entry point's one-TTI kernel of a context of this shape (rs_ctx_specialize)
         fn = lib().rs_jit_selfcheck_dropin
     if group:
-        fn = lib().rs_jit_selfcheck_group
+        fn = lib().rs_jit_selfcheck_group_resident if resident else lib().rs_jit_selfcheck_group
     n = fn(n_slices, n_users, n_rbgs, rbg_size, threads, sched, buf, 4096)
     if n < 0:
         raise RadioSaberError(n, buf.value.decode(errors="replace"))
@@ -276,20 +283,28 @@ def jit_cache_stats():
     return dict(zip(("hits", "misses", "stores", "rejected"), (int(x) for x in out)))
 
 
-def jit_cache_file(n_slices, n_users, n_rbgs, rbg_size, threads=512, sched=RS_SCHED_MAXCELL, lean=False, streamed=False, group=False):
+def _jit_flags(lean, streamed, group, resident):
+    if resident and not group:
+        raise ValueError("resident=True needs group=True: only a group has a resident kernel")
+    return (4 if lean else 0) | (2 if streamed else 0) | (8 if group else 0) | (16 if resident else 0)
+
+
+def jit_cache_file(n_slices, n_users, n_rbgs, rbg_size, threads=512, sched=RS_SCHED_MAXCELL, lean=False, streamed=False, group=False,
+                   resident=False):
     """Path of the cache file the batch kernel of this shape lives in ('' when no cache directory can be named).  group=True: a
-    group's build of the one-TTI kernel (flag bit of value 8)."""
+    group's build of the one-TTI kernel (flag bit of value 8); with resident=True its resident form (value 16)."""
     buf = C.create_string_buffer(4096)
-    lib().rs_jit_cache_file(n_slices, n_users, n_rbgs, rbg_size, threads, sched, (4 if lean else 0) | (2 if streamed else 0) | (8 if group else 0),
+    lib().rs_jit_cache_file(n_slices, n_users, n_rbgs, rbg_size, threads, sched, _jit_flags(lean, streamed, group, resident),
                             buf, 4096)
     return buf.value.decode()
 
 
-def jit_cache_warm(n_slices, n_users, n_rbgs, rbg_size, threads=512, sched=RS_SCHED_MAXCELL, lean=False, streamed=False, group=False):
+def jit_cache_warm(n_slices, n_users, n_rbgs, rbg_size, threads=512, sched=RS_SCHED_MAXCELL, lean=False, streamed=False, group=False,
+                   resident=False):
     """Compile (or load) the batch kernel of this shape through the disk cache; no GPU needed.  Returns the code size.
-    group=True: a group's build of the one-TTI kernel."""
+    group=True: a group's build of the one-TTI kernel; with resident=True its resident form."""
     buf = C.create_string_buffer(4096)
-    n = lib().rs_jit_cache_warm(n_slices, n_users, n_rbgs, rbg_size, threads, sched, (4 if lean else 0) | (2 if streamed else 0) | (8 if group else 0),
+    n = lib().rs_jit_cache_warm(n_slices, n_users, n_rbgs, rbg_size, threads, sched, _jit_flags(lean, streamed, group, resident),
                                 buf, 4096)
     if n < 0:
         raise RadioSaberError(n, buf.value.decode(errors="replace"))
@@ -615,8 +630,8 @@ class GroupScheduler:
 
     def __init__(self, slices: SliceConfig, n_rbgs: int, rbg_size: int, n_cells: int, sched: int = RS_SCHED_MAXCELL,
                  device: int = 0, stream: Optional[int] = None, synthetic_exp: bool = False, link_tables: int = RS_LINK_DEFAULT,
-                 jit: bool = False):
-        """jit: specialize() right after the group is created."""
+                 jit: bool = False, jit_resident: bool = False):
+        """jit: specialize() right after the group is created.  jit_resident: specialize_resident() as well (independent of jit)."""
         self.slices, self.R, self.rbg_size, self.sched, self.n_cells = slices, n_rbgs, rbg_size, sched, n_cells
         self._cfg = _CfgHolder(slices, n_rbgs, rbg_size, sched, device, stream, synthetic_exp, link_tables)
         self._h = lib().rs_group_create_checked(C.byref(self._cfg.c), n_cells, RS_ABI_VERSION, C.sizeof(_Config))
@@ -624,6 +639,8 @@ class GroupScheduler:
             raise RadioSaberError(-1, lib().rs_last_error().decode())
         if jit:
             self.specialize()
+        if jit_resident:
+            self.specialize_resident()
 
     def specialize(self):
         """rs_group_specialize: the group's own hiprtc builds of the one-TTI kernel (identical results; their first calls run beside
@@ -634,6 +651,20 @@ class GroupScheduler:
         """(code, message) of rs_group_jit_status: 1 the group's builds serve, 0 not asked for, -1 build failed, -2 dropped by the self-check."""
         buf = C.create_string_buffer(768)
         rc = lib().rs_group_jit_status(self._h, buf, 768)
+        return rc, buf.value.decode(errors="replace")
+
+    def specialize_resident(self):
+        """rs_group_specialize_resident: the group's own hiprtc builds of the RESIDENT kernel, for schedule_tti_at (identical results;
+        their first calls run beside the built-in resident kernel and are compared on outputs and on state -- slice state, averages,
+        pending bytes, last update -- unless the builds carry the self-check mark: resident_jit_status()).  Independent of
+        specialize(); any time between two calls; again: a no-op."""
+        _check(lib().rs_group_specialize_resident(self._h))
+
+    def resident_jit_status(self):
+        """(code, message) of rs_group_resident_jit_status, for the resident builds alone: 1 they serve the resident calls, 0 not asked
+        for, -1 build failed, -2 dropped by the self-check."""
+        buf = C.create_string_buffer(768)
+        rc = lib().rs_group_resident_jit_status(self._h, buf, 768)
         return rc, buf.value.decode(errors="replace")
 
     def close(self):

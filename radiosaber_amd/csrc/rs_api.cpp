@@ -33,7 +33,8 @@ extern "C" hipError_t rs_prepare_kernels(int max_lds_bytes);
 struct RsJitKernel;
 extern "C" RsJitKernel* rs_jit_get(int device, int S, int U, int R, int G, int NT, int sched, int qmode, int win, char* err, size_t errlen,
                                    int flags, /* bit 0: drop-in (one-TTI) kernel, bit 1: streamed batch (cqi_refresh <= 4), bit 2: lean build,
-                                                * bit 3: a group's build of the one-TTI kernel (rs_group_kernel_jit) */
+                                                * bit 3: a group's build of the one-TTI kernel (rs_group_kernel_jit), bit 4 (with bit 3): its
+                                                * resident form (rs_group_resident_kernel_jit) */
                                    const char* variant = nullptr); /* an autotune candidate: extra -D options and / or "ss=<LLVM scheduler strategy>" */
 extern "C" int rs_jit_is_untuned(const RsJitKernel* k);
 extern "C" int rs_jit_is_verified(const RsJitKernel* k);  /* carries the self-check mark (this process, or its cache file) */
@@ -2444,12 +2445,24 @@ struct rs_group {
   std::vector<double> last_update;
   bool last_call_resident = false;
   char kname_res[56] = "";
+  /* rs_group_specialize_resident: the group's own builds of the RESIDENT form, a pair of its own beside jit[] with the same scheme (index
+   * 0 general, 1 lean; calls still to be checked, calls that agreed).  Its check also compares the resident stores: d_rchk holds them
+   * before the built-in resident kernel ran and as that kernel left them (two halves, group_rchk_half). */
+  RsJitKernel* rjit[2] = {nullptr, nullptr};
+  bool rjit_wanted = false, rjit_dropped = false, last_call_rjit = false;
+  int rchk_left[2] = {0, 0}, rchk_agreed[2] = {0, 0};
+  uint8_t* d_rchk = nullptr;
+  char rjit_msg[512] = "";
 };
 
 namespace {
 /* bytes of one half of rs_group::d_chk: [n_cells][S] slice state, then [n_cells] RsCellScalars */
 size_t group_chk_sstate(const rs_group* g) { return round_up((int)(8 * (size_t)g->b->S * g->n_cells), 256); }
 size_t group_chk_half(const rs_group* g) { return group_chk_sstate(g) + round_up((int)(sizeof(RsCellScalars) * (size_t)g->n_cells), 256); }
+/* bytes of one half of rs_group::d_rchk: [n_cells][U] averages, then [n_cells] last-update times, then [n_cells][U] pending bytes */
+size_t group_rchk_avg(const rs_group* g) { return round_up((int)(8 * (size_t)g->b->U * g->n_cells), 256); }
+size_t group_rchk_last(const rs_group* g) { return round_up((int)(8 * (size_t)g->n_cells), 256); }
+size_t group_rchk_half(const rs_group* g) { return group_rchk_avg(g) + group_rchk_last(g) + round_up((int)(4 * (size_t)g->b->U * g->n_cells), 256); }
 }  // namespace
 
 extern "C" hipError_t rs_launch_group(const RsLaunch* p, int threads, hipStream_t stream);
@@ -2545,6 +2558,7 @@ void rs_group_destroy(rs_group* g) {
   if (g->d_prb) (void)hipFree(g->d_prb);
   if (g->d_out2) (void)hipFree(g->d_out2);
   if (g->d_chk) (void)hipFree(g->d_chk);
+  if (g->d_rchk) (void)hipFree(g->d_rchk);
   if (g->d_ravg) (void)hipFree(g->d_ravg);
   if (g->d_rpend) (void)hipFree(g->d_rpend);
   if (g->d_rlast) (void)hipFree(g->d_rlast);
@@ -2759,28 +2773,52 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
   }
   /* rs_group_specialize: the group's own build -- its lean form when the call is plain for every cell (the uniform-presence rules above
    * make that a fact of the launch), the general one otherwise */
-  RsJitKernel* kd = res ? nullptr : g->jit[0]; /* (a resident call: the built-in resident kernel, whatever serves the plain calls) */
+  /* (the plain pair, rs_group_specialize, and the resident pair, rs_group_specialize_resident, are independent: each serves its own
+   * kind of call, is checked against its own built-in kernel and is dropped alone) */
+  RsJitKernel** const pair = res ? g->rjit : g->jit;
+  int* const chk_left = res ? g->rchk_left : g->chk_left;
+  int* const chk_agreed = res ? g->rchk_agreed : g->chk_agreed;
+  RsJitKernel* kd = pair[0];
   int which = 0;
-  if (!res && g->jit[1] && !has_prb && !L.queue_mode && !has_gate && !L.exact_scan && !L.gen_exp && !want_upper && !L.synthetic) { kd = g->jit[1]; which = 1; }
-  /* A build without the self-check mark serves its first calls beside the built-in group kernel (rs_group_jit_status): same slots,
-   * same slice state; every named cell's output fields and the slice state left behind must agree. */
-  const bool checked_call = kd != nullptr && g->chk_left[which] > 0;
+  if (pair[1] && !has_prb && !L.queue_mode && !has_gate && !L.exact_scan && !L.gen_exp && !want_upper && !L.synthetic) { kd = pair[1]; which = 1; }
+  /* A build without the self-check mark serves its first calls beside the built-in kernel of its kind (rs_group_jit_status,
+   * rs_group_resident_jit_status): same slots, same state; every named cell's output fields and the state left behind must agree --
+   * the slice state, and for a resident call the averages of every user id, the pending bytes and the last-update time. */
+  const bool checked_call = kd != nullptr && chk_left[which] > 0;
   const size_t ss_all = 8 * (size_t)b->S * g->n_cells, sc_all = sizeof(RsCellScalars) * (size_t)g->n_cells;
+  const size_t ra_all = 8 * (size_t)b->U * g->n_cells, rl_all = 8 * (size_t)g->n_cells, rp_all = 4 * (size_t)b->U * g->n_cells;
+  /* the three resident stores to / from one half of d_rchk */
+  auto resident_stores = [&](uint8_t* half, bool save) -> hipError_t {
+    struct { void* store; uint8_t* kept; size_t bytes; } const part[3] = {{g->d_ravg, half, ra_all},
+                                                                        {g->d_rlast, half + group_rchk_avg(g), rl_all},
+                                                                        {g->d_rpend, half + group_rchk_avg(g) + group_rchk_last(g), rp_all}};
+    for (const auto& x : part) {
+      const hipError_t e = hipMemcpyAsync(save ? (void*)x.kept : x.store, save ? x.store : (void*)x.kept, x.bytes, hipMemcpyDeviceToDevice, st);
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  };
   if (checked_call) {
     uint8_t* const before = g->d_chk;
     uint8_t* const after = g->d_chk + group_chk_half(g);
     HIP_TRY(hipMemcpyAsync(before, b->d_sstate, ss_all, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(before + group_chk_sstate(g), b->d_scal, sc_all, hipMemcpyDeviceToDevice, st));
+    if (res) HIP_TRY(resident_stores(g->d_rchk, true));
     RsLaunch Lb = L; /* the built-in kernel, its outputs into slots of its own */
     Lb.grp_out = g->d_out2;
     Lb.log_upper = want_upper ? (int32_t*)g->d_out2 : nullptr;
     Lb.done_flag = nullptr;
-    HIP_TRY(rs_launch_group(&Lb, b->threads, st));
+    if (res) HIP_TRY(rs_launch_group_resident(&Lb, b->threads, st));
+    else HIP_TRY(rs_launch_group(&Lb, b->threads, st));
     HIP_TRY(hipMemcpyAsync(g->h_out2.data(), g->d_out2, (size_t)n * g->out_stride, hipMemcpyDeviceToHost, st));
     /* keep what it left, put back what it found: the run-time build starts from the same state */
     HIP_TRY(hipMemcpyAsync(after, b->d_sstate, ss_all, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(b->d_sstate, before, ss_all, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(b->d_scal, before + group_chk_sstate(g), sc_all, hipMemcpyDeviceToDevice, st));
+    if (res) {
+      HIP_TRY(resident_stores(g->d_rchk + group_rchk_half(g), true));
+      HIP_TRY(resident_stores(g->d_rchk, false));
+    }
     /* (a mode-1 slot: BOTH kernels transpose the slot's block and store the cell's image and per-PRB copy -- the same bytes when the
      * build is right; a wrong image shows in the checked calls that read it) */
     L.done_flag = nullptr; /* completion by the stream */
@@ -2790,6 +2828,7 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
   else HIP_TRY(rs_launch_group(&L, b->threads, st));
   g->launches++;
   g->last_call_resident = res;
+  g->last_call_rjit = res && kd != nullptr;
   if (!zc) HIP_TRY(hipMemcpyAsync(g->h_out, g->d_out, (size_t)n * g->out_stride, hipMemcpyDeviceToHost, st));
   const clk::time_point t2 = g->timing ? clk::now() : clk::time_point();
   bool seen = false;
@@ -2843,7 +2882,51 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
         if (to_bits(a) != to_bits(r)) snprintf(what, sizeof what, "cell %d: slice state[%d] = %a, the built-in kernel's %a", cell, i, a, r);
       }
     }
-    if (what[0]) {
+    if (res && !what[0]) {
+      /* the resident stores of the named cells: the averages of EVERY user id of the config (the update touches them all), the pending
+       * bytes, the last-update time */
+      const uint8_t* const ref = g->d_rchk + group_rchk_half(g);
+      const size_t U = (size_t)b->U;
+      std::vector<double> a_jit(U * g->n_cells), a_ref(a_jit.size()), l_jit(g->n_cells), l_ref(g->n_cells);
+      std::vector<int32_t> p_jit(U * g->n_cells), p_ref(p_jit.size());
+      HIP_TRY(hipMemcpy(a_jit.data(), g->d_ravg, ra_all, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(a_ref.data(), ref, ra_all, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(l_jit.data(), g->d_rlast, rl_all, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(l_ref.data(), ref + group_rchk_avg(g), rl_all, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(p_jit.data(), g->d_rpend, rp_all, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(p_ref.data(), ref + group_rchk_avg(g) + group_rchk_last(g), rp_all, hipMemcpyDeviceToHost));
+      for (int k = 0; k < n && !what[0]; k++) {
+        const int cell = cell_ids ? cell_ids[k] : k;
+        for (size_t u = 0; u < U && !what[0]; u++) {
+          const double a = a_jit[cell * U + u], r = a_ref[cell * U + u];
+          if (to_bits(a) != to_bits(r)) snprintf(what, sizeof what, "cell %d: avg[%zu] = %a, the built-in kernel's %a", cell, u, a, r);
+        }
+        for (size_t u = 0; u < U && !what[0]; u++)
+          if (p_jit[cell * U + u] != p_ref[cell * U + u])
+            snprintf(what, sizeof what, "cell %d: pending_bytes[%zu] = %d, the built-in kernel's %d", cell, u, p_jit[cell * U + u], p_ref[cell * U + u]);
+        if (!what[0] && to_bits(l_jit[cell]) != to_bits(l_ref[cell]))
+          snprintf(what, sizeof what, "cell %d: last_update = %a, the built-in kernel's %a", cell, l_jit[cell], l_ref[cell]);
+      }
+    }
+    if (what[0] && res) {
+      /* the resident pair is wrong: both of its builds are dropped (and their cache files), the plain pair stays.  This call returns
+       * the built-in resident kernel's outputs and leaves its state, resident stores included; later resident calls run that kernel */
+      for (int w = 0; w < 2; w++) {
+        if (g->rjit[w]) rs_jit_reject(g->rjit[w]);
+        g->rjit[w] = nullptr;
+        g->rchk_left[w] = 0;
+      }
+      g->rjit_dropped = true;
+      g->last_call_rjit = false;
+      memcpy(g->h_out, g->h_out2.data(), (size_t)n * g->out_stride);
+      HIP_TRY(hipMemcpy(b->d_sstate, g->d_chk + group_chk_half(g), ss_all, hipMemcpyDeviceToDevice));
+      HIP_TRY(resident_stores(g->d_rchk + group_rchk_half(g), false));
+      HIP_TRY(hipStreamSynchronize(st));
+      snprintf(g->rjit_msg, sizeof g->rjit_msg, "self-check of the group's specialised resident %s build, checked call %d: %s; both resident builds are dropped, "
+               "the built-in resident kernel serves this group's resident calls (lint the code object: tools/lint_exec_restore.py)",
+               which ? "lean" : "general", g->rchk_agreed[which] + 1, what);
+      snprintf(g_err, sizeof g_err, "%s", g->rjit_msg);
+    } else if (what[0]) {
       /* the build is wrong: neither build of the shape is trusted.  Both are dropped (and their cache files); this call returns the
        * built-in kernel's outputs and state, later calls run the built-in kernels */
       for (int w = 0; w < 2; w++) {
@@ -2858,8 +2941,8 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
                "serve this group (lint the code object: tools/lint_exec_restore.py)", which ? "lean" : "general", g->chk_agreed[which] + 1, what);
       snprintf(g_err, sizeof g_err, "%s", g->jit_msg);
     } else {
-      g->chk_agreed[which]++;
-      if (--g->chk_left[which] == 0) rs_jit_mark_verified(kd);
+      chk_agreed[which]++;
+      if (--chk_left[which] == 0) rs_jit_mark_verified(kd);
     }
   }
   guard.ok = true;
@@ -3000,76 +3083,123 @@ int rs_group_image_stats(const rs_group* g, int64_t out[3]) {
 
 const char* rs_group_kernel_name(rs_group* g) {
   if (!g) return "";
-  if (g->last_call_resident) return g->kname_res; /* (resident calls run the built-in resident kernel, specialised group or not) */
+  /* (a resident call: the group's resident builds if rs_group_specialize_resident gave it some, else the built-in resident kernel --
+   * whatever serves the plain calls) */
+  if (g->last_call_resident) return g->last_call_rjit ? "rs_group_resident_kernel_jit" : g->kname_res;
   return g->jit[0] ? "rs_group_kernel_jit" : g->kname;
 }
 
 /* Shape specialisation of a group: rs_ctx_specialize for the group surface -- the one-TTI form compiled for the config's slices, RBGs,
- * PRBs per RBG, scheduler, workgroup size and user CAPACITY, entry point rs_group_kernel_jit (one workgroup per call slot), in a
- * general and a lean build.  Between calls at any time: slice state, CQI images and per-PRB stores are not touched. */
-int rs_group_specialize(rs_group* g) {
-  if (!g) return fail(RS_ERR_INVALID, "null group");
+ * PRBs per RBG, scheduler, workgroup size and user CAPACITY, one workgroup per call slot, in a general and a lean build.  Two pairs,
+ * each an option of its own: rs_group_specialize (entry point rs_group_kernel_jit, serves rs_group_schedule_tti) and
+ * rs_group_specialize_resident (rs_group_resident_kernel_jit, serves rs_group_schedule_tti_at).  Between calls at any time: slice
+ * state, CQI images, per-PRB stores and resident stores are not touched. */
+namespace {
+/* one pair's fields of rs_group */
+struct GroupJitPair {
+  RsJitKernel** jit;
+  bool *wanted, *dropped;
+  int *chk_left, *chk_agreed;
+  char* msg; /* [512] */
+  bool resident;
+};
+GroupJitPair group_jit_pair(rs_group* g, bool resident) {
+  if (resident) return {g->rjit, &g->rjit_wanted, &g->rjit_dropped, g->rchk_left, g->rchk_agreed, g->rjit_msg, true};
+  return {g->jit, &g->jit_wanted, &g->jit_dropped, g->chk_left, g->chk_agreed, g->jit_msg, false};
+}
+
+int group_specialize_pair(rs_group* g, bool resident) {
   rs_batch* b = g->b;
-  if (g->jit[0]) return RS_OK;
-  if (g->jit_dropped) return fail(RS_ERR_STATE, "%s", g->jit_msg);
+  const GroupJitPair jp = group_jit_pair(g, resident);
+  if (jp.jit[0]) return RS_OK;
+  if (*jp.dropped) return fail(RS_ERR_STATE, "%s", jp.msg);
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  g->jit_wanted = true;
+  *jp.wanted = true;
   if (!g->d_out2) {
     const size_t out_bytes = g->out_stride * (size_t)g->n_cells;
     if (hipMalloc(&g->d_out2, out_bytes) != hipSuccess || hipMalloc(&g->d_chk, 2 * group_chk_half(g)) != hipSuccess) {
       (void)hipGetLastError();
       if (g->d_out2) (void)hipFree(g->d_out2);
       g->d_out2 = g->d_chk = nullptr;
-      snprintf(g->jit_msg, sizeof g->jit_msg, "allocation of the self-check's twin blocks failed (%zu + %zu bytes)", out_bytes, 2 * group_chk_half(g));
-      return fail(RS_ERR_HIP, "%s", g->jit_msg);
+      snprintf(jp.msg, 512, "allocation of the self-check's twin blocks failed (%zu + %zu bytes)", out_bytes, 2 * group_chk_half(g));
+      return fail(RS_ERR_HIP, "%s", jp.msg);
     }
     g->h_out2.assign(out_bytes, 0);
   }
-  const int qmode = (b->sched == RS_SCHED_PF || b->sched == RS_SCHED_NVS) ? 1 : 0; /* (the gate scratch of the group's carve: carve_lds) */
-  char msg[512] = "";
-  g->jit[0] = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, qmode, 0, msg, sizeof msg, 1 | 8);
-  if (!g->jit[0]) {
-    snprintf(g->jit_msg, sizeof g->jit_msg, "%s", msg[0] ? msg : "hiprtc build failed");
-    return fail(RS_ERR_HIP, "%s", g->jit_msg);
+  if (resident && !g->d_rchk && hipMalloc(&g->d_rchk, 2 * group_rchk_half(g)) != hipSuccess) {
+    (void)hipGetLastError();
+    g->d_rchk = nullptr;
+    snprintf(jp.msg, 512, "allocation of the self-check's copies of the resident stores failed (%zu bytes)", 2 * group_rchk_half(g));
+    return fail(RS_ERR_HIP, "%s", jp.msg);
   }
-  g->jit_msg[0] = 0;
+  const int qmode = (b->sched == RS_SCHED_PF || b->sched == RS_SCHED_NVS) ? 1 : 0; /* (the gate scratch of the group's carve: carve_lds) */
+  const int flags = 1 | 8 | (resident ? 16 : 0);
+  char msg[512] = "";
+  jp.jit[0] = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, qmode, 0, msg, sizeof msg, flags);
+  if (!jp.jit[0]) {
+    snprintf(jp.msg, 512, "%s", msg[0] ? msg : "hiprtc build failed");
+    return fail(RS_ERR_HIP, "%s", jp.msg);
+  }
+  jp.msg[0] = 0;
   /* ... and its lean form (the plain call); without it the general build serves every call */
   const char* const e_on = getenv("RS_JIT_LEAN");
-  if (!e_on || atoi(e_on) != 0) g->jit[1] = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, qmode, 0, msg, sizeof msg, 1 | 4 | 8);
+  if (!e_on || atoi(e_on) != 0) jp.jit[1] = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, qmode, 0, msg, sizeof msg, flags | 4);
   /* the policy and the switches of rs_ctx_specialize: no checked calls for a build that came with the mark of an earlier check */
   int calls = 8;
   if (const char* e = getenv("RS_DROPIN_SELFCHECK_CALLS")) calls = atoi(e) > 0 ? atoi(e) : 0;
   const char* pol = getenv("RS_JIT_SELFCHECK");
   const bool never = pol && pol[0] == '0', always = pol && pol[0] == '2';
   for (int w = 0; w < 2; w++) {
-    g->chk_agreed[w] = 0;
-    g->chk_left[w] = (g->jit[w] && !never && (always || !rs_jit_is_verified(g->jit[w]))) ? calls : 0;
+    jp.chk_agreed[w] = 0;
+    jp.chk_left[w] = (jp.jit[w] && !never && (always || !rs_jit_is_verified(jp.jit[w]))) ? calls : 0;
   }
   return RS_OK;
 }
 
-int rs_group_jit_status(rs_group* g, char* msg, size_t msglen) {
-  if (!g) return fail(RS_ERR_INVALID, "null group");
+int group_jit_pair_status(rs_group* g, bool resident, char* msg, size_t msglen) {
+  const GroupJitPair jp = group_jit_pair(g, resident);
+  const char* const ref = resident ? "the built-in resident kernel field by field, resident stores included" : "the built-in kernel field by field";
   if (msg && msglen) {
-    if (g->jit_dropped || !g->jit[0]) {
-      snprintf(msg, msglen, "%s", g->jit_msg);
+    if (*jp.dropped || !jp.jit[0]) {
+      snprintf(msg, msglen, "%s", jp.msg);
     } else {
       auto state = [&](int which, char* out, size_t n) {
-        RsJitKernel* const k = g->jit[which];
+        RsJitKernel* const k = jp.jit[which];
         if (!k) snprintf(out, n, "not built");
-        else if (g->chk_left[which] > 0) snprintf(out, n, "%d checked call(s) agreed with the built-in kernel field by field, %d to go", g->chk_agreed[which], g->chk_left[which]);
-        else if (g->chk_agreed[which] > 0) snprintf(out, n, "verified (%d checked calls agreed with the built-in kernel field by field)", g->chk_agreed[which]);
+        else if (jp.chk_left[which] > 0) snprintf(out, n, "%d checked call(s) agreed with %s, %d to go", jp.chk_agreed[which], ref, jp.chk_left[which]);
+        else if (jp.chk_agreed[which] > 0) snprintf(out, n, "verified (%d checked calls agreed with %s)", jp.chk_agreed[which], ref);
         else if (rs_jit_is_verified(k)) snprintf(out, n, "carries the self-check mark of an earlier check (cache file)");
         else snprintf(out, n, "unchecked (RS_JIT_SELFCHECK=0)");
       };
-      char ge[160], le[160];
+      char ge[200], le[200];
       state(0, ge, sizeof ge);
       state(1, le, sizeof le);
       snprintf(msg, msglen, "general build: %s; lean build: %s", ge, le);
     }
   }
-  if (g->jit_dropped) return -2;
-  return g->jit[0] ? 1 : (g->jit_wanted ? -1 : 0);
+  if (*jp.dropped) return -2;
+  return jp.jit[0] ? 1 : (*jp.wanted ? -1 : 0);
+}
+}  // namespace
+
+int rs_group_specialize(rs_group* g) {
+  if (!g) return fail(RS_ERR_INVALID, "null group");
+  return group_specialize_pair(g, false);
+}
+
+int rs_group_specialize_resident(rs_group* g) {
+  if (!g) return fail(RS_ERR_INVALID, "null group");
+  return group_specialize_pair(g, true);
+}
+
+int rs_group_jit_status(rs_group* g, char* msg, size_t msglen) {
+  if (!g) return fail(RS_ERR_INVALID, "null group");
+  return group_jit_pair_status(g, false, msg, msglen);
+}
+
+int rs_group_resident_jit_status(rs_group* g, char* msg, size_t msglen) {
+  if (!g) return fail(RS_ERR_INVALID, "null group");
+  return group_jit_pair_status(g, true, msg, msglen);
 }
 
 /* ---- the reference's CQI trace files (include/radiosaber_hip.h) ---- */

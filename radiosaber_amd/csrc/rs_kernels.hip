@@ -783,7 +783,8 @@ __global__ void __launch_bounds__(512, 4) rs_group_kernel(RsLaunch p) {
 }
 
 /* ... and its resident form (rs_group_schedule_tti_at): the cells' PF averages, pending bytes and last-update times stay on the device.
- * Kernels of their own, the same 14 shapes (rs_launch_group_resident): the plain group kernels above carry none of it. */
+ * Kernels of their own, the same 14 shapes (rs_launch_group_resident): the plain group kernels above carry none of it.  A group's
+ * run-time builds of this form are rs_group_resident_kernel_jit below. */
 template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_resident_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
@@ -804,12 +805,22 @@ __global__ void __launch_bounds__(512, 4) rs_group_resident_kernel(RsLaunch p) {
 #ifndef RS_JIT_GROUP
 #define RS_JIT_GROUP 0 /* 1: a group's build of the one-TTI form (rs_group_specialize): one workgroup per call slot */
 #endif
+#ifndef RS_JIT_GROUP_RESIDENT
+#define RS_JIT_GROUP_RESIDENT 0 /* 1, with RS_JIT_GROUP: the group's build of the resident form (rs_group_specialize_resident) */
+#endif
 #if RS_JIT_GROUP
-extern "C" __global__ void __launch_bounds__(RS_JIT_NT, RS_JIT_WPE) rs_group_kernel_jit(RsLaunch p) {
+/* two entry points, one per option list: rs_group_kernel_jit, and rs_group_resident_kernel_jit for the calls that keep the cells' PF
+ * averages on the device (rs_group_schedule_tti_at).  Same text but for the name and kGrpRes; each has a general and a lean form. */
+#if RS_JIT_GROUP_RESIDENT
+#define RS_GROUP_JIT_ENTRY rs_group_resident_kernel_jit
+#else
+#define RS_GROUP_JIT_ENTRY rs_group_kernel_jit
+#endif
+extern "C" __global__ void __launch_bounds__(RS_JIT_NT, RS_JIT_WPE) RS_GROUP_JIT_ENTRY(RsLaunch p) {
 #if defined(RS_JIT_LEAN) && RS_JIT_LEAN
   /* The lean build of a group's kernel: the plain call, exactly as in the one-TTI lean kernel below -- per-RBG reports, no customised
    * slices, no gates, exponents in {0, 1}, every input an ordinary FP32 number, no UpperBound lists, no synthetic-experiment blocks
-   * (the call's uniform-presence rules make that a per-launch fact; rs_group_schedule_tti picks the build per call).  image_mode stays
+   * (the call's uniform-presence rules make that a per-launch fact; rs_group_schedule_tti and rs_group_schedule_tti_at pick the build per call).  image_mode stays
    * the slot header's word: the cells of one launch mix modes 0 / 1 / 2. */
   p.cqi_mode = RS_CQI_EPOCHS;
   p.prb_cqi = nullptr; p.queue_mode = 0; p.alpha = nullptr; p.beta = nullptr; p.hol = nullptr; p.prio = nullptr;
@@ -822,9 +833,10 @@ extern "C" __global__ void __launch_bounds__(RS_JIT_NT, RS_JIT_WPE) rs_group_ker
   constexpr RsCarve kCv = rs_carve(RS_JIT_S, RS_JIT_U, RS_JIT_R, RS_JIT_SCHED, RS_JIT_NT, RS_JIT_CARVEQ, RS_JIT_WIN);
   __shared__ __align__(16) unsigned char lds[kCv.lds_bytes];
   constexpr int kGrpSched = RS_JIT_SCHED, kGrpEpt = (RS_JIT_SCHED != 9 && RS_JIT_SCHED != 10) ? 0 : (kCv.ept <= 4 ? kCv.ept : 0);
-  constexpr bool kGrpFixed = true, kGrpRes = false; /* (resident calls of a specialised group run the built-in resident kernel) */
+  constexpr bool kGrpFixed = true, kGrpRes = RS_JIT_GROUP_RESIDENT != 0;
 #include "rs_phase_group.inc"
 }
+#undef RS_GROUP_JIT_ENTRY
 #else
 extern "C" __global__ void __launch_bounds__(RS_JIT_NT, RS_JIT_WPE) rs_cell_kernel_jit(RsLaunch p) {
 #if defined(RS_JIT_LEAN) && RS_JIT_LEAN && !RS_JIT_DIRECT

@@ -6,8 +6,9 @@
  * here assumes that the workgroups are resident together -- puts the word back to 0 for the next launch and publishes the call's
  * sequence number to the host.  Its acquire of the counter orders it behind every other workgroup's fence and release.
  *
- * Two entry points of rs_kernels.hip include this text as their body, as rs_cell_body includes its phases: the kernels built into the
- * library (rs_group_kernel: shape in the launch block) and a group's own run-time build (rs_group_kernel_jit, rs_group_specialize).
+ * The entry points of rs_kernels.hip include this text as their body, as rs_cell_body includes its phases: the kernels built into the
+ * library (rs_group_kernel, rs_group_resident_kernel: shape in the launch block) and a group's own run-time builds (rs_group_kernel_jit,
+ * rs_group_specialize; rs_group_resident_kernel_jit, rs_group_specialize_resident).
  * The includer provides `p` (the launch block), `lds` and four constants: kGrpSched, kGrpEpt, kGrpFixed -- shape, workgroup size and LDS
  * carve are the constants RS_JIT_*, RS_JIT_U being the user CAPACITY while the users of a slot stay the slot header's word -- and
  * kGrpLean -- the plain call's per-launch options are constants too.  (Text, not a function of its own: the built-in instantiations
@@ -18,7 +19,9 @@
  * RadioBearer::UpdateAverageTransmissionRate to EVERY user of the cell (ref: src/flows/radio-bearer.cpp:139-164, the operations of
  * rs_phase_p0_p1.inc's batch EWMA in their order), hands the body the averages of the call's users, and behind the body adds each
  * served user's grant -- which the one-TTI body leaves per call position in LDS (s_tx, rs_phase_p5.inc) -- to the user's pending
- * bytes.  A compile-time constant for the reason above: with kGrpRes false none of this text reaches the other instantiations. */
+ * bytes.  A compile-time constant for the reason above: with kGrpRes false none of this text reaches the other instantiations.  Under
+ * kGrpFixed the resident text's shape is constant as well: the update's range and the stores' stride are RS_JIT_U, the loop strides
+ * RS_JIT_NT, the grants' LDS offset the constexpr carve's off_tx.  Order of operations and arithmetic are the same in both forms. */
   const uint8_t* const in = p.grp_in + (size_t)blockIdx.x * (size_t)p.grp_in_stride;
   uint8_t* const out = p.grp_out + (size_t)blockIdx.x * (size_t)p.grp_out_stride;
   const RsGroupCell* const h = (const RsGroupCell*)in;
@@ -72,12 +75,12 @@
   unsigned long long grp_res_cycles = 0;
 #endif
   if constexpr (kGrpRes) {
-    /* (the built-in kernels only: run-time builds of the resident form are a follow-up, so shape and carve are the launch block's) */
+    /* (shape and carve: the launch block's in the built-in kernels, the constants RS_JIT_* in a group's run-time build) */
 #ifdef RS_STAMPS
     const unsigned long long grp_res_entry = __builtin_readcyclecounter();
 #endif
-    const int nthreads = (int)blockDim.x;
-    const int n_all = p.U; /* the config's users: the stores' stride and the update's range */
+    const int nthreads = kGrpFixed ? RS_JIT_NT : (int)blockDim.x;
+    const int n_all = kGrpFixed ? RS_JIT_U : p.U; /* the config's users: the stores' stride and the update's range */
     double* const r_avg = p.grp_avg + (size_t)cell * (size_t)n_all;
     int32_t* const r_pend = p.grp_pending + (size_t)cell * (size_t)n_all;
     /* (two words, one address for the workgroup, as the header's other words) */
@@ -133,15 +136,23 @@
     /* 3. the grants (DoStopSchedule: min(tbs_bits / 8, 100000000) bytes, rs_phase_p5.inc) from LDS, where the body's closing barrier
      *    left them for every thread -- not from the slot's output rows, which lie in host memory in the zero-copy mode.  A user is
      *    named once per call, a cell once per launch: plain adds. */
-    const int nthreads = (int)blockDim.x;
-    const int n_all = p.U;
-    const int32_t* const granted = (const int32_t*)(lds + p.off_tx);
+    const int nthreads = kGrpFixed ? RS_JIT_NT : (int)blockDim.x;
+    const int n_all = kGrpFixed ? RS_JIT_U : p.U;
+    constexpr RsCarve kGrpCv = rs_carve(RS_JIT_S, RS_JIT_U, RS_JIT_R, RS_JIT_SCHED, RS_JIT_NT, RS_JIT_CARVEQ, RS_JIT_WIN); /* (the body's own carve) */
+    const int32_t* const granted = (const int32_t*)(lds + (kGrpFixed ? kGrpCv.off_tx : p.off_tx));
     int32_t* const r_pend = p.grp_pending + (size_t)cell * (size_t)n_all;
     const int in_uid = word(&h->in_uid);
     const int32_t* const ids = p.grp_uid + (size_t)cell * (size_t)n_all; /* entry i: written by this thread before the body */
     for (int i = threadIdx.x; i < q.U; i += nthreads) {
       const int bytes = granted[i];
+#if defined(RS_FAULT_INJECT_RESIDENT)
+      /* tests only (tests/test_gpu_group_resident_specialize.py): a deliberately wrong run-time build of the RESIDENT form -- every served
+       * user is credited a byte more; the outputs stay right, so only the self-check's comparison of the resident stores can catch it.
+       * A value, no address or index; the twin of RS_FAULT_INJECT_DIRECT. */
+      if (bytes != 0) r_pend[in_uid != 0 ? ids[i] : i] += bytes + (kGrpFixed ? 1 : 0);
+#else
       if (bytes != 0) r_pend[in_uid != 0 ? ids[i] : i] += bytes;
+#endif
     }
 #ifdef RS_STAMPS
     if (threadIdx.x == 0 && q.stamps) q.stamps[9] += grp_res_cycles; /* (the update and the gather belong to the load phase; this slot's own row) */

@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
-"""us per group call with the caller's averages (rs_group_schedule_tti) and with resident averages (rs_group_schedule_tti_at), and --
-with the -DRS_STAMPS build -- the kernel's load-phase cycles (profiles/group_resident_avg.md).
+"""us per group call with the caller's averages (rs_group_schedule_tti), with resident averages (rs_group_schedule_tti_at) and with
+resident averages on the group's own run-time builds (rs_group_specialize_resident), and -- with the -DRS_STAMPS build -- the kernel's
+load-phase cycles (profiles/group_resident_avg.md, profiles/group_resident_specialize.md).
 
-    RS_DROPIN_TIMING=1 python tools/group_resident_latency.py [--variant plain|resident|both] [--calls 400]
+    RS_DROPIN_TIMING=1 python tools/group_resident_latency.py [--variant plain|resident|resident-spec|both] [--calls 400]
     RS_HIP_LIB=radiosaber_amd/libradiosaber_hip_stamps.so python tools/group_resident_latency.py     # adds the stamped load phase
 
 Workloads: 8 and 64 cells; 500 users x 25 RBGs and 100 users x 64 RBGs; scheduler 9; cqi_epoch on (new reports every 40 calls).
 RS_TREE=<another checkout> measures that tree's package (the plain variant only, for a tree without resident averages).
+resident-spec: specialize_resident() before the warm-up, whose first rounds are the builds' checked calls (80 rounds cover the 8); the
+line ends with the kernel's name and the status of the builds.
 RS_DROPIN_TIMING=1 makes the library print its own prepare / enqueue / wait / unpack split per group on stderr."""
 import argparse
 import ctypes as C
@@ -22,7 +25,7 @@ import radiosaber_amd as rs  # noqa: E402
 from radiosaber_amd.api import lib  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--variant", default="both", choices=("plain", "resident", "both"))
+ap.add_argument("--variant", default="both", choices=("plain", "resident", "resident-spec", "both"))
 ap.add_argument("--calls", type=int, default=400)
 ap.add_argument("--warmup", type=int, default=80)
 args = ap.parse_args()
@@ -46,9 +49,11 @@ for ues, R, G in ((25, 25, 4), (5, 64, 8)):
             rng = np.random.default_rng(1)
             cqi = [rng.integers(1, 16, (U, R)).astype(np.uint8) for _ in range(K)]
             avg = [rng.uniform(1e4, 1e6, U) for _ in range(K)]
-            if variant == "resident":
+            if variant != "plain":
                 for k in range(K):
                     g.set_avg(k, avg[k], 0.1)
+            if variant == "resident-spec":
+                g.specialize_resident()
             now, best = 0.1, []
             for rep in range(3):  # three repetitions: their spread is the yardstick for a difference between variants
                 t0 = 0.0
@@ -65,6 +70,7 @@ for ues, R, G in ((25, 25, 4), (5, 64, 8)):
                         g.schedule_tti_at(calls, now)
                 best.append((time.perf_counter() - t0) / args.calls * 1e6)
             lp = load_phase(g)
-            print(f"{K:3d} cells x {U} UEs x {R} RBGs, {variant:8s}: " + " / ".join(f"{b:.1f}" for b in best) + " us per call (python)"
-                  + (f", load phase {lp} cycles" if lp is not None else ""), flush=True)
+            print(f"{K:3d} cells x {U} UEs x {R} RBGs, {variant:13s}: " + " / ".join(f"{b:.1f}" for b in best) + " us per call (python)"
+                  + (f", load phase {lp} cycles" if lp is not None else "")
+                  + (f", {g.kernel_name}, {g.resident_jit_status()[1]}" if variant == "resident-spec" else ""), flush=True)
             g.close()
