@@ -85,6 +85,9 @@ def lib():
         L.rso_cell_set_second_bearer_avg.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.rso_cell_step.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_int, C.POINTER(_TtiOut)]
         L.rso_cell_allocate.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_int, C.POINTER(_TtiOut)]
+        L.rso_cell_allocate_listed.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int, C.c_int,
+                                               C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(_TtiOut)]
+        L.rso_cell_get_gates.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.rso_cell_allocate_nongreedy.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int), C.c_int,
                                                   C.POINTER(_TtiOut)]
         L.rso_cell_get_state.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64),
@@ -284,6 +287,29 @@ class Cell:
     def allocate(self, avg_rate, rand0, rand1, out):
         a = np.ascontiguousarray(avg_rate, np.float64)
         return lib().rso_cell_allocate(self.h, _p(a, C.c_double), rand0, rand1, C.byref(out.c))
+
+    def allocate_listed(self, avg_rate, out, user_ids=None, slice_id=-1, gate=None, rand0=0, rand1=0):
+        """RBsAllocation() of one call for the listed users (ascending ids; None: all, sched 7: all of slice_id) with the per-user
+        gate of the call: sched 7 required_rbs (PRBs), sched 1 data_to_transmit (bytes), in the order of the list; None = backlogged.
+        avg_rate [U] and every output are indexed by the cell's user id.  UNPINNED (tests/PINS.md)."""
+        a = np.ascontiguousarray(avg_rate, np.float64)
+        assert a.shape == (self.U,)
+        ids = None if user_ids is None else np.ascontiguousarray(user_ids, np.int32)
+        g = None if gate is None else np.ascontiguousarray(gate, np.int32)
+        n = self.U if ids is None else len(ids)
+        assert g is None or ids is None or g.shape == ids.shape
+        return lib().rso_cell_allocate_listed(self.h, _p(a, C.c_double), _optp(ids, C.c_int32), n, int(slice_id), _optp(g, C.c_int32),
+                                              rand0, rand1, C.byref(out.c))
+
+    def gates(self):
+        """(active uint8 [U], data_tx int32 [U][2], required_rbs int64 [U]) of the last step_queues' user records."""
+        act = np.zeros(self.U, np.uint8)
+        dat = np.zeros((self.U, 2), np.int32)
+        req = np.zeros(self.U, np.int64)
+        rc = lib().rso_cell_get_gates(self.h, _p(act, C.c_uint8), _p(dat, C.c_int32), _p(req, C.c_int64))
+        if rc:
+            raise RuntimeError(f"rso_cell_get_gates rc={rc}")
+        return act, dat, req
 
     def allocate_nongreedy(self, avg_rate, slice_id, draws, out):
         """sched 11: RBsAllocationNonGreedyPF for the users of `slice_id` with the rand() values in draw order."""

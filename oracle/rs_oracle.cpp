@@ -610,29 +610,35 @@ int allocate_transport(rso_cell* c, const double* avg, int rand0, int rand1, rso
 
 /* DownlinkPacketScheduler::RBsAllocation + DL_PF metric,
  * ref: downlink-packet-scheduler.cpp:179-331, dl-pf-packet-scheduler.cpp:128-140 */
-int allocate_pf(rso_cell* c, const double* avg, rso_tti_out* out) {
+int allocate_pf(rso_cell* c, const double* avg, rso_tti_out* out, const std::vector<int>* list = nullptr,
+                const int32_t* gate = nullptr) {
   const int U = c->U, R = c->R, G = c->rbg_size;
+  /* the flows of the call in container order: every user, or the listed ones (ascending); gate[i] belongs to the i-th of them */
+  const int n = list ? (int)list->size() : U;
   for (int s = 0; s < c->S; s++) { out->target_rbs[s] = 0; out->quota_rbgs[s] = 0; }
-  std::vector<char> done(U, 0);
-  std::vector<std::vector<uint8_t>> prbs(U);
+  std::vector<char> done(n, 0);
+  std::vector<std::vector<uint8_t>> prbs(n);
   int n_done = 0;
   for (int r = 0; r < R; r++) {
     out->rbg_to_user[r] = -1;
-    if (n_done == U) continue; /* :223-224 break */
+    if (n_done == n) continue; /* :223-224 break */
     double target = 0;
     int pick = -1;
-    for (int k = 0; k < U; k++) {
+    for (int i = 0; i < n; i++) {
+      const int k = list ? (*list)[i] : i;
       double se = c->eff_of_cqi[c->cqi[(size_t)k * R + r]];
       double metric = (se * 180000.) / avg[k];
-      if (metric > target && !done[k]) { target = metric; pick = k; }
+      if (metric > target && !done[i]) { target = metric; pick = i; }
     }
     if (pick < 0) continue;
-    out->rbg_to_user[r] = pick;
-    for (int k = 0; k < G; k++) prbs[pick].push_back(prb_cqi(c, pick, r, k));
-    /* :253-265 incremental TBS test against dataToTransmit*8 = 800 000 000 bits */
+    const int user = list ? (*list)[pick] : pick;
+    out->rbg_to_user[r] = user;
+    for (int k = 0; k < G; k++) prbs[pick].push_back(prb_cqi(c, user, r, k));
+    /* :253-265 incremental TBS test against dataToTransmit*8 (an InfiniteBuffer flow: 800 000 000 bits) */
     int fc = rso_final_cqi(prbs[pick].data(), (int)prbs[pick].size());
     int tbs = rso_tbs_bits(kCqiToMcs[fc - 1], (int)prbs[pick].size());
-    if (tbs >= 100000000 * 8) { done[pick] = 1; n_done++; }
+    const int data = gate ? gate[pick] : 100000000;
+    if (tbs >= data * 8) { done[pick] = 1; n_done++; }
   }
   link_adaptation(c, out->rbg_to_user, out);
   out->served_slice = -1;
@@ -671,7 +677,9 @@ int nvs_select_slice(rso_cell* c) {
   return slice_id;
 }
 
-int allocate_nvs(rso_cell* c, const double* avg, int slice, rso_tti_out* out) {
+/* required_in [U] by user id: m_requiredRBs from the caller (the gate of :299-300 as an input); NULL: formed here as
+ * InsertFlowToUser does */
+int allocate_nvs(rso_cell* c, const double* avg, int slice, rso_tti_out* out, const long* required_in = nullptr) {
   const int U = c->U, R = c->R, G = c->rbg_size;
   for (int s = 0; s < c->S; s++) { out->target_rbs[s] = 0; out->quota_rbgs[s] = 0; }
   /* m_requiredRBs (packet-scheduler.cpp:319-334): wideband CQI over ALL PRBs, then
@@ -683,14 +691,16 @@ int allocate_nvs(rso_cell* c, const double* avg, int slice, rso_tti_out* out) {
   const bool listed = !c->active.empty(); /* queue mode: only the users of the slice that have queued data */
   for (int u = 0; u < U; u++) {
     if (c->u2s[u] != slice || (listed && !c->active[u])) continue;
+    if (required_in) { required[u] = required_in[u]; continue; }
     for (int r = 0; r < R; r++)
       for (int k = 0; k < G; k++) all[r * G + k] = prb_cqi(c, u, r, k);
     int wide = rso_final_cqi(all.data(), R * G);
     /* InsertFlowToUser adds to m_requiredRBs only when it creates the user's record, i.e. for the first bearer seen */
     int first_data = 100000000;
-    if (listed) first_data = c->data_tx[(size_t)u * 2] > 0 ? c->data_tx[(size_t)u * 2] : c->data_tx[(size_t)u * 2 + 1];
+    const bool queues = listed && !c->data_tx.empty(); /* (a listed call on a backlogged cell: InfiniteBuffer flows) */
+    if (queues) first_data = c->data_tx[(size_t)u * 2] > 0 ? c->data_tx[(size_t)u * 2] : c->data_tx[(size_t)u * 2 + 1];
     required[u] = (first_data * 8) / kTbs[0][kMcsToItbs[kCqiToMcs[wide - 1]]];
-    if (listed) c->required_rbs[u] = required[u];
+    if (queues) c->required_rbs[u] = required[u];
   }
   for (int r = 0; r < R; r++) {
     double target = std::numeric_limits<double>::lowest();
@@ -800,6 +810,65 @@ int rso_cell_allocate(rso_cell* c, const double* avg, int rand0, int rand1, rso_
     case RSO_SCHED_NVS_NONGREEDY: return -4; /* rso_cell_allocate_nongreedy / rso_cell_step_rng */
     default: return allocate_transport(c, avg, rand0, rand1, out, true);
   }
+}
+
+/* RBsAllocation() of one call for a listed set of users, with the per-user gate as an input: what rs_schedule_tti sees when the
+ * caller names users through rs_tti_in.user_id and passes required_rbs / data_to_transmit.  PARITY UNPINNED: restated from
+ *   sched 7: downlink-nvs-scheduler.cpp:275-312 -- the race of every RBG starts from numeric_limits<double>::lowest() (:294), a user
+ *            competes while `GetListOfAllocatedRBs()->size() < m_requiredRBs` (:299-300; gate[i] = m_requiredRBs of the i-th listed
+ *            user), the metric is ComputeSchedulingMetric (:360-390: libm pow with the slice's integer exponents, alpha, HoL);
+ *   sched 1: downlink-packet-scheduler.cpp:179-331 -- first maximum from 0 over the listed flows, a flow leaves once
+ *            `transportBlockSize >= GetDataToTransmit() * 8` (:253-265; gate[i] = GetDataToTransmit() of the i-th listed flow);
+ *   sched 8 / 9 / 10 / 101 / 103: downlink-transport-scheduler.cpp:453-675 on GetUsersToSchedule() = the listed users (a slice
+ *            without a listed user has no target and no quota, :463-477); slice_rbs_offset_ is carried as by rso_cell_allocate.
+ * user_ids ascending, NULL = every user; outputs stay indexed by the cell's user id.  c->active is set for the call and restored.
+ * -8: bad list (not ascending, out of range, or for sched 7 a user outside `slice`), -9: a gate for a scheduler that has none. */
+int rso_cell_allocate_listed(rso_cell* c, const double* avg, const int32_t* user_ids, int n, int slice, const int32_t* gate,
+                             int rand0, int rand1, rso_tti_out* out) {
+  const int U = c->U;
+  if (c->sched == RSO_SCHED_NVS_NONGREEDY) return -4;
+  if (c->sched == RSO_SCHED_NVS && (slice < 0 || slice >= c->S)) return -8;
+  for (int s = 0; s < c->S; s++)
+    if (c->alpha[s] != 0 && c->hol.empty() && (c->sched != RSO_SCHED_NVS || s == slice)) return -3;
+  if (gate && c->sched != RSO_SCHED_NVS && c->sched != RSO_SCHED_PF) return -9;
+  std::vector<int> list;
+  if (user_ids) {
+    for (int i = 0; i < n; i++) {
+      if (user_ids[i] < 0 || user_ids[i] >= U || (i > 0 && user_ids[i] <= user_ids[i - 1])) return -8;
+      if (c->sched == RSO_SCHED_NVS && c->u2s[user_ids[i]] != slice) return -8;
+      list.push_back(user_ids[i]);
+    }
+  } else {
+    for (int u = 0; u < U; u++)
+      if (c->sched != RSO_SCHED_NVS || c->u2s[u] == slice) list.push_back(u);
+  }
+  if (c->sched == RSO_SCHED_PF) return allocate_pf(c, avg, out, &list, gate);
+  std::vector<uint8_t> saved(U, 0);
+  for (int u : list) saved[u] = 1;
+  saved.swap(c->active);
+  int rc;
+  if (c->sched == RSO_SCHED_NVS) {
+    std::vector<long> required(U, 0);
+    if (gate)
+      for (size_t i = 0; i < list.size(); i++) required[list[i]] = gate[i];
+    rc = allocate_nvs(c, avg, slice, out, gate ? required.data() : nullptr);
+  } else {
+    rc = allocate_transport(c, avg, rand0, rand1, out, true); /* -1: no listed user (DoSchedule :160-165 does not call it) */
+  }
+  saved.swap(c->active);
+  return rc;
+}
+
+/* read-only: what the last rso_cell_step_queues left in the users' records -- active [U] (in UsersToSchedule; sched 7: of the served
+ * slice), data_tx [U][2] (m_dataToTransmit), required_rbs [U] (m_requiredRBs, sched 7); any pointer may be NULL; -20 without queues */
+int rso_cell_get_gates(const rso_cell* c, uint8_t* active, int32_t* data_tx, int64_t* required_rbs) {
+  if (c->bearers.empty()) return -20;
+  for (int u = 0; u < c->U; u++) {
+    if (active) active[u] = c->active[u];
+    if (data_tx) { data_tx[u * 2] = c->data_tx[(size_t)u * 2]; data_tx[u * 2 + 1] = c->data_tx[(size_t)u * 2 + 1]; }
+    if (required_rbs) required_rbs[u] = c->required_rbs[u];
+  }
+  return 0;
 }
 
 /* DoSchedule(), ref: downlink-transport-scheduler.cpp:152-168, downlink-nvs-scheduler.cpp:196-218,

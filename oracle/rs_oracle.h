@@ -126,6 +126,14 @@ void rso_cell_set_queue_state(rso_cell* c, const double* hol, const uint8_t* pri
 int rso_cell_step(rso_cell* c, double now, int rand0, int rand1, rso_tti_out* out);
 /* RBsAllocation() alone on caller-provided PF state (no EWMA / accounting): mirrors rs_schedule_tti */
 int rso_cell_allocate(rso_cell* c, const double* avg_rate, int rand0, int rand1, rso_tti_out* out);
+/* RBsAllocation() alone for a LISTED set of users and with the per-user gate as an input: mirrors rs_schedule_tti with
+ * rs_tti_in.user_id / required_rbs / data_to_transmit.  PARITY UNPINNED (restated from downlink-nvs-scheduler.cpp:275-312 and :360-390,
+ * downlink-packet-scheduler.cpp:179-331, downlink-transport-scheduler.cpp:453-675; tests/PINS.md).
+ * user_ids [n] ascending (NULL: every user; sched 7: every user of `slice`); slice: the served slice of sched 7, else -1;
+ * gate [n] in the order of the list (NULL: backlogged): sched 7 m_requiredRBs in PRBs, sched 1 GetDataToTransmit() in bytes, any other
+ * scheduler must pass NULL.  Outputs are indexed by the cell's user id; slice_rbs_offset_ moves as in rso_cell_allocate. */
+int rso_cell_allocate_listed(rso_cell* c, const double* avg_rate, const int32_t* user_ids, int n, int slice, const int32_t* gate,
+                             int rand0, int rand1, rso_tti_out* out);
 /* sched 11: RBsAllocationNonGreedyPF for the users of `slice` with the rand() values it would draw, in draw order
  * (RSO_NONGREEDY_SAMPLES x users-of-the-slice values); and the whole DoSchedule() drawing from a generator */
 #define RSO_NONGREEDY_SAMPLES 300
@@ -191,6 +199,9 @@ int rso_run_synth_queues(rso_cell* c, const uint8_t* cqi_epochs, int n_epochs, i
 /* the same run on per-PRB grids ([U][R*G] per epoch) */
 int rso_run_synth_queues_prb(rso_cell* c, const uint8_t* cqi_prb_epochs, int n_epochs, int refresh, unsigned seed, int n_ttis,
                          int* log_rbg_to_user, int* log_tbs_bits);
+/* the users' records of the last rso_cell_step_queues, read-only: active [U], data_tx [U][2] (m_dataToTransmit), required_rbs [U]
+ * (m_requiredRBs, sched 7); any pointer may be NULL */
+int rso_cell_get_gates(const rso_cell* c, uint8_t* active, int32_t* data_tx, int64_t* required_rbs);
 /* per bearer [U][2]: PF average, cumulative bytes / RBs, MAC queue bytes and packets; any pointer may be NULL */
 void rso_cell_get_bearer_state(const rso_cell* c, double* avg, int64_t* cum_bytes, int64_t* cum_rbs, int32_t* queue_bytes,
                                int32_t* queue_packets);

@@ -214,7 +214,10 @@
         }
       } else if (DIRECT && (SCHED == 1 || SCHED == 7) && p.gate != nullptr) {
         /* Drop-in mode with finite queues (rs_tti_in.data_to_transmit / required_rbs): the same RBG-by-RBG race as above on the
-         * caller's candidates -- flows (sched 1: every passed "user" is one flow) / the served slice's users (sched 7). */
+         * caller's candidates -- flows (sched 1: every passed "user" is one flow) / the served slice's users (sched 7).  The
+         * caller's averages and delays are arbitrary doubles, so sched 7's metrics may be negative, -0.0, infinite or NaN: the race
+         * starts from lowest() with a strict '>' (downlink-nvs-scheduler.cpp:294-300: a negative metric wins when nobody better is
+         * eligible, a NaN or -inf never does) and the lanes compare through double_order_key. */
         for (int u = lane; u < U; u += 64) {
           q_need[u] = p.gate[u];
           q_done[u] = 0;
@@ -225,7 +228,7 @@
         const int sl_eps = SCHED == 7 ? (m->eps_psi[sl7] & 1) : 1, sl_psi = SCHED == 7 ? ((m->eps_psi[sl7] >> 1) & 1) : 1;
         const bool custom7 = SCHED == 7 && queue_mode_in && p.alpha[sl7] != 0;
         for (int r = 0; r < R; ++r) {
-          int bhi = -1, blo = (int)0x80000000, bpick = -1;
+          int bhi = (int)0x80000000, blo = (int)0x80000000, bpick = -1;
           for (int c0 = 0; c0 < U; c0 += 64) {
             const int u = c0 + lane;
             bool valid = u < U;
@@ -242,13 +245,15 @@
                 const double den = p.gen_exp ? s_avgk[u] : (sl_psi ? s_avgk[u] : 1.0);
                 if (!custom7) metric = num / den;
                 else metric = (prio_in && (prio_in[u] & 1) == 0) ? 0.0 : hol_in[u] * num / den;
+                valid = valid && metric > -1.7976931348623157e308; /* the scan starts from lowest() with '>': false for a NaN */
               }
             }
-            const int hi = valid ? __double2hiint(metric) : -1;
-            const int lo = (int)((unsigned)__double2loint(metric) ^ 0x80000000u);
+            int hi, lo;
+            double_order_key(metric, hi, lo);
+            hi = valid ? hi : (int)0x80000000;
             const int mhi = wave_max(hi);
             const int mlo = wave_max(hi == mhi ? lo : (int)0x80000000);
-            if (mhi >= 0 && (mhi > bhi || (mhi == bhi && mlo > blo))) {
+            if (mhi != (int)0x80000000 && (mhi > bhi || (mhi == bhi && mlo > blo))) {
               bhi = mhi;
               blo = mlo;
               bpick = c0 + __ffsll((long long)__ballot(valid && hi == mhi && lo == mlo)) - 1;

@@ -45,6 +45,17 @@ RS_DEFINE_WAVE_REDUCE(wave_sum, op_add, 0)
 RS_DEFINE_WAVE_REDUCE(wave_max, op_max, (int)0x80000000)
 RS_DEFINE_WAVE_REDUCE(wave_min, op_min, 0x7fffffff)
 
+/* Order-preserving integer key of a double that is not a NaN: (hi, lo) compared as signed integers, hi first, order like the
+ * doubles themselves, negative ones included (their magnitude bits are inverted).  -0.0 gets the key of +0.0: the two compare equal
+ * as doubles.  No valid key has hi == 0x80000000 (that would be a NaN's bit pattern): it is free to mean "nobody". */
+__device__ __forceinline__ void double_order_key(double x, int& hi, int& lo) {
+  const double z = x == 0.0 ? 0.0 : x;
+  const int h = __double2hiint(z);
+  const unsigned l = (unsigned)__double2loint(z);
+  hi = h < 0 ? (h ^ 0x7fffffff) : h;
+  lo = (int)((h < 0 ? ~l : l) ^ 0x80000000u);
+}
+
 /* maximum over each 32-lane half of the wave, both halves at once (the ladder stops before row_bcast:31: lanes 31 and 63 hold
  * their half's maximum).  Every lane of the wave must take part. */
 __device__ __forceinline__ int half_max(int v) {

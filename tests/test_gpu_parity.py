@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, synth_cqi
+from test_gpu_dropin_oracle import oracle_call, same_call
 
 pytestmark = pytest.mark.gpu
 
@@ -265,11 +266,7 @@ def test_drop_in_single_tti(rs, oracle, sched):
             sl = it % 20
             ids = np.arange(sl * 5, sl * 5 + 5)
             res = ts.schedule_tti(cqi[ids], avg[ids], user_id=ids)
-            # oracle: NVS allocation within a slice = per RBG first max of the slice metric
-            kb = rs.link_tables()["kbps"]
-            met = kb[cqi[ids]] / ((1 + avg[ids]) / 1000.0)[:, None]
-            exp = ids[np.argmax(met, axis=0)]
-            np.testing.assert_array_equal(res.rbg_to_user, exp)
+            same_call(res, oracle_call(cell, ids, cqi[ids], avg[ids], slice_id=sl), ids, f"sched 7 it {it}")
             continue
         cell.set_cqi(cqi)
         out = cell.new_out()
@@ -419,15 +416,8 @@ def test_drop_in_customised_slices(rs, oracle, sched):
             sl = it % S
             ids = np.arange(starts[sl], starts[sl + 1])
             res = ts.schedule_tti(cqi[ids], avg[ids], user_id=ids, hol_delay=hol[ids], prio_has_data=prio[ids])
-            # oracle: per RBG the first maximum of the NVS slice metric from lowest()
-            kb = rs.link_tables()["kbps"]
-            num = kb[cqi[ids]] if eps[sl] else np.ones((len(ids), R))
-            den = ((1 + avg[ids]) / 1000.0)[:, None] if psi[sl] else np.ones((len(ids), 1))
-            if alpha[sl]:
-                met = np.where(prio[ids][:, None] != 0, hol[ids][:, None] * num / den, 0.0)
-            else:
-                met = num / den
-            np.testing.assert_array_equal(res.rbg_to_user, ids[np.argmax(met, axis=0)], err_msg=f"it {it}")
+            out = oracle_call(cell, ids, cqi[ids], avg[ids], slice_id=sl, hol_delay=hol[ids], prio_has_data=prio[ids])
+            same_call(res, out, ids, f"sched 7 it {it}")
             continue
         out = cell.new_out()
         assert cell.allocate(avg, r0, r1, out) == 0
@@ -612,12 +602,12 @@ def test_every_shipped_experiment_configuration(rs, oracle):
 
 def test_drop_in_nvs_big_slice(rs, oracle):
     """sched 7 with slices of more than 32 users on average takes the split scan (runs of the served slice reduced per
-    RBG); here through the drop-in entry point, against the first-maximum rule written out in numpy."""
+    RBG); here through the drop-in entry point, against the oracle's per-call allocation (rso_cell_allocate_listed)."""
     ues, R, G = [45, 40], 25, 4
     sc = rs.SliceConfig(ues)
     ts = rs.TtiScheduler(sc, R, G, sched=7)
+    cell = oracle.Cell(ues, R, G, 7)
     rng = np.random.default_rng(31)
-    kb = rs.link_tables()["kbps"]
     for it in range(6):
         cqi = synth_cqi(700 + it, (sc.n_users, R), HIST)
         avg = rng.uniform(1e3, 5e6, sc.n_users)
@@ -625,8 +615,7 @@ def test_drop_in_nvs_big_slice(rs, oracle):
             avg[:] = 98000.0  # exact ties: the FIRST maximum must win across run boundaries
         ids = np.arange(0, 45) if it % 2 else np.arange(45, 85)
         res = ts.schedule_tti(cqi[ids], avg[ids], user_id=ids)
-        met = kb[cqi[ids]] / ((1 + avg[ids]) / 1000.0)[:, None]
-        np.testing.assert_array_equal(res.rbg_to_user, ids[np.argmax(met, axis=0)])
+        same_call(res, oracle_call(cell, ids, cqi[ids], avg[ids], slice_id=1 - it % 2), ids, f"it {it}")
     ts.close()
 
 

@@ -134,12 +134,14 @@ def test_drop_in_accepts_any_double(rs, oracle, sched):
 
 
 @pytest.mark.gpu
-def test_drop_in_nvs_accepts_any_double(rs):
-    """sched 7 (one slice per call): first maximum of the slice metric from lowest(), whatever the doubles are."""
+def test_drop_in_nvs_accepts_any_double(rs, oracle):
+    """sched 7 (one slice per call): first maximum of the slice metric from lowest(), whatever the doubles are (negative, infinite
+    and NaN metrics: test_gpu_dropin_oracle.py)."""
+    from test_gpu_dropin_oracle import oracle_call, same_call
     ues, R, G = [8] * 4, 25, 4
     sc = rs.SliceConfig(ues, weight=[0.25] * 4)
     ts = rs.TtiScheduler(sc, R, G, sched=7)
-    kb = rs.link_tables()["kbps"]
+    cell = oracle.Cell(ues, R, G, 7, weights=[0.25] * 4)
     rng = np.random.default_rng(8)
     for it in range(8):
         sl = it % 4
@@ -147,8 +149,7 @@ def test_drop_in_nvs_accepts_any_double(rs):
         cqi = synth_cqi(40 + it, (8, R), HIST)
         avg = rng.choice(np.array([1.0, 1e12, 1e300, 5e40]), 8)
         res = ts.schedule_tti(cqi, avg, user_id=ids)
-        met = kb[cqi] / ((1 + avg) / 1000.0)[:, None]
-        np.testing.assert_array_equal(res.rbg_to_user, ids[np.argmax(met, axis=0)], err_msg=f"it {it}")
+        same_call(res, oracle_call(cell, ids, cqi, avg, slice_id=sl), ids, f"it {it}")
     ts.close()
 
 
@@ -392,8 +393,9 @@ def test_drop_in_nvs_general_exponents(rs, oracle):
     ues, R, G = [8, 6, 9], 25, 4
     eps, psi = [3, -1, 2], [2, 2, -1]
     sc = rs.SliceConfig(ues, weight=[0.3, 0.3, 0.4], algo_epsilon=eps, algo_psi=psi)
+    from test_gpu_dropin_oracle import oracle_call, same_call
     ts = rs.TtiScheduler(sc, R, G, sched=7)
-    kb = np.asarray(rs.link_tables()["kbps"])
+    cell = oracle.Cell(ues, R, G, 7, weights=[0.3, 0.3, 0.4], epsilon=eps, psi=psi)  # libm's pow, as the reference calls it
     rng = np.random.default_rng(8)
     first = np.concatenate([[0], np.cumsum(ues)])
     for it in range(9):
@@ -404,19 +406,7 @@ def test_drop_in_nvs_general_exponents(rs, oracle):
         avg = np.exp(rng.uniform(np.log(1.0), np.log(5e7), n))
         need = rng.integers(0, 40, n).astype(np.int32) if it % 2 else None
         res = ts.schedule_tti(cqi, avg, user_id=ids, **({"required_rbs": need} if need is not None else {}))
-        # libm's pow, element by element: numpy's vectorised power is a different implementation (last-bit differences)
-        num = np.array([[math.pow(float(kb[c]), eps[s]) for c in row] for row in cqi])
-        den = np.array([math.pow((1.0 + float(a)) / 1000.0, psi[s]) for a in avg])
-        met = num / den[:, None]
-        left = need.copy() if need is not None else np.full(n, 1 << 30)
-        want = np.full(R, -1)
-        for r in range(R):
-            ok = left > 0
-            if ok.any():
-                k = int(np.flatnonzero(ok)[np.argmax(met[ok, r])])
-                want[r] = ids[k]
-                left[k] -= G
-        np.testing.assert_array_equal(res.rbg_to_user, want, err_msg=f"it {it}")
+        same_call(res, oracle_call(cell, ids, cqi, avg, slice_id=s, gate=need), ids, f"it {it}")
     ts.close()
 
 

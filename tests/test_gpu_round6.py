@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import synth_cqi
+from test_gpu_dropin_oracle import oracle_call, same_call
 
 pytestmark = pytest.mark.gpu
 
@@ -33,9 +34,8 @@ def _drive(rs, oracle, ts, sched, ues, R, G, n_calls, seed, use_epoch=True, refr
     (CQI_INTERVAL 40) and, use_epoch, the caller says so through cqi_epoch.  Returns the number of calls compared."""
     U = sum(ues)
     S = len(ues)
-    cell = oracle.Cell(ues, R, G, sched if sched != 7 else 9, weights=[1.0 / S] * S)
+    cell = oracle.Cell(ues, R, G, sched, weights=[1.0 / S] * S)
     rng = np.random.default_rng(seed)
-    kb = rs.link_tables()["kbps"]
     avg = rng.uniform(1e3, 5e6, U)
     cqi = prb = None
     for it in range(n_calls):
@@ -55,8 +55,7 @@ def _drive(rs, oracle, ts, sched, ues, R, G, n_calls, seed, use_epoch=True, refr
             lo = int(np.sum(ues[:sl]))
             ids = np.arange(lo, lo + ues[sl])
             res = ts.schedule_tti(cqi[ids], avg[ids], user_id=ids, cqi_epoch=epoch)
-            met = kb[cqi[ids]] / ((1 + avg[ids]) / 1000.0)[:, None]
-            np.testing.assert_array_equal(res.rbg_to_user, ids[np.argmax(met, axis=0)], err_msg=f"sched 7 call {it}")
+            same_call(res, oracle_call(cell, ids, cqi[ids], avg[ids], slice_id=sl), ids, f"sched 7 call {it}")
             continue
         if per_prb:
             cell.set_cqi_prb(prb)
@@ -489,10 +488,10 @@ def test_bench_line_carries_a_parity_sample_and_fails_when_it_is_wrong():
 @pytest.mark.parametrize("seed", [3, 4, 5, 6])
 def test_drop_in_fuzz_seeds(rs, oracle, seed, monkeypatch):
     """tools/fuzz_dropin.py (random shapes and schedulers; the CQI block and the user list change independently; per-PRB reports on some
-    seeds): a specialised, self-checked context with cqi_epoch == a built-in context without == the oracle where every user is listed."""
+    seeds): a specialised, self-checked context with cqi_epoch == a built-in context without == the oracle on every call."""
     import importlib.util
     monkeypatch.setenv("RS_JIT_SELFCHECK", "2")
     spec = importlib.util.spec_from_file_location("fuzz_dropin", ROOT / "tools" / "fuzz_dropin.py")
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    mod.one_seed(seed, 24)
+    assert mod.one_seed(seed, 24)[6] == 24, "a call went without the oracle"

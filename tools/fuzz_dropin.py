@@ -10,7 +10,8 @@ reports.  Three parties on every call:
 
     A  a specialised context (rs_ctx_specialize) with cqi_epoch, RS_JIT_SELFCHECK=2 (its first calls run beside the built-in kernel)
     B  a built-in context that is handed the true reports with cqi_epoch = 0        (every output field and the slice state: A == B)
-    O  the oracle, on the calls that schedule every user (schedulers other than NVS)  (A == O)
+    O  the oracle's per-call allocation for the listed users (rso_cell_allocate_listed: every scheduler, subsets and NVS
+       included), every output field of every call                                   (A == O)
 """
 import os
 import sys
@@ -48,7 +49,10 @@ def one_seed(seed, n_calls):
     per_prb = bool(rng.random() < 0.25) and sched != 7
     a = rs.TtiScheduler(sc, R, G, sched=sched, jit=True)
     b = rs.TtiScheduler(sc, R, G, sched=sched)
-    cell = O.Cell(ues, R, G, sched if sched != 7 else 9, weights=w)
+    # an oracle binding from before rso_cell_allocate_listed can answer only the calls that list every user of a non-NVS cell
+    # (rso_cell_allocate); the count returned says how many calls were compared, and main() refuses such a binding
+    listed = hasattr(O.Cell, "allocate_listed")
+    cell = O.Cell(ues, R, G, sched if listed or sched != 7 else 9, weights=w)
     epoch, cqi, prb, ids = 0, None, None, None
     n_oracle = n_reused = 0
     for it in range(n_calls):
@@ -87,10 +91,20 @@ def one_seed(seed, n_calls):
             np.testing.assert_array_equal(ra.upper_rbg, rb.upper_rbg)
             np.testing.assert_array_equal(ra.upper_user, rb.upper_user)
         assert a.slice_offset.tobytes() == b.slice_offset.tobytes(), f"seed {seed} call {it}: slice state"
-        if sched != 7 and len(ids) == U:
-            # the oracle carries its own slice_rbs_offset_: bring it to where the contexts were BEFORE this call
-            cell.set_cqi_prb(prb) if per_prb else cell.set_cqi(cqi)
-            out = cell.new_out()
+        cell.set_cqi_prb(prb) if per_prb else cell.set_cqi(cqi)
+        out = cell.new_out()
+        if listed:
+            # the oracle carries slice_rbs_offset_ across its calls as the contexts do; outputs by user id, the contexts' by call position
+            assert cell.allocate_listed(avg, out, ids, slice_id=int(u2s[ids[0]]) if sched == 7 else -1, rand0=r0, rand1=r1) == 0
+            for f in FIELDS:
+                want = getattr(out, f)
+                np.testing.assert_array_equal(getattr(ra, f), want[ids] if f.startswith("user_") else want,
+                                              err_msg=f"seed {seed} sched {sched} call {it}: {f} (vs oracle)")
+            if sched not in (1, 7):
+                assert a.slice_offset.tobytes() == cell.state()["slice_state"].tobytes(), f"seed {seed} call {it}: slice offsets (vs oracle)"
+            n_oracle += 1
+        elif sched != 7 and len(ids) == U:
+            # rso_cell_allocate knows neither NVS nor subsets; bring its slice_rbs_offset_ to where the contexts were BEFORE this call
             cell.set_slice_offset(prev_offset) if it else None
             assert cell.allocate(avg, r0, r1, out) == 0
             for f in FIELDS:
@@ -109,8 +123,8 @@ def main():
     first = int(sys.argv[1]) if len(sys.argv) > 1 else 100
     n = int(sys.argv[2]) if len(sys.argv) > 2 else 20
     calls = int(sys.argv[3]) if len(sys.argv) > 3 else 30
-    if not hasattr(O.Cell, "set_slice_offset"):
-        raise SystemExit("the oracle binding has no set_slice_offset")
+    if not hasattr(O.Cell, "allocate_listed"):
+        raise SystemExit("the oracle binding has no allocate_listed")
     tot_o = tot_r = 0
     for seed in range(first, first + n):
         sched, S, U, R, G, per_prb, n_o, n_r = one_seed(seed, calls)
