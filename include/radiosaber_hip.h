@@ -30,7 +30,8 @@ extern "C" {
                                rs_group_* (one TTI of several drop-in cells in one launch), rs_group_image_stats (cqi_epoch per cell of a group),
                                rs_group_specialize / rs_group_jit_status / rs_jit_selfcheck_group (a group's own self-checked builds of the one-TTI kernel),
                                rs_group_set_avg / rs_group_get_avg / rs_group_set_pending / rs_group_schedule_tti_at (a group cell's PF averages resident on the device),
-                               rs_group_specialize_resident / rs_group_resident_jit_status / rs_jit_selfcheck_group_resident (a group's own builds of the resident kernel, self-checked on state);
+                               rs_group_specialize_resident / rs_group_resident_jit_status / rs_jit_selfcheck_group_resident (a group's own builds of the resident kernel, self-checked on state),
+                               rs_group_set_bearers / rs_group_get_bearers / rs_group_schedule_tti_queued (a group cell's two bearers per user resident on the device: finite queues credited there);
                                rs_config.link_tables (RS_LINK_*) + rs_link_tables_pinned / rs_link_tables_compare, rs_tti_in.cqi_epoch (the context keeps the
                                CQI image of an unchanged report set on the device), rs_ctx_jit_status (a specialised context checks its run-time build against the
                                built-in kernel during its first calls), rs_batch_config.selfcheck -1 / 0 / 1 with run-time builds verified by default and the
@@ -347,10 +348,10 @@ int rs_jit_selfcheck_group(int n_slices, int n_users, int n_rbgs, int rbg_size, 
  *      if (a < 1) a = 1;  pending[u] = 0;  -- then last_update = now.  (The batch kernels' operations, in their order, unfused.)
  *   2. The call's users (user_id[i], or 0..n-1) are scheduled as by rs_group_schedule_tti with avg_rate[i] = avg[user_id[i]].
  *   3. Each served user's grant, min(tbs_bits / 8, 100000000) bytes (the InfiniteBuffer's dataToTransmit), is added to pending[user_id[i]].
- * A cell is one bearer per user.  A user that holds two bearers needs the ((1 + a0) + a1) - 1 form of avg_rate and
- * stays on the plain call.  A caller whose bearers have finite queues, where DoStopSchedule credits min(grant, dataToTransmit)
- * (downlink-transport-scheduler.cpp:177-188) and not the transport block, overwrites the pending bytes after the call
- * (rs_group_set_pending: a synchronising copy, outside the fast path).
+ * A cell of this form is one InfiniteBuffer bearer per user.  Users that hold two bearers, and bearers with finite queues -- where
+ * DoStopSchedule credits min(grant, dataToTransmit) (downlink-transport-scheduler.cpp:177-188) and not the transport block -- are
+ * served by the second resident form, resident bearers (rs_group_set_bearers / rs_group_schedule_tti_queued below).
+ * (rs_group_set_pending overwrites the pending bytes of this form: a synchronising copy, outside the fast path.)
  * rs_group_schedule_tti is unchanged: it still needs avg_rate, and on a resident cell it uses the caller's averages and neither reads
  * nor writes the resident state.
  * Resident calls run the resident kernel built into the library ("rs_group_resident_kernel<sched, ept>" in rs_group_kernel_name while
@@ -399,6 +400,56 @@ int rs_group_resident_jit_status(rs_group* g, char* msg, size_t msglen);
 /* build check without a GPU: do the general and the lean resident build of a group of this shape compile?  (the larger code size, or a
  * negative value with the compiler's log in err; RS_SCHED_NVS_NONGREEDY has no group builds) */
 int rs_jit_selfcheck_group_resident(int n_slices, int n_users, int n_rbgs, int rbg_size, int threads, int sched, char* err, size_t errlen);
+
+/* Resident bearers (ABI 11 addition, no layout changed): the second resident form of a group's cell.  The cell keeps, per user id of the
+ * config and per bearer (MAX_BEARERS = 2, index = the bearer's priority), RadioBearer's average rate and the bytes DoStopSchedule
+ * credited since the last update, and whether the bearer exists; one last_update per cell (the reference's bearers all share it from
+ * their first DoSchedule() on).  The caller passes what SelectFlowsToSchedule formed: data_to_transmit[k][i][b] is
+ * UserToSchedule::m_dataToTransmit[b] of the call's i-th user -- 100000000 for an InfiniteBuffer bearer, the queue size with MAC
+ * overhead for a finite one, 0 for a bearer without packets or without existence.  Per slot of rs_group_schedule_tti_queued, in this order:
+ *   1. now == last_update: nothing.  Otherwise, for every EXISTING bearer of every user id of the config, named or not:
+ *      rate = (double)(pending * 8) / (now - last_update);  a = ((1 - 0.02) * a) + (0.02 * rate);  if (a < 1) a = 1;  pending = 0;
+ *      -- then last_update = now.  Step 1 of rs_group_schedule_tti_at per bearer: same operations, same wrapping int product, unfused.
+ *      A bearer that does not exist is neither read nor written.
+ *   2. Position i's average is the sum over the bearers WITH DATA (the reference sums the bearers it inserted, ComputeSchedulingMetric
+ *      downlink-transport-scheduler.cpp:681-687), in the form whose 1 + x the kernel takes: a[b] when only bearer b has data,
+ *      ((1 + a0) + a1) - 1 when both have -- exact while the sum stays below 2^53, hence the bound on the averages.
+ *   3. The TTI is scheduled as by rs_group_schedule_tti on those averages; hol_delay, prio_has_data, required_rbs, cqi / cqi_prb,
+ *      cqi_epoch, user_id, rand0 / rand1 stay the caller's.
+ *   4. DoStopSchedule's loop (:170-221) per position: available = tbs_bits / 8; for b = 1, 0: stop when available <= 0; if
+ *      data[b] > 0: sent = min(available, data[b]); available -= sent; pending[user][b] += sent.
+ * Update-only slots: in[k].n_users == 0 is accepted by this call alone -- a finite-queue cell often has nobody to schedule, and the
+ * reference then skips RBsAllocation (:163-165) but has run the update.  Such a slot does step 1 alone: no rand() pair is consumed
+ * (rand0 / rand1 are not read), slice state and CQI image are untouched, nothing else of in[k] is read, and out[k] reads "nothing
+ * scheduled" (rbg_to_user -1, target_rbs / quota_rbgs 0; out[k]'s arrays may be NULL).  A call whose slots are all update-only
+ * still launches once.  RS_SCHED_NVS: the caller chooses the served slice, and an update-only slot moves no slice state.
+ * Queued calls run the built-in "rs_group_queued_kernel<sched, ept>" (rs_group_kernel_name while a queued call is the last one
+ * served); rs_group_specialize and rs_group_specialize_resident do not reach them: same results before and after either. */
+/* Makes `cell` bearer-resident (again, at any time between two calls; a cell is average-resident or bearer-resident, the later of
+ * rs_group_set_avg / rs_group_set_bearers wins): has_bearer[U][2] and avg[U][2] by user id and bearer priority, zero pending bytes.
+ * A user may have no bearer at all; avg of a bearer that does not exist is not read.  RS_ERR_INVALID: RS_SCHED_PF (it races flows
+ * and credits the whole block to the flow), RS_SCHED_UPPERBOUND and RS_SCHED_NVS_NONGREEDY (no restatement with queues to check
+ * against); exponents outside {0, 1}; an existing bearer's average outside 1..2^51 (so that (1 + a0) + a1 < 2^53); a
+ * last_update that is not finite. */
+int rs_group_set_bearers(rs_group* g, int32_t cell, const uint8_t* has_bearer /* [U][2], index = bearer priority */,
+                         const double* avg /* [U][2] */, double last_update);
+/* The bearer state as it is after the last call (a synchronising copy; not part of a TTI); 0 for a bearer that does not exist.  Each
+ * output may be NULL.  RS_ERR_STATE: the cell is not bearer-resident. */
+int rs_group_get_bearers(rs_group* g, int32_t cell, double* avg /* [U][2] or NULL */, int32_t* pending_bytes /* [U][2] or NULL */,
+                         double* last_update /* or NULL */);
+/* rs_group_schedule_tti for bearer-resident cells.  Every rule of a group call holds (uniform presence of optional inputs among the
+ * slots that have users, cqi_epoch per cell, subsets and permutations through cell_ids; a rejected call launches nothing and moves
+ * nothing; rs_group_launch_count and rs_group_image_stats count these calls like any others -- an update-only slot counts in no
+ * image statistic), and
+ *   - in[k].avg_rate is NULL for every k (RS_ERR_INVALID);
+ *   - every named cell is bearer-resident (RS_ERR_STATE); rs_group_schedule_tti_at on such a cell is RS_ERR_STATE too, while
+ *     rs_group_schedule_tti works on it and touches none of its resident state;
+ *   - the clock rules of rs_group_schedule_tti_at, unchanged;
+ *   - data_to_transmit[k] may be NULL only when in[k].n_users == 0; every data word is >= 0, a named user has data in at least one
+ *     bearer, and data > 0 only where the bearer exists (RS_ERR_INVALID; the library keeps a mirror of has_bearer on the host).
+ * A call that fails with RS_ERR_HIP leaves the cells it named not resident. */
+int rs_group_schedule_tti_queued(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in /* [n] */, rs_tti_out* out /* [n] */,
+                                 const double* now /* [n] */, const int32_t* const* data_to_transmit /* [n]: [in[k].n_users][2] */);
 
 /* ------------------------------------------------------------------------------------------
  * Batched mode: many independent cells resident on the device, whole DoSchedule() loops

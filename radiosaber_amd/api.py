@@ -112,6 +112,7 @@ ABI_SYMBOLS = [
     "rs_group_image_stats", "rs_group_specialize", "rs_group_jit_status", "rs_jit_selfcheck_group",
     "rs_group_set_avg", "rs_group_get_avg", "rs_group_set_pending", "rs_group_schedule_tti_at",
     "rs_group_specialize_resident", "rs_group_resident_jit_status", "rs_jit_selfcheck_group_resident",
+    "rs_group_set_bearers", "rs_group_get_bearers", "rs_group_schedule_tti_queued",
 ]
 
 _lib = None
@@ -157,6 +158,10 @@ def lib():
     L.rs_group_get_avg.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double)]
     L.rs_group_set_pending.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
     L.rs_group_schedule_tti_at.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_TtiIn), C.POINTER(_TtiOut), C.POINTER(C.c_double)]
+    L.rs_group_set_bearers.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.c_double]
+    L.rs_group_get_bearers.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double)]
+    L.rs_group_schedule_tti_queued.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_TtiIn), C.POINTER(_TtiOut),
+                                               C.POINTER(C.c_double), C.POINTER(C.POINTER(C.c_int32))]
     L.rs_group_jit_status.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.rs_jit_selfcheck_group.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
     L.rs_group_specialize_resident.argtypes = [C.c_void_p]
@@ -732,6 +737,58 @@ class GroupScheduler:
         ids = None if cell_ids is None else np.ascontiguousarray(cell_ids, np.int32)
         assert ids is None or ids.shape == (n,)
         _check(lib().rs_group_schedule_tti_at(self._h, n, _p(ids, C.c_int32) if ids is not None else None, ins, outs, _p(t, C.c_double)))
+        return results
+
+    # ---- resident bearers: both bearers of every user stay on the device, finite queues are credited there ----
+    def set_bearers(self, cell, has_bearer, avg, last_update):
+        """rs_group_set_bearers: makes `cell` bearer-resident with has_bearer [n_users][2] and avg [n_users][2] by user id and bearer
+        priority (1 <= avg <= 2**51 where the bearer exists), zero pending bytes and last_update.  Any time between two calls."""
+        U = self.slices.n_users
+        h = np.ascontiguousarray(has_bearer, np.uint8)
+        a = np.ascontiguousarray(avg, np.float64)
+        assert h.shape == (U, 2) and a.shape == (U, 2)
+        _check(lib().rs_group_set_bearers(self._h, cell, _p(h, C.c_uint8), _p(a, C.c_double), float(last_update)))
+
+    def get_bearers(self, cell):
+        """(avg float64 [n_users][2], pending bytes int32 [n_users][2], last_update) of a bearer-resident cell, 0 for a bearer that does
+        not exist: a synchronising copy, not part of a TTI."""
+        U = self.slices.n_users
+        a = np.zeros((U, 2), np.float64)
+        pend = np.zeros((U, 2), np.int32)
+        last = C.c_double(0)
+        _check(lib().rs_group_get_bearers(self._h, cell, _p(a, C.c_double), _p(pend, C.c_int32), C.byref(last)))
+        return a, pend, float(last.value)
+
+    def schedule_tti_queued(self, calls: Sequence[dict], now, cell_ids: Optional[Sequence[int]] = None) -> List[TtiResult]:
+        """rs_group_schedule_tti_queued: schedule_tti for bearer-resident cells.  calls[k] as for schedule_tti_at plus data_to_transmit
+        [n][2], UserToSchedule::m_dataToTransmit of the call's users by bearer priority; or dict(n_users=0), an update-only slot:
+        the cell's bearers get their EWMA step at now[k] and nothing is scheduled (its result reads rbg_to_user -1, targets and quotas 0)."""
+        n = len(calls)
+        S, R = self.slices.n_slices, self.R
+        ins, outs, results, keep = (_TtiIn * n)(), (_TtiOut * n)(), [], []
+        data = (C.POINTER(C.c_int32) * n)()
+        for k, kw in enumerate(calls):
+            kw = dict(kw)
+            if kw.get("n_users", None) == 0:
+                assert len(kw) == 1, "an update-only slot gives nothing but n_users=0"
+                z = np.zeros(0, np.int32)
+                res = TtiResult(np.zeros(S, np.int32), np.zeros(S, np.int32), np.zeros(R, np.int32), z, z.copy(), z.copy(), z.copy())
+                ins[k] = _TtiIn()
+                outs[k] = _TtiOut(_p(res.target_rbs, C.c_int32), _p(res.quota_rbgs, C.c_int32), _p(res.rbg_to_user, C.c_int32),
+                                  None, None, None, None, None, None)
+                results.append(res)
+                continue
+            d = np.ascontiguousarray(kw.pop("data_to_transmit"), np.int32)
+            tin, tout, res, arrays = _marshal_tti(S, R, self.rbg_size, self.sched, kw.pop("cqi", None), kw.pop("avg_rate", None), **kw)
+            assert d.shape == (tin.n_users, 2)
+            ins[k], outs[k] = tin, tout
+            data[k] = _p(d, C.c_int32)
+            results.append(res)
+            keep.append((arrays, d))
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(now, np.float64), (n,)))
+        ids = None if cell_ids is None else np.ascontiguousarray(cell_ids, np.int32)
+        assert ids is None or ids.shape == (n,)
+        _check(lib().rs_group_schedule_tti_queued(self._h, n, _p(ids, C.c_int32) if ids is not None else None, ins, outs, _p(t, C.c_double), data))
         return results
 
     def slice_offset(self, cell):

@@ -2453,6 +2453,17 @@ struct rs_group {
   int rchk_left[2] = {0, 0}, rchk_agreed[2] = {0, 0};
   uint8_t* d_rchk = nullptr;
   char rjit_msg[512] = "";
+  /* resident bearers (rs_group_set_bearers, rs_group_schedule_tti_queued): per cell [U][2] averages, pending bytes and existence bytes
+   * of the users' two bearers and the call's data words in call order (allocated by the first rs_group_set_bearers); d_rlast, d_rgather
+   * and d_ruid above serve both forms.  resident[cell] says which: 0 none, 1 averages (rs_group_set_avg), 2 bearers.  The slots' data
+   * words travel in a pinned block of their own (h_qin: [n_cells][U][2], mapped: z_qin, else copied to d_qin), so that the slots of
+   * the other calls keep their size.  has_bearer: the host's mirror of the existence bytes, [n_cells][U][2]. */
+  double* d_qavg = nullptr;
+  int32_t *d_qpend = nullptr, *d_qdata = nullptr, *h_qin = nullptr, *z_qin = nullptr, *d_qin = nullptr;
+  uint8_t* d_qhas = nullptr;
+  std::vector<uint8_t> has_bearer, empty_slot; /* empty_slot: per call slot, n_users == 0 (an update-only slot of a queued call) */
+  int last_call_kind = 0; /* 0 plain, 1 resident, 2 queued */
+  char kname_que[56] = "";
 };
 
 namespace {
@@ -2537,6 +2548,8 @@ rs_group* rs_group_create(const rs_config* cfg, int32_t n_cells) {
   const bool sorts = b->sched == RS_SCHED_MAXCELL || b->sched == RS_SCHED_UPPERBOUND;
   snprintf(g->kname, sizeof g->kname, "rs_group_kernel<%d, %d>", b->sched, sorts && ept <= 4 ? ept : 0);
   snprintf(g->kname_res, sizeof g->kname_res, "rs_group_resident_kernel<%d, %d>", b->sched, sorts && ept <= 4 ? ept : 0);
+  snprintf(g->kname_que, sizeof g->kname_que, "rs_group_queued_kernel<%d, %d>", b->sched, b->sched == RS_SCHED_MAXCELL && ept <= 4 ? ept : 0);
+  g->empty_slot.assign(n_cells, 0);
   g->resident.assign(n_cells, 0);
   g->pending_zero.assign(n_cells, 0);
   g->last_update.assign(n_cells, 0.0);
@@ -2564,6 +2577,12 @@ void rs_group_destroy(rs_group* g) {
   if (g->d_rlast) (void)hipFree(g->d_rlast);
   if (g->d_rgather) (void)hipFree(g->d_rgather);
   if (g->d_ruid) (void)hipFree(g->d_ruid);
+  if (g->d_qavg) (void)hipFree(g->d_qavg);
+  if (g->d_qpend) (void)hipFree(g->d_qpend);
+  if (g->d_qdata) (void)hipFree(g->d_qdata);
+  if (g->d_qhas) (void)hipFree(g->d_qhas);
+  if (g->d_qin) (void)hipFree(g->d_qin);
+  if (g->h_qin) (void)hipHostFree(g->h_qin);
   if (g->h_in) (void)hipHostFree(g->h_in);
   if (g->h_out) (void)hipHostFree(g->h_out);
   rs_batch_destroy(g->b);
@@ -2571,6 +2590,7 @@ void rs_group_destroy(rs_group* g) {
 }
 
 extern "C" hipError_t rs_launch_group_resident(const RsLaunch* p, int threads, hipStream_t stream);
+extern "C" hipError_t rs_launch_group_queued(const RsLaunch* p, int threads, hipStream_t stream);
 
 namespace {
 /* Resident averages and the FP32 filter.  The metric scan's filter needs (1 + a) / 1000 (scheduler 1: a) inside [2^-60, 2^60] for every
@@ -2590,8 +2610,14 @@ namespace {
  * hol_delay is still the caller's and still switches a call to the exact scan. */
 constexpr double kResidentAvgMax = 0x1p52;
 constexpr double kResidentMinDt = 0x1p-20;
+/* Resident bearers: a call position's average is a[b] of the one bearer with data or ((1 + a0) + a1) - 1, whose 1 + x must give back
+ * (1 + a0) + a1 exactly -- it does while that sum is below 2^53 -- and must stay inside the filter's range: rs_group_set_bearers refuses
+ * a > 2^51, and the growth argument above carries over bearer by bearer (the same update, |rate| < 2^51): a <= 2^51 (1 + 2^-51)^k. */
+constexpr double kBearerAvgMax = 0x1p51;
+enum { kGroupPlain = 0, kGroupResident = 1, kGroupQueued = 2 };
 
-int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out, const double* now);
+int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out, const double* now,
+                   const int32_t* const* qdata = nullptr);
 }  // namespace
 
 int rs_group_schedule_tti(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out) {
@@ -2604,11 +2630,19 @@ int rs_group_schedule_tti_at(rs_group* g, int32_t n, const int32_t* cell_ids, co
   return group_schedule(g, n, cell_ids, in, out, now);
 }
 
+int rs_group_schedule_tti_queued(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out, const double* now,
+                                 const int32_t* const* data_to_transmit) {
+  if (!g || !in || !out || !now || !data_to_transmit) return fail(RS_ERR_INVALID, "null argument");
+  return group_schedule(g, n, cell_ids, in, out, now, data_to_transmit);
+}
+
 namespace {
-/* one group call; now != null: the resident form (rs_group_schedule_tti_at) */
-int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out, const double* now) {
+/* one group call; now != null: a resident form -- averages (rs_group_schedule_tti_at) or, with qdata, bearers (rs_group_schedule_tti_queued) */
+int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out, const double* now,
+                   const int32_t* const* qdata) {
   rs_batch* b = g->b;
-  const bool res = now != nullptr;
+  const bool res = now != nullptr, que = qdata != nullptr;
+  const int kind = que ? kGroupQueued : (res ? kGroupResident : kGroupPlain);
   using clk = std::chrono::steady_clock;
   const clk::time_point t0 = g->timing ? clk::now() : clk::time_point();
   if (n < 1 || n > g->n_cells) return fail(RS_ERR_INVALID, "n %d outside 1..%d (the group's cells)", n, g->n_cells);
@@ -2629,14 +2663,21 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
   /* the presence of optional inputs is a per-launch switch of the kernel: the same for every cell of the call */
   auto gate_of = [&](const rs_tti_in& t) { return b->sched == RS_SCHED_NVS ? t.required_rbs : (b->sched == RS_SCHED_PF ? t.data_to_transmit : nullptr); };
   auto upper_of = [&](const rs_tti_out& o) { return b->sched == RS_SCHED_UPPERBOUND && (o.upper_rbg || o.upper_user); };
-  const bool has_prb = in[0].cqi_prb != nullptr, has_hol = in[0].hol_delay != nullptr, has_prio = in[0].prio_has_data != nullptr,
-             has_gate = gate_of(in[0]) != nullptr, want_upper = upper_of(out[0]);
-  for (int k = 1; k < n; k++) {
+  /* (a queued call's update-only slots, n_users == 0, give no inputs at all: the slots WITH users agree among themselves) */
+  int k0 = 0;
+  while (que && k0 < n && in[k0].n_users == 0) k0++;
+  const bool any_users = k0 < n;
+  if (!any_users) k0 = 0;
+  const bool has_prb = any_users && in[k0].cqi_prb != nullptr, has_hol = any_users && in[k0].hol_delay != nullptr,
+             has_prio = any_users && in[k0].prio_has_data != nullptr, has_gate = any_users && gate_of(in[k0]) != nullptr,
+             want_upper = any_users && upper_of(out[k0]);
+  for (int k = k0 + 1; k < n; k++) {
+    if (que && in[k].n_users == 0) continue;
     const char* what = (in[k].cqi_prb != nullptr) != has_prb ? "cqi_prb" : (in[k].hol_delay != nullptr) != has_hol ? "hol_delay"
                      : (in[k].prio_has_data != nullptr) != has_prio ? "prio_has_data"
                      : (gate_of(in[k]) != nullptr) != has_gate ? (b->sched == RS_SCHED_NVS ? "required_rbs" : "data_to_transmit")
                      : upper_of(out[k]) != want_upper ? "upper_rbg / upper_user" : nullptr;
-    if (what) return fail(RS_ERR_INVALID, "mixed call: cell slot %d and cell slot 0 differ in whether they give %s (optional inputs are given by every cell of a call or by none)", k, what);
+    if (what) return fail(RS_ERR_INVALID, "mixed call: cell slot %d and cell slot %d differ in whether they give %s (optional inputs are given by every cell of a call or by none)", k, k0, what);
   }
   if (res) {
     if (b->gen_exp)
@@ -2644,7 +2685,12 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
     for (int k = 0; k < n; k++) {
       const int cell = cell_ids ? cell_ids[k] : k;
       if (in[k].avg_rate) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): avg_rate must be NULL: the cell's averages are resident on the device", k, cell);
+      if (que && g->resident[cell] != 2) return fail(RS_ERR_STATE, "cell slot %d: cell %d is not bearer-resident (rs_group_set_bearers first)", k, cell);
+      if (!que && g->resident[cell] == 2)
+        return fail(RS_ERR_STATE, "cell slot %d: cell %d is bearer-resident (rs_group_set_bearers): rs_group_schedule_tti_queued serves it, or rs_group_set_avg makes it average-resident", k, cell);
       if (!g->resident[cell]) return fail(RS_ERR_STATE, "cell slot %d: cell %d is not resident (rs_group_set_avg first)", k, cell);
+      if (que && in[k].n_users < 0) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): n_users %d is negative", k, cell, in[k].n_users);
+      if (que && in[k].n_users > 0 && !qdata[k]) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): data_to_transmit[%d] is NULL (only an update-only slot, n_users == 0, gives none)", k, cell, k);
       const double last = g->last_update[cell];
       if (!std::isfinite(now[k])) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): now is not finite", k, cell);
       if (now[k] < last) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): now = %.17g lies before the cell's last update at %.17g", k, cell, now[k], last);
@@ -2661,6 +2707,18 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
     /* rs_tti_in.cqi_epoch, decided per cell as a context of its own would (rs_schedule_tti): the number, the user count, the user list
      * and the kind of report of the cell's valid image -- then the caller's block is neither checked, copied nor read */
     const int cell = cell_ids ? cell_ids[k] : k;
+    g->empty_slot[k] = que && in[k].n_users == 0;
+    if (g->empty_slot[k]) {
+      /* an update-only slot: its workgroup reads the header's cell, user count and clock and nothing behind the header */
+      g->modes[k] = 0;
+      pk.l = ctx_layout(0, b->R, b->S, b->G, false);
+      RsGroupCell h;
+      memset(&h, 0, sizeof h);
+      h.cell = cell;
+      h.now = now[k];
+      memcpy(slot, &h, sizeof h);
+      continue;
+    }
     const rs_group::CellImage& im = g->img[cell];
     const uint64_t epoch = (g->image_on && !(has_prb && g->prb_store_failed)) ? in[k].cqi_epoch : 0;
     const bool reuse_grid = epoch != 0 && im.valid && im.epoch == epoch && im.n == in[k].n_users && im.prb == has_prb &&
@@ -2674,6 +2732,22 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
       return fail(rc, "cell slot %d (cell %d): %.400s", k, cell, msg);
     }
     exact_scan |= pk.exact_scan; /* decided per call: one cell outside the FP32 filter's range, the exact scan for all (same results) */
+    if (que) {
+      /* the slot's data words: m_dataToTransmit[2] per call position, checked against the host's mirror of the cell's bearers */
+      const int32_t* const d = qdata[k];
+      const uint8_t* const has = g->has_bearer.data() + (size_t)cell * 2 * (size_t)b->U;
+      for (int i = 0; i < in[k].n_users; i++) {
+        const int id = in[k].user_id ? in[k].user_id[i] : i;
+        for (int bb = 0; bb < 2; bb++) {
+          if (d[2 * i + bb] < 0) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): data_to_transmit[%d][%d] = %d is negative", k, cell, i, bb, d[2 * i + bb]);
+          if (d[2 * i + bb] > 0 && !has[2 * id + bb])
+            return fail(RS_ERR_INVALID, "cell slot %d (cell %d): data_to_transmit[%d][%d] = %d, but user %d has no bearer of priority %d (rs_group_set_bearers)", k, cell, i, bb, d[2 * i + bb], id, bb);
+        }
+        if (d[2 * i] == 0 && d[2 * i + 1] == 0)
+          return fail(RS_ERR_INVALID, "cell slot %d (cell %d): user %d (call position %d) has no data in either bearer: the reference does not schedule such a user", k, cell, id, i);
+      }
+      memcpy(g->h_qin + (size_t)k * 2 * (size_t)b->U, d, 8 * (size_t)in[k].n_users);
+    }
     const CtxLayout& l = pk.l;
     const int nu = in[k].n_users;
     RsGroupCell h;
@@ -2691,7 +2765,7 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
     h.in_gate = (int32_t)l.gate; h.in_prb = (int32_t)l.prb;
     h.out_uinfo = (int32_t)l.uinfo; h.out_map = (int32_t)l.map; h.out_quota = (int32_t)l.quota; h.out_target = (int32_t)l.target;
     h.out_upper = (int32_t)l.upper;
-    if (res) {
+    if (res) { /* (both resident forms) */
       h.in_uid = in[k].user_id ? (int32_t)l.avg : 0; /* (l.avg lies behind the grid and the slice ids: never 0) */
       h.now = now[k];
     }
@@ -2732,6 +2806,7 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
   uint8_t* const dev_in = zc ? g->z_in : g->d_in;
   uint8_t* const dev_out = zc ? g->z_out : g->d_out;
   if (!zc) HIP_TRY(hipMemcpyAsync(g->d_in, g->h_in, (size_t)n * g->in_stride, hipMemcpyHostToDevice, st));
+  if (que && !g->z_qin) HIP_TRY(hipMemcpyAsync(g->d_qin, g->h_qin, 8 * (size_t)n * b->U, hipMemcpyHostToDevice, st));
   RsLaunch L = b->base;
   L.n_cells = n; /* call slots of this launch */
   L.n_ttis = 1;
@@ -2765,6 +2840,14 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
     L.grp_gather = g->d_rgather;
     L.grp_uid = g->d_ruid;
   }
+  if (que) {
+    L.grp_qavg = g->d_qavg;
+    L.grp_qpend = g->d_qpend;
+    L.grp_qhas = g->d_qhas;
+    L.grp_qdata = g->d_qdata;
+    L.grp_qin = g->z_qin ? g->z_qin : g->d_qin;
+    L.grp_qin_stride = 2 * (int64_t)b->U;
+  }
   bool poll = zc && g->poll;
   if (poll) {
     if (++g->seq == 0) g->seq = 1; /* (0 is the word's initial value) */
@@ -2778,9 +2861,9 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
   RsJitKernel** const pair = res ? g->rjit : g->jit;
   int* const chk_left = res ? g->rchk_left : g->chk_left;
   int* const chk_agreed = res ? g->rchk_agreed : g->chk_agreed;
-  RsJitKernel* kd = pair[0];
+  RsJitKernel* kd = que ? nullptr : pair[0]; /* (no run-time builds of the queued form: the built-in queued kernel serves it) */
   int which = 0;
-  if (pair[1] && !has_prb && !L.queue_mode && !has_gate && !L.exact_scan && !L.gen_exp && !want_upper && !L.synthetic) { kd = pair[1]; which = 1; }
+  if (!que && pair[1] && !has_prb && !L.queue_mode && !has_gate && !L.exact_scan && !L.gen_exp && !want_upper && !L.synthetic) { kd = pair[1]; which = 1; }
   /* A build without the self-check mark serves its first calls beside the built-in kernel of its kind (rs_group_jit_status,
    * rs_group_resident_jit_status): same slots, same state; every named cell's output fields and the state left behind must agree --
    * the slice state, and for a resident call the averages of every user id, the pending bytes and the last-update time. */
@@ -2824,9 +2907,11 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
     L.done_flag = nullptr; /* completion by the stream */
   }
   if (kd) HIP_TRY(rs_jit_launch(kd, &L, st));
+  else if (que) HIP_TRY(rs_launch_group_queued(&L, b->threads, st));
   else if (res) HIP_TRY(rs_launch_group_resident(&L, b->threads, st));
   else HIP_TRY(rs_launch_group(&L, b->threads, st));
   g->launches++;
+  g->last_call_kind = kind;
   g->last_call_resident = res;
   g->last_call_rjit = res && kd != nullptr;
   if (!zc) HIP_TRY(hipMemcpyAsync(g->h_out, g->d_out, (size_t)n * g->out_stride, hipMemcpyDeviceToHost, st));
@@ -2948,12 +3033,16 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
   guard.ok = true;
   if (res) /* the launch has completed: the cells' updates are dated now[k], and grants may be waiting */
     for (int k = 0; k < n; k++) {
-      g->last_update[cell_ids ? cell_ids[k] : k] = now[k];
-      g->pending_zero[cell_ids ? cell_ids[k] : k] = 0;
+      const int cell = cell_ids ? cell_ids[k] : k;
+      /* (an update-only slot credits nothing: behind an update no byte is waiting, without one nothing changed) */
+      if (!g->empty_slot[k]) g->pending_zero[cell] = 0;
+      else if (now[k] != g->last_update[cell]) g->pending_zero[cell] = 1;
+      g->last_update[cell] = now[k];
     }
   const clk::time_point t3 = g->timing ? clk::now() : clk::time_point();
   /* the launch has completed: the device holds these calls' reports now */
   for (int k = 0; k < n; k++) {
+    if (g->empty_slot[k]) continue; /* (no reports, no image moved, not counted) */
     const int mode = g->modes[k];
     rs_group::CellImage& im = g->img[cell_ids ? cell_ids[k] : k];
     if (mode == 0) { g->n_plain++; im.valid = false; continue; } /* (as a context: a call without a number ends the image's term) */
@@ -2966,7 +3055,19 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
     im.has_ids = in[k].user_id != nullptr;
     if (in[k].user_id) im.ids.assign(in[k].user_id, in[k].user_id + in[k].n_users);
   }
-  for (int k = 0; k < n; k++) unpack_tti(b, &in[k], &out[k], g->h_out + (size_t)k * g->out_stride, g->packs[k].l, want_upper);
+  for (int k = 0; k < n; k++) {
+    if (g->empty_slot[k]) { /* "nothing scheduled": the workgroup wrote no output */
+      if (out[k].rbg_to_user) for (int r = 0; r < b->R; r++) out[k].rbg_to_user[r] = -1;
+      for (int s = 0; s < b->S; s++) {
+        if (out[k].target_rbs) out[k].target_rbs[s] = 0;
+        if (out[k].quota_rbgs) out[k].quota_rbgs[s] = 0;
+      }
+      if (out[k].upper_rbg) for (int i = 0; i < b->S * b->R; i++) out[k].upper_rbg[i] = -1;
+      if (out[k].upper_user) for (int i = 0; i < b->S * b->R; i++) out[k].upper_user[i] = -1;
+      continue;
+    }
+    unpack_tti(b, &in[k], &out[k], g->h_out + (size_t)k * g->out_stride, g->packs[k].l, want_upper);
+  }
   if (g->timing) {
     const clk::time_point t4 = clk::now();
     auto us = [](clk::time_point a, clk::time_point b2) { return std::chrono::duration<double, std::micro>(b2 - a).count(); };
@@ -2984,6 +3085,23 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
 }
 }  // namespace
 
+namespace {
+/* what the two resident forms share: the cells' last-update times, the gather rows and the id rows (all three or none) */
+bool group_alloc_resident_shared(rs_group* g) {
+  if (g->d_rlast) return true;
+  const size_t nu = (size_t)g->b->U * (size_t)g->n_cells;
+  if (hipMalloc(&g->d_rgather, 8 * nu) == hipSuccess && hipMalloc(&g->d_ruid, 4 * nu) == hipSuccess &&
+      hipMalloc(&g->d_rlast, 8 * (size_t)g->n_cells) == hipSuccess)
+    return true;
+  (void)hipGetLastError();
+  for (void* q : {(void*)g->d_rgather, (void*)g->d_ruid, (void*)g->d_rlast})
+    if (q) (void)hipFree(q);
+  g->d_rgather = g->d_rlast = nullptr;
+  g->d_ruid = nullptr;
+  return false;
+}
+}  // namespace
+
 int rs_group_set_avg(rs_group* g, int32_t cell, const double* avg, double last_update) {
   if (!g || !avg) return fail(RS_ERR_INVALID, "null argument");
   if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
@@ -2996,15 +3114,13 @@ int rs_group_set_avg(rs_group* g, int32_t cell, const double* avg, double last_u
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   if (!g->d_ravg) {
     const size_t nu = U * (size_t)g->n_cells;
-    const bool ok = hipMalloc(&g->d_ravg, 8 * nu) == hipSuccess && hipMalloc(&g->d_rgather, 8 * nu) == hipSuccess &&
-                    hipMalloc(&g->d_rpend, 4 * nu) == hipSuccess && hipMalloc(&g->d_ruid, 4 * nu) == hipSuccess &&
-                    hipMalloc(&g->d_rlast, 8 * (size_t)g->n_cells) == hipSuccess;
+    const bool ok = group_alloc_resident_shared(g) && hipMalloc(&g->d_ravg, 8 * nu) == hipSuccess && hipMalloc(&g->d_rpend, 4 * nu) == hipSuccess;
     if (!ok) {
       (void)hipGetLastError();
-      for (void* q : {(void*)g->d_ravg, (void*)g->d_rgather, (void*)g->d_rpend, (void*)g->d_ruid, (void*)g->d_rlast})
+      for (void* q : {(void*)g->d_ravg, (void*)g->d_rpend})
         if (q) (void)hipFree(q);
-      g->d_ravg = g->d_rgather = g->d_rlast = nullptr;
-      g->d_rpend = g->d_ruid = nullptr;
+      g->d_ravg = nullptr;
+      g->d_rpend = nullptr;
       return fail(RS_ERR_HIP, "allocation of the group's resident averages failed (%zu bytes)", 24 * nu + 8 * (size_t)g->n_cells);
     }
   }
@@ -3022,7 +3138,7 @@ int rs_group_set_avg(rs_group* g, int32_t cell, const double* avg, double last_u
 int rs_group_get_avg(rs_group* g, int32_t cell, double* avg, int32_t* pending_bytes, double* last_update) {
   if (!g) return fail(RS_ERR_INVALID, "null group");
   if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
-  if (!g->resident[cell]) return fail(RS_ERR_STATE, "cell %d is not resident (rs_group_set_avg first)", cell);
+  if (g->resident[cell] != 1) return fail(RS_ERR_STATE, "cell %d is not resident (rs_group_set_avg first)", cell);
   rs_batch* b = g->b;
   const size_t U = (size_t)b->U;
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
@@ -3036,7 +3152,7 @@ int rs_group_get_avg(rs_group* g, int32_t cell, double* avg, int32_t* pending_by
 int rs_group_set_pending(rs_group* g, int32_t cell, const int32_t* pending_bytes) {
   if (!g || !pending_bytes) return fail(RS_ERR_INVALID, "null argument");
   if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
-  if (!g->resident[cell]) return fail(RS_ERR_STATE, "cell %d is not resident (rs_group_set_avg first)", cell);
+  if (g->resident[cell] != 1) return fail(RS_ERR_STATE, "cell %d is not resident (rs_group_set_avg first)", cell);
   rs_batch* b = g->b;
   const size_t U = (size_t)b->U;
   bool all_zero = true;
@@ -3050,6 +3166,78 @@ int rs_group_set_pending(rs_group* g, int32_t cell, const int32_t* pending_bytes
   g->pending_zero[cell] = 0; /* (until the copy is through) */
   HIP_TRY(hipMemcpy(g->d_rpend + (size_t)cell * U, pending_bytes, 4 * U, hipMemcpyHostToDevice));
   g->pending_zero[cell] = all_zero ? 1 : 0;
+  return RS_OK;
+}
+
+int rs_group_set_bearers(rs_group* g, int32_t cell, const uint8_t* has_bearer, const double* avg, double last_update) {
+  if (!g || !has_bearer || !avg) return fail(RS_ERR_INVALID, "null argument");
+  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
+  rs_batch* b = g->b;
+  const size_t U = (size_t)b->U, nb = 2 * U * (size_t)g->n_cells;
+  if (b->sched == RS_SCHED_PF)
+    return fail(RS_ERR_INVALID, "resident bearers are not served for RS_SCHED_PF: it races flows, not users, and credits the whole block to the flow");
+  if (b->sched == RS_SCHED_UPPERBOUND || b->sched == RS_SCHED_NVS_NONGREEDY)
+    return fail(RS_ERR_INVALID, "resident bearers are not served for scheduler %d: no restatement of it with queues exists to check them against", b->sched);
+  if (b->gen_exp)
+    return fail(RS_ERR_INVALID, "resident bearers need exponents in {0, 1}: the general exponents' pow() of the averages is taken on the host per call");
+  if (!std::isfinite(last_update)) return fail(RS_ERR_INVALID, "last_update is not finite");
+  for (size_t i = 0; i < 2 * U; i++)
+    if (has_bearer[i] && !(avg[i] >= 1 && avg[i] <= kBearerAvgMax)) /* (false for NaN) */
+      return fail(RS_ERR_INVALID, "avg[%zu][%zu] = %g outside 1..2^51 (an updated average is never below 1; the bound above keeps the sum of a user's two exact and inside the FP32 filter's range)", i / 2, i % 2, avg[i]);
+  HIP_TRY(hipSetDevice(b->cfg.cell.device));
+  if (!g->d_qavg) {
+    bool ok = group_alloc_resident_shared(g) && hipMalloc(&g->d_qavg, 8 * nb) == hipSuccess && hipMalloc(&g->d_qpend, 4 * nb) == hipSuccess &&
+              hipMalloc(&g->d_qdata, 4 * nb) == hipSuccess && hipMalloc(&g->d_qhas, nb) == hipSuccess &&
+              hipHostMalloc((void**)&g->h_qin, 4 * nb, hipHostMallocMapped) == hipSuccess;
+    if (ok && g->z_in) { /* (the group reads its slots in place: the data words too) */
+      void* z = nullptr;
+      if (hipHostGetDevicePointer(&z, g->h_qin, 0) == hipSuccess) g->z_qin = (int32_t*)z;
+    }
+    if (ok && !g->z_qin) ok = hipMalloc(&g->d_qin, 4 * nb) == hipSuccess;
+    if (!ok) {
+      (void)hipGetLastError();
+      for (void* q : {(void*)g->d_qavg, (void*)g->d_qpend, (void*)g->d_qdata, (void*)g->d_qhas, (void*)g->d_qin})
+        if (q) (void)hipFree(q);
+      if (g->h_qin) (void)hipHostFree(g->h_qin);
+      g->d_qavg = nullptr;
+      g->d_qpend = g->d_qdata = g->d_qin = g->h_qin = g->z_qin = nullptr;
+      g->d_qhas = nullptr;
+      return fail(RS_ERR_HIP, "allocation of the group's resident bearers failed (%zu bytes)", 25 * nb);
+    }
+    memset(g->h_qin, 0, 4 * nb);
+    g->has_bearer.assign(nb, 0);
+  }
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  g->resident[cell] = 0; /* (until all four copies are through) */
+  /* a bearer that does not exist holds zeros: rs_group_get_bearers reports them, the kernel neither reads nor writes them */
+  std::vector<double> a(2 * U);
+  std::vector<uint8_t> has(2 * U);
+  for (size_t i = 0; i < 2 * U; i++) {
+    has[i] = has_bearer[i] ? 1 : 0;
+    a[i] = has[i] ? avg[i] : 0.0;
+  }
+  HIP_TRY(hipMemcpy(g->d_qavg + (size_t)cell * 2 * U, a.data(), 16 * U, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(g->d_qpend + (size_t)cell * 2 * U, 0, 8 * U));
+  HIP_TRY(hipMemcpy(g->d_qhas + (size_t)cell * 2 * U, has.data(), 2 * U, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(g->d_rlast + cell, &last_update, 8, hipMemcpyHostToDevice));
+  memcpy(g->has_bearer.data() + (size_t)cell * 2 * U, has.data(), 2 * U);
+  g->resident[cell] = 2;
+  g->pending_zero[cell] = 1;
+  g->last_update[cell] = last_update;
+  return RS_OK;
+}
+
+int rs_group_get_bearers(rs_group* g, int32_t cell, double* avg, int32_t* pending_bytes, double* last_update) {
+  if (!g) return fail(RS_ERR_INVALID, "null group");
+  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
+  if (g->resident[cell] != 2) return fail(RS_ERR_STATE, "cell %d is not bearer-resident (rs_group_set_bearers first)", cell);
+  rs_batch* b = g->b;
+  const size_t U = (size_t)b->U;
+  HIP_TRY(hipSetDevice(b->cfg.cell.device));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  if (avg) HIP_TRY(hipMemcpy(avg, g->d_qavg + (size_t)cell * 2 * U, 16 * U, hipMemcpyDeviceToHost));
+  if (pending_bytes) HIP_TRY(hipMemcpy(pending_bytes, g->d_qpend + (size_t)cell * 2 * U, 8 * U, hipMemcpyDeviceToHost));
+  if (last_update) HIP_TRY(hipMemcpy(last_update, g->d_rlast + cell, 8, hipMemcpyDeviceToHost));
   return RS_OK;
 }
 
@@ -3085,6 +3273,7 @@ const char* rs_group_kernel_name(rs_group* g) {
   if (!g) return "";
   /* (a resident call: the group's resident builds if rs_group_specialize_resident gave it some, else the built-in resident kernel --
    * whatever serves the plain calls) */
+  if (g->last_call_kind == kGroupQueued) return g->kname_que; /* (whatever builds the group has: none of them serves a queued call) */
   if (g->last_call_resident) return g->last_call_rjit ? "rs_group_resident_kernel_jit" : g->kname_res;
   return g->jit[0] ? "rs_group_kernel_jit" : g->kname;
 }

@@ -344,6 +344,19 @@ struct RsLaunch {
    * RS_PRIO_PERIOD TTIs); a cell whose own count times n_cells is below it is behind the average and runs boosted until the next
    * look.  nullptr: off.  Zeroed by the host before every launch. */
   unsigned long long* prio_sum;
+  /* group calls, resident bearers (rs_group_schedule_tti_queued, rs_group_queued_kernel): a CELL of the group may instead keep the
+   * words of BOTH bearers of every user (MAX_BEARERS = 2, index = bearer priority) -- average, bytes credited since the last update,
+   * "the bearer exists" -- indexed [user id][bearer], one stride of 2 U apart; grp_last, grp_gather and grp_uid below serve this form
+   * too (a cell is resident in one form at a time).  grp_qin: per call SLOT, UserToSchedule::m_dataToTransmit[2] of the call's users
+   * in call order, as the host formed them -- may lie in host memory, read once; grp_qdata: per cell, the workgroup's copy of them for
+   * the credit behind the body.  Read by the queued kernels alone; null in every other launch.  (Six words in front of the group
+   * fields, whose places relative to one another and to the end of the block are pinned.) */
+  double* grp_qavg;          /* [group cells][U][2] */
+  int32_t* grp_qpend;        /* [group cells][U][2] */
+  const uint8_t* grp_qhas;   /* [group cells][U][2] */
+  int32_t* grp_qdata;        /* [group cells][U][2], call order */
+  const int32_t* grp_qin;    /* [call slots][grp_qin_stride], call order */
+  int64_t grp_qin_stride;    /* words per slot: 2 U of the config */
   /* group calls (rs_group_schedule_tti, rs_group_kernel in rs_kernels.hip): one workgroup per call slot.  Slot k of the input block
    * starts with an RsGroupCell header, the cell's inputs follow at RS_GROUP_HDR_BYTES in the layout of a single call; slot k of the
    * output block holds its outputs.  n_cells is the number of slots of the launch.  The fields above that a single call passes as

@@ -778,7 +778,7 @@ template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
   constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
-  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false;
+  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = false;
 #include "rs_phase_group.inc"
 }
 
@@ -789,7 +789,19 @@ template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_resident_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
   constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
-  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = true;
+  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = true, kGrpQue = false;
+#include "rs_phase_group.inc"
+}
+
+/* ... and its queued form (rs_group_schedule_tti_queued): both bearers of every user stay on the device -- averages, pending bytes,
+ * existence --, the call brings m_dataToTransmit per bearer, and a slot without users does the update alone.  Kernels of their own
+ * for the schedulers the oracle restates with queues and a per-user credit (rs_launch_group_queued): 7, 8, 9, 101, 103.  No run-time
+ * builds of this form. */
+template <int SCHED, int EPT>
+__global__ void __launch_bounds__(512, 4) rs_group_queued_kernel(RsLaunch p) {
+  extern __shared__ __align__(16) unsigned char lds[];
+  constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
+  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = true;
 #include "rs_phase_group.inc"
 }
 #else
@@ -833,7 +845,7 @@ extern "C" __global__ void __launch_bounds__(RS_JIT_NT, RS_JIT_WPE) RS_GROUP_JIT
   constexpr RsCarve kCv = rs_carve(RS_JIT_S, RS_JIT_U, RS_JIT_R, RS_JIT_SCHED, RS_JIT_NT, RS_JIT_CARVEQ, RS_JIT_WIN);
   __shared__ __align__(16) unsigned char lds[kCv.lds_bytes];
   constexpr int kGrpSched = RS_JIT_SCHED, kGrpEpt = (RS_JIT_SCHED != 9 && RS_JIT_SCHED != 10) ? 0 : (kCv.ept <= 4 ? kCv.ept : 0);
-  constexpr bool kGrpFixed = true, kGrpRes = RS_JIT_GROUP_RESIDENT != 0;
+  constexpr bool kGrpFixed = true, kGrpRes = RS_JIT_GROUP_RESIDENT != 0, kGrpQue = false;
 #include "rs_phase_group.inc"
 }
 #undef RS_GROUP_JIT_ENTRY
@@ -1057,6 +1069,31 @@ extern "C" hipError_t rs_launch_group_resident(const RsLaunch* p, int threads, h
   return hipGetLastError();
 }
 
+/* a queued group call (rs_group_schedule_tti_queued): the same grid, the kernels that keep the cells' bearers on the device */
+extern "C" hipError_t rs_launch_group_queued(const RsLaunch* p, int threads, hipStream_t stream) {
+  dim3 grid(p->n_cells), block(threads);
+  const int ept = (p->R * p->S + threads - 1) / threads;
+  if (!p->grp_qavg || !p->grp_qpend || !p->grp_qhas || !p->grp_qdata || !p->grp_qin || !p->grp_last || !p->grp_gather || !p->grp_uid)
+    return hipErrorInvalidValue;
+#define RS_LAUNCH_GROUP(SCHED_, EPT_) hipLaunchKernelGGL((rs_group_queued_kernel<SCHED_, EPT_>), grid, block, p->lds_bytes, stream, *p)
+  switch (p->sched) {
+    case 7: RS_LAUNCH_GROUP(7, 0); break;
+    case 8: RS_LAUNCH_GROUP(8, 0); break;
+    case 101: RS_LAUNCH_GROUP(101, 0); break;
+    case 103: RS_LAUNCH_GROUP(103, 0); break;
+    case 9:
+      if (ept <= 1) RS_LAUNCH_GROUP(9, 1);
+      else if (ept <= 2) RS_LAUNCH_GROUP(9, 2);
+      else if (ept <= 3) RS_LAUNCH_GROUP(9, 3);
+      else if (ept <= 4) RS_LAUNCH_GROUP(9, 4);
+      else RS_LAUNCH_GROUP(9, 0);
+      break;
+    default: return hipErrorInvalidValue;
+  }
+#undef RS_LAUNCH_GROUP
+  return hipGetLastError();
+}
+
 extern "C" hipError_t rs_prepare_kernels(int max_lds_bytes) {
 #define RS_BOTH(SCHED_, EPT_) (const void*)rs_cell_kernel<SCHED_, EPT_, false>, (const void*)rs_cell_kernel<SCHED_, EPT_, true>
   const void* fns[] = {RS_BOTH(1, 0),  RS_BOTH(7, 0),  RS_BOTH(8, 0),  RS_BOTH(101, 0), RS_BOTH(103, 0), RS_BOTH(11, 0),
@@ -1078,7 +1115,12 @@ extern "C" hipError_t rs_prepare_kernels(int max_lds_bytes) {
                        (const void*)rs_group_resident_kernel<10, 2>, (const void*)rs_group_resident_kernel<10, 3>,
                        (const void*)rs_group_resident_kernel<10, 4>, (const void*)rs_group_resident_kernel<9, 0>,
                        (const void*)rs_group_resident_kernel<9, 1>,  (const void*)rs_group_resident_kernel<9, 2>,
-                       (const void*)rs_group_resident_kernel<9, 3>,  (const void*)rs_group_resident_kernel<9, 4>};
+                       (const void*)rs_group_resident_kernel<9, 3>,  (const void*)rs_group_resident_kernel<9, 4>,
+                       (const void*)rs_group_queued_kernel<7, 0>,   (const void*)rs_group_queued_kernel<8, 0>,
+                       (const void*)rs_group_queued_kernel<101, 0>, (const void*)rs_group_queued_kernel<103, 0>,
+                       (const void*)rs_group_queued_kernel<9, 0>,   (const void*)rs_group_queued_kernel<9, 1>,
+                       (const void*)rs_group_queued_kernel<9, 2>,   (const void*)rs_group_queued_kernel<9, 3>,
+                       (const void*)rs_group_queued_kernel<9, 4>};
 #undef RS_BOTH
 
   for (const void* f : fns) {

@@ -21,7 +21,14 @@
  * served user's grant -- which the one-TTI body leaves per call position in LDS (s_tx, rs_phase_p5.inc) -- to the user's pending
  * bytes.  A compile-time constant for the reason above: with kGrpRes false none of this text reaches the other instantiations.  Under
  * kGrpFixed the resident text's shape is constant as well: the update's range and the stores' stride are RS_JIT_U, the loop strides
- * RS_JIT_NT, the grants' LDS offset the constexpr carve's off_tx.  Order of operations and arithmetic are the same in both forms. */
+ * RS_JIT_NT, the grants' LDS offset the constexpr carve's off_tx.  Order of operations and arithmetic are the same in both forms.
+ *
+ * A sixth constant, kGrpQue, makes the queued form (rs_group_schedule_tti_queued, rs_group_queued_kernel; never with kGrpRes or
+ * kGrpFixed: the library's built-in kernels only): the cell keeps BOTH bearers of every user -- average, pending bytes, existence --
+ * and the slot brings m_dataToTransmit[2] per call position.  The update strides over the 2 U bearers, the call's averages are the
+ * sums over the bearers with data, the grant is split over the bearers from the highest priority down (DoStopSchedule), and a slot
+ * without users (U = 0 in its header) does the update alone: the body and the credit are skipped, uniformly for the workgroup.  With
+ * kGrpQue false none of this text reaches the other instantiations. */
   const uint8_t* const in = p.grp_in + (size_t)blockIdx.x * (size_t)p.grp_in_stride;
   uint8_t* const out = p.grp_out + (size_t)blockIdx.x * (size_t)p.grp_out_stride;
   const RsGroupCell* const h = (const RsGroupCell*)in;
@@ -127,11 +134,98 @@
     grp_res_cycles = __builtin_readcyclecounter() - grp_res_entry;
 #endif
   }
+  if constexpr (kGrpQue) {
+    /* (built-in kernels only: shape and carve are the launch block's) */
+    const int nthreads = (int)blockDim.x;
+    const int n_all = p.U; /* the config's users: 2 n_all bearers, the stores' stride and the update's range */
+    double* const b_avg = p.grp_qavg + (size_t)cell * 2 * (size_t)n_all;
+    int32_t* const b_pend = p.grp_qpend + (size_t)cell * 2 * (size_t)n_all;
+    const uint8_t* const b_has = p.grp_qhas + (size_t)cell * 2 * (size_t)n_all;
+    auto dword = [&](const double* d) { return __hiloint2double(word((const int32_t*)d + 1), word((const int32_t*)d)); };
+    const double now = dword(&h->now);
+    const double last = dword(p.grp_last + cell);
+    /* 1. the update, for every EXISTING bearer of every user id of the cell (a bearer that does not exist is neither read nor
+     *    written); operations, wrap-around product and order of the resident form's step 1 */
+    if (!(now == last)) {
+      const double dt = now - last;
+      for (int j = threadIdx.x; j < 2 * n_all; j += nthreads) {
+        if (b_has[j] == 0) continue;
+        double a = b_avg[j];
+        const int txb = b_pend[j];
+        double rate = (double)(int32_t)((uint32_t)txb * 8u) / dt;
+        const double beta = 0.02;
+        a = ((1 - beta) * a) + (beta * rate);
+        if (a < 1) a = 1;
+        b_avg[j] = a;
+        b_pend[j] = 0;
+      }
+    }
+    /* the one barrier of this form, as the resident form's: every thread has read the last-update word, and behind it a thread reads
+     * averages that other threads wrote */
+    __syncthreads();
+    if (threadIdx.x == 0 && !(now == last)) p.grp_last[cell] = now;
+    /* 2. the call's averages: per call position the sum over the bearers WITH DATA (the reference sums the bearers it inserted,
+     *    ComputeSchedulingMetric :681-687) in the form whose 1 + x the body takes: a[b] alone, or ((1 + a0) + a1) - 1 -- exact while
+     *    the sum stays below 2^53 (rs_group_set_bearers bounds the averages).  The slot's data words go to the cell's device row for
+     *    step 4.  Thread i writes entry i of the three rows and is the thread that reads it (the body's load phase: same stride).
+     *    q.U == 0, an update-only slot: nothing to gather, and the body is skipped below. */
+    if (q.U != 0) {
+      const int in_uid = word(&h->in_uid);
+      const int32_t* const uid = (const int32_t*)(data + in_uid);
+      const int32_t* const din = p.grp_qin + (size_t)blockIdx.x * (size_t)p.grp_qin_stride;
+      double* const row = p.grp_gather + (size_t)cell * (size_t)n_all;
+      int32_t* const ids = p.grp_uid + (size_t)cell * (size_t)n_all;
+      int32_t* const keep = p.grp_qdata + (size_t)cell * 2 * (size_t)n_all;
+      for (int i = threadIdx.x; i < q.U; i += nthreads) {
+        const int id = in_uid != 0 ? uid[i] : i;
+        const int d0 = din[2 * i], d1 = din[2 * i + 1];
+        double v;
+        if (d0 > 0 && d1 > 0) v = ((1 + b_avg[2 * id]) + b_avg[2 * id + 1]) - 1;
+        else v = b_avg[2 * id + (d0 > 0 ? 0 : 1)]; /* (the host has checked: one of the two has data, and that bearer exists) */
+        row[i] = v;
+        ids[i] = id;
+        keep[2 * i] = d0;
+        keep[2 * i + 1] = d1;
+      }
+      q.avg = row;
+    }
+  }
   if constexpr (kGrpLean) { /* the plain call (rs_group_kernel_jit): no customised slices -- the slots' HoL delays and priority flags are not read */
     q.hol = nullptr;
     q.prio = nullptr;
   }
-  rs_cell_body<kGrpSched, kGrpEpt, kGrpFixed, true, false, true>(q, lds);
+  if constexpr (kGrpQue) {
+    /* (q.U is one word of the slot header: the skip is uniform for the whole workgroup, no barrier of the body is left half met) */
+    if (q.U != 0) rs_cell_body<kGrpSched, kGrpEpt, kGrpFixed, true, false, true>(q, lds);
+  } else {
+    rs_cell_body<kGrpSched, kGrpEpt, kGrpFixed, true, false, true>(q, lds);
+  }
+  if constexpr (kGrpQue) {
+    /* 4. DoStopSchedule's loop (ref: downlink-transport-scheduler.cpp:170-221): the grant of a call position -- from LDS, as the
+     *    resident form's -- goes to the user's bearers from the highest priority down, min(available, dataToTransmit) each */
+    if (q.U != 0) {
+      const int nthreads = (int)blockDim.x;
+      const int n_all = p.U;
+      const int32_t* const granted = (const int32_t*)(lds + p.off_tx);
+      int32_t* const b_pend = p.grp_qpend + (size_t)cell * 2 * (size_t)n_all;
+      const int32_t* const ids = p.grp_uid + (size_t)cell * (size_t)n_all;    /* entry i: written by this thread before the body */
+      const int32_t* const keep = p.grp_qdata + (size_t)cell * 2 * (size_t)n_all; /* entries 2i, 2i + 1: likewise */
+      for (int i = threadIdx.x; i < q.U; i += nthreads) {
+        int available = granted[i];
+        if (available <= 0) continue;
+        const int id = ids[i];
+        for (int b = 1; b >= 0; --b) {
+          if (available <= 0) break;
+          const int d = keep[2 * i + b];
+          if (d > 0) {
+            const int sent = available < d ? available : d;
+            available -= sent;
+            b_pend[2 * id + b] += sent;
+          }
+        }
+      }
+    }
+  }
   if constexpr (kGrpRes) {
     /* 3. the grants (DoStopSchedule: min(tbs_bits / 8, 100000000) bytes, rs_phase_p5.inc) from LDS, where the body's closing barrier
      *    left them for every thread -- not from the slot's output rows, which lie in host memory in the zero-copy mode.  A user is

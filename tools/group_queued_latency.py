@@ -1,0 +1,70 @@
+#!/usr/bin/env python3
+"""us per group call with resident bearers (rs_group_schedule_tti_queued) against what a finite-queue binding had before -- a resident
+call followed by rs_group_set_pending per cell -- and, as the regression check, the plain and the resident call, which another
+checkout can be measured on as well (profiles/group_queued.md).
+
+    python tools/group_queued_latency.py [--variant plain|resident|resident+pending|queued|all] [--calls 300]
+    RS_TREE=<another checkout> python tools/group_queued_latency.py --variant plain     # that tree's package
+
+Workloads: 8 and 64 cells; 500 users x 25 RBGs and 100 users x 64 RBGs; scheduler 9; cqi_epoch on (new reports every 40 calls).
+Timed through the Python layer, marshalling included, like tools/group_resident_latency.py: three repetitions per line, whose
+spread is the yardstick for a difference between lines."""
+import argparse
+import os
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+sys.path.insert(0, os.environ.get("RS_TREE", str(Path(__file__).resolve().parents[1])))
+import radiosaber_amd as rs  # noqa: E402
+
+VARIANTS = ("plain", "resident", "resident+pending", "queued")
+ap = argparse.ArgumentParser()
+ap.add_argument("--variant", default="all", choices=VARIANTS + ("all",))
+ap.add_argument("--calls", type=int, default=300)
+ap.add_argument("--warmup", type=int, default=40)
+args = ap.parse_args()
+
+for ues, R, G in ((5, 64, 8), (25, 25, 4)):
+    for K in (8, 64):
+        sc = rs.SliceConfig([ues] * 20, weight=[0.05] * 20)
+        U = 20 * ues
+        for variant in (VARIANTS if args.variant == "all" else (args.variant,)):
+            g = rs.GroupScheduler(sc, R, G, K, sched=9)
+            rng = np.random.default_rng(1)
+            cqi = [rng.integers(1, 16, (U, R)).astype(np.uint8) for _ in range(K)]
+            avg = [rng.uniform(1e4, 1e6, U) for _ in range(K)]
+            pending = np.full(U, 300, np.int32)
+            data = np.tile(np.array([100000000, 300], np.int32), (U, 1))
+            for k in range(K):
+                if variant in ("resident", "resident+pending"):
+                    g.set_avg(k, avg[k], 0.1)
+                if variant == "queued":
+                    g.set_bearers(k, np.ones((U, 2), bool), np.stack([avg[k], avg[k][::-1]], axis=1), 0.1)
+            now, best = 0.1, []
+            for rep in range(3):
+                t0 = 0.0
+                for i in range(args.warmup + args.calls):
+                    if i == args.warmup:
+                        t0 = time.perf_counter()
+                    now += 0.001
+                    calls = [dict(cqi=cqi[k], rand0=123 + i, rand1=456 + i, cqi_epoch=1 + i // 40) for k in range(K)]
+                    if variant == "plain":
+                        for k in range(K):
+                            calls[k]["avg_rate"] = avg[k]
+                        g.schedule_tti(calls)
+                    elif variant == "queued":
+                        for k in range(K):
+                            calls[k]["data_to_transmit"] = data
+                        g.schedule_tti_queued(calls, now)
+                    else:
+                        g.schedule_tti_at(calls, now)
+                        if variant == "resident+pending":
+                            for k in range(K):
+                                g.set_pending(k, pending)
+                best.append((time.perf_counter() - t0) / args.calls * 1e6)
+            print(f"{K:3d} cells x {U} UEs x {R} RBGs, {variant:16s}: " + " / ".join(f"{b:.1f}" for b in best) + f" us per call (python), {g.kernel_name}",
+                  flush=True)
+            g.close()
