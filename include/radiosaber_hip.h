@@ -31,7 +31,8 @@ extern "C" {
                                rs_group_specialize / rs_group_jit_status / rs_jit_selfcheck_group (a group's own self-checked builds of the one-TTI kernel),
                                rs_group_set_avg / rs_group_get_avg / rs_group_set_pending / rs_group_schedule_tti_at (a group cell's PF averages resident on the device),
                                rs_group_specialize_resident / rs_group_resident_jit_status / rs_jit_selfcheck_group_resident (a group's own builds of the resident kernel, self-checked on state),
-                               rs_group_set_bearers / rs_group_get_bearers / rs_group_schedule_tti_queued (a group cell's two bearers per user resident on the device: finite queues credited there);
+                               rs_group_set_bearers / rs_group_get_bearers / rs_group_schedule_tti_queued (a group cell's two bearers per user resident on the device: finite queues credited there),
+                               rs_group_specialize_queued / rs_group_queued_jit_status / rs_jit_selfcheck_group_queued (a group's own builds of the queued kernel, self-checked on the bearer stores);
                                rs_config.link_tables (RS_LINK_*) + rs_link_tables_pinned / rs_link_tables_compare, rs_tti_in.cqi_epoch (the context keeps the
                                CQI image of an unchanged report set on the device), rs_ctx_jit_status (a specialised context checks its run-time build against the
                                built-in kernel during its first calls), rs_batch_config.selfcheck -1 / 0 / 1 with run-time builds verified by default and the
@@ -313,7 +314,9 @@ int64_t rs_group_launch_count(const rs_group* g);
 int rs_group_image_stats(const rs_group* g, int64_t out[3]);
 /* "rs_group_kernel_jit" while the group's own builds serve its calls; the built-in instantiation's name before rs_group_specialize and
  * after a build was dropped.  While the last call was a resident one: "rs_group_resident_kernel_jit" if the group's resident builds
- * served it (rs_group_specialize_resident), else the built-in "rs_group_resident_kernel<sched, ept>". */
+ * served it (rs_group_specialize_resident), else the built-in "rs_group_resident_kernel<sched, ept>".  While it was a queued one:
+ * "rs_group_queued_kernel_jit" if the group's queued builds served it (rs_group_specialize_queued), else the built-in
+ * "rs_group_queued_kernel<sched, ept>". */
 const char* rs_group_kernel_name(rs_group* g);
 /* Optional, at any time between two calls: rs_ctx_specialize for a group -- the one-TTI kernel compiled for the config's slices, RBGs,
  * PRBs per RBG, scheduler, workgroup size and user capacity (hiprtc, ~2 s per build and process, cached on disk apart from the
@@ -424,7 +427,8 @@ int rs_jit_selfcheck_group_resident(int n_slices, int n_users, int n_rbgs, int r
  * scheduled" (rbg_to_user -1, target_rbs / quota_rbgs 0; out[k]'s arrays may be NULL).  A call whose slots are all update-only
  * still launches once.  RS_SCHED_NVS: the caller chooses the served slice, and an update-only slot moves no slice state.
  * Queued calls run the built-in "rs_group_queued_kernel<sched, ept>" (rs_group_kernel_name while a queued call is the last one
- * served); rs_group_specialize and rs_group_specialize_resident do not reach them: same results before and after either. */
+ * served); rs_group_specialize and rs_group_specialize_resident do not reach them: same results before and after either.  A group
+ * that wants run-time builds of this form opts in with rs_group_specialize_queued below. */
 /* Makes `cell` bearer-resident (again, at any time between two calls; a cell is average-resident or bearer-resident, the later of
  * rs_group_set_avg / rs_group_set_bearers wins): has_bearer[U][2] and avg[U][2] by user id and bearer priority, zero pending bytes.
  * A user may have no bearer at all; avg of a bearer that does not exist is not read.  RS_ERR_INVALID: RS_SCHED_PF (it races flows
@@ -450,6 +454,34 @@ int rs_group_get_bearers(rs_group* g, int32_t cell, double* avg /* [U][2] or NUL
  * A call that fails with RS_ERR_HIP leaves the cells it named not resident. */
 int rs_group_schedule_tti_queued(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in /* [n] */, rs_tti_out* out /* [n] */,
                                  const double* now /* [n] */, const int32_t* const* data_to_transmit /* [n]: [in[k].n_users][2] */);
+/* Optional, at any time between two calls, with or without rs_group_specialize and rs_group_specialize_resident: rs_group_specialize for
+ * the QUEUED call -- the queued kernel compiled for the group's shape (entry point rs_group_queued_kernel_jit, cache files of its own), a
+ * general and a lean build; rs_group_schedule_tti_queued picks the lean one under the plain call's per-launch condition, taken among the
+ * slots that have users (no per-PRB reports, no customised slices, no gate, no exact scan, no synthetic-experiment blocks;
+ * RS_JIT_LEAN=0: the general build only).  A call made of update-only slots only has no such inputs: it runs the lean build, unless the
+ * config itself rules that build out (customised slices, synthetic-experiment blocks); either build does the same update.  The other
+ * two call forms are not affected.  Cell state, CQI images and the bearer stores are not touched.  RS_OK; a second call is a no-op;
+ * RS_ERR_HIP if a build fails, the group left on the built-in queued kernel; RS_ERR_STATE (with the reason) once the queued builds were
+ * dropped; RS_ERR_INVALID for a scheduler without a queued form (RS_SCHED_PF, RS_SCHED_UPPERBOUND).
+ * The check follows rs_group_specialize_resident's policy and switches (RS_DROPIN_SELFCHECK_CALLS, RS_JIT_SELFCHECK, the mark in the
+ * cache file): before a checked call the slice state, the cell scalars and the bearer stores (averages, pending bytes, last_update) are
+ * kept; the built-in queued kernel runs into twin output slots; what it left is kept and the earlier state put back; then the group's
+ * build runs, with completion by the stream.  For every named cell the rs_tti_out fields, the slice state, avg[U][2] and
+ * pending_bytes[U][2] of EVERY user id of the config and last_update must agree bit for bit; an update-only slot is compared on state
+ * alone, and a call made only of such slots is a checked call like any other.  One difference drops the queued pair and unlinks its
+ * cache files -- the plain and the resident pair are independent and stay, and the reverse holds too --; that call returns the built-in
+ * kernel's outputs and leaves its state, bearer stores included; later queued calls run the built-in queued kernel; the message names
+ * cell, field and index ("cell 1: pending_bytes[7][0] = 301, the built-in kernel's 300").  rs_group_launch_count counts a checked call
+ * once. */
+int rs_group_specialize_queued(rs_group* g);
+/* rs_group_jit_status for the queued pair: 1 = the group's queued builds serve the queued calls, 0 = rs_group_specialize_queued was not
+ * called, -1 = it failed to build, -2 = the builds were dropped by the check.  rs_group_jit_status and rs_group_resident_jit_status keep
+ * reporting their own pair only. */
+int rs_group_queued_jit_status(rs_group* g, char* msg, size_t msglen);
+/* build check without a GPU: do the general and the lean queued build of a group of this shape compile?  (the larger code size, or a
+ * negative value with the compiler's log in err; negative for the schedulers without a queued form: RS_SCHED_PF, RS_SCHED_UPPERBOUND,
+ * RS_SCHED_NVS_NONGREEDY) */
+int rs_jit_selfcheck_group_queued(int n_slices, int n_users, int n_rbgs, int rbg_size, int threads, int sched, char* err, size_t errlen);
 
 /* ------------------------------------------------------------------------------------------
  * Batched mode: many independent cells resident on the device, whole DoSchedule() loops

@@ -113,6 +113,7 @@ ABI_SYMBOLS = [
     "rs_group_set_avg", "rs_group_get_avg", "rs_group_set_pending", "rs_group_schedule_tti_at",
     "rs_group_specialize_resident", "rs_group_resident_jit_status", "rs_jit_selfcheck_group_resident",
     "rs_group_set_bearers", "rs_group_get_bearers", "rs_group_schedule_tti_queued",
+    "rs_group_specialize_queued", "rs_group_queued_jit_status", "rs_jit_selfcheck_group_queued",
 ]
 
 _lib = None
@@ -167,6 +168,9 @@ def lib():
     L.rs_group_specialize_resident.argtypes = [C.c_void_p]
     L.rs_group_resident_jit_status.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.rs_jit_selfcheck_group_resident.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
+    L.rs_group_specialize_queued.argtypes = [C.c_void_p]
+    L.rs_group_queued_jit_status.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    L.rs_jit_selfcheck_group_queued.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
     L.rs_batch_create.restype = C.c_void_p
     L.rs_batch_create.argtypes = [C.POINTER(_BatchConfig)]
     L.rs_create_checked.restype = C.c_void_p
@@ -262,19 +266,21 @@ def _p(a, t):
 
 
 def jit_selfcheck(n_slices, n_users, n_rbgs, rbg_size, threads=512, sched=RS_SCHED_MAXCELL, queues=False, untuned=False, dropin=False,
-                  group=False, resident=False):
+                  group=False, resident=False, queued=False):
     """Compile the shape-specialised kernel for one shape (hiprtc, no GPU needed); returns the code size.  queues=True: the
     queue-model kernel of the shape.  untuned=True: without the -mllvm tuning options (the library's fallback build).
     group=True: the general and the lean build of a group of this shape (rs_group_specialize); the larger code size.
-    group=True, resident=True: the two builds of the group's resident kernel (rs_group_specialize_resident)."""
-    if resident and not group:
-        raise ValueError("resident=True needs group=True: only a group has a resident kernel")
+    group=True, resident=True: the two builds of the group's resident kernel (rs_group_specialize_resident).
+    group=True, queued=True: the two builds of the group's queued kernel (rs_group_specialize_queued; schedulers 7, 8, 9, 101, 103)."""
+    _jit_flags(False, False, group, resident, queued)
     buf = C.create_string_buffer(4096)
     fn = lib().rs_jit_selfcheck_queue if queues else (lib().rs_jit_selfcheck_untuned if untuned else lib().rs_jit_selfcheck)
     if dropin:  # the drop-in entry point's one-TTI kernel of a context of this shape (rs_ctx_specialize)
         fn = lib().rs_jit_selfcheck_dropin
     if group:
         fn = lib().rs_jit_selfcheck_group_resident if resident else lib().rs_jit_selfcheck_group
+        if queued:
+            fn = lib().rs_jit_selfcheck_group_queued
     n = fn(n_slices, n_users, n_rbgs, rbg_size, threads, sched, buf, 4096)
     if n < 0:
         raise RadioSaberError(n, buf.value.decode(errors="replace"))
@@ -288,28 +294,33 @@ def jit_cache_stats():
     return dict(zip(("hits", "misses", "stores", "rejected"), (int(x) for x in out)))
 
 
-def _jit_flags(lean, streamed, group, resident):
+def _jit_flags(lean, streamed, group, resident, queued=False):
     if resident and not group:
         raise ValueError("resident=True needs group=True: only a group has a resident kernel")
-    return (4 if lean else 0) | (2 if streamed else 0) | (8 if group else 0) | (16 if resident else 0)
+    if queued and not group:
+        raise ValueError("queued=True needs group=True: only a group has a queued kernel")
+    if queued and resident:
+        raise ValueError("resident=True and queued=True exclude each other: two forms of a group's kernel")
+    return (4 if lean else 0) | (2 if streamed else 0) | (8 if group else 0) | (16 if resident else 0) | (32 if queued else 0)
 
 
 def jit_cache_file(n_slices, n_users, n_rbgs, rbg_size, threads=512, sched=RS_SCHED_MAXCELL, lean=False, streamed=False, group=False,
-                   resident=False):
+                   resident=False, queued=False):
     """Path of the cache file the batch kernel of this shape lives in ('' when no cache directory can be named).  group=True: a
-    group's build of the one-TTI kernel (flag bit of value 8); with resident=True its resident form (value 16)."""
+    group's build of the one-TTI kernel (flag bit of value 8); with resident=True its resident form (value 16), with queued=True its
+    queued form (value 32)."""
     buf = C.create_string_buffer(4096)
-    lib().rs_jit_cache_file(n_slices, n_users, n_rbgs, rbg_size, threads, sched, _jit_flags(lean, streamed, group, resident),
+    lib().rs_jit_cache_file(n_slices, n_users, n_rbgs, rbg_size, threads, sched, _jit_flags(lean, streamed, group, resident, queued),
                             buf, 4096)
     return buf.value.decode()
 
 
 def jit_cache_warm(n_slices, n_users, n_rbgs, rbg_size, threads=512, sched=RS_SCHED_MAXCELL, lean=False, streamed=False, group=False,
-                   resident=False):
+                   resident=False, queued=False):
     """Compile (or load) the batch kernel of this shape through the disk cache; no GPU needed.  Returns the code size.
-    group=True: a group's build of the one-TTI kernel; with resident=True its resident form."""
+    group=True: a group's build of the one-TTI kernel; with resident=True its resident form, with queued=True its queued form."""
     buf = C.create_string_buffer(4096)
-    n = lib().rs_jit_cache_warm(n_slices, n_users, n_rbgs, rbg_size, threads, sched, _jit_flags(lean, streamed, group, resident),
+    n = lib().rs_jit_cache_warm(n_slices, n_users, n_rbgs, rbg_size, threads, sched, _jit_flags(lean, streamed, group, resident, queued),
                                 buf, 4096)
     if n < 0:
         raise RadioSaberError(n, buf.value.decode(errors="replace"))
@@ -635,8 +646,9 @@ class GroupScheduler:
 
     def __init__(self, slices: SliceConfig, n_rbgs: int, rbg_size: int, n_cells: int, sched: int = RS_SCHED_MAXCELL,
                  device: int = 0, stream: Optional[int] = None, synthetic_exp: bool = False, link_tables: int = RS_LINK_DEFAULT,
-                 jit: bool = False, jit_resident: bool = False):
-        """jit: specialize() right after the group is created.  jit_resident: specialize_resident() as well (independent of jit)."""
+                 jit: bool = False, jit_resident: bool = False, jit_queued: bool = False):
+        """jit: specialize() right after the group is created.  jit_resident: specialize_resident() as well (independent of jit).
+        jit_queued: specialize_queued() as well (independent of both)."""
         self.slices, self.R, self.rbg_size, self.sched, self.n_cells = slices, n_rbgs, rbg_size, sched, n_cells
         self._cfg = _CfgHolder(slices, n_rbgs, rbg_size, sched, device, stream, synthetic_exp, link_tables)
         self._h = lib().rs_group_create_checked(C.byref(self._cfg.c), n_cells, RS_ABI_VERSION, C.sizeof(_Config))
@@ -646,6 +658,8 @@ class GroupScheduler:
             self.specialize()
         if jit_resident:
             self.specialize_resident()
+        if jit_queued:
+            self.specialize_queued()
 
     def specialize(self):
         """rs_group_specialize: the group's own hiprtc builds of the one-TTI kernel (identical results; their first calls run beside
@@ -670,6 +684,20 @@ class GroupScheduler:
         for, -1 build failed, -2 dropped by the self-check."""
         buf = C.create_string_buffer(768)
         rc = lib().rs_group_resident_jit_status(self._h, buf, 768)
+        return rc, buf.value.decode(errors="replace")
+
+    def specialize_queued(self):
+        """rs_group_specialize_queued: the group's own hiprtc builds of the QUEUED kernel, for schedule_tti_queued (identical results;
+        their first calls run beside the built-in queued kernel and are compared on outputs and on state -- slice state, both bearers'
+        averages and pending bytes of every user, last update -- unless the builds carry the self-check mark: queued_jit_status()).
+        Independent of specialize() and specialize_resident(); any time between two calls; again: a no-op."""
+        _check(lib().rs_group_specialize_queued(self._h))
+
+    def queued_jit_status(self):
+        """(code, message) of rs_group_queued_jit_status, for the queued builds alone: 1 they serve the queued calls, 0 not asked for,
+        -1 build failed, -2 dropped by the self-check."""
+        buf = C.create_string_buffer(768)
+        rc = lib().rs_group_queued_jit_status(self._h, buf, 768)
         return rc, buf.value.decode(errors="replace")
 
     def close(self):

@@ -34,7 +34,8 @@ struct RsJitKernel;
 extern "C" RsJitKernel* rs_jit_get(int device, int S, int U, int R, int G, int NT, int sched, int qmode, int win, char* err, size_t errlen,
                                    int flags, /* bit 0: drop-in (one-TTI) kernel, bit 1: streamed batch (cqi_refresh <= 4), bit 2: lean build,
                                                 * bit 3: a group's build of the one-TTI kernel (rs_group_kernel_jit), bit 4 (with bit 3): its
-                                                * resident form (rs_group_resident_kernel_jit) */
+                                                * resident form (rs_group_resident_kernel_jit), bit 5 (with bit 3, never with bit 4): its
+                                                * queued form (rs_group_queued_kernel_jit) */
                                    const char* variant = nullptr); /* an autotune candidate: extra -D options and / or "ss=<LLVM scheduler strategy>" */
 extern "C" int rs_jit_is_untuned(const RsJitKernel* k);
 extern "C" int rs_jit_is_verified(const RsJitKernel* k);  /* carries the self-check mark (this process, or its cache file) */
@@ -2464,6 +2465,14 @@ struct rs_group {
   std::vector<uint8_t> has_bearer, empty_slot; /* empty_slot: per call slot, n_users == 0 (an update-only slot of a queued call) */
   int last_call_kind = 0; /* 0 plain, 1 resident, 2 queued */
   char kname_que[56] = "";
+  /* rs_group_specialize_queued: the group's own builds of the QUEUED form, a third pair beside jit[] and rjit[] with the same scheme.
+   * Its check compares the bearer stores: d_qchk holds them before the built-in queued kernel ran and as that kernel left them (two
+   * halves, group_qchk_half). */
+  RsJitKernel* qjit[2] = {nullptr, nullptr};
+  bool qjit_wanted = false, qjit_dropped = false, last_call_qjit = false;
+  int qchk_left[2] = {0, 0}, qchk_agreed[2] = {0, 0};
+  uint8_t* d_qchk = nullptr;
+  char qjit_msg[512] = "";
 };
 
 namespace {
@@ -2474,6 +2483,9 @@ size_t group_chk_half(const rs_group* g) { return group_chk_sstate(g) + round_up
 size_t group_rchk_avg(const rs_group* g) { return round_up((int)(8 * (size_t)g->b->U * g->n_cells), 256); }
 size_t group_rchk_last(const rs_group* g) { return round_up((int)(8 * (size_t)g->n_cells), 256); }
 size_t group_rchk_half(const rs_group* g) { return group_rchk_avg(g) + group_rchk_last(g) + round_up((int)(4 * (size_t)g->b->U * g->n_cells), 256); }
+/* bytes of one half of rs_group::d_qchk: [n_cells][U][2] averages, then [n_cells] last-update times, then [n_cells][U][2] pending bytes */
+size_t group_qchk_avg(const rs_group* g) { return round_up((int)(16 * (size_t)g->b->U * g->n_cells), 256); }
+size_t group_qchk_half(const rs_group* g) { return group_qchk_avg(g) + group_rchk_last(g) + round_up((int)(8 * (size_t)g->b->U * g->n_cells), 256); }
 }  // namespace
 
 extern "C" hipError_t rs_launch_group(const RsLaunch* p, int threads, hipStream_t stream);
@@ -2572,6 +2584,7 @@ void rs_group_destroy(rs_group* g) {
   if (g->d_out2) (void)hipFree(g->d_out2);
   if (g->d_chk) (void)hipFree(g->d_chk);
   if (g->d_rchk) (void)hipFree(g->d_rchk);
+  if (g->d_qchk) (void)hipFree(g->d_qchk);
   if (g->d_ravg) (void)hipFree(g->d_ravg);
   if (g->d_rpend) (void)hipFree(g->d_rpend);
   if (g->d_rlast) (void)hipFree(g->d_rlast);
@@ -2856,17 +2869,20 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
   }
   /* rs_group_specialize: the group's own build -- its lean form when the call is plain for every cell (the uniform-presence rules above
    * make that a fact of the launch), the general one otherwise */
-  /* (the plain pair, rs_group_specialize, and the resident pair, rs_group_specialize_resident, are independent: each serves its own
-   * kind of call, is checked against its own built-in kernel and is dropped alone) */
-  RsJitKernel** const pair = res ? g->rjit : g->jit;
-  int* const chk_left = res ? g->rchk_left : g->chk_left;
-  int* const chk_agreed = res ? g->rchk_agreed : g->chk_agreed;
-  RsJitKernel* kd = que ? nullptr : pair[0]; /* (no run-time builds of the queued form: the built-in queued kernel serves it) */
+  /* (the plain pair, rs_group_specialize, the resident pair, rs_group_specialize_resident, and the queued pair,
+   * rs_group_specialize_queued, are independent: each serves its own kind of call, is checked against its own built-in kernel and is
+   * dropped alone.  A queued call's per-launch facts are those of its slots with users; a call of update-only slots only has none and
+   * takes the lean build when the config allows one.) */
+  RsJitKernel** const pair = que ? g->qjit : (res ? g->rjit : g->jit);
+  int* const chk_left = que ? g->qchk_left : (res ? g->rchk_left : g->chk_left);
+  int* const chk_agreed = que ? g->qchk_agreed : (res ? g->rchk_agreed : g->chk_agreed);
+  RsJitKernel* kd = pair[0];
   int which = 0;
-  if (!que && pair[1] && !has_prb && !L.queue_mode && !has_gate && !L.exact_scan && !L.gen_exp && !want_upper && !L.synthetic) { kd = pair[1]; which = 1; }
+  if (pair[1] && !has_prb && !L.queue_mode && !has_gate && !L.exact_scan && !L.gen_exp && !want_upper && !L.synthetic) { kd = pair[1]; which = 1; }
   /* A build without the self-check mark serves its first calls beside the built-in kernel of its kind (rs_group_jit_status,
    * rs_group_resident_jit_status): same slots, same state; every named cell's output fields and the state left behind must agree --
-   * the slice state, and for a resident call the averages of every user id, the pending bytes and the last-update time. */
+   * the slice state, for a resident call the averages of every user id, the pending bytes and the last-update time, and for a queued
+   * call those of both bearers of every user id. */
   const bool checked_call = kd != nullptr && chk_left[which] > 0;
   const size_t ss_all = 8 * (size_t)b->S * g->n_cells, sc_all = sizeof(RsCellScalars) * (size_t)g->n_cells;
   const size_t ra_all = 8 * (size_t)b->U * g->n_cells, rl_all = 8 * (size_t)g->n_cells, rp_all = 4 * (size_t)b->U * g->n_cells;
@@ -2881,24 +2897,41 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
     }
     return hipSuccess;
   };
+  /* ... and the three bearer stores of a queued call to / from one half of d_qchk */
+  const size_t qa_all = 16 * (size_t)b->U * g->n_cells, qp_all = 8 * (size_t)b->U * g->n_cells;
+  auto bearer_stores = [&](uint8_t* half, bool save) -> hipError_t {
+    struct { void* store; uint8_t* kept; size_t bytes; } const part[3] = {{g->d_qavg, half, qa_all},
+                                                                        {g->d_rlast, half + group_qchk_avg(g), rl_all},
+                                                                        {g->d_qpend, half + group_qchk_avg(g) + group_rchk_last(g), qp_all}};
+    for (const auto& x : part) {
+      const hipError_t e = hipMemcpyAsync(save ? (void*)x.kept : x.store, save ? x.store : (void*)x.kept, x.bytes, hipMemcpyDeviceToDevice, st);
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  };
   if (checked_call) {
     uint8_t* const before = g->d_chk;
     uint8_t* const after = g->d_chk + group_chk_half(g);
     HIP_TRY(hipMemcpyAsync(before, b->d_sstate, ss_all, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(before + group_chk_sstate(g), b->d_scal, sc_all, hipMemcpyDeviceToDevice, st));
-    if (res) HIP_TRY(resident_stores(g->d_rchk, true));
+    if (que) HIP_TRY(bearer_stores(g->d_qchk, true));
+    else if (res) HIP_TRY(resident_stores(g->d_rchk, true));
     RsLaunch Lb = L; /* the built-in kernel, its outputs into slots of its own */
     Lb.grp_out = g->d_out2;
     Lb.log_upper = want_upper ? (int32_t*)g->d_out2 : nullptr;
     Lb.done_flag = nullptr;
-    if (res) HIP_TRY(rs_launch_group_resident(&Lb, b->threads, st));
+    if (que) HIP_TRY(rs_launch_group_queued(&Lb, b->threads, st));
+    else if (res) HIP_TRY(rs_launch_group_resident(&Lb, b->threads, st));
     else HIP_TRY(rs_launch_group(&Lb, b->threads, st));
     HIP_TRY(hipMemcpyAsync(g->h_out2.data(), g->d_out2, (size_t)n * g->out_stride, hipMemcpyDeviceToHost, st));
     /* keep what it left, put back what it found: the run-time build starts from the same state */
     HIP_TRY(hipMemcpyAsync(after, b->d_sstate, ss_all, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(b->d_sstate, before, ss_all, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(b->d_scal, before + group_chk_sstate(g), sc_all, hipMemcpyDeviceToDevice, st));
-    if (res) {
+    if (que) {
+      HIP_TRY(bearer_stores(g->d_qchk + group_qchk_half(g), true));
+      HIP_TRY(bearer_stores(g->d_qchk, false));
+    } else if (res) {
       HIP_TRY(resident_stores(g->d_rchk + group_rchk_half(g), true));
       HIP_TRY(resident_stores(g->d_rchk, false));
     }
@@ -2913,7 +2946,8 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
   g->launches++;
   g->last_call_kind = kind;
   g->last_call_resident = res;
-  g->last_call_rjit = res && kd != nullptr;
+  g->last_call_rjit = res && !que && kd != nullptr;
+  g->last_call_qjit = que && kd != nullptr;
   if (!zc) HIP_TRY(hipMemcpyAsync(g->h_out, g->d_out, (size_t)n * g->out_stride, hipMemcpyDeviceToHost, st));
   const clk::time_point t2 = g->timing ? clk::now() : clk::time_point();
   bool seen = false;
@@ -2956,18 +2990,46 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
         for (int i = 0; i < count && !what[0]; i++)
           if (a[i] != r[i]) snprintf(what, sizeof what, "cell %d: %s[%d] = %d, the built-in kernel's %d", cell, name, i, a[i], r[i]);
       };
-      differ16("rbg_to_user (call position)", l.map, b->R);
-      differ16("quota_rbgs", l.quota, b->S);
-      differ16("target_rbs", l.target, b->S);
-      differ32("user_tbs_bits", l.tbs, in[k].n_users);
-      differ32("user_nprb | final_cqi << 16 | mcs << 24", l.uinfo, in[k].n_users);
-      if (want_upper) differ32("upper lists", l.upper, b->S * b->R);
+      if (!g->empty_slot[k]) { /* (an update-only slot of a queued call: its workgroup wrote no output, the state alone is compared) */
+        differ16("rbg_to_user (call position)", l.map, b->R);
+        differ16("quota_rbgs", l.quota, b->S);
+        differ16("target_rbs", l.target, b->S);
+        differ32("user_tbs_bits", l.tbs, in[k].n_users);
+        differ32("user_nprb | final_cqi << 16 | mcs << 24", l.uinfo, in[k].n_users);
+        if (want_upper) differ32("upper lists", l.upper, b->S * b->R);
+      }
       for (int i = 0; i < b->S && !what[0]; i++) {
         const double a = ss_jit[(size_t)cell * b->S + i], r = ss_ref[(size_t)cell * b->S + i];
         if (to_bits(a) != to_bits(r)) snprintf(what, sizeof what, "cell %d: slice state[%d] = %a, the built-in kernel's %a", cell, i, a, r);
       }
     }
-    if (res && !what[0]) {
+    if (que && !what[0]) {
+      /* the bearer stores of the named cells: averages and pending bytes of BOTH bearers of every user id of the config, the
+       * last-update time */
+      const uint8_t* const ref = g->d_qchk + group_qchk_half(g);
+      const size_t B = 2 * (size_t)b->U;
+      std::vector<double> a_jit(B * g->n_cells), a_ref(a_jit.size()), l_jit(g->n_cells), l_ref(g->n_cells);
+      std::vector<int32_t> p_jit(B * g->n_cells), p_ref(p_jit.size());
+      HIP_TRY(hipMemcpy(a_jit.data(), g->d_qavg, qa_all, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(a_ref.data(), ref, qa_all, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(l_jit.data(), g->d_rlast, rl_all, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(l_ref.data(), ref + group_qchk_avg(g), rl_all, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(p_jit.data(), g->d_qpend, qp_all, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(p_ref.data(), ref + group_qchk_avg(g) + group_rchk_last(g), qp_all, hipMemcpyDeviceToHost));
+      for (int k = 0; k < n && !what[0]; k++) {
+        const int cell = cell_ids ? cell_ids[k] : k;
+        for (size_t j = 0; j < B && !what[0]; j++) {
+          const double a = a_jit[cell * B + j], r = a_ref[cell * B + j];
+          if (to_bits(a) != to_bits(r)) snprintf(what, sizeof what, "cell %d: avg[%zu][%zu] = %a, the built-in kernel's %a", cell, j / 2, j % 2, a, r);
+        }
+        for (size_t j = 0; j < B && !what[0]; j++)
+          if (p_jit[cell * B + j] != p_ref[cell * B + j])
+            snprintf(what, sizeof what, "cell %d: pending_bytes[%zu][%zu] = %d, the built-in kernel's %d", cell, j / 2, j % 2, p_jit[cell * B + j], p_ref[cell * B + j]);
+        if (!what[0] && to_bits(l_jit[cell]) != to_bits(l_ref[cell]))
+          snprintf(what, sizeof what, "cell %d: last_update = %a, the built-in kernel's %a", cell, l_jit[cell], l_ref[cell]);
+      }
+    }
+    if (res && !que && !what[0]) {
       /* the resident stores of the named cells: the averages of EVERY user id of the config (the update touches them all), the pending
        * bytes, the last-update time */
       const uint8_t* const ref = g->d_rchk + group_rchk_half(g);
@@ -2993,7 +3055,25 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
           snprintf(what, sizeof what, "cell %d: last_update = %a, the built-in kernel's %a", cell, l_jit[cell], l_ref[cell]);
       }
     }
-    if (what[0] && res) {
+    if (what[0] && que) {
+      /* the queued pair is wrong: both of its builds are dropped (and their cache files), the plain and the resident pair stay.  This
+       * call returns the built-in queued kernel's outputs and leaves its state, bearer stores included; later queued calls run that kernel */
+      for (int w = 0; w < 2; w++) {
+        if (g->qjit[w]) rs_jit_reject(g->qjit[w]);
+        g->qjit[w] = nullptr;
+        g->qchk_left[w] = 0;
+      }
+      g->qjit_dropped = true;
+      g->last_call_qjit = false;
+      memcpy(g->h_out, g->h_out2.data(), (size_t)n * g->out_stride);
+      HIP_TRY(hipMemcpy(b->d_sstate, g->d_chk + group_chk_half(g), ss_all, hipMemcpyDeviceToDevice));
+      HIP_TRY(bearer_stores(g->d_qchk + group_qchk_half(g), false));
+      HIP_TRY(hipStreamSynchronize(st));
+      snprintf(g->qjit_msg, sizeof g->qjit_msg, "self-check of the group's specialised queued %s build, checked call %d: %s; both queued builds are dropped, "
+               "the built-in queued kernel serves this group's queued calls (lint the code object: tools/lint_exec_restore.py)",
+               which ? "lean" : "general", g->qchk_agreed[which] + 1, what);
+      snprintf(g_err, sizeof g_err, "%s", g->qjit_msg);
+    } else if (what[0] && res) {
       /* the resident pair is wrong: both of its builds are dropped (and their cache files), the plain pair stays.  This call returns
        * the built-in resident kernel's outputs and leaves its state, resident stores included; later resident calls run that kernel */
       for (int w = 0; w < 2; w++) {
@@ -3273,16 +3353,17 @@ const char* rs_group_kernel_name(rs_group* g) {
   if (!g) return "";
   /* (a resident call: the group's resident builds if rs_group_specialize_resident gave it some, else the built-in resident kernel --
    * whatever serves the plain calls) */
-  if (g->last_call_kind == kGroupQueued) return g->kname_que; /* (whatever builds the group has: none of them serves a queued call) */
+  if (g->last_call_kind == kGroupQueued) return g->last_call_qjit ? "rs_group_queued_kernel_jit" : g->kname_que; /* (likewise: rs_group_specialize_queued) */
   if (g->last_call_resident) return g->last_call_rjit ? "rs_group_resident_kernel_jit" : g->kname_res;
   return g->jit[0] ? "rs_group_kernel_jit" : g->kname;
 }
 
 /* Shape specialisation of a group: rs_ctx_specialize for the group surface -- the one-TTI form compiled for the config's slices, RBGs,
- * PRBs per RBG, scheduler, workgroup size and user CAPACITY, one workgroup per call slot, in a general and a lean build.  Two pairs,
- * each an option of its own: rs_group_specialize (entry point rs_group_kernel_jit, serves rs_group_schedule_tti) and
- * rs_group_specialize_resident (rs_group_resident_kernel_jit, serves rs_group_schedule_tti_at).  Between calls at any time: slice
- * state, CQI images, per-PRB stores and resident stores are not touched. */
+ * PRBs per RBG, scheduler, workgroup size and user CAPACITY, one workgroup per call slot, in a general and a lean build.  Three pairs,
+ * each an option of its own: rs_group_specialize (entry point rs_group_kernel_jit, serves rs_group_schedule_tti),
+ * rs_group_specialize_resident (rs_group_resident_kernel_jit, serves rs_group_schedule_tti_at) and rs_group_specialize_queued
+ * (rs_group_queued_kernel_jit, serves rs_group_schedule_tti_queued).  Between calls at any time: slice state, CQI images, per-PRB
+ * stores, resident stores and bearer stores are not touched. */
 namespace {
 /* one pair's fields of rs_group */
 struct GroupJitPair {
@@ -3290,18 +3371,22 @@ struct GroupJitPair {
   bool *wanted, *dropped;
   int *chk_left, *chk_agreed;
   char* msg; /* [512] */
-  bool resident;
 };
-GroupJitPair group_jit_pair(rs_group* g, bool resident) {
-  if (resident) return {g->rjit, &g->rjit_wanted, &g->rjit_dropped, g->rchk_left, g->rchk_agreed, g->rjit_msg, true};
-  return {g->jit, &g->jit_wanted, &g->jit_dropped, g->chk_left, g->chk_agreed, g->jit_msg, false};
+/* kind: kGroupPlain, kGroupResident or kGroupQueued -- the call the pair serves */
+GroupJitPair group_jit_pair(rs_group* g, int kind) {
+  if (kind == kGroupQueued) return {g->qjit, &g->qjit_wanted, &g->qjit_dropped, g->qchk_left, g->qchk_agreed, g->qjit_msg};
+  if (kind == kGroupResident) return {g->rjit, &g->rjit_wanted, &g->rjit_dropped, g->rchk_left, g->rchk_agreed, g->rjit_msg};
+  return {g->jit, &g->jit_wanted, &g->jit_dropped, g->chk_left, g->chk_agreed, g->jit_msg};
 }
 
-int group_specialize_pair(rs_group* g, bool resident) {
+int group_specialize_pair(rs_group* g, int kind) {
   rs_batch* b = g->b;
-  const GroupJitPair jp = group_jit_pair(g, resident);
+  const bool resident = kind == kGroupResident, queued = kind == kGroupQueued;
+  const GroupJitPair jp = group_jit_pair(g, kind);
   if (jp.jit[0]) return RS_OK;
   if (*jp.dropped) return fail(RS_ERR_STATE, "%s", jp.msg);
+  if (queued && b->sched != RS_SCHED_NVS && b->sched != RS_SCHED_SEQUENTIAL && b->sched != RS_SCHED_MAXCELL && b->sched != RS_SCHED_SUBOPT && b->sched != RS_SCHED_VOGEL)
+    return fail(RS_ERR_INVALID, "scheduler %d has no queued form (rs_group_set_bearers): nothing for rs_group_specialize_queued to build", b->sched);
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   *jp.wanted = true;
   if (!g->d_out2) {
@@ -3321,8 +3406,14 @@ int group_specialize_pair(rs_group* g, bool resident) {
     snprintf(jp.msg, 512, "allocation of the self-check's copies of the resident stores failed (%zu bytes)", 2 * group_rchk_half(g));
     return fail(RS_ERR_HIP, "%s", jp.msg);
   }
+  if (queued && !g->d_qchk && hipMalloc(&g->d_qchk, 2 * group_qchk_half(g)) != hipSuccess) {
+    (void)hipGetLastError();
+    g->d_qchk = nullptr;
+    snprintf(jp.msg, 512, "allocation of the self-check's copies of the bearer stores failed (%zu bytes)", 2 * group_qchk_half(g));
+    return fail(RS_ERR_HIP, "%s", jp.msg);
+  }
   const int qmode = (b->sched == RS_SCHED_PF || b->sched == RS_SCHED_NVS) ? 1 : 0; /* (the gate scratch of the group's carve: carve_lds) */
-  const int flags = 1 | 8 | (resident ? 16 : 0);
+  const int flags = 1 | 8 | (resident ? 16 : 0) | (queued ? 32 : 0);
   char msg[512] = "";
   jp.jit[0] = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, qmode, 0, msg, sizeof msg, flags);
   if (!jp.jit[0]) {
@@ -3345,9 +3436,11 @@ int group_specialize_pair(rs_group* g, bool resident) {
   return RS_OK;
 }
 
-int group_jit_pair_status(rs_group* g, bool resident, char* msg, size_t msglen) {
-  const GroupJitPair jp = group_jit_pair(g, resident);
-  const char* const ref = resident ? "the built-in resident kernel field by field, resident stores included" : "the built-in kernel field by field";
+int group_jit_pair_status(rs_group* g, int kind, char* msg, size_t msglen) {
+  const GroupJitPair jp = group_jit_pair(g, kind);
+  const char* const ref = kind == kGroupQueued     ? "the built-in queued kernel field by field, bearer stores included"
+                          : kind == kGroupResident ? "the built-in resident kernel field by field, resident stores included"
+                                                   : "the built-in kernel field by field";
   if (msg && msglen) {
     if (*jp.dropped || !jp.jit[0]) {
       snprintf(msg, msglen, "%s", jp.msg);
@@ -3360,7 +3453,7 @@ int group_jit_pair_status(rs_group* g, bool resident, char* msg, size_t msglen) 
         else if (rs_jit_is_verified(k)) snprintf(out, n, "carries the self-check mark of an earlier check (cache file)");
         else snprintf(out, n, "unchecked (RS_JIT_SELFCHECK=0)");
       };
-      char ge[200], le[200];
+      char ge[220], le[220];
       state(0, ge, sizeof ge);
       state(1, le, sizeof le);
       snprintf(msg, msglen, "general build: %s; lean build: %s", ge, le);
@@ -3373,22 +3466,32 @@ int group_jit_pair_status(rs_group* g, bool resident, char* msg, size_t msglen) 
 
 int rs_group_specialize(rs_group* g) {
   if (!g) return fail(RS_ERR_INVALID, "null group");
-  return group_specialize_pair(g, false);
+  return group_specialize_pair(g, kGroupPlain);
 }
 
 int rs_group_specialize_resident(rs_group* g) {
   if (!g) return fail(RS_ERR_INVALID, "null group");
-  return group_specialize_pair(g, true);
+  return group_specialize_pair(g, kGroupResident);
 }
 
 int rs_group_jit_status(rs_group* g, char* msg, size_t msglen) {
   if (!g) return fail(RS_ERR_INVALID, "null group");
-  return group_jit_pair_status(g, false, msg, msglen);
+  return group_jit_pair_status(g, kGroupPlain, msg, msglen);
 }
 
 int rs_group_resident_jit_status(rs_group* g, char* msg, size_t msglen) {
   if (!g) return fail(RS_ERR_INVALID, "null group");
-  return group_jit_pair_status(g, true, msg, msglen);
+  return group_jit_pair_status(g, kGroupResident, msg, msglen);
+}
+
+int rs_group_specialize_queued(rs_group* g) {
+  if (!g) return fail(RS_ERR_INVALID, "null group");
+  return group_specialize_pair(g, kGroupQueued);
+}
+
+int rs_group_queued_jit_status(rs_group* g, char* msg, size_t msglen) {
+  if (!g) return fail(RS_ERR_INVALID, "null group");
+  return group_jit_pair_status(g, kGroupQueued, msg, msglen);
 }
 
 /* ---- the reference's CQI trace files (include/radiosaber_hip.h) ---- */

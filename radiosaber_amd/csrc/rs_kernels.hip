@@ -795,8 +795,8 @@ __global__ void __launch_bounds__(512, 4) rs_group_resident_kernel(RsLaunch p) {
 
 /* ... and its queued form (rs_group_schedule_tti_queued): both bearers of every user stay on the device -- averages, pending bytes,
  * existence --, the call brings m_dataToTransmit per bearer, and a slot without users does the update alone.  Kernels of their own
- * for the schedulers the oracle restates with queues and a per-user credit (rs_launch_group_queued): 7, 8, 9, 101, 103.  No run-time
- * builds of this form. */
+ * for the schedulers the oracle restates with queues and a per-user credit (rs_launch_group_queued): 7, 8, 9, 101, 103.  A group's
+ * run-time builds of this form are rs_group_queued_kernel_jit below. */
 template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_queued_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
@@ -820,11 +820,20 @@ __global__ void __launch_bounds__(512, 4) rs_group_queued_kernel(RsLaunch p) {
 #ifndef RS_JIT_GROUP_RESIDENT
 #define RS_JIT_GROUP_RESIDENT 0 /* 1, with RS_JIT_GROUP: the group's build of the resident form (rs_group_specialize_resident) */
 #endif
+#ifndef RS_JIT_GROUP_QUEUED
+#define RS_JIT_GROUP_QUEUED 0 /* 1, with RS_JIT_GROUP and never with RS_JIT_GROUP_RESIDENT: the group's build of the queued form (rs_group_specialize_queued) */
+#endif
 #if RS_JIT_GROUP
-/* two entry points, one per option list: rs_group_kernel_jit, and rs_group_resident_kernel_jit for the calls that keep the cells' PF
- * averages on the device (rs_group_schedule_tti_at).  Same text but for the name and kGrpRes; each has a general and a lean form. */
+/* three entry points, one per option list: rs_group_kernel_jit, rs_group_resident_kernel_jit for the calls that keep the cells' PF
+ * averages on the device (rs_group_schedule_tti_at), and rs_group_queued_kernel_jit for the calls that keep both bearers there
+ * (rs_group_schedule_tti_queued).  Same text but for the name, kGrpRes and kGrpQue; each has a general and a lean form. */
+#if RS_JIT_GROUP_RESIDENT && RS_JIT_GROUP_QUEUED
+#error "RS_JIT_GROUP_RESIDENT and RS_JIT_GROUP_QUEUED exclude each other"
+#endif
 #if RS_JIT_GROUP_RESIDENT
 #define RS_GROUP_JIT_ENTRY rs_group_resident_kernel_jit
+#elif RS_JIT_GROUP_QUEUED
+#define RS_GROUP_JIT_ENTRY rs_group_queued_kernel_jit
 #else
 #define RS_GROUP_JIT_ENTRY rs_group_kernel_jit
 #endif
@@ -832,7 +841,7 @@ extern "C" __global__ void __launch_bounds__(RS_JIT_NT, RS_JIT_WPE) RS_GROUP_JIT
 #if defined(RS_JIT_LEAN) && RS_JIT_LEAN
   /* The lean build of a group's kernel: the plain call, exactly as in the one-TTI lean kernel below -- per-RBG reports, no customised
    * slices, no gates, exponents in {0, 1}, every input an ordinary FP32 number, no UpperBound lists, no synthetic-experiment blocks
-   * (the call's uniform-presence rules make that a per-launch fact; rs_group_schedule_tti and rs_group_schedule_tti_at pick the build per call).  image_mode stays
+   * (the call's uniform-presence rules make that a per-launch fact; rs_group_schedule_tti, rs_group_schedule_tti_at and rs_group_schedule_tti_queued pick the build per call).  image_mode stays
    * the slot header's word: the cells of one launch mix modes 0 / 1 / 2. */
   p.cqi_mode = RS_CQI_EPOCHS;
   p.prb_cqi = nullptr; p.queue_mode = 0; p.alpha = nullptr; p.beta = nullptr; p.hol = nullptr; p.prio = nullptr;
@@ -845,7 +854,7 @@ extern "C" __global__ void __launch_bounds__(RS_JIT_NT, RS_JIT_WPE) RS_GROUP_JIT
   constexpr RsCarve kCv = rs_carve(RS_JIT_S, RS_JIT_U, RS_JIT_R, RS_JIT_SCHED, RS_JIT_NT, RS_JIT_CARVEQ, RS_JIT_WIN);
   __shared__ __align__(16) unsigned char lds[kCv.lds_bytes];
   constexpr int kGrpSched = RS_JIT_SCHED, kGrpEpt = (RS_JIT_SCHED != 9 && RS_JIT_SCHED != 10) ? 0 : (kCv.ept <= 4 ? kCv.ept : 0);
-  constexpr bool kGrpFixed = true, kGrpRes = RS_JIT_GROUP_RESIDENT != 0, kGrpQue = false;
+  constexpr bool kGrpFixed = true, kGrpRes = RS_JIT_GROUP_RESIDENT != 0, kGrpQue = RS_JIT_GROUP_QUEUED != 0;
 #include "rs_phase_group.inc"
 }
 #undef RS_GROUP_JIT_ENTRY

@@ -7,8 +7,9 @@
  * sequence number to the host.  Its acquire of the counter orders it behind every other workgroup's fence and release.
  *
  * The entry points of rs_kernels.hip include this text as their body, as rs_cell_body includes its phases: the kernels built into the
- * library (rs_group_kernel, rs_group_resident_kernel: shape in the launch block) and a group's own run-time builds (rs_group_kernel_jit,
- * rs_group_specialize; rs_group_resident_kernel_jit, rs_group_specialize_resident).
+ * library (rs_group_kernel, rs_group_resident_kernel, rs_group_queued_kernel: shape in the launch block) and a group's own run-time
+ * builds (rs_group_kernel_jit, rs_group_specialize; rs_group_resident_kernel_jit, rs_group_specialize_resident;
+ * rs_group_queued_kernel_jit, rs_group_specialize_queued).
  * The includer provides `p` (the launch block), `lds` and four constants: kGrpSched, kGrpEpt, kGrpFixed -- shape, workgroup size and LDS
  * carve are the constants RS_JIT_*, RS_JIT_U being the user CAPACITY while the users of a slot stay the slot header's word -- and
  * kGrpLean -- the plain call's per-launch options are constants too.  (Text, not a function of its own: the built-in instantiations
@@ -23,12 +24,14 @@
  * kGrpFixed the resident text's shape is constant as well: the update's range and the stores' stride are RS_JIT_U, the loop strides
  * RS_JIT_NT, the grants' LDS offset the constexpr carve's off_tx.  Order of operations and arithmetic are the same in both forms.
  *
- * A sixth constant, kGrpQue, makes the queued form (rs_group_schedule_tti_queued, rs_group_queued_kernel; never with kGrpRes or
- * kGrpFixed: the library's built-in kernels only): the cell keeps BOTH bearers of every user -- average, pending bytes, existence --
+ * A sixth constant, kGrpQue, makes the queued form (rs_group_schedule_tti_queued, rs_group_queued_kernel; never with kGrpRes):
+ * the cell keeps BOTH bearers of every user -- average, pending bytes, existence --
  * and the slot brings m_dataToTransmit[2] per call position.  The update strides over the 2 U bearers, the call's averages are the
  * sums over the bearers with data, the grant is split over the bearers from the highest priority down (DoStopSchedule), and a slot
  * without users (U = 0 in its header) does the update alone: the body and the credit are skipped, uniformly for the workgroup.  With
- * kGrpQue false none of this text reaches the other instantiations. */
+ * kGrpQue false none of this text reaches the other instantiations.  Under kGrpFixed (rs_group_queued_kernel_jit) the queued text's
+ * shape is constant as the resident text's: the update's range and the strides of the [U][2] stores are 2 * RS_JIT_U, the loop strides
+ * RS_JIT_NT, the grants' LDS offset the constexpr carve's off_tx.  Order of operations and arithmetic are the same in both forms. */
   const uint8_t* const in = p.grp_in + (size_t)blockIdx.x * (size_t)p.grp_in_stride;
   uint8_t* const out = p.grp_out + (size_t)blockIdx.x * (size_t)p.grp_out_stride;
   const RsGroupCell* const h = (const RsGroupCell*)in;
@@ -135,9 +138,9 @@
 #endif
   }
   if constexpr (kGrpQue) {
-    /* (built-in kernels only: shape and carve are the launch block's) */
-    const int nthreads = (int)blockDim.x;
-    const int n_all = p.U; /* the config's users: 2 n_all bearers, the stores' stride and the update's range */
+    /* (shape and carve: the launch block's in the built-in kernels, the constants RS_JIT_* in a group's run-time build) */
+    const int nthreads = kGrpFixed ? RS_JIT_NT : (int)blockDim.x;
+    const int n_all = kGrpFixed ? RS_JIT_U : p.U; /* the config's users: 2 n_all bearers, the stores' stride and the update's range */
     double* const b_avg = p.grp_qavg + (size_t)cell * 2 * (size_t)n_all;
     int32_t* const b_pend = p.grp_qpend + (size_t)cell * 2 * (size_t)n_all;
     const uint8_t* const b_has = p.grp_qhas + (size_t)cell * 2 * (size_t)n_all;
@@ -204,9 +207,10 @@
     /* 4. DoStopSchedule's loop (ref: downlink-transport-scheduler.cpp:170-221): the grant of a call position -- from LDS, as the
      *    resident form's -- goes to the user's bearers from the highest priority down, min(available, dataToTransmit) each */
     if (q.U != 0) {
-      const int nthreads = (int)blockDim.x;
-      const int n_all = p.U;
-      const int32_t* const granted = (const int32_t*)(lds + p.off_tx);
+      const int nthreads = kGrpFixed ? RS_JIT_NT : (int)blockDim.x;
+      const int n_all = kGrpFixed ? RS_JIT_U : p.U;
+      constexpr RsCarve kGrpCv = rs_carve(RS_JIT_S, RS_JIT_U, RS_JIT_R, RS_JIT_SCHED, RS_JIT_NT, RS_JIT_CARVEQ, RS_JIT_WIN); /* (the body's own carve) */
+      const int32_t* const granted = (const int32_t*)(lds + (kGrpFixed ? kGrpCv.off_tx : p.off_tx));
       int32_t* const b_pend = p.grp_qpend + (size_t)cell * 2 * (size_t)n_all;
       const int32_t* const ids = p.grp_uid + (size_t)cell * (size_t)n_all;    /* entry i: written by this thread before the body */
       const int32_t* const keep = p.grp_qdata + (size_t)cell * 2 * (size_t)n_all; /* entries 2i, 2i + 1: likewise */
@@ -220,7 +224,14 @@
           if (d > 0) {
             const int sent = available < d ? available : d;
             available -= sent;
+#if defined(RS_FAULT_INJECT_QUEUED)
+            /* tests only (tests/test_gpu_group_queued_specialize.py): a deliberately wrong run-time build of the QUEUED form -- the last
+             * bearer credited for a position gets a byte more; the outputs stay right, so only the self-check's comparison of the
+             * bearer stores can catch it.  A value, no address or index; the twin of RS_FAULT_INJECT_RESIDENT. */
+            b_pend[2 * id + b] += sent + ((kGrpFixed && (available <= 0 || b == 0 || keep[2 * i] <= 0)) ? 1 : 0);
+#else
             b_pend[2 * id + b] += sent;
+#endif
           }
         }
       }

@@ -3,12 +3,16 @@
 call followed by rs_group_set_pending per cell -- and, as the regression check, the plain and the resident call, which another
 checkout can be measured on as well (profiles/group_queued.md).
 
-    python tools/group_queued_latency.py [--variant plain|resident|resident+pending|queued|all] [--calls 300]
+    python tools/group_queued_latency.py [--variant plain|resident|resident+pending|queued|queued-spec|all] [--calls 300]
     RS_TREE=<another checkout> python tools/group_queued_latency.py --variant plain     # that tree's package
+    python tools/group_queued_latency.py --variant queued-spec --cells 27 --shapes 500x25x4 500x64x8 --sched 9 7
 
-Workloads: 8 and 64 cells; 500 users x 25 RBGs and 100 users x 64 RBGs; scheduler 9; cqi_epoch on (new reports every 40 calls).
-Timed through the Python layer, marshalling included, like tools/group_resident_latency.py: three repetitions per line, whose
-spread is the yardstick for a difference between lines."""
+queued-spec: the queued call after rs_group_specialize_queued (profiles/group_queued_specialize.md); its warm-up holds the builds'
+checked calls.  Workloads by default: 8 and 64 cells; 500 users x 25 RBGs and 100 users x 64 RBGs; scheduler 9; cqi_epoch on (new
+reports every 40 calls).  --shapes takes users x RBGs x PRBs per RBG (20 equal slices).  Scheduler 7 names the users of one slice per
+call, the slice rotating with the call, and gives no required_rbs.  Timed through the Python layer, marshalling included, like
+tools/group_resident_latency.py: three repetitions per line, whose spread is the yardstick for a difference between lines; p50 / p99
+are taken over the timed calls of all three."""
 import argparse
 import os
 import sys
@@ -20,19 +24,28 @@ import numpy as np
 sys.path.insert(0, os.environ.get("RS_TREE", str(Path(__file__).resolve().parents[1])))
 import radiosaber_amd as rs  # noqa: E402
 
-VARIANTS = ("plain", "resident", "resident+pending", "queued")
+VARIANTS = ("plain", "resident", "resident+pending", "queued", "queued-spec")
 ap = argparse.ArgumentParser()
 ap.add_argument("--variant", default="all", choices=VARIANTS + ("all",))
 ap.add_argument("--calls", type=int, default=300)
 ap.add_argument("--warmup", type=int, default=40)
+ap.add_argument("--cells", type=int, nargs="+", default=[8, 64])
+ap.add_argument("--shapes", nargs="+", default=["100x64x8", "500x25x4"], help="users x RBGs x PRBs per RBG")
+ap.add_argument("--sched", type=int, nargs="+", default=[9])
 args = ap.parse_args()
 
-for ues, R, G in ((5, 64, 8), (25, 25, 4)):
-    for K in (8, 64):
+for sched, shape in ((s, x) for s in args.sched for x in args.shapes):
+    U, R, G = (int(v) for v in shape.split("x"))
+    ues = U // 20
+    assert U == 20 * ues, "users: a multiple of 20 (20 equal slices)"
+    for K in args.cells:
         sc = rs.SliceConfig([ues] * 20, weight=[0.05] * 20)
-        U = 20 * ues
         for variant in (VARIANTS if args.variant == "all" else (args.variant,)):
-            g = rs.GroupScheduler(sc, R, G, K, sched=9)
+            if variant == "queued-spec" and not hasattr(rs.GroupScheduler, "specialize_queued"):
+                continue  # (RS_TREE names a checkout from before rs_group_specialize_queued)
+            g = rs.GroupScheduler(sc, R, G, K, sched=sched)
+            if variant == "queued-spec":
+                g.specialize_queued()
             rng = np.random.default_rng(1)
             cqi = [rng.integers(1, 16, (U, R)).astype(np.uint8) for _ in range(K)]
             avg = [rng.uniform(1e4, 1e6, U) for _ in range(K)]
@@ -41,9 +54,9 @@ for ues, R, G in ((5, 64, 8), (25, 25, 4)):
             for k in range(K):
                 if variant in ("resident", "resident+pending"):
                     g.set_avg(k, avg[k], 0.1)
-                if variant == "queued":
+                if variant in ("queued", "queued-spec"):
                     g.set_bearers(k, np.ones((U, 2), bool), np.stack([avg[k], avg[k][::-1]], axis=1), 0.1)
-            now, best = 0.1, []
+            now, best, each = 0.1, [], []
             for rep in range(3):
                 t0 = 0.0
                 for i in range(args.warmup + args.calls):
@@ -51,20 +64,28 @@ for ues, R, G in ((5, 64, 8), (25, 25, 4)):
                         t0 = time.perf_counter()
                     now += 0.001
                     calls = [dict(cqi=cqi[k], rand0=123 + i, rand1=456 + i, cqi_epoch=1 + i // 40) for k in range(K)]
+                    ids = None
+                    if sched == 7:  # the served slice's users, a new slice (and a new image) every 40 calls
+                        ids = np.arange(ues, dtype=np.int32) + ues * ((i // 40) % 20)
+                        for k in range(K):
+                            calls[k].update(cqi=cqi[k][ids], user_id=ids)
+                    t1 = time.perf_counter()
                     if variant == "plain":
                         for k in range(K):
                             calls[k]["avg_rate"] = avg[k]
                         g.schedule_tti(calls)
-                    elif variant == "queued":
+                    elif variant in ("queued", "queued-spec"):
                         for k in range(K):
-                            calls[k]["data_to_transmit"] = data
+                            calls[k]["data_to_transmit"] = data if ids is None else data[ids]
                         g.schedule_tti_queued(calls, now)
                     else:
                         g.schedule_tti_at(calls, now)
                         if variant == "resident+pending":
                             for k in range(K):
                                 g.set_pending(k, pending)
+                    if i >= args.warmup:
+                        each.append((time.perf_counter() - t1) * 1e6)
                 best.append((time.perf_counter() - t0) / args.calls * 1e6)
-            print(f"{K:3d} cells x {U} UEs x {R} RBGs, {variant:16s}: " + " / ".join(f"{b:.1f}" for b in best) + f" us per call (python), {g.kernel_name}",
+            print(f"{K:3d} cells x {U} UEs x {R} RBGs, {variant:16s}: " + " / ".join(f"{b:.1f}" for b in best) + f" us per call (python), p50 {np.percentile(each, 50):.1f} p99 {np.percentile(each, 99):.1f}, sched {sched}, {g.kernel_name}",
                   flush=True)
             g.close()
