@@ -32,7 +32,8 @@ extern "C" {
                                rs_group_set_avg / rs_group_get_avg / rs_group_set_pending / rs_group_schedule_tti_at (a group cell's PF averages resident on the device),
                                rs_group_specialize_resident / rs_group_resident_jit_status / rs_jit_selfcheck_group_resident (a group's own builds of the resident kernel, self-checked on state),
                                rs_group_set_bearers / rs_group_get_bearers / rs_group_schedule_tti_queued (a group cell's two bearers per user resident on the device: finite queues credited there),
-                               rs_group_specialize_queued / rs_group_queued_jit_status / rs_jit_selfcheck_group_queued (a group's own builds of the queued kernel, self-checked on the bearer stores);
+                               rs_group_specialize_queued / rs_group_queued_jit_status / rs_jit_selfcheck_group_queued (a group's own builds of the queued kernel, self-checked on the bearer stores),
+                               rs_group_set_counters / rs_group_get_counters / rs_group_schedule_tti_counted (a bearer-resident group cell's m_cumulateBytes / m_cumulateRBs on the device, the bytes sent per bearer returned per call);
                                rs_config.link_tables (RS_LINK_*) + rs_link_tables_pinned / rs_link_tables_compare, rs_tti_in.cqi_epoch (the context keeps the
                                CQI image of an unchanged report set on the device), rs_ctx_jit_status (a specialised context checks its run-time build against the
                                built-in kernel during its first calls), rs_batch_config.selfcheck -1 / 0 / 1 with run-time builds verified by default and the
@@ -316,7 +317,8 @@ int rs_group_image_stats(const rs_group* g, int64_t out[3]);
  * after a build was dropped.  While the last call was a resident one: "rs_group_resident_kernel_jit" if the group's resident builds
  * served it (rs_group_specialize_resident), else the built-in "rs_group_resident_kernel<sched, ept>".  While it was a queued one:
  * "rs_group_queued_kernel_jit" if the group's queued builds served it (rs_group_specialize_queued), else the built-in
- * "rs_group_queued_kernel<sched, ept>". */
+ * "rs_group_queued_kernel<sched, ept>".  While it was a counted one (rs_group_schedule_tti_counted): the built-in
+ * "rs_group_counted_kernel<sched, ept>". */
 const char* rs_group_kernel_name(rs_group* g);
 /* Optional, at any time between two calls: rs_ctx_specialize for a group -- the one-TTI kernel compiled for the config's slices, RBGs,
  * PRBs per RBG, scheduler, workgroup size and user capacity (hiprtc, ~2 s per build and process, cached on disk apart from the
@@ -482,6 +484,34 @@ int rs_group_queued_jit_status(rs_group* g, char* msg, size_t msglen);
  * negative value with the compiler's log in err; negative for the schedulers without a queued form: RS_SCHED_PF, RS_SCHED_UPPERBOUND,
  * RS_SCHED_NVS_NONGREEDY) */
 int rs_jit_selfcheck_group_queued(int n_slices, int n_users, int n_rbgs, int rbg_size, int threads, int sched, char* err, size_t errlen);
+
+/* Counted bearers (ABI 11 addition, no layout changed): a bearer-resident cell may also keep RadioBearer's m_cumulateBytes and
+ * m_cumulateRBs of both bearers of every user id on the device -- the numbers of the reference's "app:" log lines and per-slice
+ * throughput figures -- and a call through rs_group_schedule_tti_counted returns dataTransmitted per bearer, what a binding passes to
+ * UpdateTransmittedBytes and rlc->TransmissionProcedure (ref: downlink-transport-scheduler.cpp:170-221, downlink-nvs-scheduler.cpp:221-273).
+ * Such a call is rs_group_schedule_tti_queued in every rule, order of operations and result; in its step 4, for call position i, user
+ * id u and every bearer b that is credited (data[b] > 0 reached with available > 0):
+ *      cum_bytes[u][b] += sent;  cum_rbs[u][b] += the position's allocated PRBs (rs_tti_out.user_nprb[i]: the reference's
+ *      GetListOfAllocatedRBs()->size(), the same count for both bearers of a split grant);  sent[k][i][b] = sent,
+ * and sent[k][i][b] = 0 for a bearer that is not credited.  Update-only slots and positions without a grant move no counter.
+ * Counted calls run the built-in "rs_group_counted_kernel<sched, ept>", after rs_group_specialize_queued too: no run-time build
+ * reaches them. */
+/* Makes a bearer-resident `cell` counted (again, at any time between two calls) and sets its counters: [U][2] by user id and bearer
+ * priority, NULL = zeros.  A synchronising copy outside the fast path.  RS_ERR_STATE: the cell is not bearer-resident; RS_ERR_INVALID:
+ * a negative value.  rs_group_set_bearers leaves the counters and the counted state as they are (a bearer that does not exist is
+ * never written by a call); rs_group_set_avg ends the counted state, and so does a call that fails with RS_ERR_HIP for the cells it
+ * named.  rs_group_schedule_tti_queued and rs_group_schedule_tti serve a counted cell as before and leave its counters alone. */
+int rs_group_set_counters(rs_group* g, int32_t cell, const int64_t* cum_bytes /* [U][2] or NULL = zeros */, const int64_t* cum_rbs /* [U][2] or NULL */);
+/* The counters as they are after the last call (a synchronising copy; not part of a TTI).  Each output may be NULL.  RS_ERR_STATE: the
+ * cell is not counted. */
+int rs_group_get_counters(rs_group* g, int32_t cell, int64_t* cum_bytes /* [U][2] or NULL */, int64_t* cum_rbs /* [U][2] or NULL */);
+/* rs_group_schedule_tti_queued for counted cells: its rules (update-only slots, the clock rules, cqi_epoch, subsets and permutations,
+ * a rejected call launches nothing and moves nothing, launch and image statistics), and every named cell is counted (RS_ERR_STATE, the
+ * message names the cell).  sent may be NULL (the counters alone are kept); sent[k] may be NULL for an update-only slot, and for any
+ * slot whose rows the caller does not want. */
+int rs_group_schedule_tti_counted(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in /* [n] */, rs_tti_out* out /* [n] */,
+                                  const double* now /* [n] */, const int32_t* const* data_to_transmit /* [n]: [in[k].n_users][2] */,
+                                  int32_t* const* sent /* [n]: [in[k].n_users][2]; NULL, or NULL per update-only slot */);
 
 /* ------------------------------------------------------------------------------------------
  * Batched mode: many independent cells resident on the device, whole DoSchedule() loops

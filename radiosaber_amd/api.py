@@ -114,6 +114,7 @@ ABI_SYMBOLS = [
     "rs_group_specialize_resident", "rs_group_resident_jit_status", "rs_jit_selfcheck_group_resident",
     "rs_group_set_bearers", "rs_group_get_bearers", "rs_group_schedule_tti_queued",
     "rs_group_specialize_queued", "rs_group_queued_jit_status", "rs_jit_selfcheck_group_queued",
+    "rs_group_set_counters", "rs_group_get_counters", "rs_group_schedule_tti_counted",
 ]
 
 _lib = None
@@ -168,6 +169,10 @@ def lib():
     L.rs_group_specialize_resident.argtypes = [C.c_void_p]
     L.rs_group_resident_jit_status.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.rs_jit_selfcheck_group_resident.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
+    L.rs_group_set_counters.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.rs_group_get_counters.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.rs_group_schedule_tti_counted.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_TtiIn), C.POINTER(_TtiOut),
+                                                C.POINTER(C.c_double), C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32))]
     L.rs_group_specialize_queued.argtypes = [C.c_void_p]
     L.rs_group_queued_jit_status.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.rs_jit_selfcheck_group_queued.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
@@ -532,6 +537,7 @@ class TtiResult:
     user_tbs_bits: np.ndarray
     upper_rbg: Optional[np.ndarray] = None   # RS_SCHED_UPPERBOUND: [S][R] RBGs each slice took, push order, -1 padded
     upper_user: Optional[np.ndarray] = None  # ... and the user each one went to
+    sent: Optional[np.ndarray] = None        # GroupScheduler.schedule_tti_counted: [n][2] bytes DoStopSchedule sent per call position and bearer
 
 
 def _marshal_tti(S, R, rbg_size, sched, cqi, avg_rate, rand0=0, rand1=0, user_id=None, cqi_prb=None, hol_delay=None, prio_has_data=None,
@@ -791,10 +797,14 @@ class GroupScheduler:
         """rs_group_schedule_tti_queued: schedule_tti for bearer-resident cells.  calls[k] as for schedule_tti_at plus data_to_transmit
         [n][2], UserToSchedule::m_dataToTransmit of the call's users by bearer priority; or dict(n_users=0), an update-only slot:
         the cell's bearers get their EWMA step at now[k] and nothing is scheduled (its result reads rbg_to_user -1, targets and quotas 0)."""
+        return self._schedule_queued(calls, now, cell_ids, False)
+
+    def _schedule_queued(self, calls, now, cell_ids, counted):
         n = len(calls)
         S, R = self.slices.n_slices, self.R
         ins, outs, results, keep = (_TtiIn * n)(), (_TtiOut * n)(), [], []
         data = (C.POINTER(C.c_int32) * n)()
+        sent = (C.POINTER(C.c_int32) * n)()
         for k, kw in enumerate(calls):
             kw = dict(kw)
             if kw.get("n_users", None) == 0:
@@ -804,6 +814,8 @@ class GroupScheduler:
                 ins[k] = _TtiIn()
                 outs[k] = _TtiOut(_p(res.target_rbs, C.c_int32), _p(res.quota_rbgs, C.c_int32), _p(res.rbg_to_user, C.c_int32),
                                   None, None, None, None, None, None)
+                if counted:
+                    res.sent = np.zeros((0, 2), np.int32)
                 results.append(res)
                 continue
             d = np.ascontiguousarray(kw.pop("data_to_transmit"), np.int32)
@@ -811,13 +823,45 @@ class GroupScheduler:
             assert d.shape == (tin.n_users, 2)
             ins[k], outs[k] = tin, tout
             data[k] = _p(d, C.c_int32)
+            if counted:
+                res.sent = np.zeros((tin.n_users, 2), np.int32)
+                sent[k] = _p(res.sent, C.c_int32)
             results.append(res)
             keep.append((arrays, d))
         t = np.ascontiguousarray(np.broadcast_to(np.asarray(now, np.float64), (n,)))
         ids = None if cell_ids is None else np.ascontiguousarray(cell_ids, np.int32)
         assert ids is None or ids.shape == (n,)
-        _check(lib().rs_group_schedule_tti_queued(self._h, n, _p(ids, C.c_int32) if ids is not None else None, ins, outs, _p(t, C.c_double), data))
+        idp = _p(ids, C.c_int32) if ids is not None else None
+        if counted:
+            _check(lib().rs_group_schedule_tti_counted(self._h, n, idp, ins, outs, _p(t, C.c_double), data, sent))
+        else:
+            _check(lib().rs_group_schedule_tti_queued(self._h, n, idp, ins, outs, _p(t, C.c_double), data))
         return results
+
+    # ---- counted bearers: m_cumulateBytes / m_cumulateRBs of a bearer-resident cell stay on the device too ----
+    def set_counters(self, cell, cum_bytes=None, cum_rbs=None):
+        """rs_group_set_counters: makes a bearer-resident `cell` counted with cum_bytes / cum_rbs int64 [n_users][2] by user id and
+        bearer priority (None: zeros).  Any time between two calls; outside the fast path."""
+        U = self.slices.n_users
+        cb = None if cum_bytes is None else np.ascontiguousarray(cum_bytes, np.int64)
+        cr = None if cum_rbs is None else np.ascontiguousarray(cum_rbs, np.int64)
+        assert (cb is None or cb.shape == (U, 2)) and (cr is None or cr.shape == (U, 2))
+        _check(lib().rs_group_set_counters(self._h, cell, _p(cb, C.c_int64) if cb is not None else None,
+                                           _p(cr, C.c_int64) if cr is not None else None))
+
+    def get_counters(self, cell):
+        """(cum_bytes int64 [n_users][2], cum_rbs int64 [n_users][2]) of a counted cell: a synchronising copy, not part of a TTI."""
+        U = self.slices.n_users
+        cb = np.zeros((U, 2), np.int64)
+        cr = np.zeros((U, 2), np.int64)
+        _check(lib().rs_group_get_counters(self._h, cell, _p(cb, C.c_int64), _p(cr, C.c_int64)))
+        return cb, cr
+
+    def schedule_tti_counted(self, calls: Sequence[dict], now, cell_ids: Optional[Sequence[int]] = None) -> List[TtiResult]:
+        """rs_group_schedule_tti_counted: schedule_tti_queued for counted cells, same calls and same results; each bearer credited also
+        adds the bytes and the position's PRBs to its counters, and every TtiResult carries .sent [n][2], the bytes sent per call
+        position and bearer (what a binding hands to UpdateTransmittedBytes and the RLC); an update-only slot gives an empty array."""
+        return self._schedule_queued(calls, now, cell_ids, True)
 
     def slice_offset(self, cell):
         out = np.zeros(self.slices.n_slices, np.float64)

@@ -2473,6 +2473,15 @@ struct rs_group {
   int qchk_left[2] = {0, 0}, qchk_agreed[2] = {0, 0};
   uint8_t* d_qchk = nullptr;
   char qjit_msg[512] = "";
+  /* counted bearers (rs_group_set_counters, rs_group_schedule_tti_counted): per cell [U][2] m_cumulateBytes / m_cumulateRBs beside the
+   * bearer stores (allocated by the first rs_group_set_counters), and which cells are counted -- a state on top of resident[cell] == 2.
+   * The slots' sent rows come back in a pinned block of their own (h_sent: [n_cells][U][2], mapped: z_sent, else copied from d_sent),
+   * as the data words travel in h_qin.  Counted calls run the built-in counted kernel: no run-time build of this form. */
+  int64_t *d_cbytes = nullptr, *d_crbs = nullptr;
+  int32_t *h_sent = nullptr, *z_sent = nullptr, *d_sent = nullptr;
+  std::vector<uint8_t> counted;
+  bool last_call_counted = false;
+  char kname_cnt[56] = "";
 };
 
 namespace {
@@ -2561,8 +2570,10 @@ rs_group* rs_group_create(const rs_config* cfg, int32_t n_cells) {
   snprintf(g->kname, sizeof g->kname, "rs_group_kernel<%d, %d>", b->sched, sorts && ept <= 4 ? ept : 0);
   snprintf(g->kname_res, sizeof g->kname_res, "rs_group_resident_kernel<%d, %d>", b->sched, sorts && ept <= 4 ? ept : 0);
   snprintf(g->kname_que, sizeof g->kname_que, "rs_group_queued_kernel<%d, %d>", b->sched, b->sched == RS_SCHED_MAXCELL && ept <= 4 ? ept : 0);
+  snprintf(g->kname_cnt, sizeof g->kname_cnt, "rs_group_counted_kernel<%d, %d>", b->sched, b->sched == RS_SCHED_MAXCELL && ept <= 4 ? ept : 0);
   g->empty_slot.assign(n_cells, 0);
   g->resident.assign(n_cells, 0);
+  g->counted.assign(n_cells, 0);
   g->pending_zero.assign(n_cells, 0);
   g->last_update.assign(n_cells, 0.0);
   g_err[0] = 0;
@@ -2596,6 +2607,10 @@ void rs_group_destroy(rs_group* g) {
   if (g->d_qhas) (void)hipFree(g->d_qhas);
   if (g->d_qin) (void)hipFree(g->d_qin);
   if (g->h_qin) (void)hipHostFree(g->h_qin);
+  if (g->d_cbytes) (void)hipFree(g->d_cbytes);
+  if (g->d_crbs) (void)hipFree(g->d_crbs);
+  if (g->d_sent) (void)hipFree(g->d_sent);
+  if (g->h_sent) (void)hipHostFree(g->h_sent);
   if (g->h_in) (void)hipHostFree(g->h_in);
   if (g->h_out) (void)hipHostFree(g->h_out);
   rs_batch_destroy(g->b);
@@ -2604,6 +2619,7 @@ void rs_group_destroy(rs_group* g) {
 
 extern "C" hipError_t rs_launch_group_resident(const RsLaunch* p, int threads, hipStream_t stream);
 extern "C" hipError_t rs_launch_group_queued(const RsLaunch* p, int threads, hipStream_t stream);
+extern "C" hipError_t rs_launch_group_counted(const RsLaunch* p, int threads, hipStream_t stream);
 
 namespace {
 /* Resident averages and the FP32 filter.  The metric scan's filter needs (1 + a) / 1000 (scheduler 1: a) inside [2^-60, 2^60] for every
@@ -2630,7 +2646,7 @@ constexpr double kBearerAvgMax = 0x1p51;
 enum { kGroupPlain = 0, kGroupResident = 1, kGroupQueued = 2 };
 
 int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out, const double* now,
-                   const int32_t* const* qdata = nullptr);
+                   const int32_t* const* qdata = nullptr, bool cnt = false, int32_t* const* sent = nullptr);
 }  // namespace
 
 int rs_group_schedule_tti(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out) {
@@ -2649,10 +2665,17 @@ int rs_group_schedule_tti_queued(rs_group* g, int32_t n, const int32_t* cell_ids
   return group_schedule(g, n, cell_ids, in, out, now, data_to_transmit);
 }
 
+int rs_group_schedule_tti_counted(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out, const double* now,
+                                  const int32_t* const* data_to_transmit, int32_t* const* sent) {
+  if (!g || !in || !out || !now || !data_to_transmit) return fail(RS_ERR_INVALID, "null argument");
+  return group_schedule(g, n, cell_ids, in, out, now, data_to_transmit, true, sent);
+}
+
 namespace {
-/* one group call; now != null: a resident form -- averages (rs_group_schedule_tti_at) or, with qdata, bearers (rs_group_schedule_tti_queued) */
+/* one group call; now != null: a resident form -- averages (rs_group_schedule_tti_at) or, with qdata, bearers (rs_group_schedule_tti_queued;
+ * cnt: its counted twin, rs_group_schedule_tti_counted, which differs in the kernel it launches, the two counter stores and the sent rows) */
 int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out, const double* now,
-                   const int32_t* const* qdata) {
+                   const int32_t* const* qdata, bool cnt, int32_t* const* sent) {
   rs_batch* b = g->b;
   const bool res = now != nullptr, que = qdata != nullptr;
   const int kind = que ? kGroupQueued : (res ? kGroupResident : kGroupPlain);
@@ -2699,6 +2722,7 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
       const int cell = cell_ids ? cell_ids[k] : k;
       if (in[k].avg_rate) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): avg_rate must be NULL: the cell's averages are resident on the device", k, cell);
       if (que && g->resident[cell] != 2) return fail(RS_ERR_STATE, "cell slot %d: cell %d is not bearer-resident (rs_group_set_bearers first)", k, cell);
+      if (cnt && !g->counted[cell]) return fail(RS_ERR_STATE, "cell slot %d: cell %d is not counted (rs_group_set_counters first)", k, cell);
       if (!que && g->resident[cell] == 2)
         return fail(RS_ERR_STATE, "cell slot %d: cell %d is bearer-resident (rs_group_set_bearers): rs_group_schedule_tti_queued serves it, or rs_group_set_avg makes it average-resident", k, cell);
       if (!g->resident[cell]) return fail(RS_ERR_STATE, "cell slot %d: cell %d is not resident (rs_group_set_avg first)", k, cell);
@@ -2808,6 +2832,7 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
       if (!ok) for (int k = 0; k < n; k++) {
         g->img[ids ? ids[k] : k].valid = false;
         if (res) g->resident[ids ? ids[k] : k] = 0; /* (averages half updated, perhaps: resident again with rs_group_set_avg) */
+        if (res) g->counted[ids ? ids[k] : k] = 0;  /* (neither resident nor counted) */
       }
     }
   } guard{g, n, cell_ids, false, res};
@@ -2861,6 +2886,12 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
     L.grp_qin = g->z_qin ? g->z_qin : g->d_qin;
     L.grp_qin_stride = 2 * (int64_t)b->U;
   }
+  if (cnt) {
+    L.grp_cbytes = g->d_cbytes;
+    L.grp_crbs = g->d_crbs;
+    L.grp_sent = g->z_sent ? g->z_sent : g->d_sent;
+    L.grp_sent_stride = 2 * (int64_t)b->U;
+  }
   bool poll = zc && g->poll;
   if (poll) {
     if (++g->seq == 0) g->seq = 1; /* (0 is the word's initial value) */
@@ -2876,9 +2907,9 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
   RsJitKernel** const pair = que ? g->qjit : (res ? g->rjit : g->jit);
   int* const chk_left = que ? g->qchk_left : (res ? g->rchk_left : g->chk_left);
   int* const chk_agreed = que ? g->qchk_agreed : (res ? g->rchk_agreed : g->chk_agreed);
-  RsJitKernel* kd = pair[0];
+  RsJitKernel* kd = cnt ? nullptr : pair[0]; /* (a counted call: the built-in counted kernel, whatever rs_group_specialize_queued built) */
   int which = 0;
-  if (pair[1] && !has_prb && !L.queue_mode && !has_gate && !L.exact_scan && !L.gen_exp && !want_upper && !L.synthetic) { kd = pair[1]; which = 1; }
+  if (!cnt && pair[1] && !has_prb && !L.queue_mode && !has_gate && !L.exact_scan && !L.gen_exp && !want_upper && !L.synthetic) { kd = pair[1]; which = 1; }
   /* A build without the self-check mark serves its first calls beside the built-in kernel of its kind (rs_group_jit_status,
    * rs_group_resident_jit_status): same slots, same state; every named cell's output fields and the state left behind must agree --
    * the slice state, for a resident call the averages of every user id, the pending bytes and the last-update time, and for a queued
@@ -2940,6 +2971,7 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
     L.done_flag = nullptr; /* completion by the stream */
   }
   if (kd) HIP_TRY(rs_jit_launch(kd, &L, st));
+  else if (cnt) HIP_TRY(rs_launch_group_counted(&L, b->threads, st));
   else if (que) HIP_TRY(rs_launch_group_queued(&L, b->threads, st));
   else if (res) HIP_TRY(rs_launch_group_resident(&L, b->threads, st));
   else HIP_TRY(rs_launch_group(&L, b->threads, st));
@@ -2948,7 +2980,9 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
   g->last_call_resident = res;
   g->last_call_rjit = res && !que && kd != nullptr;
   g->last_call_qjit = que && kd != nullptr;
+  g->last_call_counted = cnt;
   if (!zc) HIP_TRY(hipMemcpyAsync(g->h_out, g->d_out, (size_t)n * g->out_stride, hipMemcpyDeviceToHost, st));
+  if (cnt && !g->z_sent) HIP_TRY(hipMemcpyAsync(g->h_sent, g->d_sent, 8 * (size_t)n * b->U, hipMemcpyDeviceToHost, st));
   const clk::time_point t2 = g->timing ? clk::now() : clk::time_point();
   bool seen = false;
   if (checked_call) poll = false;
@@ -3147,6 +3181,8 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
       continue;
     }
     unpack_tti(b, &in[k], &out[k], g->h_out + (size_t)k * g->out_stride, g->packs[k].l, want_upper);
+    /* (a counted call: the slot's sent rows, [n_users][2] in call order, written by the threads that credited the positions) */
+    if (cnt && sent && sent[k]) memcpy(sent[k], g->h_sent + (size_t)k * 2 * (size_t)b->U, 8 * (size_t)in[k].n_users);
   }
   if (g->timing) {
     const clk::time_point t4 = clk::now();
@@ -3205,6 +3241,7 @@ int rs_group_set_avg(rs_group* g, int32_t cell, const double* avg, double last_u
     }
   }
   HIP_TRY(hipStreamSynchronize(b->stream));
+  g->counted[cell] = 0; /* (the cell leaves the bearer form: its counters' term ends) */
   g->resident[cell] = 0; /* (until all three copies are through) */
   HIP_TRY(hipMemcpy(g->d_ravg + (size_t)cell * U, avg, 8 * U, hipMemcpyHostToDevice));
   HIP_TRY(hipMemset(g->d_rpend + (size_t)cell * U, 0, 4 * U));
@@ -3321,6 +3358,60 @@ int rs_group_get_bearers(rs_group* g, int32_t cell, double* avg, int32_t* pendin
   return RS_OK;
 }
 
+int rs_group_set_counters(rs_group* g, int32_t cell, const int64_t* cum_bytes, const int64_t* cum_rbs) {
+  if (!g) return fail(RS_ERR_INVALID, "null group");
+  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
+  if (g->resident[cell] != 2) return fail(RS_ERR_STATE, "cell %d is not bearer-resident (rs_group_set_bearers first)", cell);
+  rs_batch* b = g->b;
+  const size_t U = (size_t)b->U, nb = 2 * U * (size_t)g->n_cells;
+  for (size_t i = 0; i < 2 * U; i++) {
+    if (cum_bytes && cum_bytes[i] < 0) return fail(RS_ERR_INVALID, "cum_bytes[%zu][%zu] = %lld is negative", i / 2, i % 2, (long long)cum_bytes[i]);
+    if (cum_rbs && cum_rbs[i] < 0) return fail(RS_ERR_INVALID, "cum_rbs[%zu][%zu] = %lld is negative", i / 2, i % 2, (long long)cum_rbs[i]);
+  }
+  HIP_TRY(hipSetDevice(b->cfg.cell.device));
+  if (!g->d_cbytes) {
+    bool ok = hipMalloc(&g->d_cbytes, 8 * nb) == hipSuccess && hipMalloc(&g->d_crbs, 8 * nb) == hipSuccess &&
+              hipHostMalloc((void**)&g->h_sent, 4 * nb, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
+    if (ok && g->z_out) { /* (the group's outputs are written in place: the sent rows too) */
+      void* z = nullptr;
+      if (hipHostGetDevicePointer(&z, g->h_sent, 0) == hipSuccess) g->z_sent = (int32_t*)z;
+    }
+    if (ok && !g->z_sent) ok = hipMalloc(&g->d_sent, 4 * nb) == hipSuccess;
+    if (ok) ok = hipMemset(g->d_cbytes, 0, 8 * nb) == hipSuccess && hipMemset(g->d_crbs, 0, 8 * nb) == hipSuccess;
+    if (!ok) {
+      (void)hipGetLastError();
+      for (void* q : {(void*)g->d_cbytes, (void*)g->d_crbs, (void*)g->d_sent})
+        if (q) (void)hipFree(q);
+      if (g->h_sent) (void)hipHostFree(g->h_sent);
+      g->d_cbytes = g->d_crbs = nullptr;
+      g->d_sent = g->h_sent = g->z_sent = nullptr;
+      return fail(RS_ERR_HIP, "allocation of the group's bearer counters failed (%zu bytes)", 20 * nb);
+    }
+    memset(g->h_sent, 0, 4 * nb);
+  }
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  g->counted[cell] = 0; /* (until both copies are through) */
+  if (cum_bytes) HIP_TRY(hipMemcpy(g->d_cbytes + (size_t)cell * 2 * U, cum_bytes, 16 * U, hipMemcpyHostToDevice));
+  else HIP_TRY(hipMemset(g->d_cbytes + (size_t)cell * 2 * U, 0, 16 * U));
+  if (cum_rbs) HIP_TRY(hipMemcpy(g->d_crbs + (size_t)cell * 2 * U, cum_rbs, 16 * U, hipMemcpyHostToDevice));
+  else HIP_TRY(hipMemset(g->d_crbs + (size_t)cell * 2 * U, 0, 16 * U));
+  g->counted[cell] = 1;
+  return RS_OK;
+}
+
+int rs_group_get_counters(rs_group* g, int32_t cell, int64_t* cum_bytes, int64_t* cum_rbs) {
+  if (!g) return fail(RS_ERR_INVALID, "null group");
+  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
+  if (!g->counted[cell]) return fail(RS_ERR_STATE, "cell %d is not counted (rs_group_set_counters first)", cell);
+  rs_batch* b = g->b;
+  const size_t U = (size_t)b->U;
+  HIP_TRY(hipSetDevice(b->cfg.cell.device));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  if (cum_bytes) HIP_TRY(hipMemcpy(cum_bytes, g->d_cbytes + (size_t)cell * 2 * U, 16 * U, hipMemcpyDeviceToHost));
+  if (cum_rbs) HIP_TRY(hipMemcpy(cum_rbs, g->d_crbs + (size_t)cell * 2 * U, 16 * U, hipMemcpyDeviceToHost));
+  return RS_OK;
+}
+
 int rs_group_get_slice_offset(rs_group* g, int32_t cell, double* offset) {
   if (!g || !offset) return fail(RS_ERR_INVALID, "null argument");
   if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
@@ -3353,6 +3444,7 @@ const char* rs_group_kernel_name(rs_group* g) {
   if (!g) return "";
   /* (a resident call: the group's resident builds if rs_group_specialize_resident gave it some, else the built-in resident kernel --
    * whatever serves the plain calls) */
+  if (g->last_call_kind == kGroupQueued && g->last_call_counted) return g->kname_cnt; /* (built in only: no run-time build of the counted form) */
   if (g->last_call_kind == kGroupQueued) return g->last_call_qjit ? "rs_group_queued_kernel_jit" : g->kname_que; /* (likewise: rs_group_specialize_queued) */
   if (g->last_call_resident) return g->last_call_rjit ? "rs_group_resident_kernel_jit" : g->kname_res;
   return g->jit[0] ? "rs_group_kernel_jit" : g->kname;

@@ -344,6 +344,15 @@ struct RsLaunch {
    * RS_PRIO_PERIOD TTIs); a cell whose own count times n_cells is below it is behind the average and runs boosted until the next
    * look.  nullptr: off.  Zeroed by the host before every launch. */
   unsigned long long* prio_sum;
+  /* group calls, counted bearers (rs_group_schedule_tti_counted, rs_group_counted_kernel): a bearer-resident CELL may also keep
+   * RadioBearer::m_cumulateBytes / m_cumulateRBs of both bearers of every user, indexed as the bearer stores below; grp_sent: per call
+   * SLOT, the bytes DoStopSchedule's loop sent per call position and bearer (0: not credited) -- may lie in host memory, written once.
+   * Read by the counted kernels alone; null in every other launch.  (Four words in front of the queued form's six, for the same
+   * reason.) */
+  int64_t* grp_cbytes;       /* [group cells][U][2] */
+  int64_t* grp_crbs;         /* [group cells][U][2] */
+  int32_t* grp_sent;         /* [call slots][grp_sent_stride], call order */
+  int64_t grp_sent_stride;   /* words per slot: 2 U of the config */
   /* group calls, resident bearers (rs_group_schedule_tti_queued, rs_group_queued_kernel): a CELL of the group may instead keep the
    * words of BOTH bearers of every user (MAX_BEARERS = 2, index = bearer priority) -- average, bytes credited since the last update,
    * "the bearer exists" -- indexed [user id][bearer], one stride of 2 U apart; grp_last, grp_gather and grp_uid below serve this form

@@ -778,7 +778,7 @@ template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
   constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
-  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = false;
+  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = false, kGrpCnt = false;
 #include "rs_phase_group.inc"
 }
 
@@ -789,7 +789,7 @@ template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_resident_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
   constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
-  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = true, kGrpQue = false;
+  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = true, kGrpQue = false, kGrpCnt = false;
 #include "rs_phase_group.inc"
 }
 
@@ -801,7 +801,18 @@ template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_queued_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
   constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
-  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = true;
+  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = true, kGrpCnt = false;
+#include "rs_phase_group.inc"
+}
+
+/* ... and the queued form's counted twin (rs_group_schedule_tti_counted): the cell's bearers also keep m_cumulateBytes / m_cumulateRBs
+ * on the device, and the slot gets back the bytes sent per call position and bearer.  Kernels of their own, the queued form's nine
+ * shapes (rs_launch_group_counted): the queued kernels above carry none of it.  Built in only: no run-time build of this form. */
+template <int SCHED, int EPT>
+__global__ void __launch_bounds__(512, 4) rs_group_counted_kernel(RsLaunch p) {
+  extern __shared__ __align__(16) unsigned char lds[];
+  constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
+  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = true, kGrpCnt = true;
 #include "rs_phase_group.inc"
 }
 #else
@@ -854,7 +865,7 @@ extern "C" __global__ void __launch_bounds__(RS_JIT_NT, RS_JIT_WPE) RS_GROUP_JIT
   constexpr RsCarve kCv = rs_carve(RS_JIT_S, RS_JIT_U, RS_JIT_R, RS_JIT_SCHED, RS_JIT_NT, RS_JIT_CARVEQ, RS_JIT_WIN);
   __shared__ __align__(16) unsigned char lds[kCv.lds_bytes];
   constexpr int kGrpSched = RS_JIT_SCHED, kGrpEpt = (RS_JIT_SCHED != 9 && RS_JIT_SCHED != 10) ? 0 : (kCv.ept <= 4 ? kCv.ept : 0);
-  constexpr bool kGrpFixed = true, kGrpRes = RS_JIT_GROUP_RESIDENT != 0, kGrpQue = RS_JIT_GROUP_QUEUED != 0;
+  constexpr bool kGrpFixed = true, kGrpRes = RS_JIT_GROUP_RESIDENT != 0, kGrpQue = RS_JIT_GROUP_QUEUED != 0, kGrpCnt = false;
 #include "rs_phase_group.inc"
 }
 #undef RS_GROUP_JIT_ENTRY
@@ -1103,6 +1114,32 @@ extern "C" hipError_t rs_launch_group_queued(const RsLaunch* p, int threads, hip
   return hipGetLastError();
 }
 
+/* a counted group call (rs_group_schedule_tti_counted): the queued call's grid and stores, the kernels that also keep the counters */
+extern "C" hipError_t rs_launch_group_counted(const RsLaunch* p, int threads, hipStream_t stream) {
+  dim3 grid(p->n_cells), block(threads);
+  const int ept = (p->R * p->S + threads - 1) / threads;
+  if (!p->grp_qavg || !p->grp_qpend || !p->grp_qhas || !p->grp_qdata || !p->grp_qin || !p->grp_last || !p->grp_gather || !p->grp_uid ||
+      !p->grp_cbytes || !p->grp_crbs || !p->grp_sent)
+    return hipErrorInvalidValue;
+#define RS_LAUNCH_GROUP(SCHED_, EPT_) hipLaunchKernelGGL((rs_group_counted_kernel<SCHED_, EPT_>), grid, block, p->lds_bytes, stream, *p)
+  switch (p->sched) {
+    case 7: RS_LAUNCH_GROUP(7, 0); break;
+    case 8: RS_LAUNCH_GROUP(8, 0); break;
+    case 101: RS_LAUNCH_GROUP(101, 0); break;
+    case 103: RS_LAUNCH_GROUP(103, 0); break;
+    case 9:
+      if (ept <= 1) RS_LAUNCH_GROUP(9, 1);
+      else if (ept <= 2) RS_LAUNCH_GROUP(9, 2);
+      else if (ept <= 3) RS_LAUNCH_GROUP(9, 3);
+      else if (ept <= 4) RS_LAUNCH_GROUP(9, 4);
+      else RS_LAUNCH_GROUP(9, 0);
+      break;
+    default: return hipErrorInvalidValue;
+  }
+#undef RS_LAUNCH_GROUP
+  return hipGetLastError();
+}
+
 extern "C" hipError_t rs_prepare_kernels(int max_lds_bytes) {
 #define RS_BOTH(SCHED_, EPT_) (const void*)rs_cell_kernel<SCHED_, EPT_, false>, (const void*)rs_cell_kernel<SCHED_, EPT_, true>
   const void* fns[] = {RS_BOTH(1, 0),  RS_BOTH(7, 0),  RS_BOTH(8, 0),  RS_BOTH(101, 0), RS_BOTH(103, 0), RS_BOTH(11, 0),
@@ -1129,7 +1166,12 @@ extern "C" hipError_t rs_prepare_kernels(int max_lds_bytes) {
                        (const void*)rs_group_queued_kernel<101, 0>, (const void*)rs_group_queued_kernel<103, 0>,
                        (const void*)rs_group_queued_kernel<9, 0>,   (const void*)rs_group_queued_kernel<9, 1>,
                        (const void*)rs_group_queued_kernel<9, 2>,   (const void*)rs_group_queued_kernel<9, 3>,
-                       (const void*)rs_group_queued_kernel<9, 4>};
+                       (const void*)rs_group_queued_kernel<9, 4>,
+                       (const void*)rs_group_counted_kernel<7, 0>,   (const void*)rs_group_counted_kernel<8, 0>,
+                       (const void*)rs_group_counted_kernel<101, 0>, (const void*)rs_group_counted_kernel<103, 0>,
+                       (const void*)rs_group_counted_kernel<9, 0>,   (const void*)rs_group_counted_kernel<9, 1>,
+                       (const void*)rs_group_counted_kernel<9, 2>,   (const void*)rs_group_counted_kernel<9, 3>,
+                       (const void*)rs_group_counted_kernel<9, 4>};
 #undef RS_BOTH
 
   for (const void* f : fns) {

@@ -7,7 +7,7 @@
  * sequence number to the host.  Its acquire of the counter orders it behind every other workgroup's fence and release.
  *
  * The entry points of rs_kernels.hip include this text as their body, as rs_cell_body includes its phases: the kernels built into the
- * library (rs_group_kernel, rs_group_resident_kernel, rs_group_queued_kernel: shape in the launch block) and a group's own run-time
+ * library (rs_group_kernel, rs_group_resident_kernel, rs_group_queued_kernel, rs_group_counted_kernel: shape in the launch block) and a group's own run-time
  * builds (rs_group_kernel_jit, rs_group_specialize; rs_group_resident_kernel_jit, rs_group_specialize_resident;
  * rs_group_queued_kernel_jit, rs_group_specialize_queued).
  * The includer provides `p` (the launch block), `lds` and four constants: kGrpSched, kGrpEpt, kGrpFixed -- shape, workgroup size and LDS
@@ -31,7 +31,16 @@
  * without users (U = 0 in its header) does the update alone: the body and the credit are skipped, uniformly for the workgroup.  With
  * kGrpQue false none of this text reaches the other instantiations.  Under kGrpFixed (rs_group_queued_kernel_jit) the queued text's
  * shape is constant as the resident text's: the update's range and the strides of the [U][2] stores are 2 * RS_JIT_U, the loop strides
- * RS_JIT_NT, the grants' LDS offset the constexpr carve's off_tx.  Order of operations and arithmetic are the same in both forms. */
+ * RS_JIT_NT, the grants' LDS offset the constexpr carve's off_tx.  Order of operations and arithmetic are the same in both forms.
+ *
+ * A seventh constant, kGrpCnt, makes the counted form (rs_group_schedule_tti_counted, rs_group_counted_kernel; only with kGrpQue, built
+ * in only): the cell also keeps m_cumulateBytes / m_cumulateRBs of both bearers of every user, and the slot gets back the bytes sent
+ * per call position and bearer.  All of it sits in step 4's per-position loop: the thread that credits a bearer adds the bytes and the
+ * position's allocated PRBs to the bearer's 64-bit counters and writes the position's row of the slot's sent block.  The PRB count is
+ * G times the RBGs the position holds -- the body's link adaptation leaves, per call position, the set of RBG lanes that share it in
+ * RsMisc::maskA / maskB (rs_phase_p5.inc), and the closing barrier hands them to every thread as it hands over the grants.  With kGrpCnt
+ * false none of this text reaches the other instantiations. */
+  static_assert(!kGrpCnt || (kGrpQue && !kGrpFixed), "the counted form is the queued form's, and built in only");
   const uint8_t* const in = p.grp_in + (size_t)blockIdx.x * (size_t)p.grp_in_stride;
   uint8_t* const out = p.grp_out + (size_t)blockIdx.x * (size_t)p.grp_out_stride;
   const RsGroupCell* const h = (const RsGroupCell*)in;
@@ -214,10 +223,26 @@
       int32_t* const b_pend = p.grp_qpend + (size_t)cell * 2 * (size_t)n_all;
       const int32_t* const ids = p.grp_uid + (size_t)cell * (size_t)n_all;    /* entry i: written by this thread before the body */
       const int32_t* const keep = p.grp_qdata + (size_t)cell * 2 * (size_t)n_all; /* entries 2i, 2i + 1: likewise */
+      /* (the counted form: the cell's counters, the slot's sent rows -- zero-copy: in host memory, written once per position --, and
+       * where the body's link adaptation left the RBG lanes of every call position) */
+      int64_t* const c_bytes = kGrpCnt ? p.grp_cbytes + (size_t)cell * 2 * (size_t)n_all : nullptr;
+      int64_t* const c_rbs = kGrpCnt ? p.grp_crbs + (size_t)cell * 2 * (size_t)n_all : nullptr;
+      int32_t* const srow = kGrpCnt ? p.grp_sent + (size_t)blockIdx.x * (size_t)p.grp_sent_stride : nullptr;
+      const RsMisc* const cm = (const RsMisc*)(lds + p.off_misc);
       for (int i = threadIdx.x; i < q.U; i += nthreads) {
         int available = granted[i];
-        if (available <= 0) continue;
+        if (available <= 0) {
+          if constexpr (kGrpCnt) *(int2*)(srow + 2 * i) = make_int2(0, 0); /* no grant: no counter moves, the row says so */
+          continue;
+        }
         const int id = ids[i];
+        [[maybe_unused]] int row_sent[2] = {0, 0};
+        [[maybe_unused]] int64_t nprb = 0;
+        if constexpr (kGrpCnt) {
+          /* GetListOfAllocatedRBs()->size(): owner + 1 = i + 1 in two base-64 digits, the lanes that share both hold the position's RBGs */
+          const unsigned long long lanes = cm->maskA[(i + 1) & 63] & cm->maskB[(i + 1) >> 6];
+          nprb = (int64_t)(__popcll(lanes) * p.G);
+        }
         for (int b = 1; b >= 0; --b) {
           if (available <= 0) break;
           const int d = keep[2 * i + b];
@@ -232,8 +257,14 @@
 #else
             b_pend[2 * id + b] += sent;
 #endif
+            if constexpr (kGrpCnt) { /* a user is named once per call, a cell once per launch: plain 64-bit adds by the position's thread */
+              c_bytes[2 * id + b] += (int64_t)sent;
+              c_rbs[2 * id + b] += nprb;
+              row_sent[b] = sent;
+            }
           }
         }
+        if constexpr (kGrpCnt) *(int2*)(srow + 2 * i) = make_int2(row_sent[0], row_sent[1]);
       }
     }
   }

@@ -212,6 +212,13 @@ class BearerLogWriter:
         self.starts = starts
         self.next_start = 0
 
+    @staticmethod
+    def counter_line(ts, app, cum_bytes, cum_rbs, hol, user, slice_id, flow_format: bool = False) -> str:
+        """DoStopSchedule's line of one credited bearer, counters as they are after the credit."""
+        line = (f"{ts} {'flow' if flow_format else 'app'}: {app} cumu_bytes: {cum_bytes} "
+                f"cumu_rbs: {cum_rbs} hol_delay: {fmt_double(hol)}")
+        return line if flow_format else f"{line} user: {user} slice: {slice_id}"
+
     def lines(self, bearer_bytes, bearer_hol, bearer_rbs, t_first: float, done=None) -> List[str]:
         """One launch: bearer_bytes / bearer_hol / bearer_rbs [n_ttis][U][2] (run_logged(bearers=True), bearer_prbs), t_first = the
         batch clock before the launch (BatchScheduler.clock()[0][cell]; t_{k+1} = t_k + 0.001), done = {(user, prio): (done_tti,
@@ -242,15 +249,40 @@ class BearerLogWriter:
                     if by > 0:
                         self.cb[u, k] += by
                         self.cr[u, k] += int(bearer_rbs[j, u, k])
-                        line = (f"{ts} {'flow' if self.flow_format else 'app'}: {self.app_of[u, k]} cumu_bytes: {self.cb[u, k]} "
-                                f"cumu_rbs: {self.cr[u, k]} hol_delay: {fmt_double(bearer_hol[j, u, k])}")
-                        out.append(line if self.flow_format else f"{line} user: {u} slice: {self.u2s[u]}")
+                        out.append(self.counter_line(ts, self.app_of[u, k], self.cb[u, k], self.cr[u, k], bearer_hol[j, u, k], u,
+                                                     self.u2s[u], self.flow_format))
                     for i, dtime in sorted(ends.get((j, int(u), k), [])):
                         t, size = self.flows[(int(u), k)]
                         out.append(f"ipflow end app: {self.app_of[u, k]} flow: {i} fct: {fmt_double(dtime - t[i])} "
                                    f"flowsize: {int(size[i])} priority: {k}")
         self.tti = g0 + n
         return out
+
+
+def counted_call_lines(ts: int, ids, sent, hol_delay, cum_bytes, cum_rbs, app_of, user_to_slice) -> List[str]:
+    """The reference's "app:" lines of ONE cell's slot of a counted group call (GroupScheduler.schedule_tti_counted): one line per
+    bearer the call credited, in DoStopSchedule's order -- users ascending by id, bearer 1 before 0 -- in BearerLogWriter's format.
+    ts: the TTI's stamp; ids [n]: the call's user ids in call order (None: 0..n-1); sent [n][2]: the result's .sent; hol_delay: the
+    bearers' GetHeadOfLinePacketDelay as the caller knows them, [n][2], or [n] (one value per position, printed for either bearer),
+    or None (0: InfiniteBuffer bearers); cum_bytes / cum_rbs [U][2] by user id: the cell's counters AFTER the call, read back
+    (get_counters) or tracked from .sent and user_nprb; app_of: app_ids(slices); user_to_slice: the slice map."""
+    sent = np.asarray(sent).reshape(-1, 2)
+    n = sent.shape[0]
+    ids = np.arange(n) if ids is None else np.asarray(ids)
+    assert ids.shape == (n,)
+    hol = np.zeros((n, 2)) if hol_delay is None else np.asarray(hol_delay, np.float64)
+    if hol.ndim == 1:
+        hol = np.repeat(hol[:, None], 2, axis=1)
+    assert hol.shape == (n, 2)
+    cum_bytes, cum_rbs, app_of = np.asarray(cum_bytes), np.asarray(cum_rbs), np.asarray(app_of)
+    out = []
+    for i in np.argsort(ids, kind="stable"):
+        u = int(ids[i])
+        for k in (1, 0):
+            if sent[i, k] > 0:
+                out.append(BearerLogWriter.counter_line(ts, app_of[u, k], int(cum_bytes[u, k]), int(cum_rbs[u, k]), hol[i, k], u,
+                                                        user_to_slice[u]))
+    return out
 
 
 # reducers of the customised-slice experiment (what exp-customization/plot_fctdelay.py computes from a run's stderr)

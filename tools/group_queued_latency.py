@@ -3,12 +3,15 @@
 call followed by rs_group_set_pending per cell -- and, as the regression check, the plain and the resident call, which another
 checkout can be measured on as well (profiles/group_queued.md).
 
-    python tools/group_queued_latency.py [--variant plain|resident|resident+pending|queued|queued-spec|all] [--calls 300]
+    python tools/group_queued_latency.py [--variant plain|resident|resident+pending|queued|queued-spec|queued+host|counted|all] [--calls 300]
     RS_TREE=<another checkout> python tools/group_queued_latency.py --variant plain     # that tree's package
     python tools/group_queued_latency.py --variant queued-spec --cells 27 --shapes 500x25x4 500x64x8 --sched 9 7
 
 queued-spec: the queued call after rs_group_specialize_queued (profiles/group_queued_specialize.md); its warm-up holds the builds'
-checked calls.  Workloads by default: 8 and 64 cells; 500 users x 25 RBGs and 100 users x 64 RBGs; scheduler 9; cqi_epoch on (new
+checked calls.  queued+host: the queued call followed by what a binding did on the CPU before rs_group_schedule_tti_counted --
+DoStopSchedule's credit loop restated in numpy from user_tbs_bits and the data words, and the per-bearer byte and RB counters kept in
+host arrays; counted: the counted call, which returns the bytes sent and keeps the counters on the device
+(profiles/group_counted.md).  Workloads by default: 8 and 64 cells; 500 users x 25 RBGs and 100 users x 64 RBGs; scheduler 9; cqi_epoch on (new
 reports every 40 calls).  --shapes takes users x RBGs x PRBs per RBG (20 equal slices).  Scheduler 7 names the users of one slice per
 call, the slice rotating with the call, and gives no required_rbs.  Timed through the Python layer, marshalling included, like
 tools/group_resident_latency.py: three repetitions per line, whose spread is the yardstick for a difference between lines; p50 / p99
@@ -24,7 +27,20 @@ import numpy as np
 sys.path.insert(0, os.environ.get("RS_TREE", str(Path(__file__).resolve().parents[1])))
 import radiosaber_amd as rs  # noqa: E402
 
-VARIANTS = ("plain", "resident", "resident+pending", "queued", "queued-spec")
+VARIANTS = ("plain", "resident", "resident+pending", "queued", "queued-spec", "queued+host", "counted")
+
+
+def host_credit(res, data, ids, cum_bytes, cum_rbs):
+    """DoStopSchedule's loop of one slot on the host, vectorised over the call positions: bearer 1 first, min(available, data) each,
+    then m_cumulateBytes / m_cumulateRBs of the credited bearers"""
+    available = res.user_tbs_bits // 8
+    sent = np.zeros_like(data)
+    sent[:, 1] = np.minimum(available, data[:, 1])
+    sent[:, 0] = np.minimum(available - sent[:, 1], data[:, 0])
+    rows = slice(None) if ids is None else ids
+    cum_bytes[rows] += sent
+    cum_rbs[rows] += np.where(sent > 0, res.user_nprb[:, None], 0)
+    return sent
 ap = argparse.ArgumentParser()
 ap.add_argument("--variant", default="all", choices=VARIANTS + ("all",))
 ap.add_argument("--calls", type=int, default=300)
@@ -43,6 +59,8 @@ for sched, shape in ((s, x) for s in args.sched for x in args.shapes):
         for variant in (VARIANTS if args.variant == "all" else (args.variant,)):
             if variant == "queued-spec" and not hasattr(rs.GroupScheduler, "specialize_queued"):
                 continue  # (RS_TREE names a checkout from before rs_group_specialize_queued)
+            if variant == "counted" and not hasattr(rs.GroupScheduler, "schedule_tti_counted"):
+                continue  # (... from before rs_group_schedule_tti_counted)
             g = rs.GroupScheduler(sc, R, G, K, sched=sched)
             if variant == "queued-spec":
                 g.specialize_queued()
@@ -54,8 +72,12 @@ for sched, shape in ((s, x) for s in args.sched for x in args.shapes):
             for k in range(K):
                 if variant in ("resident", "resident+pending"):
                     g.set_avg(k, avg[k], 0.1)
-                if variant in ("queued", "queued-spec"):
+                if variant in ("queued", "queued-spec", "queued+host", "counted"):
                     g.set_bearers(k, np.ones((U, 2), bool), np.stack([avg[k], avg[k][::-1]], axis=1), 0.1)
+                if variant == "counted":
+                    g.set_counters(k)
+            host_bytes = [np.zeros((U, 2), np.int64) for _ in range(K)]
+            host_rbs = [np.zeros((U, 2), np.int64) for _ in range(K)]
             now, best, each = 0.1, [], []
             for rep in range(3):
                 t0 = 0.0
@@ -74,10 +96,16 @@ for sched, shape in ((s, x) for s in args.sched for x in args.shapes):
                         for k in range(K):
                             calls[k]["avg_rate"] = avg[k]
                         g.schedule_tti(calls)
-                    elif variant in ("queued", "queued-spec"):
+                    elif variant in ("queued", "queued-spec", "queued+host", "counted"):
                         for k in range(K):
                             calls[k]["data_to_transmit"] = data if ids is None else data[ids]
-                        g.schedule_tti_queued(calls, now)
+                        if variant == "counted":
+                            g.schedule_tti_counted(calls, now)
+                        else:
+                            res = g.schedule_tti_queued(calls, now)
+                            if variant == "queued+host":
+                                for k in range(K):
+                                    host_credit(res[k], calls[k]["data_to_transmit"], ids, host_bytes[k], host_rbs[k])
                     else:
                         g.schedule_tti_at(calls, now)
                         if variant == "resident+pending":
