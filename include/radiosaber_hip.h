@@ -33,7 +33,8 @@ extern "C" {
                                rs_group_specialize_resident / rs_group_resident_jit_status / rs_jit_selfcheck_group_resident (a group's own builds of the resident kernel, self-checked on state),
                                rs_group_set_bearers / rs_group_get_bearers / rs_group_schedule_tti_queued (a group cell's two bearers per user resident on the device: finite queues credited there),
                                rs_group_specialize_queued / rs_group_queued_jit_status / rs_jit_selfcheck_group_queued (a group's own builds of the queued kernel, self-checked on the bearer stores),
-                               rs_group_set_counters / rs_group_get_counters / rs_group_schedule_tti_counted (a bearer-resident group cell's m_cumulateBytes / m_cumulateRBs on the device, the bytes sent per bearer returned per call);
+                               rs_group_set_counters / rs_group_get_counters / rs_group_schedule_tti_counted (a bearer-resident group cell's m_cumulateBytes / m_cumulateRBs on the device, the bytes sent per bearer returned per call),
+                               rs_group_set_flows / rs_group_get_flows / rs_group_schedule_tti_flows (scheduler 1's flows of a group cell resident on the device: averages, pending bytes and counters per bearer, the whole block credited to the flow);
                                rs_config.link_tables (RS_LINK_*) + rs_link_tables_pinned / rs_link_tables_compare, rs_tti_in.cqi_epoch (the context keeps the
                                CQI image of an unchanged report set on the device), rs_ctx_jit_status (a specialised context checks its run-time build against the
                                built-in kernel during its first calls), rs_batch_config.selfcheck -1 / 0 / 1 with run-time builds verified by default and the
@@ -318,7 +319,8 @@ int rs_group_image_stats(const rs_group* g, int64_t out[3]);
  * served it (rs_group_specialize_resident), else the built-in "rs_group_resident_kernel<sched, ept>".  While it was a queued one:
  * "rs_group_queued_kernel_jit" if the group's queued builds served it (rs_group_specialize_queued), else the built-in
  * "rs_group_queued_kernel<sched, ept>".  While it was a counted one (rs_group_schedule_tti_counted): the built-in
- * "rs_group_counted_kernel<sched, ept>". */
+ * "rs_group_counted_kernel<sched, ept>".  While it was a flows one (rs_group_schedule_tti_flows): the built-in
+ * "rs_group_flows_kernel<1, 0>". */
 const char* rs_group_kernel_name(rs_group* g);
 /* Optional, at any time between two calls: rs_ctx_specialize for a group -- the one-TTI kernel compiled for the config's slices, RBGs,
  * PRBs per RBG, scheduler, workgroup size and user capacity (hiprtc, ~2 s per build and process, cached on disk apart from the
@@ -512,6 +514,42 @@ int rs_group_get_counters(rs_group* g, int32_t cell, int64_t* cum_bytes /* [U][2
 int rs_group_schedule_tti_counted(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in /* [n] */, rs_tti_out* out /* [n] */,
                                   const double* now /* [n] */, const int32_t* const* data_to_transmit /* [n]: [in[k].n_users][2] */,
                                   int32_t* const* sent /* [n]: [in[k].n_users][2]; NULL, or NULL per update-only slot */);
+
+/* Resident flows (ABI 11 addition, no layout changed): RS_SCHED_PF alone.  DL_PF_PacketScheduler races FLOWS -- bearers with data, in
+ * RRC-container order --, divides by the flow's own average and credits the whole transport block to the flow (ref:
+ * downlink-packet-scheduler.cpp:179-331, dl-pf-packet-scheduler.cpp:64-140), so its resident form is one of its own: a cell of a
+ * scheduler-1 group may keep, for both bearers of every user id, the average, the bytes credited since the last update, the existence
+ * byte, m_cumulateBytes and m_cumulateRBs on the device.  A slot of a flows call, in this order:
+ *   1. UpdateAverageTransmissionRate for every existing bearer of every user id (rs_group_schedule_tti_queued's step 1, and its clock
+ *      rules: now == last_update is the early return);
+ *   2. call position i is bearer flow_bearer[k][i] of user user_id[i], and its average is that bearer's;
+ *   3. RBsAllocation on the positions with the data_to_transmit gate, as rs_group_schedule_tti serves it for RS_SCHED_PF;
+ *   4. for every position with a grant: bytes = user_tbs_bits[i] / 8;  pending[u][b] += bytes;  cum_bytes[u][b] += bytes;
+ *      cum_rbs[u][b] += user_nprb[i] -- no min with the data: the reference hands the whole block to the RLC.
+ * rs_group_set_bearers stays refused on a scheduler-1 group, and the queued, counted and resident-average calls refuse a flow-resident
+ * cell (RS_ERR_STATE); rs_group_schedule_tti serves it as before and touches none of this state.  Flows calls run the built-in
+ * "rs_group_flows_kernel<1, 0>": no run-time build reaches them. */
+/* Makes `cell` flow-resident (again, at any time between two calls): has_bearer and avg [U][2] by user id and bearer index, zero
+ * pending bytes, last_update, and the counters (NULL = zeros).  A cell is resident in one form at a time: the later of
+ * rs_group_set_avg / rs_group_set_flows wins.  RS_ERR_INVALID: the scheduler is not RS_SCHED_PF (not served); exponents outside
+ * {0, 1}; an existing bearer's average outside 1..2^51; a last_update that is not finite; a negative counter. */
+int rs_group_set_flows(rs_group* g, int32_t cell, const uint8_t* has_bearer /* [U][2] */, const double* avg /* [U][2] */, double last_update,
+                       const int64_t* cum_bytes /* [U][2] or NULL = zeros */, const int64_t* cum_rbs /* [U][2] or NULL */);
+/* The flows' state as it is after the last call (a synchronising copy; not part of a TTI): zeros for a bearer that does not exist.
+ * Each output may be NULL.  RS_ERR_STATE: the cell is not flow-resident. */
+int rs_group_get_flows(rs_group* g, int32_t cell, double* avg /* [U][2] */, int32_t* pending_bytes /* [U][2] */, double* last_update,
+                       int64_t* cum_bytes /* [U][2] */, int64_t* cum_rbs /* [U][2] */);
+/* One TTI of n flow-resident cells: every rule of a group call (subsets and permutations through cell_ids, uniform presence of cqi_prb,
+ * cqi_epoch per cell, one launch) and the clock rules of rs_group_schedule_tti_at.  in[k].n_users counts the call's FLOWS (<= the
+ * config's n_users: a host with N users x 2 bearers creates the group with n_users = its largest flow count); user ids are below the
+ * config's n_users, user_id == NULL means user i; the pairs (user_id[i], flow_bearer[k][i]) ascend strictly in lexicographic order, so
+ * a user may hold two adjacent positions and no flow is named twice.  avg_rate, hol_delay, prio_has_data and required_rbs must be
+ * NULL; data_to_transmit is required, every word > 0, and the bearer must exist; cqi / cqi_prb hold one row per position.
+ * n_users == 0 is an update-only slot (flow_bearer[k] may be NULL; its outputs read "nothing scheduled").  Outputs are per position;
+ * rbg_to_user[r] holds the flow id 2 * user + bearer.  A rejected call launches nothing and moves nothing (RS_ERR_STATE names the
+ * cell that is not flow-resident); RS_ERR_HIP ends the flow-resident state of the cells the call named. */
+int rs_group_schedule_tti_flows(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in /* [n] */, rs_tti_out* out /* [n] */,
+                                const double* now /* [n] */, const uint8_t* const* flow_bearer /* [n]: [in[k].n_users], 0 or 1 */);
 
 /* ------------------------------------------------------------------------------------------
  * Batched mode: many independent cells resident on the device, whole DoSchedule() loops

@@ -115,6 +115,7 @@ ABI_SYMBOLS = [
     "rs_group_set_bearers", "rs_group_get_bearers", "rs_group_schedule_tti_queued",
     "rs_group_specialize_queued", "rs_group_queued_jit_status", "rs_jit_selfcheck_group_queued",
     "rs_group_set_counters", "rs_group_get_counters", "rs_group_schedule_tti_counted",
+    "rs_group_set_flows", "rs_group_get_flows", "rs_group_schedule_tti_flows",
 ]
 
 _lib = None
@@ -173,6 +174,12 @@ def lib():
     L.rs_group_get_counters.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.rs_group_schedule_tti_counted.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_TtiIn), C.POINTER(_TtiOut),
                                                 C.POINTER(C.c_double), C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32))]
+    L.rs_group_set_flows.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_int64),
+                                     C.POINTER(C.c_int64)]
+    L.rs_group_get_flows.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.rs_group_schedule_tti_flows.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_TtiIn), C.POINTER(_TtiOut),
+                                              C.POINTER(C.c_double), C.POINTER(C.POINTER(C.c_uint8))]
     L.rs_group_specialize_queued.argtypes = [C.c_void_p]
     L.rs_group_queued_jit_status.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.rs_jit_selfcheck_group_queued.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
@@ -862,6 +869,65 @@ class GroupScheduler:
         adds the bytes and the position's PRBs to its counters, and every TtiResult carries .sent [n][2], the bytes sent per call
         position and bearer (what a binding hands to UpdateTransmittedBytes and the RLC); an update-only slot gives an empty array."""
         return self._schedule_queued(calls, now, cell_ids, True)
+
+    # ---- resident flows (scheduler 1): a call position is one bearer of one user, the whole block is credited to it ----
+    def set_flows(self, cell, has_bearer, avg, last_update, cum_bytes=None, cum_rbs=None):
+        """rs_group_set_flows: makes `cell` of a scheduler-1 group flow-resident with has_bearer [n_users][2] and avg [n_users][2] by
+        user id and bearer index (1 <= avg <= 2**51 where the bearer exists), zero pending bytes, last_update and the counters
+        cum_bytes / cum_rbs int64 [n_users][2] (None: zeros).  Any time between two calls."""
+        U = self.slices.n_users
+        h = np.ascontiguousarray(has_bearer, np.uint8)
+        a = np.ascontiguousarray(avg, np.float64)
+        cb = None if cum_bytes is None else np.ascontiguousarray(cum_bytes, np.int64)
+        cr = None if cum_rbs is None else np.ascontiguousarray(cum_rbs, np.int64)
+        assert h.shape == (U, 2) and a.shape == (U, 2) and (cb is None or cb.shape == (U, 2)) and (cr is None or cr.shape == (U, 2))
+        _check(lib().rs_group_set_flows(self._h, cell, _p(h, C.c_uint8), _p(a, C.c_double), float(last_update),
+                                        _p(cb, C.c_int64) if cb is not None else None, _p(cr, C.c_int64) if cr is not None else None))
+
+    def get_flows(self, cell):
+        """(avg float64, pending bytes int32, last_update, cum_bytes int64, cum_rbs int64) of a flow-resident cell, the arrays
+        [n_users][2] and 0 for a bearer that does not exist: a synchronising copy, not part of a TTI."""
+        U = self.slices.n_users
+        a, pend = np.zeros((U, 2), np.float64), np.zeros((U, 2), np.int32)
+        cb, cr = np.zeros((U, 2), np.int64), np.zeros((U, 2), np.int64)
+        last = C.c_double(0)
+        _check(lib().rs_group_get_flows(self._h, cell, _p(a, C.c_double), _p(pend, C.c_int32), C.byref(last), _p(cb, C.c_int64),
+                                        _p(cr, C.c_int64)))
+        return a, pend, float(last.value), cb, cr
+
+    def schedule_tti_flows(self, calls: Sequence[dict], now, cell_ids: Optional[Sequence[int]] = None) -> List[TtiResult]:
+        """rs_group_schedule_tti_flows: one TTI of flow-resident cells.  calls[k]: dict(user_id [n], flow_bearer [n] (0 or 1),
+        data_to_transmit [n] (> 0), cqi [n][R] or cqi_prb [n][R * rbg_size], cqi_epoch) -- position i is bearer flow_bearer[i] of user
+        user_id[i] (None: user i), the pairs ascending; or dict(n_users=0), an update-only slot.  Results are per position, and
+        rbg_to_user holds flow ids 2 * user + bearer; the bytes credited to position i are user_tbs_bits[i] // 8."""
+        n = len(calls)
+        S, R = self.slices.n_slices, self.R
+        ins, outs, results, keep = (_TtiIn * n)(), (_TtiOut * n)(), [], []
+        bearer = (C.POINTER(C.c_uint8) * n)()
+        for k, kw in enumerate(calls):
+            kw = dict(kw)
+            if kw.get("n_users", None) == 0:
+                assert len(kw) == 1, "an update-only slot gives nothing but n_users=0"
+                z = np.zeros(0, np.int32)
+                res = TtiResult(np.zeros(S, np.int32), np.zeros(S, np.int32), np.zeros(R, np.int32), z, z.copy(), z.copy(), z.copy())
+                ins[k] = _TtiIn()
+                outs[k] = _TtiOut(_p(res.target_rbs, C.c_int32), _p(res.quota_rbgs, C.c_int32), _p(res.rbg_to_user, C.c_int32),
+                                  None, None, None, None, None, None)
+                results.append(res)
+                continue
+            fb = np.ascontiguousarray(kw.pop("flow_bearer"), np.uint8)
+            tin, tout, res, arrays = _marshal_tti(S, R, self.rbg_size, self.sched, kw.pop("cqi", None), kw.pop("avg_rate", None), **kw)
+            assert fb.shape == (tin.n_users,)
+            ins[k], outs[k] = tin, tout
+            bearer[k] = _p(fb, C.c_uint8)
+            results.append(res)
+            keep.append((arrays, fb))
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(now, np.float64), (n,)))
+        ids = None if cell_ids is None else np.ascontiguousarray(cell_ids, np.int32)
+        assert ids is None or ids.shape == (n,)
+        _check(lib().rs_group_schedule_tti_flows(self._h, n, _p(ids, C.c_int32) if ids is not None else None, ins, outs, _p(t, C.c_double),
+                                                 bearer))
+        return results
 
     def slice_offset(self, cell):
         out = np.zeros(self.slices.n_slices, np.float64)

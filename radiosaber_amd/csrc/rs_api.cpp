@@ -1886,7 +1886,8 @@ struct TtiPack {
  * bytes, the CQI grid with its zero padding (reuse_grid: left alone -- rs_tti_in.cqi_epoch), averages or the general exponents'
  * denominators, the exact-scan test, draws, gate, HoL delays and priority flags.  Shared by rs_schedule_tti (its one block) and
  * rs_group_schedule_tti (one slot per cell): the two paths cannot drift apart.  Touches nothing but `h_in` and `pk`. */
-int pack_tti(const rs_batch* b, const rs_tti_in* in, const rs_tti_out* out, uint8_t* h_in, bool reuse_grid, TtiPack* pk, bool resident_avg = false) {
+int pack_tti(const rs_batch* b, const rs_tti_in* in, const rs_tti_out* out, uint8_t* h_in, bool reuse_grid, TtiPack* pk, bool resident_avg = false,
+             bool flows = false) {
   const int n = in->n_users, R = b->R, S = b->S;
   if (n < 1 || n > b->U) return fail(RS_ERR_INVALID, "n_users %d outside 1..%d", n, b->U);
   /* resident_avg (rs_group_schedule_tti_at): the cell's averages are on the device -- none are given, and the place of the averages in
@@ -1900,7 +1901,8 @@ int pack_tti(const rs_batch* b, const rs_tti_in* in, const rs_tti_out* out, uint
   for (int i = 0; i < n; i++) {
     int id = in->user_id ? in->user_id[i] : i;
     if (id < 0 || id >= b->U) return fail(RS_ERR_INVALID, "user id %d out of range", id);
-    if (i && in->user_id && in->user_id[i] <= in->user_id[i - 1]) return fail(RS_ERR_INVALID, "user_id must ascend");
+    /* (flows, rs_group_schedule_tti_flows: a user's two bearers are two adjacent positions -- the caller has checked the pairs) */
+    if (i && in->user_id && (flows ? in->user_id[i] < in->user_id[i - 1] : in->user_id[i] <= in->user_id[i - 1])) return fail(RS_ERR_INVALID, "user_id must ascend");
     h_slice[i] = (uint8_t)b->u2s[id];
     if ((b->sched == RS_SCHED_NVS || b->sched == RS_SCHED_NVS_NONGREEDY) && h_slice[i] != h_slice[0])
       return fail(RS_ERR_INVALID, "RS_SCHED_NVS*: pass only the users of the served slice");
@@ -1989,7 +1991,8 @@ int pack_tti(const rs_batch* b, const rs_tti_in* in, const rs_tti_out* out, uint
 
 /* One cell's output block `h_out` (layout `l`) unpacked into the caller's rs_tti_out: call positions back to user ids, the packed
  * per-user word split.  Shared by rs_schedule_tti and rs_group_schedule_tti. */
-void unpack_tti(const rs_batch* b, const rs_tti_in* in, rs_tti_out* out, const uint8_t* h_out, const CtxLayout& l, bool want_upper) {
+void unpack_tti(const rs_batch* b, const rs_tti_in* in, rs_tti_out* out, const uint8_t* h_out, const CtxLayout& l, bool want_upper,
+                const uint8_t* flow_bearer = nullptr) {
   const int n = in->n_users, R = b->R, S = b->S;
   const int16_t* h_map = (const int16_t*)(h_out + l.map);
   const int16_t* h_quota = (const int16_t*)(h_out + l.quota);
@@ -1999,6 +2002,7 @@ void unpack_tti(const rs_batch* b, const rs_tti_in* in, rs_tti_out* out, const u
   for (int r = 0; r < R; r++) {
     int o = h_map[r];
     out->rbg_to_user[r] = o < 0 ? -1 : (in->user_id ? in->user_id[o] : o);
+    if (flow_bearer && o >= 0) out->rbg_to_user[r] = 2 * out->rbg_to_user[r] + flow_bearer[o]; /* (a flows call: the flow id 2 * user + bearer) */
   }
   if (want_upper) {
     const int32_t* h_upper = (const int32_t*)(h_out + l.upper);
@@ -2482,6 +2486,11 @@ struct rs_group {
   std::vector<uint8_t> counted;
   bool last_call_counted = false;
   char kname_cnt[56] = "";
+  /* resident flows (rs_group_set_flows, rs_group_schedule_tti_flows; scheduler 1 alone): resident[cell] == 3.  The cell's flows live in
+   * the bearer stores and the counter stores above (a cell is resident in one form at a time), has_bearer mirrors their existence
+   * bytes, and the slots' bearer words (0 or 1 per call position) travel in h_qin, one word per position.  Flows calls run the
+   * built-in flows kernel: no run-time build of this form. */
+  char kname_flw[56] = "";
 };
 
 namespace {
@@ -2571,6 +2580,7 @@ rs_group* rs_group_create(const rs_config* cfg, int32_t n_cells) {
   snprintf(g->kname_res, sizeof g->kname_res, "rs_group_resident_kernel<%d, %d>", b->sched, sorts && ept <= 4 ? ept : 0);
   snprintf(g->kname_que, sizeof g->kname_que, "rs_group_queued_kernel<%d, %d>", b->sched, b->sched == RS_SCHED_MAXCELL && ept <= 4 ? ept : 0);
   snprintf(g->kname_cnt, sizeof g->kname_cnt, "rs_group_counted_kernel<%d, %d>", b->sched, b->sched == RS_SCHED_MAXCELL && ept <= 4 ? ept : 0);
+  snprintf(g->kname_flw, sizeof g->kname_flw, "rs_group_flows_kernel<%d, 0>", b->sched);
   g->empty_slot.assign(n_cells, 0);
   g->resident.assign(n_cells, 0);
   g->counted.assign(n_cells, 0);
@@ -2620,6 +2630,7 @@ void rs_group_destroy(rs_group* g) {
 extern "C" hipError_t rs_launch_group_resident(const RsLaunch* p, int threads, hipStream_t stream);
 extern "C" hipError_t rs_launch_group_queued(const RsLaunch* p, int threads, hipStream_t stream);
 extern "C" hipError_t rs_launch_group_counted(const RsLaunch* p, int threads, hipStream_t stream);
+extern "C" hipError_t rs_launch_group_flows(const RsLaunch* p, int threads, hipStream_t stream);
 
 namespace {
 /* Resident averages and the FP32 filter.  The metric scan's filter needs (1 + a) / 1000 (scheduler 1: a) inside [2^-60, 2^60] for every
@@ -2643,10 +2654,11 @@ constexpr double kResidentMinDt = 0x1p-20;
  * (1 + a0) + a1 exactly -- it does while that sum is below 2^53 -- and must stay inside the filter's range: rs_group_set_bearers refuses
  * a > 2^51, and the growth argument above carries over bearer by bearer (the same update, |rate| < 2^51): a <= 2^51 (1 + 2^-51)^k. */
 constexpr double kBearerAvgMax = 0x1p51;
-enum { kGroupPlain = 0, kGroupResident = 1, kGroupQueued = 2 };
+enum { kGroupPlain = 0, kGroupResident = 1, kGroupQueued = 2, kGroupFlows = 3 };
 
 int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out, const double* now,
-                   const int32_t* const* qdata = nullptr, bool cnt = false, int32_t* const* sent = nullptr);
+                   const int32_t* const* qdata = nullptr, bool cnt = false, int32_t* const* sent = nullptr,
+                   const uint8_t* const* flow = nullptr);
 }  // namespace
 
 int rs_group_schedule_tti(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out) {
@@ -2671,14 +2683,22 @@ int rs_group_schedule_tti_counted(rs_group* g, int32_t n, const int32_t* cell_id
   return group_schedule(g, n, cell_ids, in, out, now, data_to_transmit, true, sent);
 }
 
+int rs_group_schedule_tti_flows(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out, const double* now,
+                                const uint8_t* const* flow_bearer) {
+  if (!g || !in || !out || !now || !flow_bearer) return fail(RS_ERR_INVALID, "null argument");
+  return group_schedule(g, n, cell_ids, in, out, now, nullptr, false, nullptr, flow_bearer);
+}
+
 namespace {
 /* one group call; now != null: a resident form -- averages (rs_group_schedule_tti_at) or, with qdata, bearers (rs_group_schedule_tti_queued;
- * cnt: its counted twin, rs_group_schedule_tti_counted, which differs in the kernel it launches, the two counter stores and the sent rows) */
+ * cnt: its counted twin, rs_group_schedule_tti_counted, which differs in the kernel it launches, the two counter stores and the sent rows)
+ * or, with flow, scheduler 1's flows (rs_group_schedule_tti_flows: a call position is bearer flow[k][i] of user user_id[i]) */
 int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out, const double* now,
-                   const int32_t* const* qdata, bool cnt, int32_t* const* sent) {
+                   const int32_t* const* qdata, bool cnt, int32_t* const* sent, const uint8_t* const* flow) {
   rs_batch* b = g->b;
-  const bool res = now != nullptr, que = qdata != nullptr;
-  const int kind = que ? kGroupQueued : (res ? kGroupResident : kGroupPlain);
+  const bool res = now != nullptr, que = qdata != nullptr, flw = flow != nullptr;
+  const bool slots0 = que || flw; /* the forms whose calls may hold update-only slots (n_users == 0) */
+  const int kind = flw ? kGroupFlows : (que ? kGroupQueued : (res ? kGroupResident : kGroupPlain));
   using clk = std::chrono::steady_clock;
   const clk::time_point t0 = g->timing ? clk::now() : clk::time_point();
   if (n < 1 || n > g->n_cells) return fail(RS_ERR_INVALID, "n %d outside 1..%d (the group's cells)", n, g->n_cells);
@@ -2701,14 +2721,14 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
   auto upper_of = [&](const rs_tti_out& o) { return b->sched == RS_SCHED_UPPERBOUND && (o.upper_rbg || o.upper_user); };
   /* (a queued call's update-only slots, n_users == 0, give no inputs at all: the slots WITH users agree among themselves) */
   int k0 = 0;
-  while (que && k0 < n && in[k0].n_users == 0) k0++;
+  while (slots0 && k0 < n && in[k0].n_users == 0) k0++;
   const bool any_users = k0 < n;
   if (!any_users) k0 = 0;
   const bool has_prb = any_users && in[k0].cqi_prb != nullptr, has_hol = any_users && in[k0].hol_delay != nullptr,
              has_prio = any_users && in[k0].prio_has_data != nullptr, has_gate = any_users && gate_of(in[k0]) != nullptr,
              want_upper = any_users && upper_of(out[k0]);
   for (int k = k0 + 1; k < n; k++) {
-    if (que && in[k].n_users == 0) continue;
+    if (slots0 && in[k].n_users == 0) continue;
     const char* what = (in[k].cqi_prb != nullptr) != has_prb ? "cqi_prb" : (in[k].hol_delay != nullptr) != has_hol ? "hol_delay"
                      : (in[k].prio_has_data != nullptr) != has_prio ? "prio_has_data"
                      : (gate_of(in[k]) != nullptr) != has_gate ? (b->sched == RS_SCHED_NVS ? "required_rbs" : "data_to_transmit")
@@ -2721,12 +2741,38 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
     for (int k = 0; k < n; k++) {
       const int cell = cell_ids ? cell_ids[k] : k;
       if (in[k].avg_rate) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): avg_rate must be NULL: the cell's averages are resident on the device", k, cell);
+      if (flw && g->resident[cell] != 3) return fail(RS_ERR_STATE, "cell slot %d: cell %d is not flow-resident (rs_group_set_flows first)", k, cell);
+      if (!flw && g->resident[cell] == 3)
+        return fail(RS_ERR_STATE, "cell slot %d: cell %d is flow-resident (rs_group_set_flows): rs_group_schedule_tti_flows serves it, or rs_group_set_avg makes it average-resident", k, cell);
       if (que && g->resident[cell] != 2) return fail(RS_ERR_STATE, "cell slot %d: cell %d is not bearer-resident (rs_group_set_bearers first)", k, cell);
       if (cnt && !g->counted[cell]) return fail(RS_ERR_STATE, "cell slot %d: cell %d is not counted (rs_group_set_counters first)", k, cell);
       if (!que && g->resident[cell] == 2)
         return fail(RS_ERR_STATE, "cell slot %d: cell %d is bearer-resident (rs_group_set_bearers): rs_group_schedule_tti_queued serves it, or rs_group_set_avg makes it average-resident", k, cell);
       if (!g->resident[cell]) return fail(RS_ERR_STATE, "cell slot %d: cell %d is not resident (rs_group_set_avg first)", k, cell);
-      if (que && in[k].n_users < 0) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): n_users %d is negative", k, cell, in[k].n_users);
+      if (slots0 && in[k].n_users < 0) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): n_users %d is negative", k, cell, in[k].n_users);
+      if (flw) {
+        /* positions are flows: (user, bearer) pairs in RRC-container order, each an existing bearer with data to transmit */
+        const int nf = in[k].n_users;
+        if (nf > b->U) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): n_users %d (the call's flows) outside 0..%d", k, cell, nf, b->U);
+        if (in[k].hol_delay || in[k].prio_has_data || in[k].required_rbs)
+          return fail(RS_ERR_INVALID, "cell slot %d (cell %d): %s must be NULL in a flows call", k, cell,
+                      in[k].hol_delay ? "hol_delay" : (in[k].prio_has_data ? "prio_has_data" : "required_rbs"));
+        if (nf > 0 && !flow[k]) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): flow_bearer[%d] is NULL (only an update-only slot, n_users == 0, gives none)", k, cell, k);
+        if (nf > 0 && !in[k].data_to_transmit) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): data_to_transmit is required: a flow is scheduled because it has data", k, cell);
+        const uint8_t* const has = g->has_bearer.data() + (size_t)cell * 2 * (size_t)b->U;
+        int prev = -1;
+        for (int i = 0; i < nf; i++) {
+          const int id = in[k].user_id ? in[k].user_id[i] : i, fb = flow[k][i];
+          if (id < 0 || id >= b->U) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): user id %d out of range", k, cell, id);
+          if (fb > 1) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): flow_bearer[%d] = %d is neither 0 nor 1", k, cell, i, fb);
+          if (2 * id + fb <= prev)
+            return fail(RS_ERR_INVALID, "cell slot %d (cell %d): call position %d (user %d, bearer %d) does not ascend: flows come in (user, bearer) order, each once", k, cell, i, id, fb);
+          prev = 2 * id + fb;
+          if (!has[prev]) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): call position %d names bearer %d of user %d, which does not exist (rs_group_set_flows)", k, cell, i, fb, id);
+          if (in[k].data_to_transmit[i] <= 0)
+            return fail(RS_ERR_INVALID, "cell slot %d (cell %d): data_to_transmit[%d] = %d: a flow without data is not scheduled", k, cell, i, in[k].data_to_transmit[i]);
+        }
+      }
       if (que && in[k].n_users > 0 && !qdata[k]) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): data_to_transmit[%d] is NULL (only an update-only slot, n_users == 0, gives none)", k, cell, k);
       const double last = g->last_update[cell];
       if (!std::isfinite(now[k])) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): now is not finite", k, cell);
@@ -2744,7 +2790,7 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
     /* rs_tti_in.cqi_epoch, decided per cell as a context of its own would (rs_schedule_tti): the number, the user count, the user list
      * and the kind of report of the cell's valid image -- then the caller's block is neither checked, copied nor read */
     const int cell = cell_ids ? cell_ids[k] : k;
-    g->empty_slot[k] = que && in[k].n_users == 0;
+    g->empty_slot[k] = slots0 && in[k].n_users == 0;
     if (g->empty_slot[k]) {
       /* an update-only slot: its workgroup reads the header's cell, user count and clock and nothing behind the header */
       g->modes[k] = 0;
@@ -2762,7 +2808,7 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
                             im.has_ids == (in[k].user_id != nullptr) &&
                             (!in[k].user_id || memcmp(im.ids.data(), in[k].user_id, 4 * (size_t)im.n) == 0);
     g->modes[k] = (uint8_t)(epoch == 0 ? 0 : (reuse_grid ? 2 : 1));
-    const int rc = pack_tti(b, &in[k], &out[k], slot + RS_GROUP_HDR_BYTES, reuse_grid, &pk, res);
+    const int rc = pack_tti(b, &in[k], &out[k], slot + RS_GROUP_HDR_BYTES, reuse_grid, &pk, res, flw);
     if (rc) {
       char msg[sizeof g_err];
       snprintf(msg, sizeof msg, "%s", g_err);
@@ -2784,6 +2830,10 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
           return fail(RS_ERR_INVALID, "cell slot %d (cell %d): user %d (call position %d) has no data in either bearer: the reference does not schedule such a user", k, cell, id, i);
       }
       memcpy(g->h_qin + (size_t)k * 2 * (size_t)b->U, d, 8 * (size_t)in[k].n_users);
+    }
+    if (flw) { /* the slot's bearer words, one per call position (checked above) */
+      int32_t* const w = g->h_qin + (size_t)k * 2 * (size_t)b->U;
+      for (int i = 0; i < in[k].n_users; i++) w[i] = flow[k][i];
     }
     const CtxLayout& l = pk.l;
     const int nu = in[k].n_users;
@@ -2844,7 +2894,7 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
   uint8_t* const dev_in = zc ? g->z_in : g->d_in;
   uint8_t* const dev_out = zc ? g->z_out : g->d_out;
   if (!zc) HIP_TRY(hipMemcpyAsync(g->d_in, g->h_in, (size_t)n * g->in_stride, hipMemcpyHostToDevice, st));
-  if (que && !g->z_qin) HIP_TRY(hipMemcpyAsync(g->d_qin, g->h_qin, 8 * (size_t)n * b->U, hipMemcpyHostToDevice, st));
+  if (slots0 && !g->z_qin) HIP_TRY(hipMemcpyAsync(g->d_qin, g->h_qin, 8 * (size_t)n * b->U, hipMemcpyHostToDevice, st));
   RsLaunch L = b->base;
   L.n_cells = n; /* call slots of this launch */
   L.n_ttis = 1;
@@ -2886,6 +2936,16 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
     L.grp_qin = g->z_qin ? g->z_qin : g->d_qin;
     L.grp_qin_stride = 2 * (int64_t)b->U;
   }
+  if (flw) { /* (the bearer stores and the counter stores; the bearer words where the queued form's data words travel) */
+    L.grp_qavg = g->d_qavg;
+    L.grp_qpend = g->d_qpend;
+    L.grp_qhas = g->d_qhas;
+    L.grp_qdata = g->d_qdata;
+    L.grp_qin = g->z_qin ? g->z_qin : g->d_qin;
+    L.grp_qin_stride = 2 * (int64_t)b->U;
+    L.grp_cbytes = g->d_cbytes;
+    L.grp_crbs = g->d_crbs;
+  }
   if (cnt) {
     L.grp_cbytes = g->d_cbytes;
     L.grp_crbs = g->d_crbs;
@@ -2907,9 +2967,9 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
   RsJitKernel** const pair = que ? g->qjit : (res ? g->rjit : g->jit);
   int* const chk_left = que ? g->qchk_left : (res ? g->rchk_left : g->chk_left);
   int* const chk_agreed = que ? g->qchk_agreed : (res ? g->rchk_agreed : g->chk_agreed);
-  RsJitKernel* kd = cnt ? nullptr : pair[0]; /* (a counted call: the built-in counted kernel, whatever rs_group_specialize_queued built) */
+  RsJitKernel* kd = (cnt || flw) ? nullptr : pair[0]; /* (a counted call: the built-in counted kernel, whatever rs_group_specialize_queued built; a flows call likewise) */
   int which = 0;
-  if (!cnt && pair[1] && !has_prb && !L.queue_mode && !has_gate && !L.exact_scan && !L.gen_exp && !want_upper && !L.synthetic) { kd = pair[1]; which = 1; }
+  if (!cnt && !flw && pair[1] && !has_prb && !L.queue_mode && !has_gate && !L.exact_scan && !L.gen_exp && !want_upper && !L.synthetic) { kd = pair[1]; which = 1; }
   /* A build without the self-check mark serves its first calls beside the built-in kernel of its kind (rs_group_jit_status,
    * rs_group_resident_jit_status): same slots, same state; every named cell's output fields and the state left behind must agree --
    * the slice state, for a resident call the averages of every user id, the pending bytes and the last-update time, and for a queued
@@ -2971,6 +3031,7 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
     L.done_flag = nullptr; /* completion by the stream */
   }
   if (kd) HIP_TRY(rs_jit_launch(kd, &L, st));
+  else if (flw) HIP_TRY(rs_launch_group_flows(&L, b->threads, st));
   else if (cnt) HIP_TRY(rs_launch_group_counted(&L, b->threads, st));
   else if (que) HIP_TRY(rs_launch_group_queued(&L, b->threads, st));
   else if (res) HIP_TRY(rs_launch_group_resident(&L, b->threads, st));
@@ -3180,7 +3241,7 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
       if (out[k].upper_user) for (int i = 0; i < b->S * b->R; i++) out[k].upper_user[i] = -1;
       continue;
     }
-    unpack_tti(b, &in[k], &out[k], g->h_out + (size_t)k * g->out_stride, g->packs[k].l, want_upper);
+    unpack_tti(b, &in[k], &out[k], g->h_out + (size_t)k * g->out_stride, g->packs[k].l, want_upper, flw ? flow[k] : nullptr);
     /* (a counted call: the slot's sent rows, [n_users][2] in call order, written by the threads that credited the positions) */
     if (cnt && sent && sent[k]) memcpy(sent[k], g->h_sent + (size_t)k * 2 * (size_t)b->U, 8 * (size_t)in[k].n_users);
   }
@@ -3215,6 +3276,60 @@ bool group_alloc_resident_shared(rs_group* g) {
   g->d_rgather = g->d_rlast = nullptr;
   g->d_ruid = nullptr;
   return false;
+}
+
+/* the [n_cells][U][2] bearer stores of the queued form and of the flows form, the pinned block of the slots' words and the host's
+ * mirror of the existence bytes (all or none; 25 bytes per bearer) */
+bool group_alloc_bearer_stores(rs_group* g) {
+  if (g->d_qavg) return true;
+  const size_t nb = 2 * (size_t)g->b->U * (size_t)g->n_cells;
+  bool ok = group_alloc_resident_shared(g) && hipMalloc(&g->d_qavg, 8 * nb) == hipSuccess && hipMalloc(&g->d_qpend, 4 * nb) == hipSuccess &&
+            hipMalloc(&g->d_qdata, 4 * nb) == hipSuccess && hipMalloc(&g->d_qhas, nb) == hipSuccess &&
+            hipHostMalloc((void**)&g->h_qin, 4 * nb, hipHostMallocMapped) == hipSuccess;
+  if (ok && g->z_in) { /* (the group reads its slots in place: the data words too) */
+    void* z = nullptr;
+    if (hipHostGetDevicePointer(&z, g->h_qin, 0) == hipSuccess) g->z_qin = (int32_t*)z;
+  }
+  if (ok && !g->z_qin) ok = hipMalloc(&g->d_qin, 4 * nb) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    for (void* q : {(void*)g->d_qavg, (void*)g->d_qpend, (void*)g->d_qdata, (void*)g->d_qhas, (void*)g->d_qin})
+      if (q) (void)hipFree(q);
+    if (g->h_qin) (void)hipHostFree(g->h_qin);
+    g->d_qavg = nullptr;
+    g->d_qpend = g->d_qdata = g->d_qin = g->h_qin = g->z_qin = nullptr;
+    g->d_qhas = nullptr;
+    return false;
+  }
+  memset(g->h_qin, 0, 4 * nb);
+  g->has_bearer.assign(nb, 0);
+  return true;
+}
+
+/* the [n_cells][U][2] counter stores of the counted form and of the flows form, zeroed, and the pinned block of the counted calls'
+ * sent rows (all or none; 20 bytes per bearer) */
+bool group_alloc_counter_stores(rs_group* g) {
+  if (g->d_cbytes) return true;
+  const size_t nb = 2 * (size_t)g->b->U * (size_t)g->n_cells;
+  bool ok = hipMalloc(&g->d_cbytes, 8 * nb) == hipSuccess && hipMalloc(&g->d_crbs, 8 * nb) == hipSuccess &&
+            hipHostMalloc((void**)&g->h_sent, 4 * nb, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
+  if (ok && g->z_out) { /* (the group's outputs are written in place: the sent rows too) */
+    void* z = nullptr;
+    if (hipHostGetDevicePointer(&z, g->h_sent, 0) == hipSuccess) g->z_sent = (int32_t*)z;
+  }
+  if (ok && !g->z_sent) ok = hipMalloc(&g->d_sent, 4 * nb) == hipSuccess;
+  if (ok) ok = hipMemset(g->d_cbytes, 0, 8 * nb) == hipSuccess && hipMemset(g->d_crbs, 0, 8 * nb) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    for (void* q : {(void*)g->d_cbytes, (void*)g->d_crbs, (void*)g->d_sent})
+      if (q) (void)hipFree(q);
+    if (g->h_sent) (void)hipHostFree(g->h_sent);
+    g->d_cbytes = g->d_crbs = nullptr;
+    g->d_sent = g->h_sent = g->z_sent = nullptr;
+    return false;
+  }
+  memset(g->h_sent, 0, 4 * nb);
+  return true;
 }
 }  // namespace
 
@@ -3302,28 +3417,7 @@ int rs_group_set_bearers(rs_group* g, int32_t cell, const uint8_t* has_bearer, c
     if (has_bearer[i] && !(avg[i] >= 1 && avg[i] <= kBearerAvgMax)) /* (false for NaN) */
       return fail(RS_ERR_INVALID, "avg[%zu][%zu] = %g outside 1..2^51 (an updated average is never below 1; the bound above keeps the sum of a user's two exact and inside the FP32 filter's range)", i / 2, i % 2, avg[i]);
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  if (!g->d_qavg) {
-    bool ok = group_alloc_resident_shared(g) && hipMalloc(&g->d_qavg, 8 * nb) == hipSuccess && hipMalloc(&g->d_qpend, 4 * nb) == hipSuccess &&
-              hipMalloc(&g->d_qdata, 4 * nb) == hipSuccess && hipMalloc(&g->d_qhas, nb) == hipSuccess &&
-              hipHostMalloc((void**)&g->h_qin, 4 * nb, hipHostMallocMapped) == hipSuccess;
-    if (ok && g->z_in) { /* (the group reads its slots in place: the data words too) */
-      void* z = nullptr;
-      if (hipHostGetDevicePointer(&z, g->h_qin, 0) == hipSuccess) g->z_qin = (int32_t*)z;
-    }
-    if (ok && !g->z_qin) ok = hipMalloc(&g->d_qin, 4 * nb) == hipSuccess;
-    if (!ok) {
-      (void)hipGetLastError();
-      for (void* q : {(void*)g->d_qavg, (void*)g->d_qpend, (void*)g->d_qdata, (void*)g->d_qhas, (void*)g->d_qin})
-        if (q) (void)hipFree(q);
-      if (g->h_qin) (void)hipHostFree(g->h_qin);
-      g->d_qavg = nullptr;
-      g->d_qpend = g->d_qdata = g->d_qin = g->h_qin = g->z_qin = nullptr;
-      g->d_qhas = nullptr;
-      return fail(RS_ERR_HIP, "allocation of the group's resident bearers failed (%zu bytes)", 25 * nb);
-    }
-    memset(g->h_qin, 0, 4 * nb);
-    g->has_bearer.assign(nb, 0);
-  }
+  if (!group_alloc_bearer_stores(g)) return fail(RS_ERR_HIP, "allocation of the group's resident bearers failed (%zu bytes)", 25 * nb);
   HIP_TRY(hipStreamSynchronize(b->stream));
   g->resident[cell] = 0; /* (until all four copies are through) */
   /* a bearer that does not exist holds zeros: rs_group_get_bearers reports them, the kernel neither reads nor writes them */
@@ -3369,26 +3463,7 @@ int rs_group_set_counters(rs_group* g, int32_t cell, const int64_t* cum_bytes, c
     if (cum_rbs && cum_rbs[i] < 0) return fail(RS_ERR_INVALID, "cum_rbs[%zu][%zu] = %lld is negative", i / 2, i % 2, (long long)cum_rbs[i]);
   }
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  if (!g->d_cbytes) {
-    bool ok = hipMalloc(&g->d_cbytes, 8 * nb) == hipSuccess && hipMalloc(&g->d_crbs, 8 * nb) == hipSuccess &&
-              hipHostMalloc((void**)&g->h_sent, 4 * nb, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
-    if (ok && g->z_out) { /* (the group's outputs are written in place: the sent rows too) */
-      void* z = nullptr;
-      if (hipHostGetDevicePointer(&z, g->h_sent, 0) == hipSuccess) g->z_sent = (int32_t*)z;
-    }
-    if (ok && !g->z_sent) ok = hipMalloc(&g->d_sent, 4 * nb) == hipSuccess;
-    if (ok) ok = hipMemset(g->d_cbytes, 0, 8 * nb) == hipSuccess && hipMemset(g->d_crbs, 0, 8 * nb) == hipSuccess;
-    if (!ok) {
-      (void)hipGetLastError();
-      for (void* q : {(void*)g->d_cbytes, (void*)g->d_crbs, (void*)g->d_sent})
-        if (q) (void)hipFree(q);
-      if (g->h_sent) (void)hipHostFree(g->h_sent);
-      g->d_cbytes = g->d_crbs = nullptr;
-      g->d_sent = g->h_sent = g->z_sent = nullptr;
-      return fail(RS_ERR_HIP, "allocation of the group's bearer counters failed (%zu bytes)", 20 * nb);
-    }
-    memset(g->h_sent, 0, 4 * nb);
-  }
+  if (!group_alloc_counter_stores(g)) return fail(RS_ERR_HIP, "allocation of the group's bearer counters failed (%zu bytes)", 20 * nb);
   HIP_TRY(hipStreamSynchronize(b->stream));
   g->counted[cell] = 0; /* (until both copies are through) */
   if (cum_bytes) HIP_TRY(hipMemcpy(g->d_cbytes + (size_t)cell * 2 * U, cum_bytes, 16 * U, hipMemcpyHostToDevice));
@@ -3407,6 +3482,70 @@ int rs_group_get_counters(rs_group* g, int32_t cell, int64_t* cum_bytes, int64_t
   const size_t U = (size_t)b->U;
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   HIP_TRY(hipStreamSynchronize(b->stream));
+  if (cum_bytes) HIP_TRY(hipMemcpy(cum_bytes, g->d_cbytes + (size_t)cell * 2 * U, 16 * U, hipMemcpyDeviceToHost));
+  if (cum_rbs) HIP_TRY(hipMemcpy(cum_rbs, g->d_crbs + (size_t)cell * 2 * U, 16 * U, hipMemcpyDeviceToHost));
+  return RS_OK;
+}
+
+int rs_group_set_flows(rs_group* g, int32_t cell, const uint8_t* has_bearer, const double* avg, double last_update, const int64_t* cum_bytes,
+                       const int64_t* cum_rbs) {
+  if (!g || !has_bearer || !avg) return fail(RS_ERR_INVALID, "null argument");
+  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
+  rs_batch* b = g->b;
+  const size_t U = (size_t)b->U, nb = 2 * U * (size_t)g->n_cells;
+  if (b->sched != RS_SCHED_PF)
+    return fail(RS_ERR_INVALID, "resident flows are not served for scheduler %d: only RS_SCHED_PF races flows (rs_group_set_bearers serves the schedulers that race users)", b->sched);
+  if (b->gen_exp)
+    return fail(RS_ERR_INVALID, "resident flows need exponents in {0, 1}: the general exponents' pow() of the averages is taken on the host per call");
+  if (!std::isfinite(last_update)) return fail(RS_ERR_INVALID, "last_update is not finite");
+  for (size_t i = 0; i < 2 * U; i++) {
+    if (has_bearer[i] && !(avg[i] >= 1 && avg[i] <= kBearerAvgMax)) /* (false for NaN) */
+      return fail(RS_ERR_INVALID, "avg[%zu][%zu] = %g outside 1..2^51 (an updated average is never below 1; the bound above keeps the FP32 filter's range)", i / 2, i % 2, avg[i]);
+    if (cum_bytes && cum_bytes[i] < 0) return fail(RS_ERR_INVALID, "cum_bytes[%zu][%zu] = %lld is negative", i / 2, i % 2, (long long)cum_bytes[i]);
+    if (cum_rbs && cum_rbs[i] < 0) return fail(RS_ERR_INVALID, "cum_rbs[%zu][%zu] = %lld is negative", i / 2, i % 2, (long long)cum_rbs[i]);
+  }
+  HIP_TRY(hipSetDevice(b->cfg.cell.device));
+  if (!group_alloc_bearer_stores(g) || !group_alloc_counter_stores(g))
+    return fail(RS_ERR_HIP, "allocation of the group's resident flows failed (%zu bytes)", 45 * nb);
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  g->counted[cell] = 0;
+  g->resident[cell] = 0; /* (until all six copies are through) */
+  /* a bearer that does not exist holds zeros: rs_group_get_flows reports them, the kernel neither reads nor writes them */
+  std::vector<double> a(2 * U);
+  std::vector<uint8_t> has(2 * U);
+  for (size_t i = 0; i < 2 * U; i++) {
+    has[i] = has_bearer[i] ? 1 : 0;
+    a[i] = has[i] ? avg[i] : 0.0;
+  }
+  HIP_TRY(hipMemcpy(g->d_qavg + (size_t)cell * 2 * U, a.data(), 16 * U, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(g->d_qpend + (size_t)cell * 2 * U, 0, 8 * U));
+  HIP_TRY(hipMemcpy(g->d_qhas + (size_t)cell * 2 * U, has.data(), 2 * U, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(g->d_rlast + cell, &last_update, 8, hipMemcpyHostToDevice));
+  std::vector<int64_t> cb(2 * U, 0), cr(2 * U, 0);
+  for (size_t i = 0; i < 2 * U; i++) {
+    if (cum_bytes && has[i]) cb[i] = cum_bytes[i];
+    if (cum_rbs && has[i]) cr[i] = cum_rbs[i];
+  }
+  HIP_TRY(hipMemcpy(g->d_cbytes + (size_t)cell * 2 * U, cb.data(), 16 * U, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(g->d_crbs + (size_t)cell * 2 * U, cr.data(), 16 * U, hipMemcpyHostToDevice));
+  memcpy(g->has_bearer.data() + (size_t)cell * 2 * U, has.data(), 2 * U);
+  g->resident[cell] = 3;
+  g->pending_zero[cell] = 1;
+  g->last_update[cell] = last_update;
+  return RS_OK;
+}
+
+int rs_group_get_flows(rs_group* g, int32_t cell, double* avg, int32_t* pending_bytes, double* last_update, int64_t* cum_bytes, int64_t* cum_rbs) {
+  if (!g) return fail(RS_ERR_INVALID, "null group");
+  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
+  if (g->resident[cell] != 3) return fail(RS_ERR_STATE, "cell %d is not flow-resident (rs_group_set_flows first)", cell);
+  rs_batch* b = g->b;
+  const size_t U = (size_t)b->U;
+  HIP_TRY(hipSetDevice(b->cfg.cell.device));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  if (avg) HIP_TRY(hipMemcpy(avg, g->d_qavg + (size_t)cell * 2 * U, 16 * U, hipMemcpyDeviceToHost));
+  if (pending_bytes) HIP_TRY(hipMemcpy(pending_bytes, g->d_qpend + (size_t)cell * 2 * U, 8 * U, hipMemcpyDeviceToHost));
+  if (last_update) HIP_TRY(hipMemcpy(last_update, g->d_rlast + cell, 8, hipMemcpyDeviceToHost));
   if (cum_bytes) HIP_TRY(hipMemcpy(cum_bytes, g->d_cbytes + (size_t)cell * 2 * U, 16 * U, hipMemcpyDeviceToHost));
   if (cum_rbs) HIP_TRY(hipMemcpy(cum_rbs, g->d_crbs + (size_t)cell * 2 * U, 16 * U, hipMemcpyDeviceToHost));
   return RS_OK;
@@ -3444,6 +3583,7 @@ const char* rs_group_kernel_name(rs_group* g) {
   if (!g) return "";
   /* (a resident call: the group's resident builds if rs_group_specialize_resident gave it some, else the built-in resident kernel --
    * whatever serves the plain calls) */
+  if (g->last_call_kind == kGroupFlows) return g->kname_flw; /* (built in only) */
   if (g->last_call_kind == kGroupQueued && g->last_call_counted) return g->kname_cnt; /* (built in only: no run-time build of the counted form) */
   if (g->last_call_kind == kGroupQueued) return g->last_call_qjit ? "rs_group_queued_kernel_jit" : g->kname_que; /* (likewise: rs_group_specialize_queued) */
   if (g->last_call_resident) return g->last_call_rjit ? "rs_group_resident_kernel_jit" : g->kname_res;

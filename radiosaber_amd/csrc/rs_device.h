@@ -358,7 +358,9 @@ struct RsLaunch {
    * "the bearer exists" -- indexed [user id][bearer], one stride of 2 U apart; grp_last, grp_gather and grp_uid below serve this form
    * too (a cell is resident in one form at a time).  grp_qin: per call SLOT, UserToSchedule::m_dataToTransmit[2] of the call's users
    * in call order, as the host formed them -- may lie in host memory, read once; grp_qdata: per cell, the workgroup's copy of them for
-   * the credit behind the body.  Read by the queued kernels alone; null in every other launch.  (Six words in front of the group
+   * the credit behind the body.  Read by the queued kernels alone; null in every other launch -- but for scheduler 1's flows form
+   * (rs_group_schedule_tti_flows, rs_group_flows_kernel), which keeps its flows in these bearer stores and in the counter stores above
+   * and reads from grp_qin one word per call position: the position's bearer, 0 or 1.  (Six words in front of the group
    * fields, whose places relative to one another and to the end of the block are pinned.) */
   double* grp_qavg;          /* [group cells][U][2] */
   int32_t* grp_qpend;        /* [group cells][U][2] */

@@ -778,7 +778,7 @@ template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
   constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
-  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = false, kGrpCnt = false;
+  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = false, kGrpCnt = false, kGrpFlow = false;
 #include "rs_phase_group.inc"
 }
 
@@ -789,7 +789,7 @@ template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_resident_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
   constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
-  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = true, kGrpQue = false, kGrpCnt = false;
+  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = true, kGrpQue = false, kGrpCnt = false, kGrpFlow = false;
 #include "rs_phase_group.inc"
 }
 
@@ -801,7 +801,7 @@ template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_queued_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
   constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
-  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = true, kGrpCnt = false;
+  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = true, kGrpCnt = false, kGrpFlow = false;
 #include "rs_phase_group.inc"
 }
 
@@ -812,7 +812,18 @@ template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_counted_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
   constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
-  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = true, kGrpCnt = true;
+  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = true, kGrpCnt = true, kGrpFlow = false;
+#include "rs_phase_group.inc"
+}
+
+/* ... and scheduler 1's flow-resident form (rs_group_schedule_tti_flows): DL_PF_PacketScheduler's unit is the flow, so a call position
+ * is one bearer of one user; the cell keeps both bearers' averages, pending bytes and counters on the device and the whole transport
+ * block is credited to the flow.  One kernel (rs_launch_group_flows); built in only: no run-time build of this form. */
+template <int SCHED, int EPT>
+__global__ void __launch_bounds__(512, 4) rs_group_flows_kernel(RsLaunch p) {
+  extern __shared__ __align__(16) unsigned char lds[];
+  constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
+  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = false, kGrpCnt = false, kGrpFlow = true;
 #include "rs_phase_group.inc"
 }
 #else
@@ -865,7 +876,7 @@ extern "C" __global__ void __launch_bounds__(RS_JIT_NT, RS_JIT_WPE) RS_GROUP_JIT
   constexpr RsCarve kCv = rs_carve(RS_JIT_S, RS_JIT_U, RS_JIT_R, RS_JIT_SCHED, RS_JIT_NT, RS_JIT_CARVEQ, RS_JIT_WIN);
   __shared__ __align__(16) unsigned char lds[kCv.lds_bytes];
   constexpr int kGrpSched = RS_JIT_SCHED, kGrpEpt = (RS_JIT_SCHED != 9 && RS_JIT_SCHED != 10) ? 0 : (kCv.ept <= 4 ? kCv.ept : 0);
-  constexpr bool kGrpFixed = true, kGrpRes = RS_JIT_GROUP_RESIDENT != 0, kGrpQue = RS_JIT_GROUP_QUEUED != 0, kGrpCnt = false;
+  constexpr bool kGrpFixed = true, kGrpRes = RS_JIT_GROUP_RESIDENT != 0, kGrpQue = RS_JIT_GROUP_QUEUED != 0, kGrpCnt = false, kGrpFlow = false;
 #include "rs_phase_group.inc"
 }
 #undef RS_GROUP_JIT_ENTRY
@@ -1140,6 +1151,17 @@ extern "C" hipError_t rs_launch_group_counted(const RsLaunch* p, int threads, hi
   return hipGetLastError();
 }
 
+/* a flows group call (rs_group_schedule_tti_flows): the same grid, scheduler 1's kernel that keeps the cells' flows on the device */
+extern "C" hipError_t rs_launch_group_flows(const RsLaunch* p, int threads, hipStream_t stream) {
+  dim3 grid(p->n_cells), block(threads);
+  if (p->sched != 1) return hipErrorInvalidValue;
+  if (!p->grp_qavg || !p->grp_qpend || !p->grp_qhas || !p->grp_qin || !p->grp_last || !p->grp_gather || !p->grp_uid || !p->grp_cbytes ||
+      !p->grp_crbs)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL((rs_group_flows_kernel<1, 0>), grid, block, p->lds_bytes, stream, *p);
+  return hipGetLastError();
+}
+
 extern "C" hipError_t rs_prepare_kernels(int max_lds_bytes) {
 #define RS_BOTH(SCHED_, EPT_) (const void*)rs_cell_kernel<SCHED_, EPT_, false>, (const void*)rs_cell_kernel<SCHED_, EPT_, true>
   const void* fns[] = {RS_BOTH(1, 0),  RS_BOTH(7, 0),  RS_BOTH(8, 0),  RS_BOTH(101, 0), RS_BOTH(103, 0), RS_BOTH(11, 0),
@@ -1171,7 +1193,8 @@ extern "C" hipError_t rs_prepare_kernels(int max_lds_bytes) {
                        (const void*)rs_group_counted_kernel<101, 0>, (const void*)rs_group_counted_kernel<103, 0>,
                        (const void*)rs_group_counted_kernel<9, 0>,   (const void*)rs_group_counted_kernel<9, 1>,
                        (const void*)rs_group_counted_kernel<9, 2>,   (const void*)rs_group_counted_kernel<9, 3>,
-                       (const void*)rs_group_counted_kernel<9, 4>};
+                       (const void*)rs_group_counted_kernel<9, 4>,
+                       (const void*)rs_group_flows_kernel<1, 0>};
 #undef RS_BOTH
 
   for (const void* f : fns) {

@@ -7,7 +7,7 @@
  * sequence number to the host.  Its acquire of the counter orders it behind every other workgroup's fence and release.
  *
  * The entry points of rs_kernels.hip include this text as their body, as rs_cell_body includes its phases: the kernels built into the
- * library (rs_group_kernel, rs_group_resident_kernel, rs_group_queued_kernel, rs_group_counted_kernel: shape in the launch block) and a group's own run-time
+ * library (rs_group_kernel, rs_group_resident_kernel, rs_group_queued_kernel, rs_group_counted_kernel, rs_group_flows_kernel: shape in the launch block) and a group's own run-time
  * builds (rs_group_kernel_jit, rs_group_specialize; rs_group_resident_kernel_jit, rs_group_specialize_resident;
  * rs_group_queued_kernel_jit, rs_group_specialize_queued).
  * The includer provides `p` (the launch block), `lds` and four constants: kGrpSched, kGrpEpt, kGrpFixed -- shape, workgroup size and LDS
@@ -39,8 +39,19 @@
  * position's allocated PRBs to the bearer's 64-bit counters and writes the position's row of the slot's sent block.  The PRB count is
  * G times the RBGs the position holds -- the body's link adaptation leaves, per call position, the set of RBG lanes that share it in
  * RsMisc::maskA / maskB (rs_phase_p5.inc), and the closing barrier hands them to every thread as it hands over the grants.  With kGrpCnt
- * false none of this text reaches the other instantiations. */
+ * false none of this text reaches the other instantiations.
+ *
+ * An eighth constant, kGrpFlow, makes the flow-resident form of scheduler 1 (rs_group_schedule_tti_flows, rs_group_flows_kernel; never
+ * with kGrpRes / kGrpQue, built in only): DL_PF_PacketScheduler races FLOWS -- bearers --, not users, so a call position is one bearer
+ * of one user (RRC-container order: a user may hold two adjacent positions).  The cell keeps the queued form's bearer stores and the
+ * counted form's counters; the update is the queued form's step 1, the call's average of a position is the flow's own (scheduler 1
+ * divides by it as it is: no sum, no 1 +), and behind the body the WHOLE transport block goes to the flow -- pending bytes, bytes
+ * counter, PRB counter --, no min with the data (ref: dl-pf-packet-scheduler.cpp:80-85).  The slot's bearer words (0 or 1 per call
+ * position) travel where the queued form's data words do (grp_qin), the gate is the plain PF call's (data_to_transmit, packed by the
+ * host).  With kGrpFlow false none of this text reaches the other instantiations. */
   static_assert(!kGrpCnt || (kGrpQue && !kGrpFixed), "the counted form is the queued form's, and built in only");
+  static_assert(!kGrpFlow || (!kGrpRes && !kGrpQue && !kGrpCnt && !kGrpFixed && kGrpSched == 1),
+                "the flows form is scheduler 1's, a resident form of its own, and built in only");
   const uint8_t* const in = p.grp_in + (size_t)blockIdx.x * (size_t)p.grp_in_stride;
   uint8_t* const out = p.grp_out + (size_t)blockIdx.x * (size_t)p.grp_out_stride;
   const RsGroupCell* const h = (const RsGroupCell*)in;
@@ -202,11 +213,55 @@
       q.avg = row;
     }
   }
+  if constexpr (kGrpFlow) {
+    const int nthreads = (int)blockDim.x;
+    const int n_all = p.U; /* the config's users: 2 n_all bearers, the stores' stride and the update's range */
+    double* const b_avg = p.grp_qavg + (size_t)cell * 2 * (size_t)n_all;
+    int32_t* const b_pend = p.grp_qpend + (size_t)cell * 2 * (size_t)n_all;
+    const uint8_t* const b_has = p.grp_qhas + (size_t)cell * 2 * (size_t)n_all;
+    auto dword = [&](const double* d) { return __hiloint2double(word((const int32_t*)d + 1), word((const int32_t*)d)); };
+    const double now = dword(&h->now);
+    const double last = dword(p.grp_last + cell);
+    /* 1. the update, for every EXISTING bearer of every user id of the cell: the queued form's step 1, operation by operation */
+    if (!(now == last)) {
+      const double dt = now - last;
+      for (int j = threadIdx.x; j < 2 * n_all; j += nthreads) {
+        if (b_has[j] == 0) continue;
+        double a = b_avg[j];
+        const int txb = b_pend[j];
+        double rate = (double)(int32_t)((uint32_t)txb * 8u) / dt;
+        const double beta = 0.02;
+        a = ((1 - beta) * a) + (beta * rate);
+        if (a < 1) a = 1;
+        b_avg[j] = a;
+        b_pend[j] = 0;
+      }
+    }
+    /* the one barrier of this form, as the queued form's */
+    __syncthreads();
+    if (threadIdx.x == 0 && !(now == last)) p.grp_last[cell] = now;
+    /* 2. the call's averages: position i is bearer fb[i] of user uid[i] (the host has checked: 0 or 1, the bearer exists, the id is
+     *    one of the config's), and its average is the flow's own.  Thread i writes entry i of both rows and is the thread that reads
+     *    them (the body's load phase and step 4: same stride).  q.U == 0, an update-only slot: the body is skipped below. */
+    if (q.U != 0) {
+      const int in_uid = word(&h->in_uid);
+      const int32_t* const uid = (const int32_t*)(data + in_uid);
+      const int32_t* const fb = p.grp_qin + (size_t)blockIdx.x * (size_t)p.grp_qin_stride;
+      double* const row = p.grp_gather + (size_t)cell * (size_t)n_all;
+      int32_t* const ids = p.grp_uid + (size_t)cell * (size_t)n_all;
+      for (int i = threadIdx.x; i < q.U; i += nthreads) {
+        const int f = 2 * (in_uid != 0 ? uid[i] : i) + fb[i];
+        row[i] = b_avg[f];
+        ids[i] = f;
+      }
+      q.avg = row;
+    }
+  }
   if constexpr (kGrpLean) { /* the plain call (rs_group_kernel_jit): no customised slices -- the slots' HoL delays and priority flags are not read */
     q.hol = nullptr;
     q.prio = nullptr;
   }
-  if constexpr (kGrpQue) {
+  if constexpr (kGrpQue || kGrpFlow) {
     /* (q.U is one word of the slot header: the skip is uniform for the whole workgroup, no barrier of the body is left half met) */
     if (q.U != 0) rs_cell_body<kGrpSched, kGrpEpt, kGrpFixed, true, false, true>(q, lds);
   } else {
@@ -265,6 +320,31 @@
           }
         }
         if constexpr (kGrpCnt) *(int2*)(srow + 2 * i) = make_int2(row_sent[0], row_sent[1]);
+      }
+    }
+  }
+  if constexpr (kGrpFlow) {
+    /* 4. DL_PF_PacketScheduler::DoStopSchedule (ref: dl-pf-packet-scheduler.cpp:80-85): the grant of a call position -- tbs_bits / 8,
+     *    from LDS, as the resident form's -- goes whole to the position's flow: UpdateTransmittedBytes(availableBytes) feeds the next
+     *    update and m_cumulateBytes, UpdateCumulateRBs the PRBs of the flow's block.  The PRB count: the counted form's lane masks.
+     *    A flow is named once per call, a cell once per launch: plain adds by the position's thread. */
+    if (q.U != 0) {
+      const int nthreads = (int)blockDim.x;
+      const int n_all = p.U;
+      const int32_t* const granted = (const int32_t*)(lds + p.off_tx);
+      int32_t* const b_pend = p.grp_qpend + (size_t)cell * 2 * (size_t)n_all;
+      int64_t* const c_bytes = p.grp_cbytes + (size_t)cell * 2 * (size_t)n_all;
+      int64_t* const c_rbs = p.grp_crbs + (size_t)cell * 2 * (size_t)n_all;
+      const int32_t* const ids = p.grp_uid + (size_t)cell * (size_t)n_all; /* entry i: written by this thread before the body */
+      const RsMisc* const cm = (const RsMisc*)(lds + p.off_misc);
+      for (int i = threadIdx.x; i < q.U; i += nthreads) {
+        const int bytes = granted[i];
+        if (bytes <= 0) continue;
+        const int f = ids[i];
+        const unsigned long long lanes = cm->maskA[(i + 1) & 63] & cm->maskB[(i + 1) >> 6];
+        b_pend[f] += bytes;
+        c_bytes[f] += (int64_t)bytes;
+        c_rbs[f] += (int64_t)(__popcll(lanes) * p.G);
       }
     }
   }

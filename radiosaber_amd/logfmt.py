@@ -285,6 +285,29 @@ def counted_call_lines(ts: int, ids, sent, hol_delay, cum_bytes, cum_rbs, app_of
     return out
 
 
+def flows_call_lines(ts: int, ids, flow_bearer, tbs_bits, hol_delay, cum_bytes, cum_rbs, app_of, user_to_slice) -> List[str]:
+    """The reference's "app:" lines of ONE cell's slot of a flows group call (GroupScheduler.schedule_tti_flows; scheduler 1,
+    dl-pf-packet-scheduler.cpp:89-96): one line per flow the call credited -- a position whose block holds a byte,
+    user_tbs_bits // 8 > 0 -- in FlowsToSchedule order, which is the call's: users ascending, bearer 0 before 1.
+    ts: the TTI's stamp; ids [n]: the positions' user ids (None: 0..n-1); flow_bearer [n]: their bearer words; tbs_bits [n]: the
+    result's user_tbs_bits; hol_delay [n]: the flows' GetHeadOfLinePacketDelay as the caller knows them, or None (0: InfiniteBuffer
+    flows); cum_bytes / cum_rbs [U][2] by user id: the cell's counters AFTER the call (get_flows); app_of: app_ids(slices);
+    user_to_slice: the slice map."""
+    tbs_bits = np.asarray(tbs_bits).reshape(-1)
+    n = tbs_bits.shape[0]
+    ids = np.arange(n) if ids is None else np.asarray(ids)
+    fb = np.asarray(flow_bearer).reshape(-1)
+    hol = np.zeros(n) if hol_delay is None else np.asarray(hol_delay, np.float64)
+    assert ids.shape == (n,) and fb.shape == (n,) and hol.shape == (n,)
+    cum_bytes, cum_rbs, app_of = np.asarray(cum_bytes), np.asarray(cum_rbs), np.asarray(app_of)
+    out = []
+    for i in range(n):
+        if int(tbs_bits[i]) // 8 > 0:
+            u, k = int(ids[i]), int(fb[i])
+            out.append(BearerLogWriter.counter_line(ts, app_of[u, k], int(cum_bytes[u, k]), int(cum_rbs[u, k]), hol[i], u, user_to_slice[u]))
+    return out
+
+
 # reducers of the customised-slice experiment (what exp-customization/plot_fctdelay.py computes from a run's stderr)
 def _words(line: str):
     return line.split()

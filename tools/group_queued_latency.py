@@ -3,7 +3,7 @@
 call followed by rs_group_set_pending per cell -- and, as the regression check, the plain and the resident call, which another
 checkout can be measured on as well (profiles/group_queued.md).
 
-    python tools/group_queued_latency.py [--variant plain|resident|resident+pending|queued|queued-spec|queued+host|counted|all] [--calls 300]
+    python tools/group_queued_latency.py [--variant plain|resident|resident+pending|queued|queued-spec|queued+host|counted|all|flows|plain-pf+host] [--calls 300]
     RS_TREE=<another checkout> python tools/group_queued_latency.py --variant plain     # that tree's package
     python tools/group_queued_latency.py --variant queued-spec --cells 27 --shapes 500x25x4 500x64x8 --sched 9 7
 
@@ -15,7 +15,14 @@ host arrays; counted: the counted call, which returns the bytes sent and keeps t
 reports every 40 calls).  --shapes takes users x RBGs x PRBs per RBG (20 equal slices).  Scheduler 7 names the users of one slice per
 call, the slice rotating with the call, and gives no required_rbs.  Timed through the Python layer, marshalling included, like
 tools/group_resident_latency.py: three repetitions per line, whose spread is the yardstick for a difference between lines; p50 / p99
-are taken over the timed calls of all three."""
+are taken over the timed calls of all three.
+
+flows / plain-pf+host (profiles/group_flows.md; not part of `all`): scheduler 1 whatever --sched says.  Every user has bearer 0 and
+every fifth user bearer 1 as well, all with data, so a call holds 1.2 x users positions and the group is created with that many.
+flows: rs_group_schedule_tti_flows, everything on the device.  plain-pf+host: what a scheduler-1 host did before -- per cell the
+EWMA of every bearer in numpy, rs_group_schedule_tti with the flows' averages and the data_to_transmit gate, then
+DL_PF_PacketScheduler::DoStopSchedule's credit (pending bytes, byte and RB counters per bearer) in numpy; it runs on an older checkout
+too (RS_TREE)."""
 import argparse
 import os
 import sys
@@ -28,6 +35,68 @@ sys.path.insert(0, os.environ.get("RS_TREE", str(Path(__file__).resolve().parent
 import radiosaber_amd as rs  # noqa: E402
 
 VARIANTS = ("plain", "resident", "resident+pending", "queued", "queued-spec", "queued+host", "counted")
+FLOW_VARIANTS = ("flows", "plain-pf+host")
+
+
+def host_ewma(avg, pend, has, now, last):
+    """UpdateAverageTransmissionRate of every existing bearer of one cell on the host, [U][2] arrays"""
+    rate = (pend * np.int32(8)).astype(np.float64) / (now - last)
+    a = ((1 - 0.02) * avg) + (0.02 * rate)
+    avg[has] = np.where(a < 1, 1.0, a)[has]
+    pend[has] = 0
+
+
+def run_flows(variant, U, R, G, K, calls_n, warmup):
+    """one line of the flows comparison"""
+    uid = np.sort(np.concatenate([np.arange(U), np.arange(0, U, 5)])).astype(np.int32)
+    fb = np.zeros(len(uid), np.uint8)
+    fb[1:][uid[1:] == uid[:-1]] = 1
+    F = len(uid)
+    cap = -(-F // 20) * 20
+    sc = rs.SliceConfig([cap // 20] * 20, weight=[0.05] * 20)
+    g = rs.GroupScheduler(sc, R, G, K, sched=rs.RS_SCHED_PF)
+    rng = np.random.default_rng(1)
+    cqi = [rng.integers(1, 16, (U, R)).astype(np.uint8)[uid] for _ in range(K)]
+    has = np.zeros((cap, 2), bool)
+    has[uid, fb] = True
+    avg = [np.where(has, rng.uniform(1e4, 1e6, (cap, 2)), 0.0) for _ in range(K)]
+    data = np.where(fb == 0, 100000000, 300).astype(np.int32)
+    pend = [np.zeros((cap, 2), np.int32) for _ in range(K)]
+    host_bytes = [np.zeros((cap, 2), np.int64) for _ in range(K)]
+    host_rbs = [np.zeros((cap, 2), np.int64) for _ in range(K)]
+    if variant == "flows":
+        for k in range(K):
+            g.set_flows(k, has, avg[k], 0.1)
+    now, best, each = 0.1, [], []
+    for rep in range(3):
+        t0 = 0.0
+        for i in range(warmup + calls_n):
+            if i == warmup:
+                t0 = time.perf_counter()
+            last, now = now, now + 0.001
+            calls = [dict(cqi=cqi[k], user_id=uid, data_to_transmit=data, cqi_epoch=1 + i // 40) for k in range(K)]
+            t1 = time.perf_counter()
+            if variant == "flows":
+                for k in range(K):
+                    calls[k]["flow_bearer"] = fb
+                g.schedule_tti_flows(calls, now)
+            else:
+                for k in range(K):
+                    host_ewma(avg[k], pend[k], has, now, last)
+                    calls[k]["avg_rate"] = avg[k][uid, fb]
+                    del calls[k]["user_id"]  # (the plain call takes a user once: the host names its flows by position)
+                res = g.schedule_tti(calls)
+                for k in range(K):
+                    sent = res[k].user_tbs_bits // 8
+                    pend[k][uid, fb] += sent
+                    host_bytes[k][uid, fb] += sent
+                    host_rbs[k][uid, fb] += np.where(sent > 0, res[k].user_nprb, 0)
+            if i >= warmup:
+                each.append((time.perf_counter() - t1) * 1e6)
+        best.append((time.perf_counter() - t0) / calls_n * 1e6)
+    print(f"{K:3d} cells x {U} UEs ({F} flows) x {R} RBGs, {variant:16s}: " + " / ".join(f"{b:.1f}" for b in best) + f" us per call (python), p50 {np.percentile(each, 50):.1f} p99 {np.percentile(each, 99):.1f}, sched 1, {g.kernel_name}",
+          flush=True)
+    g.close()
 
 
 def host_credit(res, data, ids, cum_bytes, cum_rbs):
@@ -42,13 +111,20 @@ def host_credit(res, data, ids, cum_bytes, cum_rbs):
     cum_rbs[rows] += np.where(sent > 0, res.user_nprb[:, None], 0)
     return sent
 ap = argparse.ArgumentParser()
-ap.add_argument("--variant", default="all", choices=VARIANTS + ("all",))
+ap.add_argument("--variant", default="all", choices=VARIANTS + ("all",) + FLOW_VARIANTS)
 ap.add_argument("--calls", type=int, default=300)
 ap.add_argument("--warmup", type=int, default=40)
 ap.add_argument("--cells", type=int, nargs="+", default=[8, 64])
 ap.add_argument("--shapes", nargs="+", default=["100x64x8", "500x25x4"], help="users x RBGs x PRBs per RBG")
 ap.add_argument("--sched", type=int, nargs="+", default=[9])
 args = ap.parse_args()
+
+if args.variant in FLOW_VARIANTS:
+    for shape in args.shapes:
+        U, R, G = (int(v) for v in shape.split("x"))
+        for K in args.cells:
+            run_flows(args.variant, U, R, G, K, args.calls, args.warmup)
+    sys.exit(0)
 
 for sched, shape in ((s, x) for s in args.sched for x in args.shapes):
     U, R, G = (int(v) for v in shape.split("x"))
