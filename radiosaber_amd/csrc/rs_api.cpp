@@ -2027,6 +2027,61 @@ void unpack_tti(const rs_batch* b, const rs_tti_in* in, rs_tti_out* out, const u
     out->user_tbs_bits[i] = h_tbs[i];
   }
 }
+
+/* The self-check of a run-time build, one call's output block (layout `l`, n users): `mine` against the built-in kernel's `ref`, field
+ * by field; the first difference is the message (`what` stays empty when there is none).  cell >= 0: a group's slot, named in front.
+ * Shared by rs_schedule_tti and rs_group_schedule_tti. */
+void compare_out_block(const uint8_t* mine, const uint8_t* ref, const CtxLayout& l, int R, int S, int n, bool want_upper, int cell, char* what,
+                       size_t len) {
+  char pre[24] = "";
+  if (cell >= 0) snprintf(pre, sizeof pre, "cell %d: ", cell);
+  auto differ = [&](const char* name, size_t off, int count, auto elem) {
+    using T = decltype(elem);
+    const T *a = (const T*)(mine + off), *r = (const T*)(ref + off);
+    for (int i = 0; i < count && !what[0]; i++)
+      if (a[i] != r[i]) snprintf(what, len, "%s%s[%d] = %d, the built-in kernel's %d", pre, name, i, (int)a[i], (int)r[i]);
+  };
+  differ("rbg_to_user (call position)", l.map, R, int16_t());
+  differ("quota_rbgs", l.quota, S, int16_t());
+  differ("target_rbs", l.target, S, int16_t());
+  differ("user_tbs_bits", l.tbs, n, int32_t());
+  differ("user_nprb | final_cqi << 16 | mcs << 24", l.uinfo, n, int32_t());
+  if (want_upper) differ("upper lists", l.upper, S * R, int32_t());
+}
+
+/* Completion by the pinned word: the kernel's last store publishes the call's sequence number behind its outputs (release, system
+ * scope; a group: the last workgroup to finish, behind every workgroup's).  Spins on the word for at most `limit_us`; true when the
+ * number was seen -- then the stream's own bookkeeping is settled without waiting: every 64th such call asks it, so that nothing piles
+ * up in the runtime. */
+bool poll_done_word(const uint8_t* word, uint32_t seq, long limit_us, long* n_polled, hipStream_t st) {
+  using clk = std::chrono::steady_clock;
+  const clk::time_point give_up = clk::now() + std::chrono::microseconds(limit_us);
+  for (unsigned spins = 0;; ++spins) {
+    if (__atomic_load_n((const uint32_t*)word, __ATOMIC_ACQUIRE) == seq) break;
+    __builtin_ia32_pause();
+    if ((spins & 255u) == 255u && clk::now() > give_up) return false;
+  }
+  if ((++*n_polled & 63) == 0) (void)hipStreamQuery(st);
+  return true;
+}
+
+/* How many calls a run-time build serves beside the built-in kernel before it is trusted (see rs_ctx_jit_status in the header): none for
+ * a build that came from the cache with the mark of an earlier process's check, or that is not there at all */
+int selfcheck_calls(RsJitKernel* k) {
+  int calls = 8;
+  if (const char* e = getenv("RS_DROPIN_SELFCHECK_CALLS")) calls = atoi(e) > 0 ? atoi(e) : 0;
+  const char* pol = getenv("RS_JIT_SELFCHECK");
+  const bool never = pol && pol[0] == '0', always = pol && pol[0] == '2';
+  return (k && !never && (always || !rs_jit_is_verified(k))) ? calls : 0;
+}
+/* one build's part of a *_jit_status message: how it earned (or is still earning) its trust; ref: what its checked calls agree with */
+void selfcheck_state(RsJitKernel* k, int left, int agreed, const char* ref, char* out, size_t n) {
+  if (!k) snprintf(out, n, "not built");
+  else if (left > 0) snprintf(out, n, "%d checked call(s) agreed with %s, %d to go", agreed, ref, left);
+  else if (agreed > 0) snprintf(out, n, "verified (%d checked calls agreed with %s)", agreed, ref);
+  else if (rs_jit_is_verified(k)) snprintf(out, n, "carries the self-check mark of an earlier check (cache file)");
+  else snprintf(out, n, "unchecked (RS_JIT_SELFCHECK=0)");
+}
 }  // namespace
 
 extern "C" {
@@ -2223,7 +2278,6 @@ int rs_schedule_tti(rs_ctx* c, const rs_tti_in* in, rs_tti_out* out) {
      * a wrong image would show in the checked calls that read it) */
   }
   const bool poll = zc && c->poll && !checked_call;
-  volatile uint32_t* const h_flag = (volatile uint32_t*)(c->h_out + c->flag_off);
   if (poll) {
     if (++c->seq == 0) c->seq = 1; /* (0 is the word's initial value) */
     L.done_flag = (uint32_t*)(c->z_out + c->flag_off);
@@ -2235,20 +2289,8 @@ int rs_schedule_tti(rs_ctx* c, const rs_tti_in* in, rs_tti_out* out) {
   const clk::time_point t2 = c->timing ? clk::now() : clk::time_point();
   bool seen = false;
   if (poll) {
-    /* the kernel's last store publishes the sequence number after its outputs (release, system scope): spin on the pinned word */
-    const clk::time_point give_up = clk::now() + std::chrono::microseconds(c->poll_us);
-    for (unsigned spins = 0;; ++spins) {
-      if (__atomic_load_n((const uint32_t*)h_flag, __ATOMIC_ACQUIRE) == c->seq) { seen = true; break; }
-      __builtin_ia32_pause();
-      if ((spins & 255u) == 255u && clk::now() > give_up) break;
-    }
-    if (seen) {
-      c->n_polled++;
-      /* the stream's own bookkeeping is settled without waiting: every 64th call asks it, so that nothing piles up in the runtime */
-      if ((c->n_polled & 63) == 0) (void)hipStreamQuery(st);
-    } else {
-      c->n_fallback++;
-    }
+    seen = poll_done_word(c->h_out + c->flag_off, c->seq, c->poll_us, &c->n_polled, st);
+    if (!seen) c->n_fallback++; /* (a context counts the polled calls that fell back, not every stream wait) */
   }
   if (!seen) HIP_TRY(hipStreamSynchronize(st));
   if (checked_call) {
@@ -2256,24 +2298,9 @@ int rs_schedule_tti(rs_ctx* c, const rs_tti_in* in, rs_tti_out* out) {
     std::vector<double> ss_jit(S), ss_ref(S);
     HIP_TRY(hipMemcpy(ss_jit.data(), b->d_sstate, sstate_bytes, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(ss_ref.data(), c->d_chk + chk_half, sstate_bytes, hipMemcpyDeviceToHost));
-    const uint8_t *ho = c->h_out, *hr = c->h_out2.data();
+    const uint8_t* const hr = c->h_out2.data();
     char what[200] = "";
-    auto differ32 = [&](const char* name, size_t off, int count) {
-      const int32_t *a = (const int32_t*)(ho + off), *r = (const int32_t*)(hr + off);
-      for (int i = 0; i < count && !what[0]; i++)
-        if (a[i] != r[i]) snprintf(what, sizeof what, "%s[%d] = %d, the built-in kernel's %d", name, i, a[i], r[i]);
-    };
-    auto differ16 = [&](const char* name, size_t off, int count) {
-      const int16_t *a = (const int16_t*)(ho + off), *r = (const int16_t*)(hr + off);
-      for (int i = 0; i < count && !what[0]; i++)
-        if (a[i] != r[i]) snprintf(what, sizeof what, "%s[%d] = %d, the built-in kernel's %d", name, i, a[i], r[i]);
-    };
-    differ16("rbg_to_user (call position)", l.map, R);
-    differ16("quota_rbgs", l.quota, S);
-    differ16("target_rbs", l.target, S);
-    differ32("user_tbs_bits", l.tbs, n);
-    differ32("user_nprb | final_cqi << 16 | mcs << 24", l.uinfo, n);
-    if (want_upper) differ32("upper lists", l.upper, S * R);
+    compare_out_block(c->h_out, hr, l, R, S, n, want_upper, -1, what, sizeof what);
     for (int i = 0; i < S && !what[0]; i++)
       if (to_bits(ss_jit[i]) != to_bits(ss_ref[i])) snprintf(what, sizeof what, "slice state[%d] = %a, the built-in kernel's %a", i, ss_jit[i], ss_ref[i]);
     if (what[0]) {
@@ -2343,15 +2370,9 @@ int rs_ctx_specialize(rs_ctx* c) {
     char msg[512] = "";
     b->jit_lean = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, gate_scratch ? 1 : 0, 0, msg, sizeof msg, 1 | 4);
   }
-  /* how many calls each build serves beside the built-in kernel before it is trusted (see rs_ctx_jit_status in the header): none for a
-   * build that came from the cache with the mark of an earlier process's check */
-  int calls = 8;
-  if (const char* e = getenv("RS_DROPIN_SELFCHECK_CALLS")) calls = atoi(e) > 0 ? atoi(e) : 0;
-  const char* pol = getenv("RS_JIT_SELFCHECK");
-  const bool never = pol && pol[0] == '0', always = pol && pol[0] == '2';
   c->chk_agreed[0] = c->chk_agreed[1] = 0;
-  c->chk_left[0] = (!never && (always || !rs_jit_is_verified(b->jit))) ? calls : 0;
-  c->chk_left[1] = (b->jit_lean && !never && (always || !rs_jit_is_verified(b->jit_lean))) ? calls : 0;
+  c->chk_left[0] = selfcheck_calls(b->jit);
+  c->chk_left[1] = selfcheck_calls(b->jit_lean);
   return RS_OK;
 }
 
@@ -2362,17 +2383,9 @@ int rs_ctx_jit_status(rs_ctx* c, char* msg, size_t msglen) {
     if (c->jit_dropped || !b->jit) {
       snprintf(msg, msglen, "%s", c->jit_msg);
     } else {
-      /* per build: how it earned (or is still earning) its trust */
-      auto state = [&](RsJitKernel* k, int which, char* out, size_t n) {
-        if (!k) snprintf(out, n, "not built");
-        else if (c->chk_left[which] > 0) snprintf(out, n, "%d checked call(s) agreed with the built-in kernel field by field, %d to go", c->chk_agreed[which], c->chk_left[which]);
-        else if (c->chk_agreed[which] > 0) snprintf(out, n, "verified (%d checked calls agreed with the built-in kernel field by field)", c->chk_agreed[which]);
-        else if (rs_jit_is_verified(k)) snprintf(out, n, "carries the self-check mark of an earlier check (cache file)");
-        else snprintf(out, n, "unchecked (RS_JIT_SELFCHECK=0)");
-      };
       char g[160], l[160];
-      state(b->jit, 0, g, sizeof g);
-      state(b->jit_lean, 1, l, sizeof l);
+      selfcheck_state(b->jit, c->chk_left[0], c->chk_agreed[0], "the built-in kernel field by field", g, sizeof g);
+      selfcheck_state(b->jit_lean, c->chk_left[1], c->chk_agreed[1], "the built-in kernel field by field", l, sizeof l);
       snprintf(msg, msglen, "general build: %s; lean build: %s", g, l);
     }
   }
@@ -2432,15 +2445,22 @@ struct rs_group {
   bool timing = false;
   double t_prep = 0, t_enq = 0, t_wait = 0, t_unpack = 0;
   long n_calls = 0, n_cell_ttis = 0, n_polled = 0, n_fallback = 0;
-  char kname[48] = "";
-  /* rs_group_specialize: the group's own builds of the one-TTI form (index 0: general build, 1: lean build for the plain call), and
-   * their check against the built-in group kernel -- calls still to be checked, calls that agreed so far (rs_ctx's scheme) */
-  RsJitKernel* jit[2] = {nullptr, nullptr};
-  bool jit_wanted = false, jit_dropped = false;
-  int chk_left[2] = {0, 0}, chk_agreed[2] = {0, 0};
-  uint8_t *d_out2 = nullptr, *d_chk = nullptr; /* the built-in kernel's output slots; the group's slice state + scalars before / after it */
+  /* Run-time builds of a group call's kernel (rs_group_specialize, rs_group_specialize_resident, rs_group_specialize_queued): one pair
+   * of builds per form that has any (index 0: general build, 1: lean build for the plain call), and their check against the form's
+   * built-in kernel -- calls still to be checked, calls that agreed so far (rs_ctx's scheme).  The three pairs are independent: each
+   * serves its own kind of call, is checked against its own built-in kernel and is dropped alone.  The check of a form with stores
+   * (kGroupForms) also compares those: d_stores_chk holds them before the built-in kernel ran and as that kernel left them (two halves,
+   * group_copy_stores). */
+  struct GroupPair {
+    RsJitKernel* jit[2] = {nullptr, nullptr};
+    bool wanted = false, dropped = false;
+    int chk_left[2] = {0, 0}, chk_agreed[2] = {0, 0};
+    uint8_t* d_stores_chk = nullptr;
+    char msg[512] = "";
+  };
+  GroupPair pair[3]; /* by kGroupPlain, kGroupResident, kGroupQueued */
+  uint8_t *d_out2 = nullptr, *d_chk = nullptr; /* every pair's: the built-in kernel's output slots; the group's slice state + scalars before / after it */
   std::vector<uint8_t> h_out2;
-  char jit_msg[512] = "";
   /* resident averages (rs_group_set_avg, rs_group_schedule_tti_at): per cell [U] averages, [U] pending bytes and the time of their
    * last update on the device (allocated by the first rs_group_set_avg), the gather rows of calls that name their users, and on the
    * host which cells are resident and a mirror of their last-update times (the clock check needs no read-back) */
@@ -2448,16 +2468,6 @@ struct rs_group {
   int32_t *d_rpend = nullptr, *d_ruid = nullptr;
   std::vector<uint8_t> resident, pending_zero; /* pending_zero: no byte can be waiting (nothing served since rs_group_set_avg / an all-zero rs_group_set_pending) */
   std::vector<double> last_update;
-  bool last_call_resident = false;
-  char kname_res[56] = "";
-  /* rs_group_specialize_resident: the group's own builds of the RESIDENT form, a pair of its own beside jit[] with the same scheme (index
-   * 0 general, 1 lean; calls still to be checked, calls that agreed).  Its check also compares the resident stores: d_rchk holds them
-   * before the built-in resident kernel ran and as that kernel left them (two halves, group_rchk_half). */
-  RsJitKernel* rjit[2] = {nullptr, nullptr};
-  bool rjit_wanted = false, rjit_dropped = false, last_call_rjit = false;
-  int rchk_left[2] = {0, 0}, rchk_agreed[2] = {0, 0};
-  uint8_t* d_rchk = nullptr;
-  char rjit_msg[512] = "";
   /* resident bearers (rs_group_set_bearers, rs_group_schedule_tti_queued): per cell [U][2] averages, pending bytes and existence bytes
    * of the users' two bearers and the call's data words in call order (allocated by the first rs_group_set_bearers); d_rlast, d_rgather
    * and d_ruid above serve both forms.  resident[cell] says which: 0 none, 1 averages (rs_group_set_avg), 2 bearers.  The slots' data
@@ -2467,16 +2477,6 @@ struct rs_group {
   int32_t *d_qpend = nullptr, *d_qdata = nullptr, *h_qin = nullptr, *z_qin = nullptr, *d_qin = nullptr;
   uint8_t* d_qhas = nullptr;
   std::vector<uint8_t> has_bearer, empty_slot; /* empty_slot: per call slot, n_users == 0 (an update-only slot of a queued call) */
-  int last_call_kind = 0; /* 0 plain, 1 resident, 2 queued */
-  char kname_que[56] = "";
-  /* rs_group_specialize_queued: the group's own builds of the QUEUED form, a third pair beside jit[] and rjit[] with the same scheme.
-   * Its check compares the bearer stores: d_qchk holds them before the built-in queued kernel ran and as that kernel left them (two
-   * halves, group_qchk_half). */
-  RsJitKernel* qjit[2] = {nullptr, nullptr};
-  bool qjit_wanted = false, qjit_dropped = false, last_call_qjit = false;
-  int qchk_left[2] = {0, 0}, qchk_agreed[2] = {0, 0};
-  uint8_t* d_qchk = nullptr;
-  char qjit_msg[512] = "";
   /* counted bearers (rs_group_set_counters, rs_group_schedule_tti_counted): per cell [U][2] m_cumulateBytes / m_cumulateRBs beside the
    * bearer stores (allocated by the first rs_group_set_counters), and which cells are counted -- a state on top of resident[cell] == 2.
    * The slots' sent rows come back in a pinned block of their own (h_sent: [n_cells][U][2], mapped: z_sent, else copied from d_sent),
@@ -2484,29 +2484,96 @@ struct rs_group {
   int64_t *d_cbytes = nullptr, *d_crbs = nullptr;
   int32_t *h_sent = nullptr, *z_sent = nullptr, *d_sent = nullptr;
   std::vector<uint8_t> counted;
-  bool last_call_counted = false;
-  char kname_cnt[56] = "";
   /* resident flows (rs_group_set_flows, rs_group_schedule_tti_flows; scheduler 1 alone): resident[cell] == 3.  The cell's flows live in
    * the bearer stores and the counter stores above (a cell is resident in one form at a time), has_bearer mirrors their existence
    * bytes, and the slots' bearer words (0 or 1 per call position) travel in h_qin, one word per position.  Flows calls run the
    * built-in flows kernel: no run-time build of this form. */
-  char kname_flw[56] = "";
+  /* rs_group_kernel_name: the last call's form (a row of kGroupForms), whether a run-time build served it, the built-in kernels' names by row */
+  int last_call_form = 0;
+  bool last_call_jit = false;
+  char kname[5][56] = {"", "", "", "", ""};
 };
 
+extern "C" hipError_t rs_launch_group(const RsLaunch* p, int threads, hipStream_t stream);
+extern "C" hipError_t rs_launch_group_resident(const RsLaunch* p, int threads, hipStream_t stream);
+extern "C" hipError_t rs_launch_group_queued(const RsLaunch* p, int threads, hipStream_t stream);
+extern "C" hipError_t rs_launch_group_counted(const RsLaunch* p, int threads, hipStream_t stream);
+extern "C" hipError_t rs_launch_group_flows(const RsLaunch* p, int threads, hipStream_t stream);
+
 namespace {
+/* The forms of a group call, one row each: what differs between them outside the validation of their inputs.  A call's row is its
+ * form, the counted twin of the queued form (rs_group_schedule_tti_counted) has the fifth. */
+enum { kGroupPlain = 0, kGroupResident = 1, kGroupQueued = 2, kGroupFlows = 3, kGroupCounted = 4 };
+enum : unsigned { /* the RsLaunch pointer sets a form's kernel reads */
+  kSetResident = 1, /* grp_avg, grp_pending, grp_last, grp_gather, grp_uid */
+  kSetBearers = 2,  /* grp_qavg, grp_qpend, grp_qhas, grp_qdata and the slots' word block grp_qin (data words; a flows call: bearer words) */
+  kSetCounters = 4, /* grp_cbytes, grp_crbs */
+  kSetSent = 8,     /* grp_sent: the slots' sent rows */
+};
+struct GroupForm {
+  hipError_t (*launch)(const RsLaunch*, int, hipStream_t); /* the built-in launcher */
+  unsigned sets;
+  bool slots0;     /* update-only slots (n_users == 0) are allowed */
+  int pair;        /* rs_group::pair[] that serves the form, -1: built-in kernel only */
+  int store_width; /* the stores its self-check saves, restores and compares: 0 none, 1 the resident stores [U], 2 the bearer stores [U][2] */
+  int jit_flags;   /* rs_jit_get: 1 one-TTI form, 8 group wrapper, 16 resident, 32 queued */
+  const char* jit_name;
+  /* the nouns of the pair's messages: "specialised <adj>%s build", "both <adj>builds are dropped, <serves>", "agreed with <ref>",
+   * "copies of the <stores>" */
+  const char *adj, *serves, *ref, *stores;
+};
+const GroupForm kGroupForms[5] = {
+    {rs_launch_group, 0, false, kGroupPlain, 0, 1 | 8, "rs_group_kernel_jit", "", "the built-in kernels serve this group", "the built-in kernel field by field", ""},
+    {rs_launch_group_resident, kSetResident, false, kGroupResident, 1, 1 | 8 | 16, "rs_group_resident_kernel_jit", "resident ",
+     "the built-in resident kernel serves this group's resident calls", "the built-in resident kernel field by field, resident stores included", "resident stores"},
+    {rs_launch_group_queued, kSetResident | kSetBearers, true, kGroupQueued, 2, 1 | 8 | 32, "rs_group_queued_kernel_jit", "queued ",
+     "the built-in queued kernel serves this group's queued calls", "the built-in queued kernel field by field, bearer stores included", "bearer stores"},
+    {rs_launch_group_flows, kSetResident | kSetBearers | kSetCounters, true, -1, 0, 0, nullptr, "", "", "", ""},
+    {rs_launch_group_counted, kSetResident | kSetBearers | kSetCounters | kSetSent, true, -1, 0, 0, nullptr, "", "", "", ""},
+};
+
 /* bytes of one half of rs_group::d_chk: [n_cells][S] slice state, then [n_cells] RsCellScalars */
 size_t group_chk_sstate(const rs_group* g) { return round_up((int)(8 * (size_t)g->b->S * g->n_cells), 256); }
 size_t group_chk_half(const rs_group* g) { return group_chk_sstate(g) + round_up((int)(sizeof(RsCellScalars) * (size_t)g->n_cells), 256); }
-/* bytes of one half of rs_group::d_rchk: [n_cells][U] averages, then [n_cells] last-update times, then [n_cells][U] pending bytes */
-size_t group_rchk_avg(const rs_group* g) { return round_up((int)(8 * (size_t)g->b->U * g->n_cells), 256); }
-size_t group_rchk_last(const rs_group* g) { return round_up((int)(8 * (size_t)g->n_cells), 256); }
-size_t group_rchk_half(const rs_group* g) { return group_rchk_avg(g) + group_rchk_last(g) + round_up((int)(4 * (size_t)g->b->U * g->n_cells), 256); }
-/* bytes of one half of rs_group::d_qchk: [n_cells][U][2] averages, then [n_cells] last-update times, then [n_cells][U][2] pending bytes */
-size_t group_qchk_avg(const rs_group* g) { return round_up((int)(16 * (size_t)g->b->U * g->n_cells), 256); }
-size_t group_qchk_half(const rs_group* g) { return group_qchk_avg(g) + group_rchk_last(g) + round_up((int)(8 * (size_t)g->b->U * g->n_cells), 256); }
-}  // namespace
 
-extern "C" hipError_t rs_launch_group(const RsLaunch* p, int threads, hipStream_t stream);
+/* The stores that a form's self-check saves, restores and compares, in the order they lie in a half of GroupPair::d_stores_chk (each
+ * rounded up to 256 bytes): the averages, the cells' last-update times, the pending bytes -- of every user id of the config (the update
+ * touches them all), for the bearer stores of BOTH bearers. */
+struct GroupStore {
+  void* dev;        /* [n_cells][elems] */
+  size_t elems;     /* per cell */
+  bool f64;         /* doubles (compared bitwise, as the int32 of the other kind are) */
+  const char* name; /* in a message, followed by the element's index */
+  size_t size() const { return f64 ? 8 : 4; }
+  size_t bytes(const rs_group* g) const { return size() * elems * (size_t)g->n_cells; }
+  size_t kept(const rs_group* g) const { return (size_t)round_up((int)bytes(g), 256); }
+};
+struct GroupStores {
+  GroupStore part[3];
+  int n;       /* 0 or 3 */
+  size_t half; /* bytes of one half of the check block */
+};
+GroupStores group_stores(const rs_group* g, const GroupForm& f) {
+  if (!f.store_width) return {};
+  const bool two = f.store_width == 2;
+  const size_t e = (size_t)f.store_width * g->b->U;
+  GroupStores s = {{{two ? g->d_qavg : g->d_ravg, e, true, "avg"}, {g->d_rlast, 1, true, "last_update"},
+                    {two ? (void*)g->d_qpend : (void*)g->d_rpend, e, false, "pending_bytes"}}, 3, 0};
+  for (const GroupStore& x : s.part) s.half += x.kept(g);
+  return s;
+}
+/* a form's stores to (save) or from one half of its pair's check block */
+hipError_t group_copy_stores(const rs_group* g, const GroupForm& f, int half, bool save) {
+  const GroupStores s = group_stores(g, f);
+  uint8_t* kept = s.n ? g->pair[f.pair].d_stores_chk + (size_t)half * s.half : nullptr;
+  for (int i = 0; i < s.n; kept += s.part[i++].kept(g)) {
+    const GroupStore& x = s.part[i];
+    const hipError_t e = hipMemcpyAsync(save ? (void*)kept : x.dev, save ? x.dev : (void*)kept, x.bytes(g), hipMemcpyDeviceToDevice, g->b->stream);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+}  // namespace
 
 rs_group* rs_group_create_checked(const rs_config* cfg, int32_t n_cells, int abi_version, size_t cfg_size) {
   if (abi_version != RS_ABI_VERSION || cfg_size != sizeof(rs_config)) {
@@ -2576,11 +2643,11 @@ rs_group* rs_group_create(const rs_config* cfg, int32_t n_cells) {
   g->modes.assign(n_cells, 0);
   const int ept = (b->R * b->S + b->threads - 1) / b->threads;
   const bool sorts = b->sched == RS_SCHED_MAXCELL || b->sched == RS_SCHED_UPPERBOUND;
-  snprintf(g->kname, sizeof g->kname, "rs_group_kernel<%d, %d>", b->sched, sorts && ept <= 4 ? ept : 0);
-  snprintf(g->kname_res, sizeof g->kname_res, "rs_group_resident_kernel<%d, %d>", b->sched, sorts && ept <= 4 ? ept : 0);
-  snprintf(g->kname_que, sizeof g->kname_que, "rs_group_queued_kernel<%d, %d>", b->sched, b->sched == RS_SCHED_MAXCELL && ept <= 4 ? ept : 0);
-  snprintf(g->kname_cnt, sizeof g->kname_cnt, "rs_group_counted_kernel<%d, %d>", b->sched, b->sched == RS_SCHED_MAXCELL && ept <= 4 ? ept : 0);
-  snprintf(g->kname_flw, sizeof g->kname_flw, "rs_group_flows_kernel<%d, 0>", b->sched);
+  snprintf(g->kname[kGroupPlain], sizeof g->kname[0], "rs_group_kernel<%d, %d>", b->sched, sorts && ept <= 4 ? ept : 0);
+  snprintf(g->kname[kGroupResident], sizeof g->kname[0], "rs_group_resident_kernel<%d, %d>", b->sched, sorts && ept <= 4 ? ept : 0);
+  snprintf(g->kname[kGroupQueued], sizeof g->kname[0], "rs_group_queued_kernel<%d, %d>", b->sched, b->sched == RS_SCHED_MAXCELL && ept <= 4 ? ept : 0);
+  snprintf(g->kname[kGroupCounted], sizeof g->kname[0], "rs_group_counted_kernel<%d, %d>", b->sched, b->sched == RS_SCHED_MAXCELL && ept <= 4 ? ept : 0);
+  snprintf(g->kname[kGroupFlows], sizeof g->kname[0], "rs_group_flows_kernel<%d, 0>", b->sched);
   g->empty_slot.assign(n_cells, 0);
   g->resident.assign(n_cells, 0);
   g->counted.assign(n_cells, 0);
@@ -2597,40 +2664,16 @@ void rs_group_destroy(rs_group* g) {
             g->n_calls, (double)g->n_cell_ttis / g->n_calls, g->t_prep / g->n_calls, g->t_enq / g->n_calls, g->t_wait / g->n_calls,
             g->t_unpack / g->n_calls, g->n_polled, g->n_fallback, (long long)g->n_reused, (long long)g->n_stored, (long long)g->n_plain);
   if (g->b && g->b->stream) (void)hipStreamSynchronize(g->b->stream);
-  if (g->d_in) (void)hipFree(g->d_in);
-  if (g->d_out) (void)hipFree(g->d_out);
-  if (g->d_count) (void)hipFree(g->d_count);
-  if (g->d_img) (void)hipFree(g->d_img);
-  if (g->d_prb) (void)hipFree(g->d_prb);
-  if (g->d_out2) (void)hipFree(g->d_out2);
-  if (g->d_chk) (void)hipFree(g->d_chk);
-  if (g->d_rchk) (void)hipFree(g->d_rchk);
-  if (g->d_qchk) (void)hipFree(g->d_qchk);
-  if (g->d_ravg) (void)hipFree(g->d_ravg);
-  if (g->d_rpend) (void)hipFree(g->d_rpend);
-  if (g->d_rlast) (void)hipFree(g->d_rlast);
-  if (g->d_rgather) (void)hipFree(g->d_rgather);
-  if (g->d_ruid) (void)hipFree(g->d_ruid);
-  if (g->d_qavg) (void)hipFree(g->d_qavg);
-  if (g->d_qpend) (void)hipFree(g->d_qpend);
-  if (g->d_qdata) (void)hipFree(g->d_qdata);
-  if (g->d_qhas) (void)hipFree(g->d_qhas);
-  if (g->d_qin) (void)hipFree(g->d_qin);
-  if (g->h_qin) (void)hipHostFree(g->h_qin);
-  if (g->d_cbytes) (void)hipFree(g->d_cbytes);
-  if (g->d_crbs) (void)hipFree(g->d_crbs);
-  if (g->d_sent) (void)hipFree(g->d_sent);
-  if (g->h_sent) (void)hipHostFree(g->h_sent);
-  if (g->h_in) (void)hipHostFree(g->h_in);
-  if (g->h_out) (void)hipHostFree(g->h_out);
+  for (void* q : {(void*)g->d_in, (void*)g->d_out, (void*)g->d_count, (void*)g->d_img, (void*)g->d_prb, (void*)g->d_out2, (void*)g->d_chk,
+                  (void*)g->pair[0].d_stores_chk, (void*)g->pair[1].d_stores_chk, (void*)g->pair[2].d_stores_chk, (void*)g->d_ravg,
+                  (void*)g->d_rpend, (void*)g->d_rlast, (void*)g->d_rgather, (void*)g->d_ruid, (void*)g->d_qavg, (void*)g->d_qpend,
+                  (void*)g->d_qdata, (void*)g->d_qhas, (void*)g->d_qin, (void*)g->d_cbytes, (void*)g->d_crbs, (void*)g->d_sent})
+    if (q) (void)hipFree(q);
+  for (void* q : {(void*)g->h_qin, (void*)g->h_sent, (void*)g->h_in, (void*)g->h_out})
+    if (q) (void)hipHostFree(q);
   rs_batch_destroy(g->b);
   delete g;
 }
-
-extern "C" hipError_t rs_launch_group_resident(const RsLaunch* p, int threads, hipStream_t stream);
-extern "C" hipError_t rs_launch_group_queued(const RsLaunch* p, int threads, hipStream_t stream);
-extern "C" hipError_t rs_launch_group_counted(const RsLaunch* p, int threads, hipStream_t stream);
-extern "C" hipError_t rs_launch_group_flows(const RsLaunch* p, int threads, hipStream_t stream);
 
 namespace {
 /* Resident averages and the FP32 filter.  The metric scan's filter needs (1 + a) / 1000 (scheduler 1: a) inside [2^-60, 2^60] for every
@@ -2654,249 +2697,294 @@ constexpr double kResidentMinDt = 0x1p-20;
  * (1 + a0) + a1 exactly -- it does while that sum is below 2^53 -- and must stay inside the filter's range: rs_group_set_bearers refuses
  * a > 2^51, and the growth argument above carries over bearer by bearer (the same update, |rate| < 2^51): a <= 2^51 (1 + 2^-51)^k. */
 constexpr double kBearerAvgMax = 0x1p51;
-enum { kGroupPlain = 0, kGroupResident = 1, kGroupQueued = 2, kGroupFlows = 3 };
 
-int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out, const double* now,
-                   const int32_t* const* qdata = nullptr, bool cnt = false, int32_t* const* sent = nullptr,
-                   const uint8_t* const* flow = nullptr);
+/* One group call: what the caller gave, then what the phases of group_schedule decide along the way.  now != null: a resident form --
+ * averages (rs_group_schedule_tti_at) or, with qdata, bearers (rs_group_schedule_tti_queued; counted: its twin,
+ * rs_group_schedule_tti_counted, which differs in the kernel it launches, the two counter stores and the sent rows) or, with flow,
+ * scheduler 1's flows (rs_group_schedule_tti_flows: a call position is bearer flow[k][i] of user user_id[i]). */
+struct GroupCall {
+  int32_t n;
+  const int32_t* cell_ids;
+  const rs_tti_in* in;
+  rs_tti_out* out;
+  const double* now;            /* [n], the resident forms */
+  const int32_t* const* qdata;  /* [n][n_users][2], queued and counted */
+  int32_t* const* sent;         /* [n][n_users][2] or null, counted */
+  const uint8_t* const* flow;   /* [n][n_users], flows */
+  int form;                     /* kGroupPlain .. kGroupFlows */
+  bool counted;
+  /* group_validate: the presence of optional inputs is a per-launch switch of the kernel, the same for every cell of the call */
+  bool has_prb, has_hol, has_prio, has_gate, want_upper;
+  /* group_pack_slots: one cell outside the FP32 filter's range, the exact scan for all (same results); the per-PRB store failed in this call */
+  bool exact_scan, store_failed_now;
+  /* group_schedule: the kernel reads and writes the pinned blocks in place.  group_run: completion by the polled word; the run-time
+   * build that serves the call (null: the form's built-in kernel; which: 0 general, 1 lean) and whether the built-in kernel ran beside it */
+  bool zc, poll, checked;
+  RsJitKernel* kd;
+  int which;
+  int cell(int k) const { return cell_ids ? cell_ids[k] : k; }
+  bool resident() const { return form != kGroupPlain; }
+  int row() const { return counted ? (int)kGroupCounted : form; }
+  const GroupForm& desc() const { return kGroupForms[row()]; }
+};
+
+int group_schedule(rs_group* g, GroupCall c);
 }  // namespace
 
 int rs_group_schedule_tti(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out) {
   if (!g || !in || !out) return fail(RS_ERR_INVALID, "null argument");
-  return group_schedule(g, n, cell_ids, in, out, nullptr);
+  return group_schedule(g, {n, cell_ids, in, out, nullptr, nullptr, nullptr, nullptr, kGroupPlain, false});
 }
 
 int rs_group_schedule_tti_at(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out, const double* now) {
   if (!g || !in || !out || !now) return fail(RS_ERR_INVALID, "null argument");
-  return group_schedule(g, n, cell_ids, in, out, now);
+  return group_schedule(g, {n, cell_ids, in, out, now, nullptr, nullptr, nullptr, kGroupResident, false});
 }
 
 int rs_group_schedule_tti_queued(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out, const double* now,
                                  const int32_t* const* data_to_transmit) {
   if (!g || !in || !out || !now || !data_to_transmit) return fail(RS_ERR_INVALID, "null argument");
-  return group_schedule(g, n, cell_ids, in, out, now, data_to_transmit);
+  return group_schedule(g, {n, cell_ids, in, out, now, data_to_transmit, nullptr, nullptr, kGroupQueued, false});
 }
 
 int rs_group_schedule_tti_counted(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out, const double* now,
                                   const int32_t* const* data_to_transmit, int32_t* const* sent) {
   if (!g || !in || !out || !now || !data_to_transmit) return fail(RS_ERR_INVALID, "null argument");
-  return group_schedule(g, n, cell_ids, in, out, now, data_to_transmit, true, sent);
+  return group_schedule(g, {n, cell_ids, in, out, now, data_to_transmit, sent, nullptr, kGroupQueued, true});
 }
 
 int rs_group_schedule_tti_flows(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out, const double* now,
                                 const uint8_t* const* flow_bearer) {
   if (!g || !in || !out || !now || !flow_bearer) return fail(RS_ERR_INVALID, "null argument");
-  return group_schedule(g, n, cell_ids, in, out, now, nullptr, false, nullptr, flow_bearer);
+  return group_schedule(g, {n, cell_ids, in, out, now, nullptr, nullptr, flow_bearer, kGroupFlows, false});
 }
 
 namespace {
-/* one group call; now != null: a resident form -- averages (rs_group_schedule_tti_at) or, with qdata, bearers (rs_group_schedule_tti_queued;
- * cnt: its counted twin, rs_group_schedule_tti_counted, which differs in the kernel it launches, the two counter stores and the sent rows)
- * or, with flow, scheduler 1's flows (rs_group_schedule_tti_flows: a call position is bearer flow[k][i] of user user_id[i]) */
-int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, rs_tti_out* out, const double* now,
-                   const int32_t* const* qdata, bool cnt, int32_t* const* sent, const uint8_t* const* flow) {
-  rs_batch* b = g->b;
-  const bool res = now != nullptr, que = qdata != nullptr, flw = flow != nullptr;
-  const bool slots0 = que || flw; /* the forms whose calls may hold update-only slots (n_users == 0) */
-  const int kind = flw ? kGroupFlows : (que ? kGroupQueued : (res ? kGroupResident : kGroupPlain));
-  using clk = std::chrono::steady_clock;
-  const clk::time_point t0 = g->timing ? clk::now() : clk::time_point();
+/* a flows call's slot k (cell `cell`): positions are flows, (user, bearer) pairs in RRC-container order, each an existing bearer with
+ * data to transmit */
+int group_validate_flows_slot(const rs_group* g, const GroupCall& c, int k, int cell) {
+  const rs_batch* b = g->b;
+  const rs_tti_in& in = c.in[k];
+  const int nf = in.n_users;
+  if (nf > b->U) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): n_users %d (the call's flows) outside 0..%d", k, cell, nf, b->U);
+  if (in.hol_delay || in.prio_has_data || in.required_rbs)
+    return fail(RS_ERR_INVALID, "cell slot %d (cell %d): %s must be NULL in a flows call", k, cell,
+                in.hol_delay ? "hol_delay" : (in.prio_has_data ? "prio_has_data" : "required_rbs"));
+  if (nf > 0 && !c.flow[k]) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): flow_bearer[%d] is NULL (only an update-only slot, n_users == 0, gives none)", k, cell, k);
+  if (nf > 0 && !in.data_to_transmit) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): data_to_transmit is required: a flow is scheduled because it has data", k, cell);
+  const uint8_t* const has = g->has_bearer.data() + (size_t)cell * 2 * (size_t)b->U;
+  int prev = -1;
+  for (int i = 0; i < nf; i++) {
+    const int id = in.user_id ? in.user_id[i] : i, fb = c.flow[k][i];
+    if (id < 0 || id >= b->U) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): user id %d out of range", k, cell, id);
+    if (fb > 1) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): flow_bearer[%d] = %d is neither 0 nor 1", k, cell, i, fb);
+    if (2 * id + fb <= prev)
+      return fail(RS_ERR_INVALID, "cell slot %d (cell %d): call position %d (user %d, bearer %d) does not ascend: flows come in (user, bearer) order, each once", k, cell, i, id, fb);
+    prev = 2 * id + fb;
+    if (!has[prev]) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): call position %d names bearer %d of user %d, which does not exist (rs_group_set_flows)", k, cell, i, fb, id);
+    if (in.data_to_transmit[i] <= 0)
+      return fail(RS_ERR_INVALID, "cell slot %d (cell %d): data_to_transmit[%d] = %d: a flow without data is not scheduled", k, cell, i, in.data_to_transmit[i]);
+  }
+  return RS_OK;
+}
+
+/* Every cell is validated before the device is touched: a rejected call is a no-op (g->named is scratch, cleared again). */
+int group_validate(rs_group* g, GroupCall& c) {
+  const rs_batch* b = g->b;
+  const int n = c.n;
+  const int32_t* const cell_ids = c.cell_ids;
+  const rs_tti_in* const in = c.in;
+  const bool slots0 = c.desc().slots0;
   if (n < 1 || n > g->n_cells) return fail(RS_ERR_INVALID, "n %d outside 1..%d (the group's cells)", n, g->n_cells);
-  /* ---- every cell is validated before the device is touched: a rejected call is a no-op ---- */
   if (cell_ids) {
     int bad = -1, dup = -1;
     for (int k = 0; k < n && bad < 0 && dup < 0; k++) {
-      const int c = cell_ids[k];
-      if (c < 0 || c >= g->n_cells) bad = k;
-      else if (g->named[c]) dup = k;
-      else g->named[c] = 1;
+      const int cell = cell_ids[k];
+      if (cell < 0 || cell >= g->n_cells) bad = k;
+      else if (g->named[cell]) dup = k;
+      else g->named[cell] = 1;
     }
     for (int k = 0; k < n; k++)
       if (cell_ids[k] >= 0 && cell_ids[k] < g->n_cells) g->named[cell_ids[k]] = 0;
     if (bad >= 0) return fail(RS_ERR_INVALID, "cell_ids[%d] = %d outside 0..%d", bad, cell_ids[bad], g->n_cells - 1);
     if (dup >= 0) return fail(RS_ERR_INVALID, "cell_ids[%d] = %d names a cell twice", dup, cell_ids[dup]);
   }
-  /* the presence of optional inputs is a per-launch switch of the kernel: the same for every cell of the call */
   auto gate_of = [&](const rs_tti_in& t) { return b->sched == RS_SCHED_NVS ? t.required_rbs : (b->sched == RS_SCHED_PF ? t.data_to_transmit : nullptr); };
   auto upper_of = [&](const rs_tti_out& o) { return b->sched == RS_SCHED_UPPERBOUND && (o.upper_rbg || o.upper_user); };
-  /* (a queued call's update-only slots, n_users == 0, give no inputs at all: the slots WITH users agree among themselves) */
+  /* (a call's update-only slots, n_users == 0, give no inputs at all: the slots WITH users agree among themselves) */
   int k0 = 0;
   while (slots0 && k0 < n && in[k0].n_users == 0) k0++;
   const bool any_users = k0 < n;
   if (!any_users) k0 = 0;
-  const bool has_prb = any_users && in[k0].cqi_prb != nullptr, has_hol = any_users && in[k0].hol_delay != nullptr,
-             has_prio = any_users && in[k0].prio_has_data != nullptr, has_gate = any_users && gate_of(in[k0]) != nullptr,
-             want_upper = any_users && upper_of(out[k0]);
+  c.has_prb = any_users && in[k0].cqi_prb != nullptr;
+  c.has_hol = any_users && in[k0].hol_delay != nullptr;
+  c.has_prio = any_users && in[k0].prio_has_data != nullptr;
+  c.has_gate = any_users && gate_of(in[k0]) != nullptr;
+  c.want_upper = any_users && upper_of(c.out[k0]);
   for (int k = k0 + 1; k < n; k++) {
     if (slots0 && in[k].n_users == 0) continue;
-    const char* what = (in[k].cqi_prb != nullptr) != has_prb ? "cqi_prb" : (in[k].hol_delay != nullptr) != has_hol ? "hol_delay"
-                     : (in[k].prio_has_data != nullptr) != has_prio ? "prio_has_data"
-                     : (gate_of(in[k]) != nullptr) != has_gate ? (b->sched == RS_SCHED_NVS ? "required_rbs" : "data_to_transmit")
-                     : upper_of(out[k]) != want_upper ? "upper_rbg / upper_user" : nullptr;
+    const char* what = (in[k].cqi_prb != nullptr) != c.has_prb ? "cqi_prb" : (in[k].hol_delay != nullptr) != c.has_hol ? "hol_delay"
+                     : (in[k].prio_has_data != nullptr) != c.has_prio ? "prio_has_data"
+                     : (gate_of(in[k]) != nullptr) != c.has_gate ? (b->sched == RS_SCHED_NVS ? "required_rbs" : "data_to_transmit")
+                     : upper_of(c.out[k]) != c.want_upper ? "upper_rbg / upper_user" : nullptr;
     if (what) return fail(RS_ERR_INVALID, "mixed call: cell slot %d and cell slot %d differ in whether they give %s (optional inputs are given by every cell of a call or by none)", k, k0, what);
   }
-  if (res) {
-    if (b->gen_exp)
-      return fail(RS_ERR_INVALID, "resident averages need exponents in {0, 1}: the general exponents' pow() of the averages is taken on the host per call");
-    for (int k = 0; k < n; k++) {
-      const int cell = cell_ids ? cell_ids[k] : k;
-      if (in[k].avg_rate) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): avg_rate must be NULL: the cell's averages are resident on the device", k, cell);
-      if (flw && g->resident[cell] != 3) return fail(RS_ERR_STATE, "cell slot %d: cell %d is not flow-resident (rs_group_set_flows first)", k, cell);
-      if (!flw && g->resident[cell] == 3)
-        return fail(RS_ERR_STATE, "cell slot %d: cell %d is flow-resident (rs_group_set_flows): rs_group_schedule_tti_flows serves it, or rs_group_set_avg makes it average-resident", k, cell);
-      if (que && g->resident[cell] != 2) return fail(RS_ERR_STATE, "cell slot %d: cell %d is not bearer-resident (rs_group_set_bearers first)", k, cell);
-      if (cnt && !g->counted[cell]) return fail(RS_ERR_STATE, "cell slot %d: cell %d is not counted (rs_group_set_counters first)", k, cell);
-      if (!que && g->resident[cell] == 2)
-        return fail(RS_ERR_STATE, "cell slot %d: cell %d is bearer-resident (rs_group_set_bearers): rs_group_schedule_tti_queued serves it, or rs_group_set_avg makes it average-resident", k, cell);
-      if (!g->resident[cell]) return fail(RS_ERR_STATE, "cell slot %d: cell %d is not resident (rs_group_set_avg first)", k, cell);
-      if (slots0 && in[k].n_users < 0) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): n_users %d is negative", k, cell, in[k].n_users);
-      if (flw) {
-        /* positions are flows: (user, bearer) pairs in RRC-container order, each an existing bearer with data to transmit */
-        const int nf = in[k].n_users;
-        if (nf > b->U) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): n_users %d (the call's flows) outside 0..%d", k, cell, nf, b->U);
-        if (in[k].hol_delay || in[k].prio_has_data || in[k].required_rbs)
-          return fail(RS_ERR_INVALID, "cell slot %d (cell %d): %s must be NULL in a flows call", k, cell,
-                      in[k].hol_delay ? "hol_delay" : (in[k].prio_has_data ? "prio_has_data" : "required_rbs"));
-        if (nf > 0 && !flow[k]) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): flow_bearer[%d] is NULL (only an update-only slot, n_users == 0, gives none)", k, cell, k);
-        if (nf > 0 && !in[k].data_to_transmit) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): data_to_transmit is required: a flow is scheduled because it has data", k, cell);
-        const uint8_t* const has = g->has_bearer.data() + (size_t)cell * 2 * (size_t)b->U;
-        int prev = -1;
-        for (int i = 0; i < nf; i++) {
-          const int id = in[k].user_id ? in[k].user_id[i] : i, fb = flow[k][i];
-          if (id < 0 || id >= b->U) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): user id %d out of range", k, cell, id);
-          if (fb > 1) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): flow_bearer[%d] = %d is neither 0 nor 1", k, cell, i, fb);
-          if (2 * id + fb <= prev)
-            return fail(RS_ERR_INVALID, "cell slot %d (cell %d): call position %d (user %d, bearer %d) does not ascend: flows come in (user, bearer) order, each once", k, cell, i, id, fb);
-          prev = 2 * id + fb;
-          if (!has[prev]) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): call position %d names bearer %d of user %d, which does not exist (rs_group_set_flows)", k, cell, i, fb, id);
-          if (in[k].data_to_transmit[i] <= 0)
-            return fail(RS_ERR_INVALID, "cell slot %d (cell %d): data_to_transmit[%d] = %d: a flow without data is not scheduled", k, cell, i, in[k].data_to_transmit[i]);
-        }
-      }
-      if (que && in[k].n_users > 0 && !qdata[k]) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): data_to_transmit[%d] is NULL (only an update-only slot, n_users == 0, gives none)", k, cell, k);
-      const double last = g->last_update[cell];
-      if (!std::isfinite(now[k])) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): now is not finite", k, cell);
-      if (now[k] < last) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): now = %.17g lies before the cell's last update at %.17g", k, cell, now[k], last);
-      if (now[k] != last && !(now[k] - last >= kResidentMinDt) && !g->pending_zero[cell])
-        return fail(RS_ERR_INVALID, "cell slot %d (cell %d): now - last_update = %.3g s is neither 0 nor at least %.3g s, and the cell may have bytes pending", k, cell, now[k] - last, kResidentMinDt);
-    }
-  }
-  HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  bool exact_scan = false;
+  if (!c.resident()) return RS_OK;
+  /* a resident call's cells: the form each is resident in, the slots' own inputs, the clock rules */
+  const bool que = c.form == kGroupQueued, flw = c.form == kGroupFlows;
+  if (b->gen_exp)
+    return fail(RS_ERR_INVALID, "resident averages need exponents in {0, 1}: the general exponents' pow() of the averages is taken on the host per call");
   for (int k = 0; k < n; k++) {
-    uint8_t* const slot = g->h_in + (size_t)k * g->in_stride;
-    TtiPack& pk = g->packs[k];
-    pk = TtiPack();
-    /* rs_tti_in.cqi_epoch, decided per cell as a context of its own would (rs_schedule_tti): the number, the user count, the user list
-     * and the kind of report of the cell's valid image -- then the caller's block is neither checked, copied nor read */
-    const int cell = cell_ids ? cell_ids[k] : k;
-    g->empty_slot[k] = slots0 && in[k].n_users == 0;
-    if (g->empty_slot[k]) {
-      /* an update-only slot: its workgroup reads the header's cell, user count and clock and nothing behind the header */
-      g->modes[k] = 0;
-      pk.l = ctx_layout(0, b->R, b->S, b->G, false);
-      RsGroupCell h;
-      memset(&h, 0, sizeof h);
-      h.cell = cell;
-      h.now = now[k];
-      memcpy(slot, &h, sizeof h);
-      continue;
-    }
-    const rs_group::CellImage& im = g->img[cell];
-    const uint64_t epoch = (g->image_on && !(has_prb && g->prb_store_failed)) ? in[k].cqi_epoch : 0;
-    const bool reuse_grid = epoch != 0 && im.valid && im.epoch == epoch && im.n == in[k].n_users && im.prb == has_prb &&
-                            im.has_ids == (in[k].user_id != nullptr) &&
-                            (!in[k].user_id || memcmp(im.ids.data(), in[k].user_id, 4 * (size_t)im.n) == 0);
-    g->modes[k] = (uint8_t)(epoch == 0 ? 0 : (reuse_grid ? 2 : 1));
-    const int rc = pack_tti(b, &in[k], &out[k], slot + RS_GROUP_HDR_BYTES, reuse_grid, &pk, res, flw);
-    if (rc) {
-      char msg[sizeof g_err];
-      snprintf(msg, sizeof msg, "%s", g_err);
-      return fail(rc, "cell slot %d (cell %d): %.400s", k, cell, msg);
-    }
-    exact_scan |= pk.exact_scan; /* decided per call: one cell outside the FP32 filter's range, the exact scan for all (same results) */
-    if (que) {
-      /* the slot's data words: m_dataToTransmit[2] per call position, checked against the host's mirror of the cell's bearers */
-      const int32_t* const d = qdata[k];
-      const uint8_t* const has = g->has_bearer.data() + (size_t)cell * 2 * (size_t)b->U;
-      for (int i = 0; i < in[k].n_users; i++) {
-        const int id = in[k].user_id ? in[k].user_id[i] : i;
-        for (int bb = 0; bb < 2; bb++) {
-          if (d[2 * i + bb] < 0) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): data_to_transmit[%d][%d] = %d is negative", k, cell, i, bb, d[2 * i + bb]);
-          if (d[2 * i + bb] > 0 && !has[2 * id + bb])
-            return fail(RS_ERR_INVALID, "cell slot %d (cell %d): data_to_transmit[%d][%d] = %d, but user %d has no bearer of priority %d (rs_group_set_bearers)", k, cell, i, bb, d[2 * i + bb], id, bb);
-        }
-        if (d[2 * i] == 0 && d[2 * i + 1] == 0)
-          return fail(RS_ERR_INVALID, "cell slot %d (cell %d): user %d (call position %d) has no data in either bearer: the reference does not schedule such a user", k, cell, id, i);
-      }
-      memcpy(g->h_qin + (size_t)k * 2 * (size_t)b->U, d, 8 * (size_t)in[k].n_users);
-    }
-    if (flw) { /* the slot's bearer words, one per call position (checked above) */
-      int32_t* const w = g->h_qin + (size_t)k * 2 * (size_t)b->U;
-      for (int i = 0; i < in[k].n_users; i++) w[i] = flow[k][i];
-    }
-    const CtxLayout& l = pk.l;
-    const int nu = in[k].n_users;
-    RsGroupCell h;
-    memset(&h, 0, sizeof h);
-    h.cell = cell;
+    const int cell = c.cell(k);
+    if (in[k].avg_rate) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): avg_rate must be NULL: the cell's averages are resident on the device", k, cell);
+    if (flw && g->resident[cell] != 3) return fail(RS_ERR_STATE, "cell slot %d: cell %d is not flow-resident (rs_group_set_flows first)", k, cell);
+    if (!flw && g->resident[cell] == 3)
+      return fail(RS_ERR_STATE, "cell slot %d: cell %d is flow-resident (rs_group_set_flows): rs_group_schedule_tti_flows serves it, or rs_group_set_avg makes it average-resident", k, cell);
+    if (que && g->resident[cell] != 2) return fail(RS_ERR_STATE, "cell slot %d: cell %d is not bearer-resident (rs_group_set_bearers first)", k, cell);
+    if (c.counted && !g->counted[cell]) return fail(RS_ERR_STATE, "cell slot %d: cell %d is not counted (rs_group_set_counters first)", k, cell);
+    if (!que && g->resident[cell] == 2)
+      return fail(RS_ERR_STATE, "cell slot %d: cell %d is bearer-resident (rs_group_set_bearers): rs_group_schedule_tti_queued serves it, or rs_group_set_avg makes it average-resident", k, cell);
+    if (!g->resident[cell]) return fail(RS_ERR_STATE, "cell slot %d: cell %d is not resident (rs_group_set_avg first)", k, cell);
+    if (slots0 && in[k].n_users < 0) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): n_users %d is negative", k, cell, in[k].n_users);
+    if (int rc = flw ? group_validate_flows_slot(g, c, k, cell) : RS_OK) return rc;
+    if (que && in[k].n_users > 0 && !c.qdata[k]) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): data_to_transmit[%d] is NULL (only an update-only slot, n_users == 0, gives none)", k, cell, k);
+    const double last = g->last_update[cell];
+    if (!std::isfinite(c.now[k])) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): now is not finite", k, cell);
+    if (c.now[k] < last) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): now = %.17g lies before the cell's last update at %.17g", k, cell, c.now[k], last);
+    if (c.now[k] != last && !(c.now[k] - last >= kResidentMinDt) && !g->pending_zero[cell])
+      return fail(RS_ERR_INVALID, "cell slot %d (cell %d): now - last_update = %.3g s is neither 0 nor at least %.3g s, and the cell may have bytes pending", k, cell, c.now[k] - last, kResidentMinDt);
+  }
+  return RS_OK;
+}
+
+/* slot k's header (RsGroupCell, rs_device.h); l == null: an update-only slot -- its workgroup reads the header's cell, user count and
+ * clock and nothing behind the header */
+void group_fill_header(const rs_group* g, const GroupCall& c, int k, const CtxLayout* l) {
+  const rs_batch* b = g->b;
+  const rs_tti_in& in = c.in[k];
+  RsGroupCell h;
+  memset(&h, 0, sizeof h);
+  h.cell = c.cell(k);
+  if (l) {
+    const int nu = in.n_users;
     h.image_mode = g->modes[k];
     h.U = nu;
     h.Upad = upad_of(nu);
     h.n_seg = b->base.n_seg;
     h.n_items = b->base.n_items;
     if (b->sched == RS_SCHED_PF) { h.n_seg = (nu + RS_PF_SEG - 1) / RS_PF_SEG; h.n_items = b->R * h.n_seg; }
-    h.rand0 = in[k].rand0;
-    h.rand1 = in[k].rand1;
-    h.in_slice = (int32_t)l.slice; h.in_avg = (int32_t)l.avg; h.in_hol = (int32_t)l.hol; h.in_prio = (int32_t)l.prio;
-    h.in_gate = (int32_t)l.gate; h.in_prb = (int32_t)l.prb;
-    h.out_uinfo = (int32_t)l.uinfo; h.out_map = (int32_t)l.map; h.out_quota = (int32_t)l.quota; h.out_target = (int32_t)l.target;
-    h.out_upper = (int32_t)l.upper;
-    if (res) { /* (both resident forms) */
-      h.in_uid = in[k].user_id ? (int32_t)l.avg : 0; /* (l.avg lies behind the grid and the slice ids: never 0) */
-      h.now = now[k];
+    h.rand0 = in.rand0;
+    h.rand1 = in.rand1;
+    h.in_slice = (int32_t)l->slice; h.in_avg = (int32_t)l->avg; h.in_hol = (int32_t)l->hol; h.in_prio = (int32_t)l->prio;
+    h.in_gate = (int32_t)l->gate; h.in_prb = (int32_t)l->prb;
+    h.out_uinfo = (int32_t)l->uinfo; h.out_map = (int32_t)l->map; h.out_quota = (int32_t)l->quota; h.out_target = (int32_t)l->target;
+    h.out_upper = (int32_t)l->upper;
+    if (c.resident()) h.in_uid = in.user_id ? (int32_t)l->avg : 0; /* (l.avg lies behind the grid and the slice ids: never 0) */
+  }
+  if (c.resident()) h.now = c.now[k];
+  memcpy(g->h_in + (size_t)k * g->in_stride, &h, sizeof h);
+}
+
+/* a queued call's slot k: its data words, m_dataToTransmit[2] per call position, checked against the host's mirror of the cell's
+ * bearers and copied to the word block */
+int group_pack_data_words(rs_group* g, const GroupCall& c, int k, int cell) {
+  const rs_batch* b = g->b;
+  const rs_tti_in& in = c.in[k];
+  const int32_t* const d = c.qdata[k];
+  const uint8_t* const has = g->has_bearer.data() + (size_t)cell * 2 * (size_t)b->U;
+  for (int i = 0; i < in.n_users; i++) {
+    const int id = in.user_id ? in.user_id[i] : i;
+    for (int bb = 0; bb < 2; bb++) {
+      if (d[2 * i + bb] < 0) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): data_to_transmit[%d][%d] = %d is negative", k, cell, i, bb, d[2 * i + bb]);
+      if (d[2 * i + bb] > 0 && !has[2 * id + bb])
+        return fail(RS_ERR_INVALID, "cell slot %d (cell %d): data_to_transmit[%d][%d] = %d, but user %d has no bearer of priority %d (rs_group_set_bearers)", k, cell, i, bb, d[2 * i + bb], id, bb);
     }
-    memcpy(slot, &h, sizeof h);
+    if (d[2 * i] == 0 && d[2 * i + 1] == 0)
+      return fail(RS_ERR_INVALID, "cell slot %d (cell %d): user %d (call position %d) has no data in either bearer: the reference does not schedule such a user", k, cell, id, i);
+  }
+  memcpy(g->h_qin + (size_t)k * 2 * (size_t)b->U, d, 8 * (size_t)in.n_users);
+  return RS_OK;
+}
+
+/* Every slot's image mode, input block, words and header; then the per-PRB store.  Writes the group's pinned blocks and per-slot scratch. */
+int group_pack_slots(rs_group* g, GroupCall& c) {
+  rs_batch* b = g->b;
+  const rs_tti_in* const in = c.in;
+  const bool slots0 = c.desc().slots0;
+  for (int k = 0; k < c.n; k++) {
+    TtiPack& pk = g->packs[k];
+    pk = TtiPack();
+    const int cell = c.cell(k);
+    g->empty_slot[k] = slots0 && in[k].n_users == 0;
+    if (g->empty_slot[k]) {
+      g->modes[k] = 0;
+      pk.l = ctx_layout(0, b->R, b->S, b->G, false);
+      group_fill_header(g, c, k, nullptr);
+      continue;
+    }
+    /* rs_tti_in.cqi_epoch, decided per cell as a context of its own would (rs_schedule_tti): the number, the user count, the user list
+     * and the kind of report of the cell's valid image -- then the caller's block is neither checked, copied nor read */
+    const rs_group::CellImage& im = g->img[cell];
+    const uint64_t epoch = (g->image_on && !(c.has_prb && g->prb_store_failed)) ? in[k].cqi_epoch : 0;
+    const bool reuse_grid = epoch != 0 && im.valid && im.epoch == epoch && im.n == in[k].n_users && im.prb == c.has_prb &&
+                            im.has_ids == (in[k].user_id != nullptr) &&
+                            (!in[k].user_id || memcmp(im.ids.data(), in[k].user_id, 4 * (size_t)im.n) == 0);
+    g->modes[k] = (uint8_t)(epoch == 0 ? 0 : (reuse_grid ? 2 : 1));
+    int rc = pack_tti(b, &in[k], &c.out[k], g->h_in + (size_t)k * g->in_stride + RS_GROUP_HDR_BYTES, reuse_grid, &pk, c.resident(), c.form == kGroupFlows);
+    if (rc) {
+      char msg[sizeof g_err];
+      snprintf(msg, sizeof msg, "%s", g_err);
+      return fail(rc, "cell slot %d (cell %d): %.400s", k, cell, msg);
+    }
+    c.exact_scan |= pk.exact_scan;
+    if (c.form == kGroupQueued && (rc = group_pack_data_words(g, c, k, cell))) return rc;
+    if (c.form == kGroupFlows) { /* the slot's bearer words, one per call position (checked by group_validate) */
+      int32_t* const w = g->h_qin + (size_t)k * 2 * (size_t)b->U;
+      for (int i = 0; i < in[k].n_users; i++) w[i] = c.flow[k][i];
+    }
+    group_fill_header(g, c, k, &pk.l);
   }
   /* the per-PRB store comes with the first call that gives per-PRB reports under a number.  (Until it exists no record says "per-PRB",
    * so such a call holds no reuse slot yet.)  Without it those calls are served as if they made no promise: same results. */
-  bool store_failed_now = false;
-  if (has_prb && !g->d_prb && !g->prb_store_failed) {
+  if (c.has_prb && !g->d_prb && !g->prb_store_failed) {
     bool wanted = false;
-    for (int k = 0; k < n; k++) wanted |= g->modes[k] != 0;
+    for (int k = 0; k < c.n; k++) wanted |= g->modes[k] != 0;
     if (wanted && hipMalloc(&g->d_prb, g->prb_stride * (size_t)g->n_cells) != hipSuccess) {
       (void)hipGetLastError();
       g->d_prb = nullptr;
-      g->prb_store_failed = store_failed_now = true;
+      g->prb_store_failed = c.store_failed_now = true;
     }
   }
-  if (has_prb && !g->d_prb)
-    for (int k = 0; k < n; k++) {
+  if (c.has_prb && !g->d_prb)
+    for (int k = 0; k < c.n; k++) {
       g->modes[k] = 0;
       ((RsGroupCell*)(g->h_in + (size_t)k * g->in_stride))->image_mode = 0;
     }
-  /* from here on the device is touched: a failure leaves the named cells' images in an unknown state */
-  struct ImageGuard {
-    rs_group* g; int n; const int32_t* ids; bool ok, res;
-    ~ImageGuard() {
-      if (!ok) for (int k = 0; k < n; k++) {
-        g->img[ids ? ids[k] : k].valid = false;
-        if (res) g->resident[ids ? ids[k] : k] = 0; /* (averages half updated, perhaps: resident again with rs_group_set_avg) */
-        if (res) g->counted[ids ? ids[k] : k] = 0;  /* (neither resident nor counted) */
-      }
+  return RS_OK;
+}
+
+/* from the first operation on the stream on, a failure leaves the named cells' images in an unknown state */
+struct ImageGuard {
+  rs_group* g;
+  const GroupCall& c;
+  bool ok;
+  ~ImageGuard() {
+    if (!ok) for (int k = 0; k < c.n; k++) {
+      g->img[c.cell(k)].valid = false;
+      if (c.resident()) g->resident[c.cell(k)] = g->counted[c.cell(k)] = 0; /* (averages half updated, perhaps: resident again with rs_group_set_avg; neither resident nor counted) */
     }
-  } guard{g, n, cell_ids, false, res};
-  hipStream_t st = b->stream;
-  const clk::time_point t1 = g->timing ? clk::now() : clk::time_point();
-  /* per-PRB reports and queue state are read again and again inside the TTI: those calls keep the device copies.  (The copy sends
-   * whole slots: a reuse slot's grid area and per-PRB block travel stale and are not read.) */
-  const bool zc = g->z_in != nullptr && !has_prb && !b->any_alpha;
-  uint8_t* const dev_in = zc ? g->z_in : g->d_in;
-  uint8_t* const dev_out = zc ? g->z_out : g->d_out;
-  if (!zc) HIP_TRY(hipMemcpyAsync(g->d_in, g->h_in, (size_t)n * g->in_stride, hipMemcpyHostToDevice, st));
-  if (slots0 && !g->z_qin) HIP_TRY(hipMemcpyAsync(g->d_qin, g->h_qin, 8 * (size_t)n * b->U, hipMemcpyHostToDevice, st));
-  RsLaunch L = b->base;
-  L.n_cells = n; /* call slots of this launch */
+  }
+};
+
+/* the call's launch block: the config's, the group's stores, and of the form's stores those that its row names */
+void group_fill_launch(const rs_group* g, const GroupCall& c, RsLaunch* launch) {
+  const rs_batch* b = g->b;
+  const unsigned sets = c.desc().sets;
+  uint8_t* const dev_in = c.zc ? g->z_in : g->d_in;
+  uint8_t* const dev_out = c.zc ? g->z_out : g->d_out;
+  RsLaunch& L = *launch;
+  L = b->base;
+  L.n_cells = c.n; /* call slots of this launch */
   L.n_ttis = 1;
   L.direct = 1;
   L.cqi_mode = RS_CQI_EPOCHS;
@@ -2909,26 +2997,26 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
   L.grp_prb = g->d_prb;
   L.grp_prb_stride = (int64_t)g->prb_stride;
   L.queue_mode = b->any_alpha ? 1 : 0;
-  L.exact_scan = exact_scan ? 1 : 0;
+  L.exact_scan = c.exact_scan ? 1 : 0;
   L.gen_exp = b->gen_exp ? 1 : 0;
   L.gen_num = b->d_gen_num;
   /* given / not given; the workgroups take the addresses from their slots */
-  L.prb_cqi = has_prb ? dev_in : nullptr;
-  L.gate = has_gate ? (const int32_t*)dev_in : nullptr;
-  L.log_upper = want_upper ? (int32_t*)dev_out : nullptr;
+  L.prb_cqi = c.has_prb ? dev_in : nullptr;
+  L.gate = c.has_gate ? (const int32_t*)dev_in : nullptr;
+  L.log_upper = c.want_upper ? (int32_t*)dev_out : nullptr;
   L.grp_in = dev_in;
   L.grp_out = dev_out;
   L.grp_in_stride = (int64_t)g->in_stride;
   L.grp_out_stride = (int64_t)g->out_stride;
   L.grp_count = g->d_count;
-  if (res) {
+  if (sets & kSetResident) {
     L.grp_avg = g->d_ravg;
     L.grp_pending = g->d_rpend;
     L.grp_last = g->d_rlast;
     L.grp_gather = g->d_rgather;
     L.grp_uid = g->d_ruid;
   }
-  if (que) {
+  if (sets & kSetBearers) {
     L.grp_qavg = g->d_qavg;
     L.grp_qpend = g->d_qpend;
     L.grp_qhas = g->d_qhas;
@@ -2936,315 +3024,259 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
     L.grp_qin = g->z_qin ? g->z_qin : g->d_qin;
     L.grp_qin_stride = 2 * (int64_t)b->U;
   }
-  if (flw) { /* (the bearer stores and the counter stores; the bearer words where the queued form's data words travel) */
-    L.grp_qavg = g->d_qavg;
-    L.grp_qpend = g->d_qpend;
-    L.grp_qhas = g->d_qhas;
-    L.grp_qdata = g->d_qdata;
-    L.grp_qin = g->z_qin ? g->z_qin : g->d_qin;
-    L.grp_qin_stride = 2 * (int64_t)b->U;
+  if (sets & kSetCounters) {
     L.grp_cbytes = g->d_cbytes;
     L.grp_crbs = g->d_crbs;
   }
-  if (cnt) {
-    L.grp_cbytes = g->d_cbytes;
-    L.grp_crbs = g->d_crbs;
+  if (sets & kSetSent) {
     L.grp_sent = g->z_sent ? g->z_sent : g->d_sent;
     L.grp_sent_stride = 2 * (int64_t)b->U;
   }
-  bool poll = zc && g->poll;
-  if (poll) {
+}
+
+/* A checked call: the form's built-in kernel first, on the same slots and the same state, its outputs into slots of its own.  What it
+ * left is kept, what it found is put back: the run-time build starts from the same state.  (A mode-1 slot: BOTH kernels transpose the
+ * slot's block and store the cell's image and per-PRB copy -- the same bytes when the build is right; a wrong image shows in the
+ * checked calls that read it.) */
+int group_run_twin(rs_group* g, const GroupCall& c, const RsLaunch& L) {
+  rs_batch* b = g->b;
+  hipStream_t st = b->stream;
+  const GroupForm& f = c.desc();
+  const size_t ss_all = 8 * (size_t)b->S * g->n_cells, sc_all = sizeof(RsCellScalars) * (size_t)g->n_cells;
+  uint8_t* const before = g->d_chk;
+  uint8_t* const after = g->d_chk + group_chk_half(g);
+  HIP_TRY(hipMemcpyAsync(before, b->d_sstate, ss_all, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(before + group_chk_sstate(g), b->d_scal, sc_all, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(group_copy_stores(g, f, 0, true));
+  RsLaunch Lb = L;
+  Lb.grp_out = g->d_out2;
+  Lb.log_upper = c.want_upper ? (int32_t*)g->d_out2 : nullptr;
+  Lb.done_flag = nullptr;
+  HIP_TRY(f.launch(&Lb, b->threads, st));
+  HIP_TRY(hipMemcpyAsync(g->h_out2.data(), g->d_out2, (size_t)c.n * g->out_stride, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(after, b->d_sstate, ss_all, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(b->d_sstate, before, ss_all, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(b->d_scal, before + group_chk_sstate(g), sc_all, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(group_copy_stores(g, f, 1, true));
+  HIP_TRY(group_copy_stores(g, f, 0, false));
+  return RS_OK;
+}
+
+/* The copies in, the launch, the copies back.  The form's run-time pair serves the call when it has one -- its lean build when the call
+ * is plain for every cell (the uniform-presence rules make that a fact of the launch; a call of update-only slots only has no facts
+ * and takes the lean build too), the general one otherwise.  A build without the self-check mark serves its first calls beside the
+ * built-in kernel of its form (group_run_twin, group_check). */
+int group_run(rs_group* g, GroupCall& c, RsLaunch& L) {
+  rs_batch* b = g->b;
+  hipStream_t st = b->stream;
+  const GroupForm& f = c.desc();
+  /* per-PRB reports and queue state are read again and again inside the TTI: those calls keep the device copies.  (The copy sends
+   * whole slots: a reuse slot's grid area and per-PRB block travel stale and are not read.) */
+  if (!c.zc) HIP_TRY(hipMemcpyAsync(g->d_in, g->h_in, (size_t)c.n * g->in_stride, hipMemcpyHostToDevice, st));
+  if ((f.sets & kSetBearers) && !g->z_qin) HIP_TRY(hipMemcpyAsync(g->d_qin, g->h_qin, 8 * (size_t)c.n * b->U, hipMemcpyHostToDevice, st));
+  c.poll = c.zc && g->poll;
+  if (c.poll) {
     if (++g->seq == 0) g->seq = 1; /* (0 is the word's initial value) */
     L.done_flag = (uint32_t*)(g->z_out + g->flag_off);
     L.done_seq = g->seq;
   }
-  /* rs_group_specialize: the group's own build -- its lean form when the call is plain for every cell (the uniform-presence rules above
-   * make that a fact of the launch), the general one otherwise */
-  /* (the plain pair, rs_group_specialize, the resident pair, rs_group_specialize_resident, and the queued pair,
-   * rs_group_specialize_queued, are independent: each serves its own kind of call, is checked against its own built-in kernel and is
-   * dropped alone.  A queued call's per-launch facts are those of its slots with users; a call of update-only slots only has none and
-   * takes the lean build when the config allows one.) */
-  RsJitKernel** const pair = que ? g->qjit : (res ? g->rjit : g->jit);
-  int* const chk_left = que ? g->qchk_left : (res ? g->rchk_left : g->chk_left);
-  int* const chk_agreed = que ? g->qchk_agreed : (res ? g->rchk_agreed : g->chk_agreed);
-  RsJitKernel* kd = (cnt || flw) ? nullptr : pair[0]; /* (a counted call: the built-in counted kernel, whatever rs_group_specialize_queued built; a flows call likewise) */
-  int which = 0;
-  if (!cnt && !flw && pair[1] && !has_prb && !L.queue_mode && !has_gate && !L.exact_scan && !L.gen_exp && !want_upper && !L.synthetic) { kd = pair[1]; which = 1; }
-  /* A build without the self-check mark serves its first calls beside the built-in kernel of its kind (rs_group_jit_status,
-   * rs_group_resident_jit_status): same slots, same state; every named cell's output fields and the state left behind must agree --
-   * the slice state, for a resident call the averages of every user id, the pending bytes and the last-update time, and for a queued
-   * call those of both bearers of every user id. */
-  const bool checked_call = kd != nullptr && chk_left[which] > 0;
-  const size_t ss_all = 8 * (size_t)b->S * g->n_cells, sc_all = sizeof(RsCellScalars) * (size_t)g->n_cells;
-  const size_t ra_all = 8 * (size_t)b->U * g->n_cells, rl_all = 8 * (size_t)g->n_cells, rp_all = 4 * (size_t)b->U * g->n_cells;
-  /* the three resident stores to / from one half of d_rchk */
-  auto resident_stores = [&](uint8_t* half, bool save) -> hipError_t {
-    struct { void* store; uint8_t* kept; size_t bytes; } const part[3] = {{g->d_ravg, half, ra_all},
-                                                                        {g->d_rlast, half + group_rchk_avg(g), rl_all},
-                                                                        {g->d_rpend, half + group_rchk_avg(g) + group_rchk_last(g), rp_all}};
-    for (const auto& x : part) {
-      const hipError_t e = hipMemcpyAsync(save ? (void*)x.kept : x.store, save ? x.store : (void*)x.kept, x.bytes, hipMemcpyDeviceToDevice, st);
-      if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-  };
-  /* ... and the three bearer stores of a queued call to / from one half of d_qchk */
-  const size_t qa_all = 16 * (size_t)b->U * g->n_cells, qp_all = 8 * (size_t)b->U * g->n_cells;
-  auto bearer_stores = [&](uint8_t* half, bool save) -> hipError_t {
-    struct { void* store; uint8_t* kept; size_t bytes; } const part[3] = {{g->d_qavg, half, qa_all},
-                                                                        {g->d_rlast, half + group_qchk_avg(g), rl_all},
-                                                                        {g->d_qpend, half + group_qchk_avg(g) + group_rchk_last(g), qp_all}};
-    for (const auto& x : part) {
-      const hipError_t e = hipMemcpyAsync(save ? (void*)x.kept : x.store, save ? x.store : (void*)x.kept, x.bytes, hipMemcpyDeviceToDevice, st);
-      if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-  };
-  if (checked_call) {
-    uint8_t* const before = g->d_chk;
-    uint8_t* const after = g->d_chk + group_chk_half(g);
-    HIP_TRY(hipMemcpyAsync(before, b->d_sstate, ss_all, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(before + group_chk_sstate(g), b->d_scal, sc_all, hipMemcpyDeviceToDevice, st));
-    if (que) HIP_TRY(bearer_stores(g->d_qchk, true));
-    else if (res) HIP_TRY(resident_stores(g->d_rchk, true));
-    RsLaunch Lb = L; /* the built-in kernel, its outputs into slots of its own */
-    Lb.grp_out = g->d_out2;
-    Lb.log_upper = want_upper ? (int32_t*)g->d_out2 : nullptr;
-    Lb.done_flag = nullptr;
-    if (que) HIP_TRY(rs_launch_group_queued(&Lb, b->threads, st));
-    else if (res) HIP_TRY(rs_launch_group_resident(&Lb, b->threads, st));
-    else HIP_TRY(rs_launch_group(&Lb, b->threads, st));
-    HIP_TRY(hipMemcpyAsync(g->h_out2.data(), g->d_out2, (size_t)n * g->out_stride, hipMemcpyDeviceToHost, st));
-    /* keep what it left, put back what it found: the run-time build starts from the same state */
-    HIP_TRY(hipMemcpyAsync(after, b->d_sstate, ss_all, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(b->d_sstate, before, ss_all, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(b->d_scal, before + group_chk_sstate(g), sc_all, hipMemcpyDeviceToDevice, st));
-    if (que) {
-      HIP_TRY(bearer_stores(g->d_qchk + group_qchk_half(g), true));
-      HIP_TRY(bearer_stores(g->d_qchk, false));
-    } else if (res) {
-      HIP_TRY(resident_stores(g->d_rchk + group_rchk_half(g), true));
-      HIP_TRY(resident_stores(g->d_rchk, false));
-    }
-    /* (a mode-1 slot: BOTH kernels transpose the slot's block and store the cell's image and per-PRB copy -- the same bytes when the
-     * build is right; a wrong image shows in the checked calls that read it) */
+  if (f.pair >= 0) {
+    const rs_group::GroupPair& p = g->pair[f.pair];
+    const bool lean = p.jit[1] && !c.has_prb && !L.queue_mode && !c.has_gate && !L.exact_scan && !L.gen_exp && !c.want_upper && !L.synthetic;
+    c.which = lean ? 1 : 0;
+    c.kd = p.jit[c.which];
+    c.checked = c.kd != nullptr && p.chk_left[c.which] > 0;
+  }
+  if (c.checked) {
+    const int rc = group_run_twin(g, c, L);
+    if (rc) return rc;
     L.done_flag = nullptr; /* completion by the stream */
   }
-  if (kd) HIP_TRY(rs_jit_launch(kd, &L, st));
-  else if (flw) HIP_TRY(rs_launch_group_flows(&L, b->threads, st));
-  else if (cnt) HIP_TRY(rs_launch_group_counted(&L, b->threads, st));
-  else if (que) HIP_TRY(rs_launch_group_queued(&L, b->threads, st));
-  else if (res) HIP_TRY(rs_launch_group_resident(&L, b->threads, st));
-  else HIP_TRY(rs_launch_group(&L, b->threads, st));
+  if (c.kd) HIP_TRY(rs_jit_launch(c.kd, &L, st));
+  else HIP_TRY(f.launch(&L, b->threads, st));
   g->launches++;
-  g->last_call_kind = kind;
-  g->last_call_resident = res;
-  g->last_call_rjit = res && !que && kd != nullptr;
-  g->last_call_qjit = que && kd != nullptr;
-  g->last_call_counted = cnt;
-  if (!zc) HIP_TRY(hipMemcpyAsync(g->h_out, g->d_out, (size_t)n * g->out_stride, hipMemcpyDeviceToHost, st));
-  if (cnt && !g->z_sent) HIP_TRY(hipMemcpyAsync(g->h_sent, g->d_sent, 8 * (size_t)n * b->U, hipMemcpyDeviceToHost, st));
-  const clk::time_point t2 = g->timing ? clk::now() : clk::time_point();
+  g->last_call_form = c.row();
+  g->last_call_jit = c.kd != nullptr;
+  if (!c.zc) HIP_TRY(hipMemcpyAsync(g->h_out, g->d_out, (size_t)c.n * g->out_stride, hipMemcpyDeviceToHost, st));
+  if ((f.sets & kSetSent) && !g->z_sent) HIP_TRY(hipMemcpyAsync(g->h_sent, g->d_sent, 8 * (size_t)c.n * b->U, hipMemcpyDeviceToHost, st));
+  return RS_OK;
+}
+
+/* by the polled word (the last workgroup to finish publishes the sequence number behind every workgroup's outputs), else by the stream */
+int group_wait(rs_group* g, const GroupCall& c) {
   bool seen = false;
-  if (checked_call) poll = false;
-  if (poll) {
-    /* the last workgroup to finish publishes the sequence number behind every workgroup's outputs (release, system scope) */
-    const volatile uint32_t* const h_flag = (const volatile uint32_t*)(g->h_out + g->flag_off);
-    const clk::time_point give_up = clk::now() + std::chrono::microseconds(g->poll_us);
-    for (unsigned spins = 0;; ++spins) {
-      if (__atomic_load_n((const uint32_t*)h_flag, __ATOMIC_ACQUIRE) == g->seq) { seen = true; break; }
-      __builtin_ia32_pause();
-      if ((spins & 255u) == 255u && clk::now() > give_up) break;
-    }
-    if (seen) {
-      g->n_polled++;
-      if ((g->n_polled & 63) == 0) (void)hipStreamQuery(st); /* (the stream's own bookkeeping, as in rs_schedule_tti) */
-    }
-  }
+  if (c.poll && !c.checked) seen = poll_done_word(g->h_out + g->flag_off, g->seq, g->poll_us, &g->n_polled, g->b->stream);
   if (!seen) {
-    g->n_fallback++;
-    HIP_TRY(hipStreamSynchronize(st));
+    g->n_fallback++; /* (a group counts every stream wait) */
+    HIP_TRY(hipStreamSynchronize(g->b->stream));
   }
-  if (checked_call) {
-    /* slot by slot, field by field: the first difference is the message */
-    std::vector<double> ss_jit((size_t)b->S * g->n_cells), ss_ref(ss_jit.size());
-    HIP_TRY(hipMemcpy(ss_jit.data(), b->d_sstate, ss_all, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(ss_ref.data(), g->d_chk + group_chk_half(g), ss_all, hipMemcpyDeviceToHost));
-    char what[240] = "";
-    for (int k = 0; k < n && !what[0]; k++) {
-      const int cell = cell_ids ? cell_ids[k] : k;
-      const CtxLayout& l = g->packs[k].l;
-      const uint8_t *ho = g->h_out + (size_t)k * g->out_stride, *hr = g->h_out2.data() + (size_t)k * g->out_stride;
-      auto differ32 = [&](const char* name, size_t off, int count) {
-        const int32_t *a = (const int32_t*)(ho + off), *r = (const int32_t*)(hr + off);
-        for (int i = 0; i < count && !what[0]; i++)
-          if (a[i] != r[i]) snprintf(what, sizeof what, "cell %d: %s[%d] = %d, the built-in kernel's %d", cell, name, i, a[i], r[i]);
-      };
-      auto differ16 = [&](const char* name, size_t off, int count) {
-        const int16_t *a = (const int16_t*)(ho + off), *r = (const int16_t*)(hr + off);
-        for (int i = 0; i < count && !what[0]; i++)
-          if (a[i] != r[i]) snprintf(what, sizeof what, "cell %d: %s[%d] = %d, the built-in kernel's %d", cell, name, i, a[i], r[i]);
-      };
-      if (!g->empty_slot[k]) { /* (an update-only slot of a queued call: its workgroup wrote no output, the state alone is compared) */
-        differ16("rbg_to_user (call position)", l.map, b->R);
-        differ16("quota_rbgs", l.quota, b->S);
-        differ16("target_rbs", l.target, b->S);
-        differ32("user_tbs_bits", l.tbs, in[k].n_users);
-        differ32("user_nprb | final_cqi << 16 | mcs << 24", l.uinfo, in[k].n_users);
-        if (want_upper) differ32("upper lists", l.upper, b->S * b->R);
+  return RS_OK;
+}
+
+/* the form's stores of the named cells, as the run-time build left them against what the built-in kernel left (the second half of the
+ * check block): per cell the averages, then the pending bytes, then the last-update time */
+int group_compare_stores(const rs_group* g, const GroupCall& c, char* what, size_t len) {
+  const GroupForm& f = c.desc();
+  const GroupStores s = group_stores(g, f);
+  if (!s.n) return RS_OK;
+  std::vector<uint8_t> jit[3], ref[3];
+  const uint8_t* kept = g->pair[f.pair].d_stores_chk + s.half;
+  for (int i = 0; i < s.n; kept += s.part[i++].kept(g)) {
+    const size_t bytes = s.part[i].bytes(g);
+    jit[i].resize(bytes);
+    ref[i].resize(bytes);
+    HIP_TRY(hipMemcpy(jit[i].data(), s.part[i].dev, bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ref[i].data(), kept, bytes, hipMemcpyDeviceToHost));
+  }
+  for (int k = 0; k < c.n && !what[0]; k++) {
+    const int cell = c.cell(k);
+    for (const int i : {0, 2, 1}) {
+      const GroupStore& x = s.part[i];
+      for (size_t j = 0; j < x.elems && !what[0]; j++) {
+        const size_t at = ((size_t)cell * x.elems + j) * x.size();
+        const void *a = jit[i].data() + at, *r = ref[i].data() + at;
+        if (memcmp(a, r, x.size()) == 0) continue;
+        char idx[48] = ""; /* (the element's index behind the store's name: "avg[3]", "avg[3][1]", "last_update") */
+        if (x.elems > 1 && f.store_width == 2) snprintf(idx, sizeof idx, "[%zu][%zu]", j / 2, j % 2);
+        else if (x.elems > 1) snprintf(idx, sizeof idx, "[%zu]", j);
+        if (x.f64) snprintf(what, len, "cell %d: %s%s = %a, the built-in kernel's %a", cell, x.name, idx, *(const double*)a, *(const double*)r);
+        else snprintf(what, len, "cell %d: %s%s = %d, the built-in kernel's %d", cell, x.name, idx, *(const int32_t*)a, *(const int32_t*)r);
       }
-      for (int i = 0; i < b->S && !what[0]; i++) {
-        const double a = ss_jit[(size_t)cell * b->S + i], r = ss_ref[(size_t)cell * b->S + i];
-        if (to_bits(a) != to_bits(r)) snprintf(what, sizeof what, "cell %d: slice state[%d] = %a, the built-in kernel's %a", cell, i, a, r);
-      }
-    }
-    if (que && !what[0]) {
-      /* the bearer stores of the named cells: averages and pending bytes of BOTH bearers of every user id of the config, the
-       * last-update time */
-      const uint8_t* const ref = g->d_qchk + group_qchk_half(g);
-      const size_t B = 2 * (size_t)b->U;
-      std::vector<double> a_jit(B * g->n_cells), a_ref(a_jit.size()), l_jit(g->n_cells), l_ref(g->n_cells);
-      std::vector<int32_t> p_jit(B * g->n_cells), p_ref(p_jit.size());
-      HIP_TRY(hipMemcpy(a_jit.data(), g->d_qavg, qa_all, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(a_ref.data(), ref, qa_all, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(l_jit.data(), g->d_rlast, rl_all, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(l_ref.data(), ref + group_qchk_avg(g), rl_all, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(p_jit.data(), g->d_qpend, qp_all, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(p_ref.data(), ref + group_qchk_avg(g) + group_rchk_last(g), qp_all, hipMemcpyDeviceToHost));
-      for (int k = 0; k < n && !what[0]; k++) {
-        const int cell = cell_ids ? cell_ids[k] : k;
-        for (size_t j = 0; j < B && !what[0]; j++) {
-          const double a = a_jit[cell * B + j], r = a_ref[cell * B + j];
-          if (to_bits(a) != to_bits(r)) snprintf(what, sizeof what, "cell %d: avg[%zu][%zu] = %a, the built-in kernel's %a", cell, j / 2, j % 2, a, r);
-        }
-        for (size_t j = 0; j < B && !what[0]; j++)
-          if (p_jit[cell * B + j] != p_ref[cell * B + j])
-            snprintf(what, sizeof what, "cell %d: pending_bytes[%zu][%zu] = %d, the built-in kernel's %d", cell, j / 2, j % 2, p_jit[cell * B + j], p_ref[cell * B + j]);
-        if (!what[0] && to_bits(l_jit[cell]) != to_bits(l_ref[cell]))
-          snprintf(what, sizeof what, "cell %d: last_update = %a, the built-in kernel's %a", cell, l_jit[cell], l_ref[cell]);
-      }
-    }
-    if (res && !que && !what[0]) {
-      /* the resident stores of the named cells: the averages of EVERY user id of the config (the update touches them all), the pending
-       * bytes, the last-update time */
-      const uint8_t* const ref = g->d_rchk + group_rchk_half(g);
-      const size_t U = (size_t)b->U;
-      std::vector<double> a_jit(U * g->n_cells), a_ref(a_jit.size()), l_jit(g->n_cells), l_ref(g->n_cells);
-      std::vector<int32_t> p_jit(U * g->n_cells), p_ref(p_jit.size());
-      HIP_TRY(hipMemcpy(a_jit.data(), g->d_ravg, ra_all, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(a_ref.data(), ref, ra_all, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(l_jit.data(), g->d_rlast, rl_all, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(l_ref.data(), ref + group_rchk_avg(g), rl_all, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(p_jit.data(), g->d_rpend, rp_all, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(p_ref.data(), ref + group_rchk_avg(g) + group_rchk_last(g), rp_all, hipMemcpyDeviceToHost));
-      for (int k = 0; k < n && !what[0]; k++) {
-        const int cell = cell_ids ? cell_ids[k] : k;
-        for (size_t u = 0; u < U && !what[0]; u++) {
-          const double a = a_jit[cell * U + u], r = a_ref[cell * U + u];
-          if (to_bits(a) != to_bits(r)) snprintf(what, sizeof what, "cell %d: avg[%zu] = %a, the built-in kernel's %a", cell, u, a, r);
-        }
-        for (size_t u = 0; u < U && !what[0]; u++)
-          if (p_jit[cell * U + u] != p_ref[cell * U + u])
-            snprintf(what, sizeof what, "cell %d: pending_bytes[%zu] = %d, the built-in kernel's %d", cell, u, p_jit[cell * U + u], p_ref[cell * U + u]);
-        if (!what[0] && to_bits(l_jit[cell]) != to_bits(l_ref[cell]))
-          snprintf(what, sizeof what, "cell %d: last_update = %a, the built-in kernel's %a", cell, l_jit[cell], l_ref[cell]);
-      }
-    }
-    if (what[0] && que) {
-      /* the queued pair is wrong: both of its builds are dropped (and their cache files), the plain and the resident pair stay.  This
-       * call returns the built-in queued kernel's outputs and leaves its state, bearer stores included; later queued calls run that kernel */
-      for (int w = 0; w < 2; w++) {
-        if (g->qjit[w]) rs_jit_reject(g->qjit[w]);
-        g->qjit[w] = nullptr;
-        g->qchk_left[w] = 0;
-      }
-      g->qjit_dropped = true;
-      g->last_call_qjit = false;
-      memcpy(g->h_out, g->h_out2.data(), (size_t)n * g->out_stride);
-      HIP_TRY(hipMemcpy(b->d_sstate, g->d_chk + group_chk_half(g), ss_all, hipMemcpyDeviceToDevice));
-      HIP_TRY(bearer_stores(g->d_qchk + group_qchk_half(g), false));
-      HIP_TRY(hipStreamSynchronize(st));
-      snprintf(g->qjit_msg, sizeof g->qjit_msg, "self-check of the group's specialised queued %s build, checked call %d: %s; both queued builds are dropped, "
-               "the built-in queued kernel serves this group's queued calls (lint the code object: tools/lint_exec_restore.py)",
-               which ? "lean" : "general", g->qchk_agreed[which] + 1, what);
-      snprintf(g_err, sizeof g_err, "%s", g->qjit_msg);
-    } else if (what[0] && res) {
-      /* the resident pair is wrong: both of its builds are dropped (and their cache files), the plain pair stays.  This call returns
-       * the built-in resident kernel's outputs and leaves its state, resident stores included; later resident calls run that kernel */
-      for (int w = 0; w < 2; w++) {
-        if (g->rjit[w]) rs_jit_reject(g->rjit[w]);
-        g->rjit[w] = nullptr;
-        g->rchk_left[w] = 0;
-      }
-      g->rjit_dropped = true;
-      g->last_call_rjit = false;
-      memcpy(g->h_out, g->h_out2.data(), (size_t)n * g->out_stride);
-      HIP_TRY(hipMemcpy(b->d_sstate, g->d_chk + group_chk_half(g), ss_all, hipMemcpyDeviceToDevice));
-      HIP_TRY(resident_stores(g->d_rchk + group_rchk_half(g), false));
-      HIP_TRY(hipStreamSynchronize(st));
-      snprintf(g->rjit_msg, sizeof g->rjit_msg, "self-check of the group's specialised resident %s build, checked call %d: %s; both resident builds are dropped, "
-               "the built-in resident kernel serves this group's resident calls (lint the code object: tools/lint_exec_restore.py)",
-               which ? "lean" : "general", g->rchk_agreed[which] + 1, what);
-      snprintf(g_err, sizeof g_err, "%s", g->rjit_msg);
-    } else if (what[0]) {
-      /* the build is wrong: neither build of the shape is trusted.  Both are dropped (and their cache files); this call returns the
-       * built-in kernel's outputs and state, later calls run the built-in kernels */
-      for (int w = 0; w < 2; w++) {
-        if (g->jit[w]) rs_jit_reject(g->jit[w]);
-        g->jit[w] = nullptr;
-        g->chk_left[w] = 0;
-      }
-      g->jit_dropped = true;
-      memcpy(g->h_out, g->h_out2.data(), (size_t)n * g->out_stride);
-      HIP_TRY(hipMemcpy(b->d_sstate, g->d_chk + group_chk_half(g), ss_all, hipMemcpyDeviceToDevice));
-      snprintf(g->jit_msg, sizeof g->jit_msg, "self-check of the group's specialised %s build, checked call %d: %s; both builds are dropped, the built-in kernels "
-               "serve this group (lint the code object: tools/lint_exec_restore.py)", which ? "lean" : "general", g->chk_agreed[which] + 1, what);
-      snprintf(g_err, sizeof g_err, "%s", g->jit_msg);
-    } else {
-      chk_agreed[which]++;
-      if (--chk_left[which] == 0) rs_jit_mark_verified(kd);
     }
   }
-  guard.ok = true;
-  if (res) /* the launch has completed: the cells' updates are dated now[k], and grants may be waiting */
-    for (int k = 0; k < n; k++) {
-      const int cell = cell_ids ? cell_ids[k] : k;
-      /* (an update-only slot credits nothing: behind an update no byte is waiting, without one nothing changed) */
-      if (!g->empty_slot[k]) g->pending_zero[cell] = 0;
-      else if (now[k] != g->last_update[cell]) g->pending_zero[cell] = 1;
-      g->last_update[cell] = now[k];
+  return RS_OK;
+}
+
+/* A checked call disagreed: the pair is wrong, neither of its builds is trusted.  Both are dropped (and their cache files); the other
+ * pairs stay.  This call returns the built-in kernel's outputs and leaves its state, the form's stores included; later calls of the
+ * form run the built-in kernel. */
+int group_drop_pair(rs_group* g, const GroupCall& c, const char* what) {
+  rs_batch* b = g->b;
+  const GroupForm& f = c.desc();
+  rs_group::GroupPair& p = g->pair[f.pair];
+  for (int w = 0; w < 2; w++) {
+    if (p.jit[w]) rs_jit_reject(p.jit[w]);
+    p.jit[w] = nullptr;
+    p.chk_left[w] = 0;
+  }
+  p.dropped = true;
+  g->last_call_jit = false;
+  memcpy(g->h_out, g->h_out2.data(), (size_t)c.n * g->out_stride);
+  HIP_TRY(hipMemcpy(b->d_sstate, g->d_chk + group_chk_half(g), 8 * (size_t)b->S * g->n_cells, hipMemcpyDeviceToDevice));
+  if (f.store_width) {
+    HIP_TRY(group_copy_stores(g, f, 1, false));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+  }
+  snprintf(p.msg, sizeof p.msg, "self-check of the group's specialised %s%s build, checked call %d: %s; both %sbuilds are dropped, %s (lint the code object: "
+           "tools/lint_exec_restore.py)", f.adj, c.which ? "lean" : "general", p.chk_agreed[c.which] + 1, what, f.adj, f.serves);
+  snprintf(g_err, sizeof g_err, "%s", p.msg);
+  return RS_OK;
+}
+
+/* a checked call's end: every named cell's output fields and the state left behind must agree with the built-in kernel's -- the slice
+ * state and the form's stores; slot by slot, field by field, the first difference is the message */
+int group_check(rs_group* g, const GroupCall& c) {
+  const rs_batch* b = g->b;
+  rs_group::GroupPair& p = g->pair[c.desc().pair];
+  const size_t ss_all = 8 * (size_t)b->S * g->n_cells;
+  std::vector<double> ss_jit((size_t)b->S * g->n_cells), ss_ref(ss_jit.size());
+  HIP_TRY(hipMemcpy(ss_jit.data(), b->d_sstate, ss_all, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(ss_ref.data(), g->d_chk + group_chk_half(g), ss_all, hipMemcpyDeviceToHost));
+  char what[240] = "";
+  for (int k = 0; k < c.n && !what[0]; k++) {
+    const int cell = c.cell(k);
+    const size_t at = (size_t)k * g->out_stride;
+    if (!g->empty_slot[k]) /* (an update-only slot: its workgroup wrote no output, the state alone is compared) */
+      compare_out_block(g->h_out + at, g->h_out2.data() + at, g->packs[k].l, b->R, b->S, c.in[k].n_users, c.want_upper, cell, what, sizeof what);
+    for (int i = 0; i < b->S && !what[0]; i++) {
+      const double a = ss_jit[(size_t)cell * b->S + i], r = ss_ref[(size_t)cell * b->S + i];
+      if (to_bits(a) != to_bits(r)) snprintf(what, sizeof what, "cell %d: slice state[%d] = %a, the built-in kernel's %a", cell, i, a, r);
     }
-  const clk::time_point t3 = g->timing ? clk::now() : clk::time_point();
-  /* the launch has completed: the device holds these calls' reports now */
-  for (int k = 0; k < n; k++) {
+  }
+  if (!what[0]) {
+    const int rc = group_compare_stores(g, c, what, sizeof what);
+    if (rc) return rc;
+  }
+  if (what[0]) return group_drop_pair(g, c, what);
+  p.chk_agreed[c.which]++;
+  if (--p.chk_left[c.which] == 0) rs_jit_mark_verified(c.kd);
+  return RS_OK;
+}
+
+/* the launch has completed: a resident call's updates are dated now[k], and grants may be waiting */
+void group_commit_clocks(rs_group* g, const GroupCall& c) {
+  if (!c.resident()) return;
+  for (int k = 0; k < c.n; k++) {
+    const int cell = c.cell(k);
+    /* (an update-only slot credits nothing: behind an update no byte is waiting, without one nothing changed) */
+    if (!g->empty_slot[k]) g->pending_zero[cell] = 0;
+    else if (c.now[k] != g->last_update[cell]) g->pending_zero[cell] = 1;
+    g->last_update[cell] = c.now[k];
+  }
+}
+
+/* ... and the device holds these calls' reports now: the cells' image records, the statistics */
+void group_commit_images(rs_group* g, const GroupCall& c) {
+  for (int k = 0; k < c.n; k++) {
     if (g->empty_slot[k]) continue; /* (no reports, no image moved, not counted) */
+    const rs_tti_in& in = c.in[k];
     const int mode = g->modes[k];
-    rs_group::CellImage& im = g->img[cell_ids ? cell_ids[k] : k];
+    rs_group::CellImage& im = g->img[c.cell(k)];
     if (mode == 0) { g->n_plain++; im.valid = false; continue; } /* (as a context: a call without a number ends the image's term) */
     if (mode == 2) { g->n_reused++; continue; }
     g->n_stored++;
     im.valid = true;
-    im.epoch = in[k].cqi_epoch;
-    im.n = in[k].n_users;
-    im.prb = has_prb;
-    im.has_ids = in[k].user_id != nullptr;
-    if (in[k].user_id) im.ids.assign(in[k].user_id, in[k].user_id + in[k].n_users);
+    im.epoch = in.cqi_epoch;
+    im.n = in.n_users;
+    im.prb = c.has_prb;
+    im.has_ids = in.user_id != nullptr;
+    if (in.user_id) im.ids.assign(in.user_id, in.user_id + in.n_users);
   }
-  for (int k = 0; k < n; k++) {
+}
+
+void group_unpack(const rs_group* g, const GroupCall& c) {
+  const rs_batch* b = g->b;
+  for (int k = 0; k < c.n; k++) {
+    rs_tti_out& out = c.out[k];
     if (g->empty_slot[k]) { /* "nothing scheduled": the workgroup wrote no output */
-      if (out[k].rbg_to_user) for (int r = 0; r < b->R; r++) out[k].rbg_to_user[r] = -1;
+      if (out.rbg_to_user) for (int r = 0; r < b->R; r++) out.rbg_to_user[r] = -1;
       for (int s = 0; s < b->S; s++) {
-        if (out[k].target_rbs) out[k].target_rbs[s] = 0;
-        if (out[k].quota_rbgs) out[k].quota_rbgs[s] = 0;
+        if (out.target_rbs) out.target_rbs[s] = 0;
+        if (out.quota_rbgs) out.quota_rbgs[s] = 0;
       }
-      if (out[k].upper_rbg) for (int i = 0; i < b->S * b->R; i++) out[k].upper_rbg[i] = -1;
-      if (out[k].upper_user) for (int i = 0; i < b->S * b->R; i++) out[k].upper_user[i] = -1;
+      if (out.upper_rbg) for (int i = 0; i < b->S * b->R; i++) out.upper_rbg[i] = -1;
+      if (out.upper_user) for (int i = 0; i < b->S * b->R; i++) out.upper_user[i] = -1;
       continue;
     }
-    unpack_tti(b, &in[k], &out[k], g->h_out + (size_t)k * g->out_stride, g->packs[k].l, want_upper, flw ? flow[k] : nullptr);
+    unpack_tti(b, &c.in[k], &out, g->h_out + (size_t)k * g->out_stride, g->packs[k].l, c.want_upper, c.form == kGroupFlows ? c.flow[k] : nullptr);
     /* (a counted call: the slot's sent rows, [n_users][2] in call order, written by the threads that credited the positions) */
-    if (cnt && sent && sent[k]) memcpy(sent[k], g->h_sent + (size_t)k * 2 * (size_t)b->U, 8 * (size_t)in[k].n_users);
+    if (c.counted && c.sent && c.sent[k]) memcpy(c.sent[k], g->h_sent + (size_t)k * 2 * (size_t)b->U, 8 * (size_t)c.in[k].n_users);
   }
+}
+
+/* one group call, phase by phase; RS_DROPIN_TIMING splits it into prepare, enqueue, wait and unpack */
+int group_schedule(rs_group* g, GroupCall c) {
+  rs_batch* b = g->b;
+  using clk = std::chrono::steady_clock;
+  const clk::time_point t0 = g->timing ? clk::now() : clk::time_point();
+  int rc = group_validate(g, c);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(b->cfg.cell.device));
+  if ((rc = group_pack_slots(g, c))) return rc;
+  ImageGuard guard{g, c, false};
+  const clk::time_point t1 = g->timing ? clk::now() : clk::time_point();
+  c.zc = g->z_in != nullptr && !c.has_prb && !b->any_alpha;
+  RsLaunch L;
+  group_fill_launch(g, c, &L);
+  if ((rc = group_run(g, c, L))) return rc;
+  const clk::time_point t2 = g->timing ? clk::now() : clk::time_point();
+  if ((rc = group_wait(g, c))) return rc;
+  if (c.checked && (rc = group_check(g, c))) return rc;
+  guard.ok = true;
+  group_commit_clocks(g, c);
+  const clk::time_point t3 = g->timing ? clk::now() : clk::time_point();
+  group_commit_images(g, c);
+  group_unpack(g, c);
   if (g->timing) {
     const clk::time_point t4 = clk::now();
     auto us = [](clk::time_point a, clk::time_point b2) { return std::chrono::duration<double, std::micro>(b2 - a).count(); };
@@ -3253,9 +3285,9 @@ int group_schedule(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti
     g->t_wait += us(t2, t3);
     g->t_unpack += us(t3, t4);
     g->n_calls++;
-    g->n_cell_ttis += n;
+    g->n_cell_ttis += c.n;
   }
-  if (store_failed_now)
+  if (c.store_failed_now)
     snprintf(g_err, sizeof g_err, "note: the group's per-PRB report store (%zu bytes) could not be allocated: calls with cqi_prb are served as if "
              "cqi_epoch were 0 from now on (same results, the block is sent on every call)", g->prb_stride * (size_t)g->n_cells);
   return RS_OK;
@@ -3581,118 +3613,82 @@ int rs_group_image_stats(const rs_group* g, int64_t out[3]) {
 
 const char* rs_group_kernel_name(rs_group* g) {
   if (!g) return "";
-  /* (a resident call: the group's resident builds if rs_group_specialize_resident gave it some, else the built-in resident kernel --
-   * whatever serves the plain calls) */
-  if (g->last_call_kind == kGroupFlows) return g->kname_flw; /* (built in only) */
-  if (g->last_call_kind == kGroupQueued && g->last_call_counted) return g->kname_cnt; /* (built in only: no run-time build of the counted form) */
-  if (g->last_call_kind == kGroupQueued) return g->last_call_qjit ? "rs_group_queued_kernel_jit" : g->kname_que; /* (likewise: rs_group_specialize_queued) */
-  if (g->last_call_resident) return g->last_call_rjit ? "rs_group_resident_kernel_jit" : g->kname_res;
-  return g->jit[0] ? "rs_group_kernel_jit" : g->kname;
+  /* (the kernel of the last call's form: the group's own build when one served it.  After a plain call: whatever serves the plain
+   * calls now) */
+  const int row = g->last_call_form;
+  const bool jit = row == kGroupPlain ? g->pair[kGroupPlain].jit[0] != nullptr : g->last_call_jit;
+  return jit ? kGroupForms[row].jit_name : g->kname[row];
 }
 
 /* Shape specialisation of a group: rs_ctx_specialize for the group surface -- the one-TTI form compiled for the config's slices, RBGs,
- * PRBs per RBG, scheduler, workgroup size and user CAPACITY, one workgroup per call slot, in a general and a lean build.  Three pairs,
- * each an option of its own: rs_group_specialize (entry point rs_group_kernel_jit, serves rs_group_schedule_tti),
+ * PRBs per RBG, scheduler, workgroup size and user CAPACITY, one workgroup per call slot, in a general and a lean build.  Three pairs
+ * (rs_group::GroupPair), each an option of its own: rs_group_specialize (entry point rs_group_kernel_jit, serves rs_group_schedule_tti),
  * rs_group_specialize_resident (rs_group_resident_kernel_jit, serves rs_group_schedule_tti_at) and rs_group_specialize_queued
  * (rs_group_queued_kernel_jit, serves rs_group_schedule_tti_queued).  Between calls at any time: slice state, CQI images, per-PRB
  * stores, resident stores and bearer stores are not touched. */
 namespace {
-/* one pair's fields of rs_group */
-struct GroupJitPair {
-  RsJitKernel** jit;
-  bool *wanted, *dropped;
-  int *chk_left, *chk_agreed;
-  char* msg; /* [512] */
-};
 /* kind: kGroupPlain, kGroupResident or kGroupQueued -- the call the pair serves */
-GroupJitPair group_jit_pair(rs_group* g, int kind) {
-  if (kind == kGroupQueued) return {g->qjit, &g->qjit_wanted, &g->qjit_dropped, g->qchk_left, g->qchk_agreed, g->qjit_msg};
-  if (kind == kGroupResident) return {g->rjit, &g->rjit_wanted, &g->rjit_dropped, g->rchk_left, g->rchk_agreed, g->rjit_msg};
-  return {g->jit, &g->jit_wanted, &g->jit_dropped, g->chk_left, g->chk_agreed, g->jit_msg};
-}
-
 int group_specialize_pair(rs_group* g, int kind) {
   rs_batch* b = g->b;
-  const bool resident = kind == kGroupResident, queued = kind == kGroupQueued;
-  const GroupJitPair jp = group_jit_pair(g, kind);
-  if (jp.jit[0]) return RS_OK;
-  if (*jp.dropped) return fail(RS_ERR_STATE, "%s", jp.msg);
-  if (queued && b->sched != RS_SCHED_NVS && b->sched != RS_SCHED_SEQUENTIAL && b->sched != RS_SCHED_MAXCELL && b->sched != RS_SCHED_SUBOPT && b->sched != RS_SCHED_VOGEL)
+  const GroupForm& f = kGroupForms[kind];
+  rs_group::GroupPair& p = g->pair[f.pair];
+  if (p.jit[0]) return RS_OK;
+  if (p.dropped) return fail(RS_ERR_STATE, "%s", p.msg);
+  if (kind == kGroupQueued && b->sched != RS_SCHED_NVS && b->sched != RS_SCHED_SEQUENTIAL && b->sched != RS_SCHED_MAXCELL && b->sched != RS_SCHED_SUBOPT && b->sched != RS_SCHED_VOGEL)
     return fail(RS_ERR_INVALID, "scheduler %d has no queued form (rs_group_set_bearers): nothing for rs_group_specialize_queued to build", b->sched);
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  *jp.wanted = true;
+  p.wanted = true;
   if (!g->d_out2) {
     const size_t out_bytes = g->out_stride * (size_t)g->n_cells;
     if (hipMalloc(&g->d_out2, out_bytes) != hipSuccess || hipMalloc(&g->d_chk, 2 * group_chk_half(g)) != hipSuccess) {
       (void)hipGetLastError();
       if (g->d_out2) (void)hipFree(g->d_out2);
       g->d_out2 = g->d_chk = nullptr;
-      snprintf(jp.msg, 512, "allocation of the self-check's twin blocks failed (%zu + %zu bytes)", out_bytes, 2 * group_chk_half(g));
-      return fail(RS_ERR_HIP, "%s", jp.msg);
+      snprintf(p.msg, sizeof p.msg, "allocation of the self-check's twin blocks failed (%zu + %zu bytes)", out_bytes, 2 * group_chk_half(g));
+      return fail(RS_ERR_HIP, "%s", p.msg);
     }
     g->h_out2.assign(out_bytes, 0);
   }
-  if (resident && !g->d_rchk && hipMalloc(&g->d_rchk, 2 * group_rchk_half(g)) != hipSuccess) {
+  const size_t stores = 2 * group_stores(g, f).half;
+  if (stores && !p.d_stores_chk && hipMalloc(&p.d_stores_chk, stores) != hipSuccess) {
     (void)hipGetLastError();
-    g->d_rchk = nullptr;
-    snprintf(jp.msg, 512, "allocation of the self-check's copies of the resident stores failed (%zu bytes)", 2 * group_rchk_half(g));
-    return fail(RS_ERR_HIP, "%s", jp.msg);
-  }
-  if (queued && !g->d_qchk && hipMalloc(&g->d_qchk, 2 * group_qchk_half(g)) != hipSuccess) {
-    (void)hipGetLastError();
-    g->d_qchk = nullptr;
-    snprintf(jp.msg, 512, "allocation of the self-check's copies of the bearer stores failed (%zu bytes)", 2 * group_qchk_half(g));
-    return fail(RS_ERR_HIP, "%s", jp.msg);
+    p.d_stores_chk = nullptr;
+    snprintf(p.msg, sizeof p.msg, "allocation of the self-check's copies of the %s failed (%zu bytes)", f.stores, stores);
+    return fail(RS_ERR_HIP, "%s", p.msg);
   }
   const int qmode = (b->sched == RS_SCHED_PF || b->sched == RS_SCHED_NVS) ? 1 : 0; /* (the gate scratch of the group's carve: carve_lds) */
-  const int flags = 1 | 8 | (resident ? 16 : 0) | (queued ? 32 : 0);
   char msg[512] = "";
-  jp.jit[0] = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, qmode, 0, msg, sizeof msg, flags);
-  if (!jp.jit[0]) {
-    snprintf(jp.msg, 512, "%s", msg[0] ? msg : "hiprtc build failed");
-    return fail(RS_ERR_HIP, "%s", jp.msg);
+  p.jit[0] = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, qmode, 0, msg, sizeof msg, f.jit_flags);
+  if (!p.jit[0]) {
+    snprintf(p.msg, sizeof p.msg, "%s", msg[0] ? msg : "hiprtc build failed");
+    return fail(RS_ERR_HIP, "%s", p.msg);
   }
-  jp.msg[0] = 0;
+  p.msg[0] = 0;
   /* ... and its lean form (the plain call); without it the general build serves every call */
   const char* const e_on = getenv("RS_JIT_LEAN");
-  if (!e_on || atoi(e_on) != 0) jp.jit[1] = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, qmode, 0, msg, sizeof msg, flags | 4);
-  /* the policy and the switches of rs_ctx_specialize: no checked calls for a build that came with the mark of an earlier check */
-  int calls = 8;
-  if (const char* e = getenv("RS_DROPIN_SELFCHECK_CALLS")) calls = atoi(e) > 0 ? atoi(e) : 0;
-  const char* pol = getenv("RS_JIT_SELFCHECK");
-  const bool never = pol && pol[0] == '0', always = pol && pol[0] == '2';
-  for (int w = 0; w < 2; w++) {
-    jp.chk_agreed[w] = 0;
-    jp.chk_left[w] = (jp.jit[w] && !never && (always || !rs_jit_is_verified(jp.jit[w]))) ? calls : 0;
+  if (!e_on || atoi(e_on) != 0) p.jit[1] = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, qmode, 0, msg, sizeof msg, f.jit_flags | 4);
+  for (int w = 0; w < 2; w++) { /* (the policy and the switches of rs_ctx_specialize) */
+    p.chk_agreed[w] = 0;
+    p.chk_left[w] = selfcheck_calls(p.jit[w]);
   }
   return RS_OK;
 }
 
 int group_jit_pair_status(rs_group* g, int kind, char* msg, size_t msglen) {
-  const GroupJitPair jp = group_jit_pair(g, kind);
-  const char* const ref = kind == kGroupQueued     ? "the built-in queued kernel field by field, bearer stores included"
-                          : kind == kGroupResident ? "the built-in resident kernel field by field, resident stores included"
-                                                   : "the built-in kernel field by field";
+  const GroupForm& f = kGroupForms[kind];
+  const rs_group::GroupPair& p = g->pair[f.pair];
   if (msg && msglen) {
-    if (*jp.dropped || !jp.jit[0]) {
-      snprintf(msg, msglen, "%s", jp.msg);
+    if (p.dropped || !p.jit[0]) {
+      snprintf(msg, msglen, "%s", p.msg);
     } else {
-      auto state = [&](int which, char* out, size_t n) {
-        RsJitKernel* const k = jp.jit[which];
-        if (!k) snprintf(out, n, "not built");
-        else if (jp.chk_left[which] > 0) snprintf(out, n, "%d checked call(s) agreed with %s, %d to go", jp.chk_agreed[which], ref, jp.chk_left[which]);
-        else if (jp.chk_agreed[which] > 0) snprintf(out, n, "verified (%d checked calls agreed with %s)", jp.chk_agreed[which], ref);
-        else if (rs_jit_is_verified(k)) snprintf(out, n, "carries the self-check mark of an earlier check (cache file)");
-        else snprintf(out, n, "unchecked (RS_JIT_SELFCHECK=0)");
-      };
       char ge[220], le[220];
-      state(0, ge, sizeof ge);
-      state(1, le, sizeof le);
+      selfcheck_state(p.jit[0], p.chk_left[0], p.chk_agreed[0], f.ref, ge, sizeof ge);
+      selfcheck_state(p.jit[1], p.chk_left[1], p.chk_agreed[1], f.ref, le, sizeof le);
       snprintf(msg, msglen, "general build: %s; lean build: %s", ge, le);
     }
   }
-  if (*jp.dropped) return -2;
-  return jp.jit[0] ? 1 : (*jp.wanted ? -1 : 0);
+  if (p.dropped) return -2;
+  return p.jit[0] ? 1 : (p.wanted ? -1 : 0);
 }
 }  // namespace
 
