@@ -324,6 +324,13 @@ class Cell:
         assert k.shape == (self.U, 2)
         lib().rso_cell_enable_queues(self.h, _p(k, C.c_uint8))
 
+    def set_bearer_avg(self, avg):
+        """avg [U][2]: every bearer's average rate (after enable_queues)."""
+        a = np.ascontiguousarray(avg, np.float64)
+        assert a.shape == (self.U, 2)
+        lib().rso_cell_set_bearer_avg.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        lib().rso_cell_set_bearer_avg(self.h, _p(a, C.c_double))
+
     def set_arrivals(self, user, prio, time, n_full, last):
         t = np.ascontiguousarray(time, np.float64)
         nf = np.ascontiguousarray(n_full, np.int32)

@@ -1094,6 +1094,11 @@ void rso_cell_enable_queues(rso_cell* c, const uint8_t* bearer_kind /* [U][2] */
   c->prio_has_data.assign(c->U, 0);
 }
 
+/* every bearer's average rate from outside, [U][2] (after rso_cell_enable_queues; a test that starts the queue model from chosen averages) */
+void rso_cell_set_bearer_avg(rso_cell* c, const double* avg /* [U][2] */) {
+  for (size_t i = 0; i < c->bearers.size(); i++) c->bearers[i].avg = avg[i];
+}
+
 void rso_cell_set_arrivals(rso_cell* c, int user, int prio, int n, const double* time, const int32_t* n_full, const int32_t* last) {
   rso_cell::Bearer& b = c->bearers[(size_t)user * 2 + prio];
   b.arr_time.assign(time, time + n);

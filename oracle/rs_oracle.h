@@ -188,6 +188,7 @@ int rso_run_trace_prb(rso_cell* c, const rso_trace_run* run, int* log_rbg_to_use
  * bearer_kind [U][2], index = bearer priority: 0 none, 1 InfiniteBuffer, 2 finite queue fed by arrival bursts */
 #define RSO_FULL_PACKET 1495 /* MAXMTUSIZE 1490 + UDP 8 + IP 20, ROHC 28 -> 3, PDCP 2 (protocolStack/packet/Packet.cpp:84-118) */
 void rso_cell_enable_queues(rso_cell* c, const uint8_t* bearer_kind);
+void rso_cell_set_bearer_avg(rso_cell* c, const double* avg); /* [U][2], after rso_cell_enable_queues */
 /* arrival bursts of one bearer, ascending in time: at time[i] the application enqueues n_full[i] packets of RSO_FULL_PACKET
  * bytes and then, if last[i] > 0, one packet of last[i] bytes */
 void rso_cell_set_arrivals(rso_cell* c, int user, int prio, int n, const double* time, const int32_t* n_full, const int32_t* last);
