@@ -33,6 +33,8 @@ extern "C" {
                                rs_group_specialize_resident / rs_group_resident_jit_status / rs_jit_selfcheck_group_resident (a group's own builds of the resident kernel, self-checked on state),
                                rs_group_set_bearers / rs_group_get_bearers / rs_group_schedule_tti_queued (a group cell's two bearers per user resident on the device: finite queues credited there),
                                rs_group_specialize_queued / rs_group_queued_jit_status / rs_jit_selfcheck_group_queued (a group's own builds of the queued kernel, self-checked on the bearer stores),
+                               rs_group_specialize_counted / rs_group_counted_jit_status / rs_jit_selfcheck_group_counted and rs_group_specialize_flows / rs_group_flows_jit_status / rs_jit_selfcheck_group_flows
+                               (a group's own builds of the counted and of the flows kernel, self-checked on bearer stores, counters and sent rows),
                                rs_group_set_counters / rs_group_get_counters / rs_group_schedule_tti_counted (a bearer-resident group cell's m_cumulateBytes / m_cumulateRBs on the device, the bytes sent per bearer returned per call),
                                rs_group_set_flows / rs_group_get_flows / rs_group_schedule_tti_flows (scheduler 1's flows of a group cell resident on the device: averages, pending bytes and counters per bearer, the whole block credited to the flow);
                                rs_config.link_tables (RS_LINK_*) + rs_link_tables_pinned / rs_link_tables_compare, rs_tti_in.cqi_epoch (the context keeps the
@@ -318,9 +320,10 @@ int rs_group_image_stats(const rs_group* g, int64_t out[3]);
  * after a build was dropped.  While the last call was a resident one: "rs_group_resident_kernel_jit" if the group's resident builds
  * served it (rs_group_specialize_resident), else the built-in "rs_group_resident_kernel<sched, ept>".  While it was a queued one:
  * "rs_group_queued_kernel_jit" if the group's queued builds served it (rs_group_specialize_queued), else the built-in
- * "rs_group_queued_kernel<sched, ept>".  While it was a counted one (rs_group_schedule_tti_counted): the built-in
- * "rs_group_counted_kernel<sched, ept>".  While it was a flows one (rs_group_schedule_tti_flows): the built-in
- * "rs_group_flows_kernel<1, 0>". */
+ * "rs_group_queued_kernel<sched, ept>".  While it was a counted one (rs_group_schedule_tti_counted): "rs_group_counted_kernel_jit" if
+ * the group's counted builds served it (rs_group_specialize_counted), else the built-in "rs_group_counted_kernel<sched, ept>".  While
+ * it was a flows one (rs_group_schedule_tti_flows): "rs_group_flows_kernel_jit" if the group's flows builds served it
+ * (rs_group_specialize_flows), else the built-in "rs_group_flows_kernel<1, 0>". */
 const char* rs_group_kernel_name(rs_group* g);
 /* Optional, at any time between two calls: rs_ctx_specialize for a group -- the one-TTI kernel compiled for the config's slices, RBGs,
  * PRBs per RBG, scheduler, workgroup size and user capacity (hiprtc, ~2 s per build and process, cached on disk apart from the
@@ -496,8 +499,8 @@ int rs_jit_selfcheck_group_queued(int n_slices, int n_users, int n_rbgs, int rbg
  *      cum_bytes[u][b] += sent;  cum_rbs[u][b] += the position's allocated PRBs (rs_tti_out.user_nprb[i]: the reference's
  *      GetListOfAllocatedRBs()->size(), the same count for both bearers of a split grant);  sent[k][i][b] = sent,
  * and sent[k][i][b] = 0 for a bearer that is not credited.  Update-only slots and positions without a grant move no counter.
- * Counted calls run the built-in "rs_group_counted_kernel<sched, ept>", after rs_group_specialize_queued too: no run-time build
- * reaches them. */
+ * Counted calls run the built-in "rs_group_counted_kernel<sched, ept>", after rs_group_specialize_queued too; a host that wants
+ * run-time builds of this form opts in with rs_group_specialize_counted below. */
 /* Makes a bearer-resident `cell` counted (again, at any time between two calls) and sets its counters: [U][2] by user id and bearer
  * priority, NULL = zeros.  A synchronising copy outside the fast path.  RS_ERR_STATE: the cell is not bearer-resident; RS_ERR_INVALID:
  * a negative value.  rs_group_set_bearers leaves the counters and the counted state as they are (a bearer that does not exist is
@@ -514,6 +517,25 @@ int rs_group_get_counters(rs_group* g, int32_t cell, int64_t* cum_bytes /* [U][2
 int rs_group_schedule_tti_counted(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in /* [n] */, rs_tti_out* out /* [n] */,
                                   const double* now /* [n] */, const int32_t* const* data_to_transmit /* [n]: [in[k].n_users][2] */,
                                   int32_t* const* sent /* [n]: [in[k].n_users][2]; NULL, or NULL per update-only slot */);
+/* rs_group_specialize_queued for the COUNTED call (ABI 11 addition), to the letter: the counted kernel compiled for the group's shape
+ * (entry point rs_group_counted_kernel_jit, cache files of its own), a general and a lean build picked by the queued call's per-launch
+ * condition (a call made of update-only slots only takes the lean build, unless the config rules it out); at any time between two
+ * calls, a second call is a no-op; RS_ERR_HIP if a build fails, the group left on the built-in counted kernel; RS_ERR_STATE (with the
+ * reason) once the counted builds were dropped; RS_ERR_INVALID for a scheduler without the form.  The five pairs are independent in
+ * both directions: rs_group_specialize_queued does not reach counted calls, this one does not reach queued calls.
+ * The check is the queued pair's (policy, switches, the mark in the cache file) on more stores: for every user id of the config and
+ * both bearers avg, pending_bytes, last_update, cum_bytes[U][2] and cum_rbs[U][2] (int64, bit for bit) are kept, put back and compared,
+ * and so is sent[k][i][b] of every named slot that has users -- the built-in kernel writes a twin sent block, allocated by the first
+ * checked call, whether or not the caller passes `sent` or a slot's row.  One difference drops the counted pair alone and unlinks its two
+ * cache files; that call returns the built-in kernel's outputs, sent rows and state with RS_OK; later counted calls run the built-in
+ * kernel; the message names cell, field and index ("cell 1: cum_rbs[7][0] = 5, the built-in kernel's 4", "cell 0: sent[3][1] = 301, the
+ * built-in kernel's 300").  rs_group_launch_count counts a checked call once. */
+int rs_group_specialize_counted(rs_group* g);
+/* rs_group_jit_status for the counted pair: 1 / 0 / -1 / -2 as rs_group_queued_jit_status; every status reports its own pair only. */
+int rs_group_counted_jit_status(rs_group* g, char* msg, size_t msglen);
+/* build check without a GPU: do the general and the lean counted build of a group of this shape compile?  (the larger code size, or a
+ * negative value with a message for the schedulers without the form, rs_jit_selfcheck_group_queued's) */
+int rs_jit_selfcheck_group_counted(int n_slices, int n_users, int n_rbgs, int rbg_size, int threads, int sched, char* err, size_t errlen);
 
 /* Resident flows (ABI 11 addition, no layout changed): RS_SCHED_PF alone.  DL_PF_PacketScheduler races FLOWS -- bearers with data, in
  * RRC-container order --, divides by the flow's own average and credits the whole transport block to the flow (ref:
@@ -528,7 +550,7 @@ int rs_group_schedule_tti_counted(rs_group* g, int32_t n, const int32_t* cell_id
  *      cum_rbs[u][b] += user_nprb[i] -- no min with the data: the reference hands the whole block to the RLC.
  * rs_group_set_bearers stays refused on a scheduler-1 group, and the queued, counted and resident-average calls refuse a flow-resident
  * cell (RS_ERR_STATE); rs_group_schedule_tti serves it as before and touches none of this state.  Flows calls run the built-in
- * "rs_group_flows_kernel<1, 0>": no run-time build reaches them. */
+ * "rs_group_flows_kernel<1, 0>"; a host that wants run-time builds of this form opts in with rs_group_specialize_flows below. */
 /* Makes `cell` flow-resident (again, at any time between two calls): has_bearer and avg [U][2] by user id and bearer index, zero
  * pending bytes, last_update, and the counters (NULL = zeros).  A cell is resident in one form at a time: the later of
  * rs_group_set_avg / rs_group_set_flows wins.  RS_ERR_INVALID: the scheduler is not RS_SCHED_PF (not served); exponents outside
@@ -550,6 +572,19 @@ int rs_group_get_flows(rs_group* g, int32_t cell, double* avg /* [U][2] */, int3
  * cell that is not flow-resident); RS_ERR_HIP ends the flow-resident state of the cells the call named. */
 int rs_group_schedule_tti_flows(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in /* [n] */, rs_tti_out* out /* [n] */,
                                 const double* now /* [n] */, const uint8_t* const* flow_bearer /* [n]: [in[k].n_users], 0 or 1 */);
+/* rs_group_specialize_queued for the FLOWS call (ABI 11 addition): the flows kernel compiled for the group's shape (entry point
+ * rs_group_flows_kernel_jit, cache files of its own), a general and a lean build.  A flows call always carries the data_to_transmit gate,
+ * so its lean build keeps the gate and is picked when no slot brings per-PRB reports, the exact scan or synthetic-experiment blocks (and
+ * the config has no customised slices).  When, errors, independence of the five pairs and the check are rs_group_specialize_counted's;
+ * RS_ERR_INVALID for every scheduler but RS_SCHED_PF.  The check keeps, puts back and compares avg, pending_bytes, last_update,
+ * cum_bytes[U][2] and cum_rbs[U][2] of every user id and both bearers; the message names cell, field and index ("cell 2:
+ * cum_bytes[4][1] = 1201, the built-in kernel's 1200"). */
+int rs_group_specialize_flows(rs_group* g);
+/* rs_group_jit_status for the flows pair: 1 / 0 / -1 / -2 as rs_group_queued_jit_status; every status reports its own pair only. */
+int rs_group_flows_jit_status(rs_group* g, char* msg, size_t msglen);
+/* build check without a GPU: do the general and the lean flows build of a group of this shape compile?  (the larger code size, or a
+ * negative value with a message for every scheduler but RS_SCHED_PF) */
+int rs_jit_selfcheck_group_flows(int n_slices, int n_users, int n_rbgs, int rbg_size, int threads, int sched, char* err, size_t errlen);
 
 /* ------------------------------------------------------------------------------------------
  * Batched mode: many independent cells resident on the device, whole DoSchedule() loops

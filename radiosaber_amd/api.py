@@ -116,6 +116,8 @@ ABI_SYMBOLS = [
     "rs_group_specialize_queued", "rs_group_queued_jit_status", "rs_jit_selfcheck_group_queued",
     "rs_group_set_counters", "rs_group_get_counters", "rs_group_schedule_tti_counted",
     "rs_group_set_flows", "rs_group_get_flows", "rs_group_schedule_tti_flows",
+    "rs_group_specialize_counted", "rs_group_counted_jit_status", "rs_jit_selfcheck_group_counted",
+    "rs_group_specialize_flows", "rs_group_flows_jit_status", "rs_jit_selfcheck_group_flows",
 ]
 
 _lib = None
@@ -183,6 +185,12 @@ def lib():
     L.rs_group_specialize_queued.argtypes = [C.c_void_p]
     L.rs_group_queued_jit_status.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.rs_jit_selfcheck_group_queued.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
+    L.rs_group_specialize_counted.argtypes = [C.c_void_p]
+    L.rs_group_counted_jit_status.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    L.rs_jit_selfcheck_group_counted.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
+    L.rs_group_specialize_flows.argtypes = [C.c_void_p]
+    L.rs_group_flows_jit_status.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    L.rs_jit_selfcheck_group_flows.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
     L.rs_batch_create.restype = C.c_void_p
     L.rs_batch_create.argtypes = [C.POINTER(_BatchConfig)]
     L.rs_create_checked.restype = C.c_void_p
@@ -278,13 +286,15 @@ def _p(a, t):
 
 
 def jit_selfcheck(n_slices, n_users, n_rbgs, rbg_size, threads=512, sched=RS_SCHED_MAXCELL, queues=False, untuned=False, dropin=False,
-                  group=False, resident=False, queued=False):
+                  group=False, resident=False, queued=False, counted=False, flows=False):
     """Compile the shape-specialised kernel for one shape (hiprtc, no GPU needed); returns the code size.  queues=True: the
     queue-model kernel of the shape.  untuned=True: without the -mllvm tuning options (the library's fallback build).
     group=True: the general and the lean build of a group of this shape (rs_group_specialize); the larger code size.
     group=True, resident=True: the two builds of the group's resident kernel (rs_group_specialize_resident).
-    group=True, queued=True: the two builds of the group's queued kernel (rs_group_specialize_queued; schedulers 7, 8, 9, 101, 103)."""
-    _jit_flags(False, False, group, resident, queued)
+    group=True, queued=True: the two builds of the group's queued kernel (rs_group_specialize_queued; schedulers 7, 8, 9, 101, 103).
+    group=True, counted=True: the two builds of the group's counted kernel (rs_group_specialize_counted; the queued form's schedulers).
+    group=True, flows=True: the two builds of the group's flows kernel (rs_group_specialize_flows; scheduler 1)."""
+    _jit_flags(False, False, group, resident, queued, counted, flows)
     buf = C.create_string_buffer(4096)
     fn = lib().rs_jit_selfcheck_queue if queues else (lib().rs_jit_selfcheck_untuned if untuned else lib().rs_jit_selfcheck)
     if dropin:  # the drop-in entry point's one-TTI kernel of a context of this shape (rs_ctx_specialize)
@@ -293,6 +303,10 @@ def jit_selfcheck(n_slices, n_users, n_rbgs, rbg_size, threads=512, sched=RS_SCH
         fn = lib().rs_jit_selfcheck_group_resident if resident else lib().rs_jit_selfcheck_group
         if queued:
             fn = lib().rs_jit_selfcheck_group_queued
+        if counted:
+            fn = lib().rs_jit_selfcheck_group_counted
+        if flows:
+            fn = lib().rs_jit_selfcheck_group_flows
     n = fn(n_slices, n_users, n_rbgs, rbg_size, threads, sched, buf, 4096)
     if n < 0:
         raise RadioSaberError(n, buf.value.decode(errors="replace"))
@@ -306,33 +320,46 @@ def jit_cache_stats():
     return dict(zip(("hits", "misses", "stores", "rejected"), (int(x) for x in out)))
 
 
-def _jit_flags(lean, streamed, group, resident, queued=False):
+def _jit_flags(lean, streamed, group, resident, queued=False, counted=False, flows=False):
+    if counted and not group:
+        raise ValueError("counted=True needs group=True: only a group has a counted kernel")
+    if flows and not group:
+        raise ValueError("flows=True needs group=True: only a group has a flows kernel")
+    if counted and resident:
+        raise ValueError("resident=True and counted=True exclude each other: two forms of a group's kernel")
+    if flows and (resident or queued or counted):
+        raise ValueError("flows=True excludes resident=True, queued=True and counted=True: a form of a group's kernel of its own")
+    if counted:
+        queued = True  # (the counted form is the queued form's twin: flag value 64 is valid only together with 32)
     if resident and not group:
         raise ValueError("resident=True needs group=True: only a group has a resident kernel")
     if queued and not group:
         raise ValueError("queued=True needs group=True: only a group has a queued kernel")
     if queued and resident:
         raise ValueError("resident=True and queued=True exclude each other: two forms of a group's kernel")
-    return (4 if lean else 0) | (2 if streamed else 0) | (8 if group else 0) | (16 if resident else 0) | (32 if queued else 0)
+    return (4 if lean else 0) | (2 if streamed else 0) | (8 if group else 0) | (16 if resident else 0) | (32 if queued else 0) | \
+        (64 if counted else 0) | (128 if flows else 0)
 
 
 def jit_cache_file(n_slices, n_users, n_rbgs, rbg_size, threads=512, sched=RS_SCHED_MAXCELL, lean=False, streamed=False, group=False,
-                   resident=False, queued=False):
+                   resident=False, queued=False, counted=False, flows=False):
     """Path of the cache file the batch kernel of this shape lives in ('' when no cache directory can be named).  group=True: a
     group's build of the one-TTI kernel (flag bit of value 8); with resident=True its resident form (value 16), with queued=True its
-    queued form (value 32)."""
+    queued form (value 32), with counted=True the queued form's counted twin (values 32 and 64), with flows=True scheduler 1's flows form
+    (value 128)."""
     buf = C.create_string_buffer(4096)
-    lib().rs_jit_cache_file(n_slices, n_users, n_rbgs, rbg_size, threads, sched, _jit_flags(lean, streamed, group, resident, queued),
+    lib().rs_jit_cache_file(n_slices, n_users, n_rbgs, rbg_size, threads, sched, _jit_flags(lean, streamed, group, resident, queued, counted, flows),
                             buf, 4096)
     return buf.value.decode()
 
 
 def jit_cache_warm(n_slices, n_users, n_rbgs, rbg_size, threads=512, sched=RS_SCHED_MAXCELL, lean=False, streamed=False, group=False,
-                   resident=False, queued=False):
+                   resident=False, queued=False, counted=False, flows=False):
     """Compile (or load) the batch kernel of this shape through the disk cache; no GPU needed.  Returns the code size.
-    group=True: a group's build of the one-TTI kernel; with resident=True its resident form, with queued=True its queued form."""
+    group=True: a group's build of the one-TTI kernel; with resident=True its resident form, with queued=True its queued form, with
+    counted=True its counted form, with flows=True its flows form."""
     buf = C.create_string_buffer(4096)
-    n = lib().rs_jit_cache_warm(n_slices, n_users, n_rbgs, rbg_size, threads, sched, _jit_flags(lean, streamed, group, resident, queued),
+    n = lib().rs_jit_cache_warm(n_slices, n_users, n_rbgs, rbg_size, threads, sched, _jit_flags(lean, streamed, group, resident, queued, counted, flows),
                                 buf, 4096)
     if n < 0:
         raise RadioSaberError(n, buf.value.decode(errors="replace"))
@@ -659,9 +686,10 @@ class GroupScheduler:
 
     def __init__(self, slices: SliceConfig, n_rbgs: int, rbg_size: int, n_cells: int, sched: int = RS_SCHED_MAXCELL,
                  device: int = 0, stream: Optional[int] = None, synthetic_exp: bool = False, link_tables: int = RS_LINK_DEFAULT,
-                 jit: bool = False, jit_resident: bool = False, jit_queued: bool = False):
+                 jit: bool = False, jit_resident: bool = False, jit_queued: bool = False, jit_counted: bool = False, jit_flows: bool = False):
         """jit: specialize() right after the group is created.  jit_resident: specialize_resident() as well (independent of jit).
-        jit_queued: specialize_queued() as well (independent of both)."""
+        jit_queued: specialize_queued() as well (independent of both).  jit_counted / jit_flows: specialize_counted() /
+        specialize_flows() as well (independent of all others)."""
         self.slices, self.R, self.rbg_size, self.sched, self.n_cells = slices, n_rbgs, rbg_size, sched, n_cells
         self._cfg = _CfgHolder(slices, n_rbgs, rbg_size, sched, device, stream, synthetic_exp, link_tables)
         self._h = lib().rs_group_create_checked(C.byref(self._cfg.c), n_cells, RS_ABI_VERSION, C.sizeof(_Config))
@@ -673,6 +701,10 @@ class GroupScheduler:
             self.specialize_resident()
         if jit_queued:
             self.specialize_queued()
+        if jit_counted:
+            self.specialize_counted()
+        if jit_flows:
+            self.specialize_flows()
 
     def specialize(self):
         """rs_group_specialize: the group's own hiprtc builds of the one-TTI kernel (identical results; their first calls run beside
@@ -711,6 +743,34 @@ class GroupScheduler:
         -1 build failed, -2 dropped by the self-check."""
         buf = C.create_string_buffer(768)
         rc = lib().rs_group_queued_jit_status(self._h, buf, 768)
+        return rc, buf.value.decode(errors="replace")
+
+    def specialize_counted(self):
+        """rs_group_specialize_counted: the group's own hiprtc builds of the COUNTED kernel, for schedule_tti_counted (identical results;
+        their first calls run beside the built-in counted kernel and are compared on outputs, sent rows and state -- slice state, both
+        bearers' averages, pending bytes, cum_bytes and cum_rbs of every user, last update -- unless the builds carry the self-check
+        mark: counted_jit_status()).  Independent of the other four pairs; any time between two calls; again: a no-op."""
+        _check(lib().rs_group_specialize_counted(self._h))
+
+    def counted_jit_status(self):
+        """(code, message) of rs_group_counted_jit_status, for the counted builds alone: 1 they serve the counted calls, 0 not asked
+        for, -1 build failed, -2 dropped by the self-check."""
+        buf = C.create_string_buffer(768)
+        rc = lib().rs_group_counted_jit_status(self._h, buf, 768)
+        return rc, buf.value.decode(errors="replace")
+
+    def specialize_flows(self):
+        """rs_group_specialize_flows: the group's own hiprtc builds of scheduler 1's FLOWS kernel, for schedule_tti_flows (identical
+        results; their first calls run beside the built-in flows kernel and are compared on outputs and on state -- slice state, both
+        bearers' averages, pending bytes, cum_bytes and cum_rbs of every user, last update -- unless the builds carry the self-check
+        mark: flows_jit_status()).  Independent of the other four pairs; any time between two calls; again: a no-op."""
+        _check(lib().rs_group_specialize_flows(self._h))
+
+    def flows_jit_status(self):
+        """(code, message) of rs_group_flows_jit_status, for the flows builds alone: 1 they serve the flows calls, 0 not asked for,
+        -1 build failed, -2 dropped by the self-check."""
+        buf = C.create_string_buffer(768)
+        rc = lib().rs_group_flows_jit_status(self._h, buf, 768)
         return rc, buf.value.decode(errors="replace")
 
     def close(self):

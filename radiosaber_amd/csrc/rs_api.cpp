@@ -2445,9 +2445,10 @@ struct rs_group {
   bool timing = false;
   double t_prep = 0, t_enq = 0, t_wait = 0, t_unpack = 0;
   long n_calls = 0, n_cell_ttis = 0, n_polled = 0, n_fallback = 0;
-  /* Run-time builds of a group call's kernel (rs_group_specialize, rs_group_specialize_resident, rs_group_specialize_queued): one pair
-   * of builds per form that has any (index 0: general build, 1: lean build for the plain call), and their check against the form's
-   * built-in kernel -- calls still to be checked, calls that agreed so far (rs_ctx's scheme).  The three pairs are independent: each
+  /* Run-time builds of a group call's kernel (rs_group_specialize, rs_group_specialize_resident, rs_group_specialize_queued,
+   * rs_group_specialize_flows, rs_group_specialize_counted): one pair
+   * of builds per form (index 0: general build, 1: lean build for the plain call), and their check against the form's
+   * built-in kernel -- calls still to be checked, calls that agreed so far (rs_ctx's scheme).  The five pairs are independent: each
    * serves its own kind of call, is checked against its own built-in kernel and is dropped alone.  The check of a form with stores
    * (kGroupForms) also compares those: d_stores_chk holds them before the built-in kernel ran and as that kernel left them (two halves,
    * group_copy_stores). */
@@ -2458,7 +2459,7 @@ struct rs_group {
     uint8_t* d_stores_chk = nullptr;
     char msg[512] = "";
   };
-  GroupPair pair[3]; /* by kGroupPlain, kGroupResident, kGroupQueued */
+  GroupPair pair[5]; /* by kGroupPlain, kGroupResident, kGroupQueued, kGroupFlows, kGroupCounted */
   uint8_t *d_out2 = nullptr, *d_chk = nullptr; /* every pair's: the built-in kernel's output slots; the group's slice state + scalars before / after it */
   std::vector<uint8_t> h_out2;
   /* resident averages (rs_group_set_avg, rs_group_schedule_tti_at): per cell [U] averages, [U] pending bytes and the time of their
@@ -2480,14 +2481,15 @@ struct rs_group {
   /* counted bearers (rs_group_set_counters, rs_group_schedule_tti_counted): per cell [U][2] m_cumulateBytes / m_cumulateRBs beside the
    * bearer stores (allocated by the first rs_group_set_counters), and which cells are counted -- a state on top of resident[cell] == 2.
    * The slots' sent rows come back in a pinned block of their own (h_sent: [n_cells][U][2], mapped: z_sent, else copied from d_sent),
-   * as the data words travel in h_qin.  Counted calls run the built-in counted kernel: no run-time build of this form. */
+   * as the data words travel in h_qin.  h_sent2 / z_sent2 / d_sent2: the twin block the built-in kernel writes in a checked call of the
+   * counted pair, sized and mapped as the first (allocated by the first checked call: group_alloc_sent_twin). */
   int64_t *d_cbytes = nullptr, *d_crbs = nullptr;
   int32_t *h_sent = nullptr, *z_sent = nullptr, *d_sent = nullptr;
+  int32_t *h_sent2 = nullptr, *z_sent2 = nullptr, *d_sent2 = nullptr;
   std::vector<uint8_t> counted;
   /* resident flows (rs_group_set_flows, rs_group_schedule_tti_flows; scheduler 1 alone): resident[cell] == 3.  The cell's flows live in
    * the bearer stores and the counter stores above (a cell is resident in one form at a time), has_bearer mirrors their existence
-   * bytes, and the slots' bearer words (0 or 1 per call position) travel in h_qin, one word per position.  Flows calls run the
-   * built-in flows kernel: no run-time build of this form. */
+   * bytes, and the slots' bearer words (0 or 1 per call position) travel in h_qin, one word per position. */
   /* rs_group_kernel_name: the last call's form (a row of kGroupForms), whether a run-time build served it, the built-in kernels' names by row */
   int last_call_form = 0;
   bool last_call_jit = false;
@@ -2514,9 +2516,10 @@ struct GroupForm {
   hipError_t (*launch)(const RsLaunch*, int, hipStream_t); /* the built-in launcher */
   unsigned sets;
   bool slots0;     /* update-only slots (n_users == 0) are allowed */
-  int pair;        /* rs_group::pair[] that serves the form, -1: built-in kernel only */
-  int store_width; /* the stores its self-check saves, restores and compares: 0 none, 1 the resident stores [U], 2 the bearer stores [U][2] */
-  int jit_flags;   /* rs_jit_get: 1 one-TTI form, 8 group wrapper, 16 resident, 32 queued */
+  int pair;        /* rs_group::pair[] that serves the form */
+  int store_width; /* the stores its self-check saves, restores and compares: 0 none, 1 the resident stores [U], 2 the bearer stores [U][2]
+                    * (a form with kSetCounters: the counter stores [U][2] too; with kSetSent: the slots' sent rows are compared as well) */
+  int jit_flags;   /* rs_jit_get: 1 one-TTI form, 8 group wrapper, 16 resident, 32 queued, 64 counted, 128 flows */
   const char* jit_name;
   /* the nouns of the pair's messages: "specialised <adj>%s build", "both <adj>builds are dropped, <serves>", "agreed with <ref>",
    * "copies of the <stores>" */
@@ -2528,8 +2531,11 @@ const GroupForm kGroupForms[5] = {
      "the built-in resident kernel serves this group's resident calls", "the built-in resident kernel field by field, resident stores included", "resident stores"},
     {rs_launch_group_queued, kSetResident | kSetBearers, true, kGroupQueued, 2, 1 | 8 | 32, "rs_group_queued_kernel_jit", "queued ",
      "the built-in queued kernel serves this group's queued calls", "the built-in queued kernel field by field, bearer stores included", "bearer stores"},
-    {rs_launch_group_flows, kSetResident | kSetBearers | kSetCounters, true, -1, 0, 0, nullptr, "", "", "", ""},
-    {rs_launch_group_counted, kSetResident | kSetBearers | kSetCounters | kSetSent, true, -1, 0, 0, nullptr, "", "", "", ""},
+    {rs_launch_group_flows, kSetResident | kSetBearers | kSetCounters, true, kGroupFlows, 2, 1 | 8 | 128, "rs_group_flows_kernel_jit", "flows ",
+     "the built-in flows kernel serves this group's flows calls", "the built-in flows kernel field by field, bearer stores and counters included", "bearer stores and counters"},
+    {rs_launch_group_counted, kSetResident | kSetBearers | kSetCounters | kSetSent, true, kGroupCounted, 2, 1 | 8 | 32 | 64, "rs_group_counted_kernel_jit", "counted ",
+     "the built-in counted kernel serves this group's counted calls", "the built-in counted kernel field by field, bearer stores, counters and sent rows included",
+     "bearer stores and counters"},
 };
 
 /* bytes of one half of rs_group::d_chk: [n_cells][S] slice state, then [n_cells] RsCellScalars */
@@ -2539,27 +2545,29 @@ size_t group_chk_half(const rs_group* g) { return group_chk_sstate(g) + round_up
 /* The stores that a form's self-check saves, restores and compares, in the order they lie in a half of GroupPair::d_stores_chk (each
  * rounded up to 256 bytes): the averages, the cells' last-update times, the pending bytes -- of every user id of the config (the update
  * touches them all), for the bearer stores of BOTH bearers. */
+enum GroupStoreKind { kStoreI32, kStoreF64, kStoreI64 }; /* every kind is compared bitwise; the kind is the element's size and how a message prints it */
 struct GroupStore {
   void* dev;        /* [n_cells][elems] */
   size_t elems;     /* per cell */
-  bool f64;         /* doubles (compared bitwise, as the int32 of the other kind are) */
+  GroupStoreKind kind;
   const char* name; /* in a message, followed by the element's index */
-  size_t size() const { return f64 ? 8 : 4; }
+  size_t size() const { return kind == kStoreI32 ? 4 : 8; }
   size_t bytes(const rs_group* g) const { return size() * elems * (size_t)g->n_cells; }
   size_t kept(const rs_group* g) const { return (size_t)round_up((int)bytes(g), 256); }
 };
 struct GroupStores {
-  GroupStore part[3];
-  int n;       /* 0 or 3 */
+  GroupStore part[5];
+  int n;       /* 0, 3, or 5: a form that keeps counters (kSetCounters) has m_cumulateBytes / m_cumulateRBs behind the other three */
   size_t half; /* bytes of one half of the check block */
 };
 GroupStores group_stores(const rs_group* g, const GroupForm& f) {
   if (!f.store_width) return {};
   const bool two = f.store_width == 2;
   const size_t e = (size_t)f.store_width * g->b->U;
-  GroupStores s = {{{two ? g->d_qavg : g->d_ravg, e, true, "avg"}, {g->d_rlast, 1, true, "last_update"},
-                    {two ? (void*)g->d_qpend : (void*)g->d_rpend, e, false, "pending_bytes"}}, 3, 0};
-  for (const GroupStore& x : s.part) s.half += x.kept(g);
+  GroupStores s = {{{two ? g->d_qavg : g->d_ravg, e, kStoreF64, "avg"}, {g->d_rlast, 1, kStoreF64, "last_update"},
+                    {two ? (void*)g->d_qpend : (void*)g->d_rpend, e, kStoreI32, "pending_bytes"},
+                    {g->d_cbytes, e, kStoreI64, "cum_bytes"}, {g->d_crbs, e, kStoreI64, "cum_rbs"}}, (f.sets & kSetCounters) ? 5 : 3, 0};
+  for (int i = 0; i < s.n; i++) s.half += s.part[i].kept(g);
   return s;
 }
 /* a form's stores to (save) or from one half of its pair's check block */
@@ -2665,11 +2673,12 @@ void rs_group_destroy(rs_group* g) {
             g->t_unpack / g->n_calls, g->n_polled, g->n_fallback, (long long)g->n_reused, (long long)g->n_stored, (long long)g->n_plain);
   if (g->b && g->b->stream) (void)hipStreamSynchronize(g->b->stream);
   for (void* q : {(void*)g->d_in, (void*)g->d_out, (void*)g->d_count, (void*)g->d_img, (void*)g->d_prb, (void*)g->d_out2, (void*)g->d_chk,
-                  (void*)g->pair[0].d_stores_chk, (void*)g->pair[1].d_stores_chk, (void*)g->pair[2].d_stores_chk, (void*)g->d_ravg,
+                  (void*)g->pair[0].d_stores_chk, (void*)g->pair[1].d_stores_chk, (void*)g->pair[2].d_stores_chk, (void*)g->pair[3].d_stores_chk,
+                  (void*)g->pair[4].d_stores_chk, (void*)g->d_sent2, (void*)g->d_ravg,
                   (void*)g->d_rpend, (void*)g->d_rlast, (void*)g->d_rgather, (void*)g->d_ruid, (void*)g->d_qavg, (void*)g->d_qpend,
                   (void*)g->d_qdata, (void*)g->d_qhas, (void*)g->d_qin, (void*)g->d_cbytes, (void*)g->d_crbs, (void*)g->d_sent})
     if (q) (void)hipFree(q);
-  for (void* q : {(void*)g->h_qin, (void*)g->h_sent, (void*)g->h_in, (void*)g->h_out})
+  for (void* q : {(void*)g->h_qin, (void*)g->h_sent, (void*)g->h_sent2, (void*)g->h_in, (void*)g->h_out})
     if (q) (void)hipHostFree(q);
   rs_batch_destroy(g->b);
   delete g;
@@ -3034,6 +3043,29 @@ void group_fill_launch(const rs_group* g, const GroupCall& c, RsLaunch* launch) 
   }
 }
 
+/* the twin of the counted calls' sent block for the built-in kernel of a checked call: pinned and mapped when the first is, else a
+ * device block copied back; allocated by the first checked call of the counted pair (the counter stores, and with them h_sent, may not
+ * exist yet when the pair is built) */
+bool group_alloc_sent_twin(rs_group* g) {
+  if (g->h_sent2) return true;
+  const size_t nb = 2 * (size_t)g->b->U * (size_t)g->n_cells;
+  bool ok = hipHostMalloc((void**)&g->h_sent2, 4 * nb, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
+  if (ok && g->z_sent) {
+    void* z = nullptr;
+    if (hipHostGetDevicePointer(&z, g->h_sent2, 0) == hipSuccess) g->z_sent2 = (int32_t*)z;
+  }
+  if (ok && !g->z_sent2) ok = hipMalloc(&g->d_sent2, 4 * nb) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    if (g->d_sent2) (void)hipFree(g->d_sent2);
+    if (g->h_sent2) (void)hipHostFree(g->h_sent2);
+    g->d_sent2 = g->h_sent2 = g->z_sent2 = nullptr;
+    return false;
+  }
+  memset(g->h_sent2, 0, 4 * nb);
+  return true;
+}
+
 /* A checked call: the form's built-in kernel first, on the same slots and the same state, its outputs into slots of its own.  What it
  * left is kept, what it found is put back: the run-time build starts from the same state.  (A mode-1 slot: BOTH kernels transpose the
  * slot's block and store the cell's image and per-PRB copy -- the same bytes when the build is right; a wrong image shows in the
@@ -3052,8 +3084,13 @@ int group_run_twin(rs_group* g, const GroupCall& c, const RsLaunch& L) {
   Lb.grp_out = g->d_out2;
   Lb.log_upper = c.want_upper ? (int32_t*)g->d_out2 : nullptr;
   Lb.done_flag = nullptr;
+  if (f.sets & kSetSent) { /* (the sent rows are outputs too: the built-in kernel's go to the twin block, whatever the caller asked for) */
+    if (!group_alloc_sent_twin(g)) return fail(RS_ERR_HIP, "allocation of the self-check's twin sent block failed (%zu bytes)", 8 * (size_t)b->U * g->n_cells);
+    Lb.grp_sent = g->z_sent2 ? g->z_sent2 : g->d_sent2;
+  }
   HIP_TRY(f.launch(&Lb, b->threads, st));
   HIP_TRY(hipMemcpyAsync(g->h_out2.data(), g->d_out2, (size_t)c.n * g->out_stride, hipMemcpyDeviceToHost, st));
+  if ((f.sets & kSetSent) && !g->z_sent2) HIP_TRY(hipMemcpyAsync(g->h_sent2, g->d_sent2, 8 * (size_t)c.n * b->U, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(after, b->d_sstate, ss_all, hipMemcpyDeviceToDevice, st));
   HIP_TRY(hipMemcpyAsync(b->d_sstate, before, ss_all, hipMemcpyDeviceToDevice, st));
   HIP_TRY(hipMemcpyAsync(b->d_scal, before + group_chk_sstate(g), sc_all, hipMemcpyDeviceToDevice, st));
@@ -3080,9 +3117,11 @@ int group_run(rs_group* g, GroupCall& c, RsLaunch& L) {
     L.done_flag = (uint32_t*)(g->z_out + g->flag_off);
     L.done_seq = g->seq;
   }
-  if (f.pair >= 0) {
+  {
     const rs_group::GroupPair& p = g->pair[f.pair];
-    const bool lean = p.jit[1] && !c.has_prb && !L.queue_mode && !c.has_gate && !L.exact_scan && !L.gen_exp && !c.want_upper && !L.synthetic;
+    /* (a flows call always carries the data_to_transmit gate: its lean build keeps it) */
+    const bool gate_free = c.form == kGroupFlows || !c.has_gate;
+    const bool lean = p.jit[1] && !c.has_prb && !L.queue_mode && gate_free && !L.exact_scan && !L.gen_exp && !c.want_upper && !L.synthetic;
     c.which = lean ? 1 : 0;
     c.kd = p.jit[c.which];
     c.checked = c.kd != nullptr && p.chk_left[c.which] > 0;
@@ -3114,12 +3153,12 @@ int group_wait(rs_group* g, const GroupCall& c) {
 }
 
 /* the form's stores of the named cells, as the run-time build left them against what the built-in kernel left (the second half of the
- * check block): per cell the averages, then the pending bytes, then the last-update time */
+ * check block): per cell the averages, then the pending bytes, then the last-update time, then the two counters of a form that keeps them */
 int group_compare_stores(const rs_group* g, const GroupCall& c, char* what, size_t len) {
   const GroupForm& f = c.desc();
   const GroupStores s = group_stores(g, f);
   if (!s.n) return RS_OK;
-  std::vector<uint8_t> jit[3], ref[3];
+  std::vector<uint8_t> jit[5], ref[5];
   const uint8_t* kept = g->pair[f.pair].d_stores_chk + s.half;
   for (int i = 0; i < s.n; kept += s.part[i++].kept(g)) {
     const size_t bytes = s.part[i].bytes(g);
@@ -3130,7 +3169,8 @@ int group_compare_stores(const rs_group* g, const GroupCall& c, char* what, size
   }
   for (int k = 0; k < c.n && !what[0]; k++) {
     const int cell = c.cell(k);
-    for (const int i : {0, 2, 1}) {
+    for (const int i : {0, 2, 1, 3, 4}) {
+      if (i >= s.n) continue;
       const GroupStore& x = s.part[i];
       for (size_t j = 0; j < x.elems && !what[0]; j++) {
         const size_t at = ((size_t)cell * x.elems + j) * x.size();
@@ -3139,7 +3179,8 @@ int group_compare_stores(const rs_group* g, const GroupCall& c, char* what, size
         char idx[48] = ""; /* (the element's index behind the store's name: "avg[3]", "avg[3][1]", "last_update") */
         if (x.elems > 1 && f.store_width == 2) snprintf(idx, sizeof idx, "[%zu][%zu]", j / 2, j % 2);
         else if (x.elems > 1) snprintf(idx, sizeof idx, "[%zu]", j);
-        if (x.f64) snprintf(what, len, "cell %d: %s%s = %a, the built-in kernel's %a", cell, x.name, idx, *(const double*)a, *(const double*)r);
+        if (x.kind == kStoreF64) snprintf(what, len, "cell %d: %s%s = %a, the built-in kernel's %a", cell, x.name, idx, *(const double*)a, *(const double*)r);
+        else if (x.kind == kStoreI64) snprintf(what, len, "cell %d: %s%s = %lld, the built-in kernel's %lld", cell, x.name, idx, (long long)*(const int64_t*)a, (long long)*(const int64_t*)r);
         else snprintf(what, len, "cell %d: %s%s = %d, the built-in kernel's %d", cell, x.name, idx, *(const int32_t*)a, *(const int32_t*)r);
       }
     }
@@ -3162,6 +3203,7 @@ int group_drop_pair(rs_group* g, const GroupCall& c, const char* what) {
   p.dropped = true;
   g->last_call_jit = false;
   memcpy(g->h_out, g->h_out2.data(), (size_t)c.n * g->out_stride);
+  if (f.sets & kSetSent) memcpy(g->h_sent, g->h_sent2, 8 * (size_t)c.n * b->U); /* (the built-in kernel's sent rows: what group_unpack hands out) */
   HIP_TRY(hipMemcpy(b->d_sstate, g->d_chk + group_chk_half(g), 8 * (size_t)b->S * g->n_cells, hipMemcpyDeviceToDevice));
   if (f.store_width) {
     HIP_TRY(group_copy_stores(g, f, 1, false));
@@ -3191,6 +3233,12 @@ int group_check(rs_group* g, const GroupCall& c) {
     for (int i = 0; i < b->S && !what[0]; i++) {
       const double a = ss_jit[(size_t)cell * b->S + i], r = ss_ref[(size_t)cell * b->S + i];
       if (to_bits(a) != to_bits(r)) snprintf(what, sizeof what, "cell %d: slice state[%d] = %a, the built-in kernel's %a", cell, i, a, r);
+    }
+    /* (a counted call: the slot's sent rows, whether or not the caller wants them; an update-only slot has none) */
+    if ((c.desc().sets & kSetSent) && !g->empty_slot[k]) {
+      const int32_t *a = g->h_sent + (size_t)k * 2 * (size_t)b->U, *r = g->h_sent2 + (size_t)k * 2 * (size_t)b->U;
+      for (int j = 0; j < 2 * c.in[k].n_users && !what[0]; j++)
+        if (a[j] != r[j]) snprintf(what, sizeof what, "cell %d: sent[%d][%d] = %d, the built-in kernel's %d", cell, j / 2, j % 2, a[j], r[j]);
     }
   }
   if (!what[0]) {
@@ -3621,13 +3669,14 @@ const char* rs_group_kernel_name(rs_group* g) {
 }
 
 /* Shape specialisation of a group: rs_ctx_specialize for the group surface -- the one-TTI form compiled for the config's slices, RBGs,
- * PRBs per RBG, scheduler, workgroup size and user CAPACITY, one workgroup per call slot, in a general and a lean build.  Three pairs
+ * PRBs per RBG, scheduler, workgroup size and user CAPACITY, one workgroup per call slot, in a general and a lean build.  Five pairs
  * (rs_group::GroupPair), each an option of its own: rs_group_specialize (entry point rs_group_kernel_jit, serves rs_group_schedule_tti),
- * rs_group_specialize_resident (rs_group_resident_kernel_jit, serves rs_group_schedule_tti_at) and rs_group_specialize_queued
- * (rs_group_queued_kernel_jit, serves rs_group_schedule_tti_queued).  Between calls at any time: slice state, CQI images, per-PRB
- * stores, resident stores and bearer stores are not touched. */
+ * rs_group_specialize_resident (rs_group_resident_kernel_jit, serves rs_group_schedule_tti_at), rs_group_specialize_queued
+ * (rs_group_queued_kernel_jit, serves rs_group_schedule_tti_queued), rs_group_specialize_counted (rs_group_counted_kernel_jit, serves
+ * rs_group_schedule_tti_counted) and rs_group_specialize_flows (rs_group_flows_kernel_jit, serves rs_group_schedule_tti_flows).  Between
+ * calls at any time: slice state, CQI images, per-PRB stores, resident stores, bearer stores and counters are not touched. */
 namespace {
-/* kind: kGroupPlain, kGroupResident or kGroupQueued -- the call the pair serves */
+/* kind: a row of kGroupForms -- the call the pair serves */
 int group_specialize_pair(rs_group* g, int kind) {
   rs_batch* b = g->b;
   const GroupForm& f = kGroupForms[kind];
@@ -3636,6 +3685,10 @@ int group_specialize_pair(rs_group* g, int kind) {
   if (p.dropped) return fail(RS_ERR_STATE, "%s", p.msg);
   if (kind == kGroupQueued && b->sched != RS_SCHED_NVS && b->sched != RS_SCHED_SEQUENTIAL && b->sched != RS_SCHED_MAXCELL && b->sched != RS_SCHED_SUBOPT && b->sched != RS_SCHED_VOGEL)
     return fail(RS_ERR_INVALID, "scheduler %d has no queued form (rs_group_set_bearers): nothing for rs_group_specialize_queued to build", b->sched);
+  if (kind == kGroupCounted && b->sched != RS_SCHED_NVS && b->sched != RS_SCHED_SEQUENTIAL && b->sched != RS_SCHED_MAXCELL && b->sched != RS_SCHED_SUBOPT && b->sched != RS_SCHED_VOGEL)
+    return fail(RS_ERR_INVALID, "scheduler %d has no counted form (rs_group_set_counters): nothing for rs_group_specialize_counted to build", b->sched);
+  if (kind == kGroupFlows && b->sched != RS_SCHED_PF)
+    return fail(RS_ERR_INVALID, "scheduler %d has no flows form (rs_group_set_flows): nothing for rs_group_specialize_flows to build", b->sched);
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   p.wanted = true;
   if (!g->d_out2) {
@@ -3720,6 +3773,26 @@ int rs_group_specialize_queued(rs_group* g) {
 int rs_group_queued_jit_status(rs_group* g, char* msg, size_t msglen) {
   if (!g) return fail(RS_ERR_INVALID, "null group");
   return group_jit_pair_status(g, kGroupQueued, msg, msglen);
+}
+
+int rs_group_specialize_counted(rs_group* g) {
+  if (!g) return fail(RS_ERR_INVALID, "null group");
+  return group_specialize_pair(g, kGroupCounted);
+}
+
+int rs_group_counted_jit_status(rs_group* g, char* msg, size_t msglen) {
+  if (!g) return fail(RS_ERR_INVALID, "null group");
+  return group_jit_pair_status(g, kGroupCounted, msg, msglen);
+}
+
+int rs_group_specialize_flows(rs_group* g) {
+  if (!g) return fail(RS_ERR_INVALID, "null group");
+  return group_specialize_pair(g, kGroupFlows);
+}
+
+int rs_group_flows_jit_status(rs_group* g, char* msg, size_t msglen) {
+  if (!g) return fail(RS_ERR_INVALID, "null group");
+  return group_jit_pair_status(g, kGroupFlows, msg, msglen);
 }
 
 /* ---- the reference's CQI trace files (include/radiosaber_hip.h) ---- */

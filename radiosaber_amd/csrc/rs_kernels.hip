@@ -807,7 +807,8 @@ __global__ void __launch_bounds__(512, 4) rs_group_queued_kernel(RsLaunch p) {
 
 /* ... and the queued form's counted twin (rs_group_schedule_tti_counted): the cell's bearers also keep m_cumulateBytes / m_cumulateRBs
  * on the device, and the slot gets back the bytes sent per call position and bearer.  Kernels of their own, the queued form's nine
- * shapes (rs_launch_group_counted): the queued kernels above carry none of it.  Built in only: no run-time build of this form. */
+ * shapes (rs_launch_group_counted): the queued kernels above carry none of it.  A group's run-time builds of this form are
+ * rs_group_counted_kernel_jit below. */
 template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_counted_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
@@ -818,7 +819,8 @@ __global__ void __launch_bounds__(512, 4) rs_group_counted_kernel(RsLaunch p) {
 
 /* ... and scheduler 1's flow-resident form (rs_group_schedule_tti_flows): DL_PF_PacketScheduler's unit is the flow, so a call position
  * is one bearer of one user; the cell keeps both bearers' averages, pending bytes and counters on the device and the whole transport
- * block is credited to the flow.  One kernel (rs_launch_group_flows); built in only: no run-time build of this form. */
+ * block is credited to the flow.  One kernel (rs_launch_group_flows).  A group's run-time builds of this form are
+ * rs_group_flows_kernel_jit below. */
 template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_flows_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
@@ -845,15 +847,36 @@ __global__ void __launch_bounds__(512, 4) rs_group_flows_kernel(RsLaunch p) {
 #ifndef RS_JIT_GROUP_QUEUED
 #define RS_JIT_GROUP_QUEUED 0 /* 1, with RS_JIT_GROUP and never with RS_JIT_GROUP_RESIDENT: the group's build of the queued form (rs_group_specialize_queued) */
 #endif
+#ifndef RS_JIT_GROUP_COUNTED
+#define RS_JIT_GROUP_COUNTED 0 /* 1, with RS_JIT_GROUP and never with RS_JIT_GROUP_RESIDENT: the group's build of the counted form (rs_group_specialize_counted); implies the queued text */
+#endif
+#ifndef RS_JIT_GROUP_FLOWS
+#define RS_JIT_GROUP_FLOWS 0 /* 1, with RS_JIT_GROUP, scheduler 1 and none of the three above: the group's build of the flows form (rs_group_specialize_flows) */
+#endif
 #if RS_JIT_GROUP
-/* three entry points, one per option list: rs_group_kernel_jit, rs_group_resident_kernel_jit for the calls that keep the cells' PF
- * averages on the device (rs_group_schedule_tti_at), and rs_group_queued_kernel_jit for the calls that keep both bearers there
- * (rs_group_schedule_tti_queued).  Same text but for the name, kGrpRes and kGrpQue; each has a general and a lean form. */
+/* five entry points, one per option list: rs_group_kernel_jit, rs_group_resident_kernel_jit for the calls that keep the cells' PF
+ * averages on the device (rs_group_schedule_tti_at), rs_group_queued_kernel_jit for the calls that keep both bearers there
+ * (rs_group_schedule_tti_queued), rs_group_counted_kernel_jit for those that keep the bearers' counters too
+ * (rs_group_schedule_tti_counted: the queued text with kGrpCnt) and rs_group_flows_kernel_jit for scheduler 1's flows
+ * (rs_group_schedule_tti_flows).  Same text but for the name and kGrpRes, kGrpQue, kGrpCnt, kGrpFlow; each has a general and a lean form. */
 #if RS_JIT_GROUP_RESIDENT && RS_JIT_GROUP_QUEUED
 #error "RS_JIT_GROUP_RESIDENT and RS_JIT_GROUP_QUEUED exclude each other"
 #endif
+#if RS_JIT_GROUP_RESIDENT && RS_JIT_GROUP_COUNTED
+#error "RS_JIT_GROUP_RESIDENT and RS_JIT_GROUP_COUNTED exclude each other"
+#endif
+#if RS_JIT_GROUP_FLOWS && (RS_JIT_GROUP_RESIDENT || RS_JIT_GROUP_QUEUED || RS_JIT_GROUP_COUNTED)
+#error "RS_JIT_GROUP_FLOWS is never combined with RS_JIT_GROUP_RESIDENT, RS_JIT_GROUP_QUEUED or RS_JIT_GROUP_COUNTED"
+#endif
+#if RS_JIT_GROUP_FLOWS && RS_JIT_SCHED != 1
+#error "RS_JIT_GROUP_FLOWS: the flows form is scheduler 1's"
+#endif
 #if RS_JIT_GROUP_RESIDENT
 #define RS_GROUP_JIT_ENTRY rs_group_resident_kernel_jit
+#elif RS_JIT_GROUP_COUNTED
+#define RS_GROUP_JIT_ENTRY rs_group_counted_kernel_jit
+#elif RS_JIT_GROUP_FLOWS
+#define RS_GROUP_JIT_ENTRY rs_group_flows_kernel_jit
 #elif RS_JIT_GROUP_QUEUED
 #define RS_GROUP_JIT_ENTRY rs_group_queued_kernel_jit
 #else
@@ -863,11 +886,15 @@ extern "C" __global__ void __launch_bounds__(RS_JIT_NT, RS_JIT_WPE) RS_GROUP_JIT
 #if defined(RS_JIT_LEAN) && RS_JIT_LEAN
   /* The lean build of a group's kernel: the plain call, exactly as in the one-TTI lean kernel below -- per-RBG reports, no customised
    * slices, no gates, exponents in {0, 1}, every input an ordinary FP32 number, no UpperBound lists, no synthetic-experiment blocks
-   * (the call's uniform-presence rules make that a per-launch fact; rs_group_schedule_tti, rs_group_schedule_tti_at and rs_group_schedule_tti_queued pick the build per call).  image_mode stays
-   * the slot header's word: the cells of one launch mix modes 0 / 1 / 2. */
+   * (the call's uniform-presence rules make that a per-launch fact; the group calls pick the build per call).  image_mode stays
+   * the slot header's word: the cells of one launch mix modes 0 / 1 / 2.  The flows call always carries the data_to_transmit gate: its
+   * lean build keeps p.gate as the launch block has it and makes every other option the constant. */
   p.cqi_mode = RS_CQI_EPOCHS;
   p.prb_cqi = nullptr; p.queue_mode = 0; p.alpha = nullptr; p.beta = nullptr; p.hol = nullptr; p.prio = nullptr;
-  p.gate = nullptr; p.exact_scan = 0; p.gen_exp = 0; p.gen_num = nullptr; p.log_upper = nullptr; p.synthetic = 0;
+#if !RS_JIT_GROUP_FLOWS
+  p.gate = nullptr;
+#endif
+  p.exact_scan = 0; p.gen_exp = 0; p.gen_num = nullptr; p.log_upper = nullptr; p.synthetic = 0;
   p.trace = nullptr; p.trace_prb = nullptr; p.epochs_prb = nullptr; p.log_keys = nullptr;
   constexpr bool kGrpLean = true;
 #else
@@ -876,7 +903,8 @@ extern "C" __global__ void __launch_bounds__(RS_JIT_NT, RS_JIT_WPE) RS_GROUP_JIT
   constexpr RsCarve kCv = rs_carve(RS_JIT_S, RS_JIT_U, RS_JIT_R, RS_JIT_SCHED, RS_JIT_NT, RS_JIT_CARVEQ, RS_JIT_WIN);
   __shared__ __align__(16) unsigned char lds[kCv.lds_bytes];
   constexpr int kGrpSched = RS_JIT_SCHED, kGrpEpt = (RS_JIT_SCHED != 9 && RS_JIT_SCHED != 10) ? 0 : (kCv.ept <= 4 ? kCv.ept : 0);
-  constexpr bool kGrpFixed = true, kGrpRes = RS_JIT_GROUP_RESIDENT != 0, kGrpQue = RS_JIT_GROUP_QUEUED != 0, kGrpCnt = false, kGrpFlow = false;
+  constexpr bool kGrpFixed = true, kGrpRes = RS_JIT_GROUP_RESIDENT != 0, kGrpQue = RS_JIT_GROUP_QUEUED != 0 || RS_JIT_GROUP_COUNTED != 0,
+                 kGrpCnt = RS_JIT_GROUP_COUNTED != 0, kGrpFlow = RS_JIT_GROUP_FLOWS != 0;
 #include "rs_phase_group.inc"
 }
 #undef RS_GROUP_JIT_ENTRY

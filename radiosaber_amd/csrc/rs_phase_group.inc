@@ -9,7 +9,8 @@
  * The entry points of rs_kernels.hip include this text as their body, as rs_cell_body includes its phases: the kernels built into the
  * library (rs_group_kernel, rs_group_resident_kernel, rs_group_queued_kernel, rs_group_counted_kernel, rs_group_flows_kernel: shape in the launch block) and a group's own run-time
  * builds (rs_group_kernel_jit, rs_group_specialize; rs_group_resident_kernel_jit, rs_group_specialize_resident;
- * rs_group_queued_kernel_jit, rs_group_specialize_queued).
+ * rs_group_queued_kernel_jit, rs_group_specialize_queued; rs_group_counted_kernel_jit, rs_group_specialize_counted;
+ * rs_group_flows_kernel_jit, rs_group_specialize_flows).
  * The includer provides `p` (the launch block), `lds` and four constants: kGrpSched, kGrpEpt, kGrpFixed -- shape, workgroup size and LDS
  * carve are the constants RS_JIT_*, RS_JIT_U being the user CAPACITY while the users of a slot stay the slot header's word -- and
  * kGrpLean -- the plain call's per-launch options are constants too.  (Text, not a function of its own: the built-in instantiations
@@ -33,25 +34,28 @@
  * shape is constant as the resident text's: the update's range and the strides of the [U][2] stores are 2 * RS_JIT_U, the loop strides
  * RS_JIT_NT, the grants' LDS offset the constexpr carve's off_tx.  Order of operations and arithmetic are the same in both forms.
  *
- * A seventh constant, kGrpCnt, makes the counted form (rs_group_schedule_tti_counted, rs_group_counted_kernel; only with kGrpQue, built
- * in only): the cell also keeps m_cumulateBytes / m_cumulateRBs of both bearers of every user, and the slot gets back the bytes sent
+ * A seventh constant, kGrpCnt, makes the counted form (rs_group_schedule_tti_counted, rs_group_counted_kernel; only with kGrpQue):
+ * the cell also keeps m_cumulateBytes / m_cumulateRBs of both bearers of every user, and the slot gets back the bytes sent
  * per call position and bearer.  All of it sits in step 4's per-position loop: the thread that credits a bearer adds the bytes and the
  * position's allocated PRBs to the bearer's 64-bit counters and writes the position's row of the slot's sent block.  The PRB count is
  * G times the RBGs the position holds -- the body's link adaptation leaves, per call position, the set of RBG lanes that share it in
  * RsMisc::maskA / maskB (rs_phase_p5.inc), and the closing barrier hands them to every thread as it hands over the grants.  With kGrpCnt
- * false none of this text reaches the other instantiations.
+ * false none of this text reaches the other instantiations.  Under kGrpFixed (rs_group_counted_kernel_jit) the counted part of step 4
+ * takes its shape as the queued part does: the RsMisc block lies at the constexpr carve's off_misc, the PRBs per RBG are RS_JIT_G.
  *
  * An eighth constant, kGrpFlow, makes the flow-resident form of scheduler 1 (rs_group_schedule_tti_flows, rs_group_flows_kernel; never
- * with kGrpRes / kGrpQue, built in only): DL_PF_PacketScheduler races FLOWS -- bearers --, not users, so a call position is one bearer
+ * with kGrpRes / kGrpQue): DL_PF_PacketScheduler races FLOWS -- bearers --, not users, so a call position is one bearer
  * of one user (RRC-container order: a user may hold two adjacent positions).  The cell keeps the queued form's bearer stores and the
  * counted form's counters; the update is the queued form's step 1, the call's average of a position is the flow's own (scheduler 1
  * divides by it as it is: no sum, no 1 +), and behind the body the WHOLE transport block goes to the flow -- pending bytes, bytes
  * counter, PRB counter --, no min with the data (ref: dl-pf-packet-scheduler.cpp:80-85).  The slot's bearer words (0 or 1 per call
  * position) travel where the queued form's data words do (grp_qin), the gate is the plain PF call's (data_to_transmit, packed by the
- * host).  With kGrpFlow false none of this text reaches the other instantiations. */
-  static_assert(!kGrpCnt || (kGrpQue && !kGrpFixed), "the counted form is the queued form's, and built in only");
-  static_assert(!kGrpFlow || (!kGrpRes && !kGrpQue && !kGrpCnt && !kGrpFixed && kGrpSched == 1),
-                "the flows form is scheduler 1's, a resident form of its own, and built in only");
+ * host).  With kGrpFlow false none of this text reaches the other instantiations.  Under kGrpFixed
+ * (rs_group_flows_kernel_jit) the flows text's shape is constant as the queued text's: the update's range and the strides of the [U][2]
+ * stores are 2 * RS_JIT_U, the loop strides RS_JIT_NT, the LDS offsets the constexpr carve's off_tx and off_misc, the PRBs per RBG
+ * RS_JIT_G.  Order of operations and arithmetic are the same in both forms. */
+  static_assert(!kGrpCnt || kGrpQue, "the counted form is the queued form's");
+  static_assert(!kGrpFlow || (!kGrpRes && !kGrpQue && !kGrpCnt && kGrpSched == 1), "the flows form is scheduler 1's, a resident form of its own");
   const uint8_t* const in = p.grp_in + (size_t)blockIdx.x * (size_t)p.grp_in_stride;
   uint8_t* const out = p.grp_out + (size_t)blockIdx.x * (size_t)p.grp_out_stride;
   const RsGroupCell* const h = (const RsGroupCell*)in;
@@ -214,8 +218,9 @@
     }
   }
   if constexpr (kGrpFlow) {
-    const int nthreads = (int)blockDim.x;
-    const int n_all = p.U; /* the config's users: 2 n_all bearers, the stores' stride and the update's range */
+    /* (shape and carve: the launch block's in the built-in kernel, the constants RS_JIT_* in a group's run-time build) */
+    const int nthreads = kGrpFixed ? RS_JIT_NT : (int)blockDim.x;
+    const int n_all = kGrpFixed ? RS_JIT_U : p.U; /* the config's users: 2 n_all bearers, the stores' stride and the update's range */
     double* const b_avg = p.grp_qavg + (size_t)cell * 2 * (size_t)n_all;
     int32_t* const b_pend = p.grp_qpend + (size_t)cell * 2 * (size_t)n_all;
     const uint8_t* const b_has = p.grp_qhas + (size_t)cell * 2 * (size_t)n_all;
@@ -283,7 +288,7 @@
       int64_t* const c_bytes = kGrpCnt ? p.grp_cbytes + (size_t)cell * 2 * (size_t)n_all : nullptr;
       int64_t* const c_rbs = kGrpCnt ? p.grp_crbs + (size_t)cell * 2 * (size_t)n_all : nullptr;
       int32_t* const srow = kGrpCnt ? p.grp_sent + (size_t)blockIdx.x * (size_t)p.grp_sent_stride : nullptr;
-      const RsMisc* const cm = (const RsMisc*)(lds + p.off_misc);
+      const RsMisc* const cm = (const RsMisc*)(lds + (kGrpFixed ? kGrpCv.off_misc : p.off_misc));
       for (int i = threadIdx.x; i < q.U; i += nthreads) {
         int available = granted[i];
         if (available <= 0) {
@@ -296,7 +301,7 @@
         if constexpr (kGrpCnt) {
           /* GetListOfAllocatedRBs()->size(): owner + 1 = i + 1 in two base-64 digits, the lanes that share both hold the position's RBGs */
           const unsigned long long lanes = cm->maskA[(i + 1) & 63] & cm->maskB[(i + 1) >> 6];
-          nprb = (int64_t)(__popcll(lanes) * p.G);
+          nprb = (int64_t)(__popcll(lanes) * (kGrpFixed ? RS_JIT_G : p.G));
         }
         for (int b = 1; b >= 0; --b) {
           if (available <= 0) break;
@@ -314,8 +319,21 @@
 #endif
             if constexpr (kGrpCnt) { /* a user is named once per call, a cell once per launch: plain 64-bit adds by the position's thread */
               c_bytes[2 * id + b] += (int64_t)sent;
+#if defined(RS_FAULT_INJECT_COUNTED) && RS_FAULT_INJECT_COUNTED == 1
+              /* tests only (tests/test_gpu_group_counted_specialize.py): a deliberately wrong run-time build of the COUNTED form -- the
+               * last bearer credited for a position gets a PRB more; outputs, sent rows and bearer stores stay right, so only the
+               * self-check's comparison of the counters can catch it.  A value, no address or index; the twin of RS_FAULT_INJECT_QUEUED. */
+              c_rbs[2 * id + b] += nprb + ((kGrpFixed && (available <= 0 || b == 0 || keep[2 * i] <= 0)) ? 1 : 0);
+#else
               c_rbs[2 * id + b] += nprb;
+#endif
+#if defined(RS_FAULT_INJECT_COUNTED) && RS_FAULT_INJECT_COUNTED == 2
+              /* tests only: ... the position's sent row gets a byte more for that bearer; pending bytes and counters stay right, so only
+               * the self-check's comparison of the sent rows can catch it */
+              row_sent[b] = sent + ((kGrpFixed && (available <= 0 || b == 0 || keep[2 * i] <= 0)) ? 1 : 0);
+#else
               row_sent[b] = sent;
+#endif
             }
           }
         }
@@ -329,22 +347,30 @@
      *    update and m_cumulateBytes, UpdateCumulateRBs the PRBs of the flow's block.  The PRB count: the counted form's lane masks.
      *    A flow is named once per call, a cell once per launch: plain adds by the position's thread. */
     if (q.U != 0) {
-      const int nthreads = (int)blockDim.x;
-      const int n_all = p.U;
-      const int32_t* const granted = (const int32_t*)(lds + p.off_tx);
+      const int nthreads = kGrpFixed ? RS_JIT_NT : (int)blockDim.x;
+      const int n_all = kGrpFixed ? RS_JIT_U : p.U;
+      constexpr RsCarve kGrpCv = rs_carve(RS_JIT_S, RS_JIT_U, RS_JIT_R, RS_JIT_SCHED, RS_JIT_NT, RS_JIT_CARVEQ, RS_JIT_WIN); /* (the body's own carve) */
+      const int32_t* const granted = (const int32_t*)(lds + (kGrpFixed ? kGrpCv.off_tx : p.off_tx));
       int32_t* const b_pend = p.grp_qpend + (size_t)cell * 2 * (size_t)n_all;
       int64_t* const c_bytes = p.grp_cbytes + (size_t)cell * 2 * (size_t)n_all;
       int64_t* const c_rbs = p.grp_crbs + (size_t)cell * 2 * (size_t)n_all;
       const int32_t* const ids = p.grp_uid + (size_t)cell * (size_t)n_all; /* entry i: written by this thread before the body */
-      const RsMisc* const cm = (const RsMisc*)(lds + p.off_misc);
+      const RsMisc* const cm = (const RsMisc*)(lds + (kGrpFixed ? kGrpCv.off_misc : p.off_misc));
       for (int i = threadIdx.x; i < q.U; i += nthreads) {
         const int bytes = granted[i];
         if (bytes <= 0) continue;
         const int f = ids[i];
         const unsigned long long lanes = cm->maskA[(i + 1) & 63] & cm->maskB[(i + 1) >> 6];
         b_pend[f] += bytes;
+#if defined(RS_FAULT_INJECT_FLOWS)
+        /* tests only (tests/test_gpu_group_flows_specialize.py): a deliberately wrong run-time build of the FLOWS form -- every credited
+         * flow's byte counter gets one more; outputs, averages and pending bytes stay right, so only the self-check's comparison of the
+         * counters can catch it.  A value, no address or index; the twin of RS_FAULT_INJECT_QUEUED. */
+        c_bytes[f] += (int64_t)bytes + (kGrpFixed ? 1 : 0);
+#else
         c_bytes[f] += (int64_t)bytes;
-        c_rbs[f] += (int64_t)(__popcll(lanes) * p.G);
+#endif
+        c_rbs[f] += (int64_t)(__popcll(lanes) * (kGrpFixed ? RS_JIT_G : p.G));
       }
     }
   }

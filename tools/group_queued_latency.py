@@ -3,7 +3,7 @@
 call followed by rs_group_set_pending per cell -- and, as the regression check, the plain and the resident call, which another
 checkout can be measured on as well (profiles/group_queued.md).
 
-    python tools/group_queued_latency.py [--variant plain|resident|resident+pending|queued|queued-spec|queued+host|counted|all|flows|plain-pf+host] [--calls 300]
+    python tools/group_queued_latency.py [--variant plain|resident|resident+pending|queued|queued-spec|queued+host|counted|counted-spec|all|flows|flows-spec|plain-pf+host] [--calls 300]
     RS_TREE=<another checkout> python tools/group_queued_latency.py --variant plain     # that tree's package
     python tools/group_queued_latency.py --variant queued-spec --cells 27 --shapes 500x25x4 500x64x8 --sched 9 7
 
@@ -11,7 +11,9 @@ queued-spec: the queued call after rs_group_specialize_queued (profiles/group_qu
 checked calls.  queued+host: the queued call followed by what a binding did on the CPU before rs_group_schedule_tti_counted --
 DoStopSchedule's credit loop restated in numpy from user_tbs_bits and the data words, and the per-bearer byte and RB counters kept in
 host arrays; counted: the counted call, which returns the bytes sent and keeps the counters on the device
-(profiles/group_counted.md).  Workloads by default: 8 and 64 cells; 500 users x 25 RBGs and 100 users x 64 RBGs; scheduler 9; cqi_epoch on (new
+(profiles/group_counted.md).  counted-spec / flows-spec: the counted call after rs_group_specialize_counted and the flows call after
+rs_group_specialize_flows (profiles/group_counted_flows_specialize.md); their warm-up holds the builds' checked calls, as queued-spec's
+does.  Workloads by default: 8 and 64 cells; 500 users x 25 RBGs and 100 users x 64 RBGs; scheduler 9; cqi_epoch on (new
 reports every 40 calls).  --shapes takes users x RBGs x PRBs per RBG (20 equal slices).  Scheduler 7 names the users of one slice per
 call, the slice rotating with the call, and gives no required_rbs.  Timed through the Python layer, marshalling included, like
 tools/group_resident_latency.py: three repetitions per line, whose spread is the yardstick for a difference between lines; p50 / p99
@@ -34,8 +36,8 @@ import numpy as np
 sys.path.insert(0, os.environ.get("RS_TREE", str(Path(__file__).resolve().parents[1])))
 import radiosaber_amd as rs  # noqa: E402
 
-VARIANTS = ("plain", "resident", "resident+pending", "queued", "queued-spec", "queued+host", "counted")
-FLOW_VARIANTS = ("flows", "plain-pf+host")
+VARIANTS = ("plain", "resident", "resident+pending", "queued", "queued-spec", "queued+host", "counted", "counted-spec")
+FLOW_VARIANTS = ("flows", "flows-spec", "plain-pf+host")
 
 
 def host_ewma(avg, pend, has, now, last):
@@ -64,7 +66,9 @@ def run_flows(variant, U, R, G, K, calls_n, warmup):
     pend = [np.zeros((cap, 2), np.int32) for _ in range(K)]
     host_bytes = [np.zeros((cap, 2), np.int64) for _ in range(K)]
     host_rbs = [np.zeros((cap, 2), np.int64) for _ in range(K)]
-    if variant == "flows":
+    if variant == "flows-spec":
+        g.specialize_flows()
+    if variant in ("flows", "flows-spec"):
         for k in range(K):
             g.set_flows(k, has, avg[k], 0.1)
     now, best, each = 0.1, [], []
@@ -76,7 +80,7 @@ def run_flows(variant, U, R, G, K, calls_n, warmup):
             last, now = now, now + 0.001
             calls = [dict(cqi=cqi[k], user_id=uid, data_to_transmit=data, cqi_epoch=1 + i // 40) for k in range(K)]
             t1 = time.perf_counter()
-            if variant == "flows":
+            if variant in ("flows", "flows-spec"):
                 for k in range(K):
                     calls[k]["flow_bearer"] = fb
                 g.schedule_tti_flows(calls, now)
@@ -137,9 +141,13 @@ for sched, shape in ((s, x) for s in args.sched for x in args.shapes):
                 continue  # (RS_TREE names a checkout from before rs_group_specialize_queued)
             if variant == "counted" and not hasattr(rs.GroupScheduler, "schedule_tti_counted"):
                 continue  # (... from before rs_group_schedule_tti_counted)
+            if variant == "counted-spec" and not hasattr(rs.GroupScheduler, "specialize_counted"):
+                continue  # (... from before rs_group_specialize_counted)
             g = rs.GroupScheduler(sc, R, G, K, sched=sched)
             if variant == "queued-spec":
                 g.specialize_queued()
+            if variant == "counted-spec":
+                g.specialize_counted()
             rng = np.random.default_rng(1)
             cqi = [rng.integers(1, 16, (U, R)).astype(np.uint8) for _ in range(K)]
             avg = [rng.uniform(1e4, 1e6, U) for _ in range(K)]
@@ -148,9 +156,9 @@ for sched, shape in ((s, x) for s in args.sched for x in args.shapes):
             for k in range(K):
                 if variant in ("resident", "resident+pending"):
                     g.set_avg(k, avg[k], 0.1)
-                if variant in ("queued", "queued-spec", "queued+host", "counted"):
+                if variant in ("queued", "queued-spec", "queued+host", "counted", "counted-spec"):
                     g.set_bearers(k, np.ones((U, 2), bool), np.stack([avg[k], avg[k][::-1]], axis=1), 0.1)
-                if variant == "counted":
+                if variant in ("counted", "counted-spec"):
                     g.set_counters(k)
             host_bytes = [np.zeros((U, 2), np.int64) for _ in range(K)]
             host_rbs = [np.zeros((U, 2), np.int64) for _ in range(K)]
@@ -172,10 +180,10 @@ for sched, shape in ((s, x) for s in args.sched for x in args.shapes):
                         for k in range(K):
                             calls[k]["avg_rate"] = avg[k]
                         g.schedule_tti(calls)
-                    elif variant in ("queued", "queued-spec", "queued+host", "counted"):
+                    elif variant in ("queued", "queued-spec", "queued+host", "counted", "counted-spec"):
                         for k in range(K):
                             calls[k]["data_to_transmit"] = data if ids is None else data[ids]
-                        if variant == "counted":
+                        if variant in ("counted", "counted-spec"):
                             g.schedule_tti_counted(calls, now)
                         else:
                             res = g.schedule_tti_queued(calls, now)
