@@ -36,7 +36,8 @@ extern "C" {
                                rs_group_specialize_counted / rs_group_counted_jit_status / rs_jit_selfcheck_group_counted and rs_group_specialize_flows / rs_group_flows_jit_status / rs_jit_selfcheck_group_flows
                                (a group's own builds of the counted and of the flows kernel, self-checked on bearer stores, counters and sent rows),
                                rs_group_set_counters / rs_group_get_counters / rs_group_schedule_tti_counted (a bearer-resident group cell's m_cumulateBytes / m_cumulateRBs on the device, the bytes sent per bearer returned per call),
-                               rs_group_set_flows / rs_group_get_flows / rs_group_schedule_tti_flows (scheduler 1's flows of a group cell resident on the device: averages, pending bytes and counters per bearer, the whole block credited to the flow);
+                               rs_group_set_flows / rs_group_get_flows / rs_group_schedule_tti_flows (scheduler 1's flows of a group cell resident on the device: averages, pending bytes and counters per bearer, the whole block credited to the flow),
+                               rs_group_run_at + RS_GROUP_MAX_RUN (T consecutive TTIs of average-resident group cells in one launch);
                                rs_config.link_tables (RS_LINK_*) + rs_link_tables_pinned / rs_link_tables_compare, rs_tti_in.cqi_epoch (the context keeps the
                                CQI image of an unchanged report set on the device), rs_ctx_jit_status (a specialised context checks its run-time build against the
                                built-in kernel during its first calls), rs_batch_config.selfcheck -1 / 0 / 1 with run-time builds verified by default and the
@@ -410,6 +411,40 @@ int rs_group_resident_jit_status(rs_group* g, char* msg, size_t msglen);
 /* build check without a GPU: do the general and the lean resident build of a group of this shape compile?  (the larger code size, or a
  * negative value with the compiler's log in err; RS_SCHED_NVS_NONGREEDY has no group builds) */
 int rs_jit_selfcheck_group_resident(int n_slices, int n_users, int n_rbgs, int rbg_size, int threads, int sched, char* err, size_t errlen);
+
+/* A run of resident calls (ABI 11 addition, no layout changed): n_ttis consecutive TTIs of every named cell in ONE kernel launch, for the
+ * host whose cells are backlogged -- one InfiniteBuffer bearer per user -- and which between two CQI reports (CQI_INTERVAL = 40 TTIs)
+ * contributes nothing per TTI but the clock and the rand() pair.  The call is, to the bit, this loop:
+ *     for (t = 0; t < n_ttis; t++) rs_group_schedule_tti_at(g, n, cell_ids, in_t, out_t, now_t);
+ * with in_t[k] = in[k] but rand0 / rand1 = rands[k][t][0 .. 1] (in[k].rand0 / rand1 themselves are not read), now_t[k] = now[k][t] and
+ * out_t[k] = out[k][t].  in[k].cqi_epoch is used as given for every t: a non-zero number makes TTIs 1 .. n_ttis-1 image hits, 0 stays 0
+ * -- the block is read each TTI and the cell's image ends.  Everything observable afterwards is what the loop leaves: every field of
+ * every rs_tti_out (upper_* lists if asked), slice state, every user's average, pending bytes and last_update, named by the call or
+ * not, the cells' image records and the three counters of rs_group_image_stats, and the state of the cells that were not named.  Two
+ * things differ on purpose: rs_group_launch_count grows by 1, and rs_group_kernel_name returns "rs_group_run_kernel<sched, ept>" while
+ * a run was the last call served.  Per workgroup the device repeats steps 1 - 3 of rs_group_schedule_tti_at n_ttis times, in their
+ * order and arithmetic, a workgroup barrier behind a device-scope fence between two TTIs, and completes once behind the last.
+ * Rules, each RS_ERR_INVALID unless stated, each checked before anything is launched (a rejected call launches nothing and moves nothing):
+ *   - every rule of rs_group_schedule_tti_at: cell_ids, uniform presence of cqi_prb and of the upper_* outputs (over every TTI of every
+ *     cell), avg_rate NULL, every named cell average-resident (RS_ERR_STATE, the message names the cell; a bearer- or flow-resident
+ *     cell too), exponents in {0, 1};
+ *   - 1 <= n_ttis <= RS_GROUP_MAX_RUN;
+ *   - the users of a cell (n_users, user_id) are the slot's, given once, the same for the whole run;
+ *   - hol_delay, prio_has_data, required_rbs and data_to_transmit are NULL: they change per TTI and belong to the host -- so a config
+ *     with a customised slice (algo_alpha != 0) is refused;
+ *   - RS_SCHED_NVS is refused (the host picks the served slice, and with it the user list, per TTI); the served schedulers are
+ *     RS_SCHED_PF, RS_SCHED_GREEDY, RS_SCHED_MAXCELL, RS_SCHED_UPPERBOUND, RS_SCHED_SUBOPT and RS_SCHED_VOGEL;
+ *   - rands == NULL only for RS_SCHED_PF, which draws no rand();
+ *   - now[k][0] obeys the at-call's clock rule against the cell's last_update; each step now[k][t] - now[k][t-1] is 0 (the
+ *     reference's early return: nothing is updated) or at least 2^-20 s.
+ * RS_ERR_HIP -- a failed allocation of the larger output blocks included: they grow to slots x n_ttis of the largest run so far -- leaves
+ * the named cells not resident and ends their images, as the at-call does.  A run always executes the kernel built into the library,
+ * before and after any rs_group_specialize*; bearer-, counted- and flow-resident cells have no runs (their data_to_transmit is the
+ * host's per TTI). */
+#define RS_GROUP_MAX_RUN 64 /* a sanity bound (>= CQI_INTERVAL = 40), not a tuned number */
+int rs_group_run_at(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in /* [n] */, int32_t n_ttis,
+                    const double* now /* [n][n_ttis] */, const int32_t* rands /* [n][n_ttis][2]: rand0, rand1 of each TTI; NULL only for RS_SCHED_PF */,
+                    rs_tti_out* out /* [n][n_ttis] */);
 
 /* Resident bearers (ABI 11 addition, no layout changed): the second resident form of a group's cell.  The cell keeps, per user id of the
  * config and per bearer (MAX_BEARERS = 2, index = the bearer's priority), RadioBearer's average rate and the bytes DoStopSchedule

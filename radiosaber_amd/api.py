@@ -110,7 +110,7 @@ ABI_SYMBOLS = [
     "rs_group_create", "rs_group_create_checked", "rs_group_destroy", "rs_group_schedule_tti",
     "rs_group_get_slice_offset", "rs_group_set_slice_offset", "rs_group_launch_count", "rs_group_kernel_name",
     "rs_group_image_stats", "rs_group_specialize", "rs_group_jit_status", "rs_jit_selfcheck_group",
-    "rs_group_set_avg", "rs_group_get_avg", "rs_group_set_pending", "rs_group_schedule_tti_at",
+    "rs_group_set_avg", "rs_group_get_avg", "rs_group_set_pending", "rs_group_schedule_tti_at", "rs_group_run_at",
     "rs_group_specialize_resident", "rs_group_resident_jit_status", "rs_jit_selfcheck_group_resident",
     "rs_group_set_bearers", "rs_group_get_bearers", "rs_group_schedule_tti_queued",
     "rs_group_specialize_queued", "rs_group_queued_jit_status", "rs_jit_selfcheck_group_queued",
@@ -163,6 +163,8 @@ def lib():
     L.rs_group_get_avg.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double)]
     L.rs_group_set_pending.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
     L.rs_group_schedule_tti_at.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_TtiIn), C.POINTER(_TtiOut), C.POINTER(C.c_double)]
+    L.rs_group_run_at.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_TtiIn), C.c_int32, C.POINTER(C.c_double),
+                                  C.POINTER(C.c_int32), C.POINTER(_TtiOut)]
     L.rs_group_set_bearers.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.c_double]
     L.rs_group_get_bearers.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double)]
     L.rs_group_schedule_tti_queued.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_TtiIn), C.POINTER(_TtiOut),
@@ -838,6 +840,36 @@ class GroupScheduler:
         ids = None if cell_ids is None else np.ascontiguousarray(cell_ids, np.int32)
         assert ids is None or ids.shape == (n,)
         _check(lib().rs_group_schedule_tti_at(self._h, n, _p(ids, C.c_int32) if ids is not None else None, ins, outs, _p(t, C.c_double)))
+        return results
+
+    def run_at(self, calls: Sequence[dict], now, rands=None, cell_ids: Optional[Sequence[int]] = None) -> List[List[TtiResult]]:
+        """rs_group_run_at: T consecutive schedule_tti_at calls in one launch.  calls[k] as for schedule_tti_at, given once per cell
+        (rand0 / rand1 are not read); now is [T] (the same clock for every cell) or [n][T]; rands is [n][T][2], the rand() pair of each
+        cell's TTIs (None: RS_SCHED_PF only).  Returns results[k][t]."""
+        n = len(calls)
+        t = np.asarray(now, np.float64)
+        assert t.ndim in (1, 2) and (t.ndim == 1 or t.shape[0] == n)
+        T = t.shape[-1]
+        t = np.ascontiguousarray(np.broadcast_to(t, (n, T)))
+        r = None if rands is None else np.ascontiguousarray(rands, np.int32)
+        assert r is None or r.shape == (n, T, 2)
+        ins, outs, results, keep = (_TtiIn * n)(), (_TtiOut * (n * max(T, 1)))(), [], []
+        for k, kw in enumerate(calls):
+            kw = dict(kw)
+            cqi, avg = kw.pop("cqi", None), kw.pop("avg_rate", None)
+            row = []
+            for j in range(max(T, 1)):  # (one rs_tti_out per TTI; the rs_tti_in is the first one's)
+                tin, tout, res, arrays = _marshal_tti(self.slices.n_slices, self.R, self.rbg_size, self.sched, cqi, avg, **kw)
+                if j == 0:
+                    ins[k] = tin
+                outs[k * max(T, 1) + j] = tout
+                row.append(res)
+                keep.append(arrays)
+            results.append(row[:T])
+        ids = None if cell_ids is None else np.ascontiguousarray(cell_ids, np.int32)
+        assert ids is None or ids.shape == (n,)
+        _check(lib().rs_group_run_at(self._h, n, _p(ids, C.c_int32) if ids is not None else None, ins, T, _p(t, C.c_double),
+                                     _p(r, C.c_int32) if r is not None else None, outs))
         return results
 
     # ---- resident bearers: both bearers of every user stay on the device, finite queues are credited there ----

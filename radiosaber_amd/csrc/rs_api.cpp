@@ -2417,6 +2417,10 @@ struct rs_group {
    * output slot: the single call's output block.  The completion word lies behind the last output slot, on its own cache line. */
   uint8_t *h_in = nullptr, *d_in = nullptr, *h_out = nullptr, *d_out = nullptr, *z_in = nullptr, *z_out = nullptr;
   size_t in_stride = 0, out_stride = 0, flag_off = 0;
+  /* runs (rs_group_run_at): the slots' per-TTI tables -- [n_cells][RS_GROUP_MAX_RUN] rows of clock, rand0, rand1 -- lie behind the last
+   * input slot, at run_table_off of h_in / d_in; the output blocks hold out_slots slots (n_cells at first, grown to slots x TTIs of the
+   * largest run so far: group_grow_out), the completion word behind the last of them */
+  size_t run_table_off = 0, out_slots = 0;
   uint32_t* d_count = nullptr; /* the launch's completion counter (rs_group_kernel) */
   bool poll = false;
   uint32_t seq = 0;
@@ -2493,7 +2497,7 @@ struct rs_group {
   /* rs_group_kernel_name: the last call's form (a row of kGroupForms), whether a run-time build served it, the built-in kernels' names by row */
   int last_call_form = 0;
   bool last_call_jit = false;
-  char kname[5][56] = {"", "", "", "", ""};
+  char kname[6][56] = {"", "", "", "", "", ""};
 };
 
 extern "C" hipError_t rs_launch_group(const RsLaunch* p, int threads, hipStream_t stream);
@@ -2501,11 +2505,13 @@ extern "C" hipError_t rs_launch_group_resident(const RsLaunch* p, int threads, h
 extern "C" hipError_t rs_launch_group_queued(const RsLaunch* p, int threads, hipStream_t stream);
 extern "C" hipError_t rs_launch_group_counted(const RsLaunch* p, int threads, hipStream_t stream);
 extern "C" hipError_t rs_launch_group_flows(const RsLaunch* p, int threads, hipStream_t stream);
+extern "C" hipError_t rs_launch_group_run(const RsLaunch* p, int threads, hipStream_t stream);
 
 namespace {
 /* The forms of a group call, one row each: what differs between them outside the validation of their inputs.  A call's row is its
- * form, the counted twin of the queued form (rs_group_schedule_tti_counted) has the fifth. */
-enum { kGroupPlain = 0, kGroupResident = 1, kGroupQueued = 2, kGroupFlows = 3, kGroupCounted = 4 };
+ * form, the counted twin of the queued form (rs_group_schedule_tti_counted) has the fifth, a run of the resident form (rs_group_run_at) the
+ * sixth. */
+enum { kGroupPlain = 0, kGroupResident = 1, kGroupQueued = 2, kGroupFlows = 3, kGroupCounted = 4, kGroupRun = 5 };
 enum : unsigned { /* the RsLaunch pointer sets a form's kernel reads */
   kSetResident = 1, /* grp_avg, grp_pending, grp_last, grp_gather, grp_uid */
   kSetBearers = 2,  /* grp_qavg, grp_qpend, grp_qhas, grp_qdata and the slots' word block grp_qin (data words; a flows call: bearer words) */
@@ -2516,7 +2522,7 @@ struct GroupForm {
   hipError_t (*launch)(const RsLaunch*, int, hipStream_t); /* the built-in launcher */
   unsigned sets;
   bool slots0;     /* update-only slots (n_users == 0) are allowed */
-  int pair;        /* rs_group::pair[] that serves the form */
+  int pair;        /* rs_group::pair[] that serves the form; -1: none, the built-in kernel always serves it */
   int store_width; /* the stores its self-check saves, restores and compares: 0 none, 1 the resident stores [U], 2 the bearer stores [U][2]
                     * (a form with kSetCounters: the counter stores [U][2] too; with kSetSent: the slots' sent rows are compared as well) */
   int jit_flags;   /* rs_jit_get: 1 one-TTI form, 8 group wrapper, 16 resident, 32 queued, 64 counted, 128 flows */
@@ -2525,7 +2531,7 @@ struct GroupForm {
    * "copies of the <stores>" */
   const char *adj, *serves, *ref, *stores;
 };
-const GroupForm kGroupForms[5] = {
+const GroupForm kGroupForms[6] = {
     {rs_launch_group, 0, false, kGroupPlain, 0, 1 | 8, "rs_group_kernel_jit", "", "the built-in kernels serve this group", "the built-in kernel field by field", ""},
     {rs_launch_group_resident, kSetResident, false, kGroupResident, 1, 1 | 8 | 16, "rs_group_resident_kernel_jit", "resident ",
      "the built-in resident kernel serves this group's resident calls", "the built-in resident kernel field by field, resident stores included", "resident stores"},
@@ -2536,6 +2542,7 @@ const GroupForm kGroupForms[5] = {
     {rs_launch_group_counted, kSetResident | kSetBearers | kSetCounters | kSetSent, true, kGroupCounted, 2, 1 | 8 | 32 | 64, "rs_group_counted_kernel_jit", "counted ",
      "the built-in counted kernel serves this group's counted calls", "the built-in counted kernel field by field, bearer stores, counters and sent rows included",
      "bearer stores and counters"},
+    {rs_launch_group_run, kSetResident, false, -1, 0, 0, "", "", "", "", ""},
 };
 
 /* bytes of one half of rs_group::d_chk: [n_cells][S] slice state, then [n_cells] RsCellScalars */
@@ -2619,7 +2626,9 @@ rs_group* rs_group_create(const rs_config* cfg, int32_t n_cells) {
   g->in_stride = round_up((int)(RS_GROUP_HDR_BYTES + l.in_total), 256);
   g->out_stride = round_up((int)l.out_total, 256);
   g->flag_off = g->out_stride * (size_t)n_cells;
-  const size_t in_bytes = g->in_stride * (size_t)n_cells, out_bytes = g->flag_off + 64;
+  g->out_slots = (size_t)n_cells;
+  g->run_table_off = g->in_stride * (size_t)n_cells;
+  const size_t in_bytes = g->run_table_off + (size_t)RS_GROUP_MAX_RUN * RS_GROUP_RUN_ROW_BYTES * (size_t)n_cells, out_bytes = g->flag_off + 64;
   g->img_stride = round_up(rs_upad_of(b->U) * b->R, 16);
   g->prb_stride = round_up(b->U * b->R * b->G, 16);
   const bool ok = hipMalloc(&g->d_in, in_bytes) == hipSuccess && hipMalloc(&g->d_out, out_bytes) == hipSuccess &&
@@ -2656,6 +2665,7 @@ rs_group* rs_group_create(const rs_config* cfg, int32_t n_cells) {
   snprintf(g->kname[kGroupQueued], sizeof g->kname[0], "rs_group_queued_kernel<%d, %d>", b->sched, b->sched == RS_SCHED_MAXCELL && ept <= 4 ? ept : 0);
   snprintf(g->kname[kGroupCounted], sizeof g->kname[0], "rs_group_counted_kernel<%d, %d>", b->sched, b->sched == RS_SCHED_MAXCELL && ept <= 4 ? ept : 0);
   snprintf(g->kname[kGroupFlows], sizeof g->kname[0], "rs_group_flows_kernel<%d, 0>", b->sched);
+  snprintf(g->kname[kGroupRun], sizeof g->kname[0], "rs_group_run_kernel<%d, %d>", b->sched, sorts && ept <= 4 ? ept : 0);
   g->empty_slot.assign(n_cells, 0);
   g->resident.assign(n_cells, 0);
   g->counted.assign(n_cells, 0);
@@ -2716,7 +2726,7 @@ struct GroupCall {
   const int32_t* cell_ids;
   const rs_tti_in* in;
   rs_tti_out* out;
-  const double* now;            /* [n], the resident forms */
+  const double* now;            /* [n], the resident forms; a run: [n][n_ttis] */
   const int32_t* const* qdata;  /* [n][n_users][2], queued and counted */
   int32_t* const* sent;         /* [n][n_users][2] or null, counted */
   const uint8_t* const* flow;   /* [n][n_users], flows */
@@ -2731,9 +2741,18 @@ struct GroupCall {
   bool zc, poll, checked;
   RsJitKernel* kd;
   int which;
+  /* a run (rs_group_run_at; form is kGroupResident): n_ttis consecutive TTIs per slot, `in` given once per slot, `now` and `out` per
+   * (slot, TTI), the rand() pairs in rands ([n][n_ttis][2] or null) */
+  bool run;
+  int32_t n_ttis;
+  const int32_t* rands;
   int cell(int k) const { return cell_ids ? cell_ids[k] : k; }
   bool resident() const { return form != kGroupPlain; }
-  int row() const { return counted ? (int)kGroupCounted : form; }
+  int row() const { return run ? (int)kGroupRun : counted ? (int)kGroupCounted : form; }
+  int ttis() const { return run ? n_ttis : 1; }
+  size_t at(int k, int t = 0) const { return run ? (size_t)k * (size_t)n_ttis + (size_t)t : (size_t)k; } /* slot k's TTI t in `now` and `out` */
+  double now_first(int k) const { return now[at(k)]; }
+  double now_last(int k) const { return now[at(k, ttis() - 1)]; }
   const GroupForm& desc() const { return kGroupForms[row()]; }
 };
 
@@ -2766,6 +2785,16 @@ int rs_group_schedule_tti_flows(rs_group* g, int32_t n, const int32_t* cell_ids,
                                 const uint8_t* const* flow_bearer) {
   if (!g || !in || !out || !now || !flow_bearer) return fail(RS_ERR_INVALID, "null argument");
   return group_schedule(g, {n, cell_ids, in, out, now, nullptr, nullptr, flow_bearer, kGroupFlows, false});
+}
+
+int rs_group_run_at(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, int32_t n_ttis, const double* now, const int32_t* rands,
+                    rs_tti_out* out) {
+  if (!g || !in || !out || !now) return fail(RS_ERR_INVALID, "null argument");
+  GroupCall c = {n, cell_ids, in, out, now, nullptr, nullptr, nullptr, kGroupResident, false};
+  c.run = true;
+  c.n_ttis = n_ttis;
+  c.rands = rands;
+  return group_schedule(g, c);
 }
 
 namespace {
@@ -2818,6 +2847,24 @@ int group_validate(rs_group* g, GroupCall& c) {
     if (bad >= 0) return fail(RS_ERR_INVALID, "cell_ids[%d] = %d outside 0..%d", bad, cell_ids[bad], g->n_cells - 1);
     if (dup >= 0) return fail(RS_ERR_INVALID, "cell_ids[%d] = %d names a cell twice", dup, cell_ids[dup]);
   }
+  if (c.run) {
+    /* a run's own rules: what the host would change from TTI to TTI has no place in it */
+    if (c.n_ttis < 1 || c.n_ttis > RS_GROUP_MAX_RUN) return fail(RS_ERR_INVALID, "n_ttis %d outside 1..%d (RS_GROUP_MAX_RUN)", c.n_ttis, RS_GROUP_MAX_RUN);
+    if (b->sched == RS_SCHED_NVS)
+      return fail(RS_ERR_INVALID, "RS_SCHED_NVS is not served by a run: the host picks the served slice, and with it the user list, per TTI");
+    if (b->any_alpha)
+      return fail(RS_ERR_INVALID, "a config with a customised slice (algo_alpha != 0) is not served by a run: hol_delay and prio_has_data change per TTI and belong to the host");
+    if (!c.rands && b->sched != RS_SCHED_PF) return fail(RS_ERR_INVALID, "rands is NULL: only RS_SCHED_PF draws no rand() pair per TTI");
+    if (g->run_table_off + (size_t)RS_GROUP_MAX_RUN * RS_GROUP_RUN_ROW_BYTES * (size_t)g->n_cells > (size_t)INT32_MAX)
+      return fail(RS_ERR_INVALID, "the group's input block is too large for a run's 32-bit table offsets");
+    for (int k = 0; k < n; k++) {
+      const char* what = in[k].hol_delay ? "hol_delay" : in[k].prio_has_data ? "prio_has_data" : in[k].required_rbs ? "required_rbs"
+                       : in[k].data_to_transmit ? "data_to_transmit" : nullptr;
+      if (what) return fail(RS_ERR_INVALID, "cell slot %d: %s must be NULL in a run: it changes per TTI and belongs to the host", k, what);
+      for (int t = 0; t < c.n_ttis; t++)
+        if (!c.out[c.at(k, t)].rbg_to_user || !c.out[c.at(k, t)].user_tbs_bits) return fail(RS_ERR_INVALID, "cell slot %d, TTI %d: null output array", k, t);
+    }
+  }
   auto gate_of = [&](const rs_tti_in& t) { return b->sched == RS_SCHED_NVS ? t.required_rbs : (b->sched == RS_SCHED_PF ? t.data_to_transmit : nullptr); };
   auto upper_of = [&](const rs_tti_out& o) { return b->sched == RS_SCHED_UPPERBOUND && (o.upper_rbg || o.upper_user); };
   /* (a call's update-only slots, n_users == 0, give no inputs at all: the slots WITH users agree among themselves) */
@@ -2829,15 +2876,19 @@ int group_validate(rs_group* g, GroupCall& c) {
   c.has_hol = any_users && in[k0].hol_delay != nullptr;
   c.has_prio = any_users && in[k0].prio_has_data != nullptr;
   c.has_gate = any_users && gate_of(in[k0]) != nullptr;
-  c.want_upper = any_users && upper_of(c.out[k0]);
+  c.want_upper = any_users && upper_of(c.out[c.at(k0)]);
   for (int k = k0 + 1; k < n; k++) {
     if (slots0 && in[k].n_users == 0) continue;
     const char* what = (in[k].cqi_prb != nullptr) != c.has_prb ? "cqi_prb" : (in[k].hol_delay != nullptr) != c.has_hol ? "hol_delay"
                      : (in[k].prio_has_data != nullptr) != c.has_prio ? "prio_has_data"
                      : (gate_of(in[k]) != nullptr) != c.has_gate ? (b->sched == RS_SCHED_NVS ? "required_rbs" : "data_to_transmit")
-                     : upper_of(c.out[k]) != c.want_upper ? "upper_rbg / upper_user" : nullptr;
+                     : upper_of(c.out[c.at(k)]) != c.want_upper ? "upper_rbg / upper_user" : nullptr;
     if (what) return fail(RS_ERR_INVALID, "mixed call: cell slot %d and cell slot %d differ in whether they give %s (optional inputs are given by every cell of a call or by none)", k, k0, what);
   }
+  for (int k = 0; c.run && k < n; k++) /* (a run: every TTI's output, the slot's first included) */
+    for (int t = 0; t < c.n_ttis; t++)
+      if (upper_of(c.out[c.at(k, t)]) != c.want_upper)
+        return fail(RS_ERR_INVALID, "mixed call: cell slot %d, TTI %d and cell slot 0, TTI 0 differ in whether they give upper_rbg / upper_user (optional outputs are given by every TTI of every cell of a run or by none)", k, t);
   if (!c.resident()) return RS_OK;
   /* a resident call's cells: the form each is resident in, the slots' own inputs, the clock rules */
   const bool que = c.form == kGroupQueued, flw = c.form == kGroupFlows;
@@ -2858,10 +2909,18 @@ int group_validate(rs_group* g, GroupCall& c) {
     if (int rc = flw ? group_validate_flows_slot(g, c, k, cell) : RS_OK) return rc;
     if (que && in[k].n_users > 0 && !c.qdata[k]) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): data_to_transmit[%d] is NULL (only an update-only slot, n_users == 0, gives none)", k, cell, k);
     const double last = g->last_update[cell];
-    if (!std::isfinite(c.now[k])) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): now is not finite", k, cell);
-    if (c.now[k] < last) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): now = %.17g lies before the cell's last update at %.17g", k, cell, c.now[k], last);
-    if (c.now[k] != last && !(c.now[k] - last >= kResidentMinDt) && !g->pending_zero[cell])
-      return fail(RS_ERR_INVALID, "cell slot %d (cell %d): now - last_update = %.3g s is neither 0 nor at least %.3g s, and the cell may have bytes pending", k, cell, c.now[k] - last, kResidentMinDt);
+    const double now0 = c.now_first(k);
+    if (!std::isfinite(now0)) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): now is not finite", k, cell);
+    if (now0 < last) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): now = %.17g lies before the cell's last update at %.17g", k, cell, now0, last);
+    if (now0 != last && !(now0 - last >= kResidentMinDt) && !g->pending_zero[cell])
+      return fail(RS_ERR_INVALID, "cell slot %d (cell %d): now - last_update = %.3g s is neither 0 nor at least %.3g s, and the cell may have bytes pending", k, cell, now0 - last, kResidentMinDt);
+    /* (a run: behind its first TTI bytes may be pending whatever the cell's state was: every later step is 0 or at least the bound) */
+    for (int t = 1; t < c.ttis(); t++) {
+      const double a = c.now[c.at(k, t - 1)], z = c.now[c.at(k, t)];
+      if (!std::isfinite(z)) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): now of TTI %d is not finite", k, cell, t);
+      if (z != a && !(z - a >= kResidentMinDt))
+        return fail(RS_ERR_INVALID, "cell slot %d (cell %d): the clock step from TTI %d to TTI %d, %.3g s, is neither 0 nor at least %.3g s", k, cell, t - 1, t, z - a, kResidentMinDt);
+    }
   }
   return RS_OK;
 }
@@ -2882,15 +2941,26 @@ void group_fill_header(const rs_group* g, const GroupCall& c, int k, const CtxLa
     h.n_seg = b->base.n_seg;
     h.n_items = b->base.n_items;
     if (b->sched == RS_SCHED_PF) { h.n_seg = (nu + RS_PF_SEG - 1) / RS_PF_SEG; h.n_items = b->R * h.n_seg; }
-    h.rand0 = in.rand0;
-    h.rand1 = in.rand1;
+    h.rand0 = c.run ? 0 : in.rand0; /* (a run: the pairs travel in the slot's table) */
+    h.rand1 = c.run ? 0 : in.rand1;
     h.in_slice = (int32_t)l->slice; h.in_avg = (int32_t)l->avg; h.in_hol = (int32_t)l->hol; h.in_prio = (int32_t)l->prio;
     h.in_gate = (int32_t)l->gate; h.in_prb = (int32_t)l->prb;
     h.out_uinfo = (int32_t)l->uinfo; h.out_map = (int32_t)l->map; h.out_quota = (int32_t)l->quota; h.out_target = (int32_t)l->target;
     h.out_upper = (int32_t)l->upper;
     if (c.resident()) h.in_uid = in.user_id ? (int32_t)l->avg : 0; /* (l.avg lies behind the grid and the slice ids: never 0) */
   }
-  if (c.resident()) h.now = c.now[k];
+  if (c.resident()) h.now = c.now_first(k);
+  if (c.run) { /* the slot's table, one row per TTI: the clock, rand0, rand1 */
+    const size_t table = g->run_table_off + (size_t)k * RS_GROUP_MAX_RUN * RS_GROUP_RUN_ROW_BYTES;
+    h.run_ttis = c.n_ttis;
+    h.run_table = (int32_t)(table - (size_t)k * g->in_stride);
+    h.run_out_step = (int32_t)g->out_stride;
+    for (int t = 0; t < c.n_ttis; t++) {
+      const int32_t pair[2] = {c.rands ? c.rands[2 * c.at(k, t)] : 0, c.rands ? c.rands[2 * c.at(k, t) + 1] : 0};
+      memcpy(g->h_in + table + (size_t)t * RS_GROUP_RUN_ROW_BYTES, &c.now[c.at(k, t)], 8);
+      memcpy(g->h_in + table + (size_t)t * RS_GROUP_RUN_ROW_BYTES + 8, pair, 8);
+    }
+  }
   memcpy(g->h_in + (size_t)k * g->in_stride, &h, sizeof h);
 }
 
@@ -2939,7 +3009,7 @@ int group_pack_slots(rs_group* g, GroupCall& c) {
                             im.has_ids == (in[k].user_id != nullptr) &&
                             (!in[k].user_id || memcmp(im.ids.data(), in[k].user_id, 4 * (size_t)im.n) == 0);
     g->modes[k] = (uint8_t)(epoch == 0 ? 0 : (reuse_grid ? 2 : 1));
-    int rc = pack_tti(b, &in[k], &c.out[k], g->h_in + (size_t)k * g->in_stride + RS_GROUP_HDR_BYTES, reuse_grid, &pk, c.resident(), c.form == kGroupFlows);
+    int rc = pack_tti(b, &in[k], &c.out[c.at(k)], g->h_in + (size_t)k * g->in_stride + RS_GROUP_HDR_BYTES, reuse_grid, &pk, c.resident(), c.form == kGroupFlows);
     if (rc) {
       char msg[sizeof g_err];
       snprintf(msg, sizeof msg, "%s", g_err);
@@ -3016,7 +3086,7 @@ void group_fill_launch(const rs_group* g, const GroupCall& c, RsLaunch* launch) 
   L.grp_in = dev_in;
   L.grp_out = dev_out;
   L.grp_in_stride = (int64_t)g->in_stride;
-  L.grp_out_stride = (int64_t)g->out_stride;
+  L.grp_out_stride = (int64_t)g->out_stride * c.ttis(); /* (a run: a slot's TTIs follow one another) */
   L.grp_count = g->d_count;
   if (sets & kSetResident) {
     L.grp_avg = g->d_ravg;
@@ -3110,6 +3180,8 @@ int group_run(rs_group* g, GroupCall& c, RsLaunch& L) {
   /* per-PRB reports and queue state are read again and again inside the TTI: those calls keep the device copies.  (The copy sends
    * whole slots: a reuse slot's grid area and per-PRB block travel stale and are not read.) */
   if (!c.zc) HIP_TRY(hipMemcpyAsync(g->d_in, g->h_in, (size_t)c.n * g->in_stride, hipMemcpyHostToDevice, st));
+  if (!c.zc && c.run)
+    HIP_TRY(hipMemcpyAsync(g->d_in + g->run_table_off, g->h_in + g->run_table_off, (size_t)c.n * RS_GROUP_MAX_RUN * RS_GROUP_RUN_ROW_BYTES, hipMemcpyHostToDevice, st));
   if ((f.sets & kSetBearers) && !g->z_qin) HIP_TRY(hipMemcpyAsync(g->d_qin, g->h_qin, 8 * (size_t)c.n * b->U, hipMemcpyHostToDevice, st));
   c.poll = c.zc && g->poll;
   if (c.poll) {
@@ -3117,7 +3189,7 @@ int group_run(rs_group* g, GroupCall& c, RsLaunch& L) {
     L.done_flag = (uint32_t*)(g->z_out + g->flag_off);
     L.done_seq = g->seq;
   }
-  {
+  if (f.pair >= 0) { /* (a run has no pair: the built-in kernel serves it) */
     const rs_group::GroupPair& p = g->pair[f.pair];
     /* (a flows call always carries the data_to_transmit gate: its lean build keeps it) */
     const bool gate_free = c.form == kGroupFlows || !c.has_gate;
@@ -3136,7 +3208,7 @@ int group_run(rs_group* g, GroupCall& c, RsLaunch& L) {
   g->launches++;
   g->last_call_form = c.row();
   g->last_call_jit = c.kd != nullptr;
-  if (!c.zc) HIP_TRY(hipMemcpyAsync(g->h_out, g->d_out, (size_t)c.n * g->out_stride, hipMemcpyDeviceToHost, st));
+  if (!c.zc) HIP_TRY(hipMemcpyAsync(g->h_out, g->d_out, (size_t)c.n * c.ttis() * g->out_stride, hipMemcpyDeviceToHost, st));
   if ((f.sets & kSetSent) && !g->z_sent) HIP_TRY(hipMemcpyAsync(g->h_sent, g->d_sent, 8 * (size_t)c.n * b->U, hipMemcpyDeviceToHost, st));
   return RS_OK;
 }
@@ -3258,8 +3330,8 @@ void group_commit_clocks(rs_group* g, const GroupCall& c) {
     const int cell = c.cell(k);
     /* (an update-only slot credits nothing: behind an update no byte is waiting, without one nothing changed) */
     if (!g->empty_slot[k]) g->pending_zero[cell] = 0;
-    else if (c.now[k] != g->last_update[cell]) g->pending_zero[cell] = 1;
-    g->last_update[cell] = c.now[k];
+    else if (c.now_first(k) != g->last_update[cell]) g->pending_zero[cell] = 1;
+    g->last_update[cell] = c.now_last(k); /* (a run: its last TTI's clock -- a step of 0 repeats the value before it) */
   }
 }
 
@@ -3270,9 +3342,12 @@ void group_commit_images(rs_group* g, const GroupCall& c) {
     const rs_tti_in& in = c.in[k];
     const int mode = g->modes[k];
     rs_group::CellImage& im = g->img[c.cell(k)];
-    if (mode == 0) { g->n_plain++; im.valid = false; continue; } /* (as a context: a call without a number ends the image's term) */
-    if (mode == 2) { g->n_reused++; continue; }
+    /* (a run, as the calls it stands for: its later TTIs read what TTI 0 read -- the slot's blocks again without a number, else the image) */
+    const int64_t later = c.ttis() - 1;
+    if (mode == 0) { g->n_plain += 1 + later; im.valid = false; continue; } /* (as a context: a call without a number ends the image's term) */
+    if (mode == 2) { g->n_reused += 1 + later; continue; }
     g->n_stored++;
+    g->n_reused += later;
     im.valid = true;
     im.epoch = in.cqi_epoch;
     im.n = in.n_users;
@@ -3296,10 +3371,41 @@ void group_unpack(const rs_group* g, const GroupCall& c) {
       if (out.upper_user) for (int i = 0; i < b->S * b->R; i++) out.upper_user[i] = -1;
       continue;
     }
+    if (c.run) { /* output slot (k, t) is a single call's output block */
+      for (int t = 0; t < c.n_ttis; t++) unpack_tti(b, &c.in[k], &c.out[c.at(k, t)], g->h_out + c.at(k, t) * g->out_stride, g->packs[k].l, c.want_upper);
+      continue;
+    }
     unpack_tti(b, &c.in[k], &out, g->h_out + (size_t)k * g->out_stride, g->packs[k].l, c.want_upper, c.form == kGroupFlows ? c.flow[k] : nullptr);
     /* (a counted call: the slot's sent rows, [n_users][2] in call order, written by the threads that credited the positions) */
     if (c.counted && c.sent && c.sent[k]) memcpy(c.sent[k], g->h_sent + (size_t)k * 2 * (size_t)b->U, 8 * (size_t)c.in[k].n_users);
   }
+}
+
+/* A run needs slots x TTIs output slots: the device block and the pinned, mapped block grow to the largest run so far, the completion word
+ * moves behind the new last slot.  Between two calls the stream is idle and nothing points into the old blocks.  The new blocks are made
+ * before the old ones go: a failure leaves the group as it was. */
+int group_grow_out(rs_group* g, size_t slots) {
+  if (slots <= g->out_slots) return RS_OK;
+  const size_t flag_off = g->out_stride * slots, bytes = flag_off + 64;
+  uint8_t *d = nullptr, *h = nullptr;
+  void* z = nullptr;
+  bool ok = hipMalloc(&d, bytes) == hipSuccess && hipHostMalloc((void**)&h, bytes, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
+  if (ok && g->z_out) ok = hipHostGetDevicePointer(&z, h, 0) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    if (d) (void)hipFree(d);
+    if (h) (void)hipHostFree(h);
+    return fail(RS_ERR_HIP, "allocation of the run's output blocks failed (%zu bytes each)", bytes);
+  }
+  memset(h, 0, bytes);
+  (void)hipFree(g->d_out);
+  (void)hipHostFree(g->h_out);
+  g->d_out = d;
+  g->h_out = h;
+  if (g->z_out) g->z_out = (uint8_t*)z;
+  g->out_slots = slots;
+  g->flag_off = flag_off;
+  return RS_OK;
 }
 
 /* one group call, phase by phase; RS_DROPIN_TIMING splits it into prepare, enqueue, wait and unpack */
@@ -3312,6 +3418,7 @@ int group_schedule(rs_group* g, GroupCall c) {
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   if ((rc = group_pack_slots(g, c))) return rc;
   ImageGuard guard{g, c, false};
+  if (c.run && (rc = group_grow_out(g, (size_t)c.n * (size_t)c.n_ttis))) return rc;
   const clk::time_point t1 = g->timing ? clk::now() : clk::time_point();
   c.zc = g->z_in != nullptr && !c.has_prb && !b->any_alpha;
   RsLaunch L;
@@ -3333,7 +3440,7 @@ int group_schedule(rs_group* g, GroupCall c) {
     g->t_wait += us(t2, t3);
     g->t_unpack += us(t3, t4);
     g->n_calls++;
-    g->n_cell_ttis += c.n;
+    g->n_cell_ttis += (long)c.n * c.ttis();
   }
   if (c.store_failed_now)
     snprintf(g_err, sizeof g_err, "note: the group's per-PRB report store (%zu bytes) could not be allocated: calls with cqi_prb are served as if "

@@ -413,8 +413,13 @@ struct RsGroupCell {
    * clock of this cell's TTI */
   int32_t in_uid;
   double now;
-  int32_t pad_[RS_GROUP_HDR_BYTES / 4 - 22];
+  /* a run of consecutive TTIs (rs_group_run_at, rs_group_run_kernel; the other kernels read none of the three): how many, where the
+   * slot's per-TTI table lies -- bytes from this header, 16 per TTI: the clock (a double), then rand0 and rand1; `now`, rand0 and rand1
+   * above are not read -- and the bytes between two of the slot's run_ttis output blocks, which follow one another in TTI order */
+  int32_t run_ttis, run_table, run_out_step;
+  int32_t pad_[RS_GROUP_HDR_BYTES / 4 - 25];
 };
+#define RS_GROUP_RUN_ROW_BYTES 16
 static_assert(sizeof(RsGroupCell) == RS_GROUP_HDR_BYTES, "the slot header keeps its size: new words come out of its padding");
 static_assert(__builtin_offsetof(RsGroupCell, image_mode) == 72 && __builtin_offsetof(RsGroupCell, now) == 80, "no existing word of the slot header moves");
 

@@ -778,7 +778,7 @@ template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
   constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
-  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = false, kGrpCnt = false, kGrpFlow = false;
+  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = false, kGrpCnt = false, kGrpFlow = false, kGrpRun = false;
 #include "rs_phase_group.inc"
 }
 
@@ -789,7 +789,7 @@ template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_resident_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
   constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
-  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = true, kGrpQue = false, kGrpCnt = false, kGrpFlow = false;
+  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = true, kGrpQue = false, kGrpCnt = false, kGrpFlow = false, kGrpRun = false;
 #include "rs_phase_group.inc"
 }
 
@@ -801,7 +801,7 @@ template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_queued_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
   constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
-  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = true, kGrpCnt = false, kGrpFlow = false;
+  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = true, kGrpCnt = false, kGrpFlow = false, kGrpRun = false;
 #include "rs_phase_group.inc"
 }
 
@@ -813,7 +813,7 @@ template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_counted_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
   constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
-  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = true, kGrpCnt = true, kGrpFlow = false;
+  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = true, kGrpCnt = true, kGrpFlow = false, kGrpRun = false;
 #include "rs_phase_group.inc"
 }
 
@@ -825,7 +825,19 @@ template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_flows_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
   constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
-  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = false, kGrpCnt = false, kGrpFlow = true;
+  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = false, kGrpCnt = false, kGrpFlow = true, kGrpRun = false;
+#include "rs_phase_group.inc"
+}
+
+/* ... and the resident form's run (rs_group_run_at): T consecutive TTIs of every named cell in one launch -- the resident form's update,
+ * body and credit T times per workgroup, the clock and the rand() pair of each TTI from the slot's table, one completion behind the last
+ * TTI.  Kernels of their own, the resident form's shapes without NVS (rs_launch_group_run): the resident kernels above carry none of it.
+ * Built in only: a group's run-time builds do not serve runs. */
+template <int SCHED, int EPT>
+__global__ void __launch_bounds__(512, 4) rs_group_run_kernel(RsLaunch p) {
+  extern __shared__ __align__(16) unsigned char lds[];
+  constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
+  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = true, kGrpQue = false, kGrpCnt = false, kGrpFlow = false, kGrpRun = true;
 #include "rs_phase_group.inc"
 }
 #else
@@ -904,7 +916,7 @@ extern "C" __global__ void __launch_bounds__(RS_JIT_NT, RS_JIT_WPE) RS_GROUP_JIT
   __shared__ __align__(16) unsigned char lds[kCv.lds_bytes];
   constexpr int kGrpSched = RS_JIT_SCHED, kGrpEpt = (RS_JIT_SCHED != 9 && RS_JIT_SCHED != 10) ? 0 : (kCv.ept <= 4 ? kCv.ept : 0);
   constexpr bool kGrpFixed = true, kGrpRes = RS_JIT_GROUP_RESIDENT != 0, kGrpQue = RS_JIT_GROUP_QUEUED != 0 || RS_JIT_GROUP_COUNTED != 0,
-                 kGrpCnt = RS_JIT_GROUP_COUNTED != 0, kGrpFlow = RS_JIT_GROUP_FLOWS != 0;
+                 kGrpCnt = RS_JIT_GROUP_COUNTED != 0, kGrpFlow = RS_JIT_GROUP_FLOWS != 0, kGrpRun = false;
 #include "rs_phase_group.inc"
 }
 #undef RS_GROUP_JIT_ENTRY
@@ -1190,6 +1202,37 @@ extern "C" hipError_t rs_launch_group_flows(const RsLaunch* p, int threads, hipS
   return hipGetLastError();
 }
 
+/* a run of resident group calls (rs_group_run_at): the same grid, the kernels that serve the slots' T TTIs in one launch */
+extern "C" hipError_t rs_launch_group_run(const RsLaunch* p, int threads, hipStream_t stream) {
+  dim3 grid(p->n_cells), block(threads);
+  const int ept = (p->R * p->S + threads - 1) / threads;
+  if (!p->grp_avg || !p->grp_pending || !p->grp_last || !p->grp_gather || !p->grp_uid) return hipErrorInvalidValue;
+#define RS_LAUNCH_GROUP(SCHED_, EPT_) hipLaunchKernelGGL((rs_group_run_kernel<SCHED_, EPT_>), grid, block, p->lds_bytes, stream, *p)
+  switch (p->sched) {
+    case 1: RS_LAUNCH_GROUP(1, 0); break;
+    case 8: RS_LAUNCH_GROUP(8, 0); break;
+    case 101: RS_LAUNCH_GROUP(101, 0); break;
+    case 103: RS_LAUNCH_GROUP(103, 0); break;
+    case 10:
+      if (ept <= 1) RS_LAUNCH_GROUP(10, 1);
+      else if (ept <= 2) RS_LAUNCH_GROUP(10, 2);
+      else if (ept <= 3) RS_LAUNCH_GROUP(10, 3);
+      else if (ept <= 4) RS_LAUNCH_GROUP(10, 4);
+      else return hipErrorInvalidValue;
+      break;
+    case 9:
+      if (ept <= 1) RS_LAUNCH_GROUP(9, 1);
+      else if (ept <= 2) RS_LAUNCH_GROUP(9, 2);
+      else if (ept <= 3) RS_LAUNCH_GROUP(9, 3);
+      else if (ept <= 4) RS_LAUNCH_GROUP(9, 4);
+      else RS_LAUNCH_GROUP(9, 0);
+      break;
+    default: return hipErrorInvalidValue;
+  }
+#undef RS_LAUNCH_GROUP
+  return hipGetLastError();
+}
+
 extern "C" hipError_t rs_prepare_kernels(int max_lds_bytes) {
 #define RS_BOTH(SCHED_, EPT_) (const void*)rs_cell_kernel<SCHED_, EPT_, false>, (const void*)rs_cell_kernel<SCHED_, EPT_, true>
   const void* fns[] = {RS_BOTH(1, 0),  RS_BOTH(7, 0),  RS_BOTH(8, 0),  RS_BOTH(101, 0), RS_BOTH(103, 0), RS_BOTH(11, 0),
@@ -1222,7 +1265,14 @@ extern "C" hipError_t rs_prepare_kernels(int max_lds_bytes) {
                        (const void*)rs_group_counted_kernel<9, 0>,   (const void*)rs_group_counted_kernel<9, 1>,
                        (const void*)rs_group_counted_kernel<9, 2>,   (const void*)rs_group_counted_kernel<9, 3>,
                        (const void*)rs_group_counted_kernel<9, 4>,
-                       (const void*)rs_group_flows_kernel<1, 0>};
+                       (const void*)rs_group_flows_kernel<1, 0>,
+                       (const void*)rs_group_run_kernel<1, 0>,   (const void*)rs_group_run_kernel<8, 0>,
+                       (const void*)rs_group_run_kernel<101, 0>, (const void*)rs_group_run_kernel<103, 0>,
+                       (const void*)rs_group_run_kernel<10, 1>,  (const void*)rs_group_run_kernel<10, 2>,
+                       (const void*)rs_group_run_kernel<10, 3>,  (const void*)rs_group_run_kernel<10, 4>,
+                       (const void*)rs_group_run_kernel<9, 0>,   (const void*)rs_group_run_kernel<9, 1>,
+                       (const void*)rs_group_run_kernel<9, 2>,   (const void*)rs_group_run_kernel<9, 3>,
+                       (const void*)rs_group_run_kernel<9, 4>};
 #undef RS_BOTH
 
   for (const void* f : fns) {

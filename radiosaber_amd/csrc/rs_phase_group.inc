@@ -53,8 +53,19 @@
  * host).  With kGrpFlow false none of this text reaches the other instantiations.  Under kGrpFixed
  * (rs_group_flows_kernel_jit) the flows text's shape is constant as the queued text's: the update's range and the strides of the [U][2]
  * stores are 2 * RS_JIT_U, the loop strides RS_JIT_NT, the LDS offsets the constexpr carve's off_tx and off_misc, the PRBs per RBG
- * RS_JIT_G.  Order of operations and arithmetic are the same in both forms. */
+ * RS_JIT_G.  Order of operations and arithmetic are the same in both forms.
+ *
+ * A ninth constant, kGrpRun, makes the run form of the resident wrapper (rs_group_run_at, rs_group_run_kernel; only with kGrpRes, built
+ * in only): the workgroup serves T consecutive TTIs of its cell -- the resident form's three steps, T times, in their order and
+ * arithmetic, then the completion chain once.  The header is read once; what changes per TTI -- the clock and the rand() pair --
+ * comes from the slot's table (RsGroupCell::run_table), output block t lies run_out_step bytes behind block t - 1, and the users are
+ * the slot's for the whole run.  TTI 0 does with the CQI reports what the slot's image_mode says; under a cqi_epoch the later TTIs
+ * load the cell's image (and read the cell's per-PRB store) as calls of their own would, without one they read the slot's blocks
+ * again.  Between two TTIs stands one workgroup barrier behind a device-scope fence: the credit of TTI t goes by call position, the
+ * update of TTI t + 1 by user id -- other threads --, and the body's load phase overwrites the LDS grants the credit reads.  A text
+ * of its own below: with kGrpRun false none of it reaches the other instantiations, whose resident text is left as it is. */
   static_assert(!kGrpCnt || kGrpQue, "the counted form is the queued form's");
+  static_assert(!kGrpRun || (kGrpRes && !kGrpFixed && !kGrpLean && kGrpSched != 7), "the run form is the resident form's, built in, and never NVS");
   static_assert(!kGrpFlow || (!kGrpRes && !kGrpQue && !kGrpCnt && kGrpSched == 1), "the flows form is scheduler 1's, a resident form of its own");
   const uint8_t* const in = p.grp_in + (size_t)blockIdx.x * (size_t)p.grp_in_stride;
   uint8_t* const out = p.grp_out + (size_t)blockIdx.x * (size_t)p.grp_out_stride;
@@ -108,7 +119,86 @@
   if (p.stamps) q.stamps = p.stamps + (size_t)blockIdx.x * 20;
   unsigned long long grp_res_cycles = 0;
 #endif
-  if constexpr (kGrpRes) {
+  if constexpr (kGrpRun) {
+    /* (shape and carve: the launch block's -- a run is served by the built-in kernels alone) */
+    const int nthreads = (int)blockDim.x;
+    const int n_all = p.U; /* the config's users: the stores' stride and the update's range */
+    double* const r_avg = p.grp_avg + (size_t)cell * (size_t)n_all;
+    int32_t* const r_pend = p.grp_pending + (size_t)cell * (size_t)n_all;
+    auto dword = [&](const double* d) { return __hiloint2double(word((const int32_t*)d + 1), word((const int32_t*)d)); };
+    const int n_run = word(&h->run_ttis);
+    const uint8_t* const table = in + word(&h->run_table);
+    const int out_step = word(&h->run_out_step);
+    const int in_uid = word(&h->in_uid);
+    const int32_t* const uid = (const int32_t*)(data + in_uid);
+    double* const row = p.grp_gather + (size_t)cell * (size_t)n_all;
+    int32_t* const ids = p.grp_uid + (size_t)cell * (size_t)n_all;
+    const int32_t* const granted = (const int32_t*)(lds + p.off_tx);
+    /* (the cell's last-update time rides in a register: every thread reads the word here, thread 0 writes it behind the loop, whose
+     * barriers lie between the two) */
+    double last = dword(p.grp_last + cell);
+    uint8_t* o = out;
+    for (int t = 0; t < n_run; ++t) {
+      const uint8_t* const tr = table + (size_t)t * RS_GROUP_RUN_ROW_BYTES;
+      const double now = dword((const double*)tr);
+      q.rand0 = word((const int32_t*)tr + 2);
+      q.rand1 = word((const int32_t*)tr + 3);
+      q.log_tbs = (int32_t*)o;
+      q.log_uinfo = (int32_t*)(o + word(&h->out_uinfo));
+      q.log_map = (int16_t*)(o + word(&h->out_map));
+      q.log_quota = (int16_t*)(o + word(&h->out_quota));
+      q.log_target = (int16_t*)(o + word(&h->out_target));
+      q.log_upper = p.log_upper ? (int32_t*)(o + word(&h->out_upper)) : nullptr;
+      /* 1. the update, for every user id of the cell: the resident form's step 1, operation by operation */
+      if (!(now == last)) {
+        const double dt = now - last;
+        for (int u = threadIdx.x; u < n_all; u += nthreads) {
+          double a = r_avg[u];
+          const int txb = r_pend[u];
+          double rate = (double)(int32_t)((uint32_t)txb * 8u) / dt;
+          const double beta = 0.02;
+          a = ((1 - beta) * a) + (beta * rate);
+          if (a < 1) a = 1;
+          r_avg[u] = a;
+          r_pend[u] = 0;
+        }
+        last = now;
+      }
+      /* behind it a thread reads averages that other threads wrote */
+      __syncthreads();
+      /* 2. the call's averages, gathered again behind every update.  Thread i writes row entry i and is the thread that reads it in the
+       *    body's load phase; the ids are the slot's in TTI 0 (it may lie in host memory) and the cell's row afterwards. */
+      q.avg = r_avg;
+      if (in_uid != 0) {
+        for (int i = threadIdx.x; i < q.U; i += nthreads) {
+          const int id = t == 0 ? uid[i] : ids[i];
+          row[i] = r_avg[id];
+          if (t == 0) ids[i] = id;
+        }
+        q.avg = row;
+      }
+      rs_cell_body<kGrpSched, kGrpEpt, kGrpFixed, true, false, true>(q, lds);
+      /* 3. the grants, from LDS, by call position: the resident form's step 3 */
+      for (int i = threadIdx.x; i < q.U; i += nthreads) {
+        const int bytes = granted[i];
+        if (bytes != 0) r_pend[in_uid != 0 ? ids[i] : i] += bytes;
+      }
+      if (t + 1 < n_run) {
+        /* (wave-uniform: n_run is a header word.)  The next TTI: its output block; under a cqi_epoch the image that TTI 0 stored or
+         * found, and the cell's per-PRB store; and the credit, the image, the per-PRB copy and the slice state out before any thread
+         * of the workgroup reads them again. */
+        o += out_step;
+        if (mode != 0) {
+          q.image_mode = 2;
+          if (p.prb_cqi) q.prb_cqi = p.grp_prb + (size_t)cell * (size_t)p.grp_prb_stride;
+        }
+        __threadfence();
+        __syncthreads();
+      }
+    }
+    if (threadIdx.x == 0) p.grp_last[cell] = last; /* (now[T-1], or the word as it was when no TTI of the run moved the clock) */
+  }
+  if constexpr (kGrpRes && !kGrpRun) {
     /* (shape and carve: the launch block's in the built-in kernels, the constants RS_JIT_* in a group's run-time build) */
 #ifdef RS_STAMPS
     const unsigned long long grp_res_entry = __builtin_readcyclecounter();
@@ -269,7 +359,7 @@
   if constexpr (kGrpQue || kGrpFlow) {
     /* (q.U is one word of the slot header: the skip is uniform for the whole workgroup, no barrier of the body is left half met) */
     if (q.U != 0) rs_cell_body<kGrpSched, kGrpEpt, kGrpFixed, true, false, true>(q, lds);
-  } else {
+  } else if constexpr (!kGrpRun) { /* (the run form has called the body in its loop) */
     rs_cell_body<kGrpSched, kGrpEpt, kGrpFixed, true, false, true>(q, lds);
   }
   if constexpr (kGrpQue) {
@@ -374,7 +464,7 @@
       }
     }
   }
-  if constexpr (kGrpRes) {
+  if constexpr (kGrpRes && !kGrpRun) {
     /* 3. the grants (DoStopSchedule: min(tbs_bits / 8, 100000000) bytes, rs_phase_p5.inc) from LDS, where the body's closing barrier
      *    left them for every thread -- not from the slot's output rows, which lie in host memory in the zero-copy mode.  A user is
      *    named once per call, a cell once per launch: plain adds. */
