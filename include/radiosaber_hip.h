@@ -37,7 +37,8 @@ extern "C" {
                                (a group's own builds of the counted and of the flows kernel, self-checked on bearer stores, counters and sent rows),
                                rs_group_set_counters / rs_group_get_counters / rs_group_schedule_tti_counted (a bearer-resident group cell's m_cumulateBytes / m_cumulateRBs on the device, the bytes sent per bearer returned per call),
                                rs_group_set_flows / rs_group_get_flows / rs_group_schedule_tti_flows (scheduler 1's flows of a group cell resident on the device: averages, pending bytes and counters per bearer, the whole block credited to the flow),
-                               rs_group_run_at + RS_GROUP_MAX_RUN (T consecutive TTIs of average-resident group cells in one launch);
+                               rs_group_run_at + RS_GROUP_MAX_RUN (T consecutive TTIs of average-resident group cells in one launch),
+                               rs_group_specialize_run / rs_group_run_jit_status / rs_jit_selfcheck_group_run (a group's own builds of the run kernel, self-checked per run on every TTI's outputs and on state);
                                rs_config.link_tables (RS_LINK_*) + rs_link_tables_pinned / rs_link_tables_compare, rs_tti_in.cqi_epoch (the context keeps the
                                CQI image of an unchanged report set on the device), rs_ctx_jit_status (a specialised context checks its run-time build against the
                                built-in kernel during its first calls), rs_batch_config.selfcheck -1 / 0 / 1 with run-time builds verified by default and the
@@ -324,7 +325,9 @@ int rs_group_image_stats(const rs_group* g, int64_t out[3]);
  * "rs_group_queued_kernel<sched, ept>".  While it was a counted one (rs_group_schedule_tti_counted): "rs_group_counted_kernel_jit" if
  * the group's counted builds served it (rs_group_specialize_counted), else the built-in "rs_group_counted_kernel<sched, ept>".  While
  * it was a flows one (rs_group_schedule_tti_flows): "rs_group_flows_kernel_jit" if the group's flows builds served it
- * (rs_group_specialize_flows), else the built-in "rs_group_flows_kernel<1, 0>". */
+ * (rs_group_specialize_flows), else the built-in "rs_group_flows_kernel<1, 0>".  While it was a run (rs_group_run_at):
+ * "rs_group_run_kernel_jit" if the group's run builds served it (rs_group_specialize_run), else the built-in
+ * "rs_group_run_kernel<sched, ept>". */
 const char* rs_group_kernel_name(rs_group* g);
 /* Optional, at any time between two calls: rs_ctx_specialize for a group -- the one-TTI kernel compiled for the config's slices, RBGs,
  * PRBs per RBG, scheduler, workgroup size and user capacity (hiprtc, ~2 s per build and process, cached on disk apart from the
@@ -421,9 +424,10 @@ int rs_jit_selfcheck_group_resident(int n_slices, int n_users, int n_rbgs, int r
  * -- the block is read each TTI and the cell's image ends.  Everything observable afterwards is what the loop leaves: every field of
  * every rs_tti_out (upper_* lists if asked), slice state, every user's average, pending bytes and last_update, named by the call or
  * not, the cells' image records and the three counters of rs_group_image_stats, and the state of the cells that were not named.  Two
- * things differ on purpose: rs_group_launch_count grows by 1, and rs_group_kernel_name returns "rs_group_run_kernel<sched, ept>" while
- * a run was the last call served.  Per workgroup the device repeats steps 1 - 3 of rs_group_schedule_tti_at n_ttis times, in their
- * order and arithmetic, a workgroup barrier behind a device-scope fence between two TTIs, and completes once behind the last.
+ * things differ on purpose: rs_group_launch_count grows by 1, and rs_group_kernel_name returns "rs_group_run_kernel<sched, ept>" (or
+ * "rs_group_run_kernel_jit", rs_group_specialize_run below) while a run was the last call served.  Per workgroup the device repeats
+ * steps 1 - 3 of rs_group_schedule_tti_at n_ttis times, in their order and arithmetic, a workgroup barrier behind a device-scope fence
+ * between two TTIs, and completes once behind the last.
  * Rules, each RS_ERR_INVALID unless stated, each checked before anything is launched (a rejected call launches nothing and moves nothing):
  *   - every rule of rs_group_schedule_tti_at: cell_ids, uniform presence of cqi_prb and of the upper_* outputs (over every TTI of every
  *     cell), avg_rate NULL, every named cell average-resident (RS_ERR_STATE, the message names the cell; a bearer- or flow-resident
@@ -438,13 +442,37 @@ int rs_jit_selfcheck_group_resident(int n_slices, int n_users, int n_rbgs, int r
  *   - now[k][0] obeys the at-call's clock rule against the cell's last_update; each step now[k][t] - now[k][t-1] is 0 (the
  *     reference's early return: nothing is updated) or at least 2^-20 s.
  * RS_ERR_HIP -- a failed allocation of the larger output blocks included: they grow to slots x n_ttis of the largest run so far -- leaves
- * the named cells not resident and ends their images, as the at-call does.  A run always executes the kernel built into the library,
- * before and after any rs_group_specialize*; bearer-, counted- and flow-resident cells have no runs (their data_to_transmit is the
- * host's per TTI). */
+ * the named cells not resident and ends their images, as the at-call does.  A run executes the run kernel built into the library
+ * unless the group has opted in to run-time builds of it with rs_group_specialize_run below; no other rs_group_specialize* reaches
+ * runs.  Bearer-, counted- and flow-resident cells have no runs (their data_to_transmit is the host's per TTI). */
 #define RS_GROUP_MAX_RUN 64 /* a sanity bound (>= CQI_INTERVAL = 40), not a tuned number */
 int rs_group_run_at(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in /* [n] */, int32_t n_ttis,
                     const double* now /* [n][n_ttis] */, const int32_t* rands /* [n][n_ttis][2]: rand0, rand1 of each TTI; NULL only for RS_SCHED_PF */,
                     rs_tti_out* out /* [n][n_ttis] */);
+/* Optional, at any time between two calls, with or without any other rs_group_specialize*: rs_group_specialize_resident for the RUN --
+ * the run kernel compiled for the group's shape (entry point rs_group_run_kernel_jit, cache files of its own), a general and a lean
+ * build; rs_group_run_at picks the lean one when the run has no per-PRB reports, no upper_* outputs and no synthetic-experiment
+ * blocks (and no exact scan; RS_JIT_LEAN=0: the general build only), the general one in every other case.  rs_group_schedule_tti_at
+ * and every other call are not affected, and no other rs_group_specialize* reaches runs: the six pairs are independent in both
+ * directions.  Cell state, CQI images and the resident stores are not touched.  RS_OK; a second call is a no-op; RS_ERR_HIP if a build
+ * fails, the group left on the built-in run kernel; RS_ERR_STATE (with the reason) once the run builds were dropped; RS_ERR_INVALID
+ * for RS_SCHED_NVS, RS_SCHED_NVS_NONGREEDY and a config with a customised slice, which no run serves.
+ * The check follows rs_group_specialize_resident's policy and switches (RS_DROPIN_SELFCHECK_CALLS, RS_JIT_SELFCHECK, the mark in the
+ * cache file); one checked call is one RUN: the slice state, the cell scalars and the resident stores are kept; the built-in run kernel
+ * serves the whole run into twin output blocks of slots x n_ttis; what it left is kept and the earlier state put back; then the
+ * group's build serves the run, with completion by the stream.  Every rs_tti_out field of every (cell, TTI) (upper_* lists if asked),
+ * the slice state, the averages and pending bytes of EVERY user id of the config and last_update must agree bit for bit.  (The image
+ * and the per-PRB copy that TTI 0 stores are the same bytes in both executions.)  One difference drops the run pair and unlinks its
+ * cache files; that call returns the built-in kernel's outputs and leaves its state, resident stores included; later runs execute
+ * the built-in run kernel; the message names cell, TTI, field and index ("cell 2, TTI 6: user_tbs_bits[1] = ...", "cell 2:
+ * pending_bytes[5] = 1391, the built-in kernel's 1390").  rs_group_launch_count and rs_group_image_stats count a checked run once. */
+int rs_group_specialize_run(rs_group* g);
+/* rs_group_jit_status for the run pair: 1 = the group's run builds serve the runs, 0 = rs_group_specialize_run was not called,
+ * -1 = it failed to build, -2 = the builds were dropped by the check.  The other status functions report their own pairs only. */
+int rs_group_run_jit_status(rs_group* g, char* msg, size_t msglen);
+/* build check without a GPU: do the general and the lean run build of a group of this shape compile?  (the larger code size, or a
+ * negative value with the compiler's log in err; negative with a message for RS_SCHED_NVS and RS_SCHED_NVS_NONGREEDY, which have no run) */
+int rs_jit_selfcheck_group_run(int n_slices, int n_users, int n_rbgs, int rbg_size, int threads, int sched, char* err, size_t errlen);
 
 /* Resident bearers (ABI 11 addition, no layout changed): the second resident form of a group's cell.  The cell keeps, per user id of the
  * config and per bearer (MAX_BEARERS = 2, index = the bearer's priority), RadioBearer's average rate and the bytes DoStopSchedule
@@ -556,7 +584,7 @@ int rs_group_schedule_tti_counted(rs_group* g, int32_t n, const int32_t* cell_id
  * (entry point rs_group_counted_kernel_jit, cache files of its own), a general and a lean build picked by the queued call's per-launch
  * condition (a call made of update-only slots only takes the lean build, unless the config rules it out); at any time between two
  * calls, a second call is a no-op; RS_ERR_HIP if a build fails, the group left on the built-in counted kernel; RS_ERR_STATE (with the
- * reason) once the counted builds were dropped; RS_ERR_INVALID for a scheduler without the form.  The five pairs are independent in
+ * reason) once the counted builds were dropped; RS_ERR_INVALID for a scheduler without the form.  The six pairs (the run pair of rs_group_specialize_run included) are independent in
  * both directions: rs_group_specialize_queued does not reach counted calls, this one does not reach queued calls.
  * The check is the queued pair's (policy, switches, the mark in the cache file) on more stores: for every user id of the config and
  * both bearers avg, pending_bytes, last_update, cum_bytes[U][2] and cum_rbs[U][2] (int64, bit for bit) are kept, put back and compared,
@@ -610,7 +638,7 @@ int rs_group_schedule_tti_flows(rs_group* g, int32_t n, const int32_t* cell_ids,
 /* rs_group_specialize_queued for the FLOWS call (ABI 11 addition): the flows kernel compiled for the group's shape (entry point
  * rs_group_flows_kernel_jit, cache files of its own), a general and a lean build.  A flows call always carries the data_to_transmit gate,
  * so its lean build keeps the gate and is picked when no slot brings per-PRB reports, the exact scan or synthetic-experiment blocks (and
- * the config has no customised slices).  When, errors, independence of the five pairs and the check are rs_group_specialize_counted's;
+ * the config has no customised slices).  When, errors, independence of the pairs and the check are rs_group_specialize_counted's;
  * RS_ERR_INVALID for every scheduler but RS_SCHED_PF.  The check keeps, puts back and compares avg, pending_bytes, last_update,
  * cum_bytes[U][2] and cum_rbs[U][2] of every user id and both bearers; the message names cell, field and index ("cell 2:
  * cum_bytes[4][1] = 1201, the built-in kernel's 1200"). */

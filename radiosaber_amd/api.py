@@ -118,6 +118,7 @@ ABI_SYMBOLS = [
     "rs_group_set_flows", "rs_group_get_flows", "rs_group_schedule_tti_flows",
     "rs_group_specialize_counted", "rs_group_counted_jit_status", "rs_jit_selfcheck_group_counted",
     "rs_group_specialize_flows", "rs_group_flows_jit_status", "rs_jit_selfcheck_group_flows",
+    "rs_group_specialize_run", "rs_group_run_jit_status", "rs_jit_selfcheck_group_run",
 ]
 
 _lib = None
@@ -193,6 +194,9 @@ def lib():
     L.rs_group_specialize_flows.argtypes = [C.c_void_p]
     L.rs_group_flows_jit_status.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.rs_jit_selfcheck_group_flows.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
+    L.rs_group_specialize_run.argtypes = [C.c_void_p]
+    L.rs_group_run_jit_status.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    L.rs_jit_selfcheck_group_run.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
     L.rs_batch_create.restype = C.c_void_p
     L.rs_batch_create.argtypes = [C.POINTER(_BatchConfig)]
     L.rs_create_checked.restype = C.c_void_p
@@ -288,15 +292,16 @@ def _p(a, t):
 
 
 def jit_selfcheck(n_slices, n_users, n_rbgs, rbg_size, threads=512, sched=RS_SCHED_MAXCELL, queues=False, untuned=False, dropin=False,
-                  group=False, resident=False, queued=False, counted=False, flows=False):
+                  group=False, resident=False, queued=False, counted=False, flows=False, run=False):
     """Compile the shape-specialised kernel for one shape (hiprtc, no GPU needed); returns the code size.  queues=True: the
     queue-model kernel of the shape.  untuned=True: without the -mllvm tuning options (the library's fallback build).
     group=True: the general and the lean build of a group of this shape (rs_group_specialize); the larger code size.
     group=True, resident=True: the two builds of the group's resident kernel (rs_group_specialize_resident).
     group=True, queued=True: the two builds of the group's queued kernel (rs_group_specialize_queued; schedulers 7, 8, 9, 101, 103).
     group=True, counted=True: the two builds of the group's counted kernel (rs_group_specialize_counted; the queued form's schedulers).
-    group=True, flows=True: the two builds of the group's flows kernel (rs_group_specialize_flows; scheduler 1)."""
-    _jit_flags(False, False, group, resident, queued, counted, flows)
+    group=True, flows=True: the two builds of the group's flows kernel (rs_group_specialize_flows; scheduler 1).
+    group=True, resident=True, run=True: the two builds of the group's run kernel (rs_group_specialize_run; never schedulers 7 and 11)."""
+    _jit_flags(False, False, group, resident, queued, counted, flows, run)
     buf = C.create_string_buffer(4096)
     fn = lib().rs_jit_selfcheck_queue if queues else (lib().rs_jit_selfcheck_untuned if untuned else lib().rs_jit_selfcheck)
     if dropin:  # the drop-in entry point's one-TTI kernel of a context of this shape (rs_ctx_specialize)
@@ -309,6 +314,8 @@ def jit_selfcheck(n_slices, n_users, n_rbgs, rbg_size, threads=512, sched=RS_SCH
             fn = lib().rs_jit_selfcheck_group_counted
         if flows:
             fn = lib().rs_jit_selfcheck_group_flows
+        if run:
+            fn = lib().rs_jit_selfcheck_group_run
     n = fn(n_slices, n_users, n_rbgs, rbg_size, threads, sched, buf, 4096)
     if n < 0:
         raise RadioSaberError(n, buf.value.decode(errors="replace"))
@@ -322,7 +329,11 @@ def jit_cache_stats():
     return dict(zip(("hits", "misses", "stores", "rejected"), (int(x) for x in out)))
 
 
-def _jit_flags(lean, streamed, group, resident, queued=False, counted=False, flows=False):
+def _jit_flags(lean, streamed, group, resident, queued=False, counted=False, flows=False, run=False):
+    if run and not (group and resident):
+        raise ValueError("run=True needs group=True and resident=True: the run kernel is the resident form's")
+    if run and (queued or counted or flows):
+        raise ValueError("run=True excludes queued=True, counted=True and flows=True: only the resident form has a run")
     if counted and not group:
         raise ValueError("counted=True needs group=True: only a group has a counted kernel")
     if flows and not group:
@@ -340,28 +351,28 @@ def _jit_flags(lean, streamed, group, resident, queued=False, counted=False, flo
     if queued and resident:
         raise ValueError("resident=True and queued=True exclude each other: two forms of a group's kernel")
     return (4 if lean else 0) | (2 if streamed else 0) | (8 if group else 0) | (16 if resident else 0) | (32 if queued else 0) | \
-        (64 if counted else 0) | (128 if flows else 0)
+        (64 if counted else 0) | (128 if flows else 0) | (256 if run else 0)
 
 
 def jit_cache_file(n_slices, n_users, n_rbgs, rbg_size, threads=512, sched=RS_SCHED_MAXCELL, lean=False, streamed=False, group=False,
-                   resident=False, queued=False, counted=False, flows=False):
+                   resident=False, queued=False, counted=False, flows=False, run=False):
     """Path of the cache file the batch kernel of this shape lives in ('' when no cache directory can be named).  group=True: a
     group's build of the one-TTI kernel (flag bit of value 8); with resident=True its resident form (value 16), with queued=True its
     queued form (value 32), with counted=True the queued form's counted twin (values 32 and 64), with flows=True scheduler 1's flows form
-    (value 128)."""
+    (value 128), with resident=True and run=True the resident form's run (values 16 and 256)."""
     buf = C.create_string_buffer(4096)
-    lib().rs_jit_cache_file(n_slices, n_users, n_rbgs, rbg_size, threads, sched, _jit_flags(lean, streamed, group, resident, queued, counted, flows),
+    lib().rs_jit_cache_file(n_slices, n_users, n_rbgs, rbg_size, threads, sched, _jit_flags(lean, streamed, group, resident, queued, counted, flows, run),
                             buf, 4096)
     return buf.value.decode()
 
 
 def jit_cache_warm(n_slices, n_users, n_rbgs, rbg_size, threads=512, sched=RS_SCHED_MAXCELL, lean=False, streamed=False, group=False,
-                   resident=False, queued=False, counted=False, flows=False):
+                   resident=False, queued=False, counted=False, flows=False, run=False):
     """Compile (or load) the batch kernel of this shape through the disk cache; no GPU needed.  Returns the code size.
     group=True: a group's build of the one-TTI kernel; with resident=True its resident form, with queued=True its queued form, with
-    counted=True its counted form, with flows=True its flows form."""
+    counted=True its counted form, with flows=True its flows form, with resident=True and run=True the resident form's run."""
     buf = C.create_string_buffer(4096)
-    n = lib().rs_jit_cache_warm(n_slices, n_users, n_rbgs, rbg_size, threads, sched, _jit_flags(lean, streamed, group, resident, queued, counted, flows),
+    n = lib().rs_jit_cache_warm(n_slices, n_users, n_rbgs, rbg_size, threads, sched, _jit_flags(lean, streamed, group, resident, queued, counted, flows, run),
                                 buf, 4096)
     if n < 0:
         raise RadioSaberError(n, buf.value.decode(errors="replace"))
@@ -688,10 +699,12 @@ class GroupScheduler:
 
     def __init__(self, slices: SliceConfig, n_rbgs: int, rbg_size: int, n_cells: int, sched: int = RS_SCHED_MAXCELL,
                  device: int = 0, stream: Optional[int] = None, synthetic_exp: bool = False, link_tables: int = RS_LINK_DEFAULT,
-                 jit: bool = False, jit_resident: bool = False, jit_queued: bool = False, jit_counted: bool = False, jit_flows: bool = False):
+                 jit: bool = False, jit_resident: bool = False, jit_queued: bool = False, jit_counted: bool = False, jit_flows: bool = False,
+                 jit_run: bool = False):
         """jit: specialize() right after the group is created.  jit_resident: specialize_resident() as well (independent of jit).
         jit_queued: specialize_queued() as well (independent of both).  jit_counted / jit_flows: specialize_counted() /
-        specialize_flows() as well (independent of all others)."""
+        specialize_flows() as well (independent of all others).  jit_run: specialize_run() as well (independent of all others: the
+        builds that serve run_at)."""
         self.slices, self.R, self.rbg_size, self.sched, self.n_cells = slices, n_rbgs, rbg_size, sched, n_cells
         self._cfg = _CfgHolder(slices, n_rbgs, rbg_size, sched, device, stream, synthetic_exp, link_tables)
         self._h = lib().rs_group_create_checked(C.byref(self._cfg.c), n_cells, RS_ABI_VERSION, C.sizeof(_Config))
@@ -707,6 +720,8 @@ class GroupScheduler:
             self.specialize_counted()
         if jit_flows:
             self.specialize_flows()
+        if jit_run:
+            self.specialize_run()
 
     def specialize(self):
         """rs_group_specialize: the group's own hiprtc builds of the one-TTI kernel (identical results; their first calls run beside
@@ -751,7 +766,7 @@ class GroupScheduler:
         """rs_group_specialize_counted: the group's own hiprtc builds of the COUNTED kernel, for schedule_tti_counted (identical results;
         their first calls run beside the built-in counted kernel and are compared on outputs, sent rows and state -- slice state, both
         bearers' averages, pending bytes, cum_bytes and cum_rbs of every user, last update -- unless the builds carry the self-check
-        mark: counted_jit_status()).  Independent of the other four pairs; any time between two calls; again: a no-op."""
+        mark: counted_jit_status()).  Independent of the other pairs; any time between two calls; again: a no-op."""
         _check(lib().rs_group_specialize_counted(self._h))
 
     def counted_jit_status(self):
@@ -765,7 +780,7 @@ class GroupScheduler:
         """rs_group_specialize_flows: the group's own hiprtc builds of scheduler 1's FLOWS kernel, for schedule_tti_flows (identical
         results; their first calls run beside the built-in flows kernel and are compared on outputs and on state -- slice state, both
         bearers' averages, pending bytes, cum_bytes and cum_rbs of every user, last update -- unless the builds carry the self-check
-        mark: flows_jit_status()).  Independent of the other four pairs; any time between two calls; again: a no-op."""
+        mark: flows_jit_status()).  Independent of the other pairs; any time between two calls; again: a no-op."""
         _check(lib().rs_group_specialize_flows(self._h))
 
     def flows_jit_status(self):
@@ -773,6 +788,21 @@ class GroupScheduler:
         -1 build failed, -2 dropped by the self-check."""
         buf = C.create_string_buffer(768)
         rc = lib().rs_group_flows_jit_status(self._h, buf, 768)
+        return rc, buf.value.decode(errors="replace")
+
+    def specialize_run(self):
+        """rs_group_specialize_run: the group's own hiprtc builds of the RUN kernel, for run_at (identical results; their first runs
+        execute beside the built-in run kernel and are compared on the outputs of every (cell, TTI) and on state -- slice state,
+        averages and pending bytes of every user id, last update -- unless the builds carry the self-check mark: run_jit_status()).
+        Independent of the other five pairs -- specialize_resident() does not reach runs, this does not reach schedule_tti_at --; any
+        time between two calls; again: a no-op."""
+        _check(lib().rs_group_specialize_run(self._h))
+
+    def run_jit_status(self):
+        """(code, message) of rs_group_run_jit_status, for the run builds alone: 1 they serve the runs, 0 not asked for, -1 build
+        failed, -2 dropped by the self-check."""
+        buf = C.create_string_buffer(768)
+        rc = lib().rs_group_run_jit_status(self._h, buf, 768)
         return rc, buf.value.decode(errors="replace")
 
     def close(self):

@@ -2029,12 +2029,13 @@ void unpack_tti(const rs_batch* b, const rs_tti_in* in, rs_tti_out* out, const u
 }
 
 /* The self-check of a run-time build, one call's output block (layout `l`, n users): `mine` against the built-in kernel's `ref`, field
- * by field; the first difference is the message (`what` stays empty when there is none).  cell >= 0: a group's slot, named in front.
- * Shared by rs_schedule_tti and rs_group_schedule_tti. */
+ * by field; the first difference is the message (`what` stays empty when there is none).  cell >= 0: a group's slot, named in front;
+ * tti >= 0: a run's TTI, named behind the cell.  Shared by rs_schedule_tti and rs_group_schedule_tti. */
 void compare_out_block(const uint8_t* mine, const uint8_t* ref, const CtxLayout& l, int R, int S, int n, bool want_upper, int cell, char* what,
-                       size_t len) {
-  char pre[24] = "";
-  if (cell >= 0) snprintf(pre, sizeof pre, "cell %d: ", cell);
+                       size_t len, int tti = -1) {
+  char pre[40] = "";
+  if (cell >= 0 && tti >= 0) snprintf(pre, sizeof pre, "cell %d, TTI %d: ", cell, tti);
+  else if (cell >= 0) snprintf(pre, sizeof pre, "cell %d: ", cell);
   auto differ = [&](const char* name, size_t off, int count, auto elem) {
     using T = decltype(elem);
     const T *a = (const T*)(mine + off), *r = (const T*)(ref + off);
@@ -2450,9 +2451,9 @@ struct rs_group {
   double t_prep = 0, t_enq = 0, t_wait = 0, t_unpack = 0;
   long n_calls = 0, n_cell_ttis = 0, n_polled = 0, n_fallback = 0;
   /* Run-time builds of a group call's kernel (rs_group_specialize, rs_group_specialize_resident, rs_group_specialize_queued,
-   * rs_group_specialize_flows, rs_group_specialize_counted): one pair
+   * rs_group_specialize_flows, rs_group_specialize_counted, rs_group_specialize_run): one pair
    * of builds per form (index 0: general build, 1: lean build for the plain call), and their check against the form's
-   * built-in kernel -- calls still to be checked, calls that agreed so far (rs_ctx's scheme).  The five pairs are independent: each
+   * built-in kernel -- calls still to be checked, calls that agreed so far (rs_ctx's scheme).  The six pairs are independent: each
    * serves its own kind of call, is checked against its own built-in kernel and is dropped alone.  The check of a form with stores
    * (kGroupForms) also compares those: d_stores_chk holds them before the built-in kernel ran and as that kernel left them (two halves,
    * group_copy_stores). */
@@ -2463,8 +2464,10 @@ struct rs_group {
     uint8_t* d_stores_chk = nullptr;
     char msg[512] = "";
   };
-  GroupPair pair[5]; /* by kGroupPlain, kGroupResident, kGroupQueued, kGroupFlows, kGroupCounted */
-  uint8_t *d_out2 = nullptr, *d_chk = nullptr; /* every pair's: the built-in kernel's output slots; the group's slice state + scalars before / after it */
+  GroupPair pair[6]; /* by kGroupPlain, kGroupResident, kGroupQueued, kGroupFlows, kGroupCounted, kGroupRun */
+  /* every pair's: the built-in kernel's output slots (out_slots of them, as d_out: group_grow_out grows both for a run); the group's
+   * slice state + scalars before / after it */
+  uint8_t *d_out2 = nullptr, *d_chk = nullptr;
   std::vector<uint8_t> h_out2;
   /* resident averages (rs_group_set_avg, rs_group_schedule_tti_at): per cell [U] averages, [U] pending bytes and the time of their
    * last update on the device (allocated by the first rs_group_set_avg), the gather rows of calls that name their users, and on the
@@ -2522,10 +2525,10 @@ struct GroupForm {
   hipError_t (*launch)(const RsLaunch*, int, hipStream_t); /* the built-in launcher */
   unsigned sets;
   bool slots0;     /* update-only slots (n_users == 0) are allowed */
-  int pair;        /* rs_group::pair[] that serves the form; -1: none, the built-in kernel always serves it */
+  int pair;        /* rs_group::pair[] that serves the form */
   int store_width; /* the stores its self-check saves, restores and compares: 0 none, 1 the resident stores [U], 2 the bearer stores [U][2]
                     * (a form with kSetCounters: the counter stores [U][2] too; with kSetSent: the slots' sent rows are compared as well) */
-  int jit_flags;   /* rs_jit_get: 1 one-TTI form, 8 group wrapper, 16 resident, 32 queued, 64 counted, 128 flows */
+  int jit_flags;   /* rs_jit_get: 1 one-TTI form, 8 group wrapper, 16 resident, 32 queued, 64 counted, 128 flows, 256 run */
   const char* jit_name;
   /* the nouns of the pair's messages: "specialised <adj>%s build", "both <adj>builds are dropped, <serves>", "agreed with <ref>",
    * "copies of the <stores>" */
@@ -2542,7 +2545,8 @@ const GroupForm kGroupForms[6] = {
     {rs_launch_group_counted, kSetResident | kSetBearers | kSetCounters | kSetSent, true, kGroupCounted, 2, 1 | 8 | 32 | 64, "rs_group_counted_kernel_jit", "counted ",
      "the built-in counted kernel serves this group's counted calls", "the built-in counted kernel field by field, bearer stores, counters and sent rows included",
      "bearer stores and counters"},
-    {rs_launch_group_run, kSetResident, false, -1, 0, 0, "", "", "", "", ""},
+    {rs_launch_group_run, kSetResident, false, kGroupRun, 1, 1 | 8 | 16 | 256, "rs_group_run_kernel_jit", "run ",
+     "the built-in run kernel serves this group's runs", "the built-in run kernel field by field over every TTI, resident stores included", "resident stores"},
 };
 
 /* bytes of one half of rs_group::d_chk: [n_cells][S] slice state, then [n_cells] RsCellScalars */
@@ -2684,7 +2688,7 @@ void rs_group_destroy(rs_group* g) {
   if (g->b && g->b->stream) (void)hipStreamSynchronize(g->b->stream);
   for (void* q : {(void*)g->d_in, (void*)g->d_out, (void*)g->d_count, (void*)g->d_img, (void*)g->d_prb, (void*)g->d_out2, (void*)g->d_chk,
                   (void*)g->pair[0].d_stores_chk, (void*)g->pair[1].d_stores_chk, (void*)g->pair[2].d_stores_chk, (void*)g->pair[3].d_stores_chk,
-                  (void*)g->pair[4].d_stores_chk, (void*)g->d_sent2, (void*)g->d_ravg,
+                  (void*)g->pair[4].d_stores_chk, (void*)g->pair[5].d_stores_chk, (void*)g->d_sent2, (void*)g->d_ravg,
                   (void*)g->d_rpend, (void*)g->d_rlast, (void*)g->d_rgather, (void*)g->d_ruid, (void*)g->d_qavg, (void*)g->d_qpend,
                   (void*)g->d_qdata, (void*)g->d_qhas, (void*)g->d_qin, (void*)g->d_cbytes, (void*)g->d_crbs, (void*)g->d_sent})
     if (q) (void)hipFree(q);
@@ -3136,7 +3140,8 @@ bool group_alloc_sent_twin(rs_group* g) {
   return true;
 }
 
-/* A checked call: the form's built-in kernel first, on the same slots and the same state, its outputs into slots of its own.  What it
+/* A checked call -- one call, or one whole run --: the form's built-in kernel first, on the same slots and the same state, its outputs
+ * into slots of its own.  What it
  * left is kept, what it found is put back: the run-time build starts from the same state.  (A mode-1 slot: BOTH kernels transpose the
  * slot's block and store the cell's image and per-PRB copy -- the same bytes when the build is right; a wrong image shows in the
  * checked calls that read it.) */
@@ -3159,7 +3164,7 @@ int group_run_twin(rs_group* g, const GroupCall& c, const RsLaunch& L) {
     Lb.grp_sent = g->z_sent2 ? g->z_sent2 : g->d_sent2;
   }
   HIP_TRY(f.launch(&Lb, b->threads, st));
-  HIP_TRY(hipMemcpyAsync(g->h_out2.data(), g->d_out2, (size_t)c.n * g->out_stride, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(g->h_out2.data(), g->d_out2, (size_t)c.n * c.ttis() * g->out_stride, hipMemcpyDeviceToHost, st)); /* (a run: slots x TTIs) */
   if ((f.sets & kSetSent) && !g->z_sent2) HIP_TRY(hipMemcpyAsync(g->h_sent2, g->d_sent2, 8 * (size_t)c.n * b->U, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(after, b->d_sstate, ss_all, hipMemcpyDeviceToDevice, st));
   HIP_TRY(hipMemcpyAsync(b->d_sstate, before, ss_all, hipMemcpyDeviceToDevice, st));
@@ -3189,15 +3194,13 @@ int group_run(rs_group* g, GroupCall& c, RsLaunch& L) {
     L.done_flag = (uint32_t*)(g->z_out + g->flag_off);
     L.done_seq = g->seq;
   }
-  if (f.pair >= 0) { /* (a run has no pair: the built-in kernel serves it) */
-    const rs_group::GroupPair& p = g->pair[f.pair];
-    /* (a flows call always carries the data_to_transmit gate: its lean build keeps it) */
-    const bool gate_free = c.form == kGroupFlows || !c.has_gate;
-    const bool lean = p.jit[1] && !c.has_prb && !L.queue_mode && gate_free && !L.exact_scan && !L.gen_exp && !c.want_upper && !L.synthetic;
-    c.which = lean ? 1 : 0;
-    c.kd = p.jit[c.which];
-    c.checked = c.kd != nullptr && p.chk_left[c.which] > 0;
-  }
+  const rs_group::GroupPair& p = g->pair[f.pair];
+  /* (a flows call always carries the data_to_transmit gate: its lean build keeps it) */
+  const bool gate_free = c.form == kGroupFlows || !c.has_gate;
+  const bool lean = p.jit[1] && !c.has_prb && !L.queue_mode && gate_free && !L.exact_scan && !L.gen_exp && !c.want_upper && !L.synthetic;
+  c.which = lean ? 1 : 0;
+  c.kd = p.jit[c.which];
+  c.checked = c.kd != nullptr && p.chk_left[c.which] > 0;
   if (c.checked) {
     const int rc = group_run_twin(g, c, L);
     if (rc) return rc;
@@ -3274,7 +3277,7 @@ int group_drop_pair(rs_group* g, const GroupCall& c, const char* what) {
   }
   p.dropped = true;
   g->last_call_jit = false;
-  memcpy(g->h_out, g->h_out2.data(), (size_t)c.n * g->out_stride);
+  memcpy(g->h_out, g->h_out2.data(), (size_t)c.n * c.ttis() * g->out_stride);
   if (f.sets & kSetSent) memcpy(g->h_sent, g->h_sent2, 8 * (size_t)c.n * b->U); /* (the built-in kernel's sent rows: what group_unpack hands out) */
   HIP_TRY(hipMemcpy(b->d_sstate, g->d_chk + group_chk_half(g), 8 * (size_t)b->S * g->n_cells, hipMemcpyDeviceToDevice));
   if (f.store_width) {
@@ -3299,9 +3302,11 @@ int group_check(rs_group* g, const GroupCall& c) {
   char what[240] = "";
   for (int k = 0; k < c.n && !what[0]; k++) {
     const int cell = c.cell(k);
-    const size_t at = (size_t)k * g->out_stride;
-    if (!g->empty_slot[k]) /* (an update-only slot: its workgroup wrote no output, the state alone is compared) */
-      compare_out_block(g->h_out + at, g->h_out2.data() + at, g->packs[k].l, b->R, b->S, c.in[k].n_users, c.want_upper, cell, what, sizeof what);
+    /* (an update-only slot: its workgroup wrote no output, the state alone is compared; a run: every TTI's block of the slot) */
+    for (int t = 0; t < c.ttis() && !g->empty_slot[k] && !what[0]; t++) {
+      const size_t at = c.at(k, t) * g->out_stride;
+      compare_out_block(g->h_out + at, g->h_out2.data() + at, g->packs[k].l, b->R, b->S, c.in[k].n_users, c.want_upper, cell, what, sizeof what, c.run ? t : -1);
+    }
     for (int i = 0; i < b->S && !what[0]; i++) {
       const double a = ss_jit[(size_t)cell * b->S + i], r = ss_ref[(size_t)cell * b->S + i];
       if (to_bits(a) != to_bits(r)) snprintf(what, sizeof what, "cell %d: slice state[%d] = %a, the built-in kernel's %a", cell, i, a, r);
@@ -3387,17 +3392,25 @@ void group_unpack(const rs_group* g, const GroupCall& c) {
 int group_grow_out(rs_group* g, size_t slots) {
   if (slots <= g->out_slots) return RS_OK;
   const size_t flag_off = g->out_stride * slots, bytes = flag_off + 64;
-  uint8_t *d = nullptr, *h = nullptr;
+  uint8_t *d = nullptr, *h = nullptr, *d2 = nullptr;
   void* z = nullptr;
   bool ok = hipMalloc(&d, bytes) == hipSuccess && hipHostMalloc((void**)&h, bytes, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
   if (ok && g->z_out) ok = hipHostGetDevicePointer(&z, h, 0) == hipSuccess;
+  /* (the self-check's twin output slots, once a pair has made them: a checked run writes slots x TTIs of them too) */
+  if (ok && g->d_out2) ok = hipMalloc(&d2, flag_off) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
     if (d) (void)hipFree(d);
     if (h) (void)hipHostFree(h);
+    if (d2) (void)hipFree(d2);
     return fail(RS_ERR_HIP, "allocation of the run's output blocks failed (%zu bytes each)", bytes);
   }
   memset(h, 0, bytes);
+  if (d2) {
+    (void)hipFree(g->d_out2);
+    g->d_out2 = d2;
+    g->h_out2.assign(flag_off, 0);
+  }
   (void)hipFree(g->d_out);
   (void)hipHostFree(g->h_out);
   g->d_out = d;
@@ -3780,7 +3793,8 @@ const char* rs_group_kernel_name(rs_group* g) {
  * (rs_group::GroupPair), each an option of its own: rs_group_specialize (entry point rs_group_kernel_jit, serves rs_group_schedule_tti),
  * rs_group_specialize_resident (rs_group_resident_kernel_jit, serves rs_group_schedule_tti_at), rs_group_specialize_queued
  * (rs_group_queued_kernel_jit, serves rs_group_schedule_tti_queued), rs_group_specialize_counted (rs_group_counted_kernel_jit, serves
- * rs_group_schedule_tti_counted) and rs_group_specialize_flows (rs_group_flows_kernel_jit, serves rs_group_schedule_tti_flows).  Between
+ * rs_group_schedule_tti_counted) and rs_group_specialize_flows (rs_group_flows_kernel_jit, serves rs_group_schedule_tti_flows); a sixth,
+ * rs_group_specialize_run (rs_group_run_kernel_jit), serves the runs of the resident form (rs_group_run_at).  Between
  * calls at any time: slice state, CQI images, per-PRB stores, resident stores, bearer stores and counters are not touched. */
 namespace {
 /* kind: a row of kGroupForms -- the call the pair serves */
@@ -3796,10 +3810,14 @@ int group_specialize_pair(rs_group* g, int kind) {
     return fail(RS_ERR_INVALID, "scheduler %d has no counted form (rs_group_set_counters): nothing for rs_group_specialize_counted to build", b->sched);
   if (kind == kGroupFlows && b->sched != RS_SCHED_PF)
     return fail(RS_ERR_INVALID, "scheduler %d has no flows form (rs_group_set_flows): nothing for rs_group_specialize_flows to build", b->sched);
+  if (kind == kGroupRun && (b->sched == RS_SCHED_NVS || b->sched == RS_SCHED_NVS_NONGREEDY))
+    return fail(RS_ERR_INVALID, "scheduler %d is not served by a run (rs_group_run_at): nothing for rs_group_specialize_run to build", b->sched);
+  if (kind == kGroupRun && b->any_alpha)
+    return fail(RS_ERR_INVALID, "a config with a customised slice (algo_alpha != 0) is not served by a run (rs_group_run_at): nothing for rs_group_specialize_run to build");
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   p.wanted = true;
   if (!g->d_out2) {
-    const size_t out_bytes = g->out_stride * (size_t)g->n_cells;
+    const size_t out_bytes = g->out_stride * g->out_slots; /* (as many slots as d_out holds: the largest run so far) */
     if (hipMalloc(&g->d_out2, out_bytes) != hipSuccess || hipMalloc(&g->d_chk, 2 * group_chk_half(g)) != hipSuccess) {
       (void)hipGetLastError();
       if (g->d_out2) (void)hipFree(g->d_out2);
@@ -3900,6 +3918,16 @@ int rs_group_specialize_flows(rs_group* g) {
 int rs_group_flows_jit_status(rs_group* g, char* msg, size_t msglen) {
   if (!g) return fail(RS_ERR_INVALID, "null group");
   return group_jit_pair_status(g, kGroupFlows, msg, msglen);
+}
+
+int rs_group_specialize_run(rs_group* g) {
+  if (!g) return fail(RS_ERR_INVALID, "null group");
+  return group_specialize_pair(g, kGroupRun);
+}
+
+int rs_group_run_jit_status(rs_group* g, char* msg, size_t msglen) {
+  if (!g) return fail(RS_ERR_INVALID, "null group");
+  return group_jit_pair_status(g, kGroupRun, msg, msglen);
 }
 
 /* ---- the reference's CQI trace files (include/radiosaber_hip.h) ---- */

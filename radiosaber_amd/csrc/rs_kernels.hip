@@ -832,7 +832,7 @@ __global__ void __launch_bounds__(512, 4) rs_group_flows_kernel(RsLaunch p) {
 /* ... and the resident form's run (rs_group_run_at): T consecutive TTIs of every named cell in one launch -- the resident form's update,
  * body and credit T times per workgroup, the clock and the rand() pair of each TTI from the slot's table, one completion behind the last
  * TTI.  Kernels of their own, the resident form's shapes without NVS (rs_launch_group_run): the resident kernels above carry none of it.
- * Built in only: a group's run-time builds do not serve runs. */
+ * A group's run-time builds of this form are rs_group_run_kernel_jit below. */
 template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_run_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
@@ -865,12 +865,16 @@ __global__ void __launch_bounds__(512, 4) rs_group_run_kernel(RsLaunch p) {
 #ifndef RS_JIT_GROUP_FLOWS
 #define RS_JIT_GROUP_FLOWS 0 /* 1, with RS_JIT_GROUP, scheduler 1 and none of the three above: the group's build of the flows form (rs_group_specialize_flows) */
 #endif
+#ifndef RS_JIT_GROUP_RUN
+#define RS_JIT_GROUP_RUN 0 /* 1, with RS_JIT_GROUP and RS_JIT_GROUP_RESIDENT, never scheduler 7: the group's build of the resident form's run (rs_group_specialize_run) */
+#endif
 #if RS_JIT_GROUP
-/* five entry points, one per option list: rs_group_kernel_jit, rs_group_resident_kernel_jit for the calls that keep the cells' PF
+/* six entry points, one per option list: rs_group_kernel_jit, rs_group_resident_kernel_jit for the calls that keep the cells' PF
  * averages on the device (rs_group_schedule_tti_at), rs_group_queued_kernel_jit for the calls that keep both bearers there
  * (rs_group_schedule_tti_queued), rs_group_counted_kernel_jit for those that keep the bearers' counters too
- * (rs_group_schedule_tti_counted: the queued text with kGrpCnt) and rs_group_flows_kernel_jit for scheduler 1's flows
- * (rs_group_schedule_tti_flows).  Same text but for the name and kGrpRes, kGrpQue, kGrpCnt, kGrpFlow; each has a general and a lean form. */
+ * (rs_group_schedule_tti_counted: the queued text with kGrpCnt), rs_group_flows_kernel_jit for scheduler 1's flows
+ * (rs_group_schedule_tti_flows) and rs_group_run_kernel_jit for the runs of the resident form (rs_group_run_at: the resident text T
+ * times per workgroup).  Same text but for the name and kGrpRes, kGrpQue, kGrpCnt, kGrpFlow, kGrpRun; each has a general and a lean form. */
 #if RS_JIT_GROUP_RESIDENT && RS_JIT_GROUP_QUEUED
 #error "RS_JIT_GROUP_RESIDENT and RS_JIT_GROUP_QUEUED exclude each other"
 #endif
@@ -883,7 +887,18 @@ __global__ void __launch_bounds__(512, 4) rs_group_run_kernel(RsLaunch p) {
 #if RS_JIT_GROUP_FLOWS && RS_JIT_SCHED != 1
 #error "RS_JIT_GROUP_FLOWS: the flows form is scheduler 1's"
 #endif
-#if RS_JIT_GROUP_RESIDENT
+#if RS_JIT_GROUP_RUN && !RS_JIT_GROUP_RESIDENT
+#error "RS_JIT_GROUP_RUN needs RS_JIT_GROUP_RESIDENT: the run form is the resident form's"
+#endif
+#if RS_JIT_GROUP_RUN && (RS_JIT_GROUP_QUEUED || RS_JIT_GROUP_COUNTED || RS_JIT_GROUP_FLOWS)
+#error "RS_JIT_GROUP_RUN is never combined with RS_JIT_GROUP_QUEUED, RS_JIT_GROUP_COUNTED or RS_JIT_GROUP_FLOWS"
+#endif
+#if RS_JIT_GROUP_RUN && RS_JIT_SCHED == 7
+#error "RS_JIT_GROUP_RUN: scheduler 7 has no run form (the host picks the served slice per TTI)"
+#endif
+#if RS_JIT_GROUP_RUN
+#define RS_GROUP_JIT_ENTRY rs_group_run_kernel_jit
+#elif RS_JIT_GROUP_RESIDENT
 #define RS_GROUP_JIT_ENTRY rs_group_resident_kernel_jit
 #elif RS_JIT_GROUP_COUNTED
 #define RS_GROUP_JIT_ENTRY rs_group_counted_kernel_jit
@@ -916,7 +931,7 @@ extern "C" __global__ void __launch_bounds__(RS_JIT_NT, RS_JIT_WPE) RS_GROUP_JIT
   __shared__ __align__(16) unsigned char lds[kCv.lds_bytes];
   constexpr int kGrpSched = RS_JIT_SCHED, kGrpEpt = (RS_JIT_SCHED != 9 && RS_JIT_SCHED != 10) ? 0 : (kCv.ept <= 4 ? kCv.ept : 0);
   constexpr bool kGrpFixed = true, kGrpRes = RS_JIT_GROUP_RESIDENT != 0, kGrpQue = RS_JIT_GROUP_QUEUED != 0 || RS_JIT_GROUP_COUNTED != 0,
-                 kGrpCnt = RS_JIT_GROUP_COUNTED != 0, kGrpFlow = RS_JIT_GROUP_FLOWS != 0, kGrpRun = false;
+                 kGrpCnt = RS_JIT_GROUP_COUNTED != 0, kGrpFlow = RS_JIT_GROUP_FLOWS != 0, kGrpRun = RS_JIT_GROUP_RUN != 0;
 #include "rs_phase_group.inc"
 }
 #undef RS_GROUP_JIT_ENTRY

@@ -55,17 +55,20 @@
  * stores are 2 * RS_JIT_U, the loop strides RS_JIT_NT, the LDS offsets the constexpr carve's off_tx and off_misc, the PRBs per RBG
  * RS_JIT_G.  Order of operations and arithmetic are the same in both forms.
  *
- * A ninth constant, kGrpRun, makes the run form of the resident wrapper (rs_group_run_at, rs_group_run_kernel; only with kGrpRes, built
- * in only): the workgroup serves T consecutive TTIs of its cell -- the resident form's three steps, T times, in their order and
+ * A ninth constant, kGrpRun, makes the run form of the resident wrapper (rs_group_run_at, rs_group_run_kernel; only with kGrpRes, never
+ * NVS): the workgroup serves T consecutive TTIs of its cell -- the resident form's three steps, T times, in their order and
  * arithmetic, then the completion chain once.  The header is read once; what changes per TTI -- the clock and the rand() pair --
  * comes from the slot's table (RsGroupCell::run_table), output block t lies run_out_step bytes behind block t - 1, and the users are
  * the slot's for the whole run.  TTI 0 does with the CQI reports what the slot's image_mode says; under a cqi_epoch the later TTIs
  * load the cell's image (and read the cell's per-PRB store) as calls of their own would, without one they read the slot's blocks
  * again.  Between two TTIs stands one workgroup barrier behind a device-scope fence: the credit of TTI t goes by call position, the
  * update of TTI t + 1 by user id -- other threads --, and the body's load phase overwrites the LDS grants the credit reads.  A text
- * of its own below: with kGrpRun false none of it reaches the other instantiations, whose resident text is left as it is. */
+ * of its own below: with kGrpRun false none of it reaches the other instantiations, whose resident text is left as it is.  Under
+ * kGrpFixed (rs_group_run_kernel_jit, rs_group_specialize_run) the run text's shape is constant as the resident text's: the update's
+ * range and the stores' stride are RS_JIT_U, the loop strides RS_JIT_NT, the grants' LDS offset the constexpr carve's off_tx; under
+ * kGrpLean the slots' HoL delays and priority flags are not read.  Order of operations and arithmetic are the same in both forms. */
   static_assert(!kGrpCnt || kGrpQue, "the counted form is the queued form's");
-  static_assert(!kGrpRun || (kGrpRes && !kGrpFixed && !kGrpLean && kGrpSched != 7), "the run form is the resident form's, built in, and never NVS");
+  static_assert(!kGrpRun || (kGrpRes && kGrpSched != 7), "the run form is the resident form's, and never NVS");
   static_assert(!kGrpFlow || (!kGrpRes && !kGrpQue && !kGrpCnt && kGrpSched == 1), "the flows form is scheduler 1's, a resident form of its own");
   const uint8_t* const in = p.grp_in + (size_t)blockIdx.x * (size_t)p.grp_in_stride;
   uint8_t* const out = p.grp_out + (size_t)blockIdx.x * (size_t)p.grp_out_stride;
@@ -120,9 +123,9 @@
   unsigned long long grp_res_cycles = 0;
 #endif
   if constexpr (kGrpRun) {
-    /* (shape and carve: the launch block's -- a run is served by the built-in kernels alone) */
-    const int nthreads = (int)blockDim.x;
-    const int n_all = p.U; /* the config's users: the stores' stride and the update's range */
+    /* (shape and carve: the launch block's in the built-in kernels, the constants RS_JIT_* in a group's run-time build) */
+    const int nthreads = kGrpFixed ? RS_JIT_NT : (int)blockDim.x;
+    const int n_all = kGrpFixed ? RS_JIT_U : p.U; /* the config's users: the stores' stride and the update's range */
     double* const r_avg = p.grp_avg + (size_t)cell * (size_t)n_all;
     int32_t* const r_pend = p.grp_pending + (size_t)cell * (size_t)n_all;
     auto dword = [&](const double* d) { return __hiloint2double(word((const int32_t*)d + 1), word((const int32_t*)d)); };
@@ -133,7 +136,12 @@
     const int32_t* const uid = (const int32_t*)(data + in_uid);
     double* const row = p.grp_gather + (size_t)cell * (size_t)n_all;
     int32_t* const ids = p.grp_uid + (size_t)cell * (size_t)n_all;
-    const int32_t* const granted = (const int32_t*)(lds + p.off_tx);
+    constexpr RsCarve kGrpCv = rs_carve(RS_JIT_S, RS_JIT_U, RS_JIT_R, RS_JIT_SCHED, RS_JIT_NT, RS_JIT_CARVEQ, RS_JIT_WIN); /* (the body's own carve) */
+    const int32_t* const granted = (const int32_t*)(lds + (kGrpFixed ? kGrpCv.off_tx : p.off_tx));
+    if constexpr (kGrpLean) { /* (the lean build: as behind the other forms' preambles -- here the body is called inside the loop) */
+      q.hol = nullptr;
+      q.prio = nullptr;
+    }
     /* (the cell's last-update time rides in a register: every thread reads the word here, thread 0 writes it behind the loop, whose
      * barriers lie between the two) */
     double last = dword(p.grp_last + cell);
@@ -181,7 +189,14 @@
       /* 3. the grants, from LDS, by call position: the resident form's step 3 */
       for (int i = threadIdx.x; i < q.U; i += nthreads) {
         const int bytes = granted[i];
+#if defined(RS_FAULT_INJECT_RUN)
+        /* tests only (tests/test_gpu_group_run_specialize.py): a deliberately wrong run-time build of the RUN form -- in the LAST TTI of
+         * a run every served user is credited a byte more; the outputs of all T TTIs stay right, so only the self-check's comparison
+         * of the resident stores can catch it.  A value, no address or index, and never T; the twin of RS_FAULT_INJECT_RESIDENT. */
+        if (bytes != 0) r_pend[in_uid != 0 ? ids[i] : i] += bytes + ((kGrpFixed && t + 1 == n_run) ? 1 : 0);
+#else
         if (bytes != 0) r_pend[in_uid != 0 ? ids[i] : i] += bytes;
+#endif
       }
       if (t + 1 < n_run) {
         /* (wave-uniform: n_run is a header word.)  The next TTI: its output block; under a cqi_epoch the image that TTI 0 stored or

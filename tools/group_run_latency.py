@@ -1,15 +1,17 @@
 #!/usr/bin/env python3
 """us per cell-TTI of a backlogged K-cell host between two CQI reports: (a) 40 rs_group_schedule_tti_at calls against (b) one
-rs_group_run_at of 40 (profiles/group_run.md).
+rs_group_run_at of 40 (profiles/group_run.md), or (b) against (c) the same run on the group's own run-time builds of the run kernel
+(rs_group_specialize_run; profiles/group_run_specialize.md).
 
-    RS_DROPIN_TIMING=1 python tools/group_run_latency.py [--blocks 20] [--ttis 40]
+    RS_DROPIN_TIMING=1 python tools/group_run_latency.py [--blocks 20] [--ttis 40] [--modes ab | bc]
 
 Workloads: 8, 27 and 64 cells; 500 users x 25 RBGs and 100 users x 64 RBGs; scheduler 9; resident averages; cqi_epoch on, a new number
 (the same reports) every block of 40 TTIs, so that the first TTI of a block stores the cells' images and the other 39 are image hits.
 Both modes run in this process on the same library, on a group each, and alternate: a, b, a, b, a, b -- three repeats per mode; a gain
-holds when (b)'s worst repeat lies below (a)'s best.  The arguments are marshalled once, outside the timed region: the time is that of
+holds when the second mode's worst repeat lies below the first mode's best.  Mode (c) warms up until the self-check of the build that
+serves its runs has finished (RS_DROPIN_SELFCHECK_CALLS checked runs, default 8): no timed run is a checked one.  The arguments are marshalled once, outside the timed region: the time is that of
 the library calls alone.  RS_DROPIN_TIMING=1 makes the library print its own prepare / enqueue / wait / unpack split per group on stderr
-when the group is closed ((a) first, then (b); per CALL: a call of (b) is 40 TTIs)."""
+when the group is closed (in the order of --modes; per CALL: a call of (b) or (c) is 40 TTIs)."""
 import argparse
 import ctypes as C
 import os
@@ -28,8 +30,11 @@ ap.add_argument("--blocks", type=int, default=20, help="blocks of --ttis TTIs pe
 ap.add_argument("--warmup", type=int, default=3, help="blocks before the first timed one")
 ap.add_argument("--ttis", type=int, default=40, help="TTIs between two report renewals (CQI_INTERVAL)")
 ap.add_argument("--cells", type=int, nargs="*", default=[8, 27, 64])
+ap.add_argument("--modes", choices=["ab", "bc"], default="ab", help="ab: 40 at-calls against one run; bc: the run on the built-in kernel against the run on the group's own builds")
 args = ap.parse_args()
 T = args.ttis
+M0, M1 = args.modes
+NAMES = {"a": f"{T} at-calls", "b": f"one run of {T}", "c": f"one specialised run of {T}"}
 
 
 def marshal(sc, R, G, K, n_out, cqi):
@@ -53,8 +58,8 @@ for ues, R, G in ((25, 25, 4), (5, 64, 8)):
         avg = [rng.uniform(1e4, 1e6, U) for _ in range(K)]
         rands = np.ascontiguousarray(rng.integers(0, 2**31 - 1, (K, T, 2)).astype(np.int32))
         groups = {}
-        for mode in "ab":
-            g = rs.GroupScheduler(sc, R, G, K, sched=9)
+        for mode in args.modes:
+            g = rs.GroupScheduler(sc, R, G, K, sched=9, jit_run=mode == "c")
             for k in range(K):
                 g.set_avg(k, avg[k], 0.1)
             groups[mode] = [g, marshal(sc, R, G, K, 1 if mode == "a" else T, cqi), 0.1, 0]   # group, arguments, clock, blocks done
@@ -78,21 +83,28 @@ for ues, R, G in ((25, 25, 4), (5, 64, 8)):
                 _check(L.rs_group_run_at(g._h, K, None, ins, T, t.ctypes.data_as(C.POINTER(C.c_double)), rands.ctypes.data_as(C.POINTER(C.c_int32)), outs))
             groups[mode][2], groups[mode][3] = now, done + 1
 
-        for mode in "ab":
+        for mode in args.modes:
             for _ in range(args.warmup):
                 block(mode)
-        us = {"a": [], "b": []}
+        if "c" in groups:   # (the plain run is served by the lean build: its checked runs end here)
+            for _ in range(64):
+                if "to go" not in groups["c"][0].run_jit_status()[1].split("lean build:")[-1]:
+                    break
+                block("c")
+            code, msg = groups["c"][0].run_jit_status()
+            assert code == 1 and "to go" not in msg.split("lean build:")[-1] and groups["c"][0].kernel_name == "rs_group_run_kernel_jit", (code, msg)
+        us = {M0: [], M1: []}
         for rep in range(3):
-            for mode in "ab":
+            for mode in args.modes:
                 t0 = time.perf_counter()
                 for _ in range(args.blocks):
                     block(mode)
                 us[mode].append((time.perf_counter() - t0) / (args.blocks * T * K) * 1e6)
-        verdict = "holds" if max(us["b"]) < min(us["a"]) else "does not hold"
-        print(f"{K:3d} cells x {U} UEs x {R} RBGs: (a) {T} at-calls " + " / ".join(f"{x:.3f}" for x in us["a"]) + f"; (b) one run of {T} "
-              + " / ".join(f"{x:.3f}" for x in us["b"]) + f" us per cell-TTI; the gain {verdict}; launches {groups['a'][0].launch_count} / "
-              f"{groups['b'][0].launch_count}, {groups['b'][0].kernel_name}", flush=True)
-        for mode in "ab":
+        verdict = "holds" if max(us[M1]) < min(us[M0]) else "does not hold"
+        print(f"{K:3d} cells x {U} UEs x {R} RBGs: ({M0}) {NAMES[M0]} " + " / ".join(f"{x:.3f}" for x in us[M0]) + f"; ({M1}) {NAMES[M1]} "
+              + " / ".join(f"{x:.3f}" for x in us[M1]) + f" us per cell-TTI; the gain {verdict}; launches {groups[M0][0].launch_count} / "
+              f"{groups[M1][0].launch_count}, {groups[M1][0].kernel_name}", flush=True)
+        for mode in args.modes:
             sys.stderr.write(f"-- {K} cells x {U} UEs x {R} RBGs, mode ({mode}):\n")
             sys.stderr.flush()
             groups[mode][0].close()
