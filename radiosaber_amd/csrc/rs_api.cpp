@@ -2500,52 +2500,39 @@ struct rs_group {
   /* rs_group_kernel_name: the last call's form (a row of kGroupForms), whether a run-time build served it, the built-in kernels' names by row */
   int last_call_form = 0;
   bool last_call_jit = false;
-  char kname[6][56] = {"", "", "", "", "", ""};
+  char kname[RS_GROUP_FORMS][56] = {"", "", "", "", "", ""}, kname_jit[RS_GROUP_FORMS][40] = {"", "", "", "", "", ""};
 };
 
-extern "C" hipError_t rs_launch_group(const RsLaunch* p, int threads, hipStream_t stream);
-extern "C" hipError_t rs_launch_group_resident(const RsLaunch* p, int threads, hipStream_t stream);
-extern "C" hipError_t rs_launch_group_queued(const RsLaunch* p, int threads, hipStream_t stream);
-extern "C" hipError_t rs_launch_group_counted(const RsLaunch* p, int threads, hipStream_t stream);
-extern "C" hipError_t rs_launch_group_flows(const RsLaunch* p, int threads, hipStream_t stream);
-extern "C" hipError_t rs_launch_group_run(const RsLaunch* p, int threads, hipStream_t stream);
+extern "C" hipError_t rs_launch_group(const RsLaunch* p, int threads, int form, hipStream_t stream);
 
 namespace {
-/* The forms of a group call, one row each: what differs between them outside the validation of their inputs.  A call's row is its
- * form, the counted twin of the queued form (rs_group_schedule_tti_counted) has the fifth, a run of the resident form (rs_group_run_at) the
- * sixth. */
-enum { kGroupPlain = 0, kGroupResident = 1, kGroupQueued = 2, kGroupFlows = 3, kGroupCounted = 4, kGroupRun = 5 };
-enum : unsigned { /* the RsLaunch pointer sets a form's kernel reads */
-  kSetResident = 1, /* grp_avg, grp_pending, grp_last, grp_gather, grp_uid */
-  kSetBearers = 2,  /* grp_qavg, grp_qpend, grp_qhas, grp_qdata and the slots' word block grp_qin (data words; a flows call: bearer words) */
-  kSetCounters = 4, /* grp_cbytes, grp_crbs */
-  kSetSent = 8,     /* grp_sent: the slots' sent rows */
-};
+/* The forms of a group call, one row each: what the HOST alone knows of a form.  What a form is -- the facts its kernels read, the
+ * launch-block pointers they dereference, the flags and names of its run-time builds, the schedulers it exists for -- is its row of
+ * rs_group_form (rs_device.h, the same row order); a call's row is its form. */
+enum { kGroupPlain = RS_GROUP_PLAIN, kGroupResident = RS_GROUP_RESIDENT, kGroupQueued = RS_GROUP_QUEUED, kGroupFlows = RS_GROUP_FLOWS,
+       kGroupCounted = RS_GROUP_COUNTED, kGroupRun = RS_GROUP_RUN };
 struct GroupForm {
-  hipError_t (*launch)(const RsLaunch*, int, hipStream_t); /* the built-in launcher */
-  unsigned sets;
   bool slots0;     /* update-only slots (n_users == 0) are allowed */
   int pair;        /* rs_group::pair[] that serves the form */
   int store_width; /* the stores its self-check saves, restores and compares: 0 none, 1 the resident stores [U], 2 the bearer stores [U][2]
-                    * (a form with kSetCounters: the counter stores [U][2] too; with kSetSent: the slots' sent rows are compared as well) */
-  int jit_flags;   /* rs_jit_get: 1 one-TTI form, 8 group wrapper, 16 resident, 32 queued, 64 counted, 128 flows, 256 run */
-  const char* jit_name;
+                    * (a form with RS_GROUP_SET_COUNTERS: the counter stores [U][2] too; with RS_GROUP_SET_SENT: the slots' sent rows are compared as well) */
   /* the nouns of the pair's messages: "specialised <adj>%s build", "both <adj>builds are dropped, <serves>", "agreed with <ref>",
    * "copies of the <stores>" */
   const char *adj, *serves, *ref, *stores;
+  unsigned sets() const { return rs_group_form(pair).sets; } /* (every form has a pair of its own: its row) */
 };
-const GroupForm kGroupForms[6] = {
-    {rs_launch_group, 0, false, kGroupPlain, 0, 1 | 8, "rs_group_kernel_jit", "", "the built-in kernels serve this group", "the built-in kernel field by field", ""},
-    {rs_launch_group_resident, kSetResident, false, kGroupResident, 1, 1 | 8 | 16, "rs_group_resident_kernel_jit", "resident ",
+const GroupForm kGroupForms[RS_GROUP_FORMS] = {
+    {false, kGroupPlain, 0, "", "the built-in kernels serve this group", "the built-in kernel field by field", ""},
+    {false, kGroupResident, 1, "resident ",
      "the built-in resident kernel serves this group's resident calls", "the built-in resident kernel field by field, resident stores included", "resident stores"},
-    {rs_launch_group_queued, kSetResident | kSetBearers, true, kGroupQueued, 2, 1 | 8 | 32, "rs_group_queued_kernel_jit", "queued ",
+    {true, kGroupQueued, 2, "queued ",
      "the built-in queued kernel serves this group's queued calls", "the built-in queued kernel field by field, bearer stores included", "bearer stores"},
-    {rs_launch_group_flows, kSetResident | kSetBearers | kSetCounters, true, kGroupFlows, 2, 1 | 8 | 128, "rs_group_flows_kernel_jit", "flows ",
+    {true, kGroupFlows, 2, "flows ",
      "the built-in flows kernel serves this group's flows calls", "the built-in flows kernel field by field, bearer stores and counters included", "bearer stores and counters"},
-    {rs_launch_group_counted, kSetResident | kSetBearers | kSetCounters | kSetSent, true, kGroupCounted, 2, 1 | 8 | 32 | 64, "rs_group_counted_kernel_jit", "counted ",
+    {true, kGroupCounted, 2, "counted ",
      "the built-in counted kernel serves this group's counted calls", "the built-in counted kernel field by field, bearer stores, counters and sent rows included",
      "bearer stores and counters"},
-    {rs_launch_group_run, kSetResident, false, kGroupRun, 1, 1 | 8 | 16 | 256, "rs_group_run_kernel_jit", "run ",
+    {false, kGroupRun, 1, "run ",
      "the built-in run kernel serves this group's runs", "the built-in run kernel field by field over every TTI, resident stores included", "resident stores"},
 };
 
@@ -2568,7 +2555,7 @@ struct GroupStore {
 };
 struct GroupStores {
   GroupStore part[5];
-  int n;       /* 0, 3, or 5: a form that keeps counters (kSetCounters) has m_cumulateBytes / m_cumulateRBs behind the other three */
+  int n;       /* 0, 3, or 5: a form that keeps counters (RS_GROUP_SET_COUNTERS) has m_cumulateBytes / m_cumulateRBs behind the other three */
   size_t half; /* bytes of one half of the check block */
 };
 GroupStores group_stores(const rs_group* g, const GroupForm& f) {
@@ -2577,7 +2564,7 @@ GroupStores group_stores(const rs_group* g, const GroupForm& f) {
   const size_t e = (size_t)f.store_width * g->b->U;
   GroupStores s = {{{two ? g->d_qavg : g->d_ravg, e, kStoreF64, "avg"}, {g->d_rlast, 1, kStoreF64, "last_update"},
                     {two ? (void*)g->d_qpend : (void*)g->d_rpend, e, kStoreI32, "pending_bytes"},
-                    {g->d_cbytes, e, kStoreI64, "cum_bytes"}, {g->d_crbs, e, kStoreI64, "cum_rbs"}}, (f.sets & kSetCounters) ? 5 : 3, 0};
+                    {g->d_cbytes, e, kStoreI64, "cum_bytes"}, {g->d_crbs, e, kStoreI64, "cum_rbs"}}, (f.sets() & RS_GROUP_SET_COUNTERS) ? 5 : 3, 0};
   for (int i = 0; i < s.n; i++) s.half += s.part[i].kept(g);
   return s;
 }
@@ -2663,13 +2650,11 @@ rs_group* rs_group_create(const rs_config* cfg, int32_t n_cells) {
   g->img.resize(n_cells);
   g->modes.assign(n_cells, 0);
   const int ept = (b->R * b->S + b->threads - 1) / b->threads;
-  const bool sorts = b->sched == RS_SCHED_MAXCELL || b->sched == RS_SCHED_UPPERBOUND;
-  snprintf(g->kname[kGroupPlain], sizeof g->kname[0], "rs_group_kernel<%d, %d>", b->sched, sorts && ept <= 4 ? ept : 0);
-  snprintf(g->kname[kGroupResident], sizeof g->kname[0], "rs_group_resident_kernel<%d, %d>", b->sched, sorts && ept <= 4 ? ept : 0);
-  snprintf(g->kname[kGroupQueued], sizeof g->kname[0], "rs_group_queued_kernel<%d, %d>", b->sched, b->sched == RS_SCHED_MAXCELL && ept <= 4 ? ept : 0);
-  snprintf(g->kname[kGroupCounted], sizeof g->kname[0], "rs_group_counted_kernel<%d, %d>", b->sched, b->sched == RS_SCHED_MAXCELL && ept <= 4 ? ept : 0);
-  snprintf(g->kname[kGroupFlows], sizeof g->kname[0], "rs_group_flows_kernel<%d, 0>", b->sched);
-  snprintf(g->kname[kGroupRun], sizeof g->kname[0], "rs_group_run_kernel<%d, %d>", b->sched, sorts && ept <= 4 ? ept : 0);
+  for (int row = 0; row < RS_GROUP_FORMS; row++) { /* (a form without a kernel for the scheduler is never called: its name says <sched, 0>) */
+    const int e = rs_group_form_serves(row, b->sched) ? rs_group_form_ept(b->sched, ept) : 0;
+    snprintf(g->kname[row], sizeof g->kname[0], "%s<%d, %d>", rs_group_form(row).stem, b->sched, e > 0 ? e : 0);
+    snprintf(g->kname_jit[row], sizeof g->kname_jit[0], "%s_jit", rs_group_form(row).stem);
+  }
   g->empty_slot.assign(n_cells, 0);
   g->resident.assign(n_cells, 0);
   g->counted.assign(n_cells, 0);
@@ -3062,7 +3047,7 @@ struct ImageGuard {
 /* the call's launch block: the config's, the group's stores, and of the form's stores those that its row names */
 void group_fill_launch(const rs_group* g, const GroupCall& c, RsLaunch* launch) {
   const rs_batch* b = g->b;
-  const unsigned sets = c.desc().sets;
+  const unsigned sets = c.desc().sets();
   uint8_t* const dev_in = c.zc ? g->z_in : g->d_in;
   uint8_t* const dev_out = c.zc ? g->z_out : g->d_out;
   RsLaunch& L = *launch;
@@ -3092,26 +3077,28 @@ void group_fill_launch(const rs_group* g, const GroupCall& c, RsLaunch* launch) 
   L.grp_in_stride = (int64_t)g->in_stride;
   L.grp_out_stride = (int64_t)g->out_stride * c.ttis(); /* (a run: a slot's TTIs follow one another) */
   L.grp_count = g->d_count;
-  if (sets & kSetResident) {
-    L.grp_avg = g->d_ravg;
-    L.grp_pending = g->d_rpend;
+  if (sets & RS_GROUP_SET_CELL) {
     L.grp_last = g->d_rlast;
     L.grp_gather = g->d_rgather;
     L.grp_uid = g->d_ruid;
   }
-  if (sets & kSetBearers) {
+  if (sets & RS_GROUP_SET_AVERAGES) {
+    L.grp_avg = g->d_ravg;
+    L.grp_pending = g->d_rpend;
+  }
+  if (sets & RS_GROUP_SET_BEARERS) {
     L.grp_qavg = g->d_qavg;
     L.grp_qpend = g->d_qpend;
     L.grp_qhas = g->d_qhas;
-    L.grp_qdata = g->d_qdata;
     L.grp_qin = g->z_qin ? g->z_qin : g->d_qin;
     L.grp_qin_stride = 2 * (int64_t)b->U;
   }
-  if (sets & kSetCounters) {
+  if (sets & RS_GROUP_SET_DATA) L.grp_qdata = g->d_qdata;
+  if (sets & RS_GROUP_SET_COUNTERS) {
     L.grp_cbytes = g->d_cbytes;
     L.grp_crbs = g->d_crbs;
   }
-  if (sets & kSetSent) {
+  if (sets & RS_GROUP_SET_SENT) {
     L.grp_sent = g->z_sent ? g->z_sent : g->d_sent;
     L.grp_sent_stride = 2 * (int64_t)b->U;
   }
@@ -3159,13 +3146,13 @@ int group_run_twin(rs_group* g, const GroupCall& c, const RsLaunch& L) {
   Lb.grp_out = g->d_out2;
   Lb.log_upper = c.want_upper ? (int32_t*)g->d_out2 : nullptr;
   Lb.done_flag = nullptr;
-  if (f.sets & kSetSent) { /* (the sent rows are outputs too: the built-in kernel's go to the twin block, whatever the caller asked for) */
+  if (f.sets() & RS_GROUP_SET_SENT) { /* (the sent rows are outputs too: the built-in kernel's go to the twin block, whatever the caller asked for) */
     if (!group_alloc_sent_twin(g)) return fail(RS_ERR_HIP, "allocation of the self-check's twin sent block failed (%zu bytes)", 8 * (size_t)b->U * g->n_cells);
     Lb.grp_sent = g->z_sent2 ? g->z_sent2 : g->d_sent2;
   }
-  HIP_TRY(f.launch(&Lb, b->threads, st));
+  HIP_TRY(rs_launch_group(&Lb, b->threads, c.row(), st));
   HIP_TRY(hipMemcpyAsync(g->h_out2.data(), g->d_out2, (size_t)c.n * c.ttis() * g->out_stride, hipMemcpyDeviceToHost, st)); /* (a run: slots x TTIs) */
-  if ((f.sets & kSetSent) && !g->z_sent2) HIP_TRY(hipMemcpyAsync(g->h_sent2, g->d_sent2, 8 * (size_t)c.n * b->U, hipMemcpyDeviceToHost, st));
+  if ((f.sets() & RS_GROUP_SET_SENT) && !g->z_sent2) HIP_TRY(hipMemcpyAsync(g->h_sent2, g->d_sent2, 8 * (size_t)c.n * b->U, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(after, b->d_sstate, ss_all, hipMemcpyDeviceToDevice, st));
   HIP_TRY(hipMemcpyAsync(b->d_sstate, before, ss_all, hipMemcpyDeviceToDevice, st));
   HIP_TRY(hipMemcpyAsync(b->d_scal, before + group_chk_sstate(g), sc_all, hipMemcpyDeviceToDevice, st));
@@ -3187,7 +3174,7 @@ int group_run(rs_group* g, GroupCall& c, RsLaunch& L) {
   if (!c.zc) HIP_TRY(hipMemcpyAsync(g->d_in, g->h_in, (size_t)c.n * g->in_stride, hipMemcpyHostToDevice, st));
   if (!c.zc && c.run)
     HIP_TRY(hipMemcpyAsync(g->d_in + g->run_table_off, g->h_in + g->run_table_off, (size_t)c.n * RS_GROUP_MAX_RUN * RS_GROUP_RUN_ROW_BYTES, hipMemcpyHostToDevice, st));
-  if ((f.sets & kSetBearers) && !g->z_qin) HIP_TRY(hipMemcpyAsync(g->d_qin, g->h_qin, 8 * (size_t)c.n * b->U, hipMemcpyHostToDevice, st));
+  if ((f.sets() & RS_GROUP_SET_BEARERS) && !g->z_qin) HIP_TRY(hipMemcpyAsync(g->d_qin, g->h_qin, 8 * (size_t)c.n * b->U, hipMemcpyHostToDevice, st));
   c.poll = c.zc && g->poll;
   if (c.poll) {
     if (++g->seq == 0) g->seq = 1; /* (0 is the word's initial value) */
@@ -3207,12 +3194,12 @@ int group_run(rs_group* g, GroupCall& c, RsLaunch& L) {
     L.done_flag = nullptr; /* completion by the stream */
   }
   if (c.kd) HIP_TRY(rs_jit_launch(c.kd, &L, st));
-  else HIP_TRY(f.launch(&L, b->threads, st));
+  else HIP_TRY(rs_launch_group(&L, b->threads, c.row(), st));
   g->launches++;
   g->last_call_form = c.row();
   g->last_call_jit = c.kd != nullptr;
   if (!c.zc) HIP_TRY(hipMemcpyAsync(g->h_out, g->d_out, (size_t)c.n * c.ttis() * g->out_stride, hipMemcpyDeviceToHost, st));
-  if ((f.sets & kSetSent) && !g->z_sent) HIP_TRY(hipMemcpyAsync(g->h_sent, g->d_sent, 8 * (size_t)c.n * b->U, hipMemcpyDeviceToHost, st));
+  if ((f.sets() & RS_GROUP_SET_SENT) && !g->z_sent) HIP_TRY(hipMemcpyAsync(g->h_sent, g->d_sent, 8 * (size_t)c.n * b->U, hipMemcpyDeviceToHost, st));
   return RS_OK;
 }
 
@@ -3278,7 +3265,7 @@ int group_drop_pair(rs_group* g, const GroupCall& c, const char* what) {
   p.dropped = true;
   g->last_call_jit = false;
   memcpy(g->h_out, g->h_out2.data(), (size_t)c.n * c.ttis() * g->out_stride);
-  if (f.sets & kSetSent) memcpy(g->h_sent, g->h_sent2, 8 * (size_t)c.n * b->U); /* (the built-in kernel's sent rows: what group_unpack hands out) */
+  if (f.sets() & RS_GROUP_SET_SENT) memcpy(g->h_sent, g->h_sent2, 8 * (size_t)c.n * b->U); /* (the built-in kernel's sent rows: what group_unpack hands out) */
   HIP_TRY(hipMemcpy(b->d_sstate, g->d_chk + group_chk_half(g), 8 * (size_t)b->S * g->n_cells, hipMemcpyDeviceToDevice));
   if (f.store_width) {
     HIP_TRY(group_copy_stores(g, f, 1, false));
@@ -3312,7 +3299,7 @@ int group_check(rs_group* g, const GroupCall& c) {
       if (to_bits(a) != to_bits(r)) snprintf(what, sizeof what, "cell %d: slice state[%d] = %a, the built-in kernel's %a", cell, i, a, r);
     }
     /* (a counted call: the slot's sent rows, whether or not the caller wants them; an update-only slot has none) */
-    if ((c.desc().sets & kSetSent) && !g->empty_slot[k]) {
+    if ((c.desc().sets() & RS_GROUP_SET_SENT) && !g->empty_slot[k]) {
       const int32_t *a = g->h_sent + (size_t)k * 2 * (size_t)b->U, *r = g->h_sent2 + (size_t)k * 2 * (size_t)b->U;
       for (int j = 0; j < 2 * c.in[k].n_users && !what[0]; j++)
         if (a[j] != r[j]) snprintf(what, sizeof what, "cell %d: sent[%d][%d] = %d, the built-in kernel's %d", cell, j / 2, j % 2, a[j], r[j]);
@@ -3785,7 +3772,7 @@ const char* rs_group_kernel_name(rs_group* g) {
    * calls now) */
   const int row = g->last_call_form;
   const bool jit = row == kGroupPlain ? g->pair[kGroupPlain].jit[0] != nullptr : g->last_call_jit;
-  return jit ? kGroupForms[row].jit_name : g->kname[row];
+  return jit ? g->kname_jit[row] : g->kname[row];
 }
 
 /* Shape specialisation of a group: rs_ctx_specialize for the group surface -- the one-TTI form compiled for the config's slices, RBGs,
@@ -3804,13 +3791,13 @@ int group_specialize_pair(rs_group* g, int kind) {
   rs_group::GroupPair& p = g->pair[f.pair];
   if (p.jit[0]) return RS_OK;
   if (p.dropped) return fail(RS_ERR_STATE, "%s", p.msg);
-  if (kind == kGroupQueued && b->sched != RS_SCHED_NVS && b->sched != RS_SCHED_SEQUENTIAL && b->sched != RS_SCHED_MAXCELL && b->sched != RS_SCHED_SUBOPT && b->sched != RS_SCHED_VOGEL)
+  if (kind == kGroupQueued && !rs_group_form_serves(kind, b->sched))
     return fail(RS_ERR_INVALID, "scheduler %d has no queued form (rs_group_set_bearers): nothing for rs_group_specialize_queued to build", b->sched);
-  if (kind == kGroupCounted && b->sched != RS_SCHED_NVS && b->sched != RS_SCHED_SEQUENTIAL && b->sched != RS_SCHED_MAXCELL && b->sched != RS_SCHED_SUBOPT && b->sched != RS_SCHED_VOGEL)
+  if (kind == kGroupCounted && !rs_group_form_serves(kind, b->sched))
     return fail(RS_ERR_INVALID, "scheduler %d has no counted form (rs_group_set_counters): nothing for rs_group_specialize_counted to build", b->sched);
-  if (kind == kGroupFlows && b->sched != RS_SCHED_PF)
+  if (kind == kGroupFlows && !rs_group_form_serves(kind, b->sched))
     return fail(RS_ERR_INVALID, "scheduler %d has no flows form (rs_group_set_flows): nothing for rs_group_specialize_flows to build", b->sched);
-  if (kind == kGroupRun && (b->sched == RS_SCHED_NVS || b->sched == RS_SCHED_NVS_NONGREEDY))
+  if (kind == kGroupRun && !rs_group_form_serves(kind, b->sched))
     return fail(RS_ERR_INVALID, "scheduler %d is not served by a run (rs_group_run_at): nothing for rs_group_specialize_run to build", b->sched);
   if (kind == kGroupRun && b->any_alpha)
     return fail(RS_ERR_INVALID, "a config with a customised slice (algo_alpha != 0) is not served by a run (rs_group_run_at): nothing for rs_group_specialize_run to build");
@@ -3835,8 +3822,9 @@ int group_specialize_pair(rs_group* g, int kind) {
     return fail(RS_ERR_HIP, "%s", p.msg);
   }
   const int qmode = (b->sched == RS_SCHED_PF || b->sched == RS_SCHED_NVS) ? 1 : 0; /* (the gate scratch of the group's carve: carve_lds) */
+  const int jit_flags = 1 | rs_group_form(kind).jit_flags; /* (1: the one-TTI form, as every group build is) */
   char msg[512] = "";
-  p.jit[0] = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, qmode, 0, msg, sizeof msg, f.jit_flags);
+  p.jit[0] = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, qmode, 0, msg, sizeof msg, jit_flags);
   if (!p.jit[0]) {
     snprintf(p.msg, sizeof p.msg, "%s", msg[0] ? msg : "hiprtc build failed");
     return fail(RS_ERR_HIP, "%s", p.msg);
@@ -3844,7 +3832,7 @@ int group_specialize_pair(rs_group* g, int kind) {
   p.msg[0] = 0;
   /* ... and its lean form (the plain call); without it the general build serves every call */
   const char* const e_on = getenv("RS_JIT_LEAN");
-  if (!e_on || atoi(e_on) != 0) p.jit[1] = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, qmode, 0, msg, sizeof msg, f.jit_flags | 4);
+  if (!e_on || atoi(e_on) != 0) p.jit[1] = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, qmode, 0, msg, sizeof msg, jit_flags | 4);
   for (int w = 0; w < 2; w++) { /* (the policy and the switches of rs_ctx_specialize) */
     p.chk_agreed[w] = 0;
     p.chk_left[w] = selfcheck_calls(p.jit[w]);

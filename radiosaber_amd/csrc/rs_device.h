@@ -423,4 +423,87 @@ struct RsGroupCell {
 static_assert(sizeof(RsGroupCell) == RS_GROUP_HDR_BYTES, "the slot header keeps its size: new words come out of its padding");
 static_assert(__builtin_offsetof(RsGroupCell, image_mode) == 72 && __builtin_offsetof(RsGroupCell, now) == 80, "no existing word of the slot header moves");
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * The forms of a group call: THE description.  The body text (rs_phase_group.inc), the built-in kernels, their launcher and LDS
+ * attribute list (rs_kernels.hip), the run-time builds (rs_jit.cpp) and the host (kGroupForms of rs_api.cpp, same row order) read it;
+ * nothing else says what a form is.  A new form is a row here, its text in rs_phase_group.inc, an entry point of its name in
+ * rs_kernels.hip and its host-only row in rs_api.cpp.
+ * ------------------------------------------------------------------------------------------------------------------ */
+enum RsGroupFormId { RS_GROUP_PLAIN = 0, RS_GROUP_RESIDENT = 1, RS_GROUP_QUEUED = 2, RS_GROUP_FLOWS = 3, RS_GROUP_COUNTED = 4, RS_GROUP_RUN = 5, RS_GROUP_FORMS = 6 };
+enum : unsigned { /* the RsLaunch pointers a form's kernel dereferences: the host fills them, the launcher refuses a null one */
+  RS_GROUP_SET_CELL = 1,      /* grp_last, grp_gather, grp_uid: every form that keeps state on the device */
+  RS_GROUP_SET_AVERAGES = 2,  /* grp_avg, grp_pending */
+  RS_GROUP_SET_BEARERS = 4,   /* grp_qavg, grp_qpend, grp_qhas and the slots' word block grp_qin (data words; a flows call: bearer words) */
+  RS_GROUP_SET_DATA = 8,      /* grp_qdata: the workgroup's copy of the data words */
+  RS_GROUP_SET_COUNTERS = 16, /* grp_cbytes, grp_crbs */
+  RS_GROUP_SET_SENT = 32,     /* grp_sent: the slots' sent rows */
+};
+/* the schedulers a group kernel may be asked for, and a set of them as a mask over their places in this list */
+#define RS_GROUP_SCHEDS 8
+constexpr int rs_group_sched_at(int i) {
+  constexpr int list[RS_GROUP_SCHEDS] = {1, 7, 8, 9, 10, 11, 101, 103};
+  return list[i];
+}
+constexpr int rs_group_sched_index(int sched) {
+  for (int i = 0; i < RS_GROUP_SCHEDS; ++i)
+    if (rs_group_sched_at(i) == sched) return i;
+  return -1;
+}
+constexpr unsigned rs_group_scheds(int a, int b = -1, int c = -1, int d = -1, int e = -1, int f = -1, int g = -1) {
+  const int s[7] = {a, b, c, d, e, f, g};
+  unsigned m = 0;
+  for (int i = 0; i < 7; ++i)
+    if (rs_group_sched_index(s[i]) >= 0) m |= 1u << rs_group_sched_index(s[i]);
+  return m;
+}
+struct RsGroupForm {
+  const char* stem;         /* <stem><SCHED, EPT> is the built-in kernel, <stem>_jit the entry point of a run-time build */
+  bool res, que, cnt, flow, run; /* what the body text reads (rs_phase_group.inc says what each one adds) */
+  unsigned sets;            /* RS_GROUP_SET_* */
+  int jit_flags;            /* rs_jit_get's flag bits of the form: 8 a group's build, 16 resident, 32 queued, 64 counted, 128 flows, 256 run */
+  unsigned scheds;          /* the schedulers the library has a kernel of this form for: its row of the matrix */
+};
+#define RS_GROUP_JIT_FLAG_BITS (8 | 16 | 32 | 64 | 128 | 256)
+constexpr RsGroupForm rs_group_form(int form) {
+  constexpr unsigned all = rs_group_scheds(1, 7, 8, 9, 10, 101, 103); /* what rs_group_create takes: every scheduler but the sampler (11) */
+  constexpr unsigned credit = rs_group_scheds(7, 8, 9, 101, 103);     /* the ones the oracle restates with queues and a per-user credit */
+  constexpr unsigned avgs = RS_GROUP_SET_CELL | RS_GROUP_SET_AVERAGES, bearers = RS_GROUP_SET_CELL | RS_GROUP_SET_BEARERS;
+  constexpr RsGroupForm rows[RS_GROUP_FORMS] = {
+      /*                                 res    que    cnt    flow   run */
+      {"rs_group_kernel",          false, false, false, false, false, 0, 8, all},
+      {"rs_group_resident_kernel", true,  false, false, false, false, avgs, 8 | 16, all},
+      {"rs_group_queued_kernel",   false, true,  false, false, false, bearers | RS_GROUP_SET_DATA, 8 | 32, credit},
+      {"rs_group_flows_kernel",    false, false, false, true,  false, bearers | RS_GROUP_SET_COUNTERS, 8 | 128, rs_group_scheds(1)},
+      {"rs_group_counted_kernel",  false, true,  true,  false, false, bearers | RS_GROUP_SET_DATA | RS_GROUP_SET_COUNTERS | RS_GROUP_SET_SENT, 8 | 32 | 64, credit},
+      {"rs_group_run_kernel",      true,  false, false, false, true,  avgs, 8 | 16 | 256, all & ~rs_group_scheds(7)}, /* (7: the host picks the served slice per TTI) */
+  };
+  return rows[form];
+}
+/* the built-in matrix: has the library a kernel of this form for this scheduler? */
+constexpr bool rs_group_form_serves(int form, int sched) {
+  return form >= 0 && form < RS_GROUP_FORMS && rs_group_sched_index(sched) >= 0 && ((rs_group_form(form).scheds >> rs_group_sched_index(sched)) & 1u) != 0;
+}
+/* ... and what the run-time builds answer (rs_jit.cpp).  ONE exception, kept as it was found: a plain or a resident build is never asked
+ * for its scheduler, so scheduler 11 -- which no group kernel serves and rs_group_create refuses -- gets a cache file and a build there. */
+constexpr bool rs_group_form_builds(int form, int sched) { return form == RS_GROUP_PLAIN || form == RS_GROUP_RESIDENT || rs_group_form_serves(form, sched); }
+/* the kernels' second template argument for `ept` sort positions per lane: the register form of the sort up to four (schedulers 9 and
+ * 10), above that scheduler 9's LDS form (0), which scheduler 10 has no built-in kernel of (-1); every other scheduler 0 */
+constexpr int rs_group_form_ept(int sched, int ept) { return (sched != 9 && sched != 10) ? 0 : (ept <= 4 ? (ept < 1 ? 1 : ept) : (sched == 9 ? 0 : -1)); }
+/* is <stem><sched, ept> one of the library's kernels?  (what rs_launch_group can launch and rs_prepare_kernels prepares) */
+constexpr bool rs_group_kernel_exists(int form, int sched, int ept) { return rs_group_form_serves(form, sched) && rs_group_form_ept(sched, ept == 0 ? 5 : ept) == ept; }
+/* is `name` the entry point of the form's run-time builds, <stem>_jit? */
+constexpr bool rs_group_jit_entry_is(int form, const char* name) {
+  for (const char* s = rs_group_form(form).stem; *s; ++s, ++name)
+    if (*s != *name) return false;
+  for (const char* s = "_jit"; *s; ++s, ++name)
+    if (*s != *name) return false;
+  return *name == 0;
+}
+/* the form that rs_jit_get's flags name: -1 when they name none (no group build, or no valid combination) */
+constexpr int rs_group_form_of_flags(int flags) {
+  for (int f = 0; f < RS_GROUP_FORMS; ++f)
+    if ((flags & RS_GROUP_JIT_FLAG_BITS) == rs_group_form(f).jit_flags) return f;
+  return -1;
+}
+
 #endif /* RS_DEVICE_H_ */

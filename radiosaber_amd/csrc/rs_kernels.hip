@@ -773,71 +773,61 @@ __global__ void __launch_bounds__(512, 4) rs_cell_kernel(RsLaunch p) {
   rs_cell_body<SCHED, EPT, false, DIRECT, QUEUE>(p, lds);
 }
 
-/* a group call on the kernels built into the library: 14 instantiations (rs_launch_group); the body is rs_phase_group.inc */
+/* The group kernels built into the library: one template per form of a group call, the body is rs_phase_group.inc, which reads the
+ * form's row of the table in rs_device.h (rs_group_form) -- that row and the text are what a form IS; the names are what traces, profiles
+ * and rs_group_kernel_name cite.  Which (scheduler, EPT) pairs exist per form: rs_group_kernel_exists (60 kernels; the one enumeration
+ * behind rs_launch_group and rs_prepare_kernels below).  A group's run-time builds are the <name>_jit entry point further down.
+ *   rs_group_kernel            rs_group_schedule_tti          shape in the launch block, nothing kept on the device
+ *   rs_group_resident_kernel   rs_group_schedule_tti_at       the cells' PF averages, pending bytes and last-update times stay on the device
+ *   rs_group_queued_kernel     rs_group_schedule_tti_queued   both bearers of every user stay there; a slot without users does the update alone
+ *   rs_group_flows_kernel      rs_group_schedule_tti_flows    scheduler 1: a call position is a flow, bearer stores and counters
+ *   rs_group_counted_kernel    rs_group_schedule_tti_counted  the queued form with m_cumulateBytes / m_cumulateRBs and the slots' sent rows
+ *   rs_group_run_kernel        rs_group_run_at                T consecutive TTIs of the resident form in one launch */
 template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
-  constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
-  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = false, kGrpCnt = false, kGrpFlow = false, kGrpRun = false;
+  constexpr int kGrpForm = RS_GROUP_PLAIN, kGrpSched = SCHED, kGrpEpt = EPT;
+  constexpr bool kGrpFixed = false, kGrpLean = false;
 #include "rs_phase_group.inc"
 }
 
-/* ... and its resident form (rs_group_schedule_tti_at): the cells' PF averages, pending bytes and last-update times stay on the device.
- * Kernels of their own, the same 14 shapes (rs_launch_group_resident): the plain group kernels above carry none of it.  A group's
- * run-time builds of this form are rs_group_resident_kernel_jit below. */
 template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_resident_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
-  constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
-  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = true, kGrpQue = false, kGrpCnt = false, kGrpFlow = false, kGrpRun = false;
+  constexpr int kGrpForm = RS_GROUP_RESIDENT, kGrpSched = SCHED, kGrpEpt = EPT;
+  constexpr bool kGrpFixed = false, kGrpLean = false;
 #include "rs_phase_group.inc"
 }
 
-/* ... and its queued form (rs_group_schedule_tti_queued): both bearers of every user stay on the device -- averages, pending bytes,
- * existence --, the call brings m_dataToTransmit per bearer, and a slot without users does the update alone.  Kernels of their own
- * for the schedulers the oracle restates with queues and a per-user credit (rs_launch_group_queued): 7, 8, 9, 101, 103.  A group's
- * run-time builds of this form are rs_group_queued_kernel_jit below. */
 template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_queued_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
-  constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
-  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = true, kGrpCnt = false, kGrpFlow = false, kGrpRun = false;
+  constexpr int kGrpForm = RS_GROUP_QUEUED, kGrpSched = SCHED, kGrpEpt = EPT;
+  constexpr bool kGrpFixed = false, kGrpLean = false;
 #include "rs_phase_group.inc"
 }
 
-/* ... and the queued form's counted twin (rs_group_schedule_tti_counted): the cell's bearers also keep m_cumulateBytes / m_cumulateRBs
- * on the device, and the slot gets back the bytes sent per call position and bearer.  Kernels of their own, the queued form's nine
- * shapes (rs_launch_group_counted): the queued kernels above carry none of it.  A group's run-time builds of this form are
- * rs_group_counted_kernel_jit below. */
 template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_counted_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
-  constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
-  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = true, kGrpCnt = true, kGrpFlow = false, kGrpRun = false;
+  constexpr int kGrpForm = RS_GROUP_COUNTED, kGrpSched = SCHED, kGrpEpt = EPT;
+  constexpr bool kGrpFixed = false, kGrpLean = false;
 #include "rs_phase_group.inc"
 }
 
-/* ... and scheduler 1's flow-resident form (rs_group_schedule_tti_flows): DL_PF_PacketScheduler's unit is the flow, so a call position
- * is one bearer of one user; the cell keeps both bearers' averages, pending bytes and counters on the device and the whole transport
- * block is credited to the flow.  One kernel (rs_launch_group_flows).  A group's run-time builds of this form are
- * rs_group_flows_kernel_jit below. */
 template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_flows_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
-  constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
-  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = false, kGrpQue = false, kGrpCnt = false, kGrpFlow = true, kGrpRun = false;
+  constexpr int kGrpForm = RS_GROUP_FLOWS, kGrpSched = SCHED, kGrpEpt = EPT;
+  constexpr bool kGrpFixed = false, kGrpLean = false;
 #include "rs_phase_group.inc"
 }
 
-/* ... and the resident form's run (rs_group_run_at): T consecutive TTIs of every named cell in one launch -- the resident form's update,
- * body and credit T times per workgroup, the clock and the rand() pair of each TTI from the slot's table, one completion behind the last
- * TTI.  Kernels of their own, the resident form's shapes without NVS (rs_launch_group_run): the resident kernels above carry none of it.
- * A group's run-time builds of this form are rs_group_run_kernel_jit below. */
 template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_run_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
-  constexpr int kGrpSched = SCHED, kGrpEpt = EPT;
-  constexpr bool kGrpFixed = false, kGrpLean = false, kGrpRes = true, kGrpQue = false, kGrpCnt = false, kGrpFlow = false, kGrpRun = true;
+  constexpr int kGrpForm = RS_GROUP_RUN, kGrpSched = SCHED, kGrpEpt = EPT;
+  constexpr bool kGrpFixed = false, kGrpLean = false;
 #include "rs_phase_group.inc"
 }
 #else
@@ -869,46 +859,34 @@ __global__ void __launch_bounds__(512, 4) rs_group_run_kernel(RsLaunch p) {
 #define RS_JIT_GROUP_RUN 0 /* 1, with RS_JIT_GROUP and RS_JIT_GROUP_RESIDENT, never scheduler 7: the group's build of the resident form's run (rs_group_specialize_run) */
 #endif
 #if RS_JIT_GROUP
-/* six entry points, one per option list: rs_group_kernel_jit, rs_group_resident_kernel_jit for the calls that keep the cells' PF
- * averages on the device (rs_group_schedule_tti_at), rs_group_queued_kernel_jit for the calls that keep both bearers there
- * (rs_group_schedule_tti_queued), rs_group_counted_kernel_jit for those that keep the bearers' counters too
- * (rs_group_schedule_tti_counted: the queued text with kGrpCnt), rs_group_flows_kernel_jit for scheduler 1's flows
- * (rs_group_schedule_tti_flows) and rs_group_run_kernel_jit for the runs of the resident form (rs_group_run_at: the resident text T
- * times per workgroup).  Same text but for the name and kGrpRes, kGrpQue, kGrpCnt, kGrpFlow, kGrpRun; each has a general and a lean form. */
-#if RS_JIT_GROUP_RESIDENT && RS_JIT_GROUP_QUEUED
-#error "RS_JIT_GROUP_RESIDENT and RS_JIT_GROUP_QUEUED exclude each other"
-#endif
-#if RS_JIT_GROUP_RESIDENT && RS_JIT_GROUP_COUNTED
-#error "RS_JIT_GROUP_RESIDENT and RS_JIT_GROUP_COUNTED exclude each other"
-#endif
-#if RS_JIT_GROUP_FLOWS && (RS_JIT_GROUP_RESIDENT || RS_JIT_GROUP_QUEUED || RS_JIT_GROUP_COUNTED)
-#error "RS_JIT_GROUP_FLOWS is never combined with RS_JIT_GROUP_RESIDENT, RS_JIT_GROUP_QUEUED or RS_JIT_GROUP_COUNTED"
-#endif
-#if RS_JIT_GROUP_FLOWS && RS_JIT_SCHED != 1
-#error "RS_JIT_GROUP_FLOWS: the flows form is scheduler 1's"
-#endif
-#if RS_JIT_GROUP_RUN && !RS_JIT_GROUP_RESIDENT
-#error "RS_JIT_GROUP_RUN needs RS_JIT_GROUP_RESIDENT: the run form is the resident form's"
-#endif
-#if RS_JIT_GROUP_RUN && (RS_JIT_GROUP_QUEUED || RS_JIT_GROUP_COUNTED || RS_JIT_GROUP_FLOWS)
-#error "RS_JIT_GROUP_RUN is never combined with RS_JIT_GROUP_QUEUED, RS_JIT_GROUP_COUNTED or RS_JIT_GROUP_FLOWS"
-#endif
-#if RS_JIT_GROUP_RUN && RS_JIT_SCHED == 7
-#error "RS_JIT_GROUP_RUN: scheduler 7 has no run form (the host picks the served slice per TTI)"
-#endif
+/* The options name a form, here and nowhere else: the entry point's name has to be a token, so the preprocessor picks it -- and the
+ * form's row with it; the flag bits the same options stand for (rs_jit_get's, rs_device.h) must name that very row, which refuses
+ * every combination that is no form, and the form must have a build for the scheduler.  Each entry point has a general and a lean form. */
 #if RS_JIT_GROUP_RUN
+#define RS_JIT_GROUP_FORM RS_GROUP_RUN
 #define RS_GROUP_JIT_ENTRY rs_group_run_kernel_jit
 #elif RS_JIT_GROUP_RESIDENT
+#define RS_JIT_GROUP_FORM RS_GROUP_RESIDENT
 #define RS_GROUP_JIT_ENTRY rs_group_resident_kernel_jit
 #elif RS_JIT_GROUP_COUNTED
+#define RS_JIT_GROUP_FORM RS_GROUP_COUNTED
 #define RS_GROUP_JIT_ENTRY rs_group_counted_kernel_jit
 #elif RS_JIT_GROUP_FLOWS
+#define RS_JIT_GROUP_FORM RS_GROUP_FLOWS
 #define RS_GROUP_JIT_ENTRY rs_group_flows_kernel_jit
 #elif RS_JIT_GROUP_QUEUED
+#define RS_JIT_GROUP_FORM RS_GROUP_QUEUED
 #define RS_GROUP_JIT_ENTRY rs_group_queued_kernel_jit
 #else
+#define RS_JIT_GROUP_FORM RS_GROUP_PLAIN
 #define RS_GROUP_JIT_ENTRY rs_group_kernel_jit
 #endif
+#define RS_STR_(x) #x
+#define RS_STR(x) RS_STR_(x)
+static_assert(rs_group_form_of_flags(8 | (RS_JIT_GROUP_RESIDENT ? 16 : 0) | ((RS_JIT_GROUP_QUEUED || RS_JIT_GROUP_COUNTED) ? 32 : 0) | (RS_JIT_GROUP_COUNTED ? 64 : 0) |
+                                     (RS_JIT_GROUP_FLOWS ? 128 : 0) | (RS_JIT_GROUP_RUN ? 256 : 0)) == RS_JIT_GROUP_FORM &&
+                  rs_group_form_builds(RS_JIT_GROUP_FORM, RS_JIT_SCHED) && rs_group_jit_entry_is(RS_JIT_GROUP_FORM, RS_STR(RS_GROUP_JIT_ENTRY)),
+              "the RS_JIT_GROUP_* options name no form of a group call (rs_group_form, rs_device.h), or none that RS_JIT_SCHED has a build of");
 extern "C" __global__ void __launch_bounds__(RS_JIT_NT, RS_JIT_WPE) RS_GROUP_JIT_ENTRY(RsLaunch p) {
 #if defined(RS_JIT_LEAN) && RS_JIT_LEAN
   /* The lean build of a group's kernel: the plain call, exactly as in the one-TTI lean kernel below -- per-RBG reports, no customised
@@ -929,9 +907,9 @@ extern "C" __global__ void __launch_bounds__(RS_JIT_NT, RS_JIT_WPE) RS_GROUP_JIT
 #endif
   constexpr RsCarve kCv = rs_carve(RS_JIT_S, RS_JIT_U, RS_JIT_R, RS_JIT_SCHED, RS_JIT_NT, RS_JIT_CARVEQ, RS_JIT_WIN);
   __shared__ __align__(16) unsigned char lds[kCv.lds_bytes];
-  constexpr int kGrpSched = RS_JIT_SCHED, kGrpEpt = (RS_JIT_SCHED != 9 && RS_JIT_SCHED != 10) ? 0 : (kCv.ept <= 4 ? kCv.ept : 0);
-  constexpr bool kGrpFixed = true, kGrpRes = RS_JIT_GROUP_RESIDENT != 0, kGrpQue = RS_JIT_GROUP_QUEUED != 0 || RS_JIT_GROUP_COUNTED != 0,
-                 kGrpCnt = RS_JIT_GROUP_COUNTED != 0, kGrpFlow = RS_JIT_GROUP_FLOWS != 0, kGrpRun = RS_JIT_GROUP_RUN != 0;
+  /* (a run-time build of scheduler 10 above four positions per lane takes the sort's LDS form, which the library carries no kernel of) */
+  constexpr int kGrpForm = RS_JIT_GROUP_FORM, kGrpSched = RS_JIT_SCHED, kGrpEpt = rs_group_form_ept(RS_JIT_SCHED, kCv.ept) < 0 ? 0 : rs_group_form_ept(RS_JIT_SCHED, kCv.ept);
+  constexpr bool kGrpFixed = true;
 #include "rs_phase_group.inc"
 }
 #undef RS_GROUP_JIT_ENTRY
@@ -1035,6 +1013,7 @@ __global__ void rs_slice_bytes_kernel(const int64_t* cum_bytes, const uint8_t* u
 }
 
 #if !defined(__HIPCC_RTC__) && !defined(RS_JIT_BUILD)
+#include <utility>
 /* host-callable launchers (defined here so that the kernels stay in one translation unit) */
 extern "C" hipError_t rs_launch_cells(const RsLaunch* p, int threads, hipStream_t stream) {
   dim3 grid(p->n_cells), block(threads);
@@ -1092,159 +1071,52 @@ extern "C" hipError_t rs_launch_cells(const RsLaunch* p, int threads, hipStream_
   return hipGetLastError();
 }
 
-/* a group call: p->n_cells call slots, one workgroup each (schedulers 1, 7, 8, 9, 10, 101, 103) */
-extern "C" hipError_t rs_launch_group(const RsLaunch* p, int threads, hipStream_t stream) {
-  dim3 grid(p->n_cells), block(threads);
-  const int ept = (p->R * p->S + threads - 1) / threads;
-#define RS_LAUNCH_GROUP(SCHED_, EPT_) hipLaunchKernelGGL((rs_group_kernel<SCHED_, EPT_>), grid, block, p->lds_bytes, stream, *p)
-  switch (p->sched) {
-    case 1: RS_LAUNCH_GROUP(1, 0); break;
-    case 7: RS_LAUNCH_GROUP(7, 0); break;
-    case 8: RS_LAUNCH_GROUP(8, 0); break;
-    case 101: RS_LAUNCH_GROUP(101, 0); break;
-    case 103: RS_LAUNCH_GROUP(103, 0); break;
-    case 10:
-      if (ept <= 1) RS_LAUNCH_GROUP(10, 1);
-      else if (ept <= 2) RS_LAUNCH_GROUP(10, 2);
-      else if (ept <= 3) RS_LAUNCH_GROUP(10, 3);
-      else if (ept <= 4) RS_LAUNCH_GROUP(10, 4);
-      else return hipErrorInvalidValue;
-      break;
-    case 9:
-      if (ept <= 1) RS_LAUNCH_GROUP(9, 1);
-      else if (ept <= 2) RS_LAUNCH_GROUP(9, 2);
-      else if (ept <= 3) RS_LAUNCH_GROUP(9, 3);
-      else if (ept <= 4) RS_LAUNCH_GROUP(9, 4);
-      else RS_LAUNCH_GROUP(9, 0);
-      break;
-    default: return hipErrorInvalidValue;
-  }
-#undef RS_LAUNCH_GROUP
-  return hipGetLastError();
+/* The group kernels of the library, ONE enumeration: every (form, scheduler, EPT) that rs_group_kernel_exists says yes to, by the
+ * form's template.  rs_launch_group launches from it and rs_prepare_kernels sets the LDS attribute from it: a kernel cannot be one
+ * without the other, and nothing outside rs_group_kernel_exists' yes is instantiated. */
+template <int FORM, int SCHED, int EPT>
+static const void* rs_group_kernel_fn() {
+  if constexpr (!rs_group_kernel_exists(FORM, SCHED, EPT)) return nullptr;
+  else if constexpr (FORM == RS_GROUP_PLAIN) return (const void*)rs_group_kernel<SCHED, EPT>;
+  else if constexpr (FORM == RS_GROUP_RESIDENT) return (const void*)rs_group_resident_kernel<SCHED, EPT>;
+  else if constexpr (FORM == RS_GROUP_QUEUED) return (const void*)rs_group_queued_kernel<SCHED, EPT>;
+  else if constexpr (FORM == RS_GROUP_FLOWS) return (const void*)rs_group_flows_kernel<SCHED, EPT>;
+  else if constexpr (FORM == RS_GROUP_COUNTED) return (const void*)rs_group_counted_kernel<SCHED, EPT>;
+  else return (const void*)rs_group_run_kernel<SCHED, EPT>;
+}
+struct RsGroupKernels {
+  const void* fn[RS_GROUP_FORMS][RS_GROUP_SCHEDS][5]; /* [form][rs_group_sched_index][EPT]; null: no such kernel */
+};
+template <int... I>
+static void rs_group_kernels_fill(RsGroupKernels& t, std::integer_sequence<int, I...>) {
+  ((t.fn[I / (5 * RS_GROUP_SCHEDS)][I / 5 % RS_GROUP_SCHEDS][I % 5] = rs_group_kernel_fn<I / (5 * RS_GROUP_SCHEDS), rs_group_sched_at(I / 5 % RS_GROUP_SCHEDS), I % 5>()), ...);
+}
+static const RsGroupKernels& rs_group_kernels() {
+  static const RsGroupKernels table = [] {
+    RsGroupKernels t{};
+    rs_group_kernels_fill(t, std::make_integer_sequence<int, RS_GROUP_FORMS * RS_GROUP_SCHEDS * 5>{});
+    return t;
+  }();
+  return table;
 }
 
-/* a resident group call (rs_group_schedule_tti_at): the same grid, the kernels that keep the cells' averages on the device */
-extern "C" hipError_t rs_launch_group_resident(const RsLaunch* p, int threads, hipStream_t stream) {
-  dim3 grid(p->n_cells), block(threads);
-  const int ept = (p->R * p->S + threads - 1) / threads;
-  if (!p->grp_avg || !p->grp_pending || !p->grp_last || !p->grp_gather || !p->grp_uid) return hipErrorInvalidValue;
-#define RS_LAUNCH_GROUP(SCHED_, EPT_) hipLaunchKernelGGL((rs_group_resident_kernel<SCHED_, EPT_>), grid, block, p->lds_bytes, stream, *p)
-  switch (p->sched) {
-    case 1: RS_LAUNCH_GROUP(1, 0); break;
-    case 7: RS_LAUNCH_GROUP(7, 0); break;
-    case 8: RS_LAUNCH_GROUP(8, 0); break;
-    case 101: RS_LAUNCH_GROUP(101, 0); break;
-    case 103: RS_LAUNCH_GROUP(103, 0); break;
-    case 10:
-      if (ept <= 1) RS_LAUNCH_GROUP(10, 1);
-      else if (ept <= 2) RS_LAUNCH_GROUP(10, 2);
-      else if (ept <= 3) RS_LAUNCH_GROUP(10, 3);
-      else if (ept <= 4) RS_LAUNCH_GROUP(10, 4);
-      else return hipErrorInvalidValue;
-      break;
-    case 9:
-      if (ept <= 1) RS_LAUNCH_GROUP(9, 1);
-      else if (ept <= 2) RS_LAUNCH_GROUP(9, 2);
-      else if (ept <= 3) RS_LAUNCH_GROUP(9, 3);
-      else if (ept <= 4) RS_LAUNCH_GROUP(9, 4);
-      else RS_LAUNCH_GROUP(9, 0);
-      break;
-    default: return hipErrorInvalidValue;
-  }
-#undef RS_LAUNCH_GROUP
-  return hipGetLastError();
-}
-
-/* a queued group call (rs_group_schedule_tti_queued): the same grid, the kernels that keep the cells' bearers on the device */
-extern "C" hipError_t rs_launch_group_queued(const RsLaunch* p, int threads, hipStream_t stream) {
-  dim3 grid(p->n_cells), block(threads);
-  const int ept = (p->R * p->S + threads - 1) / threads;
-  if (!p->grp_qavg || !p->grp_qpend || !p->grp_qhas || !p->grp_qdata || !p->grp_qin || !p->grp_last || !p->grp_gather || !p->grp_uid)
-    return hipErrorInvalidValue;
-#define RS_LAUNCH_GROUP(SCHED_, EPT_) hipLaunchKernelGGL((rs_group_queued_kernel<SCHED_, EPT_>), grid, block, p->lds_bytes, stream, *p)
-  switch (p->sched) {
-    case 7: RS_LAUNCH_GROUP(7, 0); break;
-    case 8: RS_LAUNCH_GROUP(8, 0); break;
-    case 101: RS_LAUNCH_GROUP(101, 0); break;
-    case 103: RS_LAUNCH_GROUP(103, 0); break;
-    case 9:
-      if (ept <= 1) RS_LAUNCH_GROUP(9, 1);
-      else if (ept <= 2) RS_LAUNCH_GROUP(9, 2);
-      else if (ept <= 3) RS_LAUNCH_GROUP(9, 3);
-      else if (ept <= 4) RS_LAUNCH_GROUP(9, 4);
-      else RS_LAUNCH_GROUP(9, 0);
-      break;
-    default: return hipErrorInvalidValue;
-  }
-#undef RS_LAUNCH_GROUP
-  return hipGetLastError();
-}
-
-/* a counted group call (rs_group_schedule_tti_counted): the queued call's grid and stores, the kernels that also keep the counters */
-extern "C" hipError_t rs_launch_group_counted(const RsLaunch* p, int threads, hipStream_t stream) {
-  dim3 grid(p->n_cells), block(threads);
-  const int ept = (p->R * p->S + threads - 1) / threads;
-  if (!p->grp_qavg || !p->grp_qpend || !p->grp_qhas || !p->grp_qdata || !p->grp_qin || !p->grp_last || !p->grp_gather || !p->grp_uid ||
-      !p->grp_cbytes || !p->grp_crbs || !p->grp_sent)
-    return hipErrorInvalidValue;
-#define RS_LAUNCH_GROUP(SCHED_, EPT_) hipLaunchKernelGGL((rs_group_counted_kernel<SCHED_, EPT_>), grid, block, p->lds_bytes, stream, *p)
-  switch (p->sched) {
-    case 7: RS_LAUNCH_GROUP(7, 0); break;
-    case 8: RS_LAUNCH_GROUP(8, 0); break;
-    case 101: RS_LAUNCH_GROUP(101, 0); break;
-    case 103: RS_LAUNCH_GROUP(103, 0); break;
-    case 9:
-      if (ept <= 1) RS_LAUNCH_GROUP(9, 1);
-      else if (ept <= 2) RS_LAUNCH_GROUP(9, 2);
-      else if (ept <= 3) RS_LAUNCH_GROUP(9, 3);
-      else if (ept <= 4) RS_LAUNCH_GROUP(9, 4);
-      else RS_LAUNCH_GROUP(9, 0);
-      break;
-    default: return hipErrorInvalidValue;
-  }
-#undef RS_LAUNCH_GROUP
-  return hipGetLastError();
-}
-
-/* a flows group call (rs_group_schedule_tti_flows): the same grid, scheduler 1's kernel that keeps the cells' flows on the device */
-extern "C" hipError_t rs_launch_group_flows(const RsLaunch* p, int threads, hipStream_t stream) {
-  dim3 grid(p->n_cells), block(threads);
-  if (p->sched != 1) return hipErrorInvalidValue;
-  if (!p->grp_qavg || !p->grp_qpend || !p->grp_qhas || !p->grp_qin || !p->grp_last || !p->grp_gather || !p->grp_uid || !p->grp_cbytes ||
-      !p->grp_crbs)
-    return hipErrorInvalidValue;
-  hipLaunchKernelGGL((rs_group_flows_kernel<1, 0>), grid, block, p->lds_bytes, stream, *p);
-  return hipGetLastError();
-}
-
-/* a run of resident group calls (rs_group_run_at): the same grid, the kernels that serve the slots' T TTIs in one launch */
-extern "C" hipError_t rs_launch_group_run(const RsLaunch* p, int threads, hipStream_t stream) {
-  dim3 grid(p->n_cells), block(threads);
-  const int ept = (p->R * p->S + threads - 1) / threads;
-  if (!p->grp_avg || !p->grp_pending || !p->grp_last || !p->grp_gather || !p->grp_uid) return hipErrorInvalidValue;
-#define RS_LAUNCH_GROUP(SCHED_, EPT_) hipLaunchKernelGGL((rs_group_run_kernel<SCHED_, EPT_>), grid, block, p->lds_bytes, stream, *p)
-  switch (p->sched) {
-    case 1: RS_LAUNCH_GROUP(1, 0); break;
-    case 8: RS_LAUNCH_GROUP(8, 0); break;
-    case 101: RS_LAUNCH_GROUP(101, 0); break;
-    case 103: RS_LAUNCH_GROUP(103, 0); break;
-    case 10:
-      if (ept <= 1) RS_LAUNCH_GROUP(10, 1);
-      else if (ept <= 2) RS_LAUNCH_GROUP(10, 2);
-      else if (ept <= 3) RS_LAUNCH_GROUP(10, 3);
-      else if (ept <= 4) RS_LAUNCH_GROUP(10, 4);
-      else return hipErrorInvalidValue;
-      break;
-    case 9:
-      if (ept <= 1) RS_LAUNCH_GROUP(9, 1);
-      else if (ept <= 2) RS_LAUNCH_GROUP(9, 2);
-      else if (ept <= 3) RS_LAUNCH_GROUP(9, 3);
-      else if (ept <= 4) RS_LAUNCH_GROUP(9, 4);
-      else RS_LAUNCH_GROUP(9, 0);
-      break;
-    default: return hipErrorInvalidValue;
-  }
-#undef RS_LAUNCH_GROUP
+/* a group call of the given form (RsGroupFormId): p->n_cells call slots, one workgroup each.  The index into the table costs what the
+ * switch over the scheduler and the ladder over the positions per lane cost before it. */
+extern "C" hipError_t rs_launch_group(const RsLaunch* p, int threads, int form, hipStream_t stream) {
+  if (form < 0 || form >= RS_GROUP_FORMS) return hipErrorInvalidValue;
+  const unsigned sets = rs_group_form(form).sets;
+  if ((sets & RS_GROUP_SET_CELL) && (!p->grp_last || !p->grp_gather || !p->grp_uid)) return hipErrorInvalidValue;
+  if ((sets & RS_GROUP_SET_AVERAGES) && (!p->grp_avg || !p->grp_pending)) return hipErrorInvalidValue;
+  if ((sets & RS_GROUP_SET_BEARERS) && (!p->grp_qavg || !p->grp_qpend || !p->grp_qhas || !p->grp_qin)) return hipErrorInvalidValue;
+  if ((sets & RS_GROUP_SET_DATA) && !p->grp_qdata) return hipErrorInvalidValue;
+  if ((sets & RS_GROUP_SET_COUNTERS) && (!p->grp_cbytes || !p->grp_crbs)) return hipErrorInvalidValue;
+  if ((sets & RS_GROUP_SET_SENT) && !p->grp_sent) return hipErrorInvalidValue;
+  const int si = rs_group_sched_index(p->sched), ept = rs_group_form_ept(p->sched, (p->R * p->S + threads - 1) / threads);
+  const void* const fn = (si < 0 || ept < 0) ? nullptr : rs_group_kernels().fn[form][si][ept];
+  if (!fn) return hipErrorInvalidValue;
+  RsLaunch block = *p;
+  void* args[] = {&block};
+  (void)hipLaunchKernel(fn, dim3(p->n_cells), dim3(threads), args, p->lds_bytes, stream);
   return hipGetLastError();
 }
 
@@ -1257,40 +1129,16 @@ extern "C" hipError_t rs_prepare_kernels(int max_lds_bytes) {
                        (const void*)rs_cell_kernel<8, 0, false, true>, (const void*)rs_cell_kernel<101, 0, false, true>,
                        (const void*)rs_cell_kernel<103, 0, false, true>, (const void*)rs_cell_kernel<9, 0, false, true>,
                        (const void*)rs_cell_kernel<9, 1, false, true>, (const void*)rs_cell_kernel<9, 2, false, true>,
-                       (const void*)rs_cell_kernel<9, 3, false, true>, (const void*)rs_cell_kernel<9, 4, false, true>,
-                       (const void*)rs_group_kernel<1, 0>,  (const void*)rs_group_kernel<7, 0>,  (const void*)rs_group_kernel<8, 0>,
-                       (const void*)rs_group_kernel<101, 0>, (const void*)rs_group_kernel<103, 0>,
-                       (const void*)rs_group_kernel<10, 1>, (const void*)rs_group_kernel<10, 2>, (const void*)rs_group_kernel<10, 3>,
-                       (const void*)rs_group_kernel<10, 4>, (const void*)rs_group_kernel<9, 0>,  (const void*)rs_group_kernel<9, 1>,
-                       (const void*)rs_group_kernel<9, 2>,  (const void*)rs_group_kernel<9, 3>,  (const void*)rs_group_kernel<9, 4>,
-                       (const void*)rs_group_resident_kernel<1, 0>,  (const void*)rs_group_resident_kernel<7, 0>,
-                       (const void*)rs_group_resident_kernel<8, 0>,  (const void*)rs_group_resident_kernel<101, 0>,
-                       (const void*)rs_group_resident_kernel<103, 0>, (const void*)rs_group_resident_kernel<10, 1>,
-                       (const void*)rs_group_resident_kernel<10, 2>, (const void*)rs_group_resident_kernel<10, 3>,
-                       (const void*)rs_group_resident_kernel<10, 4>, (const void*)rs_group_resident_kernel<9, 0>,
-                       (const void*)rs_group_resident_kernel<9, 1>,  (const void*)rs_group_resident_kernel<9, 2>,
-                       (const void*)rs_group_resident_kernel<9, 3>,  (const void*)rs_group_resident_kernel<9, 4>,
-                       (const void*)rs_group_queued_kernel<7, 0>,   (const void*)rs_group_queued_kernel<8, 0>,
-                       (const void*)rs_group_queued_kernel<101, 0>, (const void*)rs_group_queued_kernel<103, 0>,
-                       (const void*)rs_group_queued_kernel<9, 0>,   (const void*)rs_group_queued_kernel<9, 1>,
-                       (const void*)rs_group_queued_kernel<9, 2>,   (const void*)rs_group_queued_kernel<9, 3>,
-                       (const void*)rs_group_queued_kernel<9, 4>,
-                       (const void*)rs_group_counted_kernel<7, 0>,   (const void*)rs_group_counted_kernel<8, 0>,
-                       (const void*)rs_group_counted_kernel<101, 0>, (const void*)rs_group_counted_kernel<103, 0>,
-                       (const void*)rs_group_counted_kernel<9, 0>,   (const void*)rs_group_counted_kernel<9, 1>,
-                       (const void*)rs_group_counted_kernel<9, 2>,   (const void*)rs_group_counted_kernel<9, 3>,
-                       (const void*)rs_group_counted_kernel<9, 4>,
-                       (const void*)rs_group_flows_kernel<1, 0>,
-                       (const void*)rs_group_run_kernel<1, 0>,   (const void*)rs_group_run_kernel<8, 0>,
-                       (const void*)rs_group_run_kernel<101, 0>, (const void*)rs_group_run_kernel<103, 0>,
-                       (const void*)rs_group_run_kernel<10, 1>,  (const void*)rs_group_run_kernel<10, 2>,
-                       (const void*)rs_group_run_kernel<10, 3>,  (const void*)rs_group_run_kernel<10, 4>,
-                       (const void*)rs_group_run_kernel<9, 0>,   (const void*)rs_group_run_kernel<9, 1>,
-                       (const void*)rs_group_run_kernel<9, 2>,   (const void*)rs_group_run_kernel<9, 3>,
-                       (const void*)rs_group_run_kernel<9, 4>};
+                       (const void*)rs_cell_kernel<9, 3, false, true>, (const void*)rs_cell_kernel<9, 4, false, true>};
 #undef RS_BOTH
 
   for (const void* f : fns) {
+    hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds_bytes);
+    if (e != hipSuccess) return e;
+  }
+  const RsGroupKernels& group = rs_group_kernels();
+  for (const void* f : (const void* const(&)[RS_GROUP_FORMS * RS_GROUP_SCHEDS * 5])group.fn) {
+    if (!f) continue;
     hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds_bytes);
     if (e != hipSuccess) return e;
   }

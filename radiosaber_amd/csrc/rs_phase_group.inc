@@ -6,70 +6,55 @@
  * here assumes that the workgroups are resident together -- puts the word back to 0 for the next launch and publishes the call's
  * sequence number to the host.  Its acquire of the counter orders it behind every other workgroup's fence and release.
  *
- * The entry points of rs_kernels.hip include this text as their body, as rs_cell_body includes its phases: the kernels built into the
- * library (rs_group_kernel, rs_group_resident_kernel, rs_group_queued_kernel, rs_group_counted_kernel, rs_group_flows_kernel: shape in the launch block) and a group's own run-time
- * builds (rs_group_kernel_jit, rs_group_specialize; rs_group_resident_kernel_jit, rs_group_specialize_resident;
- * rs_group_queued_kernel_jit, rs_group_specialize_queued; rs_group_counted_kernel_jit, rs_group_specialize_counted;
- * rs_group_flows_kernel_jit, rs_group_specialize_flows).
- * The includer provides `p` (the launch block), `lds` and four constants: kGrpSched, kGrpEpt, kGrpFixed -- shape, workgroup size and LDS
- * carve are the constants RS_JIT_*, RS_JIT_U being the user CAPACITY while the users of a slot stay the slot header's word -- and
- * kGrpLean -- the plain call's per-launch options are constants too.  (Text, not a function of its own: the built-in instantiations
- * must stay the machine code they were, and a wrapper function around the inlined cell body changed their instruction counts.)
+ * The entry points of rs_kernels.hip include this text as their body, as rs_cell_body includes its phases: the six kernel templates
+ * built into the library (shape in the launch block) and the <name>_jit entry point of a group's run-time builds.  (Text, not a
+ * function of its own: the built-in instantiations must stay the machine code they were, and a wrapper function around the inlined
+ * cell body changed their instruction counts.)  The includer provides `p` (the launch block), `lds` and five constants:
+ *   kGrpForm             the form of the call, a row of rs_group_form (rs_device.h): the table says which of the texts below a form
+ *                        takes (res, que, cnt, flow, run), which launch-block pointers they dereference, and which schedulers it has
+ *                        kernels for; with a fact false none of its text reaches the instantiation
+ *   kGrpSched, kGrpEpt   the body's scheduler and sort form
+ *   kGrpFixed            a run-time build: shape, workgroup size and LDS carve are the constants RS_JIT_* -- RS_JIT_U being the user
+ *                        CAPACITY while the users of a slot stay the slot header's word --, so the updates' ranges, the stores' strides,
+ *                        the loop strides and the LDS offsets below are constants too.  Order of operations and arithmetic are the
+ *                        same in both kinds of kernel, in every form.  (The update of the averages stands written out in each of the
+ *                        four texts that have one, and each text sets up its own shape words: one helper function for the update,
+ *                        and one preamble for the shape words, each changed instruction streams -- profiles/group_forms_table.md.)
+ *   kGrpLean             the plain call's per-launch options are constants too (the slots' HoL delays and priority flags are not read)
  *
- * A fifth constant, kGrpRes, makes the resident form (rs_group_schedule_tti_at, rs_group_resident_kernel): the cell keeps its users' PF
- * averages, the bytes granted since their last update and the time of that update in HBM.  Before the body the workgroup applies
- * RadioBearer::UpdateAverageTransmissionRate to EVERY user of the cell (ref: src/flows/radio-bearer.cpp:139-164, the operations of
- * rs_phase_p0_p1.inc's batch EWMA in their order), hands the body the averages of the call's users, and behind the body adds each
- * served user's grant -- which the one-TTI body leaves per call position in LDS (s_tx, rs_phase_p5.inc) -- to the user's pending
- * bytes.  A compile-time constant for the reason above: with kGrpRes false none of this text reaches the other instantiations.  Under
- * kGrpFixed the resident text's shape is constant as well: the update's range and the stores' stride are RS_JIT_U, the loop strides
- * RS_JIT_NT, the grants' LDS offset the constexpr carve's off_tx.  Order of operations and arithmetic are the same in both forms.
- *
- * A sixth constant, kGrpQue, makes the queued form (rs_group_schedule_tti_queued, rs_group_queued_kernel; never with kGrpRes):
- * the cell keeps BOTH bearers of every user -- average, pending bytes, existence --
- * and the slot brings m_dataToTransmit[2] per call position.  The update strides over the 2 U bearers, the call's averages are the
- * sums over the bearers with data, the grant is split over the bearers from the highest priority down (DoStopSchedule), and a slot
- * without users (U = 0 in its header) does the update alone: the body and the credit are skipped, uniformly for the workgroup.  With
- * kGrpQue false none of this text reaches the other instantiations.  Under kGrpFixed (rs_group_queued_kernel_jit) the queued text's
- * shape is constant as the resident text's: the update's range and the strides of the [U][2] stores are 2 * RS_JIT_U, the loop strides
- * RS_JIT_NT, the grants' LDS offset the constexpr carve's off_tx.  Order of operations and arithmetic are the same in both forms.
- *
- * A seventh constant, kGrpCnt, makes the counted form (rs_group_schedule_tti_counted, rs_group_counted_kernel; only with kGrpQue):
- * the cell also keeps m_cumulateBytes / m_cumulateRBs of both bearers of every user, and the slot gets back the bytes sent
- * per call position and bearer.  All of it sits in step 4's per-position loop: the thread that credits a bearer adds the bytes and the
- * position's allocated PRBs to the bearer's 64-bit counters and writes the position's row of the slot's sent block.  The PRB count is
- * G times the RBGs the position holds -- the body's link adaptation leaves, per call position, the set of RBG lanes that share it in
- * RsMisc::maskA / maskB (rs_phase_p5.inc), and the closing barrier hands them to every thread as it hands over the grants.  With kGrpCnt
- * false none of this text reaches the other instantiations.  Under kGrpFixed (rs_group_counted_kernel_jit) the counted part of step 4
- * takes its shape as the queued part does: the RsMisc block lies at the constexpr carve's off_misc, the PRBs per RBG are RS_JIT_G.
- *
- * An eighth constant, kGrpFlow, makes the flow-resident form of scheduler 1 (rs_group_schedule_tti_flows, rs_group_flows_kernel; never
- * with kGrpRes / kGrpQue): DL_PF_PacketScheduler races FLOWS -- bearers --, not users, so a call position is one bearer
- * of one user (RRC-container order: a user may hold two adjacent positions).  The cell keeps the queued form's bearer stores and the
- * counted form's counters; the update is the queued form's step 1, the call's average of a position is the flow's own (scheduler 1
- * divides by it as it is: no sum, no 1 +), and behind the body the WHOLE transport block goes to the flow -- pending bytes, bytes
- * counter, PRB counter --, no min with the data (ref: dl-pf-packet-scheduler.cpp:80-85).  The slot's bearer words (0 or 1 per call
- * position) travel where the queued form's data words do (grp_qin), the gate is the plain PF call's (data_to_transmit, packed by the
- * host).  With kGrpFlow false none of this text reaches the other instantiations.  Under kGrpFixed
- * (rs_group_flows_kernel_jit) the flows text's shape is constant as the queued text's: the update's range and the strides of the [U][2]
- * stores are 2 * RS_JIT_U, the loop strides RS_JIT_NT, the LDS offsets the constexpr carve's off_tx and off_misc, the PRBs per RBG
- * RS_JIT_G.  Order of operations and arithmetic are the same in both forms.
- *
- * A ninth constant, kGrpRun, makes the run form of the resident wrapper (rs_group_run_at, rs_group_run_kernel; only with kGrpRes, never
- * NVS): the workgroup serves T consecutive TTIs of its cell -- the resident form's three steps, T times, in their order and
- * arithmetic, then the completion chain once.  The header is read once; what changes per TTI -- the clock and the rand() pair --
- * comes from the slot's table (RsGroupCell::run_table), output block t lies run_out_step bytes behind block t - 1, and the users are
- * the slot's for the whole run.  TTI 0 does with the CQI reports what the slot's image_mode says; under a cqi_epoch the later TTIs
- * load the cell's image (and read the cell's per-PRB store) as calls of their own would, without one they read the slot's blocks
- * again.  Between two TTIs stands one workgroup barrier behind a device-scope fence: the credit of TTI t goes by call position, the
- * update of TTI t + 1 by user id -- other threads --, and the body's load phase overwrites the LDS grants the credit reads.  A text
- * of its own below: with kGrpRun false none of it reaches the other instantiations, whose resident text is left as it is.  Under
- * kGrpFixed (rs_group_run_kernel_jit, rs_group_specialize_run) the run text's shape is constant as the resident text's: the update's
- * range and the stores' stride are RS_JIT_U, the loop strides RS_JIT_NT, the grants' LDS offset the constexpr carve's off_tx; under
- * kGrpLean the slots' HoL delays and priority flags are not read.  Order of operations and arithmetic are the same in both forms. */
-  static_assert(!kGrpCnt || kGrpQue, "the counted form is the queued form's");
-  static_assert(!kGrpRun || (kGrpRes && kGrpSched != 7), "the run form is the resident form's, and never NVS");
-  static_assert(!kGrpFlow || (!kGrpRes && !kGrpQue && !kGrpCnt && kGrpSched == 1), "the flows form is scheduler 1's, a resident form of its own");
+ * res (rs_group_schedule_tti_at): the cell keeps its users' PF averages, the bytes granted since their last update and the time of that
+ *   update in HBM.  Before the body the workgroup applies RadioBearer::UpdateAverageTransmissionRate to EVERY user of the cell
+ *   (ref: src/flows/radio-bearer.cpp:139-164, the operations of rs_phase_p0_p1.inc's batch EWMA in their order), hands the body the
+ *   averages of the call's users, and behind the body adds each served user's grant -- which the one-TTI body leaves per call position
+ *   in LDS (s_tx, rs_phase_p5.inc) -- to the user's pending bytes.
+ * que (rs_group_schedule_tti_queued; never with res): the cell keeps BOTH bearers of every user -- average, pending bytes, existence --
+ *   and the slot brings m_dataToTransmit[2] per call position.  The update strides over the 2 U bearers, the call's averages are the
+ *   sums over the bearers with data, the grant is split over the bearers from the highest priority down (DoStopSchedule), and a slot
+ *   without users (U = 0 in its header) does the update alone: the body and the credit are skipped, uniformly for the workgroup.
+ * cnt (rs_group_schedule_tti_counted; only with que): the cell also keeps m_cumulateBytes / m_cumulateRBs of both bearers of every
+ *   user, and the slot gets back the bytes sent per call position and bearer.  All of it sits in step 4's per-position loop: the thread
+ *   that credits a bearer adds the bytes and the position's allocated PRBs to the bearer's 64-bit counters and writes the position's
+ *   row of the slot's sent block.  The PRB count is G times the RBGs the position holds -- the body's link adaptation leaves, per call
+ *   position, the set of RBG lanes that share it in RsMisc::maskA / maskB (rs_phase_p5.inc), and the closing barrier hands them to
+ *   every thread as it hands over the grants.
+ * flow (rs_group_schedule_tti_flows; scheduler 1, never with res / que): DL_PF_PacketScheduler races FLOWS -- bearers --, not users, so a
+ *   call position is one bearer of one user (RRC-container order: a user may hold two adjacent positions).  The cell keeps the queued
+ *   form's bearer stores and the counted form's counters; the update is the queued form's step 1, the call's average of a position is
+ *   the flow's own (scheduler 1 divides by it as it is: no sum, no 1 +), and behind the body the WHOLE transport block goes to the
+ *   flow -- pending bytes, bytes counter, PRB counter --, no min with the data (ref: dl-pf-packet-scheduler.cpp:80-85).  The slot's
+ *   bearer words (0 or 1 per call position) travel where the queued form's data words do (grp_qin), the gate is the plain PF call's
+ *   (data_to_transmit, packed by the host).
+ * run (rs_group_run_at; only with res, never NVS): the workgroup serves T consecutive TTIs of its cell -- the resident form's three
+ *   steps, T times, in their order and arithmetic, then the completion chain once.  The header is read once; what changes per TTI --
+ *   the clock and the rand() pair -- comes from the slot's table (RsGroupCell::run_table), output block t lies run_out_step bytes
+ *   behind block t - 1, and the users are the slot's for the whole run.  TTI 0 does with the CQI reports what the slot's image_mode
+ *   says; under a cqi_epoch the later TTIs load the cell's image (and read the cell's per-PRB store) as calls of their own would,
+ *   without one they read the slot's blocks again.  Between two TTIs stands one workgroup barrier behind a device-scope fence: the
+ *   credit of TTI t goes by call position, the update of TTI t + 1 by user id -- other threads --, and the body's load phase overwrites
+ *   the LDS grants the credit reads.  A text of its own below: the other instantiations' resident text is left as it is. */
+  constexpr RsGroupForm kGrpF = rs_group_form(kGrpForm);
+  constexpr bool kGrpRes = kGrpF.res, kGrpQue = kGrpF.que, kGrpCnt = kGrpF.cnt, kGrpFlow = kGrpF.flow, kGrpRun = kGrpF.run;
+  static_assert(kGrpFixed ? rs_group_form_builds(kGrpForm, kGrpSched) : rs_group_form_serves(kGrpForm, kGrpSched), "no kernel of this form for this scheduler (rs_group_form, rs_device.h)");
   const uint8_t* const in = p.grp_in + (size_t)blockIdx.x * (size_t)p.grp_in_stride;
   uint8_t* const out = p.grp_out + (size_t)blockIdx.x * (size_t)p.grp_out_stride;
   const RsGroupCell* const h = (const RsGroupCell*)in;
@@ -117,6 +102,7 @@
       for (int i = threadIdx.x; i < n16; i += (kGrpFixed ? (unsigned)RS_JIT_NT : blockDim.x)) ((uint4*)store)[i] = src[i];
     }
   }
+  constexpr RsCarve kGrpCv = rs_carve(RS_JIT_S, RS_JIT_U, RS_JIT_R, RS_JIT_SCHED, RS_JIT_NT, RS_JIT_CARVEQ, RS_JIT_WIN); /* (the body's own carve: a run-time build's LDS offsets) */
 #ifdef RS_STAMPS
   /* diagnostic build: every call slot stamps a row of its own (the body stamps row `cell` of its block, and cell is 0 there) */
   if (p.stamps) q.stamps = p.stamps + (size_t)blockIdx.x * 20;
@@ -136,7 +122,6 @@
     const int32_t* const uid = (const int32_t*)(data + in_uid);
     double* const row = p.grp_gather + (size_t)cell * (size_t)n_all;
     int32_t* const ids = p.grp_uid + (size_t)cell * (size_t)n_all;
-    constexpr RsCarve kGrpCv = rs_carve(RS_JIT_S, RS_JIT_U, RS_JIT_R, RS_JIT_SCHED, RS_JIT_NT, RS_JIT_CARVEQ, RS_JIT_WIN); /* (the body's own carve) */
     const int32_t* const granted = (const int32_t*)(lds + (kGrpFixed ? kGrpCv.off_tx : p.off_tx));
     if constexpr (kGrpLean) { /* (the lean build: as behind the other forms' preambles -- here the body is called inside the loop) */
       q.hol = nullptr;
@@ -383,7 +368,6 @@
     if (q.U != 0) {
       const int nthreads = kGrpFixed ? RS_JIT_NT : (int)blockDim.x;
       const int n_all = kGrpFixed ? RS_JIT_U : p.U;
-      constexpr RsCarve kGrpCv = rs_carve(RS_JIT_S, RS_JIT_U, RS_JIT_R, RS_JIT_SCHED, RS_JIT_NT, RS_JIT_CARVEQ, RS_JIT_WIN); /* (the body's own carve) */
       const int32_t* const granted = (const int32_t*)(lds + (kGrpFixed ? kGrpCv.off_tx : p.off_tx));
       int32_t* const b_pend = p.grp_qpend + (size_t)cell * 2 * (size_t)n_all;
       const int32_t* const ids = p.grp_uid + (size_t)cell * (size_t)n_all;    /* entry i: written by this thread before the body */
@@ -454,7 +438,6 @@
     if (q.U != 0) {
       const int nthreads = kGrpFixed ? RS_JIT_NT : (int)blockDim.x;
       const int n_all = kGrpFixed ? RS_JIT_U : p.U;
-      constexpr RsCarve kGrpCv = rs_carve(RS_JIT_S, RS_JIT_U, RS_JIT_R, RS_JIT_SCHED, RS_JIT_NT, RS_JIT_CARVEQ, RS_JIT_WIN); /* (the body's own carve) */
       const int32_t* const granted = (const int32_t*)(lds + (kGrpFixed ? kGrpCv.off_tx : p.off_tx));
       int32_t* const b_pend = p.grp_qpend + (size_t)cell * 2 * (size_t)n_all;
       int64_t* const c_bytes = p.grp_cbytes + (size_t)cell * 2 * (size_t)n_all;
@@ -485,7 +468,6 @@
      *    named once per call, a cell once per launch: plain adds. */
     const int nthreads = kGrpFixed ? RS_JIT_NT : (int)blockDim.x;
     const int n_all = kGrpFixed ? RS_JIT_U : p.U;
-    constexpr RsCarve kGrpCv = rs_carve(RS_JIT_S, RS_JIT_U, RS_JIT_R, RS_JIT_SCHED, RS_JIT_NT, RS_JIT_CARVEQ, RS_JIT_WIN); /* (the body's own carve) */
     const int32_t* const granted = (const int32_t*)(lds + (kGrpFixed ? kGrpCv.off_tx : p.off_tx));
     int32_t* const r_pend = p.grp_pending + (size_t)cell * (size_t)n_all;
     const int in_uid = word(&h->in_uid);
