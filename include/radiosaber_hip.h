@@ -38,7 +38,8 @@ extern "C" {
                                rs_group_set_counters / rs_group_get_counters / rs_group_schedule_tti_counted (a bearer-resident group cell's m_cumulateBytes / m_cumulateRBs on the device, the bytes sent per bearer returned per call),
                                rs_group_set_flows / rs_group_get_flows / rs_group_schedule_tti_flows (scheduler 1's flows of a group cell resident on the device: averages, pending bytes and counters per bearer, the whole block credited to the flow),
                                rs_group_run_at + RS_GROUP_MAX_RUN (T consecutive TTIs of average-resident group cells in one launch),
-                               rs_group_specialize_run / rs_group_run_jit_status / rs_jit_selfcheck_group_run (a group's own builds of the run kernel, self-checked per run on every TTI's outputs and on state);
+                               rs_group_specialize_run / rs_group_run_jit_status / rs_jit_selfcheck_group_run (a group's own builds of the run kernel, self-checked per run on every TTI's outputs and on state),
+                               rs_group_set_avg_counters / rs_group_get_avg_counters / rs_group_run_counted_at (an average-resident group cell's m_cumulateBytes / m_cumulateRBs per user on the device, advanced by runs that may return no per-TTI outputs at all);
                                rs_config.link_tables (RS_LINK_*) + rs_link_tables_pinned / rs_link_tables_compare, rs_tti_in.cqi_epoch (the context keeps the
                                CQI image of an unchanged report set on the device), rs_ctx_jit_status (a specialised context checks its run-time build against the
                                built-in kernel during its first calls), rs_batch_config.selfcheck -1 / 0 / 1 with run-time builds verified by default and the
@@ -473,6 +474,40 @@ int rs_group_run_jit_status(rs_group* g, char* msg, size_t msglen);
 /* build check without a GPU: do the general and the lean run build of a group of this shape compile?  (the larger code size, or a
  * negative value with the compiler's log in err; negative with a message for RS_SCHED_NVS and RS_SCHED_NVS_NONGREEDY, which have no run) */
 int rs_jit_selfcheck_group_run(int n_slices, int n_users, int n_rbgs, int rbg_size, int threads, int sched, char* err, size_t errlen);
+
+/* Counted runs (ABI 11 addition, no layout changed): per-user byte and RB counters for average-resident cells, and runs that advance
+ * them.  A backlogged cell holds one InfiniteBuffer bearer per user, so RadioBearer::m_cumulateBytes / m_cumulateRBs -- the numbers
+ * behind every "app:" line and every per-slice throughput figure -- are one pair per user id of the config.  AVG-COUNTED is a state on
+ * top of average-resident, as counted is on top of bearer-resident:
+ * rs_group_set_avg_counters makes an average-resident cell avg-counted and sets its counters ([U] each, by user id; NULL = zeros).  A
+ *   synchronising copy outside the fast path.  RS_ERR_STATE when the cell is not average-resident (the message names the cell),
+ *   RS_ERR_INVALID for a negative value.  rs_group_set_avg on an avg-counted cell keeps the state and the counters (as
+ *   rs_group_set_bearers keeps a counted cell's); rs_group_set_bearers and rs_group_set_flows end it; a call that fails with RS_ERR_HIP
+ *   ends it for the cells it named.  rs_group_get_counters and rs_group_set_counters stay bearer-only: their answers on such a cell are
+ *   what they were.
+ * rs_group_get_avg_counters returns the counters as they are after the last call; RS_ERR_STATE when the cell is not avg-counted.
+ * rs_group_run_counted_at is rs_group_run_at with a credit added.  Every rule and every check of rs_group_run_at holds, each before
+ *   anything is launched, and every named cell must be avg-counted (RS_ERR_STATE, the message names the cell).  Order of operations and
+ *   every result are rs_group_run_at's: every rs_tti_out field, averages, pending bytes, last_update, slice state, image records,
+ *   rs_group_image_stats; rs_group_launch_count grows by 1.  In addition, in step 3 of every TTI, every call position i with a grant
+ *   (bytes != 0, bytes being what step 3 adds to the pending bytes: min(user_tbs_bits / 8, 100000000)) is credited as DoStopSchedule
+ *   credits one bearer per user (ref: downlink-transport-scheduler.cpp:177-190; RS_SCHED_PF: dl-pf-packet-scheduler.cpp:84-85):
+ *       cum_bytes[user_id[i]] += bytes;   cum_rbs[user_id[i]] += user_nprb[i];
+ *   A position without a grant moves no counter, a user the call does not name moves none; a TTI whose clock step is 0 still credits
+ *   (only the update is skipped).
+ *   out == NULL is the output-free run, for the whole call: the device writes no rs_tti_out row, the host unpacks none, the output
+ *   blocks do not grow; state, counters, image records and statistics are what the same run with outputs leaves.  (The upper_*
+ *   uniformity rule then has nothing to check.)
+ * rs_group_run_at, rs_group_schedule_tti_at and rs_group_schedule_tti serve an avg-counted cell as before and leave its counters alone
+ * (as the queued calls leave a counted cell's).  rs_group_kernel_name returns "rs_group_run_counted_kernel<sched, ept>" while a counted
+ * run was the last call served.  Counted runs execute the kernel built into the library, before and after every rs_group_specialize*:
+ * rs_group_specialize_run in particular does not reach them; a seventh self-checked pair is left to a later change, as it was for
+ * every other form. */
+int rs_group_set_avg_counters(rs_group* g, int32_t cell, const int64_t* cum_bytes /* [U] or NULL = zeros */, const int64_t* cum_rbs /* [U] or NULL */);
+int rs_group_get_avg_counters(rs_group* g, int32_t cell, int64_t* cum_bytes /* [U] or NULL */, int64_t* cum_rbs /* [U] or NULL */);
+int rs_group_run_counted_at(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in /* [n] */, int32_t n_ttis,
+                            const double* now /* [n][n_ttis] */, const int32_t* rands /* [n][n_ttis][2]; NULL only for RS_SCHED_PF */,
+                            rs_tti_out* out /* [n][n_ttis], or NULL: no per-TTI outputs */);
 
 /* Resident bearers (ABI 11 addition, no layout changed): the second resident form of a group's cell.  The cell keeps, per user id of the
  * config and per bearer (MAX_BEARERS = 2, index = the bearer's priority), RadioBearer's average rate and the bytes DoStopSchedule

@@ -119,6 +119,7 @@ ABI_SYMBOLS = [
     "rs_group_specialize_counted", "rs_group_counted_jit_status", "rs_jit_selfcheck_group_counted",
     "rs_group_specialize_flows", "rs_group_flows_jit_status", "rs_jit_selfcheck_group_flows",
     "rs_group_specialize_run", "rs_group_run_jit_status", "rs_jit_selfcheck_group_run",
+    "rs_group_set_avg_counters", "rs_group_get_avg_counters", "rs_group_run_counted_at",
 ]
 
 _lib = None
@@ -176,6 +177,10 @@ def lib():
     L.rs_group_resident_jit_status.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.rs_jit_selfcheck_group_resident.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
     L.rs_group_set_counters.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.rs_group_set_avg_counters.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.rs_group_get_avg_counters.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.rs_group_run_counted_at.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_TtiIn), C.c_int32, C.POINTER(C.c_double),
+                                          C.POINTER(C.c_int32), C.POINTER(_TtiOut)]
     L.rs_group_get_counters.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.rs_group_schedule_tti_counted.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_TtiIn), C.POINTER(_TtiOut),
                                                 C.POINTER(C.c_double), C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32))]
@@ -876,6 +881,9 @@ class GroupScheduler:
         """rs_group_run_at: T consecutive schedule_tti_at calls in one launch.  calls[k] as for schedule_tti_at, given once per cell
         (rand0 / rand1 are not read); now is [T] (the same clock for every cell) or [n][T]; rands is [n][T][2], the rand() pair of each
         cell's TTIs (None: RS_SCHED_PF only).  Returns results[k][t]."""
+        return self._run(lib().rs_group_run_at, calls, now, rands, cell_ids, True)
+
+    def _run(self, fn, calls, now, rands, cell_ids, outputs):
         n = len(calls)
         t = np.asarray(now, np.float64)
         assert t.ndim in (1, 2) and (t.ndim == 1 or t.shape[0] == n)
@@ -898,9 +906,34 @@ class GroupScheduler:
             results.append(row[:T])
         ids = None if cell_ids is None else np.ascontiguousarray(cell_ids, np.int32)
         assert ids is None or ids.shape == (n,)
-        _check(lib().rs_group_run_at(self._h, n, _p(ids, C.c_int32) if ids is not None else None, ins, T, _p(t, C.c_double),
-                                     _p(r, C.c_int32) if r is not None else None, outs))
-        return results
+        _check(fn(self._h, n, _p(ids, C.c_int32) if ids is not None else None, ins, T, _p(t, C.c_double),
+                  _p(r, C.c_int32) if r is not None else None, outs if outputs else None))
+        return results if outputs else None
+
+    # ---- counted runs: m_cumulateBytes / m_cumulateRBs per user of an average-resident cell stay on the device too ----
+    def set_avg_counters(self, cell, cum_bytes=None, cum_rbs=None):
+        """rs_group_set_avg_counters: makes an average-resident `cell` avg-counted with cum_bytes / cum_rbs int64 [n_users] by user id
+        (None: zeros).  Any time between two calls; outside the fast path."""
+        U = self.slices.n_users
+        cb = None if cum_bytes is None else np.ascontiguousarray(cum_bytes, np.int64)
+        cr = None if cum_rbs is None else np.ascontiguousarray(cum_rbs, np.int64)
+        assert (cb is None or cb.shape == (U,)) and (cr is None or cr.shape == (U,))
+        _check(lib().rs_group_set_avg_counters(self._h, cell, _p(cb, C.c_int64) if cb is not None else None,
+                                               _p(cr, C.c_int64) if cr is not None else None))
+
+    def get_avg_counters(self, cell):
+        """(cum_bytes int64 [n_users], cum_rbs int64 [n_users]) of an avg-counted cell: a synchronising copy, not part of a TTI."""
+        U = self.slices.n_users
+        cb = np.zeros(U, np.int64)
+        cr = np.zeros(U, np.int64)
+        _check(lib().rs_group_get_avg_counters(self._h, cell, _p(cb, C.c_int64), _p(cr, C.c_int64)))
+        return cb, cr
+
+    def run_counted_at(self, calls: Sequence[dict], now, rands=None, cell_ids: Optional[Sequence[int]] = None, outputs=True):
+        """rs_group_run_counted_at: run_at for avg-counted cells, same calls and same results; every grant also adds its bytes and the
+        position's PRBs to the user's counters.  outputs=False is the output-free run: nothing is written per TTI or unpacked, state
+        and counters are what the run with outputs leaves, and the call returns None; else results[k][t]."""
+        return self._run(lib().rs_group_run_counted_at, calls, now, rands, cell_ids, outputs)
 
     # ---- resident bearers: both bearers of every user stay on the device, finite queues are credited there ----
     def set_bearers(self, cell, has_bearer, avg, last_update):

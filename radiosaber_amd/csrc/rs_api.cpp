@@ -1894,7 +1894,7 @@ int pack_tti(const rs_batch* b, const rs_tti_in* in, const rs_tti_out* out, uint
    * the block carries the call's user ids instead when it names them (4 of the 8 bytes per user) */
   if (resident_avg && in->avg_rate) return fail(RS_ERR_INVALID, "avg_rate must be NULL: the cell's averages are resident on the device");
   if ((!in->cqi && !in->cqi_prb) || (!in->avg_rate && !resident_avg)) return fail(RS_ERR_INVALID, "null cqi/avg_rate");
-  if (!out->rbg_to_user || !out->user_tbs_bits) return fail(RS_ERR_INVALID, "null output array");
+  if (out && (!out->rbg_to_user || !out->user_tbs_bits)) return fail(RS_ERR_INVALID, "null output array"); /* (out == null: a run without outputs) */
   const CtxLayout l = ctx_layout(n, R, S, b->G, b->sched == RS_SCHED_NVS_NONGREEDY);
   pk->l = l;
   uint8_t* h_slice = h_in + l.slice;
@@ -2494,13 +2494,18 @@ struct rs_group {
   int32_t *h_sent = nullptr, *z_sent = nullptr, *d_sent = nullptr;
   int32_t *h_sent2 = nullptr, *z_sent2 = nullptr, *d_sent2 = nullptr;
   std::vector<uint8_t> counted;
+  /* counted runs (rs_group_set_avg_counters, rs_group_run_counted_at): per cell [U] m_cumulateBytes / m_cumulateRBs beside the resident
+   * averages, in stores of their own (allocated by the first rs_group_set_avg_counters; the launch block's grp_cbytes / grp_crbs point
+   * at them in a counted run), and which cells are avg-counted -- a state on top of resident[cell] == 1 */
+  int64_t *d_acbytes = nullptr, *d_acrbs = nullptr;
+  std::vector<uint8_t> avg_counted;
   /* resident flows (rs_group_set_flows, rs_group_schedule_tti_flows; scheduler 1 alone): resident[cell] == 3.  The cell's flows live in
    * the bearer stores and the counter stores above (a cell is resident in one form at a time), has_bearer mirrors their existence
    * bytes, and the slots' bearer words (0 or 1 per call position) travel in h_qin, one word per position. */
   /* rs_group_kernel_name: the last call's form (a row of kGroupForms), whether a run-time build served it, the built-in kernels' names by row */
   int last_call_form = 0;
   bool last_call_jit = false;
-  char kname[RS_GROUP_FORMS][56] = {"", "", "", "", "", ""}, kname_jit[RS_GROUP_FORMS][40] = {"", "", "", "", "", ""};
+  char kname[RS_GROUP_FORMS][56] = {"", "", "", "", "", "", ""}, kname_jit[RS_GROUP_FORMS][40] = {"", "", "", "", "", "", ""};
 };
 
 extern "C" hipError_t rs_launch_group(const RsLaunch* p, int threads, int form, hipStream_t stream);
@@ -2510,16 +2515,16 @@ namespace {
  * launch-block pointers they dereference, the flags and names of its run-time builds, the schedulers it exists for -- is its row of
  * rs_group_form (rs_device.h, the same row order); a call's row is its form. */
 enum { kGroupPlain = RS_GROUP_PLAIN, kGroupResident = RS_GROUP_RESIDENT, kGroupQueued = RS_GROUP_QUEUED, kGroupFlows = RS_GROUP_FLOWS,
-       kGroupCounted = RS_GROUP_COUNTED, kGroupRun = RS_GROUP_RUN };
+       kGroupCounted = RS_GROUP_COUNTED, kGroupRun = RS_GROUP_RUN, kGroupRunCounted = RS_GROUP_RUN_COUNTED };
 struct GroupForm {
   bool slots0;     /* update-only slots (n_users == 0) are allowed */
-  int pair;        /* rs_group::pair[] that serves the form */
+  int pair;        /* rs_group::pair[] that serves the form; -1: the form has no run-time builds, its built-in kernel serves every call */
   int store_width; /* the stores its self-check saves, restores and compares: 0 none, 1 the resident stores [U], 2 the bearer stores [U][2]
                     * (a form with RS_GROUP_SET_COUNTERS: the counter stores [U][2] too; with RS_GROUP_SET_SENT: the slots' sent rows are compared as well) */
   /* the nouns of the pair's messages: "specialised <adj>%s build", "both <adj>builds are dropped, <serves>", "agreed with <ref>",
    * "copies of the <stores>" */
   const char *adj, *serves, *ref, *stores;
-  unsigned sets() const { return rs_group_form(pair).sets; } /* (every form has a pair of its own: its row) */
+  unsigned sets() const; /* the form's row of rs_group_form */
 };
 const GroupForm kGroupForms[RS_GROUP_FORMS] = {
     {false, kGroupPlain, 0, "", "the built-in kernels serve this group", "the built-in kernel field by field", ""},
@@ -2534,7 +2539,10 @@ const GroupForm kGroupForms[RS_GROUP_FORMS] = {
      "bearer stores and counters"},
     {false, kGroupRun, 1, "run ",
      "the built-in run kernel serves this group's runs", "the built-in run kernel field by field over every TTI, resident stores included", "resident stores"},
+    /* (the counted run: the run's launcher, no pair -- group_specialize_pair and group_jit_pair_status never see the row) */
+    {false, -1, 0, "counted run ", "", "", ""},
 };
+unsigned GroupForm::sets() const { return rs_group_form((int)(this - kGroupForms)).sets; }
 
 /* bytes of one half of rs_group::d_chk: [n_cells][S] slice state, then [n_cells] RsCellScalars */
 size_t group_chk_sstate(const rs_group* g) { return round_up((int)(8 * (size_t)g->b->S * g->n_cells), 256); }
@@ -2658,6 +2666,7 @@ rs_group* rs_group_create(const rs_config* cfg, int32_t n_cells) {
   g->empty_slot.assign(n_cells, 0);
   g->resident.assign(n_cells, 0);
   g->counted.assign(n_cells, 0);
+  g->avg_counted.assign(n_cells, 0);
   g->pending_zero.assign(n_cells, 0);
   g->last_update.assign(n_cells, 0.0);
   g_err[0] = 0;
@@ -2675,7 +2684,8 @@ void rs_group_destroy(rs_group* g) {
                   (void*)g->pair[0].d_stores_chk, (void*)g->pair[1].d_stores_chk, (void*)g->pair[2].d_stores_chk, (void*)g->pair[3].d_stores_chk,
                   (void*)g->pair[4].d_stores_chk, (void*)g->pair[5].d_stores_chk, (void*)g->d_sent2, (void*)g->d_ravg,
                   (void*)g->d_rpend, (void*)g->d_rlast, (void*)g->d_rgather, (void*)g->d_ruid, (void*)g->d_qavg, (void*)g->d_qpend,
-                  (void*)g->d_qdata, (void*)g->d_qhas, (void*)g->d_qin, (void*)g->d_cbytes, (void*)g->d_crbs, (void*)g->d_sent})
+                  (void*)g->d_qdata, (void*)g->d_qhas, (void*)g->d_qin, (void*)g->d_cbytes, (void*)g->d_crbs, (void*)g->d_sent, (void*)g->d_acbytes,
+                  (void*)g->d_acrbs})
     if (q) (void)hipFree(q);
   for (void* q : {(void*)g->h_qin, (void*)g->h_sent, (void*)g->h_sent2, (void*)g->h_in, (void*)g->h_out})
     if (q) (void)hipHostFree(q);
@@ -2735,9 +2745,12 @@ struct GroupCall {
   bool run;
   int32_t n_ttis;
   const int32_t* rands;
+  /* a counted run (rs_group_run_counted_at; with run): the named cells' per-user counters are credited too; no_out: the caller wants no
+   * per-TTI outputs (out == null) -- none is written, copied or unpacked */
+  bool run_counted, no_out;
   int cell(int k) const { return cell_ids ? cell_ids[k] : k; }
   bool resident() const { return form != kGroupPlain; }
-  int row() const { return run ? (int)kGroupRun : counted ? (int)kGroupCounted : form; }
+  int row() const { return run ? (run_counted ? (int)kGroupRunCounted : (int)kGroupRun) : counted ? (int)kGroupCounted : form; }
   int ttis() const { return run ? n_ttis : 1; }
   size_t at(int k, int t = 0) const { return run ? (size_t)k * (size_t)n_ttis + (size_t)t : (size_t)k; } /* slot k's TTI t in `now` and `out` */
   double now_first(int k) const { return now[at(k)]; }
@@ -2781,6 +2794,17 @@ int rs_group_run_at(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tt
   if (!g || !in || !out || !now) return fail(RS_ERR_INVALID, "null argument");
   GroupCall c = {n, cell_ids, in, out, now, nullptr, nullptr, nullptr, kGroupResident, false};
   c.run = true;
+  c.n_ttis = n_ttis;
+  c.rands = rands;
+  return group_schedule(g, c);
+}
+
+int rs_group_run_counted_at(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, int32_t n_ttis, const double* now,
+                            const int32_t* rands, rs_tti_out* out) {
+  if (!g || !in || !now) return fail(RS_ERR_INVALID, "null argument");
+  GroupCall c = {n, cell_ids, in, out, now, nullptr, nullptr, nullptr, kGroupResident, false};
+  c.run = c.run_counted = true;
+  c.no_out = out == nullptr;
   c.n_ttis = n_ttis;
   c.rands = rands;
   return group_schedule(g, c);
@@ -2850,12 +2874,13 @@ int group_validate(rs_group* g, GroupCall& c) {
       const char* what = in[k].hol_delay ? "hol_delay" : in[k].prio_has_data ? "prio_has_data" : in[k].required_rbs ? "required_rbs"
                        : in[k].data_to_transmit ? "data_to_transmit" : nullptr;
       if (what) return fail(RS_ERR_INVALID, "cell slot %d: %s must be NULL in a run: it changes per TTI and belongs to the host", k, what);
-      for (int t = 0; t < c.n_ttis; t++)
+      for (int t = 0; t < c.n_ttis && !c.no_out; t++)
         if (!c.out[c.at(k, t)].rbg_to_user || !c.out[c.at(k, t)].user_tbs_bits) return fail(RS_ERR_INVALID, "cell slot %d, TTI %d: null output array", k, t);
     }
   }
   auto gate_of = [&](const rs_tti_in& t) { return b->sched == RS_SCHED_NVS ? t.required_rbs : (b->sched == RS_SCHED_PF ? t.data_to_transmit : nullptr); };
-  auto upper_of = [&](const rs_tti_out& o) { return b->sched == RS_SCHED_UPPERBOUND && (o.upper_rbg || o.upper_user); };
+  /* (a run without outputs has no upper_* lists to be uniform about: `at` is not dereferenced then) */
+  auto upper_of = [&](size_t at) { return !c.no_out && b->sched == RS_SCHED_UPPERBOUND && (c.out[at].upper_rbg || c.out[at].upper_user); };
   /* (a call's update-only slots, n_users == 0, give no inputs at all: the slots WITH users agree among themselves) */
   int k0 = 0;
   while (slots0 && k0 < n && in[k0].n_users == 0) k0++;
@@ -2865,18 +2890,18 @@ int group_validate(rs_group* g, GroupCall& c) {
   c.has_hol = any_users && in[k0].hol_delay != nullptr;
   c.has_prio = any_users && in[k0].prio_has_data != nullptr;
   c.has_gate = any_users && gate_of(in[k0]) != nullptr;
-  c.want_upper = any_users && upper_of(c.out[c.at(k0)]);
+  c.want_upper = any_users && upper_of(c.at(k0));
   for (int k = k0 + 1; k < n; k++) {
     if (slots0 && in[k].n_users == 0) continue;
     const char* what = (in[k].cqi_prb != nullptr) != c.has_prb ? "cqi_prb" : (in[k].hol_delay != nullptr) != c.has_hol ? "hol_delay"
                      : (in[k].prio_has_data != nullptr) != c.has_prio ? "prio_has_data"
                      : (gate_of(in[k]) != nullptr) != c.has_gate ? (b->sched == RS_SCHED_NVS ? "required_rbs" : "data_to_transmit")
-                     : upper_of(c.out[c.at(k)]) != c.want_upper ? "upper_rbg / upper_user" : nullptr;
+                     : upper_of(c.at(k)) != c.want_upper ? "upper_rbg / upper_user" : nullptr;
     if (what) return fail(RS_ERR_INVALID, "mixed call: cell slot %d and cell slot %d differ in whether they give %s (optional inputs are given by every cell of a call or by none)", k, k0, what);
   }
   for (int k = 0; c.run && k < n; k++) /* (a run: every TTI's output, the slot's first included) */
     for (int t = 0; t < c.n_ttis; t++)
-      if (upper_of(c.out[c.at(k, t)]) != c.want_upper)
+      if (upper_of(c.at(k, t)) != c.want_upper)
         return fail(RS_ERR_INVALID, "mixed call: cell slot %d, TTI %d and cell slot 0, TTI 0 differ in whether they give upper_rbg / upper_user (optional outputs are given by every TTI of every cell of a run or by none)", k, t);
   if (!c.resident()) return RS_OK;
   /* a resident call's cells: the form each is resident in, the slots' own inputs, the clock rules */
@@ -2894,6 +2919,7 @@ int group_validate(rs_group* g, GroupCall& c) {
     if (!que && g->resident[cell] == 2)
       return fail(RS_ERR_STATE, "cell slot %d: cell %d is bearer-resident (rs_group_set_bearers): rs_group_schedule_tti_queued serves it, or rs_group_set_avg makes it average-resident", k, cell);
     if (!g->resident[cell]) return fail(RS_ERR_STATE, "cell slot %d: cell %d is not resident (rs_group_set_avg first)", k, cell);
+    if (c.run_counted && !g->avg_counted[cell]) return fail(RS_ERR_STATE, "cell slot %d: cell %d is not avg-counted (rs_group_set_avg_counters first)", k, cell);
     if (slots0 && in[k].n_users < 0) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): n_users %d is negative", k, cell, in[k].n_users);
     if (int rc = flw ? group_validate_flows_slot(g, c, k, cell) : RS_OK) return rc;
     if (que && in[k].n_users > 0 && !c.qdata[k]) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): data_to_transmit[%d] is NULL (only an update-only slot, n_users == 0, gives none)", k, cell, k);
@@ -2944,6 +2970,7 @@ void group_fill_header(const rs_group* g, const GroupCall& c, int k, const CtxLa
     h.run_ttis = c.n_ttis;
     h.run_table = (int32_t)(table - (size_t)k * g->in_stride);
     h.run_out_step = (int32_t)g->out_stride;
+    h.run_no_out = c.no_out ? 1 : 0;
     for (int t = 0; t < c.n_ttis; t++) {
       const int32_t pair[2] = {c.rands ? c.rands[2 * c.at(k, t)] : 0, c.rands ? c.rands[2 * c.at(k, t) + 1] : 0};
       memcpy(g->h_in + table + (size_t)t * RS_GROUP_RUN_ROW_BYTES, &c.now[c.at(k, t)], 8);
@@ -2998,7 +3025,7 @@ int group_pack_slots(rs_group* g, GroupCall& c) {
                             im.has_ids == (in[k].user_id != nullptr) &&
                             (!in[k].user_id || memcmp(im.ids.data(), in[k].user_id, 4 * (size_t)im.n) == 0);
     g->modes[k] = (uint8_t)(epoch == 0 ? 0 : (reuse_grid ? 2 : 1));
-    int rc = pack_tti(b, &in[k], &c.out[c.at(k)], g->h_in + (size_t)k * g->in_stride + RS_GROUP_HDR_BYTES, reuse_grid, &pk, c.resident(), c.form == kGroupFlows);
+    int rc = pack_tti(b, &in[k], c.no_out ? nullptr : &c.out[c.at(k)], g->h_in + (size_t)k * g->in_stride + RS_GROUP_HDR_BYTES, reuse_grid, &pk, c.resident(), c.form == kGroupFlows);
     if (rc) {
       char msg[sizeof g_err];
       snprintf(msg, sizeof msg, "%s", g_err);
@@ -3039,7 +3066,7 @@ struct ImageGuard {
   ~ImageGuard() {
     if (!ok) for (int k = 0; k < c.n; k++) {
       g->img[c.cell(k)].valid = false;
-      if (c.resident()) g->resident[c.cell(k)] = g->counted[c.cell(k)] = 0; /* (averages half updated, perhaps: resident again with rs_group_set_avg; neither resident nor counted) */
+      if (c.resident()) g->resident[c.cell(k)] = g->counted[c.cell(k)] = g->avg_counted[c.cell(k)] = 0; /* (averages half updated, perhaps: resident again with rs_group_set_avg; neither resident nor counted) */
     }
   }
 };
@@ -3094,9 +3121,9 @@ void group_fill_launch(const rs_group* g, const GroupCall& c, RsLaunch* launch) 
     L.grp_qin_stride = 2 * (int64_t)b->U;
   }
   if (sets & RS_GROUP_SET_DATA) L.grp_qdata = g->d_qdata;
-  if (sets & RS_GROUP_SET_COUNTERS) {
-    L.grp_cbytes = g->d_cbytes;
-    L.grp_crbs = g->d_crbs;
+  if (sets & RS_GROUP_SET_COUNTERS) { /* (a cell is resident in one form at a time: the bearers' [U][2] stores, or a counted run's [U] stores) */
+    L.grp_cbytes = c.run_counted ? g->d_acbytes : g->d_cbytes;
+    L.grp_crbs = c.run_counted ? g->d_acrbs : g->d_crbs;
   }
   if (sets & RS_GROUP_SET_SENT) {
     L.grp_sent = g->z_sent ? g->z_sent : g->d_sent;
@@ -3181,7 +3208,8 @@ int group_run(rs_group* g, GroupCall& c, RsLaunch& L) {
     L.done_flag = (uint32_t*)(g->z_out + g->flag_off);
     L.done_seq = g->seq;
   }
-  const rs_group::GroupPair& p = g->pair[f.pair];
+  static const rs_group::GroupPair no_pair{}; /* (a form without run-time builds: nothing wanted, nothing built) */
+  const rs_group::GroupPair& p = f.pair >= 0 ? g->pair[f.pair] : no_pair;
   /* (a flows call always carries the data_to_transmit gate: its lean build keeps it) */
   const bool gate_free = c.form == kGroupFlows || !c.has_gate;
   const bool lean = p.jit[1] && !c.has_prb && !L.queue_mode && gate_free && !L.exact_scan && !L.gen_exp && !c.want_upper && !L.synthetic;
@@ -3198,7 +3226,7 @@ int group_run(rs_group* g, GroupCall& c, RsLaunch& L) {
   g->launches++;
   g->last_call_form = c.row();
   g->last_call_jit = c.kd != nullptr;
-  if (!c.zc) HIP_TRY(hipMemcpyAsync(g->h_out, g->d_out, (size_t)c.n * c.ttis() * g->out_stride, hipMemcpyDeviceToHost, st));
+  if (!c.zc && !c.no_out) HIP_TRY(hipMemcpyAsync(g->h_out, g->d_out, (size_t)c.n * c.ttis() * g->out_stride, hipMemcpyDeviceToHost, st));
   if ((f.sets() & RS_GROUP_SET_SENT) && !g->z_sent) HIP_TRY(hipMemcpyAsync(g->h_sent, g->d_sent, 8 * (size_t)c.n * b->U, hipMemcpyDeviceToHost, st));
   return RS_OK;
 }
@@ -3418,7 +3446,7 @@ int group_schedule(rs_group* g, GroupCall c) {
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   if ((rc = group_pack_slots(g, c))) return rc;
   ImageGuard guard{g, c, false};
-  if (c.run && (rc = group_grow_out(g, (size_t)c.n * (size_t)c.n_ttis))) return rc;
+  if (c.run && !c.no_out && (rc = group_grow_out(g, (size_t)c.n * (size_t)c.n_ttis))) return rc;
   const clk::time_point t1 = g->timing ? clk::now() : clk::time_point();
   c.zc = g->z_in != nullptr && !c.has_prb && !b->any_alpha;
   RsLaunch L;
@@ -3431,7 +3459,7 @@ int group_schedule(rs_group* g, GroupCall c) {
   group_commit_clocks(g, c);
   const clk::time_point t3 = g->timing ? clk::now() : clk::time_point();
   group_commit_images(g, c);
-  group_unpack(g, c);
+  if (!c.no_out) group_unpack(g, c);
   if (g->timing) {
     const clk::time_point t4 = clk::now();
     auto us = [](clk::time_point a, clk::time_point b2) { return std::chrono::duration<double, std::micro>(b2 - a).count(); };
@@ -3544,11 +3572,14 @@ int rs_group_set_avg(rs_group* g, int32_t cell, const double* avg, double last_u
   }
   HIP_TRY(hipStreamSynchronize(b->stream));
   g->counted[cell] = 0; /* (the cell leaves the bearer form: its counters' term ends) */
+  const uint8_t keep_counted = g->avg_counted[cell]; /* (an avg-counted cell keeps the state and its counters, as a counted cell does under rs_group_set_bearers) */
+  g->avg_counted[cell] = 0;
   g->resident[cell] = 0; /* (until all three copies are through) */
   HIP_TRY(hipMemcpy(g->d_ravg + (size_t)cell * U, avg, 8 * U, hipMemcpyHostToDevice));
   HIP_TRY(hipMemset(g->d_rpend + (size_t)cell * U, 0, 4 * U));
   HIP_TRY(hipMemcpy(g->d_rlast + cell, &last_update, 8, hipMemcpyHostToDevice));
   g->resident[cell] = 1;
+  g->avg_counted[cell] = keep_counted;
   g->pending_zero[cell] = 1;
   g->last_update[cell] = last_update;
   return RS_OK;
@@ -3607,6 +3638,7 @@ int rs_group_set_bearers(rs_group* g, int32_t cell, const uint8_t* has_bearer, c
   if (!group_alloc_bearer_stores(g)) return fail(RS_ERR_HIP, "allocation of the group's resident bearers failed (%zu bytes)", 25 * nb);
   HIP_TRY(hipStreamSynchronize(b->stream));
   g->resident[cell] = 0; /* (until all four copies are through) */
+  g->avg_counted[cell] = 0; /* (the cell leaves the average form: its per-user counters' term ends) */
   /* a bearer that does not exist holds zeros: rs_group_get_bearers reports them, the kernel neither reads nor writes them */
   std::vector<double> a(2 * U);
   std::vector<uint8_t> has(2 * U);
@@ -3674,6 +3706,51 @@ int rs_group_get_counters(rs_group* g, int32_t cell, int64_t* cum_bytes, int64_t
   return RS_OK;
 }
 
+int rs_group_set_avg_counters(rs_group* g, int32_t cell, const int64_t* cum_bytes, const int64_t* cum_rbs) {
+  if (!g) return fail(RS_ERR_INVALID, "null group");
+  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
+  if (g->resident[cell] != 1) return fail(RS_ERR_STATE, "cell %d is not average-resident (rs_group_set_avg first)", cell);
+  rs_batch* b = g->b;
+  const size_t U = (size_t)b->U, nu = U * (size_t)g->n_cells;
+  for (size_t u = 0; u < U; u++) {
+    if (cum_bytes && cum_bytes[u] < 0) return fail(RS_ERR_INVALID, "cum_bytes[%zu] = %lld is negative", u, (long long)cum_bytes[u]);
+    if (cum_rbs && cum_rbs[u] < 0) return fail(RS_ERR_INVALID, "cum_rbs[%zu] = %lld is negative", u, (long long)cum_rbs[u]);
+  }
+  HIP_TRY(hipSetDevice(b->cfg.cell.device));
+  if (!g->d_acbytes) { /* (both stores or none, zeroed: a cell's counters are read only once it is avg-counted) */
+    const bool ok = hipMalloc(&g->d_acbytes, 8 * nu) == hipSuccess && hipMalloc(&g->d_acrbs, 8 * nu) == hipSuccess &&
+                    hipMemset(g->d_acbytes, 0, 8 * nu) == hipSuccess && hipMemset(g->d_acrbs, 0, 8 * nu) == hipSuccess;
+    if (!ok) {
+      (void)hipGetLastError();
+      for (void* q : {(void*)g->d_acbytes, (void*)g->d_acrbs})
+        if (q) (void)hipFree(q);
+      g->d_acbytes = g->d_acrbs = nullptr;
+      return fail(RS_ERR_HIP, "allocation of the group's per-user counters failed (%zu bytes)", 16 * nu);
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  g->avg_counted[cell] = 0; /* (until both copies are through) */
+  if (cum_bytes) HIP_TRY(hipMemcpy(g->d_acbytes + (size_t)cell * U, cum_bytes, 8 * U, hipMemcpyHostToDevice));
+  else HIP_TRY(hipMemset(g->d_acbytes + (size_t)cell * U, 0, 8 * U));
+  if (cum_rbs) HIP_TRY(hipMemcpy(g->d_acrbs + (size_t)cell * U, cum_rbs, 8 * U, hipMemcpyHostToDevice));
+  else HIP_TRY(hipMemset(g->d_acrbs + (size_t)cell * U, 0, 8 * U));
+  g->avg_counted[cell] = 1;
+  return RS_OK;
+}
+
+int rs_group_get_avg_counters(rs_group* g, int32_t cell, int64_t* cum_bytes, int64_t* cum_rbs) {
+  if (!g) return fail(RS_ERR_INVALID, "null group");
+  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
+  if (!g->avg_counted[cell]) return fail(RS_ERR_STATE, "cell %d is not avg-counted (rs_group_set_avg_counters first)", cell);
+  rs_batch* b = g->b;
+  const size_t U = (size_t)b->U;
+  HIP_TRY(hipSetDevice(b->cfg.cell.device));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  if (cum_bytes) HIP_TRY(hipMemcpy(cum_bytes, g->d_acbytes + (size_t)cell * U, 8 * U, hipMemcpyDeviceToHost));
+  if (cum_rbs) HIP_TRY(hipMemcpy(cum_rbs, g->d_acrbs + (size_t)cell * U, 8 * U, hipMemcpyDeviceToHost));
+  return RS_OK;
+}
+
 int rs_group_set_flows(rs_group* g, int32_t cell, const uint8_t* has_bearer, const double* avg, double last_update, const int64_t* cum_bytes,
                        const int64_t* cum_rbs) {
   if (!g || !has_bearer || !avg) return fail(RS_ERR_INVALID, "null argument");
@@ -3696,6 +3773,7 @@ int rs_group_set_flows(rs_group* g, int32_t cell, const uint8_t* has_bearer, con
     return fail(RS_ERR_HIP, "allocation of the group's resident flows failed (%zu bytes)", 45 * nb);
   HIP_TRY(hipStreamSynchronize(b->stream));
   g->counted[cell] = 0;
+  g->avg_counted[cell] = 0;
   g->resident[cell] = 0; /* (until all six copies are through) */
   /* a bearer that does not exist holds zeros: rs_group_get_flows reports them, the kernel neither reads nor writes them */
   std::vector<double> a(2 * U);

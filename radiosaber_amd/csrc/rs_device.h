@@ -417,11 +417,15 @@ struct RsGroupCell {
    * slot's per-TTI table lies -- bytes from this header, 16 per TTI: the clock (a double), then rand0 and rand1; `now`, rand0 and rand1
    * above are not read -- and the bytes between two of the slot's run_ttis output blocks, which follow one another in TTI order */
   int32_t run_ttis, run_table, run_out_step;
-  int32_t pad_[RS_GROUP_HDR_BYTES / 4 - 25];
+  /* a counted run without outputs (rs_group_run_counted_at with out == NULL, rs_group_run_counted_kernel; no other kernel reads it):
+   * not 0 -- the run writes no output block, the body's log pointers stay null for all its TTIs */
+  int32_t run_no_out;
+  int32_t pad_[RS_GROUP_HDR_BYTES / 4 - 26];
 };
 #define RS_GROUP_RUN_ROW_BYTES 16
 static_assert(sizeof(RsGroupCell) == RS_GROUP_HDR_BYTES, "the slot header keeps its size: new words come out of its padding");
 static_assert(__builtin_offsetof(RsGroupCell, image_mode) == 72 && __builtin_offsetof(RsGroupCell, now) == 80, "no existing word of the slot header moves");
+static_assert(__builtin_offsetof(RsGroupCell, run_ttis) == 88 && __builtin_offsetof(RsGroupCell, run_no_out) == 100, "the run's words keep their places, the new one lies behind them");
 
 /* ------------------------------------------------------------------------------------------------------------------
  * The forms of a group call: THE description.  The body text (rs_phase_group.inc), the built-in kernels, their launcher and LDS
@@ -429,13 +433,14 @@ static_assert(__builtin_offsetof(RsGroupCell, image_mode) == 72 && __builtin_off
  * nothing else says what a form is.  A new form is a row here, its text in rs_phase_group.inc, an entry point of its name in
  * rs_kernels.hip and its host-only row in rs_api.cpp.
  * ------------------------------------------------------------------------------------------------------------------ */
-enum RsGroupFormId { RS_GROUP_PLAIN = 0, RS_GROUP_RESIDENT = 1, RS_GROUP_QUEUED = 2, RS_GROUP_FLOWS = 3, RS_GROUP_COUNTED = 4, RS_GROUP_RUN = 5, RS_GROUP_FORMS = 6 };
+enum RsGroupFormId { RS_GROUP_PLAIN = 0, RS_GROUP_RESIDENT = 1, RS_GROUP_QUEUED = 2, RS_GROUP_FLOWS = 3, RS_GROUP_COUNTED = 4, RS_GROUP_RUN = 5, RS_GROUP_RUN_COUNTED = 6,
+                     RS_GROUP_FORMS = 7 };
 enum : unsigned { /* the RsLaunch pointers a form's kernel dereferences: the host fills them, the launcher refuses a null one */
   RS_GROUP_SET_CELL = 1,      /* grp_last, grp_gather, grp_uid: every form that keeps state on the device */
   RS_GROUP_SET_AVERAGES = 2,  /* grp_avg, grp_pending */
   RS_GROUP_SET_BEARERS = 4,   /* grp_qavg, grp_qpend, grp_qhas and the slots' word block grp_qin (data words; a flows call: bearer words) */
   RS_GROUP_SET_DATA = 8,      /* grp_qdata: the workgroup's copy of the data words */
-  RS_GROUP_SET_COUNTERS = 16, /* grp_cbytes, grp_crbs */
+  RS_GROUP_SET_COUNTERS = 16, /* grp_cbytes, grp_crbs: [U][2] per cell beside the bearer stores, [U] per cell beside the averages (a counted run) */
   RS_GROUP_SET_SENT = 32,     /* grp_sent: the slots' sent rows */
 };
 /* the schedulers a group kernel may be asked for, and a set of them as a mask over their places in this list */
@@ -476,6 +481,9 @@ constexpr RsGroupForm rs_group_form(int form) {
       {"rs_group_flows_kernel",    false, false, false, true,  false, bearers | RS_GROUP_SET_COUNTERS, 8 | 128, rs_group_scheds(1)},
       {"rs_group_counted_kernel",  false, true,  true,  false, false, bearers | RS_GROUP_SET_DATA | RS_GROUP_SET_COUNTERS | RS_GROUP_SET_SENT, 8 | 32 | 64, credit},
       {"rs_group_run_kernel",      true,  false, false, false, true,  avgs, 8 | 16 | 256, all & ~rs_group_scheds(7)}, /* (7: the host picks the served slice per TTI) */
+      /* (a counted run: the run's text with per-user counters.  Its flag set names the row and nothing else: no run-time build of
+       * this form exists, rs_jit.cpp refuses the set) */
+      {"rs_group_run_counted_kernel", true, false, true, false, true, avgs | RS_GROUP_SET_COUNTERS, 8 | 16 | 64 | 256, all & ~rs_group_scheds(7)},
   };
   return rows[form];
 }
@@ -485,7 +493,9 @@ constexpr bool rs_group_form_serves(int form, int sched) {
 }
 /* ... and what the run-time builds answer (rs_jit.cpp).  ONE exception, kept as it was found: a plain or a resident build is never asked
  * for its scheduler, so scheduler 11 -- which no group kernel serves and rs_group_create refuses -- gets a cache file and a build there. */
-constexpr bool rs_group_form_builds(int form, int sched) { return form == RS_GROUP_PLAIN || form == RS_GROUP_RESIDENT || rs_group_form_serves(form, sched); }
+constexpr bool rs_group_form_builds(int form, int sched) {
+  return form != RS_GROUP_RUN_COUNTED && (form == RS_GROUP_PLAIN || form == RS_GROUP_RESIDENT || rs_group_form_serves(form, sched));
+}
 /* the kernels' second template argument for `ept` sort positions per lane: the register form of the sort up to four (schedulers 9 and
  * 10), above that scheduler 9's LDS form (0), which scheduler 10 has no built-in kernel of (-1); every other scheduler 0 */
 constexpr int rs_group_form_ept(int sched, int ept) { return (sched != 9 && sched != 10) ? 0 : (ept <= 4 ? (ept < 1 ? 1 : ept) : (sched == 9 ? 0 : -1)); }

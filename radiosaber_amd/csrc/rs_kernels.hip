@@ -775,14 +775,15 @@ __global__ void __launch_bounds__(512, 4) rs_cell_kernel(RsLaunch p) {
 
 /* The group kernels built into the library: one template per form of a group call, the body is rs_phase_group.inc, which reads the
  * form's row of the table in rs_device.h (rs_group_form) -- that row and the text are what a form IS; the names are what traces, profiles
- * and rs_group_kernel_name cite.  Which (scheduler, EPT) pairs exist per form: rs_group_kernel_exists (60 kernels; the one enumeration
+ * and rs_group_kernel_name cite.  Which (scheduler, EPT) pairs exist per form: rs_group_kernel_exists (73 kernels; the one enumeration
  * behind rs_launch_group and rs_prepare_kernels below).  A group's run-time builds are the <name>_jit entry point further down.
  *   rs_group_kernel            rs_group_schedule_tti          shape in the launch block, nothing kept on the device
  *   rs_group_resident_kernel   rs_group_schedule_tti_at       the cells' PF averages, pending bytes and last-update times stay on the device
  *   rs_group_queued_kernel     rs_group_schedule_tti_queued   both bearers of every user stay there; a slot without users does the update alone
  *   rs_group_flows_kernel      rs_group_schedule_tti_flows    scheduler 1: a call position is a flow, bearer stores and counters
  *   rs_group_counted_kernel    rs_group_schedule_tti_counted  the queued form with m_cumulateBytes / m_cumulateRBs and the slots' sent rows
- *   rs_group_run_kernel        rs_group_run_at                T consecutive TTIs of the resident form in one launch */
+ *   rs_group_run_kernel        rs_group_run_at                T consecutive TTIs of the resident form in one launch
+ *   rs_group_run_counted_kernel rs_group_run_counted_at       the run with m_cumulateBytes / m_cumulateRBs per user, with or without output blocks */
 template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
@@ -827,6 +828,14 @@ template <int SCHED, int EPT>
 __global__ void __launch_bounds__(512, 4) rs_group_run_kernel(RsLaunch p) {
   extern __shared__ __align__(16) unsigned char lds[];
   constexpr int kGrpForm = RS_GROUP_RUN, kGrpSched = SCHED, kGrpEpt = EPT;
+  constexpr bool kGrpFixed = false, kGrpLean = false;
+#include "rs_phase_group.inc"
+}
+
+template <int SCHED, int EPT>
+__global__ void __launch_bounds__(512, 4) rs_group_run_counted_kernel(RsLaunch p) {
+  extern __shared__ __align__(16) unsigned char lds[];
+  constexpr int kGrpForm = RS_GROUP_RUN_COUNTED, kGrpSched = SCHED, kGrpEpt = EPT;
   constexpr bool kGrpFixed = false, kGrpLean = false;
 #include "rs_phase_group.inc"
 }
@@ -1082,7 +1091,8 @@ static const void* rs_group_kernel_fn() {
   else if constexpr (FORM == RS_GROUP_QUEUED) return (const void*)rs_group_queued_kernel<SCHED, EPT>;
   else if constexpr (FORM == RS_GROUP_FLOWS) return (const void*)rs_group_flows_kernel<SCHED, EPT>;
   else if constexpr (FORM == RS_GROUP_COUNTED) return (const void*)rs_group_counted_kernel<SCHED, EPT>;
-  else return (const void*)rs_group_run_kernel<SCHED, EPT>;
+  else if constexpr (FORM == RS_GROUP_RUN) return (const void*)rs_group_run_kernel<SCHED, EPT>;
+  else return (const void*)rs_group_run_counted_kernel<SCHED, EPT>;
 }
 struct RsGroupKernels {
   const void* fn[RS_GROUP_FORMS][RS_GROUP_SCHEDS][5]; /* [form][rs_group_sched_index][EPT]; null: no such kernel */

@@ -51,7 +51,15 @@
  *   says; under a cqi_epoch the later TTIs load the cell's image (and read the cell's per-PRB store) as calls of their own would,
  *   without one they read the slot's blocks again.  Between two TTIs stands one workgroup barrier behind a device-scope fence: the
  *   credit of TTI t goes by call position, the update of TTI t + 1 by user id -- other threads --, and the body's load phase overwrites
- *   the LDS grants the credit reads.  A text of its own below: the other instantiations' resident text is left as it is. */
+ *   the LDS grants the credit reads.  A text of its own below: the other instantiations' resident text is left as it is.
+ * run with cnt (rs_group_run_counted_at): the cell also keeps m_cumulateBytes / m_cumulateRBs per USER -- a backlogged cell holds one
+ *   bearer per user -- in a [U] store of its own (grp_cbytes / grp_crbs point at it in this form), and step 3's thread adds the
+ *   position's grant and its PRBs to them (DoStopSchedule, ref: downlink-transport-scheduler.cpp:177-190; scheduler 1:
+ *   dl-pf-packet-scheduler.cpp:84-85).  The PRB count: the counted form's lane masks for the schedulers whose link adaptation runs in
+ *   rs_phase_p5.inc; UpperBound (10) adapts in rs_phase_p4.inc and leaves no masks -- there the count is the user's taken entries of
+ *   its slice's list in LDS, which is what its user_nprb is made of (an RBG that two slices took counts for both, so the owner map
+ *   would fall short).  With the slot header's run_no_out set the body's log pointers are null for the whole run: no output block is
+ *   written.  Both counter adds of one user in TTIs t and t + 1 are ordered by the fence and barrier that order the credit. */
   constexpr RsGroupForm kGrpF = rs_group_form(kGrpForm);
   constexpr bool kGrpRes = kGrpF.res, kGrpQue = kGrpF.que, kGrpCnt = kGrpF.cnt, kGrpFlow = kGrpF.flow, kGrpRun = kGrpF.run;
   static_assert(kGrpFixed ? rs_group_form_builds(kGrpForm, kGrpSched) : rs_group_form_serves(kGrpForm, kGrpSched), "no kernel of this form for this scheduler (rs_group_form, rs_device.h)");
@@ -142,6 +150,16 @@
       q.log_quota = (int16_t*)(o + word(&h->out_quota));
       q.log_target = (int16_t*)(o + word(&h->out_target));
       q.log_upper = p.log_upper ? (int32_t*)(o + word(&h->out_upper)) : nullptr;
+      if constexpr (kGrpCnt) { /* (every word of the counted run stands inside an `if constexpr` of its own: the run kernels keep their text) */
+        if (word(&h->run_no_out) != 0) { /* (wave-uniform: a header word.  Every store of the body to an output row stands behind one of these pointers) */
+          q.log_tbs = nullptr;
+          q.log_uinfo = nullptr;
+          q.log_map = nullptr;
+          q.log_quota = nullptr;
+          q.log_target = nullptr;
+          q.log_upper = nullptr;
+        }
+      }
       /* 1. the update, for every user id of the cell: the resident form's step 1, operation by operation */
       if (!(now == last)) {
         const double dt = now - last;
@@ -182,6 +200,30 @@
 #else
         if (bytes != 0) r_pend[in_uid != 0 ? ids[i] : i] += bytes;
 #endif
+        if constexpr (kGrpCnt) {
+          /* GetListOfAllocatedRBs()->size() of the position's block.  A user is named once per call, a cell once per launch: plain
+           * 64-bit adds by the position's thread, as the counted form's. */
+          int64_t* const c_bytes = p.grp_cbytes + (size_t)cell * (size_t)n_all; /* the cell's counters, by user id */
+          int64_t* const c_rbs = p.grp_crbs + (size_t)cell * (size_t)n_all;
+          const int n_rbg = kGrpFixed ? RS_JIT_R : p.R, prb_per_rbg = kGrpFixed ? RS_JIT_G : p.G;
+          int n_held;
+          if constexpr (kGrpSched == 10) {
+            /* (every thread walks its user's slice segment, grant or not: R entries of UpperBound's ent_user, rs_phase_p4.inc; the ones
+             * past the slice's quota say "not taken") */
+            const uint16_t* const taken = (const uint16_t*)(lds + (kGrpFixed ? kGrpCv.off_elems : p.off_elems));
+            const uint16_t* const seg = taken + (int)q.user_slice[i] * n_rbg;
+            n_held = 0;
+            for (int k = 0; k < n_rbg; ++k) n_held += seg[k] == (uint16_t)i ? 1 : 0;
+          } else {
+            const RsMisc* const cm = (const RsMisc*)(lds + (kGrpFixed ? kGrpCv.off_misc : p.off_misc));
+            n_held = __popcll(cm->maskA[(i + 1) & 63] & cm->maskB[(i + 1) >> 6]);
+          }
+          if (bytes != 0) {
+            const int id = in_uid != 0 ? ids[i] : i;
+            c_bytes[id] += (int64_t)bytes;
+            c_rbs[id] += (int64_t)(n_held * prb_per_rbg);
+          }
+        }
       }
       if (t + 1 < n_run) {
         /* (wave-uniform: n_run is a header word.)  The next TTI: its output block; under a cqi_epoch the image that TTI 0 stored or
