@@ -39,7 +39,8 @@ extern "C" {
                                rs_group_set_flows / rs_group_get_flows / rs_group_schedule_tti_flows (scheduler 1's flows of a group cell resident on the device: averages, pending bytes and counters per bearer, the whole block credited to the flow),
                                rs_group_run_at + RS_GROUP_MAX_RUN (T consecutive TTIs of average-resident group cells in one launch),
                                rs_group_specialize_run / rs_group_run_jit_status / rs_jit_selfcheck_group_run (a group's own builds of the run kernel, self-checked per run on every TTI's outputs and on state),
-                               rs_group_set_avg_counters / rs_group_get_avg_counters / rs_group_run_counted_at (an average-resident group cell's m_cumulateBytes / m_cumulateRBs per user on the device, advanced by runs that may return no per-TTI outputs at all);
+                               rs_group_set_avg_counters / rs_group_get_avg_counters / rs_group_run_counted_at (an average-resident group cell's m_cumulateBytes / m_cumulateRBs per user on the device, advanced by runs that may return no per-TTI outputs at all),
+                               rs_grant_record / rs_group_grant_bound / rs_group_run_records_at (the counted run with one compact record per grant and TTI: the reference's app: lines from a run without per-TTI outputs);
                                rs_config.link_tables (RS_LINK_*) + rs_link_tables_pinned / rs_link_tables_compare, rs_tti_in.cqi_epoch (the context keeps the
                                CQI image of an unchanged report set on the device), rs_ctx_jit_status (a specialised context checks its run-time build against the
                                built-in kernel during its first calls), rs_batch_config.selfcheck -1 / 0 / 1 with run-time builds verified by default and the
@@ -508,6 +509,41 @@ int rs_group_get_avg_counters(rs_group* g, int32_t cell, int64_t* cum_bytes /* [
 int rs_group_run_counted_at(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in /* [n] */, int32_t n_ttis,
                             const double* now /* [n][n_ttis] */, const int32_t* rands /* [n][n_ttis][2]; NULL only for RS_SCHED_PF */,
                             rs_tti_out* out /* [n][n_ttis], or NULL: no per-TTI outputs */);
+
+/* Grant records (ABI 11 addition, no layout changed): what DoStopSchedule logs, from a counted run with or without per-TTI outputs.
+ * A TTI serves a handful of users -- every scheduler but UpperBound gives an RBG to one -- so the reference's log of a TTI, its
+ * "app:" lines (scheduler 1: "flow:" lines), is a few dozen (position, user, bytes, PRBs, counters) tuples and not U output rows.
+ * The thread that credits a grant in step 3 of a counted run writes one rs_grant_record for it.
+ * rs_group_grant_bound is the most grants one cell of the group can have in one TTI (> 0): min(n_users, n_rbgs) of the config for
+ *   RS_SCHED_PF, _SEQUENTIAL, _MAXCELL, _SUBOPT and _VOGEL, which give an RBG to one user; for RS_SCHED_UPPERBOUND, where an RBG
+ *   taken by several slices is a grant for each of them, the sum over the config's slices of min(the slice's users, n_rbgs) -- n_users
+ *   when no slice has more users than there are RBGs.
+ * rs_group_run_records_at IS rs_group_run_counted_at with the same `out` -- every rule, every check, the order of operations and every
+ *   result: outputs if asked, averages, pending bytes, last_update, slice state, counters, image records, rs_group_image_stats;
+ *   rs_group_launch_count grows by 1, rs_group_kernel_name says "rs_group_run_counted_kernel<sched, ept>".  In addition, for every
+ *   slot k and TTI t, n_recs[k * n_ttis + t] is the number of call positions with a grant (bytes != 0) and
+ *   recs[(k * n_ttis + t) * rec_cap + 0 .. n_recs - 1] holds one record per such position, ASCENDING in pos: the order in which
+ *   DoStopSchedule walks its users (ref: downlink-transport-scheduler.cpp:177-190; scheduler 1: dl-pf-packet-scheduler.cpp:84-85).
+ *   Entries behind the count are not written.  A TTI whose clock step is 0 has its records like any other.
+ *   Two more rules, checked with the others before anything is launched (a rejected call launches nothing and moves nothing):
+ *   recs and n_recs are both given, and rec_cap >= rs_group_grant_bound(g); RS_ERR_INVALID otherwise.  A larger rec_cap is fine.
+ *   Should the device ever count more grants in a TTI than the list holds, nothing is written behind the capacity, n_recs carries the
+ *   count as counted, and the call returns RS_ERR_STATE naming cell and TTI -- state and counters are complete then, that TTI's
+ *   records are not.  It would mean that rs_group_grant_bound is wrong.
+ * rs_group_run_counted_at itself is what it was, with and without outputs. */
+typedef struct rs_grant_record { /* 32 bytes */
+  int32_t pos;       /* call position i of the served user */
+  int32_t user_id;   /* user_id[i], or i when the call names no ids */
+  int32_t bytes;     /* what step 3 credits: min(user_tbs_bits[i] / 8, 100000000); never 0 */
+  int32_t nprb;      /* rs_tti_out.user_nprb[i] */
+  int64_t cum_bytes; /* the user's counters AFTER this TTI's credit */
+  int64_t cum_rbs;
+} rs_grant_record;
+int rs_group_grant_bound(const rs_group* g);
+int rs_group_run_records_at(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in /* [n] */, int32_t n_ttis,
+                            const double* now /* [n][n_ttis] */, const int32_t* rands /* [n][n_ttis][2]; NULL only for RS_SCHED_PF */,
+                            rs_tti_out* out /* [n][n_ttis], or NULL: no per-TTI outputs */, int32_t rec_cap,
+                            rs_grant_record* recs /* [n][n_ttis][rec_cap] */, int32_t* n_recs /* [n][n_ttis] */);
 
 /* Resident bearers (ABI 11 addition, no layout changed): the second resident form of a group's cell.  The cell keeps, per user id of the
  * config and per bearer (MAX_BEARERS = 2, index = the bearer's priority), RadioBearer's average rate and the bytes DoStopSchedule

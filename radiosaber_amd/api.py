@@ -120,7 +120,13 @@ ABI_SYMBOLS = [
     "rs_group_specialize_flows", "rs_group_flows_jit_status", "rs_jit_selfcheck_group_flows",
     "rs_group_specialize_run", "rs_group_run_jit_status", "rs_jit_selfcheck_group_run",
     "rs_group_set_avg_counters", "rs_group_get_avg_counters", "rs_group_run_counted_at",
+    "rs_group_grant_bound", "rs_group_run_records_at",
 ]
+
+# rs_grant_record: one grant of one TTI of a counted run (32 bytes)
+GRANT_RECORD = np.dtype([("pos", np.int32), ("user_id", np.int32), ("bytes", np.int32), ("nprb", np.int32),
+                         ("cum_bytes", np.int64), ("cum_rbs", np.int64)])
+assert GRANT_RECORD.itemsize == 32
 
 _lib = None
 
@@ -181,6 +187,8 @@ def lib():
     L.rs_group_get_avg_counters.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.rs_group_run_counted_at.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_TtiIn), C.c_int32, C.POINTER(C.c_double),
                                           C.POINTER(C.c_int32), C.POINTER(_TtiOut)]
+    L.rs_group_grant_bound.argtypes = [C.c_void_p]
+    L.rs_group_run_records_at.argtypes = L.rs_group_run_counted_at.argtypes + [C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]
     L.rs_group_get_counters.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.rs_group_schedule_tti_counted.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_TtiIn), C.POINTER(_TtiOut),
                                                 C.POINTER(C.c_double), C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32))]
@@ -883,7 +891,8 @@ class GroupScheduler:
         cell's TTIs (None: RS_SCHED_PF only).  Returns results[k][t]."""
         return self._run(lib().rs_group_run_at, calls, now, rands, cell_ids, True)
 
-    def _run(self, fn, calls, now, rands, cell_ids, outputs):
+    def _run(self, fn, calls, now, rands, cell_ids, outputs, rec=None):
+        """rec: (rec_cap, recs, n_recs) -- the three extra arguments of rs_group_run_records_at (arrays, or None for a NULL pointer)"""
         n = len(calls)
         t = np.asarray(now, np.float64)
         assert t.ndim in (1, 2) and (t.ndim == 1 or t.shape[0] == n)
@@ -906,8 +915,10 @@ class GroupScheduler:
             results.append(row[:T])
         ids = None if cell_ids is None else np.ascontiguousarray(cell_ids, np.int32)
         assert ids is None or ids.shape == (n,)
+        more = () if rec is None else (int(rec[0]), rec[1].ctypes.data if rec[1] is not None else None,
+                                       _p(rec[2], C.c_int32) if rec[2] is not None else None)
         _check(fn(self._h, n, _p(ids, C.c_int32) if ids is not None else None, ins, T, _p(t, C.c_double),
-                  _p(r, C.c_int32) if r is not None else None, outs if outputs else None))
+                  _p(r, C.c_int32) if r is not None else None, outs if outputs else None, *more))
         return results if outputs else None
 
     # ---- counted runs: m_cumulateBytes / m_cumulateRBs per user of an average-resident cell stay on the device too ----
@@ -929,11 +940,27 @@ class GroupScheduler:
         _check(lib().rs_group_get_avg_counters(self._h, cell, _p(cb, C.c_int64), _p(cr, C.c_int64)))
         return cb, cr
 
-    def run_counted_at(self, calls: Sequence[dict], now, rands=None, cell_ids: Optional[Sequence[int]] = None, outputs=True):
+    def run_counted_at(self, calls: Sequence[dict], now, rands=None, cell_ids: Optional[Sequence[int]] = None, outputs=True,
+                       records=False, rec_cap=None):
         """rs_group_run_counted_at: run_at for avg-counted cells, same calls and same results; every grant also adds its bytes and the
         position's PRBs to the user's counters.  outputs=False is the output-free run: nothing is written per TTI or unpacked, state
-        and counters are what the run with outputs leaves, and the call returns None; else results[k][t]."""
-        return self._run(lib().rs_group_run_counted_at, calls, now, rands, cell_ids, outputs)
+        and counters are what the run with outputs leaves, and the call returns None; else results[k][t].
+        records=True is rs_group_run_records_at: the same run, and the call returns (results or None, recs) with recs[k][t] a
+        GRANT_RECORD array of that cell's grants in that TTI, ascending in pos -- what logfmt.run_record_lines makes the reference's
+        app: lines of.  rec_cap (default and least: grant_bound) is the room per TTI."""
+        if not records:
+            return self._run(lib().rs_group_run_counted_at, calls, now, rands, cell_ids, outputs)
+        n, T = len(calls), np.asarray(now).shape[-1]
+        cap = self.grant_bound if rec_cap is None else int(rec_cap)
+        recs = np.zeros((n, T, max(cap, 1)), GRANT_RECORD)
+        n_recs = np.zeros((n, T), np.int32)
+        res = self._run(lib().rs_group_run_records_at, calls, now, rands, cell_ids, outputs, rec=(cap, recs, n_recs))
+        return res, [[recs[k, t, :n_recs[k, t]].copy() for t in range(T)] for k in range(n)]
+
+    @property
+    def grant_bound(self):
+        """rs_group_grant_bound: the most grants one cell can have in one TTI -- the least rec_cap of a run with records."""
+        return _count(lib().rs_group_grant_bound(self._h))
 
     # ---- resident bearers: both bearers of every user stay on the device, finite queues are credited there ----
     def set_bearers(self, cell, has_bearer, avg, last_update):

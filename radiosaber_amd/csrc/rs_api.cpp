@@ -2499,6 +2499,12 @@ struct rs_group {
    * at them in a counted run), and which cells are avg-counted -- a state on top of resident[cell] == 1 */
   int64_t *d_acbytes = nullptr, *d_acrbs = nullptr;
   std::vector<uint8_t> avg_counted;
+  /* grant records (rs_group_run_records_at): the slots' record blocks -- per slot T lists of `cap` records, then T count words, see
+   * RsGroupCell::run_rec_cap -- in device memory (the kernel adds to the count words), and the pinned twin they are copied back to.
+   * Both grow to the largest call so far, as the output blocks do. */
+  uint8_t *d_recs = nullptr, *h_recs = nullptr;
+  size_t recs_bytes = 0;
+  double t_recs = 0; /* RS_DROPIN_TIMING: the share of t_unpack spent on sorting and copying records */
   /* resident flows (rs_group_set_flows, rs_group_schedule_tti_flows; scheduler 1 alone): resident[cell] == 3.  The cell's flows live in
    * the bearer stores and the counter stores above (a cell is resident in one form at a time), has_bearer mirrors their existence
    * bytes, and the slots' bearer words (0 or 1 per call position) travel in h_qin, one word per position. */
@@ -2679,15 +2685,17 @@ void rs_group_destroy(rs_group* g) {
     fprintf(stderr, "rs_group_schedule_tti x %ld (%.1f cells per call): prepare %.2f us, enqueue %.2f us, wait %.2f us, unpack %.2f us per call (%ld completed by the polled word, %ld by the stream; cell-TTIs served from the cell's CQI image %lld, that stored one %lld, without a cqi_epoch %lld)\n",
             g->n_calls, (double)g->n_cell_ttis / g->n_calls, g->t_prep / g->n_calls, g->t_enq / g->n_calls, g->t_wait / g->n_calls,
             g->t_unpack / g->n_calls, g->n_polled, g->n_fallback, (long long)g->n_reused, (long long)g->n_stored, (long long)g->n_plain);
+  if (g->timing && g->n_calls && g->t_recs > 0)
+    fprintf(stderr, "rs_group_run_records_at: of the unpack above, %.2f us per call sort and copy grant records\n", g->t_recs / g->n_calls);
   if (g->b && g->b->stream) (void)hipStreamSynchronize(g->b->stream);
   for (void* q : {(void*)g->d_in, (void*)g->d_out, (void*)g->d_count, (void*)g->d_img, (void*)g->d_prb, (void*)g->d_out2, (void*)g->d_chk,
                   (void*)g->pair[0].d_stores_chk, (void*)g->pair[1].d_stores_chk, (void*)g->pair[2].d_stores_chk, (void*)g->pair[3].d_stores_chk,
                   (void*)g->pair[4].d_stores_chk, (void*)g->pair[5].d_stores_chk, (void*)g->d_sent2, (void*)g->d_ravg,
                   (void*)g->d_rpend, (void*)g->d_rlast, (void*)g->d_rgather, (void*)g->d_ruid, (void*)g->d_qavg, (void*)g->d_qpend,
                   (void*)g->d_qdata, (void*)g->d_qhas, (void*)g->d_qin, (void*)g->d_cbytes, (void*)g->d_crbs, (void*)g->d_sent, (void*)g->d_acbytes,
-                  (void*)g->d_acrbs})
+                  (void*)g->d_acrbs, (void*)g->d_recs})
     if (q) (void)hipFree(q);
-  for (void* q : {(void*)g->h_qin, (void*)g->h_sent, (void*)g->h_sent2, (void*)g->h_in, (void*)g->h_out})
+  for (void* q : {(void*)g->h_qin, (void*)g->h_sent, (void*)g->h_sent2, (void*)g->h_in, (void*)g->h_out, (void*)g->h_recs})
     if (q) (void)hipHostFree(q);
   rs_batch_destroy(g->b);
   delete g;
@@ -2748,6 +2756,12 @@ struct GroupCall {
   /* a counted run (rs_group_run_counted_at; with run): the named cells' per-user counters are credited too; no_out: the caller wants no
    * per-TTI outputs (out == null) -- none is written, copied or unpacked */
   bool run_counted, no_out;
+  /* grant records (rs_group_run_records_at; with run_counted): recs != null -- one list of rec_cap records and one count per (slot,
+   * TTI) go to the caller; rec_dev is the lists' capacity on the device, min(rec_cap, the config's users) */
+  int32_t rec_cap, rec_dev;
+  rs_grant_record* recs;
+  int32_t* n_recs;
+  size_t rec_stride() const { return ((size_t)n_ttis * (size_t)rec_dev * sizeof(rs_grant_record) + 4 * (size_t)n_ttis + 31) / 32 * 32; } /* bytes per slot */
   int cell(int k) const { return cell_ids ? cell_ids[k] : k; }
   bool resident() const { return form != kGroupPlain; }
   int row() const { return run ? (run_counted ? (int)kGroupRunCounted : (int)kGroupRun) : counted ? (int)kGroupCounted : form; }
@@ -2807,6 +2821,37 @@ int rs_group_run_counted_at(rs_group* g, int32_t n, const int32_t* cell_ids, con
   c.no_out = out == nullptr;
   c.n_ttis = n_ttis;
   c.rands = rands;
+  return group_schedule(g, c);
+}
+
+/* most positions with a grant in one TTI of one cell.  Schedulers 1, 8, 9, 101 and 103 give an RBG to one user, and a
+ * grant needs an RBG: min(users, RBGs).  UpperBound (10) counts an RBG for every slice that took it: a slice takes at most R entries of
+ * its own list (rs_phase_p4.inc: k < quota inside a segment of R), a granted user leads at least one of them and belongs to one slice
+ * of the config, whatever subset a call names: the sum over the slices of min(the slice's users, R) -- the config's users when every
+ * slice has at most R of them.  (Nothing tighter follows from the quotas without a bound on the slice offsets they carry.) */
+int rs_group_grant_bound(const rs_group* g) {
+  if (!g) return fail(RS_ERR_INVALID, "null group");
+  const rs_batch* b = g->b;
+  if (b->sched != RS_SCHED_UPPERBOUND) return std::min(b->U, b->R);
+  std::vector<int> per_slice((size_t)b->S, 0);
+  for (int u = 0; u < b->U; u++) per_slice[(size_t)b->u2s[(size_t)u]]++;
+  int bound = 0;
+  for (int n_s : per_slice) bound += std::min(n_s, b->R);
+  return bound;
+}
+
+int rs_group_run_records_at(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in, int32_t n_ttis, const double* now,
+                            const int32_t* rands, rs_tti_out* out, int32_t rec_cap, rs_grant_record* recs, int32_t* n_recs) {
+  if (!g || !in || !now) return fail(RS_ERR_INVALID, "null argument");
+  if (!recs || !n_recs) return fail(RS_ERR_INVALID, "recs and n_recs must both be given (rs_group_run_counted_at is the run without records)");
+  GroupCall c = {n, cell_ids, in, out, now, nullptr, nullptr, nullptr, kGroupResident, false};
+  c.run = c.run_counted = true;
+  c.no_out = out == nullptr;
+  c.n_ttis = n_ttis;
+  c.rands = rands;
+  c.rec_cap = rec_cap;
+  c.recs = recs;
+  c.n_recs = n_recs;
   return group_schedule(g, c);
 }
 
@@ -2937,6 +2982,12 @@ int group_validate(rs_group* g, GroupCall& c) {
         return fail(RS_ERR_INVALID, "cell slot %d (cell %d): the clock step from TTI %d to TTI %d, %.3g s, is neither 0 nor at least %.3g s", k, cell, t - 1, t, z - a, kResidentMinDt);
     }
   }
+  if (c.recs) { /* grant records: behind the counted run's own rules */
+    const int bound = rs_group_grant_bound(g);
+    if (c.rec_cap < bound) return fail(RS_ERR_INVALID, "rec_cap %d is below rs_group_grant_bound, %d: a TTI's grants might not fit", c.rec_cap, bound);
+    c.rec_dev = std::min(c.rec_cap, b->U); /* (a TTI has at most one grant per position) */
+    if ((size_t)n * c.rec_stride() / 4 > (size_t)INT32_MAX) return fail(RS_ERR_INVALID, "the call's record blocks are too large (%zu bytes per slot)", c.rec_stride());
+  }
   return RS_OK;
 }
 
@@ -2971,6 +3022,7 @@ void group_fill_header(const rs_group* g, const GroupCall& c, int k, const CtxLa
     h.run_table = (int32_t)(table - (size_t)k * g->in_stride);
     h.run_out_step = (int32_t)g->out_stride;
     h.run_no_out = c.no_out ? 1 : 0;
+    h.run_rec_cap = c.recs ? c.rec_dev : 0;
     for (int t = 0; t < c.n_ttis; t++) {
       const int32_t pair[2] = {c.rands ? c.rands[2 * c.at(k, t)] : 0, c.rands ? c.rands[2 * c.at(k, t) + 1] : 0};
       memcpy(g->h_in + table + (size_t)t * RS_GROUP_RUN_ROW_BYTES, &c.now[c.at(k, t)], 8);
@@ -3129,6 +3181,10 @@ void group_fill_launch(const rs_group* g, const GroupCall& c, RsLaunch* launch) 
     L.grp_sent = g->z_sent ? g->z_sent : g->d_sent;
     L.grp_sent_stride = 2 * (int64_t)b->U;
   }
+  if (c.recs) { /* (a counted run has no sent rows: the two words carry its record blocks, device memory, words per slot) */
+    L.grp_sent = (int32_t*)g->d_recs;
+    L.grp_sent_stride = (int64_t)(c.rec_stride() / 4);
+  }
 }
 
 /* the twin of the counted calls' sent block for the built-in kernel of a checked call: pinned and mapped when the first is, else a
@@ -3202,7 +3258,7 @@ int group_run(rs_group* g, GroupCall& c, RsLaunch& L) {
   if (!c.zc && c.run)
     HIP_TRY(hipMemcpyAsync(g->d_in + g->run_table_off, g->h_in + g->run_table_off, (size_t)c.n * RS_GROUP_MAX_RUN * RS_GROUP_RUN_ROW_BYTES, hipMemcpyHostToDevice, st));
   if ((f.sets() & RS_GROUP_SET_BEARERS) && !g->z_qin) HIP_TRY(hipMemcpyAsync(g->d_qin, g->h_qin, 8 * (size_t)c.n * b->U, hipMemcpyHostToDevice, st));
-  c.poll = c.zc && g->poll;
+  c.poll = c.zc && g->poll && !c.recs; /* (records come back by a copy on the stream: the stream says when) */
   if (c.poll) {
     if (++g->seq == 0) g->seq = 1; /* (0 is the word's initial value) */
     L.done_flag = (uint32_t*)(g->z_out + g->flag_off);
@@ -3228,6 +3284,7 @@ int group_run(rs_group* g, GroupCall& c, RsLaunch& L) {
   g->last_call_jit = c.kd != nullptr;
   if (!c.zc && !c.no_out) HIP_TRY(hipMemcpyAsync(g->h_out, g->d_out, (size_t)c.n * c.ttis() * g->out_stride, hipMemcpyDeviceToHost, st));
   if ((f.sets() & RS_GROUP_SET_SENT) && !g->z_sent) HIP_TRY(hipMemcpyAsync(g->h_sent, g->d_sent, 8 * (size_t)c.n * b->U, hipMemcpyDeviceToHost, st));
+  if (c.recs) HIP_TRY(hipMemcpyAsync(g->h_recs, g->d_recs, (size_t)c.n * c.rec_stride(), hipMemcpyDeviceToHost, st));
   return RS_OK;
 }
 
@@ -3436,6 +3493,54 @@ int group_grow_out(rs_group* g, size_t slots) {
   return RS_OK;
 }
 
+/* The record blocks of a call with grant records: device block and pinned twin grow to the largest call so far; new blocks first, a
+ * failure leaves the group as it was. */
+int group_grow_recs(rs_group* g, size_t bytes) {
+  if (bytes <= g->recs_bytes) return RS_OK;
+  uint8_t *d = nullptr, *h = nullptr;
+  if (hipMalloc(&d, bytes) != hipSuccess || hipHostMalloc((void**)&h, bytes, hipHostMallocDefault) != hipSuccess) {
+    (void)hipGetLastError();
+    if (d) (void)hipFree(d);
+    if (h) (void)hipHostFree(h);
+    return fail(RS_ERR_HIP, "allocation of the run's record blocks failed (%zu bytes each)", bytes);
+  }
+  if (g->d_recs) (void)hipFree(g->d_recs);
+  if (g->h_recs) (void)hipHostFree(g->h_recs);
+  g->d_recs = d;
+  g->h_recs = h;
+  g->recs_bytes = bytes;
+  return RS_OK;
+}
+
+/* The caller's records: per (slot, TTI) the count, and the list in ascending position -- the device fills a list in the order its waves
+ * arrive, a position occurs once per TTI, so an insertion sort by position over at most rec_dev records makes the order the ABI
+ * promises, whatever the arrival order was.  A count above the capacity: the device wrote nothing behind the capacity; the count goes
+ * to the caller as it is and the call fails (the bound of rs_group_grant_bound would be wrong). */
+int group_unpack_records(const rs_group* g, const GroupCall& c) {
+  int bad_k = -1, bad_t = -1, bad_n = 0;
+  for (int k = 0; k < c.n; k++) {
+    const uint8_t* const slot = g->h_recs + (size_t)k * c.rec_stride();
+    const int32_t* const counts = (const int32_t*)(slot + (size_t)c.n_ttis * (size_t)c.rec_dev * sizeof(rs_grant_record));
+    for (int t = 0; t < c.n_ttis; t++) {
+      const int count = counts[t];
+      c.n_recs[c.at(k, t)] = count;
+      if ((count < 0 || count > c.rec_dev) && bad_k < 0) { bad_k = k; bad_t = t; bad_n = count; }
+      const int m = count < 0 ? 0 : std::min(count, (int)c.rec_dev);
+      const rs_grant_record* const src = (const rs_grant_record*)slot + (size_t)t * (size_t)c.rec_dev;
+      rs_grant_record* const dst = c.recs + c.at(k, t) * (size_t)c.rec_cap;
+      for (int j = 0; j < m; j++) {
+        int at = j;
+        for (; at > 0 && dst[at - 1].pos > src[j].pos; at--) dst[at] = dst[at - 1];
+        dst[at] = src[j];
+      }
+    }
+  }
+  if (bad_k >= 0)
+    return fail(RS_ERR_STATE, "cell slot %d (cell %d), TTI %d: the device counted %d grants, the record list holds %d (rs_group_grant_bound is wrong for this config); the call's state and counters are complete, the TTI's records are not",
+                bad_k, c.cell(bad_k), bad_t, bad_n, (int)c.rec_dev);
+  return RS_OK;
+}
+
 /* one group call, phase by phase; RS_DROPIN_TIMING splits it into prepare, enqueue, wait and unpack */
 int group_schedule(rs_group* g, GroupCall c) {
   rs_batch* b = g->b;
@@ -3447,6 +3552,7 @@ int group_schedule(rs_group* g, GroupCall c) {
   if ((rc = group_pack_slots(g, c))) return rc;
   ImageGuard guard{g, c, false};
   if (c.run && !c.no_out && (rc = group_grow_out(g, (size_t)c.n * (size_t)c.n_ttis))) return rc;
+  if (c.recs && (rc = group_grow_recs(g, (size_t)c.n * c.rec_stride()))) return rc;
   const clk::time_point t1 = g->timing ? clk::now() : clk::time_point();
   c.zc = g->z_in != nullptr && !c.has_prb && !b->any_alpha;
   RsLaunch L;
@@ -3460,8 +3566,11 @@ int group_schedule(rs_group* g, GroupCall c) {
   const clk::time_point t3 = g->timing ? clk::now() : clk::time_point();
   group_commit_images(g, c);
   if (!c.no_out) group_unpack(g, c);
+  const clk::time_point t3r = g->timing ? clk::now() : clk::time_point();
+  const int rc_recs = c.recs ? group_unpack_records(g, c) : RS_OK;
   if (g->timing) {
     const clk::time_point t4 = clk::now();
+    if (c.recs) g->t_recs += std::chrono::duration<double, std::micro>(t4 - t3r).count();
     auto us = [](clk::time_point a, clk::time_point b2) { return std::chrono::duration<double, std::micro>(b2 - a).count(); };
     g->t_prep += us(t0, t1);
     g->t_enq += us(t1, t2);
@@ -3470,10 +3579,10 @@ int group_schedule(rs_group* g, GroupCall c) {
     g->n_calls++;
     g->n_cell_ttis += (long)c.n * c.ttis();
   }
-  if (c.store_failed_now)
+  if (c.store_failed_now && !rc_recs) /* (a failed record check keeps its own message) */
     snprintf(g_err, sizeof g_err, "note: the group's per-PRB report store (%zu bytes) could not be allocated: calls with cqi_prb are served as if "
              "cqi_epoch were 0 from now on (same results, the block is sent on every call)", g->prb_stride * (size_t)g->n_cells);
-  return RS_OK;
+  return rc_recs;
 }
 }  // namespace
 

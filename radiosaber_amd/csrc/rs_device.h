@@ -420,12 +420,24 @@ struct RsGroupCell {
   /* a counted run without outputs (rs_group_run_counted_at with out == NULL, rs_group_run_counted_kernel; no other kernel reads it):
    * not 0 -- the run writes no output block, the body's log pointers stay null for all its TTIs */
   int32_t run_no_out;
-  int32_t pad_[RS_GROUP_HDR_BYTES / 4 - 26];
+  /* grant records of a counted run (rs_group_run_records_at; read by rs_group_run_counted_kernel alone, once per launch): 0 -- none;
+   * else the capacity of one TTI's record list.  The slot's record block lies at grp_sent + slot * grp_sent_stride (words; the counted
+   * run has no sent rows, its row of rs_group_form has no RS_GROUP_SET_SENT: the launch block carries the block there and does not
+   * grow), in DEVICE memory: run_ttis lists of run_rec_cap RsGrantRecord, then run_ttis count words. */
+  int32_t run_rec_cap;
+  int32_t pad_[RS_GROUP_HDR_BYTES / 4 - 27];
 };
+/* one grant of one TTI, as step 3 of a counted run credits it: rs_grant_record of the ABI, two 16-byte halves */
+struct RsGrantRecord {
+  int32_t pos, user_id, bytes, nprb;
+  int64_t cum_bytes, cum_rbs;
+};
+static_assert(sizeof(RsGrantRecord) == 32 && __builtin_offsetof(RsGrantRecord, cum_bytes) == 16, "rs_grant_record is 32 bytes, the counters its second half");
 #define RS_GROUP_RUN_ROW_BYTES 16
 static_assert(sizeof(RsGroupCell) == RS_GROUP_HDR_BYTES, "the slot header keeps its size: new words come out of its padding");
 static_assert(__builtin_offsetof(RsGroupCell, image_mode) == 72 && __builtin_offsetof(RsGroupCell, now) == 80, "no existing word of the slot header moves");
 static_assert(__builtin_offsetof(RsGroupCell, run_ttis) == 88 && __builtin_offsetof(RsGroupCell, run_no_out) == 100, "the run's words keep their places, the new one lies behind them");
+static_assert(__builtin_offsetof(RsGroupCell, run_rec_cap) == 104, "the records' word comes out of the padding behind run_no_out");
 
 /* ------------------------------------------------------------------------------------------------------------------
  * The forms of a group call: THE description.  The body text (rs_phase_group.inc), the built-in kernels, their launcher and LDS

@@ -59,7 +59,11 @@
  *   rs_phase_p5.inc; UpperBound (10) adapts in rs_phase_p4.inc and leaves no masks -- there the count is the user's taken entries of
  *   its slice's list in LDS, which is what its user_nprb is made of (an RBG that two slices took counts for both, so the owner map
  *   would fall short).  With the slot header's run_no_out set the body's log pointers are null for the whole run: no output block is
- *   written.  Both counter adds of one user in TTIs t and t + 1 are ordered by the fence and barrier that order the credit. */
+ *   written.  Both counter adds of one user in TTIs t and t + 1 are ordered by the fence and barrier that order the credit.
+ * run with cnt and the slot header's run_rec_cap set (rs_group_run_records_at): step 3's thread also writes a grant record -- position,
+ *   user id, bytes, PRBs, both counters as just stored -- into the TTI's list of the slot's record block in device memory; places are
+ *   handed out per wave (ballot, one add on the TTI's count word, prefix popcount), a place at or behind the capacity is not written.
+ *   The counted run's step 3 is a text of its own for that: a trip count every lane of a wave shares. */
   constexpr RsGroupForm kGrpF = rs_group_form(kGrpForm);
   constexpr bool kGrpRes = kGrpF.res, kGrpQue = kGrpF.que, kGrpCnt = kGrpF.cnt, kGrpFlow = kGrpF.flow, kGrpRun = kGrpF.run;
   static_assert(kGrpFixed ? rs_group_form_builds(kGrpForm, kGrpSched) : rs_group_form_serves(kGrpForm, kGrpSched), "no kernel of this form for this scheduler (rs_group_form, rs_device.h)");
@@ -139,6 +143,14 @@
      * barriers lie between the two) */
     double last = dword(p.grp_last + cell);
     uint8_t* o = out;
+    if constexpr (kGrpCnt) {
+      /* grant records (rs_group_run_records_at): the slot's capacity word, read once per launch.  The counted run has no sent rows, so
+       * the launch block's grp_sent / grp_sent_stride carry the record block; the workgroup's copy of the two words -- which the body
+       * does not read -- keeps the slot's own block and the capacity (0: no records, nothing is read or written through the pointer). */
+      const int rec_cap = word(&h->run_rec_cap);
+      q.grp_sent = rec_cap != 0 ? p.grp_sent + (size_t)blockIdx.x * (size_t)p.grp_sent_stride : nullptr;
+      q.grp_sent_stride = (int64_t)rec_cap;
+    }
     for (int t = 0; t < n_run; ++t) {
       const uint8_t* const tr = table + (size_t)t * RS_GROUP_RUN_ROW_BYTES;
       const double now = dword((const double*)tr);
@@ -175,6 +187,12 @@
         }
         last = now;
       }
+      if constexpr (kGrpCnt) {
+        /* (the TTI's record count starts at 0: one thread's store ahead of the barrier below, which every wave passes before its
+         * first add in step 3) */
+        if (q.grp_sent_stride != 0 && threadIdx.x == 0)
+          __hip_atomic_store((int32_t*)((RsGrantRecord*)q.grp_sent + (size_t)n_run * (size_t)q.grp_sent_stride) + t, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
       /* behind it a thread reads averages that other threads wrote */
       __syncthreads();
       /* 2. the call's averages, gathered again behind every update.  Thread i writes row entry i and is the thread that reads it in the
@@ -190,39 +208,76 @@
       }
       rs_cell_body<kGrpSched, kGrpEpt, kGrpFixed, true, false, true>(q, lds);
       /* 3. the grants, from LDS, by call position: the resident form's step 3 */
-      for (int i = threadIdx.x; i < q.U; i += nthreads) {
-        const int bytes = granted[i];
-#if defined(RS_FAULT_INJECT_RUN)
-        /* tests only (tests/test_gpu_group_run_specialize.py): a deliberately wrong run-time build of the RUN form -- in the LAST TTI of
-         * a run every served user is credited a byte more; the outputs of all T TTIs stay right, so only the self-check's comparison
-         * of the resident stores can catch it.  A value, no address or index, and never T; the twin of RS_FAULT_INJECT_RESIDENT. */
-        if (bytes != 0) r_pend[in_uid != 0 ? ids[i] : i] += bytes + ((kGrpFixed && t + 1 == n_run) ? 1 : 0);
-#else
-        if (bytes != 0) r_pend[in_uid != 0 ? ids[i] : i] += bytes;
-#endif
-        if constexpr (kGrpCnt) {
+      if constexpr (kGrpCnt) {
+        /* The counted run's step 3, a text of its own: the credit above, operation by operation, plus the counters and -- with the
+         * slot's run_rec_cap set -- one grant record per credited position.  The trip count is the workgroup's (every lane of a wave
+         * stays for the ballot; a lane behind the last position holds no grant). */
+        int64_t* const c_bytes = p.grp_cbytes + (size_t)cell * (size_t)n_all; /* the cell's counters, by user id */
+        int64_t* const c_rbs = p.grp_crbs + (size_t)cell * (size_t)n_all;
+        const int n_rbg = kGrpFixed ? RS_JIT_R : p.R, prb_per_rbg = kGrpFixed ? RS_JIT_G : p.G;
+        const int rec_cap = (int)q.grp_sent_stride; /* (wave-uniform: from a header word, see above the loop) */
+        RsGrantRecord* const rec_list = (RsGrantRecord*)q.grp_sent + (size_t)t * (size_t)rec_cap;
+        int32_t* const rec_count = (int32_t*)((RsGrantRecord*)q.grp_sent + (size_t)n_run * (size_t)rec_cap) + t;
+        for (int base = 0; base < q.U; base += nthreads) {
+          const int i = base + (int)threadIdx.x;
+          const bool inside = i < q.U;
+          const int bytes = inside ? granted[i] : 0;
           /* GetListOfAllocatedRBs()->size() of the position's block.  A user is named once per call, a cell once per launch: plain
            * 64-bit adds by the position's thread, as the counted form's. */
-          int64_t* const c_bytes = p.grp_cbytes + (size_t)cell * (size_t)n_all; /* the cell's counters, by user id */
-          int64_t* const c_rbs = p.grp_crbs + (size_t)cell * (size_t)n_all;
-          const int n_rbg = kGrpFixed ? RS_JIT_R : p.R, prb_per_rbg = kGrpFixed ? RS_JIT_G : p.G;
-          int n_held;
-          if constexpr (kGrpSched == 10) {
-            /* (every thread walks its user's slice segment, grant or not: R entries of UpperBound's ent_user, rs_phase_p4.inc; the ones
-             * past the slice's quota say "not taken") */
-            const uint16_t* const taken = (const uint16_t*)(lds + (kGrpFixed ? kGrpCv.off_elems : p.off_elems));
-            const uint16_t* const seg = taken + (int)q.user_slice[i] * n_rbg;
-            n_held = 0;
-            for (int k = 0; k < n_rbg; ++k) n_held += seg[k] == (uint16_t)i ? 1 : 0;
-          } else {
-            const RsMisc* const cm = (const RsMisc*)(lds + (kGrpFixed ? kGrpCv.off_misc : p.off_misc));
-            n_held = __popcll(cm->maskA[(i + 1) & 63] & cm->maskB[(i + 1) >> 6]);
+          int n_held = 0;
+          if (inside) {
+            if constexpr (kGrpSched == 10) {
+              /* (every thread walks its user's slice segment, grant or not: R entries of UpperBound's ent_user, rs_phase_p4.inc; the
+               * ones past the slice's quota say "not taken") */
+              const uint16_t* const taken = (const uint16_t*)(lds + (kGrpFixed ? kGrpCv.off_elems : p.off_elems));
+              const uint16_t* const seg = taken + (int)q.user_slice[i] * n_rbg;
+              for (int k = 0; k < n_rbg; ++k) n_held += seg[k] == (uint16_t)i ? 1 : 0;
+            } else {
+              const RsMisc* const cm = (const RsMisc*)(lds + (kGrpFixed ? kGrpCv.off_misc : p.off_misc));
+              n_held = __popcll(cm->maskA[(i + 1) & 63] & cm->maskB[(i + 1) >> 6]);
+            }
           }
+          const int id = bytes != 0 ? (in_uid != 0 ? ids[i] : i) : 0;
+          const int nprb = n_held * prb_per_rbg;
+          int64_t cb = 0, cr = 0;
           if (bytes != 0) {
-            const int id = in_uid != 0 ? ids[i] : i;
-            c_bytes[id] += (int64_t)bytes;
-            c_rbs[id] += (int64_t)(n_held * prb_per_rbg);
+            r_pend[id] += bytes;
+            cb = c_bytes[id] + (int64_t)bytes;
+            cr = c_rbs[id] + (int64_t)nprb;
+            c_bytes[id] = cb;
+            c_rbs[id] = cr;
           }
+          if (rec_cap != 0) {
+            /* a place in the TTI's list per grant: one add per wave on the list's count word (device memory, zeroed ahead of this
+             * TTI's first barrier; the workgroup owns the slot), the wave's first place broadcast, a lane's place behind those of the
+             * granted lanes below it.  Across waves the places come as the waves arrive: the host sorts a list by position.  A place
+             * at or behind the capacity is not written; the count says so to the host. */
+            const unsigned long long got = __ballot(bytes != 0);
+            if (got != 0ull) {
+              const int lane = (int)(threadIdx.x & 63u);
+              int first = 0;
+              if (lane == 0) first = __hip_atomic_fetch_add(rec_count, (int)__popcll(got), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+              first = __builtin_amdgcn_readfirstlane(first);
+              const int place = first + (int)__popcll(got & ((1ull << lane) - 1ull));
+              if (bytes != 0 && place < rec_cap) {
+                int4* const dst = (int4*)(rec_list + place);
+                dst[0] = make_int4(i, id, bytes, nprb);
+                dst[1] = make_int4((int)(uint32_t)cb, (int)(cb >> 32), (int)(uint32_t)cr, (int)(cr >> 32));
+              }
+            }
+          }
+        }
+      } else {
+        for (int i = threadIdx.x; i < q.U; i += nthreads) {
+          const int bytes = granted[i];
+#if defined(RS_FAULT_INJECT_RUN)
+          /* tests only (tests/test_gpu_group_run_specialize.py): a deliberately wrong run-time build of the RUN form -- in the LAST TTI of
+           * a run every served user is credited a byte more; the outputs of all T TTIs stay right, so only the self-check's comparison
+           * of the resident stores can catch it.  A value, no address or index, and never T; the twin of RS_FAULT_INJECT_RESIDENT. */
+          if (bytes != 0) r_pend[in_uid != 0 ? ids[i] : i] += bytes + ((kGrpFixed && t + 1 == n_run) ? 1 : 0);
+#else
+          if (bytes != 0) r_pend[in_uid != 0 ? ids[i] : i] += bytes;
+#endif
         }
       }
       if (t + 1 < n_run) {

@@ -47,6 +47,22 @@ def stderr_lines(tbs_bits, rbg_to_user, user_to_slice: Sequence[int], rbg_size: 
     return out
 
 
+def run_record_lines(records, user_to_slice: Sequence[int], first_ts: int = 100, pf_format: bool = False) -> List[str]:
+    """records[t]: the grant records of ONE cell's TTI t (GroupScheduler.run_counted_at(..., records=True)[1][k]: a sequence of
+    arrays of api.GRANT_RECORD) -> the lines stderr_lines writes for the same run
+    with the same starting counters.  A record carries the user's counters after the TTI's credit, so nothing is summed here; the
+    records of a TTI come in DoStopSchedule's order.  user_to_slice is by user id; pf_format as in stderr_lines."""
+    out = []
+    for t, recs in enumerate(records):
+        for r in recs:
+            u, cb, cr = int(r["user_id"]), int(r["cum_bytes"]), int(r["cum_rbs"])
+            if pf_format:
+                out.append(f"{first_ts + t} flow: {u} cumu_bytes: {cb} cumu_rbs: {cr} hol_delay: 0")
+            else:
+                out.append(f"{first_ts + t} app: {u} cumu_bytes: {cb} cumu_rbs: {cr} hol_delay: 0 user: {u} slice: {user_to_slice[u]}")
+    return out
+
+
 def stdout_lines(rbg_to_user, final_cqi, target, quota, cqi_of, first_ts: int = 100, transport: bool = True) -> List[str]:
     """The reference's allocation map.  cqi_of(n, user, rbg) -> CQI the user reported on that RBG."""
     rbg_to_user = np.asarray(rbg_to_user)

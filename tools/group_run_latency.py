@@ -2,9 +2,10 @@
 """us per cell-TTI of a backlogged K-cell host between two CQI reports: (a) 40 rs_group_schedule_tti_at calls against (b) one
 rs_group_run_at of 40 (profiles/group_run.md); (b) against (j) the same run on the group's own run-time builds of the run kernel
 (rs_group_specialize_run; profiles/group_run_specialize.md, where the mode was called c); (b) against (c) one rs_group_run_counted_at of
-40 without outputs and (d) the same with outputs (profiles/group_run_counted.md).
+40 without outputs and (d) the same with outputs (profiles/group_run_counted.md); (d) against (r) one rs_group_run_records_at of 40
+without outputs, grant records on (profiles/group_run_records.md).
 
-    RS_DROPIN_TIMING=1 python tools/group_run_latency.py [--blocks 20] [--ttis 40] [--modes ab | bj | bcd | ...] [--repeats 3]
+    RS_DROPIN_TIMING=1 python tools/group_run_latency.py [--blocks 20] [--ttis 40] [--modes ab | bj | bcd | dr | ...] [--repeats 3]
 
 Workloads: 8, 27 and 64 cells; 500 users x 25 RBGs and 100 users x 64 RBGs; scheduler 9; resident averages; cqi_epoch on, a new number
 (the same reports) every block of 40 TTIs, so that the first TTI of a block stores the cells' images and the other 39 are image hits.
@@ -13,7 +14,7 @@ holds when a later mode's worst repeat lies below the first mode's best.  (RS_TR
 parent commit's library is measured by a process of its own, alternating with this one's -- --repeats 1 per process.)  Mode (j) warms up until the self-check of the build that
 serves its runs has finished (RS_DROPIN_SELFCHECK_CALLS checked runs, default 8): no timed run is a checked one.  The arguments are marshalled once, outside the timed region: the time is that of
 the library calls alone.  RS_DROPIN_TIMING=1 makes the library print its own prepare / enqueue / wait / unpack split per group on stderr
-when the group is closed (in the order of --modes; per CALL: a call of (b), (c), (d) or (j) is 40 TTIs)."""
+when the group is closed (in the order of --modes; per CALL: a call of (b), (c), (d), (j) or (r) is 40 TTIs)."""
 import argparse
 import ctypes as C
 import os
@@ -35,13 +36,13 @@ ap.add_argument("--cells", type=int, nargs="*", default=[8, 27, 64])
 ap.add_argument("--shapes", type=int, nargs="*", default=[0, 1], help="0: 500 users x 25 RBGs, 1: 100 users x 64 RBGs")
 ap.add_argument("--repeats", type=int, default=3)
 ap.add_argument("--modes", default="ab", help="letters of a: 40 at-calls, b: one run, j: the run on the group's own builds, c: one counted run without "
-                "outputs, d: one counted run with outputs; the first is what the others are held against")
+                "outputs, d: one counted run with outputs, r: one counted run without outputs, grant records on; the first is what the others are held against")
 args = ap.parse_args()
-assert args.modes and set(args.modes) <= set("abcdj") and len(set(args.modes)) == len(args.modes)
+assert args.modes and set(args.modes) <= set("abcdjr") and len(set(args.modes)) == len(args.modes)
 T = args.ttis
 M0 = args.modes[0]
 NAMES = {"a": f"{T} at-calls", "b": f"one run of {T}", "j": f"one specialised run of {T}", "c": f"one counted run of {T} without outputs",
-         "d": f"one counted run of {T}"}
+         "d": f"one counted run of {T}", "r": f"one counted run of {T} without outputs, with records"}
 SHAPES = ((25, 25, 4), (5, 64, 8))
 
 
@@ -70,10 +71,13 @@ for ues, R, G in (SHAPES[i] for i in args.shapes):
             g = rs.GroupScheduler(sc, R, G, K, sched=9, jit_run=mode == "j")
             for k in range(K):
                 g.set_avg(k, avg[k], 0.1)
-                if mode in "cd":
+                if mode in "cdr":
                     g.set_avg_counters(k)
             groups[mode] = [g, marshal(sc, R, G, K, 1 if mode == "a" else T, cqi), 0.1, 0]   # group, arguments, clock, blocks done
         L = lib()
+        if "r" in groups:   # (the caller's record lists, rs_group_grant_bound records per cell-TTI, allocated once like the other arguments)
+            cap = groups["r"][0].grant_bound
+            recs, n_recs = np.zeros((K, T, cap), rs.api.GRANT_RECORD), np.zeros((K, T), np.int32)
 
         def block(mode):
             g, (ins, outs, _), now, done = groups[mode]
@@ -91,7 +95,11 @@ for ues, R, G in (SHAPES[i] for i in args.shapes):
                 t = np.ascontiguousarray(np.broadcast_to(now + 0.001 * np.arange(1, T + 1), (K, T)))
                 now = float(t[0, -1])
                 run = L.rs_group_run_counted_at if mode in "cd" else L.rs_group_run_at
-                _check(run(g._h, K, None, ins, T, t.ctypes.data_as(C.POINTER(C.c_double)), rands.ctypes.data_as(C.POINTER(C.c_int32)), None if mode == "c" else outs))
+                if mode == "r":
+                    _check(L.rs_group_run_records_at(g._h, K, None, ins, T, t.ctypes.data_as(C.POINTER(C.c_double)), rands.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                     None, cap, recs.ctypes.data, n_recs.ctypes.data_as(C.POINTER(C.c_int32))))
+                else:
+                    _check(run(g._h, K, None, ins, T, t.ctypes.data_as(C.POINTER(C.c_double)), rands.ctypes.data_as(C.POINTER(C.c_int32)), None if mode == "c" else outs))
             groups[mode][2], groups[mode][3] = now, done + 1
 
         for mode in args.modes:
