@@ -2410,8 +2410,80 @@ int rs_set_slice_offset(rs_ctx* c, const double* offset) {
 
 /* ---- a group of drop-in cells: one TTI of K cells in one launch (include/radiosaber_hip.h) ---- */
 
+namespace {
+/* One cell's residency.  A cell is resident in one form at a time or in none; the form's counters -- the per-user counters of the
+ * averages, the bearer counters of the bearers (a flow-resident cell always has its counters: no state of its own) -- exist only
+ * on top of their form, so a cell in no form has none.  Beside it the host's mirror of the cell's clock: the time of its last
+ * update, and whether no byte can be waiting for the next one (nothing served since the form's setter or an all-zero
+ * rs_group_set_pending).  Only the transitions below change the record. */
+struct GroupCellState {
+  enum Form : uint8_t { kNone, kAverages, kBearers, kFlows };
+  bool in(Form f) const { return form_ == f; }
+  bool counted(Form f) const { return form_ == f && counted_; } /* f's counters exist */
+  bool pending_zero() const { return pending_zero_; }
+  double last_update() const { return last_update_; }
+  /* a setter of form f starts its copies: the cell is in no form until enter().  Returns whether f's counters and their term
+   * go on behind it (the cell was in f, counted: the setter of a form keeps that form's counters and ends the other's) */
+  bool leave_for(Form f) {
+    const bool keep = counted(f);
+    leave();
+    return keep;
+  }
+  void leave() { /* (a failed call too: the stores half written, perhaps) */
+    form_ = kNone;
+    counted_ = false;
+  }
+  void enter(Form f, bool counters, double last_update) {
+    form_ = f;
+    counted_ = counters && (f == kAverages || f == kBearers);
+    pending_zero_ = true;
+    last_update_ = last_update;
+  }
+  void end_counters() { counted_ = false; }
+  void start_counters() { counted_ = form_ == kAverages || form_ == kBearers; }
+  void set_pending_zero(bool zero) { pending_zero_ = zero; }
+  /* a served call: dated `last` (a run: its last TTI's clock -- a step of 0 repeats the value before it), and grants may be waiting.
+   * (An update-only slot credits nothing: behind an update no byte is waiting, without one nothing changed.) */
+  void served(bool credited, double first, double last) {
+    if (credited) pending_zero_ = false;
+    else if (first != last_update_) pending_zero_ = true;
+    last_update_ = last;
+  }
+
+ private:
+  Form form_ = kNone;
+  bool counted_ = false, pending_zero_ = false;
+  double last_update_ = 0.0;
+};
+
+/* A pinned block of words that travels beside the call slots: the kernel reads or writes it in place through its mapping (z) when
+ * the group's main block on that side is mapped, else through a device twin (d) and a copy on the stream. */
+struct GroupStaged {
+  int32_t *h = nullptr, *z = nullptr, *d = nullptr;
+  int32_t* dev() const { return z ? z : d; } /* the pointer the kernel gets */
+  bool copied() const { return !z; }         /* a stream copy between h and d is needed */
+  bool make(size_t bytes, unsigned flags, bool map) { /* all or none; zeroed */
+    bool ok = hipHostMalloc((void**)&h, bytes, flags) == hipSuccess;
+    void* m = nullptr;
+    if (ok && map && hipHostGetDevicePointer(&m, h, 0) == hipSuccess) z = (int32_t*)m;
+    if (ok && !z) ok = hipMalloc(&d, bytes) == hipSuccess;
+    if (ok) memset(h, 0, bytes);
+    else release();
+    return ok;
+  }
+  void release() {
+    if (d) (void)hipFree(d);
+    if (h) (void)hipHostFree(h);
+    h = z = d = nullptr;
+  }
+};
+
+/* the device stores of the resident forms: the rows of kGroupStores, the indices of rs_group::store */
+enum GroupStoreId { kRavg, kRpend, kRlast, kRgather, kRuid, kQavg, kQpend, kQdata, kQhas, kCbytes, kCrbs, kAcbytes, kAcrbs, kGroupNStores };
+}  // namespace
+
 struct rs_group {
-  rs_batch* b = nullptr;     /* a direct-mode batch of n_cells cells: the config's device tables, [cells][S] slice state, [cells] scalars, the stream */
+  rs_batch* b = nullptr;    /* a direct-mode batch of n_cells cells: the config's device tables, [cells][S] slice state, [cells] scalars, the stream */
   int n_cells = 0;
   /* one mapped pinned block each way, n_cells call slots each, and their device twins for the calls that copy (per-PRB reports,
    * customised slices: read again and again inside the TTI).  Input slot: RsGroupCell header | the single call's input block;
@@ -2464,54 +2536,44 @@ struct rs_group {
     uint8_t* d_stores_chk = nullptr;
     char msg[512] = "";
   };
-  GroupPair pair[6]; /* by kGroupPlain, kGroupResident, kGroupQueued, kGroupFlows, kGroupCounted, kGroupRun */
+  GroupPair pair[RS_GROUP_RUN + 1]; /* by GroupForm::pair: every form's but the counted run's, which has no run-time builds */
   /* every pair's: the built-in kernel's output slots (out_slots of them, as d_out: group_grow_out grows both for a run); the group's
    * slice state + scalars before / after it */
   uint8_t *d_out2 = nullptr, *d_chk = nullptr;
   std::vector<uint8_t> h_out2;
-  /* resident averages (rs_group_set_avg, rs_group_schedule_tti_at): per cell [U] averages, [U] pending bytes and the time of their
-   * last update on the device (allocated by the first rs_group_set_avg), the gather rows of calls that name their users, and on the
-   * host which cells are resident and a mirror of their last-update times (the clock check needs no read-back) */
-  double *d_ravg = nullptr, *d_rlast = nullptr, *d_rgather = nullptr;
-  int32_t *d_rpend = nullptr, *d_ruid = nullptr;
-  std::vector<uint8_t> resident, pending_zero; /* pending_zero: no byte can be waiting (nothing served since rs_group_set_avg / an all-zero rs_group_set_pending) */
-  std::vector<double> last_update;
-  /* resident bearers (rs_group_set_bearers, rs_group_schedule_tti_queued): per cell [U][2] averages, pending bytes and existence bytes
-   * of the users' two bearers and the call's data words in call order (allocated by the first rs_group_set_bearers); d_rlast, d_rgather
-   * and d_ruid above serve both forms.  resident[cell] says which: 0 none, 1 averages (rs_group_set_avg), 2 bearers.  The slots' data
-   * words travel in a pinned block of their own (h_qin: [n_cells][U][2], mapped: z_qin, else copied to d_qin), so that the slots of
-   * the other calls keep their size.  has_bearer: the host's mirror of the existence bytes, [n_cells][U][2]. */
-  double* d_qavg = nullptr;
-  int32_t *d_qpend = nullptr, *d_qdata = nullptr, *h_qin = nullptr, *z_qin = nullptr, *d_qin = nullptr;
-  uint8_t* d_qhas = nullptr;
+  /* Resident cells.  A cell is resident in one form at a time (GroupCellState: cells[cell] -- the form, whether the form's counters
+   * exist on top of it, and the host's mirror of the cell's clock: the clock check needs no read-back).  What the forms keep on the
+   * device lies in the stores of kGroupStores, one row per store, [n_cells][elements per cell] each: store[row] is the row's block,
+   * null until the first setter of its allocation family makes the whole family (group_alloc_family).
+   *   the cell family    rlast, rgather, ruid: a cell's last-update time, the gather rows of calls that name their users and the ids they
+   *                      were gathered by -- every form's
+   *   averages           ravg, rpend: [U] averages and pending bytes (rs_group_set_avg, rs_group_schedule_tti_at, rs_group_run_at)
+   *   bearers            qavg, qpend, qhas, qdata: [U][2] averages, pending bytes and existence bytes of the users' two bearers and a
+   *                      call's data words in call order (rs_group_set_bearers, rs_group_schedule_tti_queued); the flows form of
+   *                      scheduler 1 keeps its flows in them too (rs_group_set_flows, rs_group_schedule_tti_flows)
+   *   bearer counters    cbytes, crbs: [U][2] m_cumulateBytes / m_cumulateRBs beside the bearer stores (rs_group_set_counters,
+   *                      rs_group_schedule_tti_counted; a flow-resident cell always has them)
+   *   per-user counters  acbytes, acrbs: [U] m_cumulateBytes / m_cumulateRBs beside the averages (rs_group_set_avg_counters,
+   *                      rs_group_run_counted_at: the launch block's grp_cbytes / grp_crbs point at them in a counted run) */
+  void* store[kGroupNStores] = {};
+  std::vector<GroupCellState> cells;
+  /* The slots' rows that travel beside the slots, [n_cells][U][2] words each, so that the slots of the other calls keep their size
+   * (GroupStaged): qin -- a queued call's data words, a flows call's bearer words (one per position), made with the bearer stores;
+   * sent -- a counted call's sent rows, made with the bearer counters; sent2 -- the twin that the built-in kernel writes in a checked
+   * call of the counted pair, made by the first such call (the counter stores, and with them sent, may not exist yet when the pair is
+   * built).  has_bearer: the host's mirror of the existence bytes, [n_cells][U][2]. */
+  GroupStaged qin, sent, sent2;
   std::vector<uint8_t> has_bearer, empty_slot; /* empty_slot: per call slot, n_users == 0 (an update-only slot of a queued call) */
-  /* counted bearers (rs_group_set_counters, rs_group_schedule_tti_counted): per cell [U][2] m_cumulateBytes / m_cumulateRBs beside the
-   * bearer stores (allocated by the first rs_group_set_counters), and which cells are counted -- a state on top of resident[cell] == 2.
-   * The slots' sent rows come back in a pinned block of their own (h_sent: [n_cells][U][2], mapped: z_sent, else copied from d_sent),
-   * as the data words travel in h_qin.  h_sent2 / z_sent2 / d_sent2: the twin block the built-in kernel writes in a checked call of the
-   * counted pair, sized and mapped as the first (allocated by the first checked call: group_alloc_sent_twin). */
-  int64_t *d_cbytes = nullptr, *d_crbs = nullptr;
-  int32_t *h_sent = nullptr, *z_sent = nullptr, *d_sent = nullptr;
-  int32_t *h_sent2 = nullptr, *z_sent2 = nullptr, *d_sent2 = nullptr;
-  std::vector<uint8_t> counted;
-  /* counted runs (rs_group_set_avg_counters, rs_group_run_counted_at): per cell [U] m_cumulateBytes / m_cumulateRBs beside the resident
-   * averages, in stores of their own (allocated by the first rs_group_set_avg_counters; the launch block's grp_cbytes / grp_crbs point
-   * at them in a counted run), and which cells are avg-counted -- a state on top of resident[cell] == 1 */
-  int64_t *d_acbytes = nullptr, *d_acrbs = nullptr;
-  std::vector<uint8_t> avg_counted;
   /* grant records (rs_group_run_records_at): the slots' record blocks -- per slot T lists of `cap` records, then T count words, see
    * RsGroupCell::run_rec_cap -- in device memory (the kernel adds to the count words), and the pinned twin they are copied back to.
    * Both grow to the largest call so far, as the output blocks do. */
   uint8_t *d_recs = nullptr, *h_recs = nullptr;
   size_t recs_bytes = 0;
   double t_recs = 0; /* RS_DROPIN_TIMING: the share of t_unpack spent on sorting and copying records */
-  /* resident flows (rs_group_set_flows, rs_group_schedule_tti_flows; scheduler 1 alone): resident[cell] == 3.  The cell's flows live in
-   * the bearer stores and the counter stores above (a cell is resident in one form at a time), has_bearer mirrors their existence
-   * bytes, and the slots' bearer words (0 or 1 per call position) travel in h_qin, one word per position. */
   /* rs_group_kernel_name: the last call's form (a row of kGroupForms), whether a run-time build served it, the built-in kernels' names by row */
   int last_call_form = 0;
   bool last_call_jit = false;
-  char kname[RS_GROUP_FORMS][56] = {"", "", "", "", "", "", ""}, kname_jit[RS_GROUP_FORMS][40] = {"", "", "", "", "", "", ""};
+  char kname[RS_GROUP_FORMS][56] = {}, kname_jit[RS_GROUP_FORMS][40] = {};
 };
 
 extern "C" hipError_t rs_launch_group(const RsLaunch* p, int threads, int form, hipStream_t stream);
@@ -2528,25 +2590,29 @@ struct GroupForm {
   int store_width; /* the stores its self-check saves, restores and compares: 0 none, 1 the resident stores [U], 2 the bearer stores [U][2]
                     * (a form with RS_GROUP_SET_COUNTERS: the counter stores [U][2] too; with RS_GROUP_SET_SENT: the slots' sent rows are compared as well) */
   /* the nouns of the pair's messages: "specialised <adj>%s build", "both <adj>builds are dropped, <serves>", "agreed with <ref>",
-   * "copies of the <stores>" */
-  const char *adj, *serves, *ref, *stores;
+   * "copies of the <stores>", "scheduler %d <lacks>: nothing for <entry> to build" (null: every scheduler of a group has the form) */
+  const char *adj, *serves, *ref, *stores, *lacks, *entry;
   unsigned sets() const; /* the form's row of rs_group_form */
 };
 const GroupForm kGroupForms[RS_GROUP_FORMS] = {
-    {false, kGroupPlain, 0, "", "the built-in kernels serve this group", "the built-in kernel field by field", ""},
+    {false, kGroupPlain, 0, "", "the built-in kernels serve this group", "the built-in kernel field by field", "", nullptr, "rs_group_specialize"},
     {false, kGroupResident, 1, "resident ",
-     "the built-in resident kernel serves this group's resident calls", "the built-in resident kernel field by field, resident stores included", "resident stores"},
+     "the built-in resident kernel serves this group's resident calls", "the built-in resident kernel field by field, resident stores included", "resident stores",
+     nullptr, "rs_group_specialize_resident"},
     {true, kGroupQueued, 2, "queued ",
-     "the built-in queued kernel serves this group's queued calls", "the built-in queued kernel field by field, bearer stores included", "bearer stores"},
+     "the built-in queued kernel serves this group's queued calls", "the built-in queued kernel field by field, bearer stores included", "bearer stores",
+     "has no queued form (rs_group_set_bearers)", "rs_group_specialize_queued"},
     {true, kGroupFlows, 2, "flows ",
-     "the built-in flows kernel serves this group's flows calls", "the built-in flows kernel field by field, bearer stores and counters included", "bearer stores and counters"},
+     "the built-in flows kernel serves this group's flows calls", "the built-in flows kernel field by field, bearer stores and counters included", "bearer stores and counters",
+     "has no flows form (rs_group_set_flows)", "rs_group_specialize_flows"},
     {true, kGroupCounted, 2, "counted ",
      "the built-in counted kernel serves this group's counted calls", "the built-in counted kernel field by field, bearer stores, counters and sent rows included",
-     "bearer stores and counters"},
+     "bearer stores and counters", "has no counted form (rs_group_set_counters)", "rs_group_specialize_counted"},
     {false, kGroupRun, 1, "run ",
-     "the built-in run kernel serves this group's runs", "the built-in run kernel field by field over every TTI, resident stores included", "resident stores"},
+     "the built-in run kernel serves this group's runs", "the built-in run kernel field by field over every TTI, resident stores included", "resident stores",
+     "is not served by a run (rs_group_run_at)", "rs_group_specialize_run"},
     /* (the counted run: the run's launcher, no pair -- group_specialize_pair and group_jit_pair_status never see the row) */
-    {false, -1, 0, "counted run ", "", "", ""},
+    {false, -1, 0, "counted run ", "", "", "", nullptr, nullptr},
 };
 unsigned GroupForm::sets() const { return rs_group_form((int)(this - kGroupForms)).sets; }
 
@@ -2554,41 +2620,95 @@ unsigned GroupForm::sets() const { return rs_group_form((int)(this - kGroupForms
 size_t group_chk_sstate(const rs_group* g) { return round_up((int)(8 * (size_t)g->b->S * g->n_cells), 256); }
 size_t group_chk_half(const rs_group* g) { return group_chk_sstate(g) + round_up((int)(sizeof(RsCellScalars) * (size_t)g->n_cells), 256); }
 
-/* The stores that a form's self-check saves, restores and compares, in the order they lie in a half of GroupPair::d_stores_chk (each
- * rounded up to 256 bytes): the averages, the cells' last-update times, the pending bytes -- of every user id of the config (the update
- * touches them all), for the bearer stores of BOTH bearers. */
-enum GroupStoreKind { kStoreI32, kStoreF64, kStoreI64 }; /* every kind is compared bitwise; the kind is the element's size and how a message prints it */
-struct GroupStore {
-  void* dev;        /* [n_cells][elems] */
-  size_t elems;     /* per cell */
+/* The device stores of the resident forms, one row each, by GroupStoreId: [n_cells][elements per cell] of one element kind.  A family
+ * is allocated together, all or none, by the first setter that needs it (group_alloc_family); rs_group_destroy, the setters' and
+ * getters' row copies and the self-check (group_stores) all read a store's shape here. */
+enum GroupStoreKind { kStoreI32, kStoreF64, kStoreI64, kStoreU8 }; /* every kind is compared bitwise; the kind is the element's size and how a message prints it */
+enum GroupFamilyId { kFamCell, kFamAverages, kFamBearers, kFamCounters, kFamAvgCounters };
+struct GroupStoreRow {
+  const char* name;
   GroupStoreKind kind;
-  const char* name; /* in a message, followed by the element's index */
-  size_t size() const { return kind == kStoreI32 ? 4 : 8; }
-  size_t bytes(const rs_group* g) const { return size() * elems * (size_t)g->n_cells; }
+  int per_user;      /* elements per cell: per_user x U of the config (the update touches every user id, of the bearer stores BOTH bearers); 0: one */
+  int family;
+  bool zeroed;       /* by its allocation: read before a setter has written every cell's row */
+  const char* field; /* in a message of the self-check, followed by the element's index; null: never compared */
+  size_t size() const { return kind == kStoreI32 ? 4 : kind == kStoreU8 ? 1 : 8; }
+  size_t elems(const rs_group* g) const { return per_user ? (size_t)per_user * g->b->U : 1; }
+  size_t row_bytes(const rs_group* g) const { return size() * elems(g); }
+  size_t bytes(const rs_group* g) const { return row_bytes(g) * (size_t)g->n_cells; }
   size_t kept(const rs_group* g) const { return (size_t)round_up((int)bytes(g), 256); }
 };
+const GroupStoreRow kGroupStores[kGroupNStores] = {
+    {"ravg", kStoreF64, 1, kFamAverages, false, "avg"},         {"rpend", kStoreI32, 1, kFamAverages, false, "pending_bytes"},
+    {"rlast", kStoreF64, 0, kFamCell, false, "last_update"},    {"rgather", kStoreF64, 1, kFamCell, false, nullptr},
+    {"ruid", kStoreI32, 1, kFamCell, false, nullptr},           {"qavg", kStoreF64, 2, kFamBearers, false, "avg"},
+    {"qpend", kStoreI32, 2, kFamBearers, false, "pending_bytes"}, {"qdata", kStoreI32, 2, kFamBearers, false, nullptr},
+    {"qhas", kStoreU8, 2, kFamBearers, false, nullptr},         {"cbytes", kStoreI64, 2, kFamCounters, true, "cum_bytes"},
+    {"crbs", kStoreI64, 2, kFamCounters, true, "cum_rbs"},      {"acbytes", kStoreI64, 1, kFamAvgCounters, true, "cum_bytes"},
+    {"acrbs", kStoreI64, 1, kFamAvgCounters, true, "cum_rbs"},
+};
+/* a family: the family it stands on (made first, and left standing when this one fails), and the staged block of the slots' rows that
+ * is made with it -- mapped when the group's block on that side is: the group reads its slots in place, the data words too; its
+ * outputs are written in place, the sent rows too */
+struct GroupFamily {
+  int needs;
+  GroupStaged rs_group::*staged;
+  unsigned pin_flags;
+  bool out_side;
+};
+const GroupFamily kGroupFamilies[] = {
+    {-1, nullptr, 0, false},
+    {kFamCell, nullptr, 0, false},
+    {kFamCell, &rs_group::qin, hipHostMallocMapped, false},
+    {-1, &rs_group::sent, hipHostMallocMapped | hipHostMallocCoherent, true},
+    {-1, nullptr, 0, false},
+};
+/* the slots' staged rows: [n_cells][U][2] words */
+size_t group_staged_bytes(const rs_group* g) { return 8 * (size_t)g->b->U * (size_t)g->n_cells; }
+
+/* A family's stores and its staged block, all or none (true: they exist); the stores that are read before they are written start
+ * as zeros.  A failure leaves nothing of the family behind. */
+bool group_alloc_family(rs_group* g, int fam) {
+  const GroupFamily& f = kGroupFamilies[fam];
+  for (int i = 0; i < kGroupNStores; i++)
+    if (kGroupStores[i].family == fam && g->store[i]) return true;
+  bool ok = f.needs < 0 || group_alloc_family(g, f.needs);
+  for (int i = 0; i < kGroupNStores && ok; i++)
+    if (kGroupStores[i].family == fam) ok = hipMalloc(&g->store[i], kGroupStores[i].bytes(g)) == hipSuccess;
+  if (ok && f.staged) ok = (g->*f.staged).make(group_staged_bytes(g), f.pin_flags, (f.out_side ? g->z_out : g->z_in) != nullptr);
+  for (int i = 0; i < kGroupNStores && ok; i++)
+    if (kGroupStores[i].family == fam && kGroupStores[i].zeroed) ok = hipMemset(g->store[i], 0, kGroupStores[i].bytes(g)) == hipSuccess;
+  if (ok) return true;
+  (void)hipGetLastError();
+  for (int i = 0; i < kGroupNStores; i++)
+    if (kGroupStores[i].family == fam && g->store[i]) {
+      (void)hipFree(g->store[i]);
+      g->store[i] = nullptr;
+    }
+  if (f.staged) (g->*f.staged).release();
+  return false;
+}
+
+/* The stores that a form's self-check saves, restores and compares -- rows of kGroupStores, in the order they lie in a half of
+ * GroupPair::d_stores_chk (each rounded up to 256 bytes): the averages, the cells' last-update times, the pending bytes. */
 struct GroupStores {
-  GroupStore part[5];
+  const int* row;
   int n;       /* 0, 3, or 5: a form that keeps counters (RS_GROUP_SET_COUNTERS) has m_cumulateBytes / m_cumulateRBs behind the other three */
   size_t half; /* bytes of one half of the check block */
 };
 GroupStores group_stores(const rs_group* g, const GroupForm& f) {
-  if (!f.store_width) return {};
-  const bool two = f.store_width == 2;
-  const size_t e = (size_t)f.store_width * g->b->U;
-  GroupStores s = {{{two ? g->d_qavg : g->d_ravg, e, kStoreF64, "avg"}, {g->d_rlast, 1, kStoreF64, "last_update"},
-                    {two ? (void*)g->d_qpend : (void*)g->d_rpend, e, kStoreI32, "pending_bytes"},
-                    {g->d_cbytes, e, kStoreI64, "cum_bytes"}, {g->d_crbs, e, kStoreI64, "cum_rbs"}}, (f.sets() & RS_GROUP_SET_COUNTERS) ? 5 : 3, 0};
-  for (int i = 0; i < s.n; i++) s.half += s.part[i].kept(g);
+  static const int rows[3][5] = {{}, {kRavg, kRlast, kRpend}, {kQavg, kRlast, kQpend, kCbytes, kCrbs}}; /* by store_width */
+  GroupStores s = {rows[f.store_width], !f.store_width ? 0 : (f.sets() & RS_GROUP_SET_COUNTERS) ? 5 : 3, 0};
+  for (int i = 0; i < s.n; i++) s.half += kGroupStores[s.row[i]].kept(g);
   return s;
 }
 /* a form's stores to (save) or from one half of its pair's check block */
 hipError_t group_copy_stores(const rs_group* g, const GroupForm& f, int half, bool save) {
   const GroupStores s = group_stores(g, f);
   uint8_t* kept = s.n ? g->pair[f.pair].d_stores_chk + (size_t)half * s.half : nullptr;
-  for (int i = 0; i < s.n; kept += s.part[i++].kept(g)) {
-    const GroupStore& x = s.part[i];
-    const hipError_t e = hipMemcpyAsync(save ? (void*)kept : x.dev, save ? x.dev : (void*)kept, x.bytes(g), hipMemcpyDeviceToDevice, g->b->stream);
+  for (int i = 0; i < s.n; kept += kGroupStores[s.row[i++]].kept(g)) {
+    void* const dev = g->store[s.row[i]];
+    const hipError_t e = hipMemcpyAsync(save ? (void*)kept : dev, save ? dev : (void*)kept, kGroupStores[s.row[i]].bytes(g), hipMemcpyDeviceToDevice, g->b->stream);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
@@ -2670,11 +2790,7 @@ rs_group* rs_group_create(const rs_config* cfg, int32_t n_cells) {
     snprintf(g->kname_jit[row], sizeof g->kname_jit[0], "%s_jit", rs_group_form(row).stem);
   }
   g->empty_slot.assign(n_cells, 0);
-  g->resident.assign(n_cells, 0);
-  g->counted.assign(n_cells, 0);
-  g->avg_counted.assign(n_cells, 0);
-  g->pending_zero.assign(n_cells, 0);
-  g->last_update.assign(n_cells, 0.0);
+  g->cells.assign(n_cells, GroupCellState());
   g_err[0] = 0;
   return g;
 }
@@ -2688,14 +2804,14 @@ void rs_group_destroy(rs_group* g) {
   if (g->timing && g->n_calls && g->t_recs > 0)
     fprintf(stderr, "rs_group_run_records_at: of the unpack above, %.2f us per call sort and copy grant records\n", g->t_recs / g->n_calls);
   if (g->b && g->b->stream) (void)hipStreamSynchronize(g->b->stream);
-  for (void* q : {(void*)g->d_in, (void*)g->d_out, (void*)g->d_count, (void*)g->d_img, (void*)g->d_prb, (void*)g->d_out2, (void*)g->d_chk,
-                  (void*)g->pair[0].d_stores_chk, (void*)g->pair[1].d_stores_chk, (void*)g->pair[2].d_stores_chk, (void*)g->pair[3].d_stores_chk,
-                  (void*)g->pair[4].d_stores_chk, (void*)g->pair[5].d_stores_chk, (void*)g->d_sent2, (void*)g->d_ravg,
-                  (void*)g->d_rpend, (void*)g->d_rlast, (void*)g->d_rgather, (void*)g->d_ruid, (void*)g->d_qavg, (void*)g->d_qpend,
-                  (void*)g->d_qdata, (void*)g->d_qhas, (void*)g->d_qin, (void*)g->d_cbytes, (void*)g->d_crbs, (void*)g->d_sent, (void*)g->d_acbytes,
-                  (void*)g->d_acrbs, (void*)g->d_recs})
+  for (void* q : {(void*)g->d_in, (void*)g->d_out, (void*)g->d_count, (void*)g->d_img, (void*)g->d_prb, (void*)g->d_out2, (void*)g->d_chk, (void*)g->d_recs})
     if (q) (void)hipFree(q);
-  for (void* q : {(void*)g->h_qin, (void*)g->h_sent, (void*)g->h_sent2, (void*)g->h_in, (void*)g->h_out, (void*)g->h_recs})
+  for (const rs_group::GroupPair& p : g->pair)
+    if (p.d_stores_chk) (void)hipFree(p.d_stores_chk);
+  for (void* q : g->store) /* (the rows of kGroupStores) */
+    if (q) (void)hipFree(q);
+  for (GroupStaged* s : {&g->qin, &g->sent, &g->sent2}) s->release();
+  for (void* q : {(void*)g->h_in, (void*)g->h_out, (void*)g->h_recs})
     if (q) (void)hipHostFree(q);
   rs_batch_destroy(g->b);
   delete g;
@@ -2723,6 +2839,20 @@ constexpr double kResidentMinDt = 0x1p-20;
  * (1 + a0) + a1 exactly -- it does while that sum is below 2^53 -- and must stay inside the filter's range: rs_group_set_bearers refuses
  * a > 2^51, and the growth argument above carries over bearer by bearer (the same update, |rate| < 2^51): a <= 2^51 (1 + 2^-51)^k. */
 constexpr double kBearerAvgMax = 0x1p51;
+
+/* what a call, a setter or a getter needs a cell to be; its refusal reads "cell %d is not <unmet>" */
+struct CellNeed {
+  GroupCellState::Form form;
+  bool counters; /* the form's counters too */
+  const char* unmet;
+  bool met(const GroupCellState& s) const { return counters ? s.counted(form) : s.in(form); }
+};
+const CellNeed kNeedAverages = {GroupCellState::kAverages, false, "resident (rs_group_set_avg first)"},
+               kNeedAveragesForCounters = {GroupCellState::kAverages, false, "average-resident (rs_group_set_avg first)"},
+               kNeedAvgCounters = {GroupCellState::kAverages, true, "avg-counted (rs_group_set_avg_counters first)"},
+               kNeedBearers = {GroupCellState::kBearers, false, "bearer-resident (rs_group_set_bearers first)"},
+               kNeedCounters = {GroupCellState::kBearers, true, "counted (rs_group_set_counters first)"},
+               kNeedFlows = {GroupCellState::kFlows, false, "flow-resident (rs_group_set_flows first)"};
 
 /* One group call: what the caller gave, then what the phases of group_schedule decide along the way.  now != null: a resident form --
  * averages (rs_group_schedule_tti_at) or, with qdata, bearers (rs_group_schedule_tti_queued; counted: its twin,
@@ -2956,23 +3086,25 @@ int group_validate(rs_group* g, GroupCall& c) {
   for (int k = 0; k < n; k++) {
     const int cell = c.cell(k);
     if (in[k].avg_rate) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): avg_rate must be NULL: the cell's averages are resident on the device", k, cell);
-    if (flw && g->resident[cell] != 3) return fail(RS_ERR_STATE, "cell slot %d: cell %d is not flow-resident (rs_group_set_flows first)", k, cell);
-    if (!flw && g->resident[cell] == 3)
+    const GroupCellState& st = g->cells[cell];
+    auto unmet = [&](const CellNeed& need) { return fail(RS_ERR_STATE, "cell slot %d: cell %d is not %s", k, cell, need.unmet); };
+    if (flw && !kNeedFlows.met(st)) return unmet(kNeedFlows);
+    if (!flw && st.in(GroupCellState::kFlows))
       return fail(RS_ERR_STATE, "cell slot %d: cell %d is flow-resident (rs_group_set_flows): rs_group_schedule_tti_flows serves it, or rs_group_set_avg makes it average-resident", k, cell);
-    if (que && g->resident[cell] != 2) return fail(RS_ERR_STATE, "cell slot %d: cell %d is not bearer-resident (rs_group_set_bearers first)", k, cell);
-    if (c.counted && !g->counted[cell]) return fail(RS_ERR_STATE, "cell slot %d: cell %d is not counted (rs_group_set_counters first)", k, cell);
-    if (!que && g->resident[cell] == 2)
+    if (que && !kNeedBearers.met(st)) return unmet(kNeedBearers);
+    if (c.counted && !kNeedCounters.met(st)) return unmet(kNeedCounters);
+    if (!que && st.in(GroupCellState::kBearers))
       return fail(RS_ERR_STATE, "cell slot %d: cell %d is bearer-resident (rs_group_set_bearers): rs_group_schedule_tti_queued serves it, or rs_group_set_avg makes it average-resident", k, cell);
-    if (!g->resident[cell]) return fail(RS_ERR_STATE, "cell slot %d: cell %d is not resident (rs_group_set_avg first)", k, cell);
-    if (c.run_counted && !g->avg_counted[cell]) return fail(RS_ERR_STATE, "cell slot %d: cell %d is not avg-counted (rs_group_set_avg_counters first)", k, cell);
+    if (st.in(GroupCellState::kNone)) return unmet(kNeedAverages);
+    if (c.run_counted && !kNeedAvgCounters.met(st)) return unmet(kNeedAvgCounters);
     if (slots0 && in[k].n_users < 0) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): n_users %d is negative", k, cell, in[k].n_users);
     if (int rc = flw ? group_validate_flows_slot(g, c, k, cell) : RS_OK) return rc;
     if (que && in[k].n_users > 0 && !c.qdata[k]) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): data_to_transmit[%d] is NULL (only an update-only slot, n_users == 0, gives none)", k, cell, k);
-    const double last = g->last_update[cell];
+    const double last = st.last_update();
     const double now0 = c.now_first(k);
     if (!std::isfinite(now0)) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): now is not finite", k, cell);
     if (now0 < last) return fail(RS_ERR_INVALID, "cell slot %d (cell %d): now = %.17g lies before the cell's last update at %.17g", k, cell, now0, last);
-    if (now0 != last && !(now0 - last >= kResidentMinDt) && !g->pending_zero[cell])
+    if (now0 != last && !(now0 - last >= kResidentMinDt) && !st.pending_zero())
       return fail(RS_ERR_INVALID, "cell slot %d (cell %d): now - last_update = %.3g s is neither 0 nor at least %.3g s, and the cell may have bytes pending", k, cell, now0 - last, kResidentMinDt);
     /* (a run: behind its first TTI bytes may be pending whatever the cell's state was: every later step is 0 or at least the bound) */
     for (int t = 1; t < c.ttis(); t++) {
@@ -3049,7 +3181,7 @@ int group_pack_data_words(rs_group* g, const GroupCall& c, int k, int cell) {
     if (d[2 * i] == 0 && d[2 * i + 1] == 0)
       return fail(RS_ERR_INVALID, "cell slot %d (cell %d): user %d (call position %d) has no data in either bearer: the reference does not schedule such a user", k, cell, id, i);
   }
-  memcpy(g->h_qin + (size_t)k * 2 * (size_t)b->U, d, 8 * (size_t)in.n_users);
+  memcpy(g->qin.h + (size_t)k * 2 * (size_t)b->U, d, 8 * (size_t)in.n_users);
   return RS_OK;
 }
 
@@ -3086,7 +3218,7 @@ int group_pack_slots(rs_group* g, GroupCall& c) {
     c.exact_scan |= pk.exact_scan;
     if (c.form == kGroupQueued && (rc = group_pack_data_words(g, c, k, cell))) return rc;
     if (c.form == kGroupFlows) { /* the slot's bearer words, one per call position (checked by group_validate) */
-      int32_t* const w = g->h_qin + (size_t)k * 2 * (size_t)b->U;
+      int32_t* const w = g->qin.h + (size_t)k * 2 * (size_t)b->U;
       for (int i = 0; i < in[k].n_users; i++) w[i] = c.flow[k][i];
     }
     group_fill_header(g, c, k, &pk.l);
@@ -3118,7 +3250,7 @@ struct ImageGuard {
   ~ImageGuard() {
     if (!ok) for (int k = 0; k < c.n; k++) {
       g->img[c.cell(k)].valid = false;
-      if (c.resident()) g->resident[c.cell(k)] = g->counted[c.cell(k)] = g->avg_counted[c.cell(k)] = 0; /* (averages half updated, perhaps: resident again with rs_group_set_avg; neither resident nor counted) */
+      if (c.resident()) g->cells[c.cell(k)].leave(); /* (averages half updated, perhaps: resident again with rs_group_set_avg; neither resident nor counted) */
     }
   }
 };
@@ -3157,57 +3289,34 @@ void group_fill_launch(const rs_group* g, const GroupCall& c, RsLaunch* launch) 
   L.grp_out_stride = (int64_t)g->out_stride * c.ttis(); /* (a run: a slot's TTIs follow one another) */
   L.grp_count = g->d_count;
   if (sets & RS_GROUP_SET_CELL) {
-    L.grp_last = g->d_rlast;
-    L.grp_gather = g->d_rgather;
-    L.grp_uid = g->d_ruid;
+    L.grp_last = (double*)g->store[kRlast];
+    L.grp_gather = (double*)g->store[kRgather];
+    L.grp_uid = (int32_t*)g->store[kRuid];
   }
   if (sets & RS_GROUP_SET_AVERAGES) {
-    L.grp_avg = g->d_ravg;
-    L.grp_pending = g->d_rpend;
+    L.grp_avg = (double*)g->store[kRavg];
+    L.grp_pending = (int32_t*)g->store[kRpend];
   }
   if (sets & RS_GROUP_SET_BEARERS) {
-    L.grp_qavg = g->d_qavg;
-    L.grp_qpend = g->d_qpend;
-    L.grp_qhas = g->d_qhas;
-    L.grp_qin = g->z_qin ? g->z_qin : g->d_qin;
+    L.grp_qavg = (double*)g->store[kQavg];
+    L.grp_qpend = (int32_t*)g->store[kQpend];
+    L.grp_qhas = (uint8_t*)g->store[kQhas];
+    L.grp_qin = g->qin.dev();
     L.grp_qin_stride = 2 * (int64_t)b->U;
   }
-  if (sets & RS_GROUP_SET_DATA) L.grp_qdata = g->d_qdata;
+  if (sets & RS_GROUP_SET_DATA) L.grp_qdata = (int32_t*)g->store[kQdata];
   if (sets & RS_GROUP_SET_COUNTERS) { /* (a cell is resident in one form at a time: the bearers' [U][2] stores, or a counted run's [U] stores) */
-    L.grp_cbytes = c.run_counted ? g->d_acbytes : g->d_cbytes;
-    L.grp_crbs = c.run_counted ? g->d_acrbs : g->d_crbs;
+    L.grp_cbytes = (int64_t*)g->store[c.run_counted ? kAcbytes : kCbytes];
+    L.grp_crbs = (int64_t*)g->store[c.run_counted ? kAcrbs : kCrbs];
   }
   if (sets & RS_GROUP_SET_SENT) {
-    L.grp_sent = g->z_sent ? g->z_sent : g->d_sent;
+    L.grp_sent = g->sent.dev();
     L.grp_sent_stride = 2 * (int64_t)b->U;
   }
   if (c.recs) { /* (a counted run has no sent rows: the two words carry its record blocks, device memory, words per slot) */
     L.grp_sent = (int32_t*)g->d_recs;
     L.grp_sent_stride = (int64_t)(c.rec_stride() / 4);
   }
-}
-
-/* the twin of the counted calls' sent block for the built-in kernel of a checked call: pinned and mapped when the first is, else a
- * device block copied back; allocated by the first checked call of the counted pair (the counter stores, and with them h_sent, may not
- * exist yet when the pair is built) */
-bool group_alloc_sent_twin(rs_group* g) {
-  if (g->h_sent2) return true;
-  const size_t nb = 2 * (size_t)g->b->U * (size_t)g->n_cells;
-  bool ok = hipHostMalloc((void**)&g->h_sent2, 4 * nb, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
-  if (ok && g->z_sent) {
-    void* z = nullptr;
-    if (hipHostGetDevicePointer(&z, g->h_sent2, 0) == hipSuccess) g->z_sent2 = (int32_t*)z;
-  }
-  if (ok && !g->z_sent2) ok = hipMalloc(&g->d_sent2, 4 * nb) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
-    if (g->d_sent2) (void)hipFree(g->d_sent2);
-    if (g->h_sent2) (void)hipHostFree(g->h_sent2);
-    g->d_sent2 = g->h_sent2 = g->z_sent2 = nullptr;
-    return false;
-  }
-  memset(g->h_sent2, 0, 4 * nb);
-  return true;
 }
 
 /* A checked call -- one call, or one whole run --: the form's built-in kernel first, on the same slots and the same state, its outputs
@@ -3230,12 +3339,16 @@ int group_run_twin(rs_group* g, const GroupCall& c, const RsLaunch& L) {
   Lb.log_upper = c.want_upper ? (int32_t*)g->d_out2 : nullptr;
   Lb.done_flag = nullptr;
   if (f.sets() & RS_GROUP_SET_SENT) { /* (the sent rows are outputs too: the built-in kernel's go to the twin block, whatever the caller asked for) */
-    if (!group_alloc_sent_twin(g)) return fail(RS_ERR_HIP, "allocation of the self-check's twin sent block failed (%zu bytes)", 8 * (size_t)b->U * g->n_cells);
-    Lb.grp_sent = g->z_sent2 ? g->z_sent2 : g->d_sent2;
+    /* (pinned and mapped when the first block is, else a device block copied back; made by the first checked call) */
+    if (!g->sent2.h && !g->sent2.make(group_staged_bytes(g), hipHostMallocMapped | hipHostMallocCoherent, !g->sent.copied())) {
+      (void)hipGetLastError();
+      return fail(RS_ERR_HIP, "allocation of the self-check's twin sent block failed (%zu bytes)", group_staged_bytes(g));
+    }
+    Lb.grp_sent = g->sent2.dev();
   }
   HIP_TRY(rs_launch_group(&Lb, b->threads, c.row(), st));
   HIP_TRY(hipMemcpyAsync(g->h_out2.data(), g->d_out2, (size_t)c.n * c.ttis() * g->out_stride, hipMemcpyDeviceToHost, st)); /* (a run: slots x TTIs) */
-  if ((f.sets() & RS_GROUP_SET_SENT) && !g->z_sent2) HIP_TRY(hipMemcpyAsync(g->h_sent2, g->d_sent2, 8 * (size_t)c.n * b->U, hipMemcpyDeviceToHost, st));
+  if ((f.sets() & RS_GROUP_SET_SENT) && g->sent2.copied()) HIP_TRY(hipMemcpyAsync(g->sent2.h, g->sent2.d, 8 * (size_t)c.n * b->U, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(after, b->d_sstate, ss_all, hipMemcpyDeviceToDevice, st));
   HIP_TRY(hipMemcpyAsync(b->d_sstate, before, ss_all, hipMemcpyDeviceToDevice, st));
   HIP_TRY(hipMemcpyAsync(b->d_scal, before + group_chk_sstate(g), sc_all, hipMemcpyDeviceToDevice, st));
@@ -3257,7 +3370,7 @@ int group_run(rs_group* g, GroupCall& c, RsLaunch& L) {
   if (!c.zc) HIP_TRY(hipMemcpyAsync(g->d_in, g->h_in, (size_t)c.n * g->in_stride, hipMemcpyHostToDevice, st));
   if (!c.zc && c.run)
     HIP_TRY(hipMemcpyAsync(g->d_in + g->run_table_off, g->h_in + g->run_table_off, (size_t)c.n * RS_GROUP_MAX_RUN * RS_GROUP_RUN_ROW_BYTES, hipMemcpyHostToDevice, st));
-  if ((f.sets() & RS_GROUP_SET_BEARERS) && !g->z_qin) HIP_TRY(hipMemcpyAsync(g->d_qin, g->h_qin, 8 * (size_t)c.n * b->U, hipMemcpyHostToDevice, st));
+  if ((f.sets() & RS_GROUP_SET_BEARERS) && g->qin.copied()) HIP_TRY(hipMemcpyAsync(g->qin.d, g->qin.h, 8 * (size_t)c.n * b->U, hipMemcpyHostToDevice, st));
   c.poll = c.zc && g->poll && !c.recs; /* (records come back by a copy on the stream: the stream says when) */
   if (c.poll) {
     if (++g->seq == 0) g->seq = 1; /* (0 is the word's initial value) */
@@ -3283,7 +3396,7 @@ int group_run(rs_group* g, GroupCall& c, RsLaunch& L) {
   g->last_call_form = c.row();
   g->last_call_jit = c.kd != nullptr;
   if (!c.zc && !c.no_out) HIP_TRY(hipMemcpyAsync(g->h_out, g->d_out, (size_t)c.n * c.ttis() * g->out_stride, hipMemcpyDeviceToHost, st));
-  if ((f.sets() & RS_GROUP_SET_SENT) && !g->z_sent) HIP_TRY(hipMemcpyAsync(g->h_sent, g->d_sent, 8 * (size_t)c.n * b->U, hipMemcpyDeviceToHost, st));
+  if ((f.sets() & RS_GROUP_SET_SENT) && g->sent.copied()) HIP_TRY(hipMemcpyAsync(g->sent.h, g->sent.d, 8 * (size_t)c.n * b->U, hipMemcpyDeviceToHost, st));
   if (c.recs) HIP_TRY(hipMemcpyAsync(g->h_recs, g->d_recs, (size_t)c.n * c.rec_stride(), hipMemcpyDeviceToHost, st));
   return RS_OK;
 }
@@ -3307,28 +3420,29 @@ int group_compare_stores(const rs_group* g, const GroupCall& c, char* what, size
   if (!s.n) return RS_OK;
   std::vector<uint8_t> jit[5], ref[5];
   const uint8_t* kept = g->pair[f.pair].d_stores_chk + s.half;
-  for (int i = 0; i < s.n; kept += s.part[i++].kept(g)) {
-    const size_t bytes = s.part[i].bytes(g);
+  for (int i = 0; i < s.n; kept += kGroupStores[s.row[i++]].kept(g)) {
+    const size_t bytes = kGroupStores[s.row[i]].bytes(g);
     jit[i].resize(bytes);
     ref[i].resize(bytes);
-    HIP_TRY(hipMemcpy(jit[i].data(), s.part[i].dev, bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(jit[i].data(), g->store[s.row[i]], bytes, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(ref[i].data(), kept, bytes, hipMemcpyDeviceToHost));
   }
   for (int k = 0; k < c.n && !what[0]; k++) {
     const int cell = c.cell(k);
     for (const int i : {0, 2, 1, 3, 4}) {
       if (i >= s.n) continue;
-      const GroupStore& x = s.part[i];
-      for (size_t j = 0; j < x.elems && !what[0]; j++) {
-        const size_t at = ((size_t)cell * x.elems + j) * x.size();
+      const GroupStoreRow& x = kGroupStores[s.row[i]];
+      const size_t elems = x.elems(g);
+      for (size_t j = 0; j < elems && !what[0]; j++) {
+        const size_t at = ((size_t)cell * elems + j) * x.size();
         const void *a = jit[i].data() + at, *r = ref[i].data() + at;
         if (memcmp(a, r, x.size()) == 0) continue;
         char idx[48] = ""; /* (the element's index behind the store's name: "avg[3]", "avg[3][1]", "last_update") */
-        if (x.elems > 1 && f.store_width == 2) snprintf(idx, sizeof idx, "[%zu][%zu]", j / 2, j % 2);
-        else if (x.elems > 1) snprintf(idx, sizeof idx, "[%zu]", j);
-        if (x.kind == kStoreF64) snprintf(what, len, "cell %d: %s%s = %a, the built-in kernel's %a", cell, x.name, idx, *(const double*)a, *(const double*)r);
-        else if (x.kind == kStoreI64) snprintf(what, len, "cell %d: %s%s = %lld, the built-in kernel's %lld", cell, x.name, idx, (long long)*(const int64_t*)a, (long long)*(const int64_t*)r);
-        else snprintf(what, len, "cell %d: %s%s = %d, the built-in kernel's %d", cell, x.name, idx, *(const int32_t*)a, *(const int32_t*)r);
+        if (elems > 1 && f.store_width == 2) snprintf(idx, sizeof idx, "[%zu][%zu]", j / 2, j % 2);
+        else if (elems > 1) snprintf(idx, sizeof idx, "[%zu]", j);
+        if (x.kind == kStoreF64) snprintf(what, len, "cell %d: %s%s = %a, the built-in kernel's %a", cell, x.field, idx, *(const double*)a, *(const double*)r);
+        else if (x.kind == kStoreI64) snprintf(what, len, "cell %d: %s%s = %lld, the built-in kernel's %lld", cell, x.field, idx, (long long)*(const int64_t*)a, (long long)*(const int64_t*)r);
+        else snprintf(what, len, "cell %d: %s%s = %d, the built-in kernel's %d", cell, x.field, idx, *(const int32_t*)a, *(const int32_t*)r);
       }
     }
   }
@@ -3350,7 +3464,7 @@ int group_drop_pair(rs_group* g, const GroupCall& c, const char* what) {
   p.dropped = true;
   g->last_call_jit = false;
   memcpy(g->h_out, g->h_out2.data(), (size_t)c.n * c.ttis() * g->out_stride);
-  if (f.sets() & RS_GROUP_SET_SENT) memcpy(g->h_sent, g->h_sent2, 8 * (size_t)c.n * b->U); /* (the built-in kernel's sent rows: what group_unpack hands out) */
+  if (f.sets() & RS_GROUP_SET_SENT) memcpy(g->sent.h, g->sent2.h, 8 * (size_t)c.n * b->U); /* (the built-in kernel's sent rows: what group_unpack hands out) */
   HIP_TRY(hipMemcpy(b->d_sstate, g->d_chk + group_chk_half(g), 8 * (size_t)b->S * g->n_cells, hipMemcpyDeviceToDevice));
   if (f.store_width) {
     HIP_TRY(group_copy_stores(g, f, 1, false));
@@ -3385,7 +3499,7 @@ int group_check(rs_group* g, const GroupCall& c) {
     }
     /* (a counted call: the slot's sent rows, whether or not the caller wants them; an update-only slot has none) */
     if ((c.desc().sets() & RS_GROUP_SET_SENT) && !g->empty_slot[k]) {
-      const int32_t *a = g->h_sent + (size_t)k * 2 * (size_t)b->U, *r = g->h_sent2 + (size_t)k * 2 * (size_t)b->U;
+      const int32_t *a = g->sent.h + (size_t)k * 2 * (size_t)b->U, *r = g->sent2.h + (size_t)k * 2 * (size_t)b->U;
       for (int j = 0; j < 2 * c.in[k].n_users && !what[0]; j++)
         if (a[j] != r[j]) snprintf(what, sizeof what, "cell %d: sent[%d][%d] = %d, the built-in kernel's %d", cell, j / 2, j % 2, a[j], r[j]);
     }
@@ -3403,13 +3517,7 @@ int group_check(rs_group* g, const GroupCall& c) {
 /* the launch has completed: a resident call's updates are dated now[k], and grants may be waiting */
 void group_commit_clocks(rs_group* g, const GroupCall& c) {
   if (!c.resident()) return;
-  for (int k = 0; k < c.n; k++) {
-    const int cell = c.cell(k);
-    /* (an update-only slot credits nothing: behind an update no byte is waiting, without one nothing changed) */
-    if (!g->empty_slot[k]) g->pending_zero[cell] = 0;
-    else if (c.now_first(k) != g->last_update[cell]) g->pending_zero[cell] = 1;
-    g->last_update[cell] = c.now_last(k); /* (a run: its last TTI's clock -- a step of 0 repeats the value before it) */
-  }
+  for (int k = 0; k < c.n; k++) g->cells[c.cell(k)].served(!g->empty_slot[k], c.now_first(k), c.now_last(k));
 }
 
 /* ... and the device holds these calls' reports now: the cells' image records, the statistics */
@@ -3454,7 +3562,7 @@ void group_unpack(const rs_group* g, const GroupCall& c) {
     }
     unpack_tti(b, &c.in[k], &out, g->h_out + (size_t)k * g->out_stride, g->packs[k].l, c.want_upper, c.form == kGroupFlows ? c.flow[k] : nullptr);
     /* (a counted call: the slot's sent rows, [n_users][2] in call order, written by the threads that credited the positions) */
-    if (c.counted && c.sent && c.sent[k]) memcpy(c.sent[k], g->h_sent + (size_t)k * 2 * (size_t)b->U, 8 * (size_t)c.in[k].n_users);
+    if (c.counted && c.sent && c.sent[k]) memcpy(c.sent[k], g->sent.h + (size_t)k * 2 * (size_t)b->U, 8 * (size_t)c.in[k].n_users);
   }
 }
 
@@ -3587,150 +3695,145 @@ int group_schedule(rs_group* g, GroupCall c) {
 }  // namespace
 
 namespace {
-/* what the two resident forms share: the cells' last-update times, the gather rows and the id rows (all three or none) */
-bool group_alloc_resident_shared(rs_group* g) {
-  if (g->d_rlast) return true;
-  const size_t nu = (size_t)g->b->U * (size_t)g->n_cells;
-  if (hipMalloc(&g->d_rgather, 8 * nu) == hipSuccess && hipMalloc(&g->d_ruid, 4 * nu) == hipSuccess &&
-      hipMalloc(&g->d_rlast, 8 * (size_t)g->n_cells) == hipSuccess)
-    return true;
-  (void)hipGetLastError();
-  for (void* q : {(void*)g->d_rgather, (void*)g->d_ruid, (void*)g->d_rlast})
-    if (q) (void)hipFree(q);
-  g->d_rgather = g->d_rlast = nullptr;
-  g->d_ruid = nullptr;
-  return false;
+/* The shared pieces of the setters and getters of a cell's resident state (none of them is part of a TTI).  The prelude: the group,
+ * the cell, the state the call needs the cell in (null: any), then -- for a call with nothing to validate or allocate in between,
+ * else by group_cell_sync behind that -- the device and an idle stream, before any copy. */
+int group_cell_sync(rs_group* g) {
+  HIP_TRY(hipSetDevice(g->b->cfg.cell.device));
+  HIP_TRY(hipStreamSynchronize(g->b->stream));
+  return RS_OK;
+}
+int group_cell_prelude(rs_group* g, int32_t cell, const CellNeed* need, bool sync) {
+  if (!g) return fail(RS_ERR_INVALID, "null group");
+  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
+  if (need && !need->met(g->cells[cell])) return fail(RS_ERR_STATE, "cell %d is not %s", cell, need->unmet);
+  return sync ? group_cell_sync(g) : RS_OK;
 }
 
-/* the [n_cells][U][2] bearer stores of the queued form and of the flows form, the pinned block of the slots' words and the host's
- * mirror of the existence bytes (all or none; 25 bytes per bearer) */
-bool group_alloc_bearer_stores(rs_group* g) {
-  if (g->d_qavg) return true;
-  const size_t nb = 2 * (size_t)g->b->U * (size_t)g->n_cells;
-  bool ok = group_alloc_resident_shared(g) && hipMalloc(&g->d_qavg, 8 * nb) == hipSuccess && hipMalloc(&g->d_qpend, 4 * nb) == hipSuccess &&
-            hipMalloc(&g->d_qdata, 4 * nb) == hipSuccess && hipMalloc(&g->d_qhas, nb) == hipSuccess &&
-            hipHostMalloc((void**)&g->h_qin, 4 * nb, hipHostMallocMapped) == hipSuccess;
-  if (ok && g->z_in) { /* (the group reads its slots in place: the data words too) */
-    void* z = nullptr;
-    if (hipHostGetDevicePointer(&z, g->h_qin, 0) == hipSuccess) g->z_qin = (int32_t*)z;
-  }
-  if (ok && !g->z_qin) ok = hipMalloc(&g->d_qin, 4 * nb) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
-    for (void* q : {(void*)g->d_qavg, (void*)g->d_qpend, (void*)g->d_qdata, (void*)g->d_qhas, (void*)g->d_qin})
-      if (q) (void)hipFree(q);
-    if (g->h_qin) (void)hipHostFree(g->h_qin);
-    g->d_qavg = nullptr;
-    g->d_qpend = g->d_qdata = g->d_qin = g->h_qin = g->z_qin = nullptr;
-    g->d_qhas = nullptr;
-    return false;
-  }
-  memset(g->h_qin, 0, 4 * nb);
-  g->has_bearer.assign(nb, 0);
-  return true;
+/* row `cell` of a store of kGroupStores: put from the host (src == null: zeroed), or got (dst == null: not wanted) */
+int group_row_put(rs_group* g, int store, int cell, const void* src) {
+  const size_t n = kGroupStores[store].row_bytes(g);
+  uint8_t* const row = (uint8_t*)g->store[store] + (size_t)cell * n;
+  HIP_TRY(src ? hipMemcpy(row, src, n, hipMemcpyHostToDevice) : hipMemset(row, 0, n));
+  return RS_OK;
+}
+int group_row_get(const rs_group* g, int store, int cell, void* dst) {
+  const size_t n = kGroupStores[store].row_bytes(g);
+  if (dst) HIP_TRY(hipMemcpy(dst, (const uint8_t*)g->store[store] + (size_t)cell * n, n, hipMemcpyDeviceToHost));
+  return RS_OK;
 }
 
-/* the [n_cells][U][2] counter stores of the counted form and of the flows form, zeroed, and the pinned block of the counted calls'
- * sent rows (all or none; 20 bytes per bearer) */
-bool group_alloc_counter_stores(rs_group* g) {
-  if (g->d_cbytes) return true;
-  const size_t nb = 2 * (size_t)g->b->U * (size_t)g->n_cells;
-  bool ok = hipMalloc(&g->d_cbytes, 8 * nb) == hipSuccess && hipMalloc(&g->d_crbs, 8 * nb) == hipSuccess &&
-            hipHostMalloc((void**)&g->h_sent, 4 * nb, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
-  if (ok && g->z_out) { /* (the group's outputs are written in place: the sent rows too) */
-    void* z = nullptr;
-    if (hipHostGetDevicePointer(&z, g->h_sent, 0) == hipSuccess) g->z_sent = (int32_t*)z;
+/* a form's averages, pending bytes and the cell's last-update time; a pair of counter stores (the rbs store follows the bytes store) */
+int group_get_state(const rs_group* g, int cell, int avg_store, int pend_store, double* avg, int32_t* pending_bytes, double* last_update) {
+  int rc = group_row_get(g, avg_store, cell, avg);
+  if (!rc) rc = group_row_get(g, pend_store, cell, pending_bytes);
+  return rc ? rc : group_row_get(g, kRlast, cell, last_update);
+}
+int group_get_counters(const rs_group* g, int cell, int bytes_store, int64_t* cum_bytes, int64_t* cum_rbs) {
+  const int rc = group_row_get(g, bytes_store, cell, cum_bytes);
+  return rc ? rc : group_row_get(g, bytes_store + 1, cell, cum_rbs);
+}
+/* ... put: null gives zeros; with mask (the cell's existence bytes), a bearer that does not exist holds zeros */
+int group_put_counters(rs_group* g, int cell, int bytes_store, const int64_t* cum_bytes, const int64_t* cum_rbs, const uint8_t* mask = nullptr) {
+  const size_t n = kGroupStores[bytes_store].elems(g);
+  const int64_t* src[2] = {cum_bytes, cum_rbs};
+  for (int w = 0; w < 2; w++) {
+    std::vector<int64_t> masked;
+    if (src[w] && mask) {
+      masked.assign(src[w], src[w] + n);
+      for (size_t i = 0; i < n; i++)
+        if (!mask[i]) masked[i] = 0;
+      src[w] = masked.data();
+    }
+    if (const int rc = group_row_put(g, bytes_store + w, cell, src[w])) return rc;
   }
-  if (ok && !g->z_sent) ok = hipMalloc(&g->d_sent, 4 * nb) == hipSuccess;
-  if (ok) ok = hipMemset(g->d_cbytes, 0, 8 * nb) == hipSuccess && hipMemset(g->d_crbs, 0, 8 * nb) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
-    for (void* q : {(void*)g->d_cbytes, (void*)g->d_crbs, (void*)g->d_sent})
-      if (q) (void)hipFree(q);
-    if (g->h_sent) (void)hipHostFree(g->h_sent);
-    g->d_cbytes = g->d_crbs = nullptr;
-    g->d_sent = g->h_sent = g->z_sent = nullptr;
-    return false;
+  return RS_OK;
+}
+/* element i of a setter's two counter arrays, [U] or [U][2] */
+int group_check_counter(const int64_t* cum_bytes, const int64_t* cum_rbs, size_t i, bool two) {
+  const int64_t* const v[2] = {cum_bytes, cum_rbs};
+  for (int w = 0; w < 2; w++) {
+    if (!v[w] || v[w][i] >= 0) continue;
+    char idx[48];
+    if (two) snprintf(idx, sizeof idx, "[%zu][%zu]", i / 2, i % 2);
+    else snprintf(idx, sizeof idx, "[%zu]", i);
+    return fail(RS_ERR_INVALID, "%s%s = %lld is negative", w ? "cum_rbs" : "cum_bytes", idx, (long long)v[w][i]);
   }
-  memset(g->h_sent, 0, 4 * nb);
-  return true;
+  return RS_OK;
+}
+/* bearer i of [U][2]: where it exists its average lies in 1..2^51 (false for NaN) */
+int group_check_bearer_avg(const uint8_t* has_bearer, const double* avg, size_t i, const char* keeps) {
+  if (!has_bearer[i] || (avg[i] >= 1 && avg[i] <= kBearerAvgMax)) return RS_OK;
+  return fail(RS_ERR_INVALID, "avg[%zu][%zu] = %g outside 1..2^51 (an updated average is never below 1; the bound above keeps %s)", i / 2, i % 2, avg[i], keeps);
+}
+/* the bearer step of rs_group_set_bearers and rs_group_set_flows: the cell's row of the bearer stores and of the host's mirror.  A
+ * bearer that does not exist holds zeros: the getter reports them, the kernel neither reads nor writes them. */
+int group_put_bearers(rs_group* g, int cell, const uint8_t* has_bearer, const double* avg, double last_update) {
+  const size_t n = 2 * (size_t)g->b->U;
+  std::vector<double> a(n);
+  std::vector<uint8_t> has(n);
+  for (size_t i = 0; i < n; i++) {
+    has[i] = has_bearer[i] ? 1 : 0;
+    a[i] = has[i] ? avg[i] : 0.0;
+  }
+  int rc = group_row_put(g, kQavg, cell, a.data());
+  if (!rc) rc = group_row_put(g, kQpend, cell, nullptr);
+  if (!rc) rc = group_row_put(g, kQhas, cell, has.data());
+  if (!rc) rc = group_row_put(g, kRlast, cell, &last_update);
+  if (rc) return rc;
+  if (g->has_bearer.empty()) g->has_bearer.assign(n * (size_t)g->n_cells, 0);
+  memcpy(g->has_bearer.data() + (size_t)cell * n, has.data(), n);
+  return RS_OK;
 }
 }  // namespace
 
 int rs_group_set_avg(rs_group* g, int32_t cell, const double* avg, double last_update) {
   if (!g || !avg) return fail(RS_ERR_INVALID, "null argument");
-  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
-  rs_batch* b = g->b;
-  const size_t U = (size_t)b->U;
+  int rc = group_cell_prelude(g, cell, nullptr, false);
+  if (rc) return rc;
+  const size_t U = (size_t)g->b->U, nu = U * (size_t)g->n_cells;
   if (!std::isfinite(last_update)) return fail(RS_ERR_INVALID, "last_update is not finite");
   for (size_t u = 0; u < U; u++)
     if (!(avg[u] >= 1 && avg[u] <= kResidentAvgMax)) /* (false for NaN) */
       return fail(RS_ERR_INVALID, "avg[%zu] = %g outside 1..2^52 (an updated average is never below 1; the bound above keeps the FP32 filter's range)", u, avg[u]);
-  HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  if (!g->d_ravg) {
-    const size_t nu = U * (size_t)g->n_cells;
-    const bool ok = group_alloc_resident_shared(g) && hipMalloc(&g->d_ravg, 8 * nu) == hipSuccess && hipMalloc(&g->d_rpend, 4 * nu) == hipSuccess;
-    if (!ok) {
-      (void)hipGetLastError();
-      for (void* q : {(void*)g->d_ravg, (void*)g->d_rpend})
-        if (q) (void)hipFree(q);
-      g->d_ravg = nullptr;
-      g->d_rpend = nullptr;
-      return fail(RS_ERR_HIP, "allocation of the group's resident averages failed (%zu bytes)", 24 * nu + 8 * (size_t)g->n_cells);
-    }
-  }
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  g->counted[cell] = 0; /* (the cell leaves the bearer form: its counters' term ends) */
-  const uint8_t keep_counted = g->avg_counted[cell]; /* (an avg-counted cell keeps the state and its counters, as a counted cell does under rs_group_set_bearers) */
-  g->avg_counted[cell] = 0;
-  g->resident[cell] = 0; /* (until all three copies are through) */
-  HIP_TRY(hipMemcpy(g->d_ravg + (size_t)cell * U, avg, 8 * U, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(g->d_rpend + (size_t)cell * U, 0, 4 * U));
-  HIP_TRY(hipMemcpy(g->d_rlast + cell, &last_update, 8, hipMemcpyHostToDevice));
-  g->resident[cell] = 1;
-  g->avg_counted[cell] = keep_counted;
-  g->pending_zero[cell] = 1;
-  g->last_update[cell] = last_update;
+  if ((rc = group_cell_sync(g))) return rc;
+  if (!group_alloc_family(g, kFamAverages))
+    return fail(RS_ERR_HIP, "allocation of the group's resident averages failed (%zu bytes)", 24 * nu + 8 * (size_t)g->n_cells);
+  GroupCellState& st = g->cells[cell];
+  /* (an avg-counted cell keeps the state and its counters, as a counted cell does under rs_group_set_bearers; a cell that leaves the
+   * bearer form ends its counters' term) */
+  const bool keep = st.leave_for(GroupCellState::kAverages);
+  if ((rc = group_row_put(g, kRavg, cell, avg)) || (rc = group_row_put(g, kRpend, cell, nullptr)) || (rc = group_row_put(g, kRlast, cell, &last_update))) return rc;
+  st.enter(GroupCellState::kAverages, keep, last_update);
   return RS_OK;
 }
 
 int rs_group_get_avg(rs_group* g, int32_t cell, double* avg, int32_t* pending_bytes, double* last_update) {
-  if (!g) return fail(RS_ERR_INVALID, "null group");
-  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
-  if (g->resident[cell] != 1) return fail(RS_ERR_STATE, "cell %d is not resident (rs_group_set_avg first)", cell);
-  rs_batch* b = g->b;
-  const size_t U = (size_t)b->U;
-  HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  if (avg) HIP_TRY(hipMemcpy(avg, g->d_ravg + (size_t)cell * U, 8 * U, hipMemcpyDeviceToHost));
-  if (pending_bytes) HIP_TRY(hipMemcpy(pending_bytes, g->d_rpend + (size_t)cell * U, 4 * U, hipMemcpyDeviceToHost));
-  if (last_update) HIP_TRY(hipMemcpy(last_update, g->d_rlast + cell, 8, hipMemcpyDeviceToHost));
-  return RS_OK;
+  const int rc = group_cell_prelude(g, cell, &kNeedAverages, true);
+  return rc ? rc : group_get_state(g, cell, kRavg, kRpend, avg, pending_bytes, last_update);
 }
 
 int rs_group_set_pending(rs_group* g, int32_t cell, const int32_t* pending_bytes) {
   if (!g || !pending_bytes) return fail(RS_ERR_INVALID, "null argument");
-  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
-  if (g->resident[cell] != 1) return fail(RS_ERR_STATE, "cell %d is not resident (rs_group_set_avg first)", cell);
-  rs_batch* b = g->b;
-  const size_t U = (size_t)b->U;
+  int rc = group_cell_prelude(g, cell, &kNeedAverages, false);
+  if (rc) return rc;
   bool all_zero = true;
-  for (size_t u = 0; u < U; u++) {
+  for (size_t u = 0; u < (size_t)g->b->U; u++) {
     if (pending_bytes[u] < 0 || pending_bytes[u] >= (1 << 28)) /* (times 8 it stays an int32) */
       return fail(RS_ERR_INVALID, "pending_bytes[%zu] = %d outside 0..2^28-1", u, pending_bytes[u]);
     all_zero &= pending_bytes[u] == 0;
   }
-  HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  g->pending_zero[cell] = 0; /* (until the copy is through) */
-  HIP_TRY(hipMemcpy(g->d_rpend + (size_t)cell * U, pending_bytes, 4 * U, hipMemcpyHostToDevice));
-  g->pending_zero[cell] = all_zero ? 1 : 0;
+  if ((rc = group_cell_sync(g))) return rc;
+  g->cells[cell].set_pending_zero(false); /* (until the copy is through) */
+  if ((rc = group_row_put(g, kRpend, cell, pending_bytes))) return rc;
+  g->cells[cell].set_pending_zero(all_zero);
   return RS_OK;
 }
 
 int rs_group_set_bearers(rs_group* g, int32_t cell, const uint8_t* has_bearer, const double* avg, double last_update) {
   if (!g || !has_bearer || !avg) return fail(RS_ERR_INVALID, "null argument");
-  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
+  int rc = group_cell_prelude(g, cell, nullptr, false);
+  if (rc) return rc;
   rs_batch* b = g->b;
   const size_t U = (size_t)b->U, nb = 2 * U * (size_t)g->n_cells;
   if (b->sched == RS_SCHED_PF)
@@ -3741,129 +3844,65 @@ int rs_group_set_bearers(rs_group* g, int32_t cell, const uint8_t* has_bearer, c
     return fail(RS_ERR_INVALID, "resident bearers need exponents in {0, 1}: the general exponents' pow() of the averages is taken on the host per call");
   if (!std::isfinite(last_update)) return fail(RS_ERR_INVALID, "last_update is not finite");
   for (size_t i = 0; i < 2 * U; i++)
-    if (has_bearer[i] && !(avg[i] >= 1 && avg[i] <= kBearerAvgMax)) /* (false for NaN) */
-      return fail(RS_ERR_INVALID, "avg[%zu][%zu] = %g outside 1..2^51 (an updated average is never below 1; the bound above keeps the sum of a user's two exact and inside the FP32 filter's range)", i / 2, i % 2, avg[i]);
-  HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  if (!group_alloc_bearer_stores(g)) return fail(RS_ERR_HIP, "allocation of the group's resident bearers failed (%zu bytes)", 25 * nb);
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  g->resident[cell] = 0; /* (until all four copies are through) */
-  g->avg_counted[cell] = 0; /* (the cell leaves the average form: its per-user counters' term ends) */
-  /* a bearer that does not exist holds zeros: rs_group_get_bearers reports them, the kernel neither reads nor writes them */
-  std::vector<double> a(2 * U);
-  std::vector<uint8_t> has(2 * U);
-  for (size_t i = 0; i < 2 * U; i++) {
-    has[i] = has_bearer[i] ? 1 : 0;
-    a[i] = has[i] ? avg[i] : 0.0;
-  }
-  HIP_TRY(hipMemcpy(g->d_qavg + (size_t)cell * 2 * U, a.data(), 16 * U, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(g->d_qpend + (size_t)cell * 2 * U, 0, 8 * U));
-  HIP_TRY(hipMemcpy(g->d_qhas + (size_t)cell * 2 * U, has.data(), 2 * U, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(g->d_rlast + cell, &last_update, 8, hipMemcpyHostToDevice));
-  memcpy(g->has_bearer.data() + (size_t)cell * 2 * U, has.data(), 2 * U);
-  g->resident[cell] = 2;
-  g->pending_zero[cell] = 1;
-  g->last_update[cell] = last_update;
+    if ((rc = group_check_bearer_avg(has_bearer, avg, i, "the sum of a user's two exact and inside the FP32 filter's range"))) return rc;
+  if ((rc = group_cell_sync(g))) return rc;
+  if (!group_alloc_family(g, kFamBearers)) return fail(RS_ERR_HIP, "allocation of the group's resident bearers failed (%zu bytes)", 25 * nb);
+  GroupCellState& st = g->cells[cell];
+  const bool keep = st.leave_for(GroupCellState::kBearers); /* (a cell that leaves the average form ends its per-user counters' term) */
+  if ((rc = group_put_bearers(g, cell, has_bearer, avg, last_update))) return rc;
+  st.enter(GroupCellState::kBearers, keep, last_update);
   return RS_OK;
 }
 
 int rs_group_get_bearers(rs_group* g, int32_t cell, double* avg, int32_t* pending_bytes, double* last_update) {
-  if (!g) return fail(RS_ERR_INVALID, "null group");
-  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
-  if (g->resident[cell] != 2) return fail(RS_ERR_STATE, "cell %d is not bearer-resident (rs_group_set_bearers first)", cell);
-  rs_batch* b = g->b;
-  const size_t U = (size_t)b->U;
-  HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  if (avg) HIP_TRY(hipMemcpy(avg, g->d_qavg + (size_t)cell * 2 * U, 16 * U, hipMemcpyDeviceToHost));
-  if (pending_bytes) HIP_TRY(hipMemcpy(pending_bytes, g->d_qpend + (size_t)cell * 2 * U, 8 * U, hipMemcpyDeviceToHost));
-  if (last_update) HIP_TRY(hipMemcpy(last_update, g->d_rlast + cell, 8, hipMemcpyDeviceToHost));
-  return RS_OK;
+  const int rc = group_cell_prelude(g, cell, &kNeedBearers, true);
+  return rc ? rc : group_get_state(g, cell, kQavg, kQpend, avg, pending_bytes, last_update);
 }
 
-int rs_group_set_counters(rs_group* g, int32_t cell, const int64_t* cum_bytes, const int64_t* cum_rbs) {
-  if (!g) return fail(RS_ERR_INVALID, "null group");
-  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
-  if (g->resident[cell] != 2) return fail(RS_ERR_STATE, "cell %d is not bearer-resident (rs_group_set_bearers first)", cell);
-  rs_batch* b = g->b;
-  const size_t U = (size_t)b->U, nb = 2 * U * (size_t)g->n_cells;
-  for (size_t i = 0; i < 2 * U; i++) {
-    if (cum_bytes && cum_bytes[i] < 0) return fail(RS_ERR_INVALID, "cum_bytes[%zu][%zu] = %lld is negative", i / 2, i % 2, (long long)cum_bytes[i]);
-    if (cum_rbs && cum_rbs[i] < 0) return fail(RS_ERR_INVALID, "cum_rbs[%zu][%zu] = %lld is negative", i / 2, i % 2, (long long)cum_rbs[i]);
-  }
-  HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  if (!group_alloc_counter_stores(g)) return fail(RS_ERR_HIP, "allocation of the group's bearer counters failed (%zu bytes)", 20 * nb);
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  g->counted[cell] = 0; /* (until both copies are through) */
-  if (cum_bytes) HIP_TRY(hipMemcpy(g->d_cbytes + (size_t)cell * 2 * U, cum_bytes, 16 * U, hipMemcpyHostToDevice));
-  else HIP_TRY(hipMemset(g->d_cbytes + (size_t)cell * 2 * U, 0, 16 * U));
-  if (cum_rbs) HIP_TRY(hipMemcpy(g->d_crbs + (size_t)cell * 2 * U, cum_rbs, 16 * U, hipMemcpyHostToDevice));
-  else HIP_TRY(hipMemset(g->d_crbs + (size_t)cell * 2 * U, 0, 16 * U));
-  g->counted[cell] = 1;
+namespace {
+/* rs_group_set_counters and rs_group_set_avg_counters: the counters of the form the cell is in, [U][2] or [U] */
+int group_set_form_counters(rs_group* g, int32_t cell, const CellNeed& need, int family, int bytes_store, const int64_t* cum_bytes, const int64_t* cum_rbs,
+                            const char* alloc_failed, size_t bytes_per_user) {
+  int rc = group_cell_prelude(g, cell, &need, false);
+  if (rc) return rc;
+  const GroupStoreRow& row = kGroupStores[bytes_store];
+  for (size_t i = 0; i < row.elems(g); i++)
+    if ((rc = group_check_counter(cum_bytes, cum_rbs, i, row.per_user == 2))) return rc;
+  if ((rc = group_cell_sync(g))) return rc;
+  if (!group_alloc_family(g, family)) return fail(RS_ERR_HIP, alloc_failed, bytes_per_user * (size_t)g->b->U * (size_t)g->n_cells);
+  g->cells[cell].end_counters(); /* (until both copies are through) */
+  if ((rc = group_put_counters(g, cell, bytes_store, cum_bytes, cum_rbs))) return rc;
+  g->cells[cell].start_counters();
   return RS_OK;
+}
+}  // namespace
+
+int rs_group_set_counters(rs_group* g, int32_t cell, const int64_t* cum_bytes, const int64_t* cum_rbs) {
+  return group_set_form_counters(g, cell, kNeedBearers, kFamCounters, kCbytes, cum_bytes, cum_rbs,
+                                 "allocation of the group's bearer counters failed (%zu bytes)", 40);
 }
 
 int rs_group_get_counters(rs_group* g, int32_t cell, int64_t* cum_bytes, int64_t* cum_rbs) {
-  if (!g) return fail(RS_ERR_INVALID, "null group");
-  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
-  if (!g->counted[cell]) return fail(RS_ERR_STATE, "cell %d is not counted (rs_group_set_counters first)", cell);
-  rs_batch* b = g->b;
-  const size_t U = (size_t)b->U;
-  HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  if (cum_bytes) HIP_TRY(hipMemcpy(cum_bytes, g->d_cbytes + (size_t)cell * 2 * U, 16 * U, hipMemcpyDeviceToHost));
-  if (cum_rbs) HIP_TRY(hipMemcpy(cum_rbs, g->d_crbs + (size_t)cell * 2 * U, 16 * U, hipMemcpyDeviceToHost));
-  return RS_OK;
+  const int rc = group_cell_prelude(g, cell, &kNeedCounters, true);
+  return rc ? rc : group_get_counters(g, cell, kCbytes, cum_bytes, cum_rbs);
 }
 
 int rs_group_set_avg_counters(rs_group* g, int32_t cell, const int64_t* cum_bytes, const int64_t* cum_rbs) {
-  if (!g) return fail(RS_ERR_INVALID, "null group");
-  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
-  if (g->resident[cell] != 1) return fail(RS_ERR_STATE, "cell %d is not average-resident (rs_group_set_avg first)", cell);
-  rs_batch* b = g->b;
-  const size_t U = (size_t)b->U, nu = U * (size_t)g->n_cells;
-  for (size_t u = 0; u < U; u++) {
-    if (cum_bytes && cum_bytes[u] < 0) return fail(RS_ERR_INVALID, "cum_bytes[%zu] = %lld is negative", u, (long long)cum_bytes[u]);
-    if (cum_rbs && cum_rbs[u] < 0) return fail(RS_ERR_INVALID, "cum_rbs[%zu] = %lld is negative", u, (long long)cum_rbs[u]);
-  }
-  HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  if (!g->d_acbytes) { /* (both stores or none, zeroed: a cell's counters are read only once it is avg-counted) */
-    const bool ok = hipMalloc(&g->d_acbytes, 8 * nu) == hipSuccess && hipMalloc(&g->d_acrbs, 8 * nu) == hipSuccess &&
-                    hipMemset(g->d_acbytes, 0, 8 * nu) == hipSuccess && hipMemset(g->d_acrbs, 0, 8 * nu) == hipSuccess;
-    if (!ok) {
-      (void)hipGetLastError();
-      for (void* q : {(void*)g->d_acbytes, (void*)g->d_acrbs})
-        if (q) (void)hipFree(q);
-      g->d_acbytes = g->d_acrbs = nullptr;
-      return fail(RS_ERR_HIP, "allocation of the group's per-user counters failed (%zu bytes)", 16 * nu);
-    }
-  }
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  g->avg_counted[cell] = 0; /* (until both copies are through) */
-  if (cum_bytes) HIP_TRY(hipMemcpy(g->d_acbytes + (size_t)cell * U, cum_bytes, 8 * U, hipMemcpyHostToDevice));
-  else HIP_TRY(hipMemset(g->d_acbytes + (size_t)cell * U, 0, 8 * U));
-  if (cum_rbs) HIP_TRY(hipMemcpy(g->d_acrbs + (size_t)cell * U, cum_rbs, 8 * U, hipMemcpyHostToDevice));
-  else HIP_TRY(hipMemset(g->d_acrbs + (size_t)cell * U, 0, 8 * U));
-  g->avg_counted[cell] = 1;
-  return RS_OK;
+  return group_set_form_counters(g, cell, kNeedAveragesForCounters, kFamAvgCounters, kAcbytes, cum_bytes, cum_rbs,
+                                 "allocation of the group's per-user counters failed (%zu bytes)", 16);
 }
 
 int rs_group_get_avg_counters(rs_group* g, int32_t cell, int64_t* cum_bytes, int64_t* cum_rbs) {
-  if (!g) return fail(RS_ERR_INVALID, "null group");
-  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
-  if (!g->avg_counted[cell]) return fail(RS_ERR_STATE, "cell %d is not avg-counted (rs_group_set_avg_counters first)", cell);
-  rs_batch* b = g->b;
-  const size_t U = (size_t)b->U;
-  HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  if (cum_bytes) HIP_TRY(hipMemcpy(cum_bytes, g->d_acbytes + (size_t)cell * U, 8 * U, hipMemcpyDeviceToHost));
-  if (cum_rbs) HIP_TRY(hipMemcpy(cum_rbs, g->d_acrbs + (size_t)cell * U, 8 * U, hipMemcpyDeviceToHost));
-  return RS_OK;
+  const int rc = group_cell_prelude(g, cell, &kNeedAvgCounters, true);
+  return rc ? rc : group_get_counters(g, cell, kAcbytes, cum_bytes, cum_rbs);
 }
 
+/* the bearer step (rs_group_set_bearers') plus the counter step (rs_group_set_counters'), the counters masked as the averages are */
 int rs_group_set_flows(rs_group* g, int32_t cell, const uint8_t* has_bearer, const double* avg, double last_update, const int64_t* cum_bytes,
                        const int64_t* cum_rbs) {
   if (!g || !has_bearer || !avg) return fail(RS_ERR_INVALID, "null argument");
-  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
+  int rc = group_cell_prelude(g, cell, nullptr, false);
+  if (rc) return rc;
   rs_batch* b = g->b;
   const size_t U = (size_t)b->U, nb = 2 * U * (size_t)g->n_cells;
   if (b->sched != RS_SCHED_PF)
@@ -3871,74 +3910,35 @@ int rs_group_set_flows(rs_group* g, int32_t cell, const uint8_t* has_bearer, con
   if (b->gen_exp)
     return fail(RS_ERR_INVALID, "resident flows need exponents in {0, 1}: the general exponents' pow() of the averages is taken on the host per call");
   if (!std::isfinite(last_update)) return fail(RS_ERR_INVALID, "last_update is not finite");
-  for (size_t i = 0; i < 2 * U; i++) {
-    if (has_bearer[i] && !(avg[i] >= 1 && avg[i] <= kBearerAvgMax)) /* (false for NaN) */
-      return fail(RS_ERR_INVALID, "avg[%zu][%zu] = %g outside 1..2^51 (an updated average is never below 1; the bound above keeps the FP32 filter's range)", i / 2, i % 2, avg[i]);
-    if (cum_bytes && cum_bytes[i] < 0) return fail(RS_ERR_INVALID, "cum_bytes[%zu][%zu] = %lld is negative", i / 2, i % 2, (long long)cum_bytes[i]);
-    if (cum_rbs && cum_rbs[i] < 0) return fail(RS_ERR_INVALID, "cum_rbs[%zu][%zu] = %lld is negative", i / 2, i % 2, (long long)cum_rbs[i]);
-  }
-  HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  if (!group_alloc_bearer_stores(g) || !group_alloc_counter_stores(g))
+  for (size_t i = 0; i < 2 * U; i++)
+    if ((rc = group_check_bearer_avg(has_bearer, avg, i, "the FP32 filter's range")) || (rc = group_check_counter(cum_bytes, cum_rbs, i, true))) return rc;
+  if ((rc = group_cell_sync(g))) return rc;
+  if (!group_alloc_family(g, kFamBearers) || !group_alloc_family(g, kFamCounters))
     return fail(RS_ERR_HIP, "allocation of the group's resident flows failed (%zu bytes)", 45 * nb);
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  g->counted[cell] = 0;
-  g->avg_counted[cell] = 0;
-  g->resident[cell] = 0; /* (until all six copies are through) */
-  /* a bearer that does not exist holds zeros: rs_group_get_flows reports them, the kernel neither reads nor writes them */
-  std::vector<double> a(2 * U);
-  std::vector<uint8_t> has(2 * U);
-  for (size_t i = 0; i < 2 * U; i++) {
-    has[i] = has_bearer[i] ? 1 : 0;
-    a[i] = has[i] ? avg[i] : 0.0;
-  }
-  HIP_TRY(hipMemcpy(g->d_qavg + (size_t)cell * 2 * U, a.data(), 16 * U, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(g->d_qpend + (size_t)cell * 2 * U, 0, 8 * U));
-  HIP_TRY(hipMemcpy(g->d_qhas + (size_t)cell * 2 * U, has.data(), 2 * U, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(g->d_rlast + cell, &last_update, 8, hipMemcpyHostToDevice));
-  std::vector<int64_t> cb(2 * U, 0), cr(2 * U, 0);
-  for (size_t i = 0; i < 2 * U; i++) {
-    if (cum_bytes && has[i]) cb[i] = cum_bytes[i];
-    if (cum_rbs && has[i]) cr[i] = cum_rbs[i];
-  }
-  HIP_TRY(hipMemcpy(g->d_cbytes + (size_t)cell * 2 * U, cb.data(), 16 * U, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(g->d_crbs + (size_t)cell * 2 * U, cr.data(), 16 * U, hipMemcpyHostToDevice));
-  memcpy(g->has_bearer.data() + (size_t)cell * 2 * U, has.data(), 2 * U);
-  g->resident[cell] = 3;
-  g->pending_zero[cell] = 1;
-  g->last_update[cell] = last_update;
+  GroupCellState& st = g->cells[cell];
+  st.leave_for(GroupCellState::kFlows); /* (whatever form the cell leaves, its counters' term ends) */
+  if ((rc = group_put_bearers(g, cell, has_bearer, avg, last_update))) return rc;
+  if ((rc = group_put_counters(g, cell, kCbytes, cum_bytes, cum_rbs, g->has_bearer.data() + (size_t)cell * 2 * U))) return rc;
+  st.enter(GroupCellState::kFlows, false, last_update);
   return RS_OK;
 }
 
 int rs_group_get_flows(rs_group* g, int32_t cell, double* avg, int32_t* pending_bytes, double* last_update, int64_t* cum_bytes, int64_t* cum_rbs) {
-  if (!g) return fail(RS_ERR_INVALID, "null group");
-  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
-  if (g->resident[cell] != 3) return fail(RS_ERR_STATE, "cell %d is not flow-resident (rs_group_set_flows first)", cell);
-  rs_batch* b = g->b;
-  const size_t U = (size_t)b->U;
-  HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  if (avg) HIP_TRY(hipMemcpy(avg, g->d_qavg + (size_t)cell * 2 * U, 16 * U, hipMemcpyDeviceToHost));
-  if (pending_bytes) HIP_TRY(hipMemcpy(pending_bytes, g->d_qpend + (size_t)cell * 2 * U, 8 * U, hipMemcpyDeviceToHost));
-  if (last_update) HIP_TRY(hipMemcpy(last_update, g->d_rlast + cell, 8, hipMemcpyDeviceToHost));
-  if (cum_bytes) HIP_TRY(hipMemcpy(cum_bytes, g->d_cbytes + (size_t)cell * 2 * U, 16 * U, hipMemcpyDeviceToHost));
-  if (cum_rbs) HIP_TRY(hipMemcpy(cum_rbs, g->d_crbs + (size_t)cell * 2 * U, 16 * U, hipMemcpyDeviceToHost));
-  return RS_OK;
+  int rc = group_cell_prelude(g, cell, &kNeedFlows, true);
+  if (!rc) rc = group_get_state(g, cell, kQavg, kQpend, avg, pending_bytes, last_update);
+  return rc ? rc : group_get_counters(g, cell, kCbytes, cum_bytes, cum_rbs);
 }
 
 int rs_group_get_slice_offset(rs_group* g, int32_t cell, double* offset) {
   if (!g || !offset) return fail(RS_ERR_INVALID, "null argument");
-  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
-  HIP_TRY(hipSetDevice(g->b->cfg.cell.device));
-  HIP_TRY(hipStreamSynchronize(g->b->stream));
+  if (const int rc = group_cell_prelude(g, cell, nullptr, true)) return rc;
   HIP_TRY(hipMemcpy(offset, g->b->d_sstate + (size_t)cell * g->b->S, 8 * g->b->S, hipMemcpyDeviceToHost));
   return RS_OK;
 }
 
 int rs_group_set_slice_offset(rs_group* g, int32_t cell, const double* offset) {
   if (!g || !offset) return fail(RS_ERR_INVALID, "null argument");
-  if (cell < 0 || cell >= g->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, g->n_cells - 1);
-  HIP_TRY(hipSetDevice(g->b->cfg.cell.device));
-  HIP_TRY(hipStreamSynchronize(g->b->stream));
+  if (const int rc = group_cell_prelude(g, cell, nullptr, true)) return rc;
   HIP_TRY(hipMemcpy(g->b->d_sstate + (size_t)cell * g->b->S, offset, 8 * g->b->S, hipMemcpyHostToDevice));
   return RS_OK;
 }
@@ -3978,16 +3978,9 @@ int group_specialize_pair(rs_group* g, int kind) {
   rs_group::GroupPair& p = g->pair[f.pair];
   if (p.jit[0]) return RS_OK;
   if (p.dropped) return fail(RS_ERR_STATE, "%s", p.msg);
-  if (kind == kGroupQueued && !rs_group_form_serves(kind, b->sched))
-    return fail(RS_ERR_INVALID, "scheduler %d has no queued form (rs_group_set_bearers): nothing for rs_group_specialize_queued to build", b->sched);
-  if (kind == kGroupCounted && !rs_group_form_serves(kind, b->sched))
-    return fail(RS_ERR_INVALID, "scheduler %d has no counted form (rs_group_set_counters): nothing for rs_group_specialize_counted to build", b->sched);
-  if (kind == kGroupFlows && !rs_group_form_serves(kind, b->sched))
-    return fail(RS_ERR_INVALID, "scheduler %d has no flows form (rs_group_set_flows): nothing for rs_group_specialize_flows to build", b->sched);
-  if (kind == kGroupRun && !rs_group_form_serves(kind, b->sched))
-    return fail(RS_ERR_INVALID, "scheduler %d is not served by a run (rs_group_run_at): nothing for rs_group_specialize_run to build", b->sched);
+  if (f.lacks && !rs_group_form_serves(kind, b->sched)) return fail(RS_ERR_INVALID, "scheduler %d %s: nothing for %s to build", b->sched, f.lacks, f.entry);
   if (kind == kGroupRun && b->any_alpha)
-    return fail(RS_ERR_INVALID, "a config with a customised slice (algo_alpha != 0) is not served by a run (rs_group_run_at): nothing for rs_group_specialize_run to build");
+    return fail(RS_ERR_INVALID, "a config with a customised slice (algo_alpha != 0) %s: nothing for %s to build", f.lacks, f.entry);
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   p.wanted = true;
   if (!g->d_out2) {
