@@ -265,7 +265,20 @@ int rs_ctx_specialize(rs_ctx* ctx);
 int rs_ctx_jit_status(rs_ctx* ctx, char* msg, size_t msglen);
 /* build check without a GPU: does that kernel compile for a context of this shape? (code size or a negative value) */
 int rs_jit_selfcheck_dropin(int n_slices, int n_users, int n_rbgs, int rbg_size, int threads, int sched, char* err, size_t errlen);
-/* slice_rbs_offset_ accessors (ref: downlink-transport-scheduler.h:38) */
+/* slice_rbs_offset_ accessors (ref: downlink-transport-scheduler.h:38)
+ * THE DOMAIN OF SLICE STATE SET FROM OUTSIDE (rs_set_slice_offset, rs_group_set_slice_offset, the slice_state of
+ * rs_batch_write_state).  A value outside it is RS_ERR_INVALID with a message, and the state stays as it was:
+ *   - every scheduler: finite values;
+ *   - RS_SCHED_SEQUENTIAL / MAXCELL / SUBOPT / VOGEL / UPPERBOUND (slice_rbs_offset_): per cell, with nb_rbs = n_rbgs * rbg_size,
+ *       5 * nb_rbs * (1 + sum |slice_weight|) + sum |offset|  <  2^15 = 32768.
+ *     Two limits stand behind it.  Every surface hands target_rbs and quota_rbgs out as int16 (rs_tti_out of a context or a group
+ *     as well as rs_batch_log), so a target of magnitude 2^15 would come back wrong; under the rule the targets stay inside +-2^15 in
+ *     the call that reads the offsets and in the one after it, and from there the offsets move toward the weights' shares.  And the
+ *     quota step divides extra_rbs, the targets and extra_rbgs by a float division with a fix-up, which equals C's '/' for
+ *     numerators of magnitude below 2^25 + 2 (33554432 + 2; 1 <= divisor <= 64; measured in tests/test_quota_edge_inputs.py) and
+ *     not beyond: a single offset is thus a factor of a thousand inside that bound minus nb_rbs.
+ *   - RS_SCHED_NVS / NVS_NONGREEDY (slice_ewma_time_): values >= 0.  The reference's scan never picks a slice with a negative score,
+ *     the kernel orders scores as integer pairs, which is the order of the doubles for non-negative ones only. */
 int rs_get_slice_offset(rs_ctx* ctx, double* offset /* [S] */);
 int rs_set_slice_offset(rs_ctx* ctx, const double* offset /* [S] */);
 
@@ -312,7 +325,8 @@ rs_group* rs_group_create_checked(const rs_config* cfg, int32_t n_cells, int abi
 void rs_group_destroy(rs_group* g);
 /* in[k] / out[k] belong to cell cell_ids[k] (NULL: cell k), k = 0..n-1; every cell is validated before anything is launched */
 int rs_group_schedule_tti(rs_group* g, int32_t n, const int32_t* cell_ids, const rs_tti_in* in /* [n] */, rs_tti_out* out /* [n] */);
-/* slice_rbs_offset_ of one cell (RS_SCHED_NVS: its slice EWMAs), as rs_get_slice_offset / rs_set_slice_offset */
+/* slice_rbs_offset_ of one cell (RS_SCHED_NVS: its slice EWMAs), as rs_get_slice_offset / rs_set_slice_offset; the setter
+ * accepts the domain stated at rs_set_slice_offset and nothing else */
 int rs_group_get_slice_offset(rs_group* g, int32_t cell, double* offset /* [S] */);
 int rs_group_set_slice_offset(rs_group* g, int32_t cell, const double* offset /* [S] */);
 /* scheduling kernels launched so far: one per successful rs_group_schedule_tti, none for a rejected one (tests, tools) */
@@ -938,7 +952,8 @@ int rs_batch_read_state(rs_batch* b, double* avg_rate, int64_t* cum_bytes, int64
  * slice_state [n_cells][S]; either may be NULL = left alone.  It does not touch the rest of a cell's state -- the grant of the last
  * TTI that the next EWMA update consumes, the clock, the rand() ring, the cumulative counters -- so it is exact before the first
  * launch (or on a batch whose last grant was zero); after a launch the pending grant is applied on top of the new averages.  Not
- * with the queue model (one average per bearer there).  (ABI 9) */
+ * with the queue model (one average per bearer there).  slice_state: every cell's values lie in the domain stated at
+ * rs_set_slice_offset, else RS_ERR_INVALID and nothing is written.  (ABI 9) */
 int rs_batch_write_state(rs_batch* b, const double* avg_rate, const double* slice_state);
 /* Checkpoint / resume (ABI 10).  A checkpoint is everything a batch carries from one launch to the next -- PF averages, the grants
  * the next EWMA update consumes, cumulative counters, slice state, every cell's clock, rand() ring and CQI-report state, the number of

@@ -268,7 +268,8 @@ class Cell:
         lib().rso_cell_set_second_bearer_avg(self.h, _p(a, C.c_double))
 
     def set_slice_offset(self, offset):
-        """slice_rbs_offset_ [S] from outside (a test that follows a context whose calls the oracle did not all take part in)."""
+        """slice_rbs_offset_ [S] from outside (a test that follows a context whose calls the oracle did not all take part in);
+        schedulers 7 and 11: slice_ewma_time_ [S], the array state()["slice_state"] returns."""
         a = np.ascontiguousarray(offset, np.float64)
         assert a.shape == (self.S,)
         lib().rso_cell_set_slice_offset.argtypes = [C.c_void_p, C.POINTER(C.c_double)]

@@ -1359,6 +1359,37 @@ int rs_batch_read_state(rs_batch* b, double* avg, int64_t* cum_bytes, int64_t* c
   return RS_OK;
 }
 
+/* The domain of slice state that comes from outside (rs_set_slice_offset, rs_group_set_slice_offset, rs_batch_write_state;
+ * include/radiosaber_hip.h states it), one cell's S values at a time.
+ *   every scheduler: finite values.
+ *   transport schedulers: every surface hands targets and quotas out as int16 (RsLaunch::log_target / log_quota: the drop-in and
+ *     group outputs too), so |target| and |quota| must stay below 2^15.  With W = nb_rbs * (1 + sum |w|) and A = sum |offset|:
+ *     in the call that reads the offsets |raw target| <= nb_rbs |w| + |offset|, |extra_rbs| <= W + A and every target lies within
+ *     W + A; afterwards |offset'| <= |target| + nb_rbs, the offsets sum to the PRBs of the RBGs left unallocated, so |extra_rbs| <=
+ *     W + nb_rbs and the next targets lie within A + 4 W; from there the offsets move toward the weights' shares.  Hence the rule
+ *     5 W + A < 2^15.  It also keeps the numerators of the quota step's idiv_small (rs_wave.h; measured in tests/test_quota_edge_inputs.py: C
+ *     division below 2^25 + 2, wrong at 2^25 + 2) a factor of a thousand inside that bound.
+ *   schedulers 7 and 11: EWMAs are >= 0.  The reference's scan ('>=' from 0, :127-131) never picks a negative score and the
+ *     kernel's integer-pair maximum orders negative doubles the other way round. */
+static int check_slice_state(const rs_batch* b, const double* v, size_t cell) {
+  const int S = b->S;
+  const bool transport = b->sched == RS_SCHED_SEQUENTIAL || b->sched == RS_SCHED_MAXCELL || b->sched == RS_SCHED_SUBOPT ||
+                         b->sched == RS_SCHED_VOGEL || b->sched == RS_SCHED_UPPERBOUND;
+  const bool nvs = b->sched == RS_SCHED_NVS || b->sched == RS_SCHED_NVS_NONGREEDY;
+  const double nb = (double)b->R * b->G;
+  double w = nb, a = 0;
+  for (int s = 0; s < S; s++) {
+    if (!std::isfinite(v[s])) return fail(RS_ERR_INVALID, "slice state [%zu][%d] = %g is not finite", cell, s, v[s]);
+    if (nvs && !(v[s] >= 0)) return fail(RS_ERR_INVALID, "slice EWMA [%zu][%d] = %g is negative (slice_ewma_time_ is an average of 0s and 1s)", cell, s, v[s]);
+    w += nb * fabs(b->weight[s]);
+    a += fabs(v[s]);
+  }
+  if (transport && !(5 * w + a < 32768.0))
+    return fail(RS_ERR_INVALID, "slice offsets of cell %zu: 5 nb_rbs (1 + sum |weight|) + sum |offset| = %g, at or above 2^15 = 32768: targets and "
+                "quotas are handed out as int16 (and the quota step's divisions are exact for numerators below 2^25 + 2 only)", cell, 5 * w + a);
+  return RS_OK;
+}
+
 /* the inverse of rs_batch_read_state for the two arrays a restart needs set: PF averages (RadioBearer::m_averageTransmissionRate,
  * ref: src/flows/radio-bearer.cpp:54 starts them at 100 000) and slice_rbs_offset_ / slice_ewma_time_ */
 int rs_batch_write_state(rs_batch* b, const double* avg, const double* slice_state) {
@@ -1369,6 +1400,9 @@ int rs_batch_write_state(rs_batch* b, const double* avg, const double* slice_sta
   if (avg)
     for (size_t i = 0; i < n; i++)
       if (!(avg[i] >= 1.0) || !(avg[i] <= 1e300)) return fail(RS_ERR_INVALID, "avg_rate[%zu] = %g: the EWMA keeps averages at or above 1 (radio-bearer.cpp:160-162)", i, avg[i]);
+  if (slice_state)
+    for (int c = 0; c < b->n_cells; c++)
+      if (const int rc = check_slice_state(b, slice_state + (size_t)c * b->S, (size_t)c)) return rc;
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   HIP_TRY(hipStreamSynchronize(b->stream));
   if (avg) HIP_TRY(hipMemcpy(b->d_avg, avg, 8 * n, hipMemcpyHostToDevice));
@@ -2403,6 +2437,7 @@ int rs_get_slice_offset(rs_ctx* c, double* offset) {
 
 int rs_set_slice_offset(rs_ctx* c, const double* offset) {
   if (!c || !offset) return fail(RS_ERR_INVALID, "null argument");
+  if (const int rc = check_slice_state(c->b, offset, 0)) return rc; /* (a refused call leaves the state as it was) */
   HIP_TRY(hipStreamSynchronize(c->b->stream));
   HIP_TRY(hipMemcpy(c->b->d_sstate, offset, 8 * c->b->S, hipMemcpyHostToDevice));
   return RS_OK;
@@ -3939,6 +3974,7 @@ int rs_group_get_slice_offset(rs_group* g, int32_t cell, double* offset) {
 int rs_group_set_slice_offset(rs_group* g, int32_t cell, const double* offset) {
   if (!g || !offset) return fail(RS_ERR_INVALID, "null argument");
   if (const int rc = group_cell_prelude(g, cell, nullptr, true)) return rc;
+  if (const int rc = check_slice_state(g->b, offset, (size_t)cell)) return rc;
   HIP_TRY(hipMemcpy(g->b->d_sstate + (size_t)cell * g->b->S, offset, 8 * g->b->S, hipMemcpyHostToDevice));
   return RS_OK;
 }
