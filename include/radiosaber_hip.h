@@ -27,6 +27,7 @@ extern "C" {
 
 #define RS_ABI_VERSION 11 /* 11: (additions, no layout changed) rs_batch_flow_record (flow completion times of the queue model),
                                rs_batch_bearer_log + rs_batch_run_logged_bearers (per-bearer DoStopSchedule rows),
+                               rs_bearer_record / rs_batch_record_bound / rs_batch_run_records (the same lines from unlogged launches: one 32-byte record per credited bearer),
                                rs_group_* (one TTI of several drop-in cells in one launch), rs_group_image_stats (cqi_epoch per cell of a group),
                                rs_group_specialize / rs_group_jit_status / rs_jit_selfcheck_group (a group's own self-checked builds of the one-TTI kernel),
                                rs_group_set_avg / rs_group_get_avg / rs_group_set_pending / rs_group_schedule_tti_at (a group cell's PF averages resident on the device),
@@ -939,6 +940,40 @@ typedef struct rs_batch_bearer_log {
   double* hol_delay;     /* [n_cells][n_ttis][U][2] */
 } rs_batch_bearer_log;
 int rs_batch_run_logged_bearers(rs_batch* b, int32_t n_ttis, const rs_batch_log* log, const rs_batch_bearer_log* bearers);
+/* Bearer records (ABI 11 addition): the same per-bearer lines from an UNLOGGED launch.  The thread that credits a bearer in
+ * DoStopSchedule writes one 32-byte record for it; nothing dense is written, no other log row is needed, and the launch takes the
+ * kernel rs_batch_run would take (the lean build included).
+ *
+ * rs_batch_record_bound is the most records one cell can get in one TTI (> 0): a credit needs a grant and a grant an RBG, so
+ * min(2 n_users, n_rbgs) for RS_SCHED_PF (an RBG goes to one flow) and 2 * min(n_users, n_rbgs) for the transport schedulers and NVS
+ * (an RBG goes to one user, a user has two bearers).  RS_ERR_STATE without the queue model.
+ *
+ * rs_batch_run_records IS rs_batch_run(b, n_ttis) -- same kernel choice, and the same state, bearer state, clock, flow record,
+ * checkpoint and jit status afterwards -- and in addition n_recs[c] = the bearers credited in cell c during these n_ttis, and
+ * recs[c * cap + 0 .. n_recs[c]-1] one record each, ascending in tti, then in user, then in the reference's loop order over the user's
+ * bearers (1 before 0 for the transport schedulers and NVS, 0 before 1 for RS_SCHED_PF): the order of the log's counter lines.
+ * Records are output, not state: no checkpoint carries them, the self-check's trial launches write none, and no other run call does.
+ * Refused before anything is launched, the batch does not move: RS_ERR_INVALID for a null argument, cap < 1, n_ttis < 1 or
+ * n_ttis > 32768 (as for logged runs); RS_ERR_STATE without rs_batch_set_bearers / rs_batch_set_arrivals; RS_ERR_HIP when the device
+ * block cannot be allocated.  Overflow -- a cell counts more than cap: nothing is written at or behind the capacity, n_recs[c] carries
+ * the count as counted, the launch completes (state, flow record and the other cells' lists are complete) and the call returns
+ * RS_ERR_RANGE naming the first such cell.  cap = n_ttis * rs_batch_record_bound(b) can never overflow.
+ * The device block holds min(cap, n_ttis * bound) places per cell, grows with the largest call so far and is freed with the batch; after
+ * an RS_ERR_HIP refusal the batch has none, and the next call allocates again.  RS_RECORDS_MAX_BYTES in the environment caps the
+ * block's size: a call that needs more is refused the same way. */
+typedef struct rs_bearer_record { /* 32 bytes */
+  int32_t tti;       /* the scheduled TTI whose DoStopSchedule credited the bearer, counted from the batch's first
+                        (the numbering of rs_batch_flow_record's done_tti): launches concatenate */
+  int32_t user;      /* user id 0..U-1 */
+  int32_t bearer;    /* bearer priority, 0 or 1 */
+  int32_t bytes;     /* what UpdateTransmittedBytes added; never 0 */
+  int32_t nprb;      /* what UpdateCumulateRBs added: the user's PRBs (schedulers 7, 8, 9, 101, 103; the same count for both
+                        bearers of a split grant), the flow's own PRBs (scheduler 1) */
+  int32_t reserved;  /* 0 */
+  double hol_delay;  /* GetHeadOfLinePacketDelay before the dequeue: bit for bit rs_batch_bearer_log.hol_delay's value */
+} rs_bearer_record;
+int rs_batch_record_bound(rs_batch* b);
+int rs_batch_run_records(rs_batch* b, int32_t n_ttis, int64_t cap, rs_bearer_record* recs /* [n_cells][cap] */, int64_t* n_recs /* [n_cells] */);
 /* `launches` back-to-back launches of n_ttis each, timed with HIP events on the batch's stream;
  * ms_per_launch[launches] receives each launch's duration */
 int rs_batch_run_timed(rs_batch* b, int32_t n_ttis, int32_t launches, float* ms_per_launch);

@@ -121,12 +121,17 @@ ABI_SYMBOLS = [
     "rs_group_specialize_run", "rs_group_run_jit_status", "rs_jit_selfcheck_group_run",
     "rs_group_set_avg_counters", "rs_group_get_avg_counters", "rs_group_run_counted_at",
     "rs_group_grant_bound", "rs_group_run_records_at",
+    "rs_batch_record_bound", "rs_batch_run_records",
 ]
 
 # rs_grant_record: one grant of one TTI of a counted run (32 bytes)
 GRANT_RECORD = np.dtype([("pos", np.int32), ("user_id", np.int32), ("bytes", np.int32), ("nprb", np.int32),
                          ("cum_bytes", np.int64), ("cum_rbs", np.int64)])
 assert GRANT_RECORD.itemsize == 32
+# rs_bearer_record: one bearer that DoStopSchedule credited in one TTI of a queue-model batch (32 bytes)
+BEARER_RECORD = np.dtype([("tti", np.int32), ("user", np.int32), ("bearer", np.int32), ("bytes", np.int32), ("nprb", np.int32),
+                          ("reserved", np.int32), ("hol_delay", np.float64)])
+assert BEARER_RECORD.itemsize == 32
 
 _lib = None
 
@@ -227,6 +232,8 @@ def lib():
     L.rs_batch_run_logged_ex.argtypes = [C.c_void_p, C.c_int32, C.POINTER(_BatchLog)]
     L.rs_batch_run_logged_bearers.argtypes = [C.c_void_p, C.c_int32, C.POINTER(_BatchLog), C.POINTER(_BatchBearerLog)]
     L.rs_batch_flow_record.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]
+    L.rs_batch_record_bound.argtypes = [C.c_void_p]
+    L.rs_batch_run_records.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
     L.rs_batch_read_clock.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.rs_batch_jit_status.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.rs_batch_prepare_launch.argtypes = [C.c_void_p, C.c_int32]
@@ -1249,6 +1256,29 @@ class BatchScheduler:
             out["slice_user"] = (keys >> 8).astype(np.int32) - 1
         if bearers:
             out["bearer_bytes"], out["bearer_hol"] = bb, bh
+        return out
+
+    def record_bound(self):
+        """rs_batch_record_bound: the most bearers DoStopSchedule can credit in one TTI of one cell (queue model)."""
+        return _count(lib().rs_batch_record_bound(self._h))
+
+    def run_records(self, n_ttis, cap=None):
+        """run(n_ttis) that also returns, per cell, a BEARER_RECORD array with one record per bearer DoStopSchedule credited in these
+        TTIs, in the order of the log's counter lines (rs_batch_run_records; what logfmt.BearerLogWriter.record_lines reads).  cap: the
+        places per cell, default n_ttis * record_bound(), which cannot overflow.  A cell that counts more than cap raises
+        RadioSaberError (RS_ERR_RANGE) after the launch has completed; the error carries .records (the lists as far as they were
+        written) and .counts (the counts as counted)."""
+        if cap is None:
+            cap = max(int(n_ttis), 1) * self.record_bound()
+        recs = np.zeros((self.n_cells, max(int(cap), 1)), BEARER_RECORD)
+        n = np.zeros(self.n_cells, np.int64)
+        rc = lib().rs_batch_run_records(self._h, n_ttis, cap, recs.ctypes.data_as(C.c_void_p), _p(n, C.c_int64))
+        out = [recs[c, :min(int(n[c]), int(cap))] for c in range(self.n_cells)]  # (views: the block's untouched pages are never mapped)
+        if rc == -5:
+            err = RadioSaberError(rc, lib().rs_last_error().decode())
+            err.records, err.counts = out, n
+            raise err
+        _check(rc)
         return out
 
     def run_timed(self, n_ttis, launches):

@@ -11,6 +11,7 @@
  */
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -316,6 +317,9 @@ struct rs_batch {
   int32_t* d_flow_tti = nullptr;
   double* d_flow_time = nullptr;
   size_t n_bursts = 0;
+  /* bearer records (rs_batch_run_records): [n_cells][cap] records, then n_cells count words; grows, never shrinks.  Output, not state. */
+  void* d_recs = nullptr;
+  size_t recs_bytes = 0;
   RsJitKernel* jit = nullptr; /* shape-specialised kernel (owned by the process-wide cache) */
   RsJitKernel* jit_lean = nullptr; /* its lean build, compiled at the first launch that can use it (launch()) */
   bool jit_lean_tried = false;
@@ -683,7 +687,7 @@ RsJitKernel* lean_kernel(rs_batch* b, int n_ttis, bool logged) {
 }
 
 int launch(rs_batch* b, int n_ttis, int16_t* d_map, int16_t* d_quota, int16_t* d_target, int32_t* d_tbs, int32_t* d_uinfo,
-           uint32_t* d_keys = nullptr, int32_t* d_bbytes = nullptr, double* d_bhol = nullptr);
+           uint32_t* d_keys = nullptr, int32_t* d_bbytes = nullptr, double* d_bhol = nullptr, void* d_recs = nullptr, int64_t rec_cap = 0);
 
 /* Everything a batch carries from one launch to the next, as (device pointer, bytes): PF averages, pending grants, cumulative counters,
  * slice state, clock / rand() ring / CQI-report state, and with the queue model the bearers' queues, averages, counters and per-user
@@ -1025,7 +1029,7 @@ int selfcheck(rs_batch* b, int n_ttis, bool logged) {
 }
 
 int launch(rs_batch* b, int n_ttis, int16_t* d_map, int16_t* d_quota, int16_t* d_target, int32_t* d_tbs, int32_t* d_uinfo,
-           uint32_t* d_keys, int32_t* d_bbytes, double* d_bhol) {
+           uint32_t* d_keys, int32_t* d_bbytes, double* d_bhol, void* d_recs, int64_t rec_cap) {
   if (n_ttis < 1) return fail(RS_ERR_INVALID, "n_ttis %d < 1", n_ttis);
   if (b->cqi_mode == RS_CQI_NONE) return fail(RS_ERR_STATE, "no CQI source set");
   if (b->any_alpha && !b->direct && !b->queues)
@@ -1063,6 +1067,9 @@ int launch(rs_batch* b, int n_ttis, int16_t* d_map, int16_t* d_quota, int16_t* d
     L.q_flags = b->d_qflags; L.q_hol = b->d_qhol;
     L.flow_tti = b->d_flow_tti; L.flow_time = b->d_flow_time;
     L.log_bbytes = d_bbytes; L.log_bhol = d_bhol;
+    /* bearer records (rs_batch_run_records; RsBearerRecord, rs_device.h): a batch launch sends no group's sent rows, the two words carry
+     * the record block and one cell's capacity.  Null in every other launch -- the self-check's and the autotune's trials included. */
+    L.grp_sent = (int32_t*)d_recs; L.grp_sent_stride = d_recs ? rec_cap : 0;
   }
   const bool logged = d_map || d_quota || d_target || d_tbs || d_uinfo || d_keys || d_bbytes;
   if (!b->selfchecked && !b->in_selfcheck && b->jit && !b->direct) {
@@ -1105,7 +1112,8 @@ void rs_batch_destroy(rs_batch* b) {
   void* ptrs[] = {b->d_tab, b->d_weight, b->d_eps, b->d_psi, b->d_alpha, b->d_beta, b->d_user_slice, b->d_tbs_eff, b->d_avg, b->d_tx, b->d_cumb, b->d_cumr,
                   b->d_sstate, b->d_scal, b->d_epochs, b->d_trace, b->d_user_trace, b->d_err, b->d_slice_bytes, b->d_stamps,
                   b->d_bearer_kind, b->d_arr_off, b->d_arr_time, b->d_arr_nfull, b->d_arr_last, b->d_qi, b->d_bavg, b->d_bcum,
-                  b->d_qflags, b->d_qhol, b->d_flow_tti, b->d_flow_time, b->d_epochs_prb, b->d_trace_prb, b->d_gen_num, b->d_prio_sum};
+                  b->d_qflags, b->d_qhol, b->d_flow_tti, b->d_flow_time, b->d_epochs_prb, b->d_trace_prb, b->d_gen_num, b->d_prio_sum,
+                  b->d_recs};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (b->own_stream && b->stream) (void)hipStreamDestroy(b->stream);
@@ -1327,6 +1335,92 @@ int rs_batch_run_logged_bearers(rs_batch* b, int32_t n_ttis, const rs_batch_log*
     if (bearers && blg->hol_delay) HIP_TRY(hipMemcpy(blg->hol_delay, d_bhol, 8 * rows * b->U * 2, hipMemcpyDeviceToHost));
   }
   return rc;
+}
+
+/* most bearers DoStopSchedule can credit in one TTI of one cell.  A credit needs a grant and a grant needs an RBG.
+ * Scheduler 1 gives an RBG to one FLOW (a bearer): min(2 U, R).  The transport schedulers and NVS give it to one USER, whose grant
+ * DoStopSchedule splits over at most its two bearers: 2 min(U, R). */
+int rs_batch_record_bound(rs_batch* b) {
+  if (!b) return fail(RS_ERR_INVALID, "null batch");
+  if (!b->queues) return fail(RS_ERR_STATE, "bearer records: the batch has no queue model (rs_batch_set_bearers / rs_batch_set_arrivals)");
+  return b->sched == RS_SCHED_PF ? std::min(2 * b->U, b->R) : 2 * std::min(b->U, b->R);
+}
+
+int rs_batch_run_records(rs_batch* b, int32_t n_ttis, int64_t cap, rs_bearer_record* recs, int64_t* n_recs) {
+  static_assert(sizeof(rs_bearer_record) == sizeof(RsBearerRecord) && offsetof(rs_bearer_record, hol_delay) == offsetof(RsBearerRecord, hol_delay),
+                "the device writes the ABI's record");
+  if (!b || !recs || !n_recs) return fail(RS_ERR_INVALID, "null argument");
+  if (cap < 1) return fail(RS_ERR_INVALID, "cap %lld < 1", (long long)cap);
+  if (n_ttis < 1) return fail(RS_ERR_INVALID, "n_ttis %d < 1", n_ttis);
+  if (n_ttis > RS_MAX_TTIS_PER_LAUNCH) return fail(RS_ERR_INVALID, "runs with records are limited to %d TTIs per call", RS_MAX_TTIS_PER_LAUNCH);
+  if (!b->queues || !b->d_arr_off)
+    return fail(RS_ERR_STATE, "bearer records: the batch has no queue model (rs_batch_set_bearers / rs_batch_set_arrivals)");
+  HIP_TRY(hipSetDevice(b->cfg.cell.device));
+  /* the device block: no cell can count more than n_ttis * bound, so a larger capacity of the caller's needs no larger list there */
+  const size_t cells = (size_t)b->n_cells;
+  const int64_t cap_dev = std::min(cap, (int64_t)n_ttis * rs_batch_record_bound(b));
+  const size_t list_bytes = cells * (size_t)cap_dev * sizeof(RsBearerRecord), need = list_bytes + 4 * cells;
+  if (need > b->recs_bytes) {
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (b->d_recs) { HIP_TRY(hipFree(b->d_recs)); b->d_recs = nullptr; b->recs_bytes = 0; }
+    /* RS_RECORDS_MAX_BYTES: the largest device block a call may ask for (unset: what the device gives).  A block above it is a failed
+     * allocation, by the very path of one: it is how the tests reach this refusal without asking a card for memory it does not have. */
+    const char* const e_max = getenv("RS_RECORDS_MAX_BYTES");
+    const bool too_large = e_max && (unsigned long long)need > strtoull(e_max, nullptr, 10);
+    if (too_large || hipMalloc(&b->d_recs, need) != hipSuccess) {
+      if (!too_large) (void)hipGetLastError();
+      b->d_recs = nullptr;
+      return fail(RS_ERR_HIP, "bearer records: no device block of %zu bytes (%zu cells x %lld records)", need, cells, (long long)cap_dev);
+    }
+    b->recs_bytes = need;
+  }
+  uint32_t* const d_count = (uint32_t*)((char*)b->d_recs + list_bytes);
+  HIP_TRY(hipMemsetAsync(d_count, 0, 4 * cells, b->stream));
+  int rc = launch(b, n_ttis, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, b->d_recs, cap_dev);
+  if (rc) return rc;
+  rc = rs_batch_sync(b);
+  if (rc == RS_ERR_HIP) return rc;
+  /* the copy back: the counts, then of every list the places that were written (copies queued on the stream, one wait) */
+  std::vector<uint32_t> count(cells);
+  HIP_TRY(hipMemcpy(count.data(), d_count, 4 * cells, hipMemcpyDeviceToHost));
+  int64_t over = -1;
+  for (size_t c = 0; c < cells; c++) {
+    n_recs[c] = (int64_t)count[c];
+    if ((int64_t)count[c] > cap_dev && over < 0) over = (int64_t)c; /* (cap_dev < cap only where nothing can exceed it) */
+    const size_t used = (size_t)std::min((int64_t)count[c], cap_dev);
+    if (used)
+      HIP_TRY(hipMemcpyAsync(recs + c * (size_t)cap, (const RsBearerRecord*)b->d_recs + c * (size_t)cap_dev, used * sizeof(RsBearerRecord),
+                             hipMemcpyDeviceToHost, b->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  /* BearerLogWriter's order: TTI, user, then the reference's loop over the user's bearers -- priority 1 first in DoStopSchedule of the
+   * transport schedulers and NVS (downlink-transport-scheduler.cpp:179), flow 0 first in DL_PF's FlowsToSchedule.  A (TTI, user, bearer)
+   * occurs once, so the result does not depend on the order the device handed the places out in.  The device hands out all places of
+   * TTI k before any of TTI k + 1 (rs_phase_queues.inc), and inside a TTI nearly in user order: an insertion sort per TTI's stretch, a
+   * few dozen records that are almost in place; a list whose TTIs do not ascend -- it would mean that guarantee broke -- is sorted in full. */
+  const bool pf = b->sched == RS_SCHED_PF;
+  auto key = [pf](const rs_bearer_record& x) { return ((uint64_t)(uint32_t)x.user << 1) | (uint64_t)(pf ? x.bearer : 1 - x.bearer); };
+  for (size_t c = 0; c < cells; c++) {
+    rs_bearer_record* const r = recs + c * (size_t)cap;
+    const size_t n = (size_t)std::min((int64_t)count[c], cap_dev);
+    bool ascending = true;
+    for (size_t i = 0, j; i < n; i = j) {
+      if (i && r[i].tti < r[i - 1].tti) ascending = false;
+      for (j = i + 1; j < n && r[j].tti == r[i].tti; j++) {
+        const rs_bearer_record x = r[j];
+        size_t k = j;
+        for (; k > i && key(r[k - 1]) > key(x); k--) r[k] = r[k - 1];
+        r[k] = x;
+      }
+    }
+    if (!ascending)
+      std::sort(r, r + n, [&key](const rs_bearer_record& x, const rs_bearer_record& y) { return x.tti != y.tti ? x.tti < y.tti : key(x) < key(y); });
+  }
+  if (rc) return rc;
+  if (over >= 0)
+    return fail(RS_ERR_RANGE, "bearer records: cell %lld credited %lld bearers in these %d TTIs, the lists hold %lld (state, flow record and the other cells' lists are complete)",
+                (long long)over, (long long)n_recs[over], n_ttis, (long long)cap);
+  return RS_OK;
 }
 
 int rs_batch_run_timed(rs_batch* b, int32_t n_ttis, int32_t launches, float* ms) {

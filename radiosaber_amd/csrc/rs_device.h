@@ -433,6 +433,18 @@ struct RsGrantRecord {
   int64_t cum_bytes, cum_rbs;
 };
 static_assert(sizeof(RsGrantRecord) == 32 && __builtin_offsetof(RsGrantRecord, cum_bytes) == 16, "rs_grant_record is 32 bytes, the counters its second half");
+/* one credited bearer of one TTI of a queue-model BATCH (rs_batch_run_records, log_bearer of rs_phase_queues.inc): rs_bearer_record of
+ * the ABI, two 16-byte halves.  A batch launch sends no group's sent rows, so the launch block carries the record block in grp_sent
+ * (device memory: [n_cells][cap] records, then one count word per cell, zeroed by the host ahead of the launch) and the capacity of
+ * one cell's list in grp_sent_stride; null / 0 in every launch that wants no records.  Only the QUEUE instantiations of rs_cell_body
+ * read the two words. */
+struct RsBearerRecord {
+  int32_t tti, user, bearer, bytes;
+  int32_t nprb, reserved;
+  double hol_delay;
+};
+static_assert(sizeof(RsBearerRecord) == 32 && __builtin_offsetof(RsBearerRecord, nprb) == 16 && __builtin_offsetof(RsBearerRecord, hol_delay) == 24,
+              "rs_bearer_record is 32 bytes, the delay the last 8 of its second half");
 #define RS_GROUP_RUN_ROW_BYTES 16
 static_assert(sizeof(RsGroupCell) == RS_GROUP_HDR_BYTES, "the slot header keeps its size: new words come out of its padding");
 static_assert(__builtin_offsetof(RsGroupCell, image_mode) == 72 && __builtin_offsetof(RsGroupCell, now) == 80, "no existing word of the slot header moves");

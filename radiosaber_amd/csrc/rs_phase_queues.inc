@@ -123,8 +123,7 @@
   /* logged launches: one row per (TTI, user, bearer) -- the bytes DoStopSchedule credited and RadioBearer::GetHeadOfLinePacketDelay
    * at that moment, before the RLC dequeue (radio-bearer.cpp:282-307: 0 with an empty MAC queue or an InfiniteBuffer bearer, else
    * now - the head packet's time stamp, at least 1e-5; the slice-priority bearer's value is the q_ho its metric used in that TTI) */
-  auto log_bearer = [&](int u, int b, int kind, int bytes, int row) {
-    if (!p.log_bbytes || row < 0) return;
+  auto bearer_hol = [&](int u, int b, int kind) -> double { /* the one expression both outputs below carry */
     double hol = 0.0;
     if (kind == 2 && QI(QF_BYTES, b, u) != 0) {
       const double head_time = q_lds ? qs_headt[b * U + u]
@@ -132,9 +131,40 @@
       hol = q_stop_t - head_time;
       if (hol < 0.00001) hol = 0.00001;
     }
-    const size_t i = (((size_t)cell * p.n_ttis + row) * U + u) * 2 + b;
-    p.log_bbytes[i] = bytes;
-    p.log_bhol[i] = hol;
+    return hol;
+  };
+  /* ... and unlogged launches that were asked for records (rs_batch_run_records): one RsBearerRecord per credited bearer instead of
+   * the dense rows.  The record block rides in the launch block's grp_sent / grp_sent_stride (rs_device.h; null in every other
+   * launch): per cell a list of grp_sent_stride places, and behind all lists the cells' count words, zeroed by the host.  A place comes
+   * from the cell's count word, one add per credited bearer by the thread that credits it -- stop_schedule_user runs under a
+   * per-thread user loop whose trips differ between the lanes of a wave, so there is no ballot to aggregate; workgroup scope, the
+   * workgroup owns the cell.  All places of TTI k are handed out before any of TTI k + 1 (barriers lie between); inside a TTI they
+   * come as the threads arrive, and the host sorts.  A place at or behind the capacity is not written: the count tells the host.
+   * (Block, capacity and count word are formed from the launch block where a record is written, like p.flow_tti in rlc_dequeue:
+   * nothing of them stays live across the TTI.) */
+  auto log_bearer = [&](int u, int b, int kind, int bytes, int nprb, int row) {
+    const bool dense = p.log_bbytes && row >= 0;
+    if (!dense && !p.grp_sent) return;
+    const double hol = bearer_hol(u, b, kind);
+    if (dense) {
+      const size_t i = (((size_t)cell * p.n_ttis + row) * U + u) * 2 + b;
+      p.log_bbytes[i] = bytes;
+      p.log_bhol[i] = hol;
+    }
+    if (p.grp_sent) {
+      /* The TTI is n_done - 1, as the flow completion record takes it, whatever `row` says: row < 0 is DoStopSchedule at the top of a
+       * launch's first TTI, and it finds no grant -- a launch ends with every grant consumed (the loop behind the last TTI), a fresh
+       * batch has none -- so every record of a launch belongs to one of its own TTIs. */
+      RsBearerRecord* const lists = (RsBearerRecord*)p.grp_sent;
+      const size_t cap = (size_t)p.grp_sent_stride;
+      uint32_t* const count = (uint32_t*)(lists + (size_t)p.n_cells * cap) + cell;
+      const uint32_t place = __hip_atomic_fetch_add(count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if ((size_t)place < cap) {
+        int4* const dst = (int4*)(lists + (size_t)cell * cap + place);
+        dst[0] = make_int4((int)(n_done - 1), u, b, bytes);
+        dst[1] = make_int4(nprb, 0, __double2loint(hol), __double2hiint(hol));
+      }
+    }
   };
   /* row: the launch's TTI whose grant this is (its log row) */
   auto stop_schedule_user = [&](int u, int row) {
@@ -154,7 +184,7 @@
         user_bytes += bytes;
         user_rbs += nprb;
         const int kind = kind_of[u * 2 + b];
-        log_bearer(u, b, kind, bytes, row);
+        log_bearer(u, b, kind, bytes, nprb, row);
         if (kind == 2) rlc_dequeue(u, b, bytes);
       }
       if (user_bytes) count_user(u, user_bytes, user_rbs);
@@ -177,7 +207,7 @@
       QI(QF_TX, b, u) += sent;
       count_bearer(u, b, sent, nprb);
       user_bytes += sent;
-      log_bearer(u, b, kind, sent, row);
+      log_bearer(u, b, kind, sent, nprb, row);
       if (kind == 2) rlc_dequeue(u, b, sent);
     }
     if (user_bytes) count_user(u, user_bytes, nprb);

@@ -241,6 +241,30 @@ class BearerLogWriter:
         done_time)} of this cell (BatchScheduler.flow_record())."""
         bearer_bytes = np.asarray(bearer_bytes)
         n = bearer_bytes.shape[0]
+        credits = [{} for _ in range(n)]
+        for j in range(n):
+            for u in np.flatnonzero(bearer_bytes[j].any(1)):
+                credits[j][int(u)] = {k: (int(bearer_bytes[j, u, k]), int(bearer_rbs[j, u, k]), bearer_hol[j, u, k])
+                                      for k in (0, 1) if bearer_bytes[j, u, k] > 0}
+        return self._launch_lines(credits, t_first, done)
+
+    def record_lines(self, records, t_first: float, n_ttis: int, done=None) -> List[str]:
+        """The same launch from its bearer records alone (BatchScheduler.run_records, one cell's BEARER_RECORD array): the lines
+        lines() writes from the dense rows and the PRB counts of a logged launch of the same n_ttis TTIs.  t_first and done as there.
+        A record's tti counts from the batch's first TTI, like this writer's; a TTI without a record still advances the clock and
+        prints the ipflow start lines that fall into it."""
+        g0 = self.tti
+        credits = [{} for _ in range(n_ttis)]
+        for r in np.asarray(records):
+            j = int(r["tti"]) - g0
+            if not 0 <= j < n_ttis:
+                raise ValueError(f"record of TTI {int(r['tti'])} outside this launch's TTIs {g0} .. {g0 + n_ttis - 1}")
+            credits[j].setdefault(int(r["user"]), {})[int(r["bearer"])] = (int(r["bytes"]), int(r["nprb"]), r["hol_delay"])
+        return self._launch_lines(credits, t_first, done)
+
+    def _launch_lines(self, credits, t_first: float, done) -> List[str]:
+        """credits[j] = {user: {prio: (bytes, PRBs, hol_delay)}} of the launch's TTI j, credited bearers only."""
+        n = len(credits)
         g0 = self.tti
         ends = {}
         for key, (dt, dtime) in (done or {}).items():
@@ -259,13 +283,13 @@ class BearerLogWriter:
                 t, app, i, u, k = self.starts[self.next_start]
                 out.append(f"ipflow start app: {app} flow: {i} flowsize: {int(self.flows[(u, k)][1][i])}")
                 self.next_start += 1
-            for u in np.flatnonzero(bearer_bytes[j].any(1)):
+            for u in sorted(credits[j]):
                 for k in self.order:
-                    by = int(bearer_bytes[j, u, k])
-                    if by > 0:
+                    if k in credits[j][u]:
+                        by, rbs, hol = credits[j][u][k]
                         self.cb[u, k] += by
-                        self.cr[u, k] += int(bearer_rbs[j, u, k])
-                        out.append(self.counter_line(ts, self.app_of[u, k], self.cb[u, k], self.cr[u, k], bearer_hol[j, u, k], u,
+                        self.cr[u, k] += rbs
+                        out.append(self.counter_line(ts, self.app_of[u, k], self.cb[u, k], self.cr[u, k], hol, u,
                                                      self.u2s[u], self.flow_format))
                     for i, dtime in sorted(ends.get((j, int(u), k), [])):
                         t, size = self.flows[(int(u), k)]

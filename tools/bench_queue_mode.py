@@ -8,8 +8,10 @@ Traffic: rs_internet_flow_arrivals (the reference's InternetFlow process) and th
 (tests/golden/video_foreman_1280k.json), generated for `--distinct` cells and repeated over the batch (the CQI grids and rand()
 seeds differ per cell, so the trajectories still differ).  Timing: HIP events around every launch (rs_batch_run_timed).
 
-  python tools/bench_queue_mode.py [--cells 512] [--ttis 1000] [--launches 3] [--sched 9,7,1] [--distinct 8] [--no-jit]
-Prints one JSON line per scheduler (and a backlogged line of the same shape for comparison with --with-backlogged)."""
+  python tools/bench_queue_mode.py [--cells 512] [--ttis 1000] [--launches 3] [--sched 9,7,1] [--distinct 8] [--no-jit] [--records]
+Prints one JSON line per scheduler (and a backlogged line of the same shape for comparison with --with-backlogged).  --records times
+run_records (cap = ttis * record_bound) instead: wall-clock per call, copy back and sort included, since the records on the host are what
+the call is for; the line also carries the records per cell-TTI and the bytes copied back per launch."""
 import argparse
 import json
 import sys
@@ -65,6 +67,7 @@ def main():
     ap.add_argument("--rbg-size", type=int, default=8)
     ap.add_argument("--no-jit", action="store_true")
     ap.add_argument("--with-backlogged", action="store_true", help="also time the same shape without the queue model")
+    ap.add_argument("--records", action="store_true", help="time run_records (one record per credited bearer) instead of run")
     a = ap.parse_args()
     if rs.device_count() < 1:
         raise SystemExit("bench_queue_mode.py needs an MI355X: the product has no CPU path")
@@ -89,7 +92,20 @@ def main():
             b.seed(seeds.astype(np.uint32))
             b.synthesize_cqi(0x5AB3, (total_ttis + 39) // 40)
             b.run(a.ttis)  # warm-up launch: code object load, queues fill
-            ms = b.run_timed(a.ttis, a.launches)
+            extra = {}
+            if a.records and queues:
+                ms, n_rec, copied = [], 0, 0
+                for _ in range(a.launches):
+                    t1 = time.perf_counter()
+                    recs = b.run_records(a.ttis)
+                    ms.append((time.perf_counter() - t1) * 1e3)
+                    n_rec += sum(len(r) for r in recs)
+                    copied += sum(len(r) for r in recs) * rs.api.BEARER_RECORD.itemsize + 4 * a.cells  # (each cell's written places, the count words)
+                ms = np.asarray(ms)
+                extra = {"records": True, "record_bound": b.record_bound(), "records_per_cell_tti": n_rec / (a.cells * a.ttis * a.launches),
+                         "bytes_copied_per_launch": copied // a.launches}
+            else:
+                ms = b.run_timed(a.ttis, a.launches)
             jit = b.jit_status()
             sb = b.slice_bytes()
             b.close()
@@ -100,6 +116,7 @@ def main():
                 "ms_per_launch": [round(float(x), 3) for x in ms], "value": a.cells * a.ttis / (best / 1e3), "unit": "TTIs/s",
                 "us_per_tti_per_cell": best * 1e3 / a.ttis, "jit": jit[0], "source_hash": rs.device_source_hash(),
                 "slice_mbps_per_cell": [round(float(x) * 8 / 1e6 / ((a.launches + 1) * a.ttis / 1000.0) / a.cells, 3) for x in sb],
+                **extra,
             }))
             sys.stdout.flush()
 

@@ -16,7 +16,8 @@ line earlier versions of this tool wrote for it (--sched1-line auto; `app` gives
 internet_flow / video_app applications (exp-customization) runs on the queue model: InternetFlow bursts from
 rs_internet_flow_arrivals at the config's rates, the video applications from the 1 280 kbit/s foreman trace
 (tests/golden/video_foreman_1280k.json, --video-trace), and the log also carries the "ipflow start" / "ipflow end" lines of the
-InternetFlow flows, with flow completion times from the batch's flow completion record.
+InternetFlow flows, with flow completion times from the batch's flow completion record.  --records takes the same lines from
+unlogged launches: the device writes one 32-byte record per credited bearer instead of dense per-TTI rows, and the log is identical.
 
 The scheduler's arithmetic is bit-exact; the position of the libc rand() stream at the first scheduled TTI depends on
 simulator set-up code outside this path (103 300 draws for the 100-UE configuration) and is taken
@@ -53,6 +54,9 @@ ap.add_argument("--sched1-line", choices=("auto", "app", "flow"), default="auto"
                 help="scheduler 1's counter line: app (DL_PF_PacketScheduler's own), flow (the base class's); auto = app with the queue "
                      "model, flow for backlogged configurations (this tool's earlier format)")
 ap.add_argument("--log", default="-", help="where the stderr-format lines go ('-' = stdout)")
+ap.add_argument("--records", action="store_true",
+                help="queue-model configurations: unlogged launches that return one record per credited bearer (run_records) instead of "
+                     "logged launches with dense rows; the log is the same")
 a = ap.parse_args()
 
 sc = rs.SliceConfig.from_json(a.config)
@@ -61,6 +65,8 @@ n_ttis = int(round(a.duration * 1000))
 U = sc.n_users
 seed = COMMON_SEEDS[a.seed] if 0 <= a.seed < 9 else COMMON_SEEDS[0]
 queues = any(int(t.get("internet_flow", 0)) or int(t.get("video_app", 0)) for t in sc.traffic)
+if a.records and not queues:
+    raise SystemExit("--records: bearer records come from the queue model; this configuration has no internet_flow / video_app applications")
 # (the queue model's batches run without the PHY error model's draws: its parity with the oracle is pinned that way)
 b = rs.BatchScheduler(sc, R, a.rbg_size, 1, sched=a.sched, phy_error_draws=not queues, jit=True)
 b.seed(np.array([seed], np.uint32), np.array([a.rand_skip], np.int64))
@@ -108,6 +114,13 @@ done = 0
 while done < n_ttis:  # logged launches of at most 2 000 TTIs keep the host log small
     n = min(2000, n_ttis - done)
     t_first = float(b.clock()[0][0])
+    if a.records:
+        records = b.run_records(n)[0]
+        rec = {(u, k): v for (c, u, k), v in b.flow_record().items() if (u, k) in flows}
+        lines = writer.record_lines(records, t_first, n, rec)
+        out.write("\n".join(lines) + ("\n" if lines else ""))
+        done += n
+        continue
     got = b.run_logged(n, bearers=queues)
     if queues:
         by, hol = got["bearer_bytes"][0], got["bearer_hol"][0]
