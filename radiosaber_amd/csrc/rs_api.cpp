@@ -1089,6 +1089,14 @@ int launch(rs_batch* b, int n_ttis, int16_t* d_map, int16_t* d_quota, int16_t* d
   return RS_OK;
 }
 
+/* the layout check of the three *_create_checked functions (rs_batch_create_checked says why); `name`: the caller's config struct */
+bool abi_matches(int abi_version, size_t cfg_size, size_t lib_size, const char* name) {
+  if (abi_version == RS_ABI_VERSION && cfg_size == lib_size) return true;
+  fail(RS_ERR_INVALID, "ABI mismatch: caller was built against ABI %d with an %s of %zu bytes, this library is ABI %d with %zu bytes", abi_version,
+       name, cfg_size, RS_ABI_VERSION, lib_size);
+  return false;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1098,12 +1106,7 @@ rs_batch* rs_batch_create(const rs_batch_config* cfg) { return batch_new(cfg, fa
 /* the same behind a deterministic layout check: the caller passes the ABI version and the struct size IT was compiled with
  * (RS_BATCH_CREATE in the header does); a caller built against another layout is refused instead of being read field-shifted */
 rs_batch* rs_batch_create_checked(const rs_batch_config* cfg, int abi_version, size_t cfg_size) {
-  if (abi_version != RS_ABI_VERSION || cfg_size != sizeof(rs_batch_config)) {
-    fail(RS_ERR_INVALID, "ABI mismatch: caller was built against ABI %d with an rs_batch_config of %zu bytes, this library is ABI %d with %zu bytes",
-         abi_version, cfg_size, RS_ABI_VERSION, sizeof(rs_batch_config));
-    return nullptr;
-  }
-  return rs_batch_create(cfg);
+  return abi_matches(abi_version, cfg_size, sizeof(rs_batch_config), "rs_batch_config") ? rs_batch_create(cfg) : nullptr;
 }
 
 void rs_batch_destroy(rs_batch* b) {
@@ -1920,6 +1923,47 @@ const char* rs_batch_kernel_name(rs_batch* b) {
 /* ===================================================================================== */
 /* drop-in mode: one RBsAllocation() per call on a one-cell batch                        */
 
+namespace {
+/* rs_tti_in.cqi_epoch: what one cell's device-resident CQI image holds -- the reports of the cell's last call that stored them (mode 1:
+ * the number, the user count, the kind of report, the user list), and whether a later call may still be served from them.  One per
+ * context, one per cell of a group.  The record says what the image holds; WHEN it stops being valid is its owner's rule (a context:
+ * ctx_pack, ctx_commit_image; a group: ImageGuard, group_commit_images). */
+struct CqiImage {
+  bool valid = false, prb = false, has_ids = false;
+  uint64_t epoch = 0;
+  int n = 0;
+  std::vector<int32_t> ids;
+  /* A call's RsLaunch / RsGroupCell image_mode under the number that counts for it (`epoch`; 0: the call makes no promise) -- 0: the
+   * caller's block is read and nothing is kept; 1: it is read and stored as the image; 2: the same reports for the same users as the
+   * stored call's -- the block is neither checked, copied nor read, the kernel reads the image (and the device copy of a per-PRB block) */
+  int mode(const rs_tti_in& in, bool per_prb, uint64_t epoch_that_counts) const {
+    if (epoch_that_counts == 0) return 0;
+    const bool same = valid && epoch == epoch_that_counts && n == in.n_users && prb == per_prb && has_ids == (in.user_id != nullptr) &&
+                      (!in.user_id || memcmp(ids.data(), in.user_id, 4 * (size_t)n) == 0);
+    return same ? 2 : 1;
+  }
+  /* a mode-1 call has completed: the device holds its reports now */
+  void stored(const rs_tti_in& in, bool per_prb) {
+    valid = true;
+    epoch = in.cqi_epoch;
+    n = in.n_users;
+    prb = per_prb;
+    has_ids = in.user_id != nullptr;
+    if (in.user_id) ids.assign(in.user_id, in.user_id + in.n_users);
+  }
+};
+
+/* A pair of run-time builds of one kernel -- index 0: the general build, 1: the lean build for the plain call -- and their check
+ * against the built-in kernel: calls still to be checked, calls that agreed so far (jit_pair_build .. jit_pair_drop below).  A
+ * specialised context has one, a group one per form. */
+struct JitPair {
+  RsJitKernel* jit[2] = {nullptr, nullptr};
+  bool wanted = false, dropped = false;
+  int chk_left[2] = {0, 0}, chk_agreed[2] = {0, 0};
+  char msg[512] = ""; /* why no build serves: the failed build's, the failed check's */
+};
+}  // namespace
+
 struct rs_ctx {
   rs_batch* b = nullptr;
   /* one pinned staging block each way, mirrored by one device block each way:
@@ -1948,18 +1992,14 @@ struct rs_ctx {
   /* rs_tti_in.cqi_epoch (round 6): the grid of the last call whose reports were new, kept on the device as the LDS image ([R][Upad]);
    * a call with the same epoch number and the same user list reads it instead of the caller's block (RsLaunch::image_mode) */
   uint8_t* d_img = nullptr;
-  bool img_valid = false, img_prb = false, img_has_ids = false;
-  uint64_t img_epoch = 0;
-  int img_n = 0;
-  std::vector<int32_t> img_ids;
+  CqiImage img;
   long n_img_reused = 0;
-  /* the specialised builds' check against the built-in kernel (rs_ctx_specialize; index 0: general build, 1: lean build):
-   * calls still to be checked, calls that agreed so far */
-  int chk_left[2] = {0, 0}, chk_agreed[2] = {0, 0};
-  bool jit_dropped = false;
-  uint8_t *d_out2 = nullptr, *d_chk = nullptr; /* the built-in kernel's output block; slice state + scalars before / after it */
+  /* rs_ctx_specialize: the context's own builds of the one-TTI kernel (the batch's jit fields stay empty: a context's batch is never
+   * launched as a batch), and the blocks of their checked calls -- the built-in kernel's output block; slice state + scalars before
+   * / after it (TwinState) */
+  JitPair pair;
+  uint8_t *d_out2 = nullptr, *d_chk = nullptr;
   std::vector<uint8_t> h_out2;
-  char jit_msg[512] = "";
 };
 
 namespace {
@@ -2211,6 +2251,118 @@ void selfcheck_state(RsJitKernel* k, int left, int agreed, const char* ref, char
   else if (rs_jit_is_verified(k)) snprintf(out, n, "carries the self-check mark of an earlier check (cache file)");
   else snprintf(out, n, "unchecked (RS_JIT_SELFCHECK=0)");
 }
+
+/* A pair's two builds for the config of `b`: rs_jit_get with `flags` (general) and `flags | 4` (lean; RS_JIT_LEAN=0: none, the general
+ * build serves every call), and how many calls each serves beside the built-in kernel.  A failed general build leaves its message in
+ * the pair. */
+int jit_pair_build(JitPair* p, const rs_batch* b, int flags) {
+  const int qmode = (b->sched == RS_SCHED_PF || b->sched == RS_SCHED_NVS) ? 1 : 0; /* (the gate scratch of a drop-in carve: carve_lds) */
+  char msg[512] = "";
+  p->wanted = true;
+  p->jit[0] = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, qmode, 0, msg, sizeof msg, flags);
+  if (!p->jit[0]) {
+    snprintf(p->msg, sizeof p->msg, "%s", msg[0] ? msg : "hiprtc build failed");
+    return fail(RS_ERR_HIP, "%s", p->msg);
+  }
+  p->msg[0] = 0;
+  const char* const e_on = getenv("RS_JIT_LEAN");
+  if (!e_on || atoi(e_on) != 0) p->jit[1] = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, qmode, 0, msg, sizeof msg, flags | 4);
+  for (int w = 0; w < 2; w++) {
+    p->chk_agreed[w] = 0;
+    p->chk_left[w] = selfcheck_calls(p->jit[w]);
+  }
+  return RS_OK;
+}
+/* the message and the code of a *_jit_status function; ref: what the pair's checked calls agree with */
+int jit_pair_status(const JitPair& p, const char* ref, char* msg, size_t msglen) {
+  if (msg && msglen) {
+    if (p.dropped || !p.jit[0]) {
+      snprintf(msg, msglen, "%s", p.msg);
+    } else {
+      char ge[220], le[220];
+      selfcheck_state(p.jit[0], p.chk_left[0], p.chk_agreed[0], ref, ge, sizeof ge);
+      selfcheck_state(p.jit[1], p.chk_left[1], p.chk_agreed[1], ref, le, sizeof le);
+      snprintf(msg, msglen, "general build: %s; lean build: %s", ge, le);
+    }
+  }
+  if (p.dropped) return -2;
+  return p.jit[0] ? 1 : (p.wanted ? -1 : 0);
+}
+/* a checked call of build `which` agreed with the built-in kernel; the last one earns the build its mark */
+void jit_pair_agreed(JitPair* p, int which) {
+  p->chk_agreed[which]++;
+  if (--p->chk_left[which] == 0) rs_jit_mark_verified(p->jit[which]);
+}
+/* a checked call disagreed: one wrong build of a shape and neither is trusted -- both are rejected (and their cache files unlinked) */
+void jit_pair_drop(JitPair* p) {
+  for (int w = 0; w < 2; w++) {
+    if (p->jit[w]) rs_jit_reject(p->jit[w]);
+    p->jit[w] = nullptr;
+    p->chk_left[w] = 0;
+  }
+  p->dropped = true;
+}
+
+/* The state of a checked call's twin run.  `d_chk` holds two halves, each the [n_cells][S] slice state and then the [n_cells]
+ * RsCellScalars of batch `b` (256-byte aligned): the first half is what the built-in kernel found, the second what it left.  A context
+ * is n_cells = 1; a group's form with stores keeps those the same way around these calls (group_copy_stores). */
+struct TwinState {
+  rs_batch* b;
+  uint8_t* d_chk;
+  int n_cells;
+  std::vector<double> mine, kept; /* fetch(): the slice state the run-time build left, and the kept half's */
+  size_t ss_bytes() const { return 8 * (size_t)b->S * n_cells; }
+  size_t sc_bytes() const { return sizeof(RsCellScalars) * (size_t)n_cells; }
+  size_t sc_off() const { return round_up((int)ss_bytes(), 256); }
+  size_t half() const { return sc_off() + round_up((int)sc_bytes(), 256); }
+  /* before the built-in kernel runs */
+  int save() const {
+    HIP_TRY(hipMemcpyAsync(d_chk, b->d_sstate, ss_bytes(), hipMemcpyDeviceToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(d_chk + sc_off(), b->d_scal, sc_bytes(), hipMemcpyDeviceToDevice, b->stream));
+    return RS_OK;
+  }
+  /* behind it: keep what it left, put back what it found -- the run-time build starts from the same state */
+  int keep_and_put_back() const {
+    HIP_TRY(hipMemcpyAsync(d_chk + half(), b->d_sstate, ss_bytes(), hipMemcpyDeviceToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(b->d_sstate, d_chk, ss_bytes(), hipMemcpyDeviceToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(b->d_scal, d_chk + sc_off(), sc_bytes(), hipMemcpyDeviceToDevice, b->stream));
+    return RS_OK;
+  }
+  /* the call has completed: both slice states to the host ... */
+  int fetch() {
+    mine.resize((size_t)b->S * n_cells);
+    kept.resize(mine.size());
+    HIP_TRY(hipMemcpy(mine.data(), b->d_sstate, ss_bytes(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(kept.data(), d_chk + half(), ss_bytes(), hipMemcpyDeviceToHost));
+    return RS_OK;
+  }
+  /* ... and cell `row`'s compared bit for bit; the first difference is the message, named as compare_out_block names a cell (`cell`) */
+  void compare(int row, int cell, char* what, size_t len) const {
+    char pre[24] = "";
+    if (cell >= 0) snprintf(pre, sizeof pre, "cell %d: ", cell);
+    for (int i = 0; i < b->S && !what[0]; i++) {
+      const double a = mine[(size_t)row * b->S + i], r = kept[(size_t)row * b->S + i];
+      if (to_bits(a) != to_bits(r)) snprintf(what, len, "%sslice state[%d] = %a, the built-in kernel's %a", pre, i, a, r);
+    }
+  }
+  /* the pair is dropped: the call leaves the built-in kernel's state */
+  int restore_kept() const {
+    HIP_TRY(hipMemcpy(b->d_sstate, d_chk + half(), ss_bytes(), hipMemcpyDeviceToDevice));
+    return RS_OK;
+  }
+};
+
+/* the drop-in switches of the environment, read when a context or a group is created */
+struct DropinEnv {
+  bool force_copy, timing, poll; /* RS_DROPIN_COPY=1, RS_DROPIN_TIMING=1, not RS_DROPIN_POLL=0 */
+  long poll_us;                  /* RS_DROPIN_POLL_US, default 2 000 */
+};
+DropinEnv dropin_env() {
+  auto is = [](const char* name, char v) { const char* e = getenv(name); return e && e[0] == v; };
+  DropinEnv env = {is("RS_DROPIN_COPY", '1'), is("RS_DROPIN_TIMING", '1'), !is("RS_DROPIN_POLL", '0'), 2000};
+  if (const char* pu = getenv("RS_DROPIN_POLL_US")) env.poll_us = atol(pu) > 0 ? atol(pu) : 2000;
+  return env;
+}
 }  // namespace
 
 extern "C" {
@@ -2221,12 +2373,7 @@ int rs_ctx_debug_heap_sorts(rs_ctx* ctx, int64_t* out) {
 }
 
 rs_ctx* rs_create_checked(const rs_config* cfg, int abi_version, size_t cfg_size) {
-  if (abi_version != RS_ABI_VERSION || cfg_size != sizeof(rs_config)) {
-    fail(RS_ERR_INVALID, "ABI mismatch: caller was built against ABI %d with an rs_config of %zu bytes, this library is ABI %d with %zu bytes",
-         abi_version, cfg_size, RS_ABI_VERSION, sizeof(rs_config));
-    return nullptr;
-  }
-  return rs_create(cfg);
+  return abi_matches(abi_version, cfg_size, sizeof(rs_config), "rs_config") ? rs_create(cfg) : nullptr;
 }
 
 rs_ctx* rs_create(const rs_config* cfg) {
@@ -2246,14 +2393,13 @@ rs_ctx* rs_create(const rs_config* cfg) {
   c->flag_off = round_up(l.out_total, 64);
   c->out_bytes = c->flag_off + 64;
   const size_t img_bytes = round_up(rs_upad_of(b->U) * b->R, 16);
-  const size_t chk_bytes = round_up(8 * b->S, 256) + round_up((int)sizeof(RsCellScalars), 256);
   bool ok = hipMalloc(&c->d_in, c->in_bytes) == hipSuccess && hipMalloc(&c->d_out, c->out_bytes) == hipSuccess &&
             hipMalloc(&c->d_img, img_bytes) == hipSuccess && hipMalloc(&c->d_out2, c->out_bytes) == hipSuccess &&
-            hipMalloc(&c->d_chk, 2 * chk_bytes) == hipSuccess &&
+            hipMalloc(&c->d_chk, 2 * TwinState{b, nullptr, 1}.half()) == hipSuccess &&
             hipHostMalloc((void**)&c->h_in, c->in_bytes, hipHostMallocMapped) == hipSuccess &&
             hipHostMalloc((void**)&c->h_out, c->out_bytes, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
-  const char* force_copy = getenv("RS_DROPIN_COPY");
-  if (ok && !(force_copy && force_copy[0] == '1')) {
+  const DropinEnv env = dropin_env();
+  if (ok && !env.force_copy) {
     void *zi = nullptr, *zo = nullptr;
     if (hipHostGetDevicePointer(&zi, c->h_in, 0) == hipSuccess && hipHostGetDevicePointer(&zo, c->h_out, 0) == hipSuccess) {
       c->z_in = (uint8_t*)zi;
@@ -2261,11 +2407,9 @@ rs_ctx* rs_create(const rs_config* cfg) {
     }
   }
   if (!ok) { fail(RS_ERR_HIP, "allocation of the staging blocks failed"); rs_destroy(c); return nullptr; }
-  const char* tm = getenv("RS_DROPIN_TIMING");
-  c->timing = tm && tm[0] == '1';
-  const char* pl = getenv("RS_DROPIN_POLL");
-  c->poll = c->z_out != nullptr && !(pl && pl[0] == '0');
-  if (const char* pu = getenv("RS_DROPIN_POLL_US")) c->poll_us = atol(pu) > 0 ? atol(pu) : 2000;
+  c->timing = env.timing;
+  c->poll = c->z_out != nullptr && env.poll;
+  c->poll_us = env.poll_us;
   if (c->h_out) memset(c->h_out + c->flag_off, 0, 64);
   c->h_out2.assign(c->out_bytes, 0);
   g_err[0] = 0;
@@ -2309,41 +2453,54 @@ void rs_destroy(rs_ctx* c) {
   delete c;
 }
 
-int rs_schedule_tti(rs_ctx* c, const rs_tti_in* in, rs_tti_out* out) {
-  if (!c || !in || !out) return fail(RS_ERR_INVALID, "null argument");
-  rs_batch* b = c->b;
-  using clk = std::chrono::steady_clock;
-  const clk::time_point t0 = c->timing ? clk::now() : clk::time_point();
-  HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  const int n = in->n_users, R = b->R, S = b->S;
-  /* rs_tti_in.cqi_epoch: the same reports for the same users as the call before?  Then the caller's block is not touched -- the kernel
-   * reads the image the context kept on the device (and, per-PRB reports, the device copy of the block) */
-  const bool same_users = c->img_valid && c->img_n == n && c->img_has_ids == (in->user_id != nullptr) &&
-                          (!in->user_id || memcmp(c->img_ids.data(), in->user_id, 4 * (size_t)n) == 0);
-  const bool reuse_grid = in->cqi_epoch != 0 && same_users && in->cqi_epoch == c->img_epoch && c->img_prb == (in->cqi_prb != nullptr);
-  const int image_mode = in->cqi_epoch == 0 ? 0 : (reuse_grid ? 2 : 1);
+namespace {
+/* One context call: what the caller gave, then what the phases of rs_schedule_tti decide along the way.  (The phases are static:
+ * inside extern "C" the unnamed namespace alone would not keep their names out of the library's exports.) */
+struct CtxCall {
+  const rs_tti_in* in;
+  rs_tti_out* out;
+  /* ctx_pack: RsLaunch::image_mode of the call, what pack_tti left for the launch */
+  int image_mode;
   TtiPack pk;
-  const int pack_rc = pack_tti(b, in, out, c->h_in, reuse_grid, &pk);
-  if (pk.grid_touched) c->img_valid = false; /* (until this call has gone through) */
-  if (pack_rc) return pack_rc;
-  const CtxLayout& l = pk.l;
-  const size_t in_bytes = pk.in_bytes;
-  const bool exact_scan = pk.exact_scan;
-  const int32_t* const gate = pk.gate;
-  hipStream_t st = b->stream;
-  const clk::time_point t1 = c->timing ? clk::now() : clk::time_point();
-  /* per-PRB reports and queue state are read again and again inside the TTI: those calls keep the device copies */
-  const bool zc = c->z_in != nullptr && !in->cqi_prb && !b->any_alpha;
-  uint8_t* const dev_in = zc ? c->z_in : c->d_in;
-  uint8_t* const dev_out = zc ? c->z_out : c->d_out;
-  if (!zc) {
-    /* (an unchanged report set: the grid and the per-PRB block are on the device already; the per-call words lie between them) */
-    if (reuse_grid) HIP_TRY(hipMemcpyAsync(c->d_in + l.slice, c->h_in + l.slice, l.prb - l.slice, hipMemcpyHostToDevice, st));
-    else HIP_TRY(hipMemcpyAsync(c->d_in, c->h_in, in_bytes, hipMemcpyHostToDevice, st));
-  }
-  RsLaunch L = b->base;
-  L.U = n;
-  L.Upad = upad_of(n);
+  /* rs_schedule_tti: the kernel reads and writes the pinned blocks in place; the caller wants UpperBound's lists.  ctx_run: completion
+   * by the polled word; the run-time build that serves the call (null: the built-in kernel; which: 0 general, 1 lean) and whether the
+   * built-in kernel ran beside it */
+  bool zc, want_upper, poll, checked;
+  RsJitKernel* kd;
+  int which;
+};
+
+/* The call's image mode -- the same reports for the same users as the call before?  then the caller's block is not touched -- and its
+ * input block.  Writes c->h_in.  The image's term ends as soon as the block's grid area was written (also when pack_tti then refuses
+ * the call) and begins again when this call has gone through (ctx_commit_image). */
+static int ctx_pack(rs_ctx* c, CtxCall& call) {
+  call.image_mode = c->img.mode(*call.in, call.in->cqi_prb != nullptr, call.in->cqi_epoch);
+  const int rc = pack_tti(c->b, call.in, call.out, c->h_in, call.image_mode == 2, &call.pk);
+  if (call.pk.grid_touched) c->img.valid = false;
+  return rc;
+}
+
+/* a launch block's output pointers: into one output block of layout l */
+static void ctx_point_outputs(RsLaunch* L, uint8_t* out, const CtxLayout& l, bool want_upper) {
+  L->log_tbs = (int32_t*)(out + l.tbs);
+  L->log_uinfo = (int32_t*)(out + l.uinfo);
+  L->log_map = (int16_t*)(out + l.map);
+  L->log_quota = (int16_t*)(out + l.quota);
+  L->log_target = (int16_t*)(out + l.target);
+  L->log_upper = want_upper ? (int32_t*)(out + l.upper) : nullptr;
+}
+
+/* the call's launch block: the config's, then the call's input and output block.  (Direct mode: the kernel clears its per-user outputs
+ * itself and reads the single grid on every call.) */
+static void ctx_fill_launch(const rs_ctx* c, const CtxCall& call, RsLaunch* launch) {
+  const rs_batch* b = c->b;
+  const rs_tti_in* in = call.in;
+  const CtxLayout& l = call.pk.l;
+  uint8_t* const dev_in = call.zc ? c->z_in : c->d_in;
+  RsLaunch& L = *launch;
+  L = b->base;
+  L.U = in->n_users;
+  L.Upad = upad_of(in->n_users);
   L.n_ttis = 1;
   L.direct = 1;
   L.rand0 = in->rand0;
@@ -2357,112 +2514,134 @@ int rs_schedule_tti(rs_ctx* c, const rs_tti_in* in, rs_tti_out* out) {
   L.avg = (double*)(dev_in + l.avg);
   L.prb_cqi = in->cqi_prb ? dev_in + l.prb : nullptr;
   L.grid_image = c->d_img;
-  L.image_mode = image_mode;
+  L.image_mode = call.image_mode;
   L.queue_mode = b->any_alpha ? 1 : 0;
   L.hol = (const double*)(dev_in + l.hol);
   L.prio = dev_in + l.prio;
   L.draws = dev_in + l.draws;
-  L.gate = gate ? (const int32_t*)(dev_in + l.gate) : nullptr;
-  L.exact_scan = exact_scan ? 1 : 0;
+  L.gate = call.pk.gate ? (const int32_t*)(dev_in + l.gate) : nullptr;
+  L.exact_scan = call.pk.exact_scan ? 1 : 0;
   L.gen_exp = b->gen_exp ? 1 : 0;
   L.gen_num = b->d_gen_num;
-  if (b->sched == RS_SCHED_PF) { L.n_seg = (n + RS_PF_SEG - 1) / RS_PF_SEG; L.n_items = R * L.n_seg; }
-  L.log_tbs = (int32_t*)(dev_out + l.tbs);
-  L.log_uinfo = (int32_t*)(dev_out + l.uinfo);
-  L.log_map = (int16_t*)(dev_out + l.map);
-  L.log_quota = (int16_t*)(dev_out + l.quota);
-  L.log_target = (int16_t*)(dev_out + l.target);
-  const bool want_upper = b->sched == RS_SCHED_UPPERBOUND && (out->upper_rbg || out->upper_user);
-  L.log_upper = want_upper ? (int32_t*)(dev_out + l.upper) : nullptr;
-  /* direct mode: the kernel clears its per-user outputs itself and reads the single grid on every call */
-  /* rs_ctx_specialize: this context's own build of the one-TTI kernel -- its lean form for the plain call (per-RBG CQI, no customised
-   * slices, no gates, exponents in {0, 1}, every input inside the FP32 filter's range), the general one otherwise */
-  RsJitKernel* kd = b->jit;
-  int which = 0; /* 0: general build, 1: lean build */
-  if (b->jit_lean && !L.prb_cqi && !L.queue_mode && !L.gate && !L.exact_scan && !L.gen_exp && !L.log_upper && !L.synthetic) { kd = b->jit_lean; which = 1; }
-  /* A run-time build that does not carry the self-check mark serves its first calls beside the built-in kernel (rs_ctx_jit_status):
-   * same inputs, same slice state; every output field and the slice state left behind must agree. */
-  const bool checked_call = kd != nullptr && c->chk_left[which] > 0;
-  const size_t sstate_bytes = 8 * (size_t)S, chk_half = round_up((int)sstate_bytes, 256) + round_up((int)sizeof(RsCellScalars), 256);
-  if (checked_call) {
-    uint8_t* const before = c->d_chk;
-    uint8_t* const after = c->d_chk + chk_half;
-    HIP_TRY(hipMemcpyAsync(before, b->d_sstate, sstate_bytes, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(before + round_up((int)sstate_bytes, 256), b->d_scal, sizeof(RsCellScalars), hipMemcpyDeviceToDevice, st));
-    RsLaunch Lb = L; /* the built-in kernel, its outputs into a block of its own */
-    Lb.log_tbs = (int32_t*)(c->d_out2 + l.tbs);
-    Lb.log_uinfo = (int32_t*)(c->d_out2 + l.uinfo);
-    Lb.log_map = (int16_t*)(c->d_out2 + l.map);
-    Lb.log_quota = (int16_t*)(c->d_out2 + l.quota);
-    Lb.log_target = (int16_t*)(c->d_out2 + l.target);
-    Lb.log_upper = want_upper ? (int32_t*)(c->d_out2 + l.upper) : nullptr;
-    Lb.done_flag = nullptr;
-    HIP_TRY(rs_launch_cells(&Lb, b->threads, st));
-    HIP_TRY(hipMemcpyAsync(c->h_out2.data(), c->d_out2, l.out_total, hipMemcpyDeviceToHost, st));
-    /* keep what it left, put back what it found: the specialised kernel starts from the same state */
-    HIP_TRY(hipMemcpyAsync(after, b->d_sstate, sstate_bytes, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(b->d_sstate, before, sstate_bytes, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(b->d_scal, before + round_up((int)sstate_bytes, 256), sizeof(RsCellScalars), hipMemcpyDeviceToDevice, st));
-    /* (a call with new reports: BOTH kernels transpose the caller's block and store the image -- the same bytes when the build is right;
-     * a wrong image would show in the checked calls that read it) */
+  if (b->sched == RS_SCHED_PF) { L.n_seg = (in->n_users + RS_PF_SEG - 1) / RS_PF_SEG; L.n_items = b->R * L.n_seg; }
+  ctx_point_outputs(&L, call.zc ? c->z_out : c->d_out, l, call.want_upper);
+}
+
+/* A checked call: the built-in kernel first, on the same inputs and the same slice state, its outputs into a block of its own.  (A call
+ * with new reports: BOTH kernels transpose the caller's block and store the image -- the same bytes when the build is right; a wrong
+ * image would show in the checked calls that read it.) */
+static int ctx_run_twin(rs_ctx* c, const CtxCall& call, const RsLaunch& L) {
+  rs_batch* b = c->b;
+  const TwinState tw{b, c->d_chk, 1};
+  if (const int rc = tw.save()) return rc;
+  RsLaunch Lb = L;
+  ctx_point_outputs(&Lb, c->d_out2, call.pk.l, call.want_upper);
+  Lb.done_flag = nullptr;
+  HIP_TRY(rs_launch_cells(&Lb, b->threads, b->stream));
+  HIP_TRY(hipMemcpyAsync(c->h_out2.data(), c->d_out2, call.pk.l.out_total, hipMemcpyDeviceToHost, b->stream));
+  return tw.keep_and_put_back();
+}
+
+/* The copies in, the launch, the copy back.  rs_ctx_specialize: this context's own build of the one-TTI kernel serves the call -- its
+ * lean form the plain call (per-RBG CQI, no customised slices, no gates, exponents in {0, 1}, every input inside the FP32 filter's
+ * range), the general one every other.  A build that does not carry the self-check mark serves its first calls beside the built-in
+ * kernel (rs_ctx_jit_status): same inputs, same slice state; every output field and the slice state left behind must agree. */
+static int ctx_run(rs_ctx* c, CtxCall& call, RsLaunch& L) {
+  rs_batch* b = c->b;
+  hipStream_t st = b->stream;
+  const CtxLayout& l = call.pk.l;
+  if (!call.zc) {
+    /* (an unchanged report set: the grid and the per-PRB block are on the device already; the per-call words lie between them) */
+    if (call.image_mode == 2) HIP_TRY(hipMemcpyAsync(c->d_in + l.slice, c->h_in + l.slice, l.prb - l.slice, hipMemcpyHostToDevice, st));
+    else HIP_TRY(hipMemcpyAsync(c->d_in, c->h_in, call.pk.in_bytes, hipMemcpyHostToDevice, st));
   }
-  const bool poll = zc && c->poll && !checked_call;
-  if (poll) {
+  const JitPair& p = c->pair;
+  const bool lean = p.jit[1] && !L.prb_cqi && !L.queue_mode && !L.gate && !L.exact_scan && !L.gen_exp && !L.log_upper && !L.synthetic;
+  call.which = lean ? 1 : 0;
+  call.kd = p.jit[call.which];
+  call.checked = call.kd != nullptr && p.chk_left[call.which] > 0;
+  if (call.checked)
+    if (const int rc = ctx_run_twin(c, call, L)) return rc;
+  call.poll = call.zc && c->poll && !call.checked;
+  if (call.poll) {
     if (++c->seq == 0) c->seq = 1; /* (0 is the word's initial value) */
     L.done_flag = (uint32_t*)(c->z_out + c->flag_off);
     L.done_seq = c->seq;
   }
-  if (kd) HIP_TRY(rs_jit_launch(kd, &L, st));
+  if (call.kd) HIP_TRY(rs_jit_launch(call.kd, &L, st));
   else HIP_TRY(rs_launch_cells(&L, b->threads, st));
-  if (!zc) HIP_TRY(hipMemcpyAsync(c->h_out, c->d_out, l.out_total, hipMemcpyDeviceToHost, st));
-  const clk::time_point t2 = c->timing ? clk::now() : clk::time_point();
+  if (!call.zc) HIP_TRY(hipMemcpyAsync(c->h_out, c->d_out, l.out_total, hipMemcpyDeviceToHost, st));
+  return RS_OK;
+}
+
+/* by the polled word (the kernel's last store), else by the stream */
+static int ctx_wait(rs_ctx* c, const CtxCall& call) {
   bool seen = false;
-  if (poll) {
-    seen = poll_done_word(c->h_out + c->flag_off, c->seq, c->poll_us, &c->n_polled, st);
+  if (call.poll) {
+    seen = poll_done_word(c->h_out + c->flag_off, c->seq, c->poll_us, &c->n_polled, c->b->stream);
     if (!seen) c->n_fallback++; /* (a context counts the polled calls that fell back, not every stream wait) */
   }
-  if (!seen) HIP_TRY(hipStreamSynchronize(st));
-  if (checked_call) {
-    /* field by field: the first difference is the message */
-    std::vector<double> ss_jit(S), ss_ref(S);
-    HIP_TRY(hipMemcpy(ss_jit.data(), b->d_sstate, sstate_bytes, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(ss_ref.data(), c->d_chk + chk_half, sstate_bytes, hipMemcpyDeviceToHost));
-    const uint8_t* const hr = c->h_out2.data();
-    char what[200] = "";
-    compare_out_block(c->h_out, hr, l, R, S, n, want_upper, -1, what, sizeof what);
-    for (int i = 0; i < S && !what[0]; i++)
-      if (to_bits(ss_jit[i]) != to_bits(ss_ref[i])) snprintf(what, sizeof what, "slice state[%d] = %a, the built-in kernel's %a", i, ss_jit[i], ss_ref[i]);
-    if (what[0]) {
-      /* the build is wrong: drop it (and its cache file), serve this call and all later ones from the built-in kernel */
-      rs_jit_reject(kd);
-      if (b->jit && b->jit != kd) rs_jit_reject(b->jit); /* (one wrong build of a shape: neither is trusted) */
-      if (b->jit_lean && b->jit_lean != kd) rs_jit_reject(b->jit_lean);
-      b->jit = nullptr;
-      b->jit_lean = nullptr;
-      c->jit_dropped = true;
-      c->chk_left[0] = c->chk_left[1] = 0;
-      memcpy(c->h_out, hr, l.out_total);
-      HIP_TRY(hipMemcpy(b->d_sstate, c->d_chk + chk_half, sstate_bytes, hipMemcpyDeviceToDevice));
-      snprintf(c->jit_msg, sizeof c->jit_msg, "self-check of the specialised %s build, checked call %d: %s; the build is dropped, the built-in kernel serves this "
-               "context (lint the code object: tools/lint_exec_restore.py)", which ? "lean" : "general", c->chk_agreed[which] + 1, what);
-      snprintf(g_err, sizeof g_err, "%s", c->jit_msg);
-    } else {
-      c->chk_agreed[which]++;
-      if (--c->chk_left[which] == 0) rs_jit_mark_verified(kd);
-    }
+  if (!seen) HIP_TRY(hipStreamSynchronize(c->b->stream));
+  return RS_OK;
+}
+
+/* A checked call's end: every output field and the slice state left behind against the built-in kernel's, field by field -- the first
+ * difference is the message.  Then the build is wrong: both are dropped (and their cache files), this call returns the built-in
+ * kernel's outputs and leaves its state, all later ones run the built-in kernel. */
+static int ctx_check(rs_ctx* c, const CtxCall& call) {
+  const rs_batch* b = c->b;
+  JitPair& p = c->pair;
+  TwinState tw{c->b, c->d_chk, 1};
+  if (const int rc = tw.fetch()) return rc;
+  char what[200] = "";
+  compare_out_block(c->h_out, c->h_out2.data(), call.pk.l, b->R, b->S, call.in->n_users, call.want_upper, -1, what, sizeof what);
+  tw.compare(0, -1, what, sizeof what);
+  if (!what[0]) {
+    jit_pair_agreed(&p, call.which);
+    return RS_OK;
   }
-  if (image_mode != 0) {
-    /* the device holds this call's reports now */
-    c->img_valid = true;
-    c->img_epoch = in->cqi_epoch;
-    c->img_n = n;
-    c->img_prb = in->cqi_prb != nullptr;
-    c->img_has_ids = in->user_id != nullptr;
-    if (in->user_id && !reuse_grid) c->img_ids.assign(in->user_id, in->user_id + n);
-    if (reuse_grid) c->n_img_reused++;
+  jit_pair_drop(&p);
+  memcpy(c->h_out, c->h_out2.data(), call.pk.l.out_total);
+  if (const int rc = tw.restore_kept()) return rc;
+  snprintf(p.msg, sizeof p.msg, "self-check of the specialised %s build, checked call %d: %s; the build is dropped, the built-in kernel serves this "
+           "context (lint the code object: tools/lint_exec_restore.py)", call.which ? "lean" : "general", p.chk_agreed[call.which] + 1, what);
+  snprintf(g_err, sizeof g_err, "%s", p.msg);
+  return RS_OK;
+}
+
+/* the call has gone through under a number: the device holds its reports now */
+static void ctx_commit_image(rs_ctx* c, const CtxCall& call) {
+  if (call.image_mode == 1) c->img.stored(*call.in, call.in->cqi_prb != nullptr);
+  if (call.image_mode == 2) {
+    c->img.valid = true;
+    c->n_img_reused++;
   }
+}
+}  // namespace
+
+/* one context call, phase by phase; RS_DROPIN_TIMING splits it into prepare, enqueue, wait and unpack */
+int rs_schedule_tti(rs_ctx* c, const rs_tti_in* in, rs_tti_out* out) {
+  if (!c || !in || !out) return fail(RS_ERR_INVALID, "null argument");
+  rs_batch* b = c->b;
+  using clk = std::chrono::steady_clock;
+  const clk::time_point t0 = c->timing ? clk::now() : clk::time_point();
+  HIP_TRY(hipSetDevice(b->cfg.cell.device));
+  CtxCall call = {in, out};
+  int rc = ctx_pack(c, call);
+  if (rc) return rc;
+  const clk::time_point t1 = c->timing ? clk::now() : clk::time_point();
+  /* per-PRB reports and queue state are read again and again inside the TTI: those calls keep the device copies */
+  call.zc = c->z_in != nullptr && !in->cqi_prb && !b->any_alpha;
+  call.want_upper = b->sched == RS_SCHED_UPPERBOUND && (out->upper_rbg || out->upper_user);
+  RsLaunch L;
+  ctx_fill_launch(c, call, &L);
+  if ((rc = ctx_run(c, call, L))) return rc;
+  const clk::time_point t2 = c->timing ? clk::now() : clk::time_point();
+  if ((rc = ctx_wait(c, call))) return rc;
+  if (call.checked && (rc = ctx_check(c, call))) return rc;
+  ctx_commit_image(c, call);
   const clk::time_point t3 = c->timing ? clk::now() : clk::time_point();
-  unpack_tti(b, in, out, c->h_out, l, want_upper);
+  unpack_tti(b, in, out, c->h_out, call.pk.l, call.want_upper);
   if (c->timing) {
     const clk::time_point t4 = clk::now();
     auto us = [](clk::time_point a, clk::time_point b2) { return std::chrono::duration<double, std::micro>(b2 - a).count(); };
@@ -2476,51 +2655,22 @@ int rs_schedule_tti(rs_ctx* c, const rs_tti_in* in, rs_tti_out* out) {
 }
 
 /* Shape specialisation of a drop-in context (round 4): the one-TTI kernel compiled for this context's slices, RBGs, PRBs per RBG,
- * scheduler and user CAPACITY (the LDS carve), the users of a call staying a launch argument.  About two seconds per shape and
- * process (cached); results are identical.  On failure the context keeps the kernels built into the library. */
+ * scheduler and user CAPACITY (the LDS carve), the users of a call staying a launch argument, in a general and a lean build (the
+ * per-call options of the plain call as constants).  About two seconds per shape and process (cached); results are identical.  On
+ * failure the context keeps the kernels built into the library. */
 int rs_ctx_specialize(rs_ctx* c) {
   if (!c) return fail(RS_ERR_INVALID, "null context");
-  rs_batch* b = c->b;
-  if (b->jit) return RS_OK;
-  if (c->jit_dropped) return fail(RS_ERR_STATE, "%s", c->jit_msg);
-  HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  const bool gate_scratch = b->sched == RS_SCHED_PF || b->sched == RS_SCHED_NVS;
-  b->jit_wanted = true;
-  b->jit = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, gate_scratch ? 1 : 0, 0, b->jit_msg, sizeof b->jit_msg, 1);
-  if (!b->jit) {
-    snprintf(c->jit_msg, sizeof c->jit_msg, "%s", b->jit_msg[0] ? b->jit_msg : "hiprtc build failed");
-    return fail(RS_ERR_HIP, "%s", c->jit_msg);
-  }
-  b->jit_msg[0] = 0;
-  c->jit_msg[0] = 0;
-  /* ... and its lean form (the per-call options of the plain call as constants); without it the general build serves every call */
-  const char* const e_on = getenv("RS_JIT_LEAN");
-  if (!e_on || atoi(e_on) != 0) {
-    char msg[512] = "";
-    b->jit_lean = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, gate_scratch ? 1 : 0, 0, msg, sizeof msg, 1 | 4);
-  }
-  c->chk_agreed[0] = c->chk_agreed[1] = 0;
-  c->chk_left[0] = selfcheck_calls(b->jit);
-  c->chk_left[1] = selfcheck_calls(b->jit_lean);
-  return RS_OK;
+  if (c->pair.jit[0]) return RS_OK;
+  if (c->pair.dropped) return fail(RS_ERR_STATE, "%s", c->pair.msg);
+  HIP_TRY(hipSetDevice(c->b->cfg.cell.device));
+  return jit_pair_build(&c->pair, c->b, 1); /* (1: the one-TTI form) */
 }
 
 int rs_ctx_jit_status(rs_ctx* c, char* msg, size_t msglen) {
   if (!c) return fail(RS_ERR_INVALID, "null context");
-  rs_batch* b = c->b;
-  if (msg && msglen) {
-    if (c->jit_dropped || !b->jit) {
-      snprintf(msg, msglen, "%s", c->jit_msg);
-    } else {
-      char g[160], l[160];
-      selfcheck_state(b->jit, c->chk_left[0], c->chk_agreed[0], "the built-in kernel field by field", g, sizeof g);
-      selfcheck_state(b->jit_lean, c->chk_left[1], c->chk_agreed[1], "the built-in kernel field by field", l, sizeof l);
-      snprintf(msg, msglen, "general build: %s; lean build: %s", g, l);
-    }
-  }
-  if (c->jit_dropped) return -2;
-  return b->jit ? 1 : (b->jit_wanted ? -1 : 0);
+  return jit_pair_status(c->pair, "the built-in kernel field by field", msg, msglen);
 }
+
 
 int rs_get_slice_offset(rs_ctx* c, double* offset) {
   if (!c || !offset) return fail(RS_ERR_INVALID, "null argument");
@@ -2633,18 +2783,12 @@ struct rs_group {
   /* rs_tti_in.cqi_epoch, per CELL (not per call slot): the grid of the cell's last call under a non-zero number, kept on the device as
    * the LDS image ([R][Upad of that call's n], d_img: [n_cells][img_stride]), its per-PRB block beside it when that call gave one
    * (d_prb: [n_cells][prb_stride], allocated by the first call that needs it), and the record that decides whether a later call may
-   * be served from them -- rs_ctx's rules (rs_schedule_tti).  A record changes only after its launch has completed.
+   * be served from them (CqiImage).  A record changes only after its launch has completed.
    * RS_GROUP_IMAGE=0 (read at create): every cqi_epoch counts as 0. */
-  struct CellImage {
-    bool valid = false, prb = false, has_ids = false;
-    uint64_t epoch = 0;
-    int n = 0;
-    std::vector<int32_t> ids;
-  };
   bool image_on = true, prb_store_failed = false;
   uint8_t *d_img = nullptr, *d_prb = nullptr;
   size_t img_stride = 0, prb_stride = 0;
-  std::vector<CellImage> img;
+  std::vector<CqiImage> img;
   std::vector<uint8_t> modes;  /* per call slot: RsGroupCell::image_mode of the call being served */
   int64_t n_reused = 0, n_stored = 0, n_plain = 0; /* cell-TTIs of successful calls in mode 2 / 1 / 0 (rs_group_image_stats) */
   /* RS_DROPIN_TIMING=1: the host-side split of the calls, printed by rs_group_destroy */
@@ -2653,21 +2797,14 @@ struct rs_group {
   long n_calls = 0, n_cell_ttis = 0, n_polled = 0, n_fallback = 0;
   /* Run-time builds of a group call's kernel (rs_group_specialize, rs_group_specialize_resident, rs_group_specialize_queued,
    * rs_group_specialize_flows, rs_group_specialize_counted, rs_group_specialize_run): one pair
-   * of builds per form (index 0: general build, 1: lean build for the plain call), and their check against the form's
-   * built-in kernel -- calls still to be checked, calls that agreed so far (rs_ctx's scheme).  The six pairs are independent: each
+   * of builds per form (JitPair), checked against the form's built-in kernel.  The six pairs are independent: each
    * serves its own kind of call, is checked against its own built-in kernel and is dropped alone.  The check of a form with stores
-   * (kGroupForms) also compares those: d_stores_chk holds them before the built-in kernel ran and as that kernel left them (two halves,
-   * group_copy_stores). */
-  struct GroupPair {
-    RsJitKernel* jit[2] = {nullptr, nullptr};
-    bool wanted = false, dropped = false;
-    int chk_left[2] = {0, 0}, chk_agreed[2] = {0, 0};
-    uint8_t* d_stores_chk = nullptr;
-    char msg[512] = "";
-  };
-  GroupPair pair[RS_GROUP_RUN + 1]; /* by GroupForm::pair: every form's but the counted run's, which has no run-time builds */
+   * (kGroupForms) also compares those: the pair's d_stores_chk holds them before the built-in kernel ran and as that kernel left them
+   * (two halves, group_copy_stores). */
+  JitPair pair[RS_GROUP_RUN + 1]; /* by GroupForm::pair: every form's but the counted run's, which has no run-time builds */
+  uint8_t* d_stores_chk[RS_GROUP_RUN + 1] = {};
   /* every pair's: the built-in kernel's output slots (out_slots of them, as d_out: group_grow_out grows both for a run); the group's
-   * slice state + scalars before / after it */
+   * slice state + scalars before / after it (TwinState) */
   uint8_t *d_out2 = nullptr, *d_chk = nullptr;
   std::vector<uint8_t> h_out2;
   /* Resident cells.  A cell is resident in one form at a time (GroupCellState: cells[cell] -- the form, whether the form's counters
@@ -2745,9 +2882,6 @@ const GroupForm kGroupForms[RS_GROUP_FORMS] = {
 };
 unsigned GroupForm::sets() const { return rs_group_form((int)(this - kGroupForms)).sets; }
 
-/* bytes of one half of rs_group::d_chk: [n_cells][S] slice state, then [n_cells] RsCellScalars */
-size_t group_chk_sstate(const rs_group* g) { return round_up((int)(8 * (size_t)g->b->S * g->n_cells), 256); }
-size_t group_chk_half(const rs_group* g) { return group_chk_sstate(g) + round_up((int)(sizeof(RsCellScalars) * (size_t)g->n_cells), 256); }
 
 /* The device stores of the resident forms, one row each, by GroupStoreId: [n_cells][elements per cell] of one element kind.  A family
  * is allocated together, all or none, by the first setter that needs it (group_alloc_family); rs_group_destroy, the setters' and
@@ -2819,7 +2953,7 @@ bool group_alloc_family(rs_group* g, int fam) {
 }
 
 /* The stores that a form's self-check saves, restores and compares -- rows of kGroupStores, in the order they lie in a half of
- * GroupPair::d_stores_chk (each rounded up to 256 bytes): the averages, the cells' last-update times, the pending bytes. */
+ * rs_group::d_stores_chk[its pair] (each rounded up to 256 bytes): the averages, the cells' last-update times, the pending bytes. */
 struct GroupStores {
   const int* row;
   int n;       /* 0, 3, or 5: a form that keeps counters (RS_GROUP_SET_COUNTERS) has m_cumulateBytes / m_cumulateRBs behind the other three */
@@ -2834,7 +2968,7 @@ GroupStores group_stores(const rs_group* g, const GroupForm& f) {
 /* a form's stores to (save) or from one half of its pair's check block */
 hipError_t group_copy_stores(const rs_group* g, const GroupForm& f, int half, bool save) {
   const GroupStores s = group_stores(g, f);
-  uint8_t* kept = s.n ? g->pair[f.pair].d_stores_chk + (size_t)half * s.half : nullptr;
+  uint8_t* kept = s.n ? g->d_stores_chk[f.pair] + (size_t)half * s.half : nullptr;
   for (int i = 0; i < s.n; kept += kGroupStores[s.row[i++]].kept(g)) {
     void* const dev = g->store[s.row[i]];
     const hipError_t e = hipMemcpyAsync(save ? (void*)kept : dev, save ? dev : (void*)kept, kGroupStores[s.row[i]].bytes(g), hipMemcpyDeviceToDevice, g->b->stream);
@@ -2845,12 +2979,7 @@ hipError_t group_copy_stores(const rs_group* g, const GroupForm& f, int half, bo
 }  // namespace
 
 rs_group* rs_group_create_checked(const rs_config* cfg, int32_t n_cells, int abi_version, size_t cfg_size) {
-  if (abi_version != RS_ABI_VERSION || cfg_size != sizeof(rs_config)) {
-    fail(RS_ERR_INVALID, "ABI mismatch: caller was built against ABI %d with an rs_config of %zu bytes, this library is ABI %d with %zu bytes",
-         abi_version, cfg_size, RS_ABI_VERSION, sizeof(rs_config));
-    return nullptr;
-  }
-  return rs_group_create(cfg, n_cells);
+  return abi_matches(abi_version, cfg_size, sizeof(rs_config), "rs_config") ? rs_group_create(cfg, n_cells) : nullptr;
 }
 
 rs_group* rs_group_create(const rs_config* cfg, int32_t n_cells) {
@@ -2891,8 +3020,8 @@ rs_group* rs_group_create(const rs_config* cfg, int32_t n_cells) {
                   hipHostMalloc((void**)&g->h_in, in_bytes, hipHostMallocMapped) == hipSuccess &&
                   hipHostMalloc((void**)&g->h_out, out_bytes, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
   if (!ok) { fail(RS_ERR_HIP, "allocation of the group's staging blocks failed (%zu + %zu bytes)", in_bytes, out_bytes); rs_group_destroy(g); return nullptr; }
-  const char* force_copy = getenv("RS_DROPIN_COPY");
-  if (!(force_copy && force_copy[0] == '1')) {
+  const DropinEnv env = dropin_env();
+  if (!env.force_copy) {
     void *zi = nullptr, *zo = nullptr;
     if (hipHostGetDevicePointer(&zi, g->h_in, 0) == hipSuccess && hipHostGetDevicePointer(&zo, g->h_out, 0) == hipSuccess) {
       g->z_in = (uint8_t*)zi;
@@ -2901,11 +3030,9 @@ rs_group* rs_group_create(const rs_config* cfg, int32_t n_cells) {
   }
   memset(g->h_in, 0, in_bytes);
   memset(g->h_out, 0, out_bytes);
-  const char* tm = getenv("RS_DROPIN_TIMING");
-  g->timing = tm && tm[0] == '1';
-  const char* pl = getenv("RS_DROPIN_POLL");
-  g->poll = g->z_out != nullptr && !(pl && pl[0] == '0');
-  if (const char* pu = getenv("RS_DROPIN_POLL_US")) g->poll_us = atol(pu) > 0 ? atol(pu) : 2000;
+  g->timing = env.timing;
+  g->poll = g->z_out != nullptr && env.poll;
+  g->poll_us = env.poll_us;
   g->named.assign(n_cells, 0);
   g->packs.resize(n_cells);
   const char* im = getenv("RS_GROUP_IMAGE");
@@ -2935,8 +3062,8 @@ void rs_group_destroy(rs_group* g) {
   if (g->b && g->b->stream) (void)hipStreamSynchronize(g->b->stream);
   for (void* q : {(void*)g->d_in, (void*)g->d_out, (void*)g->d_count, (void*)g->d_img, (void*)g->d_prb, (void*)g->d_out2, (void*)g->d_chk, (void*)g->d_recs})
     if (q) (void)hipFree(q);
-  for (const rs_group::GroupPair& p : g->pair)
-    if (p.d_stores_chk) (void)hipFree(p.d_stores_chk);
+  for (void* q : g->d_stores_chk)
+    if (q) (void)hipFree(q);
   for (void* q : g->store) /* (the rows of kGroupStores) */
     if (q) (void)hipFree(q);
   for (GroupStaged* s : {&g->qin, &g->sent, &g->sent2}) s->release();
@@ -3330,15 +3457,10 @@ int group_pack_slots(rs_group* g, GroupCall& c) {
       group_fill_header(g, c, k, nullptr);
       continue;
     }
-    /* rs_tti_in.cqi_epoch, decided per cell as a context of its own would (rs_schedule_tti): the number, the user count, the user list
-     * and the kind of report of the cell's valid image -- then the caller's block is neither checked, copied nor read */
-    const rs_group::CellImage& im = g->img[cell];
+    /* rs_tti_in.cqi_epoch, decided per cell against the cell's record; without the switch or the per-PRB store no number counts */
     const uint64_t epoch = (g->image_on && !(c.has_prb && g->prb_store_failed)) ? in[k].cqi_epoch : 0;
-    const bool reuse_grid = epoch != 0 && im.valid && im.epoch == epoch && im.n == in[k].n_users && im.prb == c.has_prb &&
-                            im.has_ids == (in[k].user_id != nullptr) &&
-                            (!in[k].user_id || memcmp(im.ids.data(), in[k].user_id, 4 * (size_t)im.n) == 0);
-    g->modes[k] = (uint8_t)(epoch == 0 ? 0 : (reuse_grid ? 2 : 1));
-    int rc = pack_tti(b, &in[k], c.no_out ? nullptr : &c.out[c.at(k)], g->h_in + (size_t)k * g->in_stride + RS_GROUP_HDR_BYTES, reuse_grid, &pk, c.resident(), c.form == kGroupFlows);
+    g->modes[k] = (uint8_t)g->img[cell].mode(in[k], c.has_prb, epoch);
+    int rc = pack_tti(b, &in[k], c.no_out ? nullptr : &c.out[c.at(k)], g->h_in + (size_t)k * g->in_stride + RS_GROUP_HDR_BYTES, g->modes[k] == 2, &pk, c.resident(), c.form == kGroupFlows);
     if (rc) {
       char msg[sizeof g_err];
       snprintf(msg, sizeof msg, "%s", g_err);
@@ -3457,11 +3579,8 @@ int group_run_twin(rs_group* g, const GroupCall& c, const RsLaunch& L) {
   rs_batch* b = g->b;
   hipStream_t st = b->stream;
   const GroupForm& f = c.desc();
-  const size_t ss_all = 8 * (size_t)b->S * g->n_cells, sc_all = sizeof(RsCellScalars) * (size_t)g->n_cells;
-  uint8_t* const before = g->d_chk;
-  uint8_t* const after = g->d_chk + group_chk_half(g);
-  HIP_TRY(hipMemcpyAsync(before, b->d_sstate, ss_all, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(before + group_chk_sstate(g), b->d_scal, sc_all, hipMemcpyDeviceToDevice, st));
+  const TwinState tw{g->b, g->d_chk, g->n_cells}; /* (every cell of the group, named or not) */
+  if (const int rc = tw.save()) return rc;
   HIP_TRY(group_copy_stores(g, f, 0, true));
   RsLaunch Lb = L;
   Lb.grp_out = g->d_out2;
@@ -3478,9 +3597,7 @@ int group_run_twin(rs_group* g, const GroupCall& c, const RsLaunch& L) {
   HIP_TRY(rs_launch_group(&Lb, b->threads, c.row(), st));
   HIP_TRY(hipMemcpyAsync(g->h_out2.data(), g->d_out2, (size_t)c.n * c.ttis() * g->out_stride, hipMemcpyDeviceToHost, st)); /* (a run: slots x TTIs) */
   if ((f.sets() & RS_GROUP_SET_SENT) && g->sent2.copied()) HIP_TRY(hipMemcpyAsync(g->sent2.h, g->sent2.d, 8 * (size_t)c.n * b->U, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(after, b->d_sstate, ss_all, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(b->d_sstate, before, ss_all, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(b->d_scal, before + group_chk_sstate(g), sc_all, hipMemcpyDeviceToDevice, st));
+  if (const int rc = tw.keep_and_put_back()) return rc;
   HIP_TRY(group_copy_stores(g, f, 1, true));
   HIP_TRY(group_copy_stores(g, f, 0, false));
   return RS_OK;
@@ -3506,8 +3623,8 @@ int group_run(rs_group* g, GroupCall& c, RsLaunch& L) {
     L.done_flag = (uint32_t*)(g->z_out + g->flag_off);
     L.done_seq = g->seq;
   }
-  static const rs_group::GroupPair no_pair{}; /* (a form without run-time builds: nothing wanted, nothing built) */
-  const rs_group::GroupPair& p = f.pair >= 0 ? g->pair[f.pair] : no_pair;
+  static const JitPair no_pair{}; /* (a form without run-time builds: nothing wanted, nothing built) */
+  const JitPair& p = f.pair >= 0 ? g->pair[f.pair] : no_pair;
   /* (a flows call always carries the data_to_transmit gate: its lean build keeps it) */
   const bool gate_free = c.form == kGroupFlows || !c.has_gate;
   const bool lean = p.jit[1] && !c.has_prb && !L.queue_mode && gate_free && !L.exact_scan && !L.gen_exp && !c.want_upper && !L.synthetic;
@@ -3548,7 +3665,7 @@ int group_compare_stores(const rs_group* g, const GroupCall& c, char* what, size
   const GroupStores s = group_stores(g, f);
   if (!s.n) return RS_OK;
   std::vector<uint8_t> jit[5], ref[5];
-  const uint8_t* kept = g->pair[f.pair].d_stores_chk + s.half;
+  const uint8_t* kept = g->d_stores_chk[f.pair] + s.half;
   for (int i = 0; i < s.n; kept += kGroupStores[s.row[i++]].kept(g)) {
     const size_t bytes = kGroupStores[s.row[i]].bytes(g);
     jit[i].resize(bytes);
@@ -3584,17 +3701,12 @@ int group_compare_stores(const rs_group* g, const GroupCall& c, char* what, size
 int group_drop_pair(rs_group* g, const GroupCall& c, const char* what) {
   rs_batch* b = g->b;
   const GroupForm& f = c.desc();
-  rs_group::GroupPair& p = g->pair[f.pair];
-  for (int w = 0; w < 2; w++) {
-    if (p.jit[w]) rs_jit_reject(p.jit[w]);
-    p.jit[w] = nullptr;
-    p.chk_left[w] = 0;
-  }
-  p.dropped = true;
+  JitPair& p = g->pair[f.pair];
+  jit_pair_drop(&p);
   g->last_call_jit = false;
   memcpy(g->h_out, g->h_out2.data(), (size_t)c.n * c.ttis() * g->out_stride);
   if (f.sets() & RS_GROUP_SET_SENT) memcpy(g->sent.h, g->sent2.h, 8 * (size_t)c.n * b->U); /* (the built-in kernel's sent rows: what group_unpack hands out) */
-  HIP_TRY(hipMemcpy(b->d_sstate, g->d_chk + group_chk_half(g), 8 * (size_t)b->S * g->n_cells, hipMemcpyDeviceToDevice));
+  if (const int rc = TwinState{g->b, g->d_chk, g->n_cells}.restore_kept()) return rc;
   if (f.store_width) {
     HIP_TRY(group_copy_stores(g, f, 1, false));
     HIP_TRY(hipStreamSynchronize(b->stream));
@@ -3609,11 +3721,8 @@ int group_drop_pair(rs_group* g, const GroupCall& c, const char* what) {
  * state and the form's stores; slot by slot, field by field, the first difference is the message */
 int group_check(rs_group* g, const GroupCall& c) {
   const rs_batch* b = g->b;
-  rs_group::GroupPair& p = g->pair[c.desc().pair];
-  const size_t ss_all = 8 * (size_t)b->S * g->n_cells;
-  std::vector<double> ss_jit((size_t)b->S * g->n_cells), ss_ref(ss_jit.size());
-  HIP_TRY(hipMemcpy(ss_jit.data(), b->d_sstate, ss_all, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(ss_ref.data(), g->d_chk + group_chk_half(g), ss_all, hipMemcpyDeviceToHost));
+  TwinState tw{g->b, g->d_chk, g->n_cells};
+  if (const int rc = tw.fetch()) return rc;
   char what[240] = "";
   for (int k = 0; k < c.n && !what[0]; k++) {
     const int cell = c.cell(k);
@@ -3622,10 +3731,7 @@ int group_check(rs_group* g, const GroupCall& c) {
       const size_t at = c.at(k, t) * g->out_stride;
       compare_out_block(g->h_out + at, g->h_out2.data() + at, g->packs[k].l, b->R, b->S, c.in[k].n_users, c.want_upper, cell, what, sizeof what, c.run ? t : -1);
     }
-    for (int i = 0; i < b->S && !what[0]; i++) {
-      const double a = ss_jit[(size_t)cell * b->S + i], r = ss_ref[(size_t)cell * b->S + i];
-      if (to_bits(a) != to_bits(r)) snprintf(what, sizeof what, "cell %d: slice state[%d] = %a, the built-in kernel's %a", cell, i, a, r);
-    }
+    tw.compare(cell, cell, what, sizeof what);
     /* (a counted call: the slot's sent rows, whether or not the caller wants them; an update-only slot has none) */
     if ((c.desc().sets() & RS_GROUP_SET_SENT) && !g->empty_slot[k]) {
       const int32_t *a = g->sent.h + (size_t)k * 2 * (size_t)b->U, *r = g->sent2.h + (size_t)k * 2 * (size_t)b->U;
@@ -3638,8 +3744,7 @@ int group_check(rs_group* g, const GroupCall& c) {
     if (rc) return rc;
   }
   if (what[0]) return group_drop_pair(g, c, what);
-  p.chk_agreed[c.which]++;
-  if (--p.chk_left[c.which] == 0) rs_jit_mark_verified(c.kd);
+  jit_pair_agreed(&g->pair[c.desc().pair], c.which);
   return RS_OK;
 }
 
@@ -3653,21 +3758,15 @@ void group_commit_clocks(rs_group* g, const GroupCall& c) {
 void group_commit_images(rs_group* g, const GroupCall& c) {
   for (int k = 0; k < c.n; k++) {
     if (g->empty_slot[k]) continue; /* (no reports, no image moved, not counted) */
-    const rs_tti_in& in = c.in[k];
     const int mode = g->modes[k];
-    rs_group::CellImage& im = g->img[c.cell(k)];
+    CqiImage& im = g->img[c.cell(k)];
     /* (a run, as the calls it stands for: its later TTIs read what TTI 0 read -- the slot's blocks again without a number, else the image) */
     const int64_t later = c.ttis() - 1;
     if (mode == 0) { g->n_plain += 1 + later; im.valid = false; continue; } /* (as a context: a call without a number ends the image's term) */
     if (mode == 2) { g->n_reused += 1 + later; continue; }
     g->n_stored++;
     g->n_reused += later;
-    im.valid = true;
-    im.epoch = in.cqi_epoch;
-    im.n = in.n_users;
-    im.prb = c.has_prb;
-    im.has_ids = in.user_id != nullptr;
-    if (in.user_id) im.ids.assign(in.user_id, in.user_id + in.n_users);
+    im.stored(c.in[k], c.has_prb);
   }
 }
 
@@ -4094,7 +4193,7 @@ const char* rs_group_kernel_name(rs_group* g) {
 
 /* Shape specialisation of a group: rs_ctx_specialize for the group surface -- the one-TTI form compiled for the config's slices, RBGs,
  * PRBs per RBG, scheduler, workgroup size and user CAPACITY, one workgroup per call slot, in a general and a lean build.  Five pairs
- * (rs_group::GroupPair), each an option of its own: rs_group_specialize (entry point rs_group_kernel_jit, serves rs_group_schedule_tti),
+ * (JitPair), each an option of its own: rs_group_specialize (entry point rs_group_kernel_jit, serves rs_group_schedule_tti),
  * rs_group_specialize_resident (rs_group_resident_kernel_jit, serves rs_group_schedule_tti_at), rs_group_specialize_queued
  * (rs_group_queued_kernel_jit, serves rs_group_schedule_tti_queued), rs_group_specialize_counted (rs_group_counted_kernel_jit, serves
  * rs_group_schedule_tti_counted) and rs_group_specialize_flows (rs_group_flows_kernel_jit, serves rs_group_schedule_tti_flows); a sixth,
@@ -4103,130 +4202,58 @@ const char* rs_group_kernel_name(rs_group* g) {
 namespace {
 /* kind: a row of kGroupForms -- the call the pair serves */
 int group_specialize_pair(rs_group* g, int kind) {
+  if (!g) return fail(RS_ERR_INVALID, "null group");
   rs_batch* b = g->b;
   const GroupForm& f = kGroupForms[kind];
-  rs_group::GroupPair& p = g->pair[f.pair];
+  JitPair& p = g->pair[f.pair];
   if (p.jit[0]) return RS_OK;
   if (p.dropped) return fail(RS_ERR_STATE, "%s", p.msg);
   if (f.lacks && !rs_group_form_serves(kind, b->sched)) return fail(RS_ERR_INVALID, "scheduler %d %s: nothing for %s to build", b->sched, f.lacks, f.entry);
   if (kind == kGroupRun && b->any_alpha)
     return fail(RS_ERR_INVALID, "a config with a customised slice (algo_alpha != 0) %s: nothing for %s to build", f.lacks, f.entry);
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  p.wanted = true;
+  p.wanted = true; /* (from here on a failure is the pair's: status -1) */
   if (!g->d_out2) {
-    const size_t out_bytes = g->out_stride * g->out_slots; /* (as many slots as d_out holds: the largest run so far) */
-    if (hipMalloc(&g->d_out2, out_bytes) != hipSuccess || hipMalloc(&g->d_chk, 2 * group_chk_half(g)) != hipSuccess) {
+    const size_t out_bytes = g->out_stride * g->out_slots, chk_bytes = 2 * TwinState{g->b, nullptr, g->n_cells}.half(); /* (as many slots as d_out holds: the largest run so far) */
+    if (hipMalloc(&g->d_out2, out_bytes) != hipSuccess || hipMalloc(&g->d_chk, chk_bytes) != hipSuccess) {
       (void)hipGetLastError();
       if (g->d_out2) (void)hipFree(g->d_out2);
       g->d_out2 = g->d_chk = nullptr;
-      snprintf(p.msg, sizeof p.msg, "allocation of the self-check's twin blocks failed (%zu + %zu bytes)", out_bytes, 2 * group_chk_half(g));
+      snprintf(p.msg, sizeof p.msg, "allocation of the self-check's twin blocks failed (%zu + %zu bytes)", out_bytes, chk_bytes);
       return fail(RS_ERR_HIP, "%s", p.msg);
     }
     g->h_out2.assign(out_bytes, 0);
   }
   const size_t stores = 2 * group_stores(g, f).half;
-  if (stores && !p.d_stores_chk && hipMalloc(&p.d_stores_chk, stores) != hipSuccess) {
+  if (stores && !g->d_stores_chk[f.pair] && hipMalloc(&g->d_stores_chk[f.pair], stores) != hipSuccess) {
     (void)hipGetLastError();
-    p.d_stores_chk = nullptr;
+    g->d_stores_chk[f.pair] = nullptr;
     snprintf(p.msg, sizeof p.msg, "allocation of the self-check's copies of the %s failed (%zu bytes)", f.stores, stores);
     return fail(RS_ERR_HIP, "%s", p.msg);
   }
-  const int qmode = (b->sched == RS_SCHED_PF || b->sched == RS_SCHED_NVS) ? 1 : 0; /* (the gate scratch of the group's carve: carve_lds) */
-  const int jit_flags = 1 | rs_group_form(kind).jit_flags; /* (1: the one-TTI form, as every group build is) */
-  char msg[512] = "";
-  p.jit[0] = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, qmode, 0, msg, sizeof msg, jit_flags);
-  if (!p.jit[0]) {
-    snprintf(p.msg, sizeof p.msg, "%s", msg[0] ? msg : "hiprtc build failed");
-    return fail(RS_ERR_HIP, "%s", p.msg);
-  }
-  p.msg[0] = 0;
-  /* ... and its lean form (the plain call); without it the general build serves every call */
-  const char* const e_on = getenv("RS_JIT_LEAN");
-  if (!e_on || atoi(e_on) != 0) p.jit[1] = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, qmode, 0, msg, sizeof msg, jit_flags | 4);
-  for (int w = 0; w < 2; w++) { /* (the policy and the switches of rs_ctx_specialize) */
-    p.chk_agreed[w] = 0;
-    p.chk_left[w] = selfcheck_calls(p.jit[w]);
-  }
-  return RS_OK;
+  return jit_pair_build(&p, b, 1 | rs_group_form(kind).jit_flags); /* (1: the one-TTI form, as every group build is) */
 }
 
 int group_jit_pair_status(rs_group* g, int kind, char* msg, size_t msglen) {
+  if (!g) return fail(RS_ERR_INVALID, "null group");
   const GroupForm& f = kGroupForms[kind];
-  const rs_group::GroupPair& p = g->pair[f.pair];
-  if (msg && msglen) {
-    if (p.dropped || !p.jit[0]) {
-      snprintf(msg, msglen, "%s", p.msg);
-    } else {
-      char ge[220], le[220];
-      selfcheck_state(p.jit[0], p.chk_left[0], p.chk_agreed[0], f.ref, ge, sizeof ge);
-      selfcheck_state(p.jit[1], p.chk_left[1], p.chk_agreed[1], f.ref, le, sizeof le);
-      snprintf(msg, msglen, "general build: %s; lean build: %s", ge, le);
-    }
-  }
-  if (p.dropped) return -2;
-  return p.jit[0] ? 1 : (p.wanted ? -1 : 0);
+  return jit_pair_status(g->pair[f.pair], f.ref, msg, msglen);
 }
 }  // namespace
 
-int rs_group_specialize(rs_group* g) {
-  if (!g) return fail(RS_ERR_INVALID, "null group");
-  return group_specialize_pair(g, kGroupPlain);
-}
-
-int rs_group_specialize_resident(rs_group* g) {
-  if (!g) return fail(RS_ERR_INVALID, "null group");
-  return group_specialize_pair(g, kGroupResident);
-}
-
-int rs_group_jit_status(rs_group* g, char* msg, size_t msglen) {
-  if (!g) return fail(RS_ERR_INVALID, "null group");
-  return group_jit_pair_status(g, kGroupPlain, msg, msglen);
-}
-
-int rs_group_resident_jit_status(rs_group* g, char* msg, size_t msglen) {
-  if (!g) return fail(RS_ERR_INVALID, "null group");
-  return group_jit_pair_status(g, kGroupResident, msg, msglen);
-}
-
-int rs_group_specialize_queued(rs_group* g) {
-  if (!g) return fail(RS_ERR_INVALID, "null group");
-  return group_specialize_pair(g, kGroupQueued);
-}
-
-int rs_group_queued_jit_status(rs_group* g, char* msg, size_t msglen) {
-  if (!g) return fail(RS_ERR_INVALID, "null group");
-  return group_jit_pair_status(g, kGroupQueued, msg, msglen);
-}
-
-int rs_group_specialize_counted(rs_group* g) {
-  if (!g) return fail(RS_ERR_INVALID, "null group");
-  return group_specialize_pair(g, kGroupCounted);
-}
-
-int rs_group_counted_jit_status(rs_group* g, char* msg, size_t msglen) {
-  if (!g) return fail(RS_ERR_INVALID, "null group");
-  return group_jit_pair_status(g, kGroupCounted, msg, msglen);
-}
-
-int rs_group_specialize_flows(rs_group* g) {
-  if (!g) return fail(RS_ERR_INVALID, "null group");
-  return group_specialize_pair(g, kGroupFlows);
-}
-
-int rs_group_flows_jit_status(rs_group* g, char* msg, size_t msglen) {
-  if (!g) return fail(RS_ERR_INVALID, "null group");
-  return group_jit_pair_status(g, kGroupFlows, msg, msglen);
-}
-
-int rs_group_specialize_run(rs_group* g) {
-  if (!g) return fail(RS_ERR_INVALID, "null group");
-  return group_specialize_pair(g, kGroupRun);
-}
-
-int rs_group_run_jit_status(rs_group* g, char* msg, size_t msglen) {
-  if (!g) return fail(RS_ERR_INVALID, "null group");
-  return group_jit_pair_status(g, kGroupRun, msg, msglen);
-}
+/* the entry points: one pair each */
+int rs_group_specialize(rs_group* g) { return group_specialize_pair(g, kGroupPlain); }
+int rs_group_jit_status(rs_group* g, char* msg, size_t msglen) { return group_jit_pair_status(g, kGroupPlain, msg, msglen); }
+int rs_group_specialize_resident(rs_group* g) { return group_specialize_pair(g, kGroupResident); }
+int rs_group_resident_jit_status(rs_group* g, char* msg, size_t msglen) { return group_jit_pair_status(g, kGroupResident, msg, msglen); }
+int rs_group_specialize_queued(rs_group* g) { return group_specialize_pair(g, kGroupQueued); }
+int rs_group_queued_jit_status(rs_group* g, char* msg, size_t msglen) { return group_jit_pair_status(g, kGroupQueued, msg, msglen); }
+int rs_group_specialize_counted(rs_group* g) { return group_specialize_pair(g, kGroupCounted); }
+int rs_group_counted_jit_status(rs_group* g, char* msg, size_t msglen) { return group_jit_pair_status(g, kGroupCounted, msg, msglen); }
+int rs_group_specialize_flows(rs_group* g) { return group_specialize_pair(g, kGroupFlows); }
+int rs_group_flows_jit_status(rs_group* g, char* msg, size_t msglen) { return group_jit_pair_status(g, kGroupFlows, msg, msglen); }
+int rs_group_specialize_run(rs_group* g) { return group_specialize_pair(g, kGroupRun); }
+int rs_group_run_jit_status(rs_group* g, char* msg, size_t msglen) { return group_jit_pair_status(g, kGroupRun, msg, msglen); }
 
 /* ---- the reference's CQI trace files (include/radiosaber_hip.h) ---- */
 

@@ -181,6 +181,45 @@ def test_cqi_epoch_never_trusts_more_than_it_can_check(rs, oracle):
         t.close()
 
 
+def test_a_refused_call_ends_the_image_only_once_the_grid_was_reached(rs):
+    """A context's image record and a refused call (a group's rule differs: test_gpu_group_epoch.test_a_rejected_call_moves_no_image).
+    A call refused BEFORE its reports are looked at (a user id out of range) leaves the image in place: the next call under the same
+    number is served from it.  A call refused BEHIND them (a negative data_to_transmit entry) ends the image's term: the next call under
+    the same number reads its block.  Against a twin context that gets the true reports with cqi_epoch = 0."""
+    ues, R, G = [2, 2], 12, 2
+    U = 4
+    sc = rs.SliceConfig(ues)
+    avg = np.array([2e4, 3e4, 2.5e4, 3.5e4])
+    data = np.full(U, 1000, np.int32)
+    block_a = np.full((U, R), 3, np.uint8)
+    block_a[0] = 15
+    block_b = np.full((U, R), 3, np.uint8)
+    block_b[3] = 15
+    ids = np.arange(U)
+    refusals = {"before the grid": (dict(user_id=np.array([0, 1, 2, U]), data_to_transmit=data), "user id 4 out of range", block_a),
+                "behind the grid": (dict(user_id=ids, data_to_transmit=np.array([1000, -1, 1000, 1000], np.int32)),
+                                    "data_to_transmit[1] = -1 is negative", block_b)}
+    for case, (bad, frag, truth) in refusals.items():
+        ts = rs.TtiScheduler(sc, R, G, sched=1)
+        twin = rs.TtiScheduler(sc, R, G, sched=1)
+        res = ts.schedule_tti(block_a, avg, 11, 22, user_id=ids, data_to_transmit=data, cqi_epoch=5)
+        ref_a = twin.schedule_tti(block_a, avg, 11, 22, user_id=ids, data_to_transmit=data)
+        _same(res, ref_a, f"{case}: the call that stores block A")
+        with pytest.raises(rs.RadioSaberError) as e:
+            ts.schedule_tti(block_b, avg, 12, 23, cqi_epoch=5, **bad)
+        assert e.value.code == -1 and frag in str(e.value), str(e.value)  # RS_ERR_INVALID
+        res = ts.schedule_tti(block_b, avg, 13, 24, user_id=ids, data_to_transmit=data, cqi_epoch=5)
+        ref = twin.schedule_tti(truth, avg, 13, 24, user_id=ids, data_to_transmit=data)
+        _same(res, ref, f"{case}: the call after the refusal")
+        # (control: served from the other block the call gives other grants, so the comparison above tells the two apart)
+        other = rs.TtiScheduler(sc, R, G, sched=1)
+        other.schedule_tti(block_a, avg, 11, 22, user_id=ids, data_to_transmit=data)
+        wrong = other.schedule_tti(block_b if truth is block_a else block_a, avg, 13, 24, user_id=ids, data_to_transmit=data)
+        assert any(not np.array_equal(getattr(wrong, f), getattr(ref, f)) for f in FIELDS), case
+        for t in (ts, twin, other):
+            t.close()
+
+
 @pytest.mark.parametrize("sched", [9, 8])
 def test_cqi_epoch_with_per_prb_reports_and_the_copy_path(rs, oracle, sched, monkeypatch):
     """Per-PRB reports travel as a device copy (not zero-copy): with an unchanged number neither the grid nor the per-PRB block is sent
