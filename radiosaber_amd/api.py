@@ -14,7 +14,7 @@ import json
 import os
 from dataclasses import dataclass, field
 from pathlib import Path
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -85,44 +85,163 @@ class _BatchBearerLog(C.Structure):
     _fields_ = [("bytes", C.POINTER(C.c_int32)), ("hol_delay", C.POINTER(C.c_double))]
 
 
-# every symbol include/radiosaber_hip.h declares (tests check the library exports all of them)
-ABI_SYMBOLS = [
-    "rs_last_error", "rs_abi_version", "rs_device_count", "rs_link_tables",
-    "rs_create", "rs_destroy", "rs_schedule_tti", "rs_get_slice_offset", "rs_set_slice_offset",
-    "rs_batch_create", "rs_batch_destroy", "rs_batch_seed", "rs_batch_upload_cqi_epochs",
-    "rs_batch_synthesize_cqi", "rs_batch_download_cqi_epochs", "rs_batch_set_trace",
-    "rs_batch_run", "rs_batch_run_async", "rs_batch_sync", "rs_batch_run_logged",
-    "rs_batch_run_timed", "rs_batch_read_state", "rs_batch_slice_bytes_device",
-    "rs_batch_slice_bytes", "rs_jit_selfcheck", "rs_jit_selfcheck_queue", "rs_batch_debug_stamps", "rs_batch_ttis_done", "rs_batch_stream", "rs_batch_kernel_name",
-    "rs_trace_read_mapping", "rs_trace_read_ue_log", "rs_trace_load_dir", "rs_hbm_copy_probe", "rs_lds_bytes_per_cell",
-    "rs_get_rbg_size", "rs_dl_prbs_for_bandwidth", "rs_batch_synthesize_cqi_at", "rs_batch_run_logged_ex",
-    "rs_batch_read_clock", "rs_batch_jit_status", "rs_batch_prepare_launch",
-    "rs_batch_upload_cqi_epochs_prb", "rs_batch_set_trace_prb",
-    "rs_batch_set_bearers", "rs_batch_set_arrivals", "rs_batch_read_bearer_state", "rs_internet_flow_arrivals",
-    "rs_device_source_hash",
-    "rs_create_checked", "rs_batch_create_checked", "rs_jit_selfcheck_untuned", "rs_batch_write_state",
-    "rs_ctx_specialize", "rs_jit_selfcheck_dropin",
-    "rs_batch_debug_heap_sorts", "rs_ctx_debug_heap_sorts",
-    "rs_jit_cache_stats", "rs_jit_cache_file", "rs_jit_cache_warm", "rs_batch_autotune_report", "rs_batch_debug_clocks",
-    "rs_batch_checkpoint_bytes", "rs_batch_checkpoint_save", "rs_batch_checkpoint_load",
-    "rs_link_tables_pinned", "rs_link_tables_compare", "rs_ctx_jit_status", "rs_jit_compiler_identity",
-    "rs_batch_flow_record", "rs_batch_run_logged_bearers",
-    "rs_group_create", "rs_group_create_checked", "rs_group_destroy", "rs_group_schedule_tti",
-    "rs_group_get_slice_offset", "rs_group_set_slice_offset", "rs_group_launch_count", "rs_group_kernel_name",
-    "rs_group_image_stats", "rs_group_specialize", "rs_group_jit_status", "rs_jit_selfcheck_group",
-    "rs_group_set_avg", "rs_group_get_avg", "rs_group_set_pending", "rs_group_schedule_tti_at", "rs_group_run_at",
-    "rs_group_specialize_resident", "rs_group_resident_jit_status", "rs_jit_selfcheck_group_resident",
-    "rs_group_set_bearers", "rs_group_get_bearers", "rs_group_schedule_tti_queued",
-    "rs_group_specialize_queued", "rs_group_queued_jit_status", "rs_jit_selfcheck_group_queued",
-    "rs_group_set_counters", "rs_group_get_counters", "rs_group_schedule_tti_counted",
-    "rs_group_set_flows", "rs_group_get_flows", "rs_group_schedule_tti_flows",
-    "rs_group_specialize_counted", "rs_group_counted_jit_status", "rs_jit_selfcheck_group_counted",
-    "rs_group_specialize_flows", "rs_group_flows_jit_status", "rs_jit_selfcheck_group_flows",
-    "rs_group_specialize_run", "rs_group_run_jit_status", "rs_jit_selfcheck_group_run",
-    "rs_group_set_avg_counters", "rs_group_get_avg_counters", "rs_group_run_counted_at",
-    "rs_group_grant_bound", "rs_group_run_records_at",
-    "rs_batch_record_bound", "rs_batch_run_records",
-]
+class GroupForm(NamedTuple):
+    """One form of a group call, as one row of rs_api.cpp's table of forms: its three C names follow from the key."""
+    key: str              # "" for the plain form
+    keywords: frozenset   # the keywords of jit_selfcheck / jit_cache_file / jit_cache_warm that select the form's builds
+    flags: int            # ... and the rs_jit_cache_* flag bits of those builds
+
+    @property
+    def specialize(self):
+        return "rs_group_specialize" + ("_" + self.key if self.key else "")
+
+    @property
+    def jit_status(self):
+        return "rs_group_" + (self.key + "_" if self.key else "") + "jit_status"
+
+    @property
+    def selfcheck(self):
+        return "rs_jit_selfcheck_group" + ("_" + self.key if self.key else "")
+
+
+# the forms in the order of RS_GROUP_PLAIN .. RS_GROUP_RUN.  counted=True implies queued=True (the counted form is the queued
+# form's twin: flag value 64 is valid only together with 32), so `counted` alone and `queued` with `counted` are the same row
+GROUP_FORMS = tuple(GroupForm(key, frozenset(kws.split()), flags) for key, kws, flags in (
+    ("", "group", 8),
+    ("resident", "group resident", 24),
+    ("queued", "group queued", 40),
+    ("counted", "group queued counted", 104),
+    ("flows", "group flows", 136),
+    ("run", "group resident run", 280),
+))
+_FORM = {f.key: f for f in GROUP_FORMS}
+
+_int, _i32, _i64, _f64, _u8, _size, _str, _ptr = C.c_int, C.c_int32, C.c_int64, C.c_double, C.c_uint8, C.c_size_t, C.c_char_p, C.c_void_p
+_P = C.POINTER
+_SHAPE = [_int] * 6                      # n_slices, n_users, n_rbgs, rbg_size, threads, sched
+_MSG = [_str, _size]                     # a message buffer and its length
+_SLOTS = [_ptr, _i32, _P(_i32), _P(_TtiIn)]               # a group, n, cell_ids, in[n]
+_RUN = _SLOTS + [_i32, _P(_f64), _P(_i32), _P(_TtiOut)]   # ... n_ttis, now, rands, out
+_CELL = [_ptr, _i32]                     # a group and one of its cells
+
+
+def _form_prototypes(key):
+    f = _FORM[key]
+    return {f.specialize: (_int, [_ptr]), f.jit_status: (_int, [_ptr] + _MSG), f.selfcheck: (_int, _SHAPE + _MSG)}
+
+
+# name -> (restype, argtypes) of every function include/radiosaber_hip.h declares, in the header's order (tests check that the
+# header declares these and no others, and that the library exports them all)
+PROTOTYPES = {
+    "rs_last_error": (_str, []),
+    "rs_abi_version": (_int, []),
+    "rs_device_count": (_int, []),
+    "rs_link_tables": (_int, [_P(_f64)] * 4),
+    "rs_link_tables_pinned": (_int, [_P(_f64)] * 4),
+    "rs_link_tables_compare": (_int, _MSG),
+    "rs_get_rbg_size": (_int, [_int]),
+    "rs_dl_prbs_for_bandwidth": (_int, [_f64]),
+    "rs_create": (_ptr, [_P(_Config)]),
+    "rs_create_checked": (_ptr, [_P(_Config), _int, _size]),
+    "rs_destroy": (_int, [_ptr]),
+    "rs_schedule_tti": (_int, [_ptr, _P(_TtiIn), _P(_TtiOut)]),
+    "rs_ctx_specialize": (_int, [_ptr]),
+    "rs_ctx_jit_status": (_int, [_ptr] + _MSG),
+    "rs_jit_selfcheck_dropin": (_int, _SHAPE + _MSG),
+    "rs_get_slice_offset": (_int, [_ptr, _P(_f64)]),
+    "rs_set_slice_offset": (_int, [_ptr, _P(_f64)]),
+    "rs_group_create": (_ptr, [_P(_Config), _i32]),
+    "rs_group_create_checked": (_ptr, [_P(_Config), _i32, _int, _size]),
+    "rs_group_destroy": (_int, [_ptr]),
+    "rs_group_schedule_tti": (_int, _SLOTS + [_P(_TtiOut)]),
+    "rs_group_get_slice_offset": (_int, _CELL + [_P(_f64)]),
+    "rs_group_set_slice_offset": (_int, _CELL + [_P(_f64)]),
+    "rs_group_launch_count": (_i64, [_ptr]),
+    "rs_group_image_stats": (_int, [_ptr, _P(_i64)]),
+    "rs_group_kernel_name": (_str, [_ptr]),
+    **_form_prototypes(""),
+    "rs_group_set_avg": (_int, _CELL + [_P(_f64), _f64]),
+    "rs_group_get_avg": (_int, _CELL + [_P(_f64), _P(_i32), _P(_f64)]),
+    "rs_group_set_pending": (_int, _CELL + [_P(_i32)]),
+    "rs_group_schedule_tti_at": (_int, _SLOTS + [_P(_TtiOut), _P(_f64)]),
+    **_form_prototypes("resident"),
+    "rs_group_run_at": (_int, _RUN),
+    **_form_prototypes("run"),
+    "rs_group_set_avg_counters": (_int, _CELL + [_P(_i64), _P(_i64)]),
+    "rs_group_get_avg_counters": (_int, _CELL + [_P(_i64), _P(_i64)]),
+    "rs_group_run_counted_at": (_int, _RUN),
+    "rs_group_grant_bound": (_int, [_ptr]),
+    "rs_group_run_records_at": (_int, _RUN + [_i32, _ptr, _P(_i32)]),
+    "rs_group_set_bearers": (_int, _CELL + [_P(_u8), _P(_f64), _f64]),
+    "rs_group_get_bearers": (_int, _CELL + [_P(_f64), _P(_i32), _P(_f64)]),
+    "rs_group_schedule_tti_queued": (_int, _SLOTS + [_P(_TtiOut), _P(_f64), _P(_P(_i32))]),
+    **_form_prototypes("queued"),
+    "rs_group_set_counters": (_int, _CELL + [_P(_i64), _P(_i64)]),
+    "rs_group_get_counters": (_int, _CELL + [_P(_i64), _P(_i64)]),
+    "rs_group_schedule_tti_counted": (_int, _SLOTS + [_P(_TtiOut), _P(_f64), _P(_P(_i32)), _P(_P(_i32))]),
+    **_form_prototypes("counted"),
+    "rs_group_set_flows": (_int, _CELL + [_P(_u8), _P(_f64), _f64, _P(_i64), _P(_i64)]),
+    "rs_group_get_flows": (_int, _CELL + [_P(_f64), _P(_i32), _P(_f64), _P(_i64), _P(_i64)]),
+    "rs_group_schedule_tti_flows": (_int, _SLOTS + [_P(_TtiOut), _P(_f64), _P(_P(_u8))]),
+    **_form_prototypes("flows"),
+    "rs_batch_create": (_ptr, [_P(_BatchConfig)]),
+    "rs_batch_create_checked": (_ptr, [_P(_BatchConfig), _int, _size]),
+    "rs_batch_destroy": (_int, [_ptr]),
+    "rs_batch_seed": (_int, [_ptr, _P(C.c_uint32), _P(_i64)]),
+    "rs_batch_upload_cqi_epochs": (_int, [_ptr, _P(_u8), _i32]),
+    "rs_batch_upload_cqi_epochs_prb": (_int, [_ptr, _P(_u8), _i32]),
+    "rs_batch_synthesize_cqi": (_int, [_ptr, C.c_uint64, _P(_f64), _i32]),
+    "rs_batch_synthesize_cqi_at": (_int, [_ptr, C.c_uint64, _P(_f64), _i32, _i64]),
+    "rs_batch_download_cqi_epochs": (_int, [_ptr, _i32, _P(_u8)]),
+    "rs_batch_set_trace": (_int, [_ptr, _P(_u8), _i32, _i32, _i32, _P(_i32)]),
+    "rs_batch_set_trace_prb": (_int, [_ptr, _P(_u8), _i32, _i32, _i32, _P(_i32)]),
+    "rs_lds_bytes_per_cell": (_int, [_int] * 5),
+    "rs_hbm_copy_probe": (_int, [_int, C.c_uint64, _int, _P(_f64)]),
+    "rs_trace_read_mapping": (_int, [_str, _P(_i32), _i32]),
+    "rs_trace_read_ue_log": (_int, [_str, _i32, _i32, _i32, _P(_u8), _P(_u8)]),
+    "rs_trace_load_dir": (_int, [_str, _i32, _i32, _i32, _i32, _P(_u8)]),
+    "rs_batch_set_bearers": (_int, [_ptr, _P(_u8)]),
+    "rs_batch_set_arrivals": (_int, [_ptr, _P(_i64), _P(_f64), _P(_i32), _P(_i32)]),
+    "rs_batch_read_bearer_state": (_int, [_ptr, _P(_f64), _P(_i64), _P(_i64), _P(_i32), _P(_i32)]),
+    "rs_internet_flow_arrivals": (_int, [_f64, _f64, _f64, C.c_uint32, _i32, _P(_f64), _P(_i32), _P(_i32)]),
+    "rs_batch_flow_record": (_int, [_ptr, _P(_i32), _P(_f64)]),
+    "rs_batch_run": (_int, [_ptr, _i32]),
+    "rs_batch_run_async": (_int, [_ptr, _i32]),
+    "rs_batch_sync": (_int, [_ptr]),
+    "rs_batch_run_logged": (_int, [_ptr, _i32, _P(C.c_int16), _P(_i32), _P(C.c_int16), _P(C.c_int16), _P(_i32)]),
+    "rs_batch_run_logged_ex": (_int, [_ptr, _i32, _P(_BatchLog)]),
+    "rs_batch_run_logged_bearers": (_int, [_ptr, _i32, _P(_BatchLog), _P(_BatchBearerLog)]),
+    "rs_batch_record_bound": (_int, [_ptr]),
+    "rs_batch_run_records": (_int, [_ptr, _i32, _i64, _ptr, _P(_i64)]),
+    "rs_batch_run_timed": (_int, [_ptr, _i32, _i32, _P(C.c_float)]),
+    "rs_batch_read_state": (_int, [_ptr, _P(_f64), _P(_i64), _P(_i64), _P(_f64)]),
+    "rs_batch_write_state": (_int, [_ptr, _P(_f64), _P(_f64)]),
+    "rs_batch_checkpoint_bytes": (_i64, [_ptr]),
+    "rs_batch_checkpoint_save": (_int, [_ptr, _ptr, _size]),
+    "rs_batch_checkpoint_load": (_int, [_ptr, _ptr, _size]),
+    "rs_batch_read_clock": (_int, [_ptr, _P(_f64), _P(_f64)]),
+    "rs_batch_jit_status": (_int, [_ptr] + _MSG),
+    "rs_batch_autotune_report": (_int, [_ptr] + _MSG),
+    "rs_batch_prepare_launch": (_int, [_ptr, _i32]),
+    "rs_batch_slice_bytes_device": (_int, [_ptr, _ptr]),
+    "rs_batch_slice_bytes": (_int, [_ptr, _P(C.c_uint64)]),
+    "rs_jit_selfcheck": (_int, _SHAPE + _MSG),
+    "rs_jit_selfcheck_untuned": (_int, _SHAPE + _MSG),
+    "rs_jit_selfcheck_queue": (_int, _SHAPE + _MSG),
+    "rs_jit_cache_stats": (None, [_P(C.c_longlong)]),
+    "rs_jit_compiler_identity": (_str, []),
+    "rs_jit_cache_file": (_int, _SHAPE + [_int] + _MSG),
+    "rs_jit_cache_warm": (_int, _SHAPE + [_int] + _MSG),
+    "rs_device_source_hash": (_str, []),
+    "rs_batch_debug_heap_sorts": (_int, [_ptr, _P(_i64)]),
+    "rs_ctx_debug_heap_sorts": (_int, [_ptr, _P(_i64)]),
+    "rs_batch_debug_clocks": (_int, [_ptr, _P(_f64), _P(_f64)]),
+    "rs_batch_debug_stamps": (_int, [_ptr, _i32, _P(C.c_uint64)]),
+    "rs_batch_ttis_done": (_i64, [_ptr]),
+    "rs_batch_stream": (_ptr, [_ptr]),
+    "rs_batch_kernel_name": (_str, [_ptr]),
+}
+ABI_SYMBOLS = list(PROTOTYPES)
 
 # rs_grant_record: one grant of one TTI of a counted run (32 bytes)
 GRANT_RECORD = np.dtype([("pos", np.int32), ("user_id", np.int32), ("bytes", np.int32), ("nprb", np.int32),
@@ -145,152 +264,9 @@ def lib():
         raise RadioSaberError(-100, f"{_LIB_PATH} is missing: run `python -m radiosaber_amd.build` "
                                     "(there is no CPU fallback)")
     L = C.CDLL(str(_LIB_PATH))
-    L.rs_last_error.restype = C.c_char_p
-    L.rs_link_tables.argtypes = [C.POINTER(C.c_double)] * 4
-    L.rs_link_tables_pinned.argtypes = [C.POINTER(C.c_double)] * 4
-    L.rs_link_tables_compare.argtypes = [C.c_char_p, C.c_size_t]
-    L.rs_ctx_jit_status.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
-    L.rs_jit_compiler_identity.restype = C.c_char_p
-    L.rs_jit_compiler_identity.argtypes = []
-    L.rs_create.restype = C.c_void_p
-    L.rs_create.argtypes = [C.POINTER(_Config)]
-    L.rs_destroy.argtypes = [C.c_void_p]
-    L.rs_schedule_tti.argtypes = [C.c_void_p, C.POINTER(_TtiIn), C.POINTER(_TtiOut)]
-    L.rs_get_slice_offset.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-    L.rs_set_slice_offset.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-    L.rs_group_create.restype = C.c_void_p
-    L.rs_group_create.argtypes = [C.POINTER(_Config), C.c_int32]
-    L.rs_group_create_checked.restype = C.c_void_p
-    L.rs_group_create_checked.argtypes = [C.POINTER(_Config), C.c_int32, C.c_int, C.c_size_t]
-    L.rs_group_destroy.argtypes = [C.c_void_p]
-    L.rs_group_schedule_tti.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_TtiIn), C.POINTER(_TtiOut)]
-    L.rs_group_get_slice_offset.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double)]
-    L.rs_group_set_slice_offset.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double)]
-    L.rs_group_launch_count.restype = C.c_int64
-    L.rs_group_launch_count.argtypes = [C.c_void_p]
-    L.rs_group_image_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-    L.rs_group_kernel_name.restype = C.c_char_p
-    L.rs_group_kernel_name.argtypes = [C.c_void_p]
-    L.rs_group_specialize.argtypes = [C.c_void_p]
-    L.rs_group_set_avg.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.c_double]
-    L.rs_group_get_avg.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double)]
-    L.rs_group_set_pending.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-    L.rs_group_schedule_tti_at.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_TtiIn), C.POINTER(_TtiOut), C.POINTER(C.c_double)]
-    L.rs_group_run_at.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_TtiIn), C.c_int32, C.POINTER(C.c_double),
-                                  C.POINTER(C.c_int32), C.POINTER(_TtiOut)]
-    L.rs_group_set_bearers.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.c_double]
-    L.rs_group_get_bearers.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double)]
-    L.rs_group_schedule_tti_queued.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_TtiIn), C.POINTER(_TtiOut),
-                                               C.POINTER(C.c_double), C.POINTER(C.POINTER(C.c_int32))]
-    L.rs_group_jit_status.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
-    L.rs_jit_selfcheck_group.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
-    L.rs_group_specialize_resident.argtypes = [C.c_void_p]
-    L.rs_group_resident_jit_status.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
-    L.rs_jit_selfcheck_group_resident.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
-    L.rs_group_set_counters.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    L.rs_group_set_avg_counters.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    L.rs_group_get_avg_counters.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    L.rs_group_run_counted_at.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_TtiIn), C.c_int32, C.POINTER(C.c_double),
-                                          C.POINTER(C.c_int32), C.POINTER(_TtiOut)]
-    L.rs_group_grant_bound.argtypes = [C.c_void_p]
-    L.rs_group_run_records_at.argtypes = L.rs_group_run_counted_at.argtypes + [C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]
-    L.rs_group_get_counters.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    L.rs_group_schedule_tti_counted.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_TtiIn), C.POINTER(_TtiOut),
-                                                C.POINTER(C.c_double), C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32))]
-    L.rs_group_set_flows.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_int64),
-                                     C.POINTER(C.c_int64)]
-    L.rs_group_get_flows.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double),
-                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    L.rs_group_schedule_tti_flows.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_TtiIn), C.POINTER(_TtiOut),
-                                              C.POINTER(C.c_double), C.POINTER(C.POINTER(C.c_uint8))]
-    L.rs_group_specialize_queued.argtypes = [C.c_void_p]
-    L.rs_group_queued_jit_status.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
-    L.rs_jit_selfcheck_group_queued.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
-    L.rs_group_specialize_counted.argtypes = [C.c_void_p]
-    L.rs_group_counted_jit_status.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
-    L.rs_jit_selfcheck_group_counted.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
-    L.rs_group_specialize_flows.argtypes = [C.c_void_p]
-    L.rs_group_flows_jit_status.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
-    L.rs_jit_selfcheck_group_flows.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
-    L.rs_group_specialize_run.argtypes = [C.c_void_p]
-    L.rs_group_run_jit_status.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
-    L.rs_jit_selfcheck_group_run.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
-    L.rs_batch_create.restype = C.c_void_p
-    L.rs_batch_create.argtypes = [C.POINTER(_BatchConfig)]
-    L.rs_create_checked.restype = C.c_void_p
-    L.rs_create_checked.argtypes = [C.POINTER(_Config), C.c_int, C.c_size_t]
-    L.rs_batch_create_checked.restype = C.c_void_p
-    L.rs_batch_create_checked.argtypes = [C.POINTER(_BatchConfig), C.c_int, C.c_size_t]
-    L.rs_jit_selfcheck_untuned.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
-    L.rs_jit_selfcheck_dropin.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
-    L.rs_ctx_specialize.argtypes = [C.c_void_p]
-    L.rs_batch_destroy.argtypes = [C.c_void_p]
-    L.rs_batch_seed.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int64)]
-    L.rs_batch_upload_cqi_epochs.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32]
-    L.rs_batch_synthesize_cqi.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_double), C.c_int32]
-    L.rs_batch_synthesize_cqi_at.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_double), C.c_int32, C.c_int64]
-    L.rs_batch_run_logged_ex.argtypes = [C.c_void_p, C.c_int32, C.POINTER(_BatchLog)]
-    L.rs_batch_run_logged_bearers.argtypes = [C.c_void_p, C.c_int32, C.POINTER(_BatchLog), C.POINTER(_BatchBearerLog)]
-    L.rs_batch_flow_record.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]
-    L.rs_batch_record_bound.argtypes = [C.c_void_p]
-    L.rs_batch_run_records.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
-    L.rs_batch_read_clock.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    L.rs_batch_jit_status.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
-    L.rs_batch_prepare_launch.argtypes = [C.c_void_p, C.c_int32]
-    L.rs_batch_upload_cqi_epochs_prb.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32]
-    L.rs_batch_set_trace_prb.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
-    L.rs_batch_set_bearers.argtypes = [C.c_void_p, C.POINTER(C.c_uint8)]
-    L.rs_batch_set_arrivals.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int32),
-                                        C.POINTER(C.c_int32)]
-    L.rs_batch_read_bearer_state.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
-                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    L.rs_internet_flow_arrivals.argtypes = [C.c_double, C.c_double, C.c_double, C.c_uint32, C.c_int32, C.POINTER(C.c_double),
-                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    L.rs_get_rbg_size.argtypes = [C.c_int]
-    L.rs_dl_prbs_for_bandwidth.argtypes = [C.c_double]
-    L.rs_batch_download_cqi_epochs.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8)]
-    L.rs_batch_set_trace.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32,
-                                     C.POINTER(C.c_int32)]
-    L.rs_batch_run.argtypes = [C.c_void_p, C.c_int32]
-    L.rs_batch_run_async.argtypes = [C.c_void_p, C.c_int32]
-    L.rs_batch_sync.argtypes = [C.c_void_p]
-    L.rs_batch_run_logged.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int16), C.POINTER(C.c_int32),
-                                      C.POINTER(C.c_int16), C.POINTER(C.c_int16), C.POINTER(C.c_int32)]
-    L.rs_batch_run_timed.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_float)]
-    L.rs_batch_read_state.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64),
-                                      C.POINTER(C.c_int64), C.POINTER(C.c_double)]
-    L.rs_batch_write_state.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    L.rs_batch_slice_bytes_device.argtypes = [C.c_void_p, C.c_void_p]
-    L.rs_batch_slice_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-    L.rs_jit_selfcheck.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
-    L.rs_jit_selfcheck_queue.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
-    L.rs_batch_debug_stamps.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint64)]
-    L.rs_batch_debug_heap_sorts.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-    L.rs_ctx_debug_heap_sorts.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-    L.rs_jit_cache_stats.argtypes = [C.POINTER(C.c_longlong)]
-    L.rs_jit_cache_stats.restype = None
-    L.rs_jit_cache_file.argtypes = [C.c_int] * 7 + [C.c_char_p, C.c_size_t]
-    L.rs_jit_cache_warm.argtypes = [C.c_int] * 7 + [C.c_char_p, C.c_size_t]
-    L.rs_batch_autotune_report.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
-    L.rs_batch_debug_clocks.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    L.rs_batch_checkpoint_bytes.restype = C.c_int64
-    L.rs_batch_checkpoint_bytes.argtypes = [C.c_void_p]
-    L.rs_batch_checkpoint_save.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    L.rs_batch_checkpoint_load.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    L.rs_batch_ttis_done.restype = C.c_int64
-    L.rs_batch_ttis_done.argtypes = [C.c_void_p]
-    L.rs_batch_stream.restype = C.c_void_p
-    L.rs_batch_stream.argtypes = [C.c_void_p]
-    L.rs_batch_kernel_name.restype = C.c_char_p
-    L.rs_batch_kernel_name.argtypes = [C.c_void_p]
-    L.rs_lds_bytes_per_cell.argtypes = [C.c_int] * 5
-    L.rs_device_source_hash.restype = C.c_char_p
-    L.rs_device_source_hash.argtypes = []
-    L.rs_hbm_copy_probe.argtypes = [C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_double)]
-    L.rs_trace_read_mapping.argtypes = [C.c_char_p, C.POINTER(C.c_int32), C.c_int32]
-    L.rs_trace_read_ue_log.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8),
-                                       C.POINTER(C.c_uint8)]
-    L.rs_trace_load_dir.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -308,7 +284,25 @@ def _count(rc):
 
 
 def _p(a, t):
-    return a.ctypes.data_as(C.POINTER(t))
+    """a's data as a t* that keeps `a` alive; NULL for None.  The pointer to a's buffer costs a third of ndarray.ctypes.data_as, which
+    builds a Python object per array; a read-only or empty array has no such buffer and takes that way."""
+    if a is None:
+        return None
+    try:
+        return C.POINTER(t)(t.from_buffer(a))
+    except (TypeError, ValueError, BufferError):
+        return a.ctypes.data_as(C.POINTER(t))
+
+
+def _opt(x, dtype, shape=None):
+    """An optional argument as a contiguous array of this dtype (and shape), or None: _p makes the NULL pointer of it.  (The refusals
+    of the group calls are raised, not asserted: they hold under python -O too.)"""
+    if x is None:
+        return None
+    a = np.ascontiguousarray(x, dtype)
+    if shape is not None and a.shape != shape:
+        raise AssertionError(f"an array of shape {a.shape} where {shape} is expected")
+    return a
 
 
 def jit_selfcheck(n_slices, n_users, n_rbgs, rbg_size, threads=512, sched=RS_SCHED_MAXCELL, queues=False, untuned=False, dropin=False,
@@ -321,21 +315,13 @@ def jit_selfcheck(n_slices, n_users, n_rbgs, rbg_size, threads=512, sched=RS_SCH
     group=True, counted=True: the two builds of the group's counted kernel (rs_group_specialize_counted; the queued form's schedulers).
     group=True, flows=True: the two builds of the group's flows kernel (rs_group_specialize_flows; scheduler 1).
     group=True, resident=True, run=True: the two builds of the group's run kernel (rs_group_specialize_run; never schedulers 7 and 11)."""
-    _jit_flags(False, False, group, resident, queued, counted, flows, run)
+    form = _group_form(group, resident, queued, counted, flows, run)
     buf = C.create_string_buffer(4096)
     fn = lib().rs_jit_selfcheck_queue if queues else (lib().rs_jit_selfcheck_untuned if untuned else lib().rs_jit_selfcheck)
     if dropin:  # the drop-in entry point's one-TTI kernel of a context of this shape (rs_ctx_specialize)
         fn = lib().rs_jit_selfcheck_dropin
-    if group:
-        fn = lib().rs_jit_selfcheck_group_resident if resident else lib().rs_jit_selfcheck_group
-        if queued:
-            fn = lib().rs_jit_selfcheck_group_queued
-        if counted:
-            fn = lib().rs_jit_selfcheck_group_counted
-        if flows:
-            fn = lib().rs_jit_selfcheck_group_flows
-        if run:
-            fn = lib().rs_jit_selfcheck_group_run
+    if form:
+        fn = getattr(lib(), form.selfcheck)
     n = fn(n_slices, n_users, n_rbgs, rbg_size, threads, sched, buf, 4096)
     if n < 0:
         raise RadioSaberError(n, buf.value.decode(errors="replace"))
@@ -349,29 +335,36 @@ def jit_cache_stats():
     return dict(zip(("hits", "misses", "stores", "rejected"), (int(x) for x in out)))
 
 
+_FORM_KEYWORDS = ("run", "flows", "counted", "queued", "resident", "group")  # the most specific first: the one a refusal names
+
+
+def _group_form(group, resident, queued=False, counted=False, flows=False, run=False):
+    """The row of GROUP_FORMS that these keywords select (None when none is set: not a group's kernel); ValueError for a set that is
+    no row, naming the first keyword that lacks what every form with it has, or meets one that no form with it has."""
+    given = frozenset(k for k, v in zip(_FORM_KEYWORDS, (run, flows, counted, queued, resident, group)) if v)
+    on = given | {"queued"} if counted else given
+    if not on:
+        return None
+    for form in GROUP_FORMS:
+        if form.keywords == on:
+            return form
+
+    def named(keywords):
+        return " and ".join(f"{k}=True" for k in reversed(_FORM_KEYWORDS) if k in keywords)
+    for k in _FORM_KEYWORDS:
+        if k in on:
+            rows = [form.keywords for form in GROUP_FORMS if k in form.keywords]
+            needs, excludes = frozenset.intersection(*rows) - on, on - frozenset.union(*rows)
+            if needs:
+                raise ValueError(f"{k}=True needs {named(needs)}: a group's kernel has no form with {k}=True otherwise")
+            if excludes:
+                raise ValueError(f"{k}=True excludes {named(excludes & given)}: a group's kernel has no form with all of them")
+    raise ValueError(f"{named(on)} select no form of a group's kernel")
+
+
 def _jit_flags(lean, streamed, group, resident, queued=False, counted=False, flows=False, run=False):
-    if run and not (group and resident):
-        raise ValueError("run=True needs group=True and resident=True: the run kernel is the resident form's")
-    if run and (queued or counted or flows):
-        raise ValueError("run=True excludes queued=True, counted=True and flows=True: only the resident form has a run")
-    if counted and not group:
-        raise ValueError("counted=True needs group=True: only a group has a counted kernel")
-    if flows and not group:
-        raise ValueError("flows=True needs group=True: only a group has a flows kernel")
-    if counted and resident:
-        raise ValueError("resident=True and counted=True exclude each other: two forms of a group's kernel")
-    if flows and (resident or queued or counted):
-        raise ValueError("flows=True excludes resident=True, queued=True and counted=True: a form of a group's kernel of its own")
-    if counted:
-        queued = True  # (the counted form is the queued form's twin: flag value 64 is valid only together with 32)
-    if resident and not group:
-        raise ValueError("resident=True needs group=True: only a group has a resident kernel")
-    if queued and not group:
-        raise ValueError("queued=True needs group=True: only a group has a queued kernel")
-    if queued and resident:
-        raise ValueError("resident=True and queued=True exclude each other: two forms of a group's kernel")
-    return (4 if lean else 0) | (2 if streamed else 0) | (8 if group else 0) | (16 if resident else 0) | (32 if queued else 0) | \
-        (64 if counted else 0) | (128 if flows else 0) | (256 if run else 0)
+    form = _group_form(group, resident, queued, counted, flows, run)
+    return (4 if lean else 0) | (2 if streamed else 0) | (form.flags if form else 0)
 
 
 def jit_cache_file(n_slices, n_users, n_rbgs, rbg_size, threads=512, sched=RS_SCHED_MAXCELL, lean=False, streamed=False, group=False,
@@ -490,7 +483,7 @@ def read_ue_trace(path, nb_rbs=512, rbg_size=8, n_rows=475, per_prb=False):
     rbg = np.zeros((n_rows, R), dtype=np.uint8)
     prb = np.zeros((n_rows, nb_rbs), dtype=np.uint8) if per_prb else None
     rc = _count(lib().rs_trace_read_ue_log(os.fsencode(str(path)), n_rows, nb_rbs, rbg_size, _p(rbg, C.c_uint8),
-                                           _p(prb, C.c_uint8) if per_prb else None))
+                                           _p(prb, C.c_uint8)))
     return (prb if per_prb else rbg), rc
 
 
@@ -620,35 +613,22 @@ def _marshal_tti(S, R, rbg_size, sched, cqi, avg_rate, rand0=0, rand1=0, user_id
         cqi = np.ascontiguousarray(cqi, np.uint8)
         n = cqi.shape[0]
         assert cqi.shape == (n, R)
-    avg = None if avg_rate is None else np.ascontiguousarray(avg_rate, np.float64)  # (None: a resident call, GroupScheduler.schedule_tti_at)
-    assert avg is None or avg.shape == (n,)
-    uid = None if user_id is None else np.ascontiguousarray(user_id, np.int32)
-    hol = None if hol_delay is None else np.ascontiguousarray(hol_delay, np.float64)
-    prio = None if prio_has_data is None else np.ascontiguousarray(prio_has_data, np.uint8)
-    draws = None if rand_draws is None else np.ascontiguousarray(rand_draws, np.int32)
+    avg = _opt(avg_rate, np.float64, (n,))  # (None: a resident call, GroupScheduler.schedule_tti_at)
+    uid, hol, prio = _opt(user_id, np.int32), _opt(hol_delay, np.float64), _opt(prio_has_data, np.uint8)
+    draws = _opt(rand_draws, np.int32)
     assert draws is None or draws.size == 300 * n
-    req = None if required_rbs is None else np.ascontiguousarray(required_rbs, np.int32)
-    dat = None if data_to_transmit is None else np.ascontiguousarray(data_to_transmit, np.int32)
-    assert (req is None or req.shape == (n,)) and (dat is None or dat.shape == (n,))
+    req, dat = _opt(required_rbs, np.int32, (n,)), _opt(data_to_transmit, np.int32, (n,))
     res = TtiResult(np.zeros(S, np.int32), np.zeros(S, np.int32), np.zeros(R, np.int32),
                     np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32))
-    tin = _TtiIn(n, _p(uid, C.c_int32) if uid is not None else None,
-                 _p(cqi, C.c_uint8) if cqi is not None else None, _p(avg, C.c_double) if avg is not None else None, rand0, rand1,
-                 _p(prb, C.c_uint8) if prb is not None else None,
-                 _p(hol, C.c_double) if hol is not None else None,
-                 _p(prio, C.c_uint8) if prio is not None else None,
-                 _p(draws, C.c_int32) if draws is not None else None,
-                 _p(req, C.c_int32) if req is not None else None,
-                 _p(dat, C.c_int32) if dat is not None else None, int(cqi_epoch))
+    tin = _TtiIn(n, _p(uid, C.c_int32), _p(cqi, C.c_uint8), _p(avg, C.c_double), rand0, rand1, _p(prb, C.c_uint8), _p(hol, C.c_double),
+                 _p(prio, C.c_uint8), _p(draws, C.c_int32), _p(req, C.c_int32), _p(dat, C.c_int32), int(cqi_epoch))
     if sched == RS_SCHED_UPPERBOUND:
         res.upper_rbg = np.full((S, R), -1, np.int32)
         res.upper_user = np.full((S, R), -1, np.int32)
     tout = _TtiOut(_p(res.target_rbs, C.c_int32), _p(res.quota_rbgs, C.c_int32),
                    _p(res.rbg_to_user, C.c_int32), _p(res.user_nprb, C.c_int32),
                    _p(res.user_final_cqi, C.c_int32), _p(res.user_mcs, C.c_int32),
-                   _p(res.user_tbs_bits, C.c_int32),
-                   _p(res.upper_rbg, C.c_int32) if res.upper_rbg is not None else None,
-                   _p(res.upper_user, C.c_int32) if res.upper_user is not None else None)
+                   _p(res.user_tbs_bits, C.c_int32), _p(res.upper_rbg, C.c_int32), _p(res.upper_user, C.c_int32))
     return tin, tout, res, (cqi, prb, avg, uid, hol, prio, draws, req, dat)
 
 
@@ -713,6 +693,22 @@ class TtiScheduler:
         _check(lib().rs_set_slice_offset(self._h, _p(a, C.c_double)))
 
 
+class _GroupCall(NamedTuple):
+    """One group call as GroupScheduler._marshal leaves it; whoever holds it keeps every array alive that the pointers name."""
+    n: int
+    ids: object      # int32* [n], or None
+    ins: object      # rs_tti_in [n]
+    outs: object     # rs_tti_out [n], of a run [n][max(T, 1)]
+    now: object      # double* [n], of a run [n][T]; None for the call without a clock
+    column: object   # the pointer column asked for, or None
+    sent: object     # the pointer column to the results' sent rows, or None
+    results: list
+    keep: list
+
+
+_NO_CLOCK = object()  # (not None: a clock of None is a NaN, as np.asarray reads it)
+
+
 class GroupScheduler:
     """Drop-in mode for a host that owns several cells: one TTI of up to n_cells cells in one kernel launch, one workgroup per cell
     (rs_group_create / rs_group_schedule_tti).  Cell k behaves exactly like a TtiScheduler of its own."""
@@ -730,85 +726,74 @@ class GroupScheduler:
         self._h = lib().rs_group_create_checked(C.byref(self._cfg.c), n_cells, RS_ABI_VERSION, C.sizeof(_Config))
         if not self._h:
             raise RadioSaberError(-1, lib().rs_last_error().decode())
-        if jit:
-            self.specialize()
-        if jit_resident:
-            self.specialize_resident()
-        if jit_queued:
-            self.specialize_queued()
-        if jit_counted:
-            self.specialize_counted()
-        if jit_flows:
-            self.specialize_flows()
-        if jit_run:
-            self.specialize_run()
+        for form, asked in zip(GROUP_FORMS, (jit, jit_resident, jit_queued, jit_counted, jit_flows, jit_run)):
+            if asked:
+                self._specialize(form.key)
+
+    def _specialize(self, key):
+        _check(getattr(lib(), _FORM[key].specialize)(self._h))
+
+    def _jit_status(self, key):
+        buf = C.create_string_buffer(768)
+        rc = getattr(lib(), _FORM[key].jit_status)(self._h, buf, 768)
+        return rc, buf.value.decode(errors="replace")
 
     def specialize(self):
         """rs_group_specialize: the group's own hiprtc builds of the one-TTI kernel (identical results; their first calls run beside
         the built-in kernel unless the builds carry the self-check mark: jit_status()).  Any time between two calls; again: a no-op."""
-        _check(lib().rs_group_specialize(self._h))
+        self._specialize("")
 
     def jit_status(self):
         """(code, message) of rs_group_jit_status: 1 the group's builds serve, 0 not asked for, -1 build failed, -2 dropped by the self-check."""
-        buf = C.create_string_buffer(768)
-        rc = lib().rs_group_jit_status(self._h, buf, 768)
-        return rc, buf.value.decode(errors="replace")
+        return self._jit_status("")
 
     def specialize_resident(self):
         """rs_group_specialize_resident: the group's own hiprtc builds of the RESIDENT kernel, for schedule_tti_at (identical results;
         their first calls run beside the built-in resident kernel and are compared on outputs and on state -- slice state, averages,
         pending bytes, last update -- unless the builds carry the self-check mark: resident_jit_status()).  Independent of
         specialize(); any time between two calls; again: a no-op."""
-        _check(lib().rs_group_specialize_resident(self._h))
+        self._specialize("resident")
 
     def resident_jit_status(self):
         """(code, message) of rs_group_resident_jit_status, for the resident builds alone: 1 they serve the resident calls, 0 not asked
         for, -1 build failed, -2 dropped by the self-check."""
-        buf = C.create_string_buffer(768)
-        rc = lib().rs_group_resident_jit_status(self._h, buf, 768)
-        return rc, buf.value.decode(errors="replace")
+        return self._jit_status("resident")
 
     def specialize_queued(self):
         """rs_group_specialize_queued: the group's own hiprtc builds of the QUEUED kernel, for schedule_tti_queued (identical results;
         their first calls run beside the built-in queued kernel and are compared on outputs and on state -- slice state, both bearers'
         averages and pending bytes of every user, last update -- unless the builds carry the self-check mark: queued_jit_status()).
         Independent of specialize() and specialize_resident(); any time between two calls; again: a no-op."""
-        _check(lib().rs_group_specialize_queued(self._h))
+        self._specialize("queued")
 
     def queued_jit_status(self):
         """(code, message) of rs_group_queued_jit_status, for the queued builds alone: 1 they serve the queued calls, 0 not asked for,
         -1 build failed, -2 dropped by the self-check."""
-        buf = C.create_string_buffer(768)
-        rc = lib().rs_group_queued_jit_status(self._h, buf, 768)
-        return rc, buf.value.decode(errors="replace")
+        return self._jit_status("queued")
 
     def specialize_counted(self):
         """rs_group_specialize_counted: the group's own hiprtc builds of the COUNTED kernel, for schedule_tti_counted (identical results;
         their first calls run beside the built-in counted kernel and are compared on outputs, sent rows and state -- slice state, both
         bearers' averages, pending bytes, cum_bytes and cum_rbs of every user, last update -- unless the builds carry the self-check
         mark: counted_jit_status()).  Independent of the other pairs; any time between two calls; again: a no-op."""
-        _check(lib().rs_group_specialize_counted(self._h))
+        self._specialize("counted")
 
     def counted_jit_status(self):
         """(code, message) of rs_group_counted_jit_status, for the counted builds alone: 1 they serve the counted calls, 0 not asked
         for, -1 build failed, -2 dropped by the self-check."""
-        buf = C.create_string_buffer(768)
-        rc = lib().rs_group_counted_jit_status(self._h, buf, 768)
-        return rc, buf.value.decode(errors="replace")
+        return self._jit_status("counted")
 
     def specialize_flows(self):
         """rs_group_specialize_flows: the group's own hiprtc builds of scheduler 1's FLOWS kernel, for schedule_tti_flows (identical
         results; their first calls run beside the built-in flows kernel and are compared on outputs and on state -- slice state, both
         bearers' averages, pending bytes, cum_bytes and cum_rbs of every user, last update -- unless the builds carry the self-check
         mark: flows_jit_status()).  Independent of the other pairs; any time between two calls; again: a no-op."""
-        _check(lib().rs_group_specialize_flows(self._h))
+        self._specialize("flows")
 
     def flows_jit_status(self):
         """(code, message) of rs_group_flows_jit_status, for the flows builds alone: 1 they serve the flows calls, 0 not asked for,
         -1 build failed, -2 dropped by the self-check."""
-        buf = C.create_string_buffer(768)
-        rc = lib().rs_group_flows_jit_status(self._h, buf, 768)
-        return rc, buf.value.decode(errors="replace")
+        return self._jit_status("flows")
 
     def specialize_run(self):
         """rs_group_specialize_run: the group's own hiprtc builds of the RUN kernel, for run_at (identical results; their first runs
@@ -816,14 +801,12 @@ class GroupScheduler:
         averages and pending bytes of every user id, last update -- unless the builds carry the self-check mark: run_jit_status()).
         Independent of the other five pairs -- specialize_resident() does not reach runs, this does not reach schedule_tti_at --; any
         time between two calls; again: a no-op."""
-        _check(lib().rs_group_specialize_run(self._h))
+        self._specialize("run")
 
     def run_jit_status(self):
         """(code, message) of rs_group_run_jit_status, for the run builds alone: 1 they serve the runs, 0 not asked for, -1 build
         failed, -2 dropped by the self-check."""
-        buf = C.create_string_buffer(768)
-        rc = lib().rs_group_run_jit_status(self._h, buf, 768)
-        return rc, buf.value.decode(errors="replace")
+        return self._jit_status("run")
 
     def close(self):
         if getattr(self, "_h", None):
@@ -832,23 +815,66 @@ class GroupScheduler:
 
     __del__ = close
 
+    _COLUMNS = {"data_to_transmit": (np.int32, C.c_int32, (2,)), "flow_bearer": (np.uint8, C.c_uint8, ())}  # dtype, C type, shape after [n]
+
+    def _marshal(self, calls, cell_ids, now=_NO_CLOCK, T=None, need_avg=False, update_only=False, column=None, sent=False):
+        """The arguments of one group call, as a _GroupCall.  now: broadcast to [n], or to [n][T] for a run of T TTIs, whose slots get
+        max(T, 1) rs_tti_out each and a row of results.  need_avg: every slot gives avg_rate.  update_only: a slot may be
+        dict(n_users=0).  column: the slot key that fills a pointer per slot ([n][2] int32 data_to_transmit, [n] uint8 flow_bearer)
+        instead of going to _marshal_tti.  sent: every result gets its .sent [n][2], and the slots a pointer column to them."""
+        n, m = len(calls), 1 if T is None else max(T, 1)
+        S, R = self.slices.n_slices, self.R
+        ins, outs, results, keep = (_TtiIn * n)(), (_TtiOut * (n * m))(), [], []
+        col = sent_col = None
+        if column is not None:
+            dtype, ctype, tail = self._COLUMNS[column]
+            col = (C.POINTER(ctype) * n)()
+        if sent:
+            sent_col = (C.POINTER(C.c_int32) * n)()
+        for k, kw in enumerate(calls):
+            kw = dict(kw)
+            if update_only and kw.get("n_users", None) == 0:  # (ins[k] stays zero: no users, the cell's update alone)
+                if len(kw) != 1:
+                    raise AssertionError("an update-only slot gives nothing but n_users=0")
+                z = np.zeros(0, np.int32)
+                res = TtiResult(np.zeros(S, np.int32), np.zeros(S, np.int32), np.zeros(R, np.int32), z, z.copy(), z.copy(), z.copy())
+                outs[k] = _TtiOut(_p(res.target_rbs, C.c_int32), _p(res.quota_rbgs, C.c_int32), _p(res.rbg_to_user, C.c_int32))
+                if sent:
+                    res.sent = np.zeros((0, 2), np.int32)
+                results.append(res)
+                continue
+            if column is not None:
+                x = np.ascontiguousarray(kw.pop(column), dtype)
+            cqi, avg = kw.pop("cqi", None), kw.pop("avg_rate") if need_avg else kw.pop("avg_rate", None)
+            row = []
+            for j in range(m):  # (a run: one rs_tti_out per TTI; the rs_tti_in is the first one's)
+                tin, tout, res, arrays = _marshal_tti(S, R, self.rbg_size, self.sched, cqi, avg, **kw)
+                if j == 0:
+                    ins[k] = tin
+                outs[k * m + j] = tout
+                row.append(res)
+                keep.append(arrays)
+            results.append(res if T is None else row[:T])
+            if column is not None:
+                if x.shape != (tin.n_users,) + tail:
+                    raise AssertionError(f"{column} of shape {x.shape} for {tin.n_users} users")
+                col[k] = _p(x, ctype)
+                keep.append(x)
+            if sent:
+                res.sent = np.zeros((tin.n_users, 2), np.int32)
+                sent_col[k] = _p(res.sent, C.c_int32)
+        t = None if now is _NO_CLOCK else np.ascontiguousarray(np.broadcast_to(np.asarray(now, np.float64), (n,) if T is None else (n, T)))
+        ids = _opt(cell_ids, np.int32, (n,))
+        keep += [t, ids]
+        return _GroupCall(n, _p(ids, C.c_int32), ins, outs, _p(t, C.c_double), col, sent_col, results, keep)
+
     def schedule_tti(self, calls: Sequence[dict], cell_ids: Optional[Sequence[int]] = None) -> List[TtiResult]:
         """calls[k]: the keyword arguments of TtiScheduler.schedule_tti for cell cell_ids[k] (None: cell k).  Optional inputs are
         given by every cell of a call or by none (a mixed call raises, nothing is launched).  cqi_epoch counts per cell: a cell whose
         call repeats the number, users and kind of report of its last stored call is served from its device-resident image."""
-        n = len(calls)
-        ins, outs, results, keep = (_TtiIn * n)(), (_TtiOut * n)(), [], []
-        for k, kw in enumerate(calls):
-            kw = dict(kw)
-            tin, tout, res, arrays = _marshal_tti(self.slices.n_slices, self.R, self.rbg_size, self.sched, kw.pop("cqi", None),
-                                                  kw.pop("avg_rate"), **kw)
-            ins[k], outs[k] = tin, tout
-            results.append(res)
-            keep.append(arrays)
-        ids = None if cell_ids is None else np.ascontiguousarray(cell_ids, np.int32)
-        assert ids is None or ids.shape == (n,)
-        _check(lib().rs_group_schedule_tti(self._h, n, _p(ids, C.c_int32) if ids is not None else None, ins, outs))
-        return results
+        c = self._marshal(calls, cell_ids, need_avg=True)
+        _check(lib().rs_group_schedule_tti(self._h, c.n, c.ids, c.ins, c.outs))
+        return c.results
 
     # ---- resident averages: the cell's PF averages, pending bytes and last-update time stay on the device ----
     def set_avg(self, cell, avg, last_update):
@@ -877,20 +903,9 @@ class GroupScheduler:
         """rs_group_schedule_tti_at: schedule_tti for resident cells.  calls[k] as for schedule_tti but without avg_rate; now[k] is
         the simulator clock of that cell's TTI (a scalar: the same for every cell).  Per cell the device applies the reference's
         EWMA to every user's average, schedules the TTI on the result and records the grants for the next update."""
-        n = len(calls)
-        ins, outs, results, keep = (_TtiIn * n)(), (_TtiOut * n)(), [], []
-        for k, kw in enumerate(calls):
-            kw = dict(kw)
-            tin, tout, res, arrays = _marshal_tti(self.slices.n_slices, self.R, self.rbg_size, self.sched, kw.pop("cqi", None),
-                                                  kw.pop("avg_rate", None), **kw)
-            ins[k], outs[k] = tin, tout
-            results.append(res)
-            keep.append(arrays)
-        t = np.ascontiguousarray(np.broadcast_to(np.asarray(now, np.float64), (n,)))
-        ids = None if cell_ids is None else np.ascontiguousarray(cell_ids, np.int32)
-        assert ids is None or ids.shape == (n,)
-        _check(lib().rs_group_schedule_tti_at(self._h, n, _p(ids, C.c_int32) if ids is not None else None, ins, outs, _p(t, C.c_double)))
-        return results
+        c = self._marshal(calls, cell_ids, now)
+        _check(lib().rs_group_schedule_tti_at(self._h, c.n, c.ids, c.ins, c.outs, c.now))
+        return c.results
 
     def run_at(self, calls: Sequence[dict], now, rands=None, cell_ids: Optional[Sequence[int]] = None) -> List[List[TtiResult]]:
         """rs_group_run_at: T consecutive schedule_tti_at calls in one launch.  calls[k] as for schedule_tti_at, given once per cell
@@ -902,50 +917,34 @@ class GroupScheduler:
         """rec: (rec_cap, recs, n_recs) -- the three extra arguments of rs_group_run_records_at (arrays, or None for a NULL pointer)"""
         n = len(calls)
         t = np.asarray(now, np.float64)
-        assert t.ndim in (1, 2) and (t.ndim == 1 or t.shape[0] == n)
+        if t.ndim not in (1, 2) or (t.ndim == 2 and t.shape[0] != n):
+            raise AssertionError("now is neither [T] nor [n][T]")
         T = t.shape[-1]
-        t = np.ascontiguousarray(np.broadcast_to(t, (n, T)))
-        r = None if rands is None else np.ascontiguousarray(rands, np.int32)
-        assert r is None or r.shape == (n, T, 2)
-        ins, outs, results, keep = (_TtiIn * n)(), (_TtiOut * (n * max(T, 1)))(), [], []
-        for k, kw in enumerate(calls):
-            kw = dict(kw)
-            cqi, avg = kw.pop("cqi", None), kw.pop("avg_rate", None)
-            row = []
-            for j in range(max(T, 1)):  # (one rs_tti_out per TTI; the rs_tti_in is the first one's)
-                tin, tout, res, arrays = _marshal_tti(self.slices.n_slices, self.R, self.rbg_size, self.sched, cqi, avg, **kw)
-                if j == 0:
-                    ins[k] = tin
-                outs[k * max(T, 1) + j] = tout
-                row.append(res)
-                keep.append(arrays)
-            results.append(row[:T])
-        ids = None if cell_ids is None else np.ascontiguousarray(cell_ids, np.int32)
-        assert ids is None or ids.shape == (n,)
-        more = () if rec is None else (int(rec[0]), rec[1].ctypes.data if rec[1] is not None else None,
-                                       _p(rec[2], C.c_int32) if rec[2] is not None else None)
-        _check(fn(self._h, n, _p(ids, C.c_int32) if ids is not None else None, ins, T, _p(t, C.c_double),
-                  _p(r, C.c_int32) if r is not None else None, outs if outputs else None, *more))
-        return results if outputs else None
+        r = _opt(rands, np.int32, (n, T, 2))
+        c = self._marshal(calls, cell_ids, t, T)
+        more = () if rec is None else (int(rec[0]), None if rec[1] is None else rec[1].ctypes.data, _p(rec[2], C.c_int32))
+        _check(fn(self._h, n, c.ids, c.ins, T, c.now, _p(r, C.c_int32), c.outs if outputs else None, *more))
+        return c.results if outputs else None
+
+    def _set_counters(self, fn, cell, shape, cum_bytes, cum_rbs, *first):
+        """the counter setters: `first` (set_flows' bearers), then cum_bytes and cum_rbs of this shape or NULL"""
+        cb, cr = _opt(cum_bytes, np.int64, shape), _opt(cum_rbs, np.int64, shape)
+        _check(fn(self._h, cell, *first, _p(cb, C.c_int64), _p(cr, C.c_int64)))
+
+    def _get_counters(self, fn, cell, shape, *first):
+        cb, cr = np.zeros(shape, np.int64), np.zeros(shape, np.int64)
+        _check(fn(self._h, cell, *first, _p(cb, C.c_int64), _p(cr, C.c_int64)))
+        return cb, cr
 
     # ---- counted runs: m_cumulateBytes / m_cumulateRBs per user of an average-resident cell stay on the device too ----
     def set_avg_counters(self, cell, cum_bytes=None, cum_rbs=None):
         """rs_group_set_avg_counters: makes an average-resident `cell` avg-counted with cum_bytes / cum_rbs int64 [n_users] by user id
         (None: zeros).  Any time between two calls; outside the fast path."""
-        U = self.slices.n_users
-        cb = None if cum_bytes is None else np.ascontiguousarray(cum_bytes, np.int64)
-        cr = None if cum_rbs is None else np.ascontiguousarray(cum_rbs, np.int64)
-        assert (cb is None or cb.shape == (U,)) and (cr is None or cr.shape == (U,))
-        _check(lib().rs_group_set_avg_counters(self._h, cell, _p(cb, C.c_int64) if cb is not None else None,
-                                               _p(cr, C.c_int64) if cr is not None else None))
+        self._set_counters(lib().rs_group_set_avg_counters, cell, (self.slices.n_users,), cum_bytes, cum_rbs)
 
     def get_avg_counters(self, cell):
         """(cum_bytes int64 [n_users], cum_rbs int64 [n_users]) of an avg-counted cell: a synchronising copy, not part of a TTI."""
-        U = self.slices.n_users
-        cb = np.zeros(U, np.int64)
-        cr = np.zeros(U, np.int64)
-        _check(lib().rs_group_get_avg_counters(self._h, cell, _p(cb, C.c_int64), _p(cr, C.c_int64)))
-        return cb, cr
+        return self._get_counters(lib().rs_group_get_avg_counters, cell, (self.slices.n_users,))
 
     def run_counted_at(self, calls: Sequence[dict], now, rands=None, cell_ids: Optional[Sequence[int]] = None, outputs=True,
                        records=False, rec_cap=None):
@@ -996,62 +995,22 @@ class GroupScheduler:
         return self._schedule_queued(calls, now, cell_ids, False)
 
     def _schedule_queued(self, calls, now, cell_ids, counted):
-        n = len(calls)
-        S, R = self.slices.n_slices, self.R
-        ins, outs, results, keep = (_TtiIn * n)(), (_TtiOut * n)(), [], []
-        data = (C.POINTER(C.c_int32) * n)()
-        sent = (C.POINTER(C.c_int32) * n)()
-        for k, kw in enumerate(calls):
-            kw = dict(kw)
-            if kw.get("n_users", None) == 0:
-                assert len(kw) == 1, "an update-only slot gives nothing but n_users=0"
-                z = np.zeros(0, np.int32)
-                res = TtiResult(np.zeros(S, np.int32), np.zeros(S, np.int32), np.zeros(R, np.int32), z, z.copy(), z.copy(), z.copy())
-                ins[k] = _TtiIn()
-                outs[k] = _TtiOut(_p(res.target_rbs, C.c_int32), _p(res.quota_rbgs, C.c_int32), _p(res.rbg_to_user, C.c_int32),
-                                  None, None, None, None, None, None)
-                if counted:
-                    res.sent = np.zeros((0, 2), np.int32)
-                results.append(res)
-                continue
-            d = np.ascontiguousarray(kw.pop("data_to_transmit"), np.int32)
-            tin, tout, res, arrays = _marshal_tti(S, R, self.rbg_size, self.sched, kw.pop("cqi", None), kw.pop("avg_rate", None), **kw)
-            assert d.shape == (tin.n_users, 2)
-            ins[k], outs[k] = tin, tout
-            data[k] = _p(d, C.c_int32)
-            if counted:
-                res.sent = np.zeros((tin.n_users, 2), np.int32)
-                sent[k] = _p(res.sent, C.c_int32)
-            results.append(res)
-            keep.append((arrays, d))
-        t = np.ascontiguousarray(np.broadcast_to(np.asarray(now, np.float64), (n,)))
-        ids = None if cell_ids is None else np.ascontiguousarray(cell_ids, np.int32)
-        assert ids is None or ids.shape == (n,)
-        idp = _p(ids, C.c_int32) if ids is not None else None
+        c = self._marshal(calls, cell_ids, now, update_only=True, column="data_to_transmit", sent=counted)
         if counted:
-            _check(lib().rs_group_schedule_tti_counted(self._h, n, idp, ins, outs, _p(t, C.c_double), data, sent))
+            _check(lib().rs_group_schedule_tti_counted(self._h, c.n, c.ids, c.ins, c.outs, c.now, c.column, c.sent))
         else:
-            _check(lib().rs_group_schedule_tti_queued(self._h, n, idp, ins, outs, _p(t, C.c_double), data))
-        return results
+            _check(lib().rs_group_schedule_tti_queued(self._h, c.n, c.ids, c.ins, c.outs, c.now, c.column))
+        return c.results
 
     # ---- counted bearers: m_cumulateBytes / m_cumulateRBs of a bearer-resident cell stay on the device too ----
     def set_counters(self, cell, cum_bytes=None, cum_rbs=None):
         """rs_group_set_counters: makes a bearer-resident `cell` counted with cum_bytes / cum_rbs int64 [n_users][2] by user id and
         bearer priority (None: zeros).  Any time between two calls; outside the fast path."""
-        U = self.slices.n_users
-        cb = None if cum_bytes is None else np.ascontiguousarray(cum_bytes, np.int64)
-        cr = None if cum_rbs is None else np.ascontiguousarray(cum_rbs, np.int64)
-        assert (cb is None or cb.shape == (U, 2)) and (cr is None or cr.shape == (U, 2))
-        _check(lib().rs_group_set_counters(self._h, cell, _p(cb, C.c_int64) if cb is not None else None,
-                                           _p(cr, C.c_int64) if cr is not None else None))
+        self._set_counters(lib().rs_group_set_counters, cell, (self.slices.n_users, 2), cum_bytes, cum_rbs)
 
     def get_counters(self, cell):
         """(cum_bytes int64 [n_users][2], cum_rbs int64 [n_users][2]) of a counted cell: a synchronising copy, not part of a TTI."""
-        U = self.slices.n_users
-        cb = np.zeros((U, 2), np.int64)
-        cr = np.zeros((U, 2), np.int64)
-        _check(lib().rs_group_get_counters(self._h, cell, _p(cb, C.c_int64), _p(cr, C.c_int64)))
-        return cb, cr
+        return self._get_counters(lib().rs_group_get_counters, cell, (self.slices.n_users, 2))
 
     def schedule_tti_counted(self, calls: Sequence[dict], now, cell_ids: Optional[Sequence[int]] = None) -> List[TtiResult]:
         """rs_group_schedule_tti_counted: schedule_tti_queued for counted cells, same calls and same results; each bearer credited also
@@ -1067,21 +1026,16 @@ class GroupScheduler:
         U = self.slices.n_users
         h = np.ascontiguousarray(has_bearer, np.uint8)
         a = np.ascontiguousarray(avg, np.float64)
-        cb = None if cum_bytes is None else np.ascontiguousarray(cum_bytes, np.int64)
-        cr = None if cum_rbs is None else np.ascontiguousarray(cum_rbs, np.int64)
-        assert h.shape == (U, 2) and a.shape == (U, 2) and (cb is None or cb.shape == (U, 2)) and (cr is None or cr.shape == (U, 2))
-        _check(lib().rs_group_set_flows(self._h, cell, _p(h, C.c_uint8), _p(a, C.c_double), float(last_update),
-                                        _p(cb, C.c_int64) if cb is not None else None, _p(cr, C.c_int64) if cr is not None else None))
+        assert h.shape == (U, 2) and a.shape == (U, 2)
+        self._set_counters(lib().rs_group_set_flows, cell, (U, 2), cum_bytes, cum_rbs, _p(h, C.c_uint8), _p(a, C.c_double), float(last_update))
 
     def get_flows(self, cell):
         """(avg float64, pending bytes int32, last_update, cum_bytes int64, cum_rbs int64) of a flow-resident cell, the arrays
         [n_users][2] and 0 for a bearer that does not exist: a synchronising copy, not part of a TTI."""
         U = self.slices.n_users
         a, pend = np.zeros((U, 2), np.float64), np.zeros((U, 2), np.int32)
-        cb, cr = np.zeros((U, 2), np.int64), np.zeros((U, 2), np.int64)
         last = C.c_double(0)
-        _check(lib().rs_group_get_flows(self._h, cell, _p(a, C.c_double), _p(pend, C.c_int32), C.byref(last), _p(cb, C.c_int64),
-                                        _p(cr, C.c_int64)))
+        cb, cr = self._get_counters(lib().rs_group_get_flows, cell, (U, 2), _p(a, C.c_double), _p(pend, C.c_int32), C.byref(last))
         return a, pend, float(last.value), cb, cr
 
     def schedule_tti_flows(self, calls: Sequence[dict], now, cell_ids: Optional[Sequence[int]] = None) -> List[TtiResult]:
@@ -1089,34 +1043,9 @@ class GroupScheduler:
         data_to_transmit [n] (> 0), cqi [n][R] or cqi_prb [n][R * rbg_size], cqi_epoch) -- position i is bearer flow_bearer[i] of user
         user_id[i] (None: user i), the pairs ascending; or dict(n_users=0), an update-only slot.  Results are per position, and
         rbg_to_user holds flow ids 2 * user + bearer; the bytes credited to position i are user_tbs_bits[i] // 8."""
-        n = len(calls)
-        S, R = self.slices.n_slices, self.R
-        ins, outs, results, keep = (_TtiIn * n)(), (_TtiOut * n)(), [], []
-        bearer = (C.POINTER(C.c_uint8) * n)()
-        for k, kw in enumerate(calls):
-            kw = dict(kw)
-            if kw.get("n_users", None) == 0:
-                assert len(kw) == 1, "an update-only slot gives nothing but n_users=0"
-                z = np.zeros(0, np.int32)
-                res = TtiResult(np.zeros(S, np.int32), np.zeros(S, np.int32), np.zeros(R, np.int32), z, z.copy(), z.copy(), z.copy())
-                ins[k] = _TtiIn()
-                outs[k] = _TtiOut(_p(res.target_rbs, C.c_int32), _p(res.quota_rbgs, C.c_int32), _p(res.rbg_to_user, C.c_int32),
-                                  None, None, None, None, None, None)
-                results.append(res)
-                continue
-            fb = np.ascontiguousarray(kw.pop("flow_bearer"), np.uint8)
-            tin, tout, res, arrays = _marshal_tti(S, R, self.rbg_size, self.sched, kw.pop("cqi", None), kw.pop("avg_rate", None), **kw)
-            assert fb.shape == (tin.n_users,)
-            ins[k], outs[k] = tin, tout
-            bearer[k] = _p(fb, C.c_uint8)
-            results.append(res)
-            keep.append((arrays, fb))
-        t = np.ascontiguousarray(np.broadcast_to(np.asarray(now, np.float64), (n,)))
-        ids = None if cell_ids is None else np.ascontiguousarray(cell_ids, np.int32)
-        assert ids is None or ids.shape == (n,)
-        _check(lib().rs_group_schedule_tti_flows(self._h, n, _p(ids, C.c_int32) if ids is not None else None, ins, outs, _p(t, C.c_double),
-                                                 bearer))
-        return results
+        c = self._marshal(calls, cell_ids, now, update_only=True, column="flow_bearer")
+        _check(lib().rs_group_schedule_tti_flows(self._h, c.n, c.ids, c.ins, c.outs, c.now, c.column))
+        return c.results
 
     def slice_offset(self, cell):
         out = np.zeros(self.slices.n_slices, np.float64)
@@ -1177,8 +1106,8 @@ class BatchScheduler:
     def seed(self, seeds, rand_skip=None):
         s = np.ascontiguousarray(seeds, np.uint32)
         assert s.shape == (self.n_cells,)
-        k = None if rand_skip is None else np.ascontiguousarray(rand_skip, np.int64)
-        _check(lib().rs_batch_seed(self._h, _p(s, C.c_uint32), _p(k, C.c_int64) if k is not None else None))
+        k = _opt(rand_skip, np.int64)
+        _check(lib().rs_batch_seed(self._h, _p(s, C.c_uint32), _p(k, C.c_int64)))
 
     def upload_cqi_epochs(self, cqi):
         a = np.ascontiguousarray(cqi, np.uint8)
@@ -1241,7 +1170,7 @@ class BatchScheduler:
         ui = np.zeros((self.n_cells, n_ttis, self.U), np.int32)
         keys = np.zeros((self.n_cells, n_ttis, self.R, self.S), np.uint32) if slice_keys else None
         lg = _BatchLog(_p(m, C.c_int16), _p(tb, C.c_int32), _p(q, C.c_int16), _p(tg, C.c_int16), _p(ui, C.c_int32),
-                       _p(keys, C.c_uint32) if slice_keys else None)
+                       _p(keys, C.c_uint32))
         if bearers:
             bb = np.zeros((self.n_cells, n_ttis, self.U, 2), np.int32)
             bh = np.zeros((self.n_cells, n_ttis, self.U, 2), np.float64)
@@ -1297,12 +1226,9 @@ class BatchScheduler:
 
     def write_state(self, avg_rate=None, slice_state=None):
         """Set the PF averages [n_cells][U] (>= 1) and / or the slice state [n_cells][S] between launches (rs_batch_write_state)."""
-        a = None if avg_rate is None else np.ascontiguousarray(avg_rate, np.float64)
-        s = None if slice_state is None else np.ascontiguousarray(slice_state, np.float64)
-        assert a is None or a.shape == (self.n_cells, self.U)
-        assert s is None or s.shape == (self.n_cells, self.S)
-        _check(lib().rs_batch_write_state(self._h, _p(a, C.c_double) if a is not None else None,
-                                          _p(s, C.c_double) if s is not None else None))
+        a = _opt(avg_rate, np.float64, (self.n_cells, self.U))
+        s = _opt(slice_state, np.float64, (self.n_cells, self.S))
+        _check(lib().rs_batch_write_state(self._h, _p(a, C.c_double), _p(s, C.c_double)))
 
     # ---- finite queues (SURVEY 8f N3) ----
     def set_bearers(self, bearer_kind):
