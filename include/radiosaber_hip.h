@@ -28,6 +28,7 @@ extern "C" {
 #define RS_ABI_VERSION 11 /* 11: (additions, no layout changed) rs_batch_flow_record (flow completion times of the queue model),
                                rs_batch_bearer_log + rs_batch_run_logged_bearers (per-bearer DoStopSchedule rows),
                                rs_bearer_record / rs_batch_record_bound / rs_batch_run_records (the same lines from unlogged launches: one 32-byte record per credited bearer),
+                               rs_batch_grant_record / rs_batch_grant_bound / rs_batch_run_grant_records / rs_jit_selfcheck_grant_records (a backlogged batch's app: lines from unlogged launches: one 32-byte record per grant),
                                rs_group_* (one TTI of several drop-in cells in one launch), rs_group_image_stats (cqi_epoch per cell of a group),
                                rs_group_specialize / rs_group_jit_status / rs_jit_selfcheck_group (a group's own self-checked builds of the one-TTI kernel),
                                rs_group_set_avg / rs_group_get_avg / rs_group_set_pending / rs_group_schedule_tti_at (a group cell's PF averages resident on the device),
@@ -974,6 +975,44 @@ typedef struct rs_bearer_record { /* 32 bytes */
 } rs_bearer_record;
 int rs_batch_record_bound(rs_batch* b);
 int rs_batch_run_records(rs_batch* b, int32_t n_ttis, int64_t cap, rs_bearer_record* recs /* [n_cells][cap] */, int64_t* n_recs /* [n_cells] */);
+/* Grant records (ABI 11 addition): the app: lines of a BACKLOGGED batch (no queue model) from an unlogged launch.  The lane that works
+ * out a served user's transport block writes one 32-byte record for it; no dense row is written, and the launch takes the build
+ * rs_batch_run would take -- general, lean or streamed -- in its records variant (a run-time build of its own, compiled at the first
+ * records launch that needs it and self-checked with records on; the general build's variant, then the built-in kernels, are the
+ * fallbacks).
+ *
+ * rs_batch_grant_bound is the most records one cell can get in one TTI: min(n_users, n_rbgs) for schedulers 1, 7, 8, 9, 101 and 103; for
+ * RS_SCHED_UPPERBOUND, whose slices take their RBGs whatever the other slices take, the sum over the config's slices of
+ * min(the slice's users, n_rbgs), as rs_group_grant_bound has it.  RS_ERR_STATE on a batch with the queue model (rs_batch_record_bound
+ * is its bound), RS_ERR_INVALID for RS_SCHED_NVS_NONGREEDY.
+ *
+ * rs_batch_run_grant_records IS rs_batch_run(b, n_ttis) -- the same state, clock, checkpoint bytes and jit status afterwards -- and in
+ * addition n_recs[c] = the (TTI, user) pairs of cell c that DoStopSchedule credits bytes > 0 in these n_ttis, and
+ * recs[c * cap + 0 .. n_recs[c]-1] one record each, ascending in tti, then in user: DoStopSchedule's walk, the order of the log's lines.
+ * Records are output, not state: no checkpoint carries them, and the self-check's and the autotune's trial launches write none into the
+ * caller's lists.  RS_SCHED_UPPERBOUND: rbg_mask holds the RBGs of the user's slice's list that went to it; two records of one TTI may
+ * share a bit.
+ * Refused before anything is launched, the batch does not move: RS_ERR_INVALID for a null argument, cap < 1, n_ttis < 1 or
+ * n_ttis > 32768, and for RS_SCHED_NVS_NONGREEDY (its kernel is another one); RS_ERR_STATE on a batch with the queue model
+ * (rs_batch_run_records is its call); RS_ERR_HIP when the device block cannot be had (RS_RECORDS_MAX_BYTES caps it, as above).
+ * Overflow -- a cell counts more than cap: nothing is written at or behind the capacity, n_recs[c] carries the count as counted, the
+ * launch completes and the call returns RS_ERR_RANGE naming the first such cell.  cap = n_ttis * rs_batch_grant_bound(b) never
+ * overflows.  The device block holds min(cap, n_ttis * bound) places per cell; it is the block rs_batch_run_records uses (a batch is
+ * queue-model or not, and both records are 32 bytes).
+ * rs_batch_jit_status: -2 also once the general build's records variant disagreed with the built-in kernels in its self-check (the
+ * message names cell, record index and field); the built-in kernels then serve the records launches, every other launch keeps its build. */
+typedef struct rs_batch_grant_record { /* 32 bytes, two 16-byte halves */
+  int32_t  tti;       /* scheduled TTI, counted from the batch's first (rs_batch_ttis_done's numbering): launches concatenate */
+  int32_t  user;      /* user id 0..U-1 */
+  int32_t  tbs_bits;  /* what rs_batch_log.tbs_bits holds for (tti, user) */
+  int32_t  bytes;     /* min(tbs_bits / 8, 100000000): what DoStopSchedule credits; never 0 */
+  uint64_t rbg_mask;  /* bit r: RBG r is among the user's allocated RBGs of this TTI */
+  int32_t  nprb;      /* uinfo & 0xffff */
+  uint8_t  final_cqi, mcs; /* uinfo >> 16 & 0xff, uinfo >> 24 */
+  uint16_t reserved;  /* 0 */
+} rs_batch_grant_record;
+int rs_batch_grant_bound(rs_batch* b);
+int rs_batch_run_grant_records(rs_batch* b, int32_t n_ttis, int64_t cap, rs_batch_grant_record* recs /* [n_cells][cap] */, int64_t* n_recs /* [n_cells] */);
 /* `launches` back-to-back launches of n_ttis each, timed with HIP events on the batch's stream;
  * ms_per_launch[launches] receives each launch's duration */
 int rs_batch_run_timed(rs_batch* b, int32_t n_ttis, int32_t launches, float* ms_per_launch);
@@ -1032,6 +1071,10 @@ int rs_jit_selfcheck_untuned(int n_slices, int n_users, int n_rbgs, int rbg_size
 /* the same for the queue-model kernel (the code object rs_batch_set_bearers switches a batch to; schedulers 1, 7, 8, 9, 101, 103) */
 int rs_jit_selfcheck_queue(int n_slices, int n_users, int n_rbgs, int rbg_size, int threads, int sched, char* err,
                            size_t errlen);
+/* the records variant (rs_batch_run_grant_records) of the batch kernel of this shape: lean = 0 the general build, 1 the lean build.
+ * A negative value with the reason in err for RS_SCHED_NVS_NONGREEDY. */
+int rs_jit_selfcheck_grant_records(int n_slices, int n_users, int n_rbgs, int rbg_size, int threads, int sched, int lean,
+                                   char* err, size_t errlen);
 /* ---- the run-time compiled kernels' cache on disk (ABI 10) ----
  * Every code object hiprtc produces (rs_batch_create with jit = 1, the lean / streamed variants, rs_ctx_specialize) is kept in
  * $RS_JIT_CACHE_DIR (default $XDG_CACHE_HOME/radiosaber_amd, else ~/.cache/radiosaber_amd; created with mode 0700), one file per (device

@@ -213,6 +213,8 @@ PROTOTYPES = {
     "rs_batch_run_logged_bearers": (_int, [_ptr, _i32, _P(_BatchLog), _P(_BatchBearerLog)]),
     "rs_batch_record_bound": (_int, [_ptr]),
     "rs_batch_run_records": (_int, [_ptr, _i32, _i64, _ptr, _P(_i64)]),
+    "rs_batch_grant_bound": (_int, [_ptr]),
+    "rs_batch_run_grant_records": (_int, [_ptr, _i32, _i64, _ptr, _P(_i64)]),
     "rs_batch_run_timed": (_int, [_ptr, _i32, _i32, _P(C.c_float)]),
     "rs_batch_read_state": (_int, [_ptr, _P(_f64), _P(_i64), _P(_i64), _P(_f64)]),
     "rs_batch_write_state": (_int, [_ptr, _P(_f64), _P(_f64)]),
@@ -228,6 +230,7 @@ PROTOTYPES = {
     "rs_jit_selfcheck": (_int, _SHAPE + _MSG),
     "rs_jit_selfcheck_untuned": (_int, _SHAPE + _MSG),
     "rs_jit_selfcheck_queue": (_int, _SHAPE + _MSG),
+    "rs_jit_selfcheck_grant_records": (_int, _SHAPE + [_int] + _MSG),
     "rs_jit_cache_stats": (None, [_P(C.c_longlong)]),
     "rs_jit_compiler_identity": (_str, []),
     "rs_jit_cache_file": (_int, _SHAPE + [_int] + _MSG),
@@ -251,6 +254,10 @@ assert GRANT_RECORD.itemsize == 32
 BEARER_RECORD = np.dtype([("tti", np.int32), ("user", np.int32), ("bearer", np.int32), ("bytes", np.int32), ("nprb", np.int32),
                           ("reserved", np.int32), ("hol_delay", np.float64)])
 assert BEARER_RECORD.itemsize == 32
+# one grant of one TTI of a backlogged batch (rs_batch_grant_record, include/radiosaber_hip.h): what BatchScheduler.run_grant_records returns
+BATCH_GRANT_RECORD = np.dtype([("tti", np.int32), ("user", np.int32), ("tbs_bits", np.int32), ("bytes", np.int32), ("rbg_mask", np.uint64),
+                               ("nprb", np.int32), ("final_cqi", np.uint8), ("mcs", np.uint8), ("reserved", np.uint16)])
+assert BATCH_GRANT_RECORD.itemsize == 32
 
 _lib = None
 
@@ -323,6 +330,16 @@ def jit_selfcheck(n_slices, n_users, n_rbgs, rbg_size, threads=512, sched=RS_SCH
     if form:
         fn = getattr(lib(), form.selfcheck)
     n = fn(n_slices, n_users, n_rbgs, rbg_size, threads, sched, buf, 4096)
+    if n < 0:
+        raise RadioSaberError(n, buf.value.decode(errors="replace"))
+    return n
+
+
+def jit_selfcheck_grant_records(n_slices, n_users, n_rbgs, rbg_size, threads=512, sched=RS_SCHED_MAXCELL, lean=False):
+    """Compile the records variant of the batch kernel of one shape (what run_grant_records builds at its first launch; hiprtc, no GPU
+    needed): the general build, or with lean=True the lean one; returns the code size.  Scheduler 11 has none: RadioSaberError."""
+    buf = C.create_string_buffer(4096)
+    n = lib().rs_jit_selfcheck_grant_records(n_slices, n_users, n_rbgs, rbg_size, threads, sched, 1 if lean else 0, buf, 4096)
     if n < 0:
         raise RadioSaberError(n, buf.value.decode(errors="replace"))
     return n
@@ -1202,6 +1219,33 @@ class BatchScheduler:
         recs = np.zeros((self.n_cells, max(int(cap), 1)), BEARER_RECORD)
         n = np.zeros(self.n_cells, np.int64)
         rc = lib().rs_batch_run_records(self._h, n_ttis, cap, recs.ctypes.data_as(C.c_void_p), _p(n, C.c_int64))
+        out = [recs[c, :min(int(n[c]), int(cap))] for c in range(self.n_cells)]  # (views: the block's untouched pages are never mapped)
+        if rc == -5:
+            err = RadioSaberError(rc, lib().rs_last_error().decode())
+            err.records, err.counts = out, n
+            raise err
+        _check(rc)
+        return out
+
+    def grant_bound(self):
+        """rs_batch_grant_bound: the most grants one cell can get in one TTI (backlogged batches; schedulers other than 11)."""
+        return _count(lib().rs_batch_grant_bound(self._h))
+
+    def run_grant_records(self, n_ttis, cap=None, out=None):
+        """run(n_ttis) that also returns, per cell, a BATCH_GRANT_RECORD array with one record per (TTI, user) DoStopSchedule credited
+        in these TTIs, ascending in TTI, then in user: the order of the log's lines (rs_batch_run_grant_records; what
+        logfmt.grant_record_lines reads).  cap: the places per cell, default n_ttis * grant_bound(), which cannot overflow.  A cell that
+        counts more than cap raises RadioSaberError (RS_ERR_RANGE) after the launch has completed; the error carries .records (the lists
+        as far as they were written) and .counts (the counts as counted).  out: a BATCH_GRANT_RECORD array [n_cells][cap] of an earlier
+        call to write into (the returned lists are views of it): a caller that launches again and again spares the host the page faults
+        of a fresh block."""
+        if cap is None:
+            cap = max(int(n_ttis), 1) * self.grant_bound() if out is None else out.shape[1]
+        if out is not None and (out.dtype != BATCH_GRANT_RECORD or out.shape != (self.n_cells, int(cap)) or not out.flags.c_contiguous):
+            raise ValueError("out is not a C-contiguous BATCH_GRANT_RECORD array of shape (n_cells, cap)")
+        recs = np.zeros((self.n_cells, max(int(cap), 1)), BATCH_GRANT_RECORD) if out is None else out
+        n = np.zeros(self.n_cells, np.int64)
+        rc = lib().rs_batch_run_grant_records(self._h, n_ttis, cap, recs.ctypes.data_as(C.c_void_p), _p(n, C.c_int64))
         out = [recs[c, :min(int(n[c]), int(cap))] for c in range(self.n_cells)]  # (views: the block's untouched pages are never mapped)
         if rc == -5:
             err = RadioSaberError(rc, lib().rs_last_error().decode())

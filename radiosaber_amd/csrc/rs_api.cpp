@@ -21,6 +21,7 @@
 #include <cstring>
 #include <new>
 #include <random>
+#include <thread>
 #include <fstream>
 #include <vector>
 
@@ -323,6 +324,14 @@ struct rs_batch {
   RsJitKernel* jit = nullptr; /* shape-specialised kernel (owned by the process-wide cache) */
   RsJitKernel* jit_lean = nullptr; /* its lean build, compiled at the first launch that can use it (launch()) */
   bool jit_lean_tried = false;
+  /* the records variants of the two (-DRS_JIT_RECORDS=1; rs_batch_run_grant_records), [0] general, [1] lean: compiled at the first
+   * records launch that would pick that build, checked with records on before they serve one (selfcheck_records) */
+  RsJitKernel* jit_rec[2] = {nullptr, nullptr};
+  bool jit_rec_tried[2] = {false, false}, jit_rec_checked[2] = {false, false};
+  bool rec_rejected = false;        /* the general records variant disagreed: the built-in kernels serve the records launches */
+  RsJitKernel* force_kernel = nullptr; /* a trial launch of selfcheck_records: this kernel and no other ... */
+  bool force_builtin = false;          /* ... or the built-in kernels */
+  int last_records = 0;             /* the last launch wrote grant records on: 0 it wrote none, 1 the built-in kernels, 2 the general variant, 3 the lean one */
   bool autotuned = false;       /* rs_batch_config.autotune: the candidates were timed (or the tuning does not apply) */
   bool selfchecked = false;     /* the self-check of the run-time builds: done (or it does not apply) */
   bool selfchecked_general = false, selfchecked_lean = false;
@@ -668,13 +677,16 @@ int check_device_err(rs_batch* b) {
  * synthetic-experiment blocks) are compile-time constants there.  Compiled once, at the first launch that qualifies
  * (RS_JIT_LEAN_MIN_TTIS, default 256: short test launches are not worth a hiprtc run; RS_JIT_LEAN=0 switches it off) or by
  * rs_batch_prepare_launch; nullptr = the general kernel (or the built-in ones) serves this launch. */
-RsJitKernel* lean_kernel(rs_batch* b, int n_ttis, bool logged) {
-  if (!b->jit || b->direct || logged) return nullptr;
+bool lean_qualifies(const rs_batch* b, int n_ttis, bool logged) {
+  if (!b->jit || b->direct || logged) return false;
   const char* const e_min = getenv("RS_JIT_LEAN_MIN_TTIS");
   const char* const e_on = getenv("RS_JIT_LEAN");
   const int lean_min = e_min ? atoi(e_min) : 256;
-  if (e_on && atoi(e_on) == 0) return nullptr;
-  if (n_ttis < lean_min || b->cqi_mode != RS_CQI_EPOCHS || b->d_epochs_prb || b->cfg.phy_error_draws || b->synthetic) return nullptr;
+  if (e_on && atoi(e_on) == 0) return false;
+  return !(n_ttis < lean_min || b->cqi_mode != RS_CQI_EPOCHS || b->d_epochs_prb || b->cfg.phy_error_draws || b->synthetic);
+}
+RsJitKernel* lean_kernel(rs_batch* b, int n_ttis, bool logged) {
+  if (!lean_qualifies(b, n_ttis, logged)) return nullptr;
   if (!b->jit_lean_tried) {
     b->jit_lean_tried = true;
     char msg[512] = "";
@@ -688,6 +700,7 @@ RsJitKernel* lean_kernel(rs_batch* b, int n_ttis, bool logged) {
 
 int launch(rs_batch* b, int n_ttis, int16_t* d_map, int16_t* d_quota, int16_t* d_target, int32_t* d_tbs, int32_t* d_uinfo,
            uint32_t* d_keys = nullptr, int32_t* d_bbytes = nullptr, double* d_bhol = nullptr, void* d_recs = nullptr, int64_t rec_cap = 0);
+int records_kernel(rs_batch* b, int n_ttis, RsJitKernel** k, int* which);
 
 /* Everything a batch carries from one launch to the next, as (device pointer, bytes): PF averages, pending grants, cumulative counters,
  * slice state, clock / rand() ring / CQI-report state, and with the queue model the bearers' queues, averages, counters and per-user
@@ -1028,6 +1041,181 @@ int selfcheck(rs_batch* b, int n_ttis, bool logged) {
   return RS_OK;
 }
 
+/* ---- grant records of a backlogged batch (rs_batch_run_grant_records) ---- */
+
+/* The pending-grant words between the two formats (selfcheck() says what they are): to_packed = false, the run-time builds' word to the
+ * plain bytes the built-in kernels read; true, plain bytes to a word whose grant is in the totals already (the built-in kernels count at
+ * grant time).  Only where the built-in kernels serve one launch of a batch whose other launches run on the run-time builds. */
+int convert_tx(rs_batch* b, bool to_packed) {
+  std::vector<int32_t> tx((size_t)b->n_cells * b->U);
+  if (hipStreamSynchronize(b->stream) != hipSuccess || hipMemcpy(tx.data(), b->d_tx, 4 * tx.size(), hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(RS_ERR_HIP, "grant records: copy of the pending grants failed");
+  for (int32_t& w : tx) w = to_packed ? (w ? ((w & RS_TX_BYTES_MASK) | RS_TX_COUNTED) : 0) : (w & RS_TX_BYTES_MASK);
+  if (hipMemcpy(b->d_tx, tx.data(), 4 * tx.size(), hipMemcpyHostToDevice) != hipSuccess) return fail(RS_ERR_HIP, "grant records: copy of the pending grants failed");
+  return RS_OK;
+}
+
+/* most grants of one cell in one TTI: a grant needs an RBG and goes to one user -- min(U, R); UpperBound's slices take their RBGs
+ * whatever the other slices take: the sum over the slices of min(the slice's users, R), as rs_group_grant_bound has it */
+int grant_bound(const rs_batch* b) {
+  if (b->sched != RS_SCHED_UPPERBOUND) return std::min(b->U, b->R);
+  int sum = 0;
+  for (int u = 0; u < b->U;) {
+    int e = u;
+    while (e < b->U && b->u2s[e] == b->u2s[u]) e++;
+    sum += std::min(e - u, b->R);
+    u = e;
+  }
+  return sum;
+}
+
+/* DoStopSchedule's walk: TTI, then user.  The device hands out all places of TTI k before any of TTI k + 1 and a (TTI, user) occurs once,
+ * so every TTI's stretch is sorted by itself, as rs_batch_run_records does it -- but a stretch comes in lane (RBG) order, which says
+ * nothing about the users' order, and an insertion sort moves a 32-byte record n / 4 times on average: a record's place is the number
+ * of records of the stretch with a smaller user (integer compares, no moves), then one pass through a small buffer.  A stretch longer
+ * than the buffer (UpperBound with many slices) and a list whose TTIs do not ascend go to std::sort. */
+void sort_grant_records(rs_batch_grant_record* r, size_t n) {
+  bool ascending = true;
+  constexpr size_t kBuf = 128;
+  rs_batch_grant_record tmp[kBuf];
+  const auto by_user = [](const rs_batch_grant_record& x, const rs_batch_grant_record& y) { return x.user < y.user; };
+  for (size_t i = 0, j; i < n; i = j) {
+    if (i && r[i].tti < r[i - 1].tti) ascending = false;
+    bool sorted = true;
+    for (j = i + 1; j < n && r[j].tti == r[i].tti; j++) sorted &= r[j - 1].user <= r[j].user;
+    if (sorted) continue;
+    const size_t m = j - i;
+    if (m > kBuf) { std::sort(r + i, r + j, by_user); continue; }
+    memcpy(tmp, r + i, m * sizeof tmp[0]);
+    for (size_t a = 0; a < m; a++) {
+      size_t rank = 0;
+      for (size_t q = 0; q < m; q++) rank += (tmp[q].user < tmp[a].user || (tmp[q].user == tmp[a].user && q < a)) ? 1 : 0;
+      r[i + rank] = tmp[a];
+    }
+  }
+  if (!ascending)
+    std::sort(r, r + n, [](const rs_batch_grant_record& x, const rs_batch_grant_record& y) { return x.tti != y.tti ? x.tti < y.tti : x.user < y.user; });
+}
+
+/* The self-check of a records variant (v: 0 general, 1 lean): a fresh compilation whose new code is the record writing, so it is checked
+ * with records on -- the batch's next min(n, 256) TTIs from one snapshot on the built-in kernels and on the variant, each into a scratch
+ * record block; the final states must agree bit for bit and the sorted lists record for record.  A variant that disagrees is dropped
+ * alone (the caller goes on to the next fallback), rs_batch_jit_status names cell, record index and field.  The snapshot is put back. */
+int selfcheck_records(rs_batch* b, int n_ttis, int v) {
+  RsJitKernel* const k = b->jit_rec[v];
+  b->jit_rec_checked[v] = true;
+  const int policy = selfcheck_policy(b);
+  if (policy == kCheckNever) return RS_OK;
+  if (policy == kCheckUnmarked && rs_jit_is_verified(k)) {
+    snprintf(b->selfcheck_msg, sizeof b->selfcheck_msg, "the records variant of the %s build carries the self-check mark of the process that checked it (cache file)", v ? "lean" : "general");
+    return RS_OK;
+  }
+  if (b->threads > 512) return RS_OK; /* no built-in kernel of this workgroup size to compare with (selfcheck() says so for the plain builds) */
+  b->in_selfcheck = true;
+  struct Leave { rs_batch* b; ~Leave() { b->in_selfcheck = false; b->force_kernel = nullptr; b->force_builtin = false; } } leave{b};
+  const StateParts sp(b);
+  const size_t cells = (size_t)b->n_cells;
+  const int trial = n_ttis < 256 ? n_ttis : 256;
+  const int64_t cap = (int64_t)trial * grant_bound(b);
+  const size_t list_bytes = cells * (size_t)cap * sizeof(RsBatchGrantRecord), block_bytes = list_bytes + 4 * cells;
+  ScratchBuffers scratch;
+  void* snap = nullptr;
+  char* block[2] = {nullptr, nullptr};
+  HIP_TRY(scratch.alloc(&snap, sp.total));
+  HIP_TRY(scratch.alloc(&block[0], block_bytes));
+  HIP_TRY(scratch.alloc(&block[1], block_bytes));
+  const int64_t done0 = b->ttis_done;
+  int rc = RS_OK;
+  StateDigest want, got;
+  if (sp.copy(b, snap, true) != hipSuccess) return fail(RS_ERR_HIP, "selfcheck: snapshot failed");
+  for (int t = 0; t < 2 && rc == RS_OK; t++) { /* t = 0: the built-in kernels, 1: the variant */
+    if (sp.copy(b, snap, false) != hipSuccess) rc = fail(RS_ERR_HIP, "selfcheck: state restore failed");
+    if (!rc && t == 0) rc = convert_tx(b, false);
+    if (!rc && hipMemsetAsync(block[t] + list_bytes, 0, 4 * cells, b->stream) != hipSuccess) rc = fail(RS_ERR_HIP, "selfcheck: record block");
+    b->force_builtin = t == 0;
+    b->force_kernel = t == 0 ? nullptr : k;
+    if (!rc) rc = launch(b, trial, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, block[t], cap);
+    b->force_builtin = false;
+    b->force_kernel = nullptr;
+    if (!rc) rc = state_digest(b, t == 0 ? &want : &got);
+  }
+  /* the two blocks, sorted as the caller's lists are */
+  std::vector<rs_batch_grant_record> list[2];
+  std::vector<uint32_t> count[2];
+  for (int t = 0; t < 2 && rc == RS_OK; t++) {
+    list[t].resize(cells * (size_t)cap);
+    count[t].resize(cells);
+    if (hipMemcpy(count[t].data(), block[t] + list_bytes, 4 * cells, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(RS_ERR_HIP, "selfcheck: copy of the records failed"); break; }
+    for (size_t c = 0; c < cells && rc == RS_OK; c++) {
+      const size_t used = (size_t)std::min((int64_t)count[t][c], cap);
+      if (used && hipMemcpy(list[t].data() + c * (size_t)cap, block[t] + c * (size_t)cap * sizeof(RsBatchGrantRecord), used * sizeof(RsBatchGrantRecord), hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail(RS_ERR_HIP, "selfcheck: copy of the records failed");
+      if (!rc) sort_grant_records(list[t].data() + c * (size_t)cap, used);
+    }
+  }
+  const hipError_t back = sp.copy(b, snap, false);
+  const hipError_t sync = hipStreamSynchronize(b->stream);
+  b->ttis_done = done0;
+  if (back != hipSuccess || sync != hipSuccess) return fail(RS_ERR_HIP, "selfcheck: the cell state could not be put back");
+  if (rc) return rc;
+  rc = check_device_err(b);
+  if (rc) return rc;
+  char why[256] = "";
+  if (got != want) snprintf(why, sizeof why, "left a state that differs from the built-in kernels' in: %s", got.diff(want).c_str());
+  for (size_t c = 0; c < cells && !why[0]; c++) {
+    if (count[0][c] != count[1][c]) { snprintf(why, sizeof why, "wrote %u grant records for cell %zu, the built-in kernels %u", count[1][c], c, count[0][c]); break; }
+    const rs_batch_grant_record *x = list[0].data() + c * (size_t)cap, *y = list[1].data() + c * (size_t)cap;
+    const size_t used = (size_t)std::min((int64_t)count[0][c], cap);
+    for (size_t i = 0; i < used && !why[0]; i++) {
+      const long long fx[9] = {x[i].tti, x[i].user, x[i].tbs_bits, x[i].bytes, (long long)x[i].rbg_mask, x[i].nprb, x[i].final_cqi, x[i].mcs, x[i].reserved};
+      const long long fy[9] = {y[i].tti, y[i].user, y[i].tbs_bits, y[i].bytes, (long long)y[i].rbg_mask, y[i].nprb, y[i].final_cqi, y[i].mcs, y[i].reserved};
+      static const char* const names[9] = {"tti", "user", "tbs_bits", "bytes", "rbg_mask", "nprb", "final_cqi", "mcs", "reserved"};
+      for (int f = 0; f < 9; f++)
+        if (fx[f] != fy[f]) {
+          snprintf(why, sizeof why, "wrote a grant record that differs from the built-in kernels': cell %zu, record %zu, field %s: %lld against %lld", c, i, names[f], fy[f], fx[f]);
+          break;
+        }
+    }
+  }
+  if (why[0]) {
+    rs_jit_reject(k);
+    b->jit_rec[v] = nullptr;
+    if (v == 0) b->rec_rejected = true;
+    snprintf(b->jit_msg, sizeof b->jit_msg, "selfcheck: after %d TTIs the records variant of the %s build %s; it is dropped and %s the records launches", trial,
+             v ? "lean" : "general", why, v ? "the general build's records variant serves" : "the built-in kernels serve");
+    return RS_OK;
+  }
+  rs_jit_mark_verified(k);
+  snprintf(b->selfcheck_msg, sizeof b->selfcheck_msg, "selfcheck over %d TTIs: the built-in kernels and the records variant of the %s build agree, state and records", trial,
+           v ? "lean" : "general");
+  return RS_OK;
+}
+
+/* The kernel of a records launch: the records variant (-DRS_JIT_RECORDS=1) of the build launch() would pick for an unlogged launch of
+ * these TTIs -- lean where it qualifies, streamed where the batch is --, compiled at the first records launch that needs it and checked
+ * with records on; it falls back as the lean build does, to the general build's variant and then (*k = nullptr) to the built-in kernels. */
+int records_kernel(rs_batch* b, int n_ttis, RsJitKernel** k, int* which) {
+  *k = nullptr;
+  if (!b->jit || b->rec_rejected) return RS_OK;
+  for (int v = lean_qualifies(b, n_ttis, false) ? 1 : 0; v >= 0; --v) {
+    if (!b->jit_rec_tried[v]) {
+      b->jit_rec_tried[v] = true;
+      char msg[512] = "";
+      b->jit_rec[v] = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, 0, slice_window(b), msg, sizeof msg,
+                                 (b->cfg.cqi_refresh <= 4 ? 2 : 0) | (v ? 4 : 0), "-DRS_JIT_RECORDS=1");
+      if (!b->jit_rec[v])
+        snprintf(b->jit_msg, sizeof b->jit_msg, "records variant of the %s build unavailable, %s the records launches (%.380s)", v ? "lean" : "general",
+                 v ? "the general build's serves" : "the built-in kernels serve", msg);
+    }
+    if (b->jit_rec[v] && !b->jit_rec_checked[v]) {
+      const int rc = selfcheck_records(b, n_ttis, v); /* (a variant that disagrees is gone afterwards) */
+      if (rc) return rc;
+    }
+    if (b->jit_rec[v]) { *k = b->jit_rec[v]; *which = v; return RS_OK; }
+  }
+  return RS_OK;
+}
+
 int launch(rs_batch* b, int n_ttis, int16_t* d_map, int16_t* d_quota, int16_t* d_target, int32_t* d_tbs, int32_t* d_uinfo,
            uint32_t* d_keys, int32_t* d_bbytes, double* d_bhol, void* d_recs, int64_t rec_cap) {
   if (n_ttis < 1) return fail(RS_ERR_INVALID, "n_ttis %d < 1", n_ttis);
@@ -1071,20 +1259,41 @@ int launch(rs_batch* b, int n_ttis, int16_t* d_map, int16_t* d_quota, int16_t* d
      * the record block and one cell's capacity.  Null in every other launch -- the self-check's and the autotune's trials included. */
     L.grp_sent = (int32_t*)d_recs; L.grp_sent_stride = d_recs ? rec_cap : 0;
   }
+  /* grant records of a backlogged batch (rs_batch_run_grant_records; RsBatchGrantRecord, rs_device.h): the same two words.  Null in every
+   * other launch -- the self-check's and the autotune's trials included; selfcheck_records' trials bring scratch blocks of their own. */
+  const bool records = !b->queues && !b->direct && d_recs != nullptr;
+  if (records) { L.grp_sent = (int32_t*)d_recs; L.grp_sent_stride = rec_cap; }
   const bool logged = d_map || d_quota || d_target || d_tbs || d_uinfo || d_keys || d_bbytes;
-  if (!b->selfchecked && !b->in_selfcheck && b->jit && !b->direct) {
+  /* (a records launch runs none of the plain builds: they are checked at the first launch they serve) */
+  if (!records && !b->selfchecked && !b->in_selfcheck && b->jit && !b->direct) {
     const int rc = selfcheck(b, n_ttis, logged); /* (its trials come back through here with `in_selfcheck` set) */
     if (rc) return rc;
   }
-  if (b->cfg.autotune && !b->autotuned && !logged && !b->in_selfcheck) { /* (never inside a self-check trial: it checks the rule table's build) */
+  if (b->cfg.autotune && !b->autotuned && !logged && !records && !b->in_selfcheck) { /* (never inside a self-check trial: it checks the rule table's build) */
     const int rc = autotune(b, n_ttis);
     if (rc) return rc;
   }
+  RsJitKernel* k = nullptr;
+  bool builtin_beside_jit = false; /* the built-in kernels serve this launch of a batch whose state the run-time builds keep */
+  if (b->force_builtin || b->force_kernel) {
+    k = b->force_kernel;
+  } else if (records) {
+    int which = 0;
+    const int rc = records_kernel(b, n_ttis, &k, &which); /* (compiles and checks the variant at its first launch) */
+    if (rc) return rc;
+    if (!k && b->threads > 512) return fail(RS_ERR_STATE, "grant records: no records variant of the run-time build is available and the built-in kernels stop at 512 threads per cell (%s)", b->jit_msg);
+    b->last_records = k ? 2 + which : 1;
+    builtin_beside_jit = !k && b->jit;
+  } else {
+    k = lean_kernel(b, n_ttis, logged);
+    if (!k) k = b->jit;
+    b->last_records = 0;
+  }
+  if (builtin_beside_jit) { const int rc = convert_tx(b, false); if (rc) return rc; }
   if (L.prio_sum) HIP_TRY(hipMemsetAsync(L.prio_sum, 0, 8, b->stream)); /* (every launch counts from zero) */
-  RsJitKernel* k = lean_kernel(b, n_ttis, logged);
-  if (!k) k = b->jit;
   if (k) HIP_TRY(rs_jit_launch(k, &L, b->stream));
   else HIP_TRY(rs_launch_cells(&L, b->threads, b->stream));
+  if (builtin_beside_jit) { const int rc = convert_tx(b, true); if (rc) return rc; }
   b->ttis_done += n_ttis;
   return RS_OK;
 }
@@ -1422,6 +1631,92 @@ int rs_batch_run_records(rs_batch* b, int32_t n_ttis, int64_t cap, rs_bearer_rec
   if (rc) return rc;
   if (over >= 0)
     return fail(RS_ERR_RANGE, "bearer records: cell %lld credited %lld bearers in these %d TTIs, the lists hold %lld (state, flow record and the other cells' lists are complete)",
+                (long long)over, (long long)n_recs[over], n_ttis, (long long)cap);
+  return RS_OK;
+}
+
+int rs_batch_grant_bound(rs_batch* b) {
+  if (!b) return fail(RS_ERR_INVALID, "null batch");
+  if (b->queues) return fail(RS_ERR_STATE, "grant records: the batch has the queue model, whose records are the bearers' (rs_batch_record_bound / rs_batch_run_records)");
+  if (b->sched == RS_SCHED_NVS_NONGREEDY) return fail(RS_ERR_INVALID, "grant records: scheduler %d runs on another kernel, which writes none", b->sched);
+  return grant_bound(b);
+}
+
+int rs_batch_run_grant_records(rs_batch* b, int32_t n_ttis, int64_t cap, rs_batch_grant_record* recs, int64_t* n_recs) {
+  static_assert(sizeof(rs_batch_grant_record) == sizeof(RsBatchGrantRecord) && offsetof(rs_batch_grant_record, rbg_mask) == offsetof(RsBatchGrantRecord, rbg_mask) &&
+                    offsetof(rs_batch_grant_record, nprb) == offsetof(RsBatchGrantRecord, nprb) && offsetof(rs_batch_grant_record, mcs) == offsetof(RsBatchGrantRecord, mcs),
+                "the device writes the ABI's record");
+  if (!b || !recs || !n_recs) return fail(RS_ERR_INVALID, "null argument");
+  if (cap < 1) return fail(RS_ERR_INVALID, "cap %lld < 1", (long long)cap);
+  if (n_ttis < 1) return fail(RS_ERR_INVALID, "n_ttis %d < 1", n_ttis);
+  if (n_ttis > RS_MAX_TTIS_PER_LAUNCH) return fail(RS_ERR_INVALID, "runs with records are limited to %d TTIs per call", RS_MAX_TTIS_PER_LAUNCH);
+  if (b->queues) return fail(RS_ERR_STATE, "grant records: the batch has the queue model, whose records are the bearers' (rs_batch_run_records)");
+  if (b->sched == RS_SCHED_NVS_NONGREEDY) return fail(RS_ERR_INVALID, "grant records: scheduler %d runs on another kernel, which writes none", b->sched);
+  if (b->direct) return fail(RS_ERR_INVALID, "grant records: not a batch");
+  HIP_TRY(hipSetDevice(b->cfg.cell.device));
+  /* the device block: no cell can count more than n_ttis * bound, so a larger capacity of the caller's needs no larger list there */
+  const size_t cells = (size_t)b->n_cells;
+  const int64_t cap_dev = std::min(cap, (int64_t)n_ttis * grant_bound(b));
+  const size_t list_bytes = cells * (size_t)cap_dev * sizeof(RsBatchGrantRecord), need = list_bytes + 4 * cells;
+  if (need > b->recs_bytes) {
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (b->d_recs) { HIP_TRY(hipFree(b->d_recs)); b->d_recs = nullptr; b->recs_bytes = 0; }
+    /* (RS_RECORDS_MAX_BYTES: as in rs_batch_run_records, a block above it is a failed allocation by the very path of one) */
+    const char* const e_max = getenv("RS_RECORDS_MAX_BYTES");
+    const bool too_large = e_max && (unsigned long long)need > strtoull(e_max, nullptr, 10);
+    if (too_large || hipMalloc(&b->d_recs, need) != hipSuccess) {
+      if (!too_large) (void)hipGetLastError();
+      b->d_recs = nullptr;
+      return fail(RS_ERR_HIP, "grant records: no device block of %zu bytes (%zu cells x %lld records)", need, cells, (long long)cap_dev);
+    }
+    b->recs_bytes = need;
+  }
+  uint32_t* const d_count = (uint32_t*)((char*)b->d_recs + list_bytes);
+  HIP_TRY(hipMemsetAsync(d_count, 0, 4 * cells, b->stream));
+  const auto now = [] { return std::chrono::steady_clock::now(); };
+  const auto t0 = now();
+  int rc = launch(b, n_ttis, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, b->d_recs, cap_dev);
+  if (rc) return rc;
+  rc = rs_batch_sync(b);
+  if (rc == RS_ERR_HIP) return rc;
+  const auto t1 = now();
+  /* the copy back: the counts, then of every list the places that were written (copies queued on the stream, one wait) */
+  std::vector<uint32_t> count(cells);
+  HIP_TRY(hipMemcpy(count.data(), d_count, 4 * cells, hipMemcpyDeviceToHost));
+  int64_t over = -1;
+  for (size_t c = 0; c < cells; c++) {
+    n_recs[c] = (int64_t)count[c];
+    if ((int64_t)count[c] > cap_dev && over < 0) over = (int64_t)c; /* (cap_dev < cap only where nothing can exceed it) */
+    const size_t used = (size_t)std::min((int64_t)count[c], cap_dev);
+    if (used)
+      HIP_TRY(hipMemcpyAsync(recs + c * (size_t)cap, (const RsBatchGrantRecord*)b->d_recs + c * (size_t)cap_dev, used * sizeof(RsBatchGrantRecord),
+                             hipMemcpyDeviceToHost, b->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  const auto t2 = now();
+  {
+    /* the cells' lists are sorted side by side: up to 8 host threads (RS_RECORDS_SORT_THREADS; 1: on the caller's thread) */
+    const char* const e_thr = getenv("RS_RECORDS_SORT_THREADS");
+    size_t n_thr = e_thr ? (size_t)std::max(1, atoi(e_thr)) : std::min<size_t>(8, std::max(1u, std::thread::hardware_concurrency()));
+    size_t total = 0;
+    for (size_t c = 0; c < cells; c++) total += (size_t)std::min((int64_t)count[c], cap_dev);
+    if (total < 65536) n_thr = 1; /* (a thread's start costs more than sorting a few thousand records) */
+    n_thr = std::min(n_thr, cells);
+    const auto work = [&](size_t first) {
+      for (size_t c = first; c < cells; c += n_thr) sort_grant_records(recs + c * (size_t)cap, (size_t)std::min((int64_t)count[c], cap_dev));
+    };
+    std::vector<std::thread> pool;
+    for (size_t k = 1; k < n_thr; k++) pool.emplace_back(work, k);
+    work(0);
+    for (std::thread& th : pool) th.join();
+  }
+  if (getenv("RS_RECORDS_TIMING")) { /* where a call's time goes (tools/bench_grant_records.py, profiles/batch_grant_records.md) */
+    const auto ms = [](auto a, auto z) { return std::chrono::duration<double, std::milli>(z - a).count(); };
+    fprintf(stderr, "rs_batch_run_grant_records: launch and wait %.3f ms, copy back %.3f ms, host sort %.3f ms\n", ms(t0, t1), ms(t1, t2), ms(t2, now()));
+  }
+  if (rc) return rc;
+  if (over >= 0)
+    return fail(RS_ERR_RANGE, "grant records: cell %lld counted %lld grants in these %d TTIs, the lists hold %lld (state and the other cells' lists are complete)",
                 (long long)over, (long long)n_recs[over], n_ttis, (long long)cap);
   return RS_OK;
 }
@@ -1866,7 +2161,7 @@ int rs_batch_prepare_launch(rs_batch* b, int32_t n_ttis) {
 int rs_batch_jit_status(rs_batch* b, char* msg, size_t msglen) {
   if (!b) return fail(RS_ERR_INVALID, "null batch");
   if (msg && msglen) snprintf(msg, msglen, "%s", b->jit_msg);
-  if (b->jit_rejected) return -2;
+  if (b->jit_rejected || b->rec_rejected) return -2; /* (rec_rejected: the records launches alone lost their run-time build) */
   if (msg && msglen && b->jit && !b->jit_msg[0] && b->selfcheck_msg[0]) snprintf(msg, msglen, "%s", b->selfcheck_msg);
   return b->jit ? 1 : (b->jit_wanted ? -1 : 0);
 }
@@ -1899,7 +2194,13 @@ int64_t rs_batch_ttis_done(rs_batch* b) { return b ? b->ttis_done : -1; }
 void* rs_batch_stream(rs_batch* b) { return b ? (void*)b->stream : nullptr; }
 const char* rs_batch_kernel_name(rs_batch* b) {
   if (!b) return "";
-  if (b->jit) return "rs_cell_kernel_jit";
+  /* after a launch with grant records: the build that served it (its records variant; the built-in kernels once the variants are gone) */
+  if (b->last_records >= 2) {
+    const bool streamed = b->cfg.cqi_refresh <= 4;
+    return b->last_records == 3 ? (streamed ? "rs_cell_kernel_jit[lean,streamed,records]" : "rs_cell_kernel_jit[lean,records]")
+                                : (streamed ? "rs_cell_kernel_jit[streamed,records]" : "rs_cell_kernel_jit[records]");
+  }
+  if (b->jit && b->last_records == 0) return "rs_cell_kernel_jit";
   switch (b->sched) {
     case 1: return "rs_cell_kernel<1, 0, false>";
     case 7: return "rs_cell_kernel<7, 0, false>";

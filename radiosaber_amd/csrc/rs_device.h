@@ -60,7 +60,8 @@ struct RsMisc {
   int32_t grid_free;             /* TTIs of this launch whose serial wave is done reading the CQI grid (the next grid may be written over it) */
   int32_t heap_sorts[3];         /* diagnostics: std::__partial_sort fallbacks of this launch, per device site (rs_sort_device.h) */
   int32_t prio_boost;            /* this cell is behind the batch's average progress: its waves ask for one issue-priority level more (RS_SETPRIO) */
-  int32_t pad3[3];
+  int32_t rec_tti;               /* scheduler 10, a launch with grant records (RsBatchGrantRecord): records of the running TTI, the leaders' place counter */
+  int32_t pad3[2];
 };
 
 /* LDS carve of one cell (byte offsets from the dynamic LDS base), a pure function of the cell shape so
@@ -445,6 +446,21 @@ struct RsBearerRecord {
 };
 static_assert(sizeof(RsBearerRecord) == 32 && __builtin_offsetof(RsBearerRecord, nprb) == 16 && __builtin_offsetof(RsBearerRecord, hol_delay) == 24,
               "rs_bearer_record is 32 bytes, the delay the last 8 of its second half");
+/* one grant of one TTI of a backlogged BATCH (rs_batch_run_grant_records; P5 of rs_phase_p5.inc, scheduler 10: rs_phase_p4.inc):
+ * rs_batch_grant_record of the ABI, two 16-byte halves -- tti, user, tbs_bits, bytes | rbg_mask, nprb, final_cqi, mcs, reserved.  The
+ * record block rides where the bearer records' does: grp_sent ([n_cells][cap] records, then one count word per cell) and
+ * grp_sent_stride (one cell's capacity); a batch is queue-model or not, so the two never meet.  Null / 0 in every launch that wants
+ * no records.  The built-in kernels look at the pointer; a run-time build has the switch as a constant (RS_JIT_RECORDS). */
+struct RsBatchGrantRecord {
+  int32_t tti, user, tbs_bits, bytes;
+  uint64_t rbg_mask;
+  int32_t nprb;
+  uint8_t final_cqi, mcs;
+  uint16_t reserved;
+};
+static_assert(sizeof(RsBatchGrantRecord) == 32 && __builtin_offsetof(RsBatchGrantRecord, rbg_mask) == 16 && __builtin_offsetof(RsBatchGrantRecord, nprb) == 24 &&
+                  __builtin_offsetof(RsBatchGrantRecord, final_cqi) == 28 && __builtin_offsetof(RsBatchGrantRecord, mcs) == 29,
+              "rs_batch_grant_record is 32 bytes, the RBG mask opens its second half");
 #define RS_GROUP_RUN_ROW_BYTES 16
 static_assert(sizeof(RsGroupCell) == RS_GROUP_HDR_BYTES, "the slot header keeps its size: new words come out of its padding");
 static_assert(__builtin_offsetof(RsGroupCell, image_mode) == 72 && __builtin_offsetof(RsGroupCell, now) == 80, "no existing word of the slot header moves");

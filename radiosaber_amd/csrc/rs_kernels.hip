@@ -555,6 +555,19 @@ __device__ __forceinline__ void rs_cell_body(const RsLaunch& p, unsigned char* l
   constexpr bool kGridAhead = FIXED && RS_JIT_STREAMED && !DIRECT && (SCHED == 1 || SCHED == 7 || SCHED == 8 || SCHED == 101 || SCHED == 103);
 #endif
   bool grid_ahead = false; /* this TTI's grid was written during the previous TTI's serial phase */
+  /* Grant records of a backlogged batch (rs_batch_run_grant_records; RsBatchGrantRecord, rs_device.h): one record per served user and
+   * TTI into the cell's list, in the order the places are handed out; the cell's count is wave-uniform (schedulers with P5: wave 0
+   * alone writes; scheduler 10: every thread adds the TTI's LDS count behind the closing barrier), rides in a register for the launch
+   * and is stored once, at the end.  The built-in kernels look at the pointer; in a run-time build the switch is the constant
+   * RS_JIT_RECORDS (rs_jit.cpp), so that a build without records carries none of this.  (Group calls and the queue model use the two
+   * words of the launch block for rows and records of their own.) */
+#ifndef RS_JIT_RECORDS
+#define RS_JIT_RECORDS 0
+#endif
+  const bool rec_on = !DIRECT && !QUEUE && (FIXED ? RS_JIT_RECORDS != 0 : p.grp_sent != nullptr);
+  const int rec_cap = rec_on ? (int)p.grp_sent_stride : 0;
+  RsBatchGrantRecord* const rec_list = rec_on ? (RsBatchGrantRecord*)p.grp_sent + (size_t)cell * (size_t)rec_cap : nullptr;
+  int rec_count = 0;
   /* (batches only; a launch argument says how many cells one dispatch round holds: 0 = no balancing) */
   const int prio_class = (!DIRECT && p.prio_round_cells > 0) ? ((int)blockIdx.x / p.prio_round_cells) & 1 : 0;
   const bool prio_windows = !DIRECT && p.prio_round_cells > 0 && p.prio_sum == nullptr;
@@ -662,6 +675,7 @@ __device__ __forceinline__ void rs_cell_body(const RsLaunch& p, unsigned char* l
       pre_listed = rs_lds_load(&m->pad[1]);
     }
     served_prev = m->served;
+    if (SCHED == 10 && rec_on) rec_count += m->rec_tti; /* (the next reset lies behind the next TTI's barriers, as `served`'s does) */
     n_done += 1;
     if (++epoch_pos == p.refresh) {
       epoch_pos = 0;
@@ -727,6 +741,8 @@ __device__ __forceinline__ void rs_cell_body(const RsLaunch& p, unsigned char* l
       scal->cqi_row = cqi_row;
       scal->served_prev = served_prev;
       scal->n_done = n_done;
+      /* the cell's record count as counted, places behind the capacity included: the host tells an overflow by it */
+      if (rec_on) ((uint32_t*)((RsBatchGrantRecord*)p.grp_sent + (size_t)p.n_cells * (size_t)rec_cap))[cell] = (uint32_t)rec_count;
       scal->clk_end = __builtin_readcyclecounter();
       scal->real_end = __builtin_amdgcn_s_memrealtime();
     }

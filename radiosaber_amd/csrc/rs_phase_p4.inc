@@ -104,7 +104,10 @@
         s_sorted[f + rank] = e;
       }
       if (tid < R) low_owner[tid] = 0x7fffffff;
-      if (tid == 0) m->served = 0;
+      if (tid == 0) {
+        m->served = 0;
+        if (rec_on) m->rec_tti = 0;
+      }
       __syncthreads();
       uint16_t* ent_user = (uint16_t*)s_elems; /* s_elems is dead: UE of entry (slice, k), 0xFFFF = not taken */
       for (int x = tid; x < N; x += nt) {
@@ -130,9 +133,11 @@
         if (!leader) continue;
         double sum = 0;
         int nprb = 0, syn_bits = 0; /* syn_bits: the synthetic-experiment transport block, every PRB at its own CQI (:653-659) */
+        unsigned long long rec_mask = 0ull; /* grant records: the RBGs of the slice's list that went to this UE */
         for (int y = x; y < f + q; ++y) {
           if (ent_user[y] != u) continue;
           const int r2 = (int)((s_sorted[y] >> 8) & 63u);
+          rec_mask |= 1ull << r2;
           if (per_prb) {
             const uint8_t* pr = prb_ptr(u, r2);
             for (int g = 0; g < G; ++g) { sum += s_e[pr[g]]; syn_bits += m->tbs1_of_cqi[pr[g]]; }
@@ -168,6 +173,20 @@
           }
         }
         atomicAdd(&m->served, 1);
+        if (rec_on && bytes > 0) {
+          /* Grant records (rs_batch_run_grant_records): the leaders take their places from one LDS counter, in arrival order, behind
+           * the cell's count of the TTIs before (rs_kernels.hip adds the TTI's count behind its closing barrier); the host sorts. */
+          const int place = rec_count + atomicAdd(&m->rec_tti, 1);
+          if (place < rec_cap) {
+            int rb = bytes;
+#if defined(RS_FAULT_INJECT_RECORDS)
+            if (FIXED) rb += 1; /* tests only, see rs_phase_p5.inc */
+#endif
+            int4* const dst = (int4*)(rec_list + place);
+            dst[0] = make_int4((int)n_done, u, tbs, rb);
+            dst[1] = make_int4((int)(uint32_t)rec_mask, (int)(uint32_t)(rec_mask >> 32), nprb, fcqi | (mcs << 8));
+          }
+        }
         if (p.log_map) {
           const size_t row = (size_t)cell * p.n_ttis + tti;
           if (p.log_tbs) p.log_tbs[row * U + u] = tbs;

@@ -65,6 +65,7 @@
       RS_P5STAMP(1);
       int tbs = 0, nprb = 0, fcqi = 0, mcs = 0;
       int tbs_bytes_next = 0; /* bytes of this TTI's grant, for the served user's next EWMA update (speculated TTIs) */
+      int rec_bytes = 0; /* grant records: what DoStopSchedule credits this leader's user (0: no record) */
       {
         /* ref: :638-651 -- PRBs in RBG-ascending order, G identical adds per RBG
          * (src/utility/eesm-effective-sinr.h:33-46 with the exp() values tabulated by the host) */
@@ -212,7 +213,35 @@
             }
           }
           if ((kSpecSched && spec_next) || (kHoldSched && ewma_next) || early17) tbs_bytes_next = bytes;
+          if (rec_on) rec_bytes = bytes;
         }
+      }
+      if (rec_on) {
+        /* Grant records (rs_batch_run_grant_records): the leaders whose users are credited take the TTI's places behind the cell's
+         * running count -- one ballot says which lanes -- and store their record as two 16-byte halves.  A lane's place among them is
+         * the number of those lanes with a smaller user: DoStopSchedule's order, so the host finds every TTI's stretch sorted (lane
+         * order is RBG order, which says nothing about the users'; sorting 50 records per cell-TTI on the host cost three times the
+         * launch, profiles/batch_grant_records.md).  The walk over the ballot's bits is wave-uniform: a scalar loop, one lane read and
+         * one compare per served user, every lane in it.  A place at or behind the capacity is not written, the count goes on. */
+        const bool w = leader && rec_bytes > 0;
+        const unsigned long long wm = __ballot(w);
+        int rank = 0;
+        for (unsigned long long it = wm; it != 0ull; it &= it - 1ull) {
+          const int o = __builtin_amdgcn_readlane(owner, __ffsll((long long)it) - 1);
+          rank += o < owner ? 1 : 0;
+        }
+        const int place = rec_count + rank;
+        if (w && place < rec_cap) {
+#if defined(RS_FAULT_INJECT_RECORDS)
+          /* tests only: a run-time build whose RECORD says one byte more than was credited -- the state agrees, only the self-check's
+           * comparison of the record lists can catch it */
+          if (FIXED) rec_bytes += 1;
+#endif
+          int4* const dst = (int4*)(rec_list + place);
+          dst[0] = make_int4((int)n_done, owner, tbs, rec_bytes);
+          dst[1] = make_int4((int)(uint32_t)same, (int)(uint32_t)(same >> 32), nprb, fcqi | (mcs << 8));
+        }
+        rec_count += __popcll(wm);
       }
       RS_P5STAMP(5);
       if ((kHoldSched && ewma_next) || early17) {

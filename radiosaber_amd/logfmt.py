@@ -63,6 +63,80 @@ def run_record_lines(records, user_to_slice: Sequence[int], first_ts: int = 100,
     return out
 
 
+def grant_record_lines(records, user_to_slice: Sequence[int], first_ts: int = 100, cum_bytes0=None, cum_rbs0=None,
+                       pf_format: bool = False) -> List[str]:
+    """records: the grant records of ONE cell (BatchScheduler.run_grant_records(...)[c], api.BATCH_GRANT_RECORD; the lists of
+    consecutive launches concatenated) -> the lines stderr_lines writes for the same run.  A record's tti counts from the batch's first
+    TTI, so first_ts is the time stamp of that TTI whichever launch the records come from.  The counters are summed here from the
+    starting values (cum_bytes0 / cum_rbs0 [U]: BatchScheduler.state() before the first of these launches; None: zero), a record
+    carries the TTI's credit alone.  The records come in DoStopSchedule's order.  pf_format as in stderr_lines."""
+    records = np.asarray(records)
+    U = len(user_to_slice)
+    cb = np.zeros(U, np.int64) if cum_bytes0 is None else np.array(cum_bytes0, np.int64)
+    cr = np.zeros(U, np.int64) if cum_rbs0 is None else np.array(cum_rbs0, np.int64)
+    out = []
+    for r in records:
+        u, ts = int(r["user"]), first_ts + int(r["tti"])
+        cb[u] += int(r["bytes"])
+        cr[u] += int(r["nprb"])
+        if pf_format:
+            out.append(f"{ts} flow: {u} cumu_bytes: {cb[u]} cumu_rbs: {cr[u]} hol_delay: 0")
+        else:
+            out.append(f"{ts} app: {u} cumu_bytes: {cb[u]} cumu_rbs: {cr[u]} hol_delay: 0 user: {u} slice: {user_to_slice[u]}")
+    return out
+
+
+def _grant_record_dtype():
+    from .api import BATCH_GRANT_RECORD  # (api imports nothing from here; the dtype has one home)
+    return BATCH_GRANT_RECORD
+
+
+def rows_from_grant_records(records, n_ttis: int, U: int, R: int, first_tti: int = 0, with_map: bool = True):
+    """The dense rows of ONE cell's n_ttis TTIs from first_tti on, rebuilt from its grant records: dict(tbs_bits [n_ttis][U], uinfo
+    [n_ttis][U] -- nprb | final_cqi << 16 | mcs << 24, run_logged's word -- and, with_map, rbg_to_user [n_ttis][R], -1 where no record
+    has the RBG).  with_map=False for scheduler 10, where two users of different slices may hold one RBG and the map (the lowest
+    slice's user) cannot be told from the masks."""
+    records = np.asarray(records)
+    tbs = np.zeros((n_ttis, U), np.int32)
+    uinfo = np.zeros((n_ttis, U), np.int32)
+    out = {"tbs_bits": tbs, "uinfo": uinfo}
+    n = records["tti"].astype(np.int64) - first_tti
+    u = records["user"].astype(np.int64)
+    if len(records) and (n.min() < 0 or n.max() >= n_ttis or u.min() < 0 or u.max() >= U):
+        raise ValueError("a grant record outside the asked TTIs or users")
+    tbs[n, u] = records["tbs_bits"]
+    uinfo[n, u] = records["nprb"].astype(np.int32) | (records["final_cqi"].astype(np.int32) << 16) | (records["mcs"].astype(np.int32) << 24)
+    if with_map:
+        m = np.full((n_ttis, R), -1, np.int16)
+        bits = (records["rbg_mask"][:, None] >> np.arange(R, dtype=np.uint64)[None, :]) & np.uint64(1)
+        k, r = np.nonzero(bits)
+        m[n[k], r] = u[k]
+        out["rbg_to_user"] = m
+    return out
+
+
+def grant_records_from_rows(tbs_bits, uinfo, rbg_to_user, first_tti: int = 0):
+    """The inverse, host only: the grant records (api.BATCH_GRANT_RECORD, ascending in TTI, then in user) that a launch with these dense
+    rows of ONE cell would return -- one per (TTI, user) with tbs_bits // 8 > 0, rbg_mask from rbg_to_user (None: masks of 0)."""
+    tbs_bits, uinfo = np.asarray(tbs_bits), np.asarray(uinfo)
+    n, u = np.nonzero(tbs_bits // 8 > 0)  # (row-major: TTI, then user)
+    recs = np.zeros(len(n), _grant_record_dtype())
+    recs["tti"] = n + first_tti
+    recs["user"] = u
+    recs["tbs_bits"] = tbs_bits[n, u]
+    recs["bytes"] = np.minimum(tbs_bits[n, u] // 8, 100000000)
+    w = uinfo[n, u].astype(np.int64)
+    recs["nprb"] = w & 0xFFFF
+    recs["final_cqi"] = (w >> 16) & 0xFF
+    recs["mcs"] = (w >> 24) & 0xFF
+    if rbg_to_user is not None:
+        m = np.asarray(rbg_to_user)
+        R = m.shape[1]
+        weights = np.uint64(1) << np.arange(R, dtype=np.uint64)
+        recs["rbg_mask"] = ((m[n] == u[:, None]).astype(np.uint64) * weights[None, :]).sum(axis=1, dtype=np.uint64)
+    return recs
+
+
 def stdout_lines(rbg_to_user, final_cqi, target, quota, cqi_of, first_ts: int = 100, transport: bool = True) -> List[str]:
     """The reference's allocation map.  cqi_of(n, user, rbg) -> CQI the user reported on that RBG."""
     rbg_to_user = np.asarray(rbg_to_user)

@@ -18,6 +18,7 @@ rs_internet_flow_arrivals at the config's rates, the video applications from the
 (tests/golden/video_foreman_1280k.json, --video-trace), and the log also carries the "ipflow start" / "ipflow end" lines of the
 InternetFlow flows, with flow completion times from the batch's flow completion record.  --records takes the same lines from
 unlogged launches: the device writes one 32-byte record per credited bearer instead of dense per-TTI rows, and the log is identical.
+A backlogged configuration takes --records too: one 32-byte record per grant (run_grant_records), the same log.
 
 The scheduler's arithmetic is bit-exact; the position of the libc rand() stream at the first scheduled TTI depends on
 simulator set-up code outside this path (103 300 draws for the 100-UE configuration) and is taken
@@ -55,8 +56,8 @@ ap.add_argument("--sched1-line", choices=("auto", "app", "flow"), default="auto"
                      "model, flow for backlogged configurations (this tool's earlier format)")
 ap.add_argument("--log", default="-", help="where the stderr-format lines go ('-' = stdout)")
 ap.add_argument("--records", action="store_true",
-                help="queue-model configurations: unlogged launches that return one record per credited bearer (run_records) instead of "
-                     "logged launches with dense rows; the log is the same")
+                help="unlogged launches that return one record per credited bearer (queue-model configurations: run_records) or per grant "
+                     "(backlogged configurations: run_grant_records) instead of logged launches with dense rows; the log is the same")
 a = ap.parse_args()
 
 sc = rs.SliceConfig.from_json(a.config)
@@ -65,8 +66,8 @@ n_ttis = int(round(a.duration * 1000))
 U = sc.n_users
 seed = COMMON_SEEDS[a.seed] if 0 <= a.seed < 9 else COMMON_SEEDS[0]
 queues = any(int(t.get("internet_flow", 0)) or int(t.get("video_app", 0)) for t in sc.traffic)
-if a.records and not queues:
-    raise SystemExit("--records: bearer records come from the queue model; this configuration has no internet_flow / video_app applications")
+if a.records and not queues and a.sched == 11:
+    raise SystemExit("--records: scheduler 11 writes no grant records (its kernel is another one)")
 # (the queue model's batches run without the PHY error model's draws: its parity with the oracle is pinned that way)
 b = rs.BatchScheduler(sc, R, a.rbg_size, 1, sched=a.sched, phy_error_draws=not queues, jit=True)
 b.seed(np.array([seed], np.uint32), np.array([a.rand_skip], np.int64))
@@ -114,6 +115,15 @@ done = 0
 while done < n_ttis:  # logged launches of at most 2 000 TTIs keep the host log small
     n = min(2000, n_ttis - done)
     t_first = float(b.clock()[0][0])
+    if a.records and not queues:
+        # a backlogged batch: one record per grant; the rows the writer reads are rebuilt from them (the map is not among them)
+        rows = logfmt.rows_from_grant_records(b.run_grant_records(n)[0], n, U, R, done, with_map=False)
+        by, hol = logfmt.bearer_rows_from_users(rows["tbs_bits"])
+        rbs = logfmt.bearer_prbs(np.zeros((n, R), np.int16), rows["uinfo"] & 0xFFFF, a.rbg_size)
+        lines = writer.lines(by, hol, rbs, t_first, None)
+        out.write("\n".join(lines) + ("\n" if lines else ""))
+        done += n
+        continue
     if a.records:
         records = b.run_records(n)[0]
         rec = {(u, k): v for (c, u, k), v in b.flow_record().items() if (u, k) in flows}
