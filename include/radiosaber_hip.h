@@ -29,6 +29,7 @@ extern "C" {
                                rs_batch_bearer_log + rs_batch_run_logged_bearers (per-bearer DoStopSchedule rows),
                                rs_bearer_record / rs_batch_record_bound / rs_batch_run_records (the same lines from unlogged launches: one 32-byte record per credited bearer),
                                rs_batch_grant_record / rs_batch_grant_bound / rs_batch_run_grant_records / rs_jit_selfcheck_grant_records (a backlogged batch's app: lines from unlogged launches: one 32-byte record per grant),
+                               rs_batch_set_cell_configs / rs_batch_get_cell_config / rs_batch_slice_totals / rs_jit_selfcheck_cell_configs (per-cell weights, exponents and slice sizes in one batch),
                                rs_group_* (one TTI of several drop-in cells in one launch), rs_group_image_stats (cqi_epoch per cell of a group),
                                rs_group_specialize / rs_group_jit_status / rs_jit_selfcheck_group (a group's own self-checked builds of the one-TTI kernel),
                                rs_group_set_avg / rs_group_get_avg / rs_group_set_pending / rs_group_schedule_tti_at (a group cell's PF averages resident on the device),
@@ -748,7 +749,8 @@ int rs_jit_selfcheck_group_flows(int n_slices, int n_users, int n_rbgs, int rbg_
 typedef struct rs_batch rs_batch;
 
 typedef struct rs_batch_config {
-  rs_config cell;            /* every cell of the batch shares this configuration              */
+  rs_config cell;            /* every cell of the batch shares this configuration -- but for the four
+                              * per-slice / per-user arrays once rs_batch_set_cell_configs gave the cells rows of their own */
   int32_t n_cells;
   int32_t first_tti;         /* TTI index of the first scheduled TTI (reference: 100 = 0.1 s)   */
   int32_t cqi_refresh;       /* synthetic/epoch source: new grid every this many TTIs (40)      */
@@ -805,6 +807,30 @@ void rs_batch_destroy(rs_batch* b);
 /* per-cell libc-compatible rand() streams: srand(seed[c]) then rand_skip[c] values discarded
  * (ref: src/scenarios/single-cell-with-interference.h:84-89, src/utility/seed.h:25-35) */
 int rs_batch_seed(rs_batch* b, const uint32_t* seed /* [n_cells] */, const int64_t* rand_skip /* [n_cells] or NULL */);
+/* Per-cell slice configurations (ABI 11 addition): what the reference's run scripts vary between the processes they start besides the
+ * seed and the trace mapping -- the configuration file -- varied between the cells of one batch.  Each array holds one row per cell; a
+ * NULL array leaves every cell the shared rs_config's values of that field.  Cell c then behaves, to the bit, like cell 0 of a one-cell
+ * batch created from an rs_config that holds row c (logged rows, PF averages, counters, slice state, clock, rand() ring).  Shared as
+ * before: n_slices, n_users, n_rbgs, rbg_size, sched, algo_alpha, algo_beta, synthetic_exp, link_tables.  Before the first TTI only
+ * (RS_ERR_STATE afterwards, as for rs_batch_seed); a second call replaces the first.  Every row is validated as a configuration is --
+ * slice ids in range and non-decreasing (empty slices allowed), algo_epsilon / algo_psi 0 or 1, finite weights -- and each cell's
+ * slice state against its own weights by rs_batch_write_state's domain rule: RS_ERR_INVALID naming the cell and the index, nothing
+ * stored.  RS_SCHED_NVS_NONGREEDY: RS_ERR_INVALID (its kernel is another one).  A batch with the queue model: RS_ERR_STATE, and
+ * rs_batch_set_bearers after this call likewise (slice priorities and customised slices stay uniform).  With jit = 1 the run-time
+ * builds are compiled again, for the longest slice window of any cell, and self-checked as any build is; a checkpoint loads only into
+ * a batch that was given the same rows; rs_batch_grant_bound for RS_SCHED_UPPERBOUND is the largest cell's; rs_batch_slice_bytes reads
+ * each cell's own map. */
+int rs_batch_set_cell_configs(rs_batch* b,
+        const double*  slice_weight  /* [n_cells][S] or NULL */,
+        const int32_t* algo_epsilon  /* [n_cells][S] or NULL */,
+        const int32_t* algo_psi      /* [n_cells][S] or NULL */,
+        const int32_t* user_to_slice /* [n_cells][U] or NULL */);
+/* one cell's row of the four (the shared configuration's where no rows were given); any output may be NULL */
+int rs_batch_get_cell_config(rs_batch* b, int32_t cell, double* slice_weight /* [S] or NULL */,
+        int32_t* algo_epsilon, int32_t* algo_psi, int32_t* user_to_slice /* [U] or NULL */);
+/* per cell and slice, the sums of the users' cumulative bytes and RBs by the cell's own map, reduced on the device (exact integer sums):
+ * the two panels of the reference's plot_throughput.py:26-56, per cell */
+int rs_batch_slice_totals(rs_batch* b, int64_t* cum_bytes /* [n_cells][S] or NULL */, int64_t* cum_rbs /* [n_cells][S] or NULL */);
 
 /* CQI source A: explicit grids. h_cqi = [n_cells][n_epochs][U][R] (host); epoch e serves scheduled
  * TTIs [e*cqi_refresh, (e+1)*cqi_refresh).  Copied to HBM once. */
@@ -1075,6 +1101,9 @@ int rs_jit_selfcheck_queue(int n_slices, int n_users, int n_rbgs, int rbg_size, 
  * A negative value with the reason in err for RS_SCHED_NVS_NONGREEDY. */
 int rs_jit_selfcheck_grant_records(int n_slices, int n_users, int n_rbgs, int rbg_size, int threads, int sched, int lean,
                                    char* err, size_t errlen);
+/* the batch kernel of this shape with per-cell configuration rows (what rs_batch_set_cell_configs compiles for a batch with jit = 1):
+ * lean = 0 the general build, 1 the lean build.  A negative value with the reason in err for RS_SCHED_NVS_NONGREEDY. */
+int rs_jit_selfcheck_cell_configs(int n_slices, int n_users, int n_rbgs, int rbg_size, int threads, int sched, int lean, char* err, size_t errlen);
 /* ---- the run-time compiled kernels' cache on disk (ABI 10) ----
  * Every code object hiprtc produces (rs_batch_create with jit = 1, the lean / streamed variants, rs_ctx_specialize) is kept in
  * $RS_JIT_CACHE_DIR (default $XDG_CACHE_HOME/radiosaber_amd, else ~/.cache/radiosaber_amd; created with mode 0700), one file per (device

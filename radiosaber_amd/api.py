@@ -188,6 +188,9 @@ PROTOTYPES = {
     "rs_batch_create_checked": (_ptr, [_P(_BatchConfig), _int, _size]),
     "rs_batch_destroy": (_int, [_ptr]),
     "rs_batch_seed": (_int, [_ptr, _P(C.c_uint32), _P(_i64)]),
+    "rs_batch_set_cell_configs": (_int, [_ptr, _P(_f64), _P(_i32), _P(_i32), _P(_i32)]),
+    "rs_batch_get_cell_config": (_int, [_ptr, _i32, _P(_f64), _P(_i32), _P(_i32), _P(_i32)]),
+    "rs_batch_slice_totals": (_int, [_ptr, _P(_i64), _P(_i64)]),
     "rs_batch_upload_cqi_epochs": (_int, [_ptr, _P(_u8), _i32]),
     "rs_batch_upload_cqi_epochs_prb": (_int, [_ptr, _P(_u8), _i32]),
     "rs_batch_synthesize_cqi": (_int, [_ptr, C.c_uint64, _P(_f64), _i32]),
@@ -231,6 +234,7 @@ PROTOTYPES = {
     "rs_jit_selfcheck_untuned": (_int, _SHAPE + _MSG),
     "rs_jit_selfcheck_queue": (_int, _SHAPE + _MSG),
     "rs_jit_selfcheck_grant_records": (_int, _SHAPE + [_int] + _MSG),
+    "rs_jit_selfcheck_cell_configs": (_int, _SHAPE + [_int] + _MSG),
     "rs_jit_cache_stats": (None, [_P(C.c_longlong)]),
     "rs_jit_compiler_identity": (_str, []),
     "rs_jit_cache_file": (_int, _SHAPE + [_int] + _MSG),
@@ -340,6 +344,17 @@ def jit_selfcheck_grant_records(n_slices, n_users, n_rbgs, rbg_size, threads=512
     needed): the general build, or with lean=True the lean one; returns the code size.  Scheduler 11 has none: RadioSaberError."""
     buf = C.create_string_buffer(4096)
     n = lib().rs_jit_selfcheck_grant_records(n_slices, n_users, n_rbgs, rbg_size, threads, sched, 1 if lean else 0, buf, 4096)
+    if n < 0:
+        raise RadioSaberError(n, buf.value.decode(errors="replace"))
+    return n
+
+
+def jit_selfcheck_cell_configs(n_slices, n_users, n_rbgs, rbg_size, threads=512, sched=RS_SCHED_MAXCELL, lean=False):
+    """Compile the batch kernel of one shape with per-cell configuration rows (what set_cell_configs builds for a batch with jit=True;
+    hiprtc, no GPU needed): the general build, or with lean=True the lean one; returns the code size.  Scheduler 11 has none:
+    RadioSaberError."""
+    buf = C.create_string_buffer(4096)
+    n = lib().rs_jit_selfcheck_cell_configs(n_slices, n_users, n_rbgs, rbg_size, threads, sched, 1 if lean else 0, buf, 4096)
     if n < 0:
         raise RadioSaberError(n, buf.value.decode(errors="replace"))
     return n
@@ -1125,6 +1140,39 @@ class BatchScheduler:
         assert s.shape == (self.n_cells,)
         k = _opt(rand_skip, np.int64)
         _check(lib().rs_batch_seed(self._h, _p(s, C.c_uint32), _p(k, C.c_int64)))
+
+    def set_cell_configs(self, configs: Sequence[SliceConfig]):
+        """One SliceConfig per cell, all of the batch's n_slices and n_users: cell c takes configs[c]'s weights, algo_epsilon, algo_psi
+        and slice sizes and then runs, to the bit, like a one-cell batch created from configs[c] (rs_batch_set_cell_configs).  Before
+        the first TTI; never with the queue model or scheduler 11.  algo_alpha / algo_beta stay the batch's."""
+        if len(configs) != self.n_cells:
+            raise ValueError(f"{len(configs)} configurations for {self.n_cells} cells")
+        for c, cfg in enumerate(configs):
+            if cfg.n_slices != self.S or cfg.n_users != self.U:
+                raise ValueError(f"configuration {c} has {cfg.n_slices} slices and {cfg.n_users} users, the batch {self.S} and {self.U}")
+            if list(cfg.algo_alpha) != list(self.slices.algo_alpha) or list(cfg.algo_beta) != list(self.slices.algo_beta):
+                raise ValueError(f"configuration {c} has algo_alpha / algo_beta of its own: the two stay the batch's")
+        w = np.ascontiguousarray([cfg.weight for cfg in configs], np.float64)
+        e = np.ascontiguousarray([cfg.algo_epsilon for cfg in configs], np.int32)
+        p = np.ascontiguousarray([cfg.algo_psi for cfg in configs], np.int32)
+        m = np.ascontiguousarray([cfg.user_to_slice for cfg in configs], np.int32)
+        _check(lib().rs_batch_set_cell_configs(self._h, _p(w, C.c_double), _p(e, C.c_int32), _p(p, C.c_int32), _p(m, C.c_int32)))
+
+    def cell_config(self, cell):
+        """The configuration cell `cell` runs: dict(weight f64[S], algo_epsilon, algo_psi i32[S], user_to_slice i32[U])
+        (rs_batch_get_cell_config; the shared configuration's rows where set_cell_configs was never called)."""
+        w, e, p = np.zeros(self.S, np.float64), np.zeros(self.S, np.int32), np.zeros(self.S, np.int32)
+        m = np.zeros(self.U, np.int32)
+        _check(lib().rs_batch_get_cell_config(self._h, int(cell), _p(w, C.c_double), _p(e, C.c_int32), _p(p, C.c_int32), _p(m, C.c_int32)))
+        return {"weight": w, "algo_epsilon": e, "algo_psi": p, "user_to_slice": m}
+
+    def slice_totals(self):
+        """{"cum_bytes", "cum_rbs"}: int64 [n_cells][S], every cell's per-user counters summed by the cell's own slice map on the
+        device (rs_batch_slice_totals)."""
+        cb = np.zeros((self.n_cells, self.S), np.int64)
+        cr = np.zeros((self.n_cells, self.S), np.int64)
+        _check(lib().rs_batch_slice_totals(self._h, _p(cb, C.c_int64), _p(cr, C.c_int64)))
+        return {"cum_bytes": cb, "cum_rbs": cr}
 
     def upload_cqi_epochs(self, cqi):
         a = np.ascontiguousarray(cqi, np.uint8)

@@ -48,7 +48,9 @@ extern "C" hipError_t rs_jit_launch(RsJitKernel* k, const RsLaunch* p, hipStream
 extern "C" hipError_t rs_launch_synth(uint8_t* epochs, int64_t grid_stride, int n_cells, int n_epochs, int U, int R, int Upad,
                                       uint64_t seed, int64_t first_cell, const uint32_t* cdf16, hipStream_t stream);
 extern "C" hipError_t rs_launch_copy_probe(const void* src, void* dst, size_t bytes, hipStream_t stream);
-extern "C" hipError_t rs_launch_slice_bytes(const int64_t* cum_bytes, const uint8_t* user_slice, int n_cells, int U,
+extern "C" hipError_t rs_launch_slice_totals(const int64_t* cum_bytes, const int64_t* cum_rbs, const uint8_t* user_slice, int64_t map_stride,
+                                             int n_cells, int U, int S, long long* out, hipStream_t stream);
+extern "C" hipError_t rs_launch_slice_bytes(const int64_t* cum_bytes, const uint8_t* user_slice, int64_t map_stride, int n_cells, int U,
                                             int S, unsigned long long* d_out, hipStream_t stream);
 
 namespace {
@@ -344,6 +346,15 @@ struct rs_batch {
   bool jit_wanted = false;
   char jit_msg[512] = ""; /* why the shape-specialised kernel is not in use (empty: it is, or it was not asked for) */
   int64_t ttis_done = 0;
+  /* per-cell configurations (rs_batch_set_cell_configs): every cell's own row of the four arrays above, on the host and
+   * on the device; the launch block then points at the rows and says so (RsLaunch::cell_cfg).  Configuration, not state. */
+  bool cell_cfg = false;
+  std::vector<double> cc_weight;               /* [cells][S] */
+  std::vector<int32_t> cc_eps, cc_psi, cc_u2s; /* [cells][S], [cells][S], [cells][U] */
+  double* d_cc_weight = nullptr;
+  int32_t *d_cc_eps = nullptr, *d_cc_psi = nullptr;
+  uint8_t* d_cc_user_slice = nullptr;
+  long long* d_totals = nullptr;               /* rs_batch_slice_totals: [2][cells][S] */
   RsLaunch base{};
 };
 
@@ -386,17 +397,33 @@ int upad_of(int U) { return rs_upad_of(U); }
 
 /* the longest slice window of the batch in the stage-1 reciprocal array: 8-aligned start of the slice's first user to the
  * 8-aligned end behind its last (a compile-time constant of the shape-specialised kernel, RS_JIT_WIN) */
-int slice_window(const rs_batch* b) {
+int map_window(const int32_t* u2s, int U) {
   int win = 0;
-  for (int u = 0; u < b->U;) {
+  for (int u = 0; u < U;) {
     int e = u;
-    while (e < b->U && b->u2s[e] == b->u2s[u]) e++;
+    while (e < U && u2s[e] == u2s[u]) e++;
     const int w = ((e + 7) & ~7) - (u & ~7);
     win = w > win ? w : win;
     u = e;
   }
   return win;
 }
+/* (a batch with per-cell maps: the longest window over all its cells -- one kernel serves them all) */
+int slice_window(const rs_batch* b) {
+  if (!b->cell_cfg) return map_window(b->u2s.data(), b->U);
+  int win = 0;
+  for (int c = 0; c < b->n_cells; c++) win = std::max(win, map_window(b->cc_u2s.data() + (size_t)c * b->U, b->U));
+  return win;
+}
+/* the -D options a batch's run-time builds carry beside the rule table's (rs_jit_get's `variant`): the per-cell reads of the load phase
+ * are a compile-time switch, named only by a batch that has per-cell rows -- every other batch's option lists are what they were */
+std::string jit_variant(const rs_batch* b, const char* more = nullptr) {
+  std::string v = more ? more : "";
+  if (b->cell_cfg) v += std::string(v.empty() ? "" : " ") + "-DRS_JIT_CELL_CONFIGS=1";
+  return v;
+}
+/* (nullptr for the empty list: rs_jit_get's key names a variant only where there is one) */
+const char* variant_arg(const std::string& v) { return v.empty() ? nullptr : v.c_str(); }
 
 void carve_lds(rs_batch* b, RsLaunch* L) {
   /* (drop-in contexts of schedulers 1 and 7 carry the gate scratch too: rs_tti_in.required_rbs / data_to_transmit) */
@@ -691,7 +718,7 @@ RsJitKernel* lean_kernel(rs_batch* b, int n_ttis, bool logged) {
     b->jit_lean_tried = true;
     char msg[512] = "";
     b->jit_lean = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, b->queues ? b->qmode : 0, slice_window(b), msg,
-                             sizeof msg, (b->cfg.cqi_refresh <= 4 ? 2 : 0) | 4);
+                             sizeof msg, (b->cfg.cqi_refresh <= 4 ? 2 : 0) | 4, variant_arg(jit_variant(b)));
     /* not an error of the launch -- the general build serves it -- but nothing silent either: rs_batch_jit_status carries the reason */
     if (!b->jit_lean) snprintf(b->jit_msg, sizeof b->jit_msg, "lean build unavailable, the general build serves every launch (%.400s)", msg);
   }
@@ -858,7 +885,7 @@ int autotune(rs_batch* b, int n_ttis) {
     char msg[512] = "";
     RsJitKernel* k = i == 0 ? k_default
                             : rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, sched, 0, win, msg, sizeof msg,
-                                         (b->cfg.cqi_refresh <= 4 ? 2 : 0) | 4, cand[i].c_str());
+                                         (b->cfg.cqi_refresh <= 4 ? 2 : 0) | 4, jit_variant(b, cand[i].c_str()).c_str());
     if (!k) { report += cand[i] + ": not built; "; continue; }
     b->jit_lean = k;
     float ms = 0;
@@ -1059,14 +1086,20 @@ int convert_tx(rs_batch* b, bool to_packed) {
  * whatever the other slices take: the sum over the slices of min(the slice's users, R), as rs_group_grant_bound has it */
 int grant_bound(const rs_batch* b) {
   if (b->sched != RS_SCHED_UPPERBOUND) return std::min(b->U, b->R);
-  int sum = 0;
-  for (int u = 0; u < b->U;) {
-    int e = u;
-    while (e < b->U && b->u2s[e] == b->u2s[u]) e++;
-    sum += std::min(e - u, b->R);
-    u = e;
+  int most = 0;
+  /* (per-cell maps: one capacity serves every cell's list -- the maximum over the cells of the per-slice sum) */
+  for (int c = 0; c < (b->cell_cfg ? b->n_cells : 1); c++) {
+    const int32_t* const u2s = b->cell_cfg ? b->cc_u2s.data() + (size_t)c * b->U : b->u2s.data();
+    int sum = 0;
+    for (int u = 0; u < b->U;) {
+      int e = u;
+      while (e < b->U && u2s[e] == u2s[u]) e++;
+      sum += std::min(e - u, b->R);
+      u = e;
+    }
+    most = std::max(most, sum);
   }
-  return sum;
+  return most;
 }
 
 /* DoStopSchedule's walk: TTI, then user.  The device hands out all places of TTI k before any of TTI k + 1 and a (TTI, user) occurs once,
@@ -1202,7 +1235,7 @@ int records_kernel(rs_batch* b, int n_ttis, RsJitKernel** k, int* which) {
       b->jit_rec_tried[v] = true;
       char msg[512] = "";
       b->jit_rec[v] = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, 0, slice_window(b), msg, sizeof msg,
-                                 (b->cfg.cqi_refresh <= 4 ? 2 : 0) | (v ? 4 : 0), "-DRS_JIT_RECORDS=1");
+                                 (b->cfg.cqi_refresh <= 4 ? 2 : 0) | (v ? 4 : 0), jit_variant(b, "-DRS_JIT_RECORDS=1").c_str());
       if (!b->jit_rec[v])
         snprintf(b->jit_msg, sizeof b->jit_msg, "records variant of the %s build unavailable, %s the records launches (%.380s)", v ? "lean" : "general",
                  v ? "the general build's serves" : "the built-in kernels serve", msg);
@@ -1325,7 +1358,7 @@ void rs_batch_destroy(rs_batch* b) {
                   b->d_sstate, b->d_scal, b->d_epochs, b->d_trace, b->d_user_trace, b->d_err, b->d_slice_bytes, b->d_stamps,
                   b->d_bearer_kind, b->d_arr_off, b->d_arr_time, b->d_arr_nfull, b->d_arr_last, b->d_qi, b->d_bavg, b->d_bcum,
                   b->d_qflags, b->d_qhol, b->d_flow_tti, b->d_flow_time, b->d_epochs_prb, b->d_trace_prb, b->d_gen_num, b->d_prio_sum,
-                  b->d_recs};
+                  b->d_recs, b->d_cc_weight, b->d_cc_eps, b->d_cc_psi, b->d_cc_user_slice, b->d_totals};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (b->own_stream && b->stream) (void)hipStreamDestroy(b->stream);
@@ -1337,6 +1370,120 @@ int rs_batch_seed(rs_batch* b, const uint32_t* seed, const int64_t* rand_skip) {
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   if (b->ttis_done) return fail(RS_ERR_STATE, "rs_batch_seed after TTIs were run");
   return init_scalars(b, seed, rand_skip);
+}
+
+/* ---- per-cell configurations ---- */
+static int check_slice_state(const rs_batch* b, const double* v, size_t cell, const double* weight = nullptr); /* (the domain rule, stated at its definition below) */
+int rs_batch_set_cell_configs(rs_batch* b, const double* slice_weight, const int32_t* algo_epsilon, const int32_t* algo_psi, const int32_t* user_to_slice) {
+  if (!b) return fail(RS_ERR_INVALID, "null batch");
+  if (b->direct) return fail(RS_ERR_INVALID, "per-cell configurations: not a batch");
+  if (b->sched == RS_SCHED_NVS_NONGREEDY) return fail(RS_ERR_INVALID, "per-cell configurations: scheduler %d runs on another kernel, which reads one configuration", b->sched);
+  if (b->queues) return fail(RS_ERR_STATE, "per-cell configurations: the batch has the queue model, which keeps one configuration for every cell");
+  if (b->ttis_done) return fail(RS_ERR_STATE, "rs_batch_set_cell_configs after TTIs were run");
+  const size_t cells = (size_t)b->n_cells, S = (size_t)b->S, U = (size_t)b->U;
+  /* a NULL array: every cell keeps the shared configuration's values for that field */
+  std::vector<double> w(cells * S);
+  std::vector<int32_t> e(cells * S), ps(cells * S), us(cells * U);
+  for (size_t c = 0; c < cells; c++) {
+    for (size_t k = 0; k < S; k++) {
+      w[c * S + k] = slice_weight ? slice_weight[c * S + k] : b->weight[k];
+      e[c * S + k] = algo_epsilon ? algo_epsilon[c * S + k] : b->eps[k];
+      ps[c * S + k] = algo_psi ? algo_psi[c * S + k] : b->psi[k];
+    }
+    for (size_t u = 0; u < U; u++) us[c * U + u] = user_to_slice ? user_to_slice[c * U + u] : b->u2s[u];
+  }
+  /* every row as validate() takes a configuration */
+  for (size_t c = 0; c < cells; c++) {
+    for (size_t k = 0; k < S; k++) {
+      if (!std::isfinite(w[c * S + k])) return fail(RS_ERR_INVALID, "cell %zu: slice_weight[%zu] = %g is not finite", c, k, w[c * S + k]);
+      if ((e[c * S + k] | 1) != 1 || (ps[c * S + k] | 1) != 1)
+        return fail(RS_ERR_INVALID, "cell %zu, slice %zu: algo_epsilon %d / algo_psi %d must be 0 or 1 in a batch", c, k, e[c * S + k], ps[c * S + k]);
+    }
+    for (size_t u = 0; u < U; u++) {
+      const int32_t sl = us[c * U + u];
+      if (sl < 0 || sl >= b->S) return fail(RS_ERR_INVALID, "cell %zu, user %zu: slice %d out of range", c, u, sl);
+      if (u && sl < us[c * U + u - 1]) return fail(RS_ERR_INVALID, "cell %zu: user_to_slice must be non-decreasing (user %zu)", c, u);
+    }
+  }
+  HIP_TRY(hipSetDevice(b->cfg.cell.device));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  { /* the slice state the cells hold now (zeros, or what rs_batch_write_state put there) against each cell's new weights */
+    std::vector<double> st(cells * S);
+    HIP_TRY(hipMemcpy(st.data(), b->d_sstate, 8 * cells * S, hipMemcpyDeviceToHost));
+    for (size_t c = 0; c < cells; c++)
+      if (const int rc = check_slice_state(b, st.data() + c * S, c, w.data() + c * S)) return rc;
+  }
+  /* one kernel serves all cells: LDS carve and run-time builds for the longest slice window of any cell -- validated and built BEFORE
+   * the batch changes, so that a refusal leaves it as it was */
+  int win = 0;
+  for (size_t c = 0; c < cells; c++) win = std::max(win, map_window(us.data() + c * U, b->U));
+  const RsCarve cv = rs_carve(b->S, b->U, b->R, b->sched, b->threads, 0, win, b->jit_wanted ? RS_NVS_WHOLE_SLICE : RS_NVS_WHOLE_SLICE_BUILTIN);
+  if (cv.lds_bytes > 160 * 1024) return fail(RS_ERR_INVALID, "cell needs %d B of LDS with a slice window of %d users (> 160 KiB)", cv.lds_bytes, win);
+  RsJitKernel* cjit = nullptr;
+  char cmsg[sizeof b->jit_msg] = {0};
+  if (b->jit_wanted) {
+    cjit = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, 0, win, cmsg, sizeof cmsg, b->cfg.cqi_refresh <= 4 ? 2 : 0,
+                      "-DRS_JIT_CELL_CONFIGS=1");
+    if (cjit) snprintf(cmsg, sizeof cmsg, "%s", rs_jit_is_untuned(cjit) ? "in use, built WITHOUT the -mllvm tuning options (hiprtc refused them): a few per cent slower" : "");
+    else if (!cmsg[0]) snprintf(cmsg, sizeof cmsg, "hiprtc build of the kernel with per-cell configurations failed");
+    if (!cjit && b->threads > 512) return fail(RS_ERR_INVALID, "threads_per_cell %d needs the shape-specialised kernel with per-cell configurations: %s", b->threads, cmsg);
+  }
+  if (!b->d_cc_weight) {
+    HIP_TRY(hipMalloc(&b->d_cc_weight, 8 * cells * S));
+    HIP_TRY(hipMalloc(&b->d_cc_eps, 4 * cells * S));
+    HIP_TRY(hipMalloc(&b->d_cc_psi, 4 * cells * S));
+    HIP_TRY(hipMalloc(&b->d_cc_user_slice, cells * U));
+  }
+  std::vector<uint8_t> us8(cells * U);
+  for (size_t i = 0; i < cells * U; i++) us8[i] = (uint8_t)us[i];
+  HIP_TRY(hipMemcpy(b->d_cc_weight, w.data(), 8 * cells * S, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b->d_cc_eps, e.data(), 4 * cells * S, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b->d_cc_psi, ps.data(), 4 * cells * S, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b->d_cc_user_slice, us8.data(), cells * U, hipMemcpyHostToDevice));
+  /* commit: rows, launch block, carve and kernels together */
+  b->cc_weight.swap(w); b->cc_eps.swap(e); b->cc_psi.swap(ps); b->cc_u2s.swap(us);
+  b->cell_cfg = true;
+  b->base.weight = b->d_cc_weight; b->base.eps = b->d_cc_eps; b->base.psi = b->d_cc_psi; b->base.user_slice = b->d_cc_user_slice;
+  b->base.cell_cfg = 1;
+  carve_lds(b, &b->base);
+  if (b->jit_wanted) {
+    /* the builds belong to the rows' window and to the switch: the lean build, the records variants, the self-check and the autotune
+     * start over with the new general build (nullptr: the built-in kernels run, rs_batch_jit_status says why) */
+    b->jit = cjit;
+    b->jit_lean = nullptr; b->jit_lean_tried = false;
+    for (int v = 0; v < 2; v++) { b->jit_rec[v] = nullptr; b->jit_rec_tried[v] = false; b->jit_rec_checked[v] = false; }
+    b->rec_rejected = false; b->jit_rejected = false;
+    b->selfchecked = false; b->selfchecked_general = false; b->selfchecked_lean = false; b->selfcheck_msg[0] = 0;
+    b->autotuned = false; b->autotune_n = 0; b->autotune_msg[0] = 0;
+    snprintf(b->jit_msg, sizeof b->jit_msg, "%s", cmsg);
+  }
+  return RS_OK;
+}
+
+int rs_batch_get_cell_config(rs_batch* b, int32_t cell, double* slice_weight, int32_t* algo_epsilon, int32_t* algo_psi, int32_t* user_to_slice) {
+  if (!b) return fail(RS_ERR_INVALID, "null batch");
+  if (cell < 0 || cell >= b->n_cells) return fail(RS_ERR_INVALID, "cell %d outside 0..%d", cell, b->n_cells - 1);
+  const size_t S = (size_t)b->S, U = (size_t)b->U, c = (size_t)cell;
+  /* (a batch that was given no rows: every cell has the shared configuration's) */
+  if (slice_weight) memcpy(slice_weight, b->cell_cfg ? b->cc_weight.data() + c * S : b->weight.data(), 8 * S);
+  if (algo_epsilon) memcpy(algo_epsilon, b->cell_cfg ? b->cc_eps.data() + c * S : b->eps.data(), 4 * S);
+  if (algo_psi) memcpy(algo_psi, b->cell_cfg ? b->cc_psi.data() + c * S : b->psi.data(), 4 * S);
+  if (user_to_slice) memcpy(user_to_slice, b->cell_cfg ? b->cc_u2s.data() + c * U : b->u2s.data(), 4 * U);
+  return RS_OK;
+}
+
+int rs_batch_slice_totals(rs_batch* b, int64_t* cum_bytes, int64_t* cum_rbs) {
+  if (!b) return fail(RS_ERR_INVALID, "null batch");
+  if (b->direct) return fail(RS_ERR_INVALID, "slice totals: not a batch");
+  const size_t n = (size_t)b->n_cells * b->S;
+  HIP_TRY(hipSetDevice(b->cfg.cell.device));
+  if (!b->d_totals) HIP_TRY(hipMalloc(&b->d_totals, 8 * 2 * n));
+  HIP_TRY(rs_launch_slice_totals(b->d_cumb, b->d_cumr, b->cell_cfg ? b->d_cc_user_slice : b->d_user_slice, b->cell_cfg ? b->U : 0, b->n_cells, b->U, b->S,
+                                 b->d_totals, b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  if (cum_bytes) HIP_TRY(hipMemcpy(cum_bytes, b->d_totals, 8 * n, hipMemcpyDeviceToHost));
+  if (cum_rbs) HIP_TRY(hipMemcpy(cum_rbs, b->d_totals + n, 8 * n, hipMemcpyDeviceToHost));
+  return RS_OK;
 }
 
 int rs_batch_upload_cqi_epochs(rs_batch* b, const uint8_t* h_cqi, int32_t n_epochs) {
@@ -1763,7 +1910,8 @@ int rs_batch_read_state(rs_batch* b, double* avg, int64_t* cum_bytes, int64_t* c
  *     division below 2^25 + 2, wrong at 2^25 + 2) a factor of a thousand inside that bound.
  *   schedulers 7 and 11: EWMAs are >= 0.  The reference's scan ('>=' from 0, :127-131) never picks a negative score and the
  *     kernel's integer-pair maximum orders negative doubles the other way round. */
-static int check_slice_state(const rs_batch* b, const double* v, size_t cell) {
+static int check_slice_state(const rs_batch* b, const double* v, size_t cell, const double* weight) {
+  if (!weight) weight = b->cell_cfg ? b->cc_weight.data() + cell * (size_t)b->S : b->weight.data(); /* (per-cell rows: the cell's own weights) */
   const int S = b->S;
   const bool transport = b->sched == RS_SCHED_SEQUENTIAL || b->sched == RS_SCHED_MAXCELL || b->sched == RS_SCHED_SUBOPT ||
                          b->sched == RS_SCHED_VOGEL || b->sched == RS_SCHED_UPPERBOUND;
@@ -1773,7 +1921,7 @@ static int check_slice_state(const rs_batch* b, const double* v, size_t cell) {
   for (int s = 0; s < S; s++) {
     if (!std::isfinite(v[s])) return fail(RS_ERR_INVALID, "slice state [%zu][%d] = %g is not finite", cell, s, v[s]);
     if (nvs && !(v[s] >= 0)) return fail(RS_ERR_INVALID, "slice EWMA [%zu][%d] = %g is negative (slice_ewma_time_ is an average of 0s and 1s)", cell, s, v[s]);
-    w += nb * fabs(b->weight[s]);
+    w += nb * fabs(weight[s]);
     a += fabs(v[s]);
   }
   if (transport && !(5 * w + a < 32768.0))
@@ -1807,6 +1955,7 @@ int rs_batch_set_bearers(rs_batch* b, const uint8_t* bearer_kind) {
   if (!b || !bearer_kind) return fail(RS_ERR_INVALID, "null argument");
   if (b->direct) return fail(RS_ERR_INVALID, "drop-in contexts take the queue state per TTI (rs_tti_in.hol_delay / prio_has_data)");
   if (b->ttis_done) return fail(RS_ERR_STATE, "rs_batch_set_bearers after TTIs were run");
+  if (b->cell_cfg) return fail(RS_ERR_STATE, "rs_batch_set_bearers after rs_batch_set_cell_configs: the queue model keeps one configuration for every cell");
   if (b->sched != RS_SCHED_SEQUENTIAL && b->sched != RS_SCHED_MAXCELL && b->sched != RS_SCHED_SUBOPT && b->sched != RS_SCHED_VOGEL &&
       b->sched != RS_SCHED_PF && b->sched != RS_SCHED_NVS)
     return fail(RS_ERR_INVALID, "finite queues: schedulers 1, 7, 8, 9, 101 and 103 only (sched %d)", b->sched);
@@ -2050,6 +2199,12 @@ uint64_t ckpt_config_hash(const rs_batch* b) {
   mix(b->beta.data(), 4 * b->beta.size());
   mix(b->eps.data(), 4 * b->eps.size());
   mix(b->psi.data(), 4 * b->psi.size());
+  if (b->cell_cfg) { /* the cells' own rows: a checkpoint continues only in a batch that was given the same ones */
+    mix(b->cc_u2s.data(), 4 * b->cc_u2s.size());
+    mix(b->cc_weight.data(), 8 * b->cc_weight.size());
+    mix(b->cc_eps.data(), 4 * b->cc_eps.size());
+    mix(b->cc_psi.data(), 4 * b->cc_psi.size());
+  }
   return h;
 }
 }  // namespace
@@ -2096,7 +2251,7 @@ int rs_batch_checkpoint_load(rs_batch* b, const void* buf, size_t buflen) {
                 h.G, h.sched, h.n_cells, h.queues);
   if (h.bytes != (uint64_t)need || buflen < (size_t)need) return fail(RS_ERR_INVALID, "checkpoint of %llu bytes, this batch's are %lld", (unsigned long long)h.bytes, (long long)need);
   if (h.config_hash != ckpt_config_hash(b))
-    return fail(RS_ERR_INVALID, "checkpoint of a batch configured differently (users per slice, slice weights / algorithm parameters, cqi_refresh, first_tti, "
+    return fail(RS_ERR_INVALID, "checkpoint of a batch configured differently (users per slice, slice weights / algorithm parameters, per-cell rows, cqi_refresh, first_tti, "
                                 "phy_error_draws, synthetic_exp or the library's state layout): the run would not continue as it began");
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   HIP_TRY(hipStreamSynchronize(b->stream));
@@ -2169,7 +2324,9 @@ int rs_batch_jit_status(rs_batch* b, char* msg, size_t msglen) {
 int rs_batch_slice_bytes_device(rs_batch* b, uint64_t* d_out) {
   if (!b || !d_out) return fail(RS_ERR_INVALID, "null argument");
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  HIP_TRY(rs_launch_slice_bytes(b->d_cumb, b->d_user_slice, b->n_cells, b->U, b->S, (unsigned long long*)d_out, b->stream));
+  /* (each cell's own map once rs_batch_set_cell_configs gave it one) */
+  HIP_TRY(rs_launch_slice_bytes(b->d_cumb, b->cell_cfg ? b->d_cc_user_slice : b->d_user_slice, b->cell_cfg ? b->U : 0, b->n_cells, b->U, b->S,
+                                (unsigned long long*)d_out, b->stream));
   return RS_OK;
 }
 

@@ -259,13 +259,17 @@ struct RsLaunch {
   int32_t rand0, rand1;      /* direct mode */
   /* configuration (device pointers) */
   const RsTables* tab;
-  const double* weight;      /* [S] */
-  const int32_t* eps;        /* [S] */
-  const int32_t* psi;        /* [S] */
-  const uint8_t* user_slice; /* [U] */
+  const double* weight;      /* [S]; [cells][S] when cell_cfg is set */
+  const int32_t* eps;        /* [S]; [cells][S] when cell_cfg is set */
+  const int32_t* psi;        /* [S]; [cells][S] when cell_cfg is set */
+  const uint8_t* user_slice; /* [U]; [cells][U] when cell_cfg is set */
   const uint8_t* prb_cqi;    /* direct mode, optional: [U][R*G] per-PRB CQI for the EESM sum */
   /* direct mode, customised slices (alpha = 1): */
   int32_t queue_mode;        /* 1: some slice has alpha != 0 */
+  /* batches, rs_batch_set_cell_configs: 1 -- weight, eps, psi and user_slice above hold one row per cell and the cell's load phase reads
+   * its own (the per-TTI path reads none of the four).  In the padding behind queue_mode: no word of the block moves.  The built-in
+   * kernels test it at run time; a run-time build has it as a constant (RS_JIT_CELL_CONFIGS) */
+  int32_t cell_cfg;
   const int32_t* alpha;      /* [S] */
   const int32_t* beta;       /* [S] */
   const double* hol;         /* [U] head-of-line delay of the slice-priority bearer */
@@ -396,6 +400,9 @@ struct RsLaunch {
   double* grp_gather;        /* [group cells][U] */
   int32_t* grp_uid;          /* [group cells][U]: the ids that grp_gather's row was gathered by */
 };
+
+static_assert(__builtin_offsetof(RsLaunch, alpha) - __builtin_offsetof(RsLaunch, queue_mode) == 8 && __builtin_offsetof(RsLaunch, cell_cfg) - __builtin_offsetof(RsLaunch, queue_mode) == 4,
+              "cell_cfg lies in the padding behind queue_mode: the launch block keeps its size and every other word its place");
 
 /* per-slot header of a group call, written by the host (rs_api.cpp: group_fill_header) */
 #define RS_GROUP_HDR_BYTES 128

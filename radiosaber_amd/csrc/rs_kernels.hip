@@ -198,6 +198,19 @@ __device__ __forceinline__ void rs_cell_body(const RsLaunch& p, unsigned char* l
   /* (a shape-specialised drop-in kernel: RS_JIT_U is the context's user capacity -- it fixes the LDS carve -- while the users of one
    * call, their grid stride and, per-flow PF, their segments are launch arguments) */
   const int S = FIXED ? RS_JIT_S : p.S, U = (FIXED && !DIRECT) ? RS_JIT_U : p.U, R = FIXED ? RS_JIT_R : p.R, G = FIXED ? RS_JIT_G : p.G;
+  /* Per-cell configurations of a batch (rs_batch_set_cell_configs): weight, eps, psi and user_slice hold one row per cell, and the load
+   * phase below -- the only reader of the four in a batch -- takes this cell's.  The built-in kernels look at the launch block's word; a
+   * run-time build has the switch as a constant (RS_JIT_CELL_CONFIGS, rs_jit.cpp), so that the build of a batch without such rows is the
+   * one it was.  (Drop-in and group calls bring their slice ids per call; the queue model keeps one configuration.) */
+#ifndef RS_JIT_CELL_CONFIGS
+#define RS_JIT_CELL_CONFIGS 0
+#endif
+  const bool cell_cfg = !DIRECT && !QUEUE && (FIXED ? RS_JIT_CELL_CONFIGS != 0 : p.cell_cfg != 0);
+  const size_t cfg_row = cell_cfg ? (size_t)cell : 0;
+  const double* const cfg_weight = p.weight + cfg_row * S;
+  const int32_t* const cfg_eps = p.eps + cfg_row * S;
+  const int32_t* const cfg_psi = p.psi + cfg_row * S;
+  const uint8_t* const cfg_user_slice = p.user_slice + cfg_row * U;
   constexpr RsCarve kCv = rs_carve(RS_JIT_S, RS_JIT_U, RS_JIT_R, RS_JIT_SCHED, RS_JIT_NT, RS_JIT_CARVEQ, RS_JIT_WIN);
   /* byte offsets of the LDS arrays: constants in a shape-specialised build */
   struct Offs { int avgk, rcp, tab, slice, tx, misc, tbs, elems, sorted, items, sortx, cqi, queue, Upad, n_seg, n_items; };
@@ -418,8 +431,8 @@ __device__ __forceinline__ void rs_cell_body(const RsLaunch& p, unsigned char* l
   if ((SCHED == 9 || SCHED == 10) && tid < 3) m->heap_sorts[tid] = 0;
   if (tid < S) {
     /* bit 0 = algo_epsilon, bit 1 = algo_psi, bit 2 = algo_alpha, bit 3 = algo_beta */
-    m->eps_psi[tid] = (uint8_t)((p.eps[tid] ? 1 : 0) | (p.psi[tid] ? 2 : 0) | ((p.alpha && p.alpha[tid]) ? 4 : 0) | ((p.beta && p.beta[tid]) ? 8 : 0));
-    s_w[tid] = p.weight[tid];
+    m->eps_psi[tid] = (uint8_t)((cfg_eps[tid] ? 1 : 0) | (cfg_psi[tid] ? 2 : 0) | ((p.alpha && p.alpha[tid]) ? 4 : 0) | ((p.beta && p.beta[tid]) ? 8 : 0));
+    s_w[tid] = cfg_weight[tid];
     s_sstate[tid] = p.slice_state[(size_t)cell * S + tid];
   }
   /* segments scanned in P3: slices (7/8/9) or fixed runs of RS_PF_SEG users (1) */
@@ -432,8 +445,8 @@ __device__ __forceinline__ void rs_cell_body(const RsLaunch& p, unsigned char* l
   if (SCHED != 1) {
     /* user_slice is non-decreasing: slice s = [first u with slice >= s, ...) */
     for (int u = tid; u < U; u += nt) {
-      int s = kPrefetch ? (int)s_uoff[u] : (int)p.user_slice[u];
-      int sp = u == 0 ? -1 : (kPrefetch ? (int)s_uoff[u - 1] : (int)p.user_slice[u - 1]);
+      int s = kPrefetch ? (int)s_uoff[u] : (int)cfg_user_slice[u];
+      int sp = u == 0 ? -1 : (kPrefetch ? (int)s_uoff[u - 1] : (int)cfg_user_slice[u - 1]);
       for (int q = sp + 1; q <= s; q++) m->seg_begin[q] = u;
     }
   }
@@ -457,7 +470,7 @@ __device__ __forceinline__ void rs_cell_body(const RsLaunch& p, unsigned char* l
         if (u < U) s_uoff[u] = (int16_t)(m->rcp_off[pre_sl[k]] | ((m->eps_psi[pre_sl[k]] & 2) ? 1 : 0));
       }
     } else {
-      for (int u = tid; u < U; u += nt) s_uoff[u] = (int16_t)(m->rcp_off[p.user_slice[u]] | (p.psi[p.user_slice[u]] ? 1 : 0));
+      for (int u = tid; u < U; u += nt) s_uoff[u] = (int16_t)(m->rcp_off[cfg_user_slice[u]] | (cfg_psi[cfg_user_slice[u]] ? 1 : 0));
     }
   }
   double t = kDirect ? 0.0 : scal->t;
@@ -1022,19 +1035,44 @@ __global__ void __launch_bounds__(256) rs_copy_probe_kernel(const uint4* __restr
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += stride) dst[i] = src[i];
 }
 
-/* per-slice cumulative bytes over all cells -> d_out[S] (uint64) */
-__global__ void rs_slice_bytes_kernel(const int64_t* cum_bytes, const uint8_t* user_slice, int n_cells, int U,
+/* per-slice cumulative bytes over all cells -> d_out[S] (uint64).  map_stride: bytes between two cells' rows of user_slice -- 0 when
+ * every cell shares one map, U when each has its own (rs_batch_set_cell_configs) */
+__global__ void rs_slice_bytes_kernel(const int64_t* cum_bytes, const uint8_t* user_slice, int64_t map_stride, int n_cells, int U,
                                       int S, unsigned long long* d_out) {
   __shared__ unsigned long long acc[64];
   if (threadIdx.x < 64) acc[threadIdx.x] = 0;
   __syncthreads();
   const int64_t total = (int64_t)n_cells * U;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    int u = (int)(i % U);
-    atomicAdd(&acc[user_slice[u]], (unsigned long long)cum_bytes[i]);
+    const int64_t c = i / U;
+    int u = (int)(i - c * U);
+    atomicAdd(&acc[user_slice[c * map_stride + u] & 63], (unsigned long long)cum_bytes[i]);
   }
   __syncthreads();
   if (threadIdx.x < S && acc[threadIdx.x]) atomicAdd(&d_out[threadIdx.x], acc[threadIdx.x]);
+}
+
+/* per cell and slice, the sums of cum_bytes and cum_rbs over the users the cell's map puts in the slice (rs_batch_slice_totals: the two
+ * panels of the reference's plot_throughput.py) -> out[2][n_cells][S], bytes then RBs.  One workgroup per cell; integer adds into an
+ * LDS table of 2 x 64 int64, so the sums are exact whatever order the lanes arrive in; every (cell, slice) word is written, zeros
+ * included, with plain vector stores. */
+__global__ void __launch_bounds__(256) rs_slice_totals_kernel(const int64_t* cum_bytes, const int64_t* cum_rbs, const uint8_t* user_slice,
+                                                              int64_t map_stride, int n_cells, int U, int S, long long* out) {
+  __shared__ unsigned long long acc[2 * 64];
+  const int cell = blockIdx.x;
+  if (threadIdx.x < 2 * 64) acc[threadIdx.x] = 0;
+  __syncthreads();
+  const uint8_t* const map = user_slice + (int64_t)cell * map_stride;
+  for (int u = threadIdx.x; u < U; u += blockDim.x) {
+    const int s = map[u] & 63;
+    atomicAdd(&acc[s], (unsigned long long)cum_bytes[(int64_t)cell * U + u]);
+    atomicAdd(&acc[64 + s], (unsigned long long)cum_rbs[(int64_t)cell * U + u]);
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < S && S <= 64) {
+    out[(int64_t)cell * S + threadIdx.x] = (long long)acc[threadIdx.x];
+    out[((int64_t)n_cells + cell) * S + threadIdx.x] = (long long)acc[64 + threadIdx.x];
+  }
 }
 
 #if !defined(__HIPCC_RTC__) && !defined(RS_JIT_BUILD)
@@ -1184,15 +1222,23 @@ extern "C" hipError_t rs_launch_synth(uint8_t* epochs, int64_t grid_stride, int 
   return hipGetLastError();
 }
 
-extern "C" hipError_t rs_launch_slice_bytes(const int64_t* cum_bytes, const uint8_t* user_slice, int n_cells, int U,
+extern "C" hipError_t rs_launch_slice_bytes(const int64_t* cum_bytes, const uint8_t* user_slice, int64_t map_stride, int n_cells, int U,
                                             int S, unsigned long long* d_out, hipStream_t stream) {
   hipError_t e = hipMemsetAsync(d_out, 0, sizeof(unsigned long long) * S, stream);
   if (e != hipSuccess) return e;
   int64_t total = (int64_t)n_cells * U;
   int blocks = (int)((total + 255) / 256);
   if (blocks > 1024) blocks = 1024;
-  hipLaunchKernelGGL(rs_slice_bytes_kernel, dim3(blocks), dim3(256), 0, stream, cum_bytes, user_slice, n_cells, U, S,
+  hipLaunchKernelGGL(rs_slice_bytes_kernel, dim3(blocks), dim3(256), 0, stream, cum_bytes, user_slice, map_stride, n_cells, U, S,
                      d_out);
+  return hipGetLastError();
+}
+
+/* out: [2][n_cells][S] int64 in device memory (rs_slice_totals_kernel) */
+extern "C" hipError_t rs_launch_slice_totals(const int64_t* cum_bytes, const int64_t* cum_rbs, const uint8_t* user_slice, int64_t map_stride,
+                                             int n_cells, int U, int S, long long* out, hipStream_t stream) {
+  if (n_cells < 1 || S < 1 || S > 64) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(rs_slice_totals_kernel, dim3(n_cells), dim3(256), 0, stream, cum_bytes, cum_rbs, user_slice, map_stride, n_cells, U, S, out);
   return hipGetLastError();
 }
 

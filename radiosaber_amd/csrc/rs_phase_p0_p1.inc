@@ -293,7 +293,7 @@
             float r32 = (uo & 1) ? __builtin_amdgcn_rcpf((float)k) : 1.0f;
             /* customised slice (ref: :694-711): metric 0 while the prioritized bearer is empty, times the
              * head-of-line delay when beta (sched 7: always) -- folded into the stage-1 factor */
-            const int sl = kPrefetch ? pre_sl[ku < kPU ? ku : 0] : (int)p.user_slice[u];
+            const int sl = kPrefetch ? pre_sl[ku < kPU ? ku : 0] : (int)cfg_user_slice[u];
             if (m->eps_psi[sl] & 4) { /* algo_alpha */
               const bool has = prio_in ? (prio_in[u] & 1) != 0 : true;
               const bool use_hol = SCHED == 7 || SCHED == 11 || (m->eps_psi[sl] & 8) != 0; /* algo_beta */
