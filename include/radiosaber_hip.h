@@ -30,6 +30,7 @@ extern "C" {
                                rs_bearer_record / rs_batch_record_bound / rs_batch_run_records (the same lines from unlogged launches: one 32-byte record per credited bearer),
                                rs_batch_grant_record / rs_batch_grant_bound / rs_batch_run_grant_records / rs_jit_selfcheck_grant_records (a backlogged batch's app: lines from unlogged launches: one 32-byte record per grant),
                                rs_batch_set_cell_configs / rs_batch_get_cell_config / rs_batch_slice_totals / rs_jit_selfcheck_cell_configs (per-cell weights, exponents and slice sizes in one batch),
+                               RS_USER_ABSENT / rs_batch_cell_users / rs_jit_selfcheck_ragged_cells (cells of different user counts in one batch: an absent-user suffix in a cell's row),
                                rs_group_* (one TTI of several drop-in cells in one launch), rs_group_image_stats (cqi_epoch per cell of a group),
                                rs_group_specialize / rs_group_jit_status / rs_jit_selfcheck_group (a group's own self-checked builds of the one-TTI kernel),
                                rs_group_set_avg / rs_group_get_avg / rs_group_set_pending / rs_group_schedule_tti_at (a group cell's PF averages resident on the device),
@@ -819,7 +820,20 @@ int rs_batch_seed(rs_batch* b, const uint32_t* seed /* [n_cells] */, const int64
  * rs_batch_set_bearers after this call likewise (slice priorities and customised slices stay uniform).  With jit = 1 the run-time
  * builds are compiled again, for the longest slice window of any cell, and self-checked as any build is; a checkpoint loads only into
  * a batch that was given the same rows; rs_batch_grant_bound for RS_SCHED_UPPERBOUND is the largest cell's; rs_batch_slice_bytes reads
- * each cell's own map. */
+ * each cell's own map.
+ * Cells of different user counts (ragged batches): a row of user_to_slice may END in RS_USER_ABSENT entries -- n_c >= 1 entries valid as
+ * above, then U - n_c times RS_USER_ABSENT.  Cell c then behaves, to the bit, like cell 0 of a one-cell batch created with n_users = n_c
+ * from the row's first n_c entries, in everything that batch returns about users 0 .. n_c - 1; its grids, trace mapping and state rows
+ * are the first n_c rows of the cell's.  The absent users u >= n_c are never scanned and never granted: they are in no record and in no
+ * rbg_to_user entry, their logged rows read as an unserved user's, and their cum_bytes / cum_rbs / avg_rate words keep, bit for bit,
+ * what they held (no decay, no write); their CQI rows, h_user_trace entries and rs_batch_write_state words are accepted, stored and
+ * ignored.  RS_ERR_INVALID naming cell and user: a slice id behind an RS_USER_ABSENT, a row of nothing else, any other negative value.
+ * The shared rs_config takes no RS_USER_ABSENT.  rs_batch_grant_bound counts each cell's own users (min(n_c, R); UpperBound: per slice)
+ * and returns the largest cell's; the slice window is taken over the present users; rs_batch_slice_bytes / rs_batch_slice_totals skip
+ * the absent ones; the checkpoint hash covers the suffixes, so a checkpoint loads only into a batch of the same counts; run-time builds
+ * of a batch with an absent user carry -DRS_JIT_CELL_CONFIGS=2 (any other batch's builds are what they were).  Still uniform: S, R,
+ * algo_alpha / algo_beta. */
+#define RS_USER_ABSENT (-1)
 int rs_batch_set_cell_configs(rs_batch* b,
         const double*  slice_weight  /* [n_cells][S] or NULL */,
         const int32_t* algo_epsilon  /* [n_cells][S] or NULL */,
@@ -831,6 +845,8 @@ int rs_batch_get_cell_config(rs_batch* b, int32_t cell, double* slice_weight /* 
 /* per cell and slice, the sums of the users' cumulative bytes and RBs by the cell's own map, reduced on the device (exact integer sums):
  * the two panels of the reference's plot_throughput.py:26-56, per cell */
 int rs_batch_slice_totals(rs_batch* b, int64_t* cum_bytes /* [n_cells][S] or NULL */, int64_t* cum_rbs /* [n_cells][S] or NULL */);
+/* every cell's user count n_c: the entries of its row before the RS_USER_ABSENT suffix; U for every cell of a batch without rows */
+int rs_batch_cell_users(rs_batch* b, int32_t* n_users /* [n_cells] */);
 
 /* CQI source A: explicit grids. h_cqi = [n_cells][n_epochs][U][R] (host); epoch e serves scheduled
  * TTIs [e*cqi_refresh, (e+1)*cqi_refresh).  Copied to HBM once. */
@@ -1104,6 +1120,8 @@ int rs_jit_selfcheck_grant_records(int n_slices, int n_users, int n_rbgs, int rb
 /* the batch kernel of this shape with per-cell configuration rows (what rs_batch_set_cell_configs compiles for a batch with jit = 1):
  * lean = 0 the general build, 1 the lean build.  A negative value with the reason in err for RS_SCHED_NVS_NONGREEDY. */
 int rs_jit_selfcheck_cell_configs(int n_slices, int n_users, int n_rbgs, int rbg_size, int threads, int sched, int lean, char* err, size_t errlen);
+/* the same with rows that end in absent users (what a ragged batch compiles: -DRS_JIT_CELL_CONFIGS=2) */
+int rs_jit_selfcheck_ragged_cells(int n_slices, int n_users, int n_rbgs, int rbg_size, int threads, int sched, int lean, char* err, size_t errlen);
 /* ---- the run-time compiled kernels' cache on disk (ABI 10) ----
  * Every code object hiprtc produces (rs_batch_create with jit = 1, the lean / streamed variants, rs_ctx_specialize) is kept in
  * $RS_JIT_CACHE_DIR (default $XDG_CACHE_HOME/radiosaber_amd, else ~/.cache/radiosaber_amd; created with mode 0700), one file per (device

@@ -349,8 +349,10 @@ struct rs_batch {
   /* per-cell configurations (rs_batch_set_cell_configs): every cell's own row of the four arrays above, on the host and
    * on the device; the launch block then points at the rows and says so (RsLaunch::cell_cfg).  Configuration, not state. */
   bool cell_cfg = false;
+  bool ragged = false;                         /* some row of cc_u2s ends in RS_USER_ABSENT: cells of different user counts */
   std::vector<double> cc_weight;               /* [cells][S] */
   std::vector<int32_t> cc_eps, cc_psi, cc_u2s; /* [cells][S], [cells][S], [cells][U] */
+  std::vector<int32_t> cc_users;               /* [cells]: the row's users before the absent suffix (U where there is none) */
   double* d_cc_weight = nullptr;
   int32_t *d_cc_eps = nullptr, *d_cc_psi = nullptr;
   uint8_t* d_cc_user_slice = nullptr;
@@ -399,7 +401,7 @@ int upad_of(int U) { return rs_upad_of(U); }
  * 8-aligned end behind its last (a compile-time constant of the shape-specialised kernel, RS_JIT_WIN) */
 int map_window(const int32_t* u2s, int U) {
   int win = 0;
-  for (int u = 0; u < U;) {
+  for (int u = 0; u < U && u2s[u] != RS_USER_ABSENT;) { /* (a ragged batch's row: the absent suffix is in no window) */
     int e = u;
     while (e < U && u2s[e] == u2s[u]) e++;
     const int w = ((e + 7) & ~7) - (u & ~7);
@@ -419,7 +421,7 @@ int slice_window(const rs_batch* b) {
  * are a compile-time switch, named only by a batch that has per-cell rows -- every other batch's option lists are what they were */
 std::string jit_variant(const rs_batch* b, const char* more = nullptr) {
   std::string v = more ? more : "";
-  if (b->cell_cfg) v += std::string(v.empty() ? "" : " ") + "-DRS_JIT_CELL_CONFIGS=1";
+  if (b->cell_cfg) v += std::string(v.empty() ? "" : " ") + (b->ragged ? "-DRS_JIT_CELL_CONFIGS=2" : "-DRS_JIT_CELL_CONFIGS=1");
   return v;
 }
 /* (nullptr for the empty list: rs_jit_get's key names a variant only where there is one) */
@@ -1085,13 +1087,17 @@ int convert_tx(rs_batch* b, bool to_packed) {
 /* most grants of one cell in one TTI: a grant needs an RBG and goes to one user -- min(U, R); UpperBound's slices take their RBGs
  * whatever the other slices take: the sum over the slices of min(the slice's users, R), as rs_group_grant_bound has it */
 int grant_bound(const rs_batch* b) {
-  if (b->sched != RS_SCHED_UPPERBOUND) return std::min(b->U, b->R);
+  if (b->sched != RS_SCHED_UPPERBOUND) { /* (a ragged batch: the largest cell's users) */
+    int users = b->U;
+    if (b->ragged) users = *std::max_element(b->cc_users.begin(), b->cc_users.end());
+    return std::min(users, b->R);
+  }
   int most = 0;
   /* (per-cell maps: one capacity serves every cell's list -- the maximum over the cells of the per-slice sum) */
   for (int c = 0; c < (b->cell_cfg ? b->n_cells : 1); c++) {
     const int32_t* const u2s = b->cell_cfg ? b->cc_u2s.data() + (size_t)c * b->U : b->u2s.data();
     int sum = 0;
-    for (int u = 0; u < b->U;) {
+    for (int u = 0; u < b->U && u2s[u] != RS_USER_ABSENT;) { /* (absent users are in no slice) */
       int e = u;
       while (e < b->U && u2s[e] == u2s[u]) e++;
       sum += std::min(e - u, b->R);
@@ -1383,7 +1389,8 @@ int rs_batch_set_cell_configs(rs_batch* b, const double* slice_weight, const int
   const size_t cells = (size_t)b->n_cells, S = (size_t)b->S, U = (size_t)b->U;
   /* a NULL array: every cell keeps the shared configuration's values for that field */
   std::vector<double> w(cells * S);
-  std::vector<int32_t> e(cells * S), ps(cells * S), us(cells * U);
+  std::vector<int32_t> e(cells * S), ps(cells * S), us(cells * U), nu(cells);
+  bool any_absent = false;
   for (size_t c = 0; c < cells; c++) {
     for (size_t k = 0; k < S; k++) {
       w[c * S + k] = slice_weight ? slice_weight[c * S + k] : b->weight[k];
@@ -1399,11 +1406,21 @@ int rs_batch_set_cell_configs(rs_batch* b, const double* slice_weight, const int
       if ((e[c * S + k] | 1) != 1 || (ps[c * S + k] | 1) != 1)
         return fail(RS_ERR_INVALID, "cell %zu, slice %zu: algo_epsilon %d / algo_psi %d must be 0 or 1 in a batch", c, k, e[c * S + k], ps[c * S + k]);
     }
+    /* a row's users, then -- a cell of fewer users than the batch's -- RS_USER_ABSENT to the end (the shared map has none) */
+    size_t n = 0;
     for (size_t u = 0; u < U; u++) {
       const int32_t sl = us[c * U + u];
+      if (sl == RS_USER_ABSENT && user_to_slice) {
+        if (u == 0) return fail(RS_ERR_INVALID, "cell %zu, user 0: RS_USER_ABSENT -- a cell has at least one user (the absent users are a suffix of the row)", c);
+        continue;
+      }
       if (sl < 0 || sl >= b->S) return fail(RS_ERR_INVALID, "cell %zu, user %zu: slice %d out of range", c, u, sl);
+      if (n != u) return fail(RS_ERR_INVALID, "cell %zu, user %zu: slice %d behind RS_USER_ABSENT (user %zu) -- the absent users are a suffix of the row", c, u, sl, n);
       if (u && sl < us[c * U + u - 1]) return fail(RS_ERR_INVALID, "cell %zu: user_to_slice must be non-decreasing (user %zu)", c, u);
+      n = u + 1;
     }
+    nu[c] = (int32_t)n;
+    any_absent |= n != U;
   }
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   HIP_TRY(hipStreamSynchronize(b->stream));
@@ -1423,7 +1440,7 @@ int rs_batch_set_cell_configs(rs_batch* b, const double* slice_weight, const int
   char cmsg[sizeof b->jit_msg] = {0};
   if (b->jit_wanted) {
     cjit = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, 0, win, cmsg, sizeof cmsg, b->cfg.cqi_refresh <= 4 ? 2 : 0,
-                      "-DRS_JIT_CELL_CONFIGS=1");
+                      any_absent ? "-DRS_JIT_CELL_CONFIGS=2" : "-DRS_JIT_CELL_CONFIGS=1");
     if (cjit) snprintf(cmsg, sizeof cmsg, "%s", rs_jit_is_untuned(cjit) ? "in use, built WITHOUT the -mllvm tuning options (hiprtc refused them): a few per cent slower" : "");
     else if (!cmsg[0]) snprintf(cmsg, sizeof cmsg, "hiprtc build of the kernel with per-cell configurations failed");
     if (!cjit && b->threads > 512) return fail(RS_ERR_INVALID, "threads_per_cell %d needs the shape-specialised kernel with per-cell configurations: %s", b->threads, cmsg);
@@ -1435,16 +1452,17 @@ int rs_batch_set_cell_configs(rs_batch* b, const double* slice_weight, const int
     HIP_TRY(hipMalloc(&b->d_cc_user_slice, cells * U));
   }
   std::vector<uint8_t> us8(cells * U);
-  for (size_t i = 0; i < cells * U; i++) us8[i] = (uint8_t)us[i];
+  for (size_t i = 0; i < cells * U; i++) us8[i] = us[i] == RS_USER_ABSENT ? (uint8_t)RS_SLICE_ABSENT : (uint8_t)us[i];
   HIP_TRY(hipMemcpy(b->d_cc_weight, w.data(), 8 * cells * S, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(b->d_cc_eps, e.data(), 4 * cells * S, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(b->d_cc_psi, ps.data(), 4 * cells * S, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(b->d_cc_user_slice, us8.data(), cells * U, hipMemcpyHostToDevice));
   /* commit: rows, launch block, carve and kernels together */
-  b->cc_weight.swap(w); b->cc_eps.swap(e); b->cc_psi.swap(ps); b->cc_u2s.swap(us);
+  b->cc_weight.swap(w); b->cc_eps.swap(e); b->cc_psi.swap(ps); b->cc_u2s.swap(us); b->cc_users.swap(nu);
   b->cell_cfg = true;
+  b->ragged = any_absent;
   b->base.weight = b->d_cc_weight; b->base.eps = b->d_cc_eps; b->base.psi = b->d_cc_psi; b->base.user_slice = b->d_cc_user_slice;
-  b->base.cell_cfg = 1;
+  b->base.cell_cfg = any_absent ? RS_CELL_CFG_RAGGED : 1;
   carve_lds(b, &b->base);
   if (b->jit_wanted) {
     /* the builds belong to the rows' window and to the switch: the lean build, the records variants, the self-check and the autotune
@@ -1469,6 +1487,13 @@ int rs_batch_get_cell_config(rs_batch* b, int32_t cell, double* slice_weight, in
   if (algo_epsilon) memcpy(algo_epsilon, b->cell_cfg ? b->cc_eps.data() + c * S : b->eps.data(), 4 * S);
   if (algo_psi) memcpy(algo_psi, b->cell_cfg ? b->cc_psi.data() + c * S : b->psi.data(), 4 * S);
   if (user_to_slice) memcpy(user_to_slice, b->cell_cfg ? b->cc_u2s.data() + c * U : b->u2s.data(), 4 * U);
+  return RS_OK;
+}
+
+int rs_batch_cell_users(rs_batch* b, int32_t* n_users) {
+  if (!b || !n_users) return fail(RS_ERR_INVALID, "null argument");
+  if (b->direct) return fail(RS_ERR_INVALID, "cell users: not a batch");
+  for (int c = 0; c < b->n_cells; c++) n_users[c] = b->cell_cfg ? b->cc_users[c] : b->U;
   return RS_OK;
 }
 

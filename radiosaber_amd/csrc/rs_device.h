@@ -30,6 +30,8 @@ typedef unsigned long size_t;
 #define RS_FULL_PACKET 1495 /* MAXMTUSIZE 1490 + UDP 8 + IP 20, ROHC 28 -> 3, PDCP 2 (ref: src/protocolStack/packet/Packet.cpp:84-118) */
 #define RS_MAX_TTIS_PER_LAUNCH 32768
 #define RS_MAX_BYTES_PER_TTI 65535
+#define RS_CELL_CFG_RAGGED 2   /* RsLaunch::cell_cfg / RS_JIT_CELL_CONFIGS: per-cell rows with absent users behind a cell's last one */
+#define RS_SLICE_ABSENT 0xFF   /* the device map's byte of an absent user (RS_USER_ABSENT; slice ids stop at 63) */
 #define RS_PF_SEG 32 /* sched 1: users are scanned in segments of this many for the per-RBG argmax */
 
 /* per-cell scratch in LDS (host needs its size for the LDS carve) */
@@ -268,7 +270,8 @@ struct RsLaunch {
   int32_t queue_mode;        /* 1: some slice has alpha != 0 */
   /* batches, rs_batch_set_cell_configs: 1 -- weight, eps, psi and user_slice above hold one row per cell and the cell's load phase reads
    * its own (the per-TTI path reads none of the four).  In the padding behind queue_mode: no word of the block moves.  The built-in
-   * kernels test it at run time; a run-time build has it as a constant (RS_JIT_CELL_CONFIGS) */
+   * kernels test it at run time; a run-time build has it as a constant (RS_JIT_CELL_CONFIGS).  RS_CELL_CFG_RAGGED (2): rows, and some
+   * row of user_slice ends in absent users (RS_SLICE_ABSENT bytes): the cell's load phase finds its own user count */
   int32_t cell_cfg;
   const int32_t* alpha;      /* [S] */
   const int32_t* beta;       /* [S] */

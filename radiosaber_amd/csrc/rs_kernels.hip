@@ -211,6 +211,22 @@ __device__ __forceinline__ void rs_cell_body(const RsLaunch& p, unsigned char* l
   const int32_t* const cfg_eps = p.eps + cfg_row * S;
   const int32_t* const cfg_psi = p.psi + cfg_row * S;
   const uint8_t* const cfg_user_slice = p.user_slice + cfg_row * U;
+  /* Ragged batches (cell_cfg == RS_CELL_CFG_RAGGED): a cell's row of user_slice may end in absent users (RS_SLICE_ABSENT), and the cell
+   * then runs as one of Un = n_c users: Un bounds every loop over users that writes -- the segment table, the EWMA and its PF terms,
+   * the next TTI's preparation, the state flush -- while U stays what the carve, the grid's pitch and every stride in HBM are made
+   * of.  An absent user's stage-1 reciprocal is never written and stays the zero of the load phase: to the scans it is one more slot
+   * outside the window.  The row is present users, then absent ones (the host checks it), so Un is found by bisection -- wave-uniform
+   * loads, once per launch.  Any other build or launch: Un is U, folded. */
+  const bool ragged = cell_cfg && (FIXED ? RS_JIT_CELL_CONFIGS == RS_CELL_CFG_RAGGED : p.cell_cfg == RS_CELL_CFG_RAGGED);
+  int un_ = U;
+  if (ragged) {
+    int lo = 0; /* (user 0 is present) */
+    while (un_ - lo > 1) {
+      const int mid = (lo + un_) >> 1;
+      if (cfg_user_slice[mid] == RS_SLICE_ABSENT) un_ = mid; else lo = mid;
+    }
+  }
+  const int Un = un_;
   constexpr RsCarve kCv = rs_carve(RS_JIT_S, RS_JIT_U, RS_JIT_R, RS_JIT_SCHED, RS_JIT_NT, RS_JIT_CARVEQ, RS_JIT_WIN);
   /* byte offsets of the LDS arrays: constants in a shape-specialised build */
   struct Offs { int avgk, rcp, tab, slice, tx, misc, tbs, elems, sorted, items, sortx, cqi, queue, Upad, n_seg, n_items; };
@@ -437,14 +453,14 @@ __device__ __forceinline__ void rs_cell_body(const RsLaunch& p, unsigned char* l
   }
   /* segments scanned in P3: slices (7/8/9) or fixed runs of RS_PF_SEG users (1) */
   if (SCHED == 1) {
-    if (tid <= o.n_seg) m->seg_begin[tid] = min(tid * RS_PF_SEG, U);
+    if (tid <= o.n_seg) m->seg_begin[tid] = min(tid * RS_PF_SEG, Un); /* (a ragged cell: empty runs behind its last user) */
   } else {
-    if (tid <= S) m->seg_begin[tid] = U; /* filled below */
+    if (tid <= S) m->seg_begin[tid] = Un; /* filled below */
   }
   __syncthreads();
   if (SCHED != 1) {
     /* user_slice is non-decreasing: slice s = [first u with slice >= s, ...) */
-    for (int u = tid; u < U; u += nt) {
+    for (int u = tid; u < Un; u += nt) {
       int s = kPrefetch ? (int)s_uoff[u] : (int)cfg_user_slice[u];
       int sp = u == 0 ? -1 : (kPrefetch ? (int)s_uoff[u - 1] : (int)cfg_user_slice[u - 1]);
       for (int q = sp + 1; q <= s; q++) m->seg_begin[q] = u;
@@ -470,7 +486,7 @@ __device__ __forceinline__ void rs_cell_body(const RsLaunch& p, unsigned char* l
         if (u < U) s_uoff[u] = (int16_t)(m->rcp_off[pre_sl[k]] | ((m->eps_psi[pre_sl[k]] & 2) ? 1 : 0));
       }
     } else {
-      for (int u = tid; u < U; u += nt) s_uoff[u] = (int16_t)(m->rcp_off[cfg_user_slice[u]] | (cfg_psi[cfg_user_slice[u]] ? 1 : 0));
+      for (int u = tid; u < Un; u += nt) s_uoff[u] = (int16_t)(m->rcp_off[cfg_user_slice[u]] | (cfg_psi[cfg_user_slice[u]] ? 1 : 0));
     }
   }
   double t = kDirect ? 0.0 : scal->t;
@@ -729,7 +745,7 @@ __device__ __forceinline__ void rs_cell_body(const RsLaunch& p, unsigned char* l
   for (int ku = 0; ku < (kCumRegs ? kKU : 1); ++ku) {
     if (!kCumRegs) break;
     const int u = tid + ku * nt;
-    if (u < U) {
+    if (u < Un) {
       /* totals = what the EWMA updates consumed + the last TTI's service still waiting in s_tx (marked as counted) */
       const int v = s_tx[u];
       const long long b = (long long)cum_b[ku] + (v & RS_TX_BYTES_MASK), r = (long long)cum_r[ku] + ((v >> RS_TX_NPRB_SHIFT) & RS_TX_NPRB_MASK);
@@ -739,7 +755,7 @@ __device__ __forceinline__ void rs_cell_body(const RsLaunch& p, unsigned char* l
       p.tx_bytes[(size_t)cell * U + u] = v ? (v | RS_TX_COUNTED) : 0;
     }
   }
-  for (int u = tid; u < U && !kCumRegs && !kDirect; u += nt) {
+  for (int u = tid; u < Un && !kCumRegs && !kDirect; u += nt) {
     p.avg[(size_t)cell * U + u] = ((kSpecSched || kHoldSched) && s_avg[u] < 1) ? 1.0 : s_avg[u];
     p.tx_bytes[(size_t)cell * U + u] = s_tx[u];
   }
@@ -1046,7 +1062,9 @@ __global__ void rs_slice_bytes_kernel(const int64_t* cum_bytes, const uint8_t* u
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t c = i / U;
     int u = (int)(i - c * U);
-    atomicAdd(&acc[user_slice[c * map_stride + u] & 63], (unsigned long long)cum_bytes[i]);
+    const int s = user_slice[c * map_stride + u];
+    if (s == RS_SLICE_ABSENT) continue; /* (a ragged batch's absent user: in no slice, whatever its counters hold) */
+    atomicAdd(&acc[s & 63], (unsigned long long)cum_bytes[i]);
   }
   __syncthreads();
   if (threadIdx.x < S && acc[threadIdx.x]) atomicAdd(&d_out[threadIdx.x], acc[threadIdx.x]);
@@ -1064,6 +1082,7 @@ __global__ void __launch_bounds__(256) rs_slice_totals_kernel(const int64_t* cum
   __syncthreads();
   const uint8_t* const map = user_slice + (int64_t)cell * map_stride;
   for (int u = threadIdx.x; u < U; u += blockDim.x) {
+    if (map[u] == RS_SLICE_ABSENT) continue; /* (a ragged batch's absent user: in no slice, whatever its counters hold) */
     const int s = map[u] & 63;
     atomicAdd(&acc[s], (unsigned long long)cum_bytes[(int64_t)cell * U + u]);
     atomicAdd(&acc[64 + s], (unsigned long long)cum_rbs[(int64_t)cell * U + u]);

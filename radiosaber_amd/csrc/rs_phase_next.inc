@@ -24,7 +24,7 @@
     }
     if (((kHoldSched && ewma_next) || early17) && wave != 0) {
       const int nsp = nt - 64, me = tid - 64;
-      for (int u = me; u < U; u += nsp) {
+      for (int u = me; u < Un; u += nsp) {
         double a = s_avg[u];
         if (a < 1) a = 1;
         const double beta = 0.02;
@@ -110,7 +110,7 @@
       RS_SETPRIO(RS_SPEC_PRIO);
       /* P1: avg' = (1 - beta) * avg + beta * 0 = (1 - beta) * avg exactly; the unclamped product stays in s_avg (a served
        * user's exact update adds beta * rate to it), the PF terms use the clamped value */
-      for (int u = me; u < U; u += nsp) {
+      for (int u = me; u < Un; u += nsp) {
         double a = s_avg[u];
         if (a < 1) a = 1;
         const double beta = 0.02;

@@ -308,13 +308,13 @@
       if constexpr (kCumRegs) {
 #pragma unroll
         for (int ku = 0; ku < kKU; ++ku)
-          if (tid + ku * nt < U) ewma_user(tid + ku * nt, ku);
+          if (tid + ku * nt < Un) ewma_user(tid + ku * nt, ku);
       } else if constexpr (kPrefetch) {
 #pragma unroll
         for (int ku = 0; ku < kPU; ++ku)
           if (tid + ku * nt < U) ewma_user(tid + ku * nt, ku);
       } else {
-        for (int u = tid, ku = 0; u < U; u += nt, ++ku) ewma_user(u, ku);
+        for (int u = tid, ku = 0; u < Un; u += nt, ++ku) ewma_user(u, ku);
       }
       if (!kDirect) last_update = t;
       __syncthreads();
@@ -325,7 +325,7 @@
 #pragma unroll
         for (int ku = 0; ku < kKU; ++ku) {
           const int u = tid + ku * nt;
-          if (u < U) {
+          if (u < Un) {
             int v = s_tx[u];
             if (v != 0) {
               /* (NVS with its winners in place runs this TTI without a barrier before wave 0's next grant: take the word atomically) */

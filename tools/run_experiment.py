@@ -22,9 +22,10 @@ A backlogged configuration takes --records too: one 32-byte record per grant (ru
 
 Several runs in one launch: the reference's scripts start one process per (configuration file, seed) of a directory -- config-pf.json and
 config-mt.json times nine seeds -- and a batch runs them as cells of one launch (per-cell configurations).  Name the
-configuration files (--config a.json b.json, one shape: the same numbers of slices and users), the seeds (--seeds 0,1,2) and a --log
-template with {config} (the file's name without .json) and {seed}; --mapping takes the same two fields.  Every log is byte for byte
-the log of the single run of its (configuration, seed).  Backlogged configurations only; scheduler 11 runs one cell per process.
+configuration files (--config a.json b.json: the same number of slices, any numbers of users -- exp-fix20slices' 5, 10, 15 and 20 UEs
+per slice go together; the batch is created at the largest and the smaller cells' maps end in absent users), the seeds (--seeds 0,1,2)
+and a --log template with {config} (the file's name without .json) and {seed}; --mapping takes the same two fields.  Every log is byte
+for byte the log of the single run of its (configuration, seed).  Backlogged configurations only; scheduler 11 runs one cell per process.
 
     python tools/run_experiment.py --sched 9 --duration 12 --config config-pf.json config-mt.json --seeds 0,1,2,3,4,5,6,7,8 \\
         --records --log 'maxcell_{config}_{seed}.log'
@@ -52,8 +53,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--sched", type=int, default=9, help="the reference's CLI scheduler number: 1, 7, 8, 9, 10, 11")
 ap.add_argument("--seed", type=int, default=0, help="index into the reference's nine common seeds")
 ap.add_argument("--duration", type=float, default=12.0, help="simulated seconds after the 0.1 s start-up")
-ap.add_argument("--config", required=True, nargs="+", help="slice configuration JSON of the experiment directory; several files of one shape "
-                                                         "(slices, users) run as cells of one batch")
+ap.add_argument("--config", required=True, nargs="+", help="slice configuration JSON of the experiment directory; several files of one number "
+                                                         "of slices (any numbers of users) run as cells of one batch")
 ap.add_argument("--seeds", default=None, help="comma-separated indices into the nine common seeds: every configuration runs with each of "
                                               "them, all in one batch (instead of --seed)")
 ap.add_argument("--traces", default=None, help="directory with ue<id>.log and the mapping file (default: synthetic CQI grids)")
@@ -76,7 +77,7 @@ a = ap.parse_args()
 seed_ids = [int(x) for x in a.seeds.split(",")] if a.seeds is not None else [a.seed]
 runs = [(Path(path).name[:-5] if path.endswith(".json") else Path(path).name, rs.SliceConfig.from_json(path), k) for path in a.config for k in seed_ids]
 n_cells = len(runs)
-sc = runs[0][1]
+sc = max((cfg for _, cfg, _ in runs), key=lambda cfg: cfg.n_users)  # the batch is created at the largest configuration
 R = a.nb_rbs // a.rbg_size
 n_ttis = int(round(a.duration * 1000))
 U = sc.n_users
@@ -91,8 +92,8 @@ if n_cells > 1:
         raise SystemExit("several runs in one batch: backlogged configurations only (the queue model keeps one configuration per batch)")
     if a.sched == 11:
         raise SystemExit("several runs in one batch: scheduler 11 reads one configuration (its kernel is another one)")
-    if any(cfg.n_slices != sc.n_slices or cfg.n_users != U for _, cfg, _ in runs):
-        raise SystemExit("several runs in one batch: every configuration needs the same numbers of slices and users")
+    if any(cfg.n_slices != sc.n_slices for _, cfg, _ in runs):
+        raise SystemExit("several runs in one batch: every configuration needs the same number of slices")
     if len(set(logs)) != n_cells:
         raise SystemExit("several runs in one batch: --log needs {config} and / or {seed} so that every run has a log of its own")
 # (the queue model's batches run without the PHY error model's draws: its parity with the oracle is pinned that way)
@@ -102,9 +103,11 @@ if n_cells > 1:
 b.seed(np.array(seeds, np.uint32), np.full(n_cells, a.rand_skip, np.int64))
 if a.traces:
     maps = []
-    for name, _, k in runs:
+    for name, cfg, k in runs:
         mapping = rs.read_trace_mapping(Path(a.traces) / a.mapping.format(config=name, seed=k))
-        maps.append(mapping[np.arange(U) % len(mapping)].astype(np.int32))
+        row = np.zeros(U, np.int32)  # (the entries of a smaller cell's absent users are stored and ignored)
+        row[:cfg.n_users] = mapping[np.arange(cfg.n_users) % len(mapping)]
+        maps.append(row)
     trace, mixed = rs.load_trace_dir(a.traces, n_traces=int(max(m.max() for m in maps)) + 1, nb_rbs=a.nb_rbs, rbg_size=a.rbg_size)
     if mixed:
         raise SystemExit(f"{mixed} RBGs carry different CQI on their PRBs: the batched replay needs uniform RBGs")
@@ -112,15 +115,19 @@ if a.traces:
 elif n_cells == 1:
     b.synthesize_cqi(seed, (n_ttis + 39) // 40)
 else:
-    # a single run draws its grids under (its seed, cell 0): each distinct seed's grids are drawn that way once, on the device, and
-    # uploaded as the epoch grids of the cells that run with it
+    # a single run draws its grids under (its seed, cell 0) at its own user count: each distinct (seed, user count)'s grids are drawn
+    # that way once, on the device, and uploaded as the epoch grids of the cells that run with them (an absent user's rows: any valid
+    # CQI, stored and ignored)
     drawn = {}
-    for sd in sorted(set(seeds)):
-        one = rs.BatchScheduler(sc, R, a.rbg_size, 1, sched=a.sched)
+    for sd, (_, cfg, _) in zip(seeds, runs):
+        if (sd, cfg.n_users) in drawn:
+            continue
+        one = rs.BatchScheduler(cfg, R, a.rbg_size, 1, sched=a.sched)
         one.synthesize_cqi(sd, (n_ttis + 39) // 40)
-        drawn[sd] = one.download_cqi_epochs(0)
+        grid = one.download_cqi_epochs(0)
         one.close()
-    b.upload_cqi_epochs(np.stack([drawn[sd] for sd in seeds]))
+        drawn[(sd, cfg.n_users)] = np.concatenate([grid, np.ones((grid.shape[0], U - cfg.n_users, R), grid.dtype)], axis=1)
+    b.upload_cqi_epochs(np.stack([drawn[(sd, cfg.n_users)] for sd, (_, cfg, _) in zip(seeds, runs)]))
 
 flows = {}
 if queues:
@@ -160,7 +167,7 @@ while done < n_ttis:  # logged launches of at most 2 000 TTIs keep the host log 
     if a.records and not queues:
         # a backlogged batch: one record per grant; the rows the writer reads are rebuilt from them (the map is not among them)
         for c, recs in enumerate(b.run_grant_records(n)):
-            rows = logfmt.rows_from_grant_records(recs, n, U, R, done, with_map=False)
+            rows = logfmt.rows_from_grant_records(recs, n, runs[c][1].n_users, R, done, with_map=False)
             by, hol = logfmt.bearer_rows_from_users(rows["tbs_bits"])
             rbs = logfmt.bearer_prbs(np.zeros((n, R), np.int16), rows["uinfo"] & 0xFFFF, a.rbg_size)
             lines = writers[c].lines(by, hol, rbs, float(t_first[c]), None)
@@ -176,13 +183,14 @@ while done < n_ttis:  # logged launches of at most 2 000 TTIs keep the host log 
         continue
     got = b.run_logged(n, bearers=queues)
     for c in range(n_cells):
+        nu = runs[c][1].n_users  # (a cell of fewer users than the batch's: its rows are the first nu)
         if queues:
             by, hol = got["bearer_bytes"][c], got["bearer_hol"][c]
             rec = {(u, k): v for (cc, u, k), v in b.flow_record().items() if (u, k) in flows}
         else:
-            by, hol = logfmt.bearer_rows_from_users(got["tbs_bits"][c])
+            by, hol = logfmt.bearer_rows_from_users(got["tbs_bits"][c][:, :nu])
             rec = None
-        rbs = logfmt.bearer_prbs(got["rbg_to_user"][c], got["nprb"][c], a.rbg_size, pf_flows=queues and a.sched == 1)
+        rbs = logfmt.bearer_prbs(got["rbg_to_user"][c], got["nprb"][c][:, :nu], a.rbg_size, pf_flows=queues and a.sched == 1)
         lines = writers[c].lines(by, hol, rbs, float(t_first[c]), rec)
         outs[c].write("\n".join(lines) + ("\n" if lines else ""))
     done += n
@@ -194,7 +202,7 @@ if n_cells == 1:
           " ".join(f"{x:.2f}" for x in (np.asarray(b.slice_bytes(), np.float64) * 8 / 1e6 / a.duration)), file=sys.stderr)
 else:
     totals = b.slice_totals()["cum_bytes"]
-    for c, (name, _, k) in enumerate(runs):
-        print(f"{name} seed {k}: {n_ttis} TTIs, {U} UEs, sched {a.sched}: per-slice Mbps " +
+    for c, (name, cfg, k) in enumerate(runs):
+        print(f"{name} seed {k}: {n_ttis} TTIs, {cfg.n_users} UEs, sched {a.sched}: per-slice Mbps " +
               " ".join(f"{x:.2f}" for x in (totals[c].astype(np.float64) * 8 / 1e6 / a.duration)), file=sys.stderr)
 b.close()
