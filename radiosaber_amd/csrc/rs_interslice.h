@@ -149,18 +149,17 @@ __device__ __forceinline__ int interslice_maximize_cell(const uint32_t* s_sorted
 template <bool K32> struct RsMaskT { typedef unsigned long long type; };
 template <> struct RsMaskT<true> { typedef uint32_t type; };
 
-/* one vector: records src[pos .. pos+64) of a stream of n, decided on the calling wave; free_rbg / left / n_taken updated */
+/* one vector: the record `e` of every `valid` lane, decided on the calling wave; `lt` = the lanes whose record the scan meets before
+ * mine (any total order of the valid lanes: the iteration below settles one more record of that order per round); free_rbg / left /
+ * n_taken updated (only the RBG and slice fields of a record are read) */
 template <class set_t>
-__device__ __forceinline__ void rs_scan_decide_vector(const uint32_t* src, int pos, int n, RsMisc* m, set_t& free_rbg, int& left,
-                                                      int& n_taken) {
+__device__ __forceinline__ void rs_scan_decide_records(uint32_t e, bool valid, unsigned long long lt, RsMisc* m, set_t& free_rbg, int& left,
+                                                       int& n_taken) {
   const int lane = lane_id();
-  const unsigned long long me = 1ull << lane, lt = me - 1ull;
+  const unsigned long long me = 1ull << lane;
   unsigned long long* const by_rbg = m->maskA;
   unsigned long long* const by_slice = m->maskB;
   unsigned char* const owner_of = (unsigned char*)m->n_level;
-  const int i = pos + lane;
-  const bool valid = i < n;
-  const uint32_t e = src[valid ? i : 0];
   const int rbg = (e >> 8) & 63, sl = e & 63;
   /* lanes of this vector by RBG and by slice (every valid lane: the ones that are not live never enter T) */
   if (valid) {
@@ -203,6 +202,68 @@ __device__ __forceinline__ void rs_scan_decide_vector(const uint32_t* src, int p
   n_taken += __popcll(T);
 }
 
+/* ... the records src[pos .. pos+64) of a stream of n */
+template <class set_t>
+__device__ __forceinline__ void rs_scan_decide_vector(const uint32_t* src, int pos, int n, RsMisc* m, set_t& free_rbg, int& left,
+                                                      int& n_taken) {
+  const int i = pos + lane_id();
+  const bool valid = i < n;
+  rs_scan_decide_records<set_t>(src[valid ? i : 0], valid, (1ull << lane_id()) - 1ull, m, free_rbg, left, n_taken);
+}
+
+/* Stable filter: the records of src[0 .. n) that are still live (RBG free, slice under quota) to dst[0 ..), in order; returns their
+ * number.  dst may be the array src points into, at or below src: the writes trail the reads (eight chunks of reads in flight). */
+template <class set_t>
+__device__ __forceinline__ int rs_scan_keep_live(const uint32_t* src, int n, uint32_t* dst, set_t free_rbg, set_t open_sl) {
+  const int lane = lane_id();
+  int kept = 0;
+  for (int b = 0; b < n; b += 8 * 64) {
+    uint32_t e[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int x = b + j * 64 + lane;
+      e[j] = src[x < n ? x : 0];
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int x = b + j * 64 + lane;
+      const int rbg = (e[j] >> 8) & 63, sl = e[j] & 63;
+      const bool inb = x < n, lv = ((free_rbg >> rbg) & (open_sl >> sl) & 1) != 0;
+      const unsigned long long mk = __builtin_amdgcn_ballot_w64(inb) & __builtin_amdgcn_ballot_w64(lv);
+      const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
+      if (inb & lv) dst[kept + below] = e[j];
+      kept += __popcll(mk);
+    }
+  }
+  return kept;
+}
+
+/*
+ * A stable sort of one wave's records by DESCENDING 4-bit key without moving a record: the lanes whose record that sort puts before
+ * mine, as a lane mask -- a larger key in any lane, or my key in a lower lane.  The four bit planes of the keys are ballots; one
+ * compare-from-the-top over them, two 32-bit halves: no LDS round trip, no lane exchange, no branch, and nothing here waits for
+ * anything but the keys.  (The rank is the mask's popcount.  Ranking and permuting the records instead -- counts per key from the
+ * same planes, a row scan, one ds_bpermute and one ds_permute -- put two LDS round trips in front of the decision step: +0.4 %
+ * on the headline against +1.6 % with the masks, same lease, profiles/greedy_from_segments.md.)
+ */
+__device__ __forceinline__ unsigned long long wave_stable_before_desc(int key, bool valid) {
+  const int lane = lane_id();
+  uint32_t gl = 0u, gh = 0u;   /* lanes with a larger key */
+  uint32_t el = ~0u, eh = ~0u; /* lanes that agree with my key in the bits seen so far */
+#pragma unroll
+  for (int b = 3; b >= 0; --b) {
+    const uint32_t mine = (uint32_t)(((int)((uint32_t)key << (31 - b))) >> 31); /* all ones when my key has bit b */
+    const unsigned long long plane = __builtin_amdgcn_ballot_w64(mine != 0u);
+    gl |= el & (uint32_t)plane & ~mine;
+    gh |= eh & (uint32_t)(plane >> 32) & ~mine;
+    el &= ~((uint32_t)plane ^ mine);
+    eh &= ~((uint32_t)(plane >> 32) ^ mine);
+  }
+  const unsigned long long vm = __builtin_amdgcn_ballot_w64(valid), lower = (1ull << lane) - 1ull;
+  const uint32_t bl = (gl | (el & (uint32_t)lower)) & (uint32_t)vm, bh = (gh | (eh & (uint32_t)(lower >> 32))) & (uint32_t)(vm >> 32);
+  return (unsigned long long)bl | ((unsigned long long)bh << 32);
+}
+
 template <int S_T, int R_T, bool K32> /* K32: at most 32 RBGs and 32 slices */
 __device__ __forceinline__ int interslice_maximize_cell_vector(uint32_t* s_sorted, RsMisc* m, int S_rt, int R_rt, int& got
 #ifdef RS_STAMPS
@@ -232,27 +293,77 @@ __device__ __forceinline__ int interslice_maximize_cell_vector(uint32_t* s_sorte
     pos += 64;
     if (n_taken < R && n - pos > 64) {
       /* keep what is still live of the rest (in place: the writes trail the reads; eight chunks of reads in flight) */
-      const set_t open_sl = (set_t)__ballot(left > 0);
-      int kept = 0;
-      for (int b = pos; b < n; b += 8 * 64) {
-        uint32_t e[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int x = b + j * 64 + lane;
-          e[j] = s_sorted[x < n ? x : 0];
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int x = b + j * 64 + lane;
-          const int rbg = (e[j] >> 8) & 63, sl = e[j] & 63;
-          const bool inb = x < n, lv = ((free_rbg >> rbg) & (open_sl >> sl) & 1) != 0;
-          const unsigned long long mk = __builtin_amdgcn_ballot_w64(inb) & __builtin_amdgcn_ballot_w64(lv);
-          const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-          if (inb & lv) s_sorted[kept + below] = e[j];
-          kept += __popcll(mk);
-        }
-      }
-      n = kept;
+      n = rs_scan_keep_live<set_t>(s_sorted + pos, n - pos, s_sorted, free_rbg, (set_t)__ballot(left > 0));
+      pos = 0;
+    }
+  }
+#ifdef RS_STAMPS
+  if (threadIdx.x == 0) {
+    stamp_acc[9] += (unsigned long long)n_taken;
+    stamp_acc[10] += (unsigned long long)n_vec; /* vectors decided */
+  }
+#endif
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  if (lane < S) got = m->quota[lane] - left;
+  const int o = ((unsigned char*)m->n_level)[lane];
+  return (lane < R && o != 0xFF) ? o : -1; /* lane r: slice that got RBG r */
+}
+
+/*
+ * The same scan over the array std::__introsort_loop LEAVES, without the final insertion sort (shape-specialised builds, DESIGN.md
+ * 3.3): s_elems holds sub-ranges of at most 16 records, ordered against each other and unordered inside, every record with its
+ * sub-range's first position from bit RS_SEG_SHIFT up (rs_sort_device.h, TAG).  The final order is the stable sort by descending
+ * key of that array, so
+ *   - the records of final rank < c are the array positions < c whenever a sub-range starts at c: the first vector is the positions
+ *     below the last sub-range start at or before 64, decided in final order (wave_stable_before_desc: the records stay in their lanes);
+ *   - what is still live of the rest, filtered in array order, is in final order once every run of sub-ranges is sorted the same
+ *     way: the survivors go into vectors of at most 64 that end where the carried start changes (a sub-range holds at most 16
+ *     records: a vector is never empty).
+ * The ~400 records of the headline shape that no vector ever holds are never ranked.  `work`: N words of scratch (the sort's
+ * exchange buffer); s_elems is only read.
+ */
+template <int S_T, int R_T, bool K32>
+__device__ __forceinline__ int interslice_maximize_cell_segments(const uint32_t* s_elems, uint32_t* work, RsMisc* m, int S_rt, int R_rt, int& got
+#ifdef RS_STAMPS
+                                                        , unsigned long long* stamp_acc
+#endif
+) {
+  const int lane = lane_id();
+  const int S = S_T ? S_T : S_rt, R = R_T ? R_T : R_rt;
+  const int N = R * S;
+  typedef typename RsMaskT<K32>::type set_t;
+  set_t free_rbg = R >= (int)(8 * sizeof(set_t)) ? ~(set_t)0 : (set_t)(((set_t)1 << R) - 1);
+  int left = lane < S ? m->quota[lane] : 0; /* lane s: quota[s] - granted[s] */
+  int n_taken = 0;
+#ifdef RS_STAMPS
+  int n_vec = 0;
+#endif
+  m->maskA[lane] = 0ull;
+  m->maskB[lane] = 0ull;
+  ((unsigned char*)m->n_level)[lane] = 0xFF;
+  /* records of *src from `pos` on that make the next vector: all that are left when they fit, otherwise the 64 next ones without the
+   * sub-range that goes on behind them */
+  auto vector_len = [&](const uint32_t* src, int pos, int n, uint32_t e) -> int {
+    if (n - pos <= 64) return n - pos;
+    const uint32_t f63 = (uint32_t)__builtin_amdgcn_readlane((int)e, 63) >> RS_SEG_SHIFT;
+    const uint32_t f64 = (uint32_t)__builtin_amdgcn_readfirstlane((int)src[pos + 64]) >> RS_SEG_SHIFT;
+    if (f64 != f63) return 64;
+    return __builtin_ctzll(__builtin_amdgcn_ballot_w64((e >> RS_SEG_SHIFT) == f63));
+  };
+  const uint32_t* src = s_elems;
+  int n = N, pos = 0;
+  while (n_taken < R && pos < n) {
+    const uint32_t e = src[pos + lane < n ? pos + lane : 0];
+    const int len = vector_len(src, pos, n, e);
+    rs_scan_decide_records<set_t>(e, lane < len, wave_stable_before_desc((int)(e >> 16) & 15, lane < len), m, free_rbg, left, n_taken);
+#ifdef RS_STAMPS
+    ++n_vec;
+#endif
+    pos += len;
+    if (n_taken < R && n - pos > 64) {
+      n = rs_scan_keep_live<set_t>(src + pos, n - pos, work, free_rbg, (set_t)__ballot(left > 0));
+      src = work;
       pos = 0;
     }
   }

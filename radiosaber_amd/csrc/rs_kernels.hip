@@ -257,6 +257,14 @@ __device__ __forceinline__ void rs_cell_body(const RsLaunch& p, unsigned char* l
   constexpr int kVecMaxR = RS_VEC_MAX_R;
   constexpr bool kVecScan = SCHED == 9 && (!FIXED || RS_JIT_R <= kVecMaxR);
   const bool vec_scan = kVecScan && R <= kVecMaxR;
+  /* Shape-specialised builds with the vector scan and the register form of the sort: no counting sort.  The sort's loop tags every
+   * record with its last sub-range and wave 0 orders, on its own lanes, only the records its vectors hold (rs_interslice.h,
+   * interslice_maximize_cell_segments).  -DRS_GREEDY_SORTED: the counting sort and the scan over s_sorted, as in the built-in kernels. */
+#ifdef RS_GREEDY_SORTED
+  constexpr bool kSegScan = false;
+#else
+  constexpr bool kSegScan = FIXED && kVecScan && EPT > 0;
+#endif
   /* Held winners (round 3): the winner of a (slice, RBG) item is NOT looked for again in a TTI in which it cannot
    * have changed -- the winner was not served in the previous TTI, the CQI grid is the same, and at the item's last scan its
    * stage-1 value led the slice by a margin that 40 TTIs of rounding and of the "+1" in (1 + avg) cannot use up.  Such TTIs scan

@@ -25,13 +25,15 @@
             if (EPT == 0) __syncthreads(); /* (the LDS form of the sort reads other positions first) */
           }
         }
-        if constexpr (EPT > 0) introsort_levels_reg<EPT, FIXED ? RS_JIT_NT : 0>(s_elems, N, s_sorted, (int32_t*)sx, m, sort_sub, 0,
+        if constexpr (EPT > 0) introsort_levels_reg<EPT, FIXED ? RS_JIT_NT : 0, kSegScan>(s_elems, N, s_sorted, (int32_t*)sx, m, sort_sub, 0,
                                                                            rs_sort_ranks_bytes(N) ? (uint16_t*)(lds + o.sortx + rs_sort_cuts_bytes(N)) : m->hist);
         else introsort_loop_levels(s_elems, N, pa, pa + N, sx, sx + N, sx + 2 * N, sx + 3 * N, m);
       }
       RS_STAMP(3);
       RS_SETPRIO(2);
-      if constexpr (EPT > 0) counting_sort_desc_owned<EPT, FIXED ? RS_JIT_NT : 0>(s_elems, s_sorted, N, m);
+      /* kSegScan: wave 0 reads the loop's array itself -- the tagged loop's closing barrier is all that is left of this phase */
+      if constexpr (kSegScan) __syncthreads();
+      else if constexpr (EPT > 0) counting_sort_desc_owned<EPT, FIXED ? RS_JIT_NT : 0>(s_elems, s_sorted, N, m);
       else counting_sort_desc(s_elems, s_sorted, N, m);
       RS_SETPRIO(0);
       RS_STAMP(4);

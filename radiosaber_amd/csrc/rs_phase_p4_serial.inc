@@ -308,7 +308,13 @@
 #else
 #define RS_SCAN_ARGS s_sorted, m, S, R, got
 #endif
-          if constexpr (kVecScan) {
+          if constexpr (kSegScan) {
+#ifdef RS_STAMPS
+            my_slice = interslice_maximize_cell_segments<kS, kR, (kS <= 32 && kR <= 32)>(s_elems, s_sorted, m, S, R, got, stamp_acc);
+#else
+            my_slice = interslice_maximize_cell_segments<kS, kR, (kS <= 32 && kR <= 32)>(s_elems, s_sorted, m, S, R, got);
+#endif
+          } else if constexpr (kVecScan) {
             if constexpr (FIXED) {
               my_slice = interslice_maximize_cell_vector<kS, kR, (kS <= 32 && kR <= 32)>(RS_SCAN_ARGS);
             } else {

@@ -230,6 +230,11 @@ __device__ void introsort_loop_levels(uint32_t* v, int N, uint16_t* posA, uint16
  * needs no special case), 32-bit counts, and the cut as the first candidate at or above the piece's first inner lane (a piece's
  * candidates are exactly its lanes from the cut on, so no upper bound is needed).  ~95 instructions per level against ~150
  * (profiles/r06_sort_staged.md; the form of rounds 3-5 is in the history up to commit 5593943, behind -DRS_FINISH_V1). */
+/* TAG (MaximizeCell's vector scan): every position writes its record back with the first position of its final
+ * sub-range -- the at most 16 records std::__final_insertion_sort orders among themselves -- in the record's free bits from
+ * RS_SEG_SHIFT up (keys are 4 bits: 16-19).  A heap-sorted range is in final order already: each of its positions is a sub-range of
+ * its own. */
+template <bool TAG = false>
 __device__ __forceinline__ void finish_subranges_on_wave(uint32_t* v, uint32_t* xbuf, int fb, int lb, int l0, int depth, Misc* m) {
   const int lane = lane_id();
   const bool mine = l0 != 0;
@@ -240,7 +245,7 @@ __device__ __forceinline__ void finish_subranges_on_wave(uint32_t* v, uint32_t* 
   while (__builtin_amdgcn_ballot_w64(L != 0) != 0ull) {
     const bool active = L != 0;
     if (depth == 0) { /* std::__partial_sort fallback: one piece after the other, each on every lane (heap_sort_on_wave) */
-      if (mine) v[x] = e;
+      if (mine) v[x] = (TAG && !active) ? e | ((uint32_t)F << RS_SEG_SHIFT) : e;
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       __builtin_amdgcn_wave_barrier();
       unsigned long long lead = __builtin_amdgcn_ballot_w64(active && x == F);
@@ -248,6 +253,11 @@ __device__ __forceinline__ void finish_subranges_on_wave(uint32_t* v, uint32_t* 
         const int j = __ffsll((long long)lead) - 1;
         lead &= lead - 1ull;
         heap_sort_on_wave(v, __builtin_amdgcn_readlane(F, j), __builtin_amdgcn_readlane(L, j), m, 1);
+      }
+      if constexpr (TAG) { /* the heap sorts moved untagged records: every position of a sorted piece names itself */
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (mine && active) v[x] = v[x] | ((uint32_t)x << RS_SEG_SHIFT);
       }
       return;
     }
@@ -296,10 +306,12 @@ __device__ __forceinline__ void finish_subranges_on_wave(uint32_t* v, uint32_t* 
     L = (active & (nL - nF > 16)) ? nL : 0;
     --depth;
   }
-  if (mine) v[x] = e;
+  if (mine) v[x] = TAG ? e | ((uint32_t)F << RS_SEG_SHIFT) : e; /* (F: where my piece began when it retired) */
 }
 
-template <int EPT, int NT = 0> /* NT: the workgroup's size where it is a compile-time constant (shape-specialised builds), 0: blockDim.x */
+/* TAG: see finish_subranges_on_wave; the tagged form leaves its closing barrier to the caller (the records retired by the levels
+ * are written before the last level's barrier, but the waves read m->n_level behind it) */
+template <int EPT, int NT = 0, bool TAG = false> /* NT: the workgroup's size where it is a compile-time constant (shape-specialised builds), 0: blockDim.x */
 __device__ __forceinline__ void introsort_levels_reg(uint32_t* v, int N, uint32_t* xbuf, int32_t* cuts, Misc* m,
                                      unsigned long long* sub, int seg_len = 0, uint16_t* ranks = nullptr) {
   /* sub-ranges per wave at which the last levels go to single waves (same-box A/B, 512 cells: one position per lane -- 500 records --
@@ -506,11 +518,17 @@ __device__ __forceinline__ void introsort_levels_reg(uint32_t* v, int N, uint32_
         const int x = i * nt + tid;
         const bool live = L[i] != 0, got = slot[i] >= 0;
         e[i] = got ? rx[i] : e[i];
-        if (got) v[x] = e[i];
+        if constexpr (!TAG) {
+          if (got) v[x] = e[i];
+        }
         const bool left = x < cut_[i];
         const int nF = left ? F[i] : cut_[i], nL = left ? cut_[i] : L[i];
         F[i] = live ? nF : F[i];
         L[i] = (live & (nL - nF > 16)) ? nL : 0;
+        if constexpr (TAG) { /* a position whose sub-range retires here writes its record once more, with the sub-range's start */
+          const bool retire = live & (L[i] == 0);
+          if (got | retire) v[x] = retire ? e[i] | ((uint32_t)F[i] << RS_SEG_SHIFT) : e[i];
+        }
         const int len = x == F[i] ? L[i] - F[i] : 0; /* > 0 on the first position of a live sub-range only (a retired one has L = 0) */
         alive += __popcll(__builtin_amdgcn_ballot_w64(len > 0)) + (__popcll(__builtin_amdgcn_ballot_w64(len > 64)) << 16);
       }
@@ -559,7 +577,7 @@ __device__ __forceinline__ void introsort_levels_reg(uint32_t* v, int N, uint32_
         used += l - f;
         ++t;
       } while (t < n_mine);
-      finish_subranges_on_wave(v, xbuf, fb, lb, l0, depth, m);
+      finish_subranges_on_wave<TAG>(v, xbuf, fb, lb, l0, depth, m);
     }
     } else {
     /* Every wave reads the whole list (at most kFinishMax * nwaves <= 32 entries, lane j = entry j), ranks the entries
@@ -606,10 +624,10 @@ __device__ __forceinline__ void introsort_levels_reg(uint32_t* v, int N, uint32_
         used += l - f;
         mine &= ~(1ull << j);
       }
-      finish_subranges_on_wave(v, xbuf, fb, lb, l0, depth, m);
+      finish_subranges_on_wave<TAG>(v, xbuf, fb, lb, l0, depth, m);
     }
     }
-    __syncthreads();
+    if constexpr (!TAG) __syncthreads();
   } else {
     /* std::__partial_sort fallback for every sub-range still longer than 16: their first positions publish them (the list of
      * the hand-off above; `v` is current, every level writes what it moves), the waves take them in turn (heap_sort_on_wave) */
@@ -630,8 +648,13 @@ __device__ __forceinline__ void introsort_levels_reg(uint32_t* v, int N, uint32_
     for (int j = wave; j < n_list; j += nwaves) {
       const int ent = cuts[j];
       heap_sort_on_wave(v, ent & 0xffff, ent >> 16, m, 0);
+      if constexpr (TAG) { /* (as in finish_subranges_on_wave: the sorted range's positions name themselves, on the wave that sorted it) */
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        for (int y = (ent & 0xffff) + lane; y < (ent >> 16); y += 64) v[y] = v[y] | ((uint32_t)y << RS_SEG_SHIFT);
+      }
     }
-    __syncthreads();
+    if constexpr (!TAG) __syncthreads();
   }
 }
 

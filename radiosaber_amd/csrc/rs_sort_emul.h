@@ -42,6 +42,11 @@ typedef unsigned long size_t;
 #define RS_HD inline
 #endif
 
+/* Packed elements are key << 16 | payload with 4-bit keys (CQIs): the bits from RS_SEG_SHIFT up are zero while an element is
+ * being sorted.  The device loop's tagged form (rs_sort_device.h) writes the first position of an element's final sub-range there
+ * once the element has retired, i.e. when no comparison reads it any more. */
+#define RS_SEG_SHIFT 20
+
 namespace rs_sort {
 
 /* comparator of the reference lambda on packed elements: a "less" b  <=>  key(a) > key(b) */
