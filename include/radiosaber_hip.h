@@ -31,6 +31,7 @@ extern "C" {
                                rs_batch_grant_record / rs_batch_grant_bound / rs_batch_run_grant_records / rs_jit_selfcheck_grant_records (a backlogged batch's app: lines from unlogged launches: one 32-byte record per grant),
                                rs_batch_set_cell_configs / rs_batch_get_cell_config / rs_batch_slice_totals / rs_jit_selfcheck_cell_configs (per-cell weights, exponents and slice sizes in one batch),
                                RS_USER_ABSENT / rs_batch_cell_users / rs_jit_selfcheck_ragged_cells (cells of different user counts in one batch: an absent-user suffix in a cell's row),
+                               rs_batch_set_cell_configs_n / rs_batch_cell_slices / rs_jit_selfcheck_ragged_slices (cells of different slice counts in one batch: an absent-slice suffix),
                                rs_group_* (one TTI of several drop-in cells in one launch), rs_group_image_stats (cqi_epoch per cell of a group),
                                rs_group_specialize / rs_group_jit_status / rs_jit_selfcheck_group (a group's own self-checked builds of the one-TTI kernel),
                                rs_group_set_avg / rs_group_get_avg / rs_group_set_pending / rs_group_schedule_tti_at (a group cell's PF averages resident on the device),
@@ -831,8 +832,8 @@ int rs_batch_seed(rs_batch* b, const uint32_t* seed /* [n_cells] */, const int64
  * The shared rs_config takes no RS_USER_ABSENT.  rs_batch_grant_bound counts each cell's own users (min(n_c, R); UpperBound: per slice)
  * and returns the largest cell's; the slice window is taken over the present users; rs_batch_slice_bytes / rs_batch_slice_totals skip
  * the absent ones; the checkpoint hash covers the suffixes, so a checkpoint loads only into a batch of the same counts; run-time builds
- * of a batch with an absent user carry -DRS_JIT_CELL_CONFIGS=2 (any other batch's builds are what they were).  Still uniform: S, R,
- * algo_alpha / algo_beta. */
+ * of a batch with an absent user carry -DRS_JIT_CELL_CONFIGS=2 (any other batch's builds are what they were).
+ * Cells of different slice counts: rs_batch_set_cell_configs_n below.  Still uniform: R, algo_alpha / algo_beta. */
 #define RS_USER_ABSENT (-1)
 int rs_batch_set_cell_configs(rs_batch* b,
         const double*  slice_weight  /* [n_cells][S] or NULL */,
@@ -847,6 +848,26 @@ int rs_batch_get_cell_config(rs_batch* b, int32_t cell, double* slice_weight /* 
 int rs_batch_slice_totals(rs_batch* b, int64_t* cum_bytes /* [n_cells][S] or NULL */, int64_t* cum_rbs /* [n_cells][S] or NULL */);
 /* every cell's user count n_c: the entries of its row before the RS_USER_ABSENT suffix; U for every cell of a batch without rows */
 int rs_batch_cell_users(rs_batch* b, int32_t* n_users /* [n_cells] */);
+/* rs_batch_set_cell_configs with a slice count per cell: 1 <= cell_slices[c] <= S (the batch's n_slices); cell_slices == NULL: exactly
+ * rs_batch_set_cell_configs.  The reference's run scripts sweep the slice count too (5, 10, 15 and 20 slices as separate processes), and a
+ * smaller count cannot be had by padding with empty zero-weight slices: both quota rotations are (i + rand()) % num_slices_ and
+ * MaximizeCell's std::sort runs over nb_rbgs * nb_slices records, whose order among equal keys depends on the length.
+ * Cell c behaves, to the bit, like cell 0 of a one-cell batch created with n_slices = S_c (and n_users = n_c) from the heads of its rows,
+ * in everything the batch returns about slices 0 .. S_c - 1 and users 0 .. n_c - 1: logged rows, grant records, PF averages, counters,
+ * slice state, clock, rand() ring, heap-sort counters.  The absent slices s >= S_c take part in nothing: their quota, target and
+ * slice_keys log entries are 0; their slice_state words keep, bit for bit, what they held (rs_batch_write_state accepts and stores values
+ * for them outside its domain rule, the kernel never writes them); their entries in the three per-slice rows are stored, returned by
+ * rs_batch_get_cell_config as given, not validated and ignored; rs_batch_slice_totals returns 0 for them and rs_batch_slice_bytes adds
+ * nothing for them (no user is theirs).  RS_ERR_INVALID naming cell and index, nothing stored: a count outside 1..S, a user_to_slice id
+ * >= S_c in front of the absent-user suffix, and everything rs_batch_set_cell_configs checks, applied to the heads.  A row may combine
+ * fewer slices with an absent-user suffix, or have fewer slices with all U users.  Refusals as for rs_batch_set_cell_configs; a later
+ * call of either function replaces the earlier one.  rs_batch_grant_bound for RS_SCHED_UPPERBOUND sums over each cell's own slices; the
+ * checkpoint hash covers the counts where one is below S; run-time builds of a batch with such a cell carry RS_JIT_CELL_CONFIGS | 4
+ * (-DRS_JIT_CELL_CONFIGS=5 or 6; any other batch's builds, option lists and cache keys are what they were). */
+int rs_batch_set_cell_configs_n(rs_batch* b, const int32_t* cell_slices /* [n_cells] or NULL */,
+        const double* slice_weight, const int32_t* algo_epsilon, const int32_t* algo_psi, const int32_t* user_to_slice);
+/* every cell's slice count S_c; S for every cell of a batch without counts */
+int rs_batch_cell_slices(rs_batch* b, int32_t* n_slices /* [n_cells] */);
 
 /* CQI source A: explicit grids. h_cqi = [n_cells][n_epochs][U][R] (host); epoch e serves scheduled
  * TTIs [e*cqi_refresh, (e+1)*cqi_refresh).  Copied to HBM once. */
@@ -1122,6 +1143,8 @@ int rs_jit_selfcheck_grant_records(int n_slices, int n_users, int n_rbgs, int rb
 int rs_jit_selfcheck_cell_configs(int n_slices, int n_users, int n_rbgs, int rbg_size, int threads, int sched, int lean, char* err, size_t errlen);
 /* the same with rows that end in absent users (what a ragged batch compiles: -DRS_JIT_CELL_CONFIGS=2) */
 int rs_jit_selfcheck_ragged_cells(int n_slices, int n_users, int n_rbgs, int rbg_size, int threads, int sched, int lean, char* err, size_t errlen);
+/* the same for a batch with a cell of fewer slices than n_slices, absent users included (-DRS_JIT_CELL_CONFIGS=6) */
+int rs_jit_selfcheck_ragged_slices(int n_slices, int n_users, int n_rbgs, int rbg_size, int threads, int sched, int lean, char* err, size_t errlen);
 /* ---- the run-time compiled kernels' cache on disk (ABI 10) ----
  * Every code object hiprtc produces (rs_batch_create with jit = 1, the lean / streamed variants, rs_ctx_specialize) is kept in
  * $RS_JIT_CACHE_DIR (default $XDG_CACHE_HOME/radiosaber_amd, else ~/.cache/radiosaber_amd; created with mode 0700), one file per (device

@@ -193,6 +193,8 @@ PROTOTYPES = {
     "rs_batch_get_cell_config": (_int, [_ptr, _i32, _P(_f64), _P(_i32), _P(_i32), _P(_i32)]),
     "rs_batch_slice_totals": (_int, [_ptr, _P(_i64), _P(_i64)]),
     "rs_batch_cell_users": (_int, [_ptr, _P(_i32)]),
+    "rs_batch_set_cell_configs_n": (_int, [_ptr, _P(_i32), _P(_f64), _P(_i32), _P(_i32), _P(_i32)]),
+    "rs_batch_cell_slices": (_int, [_ptr, _P(_i32)]),
     "rs_batch_upload_cqi_epochs": (_int, [_ptr, _P(_u8), _i32]),
     "rs_batch_upload_cqi_epochs_prb": (_int, [_ptr, _P(_u8), _i32]),
     "rs_batch_synthesize_cqi": (_int, [_ptr, C.c_uint64, _P(_f64), _i32]),
@@ -238,6 +240,7 @@ PROTOTYPES = {
     "rs_jit_selfcheck_grant_records": (_int, _SHAPE + [_int] + _MSG),
     "rs_jit_selfcheck_cell_configs": (_int, _SHAPE + [_int] + _MSG),
     "rs_jit_selfcheck_ragged_cells": (_int, _SHAPE + [_int] + _MSG),
+    "rs_jit_selfcheck_ragged_slices": (_int, _SHAPE + [_int] + _MSG),
     "rs_jit_cache_stats": (None, [_P(C.c_longlong)]),
     "rs_jit_compiler_identity": (_str, []),
     "rs_jit_cache_file": (_int, _SHAPE + [_int] + _MSG),
@@ -352,12 +355,14 @@ def jit_selfcheck_grant_records(n_slices, n_users, n_rbgs, rbg_size, threads=512
     return n
 
 
-def jit_selfcheck_cell_configs(n_slices, n_users, n_rbgs, rbg_size, threads=512, sched=RS_SCHED_MAXCELL, lean=False, ragged=False):
+def jit_selfcheck_cell_configs(n_slices, n_users, n_rbgs, rbg_size, threads=512, sched=RS_SCHED_MAXCELL, lean=False, ragged=False,
+                               ragged_slices=False):
     """Compile the batch kernel of one shape with per-cell configuration rows (what set_cell_configs builds for a batch with jit=True;
     hiprtc, no GPU needed): the general build, or with lean=True the lean one; ragged=True: the build of a batch whose cells have
-    different user counts (rows that end in RS_USER_ABSENT); returns the code size.  Scheduler 11 has none: RadioSaberError."""
+    different user counts (rows that end in RS_USER_ABSENT); ragged_slices=True: of a batch with a cell of fewer slices than n_slices
+    (absent users included); returns the code size.  Scheduler 11 has none: RadioSaberError."""
     buf = C.create_string_buffer(4096)
-    fn = lib().rs_jit_selfcheck_ragged_cells if ragged else lib().rs_jit_selfcheck_cell_configs
+    fn = lib().rs_jit_selfcheck_ragged_slices if ragged_slices else lib().rs_jit_selfcheck_ragged_cells if ragged else lib().rs_jit_selfcheck_cell_configs
     n = fn(n_slices, n_users, n_rbgs, rbg_size, threads, sched, 1 if lean else 0, buf, 4096)
     if n < 0:
         raise RadioSaberError(n, buf.value.decode(errors="replace"))
@@ -1146,24 +1151,34 @@ class BatchScheduler:
         _check(lib().rs_batch_seed(self._h, _p(s, C.c_uint32), _p(k, C.c_int64)))
 
     def set_cell_configs(self, configs: Sequence[SliceConfig]):
-        """One SliceConfig per cell, all of the batch's n_slices and of at most its n_users: cell c takes configs[c]'s weights,
-        algo_epsilon, algo_psi and slice sizes and then runs, to the bit, like a one-cell batch created from configs[c]
-        (rs_batch_set_cell_configs).  A configuration of fewer users than the batch's makes a cell of that many: its map is padded
+        """One SliceConfig per cell, of at most the batch's n_slices and n_users: cell c takes configs[c]'s weights, algo_epsilon,
+        algo_psi and slice sizes and then runs, to the bit, like a one-cell batch created from configs[c]
+        (rs_batch_set_cell_configs_n).  A configuration of fewer users than the batch's makes a cell of that many: its map is padded
         with RS_USER_ABSENT, the users behind it are never served and their state words never touched (cell_users() returns the
-        counts; state() and run_logged() keep their [cells][U] shapes).  Before the first TTI; never with the queue model or
-        scheduler 11.  algo_alpha / algo_beta stay the batch's."""
+        counts; state() and run_logged() keep their [cells][U] shapes).  A configuration of fewer slices makes a cell of that many:
+        its weights are padded with 0 and its exponents with 1, the slices behind it take part in nothing and their slice_state words
+        are never touched (cell_slices() returns the counts; the [cells][S] shapes stay).  Before the first TTI; never with the
+        queue model or scheduler 11.  algo_alpha / algo_beta stay the batch's."""
         if len(configs) != self.n_cells:
             raise ValueError(f"{len(configs)} configurations for {self.n_cells} cells")
         for c, cfg in enumerate(configs):
-            if cfg.n_slices != self.S or not 1 <= cfg.n_users <= self.U:
+            if not 1 <= cfg.n_slices <= self.S or not 1 <= cfg.n_users <= self.U:
                 raise ValueError(f"configuration {c} has {cfg.n_slices} slices and {cfg.n_users} users, the batch {self.S} and {self.U}")
-            if list(cfg.algo_alpha) != list(self.slices.algo_alpha) or list(cfg.algo_beta) != list(self.slices.algo_beta):
+            k = cfg.n_slices
+            if list(cfg.algo_alpha) != list(self.slices.algo_alpha)[:k] or list(cfg.algo_beta) != list(self.slices.algo_beta)[:k]:
                 raise ValueError(f"configuration {c} has algo_alpha / algo_beta of its own: the two stay the batch's")
-        w = np.ascontiguousarray([cfg.weight for cfg in configs], np.float64)
-        e = np.ascontiguousarray([cfg.algo_epsilon for cfg in configs], np.int32)
-        p = np.ascontiguousarray([cfg.algo_psi for cfg in configs], np.int32)
+        pad = lambda v, fill: list(v) + [fill] * (self.S - len(v))
+        n = np.ascontiguousarray([cfg.n_slices for cfg in configs], np.int32)
+        w = np.ascontiguousarray([pad(cfg.weight, 0.0) for cfg in configs], np.float64)
+        e = np.ascontiguousarray([pad(cfg.algo_epsilon, 1) for cfg in configs], np.int32)
+        p = np.ascontiguousarray([pad(cfg.algo_psi, 1) for cfg in configs], np.int32)
         m = self.padded_maps(configs, self.U)
-        _check(lib().rs_batch_set_cell_configs(self._h, _p(w, C.c_double), _p(e, C.c_int32), _p(p, C.c_int32), _p(m, C.c_int32)))
+        # (a batch whose configurations all have its n_slices makes the call it always made)
+        if (n == self.S).all():
+            _check(lib().rs_batch_set_cell_configs(self._h, _p(w, C.c_double), _p(e, C.c_int32), _p(p, C.c_int32), _p(m, C.c_int32)))
+        else:
+            _check(lib().rs_batch_set_cell_configs_n(self._h, _p(n, C.c_int32), _p(w, C.c_double), _p(e, C.c_int32), _p(p, C.c_int32),
+                                                     _p(m, C.c_int32)))
 
     @staticmethod
     def padded_maps(configs, n_users):
@@ -1178,6 +1193,13 @@ class BatchScheduler:
         gave a configuration of fewer users."""
         n = np.zeros(self.n_cells, np.int32)
         _check(lib().rs_batch_cell_users(self._h, _p(n, C.c_int32)))
+        return n
+
+    def cell_slices(self):
+        """int32 [n_cells]: every cell's slice count (rs_batch_cell_slices) -- the batch's n_slices but for the cells that
+        set_cell_configs gave a configuration of fewer slices."""
+        n = np.zeros(self.n_cells, np.int32)
+        _check(lib().rs_batch_cell_slices(self._h, _p(n, C.c_int32)))
         return n
 
     def cell_config(self, cell):

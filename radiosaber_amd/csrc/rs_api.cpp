@@ -353,6 +353,8 @@ struct rs_batch {
   std::vector<double> cc_weight;               /* [cells][S] */
   std::vector<int32_t> cc_eps, cc_psi, cc_u2s; /* [cells][S], [cells][S], [cells][U] */
   std::vector<int32_t> cc_users;               /* [cells]: the row's users before the absent suffix (U where there is none) */
+  bool ragged_slices = false;                  /* some cell has fewer slices than the batch (rs_batch_set_cell_configs_n) */
+  std::vector<int32_t> cc_slices;              /* [cells]: the cell's slice count S_c (S where none was given) */
   double* d_cc_weight = nullptr;
   int32_t *d_cc_eps = nullptr, *d_cc_psi = nullptr;
   uint8_t* d_cc_user_slice = nullptr;
@@ -419,9 +421,12 @@ int slice_window(const rs_batch* b) {
 }
 /* the -D options a batch's run-time builds carry beside the rule table's (rs_jit_get's `variant`): the per-cell reads of the load phase
  * are a compile-time switch, named only by a batch that has per-cell rows -- every other batch's option lists are what they were */
+/* (RsLaunch::cell_cfg as a build option: 1 rows, 2 rows with absent users, | 4 some cell of fewer slices than the batch) */
+int cell_cfg_word(bool absent_users, bool fewer_slices) { return (absent_users ? RS_CELL_CFG_RAGGED : 1) | (fewer_slices ? RS_CELL_CFG_SLICES : 0); }
+std::string cell_cfg_option(bool absent_users, bool fewer_slices) { return "-DRS_JIT_CELL_CONFIGS=" + std::to_string(cell_cfg_word(absent_users, fewer_slices)); }
 std::string jit_variant(const rs_batch* b, const char* more = nullptr) {
   std::string v = more ? more : "";
-  if (b->cell_cfg) v += std::string(v.empty() ? "" : " ") + (b->ragged ? "-DRS_JIT_CELL_CONFIGS=2" : "-DRS_JIT_CELL_CONFIGS=1");
+  if (b->cell_cfg) v += std::string(v.empty() ? "" : " ") + cell_cfg_option(b->ragged, b->ragged_slices);
   return v;
 }
 /* (nullptr for the empty list: rs_jit_get's key names a variant only where there is one) */
@@ -1379,8 +1384,12 @@ int rs_batch_seed(rs_batch* b, const uint32_t* seed, const int64_t* rand_skip) {
 }
 
 /* ---- per-cell configurations ---- */
-static int check_slice_state(const rs_batch* b, const double* v, size_t cell, const double* weight = nullptr); /* (the domain rule, stated at its definition below) */
+static int check_slice_state(const rs_batch* b, const double* v, size_t cell, const double* weight = nullptr, int n_slices = -1); /* (the domain rule, stated at its definition below) */
 int rs_batch_set_cell_configs(rs_batch* b, const double* slice_weight, const int32_t* algo_epsilon, const int32_t* algo_psi, const int32_t* user_to_slice) {
+  return rs_batch_set_cell_configs_n(b, nullptr, slice_weight, algo_epsilon, algo_psi, user_to_slice);
+}
+int rs_batch_set_cell_configs_n(rs_batch* b, const int32_t* cell_slices, const double* slice_weight, const int32_t* algo_epsilon, const int32_t* algo_psi,
+                                const int32_t* user_to_slice) {
   if (!b) return fail(RS_ERR_INVALID, "null batch");
   if (b->direct) return fail(RS_ERR_INVALID, "per-cell configurations: not a batch");
   if (b->sched == RS_SCHED_NVS_NONGREEDY) return fail(RS_ERR_INVALID, "per-cell configurations: scheduler %d runs on another kernel, which reads one configuration", b->sched);
@@ -1389,8 +1398,16 @@ int rs_batch_set_cell_configs(rs_batch* b, const double* slice_weight, const int
   const size_t cells = (size_t)b->n_cells, S = (size_t)b->S, U = (size_t)b->U;
   /* a NULL array: every cell keeps the shared configuration's values for that field */
   std::vector<double> w(cells * S);
-  std::vector<int32_t> e(cells * S), ps(cells * S), us(cells * U), nu(cells);
-  bool any_absent = false;
+  std::vector<int32_t> e(cells * S), ps(cells * S), us(cells * U), nu(cells), ns(cells, (int32_t)S);
+  bool any_absent = false, any_fewer = false;
+  /* a cell's slice count S_c: its rows' first S_c entries are its slices, the entries behind them belong to absent slices -- stored,
+   * returned as given, not validated, ignored */
+  for (size_t c = 0; c < cells && cell_slices; c++) {
+    if (cell_slices[c] < 1 || cell_slices[c] > b->S)
+      return fail(RS_ERR_INVALID, "cell %zu: cell_slices[%zu] = %d outside 1..%d (the batch's n_slices)", c, c, cell_slices[c], b->S);
+    ns[c] = cell_slices[c];
+    any_fewer |= ns[c] != b->S;
+  }
   for (size_t c = 0; c < cells; c++) {
     for (size_t k = 0; k < S; k++) {
       w[c * S + k] = slice_weight ? slice_weight[c * S + k] : b->weight[k];
@@ -1401,7 +1418,7 @@ int rs_batch_set_cell_configs(rs_batch* b, const double* slice_weight, const int
   }
   /* every row as validate() takes a configuration */
   for (size_t c = 0; c < cells; c++) {
-    for (size_t k = 0; k < S; k++) {
+    for (size_t k = 0; k < (size_t)ns[c]; k++) {
       if (!std::isfinite(w[c * S + k])) return fail(RS_ERR_INVALID, "cell %zu: slice_weight[%zu] = %g is not finite", c, k, w[c * S + k]);
       if ((e[c * S + k] | 1) != 1 || (ps[c * S + k] | 1) != 1)
         return fail(RS_ERR_INVALID, "cell %zu, slice %zu: algo_epsilon %d / algo_psi %d must be 0 or 1 in a batch", c, k, e[c * S + k], ps[c * S + k]);
@@ -1415,6 +1432,7 @@ int rs_batch_set_cell_configs(rs_batch* b, const double* slice_weight, const int
         continue;
       }
       if (sl < 0 || sl >= b->S) return fail(RS_ERR_INVALID, "cell %zu, user %zu: slice %d out of range", c, u, sl);
+      if (sl >= ns[c]) return fail(RS_ERR_INVALID, "cell %zu, user %zu: slice %d is absent -- the cell has %d slices (cell_slices[%zu])", c, u, sl, ns[c], c);
       if (n != u) return fail(RS_ERR_INVALID, "cell %zu, user %zu: slice %d behind RS_USER_ABSENT (user %zu) -- the absent users are a suffix of the row", c, u, sl, n);
       if (u && sl < us[c * U + u - 1]) return fail(RS_ERR_INVALID, "cell %zu: user_to_slice must be non-decreasing (user %zu)", c, u);
       n = u + 1;
@@ -1428,7 +1446,7 @@ int rs_batch_set_cell_configs(rs_batch* b, const double* slice_weight, const int
     std::vector<double> st(cells * S);
     HIP_TRY(hipMemcpy(st.data(), b->d_sstate, 8 * cells * S, hipMemcpyDeviceToHost));
     for (size_t c = 0; c < cells; c++)
-      if (const int rc = check_slice_state(b, st.data() + c * S, c, w.data() + c * S)) return rc;
+      if (const int rc = check_slice_state(b, st.data() + c * S, c, w.data() + c * S, ns[c])) return rc;
   }
   /* one kernel serves all cells: LDS carve and run-time builds for the longest slice window of any cell -- validated and built BEFORE
    * the batch changes, so that a refusal leaves it as it was */
@@ -1440,7 +1458,7 @@ int rs_batch_set_cell_configs(rs_batch* b, const double* slice_weight, const int
   char cmsg[sizeof b->jit_msg] = {0};
   if (b->jit_wanted) {
     cjit = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, 0, win, cmsg, sizeof cmsg, b->cfg.cqi_refresh <= 4 ? 2 : 0,
-                      any_absent ? "-DRS_JIT_CELL_CONFIGS=2" : "-DRS_JIT_CELL_CONFIGS=1");
+                      cell_cfg_option(any_absent, any_fewer).c_str());
     if (cjit) snprintf(cmsg, sizeof cmsg, "%s", rs_jit_is_untuned(cjit) ? "in use, built WITHOUT the -mllvm tuning options (hiprtc refused them): a few per cent slower" : "");
     else if (!cmsg[0]) snprintf(cmsg, sizeof cmsg, "hiprtc build of the kernel with per-cell configurations failed");
     if (!cjit && b->threads > 512) return fail(RS_ERR_INVALID, "threads_per_cell %d needs the shape-specialised kernel with per-cell configurations: %s", b->threads, cmsg);
@@ -1454,15 +1472,21 @@ int rs_batch_set_cell_configs(rs_batch* b, const double* slice_weight, const int
   std::vector<uint8_t> us8(cells * U);
   for (size_t i = 0; i < cells * U; i++) us8[i] = us[i] == RS_USER_ABSENT ? (uint8_t)RS_SLICE_ABSENT : (uint8_t)us[i];
   HIP_TRY(hipMemcpy(b->d_cc_weight, w.data(), 8 * cells * S, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(b->d_cc_eps, e.data(), 4 * cells * S, hipMemcpyHostToDevice));
+  { /* the device row of eps carries the cell's slice count: RS_EPS_ABSENT from slice S_c on (the host row keeps what was given) */
+    std::vector<int32_t> ed(e);
+    for (size_t c = 0; c < cells; c++)
+      for (size_t k = (size_t)ns[c]; k < S; k++) ed[c * S + k] = RS_EPS_ABSENT;
+    HIP_TRY(hipMemcpy(b->d_cc_eps, ed.data(), 4 * cells * S, hipMemcpyHostToDevice));
+  }
   HIP_TRY(hipMemcpy(b->d_cc_psi, ps.data(), 4 * cells * S, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(b->d_cc_user_slice, us8.data(), cells * U, hipMemcpyHostToDevice));
   /* commit: rows, launch block, carve and kernels together */
-  b->cc_weight.swap(w); b->cc_eps.swap(e); b->cc_psi.swap(ps); b->cc_u2s.swap(us); b->cc_users.swap(nu);
+  b->cc_weight.swap(w); b->cc_eps.swap(e); b->cc_psi.swap(ps); b->cc_u2s.swap(us); b->cc_users.swap(nu); b->cc_slices.swap(ns);
   b->cell_cfg = true;
   b->ragged = any_absent;
+  b->ragged_slices = any_fewer;
   b->base.weight = b->d_cc_weight; b->base.eps = b->d_cc_eps; b->base.psi = b->d_cc_psi; b->base.user_slice = b->d_cc_user_slice;
-  b->base.cell_cfg = any_absent ? RS_CELL_CFG_RAGGED : 1;
+  b->base.cell_cfg = cell_cfg_word(any_absent, any_fewer);
   carve_lds(b, &b->base);
   if (b->jit_wanted) {
     /* the builds belong to the rows' window and to the switch: the lean build, the records variants, the self-check and the autotune
@@ -1494,6 +1518,13 @@ int rs_batch_cell_users(rs_batch* b, int32_t* n_users) {
   if (!b || !n_users) return fail(RS_ERR_INVALID, "null argument");
   if (b->direct) return fail(RS_ERR_INVALID, "cell users: not a batch");
   for (int c = 0; c < b->n_cells; c++) n_users[c] = b->cell_cfg ? b->cc_users[c] : b->U;
+  return RS_OK;
+}
+
+int rs_batch_cell_slices(rs_batch* b, int32_t* n_slices) {
+  if (!b || !n_slices) return fail(RS_ERR_INVALID, "null argument");
+  if (b->direct) return fail(RS_ERR_INVALID, "cell slices: not a batch");
+  for (int c = 0; c < b->n_cells; c++) n_slices[c] = b->cell_cfg ? b->cc_slices[c] : b->S;
   return RS_OK;
 }
 
@@ -1935,9 +1966,10 @@ int rs_batch_read_state(rs_batch* b, double* avg, int64_t* cum_bytes, int64_t* c
  *     division below 2^25 + 2, wrong at 2^25 + 2) a factor of a thousand inside that bound.
  *   schedulers 7 and 11: EWMAs are >= 0.  The reference's scan ('>=' from 0, :127-131) never picks a negative score and the
  *     kernel's integer-pair maximum orders negative doubles the other way round. */
-static int check_slice_state(const rs_batch* b, const double* v, size_t cell, const double* weight) {
+static int check_slice_state(const rs_batch* b, const double* v, size_t cell, const double* weight, int n_slices) {
   if (!weight) weight = b->cell_cfg ? b->cc_weight.data() + cell * (size_t)b->S : b->weight.data(); /* (per-cell rows: the cell's own weights) */
-  const int S = b->S;
+  /* (a cell of fewer slices than the batch: the rule covers its own slices; an absent slice's word is stored as given and never read) */
+  const int S = n_slices > 0 ? n_slices : (b->cell_cfg && !b->cc_slices.empty()) ? b->cc_slices[cell] : b->S;
   const bool transport = b->sched == RS_SCHED_SEQUENTIAL || b->sched == RS_SCHED_MAXCELL || b->sched == RS_SCHED_SUBOPT ||
                          b->sched == RS_SCHED_VOGEL || b->sched == RS_SCHED_UPPERBOUND;
   const bool nvs = b->sched == RS_SCHED_NVS || b->sched == RS_SCHED_NVS_NONGREEDY;
@@ -2229,6 +2261,7 @@ uint64_t ckpt_config_hash(const rs_batch* b) {
     mix(b->cc_weight.data(), 8 * b->cc_weight.size());
     mix(b->cc_eps.data(), 4 * b->cc_eps.size());
     mix(b->cc_psi.data(), 4 * b->cc_psi.size());
+    if (b->ragged_slices) mix(b->cc_slices.data(), 4 * b->cc_slices.size()); /* (named only where a cell has fewer slices: other batches' hashes stay) */
   }
   return h;
 }

@@ -32,6 +32,8 @@ typedef unsigned long size_t;
 #define RS_MAX_BYTES_PER_TTI 65535
 #define RS_CELL_CFG_RAGGED 2   /* RsLaunch::cell_cfg / RS_JIT_CELL_CONFIGS: per-cell rows with absent users behind a cell's last one */
 #define RS_SLICE_ABSENT 0xFF   /* the device map's byte of an absent user (RS_USER_ABSENT; slice ids stop at 63) */
+#define RS_CELL_CFG_SLICES 4   /* ... a bit on top of 1 or 2: some cell has fewer slices than the batch (an absent-slice suffix in its rows) */
+#define RS_EPS_ABSENT (-1)     /* the device eps row's word of an absent slice (algo_epsilon is 0 or 1 in a batch): marks the cell's slice count */
 #define RS_PF_SEG 32 /* sched 1: users are scanned in segments of this many for the per-RBG argmax */
 
 /* per-cell scratch in LDS (host needs its size for the LDS carve) */
@@ -271,7 +273,8 @@ struct RsLaunch {
   /* batches, rs_batch_set_cell_configs: 1 -- weight, eps, psi and user_slice above hold one row per cell and the cell's load phase reads
    * its own (the per-TTI path reads none of the four).  In the padding behind queue_mode: no word of the block moves.  The built-in
    * kernels test it at run time; a run-time build has it as a constant (RS_JIT_CELL_CONFIGS).  RS_CELL_CFG_RAGGED (2): rows, and some
-   * row of user_slice ends in absent users (RS_SLICE_ABSENT bytes): the cell's load phase finds its own user count */
+   * row of user_slice ends in absent users (RS_SLICE_ABSENT bytes): the cell's load phase finds its own user count.  | RS_CELL_CFG_SLICES
+   * (4): some cell has fewer slices than the batch -- its row of eps ends in RS_EPS_ABSENT words and the load phase finds its slice count */
   int32_t cell_cfg;
   const int32_t* alpha;      /* [S] */
   const int32_t* beta;       /* [S] */

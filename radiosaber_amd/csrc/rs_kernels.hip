@@ -217,7 +217,26 @@ __device__ __forceinline__ void rs_cell_body(const RsLaunch& p, unsigned char* l
    * of.  An absent user's stage-1 reciprocal is never written and stays the zero of the load phase: to the scans it is one more slot
    * outside the window.  The row is present users, then absent ones (the host checks it), so Un is found by bisection -- wave-uniform
    * loads, once per launch.  Any other build or launch: Un is U, folded. */
-  const bool ragged = cell_cfg && (FIXED ? RS_JIT_CELL_CONFIGS == RS_CELL_CFG_RAGGED : p.cell_cfg == RS_CELL_CFG_RAGGED);
+  const bool ragged = cell_cfg && (FIXED ? (RS_JIT_CELL_CONFIGS & 3) == RS_CELL_CFG_RAGGED : (p.cell_cfg & 3) == RS_CELL_CFG_RAGGED);
+  /* Cells of different slice counts (cell_cfg & RS_CELL_CFG_SLICES): a cell's rows may end in absent slices, and the cell then runs as
+   * one of Sn = S_c slices.  Sn is a bound, a modulus and a length: the two quota rotations, the (RBG, slice) records' index r * Sn + s
+   * and the sort's length R * Sn, the item lists (slice-major: an absent slice's items are a suffix nobody lists), the inter-slice
+   * policies, the slice offsets and the state flush; S stays what the carve, the LDS offsets and every stride in HBM are made of.  No
+   * user maps to an absent slice (the host checks it), so to the load phase it is one more empty slice.  The device row of eps marks
+   * the absent suffix with RS_EPS_ABSENT; Sn is bisected like Un.  Any other build or launch: Sn is S, folded. */
+  constexpr bool kRaggedS = FIXED && !DIRECT && !QUEUE && (RS_JIT_CELL_CONFIGS & RS_CELL_CFG_SLICES) != 0;
+  const bool ragged_s = cell_cfg && (FIXED ? kRaggedS : (p.cell_cfg & RS_CELL_CFG_SLICES) != 0);
+  int sn_ = S;
+  if (ragged_s) {
+    int lo = 0; /* (slice 0 is present) */
+    while (sn_ - lo > 1) {
+      const int mid = (lo + sn_) >> 1;
+      if (cfg_eps[mid] == RS_EPS_ABSENT) sn_ = mid; else lo = mid;
+    }
+  }
+  /* (a constant expression wherever S is one and the build is not this variant: the phases' lambdas then name it as they name S) */
+  constexpr bool kSnIsS = FIXED && !kRaggedS;
+  const int Sn = kSnIsS ? S : sn_;
   int un_ = U;
   if (ragged) {
     int lo = 0; /* (user 0 is present) */
@@ -663,7 +682,7 @@ __device__ __forceinline__ void rs_cell_body(const RsLaunch& p, unsigned char* l
     const bool ewma_next = quota_next && (SCHED == 8 || (SCHED == 9 && FIXED && RS_JIT_U > RS_JIT_NT));
     /* ... and pack their lists for TTI t+1 (a one-chunk shape: at most 64 items per wave).  Packing them for MaximizeCell too,
      * without the early EWMA, was measured in round 4: 33.34 against 33.38 M TTIs/s -- the top of its TTI does not wait for it. */
-    const bool prelist_next = kHoldSched && ewma_next && hold_ok && n_items_rt <= 64 * nwaves;
+    const bool prelist_next = kHoldSched && ewma_next && hold_ok && n_items_n <= 64 * nwaves;
     /* schedulers 1 / 7: the other waves prepare TTI t+1 beside wave 0 (see kEarly17); not past the end of the launch */
     const bool early17 = kEarly17 && nwaves >= 2 && tti + 1 < p.n_ttis;
     bool early_scan_ok = false; /* NVS: TTI t+1 reads the CQI grid that is in LDS now */
@@ -767,7 +786,7 @@ __device__ __forceinline__ void rs_cell_body(const RsLaunch& p, unsigned char* l
     p.avg[(size_t)cell * U + u] = ((kSpecSched || kHoldSched) && s_avg[u] < 1) ? 1.0 : s_avg[u];
     p.tx_bytes[(size_t)cell * U + u] = s_tx[u];
   }
-  if (tid < S) p.slice_state[(size_t)cell * S + tid] = s_sstate[tid];
+  if (tid < Sn) p.slice_state[(size_t)cell * S + tid] = s_sstate[tid]; /* (an absent slice's word keeps what it held) */
   if (!kDirect && wave == quota_wave && lane < 31) scal->rng_r[lane] = rng.r;
   if (tid == 0) {
     if (!DIRECT) {

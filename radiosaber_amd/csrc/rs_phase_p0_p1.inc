@@ -79,6 +79,8 @@
     }
     /* which buffers this TTI's winners and records live in (see kSpecSched) */
     const int n_items_rt = o.n_items;
+    /* (a cell of fewer slices than the batch: the items are slice-major, the absent slices' are a suffix that is never listed or scanned) */
+    const int n_items_n = (ragged_s && kTransport) ? Sn * R : n_items_rt;
     uint16_t* const cur_bu = s_best_user + ((kSpecSched && (tti & 1)) ? n_items_rt : 0);
     uint16_t* const nxt_bu = s_best_user + ((kSpecSched && !(tti & 1)) ? n_items_rt : 0);
     /* held winners: pack the items of chunk k0 that this wave has to scan again into its list (item = k * nwaves + wave: the
@@ -86,7 +88,7 @@
     uint16_t* const hold_wl = hold_list + wave * 64;
     auto hold_pack = [&](int k0, int for_wave) -> int { /* for_wave: whose items (wave 1 also packs wave 0's in the serial phase) */
       const int it_l = (k0 + lane) * nwaves + for_wave;
-      const bool in = it_l < n_items_rt;
+      const bool in = it_l < n_items_n;
       const int w = in ? (int)cur_bu[it_l] : 0xFFFF;
       const bool held_bit = ((hold_bits[(k0 >> 6) * nwaves + for_wave] >> lane) & 1ull) != 0ull;
       const int sg_l = FIXED ? it_l / RS_JIT_R : idiv_small(in ? it_l : 0, R);

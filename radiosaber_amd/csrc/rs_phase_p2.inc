@@ -8,7 +8,7 @@
     bool q_first0 = false, q_first1 = false; /* my slice receives the remainder of the PRBs / of the RBGs */
     auto quota_draws = [&](int served_before) {
       /* ref: :463-521 */
-      const bool in = lane < S;
+      const bool in = lane < Sn;
       q_has = in && (QUEUE ? q_slice_act[lane] != 0 : (m->seg_begin[lane + 1] > m->seg_begin[lane]));
       q_nonempty = __popcll(__ballot(q_has));
       if (QUEUE && lane == 0) *q_any = q_nonempty;
@@ -19,19 +19,19 @@
         r0 = rng.next();
         r1 = rng.next();
       }
-      /* first non-empty slice in the rotation k = (i + rand) % S, i = 0..S-1 */
-      const int r0m = (int)((unsigned)r0 % (unsigned)S), r1m = (int)((unsigned)r1 % (unsigned)S);
+      /* first non-empty slice in the rotation k = (i + rand) % S, i = 0..S-1 (num_slices_ is the cell's own count: Sn) */
+      const int r0m = (int)((unsigned)r0 % (unsigned)Sn), r1m = (int)((unsigned)r1 % (unsigned)Sn);
       int pos0 = lane - r0m;
-      pos0 = pos0 < 0 ? pos0 + S : pos0;
+      pos0 = pos0 < 0 ? pos0 + Sn : pos0;
       pos0 = q_has ? pos0 : 1 << 20;
       q_first0 = pos0 == wave_min(pos0);
       int pos1 = lane - r1m;
-      pos1 = pos1 < 0 ? pos1 + S : pos1;
+      pos1 = pos1 < 0 ? pos1 + Sn : pos1;
       pos1 = q_has ? pos1 : 1 << 20;
       q_first1 = pos1 == wave_min(pos1);
     };
     auto quota_targets = [&]() {
-      const bool in = lane < S;
+      const bool in = lane < Sn;
       int target = 0;
       if (q_has) target = (int)(nb_rbs * s_w[lane] + s_sstate[lane]);
       int extra = nb_rbs - wave_sum(target);
@@ -62,7 +62,7 @@
         if (kDirect) {
           pick = 0; /* the caller passes only the served slice's users */
         } else {
-          const bool in = lane < S;
+          const bool in = lane < Sn;
           /* slices with queued data (ref: :101-121; with queues: a bearer with packets and dataToTransmit > 0) */
           const bool has = in && (QUEUE ? q_slice_act[lane] != 0 : (m->seg_begin[lane + 1] > m->seg_begin[lane]));
           double ew = in ? s_sstate[lane] : 1.0;

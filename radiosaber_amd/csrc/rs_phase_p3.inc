@@ -11,7 +11,7 @@
       nvs_first = nvs_lo & ~7;
       nvs_runs = idiv_small(nvs_hi - nvs_first + nvs_seg - 1, nvs_seg);
     }
-    const int n_items = nvs_split ? R * nvs_runs : o.n_items;
+    const int n_items = nvs_split ? R * nvs_runs : n_items_n;
     /* one work item = (segment, RBG): winner to bu_out[it], its record (transport schedulers) to rec_out */
     auto scan_item = [&](int it, uint16_t* bu_out, uint32_t* rec_out, auto blk_tag) -> bool {
       bool held = false;
@@ -216,7 +216,7 @@
           rec_out[sg * R + r] = ((uint32_t)bkey << 16) | ((uint32_t)r << 8) | (uint32_t)sg;
         } else if (kTransport) {
           /* MaximizeCell's vector is RBG-major, slice-minor (:357-360) */
-          rec_out[r * S + sg] = ((uint32_t)bkey << 16) | ((uint32_t)r << 8) | (uint32_t)sg;
+          rec_out[r * Sn + sg] = ((uint32_t)bkey << 16) | ((uint32_t)r << 8) | (uint32_t)sg;
         } else if (SCHED == 1 || nvs_split) {
           s_best_metric[it] = best;
         }
@@ -425,7 +425,7 @@
               }
               cur_bu[it] = (uint16_t)ul;
               /* (MaximizeCell rebuilds its records from the winners right before the sort: the sort permutes them in place) */
-              if (SCHED != 9) cur_rec[r * S + sg] = ((uint32_t)key << 16) | ((uint32_t)r << 8) | (uint32_t)sg;
+              if (SCHED != 9) cur_rec[r * Sn + sg] = ((uint32_t)key << 16) | ((uint32_t)r << 8) | (uint32_t)sg;
               /* (item = k * nwaves + wave: bit k & 63 of this wave's word k >> 6; the quads of one wave write it side by side) */
               const int kk = FIXED ? it / (RS_JIT_NT / 64) : idiv_small(it, nwaves);
               unsigned long long* const word = &hold_bits[(kk >> 6) * nwaves + wave];
@@ -593,8 +593,10 @@
        * (0: no user) | (user + 1) << 8 -- flow_spectraleff / user_index of ref :545-567 */
       for (int i = tid; i < R * S; i += nt) {
         const int r = SCHED == 10 ? i % R : i / S, sg = SCHED == 10 ? i / R : i % S;
-        const int bu = cur_bu[sg * R + r];
-        const uint32_t key = kHoldSched ? (bu == 0xFFFF ? 0u : (uint32_t)s_cqi[r * Upad + bu]) : (cur_rec[i] >> 16);
+        /* (an absent slice has no item and no record: its entries are 0; the records of the others lie Sn to an RBG) */
+        const bool absent = ragged_s && sg >= Sn;
+        const int bu = absent ? 0xFFFF : (int)cur_bu[sg * R + r];
+        const uint32_t key = absent ? 0u : kHoldSched ? (bu == 0xFFFF ? 0u : (uint32_t)s_cqi[r * Upad + bu]) : (cur_rec[(SCHED == 10 || !ragged_s) ? i : r * Sn + sg] >> 16);
         p.log_keys[((size_t)cell * p.n_ttis + tti) * R * S + r * S + sg] = key | ((bu == 0xFFFF ? 0u : (uint32_t)bu + 1u) << 8);
       }
     }

@@ -1,7 +1,10 @@
 /* rs_phase_p4.inc -- fragment of rs_cell_body (rs_kernels.hip), included inside the function: P4 on all waves: MaximizeCell's std::sort emulation (rs_sort_device.h) and UpperBound (S segmented sorts + its own apply step). */
     /* ---------------- P4: inter-slice assignment ---------------- */
     if (SCHED == 9) {
-      const int N = R * S;
+      /* (a cell of fewer slices: the vector std::sort sees holds R * Sn records -- depth limit, pivots and the 16-element threshold are
+       * that length's; position slots behind it are empty, whole ones included: to the levels they are retired positions.  The ranks'
+       * and cuts' LDS offsets stay the carve's, made of R * S) */
+      const int N = R * Sn, Ncv = R * S;
       /* std::sort emulation (:361): introsort loop, then the final insertion sort */
       {
         uint16_t* sx = (uint16_t*)(lds + o.sortx);
@@ -17,7 +20,7 @@
             /* a TTI that scanned only the listed items: every thread rebuilds the records of the positions it owns in the sort
              * (the previous sort permuted the array in place) from the winners and the CQI grid */
             for (int x = tid; x < N; x += nt) {
-              const int r = FIXED ? x / RS_JIT_S : idiv_small(x, S), sg = x - r * S;
+              const int r = (FIXED && !kRaggedS) ? x / RS_JIT_S : idiv_small(x, Sn), sg = x - r * Sn;
               const int bu = cur_bu[sg * R + r];
               const uint32_t key = bu == 0xFFFF ? 0u : (uint32_t)s_cqi[r * Upad + bu];
               s_elems[x] = (key << 16) | ((uint32_t)r << 8) | (uint32_t)sg;
@@ -26,7 +29,7 @@
           }
         }
         if constexpr (EPT > 0) introsort_levels_reg<EPT, FIXED ? RS_JIT_NT : 0, kSegScan>(s_elems, N, s_sorted, (int32_t*)sx, m, sort_sub, 0,
-                                                                           rs_sort_ranks_bytes(N) ? (uint16_t*)(lds + o.sortx + rs_sort_cuts_bytes(N)) : m->hist);
+                                                                           rs_sort_ranks_bytes(Ncv) ? (uint16_t*)(lds + o.sortx + rs_sort_cuts_bytes(Ncv)) : m->hist);
         else introsort_loop_levels(s_elems, N, pa, pa + N, sx, sx + N, sx + 2 * N, sx + 3 * N, m);
       }
       RS_STAMP(3);
@@ -46,10 +49,10 @@
        * rank inside its segment.  Then one thread per taken (slice, k) entry: the first entry of a UE is its leader and
        * sums E[cqi] over the UE's entries in push order (the slice's sorted order, not RBG order). */
       static_assert(EPT > 0, "UpperBound uses the register form of the sort (R*S <= 4 * threads)");
-      const int N = R * S;
+      const int N = R * Sn, Ncv = R * S; /* (a cell of fewer slices: Sn sorts; the LDS offsets stay the carve's) */
       RS_SETPRIO(1);
       introsort_levels_reg<EPT, FIXED ? RS_JIT_NT : 0>(s_elems, N, s_sorted, (int32_t*)(lds + o.sortx), m, sort_sub, R,
-                                                       rs_sort_ranks_bytes(N) ? (uint16_t*)(lds + o.sortx + rs_sort_cuts_bytes(N)) : m->hist);
+                                                       rs_sort_ranks_bytes(Ncv) ? (uint16_t*)(lds + o.sortx + rs_sort_cuts_bytes(Ncv)) : m->hist);
       RS_SETPRIO(0);
       int32_t* low_owner = (int32_t*)m->hist; /* per RBG: (slice << 16 | UE) of the lowest slice holding it */
       if (R > 32) {
@@ -58,7 +61,7 @@
          * element (64 RBGs: 800 instructions per thread; the as-shipped grid's UpperBound 21.3 -> M TTIs/s, profiles/r05_notes.md) */
         uint32_t* const cnt = (uint32_t*)m->maskA + wave * 16; /* free behind the sort's workgroup levels (maskA | maskB: 16 waves) */
         const unsigned long long gt_lane = lane == 63 ? 0ull : (~0ull << (lane + 1));
-        for (int sl = wave; sl < S; sl += nwaves) {
+        for (int sl = wave; sl < Sn; sl += nwaves) {
           const int f = sl * R;
           const bool valid = lane < R;
           const uint32_t e = valid ? s_elems[f + lane] : 0u;
@@ -195,7 +198,7 @@
           if (p.log_uinfo) p.log_uinfo[row * U + u] = nprb | (fcqi << 16) | (mcs << 24);
         }
       }
-      if (tid < S) {
+      if (tid < Sn) {
         /* ref: :618-620 with slice_final_rbgs = size of the slice's list */
         int q = m->quota[tid];
         q = q < 0 ? 0 : (q > R ? R : q);

@@ -298,25 +298,27 @@
       } else if constexpr (SCHED == 8 || SCHED == 9 || SCHED == 101 || SCHED == 103) {
         /* DownlinkTransportScheduler's inter-slice policies (rs_interslice.h): lane r learns the slice of RBG r */
         int my_slice;
-        constexpr int kS = FIXED ? RS_JIT_S : 0, kR = FIXED ? RS_JIT_R : 0;
-        if constexpr (SCHED == 8) my_slice = interslice_greedy_by_row<kS, kR>(cur_rec, m, S, R, got);
-        else if constexpr (SCHED == 101) my_slice = interslice_subopt<kS, kR>(cur_rec, m, (uint8_t*)(lds + o.sortx), S, R, got);
-        else if constexpr (SCHED == 103) my_slice = interslice_vogel<kS, kR>(cur_rec, m, S, R, got);
+        /* (a build for cells of fewer slices: the slice count is the cell's run-time Sn, the mask widths stay the batch's) */
+        constexpr int kS = (FIXED && !kRaggedS) ? RS_JIT_S : 0, kR = FIXED ? RS_JIT_R : 0;
+        constexpr bool kK32 = (FIXED ? RS_JIT_S : 0) <= 32 && kR <= 32;
+        if constexpr (SCHED == 8) my_slice = interslice_greedy_by_row<kS, kR>(cur_rec, m, Sn, R, got);
+        else if constexpr (SCHED == 101) my_slice = interslice_subopt<kS, kR>(cur_rec, m, (uint8_t*)(lds + o.sortx), Sn, R, got);
+        else if constexpr (SCHED == 103) my_slice = interslice_vogel<kS, kR>(cur_rec, m, Sn, R, got);
         else {
 #ifdef RS_STAMPS
-#define RS_SCAN_ARGS s_sorted, m, S, R, got, stamp_acc
+#define RS_SCAN_ARGS s_sorted, m, Sn, R, got, stamp_acc
 #else
-#define RS_SCAN_ARGS s_sorted, m, S, R, got
+#define RS_SCAN_ARGS s_sorted, m, Sn, R, got
 #endif
           if constexpr (kSegScan) {
 #ifdef RS_STAMPS
-            my_slice = interslice_maximize_cell_segments<kS, kR, (kS <= 32 && kR <= 32)>(s_elems, s_sorted, m, S, R, got, stamp_acc);
+            my_slice = interslice_maximize_cell_segments<kS, kR, kK32>(s_elems, s_sorted, m, Sn, R, got, stamp_acc);
 #else
-            my_slice = interslice_maximize_cell_segments<kS, kR, (kS <= 32 && kR <= 32)>(s_elems, s_sorted, m, S, R, got);
+            my_slice = interslice_maximize_cell_segments<kS, kR, kK32>(s_elems, s_sorted, m, Sn, R, got);
 #endif
           } else if constexpr (kVecScan) {
             if constexpr (FIXED) {
-              my_slice = interslice_maximize_cell_vector<kS, kR, (kS <= 32 && kR <= 32)>(RS_SCAN_ARGS);
+              my_slice = interslice_maximize_cell_vector<kS, kR, kK32>(RS_SCAN_ARGS);
             } else {
               if (vec_scan && R <= 32 && S <= 32) my_slice = interslice_maximize_cell_vector<0, 0, true>(RS_SCAN_ARGS);
               else if (vec_scan) my_slice = interslice_maximize_cell_vector<0, 0, false>(RS_SCAN_ARGS);
@@ -329,7 +331,7 @@
         if (((kSpecSched && spec_next) || quota_next) && !p.phy_draws) {
           /* slice_rbs_offset_ is final as soon as the RBGs are dealt out (ref: :618-620): the quota wave can start TTI t+1's
            * targets while this wave still looks up the winners and adapts the links */
-          if (lane < S) s_sstate[lane] = (double)(my_target - got * G);
+          if (lane < Sn) s_sstate[lane] = (double)(my_target - got * G);
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
           if (lane == 0) atomicExch(&fl_cur->greedy_done, 1);
         }

@@ -45,7 +45,7 @@
       const unsigned long long lead_mask = __ballot(leader);
       served_prev = __popcll(lead_mask);
       /* ref: :618-620 slice_rbs_offset_ = target - final_rbgs*rbg_size */
-      if (kTransport && lane < S && !(QUEUE && *q_any == 0))
+      if (kTransport && lane < Sn && !(QUEUE && *q_any == 0))
         s_sstate[lane] = (double)(((kSpecSched || kHoldSched) ? my_target : m->target[lane]) - got * G);
       if (lane == 0) m->served = served_prev;
       if (kHoldSched) {

@@ -22,8 +22,9 @@ A backlogged configuration takes --records too: one 32-byte record per grant (ru
 
 Several runs in one launch: the reference's scripts start one process per (configuration file, seed) of a directory -- config-pf.json and
 config-mt.json times nine seeds -- and a batch runs them as cells of one launch (per-cell configurations).  Name the
-configuration files (--config a.json b.json: the same number of slices, any numbers of users -- exp-fix20slices' 5, 10, 15 and 20 UEs
-per slice go together; the batch is created at the largest and the smaller cells' maps end in absent users), the seeds (--seeds 0,1,2)
+configuration files (--config a.json b.json: any numbers of slices and of users -- exp-fix20slices' 5, 10, 15 and 20 UEs per slice go
+together, and so do exp-fixranues' 5, 10, 15 and 20 slices; the batch is created at the largest of each, the smaller cells' maps end
+in absent users and their rows in absent slices), the seeds (--seeds 0,1,2)
 and a --log template with {config} (the file's name without .json) and {seed}; --mapping takes the same two fields.  Every log is byte
 for byte the log of the single run of its (configuration, seed).  Backlogged configurations only; scheduler 11 runs one cell per process.
 
@@ -53,8 +54,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--sched", type=int, default=9, help="the reference's CLI scheduler number: 1, 7, 8, 9, 10, 11")
 ap.add_argument("--seed", type=int, default=0, help="index into the reference's nine common seeds")
 ap.add_argument("--duration", type=float, default=12.0, help="simulated seconds after the 0.1 s start-up")
-ap.add_argument("--config", required=True, nargs="+", help="slice configuration JSON of the experiment directory; several files of one number "
-                                                         "of slices (any numbers of users) run as cells of one batch")
+ap.add_argument("--config", required=True, nargs="+", help="slice configuration JSON of the experiment directory; several files (any numbers "
+                                                         "of slices and of users) run as cells of one batch")
 ap.add_argument("--seeds", default=None, help="comma-separated indices into the nine common seeds: every configuration runs with each of "
                                               "them, all in one batch (instead of --seed)")
 ap.add_argument("--traces", default=None, help="directory with ue<id>.log and the mapping file (default: synthetic CQI grids)")
@@ -77,7 +78,13 @@ a = ap.parse_args()
 seed_ids = [int(x) for x in a.seeds.split(",")] if a.seeds is not None else [a.seed]
 runs = [(Path(path).name[:-5] if path.endswith(".json") else Path(path).name, rs.SliceConfig.from_json(path), k) for path in a.config for k in seed_ids]
 n_cells = len(runs)
-sc = max((cfg for _, cfg, _ in runs), key=lambda cfg: cfg.n_users)  # the batch is created at the largest configuration
+# the batch is created at the largest slice count and the largest user count: a configuration that has both, else an even split
+S_max, U_max = max(cfg.n_slices for _, cfg, _ in runs), max(cfg.n_users for _, cfg, _ in runs)
+sc = next((cfg for _, cfg, _ in runs if cfg.n_slices == S_max and cfg.n_users == U_max), None)
+if sc is None:
+    if U_max < S_max:
+        raise SystemExit(f"several runs in one batch: {S_max} slices need at least as many users (the largest configuration has {U_max})")
+    sc = rs.SliceConfig([U_max // S_max + (1 if s < U_max % S_max else 0) for s in range(S_max)])
 R = a.nb_rbs // a.rbg_size
 n_ttis = int(round(a.duration * 1000))
 U = sc.n_users
@@ -92,8 +99,6 @@ if n_cells > 1:
         raise SystemExit("several runs in one batch: backlogged configurations only (the queue model keeps one configuration per batch)")
     if a.sched == 11:
         raise SystemExit("several runs in one batch: scheduler 11 reads one configuration (its kernel is another one)")
-    if any(cfg.n_slices != sc.n_slices for _, cfg, _ in runs):
-        raise SystemExit("several runs in one batch: every configuration needs the same number of slices")
     if len(set(logs)) != n_cells:
         raise SystemExit("several runs in one batch: --log needs {config} and / or {seed} so that every run has a log of its own")
 # (the queue model's batches run without the PHY error model's draws: its parity with the oracle is pinned that way)
@@ -204,5 +209,5 @@ else:
     totals = b.slice_totals()["cum_bytes"]
     for c, (name, cfg, k) in enumerate(runs):
         print(f"{name} seed {k}: {n_ttis} TTIs, {cfg.n_users} UEs, sched {a.sched}: per-slice Mbps " +
-              " ".join(f"{x:.2f}" for x in (totals[c].astype(np.float64) * 8 / 1e6 / a.duration)), file=sys.stderr)
+              " ".join(f"{x:.2f}" for x in (totals[c][:cfg.n_slices].astype(np.float64) * 8 / 1e6 / a.duration)), file=sys.stderr)
 b.close()
