@@ -32,6 +32,7 @@ extern "C" {
                                rs_batch_set_cell_configs / rs_batch_get_cell_config / rs_batch_slice_totals / rs_jit_selfcheck_cell_configs (per-cell weights, exponents and slice sizes in one batch),
                                RS_USER_ABSENT / rs_batch_cell_users / rs_jit_selfcheck_ragged_cells (cells of different user counts in one batch: an absent-user suffix in a cell's row),
                                rs_batch_set_cell_configs_n / rs_batch_cell_slices / rs_jit_selfcheck_ragged_slices (cells of different slice counts in one batch: an absent-slice suffix),
+                               rs_batch_set_cqi_epochs_device / rs_batch_write_cqi_epochs_device / rs_batch_cqi_write_status / rs_batch_debug_cqi_image (a batch's epoch grids from device memory, packed by a kernel on its stream; epochs rewritten in place: a ring),
                                rs_group_* (one TTI of several drop-in cells in one launch), rs_group_image_stats (cqi_epoch per cell of a group),
                                rs_group_specialize / rs_group_jit_status / rs_jit_selfcheck_group (a group's own self-checked builds of the one-TTI kernel),
                                rs_group_set_avg / rs_group_get_avg / rs_group_set_pending / rs_group_schedule_tti_at (a group cell's PF averages resident on the device),
@@ -885,6 +886,31 @@ int rs_batch_synthesize_cqi_at(rs_batch* b, uint64_t seed, const double* cqi_wei
                                int64_t first_cell);
 /* read back the grids of one cell (either source) for the parity tests: [n_epochs][U][R] */
 int rs_batch_download_cqi_epochs(rs_batch* b, int32_t cell, uint8_t* h_cqi);
+/* CQI source A from device memory: d_cqi = [n_cells][n_epochs][U][R] bytes ON THE BATCH'S DEVICE, values 1..15, at any byte
+ * alignment (a view of a larger buffer will do).  What rs_batch_upload_cqi_epochs does with the same bytes, with the packing into
+ * the kernels' image done by a kernel on the batch's stream; the call waits for it.  d_bytes must be the byte count the shape
+ * implies and d_cqi device memory of the batch's device (hipPointerGetAttributes; a host or managed pointer is RS_ERR_INVALID):
+ * both are checked before anything is enqueued or stored.  The values are checked by the kernel: a byte outside 1..15 is stored
+ * as CQI 1, and the call returns RS_ERR_INVALID naming the lowest such byte ("CQI %d at byte %lld outside 1..15") and leaves the
+ * batch WITHOUT a CQI source, as if none had been set, until a later call succeeds. */
+int rs_batch_set_cqi_epochs_device(rs_batch* b, const uint8_t* d_cqi, size_t d_bytes, int32_t n_epochs);
+/* Rewrites epochs [first_epoch, first_epoch + n) of the epoch grids in place: d_cqi = [n_cells][n][U][R] device bytes as above, no
+ * allocation, the other epochs untouched.  1 <= n <= n_epochs, 0 <= first_epoch < n_epochs; with cqi_epoch_wrap the epoch indices
+ * are taken modulo n_epochs, without it a window that runs past the end is RS_ERR_RANGE.  RS_ERR_STATE for a batch without epoch
+ * grids and for one with a per-PRB twin (which would no longer match).  The pack is enqueued on the batch's stream: behind the
+ * launches made so far, ahead of the later ones -- a producer may refill the epochs a run has consumed while the batch goes on
+ * (the ring: DESIGN.md 2.1).  Without RS_CQI_WRITE_ASYNC the call waits and reports like the setter.  With it the call returns
+ * after the enqueue; values outside 1..15 run as CQI 1 and are reported by rs_batch_cqi_write_status.  The caller orders its
+ * producer ahead of the batch's stream and keeps d_cqi alive until the stream has passed the pack. */
+#define RS_CQI_WRITE_ASYNC 1u
+int rs_batch_write_cqi_epochs_device(rs_batch* b, int32_t first_epoch, int32_t n, const uint8_t* d_cqi, size_t d_bytes, uint32_t flags);
+/* waits for the batch's stream; RS_OK with *bad_byte = -1 when no pack since the last report met a value outside 1..15, else
+ * RS_ERR_INVALID with the lowest such byte's index in its call's d_cqi and its value; the report clears the record and leaves the
+ * batch without a CQI source, like a failing synchronous call */
+int rs_batch_cqi_write_status(rs_batch* b, int64_t* bad_byte, int32_t* bad_value);
+/* one grid exactly as stored, for the tests: `bytes` must be the image's round_up(Upad * R, 16), Upad = 8 * odd >= U; [R][Upad],
+ * zeros in the padding and the tail */
+int rs_batch_debug_cqi_image(rs_batch* b, int32_t cell, int32_t epoch, uint8_t* h_image, size_t bytes);
 /* CQI source C: the reference's trace replay.  h_trace = [n_traces][n_rows][R]; user u of cell c
  * replays trace h_user_trace[c*U+u]; refresh rule and row index exactly as
  * cqi-manager.cpp:105-123 / enb-mac-entity.cc:189-191 ((int)(Now*1000/40) % row_modulus). */

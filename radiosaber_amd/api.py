@@ -200,6 +200,10 @@ PROTOTYPES = {
     "rs_batch_synthesize_cqi": (_int, [_ptr, C.c_uint64, _P(_f64), _i32]),
     "rs_batch_synthesize_cqi_at": (_int, [_ptr, C.c_uint64, _P(_f64), _i32, _i64]),
     "rs_batch_download_cqi_epochs": (_int, [_ptr, _i32, _P(_u8)]),
+    "rs_batch_set_cqi_epochs_device": (_int, [_ptr, _ptr, _size, _i32]),
+    "rs_batch_write_cqi_epochs_device": (_int, [_ptr, _i32, _i32, _ptr, _size, C.c_uint32]),
+    "rs_batch_cqi_write_status": (_int, [_ptr, _P(_i64), _P(_i32)]),
+    "rs_batch_debug_cqi_image": (_int, [_ptr, _i32, _i32, _P(_u8), _size]),
     "rs_batch_set_trace": (_int, [_ptr, _P(_u8), _i32, _i32, _i32, _P(_i32)]),
     "rs_batch_set_trace_prb": (_int, [_ptr, _P(_u8), _i32, _i32, _i32, _P(_i32)]),
     "rs_lds_bytes_per_cell": (_int, [_int] * 5),
@@ -255,6 +259,7 @@ PROTOTYPES = {
     "rs_batch_kernel_name": (_str, [_ptr]),
 }
 ABI_SYMBOLS = list(PROTOTYPES)
+RS_CQI_WRITE_ASYNC = 1  # rs_batch_write_cqi_epochs_device: return after the enqueue
 
 # rs_grant_record: one grant of one TTI of a counted run (32 bytes)
 GRANT_RECORD = np.dtype([("pos", np.int32), ("user_id", np.int32), ("bytes", np.int32), ("nprb", np.int32),
@@ -1130,6 +1135,7 @@ class BatchScheduler:
         cqi_epoch_wrap: the uploaded / synthesized epochs cycle instead of ending the run.  queue_state_lds: 0 auto, 1 LDS, -1 HBM."""
         self.slices, self.R, self.rbg_size, self.sched, self.n_cells = slices, n_rbgs, rbg_size, sched, n_cells
         self.S, self.U = slices.n_slices, slices.n_users
+        self.device = int(device)
         self._cfg = _CfgHolder(slices, n_rbgs, rbg_size, sched, device, stream, synthetic_exp, link_tables)
         bc = _BatchConfig(self._cfg.c, n_cells, first_tti, cqi_refresh, int(phy_error_draws), threads_per_cell,
                           int(jit), int(bool(cqi_epoch_wrap)), int(queue_state_lds), int(bool(autotune)), int(selfcheck))
@@ -1139,6 +1145,9 @@ class BatchScheduler:
 
     def close(self):
         if getattr(self, "_h", None):
+            if getattr(self, "_cqi_in_flight", None):  # tensors of asynchronous writes: released once the stream has passed their packs
+                lib().rs_batch_sync(self._h)
+                self._cqi_in_flight = []
             lib().rs_batch_destroy(self._h)
             self._h = None
 
@@ -1248,6 +1257,83 @@ class BatchScheduler:
     def download_cqi_epochs(self, cell):
         out = np.zeros((self.n_epochs, self.U, self.R), np.uint8)
         _check(lib().rs_batch_download_cqi_epochs(self._h, cell, _p(out, C.c_uint8)))
+        return out
+
+    # ---- epoch grids from device memory (rs_pack_cqi_kernel on the batch's stream) ----
+    def _device_grids(self, t, what):
+        """(t's address, its byte count, its epoch count) of a torch uint8 tensor [n_cells, E, U, R] on the batch's device, contiguous
+        (a view that begins at any byte of a larger tensor will do); ValueError for anything else, before any C call.  Duck-typed:
+        torch is not imported for the checks."""
+        for attr in ("data_ptr", "is_cuda", "is_contiguous", "element_size", "shape", "device"):
+            if not hasattr(t, attr):
+                raise ValueError(f"{what}: a torch tensor on the batch's device is needed, not {type(t).__name__}")
+        if not t.is_cuda:
+            raise ValueError(f"{what}: the tensor is on {t.device}, not on the batch's device {self.device}")
+        index = t.device.index
+        if index is not None and int(index) != self.device:
+            raise ValueError(f"{what}: the tensor is on device {index}, the batch on device {self.device}")
+        if t.element_size() != 1 or not str(t.dtype).endswith("uint8"):
+            raise ValueError(f"{what}: dtype {t.dtype}, uint8 is needed")
+        shape = tuple(int(x) for x in t.shape)
+        if len(shape) != 4 or shape[0] != self.n_cells or shape[1] < 1 or shape[2:] != (self.U, self.R):
+            raise ValueError(f"{what}: shape {shape}, [{self.n_cells}, E, {self.U}, {self.R}] is needed")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: the tensor is not contiguous")
+        return int(t.data_ptr()), shape[0] * shape[1] * shape[2] * shape[3], shape[1]
+
+    def _after_torch_stream(self, t):
+        """the batch's stream, as torch sees it, made to wait for what torch's current stream has enqueued so far (the producer of t)"""
+        import torch
+        s = torch.cuda.ExternalStream(self.stream or 0, device=t.device)
+        s.wait_stream(torch.cuda.current_stream(t.device))
+        return s
+
+    def _keep_until_packed(self, s, t):
+        """An asynchronous write reads t after the call has returned: the batch holds t until an event behind the pack has completed,
+        so that the caching allocator cannot hand its memory out again before.  (Not Tensor.record_stream: the allocator would then
+        record an event on the batch's stream when the tensor is freed, which may be after close() has destroyed that stream.)"""
+        import torch
+        done = torch.cuda.Event()
+        done.record(s)
+        self._cqi_in_flight = [(e, x) for e, x in getattr(self, "_cqi_in_flight", ()) if not e.query()] + [(done, t)]
+
+    def set_cqi_epochs_device(self, t):
+        """upload_cqi_epochs from a torch uint8 tensor [n_cells, E, U, R] on the batch's device: packed, checked and clamped by a
+        kernel on the batch's stream, behind what torch's current stream has enqueued; returns when it is done
+        (rs_batch_set_cqi_epochs_device).  A value outside 1..15 raises RadioSaberError and leaves the batch without a CQI source."""
+        ptr, nbytes, n_epochs = self._device_grids(t, "set_cqi_epochs_device")
+        self._after_torch_stream(t)
+        _check(lib().rs_batch_set_cqi_epochs_device(self._h, ptr, nbytes, n_epochs))
+        self.n_epochs = n_epochs
+
+    def write_cqi_epochs_device(self, first_epoch, t, sync=True):
+        """Rewrites epochs first_epoch .. first_epoch + E - 1 (modulo n_epochs with cqi_epoch_wrap) of the grids on the device from
+        t = [n_cells, E, U, R], in place, on the batch's stream: behind the launches made so far and ahead of the later ones
+        (rs_batch_write_cqi_epochs_device).  sync=False returns after the enqueue (RS_CQI_WRITE_ASYNC): values outside 1..15 then run
+        as CQI 1 and cqi_write_status() reports them; the batch keeps t alive until the pack has read it."""
+        ptr, nbytes, n = self._device_grids(t, "write_cqi_epochs_device")
+        s = self._after_torch_stream(t)
+        _check(lib().rs_batch_write_cqi_epochs_device(self._h, int(first_epoch), n, ptr, nbytes, 0 if sync else RS_CQI_WRITE_ASYNC))
+        if not sync:
+            self._keep_until_packed(s, t)
+
+    def cqi_write_status(self):
+        """Waits for the batch's stream; None when no pack since the last report met a value outside 1..15, else (byte index in its
+        call's tensor, value) of the lowest such byte -- the report then leaves the batch without a CQI source
+        (rs_batch_cqi_write_status)."""
+        byte, value = C.c_int64(-1), C.c_int32(0)
+        rc = lib().rs_batch_cqi_write_status(self._h, C.byref(byte), C.byref(value))
+        if rc == -1 and byte.value >= 0:
+            return int(byte.value), int(value.value)
+        _check(rc)
+        return None
+
+    def debug_cqi_image(self, cell, epoch):
+        """uint8 [round_up(Upad * R, 16)]: one grid exactly as stored, [R][Upad] with its zero padding and tail (rs_batch_debug_cqi_image)"""
+        k = (self.U + 7) // 8
+        upad = 8 * (k if k & 1 else k + 1)
+        out = np.zeros((upad * self.R + 15) // 16 * 16, np.uint8)
+        _check(lib().rs_batch_debug_cqi_image(self._h, int(cell), int(epoch), _p(out, C.c_uint8), out.size))
         return out
 
     def set_trace(self, trace, user_trace, row_modulus=475):

@@ -47,6 +47,9 @@ extern "C" void rs_jit_reject(RsJitKernel* k);
 extern "C" hipError_t rs_jit_launch(RsJitKernel* k, const RsLaunch* p, hipStream_t stream);
 extern "C" hipError_t rs_launch_synth(uint8_t* epochs, int64_t grid_stride, int n_cells, int n_epochs, int U, int R, int Upad,
                                       uint64_t seed, int64_t first_cell, const uint32_t* cdf16, hipStream_t stream);
+extern "C" hipError_t rs_launch_pack_cqi(const uint8_t* src, uint8_t* epochs, unsigned long long* bad_word, int n_cells, int n_src,
+                                         int first_epoch, int n_epochs, int U, int R, int Upad, int64_t grid_stride,
+                                         hipStream_t stream);
 extern "C" hipError_t rs_launch_copy_probe(const void* src, void* dst, size_t bytes, hipStream_t stream);
 extern "C" hipError_t rs_launch_slice_totals(const int64_t* cum_bytes, const int64_t* cum_rbs, const uint8_t* user_slice, int64_t map_stride,
                                              int n_cells, int U, int S, long long* out, hipStream_t stream);
@@ -301,6 +304,8 @@ struct rs_batch {
   uint8_t *d_epochs_prb = nullptr, *d_trace_prb = nullptr; /* per-PRB twins (link adaptation) */
   int64_t grid_stride_prb = 0;
   int32_t cqi_mode = RS_CQI_NONE;
+  unsigned long long* d_cqi_bad = nullptr; /* rs_pack_cqi_kernel's error word: all ones, or the lowest source byte outside 1..15 << 8 | its value */
+  bool cqi_bad_armed = false;              /* the word is all ones, or a pack has written it: nothing to clear ahead of the next pack */
   int32_t* d_err = nullptr;
   unsigned long long* d_slice_bytes = nullptr;
   unsigned long long* d_stamps = nullptr;
@@ -1369,7 +1374,7 @@ void rs_batch_destroy(rs_batch* b) {
                   b->d_sstate, b->d_scal, b->d_epochs, b->d_trace, b->d_user_trace, b->d_err, b->d_slice_bytes, b->d_stamps,
                   b->d_bearer_kind, b->d_arr_off, b->d_arr_time, b->d_arr_nfull, b->d_arr_last, b->d_qi, b->d_bavg, b->d_bcum,
                   b->d_qflags, b->d_qhol, b->d_flow_tti, b->d_flow_time, b->d_epochs_prb, b->d_trace_prb, b->d_gen_num, b->d_prio_sum,
-                  b->d_recs, b->d_cc_weight, b->d_cc_eps, b->d_cc_psi, b->d_cc_user_slice, b->d_totals};
+                  b->d_recs, b->d_cc_weight, b->d_cc_eps, b->d_cc_psi, b->d_cc_user_slice, b->d_totals, b->d_cqi_bad};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (b->own_stream && b->stream) (void)hipStreamDestroy(b->stream);
@@ -1637,6 +1642,114 @@ int rs_batch_download_cqi_epochs(rs_batch* b, int32_t cell, uint8_t* h_cqi) {
   for (int e = 0; e < b->n_epochs; e++) /* back to the caller's [U][R] order */
     for (size_t u = 0; u < (size_t)b->U; u++)
       for (size_t r = 0; r < (size_t)b->R; r++) h_cqi[e * grid + u * b->R + r] = tmp[e * stride + r * Upad + u];
+  return RS_OK;
+}
+
+/* ---- CQI source A from device memory: rs_pack_cqi_kernel packs, checks and clamps on the batch's stream ---- */
+
+/* d_cqi must be `want` bytes of device memory on the batch's device: asked of the runtime, nothing is read */
+static int cqi_device_source(rs_batch* b, const uint8_t* d_cqi, size_t d_bytes, size_t want) {
+  if (d_bytes != want) return fail(RS_ERR_INVALID, "d_bytes is %zu, the shape implies %zu", d_bytes, want);
+  hipPointerAttribute_t at;
+  memset(&at, 0, sizeof at);
+  hipError_t e = hipPointerGetAttributes(&at, d_cqi);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(RS_ERR_INVALID, "d_cqi is not device memory (hipPointerGetAttributes: %s): a host pointer?", hipGetErrorString(e));
+  }
+  if (at.type != hipMemoryTypeDevice || at.isManaged)
+    return fail(RS_ERR_INVALID, "d_cqi is %s memory, not device memory", at.isManaged ? "managed" : "host");
+  if (at.device != b->cfg.cell.device)
+    return fail(RS_ERR_INVALID, "d_cqi is on device %d, the batch on device %d", at.device, b->cfg.cell.device);
+  void* base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)d_cqi) != hipSuccess) (void)hipGetLastError();
+  else if (d_cqi + d_bytes > (const uint8_t*)base + size)
+    return fail(RS_ERR_INVALID, "d_cqi + d_bytes ends %zu bytes behind its allocation", (size_t)(d_cqi + d_bytes - ((const uint8_t*)base + size)));
+  return RS_OK;
+}
+
+/* the pack of n source epochs into epochs (first + j) mod n_epochs of d_epochs, enqueued; the error word is cleared ahead of the
+ * first pack and after every report, and sticky in between */
+static int cqi_pack(rs_batch* b, const uint8_t* d_cqi, int32_t first, int32_t n, int32_t n_epochs, size_t stride) {
+  if (!b->d_cqi_bad) HIP_TRY(hipMalloc(&b->d_cqi_bad, 8));
+  if (!b->cqi_bad_armed) {
+    HIP_TRY(hipMemsetAsync(b->d_cqi_bad, 0xFF, 8, b->stream));
+    b->cqi_bad_armed = true;
+  }
+  HIP_TRY(rs_launch_pack_cqi(d_cqi, b->d_epochs, b->d_cqi_bad, b->n_cells, n, first, n_epochs, b->U, b->R, rs_upad_of(b->U),
+                             (int64_t)stride, b->stream));
+  return RS_OK;
+}
+
+/* waits for the stream and reads the error word: RS_OK (*bad_byte = -1), or RS_ERR_INVALID with the word cleared and the batch
+ * left without a CQI source (the stored values are clamped to CQI 1, not the caller's) */
+static int cqi_report(rs_batch* b, int64_t* bad_byte, int32_t* bad_value) {
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  unsigned long long w = ~0ull;
+  if (b->d_cqi_bad && b->cqi_bad_armed) HIP_TRY(hipMemcpy(&w, b->d_cqi_bad, 8, hipMemcpyDeviceToHost));
+  if (bad_byte) *bad_byte = -1;
+  if (bad_value) *bad_value = 0;
+  if (w == ~0ull) return RS_OK;
+  HIP_TRY(hipMemsetAsync(b->d_cqi_bad, 0xFF, 8, b->stream));
+  b->cqi_mode = RS_CQI_NONE;
+  if (bad_byte) *bad_byte = (int64_t)(w >> 8);
+  if (bad_value) *bad_value = (int32_t)(w & 0xFF);
+  return fail(RS_ERR_INVALID, "CQI %d at byte %lld outside 1..15", (int)(w & 0xFF), (long long)(w >> 8));
+}
+
+int rs_batch_set_cqi_epochs_device(rs_batch* b, const uint8_t* d_cqi, size_t d_bytes, int32_t n_epochs) {
+  if (!b || !d_cqi || n_epochs < 1) return fail(RS_ERR_INVALID, "bad argument");
+  HIP_TRY(hipSetDevice(b->cfg.cell.device));
+  const size_t grid = (size_t)b->U * b->R;
+  const size_t stride = round_up(rs_upad_of(b->U) * b->R, 16); /* RBG-major [R][Upad]: the cell kernel's LDS image */
+  int rc = cqi_device_source(b, d_cqi, d_bytes, (size_t)b->n_cells * n_epochs * grid);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  if (b->d_epochs) { HIP_TRY(hipFree(b->d_epochs)); b->d_epochs = nullptr; }
+  b->cqi_mode = RS_CQI_NONE; /* until the pack has been seen to succeed */
+  HIP_TRY(hipMalloc(&b->d_epochs, (size_t)b->n_cells * n_epochs * stride));
+  b->grid_stride = (int64_t)stride;
+  b->n_epochs = n_epochs;
+  if (b->d_epochs_prb) { HIP_TRY(hipFree(b->d_epochs_prb)); b->d_epochs_prb = nullptr; }
+  b->grid_stride_prb = 0;
+  rc = cqi_pack(b, d_cqi, 0, n_epochs, n_epochs, stride);
+  if (rc) return rc;
+  b->cqi_mode = RS_CQI_EPOCHS;
+  return cqi_report(b, nullptr, nullptr);
+}
+
+int rs_batch_write_cqi_epochs_device(rs_batch* b, int32_t first_epoch, int32_t n, const uint8_t* d_cqi, size_t d_bytes, uint32_t flags) {
+  if (!b || !d_cqi) return fail(RS_ERR_INVALID, "bad argument");
+  if (flags & ~RS_CQI_WRITE_ASYNC) return fail(RS_ERR_INVALID, "unknown flags 0x%x", flags);
+  if (b->cqi_mode != RS_CQI_EPOCHS || !b->d_epochs) return fail(RS_ERR_STATE, "no epoch grids on the device");
+  if (b->d_epochs_prb) return fail(RS_ERR_STATE, "the batch has a per-PRB twin of its grids, which a write would leave behind");
+  if (n < 1 || n > b->n_epochs) return fail(RS_ERR_INVALID, "n %d outside 1..%d", n, b->n_epochs);
+  if (first_epoch < 0 || first_epoch >= b->n_epochs) return fail(RS_ERR_INVALID, "first_epoch %d outside 0..%d", first_epoch, b->n_epochs - 1);
+  if (!b->cfg.cqi_epoch_wrap && first_epoch + n > b->n_epochs)
+    return fail(RS_ERR_RANGE, "epochs %d..%d run past the last epoch %d (no cqi_epoch_wrap)", first_epoch, first_epoch + n - 1, b->n_epochs - 1);
+  HIP_TRY(hipSetDevice(b->cfg.cell.device));
+  int rc = cqi_device_source(b, d_cqi, d_bytes, (size_t)b->n_cells * n * b->U * b->R);
+  if (rc) return rc;
+  rc = cqi_pack(b, d_cqi, first_epoch, n, b->n_epochs, (size_t)b->grid_stride);
+  if (rc || (flags & RS_CQI_WRITE_ASYNC)) return rc;
+  return cqi_report(b, nullptr, nullptr);
+}
+
+int rs_batch_cqi_write_status(rs_batch* b, int64_t* bad_byte, int32_t* bad_value) {
+  if (!b || !bad_byte || !bad_value) return fail(RS_ERR_INVALID, "null argument");
+  HIP_TRY(hipSetDevice(b->cfg.cell.device));
+  return cqi_report(b, bad_byte, bad_value);
+}
+
+int rs_batch_debug_cqi_image(rs_batch* b, int32_t cell, int32_t epoch, uint8_t* h_image, size_t bytes) {
+  if (!b || !h_image || cell < 0 || cell >= b->n_cells) return fail(RS_ERR_INVALID, "bad argument");
+  if (b->cqi_mode != RS_CQI_EPOCHS) return fail(RS_ERR_STATE, "no epoch grids on the device");
+  if (epoch < 0 || epoch >= b->n_epochs) return fail(RS_ERR_INVALID, "epoch %d outside 0..%d", epoch, b->n_epochs - 1);
+  if (bytes != (size_t)b->grid_stride) return fail(RS_ERR_INVALID, "bytes is %zu, a grid's image has %lld", bytes, (long long)b->grid_stride);
+  HIP_TRY(hipSetDevice(b->cfg.cell.device));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  HIP_TRY(hipMemcpy(h_image, b->d_epochs + ((size_t)cell * b->n_epochs + epoch) * bytes, bytes, hipMemcpyDeviceToHost));
   return RS_OK;
 }
 

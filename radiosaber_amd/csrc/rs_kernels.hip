@@ -1071,6 +1071,153 @@ __global__ void rs_synth_cqi_kernel(uint8_t* epochs, int64_t grid_stride, int n_
   }
 }
 
+/* ------------------------------------------------------------------------------------------
+ * CQI grids from device memory (rs_batch_set_cqi_epochs_device / rs_batch_write_cqi_epochs_device): the caller's [U][R] bytes
+ * -> the cell kernel's LDS image [R][Upad], zeros in the padding and in the tail up to grid_stride.
+ *
+ * One work item is (cell, source epoch, tile); a tile is RS_PACK_TU users of every RBG, so its source bytes are one contiguous
+ * span of the grid.  The image is a flat row of 8-byte halves, (row r, user group g) at half r * NG + g with NG = Upad / 8 odd;
+ * a 16-byte store is two consecutive halves, and every store belongs to the tile of its SECOND half.  Its first half is then
+ * the group in front of it in the same row -- the tile's own, or the last group of the tile before it -- or, where the store
+ * begins a row (odd rows only, NG being odd), the LAST group of the row above.  That one group (8 users, a second contiguous
+ * span) is the tile's halo: with it every store of a tile is assembled from the tile's own LDS, and every byte of the image,
+ * padding and tail included, is written by exactly one lane with one aligned 16-byte store.
+ *
+ * The spans are copied to LDS as they lie in memory: aligned dwords (the span may begin at any byte; the dwords that hold its
+ * first and last bytes are put together from byte loads, so nothing is read outside the span), checked and clamped word-wise
+ * on the way.  The LDS copy keeps the source's row pitch R; a lane gathers its 8 users of one RBG with byte reads R apart, and
+ * the lanes of a wave walk the RBGs of one parity (q -> row 2q + parity): 32 lanes read 64 consecutive bytes, 16 banks, two
+ * lanes per dword -- for any R, the odd pitch 25 and the pitch 64 alike, where lanes walking the users would meet on two banks.
+ * LDS: (RS_PACK_TU + 8) * R + 16 bytes, 8.7 KB at 64 RBGs.
+ *
+ * A byte outside 1..15 is stored as CQI 1 and reported: the lane keeps the least (byte index in the call's source << 8 | value),
+ * the wave reduces it, and one lane does one 64-bit atomicMin -- only in a wave that met such a byte.
+ * ------------------------------------------------------------------------------------------ */
+#ifndef RS_JIT_BUILD /* (a run-time build holds the cell kernels only) */
+#define RS_PACK_TU 128                        /* users per tile: 16 groups of 8, 8 stores per RBG row */
+#define RS_PACK_THREADS 256
+#define RS_PACK_MAX_R 64                      /* RS_MAX_RBGS of the header: the launcher refuses more */
+#define RS_PACK_LDS_MAIN (RS_PACK_TU * RS_PACK_MAX_R / 4 + 2) /* dwords: the span plus up to 3 bytes of misalignment, rounded up */
+#define RS_PACK_LDS_HALO (8 * RS_PACK_MAX_R / 4 + 2)
+
+/* one contiguous span of n source bytes at p -> lds (dwords, the span's byte k at byte (p & 3) + k), values outside 1..15 as 1;
+ * src_off: the span's first byte as an index into the call's source (the error word names it) */
+__device__ __forceinline__ void rs_pack_span(const uint8_t* __restrict__ p, int n, int64_t src_off, uint32_t* lds,
+                                             unsigned long long& worst) {
+  if (n <= 0) return;
+  const int a = (int)((uintptr_t)p & 3);
+  const uint32_t* __restrict__ pa = (const uint32_t*)(p - a);
+  const int nd = (a + n + 3) >> 2;
+  for (int i = threadIdx.x; i < nd; i += RS_PACK_THREADS) {
+    const int lo = 4 * i - a; /* span index of the dword's byte 0 */
+    uint32_t w;
+    if (lo >= 0 && lo + 4 <= n) {
+      w = pa[i];
+    } else { /* the span's first or last dword: only its own bytes are read, the others count as a valid 1 */
+      w = 0x01010101u;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (lo + k >= 0 && lo + k < n) w = (w & ~(0xFFu << (8 * k))) | ((uint32_t)p[lo + k] << (8 * k));
+    }
+    /* 0x80 in every byte that is 0 or above 15 (exact per byte: no carry leaves a byte) */
+    const uint32_t hi = w & 0xF0F0F0F0u;
+    const uint32_t nz = ((w & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | w;   /* bit 7 set: the byte is not 0 */
+    const uint32_t big = ((hi & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | hi; /* bit 7 set: the byte has a bit above 15 */
+    const uint32_t bad = (~nz | big) & 0x80808080u;
+    if (bad) {
+      const int k = (__ffs((int)bad) - 1) >> 3; /* the lowest address is the lowest byte */
+      const unsigned long long key = ((unsigned long long)(src_off + lo + k) << 8) | ((w >> (8 * k)) & 0xFFu);
+      worst = key < worst ? key : worst;
+      const uint32_t m = (bad >> 7) * 0xFFu;
+      w = (w & ~m) | (0x01010101u & m);
+    }
+    lds[i] = w;
+  }
+}
+
+/* the 8 bytes of users 8g .. 8g+7 in row r of the image, from a span copy whose byte 0 is user u_first's RBG 0 (base = its
+ * misalignment); zeros for users from U on and for rows from R on */
+__device__ __forceinline__ uint2 rs_pack_half(const uint8_t* lds_bytes, int base, int u_first, int g, int r, int U, int R) {
+  uint32_t v[2] = {0u, 0u};
+  if (r < R) {
+    const int u0 = 8 * g;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int u = u0 + k;
+      const uint32_t b = u < U ? lds_bytes[base + (u - u_first) * R + r] : 0u;
+      v[k >> 2] |= b << (8 * (k & 3));
+    }
+  }
+  return make_uint2(v[0], v[1]);
+}
+
+__global__ void __launch_bounds__(RS_PACK_THREADS) rs_pack_cqi_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ epochs,
+                                                                      unsigned long long* bad_word, int n_cells, int n_src,
+                                                                      int first_epoch, int n_epochs, int U, int R, int Upad,
+                                                                      int64_t grid_stride) {
+  __shared__ __align__(16) uint32_t lds_main[RS_PACK_LDS_MAIN];
+  __shared__ __align__(16) uint32_t lds_halo[RS_PACK_LDS_HALO];
+  const int NG = Upad >> 3;                                  /* groups per row: odd */
+  const int n_tiles = (NG + RS_PACK_TU / 8 - 1) / (RS_PACK_TU / 8);
+  const int n_chunks = (int)(grid_stride >> 4);
+  const int Rh = (R + 1) >> 1;                               /* rows per parity; row R (R odd) holds the tail's second half */
+  const int64_t grid = (int64_t)U * R;
+  const int64_t total = (int64_t)n_cells * n_src * n_tiles;
+  unsigned long long worst = ~0ull;
+  for (int64_t w = blockIdx.x; w < total; w += gridDim.x) {
+    const int tile = (int)(w % n_tiles);
+    const int64_t ge = w / n_tiles; /* cell * n_src + j */
+    const int j = (int)(ge % n_src);
+    const int64_t cell = ge / n_src;
+    int e = first_epoch + j;
+    if (e >= n_epochs) e -= n_epochs; /* (first_epoch < n_epochs and n_src <= n_epochs: one wrap at the most) */
+    const uint8_t* g_src = src + ge * grid;
+    uint8_t* g_dst = epochs + (cell * n_epochs + e) * grid_stride;
+
+    const int G0 = tile * (RS_PACK_TU / 8);
+    const int um0 = 8 * G0, um1 = min(U, um0 + RS_PACK_TU);  /* the tile's users */
+    const int gh = tile ? G0 - 1 : NG - 1;                   /* the halo group */
+    const int uh0 = 8 * gh, uh1 = min(U, uh0 + 8);
+    const uint8_t* pm = g_src + (int64_t)um0 * R;
+    const uint8_t* ph = g_src + (int64_t)uh0 * R;
+    rs_pack_span(pm, (um1 - um0) * R, ge * grid + (int64_t)um0 * R, lds_main, worst);
+    rs_pack_span(ph, (uh1 - uh0) * R, ge * grid + (int64_t)uh0 * R, lds_halo, worst);
+    __syncthreads();
+    const int bm = (int)((uintptr_t)pm & 3), bh = (int)((uintptr_t)ph & 3);
+    const uint8_t* mb = (const uint8_t*)lds_main;
+    const uint8_t* hb = (const uint8_t*)lds_halo;
+    /* item = ((jl * 2 + parity) * Rh + q): the store whose second half is group G0 + 2 jl + (1 - parity) of row 2 q + parity
+     * (half index row * NG + group is odd exactly there, NG being odd) */
+    const int items = (RS_PACK_TU / 16) * 2 * Rh;
+    for (int it = threadIdx.x; it < items; it += RS_PACK_THREADS) {
+      const int q = it % Rh, jp = it / Rh;
+      const int par = jp & 1, jl = jp >> 1;
+      const int r1 = 2 * q + par;
+      const int g1 = G0 + 2 * jl + (1 - par);
+      if (g1 >= NG) continue;
+      const int c = (r1 * NG + g1) >> 1;
+      if (c >= n_chunks) continue;
+      uint2 h0;
+      if (g1 > G0) h0 = rs_pack_half(mb, bm, um0, g1 - 1, r1, U, R);
+      else if (g1 > 0) h0 = rs_pack_half(hb, bh, uh0, gh, r1, U, R);
+      else h0 = rs_pack_half(hb, bh, uh0, gh, r1 - 1, U, R); /* the store begins row r1 (odd): the row above ends in it */
+      const uint2 h1 = rs_pack_half(mb, bm, um0, g1, r1, U, R);
+      *(uint4*)(g_dst + ((int64_t)c << 4)) = make_uint4(h0.x, h0.y, h1.x, h1.y);
+    }
+    __syncthreads(); /* the next item's spans overwrite the two copies */
+  }
+  if (__ballot(worst != ~0ull)) { /* wave-uniform: a wave that met no such byte does nothing */
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      const unsigned long long o = __shfl_xor(worst, d, 64);
+      worst = o < worst ? o : worst;
+    }
+    if ((threadIdx.x & 63) == 0) atomicMin(bad_word, worst);
+  }
+}
+
+#endif /* RS_JIT_BUILD */
+
 /* measurement only: 16 bytes per lane streaming copy, to quote the attainable HBM rate next to the 8 TB/s spec
  * (SURVEY 8d).  Grid-stride so that a launch of a few workgroups per CU covers any size. */
 __global__ void __launch_bounds__(256) rs_copy_probe_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, size_t n16) {
@@ -1265,6 +1412,22 @@ extern "C" hipError_t rs_launch_synth(uint8_t* epochs, int64_t grid_stride, int 
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(rs_synth_cqi_kernel, dim3(blocks), dim3(256), 0, stream, epochs, grid_stride, n_cells, n_epochs,
                      U, R, Upad, seed, first_cell, cdf);
+  return hipGetLastError();
+}
+
+/* src = [n_cells][n_src][U][R] bytes at any alignment -> epochs (first_epoch + j) mod n_epochs of every cell of
+ * epochs = [n_cells][n_epochs][grid_stride]; bad_word: rs_pack_cqi_kernel's error word (all ones = none so far) */
+extern "C" hipError_t rs_launch_pack_cqi(const uint8_t* src, uint8_t* epochs, unsigned long long* bad_word, int n_cells, int n_src,
+                                         int first_epoch, int n_epochs, int U, int R, int Upad, int64_t grid_stride,
+                                         hipStream_t stream) {
+  if (n_cells < 1 || n_src < 1 || n_src > n_epochs || first_epoch < 0 || first_epoch >= n_epochs || U < 1 ||
+      R < 1 || R > RS_PACK_MAX_R || Upad != rs_upad_of(U) || grid_stride != (((int64_t)Upad * R + 15) & ~(int64_t)15))
+    return hipErrorInvalidValue;
+  const int n_tiles = (Upad / 8 + RS_PACK_TU / 8 - 1) / (RS_PACK_TU / 8);
+  const int64_t total = (int64_t)n_cells * n_src * n_tiles;
+  const int blocks = (int)(total < 2048 ? total : 2048); /* 8 workgroups per CU; the rest is grid-strided */
+  hipLaunchKernelGGL(rs_pack_cqi_kernel, dim3(blocks), dim3(RS_PACK_THREADS), 0, stream, src, epochs, bad_word, n_cells, n_src,
+                     first_epoch, n_epochs, U, R, Upad, grid_stride);
   return hipGetLastError();
 }
 
