@@ -328,22 +328,24 @@ struct rs_batch {
   /* bearer records (rs_batch_run_records): [n_cells][cap] records, then n_cells count words; grows, never shrinks.  Output, not state. */
   void* d_recs = nullptr;
   size_t recs_bytes = 0;
-  RsJitKernel* jit = nullptr; /* shape-specialised kernel (owned by the process-wide cache) */
-  RsJitKernel* jit_lean = nullptr; /* its lean build, compiled at the first launch that can use it (launch()) */
-  bool jit_lean_tried = false;
-  /* the records variants of the two (-DRS_JIT_RECORDS=1; rs_batch_run_grant_records), [0] general, [1] lean: compiled at the first
-   * records launch that would pick that build, checked with records on before they serve one (selfcheck_records) */
-  RsJitKernel* jit_rec[2] = {nullptr, nullptr};
-  bool jit_rec_tried[2] = {false, false}, jit_rec_checked[2] = {false, false};
-  bool rec_rejected = false;        /* the general records variant disagreed: the built-in kernels serve the records launches */
-  RsJitKernel* force_kernel = nullptr; /* a trial launch of selfcheck_records: this kernel and no other ... */
-  bool force_builtin = false;          /* ... or the built-in kernels */
-  int last_records = 0;             /* the last launch wrote grant records on: 0 it wrote none, 1 the built-in kernels, 2 the general variant, 3 the lean one */
-  bool autotuned = false;       /* rs_batch_config.autotune: the candidates were timed (or the tuning does not apply) */
-  bool selfchecked = false;     /* the self-check of the run-time builds: done (or it does not apply) */
-  bool selfchecked_general = false, selfchecked_lean = false;
-  bool in_selfcheck = false;    /* its trial launches come back through launch(): not again */
-  bool jit_rejected = false;    /* ... and a run-time build disagreed with the built-in kernels: dropped */
+  /* The run-time builds of the batch's kernel (owned by the process-wide cache), one record per build: the general build (batch_new;
+   * replaced by the commits of rs_batch_set_cell_configs and rs_batch_set_bearers, reset_builds), its lean build, compiled at the
+   * first launch that can use it (lean_kernel), and the records variants of the two (-DRS_JIT_RECORDS=1; rs_batch_run_grant_records),
+   * compiled at the first records launch that would pick that build and checked with records on before they serve one
+   * (selfcheck_records).  `checked`: the self-check is through with the build -- it passed, came with the mark, or was dropped. */
+  enum Slot { kGeneral, kLean, kRecGeneral, kRecLean, kNumBuilds, kBuiltinRecords = kNumBuilds };
+  struct Build { RsJitKernel* k = nullptr; bool tried = false, checked = false; };
+  struct Builds {
+    Build at[kNumBuilds];
+    bool rejected = false;     /* the general build disagreed with the built-in kernels: dropped, they serve every launch */
+    bool rec_rejected = false; /* the general records variant disagreed: the built-in kernels serve the records launches */
+    bool checked = false;      /* the self-check of the plain builds: done (or it does not apply) */
+    bool autotuned = false;    /* rs_batch_config.autotune: the candidates were timed (or the tuning does not apply) */
+    /* what served the last launch that was no trial: kGeneral or kLean (an empty general slot: the built-in kernels), a records
+     * variant, or the built-in kernels with grant records on (kBuiltinRecords) */
+    int last = kGeneral;
+  } builds;
+  RsJitKernel* general() const { return builds.at[kGeneral].k; }
   char selfcheck_msg[160] = "";
   int autotune_n = 0;
   char autotune_msg[768] = "";
@@ -424,18 +426,38 @@ int slice_window(const rs_batch* b) {
   for (int c = 0; c < b->n_cells; c++) win = std::max(win, map_window(b->cc_u2s.data() + (size_t)c * b->U, b->U));
   return win;
 }
-/* the -D options a batch's run-time builds carry beside the rule table's (rs_jit_get's `variant`): the per-cell reads of the load phase
- * are a compile-time switch, named only by a batch that has per-cell rows -- every other batch's option lists are what they were */
-/* (RsLaunch::cell_cfg as a build option: 1 rows, 2 rows with absent users, | 4 some cell of fewer slices than the batch) */
+/* the per-cell reads of the load phase are a compile-time switch of a batch's run-time builds (-DRS_JIT_CELL_CONFIGS=<word>), named only
+ * by a batch that has per-cell rows -- every other batch's option lists are what they were.  The word is RsLaunch::cell_cfg: 1 rows,
+ * 2 rows with absent users, | 4 some cell of fewer slices than the batch */
 int cell_cfg_word(bool absent_users, bool fewer_slices) { return (absent_users ? RS_CELL_CFG_RAGGED : 1) | (fewer_slices ? RS_CELL_CFG_SLICES : 0); }
-std::string cell_cfg_option(bool absent_users, bool fewer_slices) { return "-DRS_JIT_CELL_CONFIGS=" + std::to_string(cell_cfg_word(absent_users, fewer_slices)); }
-std::string jit_variant(const rs_batch* b, const char* more = nullptr) {
-  std::string v = more ? more : "";
-  if (b->cell_cfg) v += std::string(v.empty() ? "" : " ") + cell_cfg_option(b->ragged, b->ragged_slices);
-  return v;
+
+/* The one place a batch asks for a run-time build: `slot` says which (lean bit, records variant), `extra` adds an autotune candidate's
+ * options.  The arguments are the cache's key, so every call of a batch spells them the same way: the queue mode, the slice window, the
+ * streamed bit (cqi_refresh <= 4), and the variant string -- extra, -DRS_JIT_RECORDS=1, the per-cell switch, in this order; nullptr for
+ * the empty list (the key names a variant only where there is one).  A setter that builds BEFORE it commits names what the batch is
+ * about to have (BuildAs); -1: what it has. */
+struct BuildAs { int qmode = -1, win = -1, cell_cfg = -1; };
+RsJitKernel* batch_build(const rs_batch* b, int slot, char* msg, size_t msglen, const char* extra = nullptr, const BuildAs& as = BuildAs()) {
+  const bool lean = slot == rs_batch::kLean || slot == rs_batch::kRecLean, records = slot >= rs_batch::kRecGeneral;
+  const int cfg_word = as.cell_cfg >= 0 ? as.cell_cfg : (b->cell_cfg ? cell_cfg_word(b->ragged, b->ragged_slices) : 0);
+  std::string v = extra ? extra : "";
+  if (records) v += std::string(v.empty() ? "" : " ") + "-DRS_JIT_RECORDS=1";
+  if (cfg_word) v += std::string(v.empty() ? "" : " ") + "-DRS_JIT_CELL_CONFIGS=" + std::to_string(cfg_word);
+  return rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, as.qmode >= 0 ? as.qmode : (b->queues ? b->qmode : 0),
+                    as.win >= 0 ? as.win : slice_window(b), msg, msglen, (b->cfg.cqi_refresh <= 4 ? 2 : 0) | (lean ? 4 : 0),
+                    v.empty() ? nullptr : v.c_str());
 }
-/* (nullptr for the empty list: rs_jit_get's key names a variant only where there is one) */
-const char* variant_arg(const std::string& v) { return v.empty() ? nullptr : v.c_str(); }
+/* A new general build and its message (nullptr: the built-in kernels run, rs_batch_jit_status says why); everything that belonged to
+ * the old one starts over -- the lean build, the records variants, the self-check and the autotune with their messages. */
+void reset_builds(rs_batch* b, RsJitKernel* general, const char* msg) {
+  b->builds = rs_batch::Builds();
+  b->builds.at[rs_batch::kGeneral].k = general;
+  b->builds.at[rs_batch::kGeneral].tried = true;
+  b->selfcheck_msg[0] = 0;
+  b->autotune_n = 0;
+  b->autotune_msg[0] = 0;
+  snprintf(b->jit_msg, sizeof b->jit_msg, "%s", msg);
+}
 
 void carve_lds(rs_batch* b, RsLaunch* L) {
   /* (drop-in contexts of schedulers 1 and 7 carry the gate scratch too: rs_tti_in.required_rbs / data_to_transmit) */
@@ -686,12 +708,12 @@ rs_batch* batch_new(const rs_batch_config* cfg, bool direct) {
   if (want_jit && !direct) {
     /* failure is not an error of this call: the built-in kernels stay in use and the batch keeps the reason
      * (rs_batch_jit_status); rs_last_error() is left alone */
-    b->jit_wanted = true;
-    b->jit = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, 0, slice_window(b), b->jit_msg, sizeof b->jit_msg,
-                        b->cfg.cqi_refresh <= 4 ? 2 : 0);
-    if (b->jit) snprintf(b->jit_msg, sizeof b->jit_msg, "%s", rs_jit_is_untuned(b->jit) ? "in use, built WITHOUT the -mllvm tuning options (hiprtc refused them): a few per cent slower" : "");
-    else if (!b->jit_msg[0]) snprintf(b->jit_msg, sizeof b->jit_msg, "hiprtc build failed");
-    if (!b->jit && b->threads > 512) { /* nothing else can launch this workgroup size */
+    char msg[sizeof b->jit_msg] = "";
+    RsJitKernel* const k = batch_build(b, rs_batch::kGeneral, msg, sizeof msg);
+    if (k) snprintf(msg, sizeof msg, "%s", rs_jit_is_untuned(k) ? "in use, built WITHOUT the -mllvm tuning options (hiprtc refused them): a few per cent slower" : "");
+    else if (!msg[0]) snprintf(msg, sizeof msg, "hiprtc build failed");
+    reset_builds(b, k, msg);
+    if (!k && b->threads > 512) { /* nothing else can launch this workgroup size */
       fail(RS_ERR_INVALID, "threads_per_cell %d needs the shape-specialised kernel, which could not be built: %s", b->threads, b->jit_msg);
       rs_batch_destroy(b);
       return nullptr;
@@ -717,7 +739,7 @@ int check_device_err(rs_batch* b) {
  * (RS_JIT_LEAN_MIN_TTIS, default 256: short test launches are not worth a hiprtc run; RS_JIT_LEAN=0 switches it off) or by
  * rs_batch_prepare_launch; nullptr = the general kernel (or the built-in ones) serves this launch. */
 bool lean_qualifies(const rs_batch* b, int n_ttis, bool logged) {
-  if (!b->jit || b->direct || logged) return false;
+  if (!b->general() || b->direct || logged) return false;
   const char* const e_min = getenv("RS_JIT_LEAN_MIN_TTIS");
   const char* const e_on = getenv("RS_JIT_LEAN");
   const int lean_min = e_min ? atoi(e_min) : 256;
@@ -726,20 +748,39 @@ bool lean_qualifies(const rs_batch* b, int n_ttis, bool logged) {
 }
 RsJitKernel* lean_kernel(rs_batch* b, int n_ttis, bool logged) {
   if (!lean_qualifies(b, n_ttis, logged)) return nullptr;
-  if (!b->jit_lean_tried) {
-    b->jit_lean_tried = true;
+  rs_batch::Build& lean = b->builds.at[rs_batch::kLean];
+  if (!lean.tried) {
+    lean.tried = true;
     char msg[512] = "";
-    b->jit_lean = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, b->queues ? b->qmode : 0, slice_window(b), msg,
-                             sizeof msg, (b->cfg.cqi_refresh <= 4 ? 2 : 0) | 4, variant_arg(jit_variant(b)));
+    lean.k = batch_build(b, rs_batch::kLean, msg, sizeof msg);
     /* not an error of the launch -- the general build serves it -- but nothing silent either: rs_batch_jit_status carries the reason */
-    if (!b->jit_lean) snprintf(b->jit_msg, sizeof b->jit_msg, "lean build unavailable, the general build serves every launch (%.400s)", msg);
+    if (!lean.k) snprintf(b->jit_msg, sizeof b->jit_msg, "lean build unavailable, the general build serves every launch (%.400s)", msg);
   }
-  return b->jit_lean;
+  return lean.k;
 }
 
-int launch(rs_batch* b, int n_ttis, int16_t* d_map, int16_t* d_quota, int16_t* d_target, int32_t* d_tbs, int32_t* d_uinfo,
-           uint32_t* d_keys = nullptr, int32_t* d_bbytes = nullptr, double* d_bhol = nullptr, void* d_recs = nullptr, int64_t rec_cap = 0);
-int records_kernel(rs_batch* b, int n_ttis, RsJitKernel** k, int* which);
+/* One launch of a batch: the TTIs, the device rows of a logged run (all null: unlogged), the record block with one cell's capacity
+ * (rs_batch_run_records / rs_batch_run_grant_records), and which kernel runs it.  kUsual: launch() picks -- the records variant, the
+ * lean build or the general build as they qualify, after the self-check and the autotune that are due.  kThis / kBuiltin: a TRIAL of the
+ * self-checks or the autotune on `kernel` / on the kernels built into the library; it checks nothing, tunes nothing and leaves no mark
+ * in `builds.last`. */
+struct LaunchReq {
+  int n_ttis = 0;
+  int16_t *map = nullptr, *quota = nullptr, *target = nullptr;
+  int32_t *tbs = nullptr, *uinfo = nullptr;
+  uint32_t* keys = nullptr;
+  int32_t* bbytes = nullptr; /* the per-bearer rows of a queue-model batch */
+  double* bhol = nullptr;
+  void* recs = nullptr;
+  int64_t rec_cap = 0;
+  enum Pick { kUsual, kThis, kBuiltin } pick = kUsual;
+  RsJitKernel* kernel = nullptr;
+  explicit LaunchReq(int n) : n_ttis(n) {}
+  LaunchReq(int n, Pick p, RsJitKernel* k = nullptr) : n_ttis(n), pick(p), kernel(k) {}
+  bool logged() const { return map || quota || target || tbs || uinfo || keys || bbytes; }
+};
+int launch(rs_batch* b, const LaunchReq& rq);
+int records_kernel(rs_batch* b, int n_ttis, RsJitKernel** k, int* slot);
 
 /* Everything a batch carries from one launch to the next, as (device pointer, bytes): PF averages, pending grants, cumulative counters,
  * slice state, clock / rand() ring / CQI-report state, and with the queue model the bearers' queues, averages, counters and per-user
@@ -855,14 +896,73 @@ int state_digest(rs_batch* b, StateDigest* out) {
   return RS_OK;
 }
 
+/* The pending-grant words between their two formats.  A shape-specialised kernel keeps bytes | PRBs << 20 | "counted" << 30 there (RS_TX_*:
+ * the grant is in the cumulative totals already), the built-in kernels plain bytes (they count at grant time).  to_packed = false: the
+ * run-time builds' word to plain bytes; true: plain bytes to a word whose grant is in the totals.  Wherever the built-in kernels run a
+ * launch, or take over, beside run-time builds.  The queue model's kernels, built-in and run-time, share one format (and consume every
+ * grant before the launch ends): nothing to convert there. */
+int convert_tx(rs_batch* b, bool to_packed) {
+  if (b->queues) return RS_OK;
+  std::vector<int32_t> tx((size_t)b->n_cells * b->U);
+  if (hipStreamSynchronize(b->stream) != hipSuccess || hipMemcpy(tx.data(), b->d_tx, 4 * tx.size(), hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(RS_ERR_HIP, "copy of the pending grants failed");
+  for (int32_t& w : tx) w = to_packed ? (w ? ((w & RS_TX_BYTES_MASK) | RS_TX_COUNTED) : 0) : (w & RS_TX_BYTES_MASK);
+  if (hipMemcpy(b->d_tx, tx.data(), 4 * tx.size(), hipMemcpyHostToDevice) != hipSuccess) return fail(RS_ERR_HIP, "copy of the pending grants failed");
+  return RS_OK;
+}
+
+/* The trials of the self-checks and the autotune: launches of the batch's next TTIs on a kernel the caller names, every one from the
+ * same snapshot, and the snapshot put back afterwards so that they leave no trace in the run.  Owns the snapshot, the saved TTI count
+ * and the scratch allocations (the callers' record blocks too); `who` opens its error messages. */
+struct Trials {
+  rs_batch* const b;
+  const char* const who;
+  const StateParts sp;
+  const int64_t done0;
+  ScratchBuffers scratch;
+  void* snap = nullptr;
+  bool open = false; /* the snapshot is taken and not yet put back for good */
+  Trials(rs_batch* b, const char* who, bool with_record) : b(b), who(who), sp(b, with_record), done0(b->ttis_done) {}
+  ~Trials() { if (open) (void)put_back(); } /* an early return of the caller: the run still continues from where it was */
+  int begin() {
+    if (scratch.alloc(&snap, sp.total) != hipSuccess || sp.copy(b, snap, true) != hipSuccess) return fail(RS_ERR_HIP, "%s: snapshot failed", who);
+    open = true;
+    return RS_OK;
+  }
+  /* one trial: the state of the snapshot -- the pending-grant words as plain bytes where the built-in kernels run (convert_tx) --, the
+   * launch, between the two events if the caller times it, and what it left (`out`; nullptr: not looked at) */
+  int run(const LaunchReq& rq, StateDigest* out, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
+    if (sp.copy(b, snap, false) != hipSuccess) return fail(RS_ERR_HIP, "%s: state restore failed", who);
+    int rc = rq.pick == LaunchReq::kBuiltin ? convert_tx(b, false) : RS_OK;
+    if (!rc && e0 && hipEventRecord(e0, b->stream) != hipSuccess) rc = fail(RS_ERR_HIP, "%s: timing failed", who);
+    if (!rc) rc = launch(b, rq);
+    if (!rc && e1 && hipEventRecord(e1, b->stream) != hipSuccess) rc = fail(RS_ERR_HIP, "%s: timing failed", who);
+    if (!rc && out) rc = state_digest(b, out);
+    return rc;
+  }
+  int put_back() {
+    open = false;
+    const hipError_t back = sp.copy(b, snap, false);
+    const hipError_t sync = hipStreamSynchronize(b->stream);
+    b->ttis_done = done0;
+    return back != hipSuccess || sync != hipSuccess ? fail(RS_ERR_HIP, "%s: the cell state could not be put back", who) : RS_OK;
+  }
+  /* the end of the trials: the state back, then `rc` of the trials if one failed, then the device's error word */
+  int finish(int rc) {
+    const int back = put_back();
+    return back ? back : rc ? rc : check_device_err(b);
+  }
+};
+
 /* rs_batch_config.autotune: time the lean kernel in the variants the rule table of rs_jit.cpp chooses between, on this batch's own
  * next TTIs, and keep the fastest.  Every trial starts from the same snapshot and the snapshot is put back at the end, so the tuning
  * leaves no trace in the run.  All variants compute the same results (the parity tests run them against the oracle) -- and every
  * trial's final state is compared with the rule table's: a variant that disagrees is never kept (and says so in the report). */
 int autotune(rs_batch* b, int n_ttis) {
-  if (b->autotuned || !b->cfg.autotune) return RS_OK;
-  if (!lean_kernel(b, n_ttis, false)) return RS_OK; /* this launch does not qualify for the lean build: try again at a later one */
-  b->autotuned = true;
+  if (b->builds.autotuned || !b->cfg.autotune) return RS_OK;
+  RsJitKernel* const k_default = lean_kernel(b, n_ttis, false);
+  if (!k_default) return RS_OK; /* this launch does not qualify for the lean build: try again at a later one */
+  b->builds.autotuned = true;
   const int sched = b->sched;
   if (b->queues || b->direct || !(sched == 8 || sched == 9 || sched == 101 || sched == 103)) return RS_OK;
   const int win = slice_window(b);
@@ -871,50 +971,35 @@ int autotune(rs_batch* b, int n_ttis) {
   cand.push_back(ilp_by_rule ? "ss=default" : "ss=iterative-ilp");
   cand.push_back(b->R > 32 ? "-DRS_NO_SPEC" : "-DRS_NO_HOLD");
   if (sched == 9) cand.push_back("-DRS_P3_BLOCK=8");
-  const StateParts sp(b);
-  /* the snapshot and the two events live exactly as long as this call, whichever way it returns (an early HIP_TRY return used
-   * to leave them -- and the candidate kernel -- behind) */
-  ScratchBuffers scratch;
+  /* the snapshot and the two events live exactly as long as this call, whichever way it returns; the lean slot keeps the rule table's
+   * build until a better one has been chosen (every trial names its kernel) */
+  Trials trials(b, "autotune", false);
   ScratchEvents events;
-  void* snapshot = nullptr;
-  RsJitKernel* const k_default = b->jit_lean;
-  const int64_t done0 = b->ttis_done;
-  struct Restore { /* whatever happens: the rule table's build unless a better one was chosen, the TTI count as it was */
-    rs_batch* b; RsJitKernel* k; int64_t done;
-    ~Restore() { b->jit_lean = k; b->ttis_done = done; }
-  } restore{b, k_default, done0};
-  HIP_TRY(scratch.alloc(&snapshot, sp.total));
   HIP_TRY(events.create(2));
   const hipEvent_t e0 = events.ev[0], e1 = events.ev[1];
   const int trial = n_ttis < 512 ? n_ttis : 512;
   RsJitKernel* best = k_default;
   float best_ms = 0, default_ms = 0;
   StateDigest default_digest;
-  int rc = RS_OK;
-  HIP_TRY(sp.copy(b, snapshot, true));
+  int rc = trials.begin();
+  if (rc) return rc;
   std::string report;
   for (size_t i = 0; i < cand.size() && rc == RS_OK; i++) {
     char msg[512] = "";
-    RsJitKernel* k = i == 0 ? k_default
-                            : rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, sched, 0, win, msg, sizeof msg,
-                                         (b->cfg.cqi_refresh <= 4 ? 2 : 0) | 4, jit_variant(b, cand[i].c_str()).c_str());
+    RsJitKernel* k = i == 0 ? k_default : batch_build(b, rs_batch::kLean, msg, sizeof msg, cand[i].c_str());
     if (!k) { report += cand[i] + ": not built; "; continue; }
-    b->jit_lean = k;
     float ms = 0;
-    for (int rep = 0; rep < 3 && rc == RS_OK; rep++) { /* one warm launch, then the faster of two */
-      if (sp.copy(b, snapshot, false) != hipSuccess || hipEventRecord(e0, b->stream) != hipSuccess) { rc = fail(RS_ERR_HIP, "autotune: state restore failed"); break; }
-      rc = launch(b, trial, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    StateDigest digest;
+    for (int rep = 0; rep < 3 && rc == RS_OK; rep++) { /* one warm launch, then the faster of two; the state the last one left */
+      rc = trials.run(LaunchReq(trial, LaunchReq::kThis, k), rep == 2 ? &digest : nullptr, e0, e1);
       if (rc) break;
       float t = 0;
-      if (hipEventRecord(e1, b->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&t, e0, e1) != hipSuccess) {
+      if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&t, e0, e1) != hipSuccess) {
         rc = fail(RS_ERR_HIP, "autotune: timing failed");
         break;
       }
       if (rep == 1 || (rep == 2 && t < ms)) ms = t;
     }
-    if (rc) break;
-    StateDigest digest;
-    rc = state_digest(b, &digest);
     if (rc) break;
     if (i == 0) default_digest = digest;
     char line[320];
@@ -936,13 +1021,9 @@ int autotune(rs_batch* b, int n_ttis) {
     else if (ms < best_ms && ms < 0.99f * default_ms) { best = k; best_ms = ms; }
   }
   /* the run continues from where it was, whatever happened above */
-  const hipError_t back = sp.copy(b, snapshot, false);
-  const hipError_t sync = hipStreamSynchronize(b->stream);
-  if (back != hipSuccess || sync != hipSuccess) return fail(RS_ERR_HIP, "autotune: the cell state could not be put back");
+  rc = trials.finish(rc);
   if (rc) return rc;
-  rc = check_device_err(b);
-  if (rc) return rc;
-  restore.k = best;
+  b->builds.at[rs_batch::kLean].k = best;
   snprintf(b->autotune_msg, sizeof b->autotune_msg, "autotune over %d TTIs: %skept %s", trial, report.c_str(),
            best == k_default ? "the rule table's build" : "the fastest");
   return RS_OK;
@@ -973,126 +1054,87 @@ int selfcheck_policy(const rs_batch* b) {
  * silently advanced them). */
 int selfcheck(rs_batch* b, int n_ttis, bool logged) {
   const int policy = selfcheck_policy(b);
-  if (policy == kCheckNever || b->selfchecked || b->in_selfcheck) return RS_OK;
-  if (!b->jit || b->direct) { b->selfchecked = true; return RS_OK; } /* nothing run-time compiled */
+  rs_batch::Builds& B = b->builds;
+  rs_batch::Build &gen = B.at[rs_batch::kGeneral], &lean = B.at[rs_batch::kLean];
+  if (policy == kCheckNever || B.checked) return RS_OK;
+  if (!gen.k || b->direct) { B.checked = true; return RS_OK; } /* nothing run-time compiled */
   if (b->threads > 512) { /* no built-in kernel of this workgroup size to compare with */
-    b->selfchecked = true;
+    B.checked = true;
     snprintf(b->selfcheck_msg, sizeof b->selfcheck_msg, "not self-checked: the kernels built into the library stop at 512 threads per cell");
     return RS_OK;
   }
   /* the general build at the first launch; the lean build at the first launch that qualifies for it (RS_JIT_LEAN_MIN_TTIS, unlogged) */
-  RsJitKernel* const k_gen = b->jit;
   RsJitKernel* const k_lean = lean_kernel(b, n_ttis, logged);
-  const bool need_gen = !b->selfchecked_general && (policy == kCheckAll || !rs_jit_is_verified(k_gen));
-  const bool need_lean = k_lean && !b->selfchecked_lean && (policy == kCheckAll || !rs_jit_is_verified(k_lean));
+  const bool need_gen = !gen.checked && (policy == kCheckAll || !rs_jit_is_verified(gen.k));
+  const bool need_lean = k_lean && !lean.checked && (policy == kCheckAll || !rs_jit_is_verified(k_lean));
   const char* const e_on = getenv("RS_JIT_LEAN");
   const bool lean_off = e_on && atoi(e_on) == 0;
   if (!need_gen && !need_lean) {
     /* builds that came with the mark of an earlier process's check */
-    if (!b->selfchecked_general) {
-      b->selfchecked_general = true;
+    if (!gen.checked) {
+      gen.checked = true;
       snprintf(b->selfcheck_msg, sizeof b->selfcheck_msg, "the run-time build carries the self-check mark of the process that compiled it (cache file)");
     }
-    if (k_lean) b->selfchecked_lean = true;
-    b->selfchecked = b->selfchecked_lean || lean_off;
+    if (k_lean) lean.checked = true;
+    B.checked = lean.checked || lean_off;
     return RS_OK;
   }
-  b->in_selfcheck = true;
-  struct Leave { rs_batch* b; ~Leave() { b->in_selfcheck = false; } } leave{b};
-  const StateParts sp(b, true); /* (the trials write the flow completion record: it is put back with the state and compared) */
-  ScratchBuffers scratch;
-  void* snap = nullptr;
-  HIP_TRY(scratch.alloc(&snap, sp.total));
-  const int64_t done0 = b->ttis_done;
+  /* The trials name their kernel: the lean trial runs the lean build however short it is (a launch of `trial` TTIs picking for itself
+   * would compare them with RS_JIT_LEAN_MIN_TTIS).  The built-in kernels keep plain bytes in the pending-grant words where a
+   * shape-specialised kernel keeps bytes | PRBs << 20 | "counted" << 30 (RS_TX_*): Trials::run converts (convert_tx). */
+  Trials trials(b, "selfcheck", true); /* (the trials write the flow completion record: it is put back with the state and compared) */
   const int trial = n_ttis < 256 ? n_ttis : 256;
-  int rc = RS_OK;
   StateDigest want, got;
   const char* bad = nullptr;
-  /* the pending-grant words of a shape-specialised kernel are bytes | PRBs << 20 | "counted" << 30 (RS_TX_*: the grant is in the
-   * cumulative totals already); the built-in kernels keep plain bytes there (and count at grant time).  The queue model's kernels, built-in
-   * and run-time, share one format (and consume every grant before the launch ends): nothing to convert there. */
-  auto plain_tx = [&]() -> int {
-    if (b->queues) return RS_OK;
-    std::vector<int32_t> tx((size_t)b->n_cells * b->U);
-    if (hipStreamSynchronize(b->stream) != hipSuccess || hipMemcpy(tx.data(), b->d_tx, 4 * tx.size(), hipMemcpyDeviceToHost) != hipSuccess) return fail(RS_ERR_HIP, "selfcheck: copy failed");
-    for (int32_t& w : tx) w &= RS_TX_BYTES_MASK;
-    if (hipMemcpy(b->d_tx, tx.data(), 4 * tx.size(), hipMemcpyHostToDevice) != hipSuccess) return fail(RS_ERR_HIP, "selfcheck: copy failed");
-    return RS_OK;
-  };
-  if (sp.copy(b, snap, true) != hipSuccess) return fail(RS_ERR_HIP, "selfcheck: snapshot failed");
-  for (int v = 0; v < 3 && rc == RS_OK && !bad; v++) {
-    /* v = 0: built-in (no run-time kernel visible to launch()), 1: the general build alone, 2: the lean build */
-    if ((v == 1 && !need_gen) || (v == 2 && !need_lean)) continue;
-    b->jit = v == 0 ? nullptr : k_gen;
-    RsJitKernel* const keep_lean = b->jit_lean;
-    const bool keep_tried = b->jit_lean_tried;
-    if (v < 2) { b->jit_lean = nullptr; b->jit_lean_tried = true; }
-    if (sp.copy(b, snap, false) != hipSuccess) rc = fail(RS_ERR_HIP, "selfcheck: state restore failed");
-    if (!rc && v == 0) rc = plain_tx();
-    if (!rc) rc = launch(b, trial, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    b->jit_lean = keep_lean;
-    b->jit_lean_tried = keep_tried;
-    if (!rc) rc = state_digest(b, v == 0 ? &want : &got);
-    if (!rc && v > 0 && got != want) bad = v == 1 ? "general" : "lean";
-  }
-  b->jit = k_gen;
-  const hipError_t back = sp.copy(b, snap, false);
-  const hipError_t sync = hipStreamSynchronize(b->stream);
-  b->ttis_done = done0;
-  if (back != hipSuccess || sync != hipSuccess) return fail(RS_ERR_HIP, "selfcheck: the cell state could not be put back");
+  int rc = trials.begin();
   if (rc) return rc;
-  rc = check_device_err(b);
+  rc = trials.run(LaunchReq(trial, LaunchReq::kBuiltin), &want);
+  if (!rc && need_gen) {
+    rc = trials.run(LaunchReq(trial, LaunchReq::kThis, gen.k), &got);
+    if (!rc && got != want) bad = "general";
+  }
+  if (!rc && !bad && need_lean) {
+    rc = trials.run(LaunchReq(trial, LaunchReq::kThis, k_lean), &got);
+    if (!rc && got != want) bad = "lean";
+  }
+  rc = trials.finish(rc);
   if (rc) return rc;
   if (bad && bad[0] == 'l') {
     /* the lean build alone is wrong (the general one agreed just now or earlier, or carries the mark): the general build keeps serving every launch */
     rs_jit_reject(k_lean);
-    if (need_gen) { b->selfchecked_general = true; rs_jit_mark_verified(k_gen); }
-    b->jit_lean = nullptr;
-    b->jit_lean_tried = true;
-    b->selfchecked_lean = true;
-    b->selfchecked = true;
+    if (need_gen) { gen.checked = true; rs_jit_mark_verified(gen.k); }
+    lean = {nullptr, true, true};
+    B.checked = true;
     snprintf(b->jit_msg, sizeof b->jit_msg, "selfcheck: after %d TTIs the lean build of the shape-specialised kernel left a state that differs from the "
              "built-in kernels' in: %s; it is dropped and the general build, which agreed, serves every launch", trial, got.diff(want).c_str());
     return RS_OK;
   }
   if (bad) {
-    rs_jit_reject(k_gen);
-    b->jit = nullptr;
-    b->jit_lean = nullptr;
-    b->jit_lean_tried = true;
-    b->jit_rejected = true;
-    b->selfchecked = true;
+    rs_jit_reject(gen.k);
+    gen.k = nullptr;
+    lean.k = nullptr;
+    lean.tried = true;
+    B.rejected = true;
+    B.checked = true;
     /* the state just put back may have been left by the shape-specialised kernel: the built-in kernels that take over read plain bytes
      * (the first EWMA after a rejection used the packed word as a byte count) */
-    rc = plain_tx();
+    rc = convert_tx(b, false);
     if (rc) return rc;
     snprintf(b->jit_msg, sizeof b->jit_msg, "selfcheck: after %d TTIs the %s build of the shape-specialised kernel left a state that differs from the "
              "built-in kernels' in: %s; the batch runs on the built-in kernels (lint the code object: tools/lint_exec_restore.py)", trial, bad,
              got.diff(want).c_str());
     return RS_OK;
   }
-  if (need_gen) { b->selfchecked_general = true; rs_jit_mark_verified(k_gen); }
-  if (need_lean) { b->selfchecked_lean = true; rs_jit_mark_verified(k_lean); }
-  if (!need_lean && k_lean) b->selfchecked_lean = true; /* (came with the mark) */
+  if (need_gen) { gen.checked = true; rs_jit_mark_verified(gen.k); }
+  if (need_lean) rs_jit_mark_verified(k_lean);
+  if (k_lean) lean.checked = true; /* (checked just now, or came with the mark) */
   snprintf(b->selfcheck_msg, sizeof b->selfcheck_msg, "selfcheck over %d TTIs: the built-in kernels and the %s build%s agree", trial,
-           b->selfchecked_lean ? "general and lean" : "general", b->selfchecked_lean ? "s" : "");
-  b->selfchecked = b->selfchecked_lean || lean_off; /* the lean build is still to come: look again at the next launch */
+           lean.checked ? "general and lean" : "general", lean.checked ? "s" : "");
+  B.checked = lean.checked || lean_off; /* the lean build is still to come: look again at the next launch */
   return RS_OK;
 }
 
 /* ---- grant records of a backlogged batch (rs_batch_run_grant_records) ---- */
-
-/* The pending-grant words between the two formats (selfcheck() says what they are): to_packed = false, the run-time builds' word to the
- * plain bytes the built-in kernels read; true, plain bytes to a word whose grant is in the totals already (the built-in kernels count at
- * grant time).  Only where the built-in kernels serve one launch of a batch whose other launches run on the run-time builds. */
-int convert_tx(rs_batch* b, bool to_packed) {
-  std::vector<int32_t> tx((size_t)b->n_cells * b->U);
-  if (hipStreamSynchronize(b->stream) != hipSuccess || hipMemcpy(tx.data(), b->d_tx, 4 * tx.size(), hipMemcpyDeviceToHost) != hipSuccess)
-    return fail(RS_ERR_HIP, "grant records: copy of the pending grants failed");
-  for (int32_t& w : tx) w = to_packed ? (w ? ((w & RS_TX_BYTES_MASK) | RS_TX_COUNTED) : 0) : (w & RS_TX_BYTES_MASK);
-  if (hipMemcpy(b->d_tx, tx.data(), 4 * tx.size(), hipMemcpyHostToDevice) != hipSuccess) return fail(RS_ERR_HIP, "grant records: copy of the pending grants failed");
-  return RS_OK;
-}
 
 /* most grants of one cell in one TTI: a grant needs an RBG and goes to one user -- min(U, R); UpperBound's slices take their RBGs
  * whatever the other slices take: the sum over the slices of min(the slice's users, R), as rs_group_grant_bound has it */
@@ -1151,8 +1193,9 @@ void sort_grant_records(rs_batch_grant_record* r, size_t n) {
  * record block; the final states must agree bit for bit and the sorted lists record for record.  A variant that disagrees is dropped
  * alone (the caller goes on to the next fallback), rs_batch_jit_status names cell, record index and field.  The snapshot is put back. */
 int selfcheck_records(rs_batch* b, int n_ttis, int v) {
-  RsJitKernel* const k = b->jit_rec[v];
-  b->jit_rec_checked[v] = true;
+  rs_batch::Build& var = b->builds.at[rs_batch::kRecGeneral + v];
+  RsJitKernel* const k = var.k;
+  var.checked = true;
   const int policy = selfcheck_policy(b);
   if (policy == kCheckNever) return RS_OK;
   if (policy == kCheckUnmarked && rs_jit_is_verified(k)) {
@@ -1160,33 +1203,23 @@ int selfcheck_records(rs_batch* b, int n_ttis, int v) {
     return RS_OK;
   }
   if (b->threads > 512) return RS_OK; /* no built-in kernel of this workgroup size to compare with (selfcheck() says so for the plain builds) */
-  b->in_selfcheck = true;
-  struct Leave { rs_batch* b; ~Leave() { b->in_selfcheck = false; b->force_kernel = nullptr; b->force_builtin = false; } } leave{b};
-  const StateParts sp(b);
+  Trials trials(b, "selfcheck", false);
   const size_t cells = (size_t)b->n_cells;
   const int trial = n_ttis < 256 ? n_ttis : 256;
   const int64_t cap = (int64_t)trial * grant_bound(b);
   const size_t list_bytes = cells * (size_t)cap * sizeof(RsBatchGrantRecord), block_bytes = list_bytes + 4 * cells;
-  ScratchBuffers scratch;
-  void* snap = nullptr;
   char* block[2] = {nullptr, nullptr};
-  HIP_TRY(scratch.alloc(&snap, sp.total));
-  HIP_TRY(scratch.alloc(&block[0], block_bytes));
-  HIP_TRY(scratch.alloc(&block[1], block_bytes));
-  const int64_t done0 = b->ttis_done;
-  int rc = RS_OK;
+  HIP_TRY(trials.scratch.alloc(&block[0], block_bytes));
+  HIP_TRY(trials.scratch.alloc(&block[1], block_bytes));
   StateDigest want, got;
-  if (sp.copy(b, snap, true) != hipSuccess) return fail(RS_ERR_HIP, "selfcheck: snapshot failed");
+  int rc = trials.begin();
+  if (rc) return rc;
   for (int t = 0; t < 2 && rc == RS_OK; t++) { /* t = 0: the built-in kernels, 1: the variant */
-    if (sp.copy(b, snap, false) != hipSuccess) rc = fail(RS_ERR_HIP, "selfcheck: state restore failed");
-    if (!rc && t == 0) rc = convert_tx(b, false);
-    if (!rc && hipMemsetAsync(block[t] + list_bytes, 0, 4 * cells, b->stream) != hipSuccess) rc = fail(RS_ERR_HIP, "selfcheck: record block");
-    b->force_builtin = t == 0;
-    b->force_kernel = t == 0 ? nullptr : k;
-    if (!rc) rc = launch(b, trial, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, block[t], cap);
-    b->force_builtin = false;
-    b->force_kernel = nullptr;
-    if (!rc) rc = state_digest(b, t == 0 ? &want : &got);
+    if (hipMemsetAsync(block[t] + list_bytes, 0, 4 * cells, b->stream) != hipSuccess) rc = fail(RS_ERR_HIP, "selfcheck: record block");
+    LaunchReq rq(trial, t == 0 ? LaunchReq::kBuiltin : LaunchReq::kThis, t == 0 ? nullptr : k);
+    rq.recs = block[t];
+    rq.rec_cap = cap;
+    if (!rc) rc = trials.run(rq, t == 0 ? &want : &got);
   }
   /* the two blocks, sorted as the caller's lists are */
   std::vector<rs_batch_grant_record> list[2];
@@ -1202,12 +1235,7 @@ int selfcheck_records(rs_batch* b, int n_ttis, int v) {
       if (!rc) sort_grant_records(list[t].data() + c * (size_t)cap, used);
     }
   }
-  const hipError_t back = sp.copy(b, snap, false);
-  const hipError_t sync = hipStreamSynchronize(b->stream);
-  b->ttis_done = done0;
-  if (back != hipSuccess || sync != hipSuccess) return fail(RS_ERR_HIP, "selfcheck: the cell state could not be put back");
-  if (rc) return rc;
-  rc = check_device_err(b);
+  rc = trials.finish(rc);
   if (rc) return rc;
   char why[256] = "";
   if (got != want) snprintf(why, sizeof why, "left a state that differs from the built-in kernels' in: %s", got.diff(want).c_str());
@@ -1228,8 +1256,8 @@ int selfcheck_records(rs_batch* b, int n_ttis, int v) {
   }
   if (why[0]) {
     rs_jit_reject(k);
-    b->jit_rec[v] = nullptr;
-    if (v == 0) b->rec_rejected = true;
+    var.k = nullptr;
+    if (v == 0) b->builds.rec_rejected = true;
     snprintf(b->jit_msg, sizeof b->jit_msg, "selfcheck: after %d TTIs the records variant of the %s build %s; it is dropped and %s the records launches", trial,
              v ? "lean" : "general", why, v ? "the general build's records variant serves" : "the built-in kernels serve");
     return RS_OK;
@@ -1243,30 +1271,31 @@ int selfcheck_records(rs_batch* b, int n_ttis, int v) {
 /* The kernel of a records launch: the records variant (-DRS_JIT_RECORDS=1) of the build launch() would pick for an unlogged launch of
  * these TTIs -- lean where it qualifies, streamed where the batch is --, compiled at the first records launch that needs it and checked
  * with records on; it falls back as the lean build does, to the general build's variant and then (*k = nullptr) to the built-in kernels. */
-int records_kernel(rs_batch* b, int n_ttis, RsJitKernel** k, int* which) {
+int records_kernel(rs_batch* b, int n_ttis, RsJitKernel** k, int* slot) {
   *k = nullptr;
-  if (!b->jit || b->rec_rejected) return RS_OK;
+  *slot = rs_batch::kBuiltinRecords;
+  if (!b->general() || b->builds.rec_rejected) return RS_OK;
   for (int v = lean_qualifies(b, n_ttis, false) ? 1 : 0; v >= 0; --v) {
-    if (!b->jit_rec_tried[v]) {
-      b->jit_rec_tried[v] = true;
+    rs_batch::Build& var = b->builds.at[rs_batch::kRecGeneral + v];
+    if (!var.tried) {
+      var.tried = true;
       char msg[512] = "";
-      b->jit_rec[v] = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, 0, slice_window(b), msg, sizeof msg,
-                                 (b->cfg.cqi_refresh <= 4 ? 2 : 0) | (v ? 4 : 0), jit_variant(b, "-DRS_JIT_RECORDS=1").c_str());
-      if (!b->jit_rec[v])
+      var.k = batch_build(b, rs_batch::kRecGeneral + v, msg, sizeof msg);
+      if (!var.k)
         snprintf(b->jit_msg, sizeof b->jit_msg, "records variant of the %s build unavailable, %s the records launches (%.380s)", v ? "lean" : "general",
                  v ? "the general build's serves" : "the built-in kernels serve", msg);
     }
-    if (b->jit_rec[v] && !b->jit_rec_checked[v]) {
+    if (var.k && !var.checked) {
       const int rc = selfcheck_records(b, n_ttis, v); /* (a variant that disagrees is gone afterwards) */
       if (rc) return rc;
     }
-    if (b->jit_rec[v]) { *k = b->jit_rec[v]; *which = v; return RS_OK; }
+    if (var.k) { *k = var.k; *slot = rs_batch::kRecGeneral + v; return RS_OK; }
   }
   return RS_OK;
 }
 
-int launch(rs_batch* b, int n_ttis, int16_t* d_map, int16_t* d_quota, int16_t* d_target, int32_t* d_tbs, int32_t* d_uinfo,
-           uint32_t* d_keys, int32_t* d_bbytes, double* d_bhol, void* d_recs, int64_t rec_cap) {
+int launch(rs_batch* b, const LaunchReq& rq) {
+  const int n_ttis = rq.n_ttis;
   if (n_ttis < 1) return fail(RS_ERR_INVALID, "n_ttis %d < 1", n_ttis);
   if (b->cqi_mode == RS_CQI_NONE) return fail(RS_ERR_STATE, "no CQI source set");
   if (b->any_alpha && !b->direct && !b->queues)
@@ -1274,10 +1303,10 @@ int launch(rs_batch* b, int n_ttis, int16_t* d_map, int16_t* d_quota, int16_t* d
   if (b->queues && !b->d_arr_off) return fail(RS_ERR_STATE, "rs_batch_set_arrivals has not been called");
   if (n_ttis > RS_MAX_TTIS_PER_LAUNCH) {
     /* longer runs go out as several launches (state carries over; the per-launch counters of the kernel are 32-bit) */
-    if (d_map || d_tbs || d_uinfo || d_keys || d_bbytes) return fail(RS_ERR_INVALID, "logged runs are limited to %d TTIs per call", RS_MAX_TTIS_PER_LAUNCH);
+    if (rq.logged()) return fail(RS_ERR_INVALID, "logged runs are limited to %d TTIs per call", RS_MAX_TTIS_PER_LAUNCH);
     for (int done = 0; done < n_ttis;) {
       const int chunk = n_ttis - done < RS_MAX_TTIS_PER_LAUNCH ? n_ttis - done : RS_MAX_TTIS_PER_LAUNCH;
-      const int rc = launch(b, chunk, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+      const int rc = launch(b, LaunchReq(chunk));
       if (rc) return rc;
       done += chunk;
     }
@@ -1292,8 +1321,8 @@ int launch(rs_batch* b, int n_ttis, int16_t* d_map, int16_t* d_quota, int16_t* d
   L.user_trace = b->d_user_trace;
   L.epochs_prb = b->cqi_mode == RS_CQI_EPOCHS ? b->d_epochs_prb : nullptr; L.grid_stride_prb = b->grid_stride_prb;
   L.trace_prb = b->cqi_mode == RS_CQI_TRACE ? b->d_trace_prb : nullptr;
-  L.log_map = d_map; L.log_quota = d_quota; L.log_target = d_target; L.log_tbs = d_tbs; L.log_uinfo = d_uinfo;
-  L.log_keys = d_keys;
+  L.log_map = rq.map; L.log_quota = rq.quota; L.log_target = rq.target; L.log_tbs = rq.tbs; L.log_uinfo = rq.uinfo;
+  L.log_keys = rq.keys;
   if (b->queues) {
     const size_t n = (size_t)b->n_cells * 2 * b->U;
     L.bearer_kind = b->d_bearer_kind; L.arr_off = b->d_arr_off; L.arr_time = b->d_arr_time;
@@ -1303,40 +1332,40 @@ int launch(rs_batch* b, int n_ttis, int16_t* d_map, int16_t* d_quota, int16_t* d
     L.b_avg = b->d_bavg; L.b_cumb = b->d_bcum; L.b_cumr = b->d_bcum + n;
     L.q_flags = b->d_qflags; L.q_hol = b->d_qhol;
     L.flow_tti = b->d_flow_tti; L.flow_time = b->d_flow_time;
-    L.log_bbytes = d_bbytes; L.log_bhol = d_bhol;
+    L.log_bbytes = rq.bbytes; L.log_bhol = rq.bhol;
     /* bearer records (rs_batch_run_records; RsBearerRecord, rs_device.h): a batch launch sends no group's sent rows, the two words carry
      * the record block and one cell's capacity.  Null in every other launch -- the self-check's and the autotune's trials included. */
-    L.grp_sent = (int32_t*)d_recs; L.grp_sent_stride = d_recs ? rec_cap : 0;
+    L.grp_sent = (int32_t*)rq.recs; L.grp_sent_stride = rq.recs ? rq.rec_cap : 0;
   }
   /* grant records of a backlogged batch (rs_batch_run_grant_records; RsBatchGrantRecord, rs_device.h): the same two words.  Null in every
    * other launch -- the self-check's and the autotune's trials included; selfcheck_records' trials bring scratch blocks of their own. */
-  const bool records = !b->queues && !b->direct && d_recs != nullptr;
-  if (records) { L.grp_sent = (int32_t*)d_recs; L.grp_sent_stride = rec_cap; }
-  const bool logged = d_map || d_quota || d_target || d_tbs || d_uinfo || d_keys || d_bbytes;
+  const bool records = !b->queues && !b->direct && rq.recs != nullptr;
+  if (records) { L.grp_sent = (int32_t*)rq.recs; L.grp_sent_stride = rq.rec_cap; }
+  const bool logged = rq.logged(), trial = rq.pick != LaunchReq::kUsual;
   /* (a records launch runs none of the plain builds: they are checked at the first launch they serve) */
-  if (!records && !b->selfchecked && !b->in_selfcheck && b->jit && !b->direct) {
-    const int rc = selfcheck(b, n_ttis, logged); /* (its trials come back through here with `in_selfcheck` set) */
+  if (!trial && !records && !b->builds.checked && b->general() && !b->direct) {
+    const int rc = selfcheck(b, n_ttis, logged); /* (its trials come back through here, as trials) */
     if (rc) return rc;
   }
-  if (b->cfg.autotune && !b->autotuned && !logged && !records && !b->in_selfcheck) { /* (never inside a self-check trial: it checks the rule table's build) */
+  if (!trial && b->cfg.autotune && !b->builds.autotuned && !logged && !records) {
     const int rc = autotune(b, n_ttis);
     if (rc) return rc;
   }
   RsJitKernel* k = nullptr;
   bool builtin_beside_jit = false; /* the built-in kernels serve this launch of a batch whose state the run-time builds keep */
-  if (b->force_builtin || b->force_kernel) {
-    k = b->force_kernel;
+  if (trial) {
+    k = rq.pick == LaunchReq::kThis ? rq.kernel : nullptr; /* (the built-in kernels' trial: Trials::run has converted the pending-grant words) */
   } else if (records) {
-    int which = 0;
-    const int rc = records_kernel(b, n_ttis, &k, &which); /* (compiles and checks the variant at its first launch) */
+    int slot = rs_batch::kBuiltinRecords;
+    const int rc = records_kernel(b, n_ttis, &k, &slot); /* (compiles and checks the variant at its first launch) */
     if (rc) return rc;
     if (!k && b->threads > 512) return fail(RS_ERR_STATE, "grant records: no records variant of the run-time build is available and the built-in kernels stop at 512 threads per cell (%s)", b->jit_msg);
-    b->last_records = k ? 2 + which : 1;
-    builtin_beside_jit = !k && b->jit;
+    b->builds.last = slot;
+    builtin_beside_jit = !k && b->general();
   } else {
     k = lean_kernel(b, n_ttis, logged);
-    if (!k) k = b->jit;
-    b->last_records = 0;
+    b->builds.last = k ? rs_batch::kLean : rs_batch::kGeneral;
+    if (!k) k = b->general();
   }
   if (builtin_beside_jit) { const int rc = convert_tx(b, false); if (rc) return rc; }
   if (L.prio_sum) HIP_TRY(hipMemsetAsync(L.prio_sum, 0, 8, b->stream)); /* (every launch counts from zero) */
@@ -1462,8 +1491,10 @@ int rs_batch_set_cell_configs_n(rs_batch* b, const int32_t* cell_slices, const d
   RsJitKernel* cjit = nullptr;
   char cmsg[sizeof b->jit_msg] = {0};
   if (b->jit_wanted) {
-    cjit = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, 0, win, cmsg, sizeof cmsg, b->cfg.cqi_refresh <= 4 ? 2 : 0,
-                      cell_cfg_option(any_absent, any_fewer).c_str());
+    BuildAs as;
+    as.win = win;
+    as.cell_cfg = cell_cfg_word(any_absent, any_fewer);
+    cjit = batch_build(b, rs_batch::kGeneral, cmsg, sizeof cmsg, nullptr, as);
     if (cjit) snprintf(cmsg, sizeof cmsg, "%s", rs_jit_is_untuned(cjit) ? "in use, built WITHOUT the -mllvm tuning options (hiprtc refused them): a few per cent slower" : "");
     else if (!cmsg[0]) snprintf(cmsg, sizeof cmsg, "hiprtc build of the kernel with per-cell configurations failed");
     if (!cjit && b->threads > 512) return fail(RS_ERR_INVALID, "threads_per_cell %d needs the shape-specialised kernel with per-cell configurations: %s", b->threads, cmsg);
@@ -1493,17 +1524,8 @@ int rs_batch_set_cell_configs_n(rs_batch* b, const int32_t* cell_slices, const d
   b->base.weight = b->d_cc_weight; b->base.eps = b->d_cc_eps; b->base.psi = b->d_cc_psi; b->base.user_slice = b->d_cc_user_slice;
   b->base.cell_cfg = cell_cfg_word(any_absent, any_fewer);
   carve_lds(b, &b->base);
-  if (b->jit_wanted) {
-    /* the builds belong to the rows' window and to the switch: the lean build, the records variants, the self-check and the autotune
-     * start over with the new general build (nullptr: the built-in kernels run, rs_batch_jit_status says why) */
-    b->jit = cjit;
-    b->jit_lean = nullptr; b->jit_lean_tried = false;
-    for (int v = 0; v < 2; v++) { b->jit_rec[v] = nullptr; b->jit_rec_tried[v] = false; b->jit_rec_checked[v] = false; }
-    b->rec_rejected = false; b->jit_rejected = false;
-    b->selfchecked = false; b->selfchecked_general = false; b->selfchecked_lean = false; b->selfcheck_msg[0] = 0;
-    b->autotuned = false; b->autotune_n = 0; b->autotune_msg[0] = 0;
-    snprintf(b->jit_msg, sizeof b->jit_msg, "%s", cmsg);
-  }
+  /* the builds belong to the rows' window and to the switch: everything starts over with the new general build */
+  if (b->jit_wanted) reset_builds(b, cjit, cmsg);
   return RS_OK;
 }
 
@@ -1794,7 +1816,7 @@ int rs_batch_set_trace_prb(rs_batch* b, const uint8_t* h_trace_prb, int32_t n_tr
 
 int rs_batch_run_async(rs_batch* b, int32_t n_ttis) {
   if (!b) return fail(RS_ERR_INVALID, "null batch");
-  return launch(b, n_ttis, nullptr, nullptr, nullptr, nullptr, nullptr);
+  return launch(b, LaunchReq(n_ttis));
 }
 
 int rs_batch_sync(rs_batch* b) {
@@ -1850,7 +1872,10 @@ int rs_batch_run_logged_bearers(rs_batch* b, int32_t n_ttis, const rs_batch_log*
     HIP_TRY(hipMemsetAsync(d_bbytes, 0, 4 * rows * b->U * 2, b->stream));
     HIP_TRY(hipMemsetAsync(d_bhol, 0, 8 * rows * b->U * 2, b->stream));
   }
-  int rc = launch(b, n_ttis, d_map, d_quota, d_target, d_tbs, d_uinfo, d_keys, d_bbytes, d_bhol);
+  LaunchReq rq(n_ttis);
+  rq.map = d_map; rq.quota = d_quota; rq.target = d_target; rq.tbs = d_tbs; rq.uinfo = d_uinfo; rq.keys = d_keys;
+  rq.bbytes = d_bbytes; rq.bhol = d_bhol;
+  int rc = launch(b, rq);
   if (!rc) rc = rs_batch_sync(b);
   if (!rc) {
     if (lg->rbg_to_user) HIP_TRY(hipMemcpy(lg->rbg_to_user, d_map, 2 * rows * b->R, hipMemcpyDeviceToHost));
@@ -1863,6 +1888,63 @@ int rs_batch_run_logged_bearers(rs_batch* b, int32_t n_ttis, const rs_batch_log*
     if (bearers && blg->hol_delay) HIP_TRY(hipMemcpy(blg->hol_delay, d_bhol, 8 * rows * b->U * 2, hipMemcpyDeviceToHost));
   }
   return rc;
+}
+
+/* What rs_batch_run_records and rs_batch_run_grant_records share: a launch of n_ttis TTIs that writes records of rec_size bytes, at most
+ * `bound` per cell and TTI, into the batch's device block, and the copy back into the caller's lists (cap places per cell); `what` opens
+ * the messages.  The lists come back unsorted.  A wait that ended in a range error (`rc`) and a cell that counted more than its list
+ * holds (`over`) are the caller's to report, once the lists are complete. */
+struct RecordsRun {
+  std::vector<uint32_t> count;    /* per cell, as the device counted */
+  int64_t cap_dev = 0, over = -1; /* one cell's places in the device block; the first cell that counted more (-1: none) */
+  int rc = RS_OK;
+  std::chrono::steady_clock::time_point t0, t1, t2; /* before the launch, after the wait, after the copy back */
+  size_t used(size_t c) const { return (size_t)std::min((int64_t)count[c], cap_dev); }
+};
+static int run_with_records(rs_batch* b, int n_ttis, int64_t cap, int bound, size_t rec_size, const char* what, void* recs, int64_t* n_recs,
+                            RecordsRun* out) {
+  /* the device block: no cell can count more than n_ttis * bound, so a larger capacity of the caller's needs no larger list there */
+  const size_t cells = (size_t)b->n_cells;
+  const int64_t cap_dev = out->cap_dev = std::min(cap, (int64_t)n_ttis * bound);
+  const size_t list_bytes = cells * (size_t)cap_dev * rec_size, need = list_bytes + 4 * cells;
+  if (need > b->recs_bytes) {
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (b->d_recs) { HIP_TRY(hipFree(b->d_recs)); b->d_recs = nullptr; b->recs_bytes = 0; }
+    /* RS_RECORDS_MAX_BYTES: the largest device block a call may ask for (unset: what the device gives).  A block above it is a failed
+     * allocation, by the very path of one: it is how the tests reach this refusal without asking a card for memory it does not have. */
+    const char* const e_max = getenv("RS_RECORDS_MAX_BYTES");
+    const bool too_large = e_max && (unsigned long long)need > strtoull(e_max, nullptr, 10);
+    if (too_large || hipMalloc(&b->d_recs, need) != hipSuccess) {
+      if (!too_large) (void)hipGetLastError();
+      b->d_recs = nullptr;
+      return fail(RS_ERR_HIP, "%s: no device block of %zu bytes (%zu cells x %lld records)", what, need, cells, (long long)cap_dev);
+    }
+    b->recs_bytes = need;
+  }
+  uint32_t* const d_count = (uint32_t*)((char*)b->d_recs + list_bytes);
+  HIP_TRY(hipMemsetAsync(d_count, 0, 4 * cells, b->stream));
+  out->t0 = std::chrono::steady_clock::now();
+  LaunchReq rq(n_ttis);
+  rq.recs = b->d_recs;
+  rq.rec_cap = cap_dev;
+  int rc = launch(b, rq);
+  if (rc) return rc;
+  rc = out->rc = rs_batch_sync(b);
+  if (rc == RS_ERR_HIP) return rc;
+  out->t1 = std::chrono::steady_clock::now();
+  /* the copy back: the counts, then of every list the places that were written (copies queued on the stream, one wait) */
+  out->count.resize(cells);
+  HIP_TRY(hipMemcpy(out->count.data(), d_count, 4 * cells, hipMemcpyDeviceToHost));
+  for (size_t c = 0; c < cells; c++) {
+    n_recs[c] = (int64_t)out->count[c];
+    if (n_recs[c] > cap_dev && out->over < 0) out->over = (int64_t)c; /* (cap_dev < cap only where nothing can exceed it) */
+    if (out->used(c))
+      HIP_TRY(hipMemcpyAsync((char*)recs + c * (size_t)cap * rec_size, (const char*)b->d_recs + c * (size_t)cap_dev * rec_size, out->used(c) * rec_size,
+                             hipMemcpyDeviceToHost, b->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  out->t2 = std::chrono::steady_clock::now();
+  return RS_OK;
 }
 
 /* most bearers DoStopSchedule can credit in one TTI of one cell.  A credit needs a grant and a grant needs an RBG.
@@ -1884,43 +1966,9 @@ int rs_batch_run_records(rs_batch* b, int32_t n_ttis, int64_t cap, rs_bearer_rec
   if (!b->queues || !b->d_arr_off)
     return fail(RS_ERR_STATE, "bearer records: the batch has no queue model (rs_batch_set_bearers / rs_batch_set_arrivals)");
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  /* the device block: no cell can count more than n_ttis * bound, so a larger capacity of the caller's needs no larger list there */
+  RecordsRun run;
+  if (const int rc = run_with_records(b, n_ttis, cap, rs_batch_record_bound(b), sizeof(RsBearerRecord), "bearer records", recs, n_recs, &run)) return rc;
   const size_t cells = (size_t)b->n_cells;
-  const int64_t cap_dev = std::min(cap, (int64_t)n_ttis * rs_batch_record_bound(b));
-  const size_t list_bytes = cells * (size_t)cap_dev * sizeof(RsBearerRecord), need = list_bytes + 4 * cells;
-  if (need > b->recs_bytes) {
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    if (b->d_recs) { HIP_TRY(hipFree(b->d_recs)); b->d_recs = nullptr; b->recs_bytes = 0; }
-    /* RS_RECORDS_MAX_BYTES: the largest device block a call may ask for (unset: what the device gives).  A block above it is a failed
-     * allocation, by the very path of one: it is how the tests reach this refusal without asking a card for memory it does not have. */
-    const char* const e_max = getenv("RS_RECORDS_MAX_BYTES");
-    const bool too_large = e_max && (unsigned long long)need > strtoull(e_max, nullptr, 10);
-    if (too_large || hipMalloc(&b->d_recs, need) != hipSuccess) {
-      if (!too_large) (void)hipGetLastError();
-      b->d_recs = nullptr;
-      return fail(RS_ERR_HIP, "bearer records: no device block of %zu bytes (%zu cells x %lld records)", need, cells, (long long)cap_dev);
-    }
-    b->recs_bytes = need;
-  }
-  uint32_t* const d_count = (uint32_t*)((char*)b->d_recs + list_bytes);
-  HIP_TRY(hipMemsetAsync(d_count, 0, 4 * cells, b->stream));
-  int rc = launch(b, n_ttis, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, b->d_recs, cap_dev);
-  if (rc) return rc;
-  rc = rs_batch_sync(b);
-  if (rc == RS_ERR_HIP) return rc;
-  /* the copy back: the counts, then of every list the places that were written (copies queued on the stream, one wait) */
-  std::vector<uint32_t> count(cells);
-  HIP_TRY(hipMemcpy(count.data(), d_count, 4 * cells, hipMemcpyDeviceToHost));
-  int64_t over = -1;
-  for (size_t c = 0; c < cells; c++) {
-    n_recs[c] = (int64_t)count[c];
-    if ((int64_t)count[c] > cap_dev && over < 0) over = (int64_t)c; /* (cap_dev < cap only where nothing can exceed it) */
-    const size_t used = (size_t)std::min((int64_t)count[c], cap_dev);
-    if (used)
-      HIP_TRY(hipMemcpyAsync(recs + c * (size_t)cap, (const RsBearerRecord*)b->d_recs + c * (size_t)cap_dev, used * sizeof(RsBearerRecord),
-                             hipMemcpyDeviceToHost, b->stream));
-  }
-  HIP_TRY(hipStreamSynchronize(b->stream));
   /* BearerLogWriter's order: TTI, user, then the reference's loop over the user's bearers -- priority 1 first in DoStopSchedule of the
    * transport schedulers and NVS (downlink-transport-scheduler.cpp:179), flow 0 first in DL_PF's FlowsToSchedule.  A (TTI, user, bearer)
    * occurs once, so the result does not depend on the order the device handed the places out in.  The device hands out all places of
@@ -1930,7 +1978,7 @@ int rs_batch_run_records(rs_batch* b, int32_t n_ttis, int64_t cap, rs_bearer_rec
   auto key = [pf](const rs_bearer_record& x) { return ((uint64_t)(uint32_t)x.user << 1) | (uint64_t)(pf ? x.bearer : 1 - x.bearer); };
   for (size_t c = 0; c < cells; c++) {
     rs_bearer_record* const r = recs + c * (size_t)cap;
-    const size_t n = (size_t)std::min((int64_t)count[c], cap_dev);
+    const size_t n = run.used(c);
     bool ascending = true;
     for (size_t i = 0, j; i < n; i = j) {
       if (i && r[i].tti < r[i - 1].tti) ascending = false;
@@ -1944,10 +1992,10 @@ int rs_batch_run_records(rs_batch* b, int32_t n_ttis, int64_t cap, rs_bearer_rec
     if (!ascending)
       std::sort(r, r + n, [&key](const rs_bearer_record& x, const rs_bearer_record& y) { return x.tti != y.tti ? x.tti < y.tti : key(x) < key(y); });
   }
-  if (rc) return rc;
-  if (over >= 0)
+  if (run.rc) return run.rc;
+  if (run.over >= 0)
     return fail(RS_ERR_RANGE, "bearer records: cell %lld credited %lld bearers in these %d TTIs, the lists hold %lld (state, flow record and the other cells' lists are complete)",
-                (long long)over, (long long)n_recs[over], n_ttis, (long long)cap);
+                (long long)run.over, (long long)n_recs[run.over], n_ttis, (long long)cap);
   return RS_OK;
 }
 
@@ -1970,56 +2018,19 @@ int rs_batch_run_grant_records(rs_batch* b, int32_t n_ttis, int64_t cap, rs_batc
   if (b->sched == RS_SCHED_NVS_NONGREEDY) return fail(RS_ERR_INVALID, "grant records: scheduler %d runs on another kernel, which writes none", b->sched);
   if (b->direct) return fail(RS_ERR_INVALID, "grant records: not a batch");
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  /* the device block: no cell can count more than n_ttis * bound, so a larger capacity of the caller's needs no larger list there */
+  RecordsRun run;
+  if (const int rc = run_with_records(b, n_ttis, cap, grant_bound(b), sizeof(RsBatchGrantRecord), "grant records", recs, n_recs, &run)) return rc;
   const size_t cells = (size_t)b->n_cells;
-  const int64_t cap_dev = std::min(cap, (int64_t)n_ttis * grant_bound(b));
-  const size_t list_bytes = cells * (size_t)cap_dev * sizeof(RsBatchGrantRecord), need = list_bytes + 4 * cells;
-  if (need > b->recs_bytes) {
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    if (b->d_recs) { HIP_TRY(hipFree(b->d_recs)); b->d_recs = nullptr; b->recs_bytes = 0; }
-    /* (RS_RECORDS_MAX_BYTES: as in rs_batch_run_records, a block above it is a failed allocation by the very path of one) */
-    const char* const e_max = getenv("RS_RECORDS_MAX_BYTES");
-    const bool too_large = e_max && (unsigned long long)need > strtoull(e_max, nullptr, 10);
-    if (too_large || hipMalloc(&b->d_recs, need) != hipSuccess) {
-      if (!too_large) (void)hipGetLastError();
-      b->d_recs = nullptr;
-      return fail(RS_ERR_HIP, "grant records: no device block of %zu bytes (%zu cells x %lld records)", need, cells, (long long)cap_dev);
-    }
-    b->recs_bytes = need;
-  }
-  uint32_t* const d_count = (uint32_t*)((char*)b->d_recs + list_bytes);
-  HIP_TRY(hipMemsetAsync(d_count, 0, 4 * cells, b->stream));
-  const auto now = [] { return std::chrono::steady_clock::now(); };
-  const auto t0 = now();
-  int rc = launch(b, n_ttis, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, b->d_recs, cap_dev);
-  if (rc) return rc;
-  rc = rs_batch_sync(b);
-  if (rc == RS_ERR_HIP) return rc;
-  const auto t1 = now();
-  /* the copy back: the counts, then of every list the places that were written (copies queued on the stream, one wait) */
-  std::vector<uint32_t> count(cells);
-  HIP_TRY(hipMemcpy(count.data(), d_count, 4 * cells, hipMemcpyDeviceToHost));
-  int64_t over = -1;
-  for (size_t c = 0; c < cells; c++) {
-    n_recs[c] = (int64_t)count[c];
-    if ((int64_t)count[c] > cap_dev && over < 0) over = (int64_t)c; /* (cap_dev < cap only where nothing can exceed it) */
-    const size_t used = (size_t)std::min((int64_t)count[c], cap_dev);
-    if (used)
-      HIP_TRY(hipMemcpyAsync(recs + c * (size_t)cap, (const RsBatchGrantRecord*)b->d_recs + c * (size_t)cap_dev, used * sizeof(RsBatchGrantRecord),
-                             hipMemcpyDeviceToHost, b->stream));
-  }
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  const auto t2 = now();
   {
     /* the cells' lists are sorted side by side: up to 8 host threads (RS_RECORDS_SORT_THREADS; 1: on the caller's thread) */
     const char* const e_thr = getenv("RS_RECORDS_SORT_THREADS");
     size_t n_thr = e_thr ? (size_t)std::max(1, atoi(e_thr)) : std::min<size_t>(8, std::max(1u, std::thread::hardware_concurrency()));
     size_t total = 0;
-    for (size_t c = 0; c < cells; c++) total += (size_t)std::min((int64_t)count[c], cap_dev);
+    for (size_t c = 0; c < cells; c++) total += run.used(c);
     if (total < 65536) n_thr = 1; /* (a thread's start costs more than sorting a few thousand records) */
     n_thr = std::min(n_thr, cells);
     const auto work = [&](size_t first) {
-      for (size_t c = first; c < cells; c += n_thr) sort_grant_records(recs + c * (size_t)cap, (size_t)std::min((int64_t)count[c], cap_dev));
+      for (size_t c = first; c < cells; c += n_thr) sort_grant_records(recs + c * (size_t)cap, run.used(c));
     };
     std::vector<std::thread> pool;
     for (size_t k = 1; k < n_thr; k++) pool.emplace_back(work, k);
@@ -2028,12 +2039,12 @@ int rs_batch_run_grant_records(rs_batch* b, int32_t n_ttis, int64_t cap, rs_batc
   }
   if (getenv("RS_RECORDS_TIMING")) { /* where a call's time goes (tools/bench_grant_records.py, profiles/batch_grant_records.md) */
     const auto ms = [](auto a, auto z) { return std::chrono::duration<double, std::milli>(z - a).count(); };
-    fprintf(stderr, "rs_batch_run_grant_records: launch and wait %.3f ms, copy back %.3f ms, host sort %.3f ms\n", ms(t0, t1), ms(t1, t2), ms(t2, now()));
+    fprintf(stderr, "rs_batch_run_grant_records: launch and wait %.3f ms, copy back %.3f ms, host sort %.3f ms\n", ms(run.t0, run.t1), ms(run.t1, run.t2), ms(run.t2, std::chrono::steady_clock::now()));
   }
-  if (rc) return rc;
-  if (over >= 0)
+  if (run.rc) return run.rc;
+  if (run.over >= 0)
     return fail(RS_ERR_RANGE, "grant records: cell %lld counted %lld grants in these %d TTIs, the lists hold %lld (state and the other cells' lists are complete)",
-                (long long)over, (long long)n_recs[over], n_ttis, (long long)cap);
+                (long long)run.over, (long long)n_recs[run.over], n_ttis, (long long)cap);
   return RS_OK;
 }
 
@@ -2046,7 +2057,7 @@ int rs_batch_run_timed(rs_batch* b, int32_t n_ttis, int32_t launches, float* ms)
   int rc = RS_OK;
   HIP_TRY(hipEventRecord(ev[0], b->stream));
   for (int i = 0; i < launches && !rc; i++) {
-    rc = launch(b, n_ttis, nullptr, nullptr, nullptr, nullptr, nullptr);
+    rc = launch(b, LaunchReq(n_ttis));
     if (!rc) HIP_TRY(hipEventRecord(ev[i + 1], b->stream));
   }
   if (!rc) rc = rs_batch_sync(b);
@@ -2155,8 +2166,9 @@ int rs_batch_set_bearers(rs_batch* b, const uint8_t* bearer_kind) {
   RsJitKernel* qjit = nullptr;
   char qmsg[sizeof b->jit_msg] = {0};
   if (b->jit_wanted) { /* the shape-specialised kernel of the queue model is a different code object */
-    qjit = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, qmode, slice_window(b), qmsg, sizeof qmsg,
-                      b->cfg.cqi_refresh <= 4 ? 2 : 0); /* (the streamed bit as batch_new and lean_kernel set it: the general and the lean build differ in the lean bit only) */
+    BuildAs as;
+    as.qmode = qmode;
+    qjit = batch_build(b, rs_batch::kGeneral, qmsg, sizeof qmsg, nullptr, as);
     if (!qjit && !qmsg[0]) snprintf(qmsg, sizeof qmsg, "hiprtc build of the queue-model kernel failed");
     if (!qjit && b->threads > 512) return fail(RS_ERR_INVALID, "threads_per_cell %d needs the shape-specialised queue-model kernel: %s", b->threads, qmsg);
   }
@@ -2180,12 +2192,9 @@ int rs_batch_set_bearers(rs_batch* b, const uint8_t* bearer_kind) {
   b->queues = true;
   b->qmode = qmode;
   carve_lds(b, &b->base); /* schedulers 1 and 7 keep per-bearer scratch in LDS in this mode */
-  if (b->jit_wanted) {
-    b->jit = qjit; /* nullptr: the built-in queue kernels run, rs_batch_jit_status says why */
-    b->jit_lean = nullptr; /* the lean build belongs to the kernel it is a build of: the queue model's is compiled on demand */
-    b->jit_lean_tried = false;
-    snprintf(b->jit_msg, sizeof b->jit_msg, "%s", qmsg);
-  }
+  /* the queue-model build is another code object: what an earlier self-check (rs_batch_prepare_launch) found says nothing about it, and
+   * its lean build is compiled on demand */
+  if (b->jit_wanted) reset_builds(b, qjit, qmsg);
   return RS_OK;
 }
 
@@ -2397,7 +2406,7 @@ int rs_batch_checkpoint_save(rs_batch* b, void* buf, size_t buflen) {
   CkptHeader h{};
   memcpy(h.magic, "RSCK2\0\0", 8);
   h.S = b->S; h.U = b->U; h.R = b->R; h.G = b->G; h.sched = b->sched; h.n_cells = b->n_cells; h.queues = b->queues ? 1 : 0;
-  h.packed_tx = (b->jit && !b->queues) ? 1 : 0;
+  h.packed_tx = (b->general() && !b->queues) ? 1 : 0;
   h.ttis_done = b->ttis_done;
   h.bytes = (uint64_t)need;
   h.config_hash = ckpt_config_hash(b);
@@ -2433,7 +2442,7 @@ int rs_batch_checkpoint_load(rs_batch* b, const void* buf, size_t buflen) {
        * "counted" set (the grant is in the cumulative totals already, whoever wrote it), the built-in kernels want plain bytes */
       std::vector<int32_t> tx(q.n / 4);
       memcpy(tx.data(), in, q.n);
-      const bool want_packed = b->jit != nullptr;
+      const bool want_packed = b->general() != nullptr;
       for (int32_t& w : tx) {
         if (want_packed && !h.packed_tx) w = w ? (w | RS_TX_COUNTED) : 0; /* (no PRB count: it is in the totals, nothing reads it again) */
         else if (!want_packed && h.packed_tx) w &= RS_TX_BYTES_MASK;
@@ -2473,11 +2482,11 @@ int rs_batch_prepare_launch(rs_batch* b, int32_t n_ttis) {
   if (b->cqi_mode == RS_CQI_NONE) return fail(RS_ERR_STATE, "no CQI source set");
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   (void)lean_kernel(b, n_ttis > RS_MAX_TTIS_PER_LAUNCH ? RS_MAX_TTIS_PER_LAUNCH : n_ttis, false);
-  if (!b->selfchecked) {
+  if (!b->builds.checked) {
     const int rc = selfcheck(b, n_ttis > RS_MAX_TTIS_PER_LAUNCH ? RS_MAX_TTIS_PER_LAUNCH : n_ttis, false);
     if (rc) return rc;
   }
-  if (b->cfg.autotune && !b->autotuned) {
+  if (b->cfg.autotune && !b->builds.autotuned) {
     const int rc = autotune(b, n_ttis > RS_MAX_TTIS_PER_LAUNCH ? RS_MAX_TTIS_PER_LAUNCH : n_ttis);
     if (rc) return rc;
   }
@@ -2487,9 +2496,9 @@ int rs_batch_prepare_launch(rs_batch* b, int32_t n_ttis) {
 int rs_batch_jit_status(rs_batch* b, char* msg, size_t msglen) {
   if (!b) return fail(RS_ERR_INVALID, "null batch");
   if (msg && msglen) snprintf(msg, msglen, "%s", b->jit_msg);
-  if (b->jit_rejected || b->rec_rejected) return -2; /* (rec_rejected: the records launches alone lost their run-time build) */
-  if (msg && msglen && b->jit && !b->jit_msg[0] && b->selfcheck_msg[0]) snprintf(msg, msglen, "%s", b->selfcheck_msg);
-  return b->jit ? 1 : (b->jit_wanted ? -1 : 0);
+  if (b->builds.rejected || b->builds.rec_rejected) return -2; /* (rec_rejected: the records launches alone lost their run-time build) */
+  if (msg && msglen && b->general() && !b->jit_msg[0] && b->selfcheck_msg[0]) snprintf(msg, msglen, "%s", b->selfcheck_msg);
+  return b->general() ? 1 : (b->jit_wanted ? -1 : 0);
 }
 
 int rs_batch_slice_bytes_device(rs_batch* b, uint64_t* d_out) {
@@ -2523,12 +2532,13 @@ void* rs_batch_stream(rs_batch* b) { return b ? (void*)b->stream : nullptr; }
 const char* rs_batch_kernel_name(rs_batch* b) {
   if (!b) return "";
   /* after a launch with grant records: the build that served it (its records variant; the built-in kernels once the variants are gone) */
-  if (b->last_records >= 2) {
+  const int last = b->builds.last;
+  if (last == rs_batch::kRecGeneral || last == rs_batch::kRecLean) {
     const bool streamed = b->cfg.cqi_refresh <= 4;
-    return b->last_records == 3 ? (streamed ? "rs_cell_kernel_jit[lean,streamed,records]" : "rs_cell_kernel_jit[lean,records]")
+    return last == rs_batch::kRecLean ? (streamed ? "rs_cell_kernel_jit[lean,streamed,records]" : "rs_cell_kernel_jit[lean,records]")
                                 : (streamed ? "rs_cell_kernel_jit[streamed,records]" : "rs_cell_kernel_jit[records]");
   }
-  if (b->jit && b->last_records == 0) return "rs_cell_kernel_jit";
+  if (b->general() && last != rs_batch::kBuiltinRecords) return "rs_cell_kernel_jit";
   switch (b->sched) {
     case 1: return "rs_cell_kernel<1, 0, false>";
     case 7: return "rs_cell_kernel<7, 0, false>";
