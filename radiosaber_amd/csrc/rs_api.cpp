@@ -28,33 +28,7 @@
 #include "../../include/radiosaber_hip.h"
 #include "rs_amc_tables.inc"
 #include "rs_link_pinned.inc"
-#include "rs_device.h"
-
-extern "C" hipError_t rs_launch_cells(const RsLaunch* p, int threads, hipStream_t stream);
-extern "C" hipError_t rs_prepare_kernels(int max_lds_bytes);
-struct RsJitKernel;
-extern "C" RsJitKernel* rs_jit_get(int device, int S, int U, int R, int G, int NT, int sched, int qmode, int win, char* err, size_t errlen,
-                                   int flags, /* bit 0: drop-in (one-TTI) kernel, bit 1: streamed batch (cqi_refresh <= 4), bit 2: lean build,
-                                                * bit 3: a group's build of the one-TTI kernel (rs_group_kernel_jit), bit 4 (with bit 3): its
-                                                * resident form (rs_group_resident_kernel_jit), bit 5 (with bit 3, never with bit 4): its
-                                                * queued form (rs_group_queued_kernel_jit) */
-                                   const char* variant = nullptr); /* an autotune candidate: extra -D options and / or "ss=<LLVM scheduler strategy>" */
-extern "C" int rs_jit_is_untuned(const RsJitKernel* k);
-extern "C" int rs_jit_is_verified(const RsJitKernel* k);  /* carries the self-check mark (this process, or its cache file) */
-extern "C" int rs_jit_was_loaded(const RsJitKernel* k);   /* came from the disk cache */
-extern "C" void rs_jit_mark_verified(RsJitKernel* k);
-extern "C" void rs_jit_reject(RsJitKernel* k);
-extern "C" hipError_t rs_jit_launch(RsJitKernel* k, const RsLaunch* p, hipStream_t stream);
-extern "C" hipError_t rs_launch_synth(uint8_t* epochs, int64_t grid_stride, int n_cells, int n_epochs, int U, int R, int Upad,
-                                      uint64_t seed, int64_t first_cell, const uint32_t* cdf16, hipStream_t stream);
-extern "C" hipError_t rs_launch_pack_cqi(const uint8_t* src, uint8_t* epochs, unsigned long long* bad_word, int n_cells, int n_src,
-                                         int first_epoch, int n_epochs, int U, int R, int Upad, int64_t grid_stride,
-                                         hipStream_t stream);
-extern "C" hipError_t rs_launch_copy_probe(const void* src, void* dst, size_t bytes, hipStream_t stream);
-extern "C" hipError_t rs_launch_slice_totals(const int64_t* cum_bytes, const int64_t* cum_rbs, const uint8_t* user_slice, int64_t map_stride,
-                                             int n_cells, int U, int S, long long* out, hipStream_t stream);
-extern "C" hipError_t rs_launch_slice_bytes(const int64_t* cum_bytes, const uint8_t* user_slice, int64_t map_stride, int n_cells, int U,
-                                            int S, unsigned long long* d_out, hipStream_t stream);
+#include "rs_host.h"
 
 namespace {
 
@@ -443,9 +417,12 @@ RsJitKernel* batch_build(const rs_batch* b, int slot, char* msg, size_t msglen, 
   std::string v = extra ? extra : "";
   if (records) v += std::string(v.empty() ? "" : " ") + "-DRS_JIT_RECORDS=1";
   if (cfg_word) v += std::string(v.empty() ? "" : " ") + "-DRS_JIT_CELL_CONFIGS=" + std::to_string(cfg_word);
-  return rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, as.qmode >= 0 ? as.qmode : (b->queues ? b->qmode : 0),
-                    as.win >= 0 ? as.win : slice_window(b), msg, msglen, (b->cfg.cqi_refresh <= 4 ? 2 : 0) | (lean ? 4 : 0),
-                    v.empty() ? nullptr : v.c_str());
+  const RsJitSpec spec = {.S = b->S, .U = b->U, .R = b->R, .G = b->G, .NT = b->threads, .sched = b->sched,
+                          .qmode = as.qmode >= 0 ? as.qmode : (b->queues ? b->qmode : 0),
+                          .win = as.win >= 0 ? as.win : slice_window(b),
+                          .flags = (b->cfg.cqi_refresh <= 4 ? 2 : 0) | (lean ? 4 : 0),
+                          .variant = v.empty() ? nullptr : v.c_str()};
+  return rs_jit_get(b->cfg.cell.device, spec, msg, msglen);
 }
 /* A new general build and its message (nullptr: the built-in kernels run, rs_batch_jit_status says why); everything that belonged to
  * the old one starts over -- the lean build, the records variants, the self-check and the autotune with their messages. */
@@ -2895,17 +2872,20 @@ void selfcheck_state(RsJitKernel* k, int left, int agreed, const char* ref, char
  * build serves every call), and how many calls each serves beside the built-in kernel.  A failed general build leaves its message in
  * the pair. */
 int jit_pair_build(JitPair* p, const rs_batch* b, int flags) {
-  const int qmode = (b->sched == RS_SCHED_PF || b->sched == RS_SCHED_NVS) ? 1 : 0; /* (the gate scratch of a drop-in carve: carve_lds) */
+  RsJitSpec spec = {.S = b->S, .U = b->U, .R = b->R, .G = b->G, .NT = b->threads, .sched = b->sched,
+                    .qmode = (b->sched == RS_SCHED_PF || b->sched == RS_SCHED_NVS) ? 1 : 0, /* (the gate scratch of a drop-in carve: carve_lds) */
+                    .flags = flags};
   char msg[512] = "";
   p->wanted = true;
-  p->jit[0] = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, qmode, 0, msg, sizeof msg, flags);
+  p->jit[0] = rs_jit_get(b->cfg.cell.device, spec, msg, sizeof msg);
   if (!p->jit[0]) {
     snprintf(p->msg, sizeof p->msg, "%s", msg[0] ? msg : "hiprtc build failed");
     return fail(RS_ERR_HIP, "%s", p->msg);
   }
   p->msg[0] = 0;
   const char* const e_on = getenv("RS_JIT_LEAN");
-  if (!e_on || atoi(e_on) != 0) p->jit[1] = rs_jit_get(b->cfg.cell.device, b->S, b->U, b->R, b->G, b->threads, b->sched, qmode, 0, msg, sizeof msg, flags | 4);
+  spec.flags |= 4;
+  if (!e_on || atoi(e_on) != 0) p->jit[1] = rs_jit_get(b->cfg.cell.device, spec, msg, sizeof msg);
   for (int w = 0; w < 2; w++) {
     p->chk_agreed[w] = 0;
     p->chk_left[w] = selfcheck_calls(p->jit[w]);
@@ -3480,8 +3460,6 @@ struct rs_group {
   bool last_call_jit = false;
   char kname[RS_GROUP_FORMS][56] = {}, kname_jit[RS_GROUP_FORMS][40] = {};
 };
-
-extern "C" hipError_t rs_launch_group(const RsLaunch* p, int threads, int form, hipStream_t stream);
 
 namespace {
 /* The forms of a group call, one row each: what the HOST alone knows of a form.  What a form is -- the facts its kernels read, the

@@ -1270,6 +1270,7 @@ __global__ void __launch_bounds__(256) rs_slice_totals_kernel(const int64_t* cum
 
 #if !defined(__HIPCC_RTC__) && !defined(RS_JIT_BUILD)
 #include <utility>
+#include "rs_host.h"
 /* host-callable launchers (defined here so that the kernels stay in one translation unit) */
 extern "C" hipError_t rs_launch_cells(const RsLaunch* p, int threads, hipStream_t stream) {
   dim3 grid(p->n_cells), block(threads);
