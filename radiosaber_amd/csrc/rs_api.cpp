@@ -29,6 +29,7 @@
 #include "rs_amc_tables.inc"
 #include "rs_link_pinned.inc"
 #include "rs_host.h"
+#include "rs_devmem.h"
 
 namespace {
 
@@ -252,56 +253,57 @@ struct rs_batch {
   bool any_alpha = false;
   bool synthetic = false;    /* rs_config.synthetic_exp */
   bool gen_exp = false;      /* drop-in context with an exponent outside {0, 1} (ref: packet-scheduler.h:38-49 takes any int) */
-  double* d_gen_num = nullptr; /* [S][16] pow(kbps[cqi], algo_epsilon[s]), host libm */
-  int32_t *d_alpha = nullptr, *d_beta = nullptr;
   int S, U, R, G, sched, n_cells, threads;
   bool direct = false;
   hipStream_t stream = nullptr;
   bool own_stream = false;
-  /* device */
-  RsTables* d_tab = nullptr;
-  double* d_weight = nullptr;
-  int32_t *d_eps = nullptr, *d_psi = nullptr;
-  uint8_t* d_user_slice = nullptr;
-  int32_t* d_tbs_eff = nullptr;
-  double* d_avg = nullptr;
-  int32_t* d_tx = nullptr;
-  int64_t *d_cumb = nullptr, *d_cumr = nullptr;
-  double* d_sstate = nullptr;
-  RsCellScalars* d_scal = nullptr;
-  uint8_t* d_epochs = nullptr;
-  int64_t grid_stride = 0;
-  int32_t n_epochs = 0;
-  uint8_t* d_trace = nullptr;
-  int32_t n_traces = 0, n_rows = 0, row_mod = 0;
-  int32_t* d_user_trace = nullptr;
-  uint8_t *d_epochs_prb = nullptr, *d_trace_prb = nullptr; /* per-PRB twins (link adaptation) */
-  int64_t grid_stride_prb = 0;
-  int32_t cqi_mode = RS_CQI_NONE;
-  unsigned long long* d_cqi_bad = nullptr; /* rs_pack_cqi_kernel's error word: all ones, or the lowest source byte outside 1..15 << 8 | its value */
-  bool cqi_bad_armed = false;              /* the word is all ones, or a pack has written it: nothing to clear ahead of the next pack */
-  int32_t* d_err = nullptr;
-  unsigned long long* d_slice_bytes = nullptr;
-  unsigned long long* d_stamps = nullptr;
+  /* Device memory: every array is a DevBuf (rs_devmem.h), which frees itself with the batch and knows its size -- a size is written
+   * once, where the array is made (batch_alloc and the setters), and read from the buffer everywhere else. */
+  DevBuf<double> d_gen_num; /* [S][16] pow(kbps[cqi], algo_epsilon[s]), host libm */
+  DevBuf<int32_t> d_alpha, d_beta;
+  DevBuf<RsTables> d_tab;
+  DevBuf<double> d_weight;
+  DevBuf<int32_t> d_eps, d_psi;
+  DevBuf<uint8_t> d_user_slice;
+  DevBuf<int32_t> d_tbs_eff;
+  DevBuf<double> d_avg;           /* [cells][U], as d_tx, d_cumb, d_cumr */
+  DevBuf<int32_t> d_tx;
+  DevBuf<int64_t> d_cumb, d_cumr;
+  DevBuf<double> d_sstate;        /* [cells][S] */
+  DevBuf<RsCellScalars> d_scal;   /* [cells] */
+  /* The CQI source: which kind the batch reads, its arrays and their numbers.  A setter validates on the host, clears the record,
+   * allocates and fills, and names the mode last (cqi_replace): the old grids go before the new ones are asked for -- they are the
+   * batch's largest allocation --, and a failure on the way leaves no source, never a mode whose arrays are missing. */
+  struct CqiSource {
+    int32_t mode = RS_CQI_NONE;
+    DevBuf<uint8_t> epochs, epochs_prb, trace, trace_prb; /* epoch grids / trace tables; _prb: the per-PRB twins (link adaptation) */
+    DevBuf<int32_t> user_trace;
+    int64_t grid_stride = 0, grid_stride_prb = 0;
+    int32_t n_epochs = 0, n_traces = 0, n_rows = 0, row_mod = 0;
+    void clear() { *this = CqiSource(); } /* no source: the arrays released, the numbers zero */
+  } cqi;
+  DevBuf<unsigned long long> d_cqi_bad; /* rs_pack_cqi_kernel's error word: all ones, or the lowest source byte outside 1..15 << 8 | its value */
+  bool cqi_bad_armed = false;           /* the word is all ones, or a pack has written it: nothing to clear ahead of the next pack */
+  DevBuf<int32_t> d_err;
+  DevBuf<uint64_t> d_slice_bytes;
+  DevBuf<unsigned long long> d_stamps;
   /* finite queues (rs_batch_set_bearers / rs_batch_set_arrivals) */
   bool queues = false;
   int qmode = 2;             /* rs_carve's `queue` argument once the queue model is on: 2 = bearers' hot words in LDS when they fit, 3 = in HBM */
-  uint8_t* d_bearer_kind = nullptr;
-  int64_t* d_arr_off = nullptr;
-  double* d_arr_time = nullptr;
-  int32_t *d_arr_nfull = nullptr, *d_arr_last = nullptr;
-  int32_t* d_qi = nullptr;   /* 7 arrays [cells][2][U]: head, tail, pk, frag, bytes, pkts, tx */
-  double* d_bavg = nullptr;  /* [cells][2][U] */
-  int64_t* d_bcum = nullptr; /* 2 arrays [cells][2][U]: bytes, rbs */
-  uint8_t* d_qflags = nullptr;
-  double* d_qhol = nullptr;
+  DevBuf<uint8_t> d_bearer_kind;
+  DevBuf<int64_t> d_arr_off;
+  DevBuf<double> d_arr_time;
+  DevBuf<int32_t> d_arr_nfull, d_arr_last;
+  DevBuf<int32_t> d_qi;   /* 7 arrays [cells][2][U]: head, tail, pk, frag, bytes, pkts, tx (plane()) */
+  DevBuf<double> d_bavg;  /* [cells][2][U] */
+  DevBuf<int64_t> d_bcum; /* 2 arrays [cells][2][U]: bytes, rbs */
+  DevBuf<uint8_t> d_qflags;
+  DevBuf<double> d_qhol;
   /* the flow completion record, one entry per arrival burst (rs_batch_flow_record): output, not state -- not in a checkpoint */
-  int32_t* d_flow_tti = nullptr;
-  double* d_flow_time = nullptr;
-  size_t n_bursts = 0;
+  DevBuf<int32_t> d_flow_tti;
+  DevBuf<double> d_flow_time;
   /* bearer records (rs_batch_run_records): [n_cells][cap] records, then n_cells count words; grows, never shrinks.  Output, not state. */
-  void* d_recs = nullptr;
-  size_t recs_bytes = 0;
+  DevBuf<char> d_recs;
   /* The run-time builds of the batch's kernel (owned by the process-wide cache), one record per build: the general build (batch_new;
    * replaced by the commits of rs_batch_set_cell_configs and rs_batch_set_bearers, reset_builds), its lean build, compiled at the
    * first launch that can use it (lean_kernel), and the records variants of the two (-DRS_JIT_RECORDS=1; rs_batch_run_grant_records),
@@ -323,7 +325,7 @@ struct rs_batch {
   char selfcheck_msg[160] = "";
   int autotune_n = 0;
   char autotune_msg[768] = "";
-  unsigned long long* d_prio_sum = nullptr; /* TTIs done by all cells of the running launch (the cells' issue-priority feedback) */
+  DevBuf<unsigned long long> d_prio_sum; /* TTIs done by all cells of the running launch (the cells' issue-priority feedback) */
   bool jit_wanted = false;
   char jit_msg[512] = ""; /* why the shape-specialised kernel is not in use (empty: it is, or it was not asked for) */
   int64_t ttis_done = 0;
@@ -336,10 +338,10 @@ struct rs_batch {
   std::vector<int32_t> cc_users;               /* [cells]: the row's users before the absent suffix (U where there is none) */
   bool ragged_slices = false;                  /* some cell has fewer slices than the batch (rs_batch_set_cell_configs_n) */
   std::vector<int32_t> cc_slices;              /* [cells]: the cell's slice count S_c (S where none was given) */
-  double* d_cc_weight = nullptr;
-  int32_t *d_cc_eps = nullptr, *d_cc_psi = nullptr;
-  uint8_t* d_cc_user_slice = nullptr;
-  long long* d_totals = nullptr;               /* rs_batch_slice_totals: [2][cells][S] */
+  DevBuf<double> d_cc_weight;
+  DevBuf<int32_t> d_cc_eps, d_cc_psi;
+  DevBuf<uint8_t> d_cc_user_slice;
+  DevBuf<long long> d_totals;                  /* rs_batch_slice_totals: [2][cells][S] */
   RsLaunch base{};
 };
 
@@ -473,8 +475,36 @@ int init_scalars(rs_batch* b, const uint32_t* seed, const int64_t* skip) {
     s.rng_f = g.f;
     s.rng_b = g.b;
   }
-  HIP_TRY(hipMemcpy(b->d_scal, sc.data(), sizeof(RsCellScalars) * b->n_cells, hipMemcpyHostToDevice));
+  HIP_TRY(b->d_scal.upload(sc.data()));
   return RS_OK;
+}
+/* the cells' scalar records as the device holds them now (the caller has waited for the stream) */
+int read_scalars(const rs_batch* b, std::vector<RsCellScalars>* sc) {
+  sc->resize(b->d_scal.count());
+  HIP_TRY(b->d_scal.download(sc->data()));
+  return RS_OK;
+}
+
+/* the device's compute units; 256 (an MI355X) where the runtime does not say */
+int device_cus(int device) {
+  hipDeviceProp_t prop;
+  return hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+}
+
+/* the k-th [cells][2][U] array of a queue-model block that holds several (d_qi, d_bcum): each is as long as d_bavg, which holds one */
+template <typename T>
+T* plane(const rs_batch* b, const DevBuf<T>& block, int k) { return block.get() + (size_t)k * b->d_bavg.count(); }
+
+/* The one sequence of the six CQI setters (rs_batch::CqiSource).  A setter has validated its arguments on the host.  Then: the old
+ * source goes, whatever its kind; `fill` allocates the new arrays and writes them and their numbers; the mode is named last.  Any
+ * failure of `fill` clears again: the batch has no source and launch() refuses with "no CQI source set". */
+template <typename Fill>
+int cqi_replace(rs_batch* b, int32_t mode, Fill fill) {
+  b->cqi.clear();
+  const int rc = fill(b->cqi);
+  if (rc) b->cqi.clear();
+  else b->cqi.mode = mode;
+  return rc;
 }
 
 int batch_alloc(rs_batch* b) {
@@ -510,22 +540,15 @@ int batch_alloc(rs_batch* b) {
    * In the as-shipped -O0 build McsToItbs[29] sits 128 bytes in front of the table, so
    * T[-1][i] = McsToItbs[5+i] for i <= 23 and 0 (padding) beyond. */
   for (int i = 0; i < 27; i++) t.tbs_row_m1[i] = i <= 23 ? kMcsToItbs[5 + i] : 0;
-  HIP_TRY(hipMalloc(&b->d_tab, sizeof t));
-  HIP_TRY(hipMemcpy(b->d_tab, &t, sizeof t, hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&b->d_weight, 8 * S));
-  HIP_TRY(hipMemcpy(b->d_weight, b->weight.data(), 8 * S, hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&b->d_eps, 4 * S));
-  HIP_TRY(hipMemcpy(b->d_eps, b->eps.data(), 4 * S, hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&b->d_psi, 4 * S));
-  HIP_TRY(hipMemcpy(b->d_psi, b->psi.data(), 4 * S, hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&b->d_alpha, 4 * S));
-  HIP_TRY(hipMemcpy(b->d_alpha, b->alpha.data(), 4 * S, hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&b->d_beta, 4 * S));
-  HIP_TRY(hipMemcpy(b->d_beta, b->beta.data(), 4 * S, hipMemcpyHostToDevice));
+  HIP_TRY(b->d_tab.assign(&t, 1));
+  HIP_TRY(b->d_weight.assign(b->weight.data(), S));
+  HIP_TRY(b->d_eps.assign(b->eps.data(), S));
+  HIP_TRY(b->d_psi.assign(b->psi.data(), S));
+  HIP_TRY(b->d_alpha.assign(b->alpha.data(), S));
+  HIP_TRY(b->d_beta.assign(b->beta.data(), S));
   std::vector<uint8_t> us(U);
   for (size_t u = 0; u < U; u++) us[u] = (uint8_t)b->u2s[u];
-  HIP_TRY(hipMalloc(&b->d_user_slice, U));
-  HIP_TRY(hipMemcpy(b->d_user_slice, us.data(), U, hipMemcpyHostToDevice));
+  HIP_TRY(b->d_user_slice.assign(us.data(), U));
   {
     /* TBS bits of n RBGs = n*G PRBs per itbs (AMCModule.cpp:306-317); row 0 unused.  The device gets them with the CQI -> MCS -> I_TBS
      * step folded in, [R+1][16] indexed by final CQI: the kernel's LDS table is then a straight copy (round 6: the two dependent loads
@@ -544,8 +567,7 @@ int batch_alloc(rs_batch* b) {
     std::vector<int32_t> te16((size_t)(b->R + 1) * 16, 0);
     for (int n = 0; n <= b->R; n++)
       for (int c = 0; c < 16; c++) te16[(size_t)n * 16 + c] = te[(size_t)n * 27 + t.itbs_of_cqi[c]];
-    HIP_TRY(hipMalloc(&b->d_tbs_eff, 4 * te16.size()));
-    HIP_TRY(hipMemcpy(b->d_tbs_eff, te16.data(), 4 * te16.size(), hipMemcpyHostToDevice));
+    HIP_TRY(b->d_tbs_eff.assign(te16.data(), te16.size()));
   }
   if (b->gen_exp) {
     /* ref: downlink-transport-scheduler.cpp:688-693  pow(spectralEfficiency * 180000 / 1000, epsilon), with this host's libm --
@@ -553,28 +575,20 @@ int batch_alloc(rs_batch* b) {
     std::vector<double> gn((size_t)S * 16, 0.0);
     for (size_t s = 0; s < S; s++)
       for (int c = 1; c <= 15; c++) gn[s * 16 + c] = pow(t.kbps[c], b->eps[s]);
-    HIP_TRY(hipMalloc(&b->d_gen_num, 8 * gn.size()));
-    HIP_TRY(hipMemcpy(b->d_gen_num, gn.data(), 8 * gn.size(), hipMemcpyHostToDevice));
+    HIP_TRY(b->d_gen_num.assign(gn.data(), gn.size()));
   }
-  HIP_TRY(hipMalloc(&b->d_avg, 8 * cells * U));
-  HIP_TRY(hipMalloc(&b->d_tx, 4 * cells * U));
-  HIP_TRY(hipMalloc(&b->d_cumb, 8 * cells * U));
-  HIP_TRY(hipMalloc(&b->d_cumr, 8 * cells * U));
-  HIP_TRY(hipMalloc(&b->d_sstate, 8 * cells * S));
-  HIP_TRY(hipMalloc(&b->d_scal, sizeof(RsCellScalars) * cells));
-  HIP_TRY(hipMalloc(&b->d_err, 4));
-  HIP_TRY(hipMalloc(&b->d_slice_bytes, 8 * 64));
-  HIP_TRY(hipMemset(b->d_err, 0, 4));
+  const std::vector<double> avg(cells * U, 100000.0); /* radio-bearer.cpp:54 */
+  HIP_TRY(b->d_avg.assign(avg.data(), cells * U));
+  HIP_TRY(b->d_tx.alloc_zeroed(cells * U));
+  HIP_TRY(b->d_cumb.alloc_zeroed(cells * U));
+  HIP_TRY(b->d_cumr.alloc_zeroed(cells * U));
+  HIP_TRY(b->d_sstate.alloc_zeroed(cells * S));
+  HIP_TRY(b->d_scal.alloc(cells));
+  HIP_TRY(b->d_err.alloc_zeroed(1));
+  HIP_TRY(b->d_slice_bytes.alloc(64));
 #ifdef RS_STAMPS
-  HIP_TRY(hipMalloc(&b->d_stamps, 8 * 20 * (size_t)b->n_cells));
-  HIP_TRY(hipMemset(b->d_stamps, 0, 8 * 20 * (size_t)b->n_cells));
+  HIP_TRY(b->d_stamps.alloc_zeroed(20 * cells));
 #endif
-  std::vector<double> avg(cells * U, 100000.0); /* radio-bearer.cpp:54 */
-  HIP_TRY(hipMemcpy(b->d_avg, avg.data(), 8 * cells * U, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(b->d_tx, 0, 4 * cells * U));
-  HIP_TRY(hipMemset(b->d_cumb, 0, 8 * cells * U));
-  HIP_TRY(hipMemset(b->d_cumr, 0, 8 * cells * U));
-  HIP_TRY(hipMemset(b->d_sstate, 0, 8 * cells * S));
   rc = init_scalars(b, nullptr, nullptr);
   if (rc) return rc;
 
@@ -599,15 +613,12 @@ int batch_alloc(rs_batch* b) {
     /* co-resident cells take turns at the issue priority (RS_SETPRIO, rs_kernels.hip) when the batch has more cells than the device has
      * compute units -- the second dispatch round shares its CUs with the first, which would win every tie by age.  RS_PRIO_BALANCE=0 / 1
      * overrides. */
-    hipDeviceProp_t prop;
-    int cus = 256;
-    if (hipGetDeviceProperties(&prop, b->cfg.cell.device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
+    const int cus = device_cus(b->cfg.cell.device);
     int mode = (!b->direct && b->n_cells > cus) ? 2 : 0; /* 2: feedback through a progress sum (rs_kernels.hip), 1: time windows, 0: off */
     if (const char* e = getenv("RS_PRIO_BALANCE")) mode = b->direct ? 0 : atoi(e);
     L.prio_round_cells = mode == 1 ? cus : 0;
     if (mode == 2) {
-      HIP_TRY(hipMalloc(&b->d_prio_sum, 8));
-      HIP_TRY(hipMemset(b->d_prio_sum, 0, 8));
+      HIP_TRY(b->d_prio_sum.alloc_zeroed(1));
       L.prio_sum = b->d_prio_sum;
     }
   }
@@ -625,11 +636,7 @@ rs_batch* batch_new(const rs_batch_config* cfg, bool direct) {
   if (threads == 0) {
     /* default: 512 threads per cell while the batch leaves at most ~2 cells per CU (per-level latency
      * matters), 256 (two array positions per lane, fewer instructions per level) once 4+ cells share a CU */
-    hipDeviceProp_t prop;
-    int cus = 256;
-    if (hipGetDeviceProperties(&prop, cfg->cell.device) == hipSuccess && prop.multiProcessorCount > 0)
-      cus = prop.multiProcessorCount;
-    threads = (!direct && cfg->n_cells >= 4 * cus) ? 256 : 512;
+    threads = (!direct && cfg->n_cells >= 4 * device_cus(cfg->cell.device)) ? 256 : 512;
   }
   int want_jit = cfg->jit;
   if (const char* e = getenv("RS_JIT")) want_jit = atoi(e);
@@ -702,9 +709,9 @@ rs_batch* batch_new(const rs_batch_config* cfg, bool direct) {
 int check_device_err(rs_batch* b) {
   int e = 0;
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  HIP_TRY(hipMemcpy(&e, b->d_err, 4, hipMemcpyDeviceToHost));
+  HIP_TRY(b->d_err.download(&e));
   if (e) {
-    HIP_TRY(hipMemset(b->d_err, 0, 4));
+    HIP_TRY(b->d_err.zero());
     return fail(RS_ERR_RANGE, e == RS_CQI_EPOCHS ? "ran past the last CQI epoch" : "trace row outside the uploaded rows");
   }
   return RS_OK;
@@ -721,7 +728,7 @@ bool lean_qualifies(const rs_batch* b, int n_ttis, bool logged) {
   const char* const e_on = getenv("RS_JIT_LEAN");
   const int lean_min = e_min ? atoi(e_min) : 256;
   if (e_on && atoi(e_on) == 0) return false;
-  return !(n_ttis < lean_min || b->cqi_mode != RS_CQI_EPOCHS || b->d_epochs_prb || b->cfg.phy_error_draws || b->synthetic);
+  return !(n_ttis < lean_min || b->cqi.mode != RS_CQI_EPOCHS || b->cqi.epochs_prb || b->cfg.phy_error_draws || b->synthetic);
 }
 RsJitKernel* lean_kernel(rs_batch* b, int n_ttis, bool logged) {
   if (!lean_qualifies(b, n_ttis, logged)) return nullptr;
@@ -762,18 +769,13 @@ int records_kernel(rs_batch* b, int n_ttis, RsJitKernel** k, int* slot);
 /* Everything a batch carries from one launch to the next, as (device pointer, bytes): PF averages, pending grants, cumulative counters,
  * slice state, clock / rand() ring / CQI-report state, and with the queue model the bearers' queues, averages, counters and per-user
  * words.  One list for the checkpoint (rs_batch_checkpoint_*), the autotune's snapshot and the self-check's. */
-struct StatePart { void* p; size_t n; };
-std::vector<StatePart> state_parts(rs_batch* b) {
-  const size_t cells = b->n_cells, U = b->U, S = b->S, n2 = cells * 2 * U;
-  std::vector<StatePart> v = {{b->d_avg, 8 * cells * U}, {b->d_tx, 4 * cells * U}, {b->d_cumb, 8 * cells * U}, {b->d_cumr, 8 * cells * U},
-                              {b->d_sstate, 8 * cells * S}, {b->d_scal, sizeof(RsCellScalars) * cells}};
-  if (b->queues) {
-    v.push_back({b->d_qi, 4 * 7 * n2});
-    v.push_back({b->d_bavg, 8 * n2});
-    v.push_back({b->d_bcum, 8 * 2 * n2});
-    v.push_back({b->d_qflags, cells * U});
-    v.push_back({b->d_qhol, 8 * cells * U});
-  }
+struct StatePart {
+  void* p; size_t n;
+  template <typename T> StatePart(const DevBuf<T>& d) : p(d.get()), n(d.bytes()) {} /* a whole array, as the buffer has it */
+};
+std::vector<StatePart> state_parts(rs_batch* b) { /* (the order is the checkpoint's format) */
+  std::vector<StatePart> v = {b->d_avg, b->d_tx, b->d_cumb, b->d_cumr, b->d_sstate, b->d_scal};
+  if (b->queues) v.insert(v.end(), {b->d_qi, b->d_bavg, b->d_bcum, b->d_qflags, b->d_qhol});
   return v;
 }
 
@@ -783,10 +785,7 @@ struct StateParts {
   size_t total = 0;
   /* with_record: the flow completion record too (the self-check's trials write it; it is output, so the checkpoint leaves it out) */
   explicit StateParts(rs_batch* b, bool with_record = false) : parts(state_parts(b)) {
-    if (with_record && b->queues && b->d_flow_tti) {
-      parts.push_back({b->d_flow_tti, 4 * b->n_bursts});
-      parts.push_back({b->d_flow_time, 8 * b->n_bursts});
-    }
+    if (with_record && b->queues && b->d_flow_tti) parts.insert(parts.end(), {b->d_flow_tti, b->d_flow_time});
     for (const StatePart& q : parts) total += (q.n + 255) & ~(size_t)255;
   }
   hipError_t copy(rs_batch* b, void* snapshot, bool save) const {
@@ -819,27 +818,28 @@ struct StateDigest {
   }
 };
 int state_digest(rs_batch* b, StateDigest* out) {
-  const size_t cells = b->n_cells, U = b->U, S = b->S;
   HIP_TRY(hipStreamSynchronize(b->stream));
-  std::vector<unsigned char> h(8 * cells * U);
   auto fnv = [](const void* p, size_t n, unsigned long long d = 1469598103934665603ull) {
     const unsigned char* c = (const unsigned char*)p;
     for (size_t i = 0; i < n; i++) { d ^= c[i]; d *= 1099511628211ull; }
     return d;
   };
-  int k = 0;
-  for (void* dev : {(void*)b->d_avg, (void*)b->d_cumb, (void*)b->d_cumr}) {
-    HIP_TRY(hipMemcpy(h.data(), dev, 8 * cells * U, hipMemcpyDeviceToHost));
-    out->part[k++] = fnv(h.data(), 8 * cells * U);
-  }
-  HIP_TRY(hipMemcpy(h.data(), b->d_sstate, 8 * cells * S, hipMemcpyDeviceToHost));
-  out->part[3] = fnv(h.data(), 8 * cells * S);
-  std::vector<int32_t> tx(cells * U);
-  HIP_TRY(hipMemcpy(tx.data(), b->d_tx, 4 * cells * U, hipMemcpyDeviceToHost));
+  std::vector<unsigned char> h;
+  const auto whole = [&](const StatePart& q, unsigned long long* d) -> int { /* one array, as it is */
+    h.resize(q.n);
+    HIP_TRY(hipMemcpy(h.data(), q.p, q.n, hipMemcpyDeviceToHost));
+    *d = fnv(h.data(), q.n);
+    return RS_OK;
+  };
+  const StatePart plain[4] = {b->d_avg, b->d_cumb, b->d_cumr, b->d_sstate};
+  for (int i = 0; i < 4; i++)
+    if (const int rc = whole(plain[i], &out->part[i])) return rc;
+  std::vector<int32_t> tx(b->d_tx.count());
+  HIP_TRY(b->d_tx.download(tx.data()));
   for (int32_t& v : tx) v &= RS_TX_BYTES_MASK;
-  out->part[4] = fnv(tx.data(), 4 * cells * U);
-  std::vector<RsCellScalars> sc(cells);
-  HIP_TRY(hipMemcpy(sc.data(), b->d_scal, sizeof(RsCellScalars) * cells, hipMemcpyDeviceToHost));
+  out->part[4] = fnv(tx.data(), 4 * tx.size());
+  std::vector<RsCellScalars> sc;
+  if (const int rc = read_scalars(b, &sc)) return rc;
   for (int i = 5; i < 10; i++) out->part[i] = 1469598103934665603ull;
   for (const RsCellScalars& c : sc) {
     out->part[5] = fnv(&c.t, 8, out->part[5]);
@@ -848,7 +848,7 @@ int state_digest(rs_batch* b, StateDigest* out) {
     /* (read by the error model's draws only: a lean build, which serves batches without them, does not keep it) */
     if (b->cfg.phy_error_draws) out->part[8] = fnv(&c.served_prev, 4, out->part[8]);
     unsigned long long d = out->part[9];
-    if (b->cqi_mode == RS_CQI_TRACE) { d = fnv(&c.last_sent, 8, d); d = fnv(&c.reported, 4, d); d = fnv(&c.cqi_row, 4, d); }
+    if (b->cqi.mode == RS_CQI_TRACE) { d = fnv(&c.last_sent, 8, d); d = fnv(&c.reported, 4, d); d = fnv(&c.cqi_row, 4, d); }
     /* the ring in age order: the kernels may leave it rotated differently (f, b) with the same future */
     for (int i = 0; i < 31; i++) { const uint32_t w = c.rng_r[(c.rng_f + i) % 31]; d = fnv(&w, 4, d); }
     out->part[9] = d;
@@ -856,17 +856,13 @@ int state_digest(rs_batch* b, StateDigest* out) {
   if (b->queues) {
     /* the queue model: head, tail, pk, frag, bytes, pkts, tx of every bearer; its PF average; its cumulative bytes / RBs.  (The per-user
      * flag and HoL words are rebuilt by every TTI's first phase before anything reads them: scratch, not compared.) */
-    const size_t n2 = cells * 2 * U;
-    const StatePart q[3] = {{b->d_qi, 4 * 7 * n2}, {b->d_bavg, 8 * n2}, {b->d_bcum, 8 * 2 * n2}};
-    for (int i = 0; i < 3; i++) {
-      std::vector<unsigned char> hq(q[i].n);
-      HIP_TRY(hipMemcpy(hq.data(), q[i].p, q[i].n, hipMemcpyDeviceToHost));
-      out->part[10 + i] = fnv(hq.data(), q[i].n);
-    }
+    const StatePart q[3] = {b->d_qi, b->d_bavg, b->d_bcum};
+    for (int i = 0; i < 3; i++)
+      if (const int rc = whole(q[i], &out->part[10 + i])) return rc;
     if (b->d_flow_tti) { /* the record: TTI indices and clock values of the completed flows */
-      std::vector<unsigned char> hr(12 * b->n_bursts);
-      HIP_TRY(hipMemcpy(hr.data(), b->d_flow_tti, 4 * b->n_bursts, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(hr.data() + 4 * b->n_bursts, b->d_flow_time, 8 * b->n_bursts, hipMemcpyDeviceToHost));
+      std::vector<unsigned char> hr(b->d_flow_tti.bytes() + b->d_flow_time.bytes());
+      HIP_TRY(b->d_flow_tti.download(hr.data()));
+      HIP_TRY(b->d_flow_time.download(hr.data() + b->d_flow_tti.bytes()));
       out->part[13] = fnv(hr.data(), hr.size());
     }
   }
@@ -880,11 +876,11 @@ int state_digest(rs_batch* b, StateDigest* out) {
  * grant before the launch ends): nothing to convert there. */
 int convert_tx(rs_batch* b, bool to_packed) {
   if (b->queues) return RS_OK;
-  std::vector<int32_t> tx((size_t)b->n_cells * b->U);
-  if (hipStreamSynchronize(b->stream) != hipSuccess || hipMemcpy(tx.data(), b->d_tx, 4 * tx.size(), hipMemcpyDeviceToHost) != hipSuccess)
+  std::vector<int32_t> tx(b->d_tx.count());
+  if (hipStreamSynchronize(b->stream) != hipSuccess || b->d_tx.download(tx.data()) != hipSuccess)
     return fail(RS_ERR_HIP, "copy of the pending grants failed");
   for (int32_t& w : tx) w = to_packed ? (w ? ((w & RS_TX_BYTES_MASK) | RS_TX_COUNTED) : 0) : (w & RS_TX_BYTES_MASK);
-  if (hipMemcpy(b->d_tx, tx.data(), 4 * tx.size(), hipMemcpyHostToDevice) != hipSuccess) return fail(RS_ERR_HIP, "copy of the pending grants failed");
+  if (b->d_tx.upload(tx.data()) != hipSuccess) return fail(RS_ERR_HIP, "copy of the pending grants failed");
   return RS_OK;
 }
 
@@ -1274,7 +1270,7 @@ int records_kernel(rs_batch* b, int n_ttis, RsJitKernel** k, int* slot) {
 int launch(rs_batch* b, const LaunchReq& rq) {
   const int n_ttis = rq.n_ttis;
   if (n_ttis < 1) return fail(RS_ERR_INVALID, "n_ttis %d < 1", n_ttis);
-  if (b->cqi_mode == RS_CQI_NONE) return fail(RS_ERR_STATE, "no CQI source set");
+  if (b->cqi.mode == RS_CQI_NONE) return fail(RS_ERR_STATE, "no CQI source set");
   if (b->any_alpha && !b->direct && !b->queues)
     return fail(RS_ERR_STATE, "customised slices (algo_alpha = 1) read queue state: call rs_batch_set_bearers / rs_batch_set_arrivals first");
   if (b->queues && !b->d_arr_off) return fail(RS_ERR_STATE, "rs_batch_set_arrivals has not been called");
@@ -1292,21 +1288,21 @@ int launch(rs_batch* b, const LaunchReq& rq) {
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   RsLaunch L = b->base;
   L.n_ttis = n_ttis;
-  L.cqi_mode = b->cqi_mode;
-  L.epochs = b->d_epochs; L.grid_stride = b->grid_stride; L.n_epochs = b->n_epochs;
-  L.trace = b->d_trace; L.n_traces = b->n_traces; L.n_rows = b->n_rows; L.row_mod = b->row_mod;
-  L.user_trace = b->d_user_trace;
-  L.epochs_prb = b->cqi_mode == RS_CQI_EPOCHS ? b->d_epochs_prb : nullptr; L.grid_stride_prb = b->grid_stride_prb;
-  L.trace_prb = b->cqi_mode == RS_CQI_TRACE ? b->d_trace_prb : nullptr;
+  const rs_batch::CqiSource& q = b->cqi; /* (a batch holds the arrays of the kind it reads and no others: the rest are null) */
+  L.cqi_mode = q.mode;
+  L.epochs = q.epochs; L.grid_stride = q.grid_stride; L.n_epochs = q.n_epochs;
+  L.trace = q.trace; L.n_traces = q.n_traces; L.n_rows = q.n_rows; L.row_mod = q.row_mod;
+  L.user_trace = q.user_trace;
+  L.epochs_prb = q.epochs_prb; L.grid_stride_prb = q.grid_stride_prb;
+  L.trace_prb = q.trace_prb;
   L.log_map = rq.map; L.log_quota = rq.quota; L.log_target = rq.target; L.log_tbs = rq.tbs; L.log_uinfo = rq.uinfo;
   L.log_keys = rq.keys;
   if (b->queues) {
-    const size_t n = (size_t)b->n_cells * 2 * b->U;
     L.bearer_kind = b->d_bearer_kind; L.arr_off = b->d_arr_off; L.arr_time = b->d_arr_time;
     L.arr_nfull = b->d_arr_nfull; L.arr_last = b->d_arr_last;
-    L.q_head = b->d_qi; L.q_tail = b->d_qi + n; L.q_pk = b->d_qi + 2 * n; L.q_frag = b->d_qi + 3 * n;
-    L.q_bytes = b->d_qi + 4 * n; L.q_pkts = b->d_qi + 5 * n; L.b_tx = b->d_qi + 6 * n;
-    L.b_avg = b->d_bavg; L.b_cumb = b->d_bcum; L.b_cumr = b->d_bcum + n;
+    L.q_head = plane(b, b->d_qi, 0); L.q_tail = plane(b, b->d_qi, 1); L.q_pk = plane(b, b->d_qi, 2); L.q_frag = plane(b, b->d_qi, 3);
+    L.q_bytes = plane(b, b->d_qi, 4); L.q_pkts = plane(b, b->d_qi, 5); L.b_tx = plane(b, b->d_qi, 6);
+    L.b_avg = b->d_bavg; L.b_cumb = plane(b, b->d_bcum, 0); L.b_cumr = plane(b, b->d_bcum, 1);
     L.q_flags = b->d_qflags; L.q_hol = b->d_qhol;
     L.flow_tti = b->d_flow_tti; L.flow_time = b->d_flow_time;
     L.log_bbytes = rq.bbytes; L.log_bhol = rq.bhol;
@@ -1376,15 +1372,9 @@ rs_batch* rs_batch_create_checked(const rs_batch_config* cfg, int abi_version, s
 void rs_batch_destroy(rs_batch* b) {
   if (!b) return;
   if (b->stream) (void)hipStreamSynchronize(b->stream);
-  void* ptrs[] = {b->d_tab, b->d_weight, b->d_eps, b->d_psi, b->d_alpha, b->d_beta, b->d_user_slice, b->d_tbs_eff, b->d_avg, b->d_tx, b->d_cumb, b->d_cumr,
-                  b->d_sstate, b->d_scal, b->d_epochs, b->d_trace, b->d_user_trace, b->d_err, b->d_slice_bytes, b->d_stamps,
-                  b->d_bearer_kind, b->d_arr_off, b->d_arr_time, b->d_arr_nfull, b->d_arr_last, b->d_qi, b->d_bavg, b->d_bcum,
-                  b->d_qflags, b->d_qhol, b->d_flow_tti, b->d_flow_time, b->d_epochs_prb, b->d_trace_prb, b->d_gen_num, b->d_prio_sum,
-                  b->d_recs, b->d_cc_weight, b->d_cc_eps, b->d_cc_psi, b->d_cc_user_slice, b->d_totals, b->d_cqi_bad};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  if (b->own_stream && b->stream) (void)hipStreamDestroy(b->stream);
-  delete b;
+  const hipStream_t own = b->own_stream ? b->stream : nullptr;
+  delete b; /* every device array frees itself here (DevBuf), ahead of the stream as before */
+  if (own) (void)hipStreamDestroy(own);
 }
 
 int rs_batch_seed(rs_batch* b, const uint32_t* seed, const int64_t* rand_skip) {
@@ -1454,8 +1444,8 @@ int rs_batch_set_cell_configs_n(rs_batch* b, const int32_t* cell_slices, const d
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   HIP_TRY(hipStreamSynchronize(b->stream));
   { /* the slice state the cells hold now (zeros, or what rs_batch_write_state put there) against each cell's new weights */
-    std::vector<double> st(cells * S);
-    HIP_TRY(hipMemcpy(st.data(), b->d_sstate, 8 * cells * S, hipMemcpyDeviceToHost));
+    std::vector<double> st(b->d_sstate.count());
+    HIP_TRY(b->d_sstate.download(st.data()));
     for (size_t c = 0; c < cells; c++)
       if (const int rc = check_slice_state(b, st.data() + c * S, c, w.data() + c * S, ns[c])) return rc;
   }
@@ -1476,23 +1466,19 @@ int rs_batch_set_cell_configs_n(rs_batch* b, const int32_t* cell_slices, const d
     else if (!cmsg[0]) snprintf(cmsg, sizeof cmsg, "hiprtc build of the kernel with per-cell configurations failed");
     if (!cjit && b->threads > 512) return fail(RS_ERR_INVALID, "threads_per_cell %d needs the shape-specialised kernel with per-cell configurations: %s", b->threads, cmsg);
   }
-  if (!b->d_cc_weight) {
-    HIP_TRY(hipMalloc(&b->d_cc_weight, 8 * cells * S));
-    HIP_TRY(hipMalloc(&b->d_cc_eps, 4 * cells * S));
-    HIP_TRY(hipMalloc(&b->d_cc_psi, 4 * cells * S));
-    HIP_TRY(hipMalloc(&b->d_cc_user_slice, cells * U));
-  }
+  /* the four rows, all or none; a later call writes into them */
+  if (!b->d_cc_weight) HIP_TRY(dev_alloc_all(b->d_cc_weight, cells * S, b->d_cc_eps, cells * S, b->d_cc_psi, cells * S, b->d_cc_user_slice, cells * U));
   std::vector<uint8_t> us8(cells * U);
   for (size_t i = 0; i < cells * U; i++) us8[i] = us[i] == RS_USER_ABSENT ? (uint8_t)RS_SLICE_ABSENT : (uint8_t)us[i];
-  HIP_TRY(hipMemcpy(b->d_cc_weight, w.data(), 8 * cells * S, hipMemcpyHostToDevice));
+  HIP_TRY(b->d_cc_weight.upload(w.data()));
   { /* the device row of eps carries the cell's slice count: RS_EPS_ABSENT from slice S_c on (the host row keeps what was given) */
     std::vector<int32_t> ed(e);
     for (size_t c = 0; c < cells; c++)
       for (size_t k = (size_t)ns[c]; k < S; k++) ed[c * S + k] = RS_EPS_ABSENT;
-    HIP_TRY(hipMemcpy(b->d_cc_eps, ed.data(), 4 * cells * S, hipMemcpyHostToDevice));
+    HIP_TRY(b->d_cc_eps.upload(ed.data()));
   }
-  HIP_TRY(hipMemcpy(b->d_cc_psi, ps.data(), 4 * cells * S, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(b->d_cc_user_slice, us8.data(), cells * U, hipMemcpyHostToDevice));
+  HIP_TRY(b->d_cc_psi.upload(ps.data()));
+  HIP_TRY(b->d_cc_user_slice.upload(us8.data()));
   /* commit: rows, launch block, carve and kernels together */
   b->cc_weight.swap(w); b->cc_eps.swap(e); b->cc_psi.swap(ps); b->cc_u2s.swap(us); b->cc_users.swap(nu); b->cc_slices.swap(ns);
   b->cell_cfg = true;
@@ -1535,9 +1521,9 @@ int rs_batch_cell_slices(rs_batch* b, int32_t* n_slices) {
 int rs_batch_slice_totals(rs_batch* b, int64_t* cum_bytes, int64_t* cum_rbs) {
   if (!b) return fail(RS_ERR_INVALID, "null batch");
   if (b->direct) return fail(RS_ERR_INVALID, "slice totals: not a batch");
-  const size_t n = (size_t)b->n_cells * b->S;
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  if (!b->d_totals) HIP_TRY(hipMalloc(&b->d_totals, 8 * 2 * n));
+  if (!b->d_totals) HIP_TRY(b->d_totals.alloc(2 * b->d_sstate.count())); /* bytes and RBs, each [cells][S] */
+  const size_t n = b->d_totals.count() / 2;
   HIP_TRY(rs_launch_slice_totals(b->d_cumb, b->d_cumr, b->cell_cfg ? b->d_cc_user_slice : b->d_user_slice, b->cell_cfg ? b->U : 0, b->n_cells, b->U, b->S,
                                  b->d_totals, b->stream));
   HIP_TRY(hipStreamSynchronize(b->stream));
@@ -1546,28 +1532,41 @@ int rs_batch_slice_totals(rs_batch* b, int64_t* cum_bytes, int64_t* cum_rbs) {
   return RS_OK;
 }
 
-int rs_batch_upload_cqi_epochs(rs_batch* b, const uint8_t* h_cqi, int32_t n_epochs) {
-  if (!b || !h_cqi || n_epochs < 1) return fail(RS_ERR_INVALID, "bad argument");
+/* ---- the CQI source: six setters, one sequence (cqi_replace) ---- */
+
+/* the stride of one stored grid, the cell kernel's LDS image: RBG-major [R][Upad] with zero padding (a refresh is a straight copy) */
+static size_t grid_stride_of(const rs_batch* b) { return (size_t)round_up(rs_upad_of(b->U) * b->R, 16); }
+
+/* epoch grids from host memory [cells][n_epochs][U][R], and -- h_cqi_prb -- their per-PRB twin [cells][n_epochs][U][R * G] */
+static int upload_epochs(rs_batch* b, const uint8_t* h_cqi, int32_t n_epochs, const uint8_t* h_cqi_prb) {
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  const size_t grid = (size_t)b->U * b->R;
-  /* device-resident form = the cell kernel's LDS image: RBG-major [R][Upad] with zero padding (a refresh is a straight copy) */
-  const size_t Upad = (size_t)rs_upad_of(b->U);
-  const size_t stride = round_up((int)(Upad * b->R), 16);
+  const size_t grid = (size_t)b->U * b->R, Upad = (size_t)rs_upad_of(b->U), stride = grid_stride_of(b);
   const size_t total = (size_t)b->n_cells * n_epochs;
   for (size_t i = 0; i < total * grid; i++)
     if (h_cqi[i] < 1 || h_cqi[i] > 15) return fail(RS_ERR_INVALID, "CQI %d at byte %zu outside 1..15", h_cqi[i], i);
-  std::vector<uint8_t> packed(total * stride, 0);
+  std::vector<uint8_t> packed(total * stride, 0), packed_prb;
   for (size_t g = 0; g < total; g++)
     for (size_t u = 0; u < (size_t)b->U; u++)
       for (size_t r = 0; r < (size_t)b->R; r++) packed[g * stride + r * Upad + u] = h_cqi[g * grid + u * b->R + r];
-  if (b->d_epochs) { HIP_TRY(hipFree(b->d_epochs)); b->d_epochs = nullptr; }
-  HIP_TRY(hipMalloc(&b->d_epochs, packed.size()));
-  HIP_TRY(hipMemcpy(b->d_epochs, packed.data(), packed.size(), hipMemcpyHostToDevice));
-  b->grid_stride = (int64_t)stride;
-  b->n_epochs = n_epochs;
-  b->cqi_mode = RS_CQI_EPOCHS;
-  if (b->d_epochs_prb) { HIP_TRY(hipFree(b->d_epochs_prb)); b->d_epochs_prb = nullptr; }
-  return RS_OK;
+  const size_t grid_prb = grid * b->G, stride_prb = round_up((int)grid_prb, 16);
+  if (h_cqi_prb) {
+    packed_prb.assign(total * stride_prb, 0);
+    for (size_t g = 0; g < total; g++) memcpy(&packed_prb[g * stride_prb], h_cqi_prb + g * grid_prb, grid_prb);
+  }
+  return cqi_replace(b, RS_CQI_EPOCHS, [&](rs_batch::CqiSource& q) -> int {
+    HIP_TRY(q.epochs.assign(packed.data(), packed.size()));
+    q.grid_stride = (int64_t)stride;
+    q.n_epochs = n_epochs;
+    if (!h_cqi_prb) return RS_OK;
+    HIP_TRY(q.epochs_prb.assign(packed_prb.data(), packed_prb.size()));
+    q.grid_stride_prb = (int64_t)stride_prb;
+    return RS_OK;
+  });
+}
+
+int rs_batch_upload_cqi_epochs(rs_batch* b, const uint8_t* h_cqi, int32_t n_epochs) {
+  if (!b || !h_cqi || n_epochs < 1) return fail(RS_ERR_INVALID, "bad argument");
+  return upload_epochs(b, h_cqi, n_epochs, nullptr);
 }
 
 int rs_batch_upload_cqi_epochs_prb(rs_batch* b, const uint8_t* h_cqi_prb, int32_t n_epochs) {
@@ -1580,15 +1579,7 @@ int rs_batch_upload_cqi_epochs_prb(rs_batch* b, const uint8_t* h_cqi_prb, int32_
       for (size_t r = 0; r < (size_t)b->R; r++) rbg[(g * b->U + u) * b->R + r] = h_cqi_prb[g * grid + u * per_user + r * b->G];
   for (size_t i = 0; i < total * grid; i++)
     if (h_cqi_prb[i] < 1 || h_cqi_prb[i] > 15) return fail(RS_ERR_INVALID, "CQI %d at byte %zu outside 1..15", h_cqi_prb[i], i);
-  int rc = rs_batch_upload_cqi_epochs(b, rbg.data(), n_epochs);
-  if (rc) return rc;
-  const size_t stride = round_up((int)grid, 16);
-  std::vector<uint8_t> packed(total * stride, 0);
-  for (size_t g = 0; g < total; g++) memcpy(&packed[g * stride], h_cqi_prb + g * grid, grid);
-  HIP_TRY(hipMalloc(&b->d_epochs_prb, packed.size()));
-  HIP_TRY(hipMemcpy(b->d_epochs_prb, packed.data(), packed.size(), hipMemcpyHostToDevice));
-  b->grid_stride_prb = (int64_t)stride;
-  return RS_OK;
+  return upload_epochs(b, rbg.data(), n_epochs, h_cqi_prb);
 }
 
 int rs_batch_synthesize_cqi(rs_batch* b, uint64_t seed, const double* w, int32_t n_epochs) {
@@ -1613,32 +1604,28 @@ int rs_batch_synthesize_cqi_at(rs_batch* b, uint64_t seed, const double* w, int3
   }
   cdf[14] = 4294967295u;
   cdf[15] = 4294967295u;
-  const int Upad = rs_upad_of(b->U);
-  const size_t stride = round_up(Upad * b->R, 16); /* RBG-major [R][Upad]: the cell kernel's LDS image */
-  const size_t bytes = (size_t)b->n_cells * n_epochs * stride;
-  if (b->d_epochs) { HIP_TRY(hipFree(b->d_epochs)); b->d_epochs = nullptr; }
-  HIP_TRY(hipMalloc(&b->d_epochs, bytes));
-  HIP_TRY(rs_launch_synth(b->d_epochs, (int64_t)stride, b->n_cells, n_epochs, b->U, b->R, Upad, seed, first_cell, cdf, b->stream));
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  b->grid_stride = (int64_t)stride;
-  b->n_epochs = n_epochs;
-  b->cqi_mode = RS_CQI_EPOCHS;
-  /* the per-PRB twin of an earlier upload belongs to the grids just replaced (other epoch count, other values) */
-  if (b->d_epochs_prb) { HIP_TRY(hipFree(b->d_epochs_prb)); b->d_epochs_prb = nullptr; }
-  b->grid_stride_prb = 0;
-  return RS_OK;
+  const size_t stride = grid_stride_of(b);
+  return cqi_replace(b, RS_CQI_EPOCHS, [&](rs_batch::CqiSource& q) -> int {
+    HIP_TRY(q.epochs.alloc((size_t)b->n_cells * n_epochs * stride));
+    HIP_TRY(rs_launch_synth(q.epochs, (int64_t)stride, b->n_cells, n_epochs, b->U, b->R, rs_upad_of(b->U), seed, first_cell, cdf, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    q.grid_stride = (int64_t)stride;
+    q.n_epochs = n_epochs;
+    return RS_OK;
+  });
 }
 
 int rs_batch_download_cqi_epochs(rs_batch* b, int32_t cell, uint8_t* h_cqi) {
   if (!b || !h_cqi || cell < 0 || cell >= b->n_cells) return fail(RS_ERR_INVALID, "bad argument");
-  if (b->cqi_mode != RS_CQI_EPOCHS) return fail(RS_ERR_STATE, "no epoch grids on the device");
+  const rs_batch::CqiSource& q = b->cqi;
+  if (q.mode != RS_CQI_EPOCHS) return fail(RS_ERR_STATE, "no epoch grids on the device");
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   HIP_TRY(hipStreamSynchronize(b->stream));
-  const size_t grid = (size_t)b->U * b->R, stride = (size_t)b->grid_stride;
-  std::vector<uint8_t> tmp((size_t)b->n_epochs * stride);
-  HIP_TRY(hipMemcpy(tmp.data(), b->d_epochs + (size_t)cell * b->n_epochs * stride, tmp.size(), hipMemcpyDeviceToHost));
+  const size_t grid = (size_t)b->U * b->R, stride = (size_t)q.grid_stride;
+  std::vector<uint8_t> tmp((size_t)q.n_epochs * stride);
+  HIP_TRY(hipMemcpy(tmp.data(), q.epochs + (size_t)cell * q.n_epochs * stride, tmp.size(), hipMemcpyDeviceToHost));
   const size_t Upad = (size_t)rs_upad_of(b->U);
-  for (int e = 0; e < b->n_epochs; e++) /* back to the caller's [U][R] order */
+  for (int e = 0; e < q.n_epochs; e++) /* back to the caller's [U][R] order */
     for (size_t u = 0; u < (size_t)b->U; u++)
       for (size_t r = 0; r < (size_t)b->R; r++) h_cqi[e * grid + u * b->R + r] = tmp[e * stride + r * Upad + u];
   return RS_OK;
@@ -1668,16 +1655,15 @@ static int cqi_device_source(rs_batch* b, const uint8_t* d_cqi, size_t d_bytes, 
   return RS_OK;
 }
 
-/* the pack of n source epochs into epochs (first + j) mod n_epochs of d_epochs, enqueued; the error word is cleared ahead of the
+/* the pack of n source epochs into epochs (first + j) mod n_epochs of the grids `q`, enqueued; the error word is cleared ahead of the
  * first pack and after every report, and sticky in between */
-static int cqi_pack(rs_batch* b, const uint8_t* d_cqi, int32_t first, int32_t n, int32_t n_epochs, size_t stride) {
-  if (!b->d_cqi_bad) HIP_TRY(hipMalloc(&b->d_cqi_bad, 8));
+static int cqi_pack(rs_batch* b, const rs_batch::CqiSource& q, const uint8_t* d_cqi, int32_t first, int32_t n) {
+  if (!b->d_cqi_bad) HIP_TRY(b->d_cqi_bad.alloc(1));
   if (!b->cqi_bad_armed) {
     HIP_TRY(hipMemsetAsync(b->d_cqi_bad, 0xFF, 8, b->stream));
     b->cqi_bad_armed = true;
   }
-  HIP_TRY(rs_launch_pack_cqi(d_cqi, b->d_epochs, b->d_cqi_bad, b->n_cells, n, first, n_epochs, b->U, b->R, rs_upad_of(b->U),
-                             (int64_t)stride, b->stream));
+  HIP_TRY(rs_launch_pack_cqi(d_cqi, q.epochs, b->d_cqi_bad, b->n_cells, n, first, q.n_epochs, b->U, b->R, rs_upad_of(b->U), q.grid_stride, b->stream));
   return RS_OK;
 }
 
@@ -1686,12 +1672,12 @@ static int cqi_pack(rs_batch* b, const uint8_t* d_cqi, int32_t first, int32_t n,
 static int cqi_report(rs_batch* b, int64_t* bad_byte, int32_t* bad_value) {
   HIP_TRY(hipStreamSynchronize(b->stream));
   unsigned long long w = ~0ull;
-  if (b->d_cqi_bad && b->cqi_bad_armed) HIP_TRY(hipMemcpy(&w, b->d_cqi_bad, 8, hipMemcpyDeviceToHost));
+  if (b->d_cqi_bad && b->cqi_bad_armed) HIP_TRY(b->d_cqi_bad.download(&w));
   if (bad_byte) *bad_byte = -1;
   if (bad_value) *bad_value = 0;
   if (w == ~0ull) return RS_OK;
   HIP_TRY(hipMemsetAsync(b->d_cqi_bad, 0xFF, 8, b->stream));
-  b->cqi_mode = RS_CQI_NONE;
+  b->cqi.clear();
   if (bad_byte) *bad_byte = (int64_t)(w >> 8);
   if (bad_value) *bad_value = (int32_t)(w & 0xFF);
   return fail(RS_ERR_INVALID, "CQI %d at byte %lld outside 1..15", (int)(w & 0xFF), (long long)(w >> 8));
@@ -1700,37 +1686,32 @@ static int cqi_report(rs_batch* b, int64_t* bad_byte, int32_t* bad_value) {
 int rs_batch_set_cqi_epochs_device(rs_batch* b, const uint8_t* d_cqi, size_t d_bytes, int32_t n_epochs) {
   if (!b || !d_cqi || n_epochs < 1) return fail(RS_ERR_INVALID, "bad argument");
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  const size_t grid = (size_t)b->U * b->R;
-  const size_t stride = round_up(rs_upad_of(b->U) * b->R, 16); /* RBG-major [R][Upad]: the cell kernel's LDS image */
-  int rc = cqi_device_source(b, d_cqi, d_bytes, (size_t)b->n_cells * n_epochs * grid);
+  int rc = cqi_device_source(b, d_cqi, d_bytes, (size_t)b->n_cells * n_epochs * b->U * b->R);
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(b->stream));
-  if (b->d_epochs) { HIP_TRY(hipFree(b->d_epochs)); b->d_epochs = nullptr; }
-  b->cqi_mode = RS_CQI_NONE; /* until the pack has been seen to succeed */
-  HIP_TRY(hipMalloc(&b->d_epochs, (size_t)b->n_cells * n_epochs * stride));
-  b->grid_stride = (int64_t)stride;
-  b->n_epochs = n_epochs;
-  if (b->d_epochs_prb) { HIP_TRY(hipFree(b->d_epochs_prb)); b->d_epochs_prb = nullptr; }
-  b->grid_stride_prb = 0;
-  rc = cqi_pack(b, d_cqi, 0, n_epochs, n_epochs, stride);
-  if (rc) return rc;
-  b->cqi_mode = RS_CQI_EPOCHS;
-  return cqi_report(b, nullptr, nullptr);
+  rc = cqi_replace(b, RS_CQI_EPOCHS, [&](rs_batch::CqiSource& q) -> int {
+    HIP_TRY(q.epochs.alloc((size_t)b->n_cells * n_epochs * grid_stride_of(b)));
+    q.grid_stride = (int64_t)grid_stride_of(b);
+    q.n_epochs = n_epochs;
+    return cqi_pack(b, q, d_cqi, 0, n_epochs);
+  });
+  return rc ? rc : cqi_report(b, nullptr, nullptr); /* (a value outside 1..15: the report leaves the batch without a source) */
 }
 
 int rs_batch_write_cqi_epochs_device(rs_batch* b, int32_t first_epoch, int32_t n, const uint8_t* d_cqi, size_t d_bytes, uint32_t flags) {
   if (!b || !d_cqi) return fail(RS_ERR_INVALID, "bad argument");
   if (flags & ~RS_CQI_WRITE_ASYNC) return fail(RS_ERR_INVALID, "unknown flags 0x%x", flags);
-  if (b->cqi_mode != RS_CQI_EPOCHS || !b->d_epochs) return fail(RS_ERR_STATE, "no epoch grids on the device");
-  if (b->d_epochs_prb) return fail(RS_ERR_STATE, "the batch has a per-PRB twin of its grids, which a write would leave behind");
-  if (n < 1 || n > b->n_epochs) return fail(RS_ERR_INVALID, "n %d outside 1..%d", n, b->n_epochs);
-  if (first_epoch < 0 || first_epoch >= b->n_epochs) return fail(RS_ERR_INVALID, "first_epoch %d outside 0..%d", first_epoch, b->n_epochs - 1);
-  if (!b->cfg.cqi_epoch_wrap && first_epoch + n > b->n_epochs)
-    return fail(RS_ERR_RANGE, "epochs %d..%d run past the last epoch %d (no cqi_epoch_wrap)", first_epoch, first_epoch + n - 1, b->n_epochs - 1);
+  const rs_batch::CqiSource& q = b->cqi;
+  if (q.mode != RS_CQI_EPOCHS) return fail(RS_ERR_STATE, "no epoch grids on the device");
+  if (q.epochs_prb) return fail(RS_ERR_STATE, "the batch has a per-PRB twin of its grids, which a write would leave behind");
+  if (n < 1 || n > q.n_epochs) return fail(RS_ERR_INVALID, "n %d outside 1..%d", n, q.n_epochs);
+  if (first_epoch < 0 || first_epoch >= q.n_epochs) return fail(RS_ERR_INVALID, "first_epoch %d outside 0..%d", first_epoch, q.n_epochs - 1);
+  if (!b->cfg.cqi_epoch_wrap && first_epoch + n > q.n_epochs)
+    return fail(RS_ERR_RANGE, "epochs %d..%d run past the last epoch %d (no cqi_epoch_wrap)", first_epoch, first_epoch + n - 1, q.n_epochs - 1);
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   int rc = cqi_device_source(b, d_cqi, d_bytes, (size_t)b->n_cells * n * b->U * b->R);
   if (rc) return rc;
-  rc = cqi_pack(b, d_cqi, first_epoch, n, b->n_epochs, (size_t)b->grid_stride);
+  rc = cqi_pack(b, q, d_cqi, first_epoch, n);
   if (rc || (flags & RS_CQI_WRITE_ASYNC)) return rc;
   return cqi_report(b, nullptr, nullptr);
 }
@@ -1743,17 +1724,19 @@ int rs_batch_cqi_write_status(rs_batch* b, int64_t* bad_byte, int32_t* bad_value
 
 int rs_batch_debug_cqi_image(rs_batch* b, int32_t cell, int32_t epoch, uint8_t* h_image, size_t bytes) {
   if (!b || !h_image || cell < 0 || cell >= b->n_cells) return fail(RS_ERR_INVALID, "bad argument");
-  if (b->cqi_mode != RS_CQI_EPOCHS) return fail(RS_ERR_STATE, "no epoch grids on the device");
-  if (epoch < 0 || epoch >= b->n_epochs) return fail(RS_ERR_INVALID, "epoch %d outside 0..%d", epoch, b->n_epochs - 1);
-  if (bytes != (size_t)b->grid_stride) return fail(RS_ERR_INVALID, "bytes is %zu, a grid's image has %lld", bytes, (long long)b->grid_stride);
+  const rs_batch::CqiSource& q = b->cqi;
+  if (q.mode != RS_CQI_EPOCHS) return fail(RS_ERR_STATE, "no epoch grids on the device");
+  if (epoch < 0 || epoch >= q.n_epochs) return fail(RS_ERR_INVALID, "epoch %d outside 0..%d", epoch, q.n_epochs - 1);
+  if (bytes != (size_t)q.grid_stride) return fail(RS_ERR_INVALID, "bytes is %zu, a grid's image has %lld", bytes, (long long)q.grid_stride);
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   HIP_TRY(hipStreamSynchronize(b->stream));
-  HIP_TRY(hipMemcpy(h_image, b->d_epochs + ((size_t)cell * b->n_epochs + epoch) * bytes, bytes, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h_image, q.epochs + ((size_t)cell * q.n_epochs + epoch) * bytes, bytes, hipMemcpyDeviceToHost));
   return RS_OK;
 }
 
-int rs_batch_set_trace(rs_batch* b, const uint8_t* h_trace, int32_t n_traces, int32_t n_rows, int32_t row_modulus,
-                       const int32_t* h_user_trace) {
+/* trace tables from host memory [n_traces][n_rows][R] with every user's trace id, and -- h_trace_prb -- their per-PRB twin */
+static int upload_trace(rs_batch* b, const uint8_t* h_trace, int32_t n_traces, int32_t n_rows, int32_t row_modulus, const int32_t* h_user_trace,
+                        const uint8_t* h_trace_prb) {
   if (!b || !h_trace || !h_user_trace || n_traces < 1 || n_rows < 1 || row_modulus < 1)
     return fail(RS_ERR_INVALID, "bad argument");
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
@@ -1763,16 +1746,18 @@ int rs_batch_set_trace(rs_batch* b, const uint8_t* h_trace, int32_t n_traces, in
   const size_t nu = (size_t)b->n_cells * b->U;
   for (size_t i = 0; i < nu; i++)
     if (h_user_trace[i] < 0 || h_user_trace[i] >= n_traces) return fail(RS_ERR_INVALID, "trace id %d out of range", h_user_trace[i]);
-  if (b->d_trace) { HIP_TRY(hipFree(b->d_trace)); b->d_trace = nullptr; }
-  if (b->d_user_trace) { HIP_TRY(hipFree(b->d_user_trace)); b->d_user_trace = nullptr; }
-  HIP_TRY(hipMalloc(&b->d_trace, tb));
-  HIP_TRY(hipMemcpy(b->d_trace, h_trace, tb, hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&b->d_user_trace, 4 * nu));
-  HIP_TRY(hipMemcpy(b->d_user_trace, h_user_trace, 4 * nu, hipMemcpyHostToDevice));
-  b->n_traces = n_traces; b->n_rows = n_rows; b->row_mod = row_modulus;
-  b->cqi_mode = RS_CQI_TRACE;
-  if (b->d_trace_prb) { HIP_TRY(hipFree(b->d_trace_prb)); b->d_trace_prb = nullptr; }
-  return RS_OK;
+  return cqi_replace(b, RS_CQI_TRACE, [&](rs_batch::CqiSource& q) -> int {
+    HIP_TRY(q.trace.assign(h_trace, tb));
+    HIP_TRY(q.user_trace.assign(h_user_trace, nu));
+    q.n_traces = n_traces; q.n_rows = n_rows; q.row_mod = row_modulus;
+    if (h_trace_prb) HIP_TRY(q.trace_prb.assign(h_trace_prb, tb * b->G));
+    return RS_OK;
+  });
+}
+
+int rs_batch_set_trace(rs_batch* b, const uint8_t* h_trace, int32_t n_traces, int32_t n_rows, int32_t row_modulus,
+                       const int32_t* h_user_trace) {
+  return upload_trace(b, h_trace, n_traces, n_rows, row_modulus, h_user_trace, nullptr);
 }
 
 int rs_batch_set_trace_prb(rs_batch* b, const uint8_t* h_trace_prb, int32_t n_traces, int32_t n_rows, int32_t row_modulus,
@@ -1784,11 +1769,7 @@ int rs_batch_set_trace_prb(rs_batch* b, const uint8_t* h_trace_prb, int32_t n_tr
   std::vector<uint8_t> rbg(rows * b->R);
   for (size_t q = 0; q < rows; q++)
     for (size_t r = 0; r < (size_t)b->R; r++) rbg[q * b->R + r] = h_trace_prb[q * per_row + r * b->G];
-  int rc = rs_batch_set_trace(b, rbg.data(), n_traces, n_rows, row_modulus, h_user_trace);
-  if (rc) return rc;
-  HIP_TRY(hipMalloc(&b->d_trace_prb, rows * per_row));
-  HIP_TRY(hipMemcpy(b->d_trace_prb, h_trace_prb, rows * per_row, hipMemcpyHostToDevice));
-  return RS_OK;
+  return upload_trace(b, rbg.data(), n_traces, n_rows, row_modulus, h_user_trace, h_trace_prb);
 }
 
 int rs_batch_run_async(rs_batch* b, int32_t n_ttis) {
@@ -1884,25 +1865,23 @@ static int run_with_records(rs_batch* b, int n_ttis, int64_t cap, int bound, siz
   const size_t cells = (size_t)b->n_cells;
   const int64_t cap_dev = out->cap_dev = std::min(cap, (int64_t)n_ttis * bound);
   const size_t list_bytes = cells * (size_t)cap_dev * rec_size, need = list_bytes + 4 * cells;
-  if (need > b->recs_bytes) {
+  if (need > b->d_recs.bytes()) {
     HIP_TRY(hipStreamSynchronize(b->stream));
-    if (b->d_recs) { HIP_TRY(hipFree(b->d_recs)); b->d_recs = nullptr; b->recs_bytes = 0; }
+    b->d_recs.release(); /* (the old block first: the two together may be more than the device has) */
     /* RS_RECORDS_MAX_BYTES: the largest device block a call may ask for (unset: what the device gives).  A block above it is a failed
      * allocation, by the very path of one: it is how the tests reach this refusal without asking a card for memory it does not have. */
     const char* const e_max = getenv("RS_RECORDS_MAX_BYTES");
     const bool too_large = e_max && (unsigned long long)need > strtoull(e_max, nullptr, 10);
-    if (too_large || hipMalloc(&b->d_recs, need) != hipSuccess) {
+    if (too_large || b->d_recs.alloc(need) != hipSuccess) {
       if (!too_large) (void)hipGetLastError();
-      b->d_recs = nullptr;
       return fail(RS_ERR_HIP, "%s: no device block of %zu bytes (%zu cells x %lld records)", what, need, cells, (long long)cap_dev);
     }
-    b->recs_bytes = need;
   }
-  uint32_t* const d_count = (uint32_t*)((char*)b->d_recs + list_bytes);
+  uint32_t* const d_count = (uint32_t*)(b->d_recs + list_bytes);
   HIP_TRY(hipMemsetAsync(d_count, 0, 4 * cells, b->stream));
   out->t0 = std::chrono::steady_clock::now();
   LaunchReq rq(n_ttis);
-  rq.recs = b->d_recs;
+  rq.recs = b->d_recs.get();
   rq.rec_cap = cap_dev;
   int rc = launch(b, rq);
   if (rc) return rc;
@@ -1916,7 +1895,7 @@ static int run_with_records(rs_batch* b, int n_ttis, int64_t cap, int bound, siz
     n_recs[c] = (int64_t)out->count[c];
     if (n_recs[c] > cap_dev && out->over < 0) out->over = (int64_t)c; /* (cap_dev < cap only where nothing can exceed it) */
     if (out->used(c))
-      HIP_TRY(hipMemcpyAsync((char*)recs + c * (size_t)cap * rec_size, (const char*)b->d_recs + c * (size_t)cap_dev * rec_size, out->used(c) * rec_size,
+      HIP_TRY(hipMemcpyAsync((char*)recs + c * (size_t)cap * rec_size, b->d_recs + c * (size_t)cap_dev * rec_size, out->used(c) * rec_size,
                              hipMemcpyDeviceToHost, b->stream));
   }
   HIP_TRY(hipStreamSynchronize(b->stream));
@@ -2047,11 +2026,10 @@ int rs_batch_read_state(rs_batch* b, double* avg, int64_t* cum_bytes, int64_t* c
   if (!b) return fail(RS_ERR_INVALID, "null batch");
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   HIP_TRY(hipStreamSynchronize(b->stream));
-  const size_t n = (size_t)b->n_cells * b->U;
-  if (avg) HIP_TRY(hipMemcpy(avg, b->d_avg, 8 * n, hipMemcpyDeviceToHost));
-  if (cum_bytes) HIP_TRY(hipMemcpy(cum_bytes, b->d_cumb, 8 * n, hipMemcpyDeviceToHost));
-  if (cum_rbs) HIP_TRY(hipMemcpy(cum_rbs, b->d_cumr, 8 * n, hipMemcpyDeviceToHost));
-  if (slice_state) HIP_TRY(hipMemcpy(slice_state, b->d_sstate, 8 * (size_t)b->n_cells * b->S, hipMemcpyDeviceToHost));
+  if (avg) HIP_TRY(b->d_avg.download(avg));
+  if (cum_bytes) HIP_TRY(b->d_cumb.download(cum_bytes));
+  if (cum_rbs) HIP_TRY(b->d_cumr.download(cum_rbs));
+  if (slice_state) HIP_TRY(b->d_sstate.download(slice_state));
   return RS_OK;
 }
 
@@ -2094,17 +2072,16 @@ int rs_batch_write_state(rs_batch* b, const double* avg, const double* slice_sta
   if (!b) return fail(RS_ERR_INVALID, "null batch");
   if (b->direct) return fail(RS_ERR_INVALID, "drop-in contexts take the averages per call");
   if (b->queues) return fail(RS_ERR_STATE, "the queue model keeps one average per bearer: not settable through this call");
-  const size_t n = (size_t)b->n_cells * b->U;
   if (avg)
-    for (size_t i = 0; i < n; i++)
+    for (size_t i = 0; i < b->d_avg.count(); i++)
       if (!(avg[i] >= 1.0) || !(avg[i] <= 1e300)) return fail(RS_ERR_INVALID, "avg_rate[%zu] = %g: the EWMA keeps averages at or above 1 (radio-bearer.cpp:160-162)", i, avg[i]);
   if (slice_state)
     for (int c = 0; c < b->n_cells; c++)
       if (const int rc = check_slice_state(b, slice_state + (size_t)c * b->S, (size_t)c)) return rc;
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   HIP_TRY(hipStreamSynchronize(b->stream));
-  if (avg) HIP_TRY(hipMemcpy(b->d_avg, avg, 8 * n, hipMemcpyHostToDevice));
-  if (slice_state) HIP_TRY(hipMemcpy(b->d_sstate, slice_state, 8 * (size_t)b->n_cells * b->S, hipMemcpyHostToDevice));
+  if (avg) HIP_TRY(b->d_avg.upload(avg));
+  if (slice_state) HIP_TRY(b->d_sstate.upload(slice_state));
   return RS_OK;
 }
 
@@ -2132,10 +2109,7 @@ int rs_batch_set_bearers(rs_batch* b, const uint8_t* bearer_kind) {
   int qmode = 2;
   {
     const RsCarve lds_c = rs_carve(b->S, b->U, b->R, b->sched, b->threads, 2), hbm_c = rs_carve(b->S, b->U, b->R, b->sched, b->threads, 3);
-    hipDeviceProp_t prop;
-    int cus = 256;
-    if (hipGetDeviceProperties(&prop, b->cfg.cell.device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-    const bool halves = lds_c.q_lds && lds_c.lds_bytes > 80 * 1024 && hbm_c.lds_bytes <= 80 * 1024 && b->n_cells > cus;
+    const bool halves = lds_c.q_lds && lds_c.lds_bytes > 80 * 1024 && hbm_c.lds_bytes <= 80 * 1024 && b->n_cells > device_cus(b->cfg.cell.device);
     if (b->cfg.queue_state_lds < 0 || (b->cfg.queue_state_lds == 0 && halves)) qmode = 3;
     const RsCarve qc = qmode == 2 ? lds_c : hbm_c;
     if (qc.lds_bytes > 160 * 1024) return fail(RS_ERR_INVALID, "cell needs %d B of LDS with the queue model (> 160 KiB)", qc.lds_bytes);
@@ -2149,22 +2123,18 @@ int rs_batch_set_bearers(rs_batch* b, const uint8_t* bearer_kind) {
     if (!qjit && !qmsg[0]) snprintf(qmsg, sizeof qmsg, "hiprtc build of the queue-model kernel failed");
     if (!qjit && b->threads > 512) return fail(RS_ERR_INVALID, "threads_per_cell %d needs the shape-specialised queue-model kernel: %s", b->threads, qmsg);
   }
-  const size_t n = (size_t)b->n_cells * 2 * U;
-  if (!b->d_bearer_kind) {
-    HIP_TRY(hipMalloc(&b->d_bearer_kind, 2 * U));
-    HIP_TRY(hipMalloc(&b->d_qi, 4 * 7 * n));
-    HIP_TRY(hipMalloc(&b->d_bavg, 8 * n));
-    HIP_TRY(hipMalloc(&b->d_bcum, 8 * 2 * n));
-    HIP_TRY(hipMalloc(&b->d_qflags, (size_t)b->n_cells * U));
-    HIP_TRY(hipMalloc(&b->d_qhol, 8 * (size_t)b->n_cells * U));
-  }
-  HIP_TRY(hipMemcpy(b->d_bearer_kind, bearer_kind, 2 * U, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(b->d_qi, 0, 4 * 7 * n));
-  HIP_TRY(hipMemset(b->d_bcum, 0, 8 * 2 * n));
-  HIP_TRY(hipMemset(b->d_qflags, 0, (size_t)b->n_cells * U));
-  HIP_TRY(hipMemset(b->d_qhol, 0, 8 * (size_t)b->n_cells * U));
-  std::vector<double> avg(n, 100000.0); /* radio-bearer.cpp:54 */
-  HIP_TRY(hipMemcpy(b->d_bavg, avg.data(), 8 * n, hipMemcpyHostToDevice));
+  /* the six queue arrays, all or none (still before the batch changes); a later call writes into them.  nu: one [cells][U] array of
+   * per-user words, n: one [cells][2][U] array of per-bearer words */
+  const size_t nu = (size_t)b->n_cells * U, n = 2 * nu;
+  if (!b->d_bearer_kind)
+    HIP_TRY(dev_alloc_all(b->d_bearer_kind, 2 * U, b->d_qi, 7 * n, b->d_bavg, n, b->d_bcum, 2 * n, b->d_qflags, nu, b->d_qhol, nu));
+  HIP_TRY(b->d_bearer_kind.upload(bearer_kind));
+  HIP_TRY(b->d_qi.zero());
+  HIP_TRY(b->d_bcum.zero());
+  HIP_TRY(b->d_qflags.zero());
+  HIP_TRY(b->d_qhol.zero());
+  const std::vector<double> avg(n, 100000.0); /* radio-bearer.cpp:54 */
+  HIP_TRY(b->d_bavg.upload(avg.data()));
   /* commit: mode, carve and kernel together (the queue = 0 kernel must never run with queue arguments) */
   b->queues = true;
   b->qmode = qmode;
@@ -2191,31 +2161,22 @@ int rs_batch_set_arrivals(rs_batch* b, const int64_t* offsets, const double* tim
   }
   const size_t total = (size_t)offsets[nb];
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
-  void* old[] = {b->d_arr_off, b->d_arr_time, b->d_arr_nfull, b->d_arr_last, b->d_flow_tti, b->d_flow_time};
-  for (void* q : old)
-    if (q) HIP_TRY(hipFree(q));
-  b->d_arr_off = nullptr; b->d_arr_time = nullptr; b->d_arr_nfull = nullptr; b->d_arr_last = nullptr;
-  b->d_flow_tti = nullptr; b->d_flow_time = nullptr; b->n_bursts = 0;
-  HIP_TRY(hipMalloc(&b->d_arr_off, 8 * (nb + 1)));
-  HIP_TRY(hipMalloc(&b->d_arr_time, 8 * (total ? total : 1)));
-  HIP_TRY(hipMalloc(&b->d_arr_nfull, 4 * (total ? total : 1)));
-  HIP_TRY(hipMalloc(&b->d_arr_last, 4 * (total ? total : 1)));
-  HIP_TRY(hipMemcpy(b->d_arr_off, offsets, 8 * (nb + 1), hipMemcpyHostToDevice));
-  if (total) {
-    HIP_TRY(hipMemcpy(b->d_arr_time, time, 8 * total, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b->d_arr_nfull, n_full, 4 * total, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b->d_arr_last, last_bytes, 4 * total, hipMemcpyHostToDevice));
-  }
-  /* the flow completion record: -1 = not completed */
-  HIP_TRY(hipMalloc(&b->d_flow_tti, 4 * (total ? total : 1)));
-  HIP_TRY(hipMalloc(&b->d_flow_time, 8 * (total ? total : 1)));
-  b->n_bursts = total;
-  if (total) {
-    const std::vector<int32_t> none_tti(total, -1);
-    const std::vector<double> none_time(total, -1.0);
-    HIP_TRY(hipMemcpy(b->d_flow_tti, none_tti.data(), 4 * total, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b->d_flow_time, none_time.data(), 8 * total, hipMemcpyHostToDevice));
-  }
+  /* the four lists and the flow completion record (-1 = not completed; its length is the burst count): built and filled beside the
+   * batch's present ones, which stay in place if anything fails, then committed together.  (A list of no bursts: blocks of one byte.) */
+  DevBuf<int64_t> off;
+  DevBuf<double> at, flow_time;
+  DevBuf<int32_t> nfull, last, flow_tti;
+  HIP_TRY(dev_alloc_all(off, nb + 1, at, total, nfull, total, last, total, flow_tti, total, flow_time, total));
+  const std::vector<int32_t> none_tti(total, -1);
+  const std::vector<double> none_time(total, -1.0);
+  HIP_TRY(off.upload(offsets));
+  HIP_TRY(at.upload(time));
+  HIP_TRY(nfull.upload(n_full));
+  HIP_TRY(last.upload(last_bytes));
+  HIP_TRY(flow_tti.upload(none_tti.data()));
+  HIP_TRY(flow_time.upload(none_time.data()));
+  b->d_arr_off = std::move(off); b->d_arr_time = std::move(at); b->d_arr_nfull = std::move(nfull); b->d_arr_last = std::move(last);
+  b->d_flow_tti = std::move(flow_tti); b->d_flow_time = std::move(flow_time);
   return RS_OK;
 }
 
@@ -2224,8 +2185,8 @@ int rs_batch_flow_record(rs_batch* b, int32_t* done_tti, double* done_time) {
   if (!b->queues || !b->d_flow_tti) return fail(RS_ERR_STATE, "no flow completion record: the batch has no arrivals (rs_batch_set_bearers / rs_batch_set_arrivals)");
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   HIP_TRY(hipStreamSynchronize(b->stream));
-  if (done_tti && b->n_bursts) HIP_TRY(hipMemcpy(done_tti, b->d_flow_tti, 4 * b->n_bursts, hipMemcpyDeviceToHost));
-  if (done_time && b->n_bursts) HIP_TRY(hipMemcpy(done_time, b->d_flow_time, 8 * b->n_bursts, hipMemcpyDeviceToHost));
+  if (done_tti) HIP_TRY(b->d_flow_tti.download(done_tti));
+  if (done_time) HIP_TRY(b->d_flow_time.download(done_time));
   return RS_OK;
 }
 
@@ -2235,7 +2196,7 @@ int rs_batch_read_bearer_state(rs_batch* b, double* avg, int64_t* cum_bytes, int
   if (!b->queues) return fail(RS_ERR_STATE, "the batch has no bearers (rs_batch_set_bearers)");
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   HIP_TRY(hipStreamSynchronize(b->stream));
-  const size_t U = b->U, n = (size_t)b->n_cells * 2 * U;
+  const size_t U = b->U, n = b->d_bavg.count();
   /* device layout [cells][2][U] -> [cells][U][2] */
   auto gather = [&](auto* dst, const auto* src_dev, auto zero) -> int {
     std::vector<decltype(zero)> tmp(n);
@@ -2246,11 +2207,11 @@ int rs_batch_read_bearer_state(rs_batch* b, double* avg, int64_t* cum_bytes, int
     return RS_OK;
   };
   int rc = RS_OK;
-  if (avg && !rc) rc = gather(avg, b->d_bavg, 0.0);
-  if (cum_bytes && !rc) rc = gather(cum_bytes, b->d_bcum, (int64_t)0);
-  if (cum_rbs && !rc) rc = gather(cum_rbs, b->d_bcum + n, (int64_t)0);
-  if (queue_bytes && !rc) rc = gather(queue_bytes, b->d_qi + 4 * n, (int32_t)0);
-  if (queue_packets && !rc) rc = gather(queue_packets, b->d_qi + 5 * n, (int32_t)0);
+  if (avg && !rc) rc = gather(avg, b->d_bavg.get(), 0.0);
+  if (cum_bytes && !rc) rc = gather(cum_bytes, plane(b, b->d_bcum, 0), (int64_t)0);
+  if (cum_rbs && !rc) rc = gather(cum_rbs, plane(b, b->d_bcum, 1), (int64_t)0);
+  if (queue_bytes && !rc) rc = gather(queue_bytes, plane(b, b->d_qi, 4), (int32_t)0);
+  if (queue_packets && !rc) rc = gather(queue_packets, plane(b, b->d_qi, 5), (int32_t)0);
   return rc;
 }
 
@@ -2303,8 +2264,8 @@ int rs_batch_read_clock(rs_batch* b, double* t, double* last_update) {
   if (!b) return fail(RS_ERR_INVALID, "null batch");
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   HIP_TRY(hipStreamSynchronize(b->stream));
-  std::vector<RsCellScalars> sc(b->n_cells);
-  HIP_TRY(hipMemcpy(sc.data(), b->d_scal, sizeof(RsCellScalars) * b->n_cells, hipMemcpyDeviceToHost));
+  std::vector<RsCellScalars> sc;
+  if (const int rc = read_scalars(b, &sc)) return rc;
   for (int c = 0; c < b->n_cells; c++) {
     if (t) t[c] = sc[c].t;
     if (last_update) last_update[c] = sc[c].last_update;
@@ -2316,8 +2277,8 @@ int rs_batch_debug_heap_sorts(rs_batch* b, int64_t* out) {
   if (!b || !out) return fail(RS_ERR_INVALID, "null argument");
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   HIP_TRY(hipStreamSynchronize(b->stream));
-  std::vector<RsCellScalars> sc(b->n_cells);
-  HIP_TRY(hipMemcpy(sc.data(), b->d_scal, sizeof(RsCellScalars) * b->n_cells, hipMemcpyDeviceToHost));
+  std::vector<RsCellScalars> sc;
+  if (const int rc = read_scalars(b, &sc)) return rc;
   for (int c = 0; c < b->n_cells; c++)
     for (int k = 0; k < 3; k++) out[c * 3 + k] = sc[c].heap_sorts[k];
   return RS_OK;
@@ -2438,8 +2399,8 @@ int rs_batch_debug_clocks(rs_batch* b, double* shader_mhz, double* kernel_ms) {
   if (!b) return fail(RS_ERR_INVALID, "null batch");
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   HIP_TRY(hipStreamSynchronize(b->stream));
-  std::vector<RsCellScalars> sc(b->n_cells);
-  HIP_TRY(hipMemcpy(sc.data(), b->d_scal, sizeof(RsCellScalars) * b->n_cells, hipMemcpyDeviceToHost));
+  std::vector<RsCellScalars> sc;
+  if (const int rc = read_scalars(b, &sc)) return rc;
   for (int c = 0; c < b->n_cells; c++) {
     const double real = (double)(sc[c].real_end - sc[c].real_begin), clk = (double)(sc[c].clk_end - sc[c].clk_begin);
     if (shader_mhz) shader_mhz[c] = real > 0 ? clk / real * 100.0 : 0.0; /* s_memrealtime ticks at 100 MHz */
@@ -2456,7 +2417,7 @@ int rs_batch_autotune_report(rs_batch* b, char* msg, size_t msglen) {
 
 int rs_batch_prepare_launch(rs_batch* b, int32_t n_ttis) {
   if (!b || n_ttis < 1) return fail(RS_ERR_INVALID, "bad argument");
-  if (b->cqi_mode == RS_CQI_NONE) return fail(RS_ERR_STATE, "no CQI source set");
+  if (b->cqi.mode == RS_CQI_NONE) return fail(RS_ERR_STATE, "no CQI source set");
   HIP_TRY(hipSetDevice(b->cfg.cell.device));
   (void)lean_kernel(b, n_ttis > RS_MAX_TTIS_PER_LAUNCH ? RS_MAX_TTIS_PER_LAUNCH : n_ttis, false);
   if (!b->builds.checked) {
@@ -2489,7 +2450,7 @@ int rs_batch_slice_bytes_device(rs_batch* b, uint64_t* d_out) {
 
 int rs_batch_slice_bytes(rs_batch* b, uint64_t* h_out) {
   if (!b || !h_out) return fail(RS_ERR_INVALID, "null argument");
-  int rc = rs_batch_slice_bytes_device(b, (uint64_t*)b->d_slice_bytes);
+  int rc = rs_batch_slice_bytes_device(b, b->d_slice_bytes);
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(b->stream));
   HIP_TRY(hipMemcpy(h_out, b->d_slice_bytes, 8 * b->S, hipMemcpyDeviceToHost));
